@@ -26,7 +26,10 @@
            touches the GPU) and relays rank 0's line; --transport multi drives the N devices from this one process
            through the C ABI's lsqr_multi_* entry points (peer copies instead of RCCL).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--points P] [--batch H] [--workload plane]
+  outputs  --dump-outputs DIR writes what the last timed step of each rate returned (final fit, winner record) as .npy
+           files: inputs and hypothesis stream are seeded, so two builds run with the same arguments compare exactly.
+
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--points P] [--batch H] [--workload plane] [--dump-outputs DIR]
 """
 import argparse
 import json
@@ -127,7 +130,14 @@ def parse(argv=None):
                     help="--gpus N > 1: if RCCL cannot come up on ANY rank, continue over gloo (labelled in "
                          "config.collectives) instead of exiting non-zero.  Never the default: a scaling line must not "
                          "be a gloo line by accident")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", default=None, type=os.path.abspath, metavar="DIR",
+                    help="after the timed steps, write what the last timed step of each rate returned to its caller "
+                         "(final fit, winner record) as DIR/<rate>_params.npy and DIR/<rate>_winner.npy (float64), so "
+                         "that two builds can be compared output for output on the same seeded inputs")
+    a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 def make_data(workload, n, outliers):
@@ -645,8 +655,8 @@ class Run:
         if r is None or r["info"].best_votes == 0:
             return None
         f = r["info"].fit
-        return {"votes": int(r["info"].best_votes), "fit": r["params"], "cnt": int(f.n_used),
-                "lm_info": int(f.lm_info), "lm_nfev": int(f.lm_nfev), "cost": float(f.cost),
+        return {"votes": int(r["info"].best_votes), "index": int(r["info"].best_index), "fit": r["params"],
+                "cnt": int(f.n_used), "lm_info": int(f.lm_info), "lm_nfev": int(f.lm_nfev), "cost": float(f.cost),
                 "lm_stall": int(f.reserved)}
 
     @staticmethod
@@ -654,7 +664,7 @@ class Run:
         if r is None:
             return None
         votes, gidx, par, fit, cnt, info = r
-        return {"votes": int(votes), "fit": fit, "cnt": int(cnt),
+        return {"votes": int(votes), "index": int(gidx), "fit": fit, "cnt": int(cnt),
                 "lm_info": int(getattr(info, "lm_info", 0) or 0), "lm_nfev": int(getattr(info, "lm_nfev", 0) or 0),
                 "cost": float(getattr(info, "cost", 0.0) or 0.0), "lm_stall": int(getattr(info, "reserved", 0) or 0)}
 
@@ -1076,6 +1086,19 @@ def rates_for(a):
     return [("early_exit", 1), ("full_count", 0)]
 
 
+def dump_outputs(path, lasts):
+    """--dump-outputs: lasts = [(rate, result of the rate's last timed step as Run._res / _res_step give it)].  Per rate,
+    <rate>_params.npy holds the final fit's parameters (empty when the fit failed) and <rate>_winner.npy the winner
+    record [votes, index, inliers, lm_info, lm_nfev, cost] (zeros when no hypothesis got a vote)."""
+    os.makedirs(path, exist_ok=True)
+    for mode, last in lasts:
+        params = np.asarray(last["fit"] if last else [], dtype=np.float64)
+        winner = np.array([last["votes"], last["index"], last["cnt"], last["lm_info"], last["lm_nfev"], last["cost"]]
+                          if last else np.zeros(6), dtype=np.float64)
+        np.save(os.path.join(path, mode + "_params.npy"), params)
+        np.save(os.path.join(path, mode + "_winner.npy"), winner)
+
+
 def run_workload(a, dist, device, local, backend, force_dist, cpu_budget, headline=True):
     R = Run(a, dist, device, local, backend, force_dist)
     try:
@@ -1083,6 +1106,8 @@ def run_workload(a, dist, device, local, backend, force_dist, cpu_budget, headli
         for mode, bound in rates_for(a):
             rates.append(R.measure(mode, bound))
         rates.sort(key=lambda r: r["mode"] != "full_count")   # (stable: full_count, the unit of `value`, first)
+        if a.dump_outputs and R.comm.rank == 0:
+            dump_outputs(a.dump_outputs, [(r["mode"], r["last"]) for r in rates])
         return report(R, rates, cpu_budget, headline) if R.comm.rank == 0 else None
     finally:
         R.close()
@@ -1291,6 +1316,8 @@ def launch_ranks(a):
     touched the GPU and never will), relay rank 0's JSON line, exit non-zero if any rank failed"""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=%d" % a.gpus,
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()), os.path.abspath(__file__)] + sys.argv[1:]
+    if a.dump_outputs:      # the ranks run in ROOT: hand them the directory resolved here
+        cmd += ["--dump-outputs", a.dump_outputs]
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     env.setdefault("OMP_NUM_THREADS", "4")
@@ -1325,6 +1352,7 @@ def run_multi(a):
     with MultiContext(devs) as mc:
         mc.set_model(model, 64 if w == "dense" else 3, DELTA[w], ls_type).upload(data)
         out_rates = {}
+        lasts = []
         last = None
         step = 0
         for mode, bound in rates_for(a):
@@ -1340,6 +1368,9 @@ def run_multi(a):
                     step += 1
                 vals.append(H * a.gpus * a.steps / (time.perf_counter() - t0))
             out_rates[mode] = vals
+            lasts.append((mode, Run._res(last)))
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, lasts)
     first = "full_count" if "full_count" in out_rates else rates_for(a)[0][0]   # (`value` counts everything when measured)
     value = float(np.median(out_rates[first]))
     f = last["info"].fit

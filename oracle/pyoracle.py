@@ -219,16 +219,25 @@ def ctr_subsets(seed, first, count, n, k):
     return out
 
 
+def _params(prefill):
+    """the caller's parameter vector as the run receives it (prefill: what it held before the call)"""
+    params = np.zeros(80)
+    nparams = C.c_int(0)
+    if prefill is not None:
+        params[:len(prefill)] = prefill
+        nparams = C.c_int(len(prefill))
+    return params, nparams
+
+
 def ransac(c, data, p, sampler="ref", seed=1, subsets=None, first=0, full_scan=False,
-           trace_cap=4096):
+           trace_cap=4096, prefill=None):
     """Run the restated RANSAC.hxx.  sampler: 'ref' (rand() formula fed by the LCG seeded with
     `seed`), 'list' (explicit subsets, draw order), 'ctr' (product's counter sampler)."""
     L = lib()
     a = as_records(c, data)
     n = a.shape[0]
     k = L.orc_min_subset(C.byref(c))
-    params = np.zeros(80)
-    nparams = C.c_int(0)
+    params, nparams = _params(prefill)
     cons = np.zeros(max(n, 1), dtype=np.uint8)
     votes = np.zeros(trace_cap, dtype=np.uint32)
     status = np.zeros(trace_cap, dtype=np.uint8)
@@ -265,12 +274,11 @@ def ransac(c, data, p, sampler="ref", seed=1, subsets=None, first=0, full_scan=F
                 subsets=subs[:it].copy(), best_iter=tr.best_iter, best_votes=tr.best_votes)
 
 
-def ransac_exhaustive(c, data):
+def ransac_exhaustive(c, data, prefill=None):
     L = lib()
     a = as_records(c, data)
     n = a.shape[0]
-    params = np.zeros(80)
-    nparams = C.c_int(0)
+    params, nparams = _params(prefill)
     cons = np.zeros(max(n, 1), dtype=np.uint8)
     frac = L.orc_ransac_exhaustive(C.byref(c), _d(a), n, a.shape[1], _d(params),
                                    C.byref(nparams), cons.ctypes.data)
@@ -283,11 +291,7 @@ def ref_ransac(c, data, p, seed=1, exhaustive=False, prefill=None, subsets_cap=0
     a = as_records(c, data)
     n = a.shape[0]
     k = lib().orc_min_subset(C.byref(c))
-    params = np.zeros(80)
-    nparams = C.c_int(0)
-    if prefill is not None:
-        params[:len(prefill)] = prefill
-        nparams = C.c_int(len(prefill))
+    params, nparams = _params(prefill)
     cons = np.zeros(max(n, 1), dtype=np.uint8)
     st = (C.c_uint64 * 4)()
     subs = np.zeros((max(subsets_cap, 1), k), dtype=np.uint32)

@@ -11,6 +11,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 rank, world, port, allow, mode = int(sys.argv[1]), int(sys.argv[2]), sys.argv[3], sys.argv[4] == "1", sys.argv[5]
 os.environ.update({"MASTER_ADDR": "127.0.0.1", "MASTER_PORT": port, "RANK": str(rank), "WORLD_SIZE": str(world)})
+# the case under test is a host without a usable device: on a GPU host the ranks are shown none, so that RCCL fails the
+# same way there (two ranks on one visible card would fail differently, or -- in mode "some" -- not at all)
+os.environ.update({"HIP_VISIBLE_DEVICES": "-1", "CUDA_VISIBLE_DEVICES": "-1"})
 import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 import bench  # noqa: E402

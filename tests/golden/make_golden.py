@@ -11,6 +11,8 @@ Outputs (all data, no reference source text):
                             seeded data and seeded rand() streams
   config1_ref_vectors.npz   BASELINE configs[0] as written (plane, 10 k points, 30 % outliers, p = 0.999) run by the
                             REFERENCE RANSAC.hxx: subsets drawn, fraction, consensus set, parameters, call counts
+  live_ref_vectors.npz      the REFERENCE RANSAC.hxx on the inputs of tests/test_oracle_ransac.py's live comparisons
+                            (seeded plane / sphere / line runs; invalid input with prefilled parameters)
   numerics_vectors.npz      NumPy/SciPy results (eigh, svd, lstsq, MINPACK lmder through
                             scipy.optimize.leastsq) on seeded inputs
   us_lm_vectors.npz         SciPy MINPACK on the US calibration at the reference's 1e-15 tolerances, 1 k / 20 k /
@@ -91,6 +93,46 @@ def config1_vectors():
         out[key + "counts"] = np.array([r["estimate_calls"], r["agree_calls"], r["ls_calls"], r["rand_calls"]],
                                        dtype=np.int64)
     np.savez_compressed(os.path.join(HERE, "config1_ref_vectors.npz"), **out)
+
+
+LIVE_SEEDS = (101, 202, 303, 404)
+
+
+def live_cases(seed):
+    """(name, cfg, records, p) of tests/test_oracle_ransac.py::test_live_against_reference"""
+    return (("plane", O.cfg(O.PLANE, 3, 0.5), synth.plane(3000, 0.5, seed=seed)[0], 0.999),
+            ("sphere", O.cfg(O.SPHERE, 3, 0.5, O.LS_ALGEBRAIC), synth.sphere(1500, 0.4, seed=seed)[0], 0.99),
+            ("line", O.cfg(O.LINE, 2, 0.5), synth.line(500, 0.5, seed=seed, dim=2)[0], 0.999))
+
+
+def invalid_input_cases():
+    """(name, records, p, exhaustive) of tests/test_oracle_ransac.py::test_live_reference_invalid_input_untouched, all
+    with the parameters prefilled as [1, 2, 3]"""
+    data = synth.plane(50, 0.2)[0]
+    return (("p1", data, 1.0, False), ("n2", data[:2], 0.9, False), ("n2_exh", data[:2], 0.9, True))
+
+
+def live_vectors():
+    """the reference's outputs for the runs test_oracle_ransac.py once made only against a live oracle/_ref: the records
+    are seeded (not stored, pinned by their sha256); stored: fraction, parameters, consensus set (packed bits),
+    estimate() calls -- and, for the invalid inputs, fraction and the parameters the reference left"""
+    import hashlib
+    out = {}
+    for seed in LIVE_SEEDS:
+        for name, c, data, p in live_cases(seed):
+            key = "%s_s%d_" % (name, seed)
+            r = O.ref_ransac(c, data, p, seed=seed, subsets_cap=4096)
+            out[key + "data_sha"] = np.frombuffer(hashlib.sha256(data.tobytes()).digest(), dtype=np.uint8)
+            out[key + "fraction"] = np.array([r["fraction"]])
+            out[key + "params"] = r["params"]
+            out[key + "consensus_bits"] = np.packbits(r["consensus"])
+            out[key + "estimate_calls"] = np.array([r["estimate_calls"]], dtype=np.int64)
+    c = O.cfg(O.PLANE, 3, 0.5)
+    for name, data, p, exh in invalid_input_cases():
+        r = O.ref_ransac(c, data, p, exhaustive=exh, prefill=[1.0, 2.0, 3.0])
+        out["invalid_%s_fraction" % name] = np.array([r["fraction"]])
+        out["invalid_%s_params" % name] = r["params"]
+    np.savez_compressed(os.path.join(HERE, "live_ref_vectors.npz"), **out)
 
 
 def numerics_vectors():
@@ -186,12 +228,16 @@ if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "config1":
         config1_vectors()
         sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "live":
+        live_vectors()
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "us_lm_flags":
         us_lm_flag_table()
         sys.exit(0)
     copy_data()
     ransac_vectors()
     config1_vectors()
+    live_vectors()
     numerics_vectors()
     us_lm_vectors()
     us_lm_flag_table()

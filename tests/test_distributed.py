@@ -92,7 +92,9 @@ def _worker(rank, world, port, data, out):
     assert np.allclose(st[3], fit, rtol=0, atol=1e-12)
     if rank == 0:
         out.put((votes, gidx, par, fit, cnt, votes2, gidx2))
-    dist.barrier()
+    # the closing barrier as an all-reduce of a host tensor: gloo's barrier() asks the HIP runtime for its devices, which
+    # on a GPU box opens the GPU in every one of these CPU-only ranks (eight of them exceed a shared card's process cap)
+    dist.all_reduce(torch.zeros(1))
     dist.destroy_process_group()
 
 

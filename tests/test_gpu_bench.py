@@ -9,6 +9,7 @@ import subprocess
 import sys
 import tempfile
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -88,14 +89,24 @@ def _check(j, streams, n_gpus=1):
     assert len(j["per_rank_hypotheses_per_s"]) == j["config"]["world_size"]
 
 
-def test_bench_lanes_and_single_stream():
-    a = _run(["--workload", "plane"])
+def test_bench_lanes_and_single_stream(tmp_path):
+    a = _run(["--workload", "plane", "--dump-outputs", str(tmp_path / "a")])
     _check(a, 4)
-    b = _run(["--workload", "plane", "--streams", "1"])
+    b = _run(["--workload", "plane", "--streams", "1", "--dump-outputs", str(tmp_path / "b")])
     _check(b, 1)
     # the same steps: the last step's winner and fit do not depend on the number of streams
     assert a["final_fit"]["winner_votes"] == b["final_fit"]["winner_votes"]
     assert a["final_fit"]["params"] == b["final_fit"]["params"]
+    # --dump-outputs: what the last timed step of each rate returned, the same files on both drivers of the steps; the
+    # headline's final fit is the full-count rate's
+    for rate in ("full_count", "early_exit"):
+        for what in ("params", "winner"):
+            f = "%s_%s.npy" % (rate, what)
+            x, y = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+            assert x.dtype == np.float64 and np.array_equal(x, y), f
+    assert np.load(tmp_path / "a" / "full_count_params.npy").tolist() == a["final_fit"]["params"]
+    w = np.load(tmp_path / "a" / "full_count_winner.npy")
+    assert w[0] == a["final_fit"]["winner_votes"] and w[2] == a["final_fit"]["inliers"]
     # counting everything and the bounded scan see different work, and say so
     wf, we = a["roofline"]["work_model"], a["roofline_early_exit"]["work_model"]
     assert not wf["bounded_scan"] and wf["hypotheses_counted_exactly"] == 4096

@@ -1,6 +1,7 @@
 """Pins oracle/ransac.c (restated RANSAC.hxx) against outputs of the REFERENCE's own
-RANSAC.hxx: committed vectors (tests/golden/ransac_ref_vectors.npz, produced through
-oracle/_ref by tests/golden/make_golden.py) and, when oracle/_ref is present, live runs."""
+RANSAC.hxx: committed vectors (tests/golden/ransac_ref_vectors.npz, config1_ref_vectors.npz and
+live_ref_vectors.npz, produced through oracle/_ref by tests/golden/make_golden.py) and, when oracle/_ref is present,
+live runs."""
 import os
 
 import numpy as np
@@ -77,32 +78,54 @@ def test_invalid_input_conventions():
     assert r["fraction"] == 0
 
 
-@pytest.mark.skipif(not O.ref_available(), reason="oracle/_ref not built (no /root/reference)")
+@pytest.fixture(scope="module")
+def lv(golden_dir):
+    return np.load(os.path.join(golden_dir, "live_ref_vectors.npz"))
+
+
+def _live_cases(seed):
+    return (("plane", O.cfg(O.PLANE, 3, 0.5), synth.plane(3000, 0.5, seed=seed)[0], 0.999),
+            ("sphere", O.cfg(O.SPHERE, 3, 0.5, O.LS_ALGEBRAIC), synth.sphere(1500, 0.4, seed=seed)[0], 0.99),
+            ("line", O.cfg(O.LINE, 2, 0.5), synth.line(500, 0.5, seed=seed, dim=2)[0], 0.999))
+
+
 @pytest.mark.parametrize("seed", [101, 202, 303, 404])
-def test_live_against_reference(seed):
-    for c, data, p in (
-            (O.cfg(O.PLANE, 3, 0.5), synth.plane(3000, 0.5, seed=seed)[0], 0.999),
-            (O.cfg(O.SPHERE, 3, 0.5, O.LS_ALGEBRAIC), synth.sphere(1500, 0.4, seed=seed)[0], 0.99),
-            (O.cfg(O.LINE, 2, 0.5), synth.line(500, 0.5, seed=seed, dim=2)[0], 0.999)):
+def test_live_against_reference(lv, seed):
+    """the restated loop against the reference's RANSAC.hxx on the same rand() stream: the reference's outputs stored in
+    tests/golden/live_ref_vectors.npz (tests/golden/make_golden.py), and a live run when oracle/_ref is present"""
+    import hashlib
+    for name, c, data, p in _live_cases(seed):
+        key = "%s_s%d_" % (name, seed)
+        assert np.array_equal(np.frombuffer(hashlib.sha256(data.tobytes()).digest(), dtype=np.uint8),
+                              lv[key + "data_sha"])
+        refs = [dict(fraction=lv[key + "fraction"][0], params=lv[key + "params"],
+                     consensus=np.unpackbits(lv[key + "consensus_bits"])[:len(data)],
+                     estimate_calls=lv[key + "estimate_calls"][0])]
+        if O.ref_available():
+            refs.append(O.ref_ransac(c, data, p, seed=seed, subsets_cap=4096))
         a = O.ransac(c, data, p, sampler="ref", seed=seed)
-        b = O.ref_ransac(c, data, p, seed=seed, subsets_cap=4096)
-        assert a["fraction"] == b["fraction"]
-        assert np.array_equal(a["consensus"], b["consensus"])
-        assert np.array_equal(a["params"], b["params"])
-        assert (a["status"] != 1).sum() == b["estimate_calls"]
+        for b in refs:
+            assert a["fraction"] == b["fraction"]
+            assert np.array_equal(a["consensus"], b["consensus"])
+            assert np.array_equal(a["params"], b["params"])
+            assert (a["status"] != 1).sum() == b["estimate_calls"]
 
 
-@pytest.mark.skipif(not O.ref_available(), reason="oracle/_ref not built (no /root/reference)")
-def test_live_reference_invalid_input_untouched():
+def test_live_reference_invalid_input_untouched(lv):
+    """RANSAC.hxx:16-19 leaves the caller's parameters untouched on invalid input; the exhaustive overload clears them
+    first (RANSAC.hxx:165): the reference's outputs (stored, and live when oracle/_ref is present) and the restated
+    loops', on parameters prefilled with [1, 2, 3]"""
     c = O.cfg(O.PLANE, 3, 0.5)
     data = synth.plane(50, 0.2)[0]
-    r = O.ref_ransac(c, data, 1.0, prefill=[1.0, 2.0, 3.0])
-    assert r["fraction"] == 0 and np.array_equal(r["params"], [1.0, 2.0, 3.0])
-    r = O.ref_ransac(c, data[:2], 0.9, prefill=[1.0, 2.0, 3.0])
-    assert r["fraction"] == 0 and np.array_equal(r["params"], [1.0, 2.0, 3.0])
-    # exhaustive overload clears first (RANSAC.hxx:165)
-    r = O.ref_ransac(c, data[:2], 0.9, exhaustive=True, prefill=[1.0, 2.0, 3.0])
-    assert r["fraction"] == 0 and len(r["params"]) == 0
+    pre = [1.0, 2.0, 3.0]
+    for name, d, p, exh in (("p1", data, 1.0, False), ("n2", data[:2], 0.9, False), ("n2_exh", data[:2], 0.9, True)):
+        ref = (lv["invalid_%s_fraction" % name][0], lv["invalid_%s_params" % name])
+        assert ref[0] == 0 and np.array_equal(ref[1], [] if exh else pre)
+        runs = [O.ransac_exhaustive(c, d, prefill=pre) if exh else O.ransac(c, d, p, prefill=pre)]
+        if O.ref_available():
+            runs.append(O.ref_ransac(c, d, p, exhaustive=exh, prefill=pre))
+        for r in runs:
+            assert r["fraction"] == ref[0] and np.array_equal(r["params"], ref[1])
 
 
 def test_counter_sampler_properties():
