@@ -247,6 +247,36 @@ LSQR_API int lsqr_residuals(lsqr_ctx *ctx, const double *params, size_t begin, s
 LSQR_API int lsqr_ransac(lsqr_ctx *ctx, double p, uint64_t seed, const uint32_t *subsets,
                          size_t n_subsets, double *params_out, uint8_t *consensus_out,
                          lsqr_ransac_info *info);
+/* Many independent RANSAC<T,S>::compute() problems (probabilistic overload, RANSAC.h:75-79) in one call.
+ * Problem j is records [offsets[j], offsets[j+1]) of host_records (stride_bytes apart, laid out as for
+ * lsqr_upload), walks sampler stream seeds[j] and is decided exactly as lsqr_ransac(ctx, p, seeds[j], NULL, 0, ...)
+ * would decide it on those records alone.
+ *   Models: LSQR_MODEL_PLANE, LSQR_MODEL_LINE and LSQR_MODEL_SPHERE with ls_type = LSQR_LS_ALGEBRAIC, in every
+ *     dimension lsqr_set_model accepts for them, taken from the context's lsqr_set_model (none set:
+ *     LSQR_ERR_STATE).  Any other model, and the geometric (LM) sphere, returns LSQR_ERR_INVALID for the call.
+ *   Per-problem outcome in status_out[j]: N_j < k -> LSQR_ERR_INVALID (info zeroed, fraction 0, params untouched,
+ *     RANSAC.hxx:16-19); no valid hypothesis or a failed fit -> LSQR_EMPTY (params untouched); else LSQR_OK with
+ *     params_out[j * lsqr_num_params .. + lsqr_num_params) written.
+ *   Bad arguments (offsets[0] != 0 or decreasing, a problem of more than 2^32 - 16 records, p outside (0, 1), a null
+ *     required pointer, stride_bytes below the record) return LSQR_ERR_INVALID and write nothing.  n_problems == 0
+ *     is a no-op returning LSQR_OK.  Otherwise the call returns LSQR_OK.
+ *   Bit-identical to that lsqr_ransac call: status, iterations, best_index, best_votes, fraction, n_params,
+ *     fit.n_used and the consensus bytes (consensus_out, nullable: offsets[n_problems] bytes in record order;
+ *     0 for every record of a problem without a winner).  The parameters agree up to the order of the fp64 sums of
+ *     the final fit.  info.evaluated depends on the batch schedule.  The options max_iterations and the 2^22
+ *     no-model safety stop of lsqr_ransac apply per problem.
+ *   Independence: problem j's results, parameters included, are bit-identical whichever other problems share the
+ *     call, in whatever order, and however the rounds are cut (option "many_round_hypotheses": hypotheses per round,
+ *     0 = default 2^21; a problem whose batch alone exceeds it gets a round of its own).
+ *   The context's own upload, hypotheses and mask are not touched; the work runs on the context's current stream
+ *   (lsqr_set_stream).  lsqr_multi handles have no batched form: call it on one device's context. */
+LSQR_API int lsqr_ransac_many(lsqr_ctx *ctx, const void *host_records, size_t stride_bytes,
+                              const uint64_t *offsets /* n_problems + 1, offsets[0] == 0, non-decreasing */,
+                              size_t n_problems, double p, const uint64_t *seeds /* n_problems */,
+                              double *params_out      /* n_problems * lsqr_num_params */,
+                              uint8_t *consensus_out  /* nullable: offsets[n_problems] bytes, record order */,
+                              lsqr_ransac_info *infos /* n_problems */,
+                              int32_t *status_out     /* n_problems: LSQR_OK / LSQR_EMPTY / LSQR_ERR_INVALID */);
 /* One fixed-size batch of the same loop without the adaptive stopping rule: hypotheses
  * [first_index, first_index + H) of the sampler stream `seed` are solved and scanned, the first
  * hypothesis with the maximal vote count wins (the strict '>' of RANSAC.hxx:100), its consensus set

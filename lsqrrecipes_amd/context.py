@@ -256,6 +256,44 @@ class Context:
                     consensus=cons[:self.n] if (cons is not None and info.best_votes > 0) else None,
                     info=info)
 
+    def ransac_many(self, problems, p, seeds=None, want_consensus=True):
+        """Many independent RANSAC problems in one call (lsqr_ransac_many) with the context's model.
+        problems: a list of record arrays, or (records, offsets) with problem j = records[offsets[j]:offsets[j+1]].
+        seeds: one sampler stream per problem (default 1 + arange(n)); problem j is decided as
+        ransac(p, seed=seeds[j]) on its records alone.  -> dict of arrays: status, fraction, iterations,
+        best_index, best_votes, evaluated, n_params, n_used, params (n x P, zero rows where status is not OK),
+        consensus (flat, aligned with offsets; None unless want_consensus) and offsets."""
+        if self.cfg is None:
+            raise L.LsqrError(L.ERR_STATE, "set_model has not been called")
+        if isinstance(problems, tuple):
+            recs, offs = problems
+            recs = np.ascontiguousarray(recs, dtype=np.float64).reshape(-1, self.ND)
+            offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        else:
+            parts = [np.asarray(a, dtype=np.float64).reshape(-1, self.ND) for a in problems]
+            offs = np.zeros(len(parts) + 1, dtype=np.uint64)
+            offs[1:] = np.cumsum([a.shape[0] for a in parts])
+            recs = np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros((0, self.ND)))
+        n = len(offs) - 1
+        seeds = (1 + np.arange(n, dtype=np.uint64)) if seeds is None else np.ascontiguousarray(seeds, dtype=np.uint64)
+        if seeds.shape != (n,):
+            raise ValueError("one seed per problem")
+        params = np.zeros((max(n, 1), self.P))
+        total = int(offs[-1]) if n else 0
+        cons = np.zeros(max(total, 1), dtype=np.uint8) if want_consensus else None
+        infos = (L.RansacInfo * max(n, 1))()
+        status = np.zeros(max(n, 1), dtype=np.int32)
+        self._chk(self._lib.lsqr_ransac_many(self._h, L.ptr(recs), self.ND * 8, L.ptr(offs), n, float(p),
+                                             L.ptr(seeds), L.ptr(params), L.ptr(cons), infos, L.ptr(status)))
+        status, params = status[:n], params[:n]
+        params[status != L.OK] = 0.0
+        inf = np.ctypeslib.as_array(infos)[:n]  # structured view of the lsqr_ransac_info array
+        f = lambda name: inf[name].copy()
+        return dict(status=status, fraction=f("fraction"), iterations=f("iterations"), best_index=f("best_index"),
+                    best_votes=f("best_votes"), evaluated=f("evaluated"), n_params=f("n_params"),
+                    n_used=inf["fit"]["n_used"].copy(), params=params,
+                    consensus=cons[:total] if cons is not None else None, offsets=offs)
+
     def batch_fit(self, seed, first, H, want_consensus=False):
         """One fixed-size batch end to end on the device (lsqr_batch_fit): winner of hypotheses
         [first, first + H) of the sampler stream, its consensus set, the final fit."""

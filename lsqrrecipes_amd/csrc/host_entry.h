@@ -123,6 +123,9 @@ struct DedupSet {
   };
   std::vector<Key> tab;
   size_t used = 0;
+  size_t first_cap = 8192;  // slots of the first table (a power of two); lsqr_ransac_many keeps one set per problem
+  DedupSet() = default;
+  explicit DedupSet(size_t cap) : first_cap(cap) {}
   std::set<std::vector<uint32_t>, TupleLess> big;
   static uint64_t mix(uint64_t x) {
     x ^= x >> 33;
@@ -135,7 +138,7 @@ struct DedupSet {
   void grow() {
     std::vector<Key> old;
     old.swap(tab);
-    tab.assign(old.empty() ? 8192 : old.size() * 2, Key{0, 0});
+    tab.assign(old.empty() ? first_cap : old.size() * 2, Key{0, 0});
     used = 0;
     for (const Key &k : old)
       if (k.a | k.b) put(k);

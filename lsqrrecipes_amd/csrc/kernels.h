@@ -998,15 +998,10 @@ struct SolveOut {
   double params[64];
 };
 
+// the small solve of one moment block on one lane: k_solve, and the batched solve of lsqr_ransac_many (many.h)
 template <class M>
-__global__ __launch_bounds__(64) void k_solve(const double *__restrict__ mom,
-                                              const double *__restrict__ org, ModelConsts mc,
-                                              SolveOut *__restrict__ out) {
-  __shared__ double m[MOM_MAX];
-  __shared__ double ws[M::NMOM > 40 ? 512 : 8];  // workspace for the larger normal-equation solves
-  for (int i = threadIdx.x; i < (int)M::NMOM; i += 64) m[i] = mom[i];
-  __syncthreads();
-  if (threadIdx.x != 0) return;
+__device__ inline void solve_small(const double *m, const double *org, const ModelConsts &mc, double *ws,
+                                   SolveOut *__restrict__ out) {
   double par[M::P];
   bool ok;
   if constexpr (requires { M::solve_ws(m, org, mc, par, ws); }) ok = M::solve_ws(m, org, mc, par, ws);
@@ -1018,6 +1013,18 @@ __global__ __launch_bounds__(64) void k_solve(const double *__restrict__ mom,
   out->cont = 0;
   out->cost = 0.0;
   for (int j = 0; j < M::P; j++) out->params[j] = ok ? par[j] : 0.0;
+}
+
+template <class M>
+__global__ __launch_bounds__(64) void k_solve(const double *__restrict__ mom,
+                                              const double *__restrict__ org, ModelConsts mc,
+                                              SolveOut *__restrict__ out) {
+  __shared__ double m[MOM_MAX];
+  __shared__ double ws[M::NMOM > 40 ? 512 : 8];  // workspace for the larger normal-equation solves
+  for (int i = threadIdx.x; i < (int)M::NMOM; i += 64) m[i] = mom[i];
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  solve_small<M>(m, org, mc, ws, out);
 }
 
 // LM: state lives in device memory; the trial point the next pass must evaluate is state->xtrial.

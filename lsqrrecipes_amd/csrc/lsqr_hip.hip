@@ -35,6 +35,7 @@
 #include "phantom.h"
 #include "lm_persist.h"
 #include "host_entry.h"
+#include "many.h"
 
 #include <condition_variable>
 #include <mutex>
@@ -229,6 +230,8 @@ struct lsqr_ctx {
   int opt_mask_diag = 0;  // timing diagnostics of k_mask_syrk_dense: 1 = no matrix instructions, 2 = no row evaluation
   int opt_mask_band = 0;  // tests: scale factor of the dense fused mask's band (forces its serial re-evaluation path)
   long long opt_max_iter = 0;  // 0 = the reference's bound (numTries <= C(N,k))
+  long long opt_many_round = 0;  // lsqr_ransac_many: hypotheses per round (0 = kManyRoundDefault)
+  ManyBufs *many = nullptr;       // lsqr_ransac_many's buffers (its own: the context's upload is not touched)
   LmState h_lm;  // host copy of the LM state (opt_lm_host)
   double *d_lmrec = nullptr;  // consensus set copied tight and in order for the iterative fits (k_compact_*)
   size_t lmrec_cap = 0;
@@ -2812,14 +2815,13 @@ int set_fit_origin(lsqr_ctx *c, bool from_model) {
     if constexpr (M::IS_DENSE || requires { M::IS_PHANTOM; }) {
       return LSQR_OK;
     } else {
-      bool first_datum = !from_model;
-      if constexpr (requires { M::ORIGIN_FIRST; }) first_datum = true;
-      if (first_datum) {
+      const int off = fit_origin_offset<M>(c->cfg);  // (many.h: lsqr_ransac_many takes the same origin)
+      if (!from_model || off < 0) {
         HIPCHK(c, hipMemcpyAsync(c->d_vec, c->d_data, sizeof(double) * M::ND, hipMemcpyDeviceToDevice,
                                  c->stream));
       } else {
-        HIPCHK(c, hipMemcpyAsync(c->d_vec, c->d_par + (c->cfg.model == LSQR_MODEL_SPHERE ? 0 : M::ND),
-                                 sizeof(double) * M::ND, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->d_vec, c->d_par + off, sizeof(double) * M::ND, hipMemcpyDeviceToDevice,
+                                 c->stream));
       }
       return LSQR_OK;
     }
@@ -2920,6 +2922,7 @@ void lsqr_ctx_destroy(lsqr_ctx *c) {
     }
   (void)hipStreamSynchronize(c->stream);
   free_index(c);
+  many_free(c->many);
   void *bufs[] = {c->d_refused, c->d_us16, c->d_us16_x, c->d_h16, c->d_h16_bs, c->d_h16_thr, c->d_ddpart, c->d_ub2, c->d_axis, c->d_cellT, c->d_vpart, c->d_paircnt, c->d_paircost, c->d_sel, c->d_bsel, c->d_hparams2, c->d_hparams2_f32, c->d_votes2, c->d_lmrec, c->d_idx_scratch, c->d_ub, c->d_queues, c->d_data_owned, c->d_subsets, c->d_hparams, c->d_hparams_f32, c->d_amb, c->d_valid, c->d_votes, c->d_mask, c->d_rows,
                   c->d_partials, c->d_mom, c->d_vec, c->d_par, c->d_best, c->d_lm, c->d_out, c->d_counter};
   for (void *b : bufs)
@@ -3718,6 +3721,59 @@ int lsqr_ransac(lsqr_ctx *c, double p, uint64_t seed, const uint32_t *subsets, s
   info->best_index = rs[RS_BEST_IDX];
   return finish_ransac(c, rs[RS_HAS] != 0, (uint32_t)rs[RS_BEST], params_out,
                        consensus_out, info);
+}
+
+// ---- many independent RANSAC<T,S>::compute() problems (many.h) ------------------------------------------------
+int lsqr_ransac_many(lsqr_ctx *c, const void *host_records, size_t stride_bytes, const uint64_t *offsets,
+                     size_t n_problems, double p, const uint64_t *seeds, double *params_out, uint8_t *consensus_out,
+                     lsqr_ransac_info *infos, int32_t *status_out) {
+  int st = need_ready(c, false);
+  if (st != LSQR_OK) return st;
+  const lsqr_model_cfg &cfg = c->cfg;
+  if (cfg.model != LSQR_MODEL_PLANE && cfg.model != LSQR_MODEL_LINE && cfg.model != LSQR_MODEL_SPHERE)
+    return fail(c, LSQR_ERR_INVALID, "lsqr_ransac_many: plane, line and algebraic sphere only (model %d)", cfg.model);
+  if (cfg.model == LSQR_MODEL_SPHERE && cfg.ls_type != LSQR_LS_ALGEBRAIC)
+    return fail(c, LSQR_ERR_INVALID, "lsqr_ransac_many: the geometric (LM) sphere fit is not batched; use LSQR_LS_ALGEBRAIC");
+  if (n_problems == 0) return LSQR_OK;
+  if (!offsets || !seeds || !params_out || !infos || !status_out)
+    return fail(c, LSQR_ERR_INVALID, "lsqr_ransac_many: null argument");
+  if (!(p > 0.0) || !(p < 1.0)) return fail(c, LSQR_ERR_INVALID, "lsqr_ransac_many: p must lie in (0, 1)");
+  if (offsets[0] != 0) return fail(c, LSQR_ERR_INVALID, "lsqr_ransac_many: offsets[0] must be 0");
+  for (size_t j = 0; j < n_problems; j++) {
+    if (offsets[j + 1] < offsets[j]) return fail(c, LSQR_ERR_INVALID, "lsqr_ransac_many: offsets decrease at %zu", j);
+    if (offsets[j + 1] - offsets[j] > 0xFFFFFFF0ull)
+      return fail(c, LSQR_ERR_INVALID, "lsqr_ransac_many: problem %zu has more than 2^32 - 16 records", j);
+  }
+  if (offsets[n_problems] > 0 && !host_records) return fail(c, LSQR_ERR_INVALID, "lsqr_ransac_many: null records");
+  if (stride_bytes < sizeof(double) * (size_t)c->ND)
+    return fail(c, LSQR_ERR_INVALID, "lsqr_ransac_many: stride %zu below the record's %zu bytes", stride_bytes,
+                sizeof(double) * (size_t)c->ND);
+  if (!c->many) c->many = new ManyBufs();
+  ManyJob J;
+  J.stream = c->stream;
+  J.cfg = cfg;
+  J.mc = c->mc;
+  J.host = (const char *)host_records;
+  J.stride = stride_bytes;
+  J.offsets = offsets;
+  J.n = n_problems;
+  J.p = p;
+  J.seeds = seeds;
+  J.params_out = params_out;
+  J.consensus_out = consensus_out;
+  J.infos = infos;
+  J.status_out = status_out;
+  J.max_iter = c->opt_max_iter;
+  J.round_cap = c->opt_many_round > 0 ? (size_t)c->opt_many_round : kManyRoundDefault;
+  J.buf = c->many;
+  J.err[0] = 0;
+  st = dispatch(cfg, [&](auto tag) -> int {
+    typedef typename decltype(tag)::type M;
+    if constexpr (ManyModel<M>::value) return many_run<M>(J);
+    else return LSQR_ERR_INVALID;
+  });
+  if (st != LSQR_OK) return fail(c, st, "lsqr_ransac_many: %s", J.err[0] ? J.err : "model not in this build");
+  return LSQR_OK;
 }
 
 int lsqr_ransac_exhaustive(lsqr_ctx *c, double *params_out, uint8_t *consensus_out,
@@ -4775,6 +4831,11 @@ static int set_option_one(lsqr_ctx *c, const char *name, int value) {
   }
   if (!strcmp(name, "max_iterations")) {  // budget for lsqr_ransac (0 = reference behaviour)
     c->opt_max_iter = value;
+    return LSQR_OK;
+  }
+  if (!strcmp(name, "many_round_hypotheses")) {  // lsqr_ransac_many: hypotheses per round (0 = default)
+    if (value < 0) return fail(c, LSQR_ERR_INVALID, "many_round_hypotheses must be >= 0");
+    c->opt_many_round = value;
     return LSQR_OK;
   }
   if (!strcmp(name, "syrk_diag")) {  // 1: loads only, 2: MFMAs only (timing diagnostics, wrong sums)

@@ -1,0 +1,617 @@
+// many.h -- lsqr_ransac_many: many independent RANSAC<T,S>::compute() problems (plane, line, algebraic sphere) in
+// one call.  The problems' records are uploaded once, packed; then ROUNDS: every unfinished problem gets its next
+// batch of hypotheses (the schedule of lsqr_ransac: 256 -> 1024 -> 4096, capped by the adaptive bound), the host
+// replays each problem's serial loop over its votes (host_entry.h: host_replay + one DedupSet per problem), and
+// the rows of the problems whose best changed are copied into a per-problem best array on the device.  When every
+// problem is done, one segmented consensus mask + moment pass and one batched small solve finish them all.
+//
+//   k_many_sample_estimate  one lane per (problem, hypothesis) of the round: ctr_subset on the problem's stream at
+//                           its running index, M::estimate on the gathered records, M::prepare -> scan row
+//   k_many_scan             one workgroup per tile (problem, <= 256 hypotheses, <= kManySeg records); lane =
+//                           hypothesis with its scan row in registers; the records are staged through LDS and
+//                           read by every lane at the same address (broadcast); exact fp64 M::agree
+//   k_many_gather           winners' scan rows -> best[problem]
+//   k_many_mask_moments     consensus mask + phase-0 moment block about the winner's own point, one workgroup per
+//                           kManyPart records of a problem
+//   k_many_solve            one wave per problem: fixed-order sum of its parts, then solve_small (= k_solve)
+//
+// Independence: every quantity a problem's result depends on is a function of that problem's records alone: its
+// hypotheses (its own stream), its votes (integer sums), its moment block (parts of kManyPart records in record
+// order, reduced in part order).  The round cap only decides which problems share a round.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cstdlib>
+#include <cstdio>
+#include <cstring>
+#include <memory>
+#include <thread>
+#include <vector>
+
+#include "host_entry.h"
+#include "kernels.h"
+
+namespace lsqr {
+
+constexpr int kManyBlock = 256;            // hypotheses per scan tile: four waves, one lane each
+constexpr int kManyStage = 256;            // records per LDS stage (8-D: 16 KiB)
+constexpr uint64_t kManySeg = 16384;       // records per scan tile: longer problems are split, votes summed exactly
+constexpr uint64_t kManyPart = 8192;       // records per workgroup of the finish (fixes the moment sums' order)
+constexpr size_t kManyRoundDefault = 1u << 21;  // hypotheses per round (option many_round_hypotheses = 0)
+
+struct ManyItem {   // one problem's batch in a round
+  uint64_t rec;     // first record of the problem in the packed upload
+  uint64_t n;       // its record count
+  uint64_t seed;    // its sampler stream
+  uint64_t first;   // stream index of the batch's first hypothesis
+  uint32_t h0, H;   // rows [h0, h0 + H) of the round's hypothesis arrays
+};
+struct ManyTile {   // scan work item: rows [h0, h0 + nh) against records [r0, r1)
+  uint64_t r0, r1;
+  uint32_t h0, nh;
+};
+struct ManyPart {   // finish work item: records [r0, r1) of problem j (finishing slot f)
+  uint64_t r0, r1;
+  uint32_t j, f;
+};
+
+// the models lsqr_ransac_many runs: plane, line and sphere in every dimension (sphere: algebraic fit only)
+template <class M> struct ManyModel { static constexpr bool value = false; };
+template <int D> struct ManyModel<PlaneModel<D>> { static constexpr bool value = true; };
+template <int D> struct ManyModel<LineModel<D>> { static constexpr bool value = true; };
+template <int D> struct ManyModel<SphereModel<D>> { static constexpr bool value = true; };
+template <int D> struct ManyModel<PlaneModelN<D>> { static constexpr bool value = true; };
+template <int D> struct ManyModel<LineModelN<D>> { static constexpr bool value = true; };
+template <int D> struct ManyModel<SphereModelN<D>> { static constexpr bool value = true; };
+
+// where the fit origin lies in a scan-parameter row (the rule of set_fit_origin): the model's own point -- the
+// sphere's centre, the plane's / line's point --, or -1 for the models whose parameters hold no point (first record)
+template <class M>
+inline int fit_origin_offset(const lsqr_model_cfg &cfg) {
+  if constexpr (requires { M::ORIGIN_FIRST; }) return -1;
+  else return cfg.model == LSQR_MODEL_SPHERE ? 0 : (int)M::ND;
+}
+
+#if defined(__HIPCC__)
+template <class M>
+__global__ __launch_bounds__(kBlock) void k_many_sample_estimate(const double *__restrict__ data,
+                                                                 const ManyItem *__restrict__ items, int n_items,
+                                                                 uint32_t H, ModelConsts mc,
+                                                                 double *__restrict__ hparams,
+                                                                 uint8_t *__restrict__ valid) {
+  const uint32_t h = blockIdx.x * kBlock + threadIdx.x;
+  if (h >= H) return;
+  int lo = 0, hi = n_items - 1;  // the last item with h0 <= h
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (items[mid].h0 <= h) lo = mid;
+    else hi = mid - 1;
+  }
+  const ManyItem it = items[lo];
+  uint32_t idx[M::K], sorted[M::K];
+  ctr_subset(it.seed, it.first + (h - it.h0), it.n, M::K, idx, sorted);
+  double r[M::K][M::ND];
+  for (int l = 0; l < M::K; l++)
+    for (int j = 0; j < M::ND; j++) r[l][j] = data[(it.rec + idx[l]) * M::ND + j];
+  // from here on as k_estimate
+  double par[M::P];
+  const bool ok = M::estimate(r, mc, par);
+  const double qnan = __builtin_nan("");
+  double sp[M::SP];
+  for (int j = 0; j < M::P; j++) sp[j] = ok ? par[j] : qnan;
+  for (int j = M::P; j < M::SP; j++) sp[j] = 0.0;
+  M::prepare(sp, mc);
+  for (int j = 0; j < M::SP; j++) hparams[(size_t)h * M::SP + j] = sp[j];
+  valid[h] = ok ? 1 : 0;
+}
+
+template <class M>
+__global__ __launch_bounds__(kManyBlock) void k_many_scan(const double *__restrict__ data,
+                                                          const ManyTile *__restrict__ tiles,
+                                                          const double *__restrict__ hparams,
+                                                          const uint8_t *__restrict__ valid, ModelConsts mc,
+                                                          uint32_t *__restrict__ votes) {
+  static_assert(M::REC == M::ND, "point models: a record is its ND coordinates");
+  __shared__ double s_rec[kManyStage * M::ND];
+  const ManyTile t = tiles[blockIdx.x];
+  const uint32_t lane = threadIdx.x;
+  const bool live = lane < t.nh && valid[t.h0 + lane];
+  double sp[M::SP];
+#pragma unroll
+  for (int j = 0; j < M::SP; j++) sp[j] = live ? hparams[(size_t)(t.h0 + lane) * M::SP + j] : 0.0;
+  uint32_t c = 0;
+  for (uint64_t r0 = t.r0; r0 < t.r1; r0 += kManyStage) {
+    const uint32_t m = (uint32_t)(t.r1 - r0 < (uint64_t)kManyStage ? t.r1 - r0 : (uint64_t)kManyStage);
+    __syncthreads();  // the previous stage has been read
+    const double *src = data + r0 * M::ND;
+    for (uint32_t q = threadIdx.x; q < m * M::ND; q += kManyBlock) s_rec[q] = src[q];
+    __syncthreads();
+    if (live) {
+      for (uint32_t i = 0; i < m; i++) {
+        double x[M::REC];
+#pragma unroll
+        for (int d = 0; d < M::REC; d++) x[d] = s_rec[i * M::ND + d];  // same address in every lane: broadcast
+        c += M::agree(sp, x, mc) ? 1u : 0u;
+      }
+    }
+  }
+  if (live && c) atomicAdd(&votes[t.h0 + lane], c);
+}
+
+__global__ __launch_bounds__(kBlock) void k_many_gather(const uint32_t *__restrict__ pairs, uint32_t n_pairs, int sp,
+                                                        const double *__restrict__ hparams,
+                                                        double *__restrict__ best) {
+  const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
+  if (t >= n_pairs * (uint32_t)sp) return;
+  const uint32_t w = t / sp, k = t % sp;  // pair w = (problem, round row)
+  best[(size_t)pairs[2 * w] * sp + k] = hparams[(size_t)pairs[2 * w + 1] * sp + k];
+}
+
+// k_mask_moments for a part of one problem: the same per-thread order, shuffle tree and wave sum
+template <class M>
+__global__ __launch_bounds__(kBlock) void k_many_mask_moments(const double *__restrict__ data,
+                                                              const ManyPart *__restrict__ parts,
+                                                              const double *__restrict__ best, int org_off,
+                                                              ModelConsts mc, uint8_t *__restrict__ mask,
+                                                              unsigned long long *__restrict__ counts,
+                                                              double *__restrict__ partials) {
+  typedef AccLs<M> A;
+  __shared__ double s_m[kBlock / 64][A::N];
+  __shared__ uint32_t s_c[kBlock / 64];
+  const ManyPart pt = parts[blockIdx.x];
+  double acc[A::N];
+#pragma unroll
+  for (int k = 0; k < A::N; k++) acc[k] = 0.0;
+  double sp[M::SP];
+  for (int j = 0; j < M::SP; j++) sp[j] = best[(size_t)pt.j * M::SP + j];
+  constexpr int NC = M::P > M::REC ? M::P : M::REC;
+  double cv[NC];
+  for (int k = 0; k < NC; k++) cv[k] = k < M::ND ? sp[org_off + k] : 0.0;
+  uint32_t local = 0;
+  for (uint64_t i = pt.r0 + threadIdx.x; i < pt.r1; i += kBlock) {
+    double x[M::REC];
+    M::load(data + i * M::ND, mc, x);
+    const bool a = M::agree(sp, x, mc);
+    mask[i] = a ? 1 : 0;
+    if (!a) continue;
+    local++;
+    A::acc(x, cv, acc);
+  }
+#pragma unroll
+  for (int k = 0; k < A::N; k++) {
+    double v = acc[k];
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
+    if ((threadIdx.x & 63) == 0) s_m[threadIdx.x >> 6][k] = v;
+  }
+  for (int o = 32; o > 0; o >>= 1) local += __shfl_down(local, o);
+  if ((threadIdx.x & 63) == 0) s_c[threadIdx.x >> 6] = local;
+  __syncthreads();
+  if (threadIdx.x < A::N) {
+    double t = 0.0;
+    for (int w = 0; w < kBlock / 64; w++) t += s_m[w][threadIdx.x];
+    partials[(size_t)blockIdx.x * A::N + threadIdx.x] = t;
+  }
+  if (threadIdx.x == 0) {
+    unsigned long long t = 0;
+    for (int w = 0; w < kBlock / 64; w++) t += s_c[w];
+    if (t) atomicAdd(&counts[pt.f], t);
+  }
+}
+
+// one wave per finishing problem f: its parts [pbeg[f], pbeg[f+1]) summed in part order, then the solve of k_solve
+template <class M>
+__global__ __launch_bounds__(64) void k_many_solve(const double *__restrict__ partials,
+                                                   const uint32_t *__restrict__ pbeg,
+                                                   const uint32_t *__restrict__ fin, const double *__restrict__ best,
+                                                   int org_off, ModelConsts mc, SolveOut *__restrict__ out) {
+  __shared__ double m[MOM_MAX];
+  __shared__ double ws[M::NMOM > 40 ? 512 : 8];
+  const uint32_t f = blockIdx.x;
+  for (int k = threadIdx.x; k < (int)M::NMOM; k += 64) {
+    double t = 0.0;
+    for (uint32_t q = pbeg[f]; q < pbeg[f + 1]; q++) t += partials[(size_t)q * M::NMOM + k];
+    m[k] = t;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  constexpr int NC = M::P > M::REC ? M::P : M::REC;
+  double org[NC];
+  for (int k = 0; k < NC; k++) org[k] = k < M::ND ? best[(size_t)fin[f] * M::SP + org_off + k] : 0.0;
+  solve_small<M>(m, org, mc, ws, out + f);
+}
+#endif
+
+// ---- host side -------------------------------------------------------------------------------------------------
+// device and pinned buffers of the call, owned by the context and grown on demand
+struct ManyBufs {
+  double *d_data = nullptr, *d_hparams = nullptr, *d_best = nullptr, *d_partials = nullptr;
+  ManyItem *d_items = nullptr;
+  ManyTile *d_tiles = nullptr;
+  ManyPart *d_parts = nullptr;
+  uint8_t *d_valid = nullptr, *d_mask = nullptr;
+  uint32_t *d_votes = nullptr, *d_pairs = nullptr, *d_pbeg = nullptr, *d_fin = nullptr;
+  unsigned long long *d_counts = nullptr;
+  SolveOut *d_out = nullptr;
+  size_t c_data = 0, c_hparams = 0, c_best = 0, c_partials = 0, c_items = 0, c_tiles = 0, c_parts = 0, c_valid = 0,
+         c_mask = 0, c_votes = 0, c_pairs = 0, c_pbeg = 0, c_fin = 0, c_counts = 0, c_out = 0;
+  char *h_stage = nullptr, *h_pairs = nullptr;  // pinned: the round's tables and results / the winner pairs
+  size_t c_stage = 0, c_hpairs = 0;
+};
+
+#if defined(__HIPCC__)
+inline void many_free(ManyBufs *b) {
+  if (!b) return;
+  void *dev[] = {b->d_data, b->d_hparams, b->d_best, b->d_partials, b->d_items, b->d_tiles, b->d_parts, b->d_valid,
+                 b->d_mask, b->d_votes, b->d_pairs, b->d_pbeg, b->d_fin, b->d_counts, b->d_out};
+  for (void *p : dev)
+    if (p) (void)hipFree(p);
+  if (b->h_stage) (void)hipHostFree(b->h_stage);
+  if (b->h_pairs) (void)hipHostFree(b->h_pairs);
+  delete b;
+}
+
+template <class T>
+hipError_t many_grow(T **p, size_t *cap, size_t n) {
+  if (n <= *cap && *p) return hipSuccess;
+  if (*p) (void)hipFree(*p);
+  *p = nullptr;
+  *cap = 0;
+  const size_t want = std::max<size_t>(n + n / 4, 64);
+  hipError_t e = hipMalloc((void **)p, sizeof(T) * want);
+  if (e == hipSuccess) *cap = want;
+  return e;
+}
+// pinned host memory; the caller has synchronised the stream if an old buffer may still be read by a copy
+inline hipError_t many_grow_pinned(char **p, size_t *cap, size_t bytes) {
+  if (bytes <= *cap && *p) return hipSuccess;
+  if (*p) (void)hipHostFree(*p);
+  *p = nullptr;
+  *cap = 0;
+  const size_t want = std::max<size_t>(bytes + bytes / 4, 1 << 16);
+  hipError_t e = hipHostMalloc((void **)p, want);
+  if (e == hipSuccess) *cap = want;
+  return e;
+}
+
+struct ManyJob {
+  hipStream_t stream;
+  lsqr_model_cfg cfg;
+  ModelConsts mc;
+  const char *host;  // records, stride bytes apart
+  size_t stride;
+  const uint64_t *offsets;
+  size_t n;  // problems
+  double p;
+  const uint64_t *seeds;
+  double *params_out;
+  uint8_t *consensus_out;
+  lsqr_ransac_info *infos;
+  int32_t *status_out;
+  long long max_iter;  // option max_iterations
+  size_t round_cap;    // hypotheses per round (a problem whose batch alone exceeds it gets a round of its own)
+  ManyBufs *buf;
+  char err[256];
+};
+
+#define MANYCHK(call)                                                                                \
+  do {                                                                                               \
+    hipError_t e_ = (call);                                                                          \
+    if (e_ != hipSuccess) {                                                                          \
+      snprintf(J.err, sizeof J.err, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, \
+               __LINE__);                                                                            \
+      return LSQR_ERR_HIP;                                                                           \
+    }                                                                                                \
+  } while (0)
+
+// the per-problem state of lsqr_ransac's loop
+struct ManyProb {
+  uint64_t rs[6];
+  uint64_t base = 0, evaluated = 0;
+  size_t batch = 256;
+  bool live = false;
+  std::unique_ptr<DedupSet> dedup;
+};
+
+// host replay of items [i0, i1) of a round: lsqr_ransac's loop body after the batch's votes are in.  Subsets are
+// regenerated on the host (the same ctr_subset), piece by piece, only as far as the replay consumes them.
+template <class M>
+void many_replay(const ManyJob &J, std::vector<ManyProb> &pr, const std::vector<uint32_t> &item_prob,
+                 const ManyItem *items, size_t i0, size_t i1, const uint32_t *votes, const uint8_t *valid,
+                 std::vector<uint32_t> *pairs) {
+  constexpr int K = M::K;
+  constexpr size_t kPiece = 64;
+  uint32_t sub[kPiece * K], sorted[K];
+  for (size_t t = i0; t < i1; t++) {
+    const ManyItem &it = items[t];
+    const uint32_t j = item_prob[t];
+    ManyProb &q = pr[j];
+    if (!q.dedup) q.dedup.reset(new DedupSet(1024));
+    const uint64_t prev_best_idx = q.rs[RS_BEST_IDX];
+    const bool had = q.rs[RS_HAS] != 0;
+    size_t used = 0;
+    while (used < it.H) {  // host_replay over the batch, fed in pieces: the same sequential loop
+      const size_t m = std::min<size_t>(kPiece, it.H - used);
+      for (size_t e = 0; e < m; e++) ctr_subset(it.seed, it.first + used + e, it.n, K, sub + e * K, sorted);
+      const size_t u = host_replay(it.n, K, J.p, sub, valid + it.h0 + used, votes + it.h0 + used, m,
+                                   it.first + used, q.dedup.get(), q.rs);
+      used += u;
+      if (u < m) break;
+    }
+    q.evaluated += it.H;
+    if (q.rs[RS_HAS] && (!had || q.rs[RS_BEST_IDX] != prev_best_idx)) {
+      pairs->push_back(j);
+      pairs->push_back(it.h0 + (uint32_t)(q.rs[RS_BEST_IDX] - it.first));
+    }
+    q.base += used;
+    bool done = q.rs[RS_DONE] != 0 || used < it.H;
+    q.batch = std::min<size_t>(q.batch * 4, 4096);
+    // lsqr_ransac's safety stop (2^22 iterations without any model) and the caller's budget
+    if (!q.rs[RS_HAS] && q.base >= (1ull << 22)) done = true;
+    if (J.max_iter > 0 && q.base >= (uint64_t)J.max_iter) done = true;
+    if (done) {
+      q.live = false;
+      q.dedup.reset();
+    }
+  }
+}
+
+template <class M>
+int many_run(ManyJob &J) {
+  constexpr int K = M::K, ND = M::ND, SP = M::SP;
+  ManyBufs &B = *J.buf;
+  const size_t NP = J.n;
+  const uint64_t NT = J.offsets[NP];
+  const int org_off = fit_origin_offset<M>(J.cfg);
+  static_assert(M::NMOM <= 64, "one lane per moment in k_many_solve");
+
+  std::vector<ManyProb> pr(NP);
+  for (size_t j = 0; j < NP; j++) {
+    memset(&J.infos[j], 0, sizeof(lsqr_ransac_info));
+    const uint64_t n = J.offsets[j + 1] - J.offsets[j];
+    if (n < (uint64_t)K) {  // RANSAC.hxx:16-19: return 0, parameters untouched
+      J.status_out[j] = LSQR_ERR_INVALID;
+      continue;
+    }
+    host_replay_init(n, K, J.p, pr[j].rs);
+    pr[j].live = !pr[j].rs[RS_DONE];
+  }
+
+  // one upload of every problem's records, packed (ND doubles per record)
+  std::vector<double> packed;
+  const double *src = (const double *)J.host;
+  if (NT > 0) {
+    MANYCHK(many_grow(&B.d_data, &B.c_data, NT * ND));
+    if (J.stride != sizeof(double) * ND) {
+      packed.resize(NT * ND);
+      for (uint64_t i = 0; i < NT; i++) memcpy(&packed[i * ND], J.host + i * J.stride, sizeof(double) * ND);
+      src = packed.data();
+    }
+    MANYCHK(hipMemcpyAsync(B.d_data, src, sizeof(double) * ND * NT, hipMemcpyHostToDevice, J.stream));
+  }
+  MANYCHK(many_grow(&B.d_best, &B.c_best, std::max<size_t>(NP, 1) * SP));
+
+  const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
+  // diagnostics (LSQR_MANY_TRACE): per round the batches, hypotheses, tiles, device wait and host replay time
+  static const bool trace = getenv("LSQR_MANY_TRACE") != nullptr;
+  typedef std::chrono::steady_clock Clock;
+  int round = 0;
+  std::vector<uint32_t> live, item_prob;
+  std::vector<ManyItem> items;
+  std::vector<ManyTile> tiles;
+  size_t cursor = 0;
+  for (;;) {
+    live.clear();
+    for (size_t j = 0; j < NP; j++)
+      if (pr[j].live) live.push_back((uint32_t)j);
+    if (live.empty()) break;
+    // this round's batches: lsqr_ransac's loop head per problem; problems beyond the cap wait for the next round
+    items.clear();
+    item_prob.clear();
+    uint64_t Ht = 0;
+    const size_t L = live.size();
+    size_t taken = 0;
+    for (; taken < L; taken++) {
+      const uint32_t j = live[(cursor + taken) % L];
+      ManyProb &q = pr[j];
+      size_t H = q.batch;
+      const uint64_t remaining = q.rs[RS_TRIES] - q.base;
+      if (remaining < H) H = (size_t)remaining;
+      if (H == 0) {
+        q.live = false;
+        q.dedup.reset();
+        continue;
+      }
+      if (!items.empty() && Ht + H > J.round_cap) break;
+      ManyItem it;
+      it.rec = J.offsets[j];
+      it.n = J.offsets[j + 1] - J.offsets[j];
+      it.seed = J.seeds[j];
+      it.first = q.base;
+      it.h0 = (uint32_t)Ht;
+      it.H = (uint32_t)H;
+      items.push_back(it);
+      item_prob.push_back(j);
+      Ht += H;
+    }
+    cursor = L ? (cursor + taken) % L : 0;
+    if (items.empty()) continue;
+    // scan tiles, largest cost first, so that one long problem does not set the tail
+    tiles.clear();
+    for (const ManyItem &it : items)
+      for (uint32_t h = 0; h < it.H; h += kManyBlock)
+        for (uint64_t r = 0; r < it.n; r += kManySeg) {
+          ManyTile t;
+          t.r0 = it.rec + r;
+          t.r1 = it.rec + std::min<uint64_t>(it.n, r + kManySeg);
+          t.h0 = it.h0 + h;
+          t.nh = std::min<uint32_t>(kManyBlock, it.H - h);
+          tiles.push_back(t);
+        }
+    std::stable_sort(tiles.begin(), tiles.end(), [](const ManyTile &a, const ManyTile &b) {
+      return (uint64_t)a.nh * (a.r1 - a.r0) > (uint64_t)b.nh * (b.r1 - b.r0);
+    });
+    const size_t b_items = sizeof(ManyItem) * items.size(), b_tiles = sizeof(ManyTile) * tiles.size();
+    const size_t o_tiles = (b_items + 15) & ~(size_t)15, o_votes = (o_tiles + b_tiles + 15) & ~(size_t)15;
+    const size_t o_valid = o_votes + sizeof(uint32_t) * Ht;
+    MANYCHK(many_grow_pinned(&B.h_stage, &B.c_stage, o_valid + Ht));  // the previous round ended in a sync
+    memcpy(B.h_stage, items.data(), b_items);
+    memcpy(B.h_stage + o_tiles, tiles.data(), b_tiles);
+    MANYCHK(many_grow(&B.d_items, &B.c_items, items.size()));
+    MANYCHK(many_grow(&B.d_tiles, &B.c_tiles, tiles.size()));
+    MANYCHK(many_grow(&B.d_hparams, &B.c_hparams, Ht * SP));
+    MANYCHK(many_grow(&B.d_valid, &B.c_valid, Ht));
+    MANYCHK(many_grow(&B.d_votes, &B.c_votes, Ht));
+    MANYCHK(hipMemcpyAsync(B.d_items, B.h_stage, b_items, hipMemcpyHostToDevice, J.stream));
+    MANYCHK(hipMemcpyAsync(B.d_tiles, B.h_stage + o_tiles, b_tiles, hipMemcpyHostToDevice, J.stream));
+    MANYCHK(hipMemsetAsync(B.d_votes, 0, sizeof(uint32_t) * Ht, J.stream));
+    hipLaunchKernelGGL((k_many_sample_estimate<M>), dim3((unsigned)((Ht + kBlock - 1) / kBlock)), dim3(kBlock), 0,
+                       J.stream, B.d_data, B.d_items, (int)items.size(), (uint32_t)Ht, J.mc, B.d_hparams, B.d_valid);
+    MANYCHK(hipGetLastError());
+    hipLaunchKernelGGL((k_many_scan<M>), dim3((unsigned)tiles.size()), dim3(kManyBlock), 0, J.stream, B.d_data,
+                       B.d_tiles, B.d_hparams, B.d_valid, J.mc, B.d_votes);
+    MANYCHK(hipGetLastError());
+    uint32_t *h_votes = (uint32_t *)(B.h_stage + o_votes);
+    uint8_t *h_valid = (uint8_t *)(B.h_stage + o_valid);
+    MANYCHK(hipMemcpyAsync(h_votes, B.d_votes, sizeof(uint32_t) * Ht, hipMemcpyDeviceToHost, J.stream));
+    MANYCHK(hipMemcpyAsync(h_valid, B.d_valid, Ht, hipMemcpyDeviceToHost, J.stream));
+    const Clock::time_point t_sync = Clock::now();
+    MANYCHK(hipStreamSynchronize(J.stream));
+    const Clock::time_point t_replay = Clock::now();
+    // replay, problems spread over host threads (each item touches its own problem's state only)
+    const size_t NI = items.size();
+    const unsigned T = (unsigned)std::min<size_t>(std::min<unsigned>(hw, 16), (NI + 127) / 128);
+    std::vector<std::vector<uint32_t>> pairs(std::max(1u, T));
+    if (T <= 1) {
+      many_replay<M>(J, pr, item_prob, items.data(), 0, NI, h_votes, h_valid, &pairs[0]);
+    } else {
+      std::vector<std::thread> th;
+      for (unsigned w = 0; w < T; w++)
+        th.emplace_back([&, w] {
+          many_replay<M>(J, pr, item_prob, items.data(), NI * w / T, NI * (w + 1) / T, h_votes, h_valid, &pairs[w]);
+        });
+      for (auto &x : th) x.join();
+    }
+    size_t np = 0;
+    for (auto &v : pairs) np += v.size();
+    if (trace)
+      fprintf(stderr, "ransac_many round %d: %zu batches, %llu hypotheses, %zu tiles, wait %.3f ms, replay %.3f ms\n",
+              round, NI, (unsigned long long)Ht, tiles.size(),
+              std::chrono::duration<double, std::milli>(t_replay - t_sync).count(),
+              std::chrono::duration<double, std::milli>(Clock::now() - t_replay).count());
+    round++;
+    if (np) {  // winner rows -> best[problem], on the device, before the next round overwrites the rows
+      MANYCHK(many_grow_pinned(&B.h_pairs, &B.c_hpairs, sizeof(uint32_t) * np));
+      size_t o = 0;
+      for (auto &v : pairs) {
+        memcpy((uint32_t *)B.h_pairs + o, v.data(), sizeof(uint32_t) * v.size());
+        o += v.size();
+      }
+      MANYCHK(many_grow(&B.d_pairs, &B.c_pairs, np));
+      MANYCHK(hipMemcpyAsync(B.d_pairs, B.h_pairs, sizeof(uint32_t) * np, hipMemcpyHostToDevice, J.stream));
+      const uint32_t npairs = (uint32_t)(np / 2);
+      hipLaunchKernelGGL(k_many_gather, dim3((unsigned)((npairs * SP + kBlock - 1) / kBlock)), dim3(kBlock), 0,
+                         J.stream, B.d_pairs, npairs, (int)SP, B.d_hparams, B.d_best);
+      MANYCHK(hipGetLastError());
+      // the next round writes h_pairs only after its own synchronisation, which follows this copy
+    }
+  }
+
+  // ---- finish: finish_ransac for every problem with a winner -----------------------------------------------------
+  std::vector<uint32_t> fin, pbeg;
+  std::vector<ManyPart> parts;
+  for (size_t j = 0; j < NP; j++) {
+    const uint64_t n = J.offsets[j + 1] - J.offsets[j];
+    if (n < (uint64_t)K) continue;
+    ManyProb &q = pr[j];
+    lsqr_ransac_info &info = J.infos[j];
+    info.iterations = q.rs[RS_I];
+    info.best_index = q.rs[RS_BEST_IDX];
+    info.evaluated = q.evaluated;
+    info.best_votes = (uint32_t)q.rs[RS_BEST];
+    info.fraction = (double)info.best_votes / (double)n;
+    info.n_params = 0;
+    if (!q.rs[RS_HAS] || info.best_votes == 0) {
+      J.status_out[j] = LSQR_EMPTY;
+      continue;
+    }
+    const uint32_t f = (uint32_t)fin.size();
+    fin.push_back((uint32_t)j);
+    pbeg.push_back((uint32_t)parts.size());
+    for (uint64_t r = 0; r < n; r += kManyPart)
+      parts.push_back(ManyPart{J.offsets[j] + r, J.offsets[j] + std::min<uint64_t>(n, r + kManyPart), (uint32_t)j, f});
+  }
+  pbeg.push_back((uint32_t)parts.size());
+  const size_t NF = fin.size();
+  std::vector<unsigned long long> counts(NF);
+  std::vector<SolveOut> outs(NF);
+  if (NF) {
+    MANYCHK(many_grow(&B.d_parts, &B.c_parts, parts.size()));
+    MANYCHK(many_grow(&B.d_pbeg, &B.c_pbeg, pbeg.size()));
+    MANYCHK(many_grow(&B.d_fin, &B.c_fin, NF));
+    MANYCHK(many_grow(&B.d_counts, &B.c_counts, NF));
+    MANYCHK(many_grow(&B.d_out, &B.c_out, NF));
+    MANYCHK(many_grow(&B.d_partials, &B.c_partials, parts.size() * M::NMOM));
+    MANYCHK(many_grow(&B.d_mask, &B.c_mask, NT));
+    const size_t b_parts = sizeof(ManyPart) * parts.size(), o_pbeg = (b_parts + 15) & ~(size_t)15;
+    const size_t o_fin = (o_pbeg + sizeof(uint32_t) * pbeg.size() + 15) & ~(size_t)15;
+    MANYCHK(many_grow_pinned(&B.h_stage, &B.c_stage, o_fin + sizeof(uint32_t) * NF));
+    memcpy(B.h_stage, parts.data(), b_parts);
+    memcpy(B.h_stage + o_pbeg, pbeg.data(), sizeof(uint32_t) * pbeg.size());
+    memcpy(B.h_stage + o_fin, fin.data(), sizeof(uint32_t) * NF);
+    MANYCHK(hipMemcpyAsync(B.d_parts, B.h_stage, b_parts, hipMemcpyHostToDevice, J.stream));
+    MANYCHK(hipMemcpyAsync(B.d_pbeg, B.h_stage + o_pbeg, sizeof(uint32_t) * pbeg.size(), hipMemcpyHostToDevice,
+                           J.stream));
+    MANYCHK(hipMemcpyAsync(B.d_fin, B.h_stage + o_fin, sizeof(uint32_t) * NF, hipMemcpyHostToDevice, J.stream));
+    MANYCHK(hipMemsetAsync(B.d_counts, 0, sizeof(unsigned long long) * NF, J.stream));
+    hipLaunchKernelGGL((k_many_mask_moments<M>), dim3((unsigned)parts.size()), dim3(kBlock), 0, J.stream, B.d_data,
+                       B.d_parts, B.d_best, org_off, J.mc, B.d_mask, B.d_counts, B.d_partials);
+    MANYCHK(hipGetLastError());
+    hipLaunchKernelGGL((k_many_solve<M>), dim3((unsigned)NF), dim3(64), 0, J.stream, B.d_partials, B.d_pbeg, B.d_fin,
+                       B.d_best, org_off, J.mc, B.d_out);
+    MANYCHK(hipGetLastError());
+    MANYCHK(hipMemcpyAsync(counts.data(), B.d_counts, sizeof(unsigned long long) * NF, hipMemcpyDeviceToHost,
+                           J.stream));
+    MANYCHK(hipMemcpyAsync(outs.data(), B.d_out, sizeof(SolveOut) * NF, hipMemcpyDeviceToHost, J.stream));
+    if (J.consensus_out && NT)
+      MANYCHK(hipMemcpyAsync(J.consensus_out, B.d_mask, NT, hipMemcpyDeviceToHost, J.stream));
+  }
+  MANYCHK(hipStreamSynchronize(J.stream));
+  for (size_t f = 0; f < NF; f++) {
+    const uint32_t j = fin[f];
+    if (counts[f] != J.infos[j].best_votes) {
+      snprintf(J.err, sizeof J.err, "problem %u: consensus mask count %llu != scan votes %u", j, counts[f],
+               J.infos[j].best_votes);
+      return LSQR_ERR_HIP;
+    }
+  }
+  const int P = M::P;
+  std::vector<uint8_t> has_mask(NP, 0);
+  for (size_t f = 0; f < NF; f++) {
+    const uint32_t j = fin[f];
+    const SolveOut &o = outs[f];
+    lsqr_ransac_info &info = J.infos[j];
+    has_mask[j] = 1;
+    info.fit.n_params = o.ok ? o.n_params : 0;
+    info.fit.n_used = counts[f];
+    info.fit.cost = o.cost;
+    if (!o.ok) {
+      J.status_out[j] = LSQR_EMPTY;
+      continue;
+    }
+    info.n_params = o.n_params;
+    for (int k = 0; k < P; k++) J.params_out[(size_t)j * P + k] = o.params[k];
+    J.status_out[j] = LSQR_OK;
+  }
+  if (J.consensus_out)  // problems without a winner: no consensus set
+    for (size_t j = 0; j < NP; j++)
+      if (!has_mask[j] && J.offsets[j + 1] > J.offsets[j])
+        memset(J.consensus_out + J.offsets[j], 0, J.offsets[j + 1] - J.offsets[j]);
+  return LSQR_OK;
+}
+#undef MANYCHK
+#endif
+
+}  // namespace lsqr

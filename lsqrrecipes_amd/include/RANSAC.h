@@ -110,6 +110,69 @@ class RANSAC {
     return finish(ok, info, p, cons, parameters, consensusSet);
   }
 
+  // Many independent probabilistic searches (not in the reference): problem j is data[j] and walks sampler stream
+  // seed() + j, so computeMany(...)[j] equals compute() on data[j] after seed(seed() + j).  Per problem as
+  // compute(): invalid input returns 0 and leaves parameters[j] untouched, a search that finds nothing clears it.
+  // Plane, line and algebraic sphere run in ONE device call (lsqr_ransac_many: one upload, batched rounds, one
+  // finish); estimators without a device model loop over the plugin path, other device estimators over compute(),
+  // with the same seeds.  Under LSQR_DEVICES the batched call runs on the first listed device's context (problems
+  // are not sharded over devices).  lastInfo() is not updated.
+  static std::vector<double> computeMany(std::vector<std::vector<S> > &parameters,
+                                         ParametersEstimator<T, S> *paramEstimator,
+                                         const std::vector<std::vector<T> > &data, double desiredProbabilityForNoOutliers,
+                                         std::vector<std::vector<bool> > *consensusSets = NULL) {
+    if (!paramEstimator) throw std::invalid_argument("lsqrRecipes::RANSAC: null estimator");
+    const size_t n = data.size();
+    const double p = desiredProbabilityForNoOutliers;
+    parameters.resize(n);
+    if (consensusSets) consensusSets->resize(n);
+    std::vector<double> fraction(n, 0.0);
+    if (n == 0 || p >= 1.0 || p <= 0.0) return fraction;  // RANSAC.hxx:16-19 for every problem
+    lsqr_model_cfg cfg;
+    const bool device = paramEstimator->deviceModel(cfg) && !forceHostLoop();
+    const bool batched = device && (cfg.model == LSQR_MODEL_PLANE || cfg.model == LSQR_MODEL_LINE ||
+                                    (cfg.model == LSQR_MODEL_SPHERE && cfg.ls_type == LSQR_LS_ALGEBRAIC));
+    if (!batched) {
+      const uint64_t s0 = seed();
+      for (size_t j = 0; j < n; j++) {
+        seed() = s0 + j;
+        // (compute() reads the records only; it takes them by non-const reference as the reference does)
+        fraction[j] = compute(parameters[j], paramEstimator, const_cast<std::vector<T> &>(data[j]), p,
+                              consensusSets ? &(*consensusSets)[j] : NULL);
+      }
+      seed() = s0;
+      return fraction;
+    }
+    std::vector<uint64_t> offsets(n + 1, 0), seeds(n);
+    for (size_t j = 0; j < n; j++) {
+      offsets[j + 1] = offsets[j] + data[j].size();
+      seeds[j] = seed() + j;
+    }
+    std::vector<T> records;
+    records.reserve((size_t)offsets[n]);
+    for (size_t j = 0; j < n; j++) records.insert(records.end(), data[j].begin(), data[j].end());
+    detail::Device &d = detail::Device::instance();
+    lsqr_ctx *ctx = d.ctx();
+    if (lsqr_multi *m = d.multi()) ctx = lsqr_multi_ctx(m, 0);
+    d.check(lsqr_set_model(ctx, &cfg));
+    const int P = lsqr_num_params(&cfg);
+    std::vector<double> par(n * (size_t)P);
+    std::vector<uint8_t> cons(consensusSets ? (size_t)offsets[n] : 0);
+    std::vector<lsqr_ransac_info> info(n);
+    std::vector<int32_t> status(n);
+    d.check(lsqr_ransac_many(ctx, records.empty() ? NULL : &records[0], sizeof(T), &offsets[0], n, p, &seeds[0],
+                             &par[0], cons.empty() ? NULL : &cons[0], &info[0], &status[0]));
+    for (size_t j = 0; j < n; j++) {
+      if (status[j] == LSQR_ERR_INVALID) continue;  // fewer records than a minimal subset: untouched, 0
+      parameters[j].clear();  // RANSAC.hxx:43
+      if (info[j].best_votes > 0 && consensusSets)
+        (*consensusSets)[j].assign(cons.begin() + (size_t)offsets[j], cons.begin() + (size_t)offsets[j + 1]);
+      if (status[j] == LSQR_OK) parameters[j].assign(&par[j * P], &par[j * P] + info[j].n_params);
+      fraction[j] = info[j].fraction;
+    }
+    return fraction;
+  }
+
   // sampler stream of the probabilistic overload (default 1); set it to vary the hypotheses
   static uint64_t &seed() {
     static thread_local uint64_t s = 1;
