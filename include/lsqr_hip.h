@@ -251,9 +251,13 @@ LSQR_API int lsqr_ransac(lsqr_ctx *ctx, double p, uint64_t seed, const uint32_t 
  * Problem j is records [offsets[j], offsets[j+1]) of host_records (stride_bytes apart, laid out as for
  * lsqr_upload), walks sampler stream seeds[j] and is decided exactly as lsqr_ransac(ctx, p, seeds[j], NULL, 0, ...)
  * would decide it on those records alone.
- *   Models: LSQR_MODEL_PLANE, LSQR_MODEL_LINE and LSQR_MODEL_SPHERE with ls_type = LSQR_LS_ALGEBRAIC, in every
- *     dimension lsqr_set_model accepts for them, taken from the context's lsqr_set_model (none set:
- *     LSQR_ERR_STATE).  Any other model, and the geometric (LM) sphere, returns LSQR_ERR_INVALID for the call.
+ *   Models, taken from the context's lsqr_set_model (none set: LSQR_ERR_STATE):
+ *     accepted: LSQR_MODEL_PLANE, LSQR_MODEL_LINE and LSQR_MODEL_SPHERE with ls_type = LSQR_LS_ALGEBRAIC, in every
+ *       dimension lsqr_set_model accepts for them; LSQR_MODEL_ABSOR (ls_type 0, or 2: weighted, records of 7
+ *       doubles), LSQR_MODEL_PIVOT (Frame records of 13 slots), LSQR_MODEL_RAY (with its aux minimum angle) and
+ *       LSQR_MODEL_LINE2D.  Records are lsqr_record_doubles(cfg) wide, as for lsqr_upload.
+ *     refused with LSQR_ERR_INVALID for the call: LSQR_MODEL_DENSE, LSQR_MODEL_US_SINGLE, LSQR_MODEL_US_POINTER,
+ *       LSQR_MODEL_PHANTOM and the geometric (LM) sphere.
  *   Per-problem outcome in status_out[j]: N_j < k -> LSQR_ERR_INVALID (info zeroed, fraction 0, params untouched,
  *     RANSAC.hxx:16-19); no valid hypothesis or a failed fit -> LSQR_EMPTY (params untouched); else LSQR_OK with
  *     params_out[j * lsqr_num_params .. + lsqr_num_params) written.

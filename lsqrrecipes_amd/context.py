@@ -257,7 +257,9 @@ class Context:
                     info=info)
 
     def ransac_many(self, problems, p, seeds=None, want_consensus=True):
-        """Many independent RANSAC problems in one call (lsqr_ransac_many) with the context's model.
+        """Many independent RANSAC problems in one call (lsqr_ransac_many) with the context's model: plane, line,
+        algebraic sphere, absolute orientation (ls_type 0, or 2 with 7-double weighted records), pivot, ray and 2-D
+        line; any other model raises LsqrError(ERR_INVALID).  Records are self.ND doubles wide, as for upload.
         problems: a list of record arrays, or (records, offsets) with problem j = records[offsets[j]:offsets[j+1]].
         seeds: one sampler stream per problem (default 1 + arange(n)); problem j is decided as
         ransac(p, seed=seeds[j]) on its records alone.  -> dict of arrays: status, fraction, iterations,

@@ -3730,8 +3730,12 @@ int lsqr_ransac_many(lsqr_ctx *c, const void *host_records, size_t stride_bytes,
   int st = need_ready(c, false);
   if (st != LSQR_OK) return st;
   const lsqr_model_cfg &cfg = c->cfg;
-  if (cfg.model != LSQR_MODEL_PLANE && cfg.model != LSQR_MODEL_LINE && cfg.model != LSQR_MODEL_SPHERE)
-    return fail(c, LSQR_ERR_INVALID, "lsqr_ransac_many: plane, line and algebraic sphere only (model %d)", cfg.model);
+  if (cfg.model != LSQR_MODEL_PLANE && cfg.model != LSQR_MODEL_LINE && cfg.model != LSQR_MODEL_SPHERE &&
+      cfg.model != LSQR_MODEL_ABSOR && cfg.model != LSQR_MODEL_PIVOT && cfg.model != LSQR_MODEL_RAY &&
+      cfg.model != LSQR_MODEL_LINE2D)
+    return fail(c, LSQR_ERR_INVALID,
+                "lsqr_ransac_many: plane, line, algebraic sphere, absolute orientation, pivot, ray and 2-D line only "
+                "(model %d)", cfg.model);
   if (cfg.model == LSQR_MODEL_SPHERE && cfg.ls_type != LSQR_LS_ALGEBRAIC)
     return fail(c, LSQR_ERR_INVALID, "lsqr_ransac_many: the geometric (LM) sphere fit is not batched; use LSQR_LS_ALGEBRAIC");
   if (n_problems == 0) return LSQR_OK;
@@ -3757,6 +3761,7 @@ int lsqr_ransac_many(lsqr_ctx *c, const void *host_records, size_t stride_bytes,
   J.stride = stride_bytes;
   J.offsets = offsets;
   J.n = n_problems;
+  J.W = c->ND;  // lsqr_record_doubles(cfg)
   J.p = p;
   J.seeds = seeds;
   J.params_out = params_out;

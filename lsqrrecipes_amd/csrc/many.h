@@ -1,9 +1,10 @@
-// many.h -- lsqr_ransac_many: many independent RANSAC<T,S>::compute() problems (plane, line, algebraic sphere) in
-// one call.  The problems' records are uploaded once, packed; then ROUNDS: every unfinished problem gets its next
-// batch of hypotheses (the schedule of lsqr_ransac: 256 -> 1024 -> 4096, capped by the adaptive bound), the host
-// replays each problem's serial loop over its votes (host_entry.h: host_replay + one DedupSet per problem), and
-// the rows of the problems whose best changed are copied into a per-problem best array on the device.  When every
-// problem is done, one segmented consensus mask + moment pass and one batched small solve finish them all.
+// many.h -- lsqr_ransac_many: many independent RANSAC<T,S>::compute() problems (plane, line, algebraic sphere, absolute
+// orientation, pivot calibration, ray intersection, 2-D line) in one call.  The problems' records are uploaded once,
+// packed; then ROUNDS: every unfinished problem gets its next batch of hypotheses (the schedule of lsqr_ransac: 256 ->
+// 1024 -> 4096, capped by the adaptive bound), the host replays each problem's serial loop over its votes
+// (host_entry.h: host_replay + one DedupSet per problem), and the rows of the problems whose best changed are copied
+// into a per-problem best array on the device.  When every problem is done, one segmented consensus mask + moment pass
+// and one batched small solve finish them all.
 //
 //   k_many_sample_estimate  one lane per (problem, hypothesis) of the round: ctr_subset on the problem's stream at
 //                           its running index, M::estimate on the gathered records, M::prepare -> scan row
@@ -14,6 +15,11 @@
 //   k_many_mask_moments     consensus mask + phase-0 moment block about the winner's own point, one workgroup per
 //                           kManyPart records of a problem
 //   k_many_solve            one wave per problem: fixed-order sum of its parts, then solve_small (= k_solve)
+//
+// Records: W = lsqr_record_doubles(cfg) doubles each (the context's record width, packed on upload), read through
+// M::load as the single path reads them: absolute orientation's weight slot (W = 7 with ls_type 2), the pivot
+// frame's 12 doubles of 13.  Fit origin: the winner's own point (fit_origin_offset), or -- for the ORIGIN_FIRST
+// models -- the first ND doubles of the problem's first record, as set_fit_origin takes the upload's first record.
 //
 // Independence: every quantity a problem's result depends on is a function of that problem's records alone: its
 // hypotheses (its own stream), its votes (integer sums), its moment block (parts of kManyPart records in record
@@ -37,7 +43,7 @@
 namespace lsqr {
 
 constexpr int kManyBlock = 256;            // hypotheses per scan tile: four waves, one lane each
-constexpr int kManyStage = 256;            // records per LDS stage (8-D: 16 KiB)
+constexpr int kManyStage = 256;            // records per LDS stage (8-D: 16 KiB, pivot frames: 26 KiB)
 constexpr uint64_t kManySeg = 16384;       // records per scan tile: longer problems are split, votes summed exactly
 constexpr uint64_t kManyPart = 8192;       // records per workgroup of the finish (fixes the moment sums' order)
 constexpr size_t kManyRoundDefault = 1u << 21;  // hypotheses per round (option many_round_hypotheses = 0)
@@ -53,12 +59,15 @@ struct ManyTile {   // scan work item: rows [h0, h0 + nh) against records [r0, r
   uint64_t r0, r1;
   uint32_t h0, nh;
 };
-struct ManyPart {   // finish work item: records [r0, r1) of problem j (finishing slot f)
-  uint64_t r0, r1;
+struct ManyPart {   // finish work item: records [r0, r1) of problem j (finishing slot f), whose first record is org
+  uint64_t r0, r1, org;
   uint32_t j, f;
 };
 
-// the models lsqr_ransac_many runs: plane, line and sphere in every dimension (sphere: algebraic fit only)
+// the models lsqr_ransac_many runs: plane, line and sphere in every dimension (sphere: algebraic fit only), and the
+// closed-form estimators of rigid.h.  Their estimate / agree / solve read only the call-independent ModelConsts
+// fields (delta, delta_sq, ls_type, aux); absmax / absmax_rot belong to the context's own upload and are read by
+// the fp32 filters alone (prepare_f32), which this path does not run.
 template <class M> struct ManyModel { static constexpr bool value = false; };
 template <int D> struct ManyModel<PlaneModel<D>> { static constexpr bool value = true; };
 template <int D> struct ManyModel<LineModel<D>> { static constexpr bool value = true; };
@@ -66,6 +75,15 @@ template <int D> struct ManyModel<SphereModel<D>> { static constexpr bool value 
 template <int D> struct ManyModel<PlaneModelN<D>> { static constexpr bool value = true; };
 template <int D> struct ManyModel<LineModelN<D>> { static constexpr bool value = true; };
 template <int D> struct ManyModel<SphereModelN<D>> { static constexpr bool value = true; };
+template <> struct ManyModel<AbsOrModel> { static constexpr bool value = true; };
+template <> struct ManyModel<PivotModel> { static constexpr bool value = true; };
+template <> struct ManyModel<RayModel> { static constexpr bool value = true; };
+template <> struct ManyModel<Line2DModel> { static constexpr bool value = true; };  // (not matched as PlaneModel<2>)
+
+// doubles per record: ND, except absolute orientation, whose records carry a weight with ls_type 2 (W = 6 or 7, a
+// call's value); the LDS stage of the scan holds the widest
+template <class M> constexpr int many_wmax() { return M::REC > M::ND ? M::REC : M::ND; }
+template <class M> LSQR_HD int many_width(int W) { return M::REC > M::ND ? W : (int)M::ND; }
 
 // where the fit origin lies in a scan-parameter row (the rule of set_fit_origin): the model's own point -- the
 // sphere's centre, the plane's / line's point --, or -1 for the models whose parameters hold no point (first record)
@@ -77,7 +95,7 @@ inline int fit_origin_offset(const lsqr_model_cfg &cfg) {
 
 #if defined(__HIPCC__)
 template <class M>
-__global__ __launch_bounds__(kBlock) void k_many_sample_estimate(const double *__restrict__ data,
+__global__ __launch_bounds__(kBlock) void k_many_sample_estimate(const double *__restrict__ data, int W,
                                                                  const ManyItem *__restrict__ items, int n_items,
                                                                  uint32_t H, ModelConsts mc,
                                                                  double *__restrict__ hparams,
@@ -93,9 +111,10 @@ __global__ __launch_bounds__(kBlock) void k_many_sample_estimate(const double *_
   const ManyItem it = items[lo];
   uint32_t idx[M::K], sorted[M::K];
   ctr_subset(it.seed, it.first + (h - it.h0), it.n, M::K, idx, sorted);
+  const int w = many_width<M>(W);
   double r[M::K][M::ND];
   for (int l = 0; l < M::K; l++)
-    for (int j = 0; j < M::ND; j++) r[l][j] = data[(it.rec + idx[l]) * M::ND + j];
+    for (int j = 0; j < M::ND; j++) r[l][j] = data[(it.rec + idx[l]) * w + j];
   // from here on as k_estimate
   double par[M::P];
   const bool ok = M::estimate(r, mc, par);
@@ -109,13 +128,13 @@ __global__ __launch_bounds__(kBlock) void k_many_sample_estimate(const double *_
 }
 
 template <class M>
-__global__ __launch_bounds__(kManyBlock) void k_many_scan(const double *__restrict__ data,
+__global__ __launch_bounds__(kManyBlock) void k_many_scan(const double *__restrict__ data, int W,
                                                           const ManyTile *__restrict__ tiles,
                                                           const double *__restrict__ hparams,
                                                           const uint8_t *__restrict__ valid, ModelConsts mc,
                                                           uint32_t *__restrict__ votes) {
-  static_assert(M::REC == M::ND, "point models: a record is its ND coordinates");
-  __shared__ double s_rec[kManyStage * M::ND];
+  __shared__ double s_rec[kManyStage * many_wmax<M>()];
+  const int w = many_width<M>(W);
   const ManyTile t = tiles[blockIdx.x];
   const uint32_t lane = threadIdx.x;
   const bool live = lane < t.nh && valid[t.h0 + lane];
@@ -126,14 +145,13 @@ __global__ __launch_bounds__(kManyBlock) void k_many_scan(const double *__restri
   for (uint64_t r0 = t.r0; r0 < t.r1; r0 += kManyStage) {
     const uint32_t m = (uint32_t)(t.r1 - r0 < (uint64_t)kManyStage ? t.r1 - r0 : (uint64_t)kManyStage);
     __syncthreads();  // the previous stage has been read
-    const double *src = data + r0 * M::ND;
-    for (uint32_t q = threadIdx.x; q < m * M::ND; q += kManyBlock) s_rec[q] = src[q];
+    const double *src = data + r0 * w;
+    for (uint32_t q = threadIdx.x; q < m * w; q += kManyBlock) s_rec[q] = src[q];
     __syncthreads();
     if (live) {
       for (uint32_t i = 0; i < m; i++) {
         double x[M::REC];
-#pragma unroll
-        for (int d = 0; d < M::REC; d++) x[d] = s_rec[i * M::ND + d];  // same address in every lane: broadcast
+        M::load(s_rec + i * w, mc, x);  // same address in every lane: broadcast
         c += M::agree(sp, x, mc) ? 1u : 0u;
       }
     }
@@ -152,7 +170,7 @@ __global__ __launch_bounds__(kBlock) void k_many_gather(const uint32_t *__restri
 
 // k_mask_moments for a part of one problem: the same per-thread order, shuffle tree and wave sum
 template <class M>
-__global__ __launch_bounds__(kBlock) void k_many_mask_moments(const double *__restrict__ data,
+__global__ __launch_bounds__(kBlock) void k_many_mask_moments(const double *__restrict__ data, int W,
                                                               const ManyPart *__restrict__ parts,
                                                               const double *__restrict__ best, int org_off,
                                                               ModelConsts mc, uint8_t *__restrict__ mask,
@@ -169,11 +187,14 @@ __global__ __launch_bounds__(kBlock) void k_many_mask_moments(const double *__re
   for (int j = 0; j < M::SP; j++) sp[j] = best[(size_t)pt.j * M::SP + j];
   constexpr int NC = M::P > M::REC ? M::P : M::REC;
   double cv[NC];
-  for (int k = 0; k < NC; k++) cv[k] = k < M::ND ? sp[org_off + k] : 0.0;
+  const int w = many_width<M>(W);
+  // (ORIGIN_FIRST: the problem's first record; both from global memory, so that sp stays in registers)
+  const double *org = org_off < 0 ? data + pt.org * w : best + (size_t)pt.j * M::SP + org_off;
+  for (int k = 0; k < NC; k++) cv[k] = k < M::ND ? org[k] : 0.0;
   uint32_t local = 0;
   for (uint64_t i = pt.r0 + threadIdx.x; i < pt.r1; i += kBlock) {
     double x[M::REC];
-    M::load(data + i * M::ND, mc, x);
+    M::load(data + i * w, mc, x);
     const bool a = M::agree(sp, x, mc);
     mask[i] = a ? 1 : 0;
     if (!a) continue;
@@ -203,7 +224,9 @@ __global__ __launch_bounds__(kBlock) void k_many_mask_moments(const double *__re
 
 // one wave per finishing problem f: its parts [pbeg[f], pbeg[f+1]) summed in part order, then the solve of k_solve
 template <class M>
-__global__ __launch_bounds__(64) void k_many_solve(const double *__restrict__ partials,
+__global__ __launch_bounds__(64) void k_many_solve(const double *__restrict__ data, int W,
+                                                   const ManyPart *__restrict__ parts,
+                                                   const double *__restrict__ partials,
                                                    const uint32_t *__restrict__ pbeg,
                                                    const uint32_t *__restrict__ fin, const double *__restrict__ best,
                                                    int org_off, ModelConsts mc, SolveOut *__restrict__ out) {
@@ -219,7 +242,9 @@ __global__ __launch_bounds__(64) void k_many_solve(const double *__restrict__ pa
   if (threadIdx.x != 0) return;
   constexpr int NC = M::P > M::REC ? M::P : M::REC;
   double org[NC];
-  for (int k = 0; k < NC; k++) org[k] = k < M::ND ? best[(size_t)fin[f] * M::SP + org_off + k] : 0.0;
+  const double *o = org_off < 0 ? data + parts[pbeg[f]].org * many_width<M>(W)
+                                 : best + (size_t)fin[f] * M::SP + org_off;
+  for (int k = 0; k < NC; k++) org[k] = k < M::ND ? o[k] : 0.0;
   solve_small<M>(m, org, mc, ws, out + f);
 }
 #endif
@@ -284,6 +309,7 @@ struct ManyJob {
   size_t stride;
   const uint64_t *offsets;
   size_t n;  // problems
+  int W;     // doubles per record (lsqr_record_doubles)
   double p;
   const uint64_t *seeds;
   double *params_out;
@@ -360,7 +386,8 @@ void many_replay(const ManyJob &J, std::vector<ManyProb> &pr, const std::vector<
 
 template <class M>
 int many_run(ManyJob &J) {
-  constexpr int K = M::K, ND = M::ND, SP = M::SP;
+  constexpr int K = M::K, SP = M::SP;
+  const int W = many_width<M>(J.W);
   ManyBufs &B = *J.buf;
   const size_t NP = J.n;
   const uint64_t NT = J.offsets[NP];
@@ -379,17 +406,22 @@ int many_run(ManyJob &J) {
     pr[j].live = !pr[j].rs[RS_DONE];
   }
 
-  // one upload of every problem's records, packed (ND doubles per record)
+  if (W != J.W) {
+    snprintf(J.err, sizeof J.err, "record width %d != the model's %d doubles", J.W, W);
+    return LSQR_ERR_INVALID;
+  }
+  // one upload of every problem's records, packed (W doubles per record, copied as raw bytes: the pivot frame's
+  // int slot travels as it is)
   std::vector<double> packed;
   const double *src = (const double *)J.host;
   if (NT > 0) {
-    MANYCHK(many_grow(&B.d_data, &B.c_data, NT * ND));
-    if (J.stride != sizeof(double) * ND) {
-      packed.resize(NT * ND);
-      for (uint64_t i = 0; i < NT; i++) memcpy(&packed[i * ND], J.host + i * J.stride, sizeof(double) * ND);
+    MANYCHK(many_grow(&B.d_data, &B.c_data, NT * W));
+    if (J.stride != sizeof(double) * W) {
+      packed.resize(NT * W);
+      for (uint64_t i = 0; i < NT; i++) memcpy(&packed[i * W], J.host + i * J.stride, sizeof(double) * W);
       src = packed.data();
     }
-    MANYCHK(hipMemcpyAsync(B.d_data, src, sizeof(double) * ND * NT, hipMemcpyHostToDevice, J.stream));
+    MANYCHK(hipMemcpyAsync(B.d_data, src, sizeof(double) * W * NT, hipMemcpyHostToDevice, J.stream));
   }
   MANYCHK(many_grow(&B.d_best, &B.c_best, std::max<size_t>(NP, 1) * SP));
 
@@ -468,9 +500,10 @@ int many_run(ManyJob &J) {
     MANYCHK(hipMemcpyAsync(B.d_tiles, B.h_stage + o_tiles, b_tiles, hipMemcpyHostToDevice, J.stream));
     MANYCHK(hipMemsetAsync(B.d_votes, 0, sizeof(uint32_t) * Ht, J.stream));
     hipLaunchKernelGGL((k_many_sample_estimate<M>), dim3((unsigned)((Ht + kBlock - 1) / kBlock)), dim3(kBlock), 0,
-                       J.stream, B.d_data, B.d_items, (int)items.size(), (uint32_t)Ht, J.mc, B.d_hparams, B.d_valid);
+                       J.stream, B.d_data, W, B.d_items, (int)items.size(), (uint32_t)Ht, J.mc, B.d_hparams,
+                       B.d_valid);
     MANYCHK(hipGetLastError());
-    hipLaunchKernelGGL((k_many_scan<M>), dim3((unsigned)tiles.size()), dim3(kManyBlock), 0, J.stream, B.d_data,
+    hipLaunchKernelGGL((k_many_scan<M>), dim3((unsigned)tiles.size()), dim3(kManyBlock), 0, J.stream, B.d_data, W,
                        B.d_tiles, B.d_hparams, B.d_valid, J.mc, B.d_votes);
     MANYCHK(hipGetLastError());
     uint32_t *h_votes = (uint32_t *)(B.h_stage + o_votes);
@@ -541,7 +574,8 @@ int many_run(ManyJob &J) {
     fin.push_back((uint32_t)j);
     pbeg.push_back((uint32_t)parts.size());
     for (uint64_t r = 0; r < n; r += kManyPart)
-      parts.push_back(ManyPart{J.offsets[j] + r, J.offsets[j] + std::min<uint64_t>(n, r + kManyPart), (uint32_t)j, f});
+      parts.push_back(ManyPart{J.offsets[j] + r, J.offsets[j] + std::min<uint64_t>(n, r + kManyPart), J.offsets[j],
+                               (uint32_t)j, f});
   }
   pbeg.push_back((uint32_t)parts.size());
   const size_t NF = fin.size();
@@ -567,10 +601,10 @@ int many_run(ManyJob &J) {
     MANYCHK(hipMemcpyAsync(B.d_fin, B.h_stage + o_fin, sizeof(uint32_t) * NF, hipMemcpyHostToDevice, J.stream));
     MANYCHK(hipMemsetAsync(B.d_counts, 0, sizeof(unsigned long long) * NF, J.stream));
     hipLaunchKernelGGL((k_many_mask_moments<M>), dim3((unsigned)parts.size()), dim3(kBlock), 0, J.stream, B.d_data,
-                       B.d_parts, B.d_best, org_off, J.mc, B.d_mask, B.d_counts, B.d_partials);
+                       W, B.d_parts, B.d_best, org_off, J.mc, B.d_mask, B.d_counts, B.d_partials);
     MANYCHK(hipGetLastError());
-    hipLaunchKernelGGL((k_many_solve<M>), dim3((unsigned)NF), dim3(64), 0, J.stream, B.d_partials, B.d_pbeg, B.d_fin,
-                       B.d_best, org_off, J.mc, B.d_out);
+    hipLaunchKernelGGL((k_many_solve<M>), dim3((unsigned)NF), dim3(64), 0, J.stream, B.d_data, W, B.d_parts,
+                       B.d_partials, B.d_pbeg, B.d_fin, B.d_best, org_off, J.mc, B.d_out);
     MANYCHK(hipGetLastError());
     MANYCHK(hipMemcpyAsync(counts.data(), B.d_counts, sizeof(unsigned long long) * NF, hipMemcpyDeviceToHost,
                            J.stream));

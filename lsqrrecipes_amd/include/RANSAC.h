@@ -113,10 +113,12 @@ class RANSAC {
   // Many independent probabilistic searches (not in the reference): problem j is data[j] and walks sampler stream
   // seed() + j, so computeMany(...)[j] equals compute() on data[j] after seed(seed() + j).  Per problem as
   // compute(): invalid input returns 0 and leaves parameters[j] untouched, a search that finds nothing clears it.
-  // Plane, line and algebraic sphere run in ONE device call (lsqr_ransac_many: one upload, batched rounds, one
-  // finish); estimators without a device model loop over the plugin path, other device estimators over compute(),
-  // with the same seeds.  Under LSQR_DEVICES the batched call runs on the first listed device's context (problems
-  // are not sharded over devices).  lastInfo() is not updated.
+  // Plane, line, algebraic sphere, absolute orientation, pivot calibration, ray intersection and the 2-D line run in
+  // ONE device call (lsqr_ransac_many: one upload, batched rounds, one finish; the records are packed sizeof(T)
+  // apart, as compute() uploads them); estimators without a device model loop over the plugin path, other device
+  // estimators (dense system, US calibrations, plane phantom, geometric sphere) over compute(), with the same seeds.
+  // Under LSQR_DEVICES the batched call runs on the first listed device's context (problems are not sharded over
+  // devices).  lastInfo() is not updated.
   static std::vector<double> computeMany(std::vector<std::vector<S> > &parameters,
                                          ParametersEstimator<T, S> *paramEstimator,
                                          const std::vector<std::vector<T> > &data, double desiredProbabilityForNoOutliers,
@@ -131,7 +133,9 @@ class RANSAC {
     lsqr_model_cfg cfg;
     const bool device = paramEstimator->deviceModel(cfg) && !forceHostLoop();
     const bool batched = device && (cfg.model == LSQR_MODEL_PLANE || cfg.model == LSQR_MODEL_LINE ||
-                                    (cfg.model == LSQR_MODEL_SPHERE && cfg.ls_type == LSQR_LS_ALGEBRAIC));
+                                    (cfg.model == LSQR_MODEL_SPHERE && cfg.ls_type == LSQR_LS_ALGEBRAIC) ||
+                                    cfg.model == LSQR_MODEL_ABSOR || cfg.model == LSQR_MODEL_PIVOT ||
+                                    cfg.model == LSQR_MODEL_RAY || cfg.model == LSQR_MODEL_LINE2D);
     if (!batched) {
       const uint64_t s0 = seed();
       for (size_t j = 0; j < n; j++) {

@@ -4,7 +4,14 @@ Shapes (the loop is timed on the first --loop problems and extrapolated when the
   plane  3-D  10 000 problems x  1 000 records, 50 % inliers
   sphere 3-D   1 000 problems x 10 000 records (algebraic), 50 % inliers
   line   3-D 100 000 problems x    100 records, 50 % inliers
-and the single-call latency of Context.ransac (upload + compute) at N = 100 / 1 000 / 10 000.  Every timed call
+and the single-call latency of Context.ransac (upload + compute) at N = 100 / 1 000 / 10 000.  --shapes picks the
+shapes (default: the three above); the closed-form estimators' shapes (--shapes rigid: all four; the latency rows
+are skipped when no point shape is listed):
+  rays       100 000 problems x     12 rays,   70 % inliers, 1 degree minimum angle
+  absor       10 000 problems x     20 pairs,  70 % inliers (unweighted)
+  pivot        1 000 problems x    300 frames, 70 % inliers
+  line2d     100 000 problems x    200 points, 50 % inliers
+Each row also gives the loop's time per problem (loop_ms_per_problem).  Every timed call
 ends in a device synchronisation (both entry points return host results); each shape is warmed first; the two
 paths alternate in one process.  --quick: one repetition, small loop (for a kernel-trace run under rocprofv3).
 One JSON line per shape and size on stdout; --out FILE also writes them all to FILE."""
@@ -44,6 +51,59 @@ def gen(model, n_prob, n_rec, inl, seed):
     return np.ascontiguousarray(pts.reshape(-1, 3)), offs
 
 
+def random_rotations(g, shape):
+    """uniform random rotation matrices (shape + (3, 3)) from unit quaternions [s, qx, qy, qz]"""
+    q = g.normal(size=shape + (4,))
+    q /= np.linalg.norm(q, axis=-1, keepdims=True)
+    s, x, y, z = (q[..., i] for i in range(4))
+    R = np.stack([1 - 2 * (y * y + z * z), 2 * (x * y - s * z), 2 * (x * z + s * y),
+                  2 * (x * y + s * z), 1 - 2 * (x * x + z * z), 2 * (y * z - s * x),
+                  2 * (x * z - s * y), 2 * (y * z + s * x), 1 - 2 * (x * x + y * y)], axis=-1)
+    return R.reshape(shape + (3, 3))
+
+
+def gen_rigid(name, n_prob, n_rec, inl, seed):
+    """(records (n_prob * n_rec, W), offsets) for the closed-form estimators, one random truth per problem:
+    rays aimed at a point (sigma 0.3), point pairs under a rigid motion (sigma 0.2), pivoting frames (sigma 0.15),
+    points near a 2-D line (sigma 0.2); outliers as in synth.py"""
+    g = np.random.default_rng(seed)
+    P, N = n_prob, n_rec
+    is_out = g.random((P, N)) >= inl
+    if name == "rays":
+        target = g.uniform(-1000, 1000, (P, 1, 3))
+        p = g.uniform(-1000, 1000, (P, N, 3))
+        aim = np.where(is_out[..., None], g.uniform(-1000, 1000, (P, N, 3)), target + g.normal(0, 0.3, (P, N, 3)))
+        d = aim - p
+        d /= np.linalg.norm(d, axis=2, keepdims=True)
+        recs = np.concatenate([p, d], axis=2)
+    elif name == "absor":
+        R, t = random_rotations(g, (P,)), g.uniform(-1000, 1000, (P, 1, 3))
+        first = g.uniform(-100, 100, (P, N, 3))
+        second = np.einsum("pij,pnj->pni", R, first) + t + g.normal(0, 0.2, (P, N, 3))
+        second[is_out] += g.uniform(5, 50, (int(is_out.sum()), 3))
+        recs = np.concatenate([first, second], axis=2)
+    elif name == "pivot":
+        tip, piv = g.uniform(-200, 200, (P, 1, 3)), g.uniform(-1000, 1000, (P, 1, 3))
+        R = random_rotations(g, (P, N))
+        t = piv - np.einsum("pnij,pnj->pni", R, np.broadcast_to(tip, (P, N, 3))) + g.normal(0, 0.15, (P, N, 3))
+        t[is_out] += g.uniform(-40, 40, (int(is_out.sum()), 3))
+        recs = np.concatenate([R.reshape(P, N, 9), t, np.zeros((P, N, 1))], axis=2)
+    else:
+        a, ang = g.uniform(-500, 500, (P, 1, 2)), g.uniform(0, np.pi, (P, 1))
+        u = np.stack([np.cos(ang), np.sin(ang)], axis=-1)
+        pts = a + g.uniform(-100, 100, (P, N, 1)) * u + g.normal(0, 0.2, (P, N, 2))
+        pts[is_out] = (a + g.uniform(-100, 100, (P, N, 2)))[is_out]
+        recs = pts
+    offs = np.arange(P + 1, dtype=np.uint64) * N
+    return np.ascontiguousarray(recs.reshape(P * N, -1)), offs
+
+
+POINT_SHAPES = {"plane": (L.PLANE, 10_000, 1_000), "sphere": (L.SPHERE, 1_000, 10_000), "line": (L.LINE, 100_000, 100)}
+# name -> (model, problems, records, inlier share, delta, aux)
+RIGID_SHAPES = {"rays": (L.RAY, 100_000, 12, 0.7, 1.0, np.pi / 180), "absor": (L.ABSOR, 10_000, 20, 0.7, 1.0, 0.0),
+                "pivot": (L.PIVOT, 1_000, 300, 0.7, 1.0, 0.0), "line2d": (L.LINE2D, 100_000, 200, 0.5, 0.5, 0.0)}
+
+
 def timed(f, reps):
     t = []
     r = None
@@ -60,16 +120,28 @@ def main():
     ap.add_argument("--loop", type=int, default=1000, help="problems of the per-problem loop (extrapolated)")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--out", default=None, help="also write the results as one JSON file")
+    ap.add_argument("--shapes", default="plane,sphere,line",
+                    help="comma-separated shapes (%s), or 'rigid' for the last four" % ", ".join(
+                        list(POINT_SHAPES) + list(RIGID_SHAPES)))
     a = ap.parse_args()
+    names = list(RIGID_SHAPES) if a.shapes == "rigid" else a.shapes.split(",")
+    for name in names:
+        if name not in POINT_SHAPES and name not in RIGID_SHAPES:
+            ap.error("unknown shape %r" % name)
     reps = 1 if a.quick else a.reps
     loop_n = 100 if a.quick else a.loop
     ctx = Context(0)
     out = dict(shapes=[], latency=[])
-    shapes = [("plane", L.PLANE, 10_000, 1_000), ("sphere", L.SPHERE, 1_000, 10_000), ("line", L.LINE, 100_000, 100)]
-    for name, model, P, N in shapes:
-        recs, offs = gen(model, P, N, 0.5, seed=model)
+    for name in names:
+        if name in POINT_SHAPES:
+            model, P, N = POINT_SHAPES[name]
+            recs, offs = gen(model, P, N, 0.5, seed=model)
+            ctx.set_model(model, 3, 0.5, L.LS_ALGEBRAIC)
+        else:
+            model, P, N, inl, delta, aux = RIGID_SHAPES[name]
+            recs, offs = gen_rigid(name, P, N, inl, seed=model)
+            ctx.set_model(model, 2 if model == L.LINE2D else 3, delta, 0, aux=aux)
         seeds = 1 + np.arange(P, dtype=np.uint64)
-        ctx.set_model(model, 3, 0.5, L.LS_ALGEBRAIC)
         many = lambda: ctx.ransac_many((recs, offs), 0.999, seeds=seeds)
         m = min(loop_n, P)
 
@@ -90,12 +162,13 @@ def main():
         tm, tl = float(np.median(t_many)), float(np.median(t_loop)) * P / m
         ev = res["evaluated"].astype(np.float64)
         row = dict(shape=name, problems=P, records=N, many_ms=1e3 * tm, loop_ms=1e3 * tl,
+                   loop_ms_per_problem=1e3 * tl / P,
                    loop_extrapolated_from=m if m < P else None, speedup=tl / tm,
                    ok=int(np.sum(res["status"] == L.OK)), mean_iterations=float(np.mean(res["iterations"])),
                    hypotheses_scanned=float(ev.sum()), agree_evaluations=float((ev * N).sum()))
         out["shapes"].append(row)
         print(json.dumps(row), flush=True)
-    for n in (100, 1_000, 10_000):
+    for n in ((100, 1_000, 10_000) if any(nm in POINT_SHAPES for nm in names) else ()):
         recs, _ = gen(L.PLANE, 1, n, 0.5, seed=n)
         ctx.set_model(L.PLANE, 3, 0.5)
 
