@@ -223,7 +223,8 @@ struct lsqr_ctx {
   LmState *d_lm = nullptr;
   SolveOut *d_out = nullptr;
   unsigned long long *d_counter = nullptr;
-  bool origin_valid = false;
+  bool origin_valid = false;  // d_par holds the parameters the device mask was made from (set_fit_origin)
+  uint64_t win_rec = 0;       // first drawn record of the winning minimal subset (lsqr_ransac*, set_fit_origin)
   int opt_ppl = 0, opt_filter = 1, opt_lm_host = 1, opt_syrk_diag = 0;
   int opt_fuse_mask = 1;  // winner's mask + moment block in one pass (0: two kernels, for A/B runs)
   int opt_mask_ring = 4;  // k_mask_syrk_dense: tile buffers per wave (2: two workgroups per CU; 4: one, three tiles in flight)
@@ -2149,9 +2150,101 @@ void lm_settings(const lsqr_model_cfg &cfg, int *n, double *ftol, double *xtol, 
   }
 }
 
+// ---- the fit origin ------------------------------------------------------------------------------------------------
+// The closed-form fits accumulate their moments about an origin and add it back in solve (rigid.h, models.h); the
+// shift keeps the sums free of cancellation.  The origin must be finite and near the records that are summed, or it
+// decides the result: a NaN / Inf origin makes every parameter NaN, a far one loses the rotation in rounding.  The
+// rule, for every entry point (many.h takes the same records):
+//   RANSAC finish (ORG_WINNER: the winner is known on the host, ORG_WINNER_DEV: k_best's packed value on the device)
+//     - plane, line, sphere: the winner's own point in its scan row (fit_origin_offset);
+//     - absolute orientation, ray, pivot (ORIGIN_FIRST: the parameters hold no point): the first drawn record of the
+//       winning minimal subset -- finite and in the inlier cloud whenever the winner has votes;
+//   masked fit without a winner (ORG_MASK: lsqr_set_mask, or an ORIGIN_FIRST model after lsqr_mask): the first record
+//     whose mask bit is set; plane / line / sphere after a device mask: the point of the parameters it was made from;
+//   unmasked fit (ORG_ALL): the first record, which is summed anyway.
+enum FitOrigin { ORG_WINNER, ORG_WINNER_DEV, ORG_MASK, ORG_ALL };
+
+// ORG_WINNER_DEV: the first drawn record of the subset of the packed winner (zeros without a winner: nothing agrees)
+__global__ void k_winner_origin(const unsigned long long *__restrict__ packed, const uint32_t *__restrict__ subsets,
+                                int K, const double *__restrict__ data, size_t stride, int nd,
+                                double *__restrict__ org) {
+  const unsigned long long pk = *packed;
+  const int t = threadIdx.x;
+  if (t >= nd) return;
+  if (pk == 0) {
+    org[t] = 0.0;
+    return;
+  }
+  const size_t e = 0xFFFFFFFFull - (pk & 0xFFFFFFFFull);
+  org[t] = data[(size_t)subsets[e * K] * stride + t];
+}
+
+// ORG_MASK: the smallest i < n with mask[i] != 0 -> *first (the caller sets it to ~0 first)
+__global__ __launch_bounds__(kBlock) void k_first_masked(const uint8_t *__restrict__ mask, size_t n,
+                                                         unsigned long long *__restrict__ first) {
+  unsigned long long mine = ~0ull;
+  for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kBlock)
+    if (mask[i]) {  // ascending per lane: the lane's first hit is its smallest
+      mine = i;
+      break;
+    }
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned long long v = __shfl_down(mine, o);
+    mine = v < mine ? v : mine;
+  }
+  if ((threadIdx.x & 63) == 0 && mine != ~0ull) atomicMin(first, mine);
+}
+
+// record *idx -> org (zeros for ~0: an empty mask, the fit comes out empty)
+__global__ void k_record_origin(const unsigned long long *__restrict__ idx, const double *__restrict__ data,
+                                size_t stride, int nd, double *__restrict__ org) {
+  const int t = threadIdx.x;
+  if (t >= nd) return;
+  const unsigned long long i = *idx;
+  org[t] = i == ~0ull ? 0.0 : data[(size_t)i * stride + t];
+}
+
+// the fit origin -> d_vec (ORG_WINNER: d_par holds the winner's scan row and c->win_rec its first drawn record;
+// ORG_WINNER_DEV: d_counter[1] its packed value and d_subsets the batch's subsets)
+int set_fit_origin(lsqr_ctx *c, FitOrigin how) {
+  return dispatch(c->cfg, [&](auto tag) -> int {
+    typedef typename decltype(tag)::type M;
+    if constexpr (M::IS_DENSE || requires { M::IS_PHANTOM; }) {
+      return LSQR_OK;
+    } else {
+      const int off = fit_origin_offset<M>(c->cfg);  // (many.h: lsqr_ransac_many takes the same origin)
+      const bool own_point = how == ORG_WINNER || how == ORG_WINNER_DEV || (how == ORG_MASK && c->origin_valid);
+      if (off >= 0 && own_point) {
+        HIPCHK(c, hipMemcpyAsync(c->d_vec, c->d_par + off, sizeof(double) * M::ND, hipMemcpyDeviceToDevice,
+                                 c->stream));
+      } else if (how == ORG_WINNER || how == ORG_ALL) {
+        const size_t r = how == ORG_WINNER ? (size_t)c->win_rec : 0;
+        if (r >= c->n) return fail(c, LSQR_ERR_STATE, "fit origin: record %zu of %zu", r, c->n);
+        HIPCHK(c, hipMemcpyAsync(c->d_vec, c->d_data + r * c->stride, sizeof(double) * M::ND,
+                                 hipMemcpyDeviceToDevice, c->stream));
+      } else if (how == ORG_WINNER_DEV) {
+        hipLaunchKernelGGL(k_winner_origin, dim3(1), dim3(64), 0, c->stream, c->d_counter + 1, c->d_subsets, c->K,
+                           c->d_data, c->stride, (int)M::ND, c->d_vec);
+        HIPCHK(c, hipGetLastError());
+      } else {  // ORG_MASK
+        unsigned long long *first = c->d_counter + 6;
+        HIPCHK(c, hipMemsetAsync(first, 0xFF, sizeof(unsigned long long), c->stream));
+        hipLaunchKernelGGL(k_first_masked, dim3(grid_for(c->n, kBlock * 16, 1024)), dim3(kBlock), 0, c->stream,
+                           c->d_mask, c->n, first);
+        HIPCHK(c, hipGetLastError());
+        hipLaunchKernelGGL(k_record_origin, dim3(1), dim3(64), 0, c->stream, first, c->d_data, c->stride,
+                           (int)M::ND, c->d_vec);
+        HIPCHK(c, hipGetLastError());
+      }
+      return LSQR_OK;
+    }
+  });
+}
+
 // the closed-form part of run_fit without the read-back: moments + solve chained on the stream, result in
 // d_out.  Models whose fit needs the host in the loop (LM, the phantom's Gram solve) are refused.
-int enqueue_fit(lsqr_ctx *c, int use_mask, bool have_moments = false) {
+// have_origin: the caller has put the fit origin into d_vec (set_fit_origin)
+int enqueue_fit(lsqr_ctx *c, int use_mask, bool have_moments = false, bool have_origin = false) {
   if (wants_lm(c->cfg) || c->cfg.model == LSQR_MODEL_PHANTOM)
     return fail(c, LSQR_ERR_INVALID, "this fit needs the host between device passes");
   return dispatch(c->cfg, [&](auto tag) -> int {
@@ -2162,15 +2255,7 @@ int enqueue_fit(lsqr_ctx *c, int use_mask, bool have_moments = false) {
       return launch_solve_dense(c, true, use_mask, 0, c->n);
     } else {
       if (!have_moments) {
-        bool first_datum = !c->origin_valid;
-        if constexpr (requires { M::ORIGIN_FIRST; }) first_datum = true;
-        if (first_datum) {
-          HIPCHK(c, hipMemcpyAsync(c->d_vec, c->d_data, sizeof(double) * M::ND, hipMemcpyDeviceToDevice,
-                                   c->stream));
-        } else {
-          HIPCHK(c, hipMemcpyAsync(c->d_vec, c->d_par + (c->cfg.model == LSQR_MODEL_SPHERE ? 0 : M::ND),
-                                   sizeof(double) * M::ND, hipMemcpyDeviceToDevice, c->stream));
-        }
+        if (!have_origin && (st = set_fit_origin(c, use_mask ? ORG_MASK : ORG_ALL)) != LSQR_OK) return st;
         if ((st = launch_moments<M>(c, use_mask, 0, c->n, 0, &nmom)) != LSQR_OK) return st;
       }
       ProfScope ps(c, KID_SOLVE);
@@ -2408,7 +2493,8 @@ int lm_persist_fit(lsqr_ctx *c, const double *tiles, size_t cnt, int nb, LmState
 
 // leastSquaresEstimate over [0,n) (single device).  Leaves the result in d_out.
 // have_moments: d_mom already holds the phase-0 block about d_vec (launch_mask_moments)
-int run_fit(lsqr_ctx *c, int use_mask, SolveOut *out, bool have_moments = false) {
+// have_origin: the caller has put the fit origin into d_vec (set_fit_origin)
+int run_fit(lsqr_ctx *c, int use_mask, SolveOut *out, bool have_moments = false, bool have_origin = false) {
   return dispatch(c->cfg, [&](auto tag) -> int {
     typedef typename decltype(tag)::type M;
     int nmom = 0, st;
@@ -2425,15 +2511,7 @@ int run_fit(lsqr_ctx *c, int use_mask, SolveOut *out, bool have_moments = false)
       return read_out(c, out);
     } else {
     if (!have_moments) {
-    bool first_datum = !c->origin_valid;  // default origin: the first observation
-    if constexpr (requires { M::ORIGIN_FIRST; }) first_datum = true;  // parameters hold no point
-    if (first_datum) {
-      HIPCHK(c, hipMemcpyAsync(c->d_vec, c->d_data, sizeof(double) * M::ND,
-                               hipMemcpyDeviceToDevice, c->stream));
-    } else {
-      HIPCHK(c, hipMemcpyAsync(c->d_vec, c->d_par + (c->cfg.model == LSQR_MODEL_SPHERE ? 0 : M::ND),
-                               sizeof(double) * M::ND, hipMemcpyDeviceToDevice, c->stream));
-    }
+    if (!have_origin && (st = set_fit_origin(c, use_mask ? ORG_MASK : ORG_ALL)) != LSQR_OK) return st;
     if ((st = launch_moments<M>(c, use_mask, 0, c->n, 0, &nmom)) != LSQR_OK) return st;
     }
     {
@@ -2805,27 +2883,6 @@ int launch_mask_moments(lsqr_ctx *c, size_t begin, size_t end, int *nmom, bool *
   c->origin_valid = true;
   *fused = true;
   return LSQR_OK;
-}
-
-// origin of a masked fit as run_fit chooses it: the model's own point (d_par) once a mask exists, the first
-// record for the models whose parameters hold no point
-int set_fit_origin(lsqr_ctx *c, bool from_model) {
-  return dispatch(c->cfg, [&](auto tag) -> int {
-    typedef typename decltype(tag)::type M;
-    if constexpr (M::IS_DENSE || requires { M::IS_PHANTOM; }) {
-      return LSQR_OK;
-    } else {
-      const int off = fit_origin_offset<M>(c->cfg);  // (many.h: lsqr_ransac_many takes the same origin)
-      if (!from_model || off < 0) {
-        HIPCHK(c, hipMemcpyAsync(c->d_vec, c->d_data, sizeof(double) * M::ND, hipMemcpyDeviceToDevice,
-                                 c->stream));
-      } else {
-        HIPCHK(c, hipMemcpyAsync(c->d_vec, c->d_par + off, sizeof(double) * M::ND, hipMemcpyDeviceToDevice,
-                                 c->stream));
-      }
-      return LSQR_OK;
-    }
-  });
 }
 
 // the winner's scan parameters -> d_par, on the device (no host round trip between scan and mask)
@@ -3620,7 +3677,7 @@ static int finish_ransac(lsqr_ctx *c, bool has_best, uint32_t best_votes, double
   HIPCHK(c, hipMemcpyAsync(c->d_par, c->d_best, sizeof(double) * c->HS, hipMemcpyDeviceToDevice, c->stream));
   bool fused = false;
   int nm = 0;
-  if ((st = set_fit_origin(c, true)) != LSQR_OK) return st;
+  if ((st = set_fit_origin(c, ORG_WINNER)) != LSQR_OK) return st;
   if ((st = launch_mask_moments(c, 0, c->n, &nm, &fused)) != LSQR_OK) return st;
   if (!fused && (st = launch_mask(c, 0, c->n)) != LSQR_OK) return st;
   unsigned long long *pin2 = (unsigned long long *)((char *)c->h_pin + 8192);
@@ -3629,7 +3686,7 @@ static int finish_ransac(lsqr_ctx *c, bool has_best, uint32_t best_votes, double
     HIPCHK(c, hipMemcpyAsync(consensus_out, c->d_mask, c->n, hipMemcpyDeviceToHost, c->stream));
   SolveOut out;
   memset(&out, 0, sizeof out);
-  if ((st = run_fit(c, 1, &out, fused)) != LSQR_OK) return st;  // synchronises the stream
+  if ((st = run_fit(c, 1, &out, fused, true)) != LSQR_OK) return st;  // synchronises the stream
   const unsigned long long cnt = pin2[0];
   if (cnt != best_votes)
     return fail(c, LSQR_ERR_HIP, "consensus mask count %llu != scan votes %u", cnt, best_votes);
@@ -3707,6 +3764,7 @@ int lsqr_ransac(lsqr_ctx *c, double p, uint64_t seed, const uint32_t *subsets, s
       // the winner's row stays on the device (the next batch overwrites d_hparams): no host round trip
       HIPCHK(c, hipMemcpyAsync(c->d_best, c->d_hparams + e * c->HS, sizeof(double) * c->HS,
                                hipMemcpyDeviceToDevice, c->stream));
+      c->win_rec = p_sub[e * k];  // its first drawn record: the fit origin of the ORIGIN_FIRST models
     }
     base += used;
     if (used < H) break;
@@ -3829,6 +3887,7 @@ int lsqr_ransac_exhaustive(lsqr_ctx *c, double *params_out, uint8_t *consensus_o
     if (winner >= 0) {
       HIPCHK(c, hipMemcpyAsync(c->d_best, c->d_hparams + (size_t)winner * c->HS, sizeof(double) * c->HS,
                                hipMemcpyDeviceToDevice, c->stream));
+      c->win_rec = sub[(size_t)winner * k];
     }
     index += H;
     info->evaluated += H;
@@ -3855,7 +3914,7 @@ int lsqr_batch_fit(lsqr_ctx *c, uint64_t seed, uint64_t first, size_t H, double 
   HIPCHK(c, hipGetLastError());
   bool fused = false;
   int nm = 0;
-  if ((st = set_fit_origin(c, true)) != LSQR_OK) return st;
+  if ((st = set_fit_origin(c, ORG_WINNER_DEV)) != LSQR_OK) return st;
   if ((st = launch_mask_moments(c, 0, c->n, &nm, &fused)) != LSQR_OK) return st;
   if (!fused && (st = launch_mask(c, 0, c->n)) != LSQR_OK) return st;
   unsigned long long *pin2 = (unsigned long long *)((char *)c->h_pin + 8192);
@@ -3865,7 +3924,7 @@ int lsqr_batch_fit(lsqr_ctx *c, uint64_t seed, uint64_t first, size_t H, double 
     HIPCHK(c, hipMemcpyAsync(consensus_out, c->d_mask, c->n, hipMemcpyDeviceToHost, c->stream));
   SolveOut out;
   memset(&out, 0, sizeof out);
-  if ((st = run_fit(c, 1, &out, fused)) != LSQR_OK) return st;  // synchronises the stream
+  if ((st = run_fit(c, 1, &out, fused, true)) != LSQR_OK) return st;  // synchronises the stream
   const unsigned long long cnt = pin2[0], pk = pin2[1];
   if (info) {
     memset(info, 0, sizeof *info);
@@ -4018,13 +4077,13 @@ int lsqr_batch_fit_enqueue(lsqr_ctx *c, uint64_t seed, uint64_t first, size_t H,
   HIPCHK(c, hipGetLastError());
   bool fused = false;
   int nm = 0;
-  if ((st = set_fit_origin(c, true)) != LSQR_OK) return st;
+  if ((st = set_fit_origin(c, ORG_WINNER_DEV)) != LSQR_OK) return st;
   if ((st = launch_mask_moments(c, 0, c->n, &nm, &fused)) != LSQR_OK) return st;
   if (!fused && (st = launch_mask(c, 0, c->n)) != LSQR_OK) return st;
   char *pin = slot_pin(c, slot);
   HIPCHK(c, hipMemcpyAsync(pin, c->d_counter, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost,
                            c->stream));  // {inliers, packed winner}
-  if ((st = enqueue_fit(c, 1, fused)) != LSQR_OK) return st;
+  if ((st = enqueue_fit(c, 1, fused, true)) != LSQR_OK) return st;
   HIPCHK(c, hipMemcpyAsync(pin + 64, c->d_out, sizeof(SolveOut), hipMemcpyDeviceToHost, c->stream));
   if (!c->slot_ev[slot]) HIPCHK(c, hipEventCreateWithFlags(&c->slot_ev[slot], hipEventDisableTiming));
   HIPCHK(c, hipEventRecord(c->slot_ev[slot], c->stream));

@@ -18,8 +18,8 @@
 //
 // Records: W = lsqr_record_doubles(cfg) doubles each (the context's record width, packed on upload), read through
 // M::load as the single path reads them: absolute orientation's weight slot (W = 7 with ls_type 2), the pivot
-// frame's 12 doubles of 13.  Fit origin: the winner's own point (fit_origin_offset), or -- for the ORIGIN_FIRST
-// models -- the first ND doubles of the problem's first record, as set_fit_origin takes the upload's first record.
+// frame's 12 doubles of 13.  Fit origin: set_fit_origin's rule for a RANSAC finish -- the winner's own point
+// (fit_origin_offset), or for the ORIGIN_FIRST models the first drawn record of the winning minimal subset.
 //
 // Independence: every quantity a problem's result depends on is a function of that problem's records alone: its
 // hypotheses (its own stream), its votes (integer sums), its moment block (parts of kManyPart records in record
@@ -59,7 +59,7 @@ struct ManyTile {   // scan work item: rows [h0, h0 + nh) against records [r0, r
   uint64_t r0, r1;
   uint32_t h0, nh;
 };
-struct ManyPart {   // finish work item: records [r0, r1) of problem j (finishing slot f), whose first record is org
+struct ManyPart {   // finish work item: records [r0, r1) of problem j (finishing slot f); org: its fit origin's record
   uint64_t r0, r1, org;
   uint32_t j, f;
 };
@@ -86,7 +86,8 @@ template <class M> constexpr int many_wmax() { return M::REC > M::ND ? M::REC : 
 template <class M> LSQR_HD int many_width(int W) { return M::REC > M::ND ? W : (int)M::ND; }
 
 // where the fit origin lies in a scan-parameter row (the rule of set_fit_origin): the model's own point -- the
-// sphere's centre, the plane's / line's point --, or -1 for the models whose parameters hold no point (first record)
+// sphere's centre, the plane's / line's point --, or -1 for the models whose parameters hold no point (their origin is
+// the first drawn record of the winning minimal subset)
 template <class M>
 inline int fit_origin_offset(const lsqr_model_cfg &cfg) {
   if constexpr (requires { M::ORIGIN_FIRST; }) return -1;
@@ -188,7 +189,8 @@ __global__ __launch_bounds__(kBlock) void k_many_mask_moments(const double *__re
   constexpr int NC = M::P > M::REC ? M::P : M::REC;
   double cv[NC];
   const int w = many_width<M>(W);
-  // (ORIGIN_FIRST: the problem's first record; both from global memory, so that sp stays in registers)
+  // (ORIGIN_FIRST: the first drawn record of the winning subset; both from global memory, so that sp stays in
+  // registers)
   const double *org = org_off < 0 ? data + pt.org * w : best + (size_t)pt.j * M::SP + org_off;
   for (int k = 0; k < NC; k++) cv[k] = k < M::ND ? org[k] : 0.0;
   uint32_t local = 0;
@@ -573,8 +575,14 @@ int many_run(ManyJob &J) {
     const uint32_t f = (uint32_t)fin.size();
     fin.push_back((uint32_t)j);
     pbeg.push_back((uint32_t)parts.size());
+    uint64_t org = J.offsets[j];  // (unused with org_off >= 0)
+    if (org_off < 0) {  // the winner's first drawn record, as lsqr_ransac reads it from d_subsets
+      uint32_t idx[K], sorted[K];
+      ctr_subset(J.seeds[j], q.rs[RS_BEST_IDX], n, K, idx, sorted);
+      org += idx[0];
+    }
     for (uint64_t r = 0; r < n; r += kManyPart)
-      parts.push_back(ManyPart{J.offsets[j] + r, J.offsets[j] + std::min<uint64_t>(n, r + kManyPart), J.offsets[j],
+      parts.push_back(ManyPart{J.offsets[j] + r, J.offsets[j] + std::min<uint64_t>(n, r + kManyPart), org,
                                (uint32_t)j, f});
   }
   pbeg.push_back((uint32_t)parts.size());

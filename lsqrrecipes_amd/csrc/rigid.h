@@ -142,7 +142,8 @@ struct AbsOrModel {
     frame_from_quaternion(sp[0], sp[1], sp[2], sp[3], false, sp + 7);
     return sqrt(dist_sq(sp, x));
   }
-  // moments about org = (first, second) of the first datum: {sum w, sum w l', sum w r', sum w l' r'^T}
+  // moments about org = (first, second) of one record near the consensus set (set_fit_origin: the first drawn record of
+  // the winning subset): {sum w, sum w l', sum w r', sum w l' r'^T}
   // (AbsoluteOrientation...cxx:133-168 accumulates the same sums un-shifted with w = 1, :223-258 with the
   // caller's weights; multiplying by w = 1.0 is exact, so the unweighted block is unchanged)
   static LSQR_HD void accumulate(const double *x, const double *org, double *m) {
@@ -369,7 +370,8 @@ struct RayModel {
     double dx = sp[0] - p[0] - t * n[0], dy = sp[1] - p[1] - t * n[1], dz = sp[2] - p[2] - t * n[2];
     return sqrt(dx * dx + dy * dy + dz * dz);
   }
-  // RayIntersection...Estimator.cxx:103-127, ray origins taken about org (first ray's origin):
+  // RayIntersection...Estimator.cxx:103-127, ray origins taken about org (the origin of a ray near the consensus set,
+  // set_fit_origin: the first drawn ray of the winning subset):
   //   [N I - sum n n^T] (x - org) = sum (p' - (n.p') n),  p' = p - org
   static LSQR_HD void accumulate(const double *x, const double *org, double *m) {
     const double *n = x + 3;

@@ -225,3 +225,67 @@ def test_argument_errors(ctx):
     with Context(0) as fresh:   # no model set
         st, untouched = _raw(fresh, recs, [0, 100, 300], 0.99, 3)
         assert st == L.ERR_STATE and untouched
+
+
+# ---- edges of the batched path: tile / part / segment tails, N-D models, the caller's budget ---------------------------
+TAIL_SIZES = [255, 256, 257, 8191, 8192, 8193, 16383, 16384, 16385, 32769]  # kManyStage, kManyPart, kManySeg +- 1
+
+
+def test_tile_and_part_tails(ctx):
+    """problems one record either side of the LDS stage (256), the finish part (8192) and the scan segment (16384):
+    all-inlier problems vote n and fit as the oracle fits all records; at 50 % outliers, as the single path"""
+    k = 3
+    sizes = [k, k + 1] + TAIL_SIZES
+    clean = [synth.plane(n, 0.0, seed=40 + j, sigma=0.0)[0] for j, n in enumerate(sizes)]
+    seeds = 3 + np.arange(len(sizes), dtype=np.uint64)
+    res = _set(ctx, L.PLANE, 3).ransac_many(clean, 0.999, seeds=seeds)
+    oc = O.cfg(L.PLANE, 3, DELTA, L.LS_ALGEBRAIC)
+    offs = res["offsets"]
+    for j, n in enumerate(sizes):
+        assert res["status"][j] == L.OK and res["best_votes"][j] == n and res["n_used"][j] == n, (n, res["best_votes"][j])
+        assert np.all(res["consensus"][int(offs[j]):int(offs[j + 1])] == 1), n
+        want = O.ls(oc, clean[j])
+        assert _close(_align(L.PLANE, 3, res["params"][j], want), want, 1e-6), (n, res["params"][j], want)
+    noisy = [synth.plane(n, 0.5, seed=60 + j)[0] for j, n in enumerate(sizes)]
+    res = ctx.ransac_many(noisy, 0.999, seeds=seeds)
+    _check_against_single(ctx, L.PLANE, 3, noisy, k, res, seeds)
+
+
+@pytest.mark.parametrize("dim", [4, 6, 8])
+@pytest.mark.parametrize("model", [L.PLANE, L.SPHERE, L.LINE])
+def test_nd_models(ctx, model, dim):
+    """plane, sphere and line above 3-D (ManyModel<...N<D>>): every problem as the single path, a sample as the
+    oracle"""
+    probs, k = _problems(model, dim, count=24, seed=2)
+    seeds = 9 + np.arange(len(probs), dtype=np.uint64)
+    res = _set(ctx, model, dim).ransac_many(probs, 0.999, seeds=seeds)
+    assert np.sum(res["status"] == L.OK) >= 15, res["status"]
+    _check_against_single(ctx, model, dim, probs, k, res, seeds)
+    oc = O.cfg(model, dim, DELTA, L.LS_ALGEBRAIC)
+    offs = res["offsets"]
+    for j in [j for j in range(len(probs)) if res["status"][j] == L.OK][:3]:
+        w = O.ransac(oc, probs[j], 0.999, sampler="ctr", seed=int(seeds[j]))
+        assert res["iterations"][j] == w["iters"] and res["best_votes"][j] == w["best_votes"], j
+        assert np.array_equal(res["consensus"][int(offs[j]):int(offs[j + 1])], w["consensus"]), j
+        assert _close(_align(model, dim, res["params"][j], w["params"]), w["params"], 1e-6), j
+
+
+@pytest.mark.parametrize("budget", [1, 255, 256, 300, 5000])
+def test_max_iterations_budget(ctx, budget):
+    """the option max_iterations stops each problem where lsqr_ransac stops: iterations, evaluated hypotheses, winner
+    and fit as Context.ransac under the same option"""
+    g = np.random.default_rng(budget)
+    probs = [synth.plane(int(g.integers(50, 3000)), float(g.uniform(0.6, 0.9)), seed=int(g.integers(1 << 30)))[0]
+             for _ in range(12)]
+    seeds = 21 + np.arange(len(probs), dtype=np.uint64)
+    try:
+        ctx.set_option("max_iterations", budget)
+        res = _set(ctx, L.PLANE, 3).ransac_many(probs, 0.999, seeds=seeds)
+        _check_against_single(ctx, L.PLANE, 3, probs, 3, res, seeds)
+        for j, rec in enumerate(probs):
+            _set(ctx, L.PLANE, 3).upload(rec)
+            r = ctx.ransac(0.999, seed=int(seeds[j]))
+            assert res["evaluated"][j] == r["info"].evaluated, j
+    finally:
+        ctx.set_option("max_iterations", 0)
+    assert np.any(res["iterations"] >= min(budget, 256))

@@ -263,3 +263,38 @@ def test_argument_errors(ctx):
         st, untouched = _raw(ctx, np.zeros((300, nd)), [0, 100, 300], 0.99, nd)
         assert st == L.ERR_INVALID and untouched, model
         assert b"lsqr_ransac_many" in ctx._lib.lsqr_last_error(ctx._h)
+
+
+def _strided(ctx, recs, offs, seeds, pad):
+    """lsqr_ransac_many through the C ABI with `pad` extra doubles between records (the strided repack) -> outputs"""
+    n = len(offs) - 1
+    nd = recs.shape[1]
+    wide = np.full((recs.shape[0], nd + pad), np.nan)   # the padding must never be read
+    wide[:, :nd] = recs
+    params = np.zeros((n, ctx.P))
+    cons = np.zeros(int(offs[-1]), dtype=np.uint8)
+    infos = (L.RansacInfo * n)()
+    status = np.zeros(n, dtype=np.int32)
+    offs = np.ascontiguousarray(offs, dtype=np.uint64)
+    st = ctx._lib.lsqr_ransac_many(ctx._h, L.ptr(wide), (nd + pad) * 8, L.ptr(offs), n, 0.999, L.ptr(seeds),
+                                   L.ptr(params), L.ptr(cons), infos, L.ptr(status))
+    assert st == L.OK
+    inf = np.ctypeslib.as_array(infos)
+    return status, params, cons, inf["iterations"].copy(), inf["best_index"].copy(), inf["fit"]["n_used"].copy()
+
+
+@pytest.mark.parametrize("name", ["absor", WEIGHTED, "pivot"])
+def test_strided_records(ctx, name):
+    """records further apart than their width (stride = W*8 + 8, + 24): the same results, bit for bit, as packed"""
+    probs, k, _ = _problems(name, count=30, seed=3, max_n=600)
+    seeds = 7 + np.arange(len(probs), dtype=np.uint64)
+    _set(ctx, name)
+    res = ctx.ransac_many(probs, 0.999, seeds=seeds)
+    recs = np.ascontiguousarray(np.concatenate(probs))
+    for pad in (1, 3):
+        status, params, cons, iters, best, used = _strided(ctx, recs, res["offsets"], seeds, pad)
+        assert np.array_equal(status, res["status"]) and np.array_equal(iters, res["iterations"])
+        assert np.array_equal(best, res["best_index"]) and np.array_equal(used, res["n_used"])
+        assert np.array_equal(cons, res["consensus"])
+        params[status != L.OK] = 0.0
+        assert np.array_equal(params.view(np.uint64), res["params"].view(np.uint64)), pad
