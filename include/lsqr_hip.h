@@ -281,6 +281,33 @@ LSQR_API int lsqr_ransac_many(lsqr_ctx *ctx, const void *host_records, size_t st
                               uint8_t *consensus_out  /* nullable: offsets[n_problems] bytes, record order */,
                               lsqr_ransac_info *infos /* n_problems */,
                               int32_t *status_out     /* n_problems: LSQR_OK / LSQR_EMPTY / LSQR_ERR_INVALID */);
+/* RANSAC<T,S>::compute() with an iterative (Levenberg-Marquardt) final fit, many problems in one call.  Same
+ * arguments and per-problem contract as lsqr_ransac_many; models: the geometric sphere (LSQR_MODEL_SPHERE with
+ * ls_type LSQR_LS_GEOMETRIC), dim 2..8.  Any other model returns LSQR_ERR_INVALID and writes nothing (the closed-form
+ * fits are batched by lsqr_ransac_many).
+ *   Problem j against lsqr_ransac(ctx, p, seeds[j], NULL, 0, ...) on a geometric-sphere context holding its records
+ *     alone: bit-identical status, iterations, best_index, best_votes, fraction, consensus bytes and fit.n_used; the
+ *     parameters and fit.cost agree within the LM tolerances (only the fp64 summation order of the moment blocks
+ *     differs), fit.lm_info, fit.lm_nfev and fit.reserved (stall) are those of the batched LM run.
+ *   LSQR_EMPTY when there is no winner, the algebraic start fails (then fit.lm_info = 0) or the LM run ends with
+ *     fit.lm_info outside 1..4 (then n_params = 0 and the parameters are untouched), as on the single path.
+ *   Independence as for lsqr_ransac_many, carried through the LM: problem j's results, parameters and lm_nfev
+ *     included, are bit-identical whatever the other problems, their order, or "many_round_hypotheses". */
+LSQR_API int lsqr_ransac_many_lm(lsqr_ctx *ctx, const void *host_records, size_t stride_bytes,
+                                 const uint64_t *offsets, size_t n_problems, double p, const uint64_t *seeds,
+                                 double *params_out, uint8_t *consensus_out, lsqr_ransac_info *infos,
+                                 int32_t *status_out);
+/* SphereParametersEstimator::geometricLeastSquaresEstimate over many record sets: set j is records
+ * [offsets[j], offsets[j+1]) (laid out as for lsqr_ransac_many) restricted to masks (nullable: all records;
+ * else offsets[n_sets] bytes, record order), started at x0 + j * lsqr_num_params.  Geometric sphere only, as
+ * lsqr_ransac_many_lm.  Per set, as lsqr_upload + lsqr_set_mask + lsqr_lm_begin / lsqr_lm_step within the LM
+ * tolerances: status_out[j] LSQR_OK (params_out[j * P ..] written) or LSQR_EMPTY (lm_info outside 1..4, parameters
+ * untouched); fits[j] carries n_params, lm_info, lm_nfev, reserved (the stall evaluation, as lsqr_ls_fit), cost and
+ * n_used.  An empty set or mask: LSQR_ERR_INVALID for that set, its parameters and fit untouched.  Argument errors
+ * as lsqr_ransac_many; the context's own upload is not touched; the work runs on the context's stream. */
+LSQR_API int lsqr_lm_fit_many(lsqr_ctx *ctx, const void *host_records, size_t stride_bytes,
+                              const uint64_t *offsets, size_t n_sets, const uint8_t *masks, const double *x0,
+                              double *params_out, lsqr_fit_info *fits, int32_t *status_out);
 /* One fixed-size batch of the same loop without the adaptive stopping rule: hypotheses
  * [first_index, first_index + H) of the sampler stream `seed` are solved and scanned, the first
  * hypothesis with the maximal vote count wins (the strict '>' of RANSAC.hxx:100), its consensus set

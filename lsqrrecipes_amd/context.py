@@ -296,6 +296,77 @@ class Context:
                     n_used=inf["fit"]["n_used"].copy(), params=params,
                     consensus=cons[:total] if cons is not None else None, offsets=offs)
 
+    def _many_records(self, problems):
+        if isinstance(problems, tuple):
+            recs, offs = problems
+            recs = np.ascontiguousarray(recs, dtype=np.float64).reshape(-1, self.ND)
+            offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        else:
+            parts = [np.asarray(a, dtype=np.float64).reshape(-1, self.ND) for a in problems]
+            offs = np.zeros(len(parts) + 1, dtype=np.uint64)
+            offs[1:] = np.cumsum([a.shape[0] for a in parts])
+            recs = np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros((0, self.ND)))
+        return recs, offs
+
+    def ransac_many_lm(self, problems, p, seeds=None, want_consensus=True):
+        """ransac_many with the geometric sphere's Levenberg-Marquardt finish (lsqr_ransac_many_lm); the context's
+        model must be the sphere with ls_type LS_GEOMETRIC, else LsqrError(ERR_INVALID).  Problem j is decided as
+        ransac(p, seed=seeds[j]) on its records alone.  -> ransac_many's dict plus the arrays lm_info, lm_nfev and
+        cost of each problem's final fit."""
+        if self.cfg is None:
+            raise L.LsqrError(L.ERR_STATE, "set_model has not been called")
+        recs, offs = self._many_records(problems)
+        n = len(offs) - 1
+        seeds = (1 + np.arange(n, dtype=np.uint64)) if seeds is None else np.ascontiguousarray(seeds, dtype=np.uint64)
+        if seeds.shape != (n,):
+            raise ValueError("one seed per problem")
+        params = np.zeros((max(n, 1), self.P))
+        total = int(offs[-1]) if n else 0
+        cons = np.zeros(max(total, 1), dtype=np.uint8) if want_consensus else None
+        infos = (L.RansacInfo * max(n, 1))()
+        status = np.zeros(max(n, 1), dtype=np.int32)
+        self._chk(self._lib.lsqr_ransac_many_lm(self._h, L.ptr(recs), self.ND * 8, L.ptr(offs), n, float(p),
+                                                L.ptr(seeds), L.ptr(params), L.ptr(cons), infos, L.ptr(status)))
+        status, params = status[:n], params[:n]
+        params[status != L.OK] = 0.0
+        inf = np.ctypeslib.as_array(infos)[:n]
+        f = lambda name: inf[name].copy()
+        fit = inf["fit"]
+        return dict(status=status, fraction=f("fraction"), iterations=f("iterations"), best_index=f("best_index"),
+                    best_votes=f("best_votes"), evaluated=f("evaluated"), n_params=f("n_params"),
+                    n_used=fit["n_used"].copy(), lm_info=fit["lm_info"].copy(), lm_nfev=fit["lm_nfev"].copy(),
+                    cost=fit["cost"].copy(), params=params,
+                    consensus=cons[:total] if cons is not None else None, offsets=offs)
+
+    def lm_fit_many(self, problems, x0, masks=None):
+        """The geometric sphere fit (SphereParametersEstimator::geometricLeastSquaresEstimate) of many record sets
+        in one call (lsqr_lm_fit_many).  problems as for ransac_many; x0: one start per set (n x P); masks
+        (optional): one byte per record, aligned with the flat records.  -> dict of arrays: status (OK / EMPTY /
+        ERR_INVALID for an empty set or mask), params (n x P, zero rows where status is not OK), lm_info, lm_nfev,
+        cost and n_used."""
+        if self.cfg is None:
+            raise L.LsqrError(L.ERR_STATE, "set_model has not been called")
+        recs, offs = self._many_records(problems)
+        n = len(offs) - 1
+        x0 = np.ascontiguousarray(x0, dtype=np.float64).reshape(-1, self.P)
+        if x0.shape[0] != n:
+            raise ValueError("one start per set")
+        m = None
+        if masks is not None:
+            m = np.ascontiguousarray(masks, dtype=np.uint8).reshape(-1)
+            if m.shape[0] != int(offs[-1]):
+                raise ValueError("one mask byte per record")
+        params = np.zeros((max(n, 1), self.P))
+        fits = (L.FitInfo * max(n, 1))()
+        status = np.zeros(max(n, 1), dtype=np.int32)
+        self._chk(self._lib.lsqr_lm_fit_many(self._h, L.ptr(recs), self.ND * 8, L.ptr(offs), n, L.ptr(m),
+                                             L.ptr(x0), L.ptr(params), fits, L.ptr(status)))
+        status, params = status[:n], params[:n]
+        params[status != L.OK] = 0.0
+        fi = np.ctypeslib.as_array(fits)[:n]
+        return dict(status=status, params=params, lm_info=fi["lm_info"].copy(), lm_nfev=fi["lm_nfev"].copy(),
+                    cost=fi["cost"].copy(), n_used=fi["n_used"].copy())
+
     def batch_fit(self, seed, first, H, want_consensus=False):
         """One fixed-size batch end to end on the device (lsqr_batch_fit): winner of hypotheses
         [first, first + H) of the sampler stream, its consensus set, the final fit."""

@@ -3839,6 +3839,101 @@ int lsqr_ransac_many(lsqr_ctx *c, const void *host_records, size_t stride_bytes,
   return LSQR_OK;
 }
 
+// ---- the same with the geometric sphere's Levenberg-Marquardt finish (many.h + many_lm.h) ----------------------------
+// the checks lsqr_ransac_many makes of its record arguments (after its own of the model and the outputs)
+static int many_check_records(lsqr_ctx *c, const char *fn, const void *host_records, size_t stride_bytes,
+                              const uint64_t *offsets, size_t n) {
+  if (offsets[0] != 0) return fail(c, LSQR_ERR_INVALID, "%s: offsets[0] must be 0", fn);
+  for (size_t j = 0; j < n; j++) {
+    if (offsets[j + 1] < offsets[j]) return fail(c, LSQR_ERR_INVALID, "%s: offsets decrease at %zu", fn, j);
+    if (offsets[j + 1] - offsets[j] > 0xFFFFFFF0ull)
+      return fail(c, LSQR_ERR_INVALID, "%s: problem %zu has more than 2^32 - 16 records", fn, j);
+  }
+  if (offsets[n] > 0 && !host_records) return fail(c, LSQR_ERR_INVALID, "%s: null records", fn);
+  if (stride_bytes < sizeof(double) * (size_t)c->ND)
+    return fail(c, LSQR_ERR_INVALID, "%s: stride %zu below the record's %zu bytes", fn, stride_bytes,
+                sizeof(double) * (size_t)c->ND);
+  return LSQR_OK;
+}
+
+static void many_job_lm(lsqr_ctx *c, ManyJob &J, const void *host_records, size_t stride_bytes,
+                        const uint64_t *offsets, size_t n) {
+  if (!c->many) c->many = new ManyBufs();
+  J.stream = c->stream;
+  J.cfg = c->cfg;
+  J.mc = c->mc;
+  J.host = (const char *)host_records;
+  J.stride = stride_bytes;
+  J.offsets = offsets;
+  J.n = n;
+  J.W = c->ND;
+  J.max_iter = c->opt_max_iter;
+  J.round_cap = c->opt_many_round > 0 ? (size_t)c->opt_many_round : kManyRoundDefault;
+  J.buf = c->many;
+  J.err[0] = 0;
+  J.lm = true;
+  lm_settings(c->cfg, &J.lm_n, &J.lm_ftol, &J.lm_xtol, &J.lm_gtol, &J.lm_maxfev);
+}
+
+int lsqr_ransac_many_lm(lsqr_ctx *c, const void *host_records, size_t stride_bytes, const uint64_t *offsets,
+                        size_t n_problems, double p, const uint64_t *seeds, double *params_out,
+                        uint8_t *consensus_out, lsqr_ransac_info *infos, int32_t *status_out) {
+  int st = need_ready(c, false);
+  if (st != LSQR_OK) return st;
+  if (c->cfg.model != LSQR_MODEL_SPHERE || c->cfg.ls_type != LSQR_LS_GEOMETRIC)
+    return fail(c, LSQR_ERR_INVALID,
+                "lsqr_ransac_many_lm: the geometric sphere only (model %d, ls_type %d); the closed-form fits are "
+                "batched by lsqr_ransac_many", c->cfg.model, c->cfg.ls_type);
+  if (n_problems == 0) return LSQR_OK;
+  if (!offsets || !seeds || !params_out || !infos || !status_out)
+    return fail(c, LSQR_ERR_INVALID, "lsqr_ransac_many_lm: null argument");
+  if (!(p > 0.0) || !(p < 1.0)) return fail(c, LSQR_ERR_INVALID, "lsqr_ransac_many_lm: p must lie in (0, 1)");
+  if ((st = many_check_records(c, "lsqr_ransac_many_lm", host_records, stride_bytes, offsets, n_problems)) != LSQR_OK)
+    return st;
+  ManyJob J;
+  many_job_lm(c, J, host_records, stride_bytes, offsets, n_problems);
+  J.p = p;
+  J.seeds = seeds;
+  J.params_out = params_out;
+  J.consensus_out = consensus_out;
+  J.infos = infos;
+  J.status_out = status_out;
+  st = dispatch(c->cfg, [&](auto tag) -> int {
+    typedef typename decltype(tag)::type M;
+    if constexpr (ManyModel<M>::value && requires { M::NMOM_LM; }) return many_run<M>(J);
+    else return LSQR_ERR_INVALID;
+  });
+  if (st != LSQR_OK) return fail(c, st, "lsqr_ransac_many_lm: %s", J.err[0] ? J.err : "model not in this build");
+  return LSQR_OK;
+}
+
+int lsqr_lm_fit_many(lsqr_ctx *c, const void *host_records, size_t stride_bytes, const uint64_t *offsets,
+                     size_t n_sets, const uint8_t *masks, const double *x0, double *params_out, lsqr_fit_info *fits,
+                     int32_t *status_out) {
+  int st = need_ready(c, false);
+  if (st != LSQR_OK) return st;
+  if (c->cfg.model != LSQR_MODEL_SPHERE || c->cfg.ls_type != LSQR_LS_GEOMETRIC)
+    return fail(c, LSQR_ERR_INVALID,
+                "lsqr_lm_fit_many: the geometric sphere only (model %d, ls_type %d); the closed-form fits of many "
+                "problems are batched by lsqr_ransac_many", c->cfg.model, c->cfg.ls_type);
+  if (n_sets == 0) return LSQR_OK;
+  if (!offsets || !x0 || !params_out || !fits || !status_out)
+    return fail(c, LSQR_ERR_INVALID, "lsqr_lm_fit_many: null argument");
+  if ((st = many_check_records(c, "lsqr_lm_fit_many", host_records, stride_bytes, offsets, n_sets)) != LSQR_OK)
+    return st;
+  ManyJob J;
+  many_job_lm(c, J, host_records, stride_bytes, offsets, n_sets);
+  J.params_out = params_out;
+  J.status_out = status_out;
+  st = dispatch(c->cfg, [&](auto tag) -> int {
+    typedef typename decltype(tag)::type M;
+    if constexpr (ManyModel<M>::value && requires { M::NMOM_LM; }) return many_lm_fit<M>(J, masks, x0, fits);
+    else return LSQR_ERR_INVALID;
+  });
+  if (st != LSQR_OK) return fail(c, st, "lsqr_lm_fit_many: %s", J.err[0] ? J.err : "model not in this build");
+  return LSQR_OK;
+}
+
 int lsqr_ransac_exhaustive(lsqr_ctx *c, double *params_out, uint8_t *consensus_out,
                            lsqr_ransac_info *info) {
   lsqr_ransac_info local;

@@ -47,6 +47,11 @@ constexpr int kManyStage = 256;            // records per LDS stage (8-D: 16 KiB
 constexpr uint64_t kManySeg = 16384;       // records per scan tile: longer problems are split, votes summed exactly
 constexpr uint64_t kManyPart = 8192;       // records per workgroup of the finish (fixes the moment sums' order)
 constexpr size_t kManyRoundDefault = 1u << 21;  // hypotheses per round (option many_round_hypotheses = 0)
+}  // namespace lsqr
+
+#include "many_lm.h"  // the LM stage of lsqr_ransac_many_lm (its parts are kManyPart inliers)
+
+namespace lsqr {
 
 struct ManyItem {   // one problem's batch in a round
   uint64_t rec;     // first record of the problem in the packed upload
@@ -266,6 +271,7 @@ struct ManyBufs {
          c_mask = 0, c_votes = 0, c_pairs = 0, c_pbeg = 0, c_fin = 0, c_counts = 0, c_out = 0;
   char *h_stage = nullptr, *h_pairs = nullptr;  // pinned: the round's tables and results / the winner pairs
   size_t c_stage = 0, c_hpairs = 0;
+  ManyLmBufs lm;  // the LM stage of lsqr_ransac_many_lm / lsqr_lm_fit_many (many_lm.h)
 };
 
 #if defined(__HIPCC__)
@@ -277,6 +283,7 @@ inline void many_free(ManyBufs *b) {
     if (p) (void)hipFree(p);
   if (b->h_stage) (void)hipHostFree(b->h_stage);
   if (b->h_pairs) (void)hipHostFree(b->h_pairs);
+  many_lm_free(b->lm);
   delete b;
 }
 
@@ -320,6 +327,9 @@ struct ManyJob {
   int32_t *status_out;
   long long max_iter;  // option max_iterations
   size_t round_cap;    // hypotheses per round (a problem whose batch alone exceeds it gets a round of its own)
+  bool lm = false;     // lsqr_ransac_many_lm: the geometric sphere's LM fit from the algebraic one (many_lm.h)
+  int lm_n = 0, lm_maxfev = 0;  // ... with lm_settings
+  double lm_ftol = 0, lm_xtol = 0, lm_gtol = 0;
   ManyBufs *buf;
   char err[256];
 };
@@ -333,6 +343,23 @@ struct ManyJob {
       return LSQR_ERR_HIP;                                                                           \
     }                                                                                                \
   } while (0)
+
+// one upload of every problem's records, packed (W doubles per record, copied as raw bytes: the pivot frame's int slot
+// travels as it is); `packed` holds the staging copy of strided records until the copy has been issued
+inline int many_upload(ManyJob &J, int W, uint64_t NT, std::vector<double> &packed) {
+  ManyBufs &B = *J.buf;
+  const double *src = (const double *)J.host;
+  if (NT > 0) {
+    MANYCHK(many_grow(&B.d_data, &B.c_data, NT * W));
+    if (J.stride != sizeof(double) * W) {
+      packed.resize(NT * W);
+      for (uint64_t i = 0; i < NT; i++) memcpy(&packed[i * W], J.host + i * J.stride, sizeof(double) * W);
+      src = packed.data();
+    }
+    MANYCHK(hipMemcpyAsync(B.d_data, src, sizeof(double) * W * NT, hipMemcpyHostToDevice, J.stream));
+  }
+  return LSQR_OK;
+}
 
 // the per-problem state of lsqr_ransac's loop
 struct ManyProb {
@@ -395,6 +422,7 @@ int many_run(ManyJob &J) {
   const uint64_t NT = J.offsets[NP];
   const int org_off = fit_origin_offset<M>(J.cfg);
   static_assert(M::NMOM <= 64, "one lane per moment in k_many_solve");
+  int st0;
 
   std::vector<ManyProb> pr(NP);
   for (size_t j = 0; j < NP; j++) {
@@ -412,19 +440,8 @@ int many_run(ManyJob &J) {
     snprintf(J.err, sizeof J.err, "record width %d != the model's %d doubles", J.W, W);
     return LSQR_ERR_INVALID;
   }
-  // one upload of every problem's records, packed (W doubles per record, copied as raw bytes: the pivot frame's
-  // int slot travels as it is)
   std::vector<double> packed;
-  const double *src = (const double *)J.host;
-  if (NT > 0) {
-    MANYCHK(many_grow(&B.d_data, &B.c_data, NT * W));
-    if (J.stride != sizeof(double) * W) {
-      packed.resize(NT * W);
-      for (uint64_t i = 0; i < NT; i++) memcpy(&packed[i * W], J.host + i * J.stride, sizeof(double) * W);
-      src = packed.data();
-    }
-    MANYCHK(hipMemcpyAsync(B.d_data, src, sizeof(double) * W * NT, hipMemcpyHostToDevice, J.stream));
-  }
+  if ((st0 = many_upload(J, W, NT, packed)) != LSQR_OK) return st0;
   MANYCHK(many_grow(&B.d_best, &B.c_best, std::max<size_t>(NP, 1) * SP));
 
   const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
@@ -630,12 +647,57 @@ int many_run(ManyJob &J) {
     }
   }
   const int P = M::P;
+  // lsqr_ransac_many_lm: the LM fit of every consensus set whose algebraic fit succeeded, started there
+  // (run_fit: Sphere...hxx:231-232 -- a failed algebraic fit is the empty result)
+  std::vector<int> lm_of(J.lm ? NF : 0, -1);
+  std::vector<ManyLmOut> lm_res;
+  if constexpr (requires { M::NMOM_LM; }) {
+    if (J.lm) {
+      std::vector<ManyLmProb> lp;
+      for (size_t f = 0; f < NF; f++) {
+        if (!outs[f].ok) continue;
+        const uint32_t j = fin[f];
+        lm_of[f] = (int)lp.size();
+        ManyLmProb q{};
+        q.rec = J.offsets[j];
+        q.n = J.offsets[j + 1] - J.offsets[j];
+        q.cnt = counts[f];
+        q.xsrc = (uint32_t)f;
+        lp.push_back(q);
+      }
+      ManyLmJob L;
+      L.stream = J.stream;
+      L.d_data = B.d_data;
+      L.d_mask = B.d_mask;
+      L.d_x0 = (const double *)((const char *)B.d_out + offsetof(SolveOut, params));
+      L.x0_stride = sizeof(SolveOut) / sizeof(double);
+      L.n = J.lm_n;
+      L.maxfev = J.lm_maxfev;
+      L.ftol = J.lm_ftol;
+      L.xtol = J.lm_xtol;
+      L.gtol = J.lm_gtol;
+      L.buf = &B.lm;
+      L.err = J.err;
+      L.err_len = sizeof J.err;
+      if ((st0 = many_lm_run<M>(L, lp, lm_res)) != LSQR_OK) return st0;
+    }
+  }
   std::vector<uint8_t> has_mask(NP, 0);
   for (size_t f = 0; f < NF; f++) {
     const uint32_t j = fin[f];
-    const SolveOut &o = outs[f];
+    SolveOut o = outs[f];
     lsqr_ransac_info &info = J.infos[j];
     has_mask[j] = 1;
+    if (J.lm && lm_of[f] >= 0) {  // finish_ransac after run_fit's LM branch
+      const ManyLmOut &r = lm_res[lm_of[f]];
+      o.ok = r.ok;
+      o.n_params = r.n_params;
+      info.fit.lm_info = r.lm_info;
+      info.fit.lm_nfev = r.lm_nfev;
+      info.fit.reserved = r.stall;
+      o.cost = r.cost;
+      for (int k = 0; k < P; k++) o.params[k] = r.params[k];
+    }
     info.fit.n_params = o.ok ? o.n_params : 0;
     info.fit.n_used = counts[f];
     info.fit.cost = o.cost;
@@ -651,6 +713,87 @@ int many_run(ManyJob &J) {
     for (size_t j = 0; j < NP; j++)
       if (!has_mask[j] && J.offsets[j + 1] > J.offsets[j])
         memset(J.consensus_out + J.offsets[j], 0, J.offsets[j + 1] - J.offsets[j]);
+  return LSQR_OK;
+}
+
+// lsqr_lm_fit_many: set j = records [offsets[j], offsets[j+1]) where masks (nullable: every record) is set, fitted
+// by the LM stage from x0 + j * P; the single-set path's result (lsqr_lm_begin / lsqr_lm_step)
+template <class M>
+int many_lm_fit(ManyJob &J, const uint8_t *masks, const double *x0, lsqr_fit_info *fits) {
+  constexpr int P = M::P;
+  const int W = many_width<M>(J.W);
+  ManyBufs &B = *J.buf;
+  const size_t NS = J.n;
+  const uint64_t NT = J.offsets[NS];
+  if (W != J.W) {
+    snprintf(J.err, sizeof J.err, "record width %d != the model's %d doubles", J.W, W);
+    return LSQR_ERR_INVALID;
+  }
+  std::vector<ManyLmProb> lp;
+  std::vector<uint32_t> set_of;
+  for (size_t j = 0; j < NS; j++) {
+    const uint64_t r0 = J.offsets[j], r1 = J.offsets[j + 1];
+    uint64_t cnt = r1 - r0;
+    if (masks) {
+      cnt = 0;
+      for (uint64_t i = r0; i < r1; i++) cnt += masks[i] != 0;
+    }
+    if (cnt == 0) {  // nothing to fit: outputs untouched
+      J.status_out[j] = LSQR_ERR_INVALID;
+      continue;
+    }
+    ManyLmProb q{};
+    q.rec = r0;
+    q.n = r1 - r0;
+    q.cnt = cnt;
+    q.xsrc = (uint32_t)j;
+    lp.push_back(q);
+    set_of.push_back((uint32_t)j);
+  }
+  if (lp.empty()) return LSQR_OK;
+  std::vector<double> packed;
+  int st;
+  if ((st = many_upload(J, W, NT, packed)) != LSQR_OK) return st;
+  if (masks) {
+    MANYCHK(many_grow(&B.d_mask, &B.c_mask, NT));
+    MANYCHK(hipMemcpyAsync(B.d_mask, masks, NT, hipMemcpyHostToDevice, J.stream));
+  }
+  MANYCHK(many_grow(&B.d_best, &B.c_best, NS * P));  // the starts (no RANSAC rounds run here)
+  MANYCHK(hipMemcpyAsync(B.d_best, x0, sizeof(double) * NS * P, hipMemcpyHostToDevice, J.stream));
+  ManyLmJob L;
+  L.stream = J.stream;
+  L.d_data = B.d_data;
+  L.d_mask = masks ? B.d_mask : nullptr;
+  L.d_x0 = B.d_best;
+  L.x0_stride = P;
+  L.n = J.lm_n;
+  L.maxfev = J.lm_maxfev;
+  L.ftol = J.lm_ftol;
+  L.xtol = J.lm_xtol;
+  L.gtol = J.lm_gtol;
+  L.buf = &B.lm;
+  L.err = J.err;
+  L.err_len = sizeof J.err;
+  std::vector<ManyLmOut> res;
+  if ((st = many_lm_run<M>(L, lp, res)) != LSQR_OK) return st;
+  for (size_t q = 0; q < lp.size(); q++) {
+    const uint32_t j = set_of[q];
+    const ManyLmOut &r = res[q];
+    lsqr_fit_info &fi = fits[j];
+    memset(&fi, 0, sizeof fi);
+    fi.n_params = r.n_params;
+    fi.lm_info = r.lm_info;
+    fi.lm_nfev = r.lm_nfev;
+    fi.reserved = r.stall;
+    fi.n_used = lp[q].cnt;
+    fi.cost = r.cost;
+    if (!r.ok) {  // lsqr_lm_step: a failed run hands out no parameters
+      J.status_out[j] = LSQR_EMPTY;
+      continue;
+    }
+    for (int k = 0; k < r.n_params; k++) J.params_out[(size_t)j * P + k] = r.params[k];
+    J.status_out[j] = LSQR_OK;
+  }
   return LSQR_OK;
 }
 #undef MANYCHK

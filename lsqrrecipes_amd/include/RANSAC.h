@@ -115,8 +115,10 @@ class RANSAC {
   // compute(): invalid input returns 0 and leaves parameters[j] untouched, a search that finds nothing clears it.
   // Plane, line, algebraic sphere, absolute orientation, pivot calibration, ray intersection and the 2-D line run in
   // ONE device call (lsqr_ransac_many: one upload, batched rounds, one finish; the records are packed sizeof(T)
-  // apart, as compute() uploads them); estimators without a device model loop over the plugin path, other device
-  // estimators (dense system, US calibrations, plane phantom, geometric sphere) over compute(), with the same seeds.
+  // apart, as compute() uploads them); the geometric sphere (SphereParametersEstimator's default) runs in one
+  // lsqr_ransac_many_lm call, its LM finish batched on the device too.  Estimators without a device model loop over
+  // the plugin path, other device estimators (dense system, US calibrations, plane phantom) over compute(), with the
+  // same seeds.
   // Under LSQR_DEVICES the batched call runs on the first listed device's context (problems are not sharded over
   // devices).  lastInfo() is not updated.
   static std::vector<double> computeMany(std::vector<std::vector<S> > &parameters,
@@ -132,8 +134,10 @@ class RANSAC {
     if (n == 0 || p >= 1.0 || p <= 0.0) return fraction;  // RANSAC.hxx:16-19 for every problem
     lsqr_model_cfg cfg;
     const bool device = paramEstimator->deviceModel(cfg) && !forceHostLoop();
+    // the geometric sphere's LM finish: lsqr_ransac_many_lm; the closed-form fits: lsqr_ransac_many
+    const bool lm = device && cfg.model == LSQR_MODEL_SPHERE && cfg.ls_type == LSQR_LS_GEOMETRIC;
     const bool batched = device && (cfg.model == LSQR_MODEL_PLANE || cfg.model == LSQR_MODEL_LINE ||
-                                    (cfg.model == LSQR_MODEL_SPHERE && cfg.ls_type == LSQR_LS_ALGEBRAIC) ||
+                                    cfg.model == LSQR_MODEL_SPHERE ||
                                     cfg.model == LSQR_MODEL_ABSOR || cfg.model == LSQR_MODEL_PIVOT ||
                                     cfg.model == LSQR_MODEL_RAY || cfg.model == LSQR_MODEL_LINE2D);
     if (!batched) {
@@ -164,8 +168,9 @@ class RANSAC {
     std::vector<uint8_t> cons(consensusSets ? (size_t)offsets[n] : 0);
     std::vector<lsqr_ransac_info> info(n);
     std::vector<int32_t> status(n);
-    d.check(lsqr_ransac_many(ctx, records.empty() ? NULL : &records[0], sizeof(T), &offsets[0], n, p, &seeds[0],
-                             &par[0], cons.empty() ? NULL : &cons[0], &info[0], &status[0]));
+    d.check((lm ? lsqr_ransac_many_lm : lsqr_ransac_many)(ctx, records.empty() ? NULL : &records[0], sizeof(T),
+                                                          &offsets[0], n, p, &seeds[0], &par[0],
+                                                          cons.empty() ? NULL : &cons[0], &info[0], &status[0]));
     for (size_t j = 0; j < n; j++) {
       if (status[j] == LSQR_ERR_INVALID) continue;  // fewer records than a minimal subset: untouched, 0
       parameters[j].clear();  // RANSAC.hxx:43

@@ -11,6 +11,10 @@ are skipped when no point shape is listed):
   absor       10 000 problems x     20 pairs,  70 % inliers (unweighted)
   pivot        1 000 problems x    300 frames, 70 % inliers
   line2d     100 000 problems x    200 points, 50 % inliers
+and the geometric (Levenberg-Marquardt) sphere, Context.ransac_many_lm against the loop on a geometric context
+(--shapes geometric: both):
+  sphere_lm         1 000 problems x 10 000 records, 50 % inliers
+  sphere_lm_small  10 000 problems x    300 records, 50 % inliers
 Each row also gives the loop's time per problem (loop_ms_per_problem).  Every timed call
 ends in a device synchronisation (both entry points return host results); each shape is warmed first; the two
 paths alternate in one process.  --quick: one repetition, small loop (for a kernel-trace run under rocprofv3).
@@ -102,6 +106,7 @@ POINT_SHAPES = {"plane": (L.PLANE, 10_000, 1_000), "sphere": (L.SPHERE, 1_000, 1
 # name -> (model, problems, records, inlier share, delta, aux)
 RIGID_SHAPES = {"rays": (L.RAY, 100_000, 12, 0.7, 1.0, np.pi / 180), "absor": (L.ABSOR, 10_000, 20, 0.7, 1.0, 0.0),
                 "pivot": (L.PIVOT, 1_000, 300, 0.7, 1.0, 0.0), "line2d": (L.LINE2D, 100_000, 200, 0.5, 0.5, 0.0)}
+GEOMETRIC_SHAPES = {"sphere_lm": (1_000, 10_000), "sphere_lm_small": (10_000, 300)}
 
 
 def timed(f, reps):
@@ -121,28 +126,34 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--out", default=None, help="also write the results as one JSON file")
     ap.add_argument("--shapes", default="plane,sphere,line",
-                    help="comma-separated shapes (%s), or 'rigid' for the last four" % ", ".join(
-                        list(POINT_SHAPES) + list(RIGID_SHAPES)))
+                    help="comma-separated shapes (%s), or 'rigid' / 'geometric' for the closed-form estimators' / "
+                         "the LM sphere's" % ", ".join(list(POINT_SHAPES) + list(RIGID_SHAPES) + list(GEOMETRIC_SHAPES)))
     a = ap.parse_args()
-    names = list(RIGID_SHAPES) if a.shapes == "rigid" else a.shapes.split(",")
+    names = {"rigid": list(RIGID_SHAPES), "geometric": list(GEOMETRIC_SHAPES)}.get(a.shapes, a.shapes.split(","))
     for name in names:
-        if name not in POINT_SHAPES and name not in RIGID_SHAPES:
+        if name not in POINT_SHAPES and name not in RIGID_SHAPES and name not in GEOMETRIC_SHAPES:
             ap.error("unknown shape %r" % name)
     reps = 1 if a.quick else a.reps
     loop_n = 100 if a.quick else a.loop
     ctx = Context(0)
     out = dict(shapes=[], latency=[])
     for name in names:
+        batched = ctx.ransac_many
         if name in POINT_SHAPES:
             model, P, N = POINT_SHAPES[name]
             recs, offs = gen(model, P, N, 0.5, seed=model)
             ctx.set_model(model, 3, 0.5, L.LS_ALGEBRAIC)
+        elif name in GEOMETRIC_SHAPES:
+            model, (P, N) = L.SPHERE, GEOMETRIC_SHAPES[name]
+            recs, offs = gen(model, P, N, 0.5, seed=model + N)
+            ctx.set_model(model, 3, 0.5, L.LS_GEOMETRIC)
+            batched = ctx.ransac_many_lm
         else:
             model, P, N, inl, delta, aux = RIGID_SHAPES[name]
             recs, offs = gen_rigid(name, P, N, inl, seed=model)
             ctx.set_model(model, 2 if model == L.LINE2D else 3, delta, 0, aux=aux)
         seeds = 1 + np.arange(P, dtype=np.uint64)
-        many = lambda: ctx.ransac_many((recs, offs), 0.999, seeds=seeds)
+        many = lambda: batched((recs, offs), 0.999, seeds=seeds)
         m = min(loop_n, P)
 
         def loop():
