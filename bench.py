@@ -13,12 +13,18 @@
                                 maximum are not counted to the end (scan_bound 1: cell-box vote bounds for the point
                                 models, chunked abandonment for the dense / US scans).  Winner, consensus set and fit are
                                 identical (tests/test_gpu_fullsize.py); the rate depends on the data.
-           Each rate has its own roofline block (roofline / roofline_early_exit).
+           With --full each rate has its own roofline block (roofline / roofline_early_exit).
   repeats  every rate is timed over --repeats regions of exactly K steps (barrier + synchronise on both sides, max over
            ranks); `value` is the median region, all regions are listed.
-  legs     the default single-GPU run appends legs (20 steps after 5, one timed region) of BASELINE configs 3-5 -- sphere +
-           geometric fit, dense 2 M x 64, US calibration with the iterative and the analytic fit -- and of the plane phantom
-            as other_configs[].
+  plain    a run without --full does what the headline needs and nothing else: set up, prime, warm up, the timed
+           regions of both rates, --dump-outputs, the line.  Its `value`, `ms_per_step` and dumped outputs are those of
+           the same run with --full.
+  --full   adds what takes runs of its own or is measured beside the headline: the one-stream pass and the roofline
+           block of each rate, the per-kernel tables, the index rebuild, RANSAC::compute() end to end and cold, the CPU
+           baselines, and the legs below.
+  legs     the --full single-GPU plane run appends legs (20 steps after 5, one timed region) of BASELINE configs 3-5 --
+           sphere + geometric fit, dense 2 M x 64, US calibration with the iterative and the analytic fit -- and of the
+           plane phantom as other_configs[].
   N > 1    one process per GPU (torch.distributed, RCCL): observations replicated, the hypothesis stream sharded;
            all-reduce(MAX) picks the winner, all-reduce(SUM) of the moment block of each rank's observation slice gives
            the final fit.  scaling = "weak" (H per GPU fixed).  `python bench.py --gpus N` without a launcher
@@ -30,6 +36,7 @@
            files: inputs and hypothesis stream are seeded, so two builds run with the same arguments compare exactly.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--points P] [--batch H] [--workload plane] [--dump-outputs DIR]
+                  [--full]
 """
 import argparse
 import json
@@ -92,7 +99,7 @@ def parse(argv=None):
     ap.add_argument("--no-filter", action="store_true", help="plain fp64 scan (no fp32 pre-filter)")
     ap.add_argument("--no-index", action="store_true", help="exhaustive scan (no spatial index)")
     ap.add_argument("--outliers", type=float, default=0.5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
     ap.add_argument("--us-fit", default="iterative", choices=["iterative", "analytic"],
                     help="final fit of the US workload: Levenberg-Marquardt with the reference's settings (BASELINE "
                          "config 5 as written: tolerances 1e-15, 5000 evaluations -- at 1 M frames MINPACK uses all "
@@ -106,20 +113,20 @@ def parse(argv=None):
     ap.add_argument("--no-pipeline", action="store_true",
                     help="single GPU: one blocking lsqr_batch_fit per step instead of pipelined batches")
     ap.add_argument("--no-end-to-end", action="store_true",
-                    help="skip the adaptive RANSAC::compute() timing after the steps (profiling runs: "
+                    help="--full: skip the adaptive RANSAC::compute() timing after the steps (profiling runs: "
                          "keeps one launch shape per kernel)")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the short legs of BASELINE configs 3-5 appended to the default plane run")
+                    help="--full: skip the short legs of BASELINE configs 3-5 appended to the plane run")
     ap.add_argument("--rates", default="both", choices=["both", "full", "early"],
                     help="which hypothesis rates to time (profiling runs: one, so that one scan arrangement runs)")
     ap.add_argument("--transport", default="rccl", choices=["rccl", "multi"],
                     help="--gpus N > 1: rccl = one process per GPU (torch.distributed), multi = this one process "
                          "drives the N devices through lsqr_multi_* (peer copies)")
-    ap.add_argument("--cpu-points", type=int, default=0, help="observations for the CPU leg "
+    ap.add_argument("--cpu-points", type=int, default=0, help="--full: observations for the CPU leg "
                     "(0 = same as --points)")
-    ap.add_argument("--leg-scale", type=float, default=1.0, help="scale the observation counts of the other_configs "
-                    "legs (tests; 1 = the BASELINE sizes)")
-    ap.add_argument("--cpu-seconds", type=float, default=0.0, help="budget of the CPU full-count sample "
+    ap.add_argument("--leg-scale", type=float, default=1.0, help="--full: scale the observation counts of the "
+                    "other_configs legs (tests; 1 = the BASELINE sizes)")
+    ap.add_argument("--cpu-seconds", type=float, default=0.0, help="--full: budget of the CPU full-count sample "
                     "(0 = 4 s for the headline, 3 s per leg)")
     ap.add_argument("--option", action="append", default=[], metavar="NAME=VALUE",
                     help="lsqr_set_option on every context of the run (A/B runs: scan_refine=0, scan_pairs=2, ...)")
@@ -134,6 +141,11 @@ def parse(argv=None):
                     help="after the timed steps, write what the last timed step of each rate returned to its caller "
                          "(final fit, winner record) as DIR/<rate>_params.npy and DIR/<rate>_winner.npy (float64), so "
                          "that two builds can be compared output for output on the same seeded inputs")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: the one-stream pass and roofline block of each rate, the "
+                         "per-kernel tables, the index rebuild, RANSAC::compute() end to end and cold, the CPU "
+                         "baselines and (plane, one GPU) the legs of the other configs.  Without it a run sets up, "
+                         "warms up, times the steps, writes --dump-outputs and prints the line")
     a = ap.parse_args(argv)
     if a.steps < 1:
         ap.error("--steps must be at least 1")
@@ -772,8 +784,8 @@ class Run:
         self.cur_streams = 1 if on else self.a.streams
 
     def measure(self, mode, bound):
-        """one hypothesis rate: prime, warm up, `repeats` timed regions, then the same chain on ONE stream for the
-        per-kernel figures"""
+        """one hypothesis rate: prime, warm up, `repeats` timed regions; --full: then the same chain on ONE stream for
+        the per-kernel figures, and the roofline block"""
         a, ctx, H = self.a, self.ctx, self.H
         if bound is not None:
             self.set_option("scan_bound", bound)
@@ -800,7 +812,7 @@ class Run:
         prof_steps = a.steps * max(1, a.repeats)      # steps the profile above covers
         ctx.profile(False)
         single_stream = None
-        if self.multi_stream:
+        if self.multi_stream and a.full:
             # Kernel durations measured while batches of several streams share the device overlap each other; the
             # per-kernel figures (roofline, kernel_hbm, kernels_ms) come from the SAME steps run once more on one
             # stream, right after the timed regions.  The rate is the multi-stream figure of the timed regions.
@@ -825,17 +837,18 @@ class Run:
         vals = [H * a.gpus * a.steps / dt for dt in regions]
         med = float(np.median(vals))
         dt_med = H * a.gpus * a.steps / med
-        if not self.single and a.workload in ("plane", "sphere", "line") and self.closed_form:
-            # the multi-GPU step leaves the re-derived winner (a batch of one) as the context's current batch: the work
-            # model of the roofline is taken on a full batch of this rank, as in the single-GPU run (untimed)
-            ctx.batch_fit(0xC0FFEE, self.comm.rank * H, H)
         n_scan, ms_scan = prof["scan"]
         scan_ms = ms_scan / max(n_scan, 1)
         out = {"mode": mode, "value": med, "values": vals, "ms_per_step": dt_med / a.steps * 1e3,
                "region_s": regions, "per_rank": per_rank, "last": last, "prof": prof, "idx_warm": idx_warm,
                "abs_warm": abs_warm, "single_stream": single_stream, "scan_ms": scan_ms, "lm_evaluations": nfev,
-               "prof_steps": prof_steps,
-               "roofline": scan_roofline(self, mode, scan_ms, n_scan)}
+               "prof_steps": prof_steps, "roofline": None}
+        if a.full:
+            if not self.single and a.workload in ("plane", "sphere", "line") and self.closed_form:
+                # the multi-GPU step leaves the re-derived winner (a batch of one) as the context's current batch: the
+                # work model of the roofline is taken on a full batch of this rank, as in the single-GPU run (untimed)
+                ctx.batch_fit(0xC0FFEE, self.comm.rank * H, H)
+            out["roofline"] = scan_roofline(self, mode, scan_ms, n_scan)
         return out
 
 
@@ -905,7 +918,7 @@ def report(R, rates, cpu_budget, headline=True):
         "metric": METRIC,
         "value": value, "unit": "hypotheses/s", "n_gpus": a.gpus, "steps": a.steps,
         "warmup": a.warmup, "ms_per_step": main_rate["ms_per_step"], "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+        "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic", "full": a.full,
         "config": {"workload": "%sParametersEstimator + RANSAC, %d points, %d%% outliers, "
                                "delta=%.2f (BASELINE.json configs[1])" % (
                                    w.capitalize(), a.points, round(a.outliers * 100), R.delta)
@@ -945,6 +958,8 @@ def report(R, rates, cpu_budget, headline=True):
                      "evaluations_per_step": tot / (a.steps * max(1, a.repeats)),
                      "note": "one evaluation = one device pass (k_lm_pass*) over the winner's consensus set + the "
                              "MINPACK step; with --streams > 1 several fits are in flight"}
+    if not a.full:
+        return out          # a plain run: the figures of the timed regions only
     out["roofline"] = main_rate["roofline"]
     # the same work against the TIMED REGION's step time (several streams): `frac` above prices the dominant kernel by its
     # own duration on one stream, and that duration can exceed ms_per_step of the multi-stream region (VERDICT r04, weak
@@ -1124,9 +1139,9 @@ LEGS = (("sphere", "iterative", "SphereParametersEstimator + RANSAC, 10 M points
 
 
 def run_legs(a0, local):
-    """legs of BASELINE configs 3-5 (+ the US analytic fit and the plane phantom) on this GPU (the headline's 20 steps after 5 warm-up steps, one timed region each:
-    with 5 steps after 2 the legs read 5-8 % below the same workloads' own runs), so that the driver's own run
-    observes them"""
+    """--full: legs of BASELINE configs 3-5 (+ the US analytic fit and the plane phantom) on this GPU (the headline's 20
+    steps after 5 warm-up steps, one timed region each: with 5 steps after 2 the legs read 5-8 % below the same
+    workloads' own runs), so that the driver's own run observes them"""
     legs = []
     for w, fit, title in LEGS:
         t0 = time.perf_counter()
@@ -1141,6 +1156,7 @@ def run_legs(a0, local):
             a.streams, a.steps, a.warmup = 8, 24, 8      # eight host threads with a context each (see --streams)
         a.no_end_to_end = True
         a.no_cpu_baseline = a0.no_cpu_baseline
+        a.full = True                                   # a leg carries its roofline and CPU baseline
         try:
             o = run_workload(a, None, "cpu", local, "nccl", False, a0.cpu_seconds or 3.0, headline=False)
             keep = {k: o[k] for k in o if k in (
@@ -1239,7 +1255,7 @@ def headline(out, detail_path):
     h = {"metric": out["metric"], "value": out["value"], "unit": out["unit"], "n_gpus": out["n_gpus"],
          "steps": out["steps"], "warmup": out["warmup"], "ms_per_step": out["ms_per_step"],
          "higher_is_better": True, "scaling": out["scaling"], "vs_baseline": None, "dtype": out["dtype"],
-         "data": out["data"],
+         "data": out["data"], "full": out.get("full"),
          "config": {"workload": cfg["workload"][:140], "points": cfg["points"],
                     "hypotheses_per_gpu_per_step": cfg["hypotheses_per_gpu_per_step"], "streams": cfg.get("streams"),
                     "world_size": cfg.get("world_size"), "collectives": str(cfg.get("collectives"))[:120],
@@ -1376,7 +1392,7 @@ def run_multi(a):
     f = last["info"].fit
     out = {"metric": METRIC, "value": value, "unit": "hypotheses/s", "n_gpus": a.gpus, "steps": a.steps,
            "warmup": a.warmup, "ms_per_step": H * a.gpus / value * 1e3, "higher_is_better": True, "scaling": "weak",
-           "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+           "vs_baseline": None, "dtype": "f64", "data": "synthetic", "full": a.full,
            "config": {"workload": "%s estimator + RANSAC, %d observations" % (w, a.points), "points": a.points,
                       "hypotheses_per_gpu_per_step": H, "world_size": a.gpus, "devices": devs,
                       "collectives": "peer copies (lsqr_multi)", "streams": 1, "repeats": max(1, a.repeats),
@@ -1526,7 +1542,7 @@ def main():
     out = run_workload(a, dist, device, local, backend, force_dist, a.cpu_seconds or 4.0, headline=True)
     if rank == 0:
         single_plain = a.gpus == 1 and dist is None
-        if single_plain and a.workload == "plane" and not a.no_other_configs and a.rates == "both":
+        if a.full and single_plain and a.workload == "plane" and not a.no_other_configs and a.rates == "both":
             out["other_configs"] = run_legs(a, local)
         emit(out, a)
     if dist is not None:

@@ -15,6 +15,12 @@ def test_steps_must_be_positive():
         bench.parse(["--steps", "0"])
 
 
+def test_full_is_opt_in():
+    """a plain run times the steps and prints the line; the analysis beside it is asked for with --full"""
+    assert bench.parse([]).full is False
+    assert bench.parse(["--full"]).full is True
+
+
 def test_dump_directory_is_absolute_and_off_by_default(tmp_path, monkeypatch):
     assert bench.parse([]).dump_outputs is None
     monkeypatch.chdir(tmp_path)

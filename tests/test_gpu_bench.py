@@ -18,18 +18,20 @@ LAUNCHER_ENV = ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"
                 "TORCHELASTIC_RUN_ID")
 
 
-def _run(args, env=None, extra=("--no-cpu-baseline", "--no-end-to-end", "--no-other-configs"), rc=0, points="200000"):
+def _run(args, env=None, extra=("--no-cpu-baseline", "--no-end-to-end", "--no-other-configs"), rc=0, points="200000",
+         full=True):
     """-> the FULL record (the --detail file), after checking the stdout contract: the LAST line is the compact
     headline (< 4 KB, the driver parses it), any earlier JSON lines are the short per-leg lines, the whole stdout fits
-    the driver's 8 KB tail, and the headline's numbers are the detail's"""
+    the driver's 8 KB tail, and the headline's numbers are the detail's.  full: run with --full (roofline blocks,
+    one-stream pass, CPU baselines, legs), which the checks below are about"""
     e = {k: v for k, v in os.environ.items() if k not in LAUNCHER_ENV}
     if env:
         e.update(env)
     with tempfile.TemporaryDirectory() as td:
         detail = os.path.join(td, "detail.json")
         r = subprocess.run([sys.executable, "bench.py", "--points", points, "--steps", "6", "--warmup", "2",
-                            "--repeats", "2", "--detail", detail] + list(extra) + args, cwd=ROOT, env=e,
-                           capture_output=True, text=True, timeout=900)
+                            "--repeats", "2", "--detail", detail] + ["--full"] * full + list(extra) + args,
+                           cwd=ROOT, env=e, capture_output=True, text=True, timeout=900)
         if rc:
             assert r.returncode != 0, (r.returncode, r.stderr[-3000:])     # (torchrun maps a rank's exit 3 to 1)
             assert "RCCL did not come up" in r.stderr, r.stderr[-3000:]
@@ -111,6 +113,33 @@ def test_bench_lanes_and_single_stream(tmp_path):
     wf, we = a["roofline"]["work_model"], a["roofline_early_exit"]["work_model"]
     assert not wf["bounded_scan"] and wf["hypotheses_counted_exactly"] == 4096
     assert we["bounded_scan"] and we["hypotheses_counted_exactly"] < 4096
+
+
+def test_bench_plain_run_times_the_same_steps_without_the_extras(tmp_path):
+    """a run without --full (and without any --no-* switch) produces the headline's figures alone -- no one-stream pass,
+    roofline, per-kernel tables, compute() timings, CPU baseline or legs -- and times the steps of the --full run: the
+    last timed step of each rate returns the same outputs"""
+    p = _run(["--workload", "plane", "--dump-outputs", str(tmp_path / "plain")], extra=(), full=False)
+    h = p["_headline"]
+    assert p["full"] is False and h["full"] is False and p["_legs"] == []
+    for k in ("single_stream", "roofline", "roofline_early_exit", "kernel_hbm", "kernels_ms", "index",
+              "compute_end_to_end", "cpu_baseline", "cold_call", "other_configs"):
+        assert p.get(k) is None, k
+    assert h["roofline"] is None and h["cpu_baseline"] is None and h["one_stream"] is None
+    assert p["steps"] == 6 and p["warmup"] == 2 and p["config"]["streams"] == 4 and p["unit"] == "hypotheses/s"
+    assert p["value_is"] == "full_count" and p["value"] == p["value_full_count"] and p["value_early_exit"] > 0
+    assert len(p["repeats"]["full_count"]) == 2 and len(p["repeats"]["early_exit"]) == 2
+    assert abs(p["value"] - 4096 * 6 / (p["ms_per_step"] * 6e-3)) < 1e-6 * p["value"]
+    assert p["final_fit"]["winner_votes"] > 0 and p["final_fit"]["residual_min_max_mean_sumsq"] is not None
+    f = _run(["--workload", "plane", "--dump-outputs", str(tmp_path / "full")])
+    _check(f, 4)
+    assert f["full"] is True and f["_headline"]["full"] is True
+    assert p["final_fit"]["winner_votes"] == f["final_fit"]["winner_votes"]
+    assert p["final_fit"]["params"] == f["final_fit"]["params"]
+    names = sorted(os.listdir(tmp_path / "full"))
+    assert len(names) == 4 and sorted(os.listdir(tmp_path / "plain")) == names
+    for name in names:
+        assert np.array_equal(np.load(tmp_path / "plain" / name), np.load(tmp_path / "full" / name)), name
 
 
 def test_bench_host_threads_for_the_iterative_fit():

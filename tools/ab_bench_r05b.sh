@@ -1,5 +1,5 @@
 run() { label="$1"; shift
-  timeout -k 10 200 python bench.py "$@" --no-cpu-baseline --no-end-to-end --no-other-configs --repeats 1 --detail gpurun_out/ab_detail.json 2>/dev/null | tail -1 | python -c "
+  timeout -k 10 200 python bench.py "$@" --full --no-cpu-baseline --no-end-to-end --no-other-configs --repeats 1 --detail ${TMPDIR:-/tmp}/ab_detail.json 2>/dev/null | tail -1 | python -c "
 import sys,json
 d=json.loads(sys.stdin.read())
 print('$label', 'value', d['value'], 'one_stream', d.get('one_stream'), 'ms/step', d['ms_per_step'])"
