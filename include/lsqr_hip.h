@@ -308,6 +308,37 @@ LSQR_API int lsqr_ransac_many_lm(lsqr_ctx *ctx, const void *host_records, size_t
 LSQR_API int lsqr_lm_fit_many(lsqr_ctx *ctx, const void *host_records, size_t stride_bytes,
                               const uint64_t *offsets, size_t n_sets, const uint8_t *masks, const double *x0,
                               double *params_out, lsqr_fit_info *fits, int32_t *status_out);
+/* DenseLinearEquationSystemParametersEstimator<double,n> (robust linear regression), many problems in one call.
+ * Same arguments and per-problem contract as lsqr_ransac_many; model: LSQR_MODEL_DENSE only, dim 1..64, records of
+ * n + 1 doubles (AugmentedRow: a[0..n), b).  Any other model returns LSQR_ERR_INVALID and writes nothing
+ * (lsqr_ransac_many and lsqr_ransac_many_lm keep refusing the dense model).
+ *   Problem j against lsqr_ransac(ctx, p, seeds[j], NULL, 0, ...) on a dense context holding its records alone:
+ *     bit-identical status, iterations, best_index, best_votes, fraction, fit.n_used and consensus bytes (the
+ *     minimal solves are the single path's elimination / SVD pseudo-inverse, the votes its exact running sum); the
+ *     parameters agree up to the fp64 summation order of the final fit's normal equations.  fit.reserved = 1 when
+ *     the finish took the double-double route (a pivot below 1e-6 max|A^T A|: the system is solved again from its
+ *     consensus rows, as lsqr_ransac does), else 0; with option "dense_dd" 0 the block's pseudo-inverse decides and
+ *     reserved is 2 where lsqr_ransac reports 2.  Options "dense_fast_solve", "dense_dd", "max_iterations" and the
+ *     2^22 no-model stop apply per problem as in lsqr_ransac.
+ *   Independence as for lsqr_ransac_many: problem j's results, parameters included, are bit-identical whatever the
+ *     other problems, their order, or "many_round_hypotheses".  Its default (0) here is the number of hypotheses
+ *     whose rows (n padded to 8 / 16 / 32 / 64 doubles), subsets and flags fit in 256 MiB, at most 2^21: 2^21 up
+ *     to n = 8, 1.3 to 1.5 million at n = 9..16, 343 000 at n = 64.
+ *   The context's own upload, hypotheses and mask are not touched; the work runs on the context's stream. */
+LSQR_API int lsqr_ransac_many_dense(lsqr_ctx *ctx, const void *host_records, size_t stride_bytes,
+                                    const uint64_t *offsets, size_t n_problems, double p, const uint64_t *seeds,
+                                    double *params_out, uint8_t *consensus_out, lsqr_ransac_info *infos,
+                                    int32_t *status_out);
+/* DenseLinearEquationSystemParametersEstimator::leastSquaresEstimate over many row sets: set j is records
+ * [offsets[j], offsets[j+1]) (laid out as for lsqr_ransac_many_dense) restricted to masks (nullable: all records;
+ * else offsets[n_sets] bytes, record order).  Dense model only, as lsqr_ransac_many_dense.  Per set, as lsqr_upload +
+ * lsqr_set_mask + lsqr_ls_fit within fp64 summation order: status_out[j] LSQR_OK (params_out[j * n ..] written) or
+ * LSQR_EMPTY (rank deficient, parameters untouched); fits[j] carries n_params, reserved (as lsqr_ls_fit: 1 = the
+ * double-double route) and n_used (the set's rows in use).  An empty set or mask: LSQR_ERR_INVALID for that set, its
+ * parameters and fit untouched.  Argument errors as lsqr_ransac_many; the context's own upload is not touched. */
+LSQR_API int lsqr_dense_fit_many(lsqr_ctx *ctx, const void *host_records, size_t stride_bytes,
+                                 const uint64_t *offsets, size_t n_sets, const uint8_t *masks /* nullable */,
+                                 double *params_out, lsqr_fit_info *fits, int32_t *status_out);
 /* One fixed-size batch of the same loop without the adaptive stopping rule: hypotheses
  * [first_index, first_index + H) of the sampler stream `seed` are solved and scanned, the first
  * hypothesis with the maximal vote count wins (the strict '>' of RANSAC.hxx:100), its consensus set

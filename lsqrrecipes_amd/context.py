@@ -367,6 +367,59 @@ class Context:
         return dict(status=status, params=params, lm_info=fi["lm_info"].copy(), lm_nfev=fi["lm_nfev"].copy(),
                     cost=fi["cost"].copy(), n_used=fi["n_used"].copy())
 
+    def ransac_many_dense(self, problems, p, seeds=None, want_consensus=True):
+        """ransac_many for the dense linear system (lsqr_ransac_many_dense, DenseLinearEquationSystemParameters-
+        Estimator<double,n>); the context's model must be DENSE, else LsqrError(ERR_INVALID).  Records are n + 1
+        doubles (a, b).  Problem j is decided as ransac(p, seed=seeds[j]) on its records alone.  -> ransac_many's
+        dict plus the array reserved (fit.reserved: 1 where the finish took the double-double route)."""
+        if self.cfg is None:
+            raise L.LsqrError(L.ERR_STATE, "set_model has not been called")
+        recs, offs = self._many_records(problems)
+        n = len(offs) - 1
+        seeds = (1 + np.arange(n, dtype=np.uint64)) if seeds is None else np.ascontiguousarray(seeds, dtype=np.uint64)
+        if seeds.shape != (n,):
+            raise ValueError("one seed per problem")
+        params = np.zeros((max(n, 1), self.P))
+        total = int(offs[-1]) if n else 0
+        cons = np.zeros(max(total, 1), dtype=np.uint8) if want_consensus else None
+        infos = (L.RansacInfo * max(n, 1))()
+        status = np.zeros(max(n, 1), dtype=np.int32)
+        self._chk(self._lib.lsqr_ransac_many_dense(self._h, L.ptr(recs), self.ND * 8, L.ptr(offs), n, float(p),
+                                                   L.ptr(seeds), L.ptr(params), L.ptr(cons), infos, L.ptr(status)))
+        status, params = status[:n], params[:n]
+        params[status != L.OK] = 0.0
+        inf = np.ctypeslib.as_array(infos)[:n]
+        f = lambda name: inf[name].copy()
+        return dict(status=status, fraction=f("fraction"), iterations=f("iterations"), best_index=f("best_index"),
+                    best_votes=f("best_votes"), evaluated=f("evaluated"), n_params=f("n_params"),
+                    n_used=inf["fit"]["n_used"].copy(), reserved=inf["fit"]["reserved"].copy(), params=params,
+                    consensus=cons[:total] if cons is not None else None, offsets=offs)
+
+    def dense_fit_many(self, problems, masks=None):
+        """DenseLinearEquationSystemParametersEstimator::leastSquaresEstimate of many row sets in one call
+        (lsqr_dense_fit_many).  problems as for ransac_many; masks (optional): one byte per record, aligned with the
+        flat records.  -> dict of arrays: status (OK / EMPTY / ERR_INVALID for an empty set or mask), params (n x P,
+        zero rows where status is not OK), n_params, reserved (1: the double-double route) and n_used."""
+        if self.cfg is None:
+            raise L.LsqrError(L.ERR_STATE, "set_model has not been called")
+        recs, offs = self._many_records(problems)
+        n = len(offs) - 1
+        m = None
+        if masks is not None:
+            m = np.ascontiguousarray(masks, dtype=np.uint8).reshape(-1)
+            if m.shape[0] != int(offs[-1]):
+                raise ValueError("one mask byte per record")
+        params = np.zeros((max(n, 1), self.P))
+        fits = (L.FitInfo * max(n, 1))()
+        status = np.zeros(max(n, 1), dtype=np.int32)
+        self._chk(self._lib.lsqr_dense_fit_many(self._h, L.ptr(recs), self.ND * 8, L.ptr(offs), n, L.ptr(m),
+                                                L.ptr(params), fits, L.ptr(status)))
+        status, params = status[:n], params[:n]
+        params[status != L.OK] = 0.0
+        fi = np.ctypeslib.as_array(fits)[:n]
+        return dict(status=status, params=params, n_params=fi["n_params"].copy(), reserved=fi["reserved"].copy(),
+                    n_used=fi["n_used"].copy())
+
     def batch_fit(self, seed, first, H, want_consensus=False):
         """One fixed-size batch end to end on the device (lsqr_batch_fit): winner of hypotheses
         [first, first + H) of the sampler stream, its consensus set, the final fit."""

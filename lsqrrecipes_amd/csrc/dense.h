@@ -1213,8 +1213,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NBUF == 2 ?
 // flag (nullable): raised instead of taking the eigen / SVD path on G when the elimination is refused -- the caller
 // then solves the system again from the rows (k_gram_dd_dense / k_dense_dd_solve below); with flag == nullptr (only
 // the block is at hand: lsqr_solve_moments, the multi-GPU sum) the pseudo-inverse of G decides, rank test relative.
-__global__ __launch_bounds__(256) void k_solve_dense(const double *__restrict__ mom, int n, int fast,
-                                                     SolveOut *__restrict__ out, int *__restrict__ flag) {
+// (the body of one workgroup: k_solve_dense, and k_many_dense_solve (many_dense.h) for one problem each)
+__device__ inline void solve_dense_wg(const double *__restrict__ mom, int n, int fast, SolveOut *__restrict__ out,
+                                      int *__restrict__ flag) {
   extern __shared__ double sm[];
   const int tid = threadIdx.x, nz = n + 1, lda = n | 1;
   const int ne = nz * (nz + 1) / 2;
@@ -1310,6 +1311,10 @@ __global__ __launch_bounds__(256) void k_solve_dense(const double *__restrict__ 
     out->pad = s_hint ? 2 : 0;
   }
   for (int j = tid; j < n; j += 256) out->params[j] = ok ? x[j] : 0.0;
+}
+__global__ __launch_bounds__(256) void k_solve_dense(const double *__restrict__ mom, int n, int fast,
+                                                     SolveOut *__restrict__ out, int *__restrict__ flag) {
+  solve_dense_wg(mom, n, fast, out, flag);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

@@ -36,6 +36,7 @@
 #include "lm_persist.h"
 #include "host_entry.h"
 #include "many.h"
+#include "many_dense.h"
 
 #include <condition_variable>
 #include <mutex>
@@ -3856,8 +3857,10 @@ static int many_check_records(lsqr_ctx *c, const char *fn, const void *host_reco
   return LSQR_OK;
 }
 
-static void many_job_lm(lsqr_ctx *c, ManyJob &J, const void *host_records, size_t stride_bytes,
-                        const uint64_t *offsets, size_t n) {
+// the context's part of a batched job (lsqr_ransac_many_lm / _dense, lsqr_lm_fit_many / lsqr_dense_fit_many): records,
+// model, stream, buffers, the loop's options; round_cap 0 when the option is unset (the caller's default)
+static void many_job(lsqr_ctx *c, ManyJob &J, const void *host_records, size_t stride_bytes, const uint64_t *offsets,
+                     size_t n) {
   if (!c->many) c->many = new ManyBufs();
   J.stream = c->stream;
   J.cfg = c->cfg;
@@ -3868,9 +3871,15 @@ static void many_job_lm(lsqr_ctx *c, ManyJob &J, const void *host_records, size_
   J.n = n;
   J.W = c->ND;
   J.max_iter = c->opt_max_iter;
-  J.round_cap = c->opt_many_round > 0 ? (size_t)c->opt_many_round : kManyRoundDefault;
+  J.round_cap = c->opt_many_round > 0 ? (size_t)c->opt_many_round : 0;
   J.buf = c->many;
   J.err[0] = 0;
+}
+
+static void many_job_lm(lsqr_ctx *c, ManyJob &J, const void *host_records, size_t stride_bytes,
+                        const uint64_t *offsets, size_t n) {
+  many_job(c, J, host_records, stride_bytes, offsets, n);
+  if (J.round_cap == 0) J.round_cap = kManyRoundDefault;
   J.lm = true;
   lm_settings(c->cfg, &J.lm_n, &J.lm_ftol, &J.lm_xtol, &J.lm_gtol, &J.lm_maxfev);
 }
@@ -3931,6 +3940,72 @@ int lsqr_lm_fit_many(lsqr_ctx *c, const void *host_records, size_t stride_bytes,
     else return LSQR_ERR_INVALID;
   });
   if (st != LSQR_OK) return fail(c, st, "lsqr_lm_fit_many: %s", J.err[0] ? J.err : "model not in this build");
+  return LSQR_OK;
+}
+
+// ---- the same for the dense linear system (many_dense.h) -------------------------------------------------------------
+static void many_job_dense(lsqr_ctx *c, ManyJob &J, const void *host_records, size_t stride_bytes,
+                           const uint64_t *offsets, size_t n) {
+  many_job(c, J, host_records, stride_bytes, offsets, n);  // round_cap 0: many_dense_round_cap
+  J.dense_fast = c->opt_dense_fast ? 1 : 0;
+  J.dense_dd = c->opt_dense_dd ? 1 : 0;
+}
+
+int lsqr_ransac_many_dense(lsqr_ctx *c, const void *host_records, size_t stride_bytes, const uint64_t *offsets,
+                           size_t n_problems, double p, const uint64_t *seeds, double *params_out,
+                           uint8_t *consensus_out, lsqr_ransac_info *infos, int32_t *status_out) {
+  int st = need_ready(c, false);
+  if (st != LSQR_OK) return st;
+  if (c->cfg.model != LSQR_MODEL_DENSE)
+    return fail(c, LSQR_ERR_INVALID,
+                "lsqr_ransac_many_dense: the dense linear system only (model %d); the other models are batched by "
+                "lsqr_ransac_many / lsqr_ransac_many_lm", c->cfg.model);
+  if (n_problems == 0) return LSQR_OK;
+  if (!offsets || !seeds || !params_out || !infos || !status_out)
+    return fail(c, LSQR_ERR_INVALID, "lsqr_ransac_many_dense: null argument");
+  if (!(p > 0.0) || !(p < 1.0)) return fail(c, LSQR_ERR_INVALID, "lsqr_ransac_many_dense: p must lie in (0, 1)");
+  if ((st = many_check_records(c, "lsqr_ransac_many_dense", host_records, stride_bytes, offsets, n_problems)) !=
+      LSQR_OK)
+    return st;
+  ManyJob J;
+  many_job_dense(c, J, host_records, stride_bytes, offsets, n_problems);
+  J.p = p;
+  J.seeds = seeds;
+  J.params_out = params_out;
+  J.consensus_out = consensus_out;
+  J.infos = infos;
+  J.status_out = status_out;
+  st = dispatch(c->cfg, [&](auto tag) -> int {
+    typedef typename decltype(tag)::type M;
+    if constexpr (M::IS_DENSE) return many_dense_run<M::NR>(J);
+    else return LSQR_ERR_INVALID;
+  });
+  if (st != LSQR_OK) return fail(c, st, "lsqr_ransac_many_dense: %s", J.err[0] ? J.err : "model not in this build");
+  return LSQR_OK;
+}
+
+int lsqr_dense_fit_many(lsqr_ctx *c, const void *host_records, size_t stride_bytes, const uint64_t *offsets,
+                        size_t n_sets, const uint8_t *masks, double *params_out, lsqr_fit_info *fits,
+                        int32_t *status_out) {
+  int st = need_ready(c, false);
+  if (st != LSQR_OK) return st;
+  if (c->cfg.model != LSQR_MODEL_DENSE)
+    return fail(c, LSQR_ERR_INVALID, "lsqr_dense_fit_many: the dense linear system only (model %d)", c->cfg.model);
+  if (n_sets == 0) return LSQR_OK;
+  if (!offsets || !params_out || !fits || !status_out)
+    return fail(c, LSQR_ERR_INVALID, "lsqr_dense_fit_many: null argument");
+  if ((st = many_check_records(c, "lsqr_dense_fit_many", host_records, stride_bytes, offsets, n_sets)) != LSQR_OK)
+    return st;
+  ManyJob J;
+  many_job_dense(c, J, host_records, stride_bytes, offsets, n_sets);
+  J.params_out = params_out;
+  J.status_out = status_out;
+  st = dispatch(c->cfg, [&](auto tag) -> int {
+    typedef typename decltype(tag)::type M;
+    if constexpr (M::IS_DENSE) return many_dense_fit<M::NR>(J, masks, fits);
+    else return LSQR_ERR_INVALID;
+  });
+  if (st != LSQR_OK) return fail(c, st, "lsqr_dense_fit_many: %s", J.err[0] ? J.err : "model not in this build");
   return LSQR_OK;
 }
 

@@ -272,13 +272,20 @@ struct ManyBufs {
   char *h_stage = nullptr, *h_pairs = nullptr;  // pinned: the round's tables and results / the winner pairs
   size_t c_stage = 0, c_hpairs = 0;
   ManyLmBufs lm;  // the LM stage of lsqr_ransac_many_lm / lsqr_lm_fit_many (many_lm.h)
+  // lsqr_ransac_many_dense / lsqr_dense_fit_many (many_dense.h): the round's subsets, the minimal systems the
+  // elimination refused, the problems' moment blocks, their double-double flags and the double-double Gram partials
+  uint32_t *d_sub = nullptr, *d_marked = nullptr;
+  double *d_mom = nullptr, *d_ddpart = nullptr;
+  int *d_flags = nullptr;
+  size_t c_sub = 0, c_marked = 0, c_mom = 0, c_ddpart = 0, c_flags = 0;
 };
 
 #if defined(__HIPCC__)
 inline void many_free(ManyBufs *b) {
   if (!b) return;
   void *dev[] = {b->d_data, b->d_hparams, b->d_best, b->d_partials, b->d_items, b->d_tiles, b->d_parts, b->d_valid,
-                 b->d_mask, b->d_votes, b->d_pairs, b->d_pbeg, b->d_fin, b->d_counts, b->d_out};
+                 b->d_mask, b->d_votes, b->d_pairs, b->d_pbeg, b->d_fin, b->d_counts, b->d_out,
+                 b->d_sub, b->d_marked, b->d_mom, b->d_ddpart, b->d_flags};
   for (void *p : dev)
     if (p) (void)hipFree(p);
   if (b->h_stage) (void)hipHostFree(b->h_stage);
@@ -330,6 +337,7 @@ struct ManyJob {
   bool lm = false;     // lsqr_ransac_many_lm: the geometric sphere's LM fit from the algebraic one (many_lm.h)
   int lm_n = 0, lm_maxfev = 0;  // ... with lm_settings
   double lm_ftol = 0, lm_xtol = 0, lm_gtol = 0;
+  int dense_fast = 1, dense_dd = 1;  // lsqr_ransac_many_dense: options dense_fast_solve / dense_dd (many_dense.h)
   ManyBufs *buf;
   char err[256];
 };
@@ -372,13 +380,12 @@ struct ManyProb {
 
 // host replay of items [i0, i1) of a round: lsqr_ransac's loop body after the batch's votes are in.  Subsets are
 // regenerated on the host (the same ctr_subset), piece by piece, only as far as the replay consumes them.
-template <class M>
-void many_replay(const ManyJob &J, std::vector<ManyProb> &pr, const std::vector<uint32_t> &item_prob,
-                 const ManyItem *items, size_t i0, size_t i1, const uint32_t *votes, const uint8_t *valid,
-                 std::vector<uint32_t> *pairs) {
-  constexpr int K = M::K;
+// K: the minimal subset's size (<= 64: the dense system's n)
+inline void many_replay(const ManyJob &J, std::vector<ManyProb> &pr, const std::vector<uint32_t> &item_prob,
+                        const ManyItem *items, size_t i0, size_t i1, const uint32_t *votes, const uint8_t *valid,
+                        std::vector<uint32_t> *pairs, int K) {
   constexpr size_t kPiece = 64;
-  uint32_t sub[kPiece * K], sorted[K];
+  std::vector<uint32_t> sub(kPiece * K), sorted(K);
   for (size_t t = i0; t < i1; t++) {
     const ManyItem &it = items[t];
     const uint32_t j = item_prob[t];
@@ -389,8 +396,9 @@ void many_replay(const ManyJob &J, std::vector<ManyProb> &pr, const std::vector<
     size_t used = 0;
     while (used < it.H) {  // host_replay over the batch, fed in pieces: the same sequential loop
       const size_t m = std::min<size_t>(kPiece, it.H - used);
-      for (size_t e = 0; e < m; e++) ctr_subset(it.seed, it.first + used + e, it.n, K, sub + e * K, sorted);
-      const size_t u = host_replay(it.n, K, J.p, sub, valid + it.h0 + used, votes + it.h0 + used, m,
+      for (size_t e = 0; e < m; e++)
+        ctr_subset(it.seed, it.first + used + e, it.n, K, sub.data() + e * K, sorted.data());
+      const size_t u = host_replay(it.n, K, J.p, sub.data(), valid + it.h0 + used, votes + it.h0 + used, m,
                                    it.first + used, q.dedup.get(), q.rs);
       used += u;
       if (u < m) break;
@@ -413,37 +421,15 @@ void many_replay(const ManyJob &J, std::vector<ManyProb> &pr, const std::vector<
   }
 }
 
-template <class M>
-int many_run(ManyJob &J) {
-  constexpr int K = M::K, SP = M::SP;
-  const int W = many_width<M>(J.W);
+// lsqr_ransac_many's rounds over the live problems of pr (host_replay_init done): per round the batches, the scan
+// tiles (<= kManyBlock hypotheses x <= seg records, largest first), launch(n_items, Ht, n_tiles) -- the model's
+// kernels: B.d_items / B.d_tiles in, B.d_hparams (SP doubles per hypothesis), B.d_valid and B.d_votes (zeroed) out --,
+// the host replay (K: the minimal subset's size) and the gather of the winners' rows into B.d_best
+template <class Launch>
+int many_rounds(ManyJob &J, std::vector<ManyProb> &pr, int K, int SP, uint64_t seg, Launch &&launch) {
   ManyBufs &B = *J.buf;
   const size_t NP = J.n;
-  const uint64_t NT = J.offsets[NP];
-  const int org_off = fit_origin_offset<M>(J.cfg);
-  static_assert(M::NMOM <= 64, "one lane per moment in k_many_solve");
-  int st0;
-
-  std::vector<ManyProb> pr(NP);
-  for (size_t j = 0; j < NP; j++) {
-    memset(&J.infos[j], 0, sizeof(lsqr_ransac_info));
-    const uint64_t n = J.offsets[j + 1] - J.offsets[j];
-    if (n < (uint64_t)K) {  // RANSAC.hxx:16-19: return 0, parameters untouched
-      J.status_out[j] = LSQR_ERR_INVALID;
-      continue;
-    }
-    host_replay_init(n, K, J.p, pr[j].rs);
-    pr[j].live = !pr[j].rs[RS_DONE];
-  }
-
-  if (W != J.W) {
-    snprintf(J.err, sizeof J.err, "record width %d != the model's %d doubles", J.W, W);
-    return LSQR_ERR_INVALID;
-  }
-  std::vector<double> packed;
-  if ((st0 = many_upload(J, W, NT, packed)) != LSQR_OK) return st0;
-  MANYCHK(many_grow(&B.d_best, &B.c_best, std::max<size_t>(NP, 1) * SP));
-
+  int st;
   const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
   // diagnostics (LSQR_MANY_TRACE): per round the batches, hypotheses, tiles, device wait and host replay time
   static const bool trace = getenv("LSQR_MANY_TRACE") != nullptr;
@@ -493,10 +479,10 @@ int many_run(ManyJob &J) {
     tiles.clear();
     for (const ManyItem &it : items)
       for (uint32_t h = 0; h < it.H; h += kManyBlock)
-        for (uint64_t r = 0; r < it.n; r += kManySeg) {
+        for (uint64_t r = 0; r < it.n; r += seg) {
           ManyTile t;
           t.r0 = it.rec + r;
-          t.r1 = it.rec + std::min<uint64_t>(it.n, r + kManySeg);
+          t.r1 = it.rec + std::min<uint64_t>(it.n, r + seg);
           t.h0 = it.h0 + h;
           t.nh = std::min<uint32_t>(kManyBlock, it.H - h);
           tiles.push_back(t);
@@ -518,13 +504,7 @@ int many_run(ManyJob &J) {
     MANYCHK(hipMemcpyAsync(B.d_items, B.h_stage, b_items, hipMemcpyHostToDevice, J.stream));
     MANYCHK(hipMemcpyAsync(B.d_tiles, B.h_stage + o_tiles, b_tiles, hipMemcpyHostToDevice, J.stream));
     MANYCHK(hipMemsetAsync(B.d_votes, 0, sizeof(uint32_t) * Ht, J.stream));
-    hipLaunchKernelGGL((k_many_sample_estimate<M>), dim3((unsigned)((Ht + kBlock - 1) / kBlock)), dim3(kBlock), 0,
-                       J.stream, B.d_data, W, B.d_items, (int)items.size(), (uint32_t)Ht, J.mc, B.d_hparams,
-                       B.d_valid);
-    MANYCHK(hipGetLastError());
-    hipLaunchKernelGGL((k_many_scan<M>), dim3((unsigned)tiles.size()), dim3(kManyBlock), 0, J.stream, B.d_data, W,
-                       B.d_tiles, B.d_hparams, B.d_valid, J.mc, B.d_votes);
-    MANYCHK(hipGetLastError());
+    if ((st = launch(items.size(), Ht, tiles.size())) != LSQR_OK) return st;
     uint32_t *h_votes = (uint32_t *)(B.h_stage + o_votes);
     uint8_t *h_valid = (uint8_t *)(B.h_stage + o_valid);
     MANYCHK(hipMemcpyAsync(h_votes, B.d_votes, sizeof(uint32_t) * Ht, hipMemcpyDeviceToHost, J.stream));
@@ -532,17 +512,20 @@ int many_run(ManyJob &J) {
     const Clock::time_point t_sync = Clock::now();
     MANYCHK(hipStreamSynchronize(J.stream));
     const Clock::time_point t_replay = Clock::now();
-    // replay, problems spread over host threads (each item touches its own problem's state only)
+    // replay, problems spread over host threads (each item touches its own problem's state only); an item's cost
+    // grows as K^2 (ctr_subset), so the dense system's large subsets take threads at fewer items
     const size_t NI = items.size();
-    const unsigned T = (unsigned)std::min<size_t>(std::min<unsigned>(hw, 16), (NI + 127) / 128);
+    const size_t per_item = std::max<size_t>((size_t)K * K / 64, 1);
+    const unsigned T = (unsigned)std::min<size_t>(std::min<unsigned>(hw, 16), (NI * per_item + 127) / 128);
     std::vector<std::vector<uint32_t>> pairs(std::max(1u, T));
     if (T <= 1) {
-      many_replay<M>(J, pr, item_prob, items.data(), 0, NI, h_votes, h_valid, &pairs[0]);
+      many_replay(J, pr, item_prob, items.data(), 0, NI, h_votes, h_valid, &pairs[0], K);
     } else {
       std::vector<std::thread> th;
       for (unsigned w = 0; w < T; w++)
         th.emplace_back([&, w] {
-          many_replay<M>(J, pr, item_prob, items.data(), NI * w / T, NI * (w + 1) / T, h_votes, h_valid, &pairs[w]);
+          many_replay(J, pr, item_prob, items.data(), NI * w / T, NI * (w + 1) / T, h_votes, h_valid, &pairs[w],
+                      K);
         });
       for (auto &x : th) x.join();
     }
@@ -570,6 +553,52 @@ int many_run(ManyJob &J) {
       // the next round writes h_pairs only after its own synchronisation, which follows this copy
     }
   }
+
+  return LSQR_OK;
+}
+
+template <class M>
+int many_run(ManyJob &J) {
+  constexpr int K = M::K, SP = M::SP;
+  const int W = many_width<M>(J.W);
+  ManyBufs &B = *J.buf;
+  const size_t NP = J.n;
+  const uint64_t NT = J.offsets[NP];
+  const int org_off = fit_origin_offset<M>(J.cfg);
+  static_assert(M::NMOM <= 64, "one lane per moment in k_many_solve");
+  int st0;
+
+  std::vector<ManyProb> pr(NP);
+  for (size_t j = 0; j < NP; j++) {
+    memset(&J.infos[j], 0, sizeof(lsqr_ransac_info));
+    const uint64_t n = J.offsets[j + 1] - J.offsets[j];
+    if (n < (uint64_t)K) {  // RANSAC.hxx:16-19: return 0, parameters untouched
+      J.status_out[j] = LSQR_ERR_INVALID;
+      continue;
+    }
+    host_replay_init(n, K, J.p, pr[j].rs);
+    pr[j].live = !pr[j].rs[RS_DONE];
+  }
+
+  if (W != J.W) {
+    snprintf(J.err, sizeof J.err, "record width %d != the model's %d doubles", J.W, W);
+    return LSQR_ERR_INVALID;
+  }
+  std::vector<double> packed;
+  if ((st0 = many_upload(J, W, NT, packed)) != LSQR_OK) return st0;
+  MANYCHK(many_grow(&B.d_best, &B.c_best, std::max<size_t>(NP, 1) * SP));
+
+  if ((st0 = many_rounds(J, pr, K, SP, kManySeg, [&](size_t n_items, uint64_t Ht, size_t n_tiles) -> int {
+         hipLaunchKernelGGL((k_many_sample_estimate<M>), dim3((unsigned)((Ht + kBlock - 1) / kBlock)), dim3(kBlock),
+                            0, J.stream, B.d_data, W, B.d_items, (int)n_items, (uint32_t)Ht, J.mc, B.d_hparams,
+                            B.d_valid);
+         MANYCHK(hipGetLastError());
+         hipLaunchKernelGGL((k_many_scan<M>), dim3((unsigned)n_tiles), dim3(kManyBlock), 0, J.stream, B.d_data, W,
+                            B.d_tiles, B.d_hparams, B.d_valid, J.mc, B.d_votes);
+         MANYCHK(hipGetLastError());
+         return LSQR_OK;
+       })) != LSQR_OK)
+    return st0;
 
   // ---- finish: finish_ransac for every problem with a winner -----------------------------------------------------
   std::vector<uint32_t> fin, pbeg;

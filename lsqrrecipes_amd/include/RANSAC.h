@@ -116,9 +116,10 @@ class RANSAC {
   // Plane, line, algebraic sphere, absolute orientation, pivot calibration, ray intersection and the 2-D line run in
   // ONE device call (lsqr_ransac_many: one upload, batched rounds, one finish; the records are packed sizeof(T)
   // apart, as compute() uploads them); the geometric sphere (SphereParametersEstimator's default) runs in one
-  // lsqr_ransac_many_lm call, its LM finish batched on the device too.  Estimators without a device model loop over
-  // the plugin path, other device estimators (dense system, US calibrations, plane phantom) over compute(), with the
-  // same seeds.
+  // lsqr_ransac_many_lm call, its LM finish batched on the device too, and the dense linear system
+  // (DenseLinearEquationSystemParametersEstimator) in one lsqr_ransac_many_dense call.  Estimators without a device
+  // model loop over the plugin path, other device estimators (US calibrations, plane phantom) over compute(), with
+  // the same seeds.
   // Under LSQR_DEVICES the batched call runs on the first listed device's context (problems are not sharded over
   // devices).  lastInfo() is not updated.
   static std::vector<double> computeMany(std::vector<std::vector<S> > &parameters,
@@ -136,8 +137,9 @@ class RANSAC {
     const bool device = paramEstimator->deviceModel(cfg) && !forceHostLoop();
     // the geometric sphere's LM finish: lsqr_ransac_many_lm; the closed-form fits: lsqr_ransac_many
     const bool lm = device && cfg.model == LSQR_MODEL_SPHERE && cfg.ls_type == LSQR_LS_GEOMETRIC;
+    const bool dense = device && cfg.model == LSQR_MODEL_DENSE;  // lsqr_ransac_many_dense
     const bool batched = device && (cfg.model == LSQR_MODEL_PLANE || cfg.model == LSQR_MODEL_LINE ||
-                                    cfg.model == LSQR_MODEL_SPHERE ||
+                                    cfg.model == LSQR_MODEL_SPHERE || cfg.model == LSQR_MODEL_DENSE ||
                                     cfg.model == LSQR_MODEL_ABSOR || cfg.model == LSQR_MODEL_PIVOT ||
                                     cfg.model == LSQR_MODEL_RAY || cfg.model == LSQR_MODEL_LINE2D);
     if (!batched) {
@@ -168,9 +170,9 @@ class RANSAC {
     std::vector<uint8_t> cons(consensusSets ? (size_t)offsets[n] : 0);
     std::vector<lsqr_ransac_info> info(n);
     std::vector<int32_t> status(n);
-    d.check((lm ? lsqr_ransac_many_lm : lsqr_ransac_many)(ctx, records.empty() ? NULL : &records[0], sizeof(T),
-                                                          &offsets[0], n, p, &seeds[0], &par[0],
-                                                          cons.empty() ? NULL : &cons[0], &info[0], &status[0]));
+    d.check((lm ? lsqr_ransac_many_lm : dense ? lsqr_ransac_many_dense : lsqr_ransac_many)(
+        ctx, records.empty() ? NULL : &records[0], sizeof(T), &offsets[0], n, p, &seeds[0], &par[0],
+        cons.empty() ? NULL : &cons[0], &info[0], &status[0]));
     for (size_t j = 0; j < n; j++) {
       if (status[j] == LSQR_ERR_INVALID) continue;  // fewer records than a minimal subset: untouched, 0
       parameters[j].clear();  // RANSAC.hxx:43

@@ -15,6 +15,11 @@ and the geometric (Levenberg-Marquardt) sphere, Context.ransac_many_lm against t
 (--shapes geometric: both):
   sphere_lm         1 000 problems x 10 000 records, 50 % inliers
   sphere_lm_small  10 000 problems x    300 records, 50 % inliers
+and the dense linear system (robust linear regression), Context.ransac_many_dense against the loop on a dense
+context (--shapes dense: all three; delta 0.1, 1e-3 relative noise on b, outliers' b scaled by 20 as synth.dense):
+  dense6   n =  6  10 000 problems x    500 rows, 20 % outliers
+  dense16  n = 16   1 000 problems x  5 000 rows, 10 % outliers
+  dense64  n = 64     100 problems x 20 000 rows,  3 % outliers
 Each row also gives the loop's time per problem (loop_ms_per_problem).  Every timed call
 ends in a device synchronisation (both entry points return host results); each shape is warmed first; the two
 paths alternate in one process.  --quick: one repetition, small loop (for a kernel-trace run under rocprofv3).
@@ -53,6 +58,20 @@ def gen(model, n_prob, n_rec, inl, seed):
     pts[is_out] = out[is_out]
     offs = np.arange(P + 1, dtype=np.uint64) * N
     return np.ascontiguousarray(pts.reshape(-1, 3)), offs
+
+
+def gen_dense(n, n_prob, n_rec, inl, seed):
+    """(rows (n_prob * n_rec, n + 1), offsets): one random x per problem, a uniform in [-1, 1]^n, b = a.x with 1e-3
+    relative noise, the outliers' b scaled by 20 (synth.dense's model)"""
+    g = np.random.default_rng(seed)
+    rows = np.empty((n_prob, n_rec, n + 1))
+    for j in range(n_prob):
+        A = g.uniform(-1.0, 1.0, (n_rec, n))
+        b = (A @ g.uniform(-1.0, 1.0, n)) * (1.0 + g.uniform(-1e-3, 1e-3, n_rec))
+        b[g.random(n_rec) >= inl] *= 20.0
+        rows[j, :, :n], rows[j, :, n] = A, b
+    offs = np.arange(n_prob + 1, dtype=np.uint64) * n_rec
+    return rows.reshape(n_prob * n_rec, n + 1), offs
 
 
 def random_rotations(g, shape):
@@ -107,6 +126,8 @@ POINT_SHAPES = {"plane": (L.PLANE, 10_000, 1_000), "sphere": (L.SPHERE, 1_000, 1
 RIGID_SHAPES = {"rays": (L.RAY, 100_000, 12, 0.7, 1.0, np.pi / 180), "absor": (L.ABSOR, 10_000, 20, 0.7, 1.0, 0.0),
                 "pivot": (L.PIVOT, 1_000, 300, 0.7, 1.0, 0.0), "line2d": (L.LINE2D, 100_000, 200, 0.5, 0.5, 0.0)}
 GEOMETRIC_SHAPES = {"sphere_lm": (1_000, 10_000), "sphere_lm_small": (10_000, 300)}
+# name -> (n, problems, rows, inlier share)
+DENSE_SHAPES = {"dense6": (6, 10_000, 500, 0.8), "dense16": (16, 1_000, 5_000, 0.9), "dense64": (64, 100, 20_000, 0.97)}
 
 
 def timed(f, reps):
@@ -126,12 +147,15 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--out", default=None, help="also write the results as one JSON file")
     ap.add_argument("--shapes", default="plane,sphere,line",
-                    help="comma-separated shapes (%s), or 'rigid' / 'geometric' for the closed-form estimators' / "
-                         "the LM sphere's" % ", ".join(list(POINT_SHAPES) + list(RIGID_SHAPES) + list(GEOMETRIC_SHAPES)))
+                    help="comma-separated shapes (%s), or 'rigid' / 'geometric' / 'dense' for the closed-form "
+                         "estimators' / the LM sphere's / the dense system's"
+                         % ", ".join(list(POINT_SHAPES) + list(RIGID_SHAPES) + list(GEOMETRIC_SHAPES) + list(DENSE_SHAPES)))
     a = ap.parse_args()
-    names = {"rigid": list(RIGID_SHAPES), "geometric": list(GEOMETRIC_SHAPES)}.get(a.shapes, a.shapes.split(","))
+    names = {"rigid": list(RIGID_SHAPES), "geometric": list(GEOMETRIC_SHAPES),
+             "dense": list(DENSE_SHAPES)}.get(a.shapes, a.shapes.split(","))
     for name in names:
-        if name not in POINT_SHAPES and name not in RIGID_SHAPES and name not in GEOMETRIC_SHAPES:
+        if (name not in POINT_SHAPES and name not in RIGID_SHAPES and name not in GEOMETRIC_SHAPES
+                and name not in DENSE_SHAPES):
             ap.error("unknown shape %r" % name)
     reps = 1 if a.quick else a.reps
     loop_n = 100 if a.quick else a.loop
@@ -148,6 +172,11 @@ def main():
             recs, offs = gen(model, P, N, 0.5, seed=model + N)
             ctx.set_model(model, 3, 0.5, L.LS_GEOMETRIC)
             batched = ctx.ransac_many_lm
+        elif name in DENSE_SHAPES:
+            n, P, N, inl = DENSE_SHAPES[name]
+            recs, offs = gen_dense(n, P, N, inl, seed=n)
+            ctx.set_model(L.DENSE, n, 0.1)
+            batched = ctx.ransac_many_dense
         else:
             model, P, N, inl, delta, aux = RIGID_SHAPES[name]
             recs, offs = gen_rigid(name, P, N, inl, seed=model)
