@@ -265,38 +265,11 @@ class Context:
         ransac(p, seed=seeds[j]) on its records alone.  -> dict of arrays: status, fraction, iterations,
         best_index, best_votes, evaluated, n_params, n_used, params (n x P, zero rows where status is not OK),
         consensus (flat, aligned with offsets; None unless want_consensus) and offsets."""
-        if self.cfg is None:
-            raise L.LsqrError(L.ERR_STATE, "set_model has not been called")
-        if isinstance(problems, tuple):
-            recs, offs = problems
-            recs = np.ascontiguousarray(recs, dtype=np.float64).reshape(-1, self.ND)
-            offs = np.ascontiguousarray(offs, dtype=np.uint64)
-        else:
-            parts = [np.asarray(a, dtype=np.float64).reshape(-1, self.ND) for a in problems]
-            offs = np.zeros(len(parts) + 1, dtype=np.uint64)
-            offs[1:] = np.cumsum([a.shape[0] for a in parts])
-            recs = np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros((0, self.ND)))
-        n = len(offs) - 1
-        seeds = (1 + np.arange(n, dtype=np.uint64)) if seeds is None else np.ascontiguousarray(seeds, dtype=np.uint64)
-        if seeds.shape != (n,):
-            raise ValueError("one seed per problem")
-        params = np.zeros((max(n, 1), self.P))
-        total = int(offs[-1]) if n else 0
-        cons = np.zeros(max(total, 1), dtype=np.uint8) if want_consensus else None
-        infos = (L.RansacInfo * max(n, 1))()
-        status = np.zeros(max(n, 1), dtype=np.int32)
-        self._chk(self._lib.lsqr_ransac_many(self._h, L.ptr(recs), self.ND * 8, L.ptr(offs), n, float(p),
-                                             L.ptr(seeds), L.ptr(params), L.ptr(cons), infos, L.ptr(status)))
-        status, params = status[:n], params[:n]
-        params[status != L.OK] = 0.0
-        inf = np.ctypeslib.as_array(infos)[:n]  # structured view of the lsqr_ransac_info array
-        f = lambda name: inf[name].copy()
-        return dict(status=status, fraction=f("fraction"), iterations=f("iterations"), best_index=f("best_index"),
-                    best_votes=f("best_votes"), evaluated=f("evaluated"), n_params=f("n_params"),
-                    n_used=inf["fit"]["n_used"].copy(), params=params,
-                    consensus=cons[:total] if cons is not None else None, offsets=offs)
+        return self._ransac_many(self._lib.lsqr_ransac_many, problems, p, seeds, want_consensus)
 
     def _many_records(self, problems):
+        if self.cfg is None:
+            raise L.LsqrError(L.ERR_STATE, "set_model has not been called")
         if isinstance(problems, tuple):
             recs, offs = problems
             recs = np.ascontiguousarray(recs, dtype=np.float64).reshape(-1, self.ND)
@@ -308,13 +281,9 @@ class Context:
             recs = np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros((0, self.ND)))
         return recs, offs
 
-    def ransac_many_lm(self, problems, p, seeds=None, want_consensus=True):
-        """ransac_many with the geometric sphere's Levenberg-Marquardt finish (lsqr_ransac_many_lm); the context's
-        model must be the sphere with ls_type LS_GEOMETRIC, else LsqrError(ERR_INVALID).  Problem j is decided as
-        ransac(p, seed=seeds[j]) on its records alone.  -> ransac_many's dict plus the arrays lm_info, lm_nfev and
-        cost of each problem's final fit."""
-        if self.cfg is None:
-            raise L.LsqrError(L.ERR_STATE, "set_model has not been called")
+    def _ransac_many(self, fn, problems, p, seeds, want_consensus, extra=()):
+        """one call of fn (lsqr_ransac_many's signature) -> ransac_many's dict, with the fields `extra` of every
+        problem's lsqr_fit_info after n_used"""
         recs, offs = self._many_records(problems)
         n = len(offs) - 1
         seeds = (1 + np.arange(n, dtype=np.uint64)) if seeds is None else np.ascontiguousarray(seeds, dtype=np.uint64)
@@ -325,18 +294,51 @@ class Context:
         cons = np.zeros(max(total, 1), dtype=np.uint8) if want_consensus else None
         infos = (L.RansacInfo * max(n, 1))()
         status = np.zeros(max(n, 1), dtype=np.int32)
-        self._chk(self._lib.lsqr_ransac_many_lm(self._h, L.ptr(recs), self.ND * 8, L.ptr(offs), n, float(p),
-                                                L.ptr(seeds), L.ptr(params), L.ptr(cons), infos, L.ptr(status)))
+        self._chk(fn(self._h, L.ptr(recs), self.ND * 8, L.ptr(offs), n, float(p), L.ptr(seeds), L.ptr(params),
+                     L.ptr(cons), infos, L.ptr(status)))
         status, params = status[:n], params[:n]
         params[status != L.OK] = 0.0
-        inf = np.ctypeslib.as_array(infos)[:n]
+        inf = np.ctypeslib.as_array(infos)[:n]  # structured view of the lsqr_ransac_info array
         f = lambda name: inf[name].copy()
         fit = inf["fit"]
         return dict(status=status, fraction=f("fraction"), iterations=f("iterations"), best_index=f("best_index"),
                     best_votes=f("best_votes"), evaluated=f("evaluated"), n_params=f("n_params"),
-                    n_used=fit["n_used"].copy(), lm_info=fit["lm_info"].copy(), lm_nfev=fit["lm_nfev"].copy(),
-                    cost=fit["cost"].copy(), params=params,
+                    n_used=fit["n_used"].copy(), **{k: fit[k].copy() for k in extra}, params=params,
                     consensus=cons[:total] if cons is not None else None, offsets=offs)
+
+    def _fit_many(self, fn, problems, masks, keys, x0=None):
+        """one call of fn (lsqr_dense_fit_many's signature; with x0, lsqr_lm_fit_many's) -> dict of status, params
+        and the fields `keys` of every set's lsqr_fit_info"""
+        recs, offs = self._many_records(problems)
+        n = len(offs) - 1
+        starts = ()
+        if x0 is not None:
+            x0 = np.ascontiguousarray(x0, dtype=np.float64).reshape(-1, self.P)
+            if x0.shape[0] != n:
+                raise ValueError("one start per set")
+            starts = (L.ptr(x0),)
+        m = None
+        if masks is not None:
+            m = np.ascontiguousarray(masks, dtype=np.uint8).reshape(-1)
+            if m.shape[0] != int(offs[-1]):
+                raise ValueError("one mask byte per record")
+        params = np.zeros((max(n, 1), self.P))
+        fits = (L.FitInfo * max(n, 1))()
+        status = np.zeros(max(n, 1), dtype=np.int32)
+        self._chk(fn(self._h, L.ptr(recs), self.ND * 8, L.ptr(offs), n, L.ptr(m), *starts, L.ptr(params), fits,
+                     L.ptr(status)))
+        status, params = status[:n], params[:n]
+        params[status != L.OK] = 0.0
+        fi = np.ctypeslib.as_array(fits)[:n]
+        return dict(status=status, params=params, **{k: fi[k].copy() for k in keys})
+
+    def ransac_many_lm(self, problems, p, seeds=None, want_consensus=True):
+        """ransac_many with the geometric sphere's Levenberg-Marquardt finish (lsqr_ransac_many_lm); the context's
+        model must be the sphere with ls_type LS_GEOMETRIC, else LsqrError(ERR_INVALID).  Problem j is decided as
+        ransac(p, seed=seeds[j]) on its records alone.  -> ransac_many's dict plus the arrays lm_info, lm_nfev and
+        cost of each problem's final fit."""
+        return self._ransac_many(self._lib.lsqr_ransac_many_lm, problems, p, seeds, want_consensus,
+                                 extra=("lm_info", "lm_nfev", "cost"))
 
     def lm_fit_many(self, problems, x0, masks=None):
         """The geometric sphere fit (SphereParametersEstimator::geometricLeastSquaresEstimate) of many record sets
@@ -344,81 +346,23 @@ class Context:
         (optional): one byte per record, aligned with the flat records.  -> dict of arrays: status (OK / EMPTY /
         ERR_INVALID for an empty set or mask), params (n x P, zero rows where status is not OK), lm_info, lm_nfev,
         cost and n_used."""
-        if self.cfg is None:
-            raise L.LsqrError(L.ERR_STATE, "set_model has not been called")
-        recs, offs = self._many_records(problems)
-        n = len(offs) - 1
-        x0 = np.ascontiguousarray(x0, dtype=np.float64).reshape(-1, self.P)
-        if x0.shape[0] != n:
-            raise ValueError("one start per set")
-        m = None
-        if masks is not None:
-            m = np.ascontiguousarray(masks, dtype=np.uint8).reshape(-1)
-            if m.shape[0] != int(offs[-1]):
-                raise ValueError("one mask byte per record")
-        params = np.zeros((max(n, 1), self.P))
-        fits = (L.FitInfo * max(n, 1))()
-        status = np.zeros(max(n, 1), dtype=np.int32)
-        self._chk(self._lib.lsqr_lm_fit_many(self._h, L.ptr(recs), self.ND * 8, L.ptr(offs), n, L.ptr(m),
-                                             L.ptr(x0), L.ptr(params), fits, L.ptr(status)))
-        status, params = status[:n], params[:n]
-        params[status != L.OK] = 0.0
-        fi = np.ctypeslib.as_array(fits)[:n]
-        return dict(status=status, params=params, lm_info=fi["lm_info"].copy(), lm_nfev=fi["lm_nfev"].copy(),
-                    cost=fi["cost"].copy(), n_used=fi["n_used"].copy())
+        return self._fit_many(self._lib.lsqr_lm_fit_many, problems, masks, ("lm_info", "lm_nfev", "cost", "n_used"),
+                              x0=x0)
 
     def ransac_many_dense(self, problems, p, seeds=None, want_consensus=True):
         """ransac_many for the dense linear system (lsqr_ransac_many_dense, DenseLinearEquationSystemParameters-
         Estimator<double,n>); the context's model must be DENSE, else LsqrError(ERR_INVALID).  Records are n + 1
         doubles (a, b).  Problem j is decided as ransac(p, seed=seeds[j]) on its records alone.  -> ransac_many's
         dict plus the array reserved (fit.reserved: 1 where the finish took the double-double route)."""
-        if self.cfg is None:
-            raise L.LsqrError(L.ERR_STATE, "set_model has not been called")
-        recs, offs = self._many_records(problems)
-        n = len(offs) - 1
-        seeds = (1 + np.arange(n, dtype=np.uint64)) if seeds is None else np.ascontiguousarray(seeds, dtype=np.uint64)
-        if seeds.shape != (n,):
-            raise ValueError("one seed per problem")
-        params = np.zeros((max(n, 1), self.P))
-        total = int(offs[-1]) if n else 0
-        cons = np.zeros(max(total, 1), dtype=np.uint8) if want_consensus else None
-        infos = (L.RansacInfo * max(n, 1))()
-        status = np.zeros(max(n, 1), dtype=np.int32)
-        self._chk(self._lib.lsqr_ransac_many_dense(self._h, L.ptr(recs), self.ND * 8, L.ptr(offs), n, float(p),
-                                                   L.ptr(seeds), L.ptr(params), L.ptr(cons), infos, L.ptr(status)))
-        status, params = status[:n], params[:n]
-        params[status != L.OK] = 0.0
-        inf = np.ctypeslib.as_array(infos)[:n]
-        f = lambda name: inf[name].copy()
-        return dict(status=status, fraction=f("fraction"), iterations=f("iterations"), best_index=f("best_index"),
-                    best_votes=f("best_votes"), evaluated=f("evaluated"), n_params=f("n_params"),
-                    n_used=inf["fit"]["n_used"].copy(), reserved=inf["fit"]["reserved"].copy(), params=params,
-                    consensus=cons[:total] if cons is not None else None, offsets=offs)
+        return self._ransac_many(self._lib.lsqr_ransac_many_dense, problems, p, seeds, want_consensus,
+                                 extra=("reserved",))
 
     def dense_fit_many(self, problems, masks=None):
         """DenseLinearEquationSystemParametersEstimator::leastSquaresEstimate of many row sets in one call
         (lsqr_dense_fit_many).  problems as for ransac_many; masks (optional): one byte per record, aligned with the
         flat records.  -> dict of arrays: status (OK / EMPTY / ERR_INVALID for an empty set or mask), params (n x P,
         zero rows where status is not OK), n_params, reserved (1: the double-double route) and n_used."""
-        if self.cfg is None:
-            raise L.LsqrError(L.ERR_STATE, "set_model has not been called")
-        recs, offs = self._many_records(problems)
-        n = len(offs) - 1
-        m = None
-        if masks is not None:
-            m = np.ascontiguousarray(masks, dtype=np.uint8).reshape(-1)
-            if m.shape[0] != int(offs[-1]):
-                raise ValueError("one mask byte per record")
-        params = np.zeros((max(n, 1), self.P))
-        fits = (L.FitInfo * max(n, 1))()
-        status = np.zeros(max(n, 1), dtype=np.int32)
-        self._chk(self._lib.lsqr_dense_fit_many(self._h, L.ptr(recs), self.ND * 8, L.ptr(offs), n, L.ptr(m),
-                                                L.ptr(params), fits, L.ptr(status)))
-        status, params = status[:n], params[:n]
-        params[status != L.OK] = 0.0
-        fi = np.ctypeslib.as_array(fits)[:n]
-        return dict(status=status, params=params, n_params=fi["n_params"].copy(), reserved=fi["reserved"].copy(),
-                    n_used=fi["n_used"].copy())
+        return self._fit_many(self._lib.lsqr_dense_fit_many, problems, masks, ("n_params", "reserved", "n_used"))
 
     def batch_fit(self, seed, first, H, want_consensus=False):
         """One fixed-size batch end to end on the device (lsqr_batch_fit): winner of hypotheses

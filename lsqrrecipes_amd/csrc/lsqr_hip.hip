@@ -3782,68 +3782,22 @@ int lsqr_ransac(lsqr_ctx *c, double p, uint64_t seed, const uint32_t *subsets, s
                        consensus_out, info);
 }
 
-// ---- many independent RANSAC<T,S>::compute() problems (many.h) ------------------------------------------------
-int lsqr_ransac_many(lsqr_ctx *c, const void *host_records, size_t stride_bytes, const uint64_t *offsets,
-                     size_t n_problems, double p, const uint64_t *seeds, double *params_out, uint8_t *consensus_out,
-                     lsqr_ransac_info *infos, int32_t *status_out) {
+// ---- many independent problems in one call (many.h, many_lm.h, many_dense.h) ---------------------------------------
+// What the six batched entry points share.  The checks, in the contract's order: the context is ready; the entry
+// point's model gate (gate(): LSQR_OK, or its own fail()); n == 0 is LSQR_OK with every output untouched; null
+// arguments (args: the entry point's own pointers are all there); p, where given (the RANSAC kind); offsets; records;
+// stride.  Then the job from the context -- the caller has set what its kind alone has: p, the seeds and the outputs
+// -- and run(J, tag), dispatched on the model.  J.lm is the geometric sphere, which only the _lm gates let through.
+extern "C++" {
+template <class Gate, class Run>
+static int many_call(lsqr_ctx *c, const char *fn, ManyJob &J, const void *host_records, size_t stride_bytes,
+                     const uint64_t *offsets, size_t n, bool args, const double *p, Gate &&gate, Run &&run) {
   int st = need_ready(c, false);
   if (st != LSQR_OK) return st;
-  const lsqr_model_cfg &cfg = c->cfg;
-  if (cfg.model != LSQR_MODEL_PLANE && cfg.model != LSQR_MODEL_LINE && cfg.model != LSQR_MODEL_SPHERE &&
-      cfg.model != LSQR_MODEL_ABSOR && cfg.model != LSQR_MODEL_PIVOT && cfg.model != LSQR_MODEL_RAY &&
-      cfg.model != LSQR_MODEL_LINE2D)
-    return fail(c, LSQR_ERR_INVALID,
-                "lsqr_ransac_many: plane, line, algebraic sphere, absolute orientation, pivot, ray and 2-D line only "
-                "(model %d)", cfg.model);
-  if (cfg.model == LSQR_MODEL_SPHERE && cfg.ls_type != LSQR_LS_ALGEBRAIC)
-    return fail(c, LSQR_ERR_INVALID, "lsqr_ransac_many: the geometric (LM) sphere fit is not batched; use LSQR_LS_ALGEBRAIC");
-  if (n_problems == 0) return LSQR_OK;
-  if (!offsets || !seeds || !params_out || !infos || !status_out)
-    return fail(c, LSQR_ERR_INVALID, "lsqr_ransac_many: null argument");
-  if (!(p > 0.0) || !(p < 1.0)) return fail(c, LSQR_ERR_INVALID, "lsqr_ransac_many: p must lie in (0, 1)");
-  if (offsets[0] != 0) return fail(c, LSQR_ERR_INVALID, "lsqr_ransac_many: offsets[0] must be 0");
-  for (size_t j = 0; j < n_problems; j++) {
-    if (offsets[j + 1] < offsets[j]) return fail(c, LSQR_ERR_INVALID, "lsqr_ransac_many: offsets decrease at %zu", j);
-    if (offsets[j + 1] - offsets[j] > 0xFFFFFFF0ull)
-      return fail(c, LSQR_ERR_INVALID, "lsqr_ransac_many: problem %zu has more than 2^32 - 16 records", j);
-  }
-  if (offsets[n_problems] > 0 && !host_records) return fail(c, LSQR_ERR_INVALID, "lsqr_ransac_many: null records");
-  if (stride_bytes < sizeof(double) * (size_t)c->ND)
-    return fail(c, LSQR_ERR_INVALID, "lsqr_ransac_many: stride %zu below the record's %zu bytes", stride_bytes,
-                sizeof(double) * (size_t)c->ND);
-  if (!c->many) c->many = new ManyBufs();
-  ManyJob J;
-  J.stream = c->stream;
-  J.cfg = cfg;
-  J.mc = c->mc;
-  J.host = (const char *)host_records;
-  J.stride = stride_bytes;
-  J.offsets = offsets;
-  J.n = n_problems;
-  J.W = c->ND;  // lsqr_record_doubles(cfg)
-  J.p = p;
-  J.seeds = seeds;
-  J.params_out = params_out;
-  J.consensus_out = consensus_out;
-  J.infos = infos;
-  J.status_out = status_out;
-  J.max_iter = c->opt_max_iter;
-  J.round_cap = c->opt_many_round > 0 ? (size_t)c->opt_many_round : kManyRoundDefault;
-  J.buf = c->many;
-  J.err[0] = 0;
-  st = dispatch(cfg, [&](auto tag) -> int {
-    typedef typename decltype(tag)::type M;
-    if constexpr (ManyModel<M>::value) return many_run<M>(J);
-    else return LSQR_ERR_INVALID;
-  });
-  if (st != LSQR_OK) return fail(c, st, "lsqr_ransac_many: %s", J.err[0] ? J.err : "model not in this build");
-  return LSQR_OK;
-}
-
-// ---- the same with the geometric sphere's Levenberg-Marquardt finish (many.h + many_lm.h) ----------------------------
-// the checks lsqr_ransac_many makes of its record arguments (after its own of the model and the outputs)
-static int many_check_records(lsqr_ctx *c, const char *fn, const void *host_records, size_t stride_bytes,
-                              const uint64_t *offsets, size_t n) {
+  if ((st = gate()) != LSQR_OK) return st;
+  if (n == 0) return LSQR_OK;
+  if (!offsets || !args) return fail(c, LSQR_ERR_INVALID, "%s: null argument", fn);
+  if (p && (!(*p > 0.0) || !(*p < 1.0))) return fail(c, LSQR_ERR_INVALID, "%s: p must lie in (0, 1)", fn);
   if (offsets[0] != 0) return fail(c, LSQR_ERR_INVALID, "%s: offsets[0] must be 0", fn);
   for (size_t j = 0; j < n; j++) {
     if (offsets[j + 1] < offsets[j]) return fail(c, LSQR_ERR_INVALID, "%s: offsets decrease at %zu", fn, j);
@@ -3854,13 +3808,6 @@ static int many_check_records(lsqr_ctx *c, const char *fn, const void *host_reco
   if (stride_bytes < sizeof(double) * (size_t)c->ND)
     return fail(c, LSQR_ERR_INVALID, "%s: stride %zu below the record's %zu bytes", fn, stride_bytes,
                 sizeof(double) * (size_t)c->ND);
-  return LSQR_OK;
-}
-
-// the context's part of a batched job (lsqr_ransac_many_lm / _dense, lsqr_lm_fit_many / lsqr_dense_fit_many): records,
-// model, stream, buffers, the loop's options; round_cap 0 when the option is unset (the caller's default)
-static void many_job(lsqr_ctx *c, ManyJob &J, const void *host_records, size_t stride_bytes, const uint64_t *offsets,
-                     size_t n) {
   if (!c->many) c->many = new ManyBufs();
   J.stream = c->stream;
   J.cfg = c->cfg;
@@ -3869,144 +3816,145 @@ static void many_job(lsqr_ctx *c, ManyJob &J, const void *host_records, size_t s
   J.stride = stride_bytes;
   J.offsets = offsets;
   J.n = n;
-  J.W = c->ND;
+  J.W = c->ND;  // lsqr_record_doubles(cfg)
   J.max_iter = c->opt_max_iter;
   J.round_cap = c->opt_many_round > 0 ? (size_t)c->opt_many_round : 0;
-  J.buf = c->many;
-  J.err[0] = 0;
-}
-
-static void many_job_lm(lsqr_ctx *c, ManyJob &J, const void *host_records, size_t stride_bytes,
-                        const uint64_t *offsets, size_t n) {
-  many_job(c, J, host_records, stride_bytes, offsets, n);
-  if (J.round_cap == 0) J.round_cap = kManyRoundDefault;
-  J.lm = true;
+  J.lm = c->cfg.model == LSQR_MODEL_SPHERE && c->cfg.ls_type == LSQR_LS_GEOMETRIC;
   lm_settings(c->cfg, &J.lm_n, &J.lm_ftol, &J.lm_xtol, &J.lm_gtol, &J.lm_maxfev);
+  J.dense_fast = c->opt_dense_fast ? 1 : 0;
+  J.dense_dd = c->opt_dense_dd ? 1 : 0;
+  J.buf = c->many;
+  st = dispatch(c->cfg, [&](auto tag) -> int { return run(J, tag); });
+  if (st != LSQR_OK) return fail(c, st, "%s: %s", fn, J.err[0] ? J.err : "model not in this build");
+  return LSQR_OK;
 }
 
-int lsqr_ransac_many_lm(lsqr_ctx *c, const void *host_records, size_t stride_bytes, const uint64_t *offsets,
-                        size_t n_problems, double p, const uint64_t *seeds, double *params_out,
-                        uint8_t *consensus_out, lsqr_ransac_info *infos, int32_t *status_out) {
-  int st = need_ready(c, false);
-  if (st != LSQR_OK) return st;
-  if (c->cfg.model != LSQR_MODEL_SPHERE || c->cfg.ls_type != LSQR_LS_GEOMETRIC)
-    return fail(c, LSQR_ERR_INVALID,
-                "lsqr_ransac_many_lm: the geometric sphere only (model %d, ls_type %d); the closed-form fits are "
-                "batched by lsqr_ransac_many", c->cfg.model, c->cfg.ls_type);
-  if (n_problems == 0) return LSQR_OK;
-  if (!offsets || !seeds || !params_out || !infos || !status_out)
-    return fail(c, LSQR_ERR_INVALID, "lsqr_ransac_many_lm: null argument");
-  if (!(p > 0.0) || !(p < 1.0)) return fail(c, LSQR_ERR_INVALID, "lsqr_ransac_many_lm: p must lie in (0, 1)");
-  if ((st = many_check_records(c, "lsqr_ransac_many_lm", host_records, stride_bytes, offsets, n_problems)) != LSQR_OK)
-    return st;
+// the RANSAC kind: lsqr_ransac_many, _lm and _dense take the same arguments
+template <class Gate, class Run>
+static int many_ransac_call(lsqr_ctx *c, const char *fn, const void *host_records, size_t stride_bytes,
+                            const uint64_t *offsets, size_t n_problems, double p, const uint64_t *seeds,
+                            double *params_out, uint8_t *consensus_out, lsqr_ransac_info *infos, int32_t *status_out,
+                            Gate &&gate, Run &&run) {
   ManyJob J;
-  many_job_lm(c, J, host_records, stride_bytes, offsets, n_problems);
   J.p = p;
   J.seeds = seeds;
   J.params_out = params_out;
   J.consensus_out = consensus_out;
   J.infos = infos;
   J.status_out = status_out;
-  st = dispatch(c->cfg, [&](auto tag) -> int {
-    typedef typename decltype(tag)::type M;
-    if constexpr (ManyModel<M>::value && requires { M::NMOM_LM; }) return many_run<M>(J);
-    else return LSQR_ERR_INVALID;
-  });
-  if (st != LSQR_OK) return fail(c, st, "lsqr_ransac_many_lm: %s", J.err[0] ? J.err : "model not in this build");
-  return LSQR_OK;
+  return many_call(c, fn, J, host_records, stride_bytes, offsets, n_problems,
+                   seeds && params_out && infos && status_out, &p, gate, run);
+}
+}  // extern "C++"
+
+// many independent RANSAC<T,S>::compute() problems of the closed-form models (many.h)
+int lsqr_ransac_many(lsqr_ctx *c, const void *host_records, size_t stride_bytes, const uint64_t *offsets,
+                     size_t n_problems, double p, const uint64_t *seeds, double *params_out, uint8_t *consensus_out,
+                     lsqr_ransac_info *infos, int32_t *status_out) {
+  return many_ransac_call(
+      c, "lsqr_ransac_many", host_records, stride_bytes, offsets, n_problems, p, seeds, params_out, consensus_out,
+      infos, status_out,
+      [&]() -> int {
+        const lsqr_model_cfg &cfg = c->cfg;
+        if (cfg.model != LSQR_MODEL_PLANE && cfg.model != LSQR_MODEL_LINE && cfg.model != LSQR_MODEL_SPHERE &&
+            cfg.model != LSQR_MODEL_ABSOR && cfg.model != LSQR_MODEL_PIVOT && cfg.model != LSQR_MODEL_RAY &&
+            cfg.model != LSQR_MODEL_LINE2D)
+          return fail(c, LSQR_ERR_INVALID,
+                      "lsqr_ransac_many: plane, line, algebraic sphere, absolute orientation, pivot, ray and 2-D line "
+                      "only (model %d)", cfg.model);
+        if (cfg.model == LSQR_MODEL_SPHERE && cfg.ls_type != LSQR_LS_ALGEBRAIC)
+          return fail(c, LSQR_ERR_INVALID,
+                      "lsqr_ransac_many: the geometric (LM) sphere fit is not batched; use LSQR_LS_ALGEBRAIC");
+        return LSQR_OK;
+      },
+      [](ManyJob &J, auto tag) -> int {
+        typedef typename decltype(tag)::type M;
+        if constexpr (ManyModel<M>::value) return many_run<M>(J);
+        else return LSQR_ERR_INVALID;
+      });
+}
+
+// the same with the geometric sphere's Levenberg-Marquardt finish (many.h + many_lm.h)
+int lsqr_ransac_many_lm(lsqr_ctx *c, const void *host_records, size_t stride_bytes, const uint64_t *offsets,
+                        size_t n_problems, double p, const uint64_t *seeds, double *params_out,
+                        uint8_t *consensus_out, lsqr_ransac_info *infos, int32_t *status_out) {
+  return many_ransac_call(
+      c, "lsqr_ransac_many_lm", host_records, stride_bytes, offsets, n_problems, p, seeds, params_out, consensus_out,
+      infos, status_out,
+      [&]() -> int {
+        if (c->cfg.model == LSQR_MODEL_SPHERE && c->cfg.ls_type == LSQR_LS_GEOMETRIC) return LSQR_OK;
+        return fail(c, LSQR_ERR_INVALID,
+                    "lsqr_ransac_many_lm: the geometric sphere only (model %d, ls_type %d); the closed-form fits are "
+                    "batched by lsqr_ransac_many", c->cfg.model, c->cfg.ls_type);
+      },
+      [](ManyJob &J, auto tag) -> int {
+        typedef typename decltype(tag)::type M;
+        if constexpr (ManyModel<M>::value && requires { M::NMOM_LM; }) return many_run<M>(J);
+        else return LSQR_ERR_INVALID;
+      });
 }
 
 int lsqr_lm_fit_many(lsqr_ctx *c, const void *host_records, size_t stride_bytes, const uint64_t *offsets,
                      size_t n_sets, const uint8_t *masks, const double *x0, double *params_out, lsqr_fit_info *fits,
                      int32_t *status_out) {
-  int st = need_ready(c, false);
-  if (st != LSQR_OK) return st;
-  if (c->cfg.model != LSQR_MODEL_SPHERE || c->cfg.ls_type != LSQR_LS_GEOMETRIC)
-    return fail(c, LSQR_ERR_INVALID,
-                "lsqr_lm_fit_many: the geometric sphere only (model %d, ls_type %d); the closed-form fits of many "
-                "problems are batched by lsqr_ransac_many", c->cfg.model, c->cfg.ls_type);
-  if (n_sets == 0) return LSQR_OK;
-  if (!offsets || !x0 || !params_out || !fits || !status_out)
-    return fail(c, LSQR_ERR_INVALID, "lsqr_lm_fit_many: null argument");
-  if ((st = many_check_records(c, "lsqr_lm_fit_many", host_records, stride_bytes, offsets, n_sets)) != LSQR_OK)
-    return st;
   ManyJob J;
-  many_job_lm(c, J, host_records, stride_bytes, offsets, n_sets);
   J.params_out = params_out;
   J.status_out = status_out;
-  st = dispatch(c->cfg, [&](auto tag) -> int {
-    typedef typename decltype(tag)::type M;
-    if constexpr (ManyModel<M>::value && requires { M::NMOM_LM; }) return many_lm_fit<M>(J, masks, x0, fits);
-    else return LSQR_ERR_INVALID;
-  });
-  if (st != LSQR_OK) return fail(c, st, "lsqr_lm_fit_many: %s", J.err[0] ? J.err : "model not in this build");
-  return LSQR_OK;
+  return many_call(
+      c, "lsqr_lm_fit_many", J, host_records, stride_bytes, offsets, n_sets, x0 && params_out && fits && status_out,
+      nullptr,
+      [&]() -> int {
+        if (c->cfg.model == LSQR_MODEL_SPHERE && c->cfg.ls_type == LSQR_LS_GEOMETRIC) return LSQR_OK;
+        return fail(c, LSQR_ERR_INVALID,
+                    "lsqr_lm_fit_many: the geometric sphere only (model %d, ls_type %d); the closed-form fits of many "
+                    "problems are batched by lsqr_ransac_many", c->cfg.model, c->cfg.ls_type);
+      },
+      [&](ManyJob &J, auto tag) -> int {
+        typedef typename decltype(tag)::type M;
+        if constexpr (ManyModel<M>::value && requires { M::NMOM_LM; }) return many_lm_fit<M>(J, masks, x0, fits);
+        else return LSQR_ERR_INVALID;
+      });
 }
 
-// ---- the same for the dense linear system (many_dense.h) -------------------------------------------------------------
-static void many_job_dense(lsqr_ctx *c, ManyJob &J, const void *host_records, size_t stride_bytes,
-                           const uint64_t *offsets, size_t n) {
-  many_job(c, J, host_records, stride_bytes, offsets, n);  // round_cap 0: many_dense_round_cap
-  J.dense_fast = c->opt_dense_fast ? 1 : 0;
-  J.dense_dd = c->opt_dense_dd ? 1 : 0;
-}
-
+// the same for the dense linear system (many_dense.h)
 int lsqr_ransac_many_dense(lsqr_ctx *c, const void *host_records, size_t stride_bytes, const uint64_t *offsets,
                            size_t n_problems, double p, const uint64_t *seeds, double *params_out,
                            uint8_t *consensus_out, lsqr_ransac_info *infos, int32_t *status_out) {
-  int st = need_ready(c, false);
-  if (st != LSQR_OK) return st;
-  if (c->cfg.model != LSQR_MODEL_DENSE)
-    return fail(c, LSQR_ERR_INVALID,
-                "lsqr_ransac_many_dense: the dense linear system only (model %d); the other models are batched by "
-                "lsqr_ransac_many / lsqr_ransac_many_lm", c->cfg.model);
-  if (n_problems == 0) return LSQR_OK;
-  if (!offsets || !seeds || !params_out || !infos || !status_out)
-    return fail(c, LSQR_ERR_INVALID, "lsqr_ransac_many_dense: null argument");
-  if (!(p > 0.0) || !(p < 1.0)) return fail(c, LSQR_ERR_INVALID, "lsqr_ransac_many_dense: p must lie in (0, 1)");
-  if ((st = many_check_records(c, "lsqr_ransac_many_dense", host_records, stride_bytes, offsets, n_problems)) !=
-      LSQR_OK)
-    return st;
-  ManyJob J;
-  many_job_dense(c, J, host_records, stride_bytes, offsets, n_problems);
-  J.p = p;
-  J.seeds = seeds;
-  J.params_out = params_out;
-  J.consensus_out = consensus_out;
-  J.infos = infos;
-  J.status_out = status_out;
-  st = dispatch(c->cfg, [&](auto tag) -> int {
-    typedef typename decltype(tag)::type M;
-    if constexpr (M::IS_DENSE) return many_dense_run<M::NR>(J);
-    else return LSQR_ERR_INVALID;
-  });
-  if (st != LSQR_OK) return fail(c, st, "lsqr_ransac_many_dense: %s", J.err[0] ? J.err : "model not in this build");
-  return LSQR_OK;
+  return many_ransac_call(
+      c, "lsqr_ransac_many_dense", host_records, stride_bytes, offsets, n_problems, p, seeds, params_out,
+      consensus_out, infos, status_out,
+      [&]() -> int {
+        if (c->cfg.model == LSQR_MODEL_DENSE) return LSQR_OK;
+        return fail(c, LSQR_ERR_INVALID,
+                    "lsqr_ransac_many_dense: the dense linear system only (model %d); the other models are batched by "
+                    "lsqr_ransac_many / lsqr_ransac_many_lm", c->cfg.model);
+      },
+      [](ManyJob &J, auto tag) -> int {
+        typedef typename decltype(tag)::type M;
+        if constexpr (M::IS_DENSE) return many_dense_run<M::NR>(J);
+        else return LSQR_ERR_INVALID;
+      });
 }
 
 int lsqr_dense_fit_many(lsqr_ctx *c, const void *host_records, size_t stride_bytes, const uint64_t *offsets,
                         size_t n_sets, const uint8_t *masks, double *params_out, lsqr_fit_info *fits,
                         int32_t *status_out) {
-  int st = need_ready(c, false);
-  if (st != LSQR_OK) return st;
-  if (c->cfg.model != LSQR_MODEL_DENSE)
-    return fail(c, LSQR_ERR_INVALID, "lsqr_dense_fit_many: the dense linear system only (model %d)", c->cfg.model);
-  if (n_sets == 0) return LSQR_OK;
-  if (!offsets || !params_out || !fits || !status_out)
-    return fail(c, LSQR_ERR_INVALID, "lsqr_dense_fit_many: null argument");
-  if ((st = many_check_records(c, "lsqr_dense_fit_many", host_records, stride_bytes, offsets, n_sets)) != LSQR_OK)
-    return st;
   ManyJob J;
-  many_job_dense(c, J, host_records, stride_bytes, offsets, n_sets);
   J.params_out = params_out;
   J.status_out = status_out;
-  st = dispatch(c->cfg, [&](auto tag) -> int {
-    typedef typename decltype(tag)::type M;
-    if constexpr (M::IS_DENSE) return many_dense_fit<M::NR>(J, masks, fits);
-    else return LSQR_ERR_INVALID;
-  });
-  if (st != LSQR_OK) return fail(c, st, "lsqr_dense_fit_many: %s", J.err[0] ? J.err : "model not in this build");
-  return LSQR_OK;
+  return many_call(
+      c, "lsqr_dense_fit_many", J, host_records, stride_bytes, offsets, n_sets, params_out && fits && status_out,
+      nullptr,
+      [&]() -> int {
+        if (c->cfg.model == LSQR_MODEL_DENSE) return LSQR_OK;
+        return fail(c, LSQR_ERR_INVALID, "lsqr_dense_fit_many: the dense linear system only (model %d)",
+                    c->cfg.model);
+      },
+      [&](ManyJob &J, auto tag) -> int {
+        typedef typename decltype(tag)::type M;
+        if constexpr (M::IS_DENSE) return many_dense_fit<M::NR>(J, masks, fits);
+        else return LSQR_ERR_INVALID;
+      });
 }
 
 int lsqr_ransac_exhaustive(lsqr_ctx *c, double *params_out, uint8_t *consensus_out,

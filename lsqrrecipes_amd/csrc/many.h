@@ -24,6 +24,10 @@
 // Independence: every quantity a problem's result depends on is a function of that problem's records alone: its
 // hypotheses (its own stream), its votes (integer sums), its moment block (parts of kManyPart records in record
 // order, reduced in part order).  The round cap only decides which problems share a round.
+//
+// Host side: the frame of a batched call -- many_begin, many_rounds, many_plan_finish, many_stage_finish,
+// many_fetch_finish, many_end for a RANSAC job; many_fit_begin, many_write_fits for a *_fit_many job -- is here, for
+// many_run, the LM stage (many_lm.h) and the dense system (many_dense.h), which add their kernels and what is theirs.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -47,7 +51,34 @@ constexpr int kManyStage = 256;            // records per LDS stage (8-D: 16 KiB
 constexpr uint64_t kManySeg = 16384;       // records per scan tile: longer problems are split, votes summed exactly
 constexpr uint64_t kManyPart = 8192;       // records per workgroup of the finish (fixes the moment sums' order)
 constexpr size_t kManyRoundDefault = 1u << 21;  // hypotheses per round (option many_round_hypotheses = 0)
+
+#if defined(__HIPCC__)
+// a device buffer of the batched calls, grown on demand
+template <class T>
+hipError_t many_grow(T **p, size_t *cap, size_t n) {
+  if (n <= *cap && *p) return hipSuccess;
+  if (*p) (void)hipFree(*p);
+  *p = nullptr;
+  *cap = 0;
+  const size_t want = std::max<size_t>(n + n / 4, 64);
+  hipError_t e = hipMalloc((void **)p, sizeof(T) * want);
+  if (e == hipSuccess) *cap = want;
+  return e;
+}
+#endif
 }  // namespace lsqr
+
+// a HIP call of the batched host code (many.h, many_lm.h, many_dense.h; undefined at the end of the last): J is the
+// job at hand, a ManyJob or the LM stage's ManyLmJob, whose err is the ManyJob's
+#define MANYCHK(call)                                                                                \
+  do {                                                                                               \
+    hipError_t e_ = (call);                                                                          \
+    if (e_ != hipSuccess) {                                                                          \
+      snprintf(J.err, sizeof J.err, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, \
+               __LINE__);                                                                            \
+      return LSQR_ERR_HIP;                                                                           \
+    }                                                                                                \
+  } while (0)
 
 #include "many_lm.h"  // the LM stage of lsqr_ransac_many_lm (its parts are kManyPart inliers)
 
@@ -294,17 +325,6 @@ inline void many_free(ManyBufs *b) {
   delete b;
 }
 
-template <class T>
-hipError_t many_grow(T **p, size_t *cap, size_t n) {
-  if (n <= *cap && *p) return hipSuccess;
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  const size_t want = std::max<size_t>(n + n / 4, 64);
-  hipError_t e = hipMalloc((void **)p, sizeof(T) * want);
-  if (e == hipSuccess) *cap = want;
-  return e;
-}
 // pinned host memory; the caller has synchronised the stream if an old buffer may still be read by a copy
 inline hipError_t many_grow_pinned(char **p, size_t *cap, size_t bytes) {
   if (bytes <= *cap && *p) return hipSuccess;
@@ -317,52 +337,57 @@ inline hipError_t many_grow_pinned(char **p, size_t *cap, size_t bytes) {
   return e;
 }
 
+// One batched call.  The entry point fills it from the context (lsqr_hip.hip: many_call); p, seeds, consensus_out and
+// infos are a RANSAC call's and stay unset in a *_fit_many job, which reads none of them.
 struct ManyJob {
-  hipStream_t stream;
-  lsqr_model_cfg cfg;
-  ModelConsts mc;
-  const char *host;  // records, stride bytes apart
-  size_t stride;
-  const uint64_t *offsets;
-  size_t n;  // problems
-  int W;     // doubles per record (lsqr_record_doubles)
-  double p;
-  const uint64_t *seeds;
-  double *params_out;
-  uint8_t *consensus_out;
-  lsqr_ransac_info *infos;
-  int32_t *status_out;
-  long long max_iter;  // option max_iterations
-  size_t round_cap;    // hypotheses per round (a problem whose batch alone exceeds it gets a round of its own)
-  bool lm = false;     // lsqr_ransac_many_lm: the geometric sphere's LM fit from the algebraic one (many_lm.h)
-  int lm_n = 0, lm_maxfev = 0;  // ... with lm_settings
+  hipStream_t stream = nullptr;
+  lsqr_model_cfg cfg = {};
+  ModelConsts mc = {};
+  const char *host = nullptr;  // records, stride bytes apart
+  size_t stride = 0;
+  const uint64_t *offsets = nullptr;
+  size_t n = 0;  // problems
+  int W = 0;     // doubles per record (lsqr_record_doubles)
+  double p = 0;
+  const uint64_t *seeds = nullptr;
+  double *params_out = nullptr;
+  uint8_t *consensus_out = nullptr;
+  lsqr_ransac_info *infos = nullptr;
+  int32_t *status_out = nullptr;
+  long long max_iter = 0;  // option max_iterations
+  // hypotheses per round (a problem whose batch alone exceeds it gets a round of its own): option
+  // many_round_hypotheses; 0: the path's default, resolved by many_run / many_dense_run
+  size_t round_cap = 0;
+  bool lm = false;  // the geometric sphere: many_run ends in the LM fit from the algebraic one (many_lm.h)
+  int lm_n = 0, lm_maxfev = 0;  // lm_settings
   double lm_ftol = 0, lm_xtol = 0, lm_gtol = 0;
-  int dense_fast = 1, dense_dd = 1;  // lsqr_ransac_many_dense: options dense_fast_solve / dense_dd (many_dense.h)
-  ManyBufs *buf;
-  char err[256];
+  int dense_fast = 1, dense_dd = 1;  // options dense_fast_solve / dense_dd (many_dense.h)
+  ManyBufs *buf = nullptr;
+  std::vector<double> packed;  // many_upload's staging copy of strided records
+  char err[256] = "";
 };
 
-#define MANYCHK(call)                                                                                \
-  do {                                                                                               \
-    hipError_t e_ = (call);                                                                          \
-    if (e_ != hipSuccess) {                                                                          \
-      snprintf(J.err, sizeof J.err, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, \
-               __LINE__);                                                                            \
-      return LSQR_ERR_HIP;                                                                           \
-    }                                                                                                \
-  } while (0)
+// The record width the model's kernels read against the job's.  It cannot differ (J.W is the context's own ND for the
+// same cfg); it is tested once, before anything is written.
+inline int many_check_width(ManyJob &J, int W) {
+  if (W == J.W) return LSQR_OK;
+  snprintf(J.err, sizeof J.err, "record width %d != the model's %d doubles", J.W, W);
+  return LSQR_ERR_INVALID;
+}
 
 // one upload of every problem's records, packed (W doubles per record, copied as raw bytes: the pivot frame's int slot
-// travels as it is); `packed` holds the staging copy of strided records until the copy has been issued
-inline int many_upload(ManyJob &J, int W, uint64_t NT, std::vector<double> &packed) {
+// travels as it is)
+inline int many_upload(ManyJob &J) {
   ManyBufs &B = *J.buf;
+  const uint64_t NT = J.offsets[J.n];
+  const size_t W = J.W;
   const double *src = (const double *)J.host;
   if (NT > 0) {
     MANYCHK(many_grow(&B.d_data, &B.c_data, NT * W));
     if (J.stride != sizeof(double) * W) {
-      packed.resize(NT * W);
-      for (uint64_t i = 0; i < NT; i++) memcpy(&packed[i * W], J.host + i * J.stride, sizeof(double) * W);
-      src = packed.data();
+      J.packed.resize(NT * W);
+      for (uint64_t i = 0; i < NT; i++) memcpy(&J.packed[i * W], J.host + i * J.stride, sizeof(double) * W);
+      src = J.packed.data();
     }
     MANYCHK(hipMemcpyAsync(B.d_data, src, sizeof(double) * W * NT, hipMemcpyHostToDevice, J.stream));
   }
@@ -557,36 +582,247 @@ int many_rounds(ManyJob &J, std::vector<ManyProb> &pr, int K, int SP, uint64_t s
   return LSQR_OK;
 }
 
-template <class M>
-int many_run(ManyJob &J) {
-  constexpr int K = M::K, SP = M::SP;
-  const int W = many_width<M>(J.W);
-  ManyBufs &B = *J.buf;
-  const size_t NP = J.n;
-  const uint64_t NT = J.offsets[NP];
-  const int org_off = fit_origin_offset<M>(J.cfg);
-  static_assert(M::NMOM <= 64, "one lane per moment in k_many_solve");
-  int st0;
+// ---- the frame of a batched call, shared by the closed-form models (many_run), their LM stage and the dense system
+// (many_dense.h).  A RANSAC job: many_begin, many_rounds, many_plan_finish, many_stage_finish + the model's finish
+// kernels, many_fetch_finish, many_end.  A *_fit_many job: many_fit_begin, the model's fit, many_write_fits. --------
 
-  std::vector<ManyProb> pr(NP);
-  for (size_t j = 0; j < NP; j++) {
+// The start of a RANSAC job: every problem's loop state (K: the minimal subset's size; the dense system's is known at
+// run time only), the upload, and room for the winners' rows (SP doubles per problem).  A problem of fewer than K
+// records is RANSAC.hxx:16-19's "return 0": info cleared, status ERR_INVALID, every other output untouched.
+inline int many_begin(ManyJob &J, int W, int K, int SP, std::vector<ManyProb> &pr) {
+  int st;
+  if ((st = many_check_width(J, W)) != LSQR_OK) return st;
+  pr.resize(J.n);
+  for (size_t j = 0; j < J.n; j++) {
     memset(&J.infos[j], 0, sizeof(lsqr_ransac_info));
     const uint64_t n = J.offsets[j + 1] - J.offsets[j];
-    if (n < (uint64_t)K) {  // RANSAC.hxx:16-19: return 0, parameters untouched
+    if (n < (uint64_t)K) {
       J.status_out[j] = LSQR_ERR_INVALID;
       continue;
     }
     host_replay_init(n, K, J.p, pr[j].rs);
     pr[j].live = !pr[j].rs[RS_DONE];
   }
+  if ((st = many_upload(J)) != LSQR_OK) return st;
+  MANYCHK(many_grow(&J.buf->d_best, &J.buf->c_best, std::max<size_t>(J.n, 1) * SP));
+  return LSQR_OK;
+}
 
-  if (W != J.W) {
-    snprintf(J.err, sizeof J.err, "record width %d != the model's %d doubles", J.W, W);
-    return LSQR_ERR_INVALID;
+// The finish of a job.  The problems (sets) with something to fit take the finishing slots f = 0, 1, ... in problem
+// order: slot f is problem fin[f], and its work items are parts [pbeg[f], pbeg[f + 1]), kManyPart records each.
+// counts / outs: each slot's records in use and its fit, after many_fetch_finish.
+struct ManyFinish {
+  std::vector<uint32_t> fin, pbeg = {0};
+  std::vector<ManyPart> parts;
+  std::vector<unsigned long long> counts;
+  std::vector<SolveOut> outs;
+  size_t size() const { return fin.size(); }
+  // problem j = records [r0, r1), its moments summed about record org (where the model's kernels read one)
+  void add(uint32_t j, uint64_t r0, uint64_t r1, uint64_t org) {
+    const uint32_t f = (uint32_t)fin.size();
+    fin.push_back(j);
+    for (uint64_t r = r0; r < r1; r += kManyPart)
+      parts.push_back(ManyPart{r, std::min<uint64_t>(r1, r + kManyPart), org, j, f});
+    pbeg.push_back((uint32_t)parts.size());
   }
-  std::vector<double> packed;
-  if ((st0 = many_upload(J, W, NT, packed)) != LSQR_OK) return st0;
-  MANYCHK(many_grow(&B.d_best, &B.c_best, std::max<size_t>(NP, 1) * SP));
+};
+
+// The plan of a RANSAC job's finish, after the rounds: finish_ransac's info fields of every problem that ran; status
+// EMPTY where there is no winner or no vote; a finishing slot for the others.  org(j, q): the origin record of
+// problem j's parts.
+template <class Org>
+ManyFinish many_plan_finish(ManyJob &J, const std::vector<ManyProb> &pr, int K, Org &&org) {
+  ManyFinish F;
+  for (size_t j = 0; j < J.n; j++) {
+    const uint64_t n = J.offsets[j + 1] - J.offsets[j];
+    if (n < (uint64_t)K) continue;
+    const ManyProb &q = pr[j];
+    lsqr_ransac_info &info = J.infos[j];
+    info.iterations = q.rs[RS_I];
+    info.best_index = q.rs[RS_BEST_IDX];
+    info.evaluated = q.evaluated;
+    info.best_votes = (uint32_t)q.rs[RS_BEST];
+    info.fraction = (double)info.best_votes / (double)n;
+    info.n_params = 0;
+    if (!q.rs[RS_HAS] || info.best_votes == 0) {
+      J.status_out[j] = LSQR_EMPTY;
+      continue;
+    }
+    F.add((uint32_t)j, J.offsets[j], J.offsets[j + 1], org(j, q));
+  }
+  return F;
+}
+
+// The finish tables of F (not empty) onto the device, staged through h_stage: parts, pbeg and, where a kernel reads it
+// (with_fin), fin; room for the slots' counts and fits, the counts zeroed.
+inline int many_stage_finish(ManyJob &J, const ManyFinish &F, bool with_fin) {
+  ManyBufs &B = *J.buf;
+  const size_t NF = F.size();
+  const size_t b_parts = sizeof(ManyPart) * F.parts.size(), b_pbeg = sizeof(uint32_t) * F.pbeg.size();
+  const size_t o_pbeg = (b_parts + 15) & ~(size_t)15, o_fin = (o_pbeg + b_pbeg + 15) & ~(size_t)15;
+  MANYCHK(many_grow(&B.d_parts, &B.c_parts, F.parts.size()));
+  MANYCHK(many_grow(&B.d_pbeg, &B.c_pbeg, F.pbeg.size()));
+  if (with_fin) MANYCHK(many_grow(&B.d_fin, &B.c_fin, NF));
+  MANYCHK(many_grow(&B.d_counts, &B.c_counts, NF));
+  MANYCHK(many_grow(&B.d_out, &B.c_out, NF));
+  MANYCHK(many_grow_pinned(&B.h_stage, &B.c_stage, with_fin ? o_fin + sizeof(uint32_t) * NF : o_pbeg + b_pbeg));
+  memcpy(B.h_stage, F.parts.data(), b_parts);
+  memcpy(B.h_stage + o_pbeg, F.pbeg.data(), b_pbeg);
+  MANYCHK(hipMemcpyAsync(B.d_parts, B.h_stage, b_parts, hipMemcpyHostToDevice, J.stream));
+  MANYCHK(hipMemcpyAsync(B.d_pbeg, B.h_stage + o_pbeg, b_pbeg, hipMemcpyHostToDevice, J.stream));
+  if (with_fin) {
+    memcpy(B.h_stage + o_fin, F.fin.data(), sizeof(uint32_t) * NF);
+    MANYCHK(hipMemcpyAsync(B.d_fin, B.h_stage + o_fin, sizeof(uint32_t) * NF, hipMemcpyHostToDevice, J.stream));
+  }
+  MANYCHK(hipMemsetAsync(B.d_counts, 0, sizeof(unsigned long long) * NF, J.stream));
+  return LSQR_OK;
+}
+
+// The slots' counts and fits back from the device, behind the finish kernels, and the job's synchronisation.  A RANSAC
+// job (ransac) also takes the consensus bytes from B.d_mask and checks, as finish_ransac does, that every winner's
+// mask count is its scan's vote.
+inline int many_fetch_finish(ManyJob &J, ManyFinish &F, bool ransac) {
+  ManyBufs &B = *J.buf;
+  const size_t NF = F.size();
+  const uint64_t NT = J.offsets[J.n];
+  F.counts.assign(NF, 0);
+  F.outs.assign(NF, SolveOut());
+  if (NF) {
+    MANYCHK(hipMemcpyAsync(F.counts.data(), B.d_counts, sizeof(unsigned long long) * NF, hipMemcpyDeviceToHost,
+                           J.stream));
+    MANYCHK(hipMemcpyAsync(F.outs.data(), B.d_out, sizeof(SolveOut) * NF, hipMemcpyDeviceToHost, J.stream));
+    if (ransac && J.consensus_out && NT)
+      MANYCHK(hipMemcpyAsync(J.consensus_out, B.d_mask, NT, hipMemcpyDeviceToHost, J.stream));
+  }
+  MANYCHK(hipStreamSynchronize(J.stream));
+  for (size_t f = 0; f < NF; f++) {
+    const uint32_t j = F.fin[f];
+    if (ransac && F.counts[f] != J.infos[j].best_votes) {
+      snprintf(J.err, sizeof J.err, "problem %u: consensus mask count %llu != scan votes %u", j, F.counts[f],
+               J.infos[j].best_votes);
+      return LSQR_ERR_HIP;
+    }
+  }
+  return LSQR_OK;
+}
+
+// The end of a RANSAC job: finish_ransac's outputs of every finishing problem from its final fit F.outs[f], whose
+// lm_info / lm_nfev / pad go to fit.lm_info / lm_nfev / reserved (the caller has set what its solve does not write);
+// P parameters per problem; a failed fit is EMPTY with fit.n_params 0.  The problems without a winner have no
+// consensus set: their bytes are zeroed.
+inline void many_end(ManyJob &J, const ManyFinish &F, int P) {
+  std::vector<uint8_t> has_mask(J.n, 0);
+  for (size_t f = 0; f < F.size(); f++) {
+    const uint32_t j = F.fin[f];
+    const SolveOut &o = F.outs[f];
+    lsqr_ransac_info &info = J.infos[j];
+    has_mask[j] = 1;
+    info.fit.n_params = o.ok ? o.n_params : 0;
+    info.fit.lm_info = o.lm_info;
+    info.fit.lm_nfev = o.lm_nfev;
+    info.fit.reserved = o.pad;
+    info.fit.n_used = F.counts[f];
+    info.fit.cost = o.cost;
+    if (!o.ok) {
+      J.status_out[j] = LSQR_EMPTY;
+      continue;
+    }
+    info.n_params = o.n_params;
+    for (int k = 0; k < P; k++) J.params_out[(size_t)j * P + k] = o.params[k];
+    J.status_out[j] = LSQR_OK;
+  }
+  if (J.consensus_out)
+    for (size_t j = 0; j < J.n; j++)
+      if (!has_mask[j] && J.offsets[j + 1] > J.offsets[j])
+        memset(J.consensus_out + J.offsets[j], 0, J.offsets[j + 1] - J.offsets[j]);
+}
+
+// The plan of a *_fit_many job: set j = records [offsets[j], offsets[j+1]) where masks (nullable: every record) is
+// set.  sets / used: the sets with something to fit and their records in use; a set with none has status ERR_INVALID
+// and its outputs untouched.  With a set to fit, the records go up, and the masks to B.d_mask.
+inline int many_fit_begin(ManyJob &J, int W, const uint8_t *masks, std::vector<uint32_t> &sets,
+                          std::vector<uint64_t> &used) {
+  ManyBufs &B = *J.buf;
+  const uint64_t NT = J.offsets[J.n];
+  int st;
+  if ((st = many_check_width(J, W)) != LSQR_OK) return st;
+  for (size_t j = 0; j < J.n; j++) {
+    const uint64_t r0 = J.offsets[j], r1 = J.offsets[j + 1];
+    uint64_t cnt = r1 - r0;
+    if (masks) {
+      cnt = 0;
+      for (uint64_t i = r0; i < r1; i++) cnt += masks[i] != 0;
+    }
+    if (cnt == 0) {
+      J.status_out[j] = LSQR_ERR_INVALID;
+      continue;
+    }
+    sets.push_back((uint32_t)j);
+    used.push_back(cnt);
+  }
+  if (sets.empty()) return LSQR_OK;
+  if ((st = many_upload(J)) != LSQR_OK) return st;
+  if (masks) {
+    MANYCHK(many_grow(&B.d_mask, &B.c_mask, NT));
+    MANYCHK(hipMemcpyAsync(B.d_mask, masks, NT, hipMemcpyHostToDevice, J.stream));
+  }
+  return LSQR_OK;
+}
+
+// The end of a *_fit_many job: the lsqr_fit_info, status and parameters (P per set) of the fitted sets from their fits
+// outs[q] (lm_info / lm_nfev / pad as in many_end).  n_params is the solver's even where the fit failed; a failed fit
+// is EMPTY and hands out no parameters (lsqr_lm_step, lsqr_ls_fit).
+inline void many_write_fits(ManyJob &J, lsqr_fit_info *fits, int P, const std::vector<uint32_t> &sets,
+                            const std::vector<uint64_t> &used, const std::vector<SolveOut> &outs) {
+  for (size_t q = 0; q < sets.size(); q++) {
+    const uint32_t j = sets[q];
+    const SolveOut &o = outs[q];
+    lsqr_fit_info &fi = fits[j];
+    memset(&fi, 0, sizeof fi);
+    fi.n_params = o.n_params;
+    fi.lm_info = o.lm_info;
+    fi.lm_nfev = o.lm_nfev;
+    fi.reserved = o.pad;
+    fi.n_used = used[q];
+    fi.cost = o.cost;
+    if (!o.ok) {
+      J.status_out[j] = LSQR_EMPTY;
+      continue;
+    }
+    for (int k = 0; k < o.n_params; k++) J.params_out[(size_t)j * P + k] = o.params[k];
+    J.status_out[j] = LSQR_OK;
+  }
+}
+
+// The LM stage's job over J's upload: the mask (nullable: every record) and the starts (x0_stride doubles apart), both
+// on the device.  A finished LM problem is read as the SolveOut of the shared frame (pad: the stall diagnostic).
+inline ManyLmJob many_lm_job(ManyJob &J, const uint8_t *d_mask, const double *d_x0, size_t x0_stride) {
+  return ManyLmJob{J.stream, J.buf->d_data, d_mask,    d_x0,      x0_stride, J.lm_n,
+                   J.lm_maxfev, J.lm_ftol,    J.lm_xtol, J.lm_gtol, &J.buf->lm, J.err};
+}
+inline SolveOut many_lm_solve_out(const ManyLmOut &r) {
+  SolveOut o = {};
+  o.ok = r.ok;
+  o.n_params = r.n_params;
+  o.lm_info = r.lm_info;
+  o.lm_nfev = r.lm_nfev;
+  o.pad = r.stall;
+  o.cost = r.cost;
+  for (int k = 0; k < LM_NMAX; k++) o.params[k] = r.params[k];
+  return o;
+}
+
+template <class M>
+int many_run(ManyJob &J) {
+  constexpr int K = M::K, SP = M::SP, P = M::P;
+  const int W = many_width<M>(J.W);
+  ManyBufs &B = *J.buf;
+  const int org_off = fit_origin_offset<M>(J.cfg);
+  static_assert(M::NMOM <= 64, "one lane per moment in k_many_solve");
+  int st0;
+  if (J.round_cap == 0) J.round_cap = kManyRoundDefault;
+  std::vector<ManyProb> pr;
+  if ((st0 = many_begin(J, W, K, SP, pr)) != LSQR_OK) return st0;
 
   if ((st0 = many_rounds(J, pr, K, SP, kManySeg, [&](size_t n_items, uint64_t Ht, size_t n_tiles) -> int {
          hipLaunchKernelGGL((k_many_sample_estimate<M>), dim3((unsigned)((Ht + kBlock - 1) / kBlock)), dim3(kBlock),
@@ -601,147 +837,48 @@ int many_run(ManyJob &J) {
     return st0;
 
   // ---- finish: finish_ransac for every problem with a winner -----------------------------------------------------
-  std::vector<uint32_t> fin, pbeg;
-  std::vector<ManyPart> parts;
-  for (size_t j = 0; j < NP; j++) {
-    const uint64_t n = J.offsets[j + 1] - J.offsets[j];
-    if (n < (uint64_t)K) continue;
-    ManyProb &q = pr[j];
-    lsqr_ransac_info &info = J.infos[j];
-    info.iterations = q.rs[RS_I];
-    info.best_index = q.rs[RS_BEST_IDX];
-    info.evaluated = q.evaluated;
-    info.best_votes = (uint32_t)q.rs[RS_BEST];
-    info.fraction = (double)info.best_votes / (double)n;
-    info.n_params = 0;
-    if (!q.rs[RS_HAS] || info.best_votes == 0) {
-      J.status_out[j] = LSQR_EMPTY;
-      continue;
-    }
-    const uint32_t f = (uint32_t)fin.size();
-    fin.push_back((uint32_t)j);
-    pbeg.push_back((uint32_t)parts.size());
+  ManyFinish F = many_plan_finish(J, pr, K, [&](size_t j, const ManyProb &q) {
     uint64_t org = J.offsets[j];  // (unused with org_off >= 0)
     if (org_off < 0) {  // the winner's first drawn record, as lsqr_ransac reads it from d_subsets
       uint32_t idx[K], sorted[K];
-      ctr_subset(J.seeds[j], q.rs[RS_BEST_IDX], n, K, idx, sorted);
+      ctr_subset(J.seeds[j], q.rs[RS_BEST_IDX], J.offsets[j + 1] - J.offsets[j], K, idx, sorted);
       org += idx[0];
     }
-    for (uint64_t r = 0; r < n; r += kManyPart)
-      parts.push_back(ManyPart{J.offsets[j] + r, J.offsets[j] + std::min<uint64_t>(n, r + kManyPart), org,
-                               (uint32_t)j, f});
-  }
-  pbeg.push_back((uint32_t)parts.size());
-  const size_t NF = fin.size();
-  std::vector<unsigned long long> counts(NF);
-  std::vector<SolveOut> outs(NF);
+    return org;
+  });
+  const size_t NF = F.size();
   if (NF) {
-    MANYCHK(many_grow(&B.d_parts, &B.c_parts, parts.size()));
-    MANYCHK(many_grow(&B.d_pbeg, &B.c_pbeg, pbeg.size()));
-    MANYCHK(many_grow(&B.d_fin, &B.c_fin, NF));
-    MANYCHK(many_grow(&B.d_counts, &B.c_counts, NF));
-    MANYCHK(many_grow(&B.d_out, &B.c_out, NF));
-    MANYCHK(many_grow(&B.d_partials, &B.c_partials, parts.size() * M::NMOM));
-    MANYCHK(many_grow(&B.d_mask, &B.c_mask, NT));
-    const size_t b_parts = sizeof(ManyPart) * parts.size(), o_pbeg = (b_parts + 15) & ~(size_t)15;
-    const size_t o_fin = (o_pbeg + sizeof(uint32_t) * pbeg.size() + 15) & ~(size_t)15;
-    MANYCHK(many_grow_pinned(&B.h_stage, &B.c_stage, o_fin + sizeof(uint32_t) * NF));
-    memcpy(B.h_stage, parts.data(), b_parts);
-    memcpy(B.h_stage + o_pbeg, pbeg.data(), sizeof(uint32_t) * pbeg.size());
-    memcpy(B.h_stage + o_fin, fin.data(), sizeof(uint32_t) * NF);
-    MANYCHK(hipMemcpyAsync(B.d_parts, B.h_stage, b_parts, hipMemcpyHostToDevice, J.stream));
-    MANYCHK(hipMemcpyAsync(B.d_pbeg, B.h_stage + o_pbeg, sizeof(uint32_t) * pbeg.size(), hipMemcpyHostToDevice,
-                           J.stream));
-    MANYCHK(hipMemcpyAsync(B.d_fin, B.h_stage + o_fin, sizeof(uint32_t) * NF, hipMemcpyHostToDevice, J.stream));
-    MANYCHK(hipMemsetAsync(B.d_counts, 0, sizeof(unsigned long long) * NF, J.stream));
-    hipLaunchKernelGGL((k_many_mask_moments<M>), dim3((unsigned)parts.size()), dim3(kBlock), 0, J.stream, B.d_data,
+    if ((st0 = many_stage_finish(J, F, true)) != LSQR_OK) return st0;
+    MANYCHK(many_grow(&B.d_partials, &B.c_partials, F.parts.size() * M::NMOM));
+    MANYCHK(many_grow(&B.d_mask, &B.c_mask, J.offsets[J.n]));
+    hipLaunchKernelGGL((k_many_mask_moments<M>), dim3((unsigned)F.parts.size()), dim3(kBlock), 0, J.stream, B.d_data,
                        W, B.d_parts, B.d_best, org_off, J.mc, B.d_mask, B.d_counts, B.d_partials);
     MANYCHK(hipGetLastError());
     hipLaunchKernelGGL((k_many_solve<M>), dim3((unsigned)NF), dim3(64), 0, J.stream, B.d_data, W, B.d_parts,
                        B.d_partials, B.d_pbeg, B.d_fin, B.d_best, org_off, J.mc, B.d_out);
     MANYCHK(hipGetLastError());
-    MANYCHK(hipMemcpyAsync(counts.data(), B.d_counts, sizeof(unsigned long long) * NF, hipMemcpyDeviceToHost,
-                           J.stream));
-    MANYCHK(hipMemcpyAsync(outs.data(), B.d_out, sizeof(SolveOut) * NF, hipMemcpyDeviceToHost, J.stream));
-    if (J.consensus_out && NT)
-      MANYCHK(hipMemcpyAsync(J.consensus_out, B.d_mask, NT, hipMemcpyDeviceToHost, J.stream));
   }
-  MANYCHK(hipStreamSynchronize(J.stream));
-  for (size_t f = 0; f < NF; f++) {
-    const uint32_t j = fin[f];
-    if (counts[f] != J.infos[j].best_votes) {
-      snprintf(J.err, sizeof J.err, "problem %u: consensus mask count %llu != scan votes %u", j, counts[f],
-               J.infos[j].best_votes);
-      return LSQR_ERR_HIP;
-    }
-  }
-  const int P = M::P;
-  // lsqr_ransac_many_lm: the LM fit of every consensus set whose algebraic fit succeeded, started there
-  // (run_fit: Sphere...hxx:231-232 -- a failed algebraic fit is the empty result)
-  std::vector<int> lm_of(J.lm ? NF : 0, -1);
-  std::vector<ManyLmOut> lm_res;
+  if ((st0 = many_fetch_finish(J, F, true)) != LSQR_OK) return st0;
+  for (SolveOut &o : F.outs) o.lm_info = o.lm_nfev = o.pad = 0;  // a closed-form fit's (solve_small writes no pad)
+  // lsqr_ransac_many_lm: the LM fit of every consensus set whose algebraic fit succeeded, started there (run_fit:
+  // Sphere...hxx:231-232 -- a failed algebraic fit is the empty result); its result replaces the algebraic one
+  // (finish_ransac after run_fit's LM branch)
   if constexpr (requires { M::NMOM_LM; }) {
     if (J.lm) {
       std::vector<ManyLmProb> lp;
       for (size_t f = 0; f < NF; f++) {
-        if (!outs[f].ok) continue;
-        const uint32_t j = fin[f];
-        lm_of[f] = (int)lp.size();
-        ManyLmProb q{};
-        q.rec = J.offsets[j];
-        q.n = J.offsets[j + 1] - J.offsets[j];
-        q.cnt = counts[f];
-        q.xsrc = (uint32_t)f;
-        lp.push_back(q);
+        const uint32_t j = F.fin[f];
+        if (F.outs[f].ok)
+          lp.push_back(ManyLmProb{J.offsets[j], J.offsets[j + 1] - J.offsets[j], 0, F.counts[f], (uint32_t)f, 0});
       }
-      ManyLmJob L;
-      L.stream = J.stream;
-      L.d_data = B.d_data;
-      L.d_mask = B.d_mask;
-      L.d_x0 = (const double *)((const char *)B.d_out + offsetof(SolveOut, params));
-      L.x0_stride = sizeof(SolveOut) / sizeof(double);
-      L.n = J.lm_n;
-      L.maxfev = J.lm_maxfev;
-      L.ftol = J.lm_ftol;
-      L.xtol = J.lm_xtol;
-      L.gtol = J.lm_gtol;
-      L.buf = &B.lm;
-      L.err = J.err;
-      L.err_len = sizeof J.err;
-      if ((st0 = many_lm_run<M>(L, lp, lm_res)) != LSQR_OK) return st0;
+      ManyLmJob L = many_lm_job(J, B.d_mask, (const double *)((const char *)B.d_out + offsetof(SolveOut, params)),
+                                sizeof(SolveOut) / sizeof(double));
+      std::vector<ManyLmOut> res;
+      if ((st0 = many_lm_run<M>(L, lp, res)) != LSQR_OK) return st0;
+      for (size_t q = 0; q < lp.size(); q++) F.outs[lp[q].xsrc] = many_lm_solve_out(res[q]);
     }
   }
-  std::vector<uint8_t> has_mask(NP, 0);
-  for (size_t f = 0; f < NF; f++) {
-    const uint32_t j = fin[f];
-    SolveOut o = outs[f];
-    lsqr_ransac_info &info = J.infos[j];
-    has_mask[j] = 1;
-    if (J.lm && lm_of[f] >= 0) {  // finish_ransac after run_fit's LM branch
-      const ManyLmOut &r = lm_res[lm_of[f]];
-      o.ok = r.ok;
-      o.n_params = r.n_params;
-      info.fit.lm_info = r.lm_info;
-      info.fit.lm_nfev = r.lm_nfev;
-      info.fit.reserved = r.stall;
-      o.cost = r.cost;
-      for (int k = 0; k < P; k++) o.params[k] = r.params[k];
-    }
-    info.fit.n_params = o.ok ? o.n_params : 0;
-    info.fit.n_used = counts[f];
-    info.fit.cost = o.cost;
-    if (!o.ok) {
-      J.status_out[j] = LSQR_EMPTY;
-      continue;
-    }
-    info.n_params = o.n_params;
-    for (int k = 0; k < P; k++) J.params_out[(size_t)j * P + k] = o.params[k];
-    J.status_out[j] = LSQR_OK;
-  }
-  if (J.consensus_out)  // problems without a winner: no consensus set
-    for (size_t j = 0; j < NP; j++)
-      if (!has_mask[j] && J.offsets[j + 1] > J.offsets[j])
-        memset(J.consensus_out + J.offsets[j], 0, J.offsets[j + 1] - J.offsets[j]);
+  many_end(J, F, P);
   return LSQR_OK;
 }
 
@@ -750,82 +887,26 @@ int many_run(ManyJob &J) {
 template <class M>
 int many_lm_fit(ManyJob &J, const uint8_t *masks, const double *x0, lsqr_fit_info *fits) {
   constexpr int P = M::P;
-  const int W = many_width<M>(J.W);
   ManyBufs &B = *J.buf;
-  const size_t NS = J.n;
-  const uint64_t NT = J.offsets[NS];
-  if (W != J.W) {
-    snprintf(J.err, sizeof J.err, "record width %d != the model's %d doubles", J.W, W);
-    return LSQR_ERR_INVALID;
-  }
-  std::vector<ManyLmProb> lp;
-  std::vector<uint32_t> set_of;
-  for (size_t j = 0; j < NS; j++) {
-    const uint64_t r0 = J.offsets[j], r1 = J.offsets[j + 1];
-    uint64_t cnt = r1 - r0;
-    if (masks) {
-      cnt = 0;
-      for (uint64_t i = r0; i < r1; i++) cnt += masks[i] != 0;
-    }
-    if (cnt == 0) {  // nothing to fit: outputs untouched
-      J.status_out[j] = LSQR_ERR_INVALID;
-      continue;
-    }
-    ManyLmProb q{};
-    q.rec = r0;
-    q.n = r1 - r0;
-    q.cnt = cnt;
-    q.xsrc = (uint32_t)j;
-    lp.push_back(q);
-    set_of.push_back((uint32_t)j);
-  }
-  if (lp.empty()) return LSQR_OK;
-  std::vector<double> packed;
+  std::vector<uint32_t> sets;
+  std::vector<uint64_t> used;
   int st;
-  if ((st = many_upload(J, W, NT, packed)) != LSQR_OK) return st;
-  if (masks) {
-    MANYCHK(many_grow(&B.d_mask, &B.c_mask, NT));
-    MANYCHK(hipMemcpyAsync(B.d_mask, masks, NT, hipMemcpyHostToDevice, J.stream));
+  if ((st = many_fit_begin(J, many_width<M>(J.W), masks, sets, used)) != LSQR_OK || sets.empty()) return st;
+  std::vector<ManyLmProb> lp;
+  for (size_t q = 0; q < sets.size(); q++) {
+    const uint32_t j = sets[q];
+    lp.push_back(ManyLmProb{J.offsets[j], J.offsets[j + 1] - J.offsets[j], 0, used[q], j, 0});
   }
-  MANYCHK(many_grow(&B.d_best, &B.c_best, NS * P));  // the starts (no RANSAC rounds run here)
-  MANYCHK(hipMemcpyAsync(B.d_best, x0, sizeof(double) * NS * P, hipMemcpyHostToDevice, J.stream));
-  ManyLmJob L;
-  L.stream = J.stream;
-  L.d_data = B.d_data;
-  L.d_mask = masks ? B.d_mask : nullptr;
-  L.d_x0 = B.d_best;
-  L.x0_stride = P;
-  L.n = J.lm_n;
-  L.maxfev = J.lm_maxfev;
-  L.ftol = J.lm_ftol;
-  L.xtol = J.lm_xtol;
-  L.gtol = J.lm_gtol;
-  L.buf = &B.lm;
-  L.err = J.err;
-  L.err_len = sizeof J.err;
+  MANYCHK(many_grow(&B.d_best, &B.c_best, J.n * P));  // the starts (no RANSAC rounds run here)
+  MANYCHK(hipMemcpyAsync(B.d_best, x0, sizeof(double) * J.n * P, hipMemcpyHostToDevice, J.stream));
+  ManyLmJob L = many_lm_job(J, masks ? B.d_mask : nullptr, B.d_best, P);
   std::vector<ManyLmOut> res;
   if ((st = many_lm_run<M>(L, lp, res)) != LSQR_OK) return st;
-  for (size_t q = 0; q < lp.size(); q++) {
-    const uint32_t j = set_of[q];
-    const ManyLmOut &r = res[q];
-    lsqr_fit_info &fi = fits[j];
-    memset(&fi, 0, sizeof fi);
-    fi.n_params = r.n_params;
-    fi.lm_info = r.lm_info;
-    fi.lm_nfev = r.lm_nfev;
-    fi.reserved = r.stall;
-    fi.n_used = lp[q].cnt;
-    fi.cost = r.cost;
-    if (!r.ok) {  // lsqr_lm_step: a failed run hands out no parameters
-      J.status_out[j] = LSQR_EMPTY;
-      continue;
-    }
-    for (int k = 0; k < r.n_params; k++) J.params_out[(size_t)j * P + k] = r.params[k];
-    J.status_out[j] = LSQR_OK;
-  }
+  std::vector<SolveOut> outs;
+  for (const ManyLmOut &r : res) outs.push_back(many_lm_solve_out(r));
+  many_write_fits(J, fits, P, sets, used, outs);
   return LSQR_OK;
 }
-#undef MANYCHK
 #endif
 
 }  // namespace lsqr

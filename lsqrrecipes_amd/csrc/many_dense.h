@@ -1,8 +1,9 @@
 // many_dense.h -- lsqr_ransac_many_dense: many independent RANSAC<T,S>::compute() problems of
 // DenseLinearEquationSystemParametersEstimator<double,n> (n = 1..64, records of n + 1 doubles) in one call, and
-// lsqr_dense_fit_many: the least-squares finish alone over many row sets.  The rounds are lsqr_ransac_many's
-// (many.h: many_rounds -- packed upload, 256 -> 1024 -> 4096 batches, host_replay with one DedupSet per problem,
-// k = n); the kernels are the dense single path's arithmetic, per problem:
+// lsqr_dense_fit_many: the least-squares finish alone over many row sets.  The host frame is lsqr_ransac_many's
+// (many.h: many_begin, many_rounds -- packed upload, 256 -> 1024 -> 4096 batches, host_replay with one DedupSet per
+// problem, k = n --, many_plan_finish .. many_end; many_fit_begin / many_write_fits for the fit alone); here are
+// many_dense_run's round kernels, many_dense_finish and the dense single path's arithmetic, per problem:
 //
 //   k_many_dense_estimate_w4   one wave per (problem, hypothesis), four per workgroup: the subset drawn by the wave
 //                              (k_sample_wave's rule = ctr_subset) on the problem's stream, the n x n system gathered
@@ -333,46 +334,22 @@ __global__ __launch_bounds__(256) void k_many_dense_solve(const double *__restri
 
 // ---- host side -------------------------------------------------------------------------------------------------
 #if defined(__HIPCC__)
-#define MANYCHK(call)                                                                                \
-  do {                                                                                               \
-    hipError_t e_ = (call);                                                                          \
-    if (e_ != hipSuccess) {                                                                          \
-      snprintf(J.err, sizeof J.err, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, \
-               __LINE__);                                                                            \
-      return LSQR_ERR_HIP;                                                                           \
-    }                                                                                                \
-  } while (0)
-
-// The finish of NF problems: parts (ordered by finishing slot f, pbeg[f] .. pbeg[f+1]) -> mask / moments -> solve,
-// the double-double route for the flagged ones.  best: the winners' rows (mask_out written) or nullptr (mask_in,
-// nullable, on the device).  rows[f] = the problem's record range.  Fills counts and outs; leaves the mask on B.d_mask.
+// The finish of F's slots: mask / moments -> solve, the double-double route for the flagged ones.  best: the winners'
+// rows (the consensus mask is written to B.d_mask) or nullptr (mask_in, nullable, on the device).  The counts and fits
+// stay on the device for many_fetch_finish.
 template <int NR>
-int many_dense_finish(ManyJob &J, const std::vector<ManyPart> &parts, const std::vector<uint32_t> &pbeg,
-                      const std::vector<std::pair<uint64_t, uint64_t>> &rows, const double *best,
-                      const uint8_t *mask_in, std::vector<unsigned long long> &counts, std::vector<SolveOut> &outs) {
+int many_dense_finish(ManyJob &J, const ManyFinish &F, const double *best, const uint8_t *mask_in) {
   ManyBufs &B = *J.buf;
   const int n = (int)J.cfg.dim, ps = many_dense_ps(n);
-  const size_t NF = rows.size();
-  counts.assign(NF, 0);
-  outs.assign(NF, SolveOut());
+  const size_t NF = F.size();
+  int st;
   if (NF == 0) return LSQR_OK;
-  MANYCHK(many_grow(&B.d_parts, &B.c_parts, parts.size()));
-  MANYCHK(many_grow(&B.d_pbeg, &B.c_pbeg, pbeg.size()));
-  MANYCHK(many_grow(&B.d_counts, &B.c_counts, NF));
-  MANYCHK(many_grow(&B.d_out, &B.c_out, NF));
+  if ((st = many_stage_finish(J, F, false)) != LSQR_OK) return st;  // (no kernel here reads fin)
   MANYCHK(many_grow(&B.d_flags, &B.c_flags, NF));
   MANYCHK(many_grow(&B.d_mom, &B.c_mom, NF * ps));
-  MANYCHK(many_grow(&B.d_partials, &B.c_partials, parts.size() * ps));
-  const size_t b_parts = sizeof(ManyPart) * parts.size(), o_pbeg = (b_parts + 15) & ~(size_t)15;
-  MANYCHK(many_grow_pinned(&B.h_stage, &B.c_stage, o_pbeg + sizeof(uint32_t) * pbeg.size()));
-  memcpy(B.h_stage, parts.data(), b_parts);
-  memcpy(B.h_stage + o_pbeg, pbeg.data(), sizeof(uint32_t) * pbeg.size());
-  MANYCHK(hipMemcpyAsync(B.d_parts, B.h_stage, b_parts, hipMemcpyHostToDevice, J.stream));
-  MANYCHK(hipMemcpyAsync(B.d_pbeg, B.h_stage + o_pbeg, sizeof(uint32_t) * pbeg.size(), hipMemcpyHostToDevice,
-                         J.stream));
-  MANYCHK(hipMemsetAsync(B.d_counts, 0, sizeof(unsigned long long) * NF, J.stream));
+  MANYCHK(many_grow(&B.d_partials, &B.c_partials, F.parts.size() * ps));
   MANYCHK(hipMemsetAsync(B.d_flags, 0, sizeof(int) * NF, J.stream));
-  hipLaunchKernelGGL((k_many_dense_mask_moments<NR>), dim3((unsigned)parts.size()), dim3(256), 0, J.stream, B.d_data,
+  hipLaunchKernelGGL((k_many_dense_mask_moments<NR>), dim3((unsigned)F.parts.size()), dim3(256), 0, J.stream, B.d_data,
                      n, B.d_parts, best, J.mc.delta, mask_in, B.d_mask, B.d_counts, B.d_partials, ps);
   MANYCHK(hipGetLastError());
   hipLaunchKernelGGL(k_many_dense_sum, dim3((unsigned)NF), dim3(256), 0, J.stream, B.d_partials, B.d_pbeg, n, ps,
@@ -397,7 +374,7 @@ int many_dense_finish(ManyJob &J, const std::vector<ManyPart> &parts, const std:
                                   (int)dense_dd_lds(64));
         any = true;
       }
-      const uint64_t begin = rows[f].first, end = rows[f].second;
+      const uint64_t begin = J.offsets[F.fin[f]], end = J.offsets[F.fin[f] + 1];
       const int nb = (int)std::min<uint64_t>(kDdBlocks, (end - begin + 31) / 32);
       const uint8_t *mk = best ? B.d_mask : mask_in;
       hipLaunchKernelGGL((k_gram_dd_dense<32>), dim3(nb), dim3(256), 0, J.stream, B.d_data, (size_t)(n + 1),
@@ -408,39 +385,17 @@ int many_dense_finish(ManyJob &J, const std::vector<ManyPart> &parts, const std:
       MANYCHK(hipGetLastError());
     }
   }
-  MANYCHK(hipMemcpyAsync(counts.data(), B.d_counts, sizeof(unsigned long long) * NF, hipMemcpyDeviceToHost,
-                         J.stream));
-  MANYCHK(hipMemcpyAsync(outs.data(), B.d_out, sizeof(SolveOut) * NF, hipMemcpyDeviceToHost, J.stream));
   return LSQR_OK;
 }
 
 template <int NR>
 int many_dense_run(ManyJob &J) {
   ManyBufs &B = *J.buf;
-  const int n = (int)J.cfg.dim, K = n, W = n + 1;
-  const size_t NP = J.n;
-  const uint64_t NT = J.offsets[NP];
+  const int n = (int)J.cfg.dim, K = n;
   int st0;
-  if (J.W != W) {
-    snprintf(J.err, sizeof J.err, "record width %d != the model's %d doubles", J.W, W);
-    return LSQR_ERR_INVALID;
-  }
   if (J.round_cap == 0) J.round_cap = many_dense_round_cap(n, NR);
-
-  std::vector<ManyProb> pr(NP);
-  for (size_t j = 0; j < NP; j++) {
-    memset(&J.infos[j], 0, sizeof(lsqr_ransac_info));
-    const uint64_t m = J.offsets[j + 1] - J.offsets[j];
-    if (m < (uint64_t)K) {  // RANSAC.hxx:16-19: return 0, parameters untouched
-      J.status_out[j] = LSQR_ERR_INVALID;
-      continue;
-    }
-    host_replay_init(m, K, J.p, pr[j].rs);
-    pr[j].live = !pr[j].rs[RS_DONE];
-  }
-  std::vector<double> packed;
-  if ((st0 = many_upload(J, W, NT, packed)) != LSQR_OK) return st0;
-  MANYCHK(many_grow(&B.d_best, &B.c_best, std::max<size_t>(NP, 1) * NR));
+  std::vector<ManyProb> pr;
+  if ((st0 = many_begin(J, n + 1, K, NR, pr)) != LSQR_OK) return st0;
   const size_t lds_w4 = sizeof(double) * kManyDenseWaves * ((size_t)n * (n | 1) + 2 * n);
   (void)hipFuncSetAttribute((const void *)k_many_dense_estimate_w4, hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)(sizeof(double) * kManyDenseWaves * (64 * 65 + 128)));
@@ -473,72 +428,14 @@ int many_dense_run(ManyJob &J) {
        })) != LSQR_OK)
     return st0;
 
-  // ---- finish: finish_ransac for every problem with a winner -----------------------------------------------------
-  std::vector<uint32_t> fin, pbeg;
-  std::vector<ManyPart> parts;
-  std::vector<std::pair<uint64_t, uint64_t>> rows;
-  for (size_t j = 0; j < NP; j++) {
-    const uint64_t m = J.offsets[j + 1] - J.offsets[j];
-    if (m < (uint64_t)K) continue;
-    ManyProb &q = pr[j];
-    lsqr_ransac_info &info = J.infos[j];
-    info.iterations = q.rs[RS_I];
-    info.best_index = q.rs[RS_BEST_IDX];
-    info.evaluated = q.evaluated;
-    info.best_votes = (uint32_t)q.rs[RS_BEST];
-    info.fraction = (double)info.best_votes / (double)m;
-    info.n_params = 0;
-    if (!q.rs[RS_HAS] || info.best_votes == 0) {
-      J.status_out[j] = LSQR_EMPTY;
-      continue;
-    }
-    const uint32_t f = (uint32_t)fin.size();
-    fin.push_back((uint32_t)j);
-    pbeg.push_back((uint32_t)parts.size());
-    rows.emplace_back(J.offsets[j], J.offsets[j + 1]);
-    for (uint64_t r = 0; r < m; r += kManyPart)
-      parts.push_back(ManyPart{J.offsets[j] + r, J.offsets[j] + std::min<uint64_t>(m, r + kManyPart), 0, (uint32_t)j,
-                               f});
-  }
-  pbeg.push_back((uint32_t)parts.size());
-  const size_t NF = fin.size();
-  if (NF) MANYCHK(many_grow(&B.d_mask, &B.c_mask, NT));
-  std::vector<unsigned long long> counts;
-  std::vector<SolveOut> outs;
-  if ((st0 = many_dense_finish<NR>(J, parts, pbeg, rows, B.d_best, nullptr, counts, outs)) != LSQR_OK) return st0;
-  if (NF && J.consensus_out && NT)
-    MANYCHK(hipMemcpyAsync(J.consensus_out, B.d_mask, NT, hipMemcpyDeviceToHost, J.stream));
-  MANYCHK(hipStreamSynchronize(J.stream));
-  std::vector<uint8_t> has_mask(NP, 0);
-  for (size_t f = 0; f < NF; f++) {
-    const uint32_t j = fin[f];
-    if (counts[f] != J.infos[j].best_votes) {
-      snprintf(J.err, sizeof J.err, "problem %u: consensus mask count %llu != scan votes %u", j, counts[f],
-               J.infos[j].best_votes);
-      return LSQR_ERR_HIP;
-    }
-  }
-  for (size_t f = 0; f < NF; f++) {
-    const uint32_t j = fin[f];
-    const SolveOut &o = outs[f];
-    lsqr_ransac_info &info = J.infos[j];
-    has_mask[j] = 1;
-    info.fit.n_params = o.ok ? o.n_params : 0;
-    info.fit.n_used = counts[f];
-    info.fit.cost = o.cost;
-    info.fit.reserved = o.pad;  // 1: the double-double route (2: dense_dd 0 and a pivot below 1e-6, as lsqr_ransac)
-    if (!o.ok) {
-      J.status_out[j] = LSQR_EMPTY;
-      continue;
-    }
-    info.n_params = o.n_params;
-    for (int k = 0; k < n; k++) J.params_out[(size_t)j * n + k] = o.params[k];
-    J.status_out[j] = LSQR_OK;
-  }
-  if (J.consensus_out)  // problems without a winner: no consensus set
-    for (size_t j = 0; j < NP; j++)
-      if (!has_mask[j] && J.offsets[j + 1] > J.offsets[j])
-        memset(J.consensus_out + J.offsets[j], 0, J.offsets[j + 1] - J.offsets[j]);
+  // ---- finish: finish_ransac for every problem with a winner (the dense moments have no origin) -------------------
+  ManyFinish F = many_plan_finish(J, pr, K, [](size_t, const ManyProb &) -> uint64_t { return 0; });
+  if (F.size()) MANYCHK(many_grow(&B.d_mask, &B.c_mask, J.offsets[J.n]));
+  if ((st0 = many_dense_finish<NR>(J, F, B.d_best, nullptr)) != LSQR_OK) return st0;
+  if ((st0 = many_fetch_finish(J, F, true)) != LSQR_OK) return st0;
+  // fit.reserved = SolveOut::pad: 1: the double-double route (2: dense_dd 0 and a pivot below 1e-6, as lsqr_ransac);
+  // solve_dense_wg and k_dense_dd_solve write it, and lm_info = lm_nfev = 0, on every path
+  many_end(J, F, n);
   return LSQR_OK;
 }
 
@@ -546,71 +443,20 @@ int many_dense_run(ManyJob &J) {
 // single-set path's result (lsqr_upload + lsqr_set_mask + lsqr_ls_fit)
 template <int NR>
 int many_dense_fit(ManyJob &J, const uint8_t *masks, lsqr_fit_info *fits) {
-  ManyBufs &B = *J.buf;
-  const int n = (int)J.cfg.dim, W = n + 1;
-  const size_t NS = J.n;
-  const uint64_t NT = J.offsets[NS];
-  if (J.W != W) {
-    snprintf(J.err, sizeof J.err, "record width %d != the model's %d doubles", J.W, W);
-    return LSQR_ERR_INVALID;
-  }
-  std::vector<uint32_t> set_of, pbeg;
+  const int n = (int)J.cfg.dim;
+  std::vector<uint32_t> sets;
   std::vector<uint64_t> used;
-  std::vector<ManyPart> parts;
-  std::vector<std::pair<uint64_t, uint64_t>> rows;
-  for (size_t j = 0; j < NS; j++) {
-    const uint64_t r0 = J.offsets[j], r1 = J.offsets[j + 1];
-    uint64_t cnt = r1 - r0;
-    if (masks) {
-      cnt = 0;
-      for (uint64_t i = r0; i < r1; i++) cnt += masks[i] != 0;
-    }
-    if (cnt == 0) {  // nothing to fit: outputs untouched
-      J.status_out[j] = LSQR_ERR_INVALID;
-      continue;
-    }
-    const uint32_t f = (uint32_t)set_of.size();
-    set_of.push_back((uint32_t)j);
-    used.push_back(cnt);
-    pbeg.push_back((uint32_t)parts.size());
-    rows.emplace_back(r0, r1);
-    for (uint64_t r = r0; r < r1; r += kManyPart)
-      parts.push_back(ManyPart{r, std::min<uint64_t>(r1, r + kManyPart), 0, (uint32_t)j, f});
-  }
-  pbeg.push_back((uint32_t)parts.size());
-  if (set_of.empty()) return LSQR_OK;
-  std::vector<double> packed;
   int st;
-  if ((st = many_upload(J, W, NT, packed)) != LSQR_OK) return st;
-  if (masks) {
-    MANYCHK(many_grow(&B.d_mask, &B.c_mask, NT));
-    MANYCHK(hipMemcpyAsync(B.d_mask, masks, NT, hipMemcpyHostToDevice, J.stream));
-  }
-  std::vector<unsigned long long> counts;
-  std::vector<SolveOut> outs;
-  if ((st = many_dense_finish<NR>(J, parts, pbeg, rows, nullptr, masks ? B.d_mask : nullptr, counts, outs)) !=
-      LSQR_OK)
-    return st;
-  MANYCHK(hipStreamSynchronize(J.stream));
-  for (size_t f = 0; f < set_of.size(); f++) {
-    const uint32_t j = set_of[f];
-    const SolveOut &o = outs[f];
-    lsqr_fit_info &fi = fits[j];
-    memset(&fi, 0, sizeof fi);
-    fi.n_params = o.n_params;
-    fi.reserved = o.pad;
-    fi.cost = o.cost;
-    fi.n_used = used[f];
-    if (!o.ok) {
-      J.status_out[j] = LSQR_EMPTY;
-      continue;
-    }
-    for (int k = 0; k < o.n_params; k++) J.params_out[(size_t)j * n + k] = o.params[k];
-    J.status_out[j] = LSQR_OK;
-  }
+  if ((st = many_fit_begin(J, n + 1, masks, sets, used)) != LSQR_OK || sets.empty()) return st;
+  ManyFinish F;
+  for (uint32_t j : sets) F.add(j, J.offsets[j], J.offsets[j + 1], 0);
+  if ((st = many_dense_finish<NR>(J, F, nullptr, masks ? J.buf->d_mask : nullptr)) != LSQR_OK) return st;
+  if ((st = many_fetch_finish(J, F, false)) != LSQR_OK) return st;
+  many_write_fits(J, fits, n, sets, used, F.outs);
   return LSQR_OK;
 }
-#undef MANYCHK
 #endif
 
 }  // namespace lsqr
+
+#undef MANYCHK

@@ -17,6 +17,8 @@
 // Determinism: a problem's block in every evaluation is a function of its own inliers and its own trial point only --
 // its parts are fixed by its inlier count, the sums run in a fixed order within a part and across parts -- so its
 // iterates do not depend on the other problems of the call, their order, or how the RANSAC rounds were cut.
+//
+// Included by many.h, whose kManyPart, many_grow and MANYCHK it uses; many_run and many_lm_fit there call the stage.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -239,21 +241,9 @@ inline void many_lm_free(ManyLmBufs &b) {
   b = ManyLmBufs();
 }
 
-template <class T>
-hipError_t many_lm_grow(T **p, size_t *cap, size_t n) {
-  if (n <= *cap && *p) return hipSuccess;
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  const size_t want = n + n / 4 > 64 ? n + n / 4 : 64;
-  hipError_t e = hipMalloc((void **)p, sizeof(T) * want);
-  if (e == hipSuccess) *cap = want;
-  return e;
-}
-
-// One call of the stage.  The records (D doubles each, packed) and the mask (nullable: every record) are on the
-// device; problem q's start is row prob[q].xsrc of x0 (x0_stride doubles apart, on the device).  The host fills
-// rec, n, cnt (> 0: its masked records) and xsrc; the stage fills c0 and pbeg.
+// One call of the stage (filled by many_lm_job, many.h).  The records (D doubles each, packed) and the mask (nullable:
+// every record) are on the device; problem q's start is row prob[q].xsrc of x0 (x0_stride doubles apart, on the
+// device).  The host fills rec, n, cnt (> 0: its masked records) and xsrc; the stage fills c0 and pbeg.
 struct ManyLmJob {
   hipStream_t stream;
   const double *d_data;
@@ -263,23 +253,13 @@ struct ManyLmJob {
   int n, maxfev;  // lm_settings
   double ftol, xtol, gtol;
   ManyLmBufs *buf;
-  char *err;
-  size_t err_len;
+  char (&err)[256];  // the ManyJob's, where MANYCHK (many.h) reports
 };
 
-#define MANYLMCHK(call)                                                                                  \
-  do {                                                                                                   \
-    hipError_t e_ = (call);                                                                              \
-    if (e_ != hipSuccess) {                                                                              \
-      snprintf(L.err, L.err_len, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-      return LSQR_ERR_HIP;                                                                               \
-    }                                                                                                    \
-  } while (0)
-
 template <class M>
-int many_lm_run(ManyLmJob &L, std::vector<ManyLmProb> &prob, std::vector<ManyLmOut> &res) {
+int many_lm_run(ManyLmJob &J, std::vector<ManyLmProb> &prob, std::vector<ManyLmOut> &res) {
   constexpr int D = M::ND, N = M::NMOM_LM;
-  ManyLmBufs &B = *L.buf;
+  ManyLmBufs &B = *J.buf;
   const int Q = (int)prob.size();
   res.assign(Q, ManyLmOut());
   if (Q == 0) return LSQR_OK;
@@ -299,41 +279,41 @@ int many_lm_run(ManyLmJob &L, std::vector<ManyLmProb> &prob, std::vector<ManyLmO
       parts.push_back(ManyLmPart{P.c0 + r, P.c0 + std::min<uint64_t>(P.cnt, r + kManyPart), (uint32_t)q, 0});
   }
   const uint64_t C = c;
-  MANYLMCHK(many_lm_grow(&B.d_rec, &B.c_rec, std::max<uint64_t>(C, 1) * D));
-  MANYLMCHK(many_lm_grow(&B.d_prob, &B.c_prob, (size_t)Q));
-  MANYLMCHK(many_lm_grow(&B.d_raw, &B.c_raw, raw.size()));
-  MANYLMCHK(many_lm_grow(&B.d_rcount, &B.c_rcount, raw.size()));
-  MANYLMCHK(many_lm_grow(&B.d_parts, &B.c_parts, parts.size()));
-  MANYLMCHK(many_lm_grow(&B.d_partials, &B.c_partials, parts.size() * N));
-  MANYLMCHK(many_lm_grow(&B.d_flag, &B.c_flag, (size_t)Q));
-  MANYLMCHK(many_lm_grow(&B.d_state, &B.c_state, (size_t)Q));
-  MANYLMCHK(many_lm_grow(&B.d_out, &B.c_out, (size_t)Q));
-  MANYLMCHK(many_lm_grow(&B.d_live, &B.c_live, 1));
-  if (!B.h_live) MANYLMCHK(hipHostMalloc((void **)&B.h_live, 64));
+  MANYCHK(many_grow(&B.d_rec, &B.c_rec, std::max<uint64_t>(C, 1) * D));
+  MANYCHK(many_grow(&B.d_prob, &B.c_prob, (size_t)Q));
+  MANYCHK(many_grow(&B.d_raw, &B.c_raw, raw.size()));
+  MANYCHK(many_grow(&B.d_rcount, &B.c_rcount, raw.size()));
+  MANYCHK(many_grow(&B.d_parts, &B.c_parts, parts.size()));
+  MANYCHK(many_grow(&B.d_partials, &B.c_partials, parts.size() * N));
+  MANYCHK(many_grow(&B.d_flag, &B.c_flag, (size_t)Q));
+  MANYCHK(many_grow(&B.d_state, &B.c_state, (size_t)Q));
+  MANYCHK(many_grow(&B.d_out, &B.c_out, (size_t)Q));
+  MANYCHK(many_grow(&B.d_live, &B.c_live, 1));
+  if (!B.h_live) MANYCHK(hipHostMalloc((void **)&B.h_live, 64));
   // (the host vectors are pageable: these copies complete before the calls return)
-  MANYLMCHK(hipMemcpyAsync(B.d_prob, prob.data(), sizeof(ManyLmProb) * Q, hipMemcpyHostToDevice, L.stream));
-  MANYLMCHK(hipMemcpyAsync(B.d_raw, raw.data(), sizeof(ManyLmRaw) * raw.size(), hipMemcpyHostToDevice, L.stream));
-  MANYLMCHK(hipMemcpyAsync(B.d_parts, parts.data(), sizeof(ManyLmPart) * parts.size(), hipMemcpyHostToDevice,
-                           L.stream));
-  hipLaunchKernelGGL(k_many_lm_count, dim3((unsigned)raw.size()), dim3(kBlock), 0, L.stream, B.d_raw, L.d_mask,
+  MANYCHK(hipMemcpyAsync(B.d_prob, prob.data(), sizeof(ManyLmProb) * Q, hipMemcpyHostToDevice, J.stream));
+  MANYCHK(hipMemcpyAsync(B.d_raw, raw.data(), sizeof(ManyLmRaw) * raw.size(), hipMemcpyHostToDevice, J.stream));
+  MANYCHK(hipMemcpyAsync(B.d_parts, parts.data(), sizeof(ManyLmPart) * parts.size(), hipMemcpyHostToDevice,
+                           J.stream));
+  hipLaunchKernelGGL(k_many_lm_count, dim3((unsigned)raw.size()), dim3(kBlock), 0, J.stream, B.d_raw, J.d_mask,
                      B.d_rcount);
-  MANYLMCHK(hipGetLastError());
-  hipLaunchKernelGGL((k_many_lm_write<D>), dim3((unsigned)raw.size()), dim3(kBlock), 0, L.stream, L.d_data, B.d_raw,
-                     B.d_prob, L.d_mask, B.d_rcount, B.d_rec);
-  MANYLMCHK(hipGetLastError());
-  hipLaunchKernelGGL(k_many_lm_init, dim3((unsigned)((Q + kBlock - 1) / kBlock)), dim3(kBlock), 0, L.stream, B.d_prob,
-                     Q, L.d_x0, L.x0_stride, L.n, L.ftol, L.xtol, L.gtol, L.maxfev, B.d_state, B.d_flag);
-  MANYLMCHK(hipGetLastError());
+  MANYCHK(hipGetLastError());
+  hipLaunchKernelGGL((k_many_lm_write<D>), dim3((unsigned)raw.size()), dim3(kBlock), 0, J.stream, J.d_data, B.d_raw,
+                     B.d_prob, J.d_mask, B.d_rcount, B.d_rec);
+  MANYCHK(hipGetLastError());
+  hipLaunchKernelGGL(k_many_lm_init, dim3((unsigned)((Q + kBlock - 1) / kBlock)), dim3(kBlock), 0, J.stream, B.d_prob,
+                     Q, J.d_x0, J.x0_stride, J.n, J.ftol, J.xtol, J.gtol, J.maxfev, B.d_state, B.d_flag);
+  MANYCHK(hipGetLastError());
   *B.h_live = (uint32_t)Q;
-  MANYLMCHK(hipMemcpyAsync(B.d_live, B.h_live, sizeof(uint32_t), hipMemcpyHostToDevice, L.stream));
-  MANYLMCHK(hipStreamSynchronize(L.stream));  // (h_live is written again below)
+  MANYCHK(hipMemcpyAsync(B.d_live, B.h_live, sizeof(uint32_t), hipMemcpyHostToDevice, J.stream));
+  MANYCHK(hipStreamSynchronize(J.stream));  // (h_live is written again below)
 
   // diagnostics (LSQR_MANY_TRACE): per round the live problems, the parts launched, pass / step time, device wait
   static const bool trace = getenv("LSQR_MANY_TRACE") != nullptr;
   typedef std::chrono::steady_clock Clock;
   hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
   if (trace)
-    for (auto &e : ev) MANYLMCHK(hipEventCreate(&e));
+    for (auto &e : ev) MANYCHK(hipEventCreate(&e));
   struct EvGuard {
     hipEvent_t *e;
     ~EvGuard() {
@@ -346,42 +326,41 @@ int many_lm_run(ManyLmJob &L, std::vector<ManyLmProb> &prob, std::vector<ManyLmO
   // every lm_advance call consumes one evaluation and stops at maxfev: maxfev rounds finish every problem
   int round = 0;
   for (; live > 0; round++) {
-    if (round > L.maxfev) {
-      snprintf(L.err, L.err_len, "LM stage: %u problems still live after %d rounds", live, round);
+    if (round > J.maxfev) {
+      snprintf(J.err, sizeof J.err, "LM stage: %u problems still live after %d rounds", live, round);
       return LSQR_ERR_HIP;
     }
-    if (trace) MANYLMCHK(hipEventRecord(ev[0], L.stream));
-    hipLaunchKernelGGL((k_many_lm_pass<M>), dim3((unsigned)parts.size()), dim3(kBlock), 0, L.stream, B.d_rec,
+    if (trace) MANYCHK(hipEventRecord(ev[0], J.stream));
+    hipLaunchKernelGGL((k_many_lm_pass<M>), dim3((unsigned)parts.size()), dim3(kBlock), 0, J.stream, B.d_rec,
                        B.d_parts, B.d_state, B.d_flag, B.d_partials);
-    MANYLMCHK(hipGetLastError());
-    if (trace) MANYLMCHK(hipEventRecord(ev[1], L.stream));
-    hipLaunchKernelGGL((k_many_lm_step<M>), dim3(n_steps), dim3(64 * kManyLmWaves), 0, L.stream, B.d_state, B.d_flag,
+    MANYCHK(hipGetLastError());
+    if (trace) MANYCHK(hipEventRecord(ev[1], J.stream));
+    hipLaunchKernelGGL((k_many_lm_step<M>), dim3(n_steps), dim3(64 * kManyLmWaves), 0, J.stream, B.d_state, B.d_flag,
                        B.d_prob, Q, (uint32_t)parts.size(), B.d_partials, B.d_out, B.d_live);
-    MANYLMCHK(hipGetLastError());
-    if (trace) MANYLMCHK(hipEventRecord(ev[2], L.stream));
-    MANYLMCHK(hipMemcpyAsync(B.h_live, B.d_live, sizeof(uint32_t), hipMemcpyDeviceToHost, L.stream));
+    MANYCHK(hipGetLastError());
+    if (trace) MANYCHK(hipEventRecord(ev[2], J.stream));
+    MANYCHK(hipMemcpyAsync(B.h_live, B.d_live, sizeof(uint32_t), hipMemcpyDeviceToHost, J.stream));
     const Clock::time_point t0 = Clock::now();
-    MANYLMCHK(hipStreamSynchronize(L.stream));
+    MANYCHK(hipStreamSynchronize(J.stream));
     const double wait = std::chrono::duration<double, std::milli>(Clock::now() - t0).count();
     const uint32_t now = *B.h_live;
     if (trace) {
       float t_pass = 0.f, t_step = 0.f;
-      MANYLMCHK(hipEventElapsedTime(&t_pass, ev[0], ev[1]));
-      MANYLMCHK(hipEventElapsedTime(&t_step, ev[1], ev[2]));
+      MANYCHK(hipEventElapsedTime(&t_pass, ev[0], ev[1]));
+      MANYCHK(hipEventElapsedTime(&t_step, ev[1], ev[2]));
       fprintf(stderr, "ransac_many lm round %d: %u live problems, %zu parts, pass %.3f ms, step %.3f ms, wait %.3f ms\n",
               round, live, parts.size(), t_pass, t_step, wait);
     }
     if (now > live) {
-      snprintf(L.err, L.err_len, "LM stage: live counter rose from %u to %u", live, now);
+      snprintf(J.err, sizeof J.err, "LM stage: live counter rose from %u to %u", live, now);
       return LSQR_ERR_HIP;
     }
     live = now;
   }
-  MANYLMCHK(hipMemcpyAsync(res.data(), B.d_out, sizeof(ManyLmOut) * Q, hipMemcpyDeviceToHost, L.stream));
-  MANYLMCHK(hipStreamSynchronize(L.stream));
+  MANYCHK(hipMemcpyAsync(res.data(), B.d_out, sizeof(ManyLmOut) * Q, hipMemcpyDeviceToHost, J.stream));
+  MANYCHK(hipStreamSynchronize(J.stream));
   return LSQR_OK;
 }
-#undef MANYLMCHK
 #endif
 
 }  // namespace lsqr
