@@ -9,6 +9,7 @@
 #include <chrono>
 #include <cmath>
 #include <cstdarg>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -16,6 +17,7 @@
 #include <set>
 #include <thread>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -45,6 +47,76 @@
 #include <rccl/rccl.h>  // types and prototypes only: librccl is dlopen'ed when LSQR_MULTI_TRANSPORT=rccl asks for it
 
 using namespace lsqr;
+
+// ---- the pinned staging buffer (lsqr_ctx::h_pin) ---------------------------------------------------------------
+// One 64 KiB allocation per context.  Every area has one user, or users that never overlap in time on a context;
+// the members are padded so that each area sits where it always has.
+struct BatchSlot {  // lsqr_batch_fit_enqueue -> lsqr_batch_fit_wait
+  unsigned long long head[2], pad0[2];  // {inliers, packed winner}
+  unsigned long long ovf_fill, pad1[3];  // fullest worklist segment of the slot's scan (deferred overflow check)
+  SolveOut out;
+  char pad2[2048 - 64 - sizeof(SolveOut)];
+};
+struct StepSlot {  // lsqr_step_finish_enqueue -> lsqr_step_finish_wait
+  unsigned long long packed;
+  double count;
+  uint8_t valid, pad0[47];
+  double winner[64], pad1[128 - 8 - 64];
+  SolveOut out;
+  char pad2[2048 - 1024 - sizeof(SolveOut)];
+};
+struct WinnerPin {  // lsqr_winner_moments
+  uint8_t valid, pad0[7];
+  unsigned long long count;
+  double params[64], origin[32];
+};
+struct PinLayout {
+  union {  // general scratch of the blocking entry points: what is staged here is read before the call returns
+    char scratch[8192];
+    double scratch_f64[1024];
+    unsigned long long scratch_u64[1024];
+  };
+  unsigned long long mask_head[2], pad0[1024 - 2];  // {inliers, packed winner} of a blocking finish: survives run_fit
+  WinnerPin winner;
+  char pad1[16384 - sizeof(WinnerPin)];
+  LmpCtl lmp;  // lm_persist_fit: the persistent kernel's control block after the fit
+  char pad2[8192 - sizeof(LmpCtl)];
+  double phantom_block[1024];  // the phantom's Gram block of a step (one area: phantom steps are not pipelined)
+  BatchSlot batch[2];
+  StepSlot step[2];
+  double mdev_x[4][64];  // lsqr_moments_dev: staging slots of x
+};
+static_assert(sizeof(PinLayout) <= 1 << 16, "h_pin is 64 KiB");
+static_assert(std::is_trivially_copyable_v<SolveOut> && std::is_trivially_copyable_v<LmpCtl> &&
+              std::is_trivially_copyable_v<BoundsRow>, "staged with memcpy");
+static_assert(offsetof(PinLayout, mask_head) == 8192 && offsetof(PinLayout, winner) == 16384 &&
+              offsetof(PinLayout, lmp) == 32768 && offsetof(PinLayout, phantom_block) == 40960 &&
+              offsetof(PinLayout, batch) == 49152 && offsetof(PinLayout, step) == 53248 &&
+              offsetof(PinLayout, mdev_x) == 57344, "areas stay where they were");
+static_assert(sizeof(BatchSlot) == 2048 && offsetof(BatchSlot, ovf_fill) == 32 && offsetof(BatchSlot, out) == 64 &&
+              sizeof(StepSlot) == 2048 && offsetof(StepSlot, valid) == 16 && offsetof(StepSlot, winner) == 64 &&
+              offsetof(StepSlot, out) == 1024 && offsetof(WinnerPin, params) == 16 && offsetof(WinnerPin, origin) == 528);
+// the largest things staged in the scratch area: a SolveOut, the bounds row, the LM loop's {x[64] | block}, the
+// compacted count behind 200 doubles, and the phantom's Gram block (checked at dense_ne)
+static_assert(sizeof(SolveOut) <= 8192 && sizeof(BoundsRow) <= 8192 && sizeof(double) * (64 + LM_MOM_MAX) <= 8192 &&
+              sizeof(double) * 201 <= sizeof(PinLayout::scratch));
+
+// The eight words of lsqr_ctx::d_counter.  Two pairs of names share storage; both are safe by stream order:
+//   CNT_ABSMAX is a PAIR (words 5 and 6), so its second word is CNT_FIRST.  The absmax pass of an upload or a model
+//     change writes the pair and synchronises before it returns; set_fit_origin(ORG_MASK) writes and consumes
+//     CNT_FIRST inside one fit, enqueued later on the same stream.
+//   CNT_FLAG is shared by halves: the low word is k_plane_order's count (plane scans), the high word the dense
+//     solve's double-double flag (dense fits).  A context has one model, and each user sets its half before use.
+enum {
+  CNT_MASK = 0,    // inliers of the last mask pass
+  CNT_BEST = 1,    // k_best's packed winner {votes | ~index}: CNT_MASK and CNT_BEST are read back as one pair
+  CNT_SUM = 2,     // lsqr_scan_workload: surviving cells of the selected hypotheses
+  CNT_OVF = 3,     // fullest worklist segment of a matrix-core filter
+  CNT_PAIRS = 4,   // surviving (cell, hypothesis) pairs of level 1
+  CNT_ABSMAX = 5,  // {absmax, absmax_rot}
+  CNT_FIRST = 6,   // first masked record
+  CNT_FLAG = 7
+};
 
 // ------------------------------------------------------------------------------------------------
 struct lsqr_ctx {
@@ -268,7 +340,7 @@ struct lsqr_ctx {
   hipEvent_t up_ev[kUpSlots] = {nullptr};
   int opt_upload_threads = -1;  // -1: LSQR_UPLOAD_THREADS or 4; 0: one plain hipMemcpy
   double last_upload_ms = 0.0;
-  void *h_pin = nullptr;  // pinned staging (64 KiB)
+  PinLayout *h_pin = nullptr;  // pinned staging
   void *h_batch = nullptr;  // pinned results of a lsqr_ransac batch (grown on demand)
   size_t batch_pin_cap = 0;
 
@@ -345,7 +417,10 @@ struct ProfScope {
 };
 
 size_t dense_lds_bytes(int n) { return sizeof(double) * ((size_t)2 * n * (n | 1) + 3 * n); }
-int dense_ne(int n) { return (n + 1) * (n + 2) / 2; }
+constexpr int dense_ne(int n) { return (n + 1) * (n + 2) / 2; }
+// the phantom's Gram block (30 columns + right-hand side, and the count) fits its own area and the scratch area
+static_assert(sizeof(double) * (dense_ne(30) + 1) <= sizeof(PinLayout::phantom_block) &&
+              sizeof(double) * (dense_ne(30) + 1) <= sizeof(PinLayout::scratch));
 constexpr int kDenseBlocks = 256;
 int dense_pstride(int n) { return (dense_ne(n) + 1 + 7) & ~7; }
 
@@ -476,7 +551,7 @@ int ensure_absmax(lsqr_ctx *c) {
     c->absmax_valid = true;
     return LSQR_OK;
   }
-  HIPCHK(c, hipMemsetAsync(c->d_counter + 5, 0, 2 * sizeof(unsigned long long), c->stream));
+  HIPCHK(c, hipMemsetAsync(c->d_counter + CNT_ABSMAX, 0, 2 * sizeof(unsigned long long), c->stream));
   int grid = grid_for(c->n, kBlock * 16, 1024);
   const bool us = c->cfg.model == LSQR_MODEL_US_SINGLE || c->cfg.model == LSQR_MODEL_US_POINTER ||
                   c->cfg.model == LSQR_MODEL_PHANTOM;  // Frame records: int slot 12, rotation first
@@ -484,14 +559,14 @@ int ensure_absmax(lsqr_ctx *c) {
     ProfScope ps(c, KID_ABSMAX);
     hipLaunchKernelGGL(k_absmax, dim3(grid), dim3(kBlock), 0, c->stream, c->d_data, c->stride, c->n,
                        c->ND, us ? 12 : -1, us ? 9 : (c->cfg.model == LSQR_MODEL_DENSE ? c->ND - 1 : c->ND),
-                       c->d_counter + 5);  // dense: the coefficient columns separately from the right-hand side
+                       c->d_counter + CNT_ABSMAX);  // dense: the coefficient columns separately from the right-hand side
     HIPCHK(c, hipGetLastError());
   }
-  HIPCHK(c, hipMemcpyAsync(c->h_pin, c->d_counter + 5, 2 * sizeof(unsigned long long),
+  HIPCHK(c, hipMemcpyAsync(c->h_pin->scratch, c->d_counter + CNT_ABSMAX, 2 * sizeof(unsigned long long),
                            hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, sync_stream(c));
-  memcpy(&c->mc.absmax, c->h_pin, sizeof(double));
-  memcpy(&c->mc.absmax_rot, (char *)c->h_pin + 8, sizeof(double));
+  memcpy(&c->mc.absmax, c->h_pin->scratch, sizeof(double));
+  memcpy(&c->mc.absmax_rot, c->h_pin->scratch + 8, sizeof(double));
   c->absmax_valid = true;
   return LSQR_OK;
 }
@@ -703,9 +778,9 @@ int run_bounds(lsqr_ctx *c) {
   HIPCHK(c, hipGetLastError());
   hipLaunchKernelGGL(k_bounds_final, dim3(1), dim3(256), 0, c->stream, rows, nb, rows + 1024);
   HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(c->h_pin, rows + 1024, sizeof(BoundsRow), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->h_pin->scratch, rows + 1024, sizeof(BoundsRow), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, sync_stream(c));
-  memcpy(&c->h_bounds, c->h_pin, sizeof(BoundsRow));
+  memcpy(&c->h_bounds, c->h_pin->scratch, sizeof(BoundsRow));
   c->bounds_valid = true;
   return LSQR_OK;
 }
@@ -948,14 +1023,14 @@ int with_pp(uint32_t cell_pts, F &&f) {
   return f(std::integral_constant<int, 2>{});
 }
 
-// level 1 of the two-level scan alone over the current batch: d_ub[h] = vote bound, d_counter[4] = surviving pairs
+// level 1 of the two-level scan alone over the current batch: d_ub[h] = vote bound, d_counter[CNT_PAIRS] = surviving pairs
 template <class CM, int PP>
 int run_cells_bounds(lsqr_ctx *c, uint32_t *d_ub, uint32_t *d_nc = nullptr) {
   typedef typename CM::M M;
   const CellConsts cc = cell_consts((const CM *)nullptr, c->mc);
   HIPCHK(c, hipMemsetAsync(d_ub, 0, c->H * sizeof(uint32_t), c->stream));
   if (d_nc) HIPCHK(c, hipMemsetAsync(d_nc, 0, c->H * sizeof(uint32_t), c->stream));
-  if (d_nc) HIPCHK(c, hipMemsetAsync(c->d_counter + 4, 0, sizeof(unsigned long long), c->stream));
+  if (d_nc) HIPCHK(c, hipMemsetAsync(c->d_counter + CNT_PAIRS, 0, sizeof(unsigned long long), c->stream));
   if (c->n_cells == 0) return LSQR_OK;
   // The bounds of the bounded scan are taken on merged boxes (a quarter of the tests; the bound stays valid);
   // the diagnostics (d_nc: lsqr_scan_workload) count the surviving CELLS and stay on the cells.
@@ -991,7 +1066,7 @@ int run_cells_bounds(lsqr_ctx *c, uint32_t *d_ub, uint32_t *d_nc = nullptr) {
   gx = (nbox + per - 1) / per;
   hipLaunchKernelGGL((k_cells_bounds<CM, PP>), dim3(gx, gy), dim3(256), 0, c->stream, boxes, nbox, c->n_sorted,
                      CM::ROW_F32 ? c->d_hparams_f32 : (const float *)c->d_hparams, c->d_hparams_f32,
-                     (uint32_t)c->H, cc, per, d_ub, d_nc ? c->d_counter + 4 : (unsigned long long *)nullptr, d_nc,
+                     (uint32_t)c->H, cc, per, d_ub, d_nc ? c->d_counter + CNT_PAIRS : (unsigned long long *)nullptr, d_nc,
                      (uint8_t *)nullptr, 0u, (const uint32_t *)nullptr, 0u,  // (pair total: diagnostics only -- 8192
                      (uint32_t)(128 * PP) * merge);                          // atomics on one address are ~100 us)
   HIPCHK(c, hipGetLastError());
@@ -1265,11 +1340,11 @@ int h16_probe_unit(lsqr_ctx *c) {
   // ... and 64 instructions of random operands (65 536 sums of 16 products and an addend against fp64)
   hipLaunchKernelGGL(k_dense_h16_probe_random, dim3(1), dim3(64), 0, c->stream, d_probe + kH16ProbeVariants, 64);
   HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(c->h_pin, d_probe, sizeof(float) * (kH16ProbeVariants + 1), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->h_pin->scratch, d_probe, sizeof(float) * (kH16ProbeVariants + 1), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, sync_stream(c));
-  c->h16_unit_dev = dense_h16_probe_worst((const float *)c->h_pin);
+  c->h16_unit_dev = dense_h16_probe_worst((const float *)c->h_pin->scratch);
   {
-    const double rnd = (double)((const float *)c->h_pin)[kH16ProbeVariants];
+    const double rnd = (double)((const float *)c->h_pin->scratch)[kH16ProbeVariants];
     if (!(rnd <= c->h16_unit_dev)) c->h16_unit_dev = rnd;  // (a NaN is the worst)
   }
   c->h16_unit = c->h16_unit_dev <= kH16ProbeLimit ? 1 : -1;
@@ -1360,7 +1435,7 @@ int launch_us_h16(lsqr_ctx *c, size_t rb, size_t re, const double *sp, uint32_t 
     // a workgroup's segment holds one launch's share, not four), the calibrations once
     if (PH || h0 + kUs16HypChunk >= H) {
       hipLaunchKernelGGL((k_us_recheck_seg<M>), dim3(256), dim3(1024), 0, c->stream, c->d_data, c->stride, c->d_hparams,
-                         (int)M::SP, c->mc, c->d_amb, d_segcnt, seg_cap, c->d_votes, (unsigned int *)(c->d_counter + 3));
+                         (int)M::SP, c->mc, c->d_amb, d_segcnt, seg_cap, c->d_votes, (unsigned int *)(c->d_counter + CNT_OVF));
       HIPCHK(c, hipGetLastError());
     }
   }
@@ -1460,7 +1535,7 @@ int run_scan_dense_ee(lsqr_ctx *c, bool *done) {
   } mute{c, c->prof};
   c->prof = false;
   HIPCHK(c, hipMemsetAsync(d_segcnt, 0, 1024 * sizeof(unsigned int), c->stream));
-  HIPCHK(c, hipMemsetAsync(c->d_counter + 3, 0, sizeof(unsigned long long), c->stream));
+  HIPCHK(c, hipMemsetAsync(c->d_counter + CNT_OVF, 0, sizeof(unsigned long long), c->stream));
   bool h16 = false;
   if (c->opt_dense_f32 == 2 && (st = ensure_dense_h16(c, &h16)) != LSQR_OK) return st;
   if (h16)  // the fp16 filter's rows live where the fp32 filter keeps its own (256 B per hypothesis either way)
@@ -1477,7 +1552,7 @@ int run_scan_dense_ee(lsqr_ctx *c, bool *done) {
                                 d_segcnt, seg_cap, h_dev, sel, range_dev, nullptr);
       if (s2 != LSQR_OK) return s2;
       hipLaunchKernelGGL((k_dense_recheck_seg<64>), dim3(512), dim3(256), 0, c->stream, c->d_data, c->stride,
-                         c->d_hparams, c->mc, c->d_amb, d_segcnt, seg_cap, c->d_votes, (unsigned int *)(c->d_counter + 3));
+                         c->d_hparams, c->mc, c->d_amb, d_segcnt, seg_cap, c->d_votes, (unsigned int *)(c->d_counter + CNT_OVF));
       HIPCHK(c, hipGetLastError());
       return LSQR_OK;
     }
@@ -1497,7 +1572,7 @@ int run_scan_dense_ee(lsqr_ctx *c, bool *done) {
       HIPCHK(c, hipGetLastError());
     }
     hipLaunchKernelGGL((k_dense_recheck_seg<64>), dim3(512), dim3(256), 0, c->stream, c->d_data, c->stride,
-                       c->d_hparams, c->mc, c->d_amb, d_segcnt, seg_cap, c->d_votes, (unsigned int *)(c->d_counter + 3));
+                       c->d_hparams, c->mc, c->d_amb, d_segcnt, seg_cap, c->d_votes, (unsigned int *)(c->d_counter + CNT_OVF));
     HIPCHK(c, hipGetLastError());
     return LSQR_OK;
   };
@@ -1517,9 +1592,9 @@ int run_scan_dense_ee(lsqr_ctx *c, bool *done) {
     *done = true;
     return LSQR_OK;
   }
-  HIPCHK(c, hipMemcpyAsync(c->h_pin, c->d_counter + 3, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->h_pin->scratch, c->d_counter + CNT_OVF, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, sync_stream(c));
-  c->dense_amb_max = *(unsigned int *)c->h_pin;
+  c->dense_amb_max = *(unsigned int *)c->h_pin->scratch;
   dense_worklist_debug(c, d_segcnt, seg_cap);
   if (c->dense_amb_max <= seg_cap) {
     *done = true;
@@ -1555,7 +1630,7 @@ int run_scan_us_ee(lsqr_ctx *c) {
       if ((st = ensure_us_h16<M>(c, &h16)) != LSQR_OK) return st;
       if (h16) {
         HIPCHK(c, hipMemsetAsync(d_segcnt, 0, 1024 * sizeof(unsigned int), c->stream));
-        HIPCHK(c, hipMemsetAsync(c->d_counter + 3, 0, sizeof(unsigned long long), c->stream));
+        HIPCHK(c, hipMemsetAsync(c->d_counter + CNT_OVF, 0, sizeof(unsigned long long), c->stream));
       }
     }
   }
@@ -1598,11 +1673,11 @@ int run_scan_us_ee(lsqr_ctx *c) {
     return LSQR_OK;
   }
   if (h16) {  // a worklist segment that overflowed (not seen): everything again with the packed fp32 filter
-    HIPCHK(c, hipMemcpyAsync(c->h_pin, c->d_counter + 3, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->h_pin->scratch, c->d_counter + CNT_OVF, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, sync_stream(c));
-    if (*(unsigned int *)c->h_pin > seg_cap) {
+    if (*(unsigned int *)c->h_pin->scratch > seg_cap) {
       (void)fail(c, LSQR_OK, "US fp16 filter: worklist segment overflow (fill %u > %u), fp32 filter used",
-                 *(unsigned int *)c->h_pin, seg_cap);
+                 *(unsigned int *)c->h_pin->scratch, seg_cap);
       const int keep = c->opt_us_h16;
       c->opt_us_h16 = 0;
       c->prof = mute.was;
@@ -1636,7 +1711,7 @@ int run_scan(lsqr_ctx *c) {
             }
           }
           HIPCHK(c, hipMemsetAsync(c->d_votes, 0, c->H * sizeof(uint32_t), c->stream));
-          HIPCHK(c, hipMemsetAsync(c->d_counter + 3, 0, sizeof(unsigned long long), c->stream));
+          HIPCHK(c, hipMemsetAsync(c->d_counter + CNT_OVF, 0, sizeof(unsigned long long), c->stream));
           double *d_thr = c->d_partials;  // scratch: 2 doubles per hypothesis (H <= 2^20 checked)
           if (c->H * 2 > (size_t)kDenseBlocks * 2160) return fail(c, LSQR_ERR_INVALID, "batch too large");
           size_t tiles = (c->n + 63) / 64;
@@ -1672,7 +1747,7 @@ int run_scan(lsqr_ctx *c) {
                   return st;
                 hipLaunchKernelGGL((k_dense_recheck_seg<64>), dim3((unsigned)nb16), dim3(256), 0, c->stream, c->d_data,
                                    c->stride, c->d_hparams, c->mc, c->d_amb, d_segcnt, seg_cap, c->d_votes,
-                                   (unsigned int *)(c->d_counter + 3));
+                                   (unsigned int *)(c->d_counter + CNT_OVF));
                 HIPCHK(c, hipGetLastError());
               } else {
                 ProfScope ps(c, KID_SCAN);
@@ -1695,23 +1770,23 @@ int run_scan(lsqr_ctx *c) {
                 }
                 hipLaunchKernelGGL((k_dense_recheck_seg<64>), dim3((unsigned)nblk), dim3(256), 0, c->stream, c->d_data,
                                    c->stride, c->d_hparams, c->mc, c->d_amb, d_segcnt, seg_cap, c->d_votes,
-                                   (unsigned int *)(c->d_counter + 3));
+                                   (unsigned int *)(c->d_counter + CNT_OVF));
                 HIPCHK(c, hipGetLastError());
               }
               if (c->defer_ovf) {
                 c->ovf_cap = seg_cap;
                 return LSQR_OK;
               }
-              HIPCHK(c, hipMemcpyAsync(c->h_pin, c->d_counter + 3, sizeof(unsigned long long), hipMemcpyDeviceToHost,
+              HIPCHK(c, hipMemcpyAsync(c->h_pin->scratch, c->d_counter + CNT_OVF, sizeof(unsigned long long), hipMemcpyDeviceToHost,
                                        c->stream));
               HIPCHK(c, sync_stream(c));
-              c->dense_amb_max = *(unsigned int *)c->h_pin;
+              c->dense_amb_max = *(unsigned int *)c->h_pin->scratch;
               dense_worklist_debug(c, d_segcnt, seg_cap);
               if (c->dense_amb_max <= seg_cap) return LSQR_OK;
               (void)fail(c, LSQR_OK, "dense fp16 / fp32 filter: worklist segment overflow (fill %u > %u), fp64 filter used",
                          c->dense_amb_max, seg_cap);
               HIPCHK(c, hipMemsetAsync(c->d_votes, 0, c->H * sizeof(uint32_t), c->stream));   // overflow: fp64 filter
-              HIPCHK(c, hipMemsetAsync(c->d_counter + 3, 0, sizeof(unsigned long long), c->stream));
+              HIPCHK(c, hipMemsetAsync(c->d_counter + CNT_OVF, 0, sizeof(unsigned long long), c->stream));
             }
           }
           {
@@ -1728,7 +1803,7 @@ int run_scan(lsqr_ctx *c) {
                   hipLaunchKernelGGL((k_scan_dense_mfma2<64>), dim3((unsigned)nblk), dim3(256), lds2,
                                      c->stream, c->d_data, c->stride, c->n, rpb,
                                      c->d_hparams + h0 * M::NR, d_thr + 2 * h0, hc, (int)c->cfg.dim,
-                                     c->d_votes + h0, c->d_amb, (unsigned int *)(c->d_counter + 3),
+                                     c->d_votes + h0, c->d_amb, (unsigned int *)(c->d_counter + CNT_OVF),
                                      (uint32_t)h0);
                   HIPCHK(c, hipGetLastError());
                   continue;
@@ -1738,13 +1813,13 @@ int run_scan(lsqr_ctx *c) {
               hipLaunchKernelGGL((k_scan_dense_mfma<M::NR>), dim3((unsigned)nblk), dim3(256), lds,
                                  c->stream, c->d_data, c->stride, c->n, rpb,
                                  c->d_hparams + h0 * M::NR, d_thr + 2 * h0, hc, (int)c->cfg.dim,
-                                 c->d_votes + h0, c->d_amb, (unsigned int *)(c->d_counter + 3),
+                                 c->d_votes + h0, c->d_amb, (unsigned int *)(c->d_counter + CNT_OVF),
                                  (uint32_t)h0);
               HIPCHK(c, hipGetLastError());
             }
             hipLaunchKernelGGL((k_dense_recheck<M::NR>), dim3(64), dim3(256), 0, c->stream, c->d_data,
                                c->stride, c->d_hparams, c->mc, c->d_amb,
-                               (const unsigned int *)(c->d_counter + 3), c->d_votes);
+                               (const unsigned int *)(c->d_counter + CNT_OVF), c->d_votes);
             HIPCHK(c, hipGetLastError());
           }
           // worklist overflow (never seen: ~1e-13 of the pairs are ambiguous) -> exact kernel
@@ -1752,10 +1827,10 @@ int run_scan(lsqr_ctx *c) {
             c->ovf_cap = kAmbCap;
             return LSQR_OK;
           }
-          HIPCHK(c, hipMemcpyAsync(c->h_pin, c->d_counter + 3, sizeof(unsigned long long),
+          HIPCHK(c, hipMemcpyAsync(c->h_pin->scratch, c->d_counter + CNT_OVF, sizeof(unsigned long long),
                                    hipMemcpyDeviceToHost, c->stream));
           HIPCHK(c, sync_stream(c));
-          if (*(unsigned int *)c->h_pin <= kAmbCap) return LSQR_OK;
+          if (*(unsigned int *)c->h_pin->scratch <= kAmbCap) return LSQR_OK;
         }
       }
     }
@@ -1775,7 +1850,7 @@ int run_scan(lsqr_ctx *c) {
               unsigned int *d_segcnt = (unsigned int *)((float *)c->d_partials + 2 * 8192 + 64 * 8192);
               const uint32_t seg_cap = kAmbCap / 1024;
               HIPCHK(c, hipMemsetAsync(d_segcnt, 0, 1024 * sizeof(unsigned int), c->stream));
-              HIPCHK(c, hipMemsetAsync(c->d_counter + 3, 0, sizeof(unsigned long long), c->stream));
+              HIPCHK(c, hipMemsetAsync(c->d_counter + CNT_OVF, 0, sizeof(unsigned long long), c->stream));
               {
                 ProfScope ps(c, KID_SCAN);
                 if ((st = launch_us_h16<M>(c, 0, c->n, c->d_hparams, (uint32_t)c->H, d_segcnt, seg_cap, nullptr, nullptr,
@@ -1786,12 +1861,12 @@ int run_scan(lsqr_ctx *c) {
                 c->ovf_cap = seg_cap;
                 return LSQR_OK;
               }
-              HIPCHK(c, hipMemcpyAsync(c->h_pin, c->d_counter + 3, sizeof(unsigned long long), hipMemcpyDeviceToHost,
+              HIPCHK(c, hipMemcpyAsync(c->h_pin->scratch, c->d_counter + CNT_OVF, sizeof(unsigned long long), hipMemcpyDeviceToHost,
                                        c->stream));
               HIPCHK(c, sync_stream(c));
-              if (*(unsigned int *)c->h_pin <= seg_cap) return LSQR_OK;
+              if (*(unsigned int *)c->h_pin->scratch <= seg_cap) return LSQR_OK;
               (void)fail(c, LSQR_OK, "US fp16 filter: worklist segment overflow (fill %u > %u), fp32 filter used",
-                         *(unsigned int *)c->h_pin, seg_cap);
+                         *(unsigned int *)c->h_pin->scratch, seg_cap);
               HIPCHK(c, hipMemsetAsync(c->d_votes, 0, c->H * sizeof(uint32_t), c->stream));
             }
           }
@@ -1889,7 +1964,7 @@ int run_scan(lsqr_ctx *c) {
                 // the batch in key order (cells.h: k_plane_order): similar planes share a 64-group
                 if (c->opt_hyp_order && c->H >= 1024 && c->H <= kOrderCap) {
                   const uint32_t H = (uint32_t)c->H;
-                  uint32_t *perm = c->d_sel + kPilots, *cnt = (uint32_t *)(c->d_counter + 7);
+                  uint32_t *perm = c->d_sel + kPilots, *cnt = (uint32_t *)(c->d_counter + CNT_FLAG);
                   double *sp_b = c->d_hparams2 + (size_t)kPilots * M::SP;
                   float *spf_b = c->d_hparams2_f32 + (size_t)kPilots * M::SPF;
                   uint32_t *votes_b = c->d_votes2 + kPilots;
@@ -2038,7 +2113,7 @@ void phantom_solve_block(const lsqr_model_cfg &cfg, const double *blk, SolveOut 
 int launch_solve_dense(lsqr_ctx *c, bool rows = false, int use_mask = 0, size_t begin = 0, size_t end = 0) {
   ProfScope ps(c, KID_SOLVE);
   const int n = (int)c->cfg.dim;
-  int *flag = (int *)(c->d_counter + 7) + 1;  // (the low word of the slot is k_plane_order's count: another model's)
+  int *flag = (int *)(c->d_counter + CNT_FLAG) + 1;  // (the low word of the slot is k_plane_order's count: another model's)
   rows = rows && c->opt_dense_dd && end > begin;
   if (rows) HIPCHK(c, hipMemsetAsync(flag, 0, sizeof(int), c->stream));
   hipLaunchKernelGGL(k_solve_dense, dim3(1), dim3(256), dense_lds_bytes(n), c->stream, c->d_mom, n,
@@ -2056,6 +2131,19 @@ int launch_solve_dense(lsqr_ctx *c, bool rows = false, int use_mask = 0, size_t 
                      flag, c->d_out);
   HIPCHK(c, hipGetLastError());
   return LSQR_OK;
+}
+
+// the closed-form solve of the block in d_mom about d_vec -> d_out (rows, use_mask, begin, end: launch_solve_dense)
+template <class M>
+int launch_solve(lsqr_ctx *c, bool rows = false, int use_mask = 0, size_t begin = 0, size_t end = 0) {
+  if constexpr (M::IS_DENSE) {
+    return launch_solve_dense(c, rows, use_mask, begin, end);
+  } else {
+    ProfScope ps(c, KID_SOLVE);
+    hipLaunchKernelGGL((k_solve<M>), dim3(1), dim3(64), 0, c->stream, c->d_mom, c->d_vec, c->mc, c->d_out);
+    HIPCHK(c, hipGetLastError());
+    return LSQR_OK;
+  }
 }
 
 template <class M>
@@ -2113,10 +2201,10 @@ int launch_moments(lsqr_ctx *c, int use_mask, size_t begin, size_t end, int phas
 }
 
 int read_out(lsqr_ctx *c, SolveOut *o) {
-  HIPCHK(c, hipMemcpyAsync(c->h_pin, c->d_out, sizeof(SolveOut), hipMemcpyDeviceToHost,
+  HIPCHK(c, hipMemcpyAsync(c->h_pin->scratch, c->d_out, sizeof(SolveOut), hipMemcpyDeviceToHost,
                            c->stream));
   HIPCHK(c, sync_stream(c));
-  memcpy(o, c->h_pin, sizeof(SolveOut));
+  memcpy(o, c->h_pin->scratch, sizeof(SolveOut));
   return LSQR_OK;
 }
 
@@ -2206,7 +2294,7 @@ __global__ void k_record_origin(const unsigned long long *__restrict__ idx, cons
 }
 
 // the fit origin -> d_vec (ORG_WINNER: d_par holds the winner's scan row and c->win_rec its first drawn record;
-// ORG_WINNER_DEV: d_counter[1] its packed value and d_subsets the batch's subsets)
+// ORG_WINNER_DEV: d_counter[CNT_BEST] its packed value and d_subsets the batch's subsets)
 int set_fit_origin(lsqr_ctx *c, FitOrigin how) {
   return dispatch(c->cfg, [&](auto tag) -> int {
     typedef typename decltype(tag)::type M;
@@ -2224,11 +2312,11 @@ int set_fit_origin(lsqr_ctx *c, FitOrigin how) {
         HIPCHK(c, hipMemcpyAsync(c->d_vec, c->d_data + r * c->stride, sizeof(double) * M::ND,
                                  hipMemcpyDeviceToDevice, c->stream));
       } else if (how == ORG_WINNER_DEV) {
-        hipLaunchKernelGGL(k_winner_origin, dim3(1), dim3(64), 0, c->stream, c->d_counter + 1, c->d_subsets, c->K,
+        hipLaunchKernelGGL(k_winner_origin, dim3(1), dim3(64), 0, c->stream, c->d_counter + CNT_BEST, c->d_subsets, c->K,
                            c->d_data, c->stride, (int)M::ND, c->d_vec);
         HIPCHK(c, hipGetLastError());
       } else {  // ORG_MASK
-        unsigned long long *first = c->d_counter + 6;
+        unsigned long long *first = c->d_counter + CNT_FIRST;
         HIPCHK(c, hipMemsetAsync(first, 0xFF, sizeof(unsigned long long), c->stream));
         hipLaunchKernelGGL(k_first_masked, dim3(grid_for(c->n, kBlock * 16, 1024)), dim3(kBlock), 0, c->stream,
                            c->d_mask, c->n, first);
@@ -2245,26 +2333,22 @@ int set_fit_origin(lsqr_ctx *c, FitOrigin how) {
 // the closed-form part of run_fit without the read-back: moments + solve chained on the stream, result in
 // d_out.  Models whose fit needs the host in the loop (LM, the phantom's Gram solve) are refused.
 // have_origin: the caller has put the fit origin into d_vec (set_fit_origin)
+template <class M>
+int enqueue_closed_fit(lsqr_ctx *c, int use_mask, bool have_moments, bool have_origin) {
+  int nmom = 0, st;
+  if constexpr (M::IS_DENSE) {
+    if (!have_moments && (st = launch_moments_dense(c, use_mask, 0, c->n, &nmom)) != LSQR_OK) return st;
+  } else if (!have_moments) {
+    if (!have_origin && (st = set_fit_origin(c, use_mask ? ORG_MASK : ORG_ALL)) != LSQR_OK) return st;
+    if ((st = launch_moments<M>(c, use_mask, 0, c->n, 0, &nmom)) != LSQR_OK) return st;
+  }
+  return launch_solve<M>(c, true, use_mask, 0, c->n);
+}
 int enqueue_fit(lsqr_ctx *c, int use_mask, bool have_moments = false, bool have_origin = false) {
   if (wants_lm(c->cfg) || c->cfg.model == LSQR_MODEL_PHANTOM)
     return fail(c, LSQR_ERR_INVALID, "this fit needs the host between device passes");
   return dispatch(c->cfg, [&](auto tag) -> int {
-    typedef typename decltype(tag)::type M;
-    int nmom = 0, st;
-    if constexpr (M::IS_DENSE) {
-      if (!have_moments && (st = launch_moments_dense(c, use_mask, 0, c->n, &nmom)) != LSQR_OK) return st;
-      return launch_solve_dense(c, true, use_mask, 0, c->n);
-    } else {
-      if (!have_moments) {
-        if (!have_origin && (st = set_fit_origin(c, use_mask ? ORG_MASK : ORG_ALL)) != LSQR_OK) return st;
-        if ((st = launch_moments<M>(c, use_mask, 0, c->n, 0, &nmom)) != LSQR_OK) return st;
-      }
-      ProfScope ps(c, KID_SOLVE);
-      hipLaunchKernelGGL((k_solve<M>), dim3(1), dim3(64), 0, c->stream, c->d_mom, c->d_vec, c->mc,
-                         c->d_out);
-      HIPCHK(c, hipGetLastError());
-      return LSQR_OK;
-    }
+    return enqueue_closed_fit<typename decltype(tag)::type>(c, use_mask, have_moments, have_origin);
   });
 }
 
@@ -2472,7 +2556,7 @@ int lm_persist_fit(lsqr_ctx *c, const double *tiles, size_t cnt, int nb, LmState
   hipError_t se = sync_stream(c);
   lmp_release(c->device, G);
   if (se != hipSuccess) return fail(c, LSQR_ERR_HIP, "persistent LM kernel: %s", hipGetErrorString(se));
-  LmpCtl *hc = (LmpCtl *)((char *)c->h_pin + 32768);  // (8192: the mask count finish_ransac reads after the fit; 16384, 49152+: other stagings)
+  LmpCtl *hc = &c->h_pin->lmp;  // (an area of its own, PinLayout: finish_ransac reads mask_head after the fit)
   HIPCHK(c, hipMemcpy(hc, c->d_lmp, sizeof(LmpCtl), hipMemcpyDeviceToHost));
   c->lmp_last[0] = (uint64_t)c->opt_lm_persist;
   c->lmp_last[1] = (uint64_t)Gl;
@@ -2501,26 +2585,16 @@ int run_fit(lsqr_ctx *c, int use_mask, SolveOut *out, bool have_moments = false,
     int nmom = 0, st;
     if constexpr (requires { M::IS_PHANTOM; }) {
       if ((st = launch_moments_phantom(c, use_mask, 0, c->n, &nmom)) != LSQR_OK) return st;
-      HIPCHK(c, hipMemcpyAsync(c->h_pin, c->d_mom, sizeof(double) * nmom, hipMemcpyDeviceToHost,
+      HIPCHK(c, hipMemcpyAsync(c->h_pin->scratch, c->d_mom, sizeof(double) * nmom, hipMemcpyDeviceToHost,
                                c->stream));
       HIPCHK(c, sync_stream(c));
-      phantom_solve_block(c->cfg, (const double *)c->h_pin, out);
+      phantom_solve_block(c->cfg, c->h_pin->scratch_f64, out);
       return LSQR_OK;
     } else if constexpr (M::IS_DENSE) {
-      if (!have_moments && (st = launch_moments_dense(c, use_mask, 0, c->n, &nmom)) != LSQR_OK) return st;
-      if ((st = launch_solve_dense(c, true, use_mask, 0, c->n)) != LSQR_OK) return st;
+      if ((st = enqueue_closed_fit<M>(c, use_mask, have_moments, have_origin)) != LSQR_OK) return st;
       return read_out(c, out);
     } else {
-    if (!have_moments) {
-    if (!have_origin && (st = set_fit_origin(c, use_mask ? ORG_MASK : ORG_ALL)) != LSQR_OK) return st;
-    if ((st = launch_moments<M>(c, use_mask, 0, c->n, 0, &nmom)) != LSQR_OK) return st;
-    }
-    {
-      ProfScope ps(c, KID_SOLVE);
-      hipLaunchKernelGGL((k_solve<M>), dim3(1), dim3(64), 0, c->stream, c->d_mom, c->d_vec, c->mc,
-                         c->d_out);
-      HIPCHK(c, hipGetLastError());
-    }
+    if ((st = enqueue_closed_fit<M>(c, use_mask, have_moments, have_origin)) != LSQR_OK) return st;
     if (!wants_lm(c->cfg)) return read_out(c, out);
     if ((st = read_out(c, out)) != LSQR_OK) return st;
     if (!out->ok) return LSQR_OK;  // algebraic initialiser failed -> empty (Sphere...hxx:231-232)
@@ -2534,7 +2608,7 @@ int run_fit(lsqr_ctx *c, int use_mask, SolveOut *out, bool have_moments = false,
         // a few hundred flops per evaluation; every N-scale operation stays a device pass.
         LmState &s = c->h_lm;
         lm_init(s, n, out->params, ftol, xtol, gtol, maxfev, 100.0);
-        double *pin = (double *)c->h_pin;
+        double *pin = c->h_pin->scratch_f64;
         if (c->opt_lm_fused) {
           // one launch per evaluation: trial point by value, block sums + final sum in the same kernel, the
           // result lands in pinned host memory and the host polls its sequence flag (no stream synchronisation,
@@ -2733,7 +2807,7 @@ int launch_mask(lsqr_ctx *c, size_t begin, size_t end) {
   if (st != LSQR_OK) return st;
   st = dispatch(c->cfg, [&](auto tag) -> int {
     typedef typename decltype(tag)::type M;
-    HIPCHK(c, hipMemsetAsync(c->d_counter, 0, sizeof(unsigned long long), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->d_counter + CNT_MASK, 0, sizeof(unsigned long long), c->stream));
     if constexpr (M::SP > M::P && !M::IS_DENSE) {
       hipLaunchKernelGGL((k_prepare<M>), dim3(1), dim3(64), 0, c->stream, c->d_par, c->mc);
       HIPCHK(c, hipGetLastError());
@@ -2744,13 +2818,13 @@ int launch_mask(lsqr_ctx *c, size_t begin, size_t end) {
       const size_t lds = sizeof(double) * 4 * 32 * ((n + 1) | 1);
       int grid = grid_for(end - begin, 4 * 32 * 4, 256 * 4);
       hipLaunchKernelGGL((k_mask_dense<M::NR>), dim3(grid), dim3(256), lds, c->stream, c->d_data,
-                         c->stride, begin, end, n, c->d_par, c->mc.delta, c->d_mask, c->d_counter);
+                         c->stride, begin, end, n, c->d_par, c->mc.delta, c->d_mask, c->d_counter + CNT_MASK);
       HIPCHK(c, hipGetLastError());
       return LSQR_OK;
     }
     int grid = grid_for(end - begin, kBlock * 8, 256 * 8);
     hipLaunchKernelGGL((k_mask<M>), dim3(grid), dim3(kBlock), 0, c->stream, c->d_data, c->stride,
-                       begin, end, c->d_par, c->mc, c->d_mask, c->d_counter);
+                       begin, end, c->d_par, c->mc, c->d_mask, c->d_counter + CNT_MASK);
     HIPCHK(c, hipGetLastError());
     return LSQR_OK;
   });
@@ -2767,18 +2841,18 @@ int run_mask(lsqr_ctx *c, size_t begin, size_t end, uint8_t *mask_out, uint64_t 
   // dense system: the one-pass kernel (mask + block of sums, dense.h: k_mask_syrk_dense) is the faster mask as well
   if (c->cfg.model == LSQR_MODEL_DENSE && (st = launch_mask_moments(c, begin, end, &nm, &fused)) != LSQR_OK) return st;
   if (!fused && (st = launch_mask(c, begin, end)) != LSQR_OK) return st;
-  HIPCHK(c, hipMemcpyAsync(c->h_pin, c->d_counter, sizeof(unsigned long long),
+  HIPCHK(c, hipMemcpyAsync(c->h_pin->scratch, c->d_counter + CNT_MASK, sizeof(unsigned long long),
                            hipMemcpyDeviceToHost, c->stream));
   if (mask_out)
     HIPCHK(c, hipMemcpyAsync(mask_out, c->d_mask + begin, end - begin, hipMemcpyDeviceToHost,
                              c->stream));
   HIPCHK(c, sync_stream(c));
-  if (count_out) *count_out = *(unsigned long long *)c->h_pin;
+  if (count_out) *count_out = *c->h_pin->scratch_u64;
   return LSQR_OK;
 }
 
 // mask of d_par over [begin, end) and the phase-0 moment block of the agreeing records about d_vec (set by the
-// caller) in ONE pass; -> d_mask, d_counter[0], d_mom.  *fused = false (nothing launched) for the models
+// caller) in ONE pass; -> d_mask, d_counter[CNT_MASK], d_mom.  *fused = false (nothing launched) for the models
 // whose moments are not a per-record accumulate (dense: SYRK on the matrix cores; phantom: Gram of the rows).
 int launch_mask_moments(lsqr_ctx *c, size_t begin, size_t end, int *nmom, bool *fused) {
   *fused = false;
@@ -2793,7 +2867,7 @@ int launch_mask_moments(lsqr_ctx *c, size_t begin, size_t end, int *nmom, bool *
         ((uintptr_t)c->d_data & 15) != 0 || ((begin * (size_t)nz) & 1) != 0)  // 16-byte pieces from the first row on
       return LSQR_OK;
     if ((st = ensure_absmax(c)) != LSQR_OK) return st;  // magnitudes for the band of the four-chain evaluation
-    HIPCHK(c, hipMemsetAsync(c->d_counter, 0, sizeof(unsigned long long), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->d_counter + CNT_MASK, 0, sizeof(unsigned long long), c->stream));
     const size_t cnt = end - begin;
     const int nbuf = (c->opt_mask_ring == 4 && n == 64) ? 4 : 2;
     int nb = grid_for(cnt, 64 * 4, nbuf == 2 ? 512 : 256);   // two workgroups per CU / one
@@ -2811,7 +2885,7 @@ int launch_mask_moments(lsqr_ctx *c, size_t begin, size_t end, int *nmom, bool *
       auto launch = [&](auto kern) {
         (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         hipLaunchKernelGGL(kern, dim3(nb), dim3(256), lds, c->stream, c->d_data, begin, end, chunk, n, c->d_par,
-                           c->mc.delta, c->d_mask, c->d_counter, ps, c->d_partials, c->mc.absmax_rot, c->mc.absmax,
+                           c->mc.delta, c->d_mask, c->d_counter + CNT_MASK, ps, c->d_partials, c->mc.absmax_rot, c->mc.absmax,
                            c->opt_mask_band > 0 ? (double)c->opt_mask_band : 1.0, c->opt_mask_diag);
       };
       if (nbuf == 4) {
@@ -2840,7 +2914,7 @@ int launch_mask_moments(lsqr_ctx *c, size_t begin, size_t end, int *nmom, bool *
     if constexpr (M::IS_DENSE || requires { M::IS_PHANTOM; }) {
       return LSQR_ERR_INVALID;
     } else {
-      HIPCHK(c, hipMemsetAsync(c->d_counter, 0, sizeof(unsigned long long), c->stream));
+      HIPCHK(c, hipMemsetAsync(c->d_counter + CNT_MASK, 0, sizeof(unsigned long long), c->stream));
       if constexpr (M::SP > M::P) {
         hipLaunchKernelGGL((k_prepare<M>), dim3(1), dim3(64), 0, c->stream, c->d_par, c->mc);
         HIPCHK(c, hipGetLastError());
@@ -2860,7 +2934,7 @@ int launch_mask_moments(lsqr_ctx *c, size_t begin, size_t end, int *nmom, bool *
           if (nb < 1) nb = 1;
           ProfScope ps(c, KID_MASK);
           hipLaunchKernelGGL((k_mask_moments_us_mfma<M>), dim3(nb), dim3(kBlock), 0, c->stream, c->d_data, begin, end,
-                             c->d_par, c->mc, c->d_mask, c->d_counter, c->d_partials);
+                             c->d_par, c->mc, c->d_mask, c->d_counter + CNT_MASK, c->d_partials);
           HIPCHK(c, hipGetLastError());
           done = true;
         }
@@ -2868,7 +2942,7 @@ int launch_mask_moments(lsqr_ctx *c, size_t begin, size_t end, int *nmom, bool *
       if (!done) {
         ProfScope ps(c, KID_MASK);
         hipLaunchKernelGGL((k_mask_moments<M>), dim3(nb), dim3(kBlock), 0, c->stream, c->d_data, c->stride,
-                           begin, end, chunk, c->d_par, c->d_vec, c->mc, c->d_mask, c->d_counter,
+                           begin, end, chunk, c->d_par, c->d_vec, c->mc, c->d_mask, c->d_counter + CNT_MASK,
                            c->d_partials);
         HIPCHK(c, hipGetLastError());
       }
@@ -3278,7 +3352,7 @@ int lsqr_get_hypothesis(lsqr_ctx *c, size_t h, double *params, uint8_t *valid) {
   int st = need_ready(c, true);
   if (st != LSQR_OK) return st;
   if (h >= c->H) return fail(c, LSQR_ERR_INVALID, "hypothesis index out of range");
-  double *hp = (double *)c->h_pin;
+  double *hp = c->h_pin->scratch_f64;
   HIPCHK(c, hipMemcpyAsync(hp, c->d_hparams + h * c->HS, sizeof(double) * c->P,
                            hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(hp + 64, c->d_valid + h, 1, hipMemcpyDeviceToHost, c->stream));
@@ -3293,12 +3367,12 @@ int lsqr_best(lsqr_ctx *c, uint64_t *packed) {
   if (st != LSQR_OK) return st;
   if (!packed || !c->scanned) return fail(c, LSQR_ERR_STATE, "lsqr_scan has not run");
   hipLaunchKernelGGL(k_best, dim3(1), dim3(kBlock), 0, c->stream, c->d_votes, c->d_valid,
-                     (uint32_t)c->H, c->d_counter + 1);
+                     (uint32_t)c->H, c->d_counter + CNT_BEST);
   HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(c->h_pin, c->d_counter + 1, sizeof(unsigned long long),
+  HIPCHK(c, hipMemcpyAsync(c->h_pin->scratch, c->d_counter + CNT_BEST, sizeof(unsigned long long),
                            hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, sync_stream(c));
-  *packed = *(unsigned long long *)c->h_pin;
+  *packed = *c->h_pin->scratch_u64;
   return LSQR_OK;
 }
 
@@ -3336,6 +3410,56 @@ int lsqr_set_mask(lsqr_ctx *c, const uint8_t *mask) {
   return LSQR_OK;
 }
 
+// ---- the result tail of the fit entry points -----------------------------------------------------------------------
+static void fill_info(const SolveOut &out, lsqr_fit_info *info) {
+  if (!info) return;
+  memset(info, 0, sizeof *info);
+  info->n_params = out.n_params;
+  info->lm_info = out.lm_info;
+  info->lm_nfev = out.lm_nfev;
+  info->reserved = out.pad;  // LM: stall evaluation; dense: 1 = the double-double route produced the result
+  info->cost = out.cost;
+}
+
+// the parameters of a fit that has a result, LSQR_EMPTY otherwise
+static int deliver_params(const SolveOut &out, double *params_out) {
+  if (!out.ok) return LSQR_EMPTY;
+  if (params_out)
+    for (int j = 0; j < out.n_params; j++) params_out[j] = out.params[j];
+  return LSQR_OK;
+}
+
+static int deliver_fit(const SolveOut &out, double *params_out, lsqr_fit_info *info) {
+  fill_info(out, info);
+  return deliver_params(out, params_out);
+}
+
+// the fit record of a RANSAC result (n_params is 0 without a result); lm_fields = false: lm_info, lm_nfev, reserved stay
+static void fill_ransac_fit(const SolveOut &out, uint64_t n_used, bool lm_fields, lsqr_fit_info *fit) {
+  fit->n_params = out.ok ? out.n_params : 0;
+  if (lm_fields) {
+    fit->lm_info = out.lm_info;
+    fit->lm_nfev = out.lm_nfev;
+    fit->reserved = out.pad;
+  }
+  fit->n_used = n_used;
+  fit->cost = out.cost;
+}
+
+// lsqr_ransac_info of one batch (pk: k_best's packed winner, first: the batch's stream index, cnt: the mask's inliers)
+static void fill_ransac_info(lsqr_ransac_info *info, unsigned long long pk, uint64_t first, uint64_t H, uint64_t cnt,
+                             size_t n, const SolveOut &out, bool lm_fields = true) {
+  if (!info) return;
+  memset(info, 0, sizeof *info);
+  info->fraction = n ? (double)cnt / (double)n : 0.0;
+  info->iterations = H;
+  info->evaluated = H;
+  info->best_votes = (uint32_t)(pk >> 32);
+  info->best_index = pk ? first + (0xFFFFFFFFull - (pk & 0xFFFFFFFFull)) : 0;
+  fill_ransac_fit(out, cnt, lm_fields, &info->fit);
+  info->n_params = info->fit.n_params;
+}
+
 // ---- final fit -------------------------------------------------------------------------------------
 int lsqr_ls_fit(lsqr_ctx *c, int use_mask, double *params_out, lsqr_fit_info *info) {
   int st = need_ready(c, true);
@@ -3345,25 +3469,13 @@ int lsqr_ls_fit(lsqr_ctx *c, int use_mask, double *params_out, lsqr_fit_info *in
   SolveOut out;
   memset(&out, 0, sizeof out);
   if ((st = run_fit(c, use_mask, &out)) != LSQR_OK) return st;
-  if (info) {
-    memset(info, 0, sizeof *info);
-    info->n_params = out.n_params;
-    info->lm_info = out.lm_info;
-    info->lm_nfev = out.lm_nfev;
-    info->reserved = out.pad;  // LM: stall evaluation; dense: 1 = the double-double route produced the result
-    info->cost = out.cost;
-  }
-  if (!out.ok) {
-    // a Levenberg-Marquardt run that MINPACK reports as failed (the reference then returns an empty vector):
-    // the last iterate is still handed out for diagnostics -- status LSQR_EMPTY and info->n_params == 0 say
-    // that it is not a result
-    if (params_out && out.lm_info != 0)
-      for (int j = 0; j < c->P; j++) params_out[j] = out.params[j];
-    return LSQR_EMPTY;
-  }
-  if (params_out)
-    for (int j = 0; j < out.n_params; j++) params_out[j] = out.params[j];
-  return LSQR_OK;
+  fill_info(out, info);
+  // a Levenberg-Marquardt run that MINPACK reports as failed (the reference then returns an empty vector):
+  // the last iterate is still handed out for diagnostics -- status LSQR_EMPTY and info->n_params == 0 say
+  // that it is not a result
+  if (!out.ok && params_out && out.lm_info != 0)
+    for (int j = 0; j < c->P; j++) params_out[j] = out.params[j];
+  return deliver_params(out, params_out);
 }
 
 int lsqr_moments_len(const lsqr_model_cfg *cfg, int phase) {
@@ -3382,19 +3494,34 @@ int lsqr_moments_len(const lsqr_model_cfg *cfg, int phase) {
   });
 }
 
-int lsqr_moments(lsqr_ctx *c, int use_mask, size_t begin, size_t end, int phase, const double *x,
-                 double *block_out) {
+// lsqr_moments and lsqr_moments_dev: the checks, x -> d_vec, the block of [begin, end) -> d_mom (*nmom doubles).
+// staged: x goes through pinned memory (the copy stays asynchronous) -- four slots in rotation, each guarded by an
+// event, so that a call issued before an earlier call's copy has executed cannot overwrite that copy's source
+static int enqueue_moments(lsqr_ctx *c, int use_mask, size_t begin, size_t end, int phase, const double *x,
+                           const double *block, bool staged, int *nmom) {
   int st = need_ready(c, true);
   if (st != LSQR_OK) return st;
-  if (begin > end || end > c->n || !block_out) return fail(c, LSQR_ERR_INVALID, "bad range");
+  if (begin > end || end > c->n || !block) return fail(c, LSQR_ERR_INVALID, "bad range");
   if (use_mask && !c->mask_valid) return fail(c, LSQR_ERR_STATE, "no mask on the device");
   if (!x) return fail(c, LSQR_ERR_INVALID, "moments need an origin / evaluation point");
+  const int slot = staged ? c->mdev_next++ & 3 : 0;
+  if (staged) {
+    if (!c->mdev_ev[slot]) HIPCHK(c, hipEventCreateWithFlags(&c->mdev_ev[slot], hipEventDisableTiming));
+    else HIPCHK(c, hipEventSynchronize(c->mdev_ev[slot]));
+    memcpy(c->h_pin->mdev_x[slot], x, sizeof(double) * 32);
+    x = c->h_pin->mdev_x[slot];
+  }
   HIPCHK(c, hipMemcpyAsync(c->d_vec, x, sizeof(double) * 32, hipMemcpyHostToDevice, c->stream));
-  int nmom = 0;
-  st = dispatch(c->cfg, [&](auto tag) -> int {
+  if (staged) HIPCHK(c, hipEventRecord(c->mdev_ev[slot], c->stream));
+  return dispatch(c->cfg, [&](auto tag) -> int {
     typedef typename decltype(tag)::type M;
-    return launch_moments<M>(c, use_mask, begin, end, phase, &nmom);
+    return launch_moments<M>(c, use_mask, begin, end, phase, nmom);
   });
+}
+
+int lsqr_moments(lsqr_ctx *c, int use_mask, size_t begin, size_t end, int phase, const double *x,
+                 double *block_out) {
+  int nmom = 0, st = enqueue_moments(c, use_mask, begin, end, phase, x, block_out, false, &nmom);
   if (st != LSQR_OK) return st;
   HIPCHK(c, hipMemcpyAsync(block_out, c->d_mom, sizeof(double) * nmom, hipMemcpyDeviceToHost,
                            c->stream));
@@ -3406,38 +3533,10 @@ int lsqr_moments(lsqr_ctx *c, int use_mask, size_t begin, size_t end, int phase,
 // it in place and reads it back once
 int lsqr_moments_dev(lsqr_ctx *c, int use_mask, size_t begin, size_t end, int phase, const double *x,
                      double *block_dev) {
-  int st = need_ready(c, true);
-  if (st != LSQR_OK) return st;
-  if (begin > end || end > c->n || !block_dev) return fail(c, LSQR_ERR_INVALID, "bad range");
-  if (use_mask && !c->mask_valid) return fail(c, LSQR_ERR_STATE, "no mask on the device");
-  if (!x) return fail(c, LSQR_ERR_INVALID, "moments need an origin / evaluation point");
-  // x staged in pinned memory (the copy stays asynchronous): four slots in rotation, each guarded by an event, so
-  // that a call issued before an earlier call's copy has executed cannot overwrite that copy's source
-  const int slot = c->mdev_next++ & 3;
-  if (!c->mdev_ev[slot]) HIPCHK(c, hipEventCreateWithFlags(&c->mdev_ev[slot], hipEventDisableTiming));
-  else HIPCHK(c, hipEventSynchronize(c->mdev_ev[slot]));
-  double *pin = (double *)((char *)c->h_pin + 57344 + slot * 512);
-  memcpy(pin, x, sizeof(double) * 32);
-  HIPCHK(c, hipMemcpyAsync(c->d_vec, pin, sizeof(double) * 32, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipEventRecord(c->mdev_ev[slot], c->stream));
-  int nmom = 0;
-  st = dispatch(c->cfg, [&](auto tag) -> int {
-    typedef typename decltype(tag)::type M;
-    return launch_moments<M>(c, use_mask, begin, end, phase, &nmom);
-  });
+  int nmom = 0, st = enqueue_moments(c, use_mask, begin, end, phase, x, block_dev, true, &nmom);
   if (st != LSQR_OK) return st;
   HIPCHK(c, hipMemcpyAsync(block_dev, c->d_mom, sizeof(double) * nmom, hipMemcpyDeviceToDevice, c->stream));
   return LSQR_OK;
-}
-
-static void fill_info(const SolveOut &out, lsqr_fit_info *info) {
-  if (!info) return;
-  memset(info, 0, sizeof *info);
-  info->n_params = out.n_params;
-  info->lm_info = out.lm_info;
-  info->lm_nfev = out.lm_nfev;
-  info->reserved = out.pad;  // LM: the evaluation after which the cost never again fell by more than 1e-7 relative
-  info->cost = out.cost;
 }
 
 int lsqr_solve_moments(lsqr_ctx *c, const double *block, const double *origin, double *params_out,
@@ -3449,11 +3548,7 @@ int lsqr_solve_moments(lsqr_ctx *c, const double *block, const double *origin, d
   if (c->cfg.model == LSQR_MODEL_PHANTOM) {  // solved on the host from the Gram block
     SolveOut out;
     phantom_solve_block(c->cfg, block, &out);
-    fill_info(out, info);
-    if (!out.ok) return LSQR_EMPTY;
-    if (params_out)
-      for (int j = 0; j < out.n_params; j++) params_out[j] = out.params[j];
-    return LSQR_OK;
+    return deliver_fit(out, params_out, info);
   }
   HIPCHK(c, hipMemcpyAsync(c->d_mom, block, sizeof(double) * nmom, hipMemcpyHostToDevice,
                            c->stream));
@@ -3461,24 +3556,12 @@ int lsqr_solve_moments(lsqr_ctx *c, const double *block, const double *origin, d
                            hipMemcpyHostToDevice, c->stream));
   st = dispatch(c->cfg, [&](auto tag) -> int {
     typedef typename decltype(tag)::type M;
-    if constexpr (M::IS_DENSE) {
-      return launch_solve_dense(c);
-    } else {
-      ProfScope ps(c, KID_SOLVE);
-      hipLaunchKernelGGL((k_solve<M>), dim3(1), dim3(64), 0, c->stream, c->d_mom, c->d_vec, c->mc,
-                         c->d_out);
-      HIPCHK(c, hipGetLastError());
-      return LSQR_OK;
-    }
+    return launch_solve<M>(c);
   });
   if (st != LSQR_OK) return st;
   SolveOut out;
   if ((st = read_out(c, &out)) != LSQR_OK) return st;
-  fill_info(out, info);
-  if (!out.ok) return LSQR_EMPTY;
-  if (params_out)
-    for (int j = 0; j < out.n_params; j++) params_out[j] = out.params[j];
-  return LSQR_OK;
+  return deliver_fit(out, params_out, info);
 }
 
 int lsqr_lm_begin(lsqr_ctx *c, const double *x0, double *x_trial_out) {
@@ -3498,8 +3581,8 @@ int lsqr_lm_begin(lsqr_ctx *c, const double *x0, double *x_trial_out) {
   SolveOut seed;
   memset(&seed, 0, sizeof seed);
   for (int j = 0; j < n; j++) seed.params[j] = x0[j];
-  memcpy(c->h_pin, &seed, sizeof seed);
-  HIPCHK(c, hipMemcpyAsync(c->d_out, c->h_pin, sizeof seed, hipMemcpyHostToDevice, c->stream));
+  memcpy(c->h_pin->scratch, &seed, sizeof seed);
+  HIPCHK(c, hipMemcpyAsync(c->d_out, c->h_pin->scratch, sizeof seed, hipMemcpyHostToDevice, c->stream));
   hipLaunchKernelGGL(k_lm_init, dim3(1), dim3(64), 0, c->stream, c->d_lm, c->d_out, n, ftol, xtol,
                      gtol, maxfev, 100.0);
   HIPCHK(c, hipGetLastError());
@@ -3524,41 +3607,32 @@ int lsqr_lm_step(lsqr_ctx *c, const double *block, double *x_trial_out, int *con
     phantom_lm(G, c->h_lm, &f);
     phantom_to_out(f, &out);
     *cont = 0;
-    fill_info(out, info);
-    if (!out.ok) return LSQR_EMPTY;
-    if (params_out)
-      for (int j = 0; j < out.n_params; j++) params_out[j] = out.params[j];
-    return LSQR_OK;
+    return deliver_fit(out, params_out, info);
   }
   if (c->opt_lm_host) {
     LmState &s = c->h_lm;
     bool go = lm_advance(s, block);
     *cont = go ? 1 : 0;
-    lsqr_fit_info fi;
-    memset(&fi, 0, sizeof fi);
-    fi.lm_info = s.info;
-    fi.lm_nfev = s.nfev;
-    fi.reserved = s.stall;
-    fi.cost = s.fnorm * s.fnorm;
+    SolveOut out;  // the record run_fit's host loop leaves
+    memset(&out, 0, sizeof out);
+    out.lm_info = s.info;
+    out.lm_nfev = s.nfev;
+    out.pad = s.stall;
+    out.cost = s.fnorm * s.fnorm;
     if (go) {
       if (x_trial_out)
         for (int j = 0; j < s.n; j++) x_trial_out[j] = s.xtrial[j];
-      if (info) *info = fi;
+      fill_info(out, info);
       return LSQR_OK;
     }
-    bool ok = s.info >= 1 && s.info <= 4;
-    double par[64];
-    int np = dispatch(c->cfg, [&](auto tag) -> int {
+    out.ok = s.info >= 1 && s.info <= 4;
+    const int np = dispatch(c->cfg, [&](auto tag) -> int {
       typedef typename decltype(tag)::type M;
-      if constexpr (requires { M::NMOM_LM; }) return M::lm_finalize(s.x, par);
+      if constexpr (requires { M::NMOM_LM; }) return M::lm_finalize(s.x, out.params);
       else return 0;
     });
-    fi.n_params = ok ? np : 0;
-    if (info) *info = fi;
-    if (!ok) return LSQR_EMPTY;
-    if (params_out)
-      for (int j = 0; j < np; j++) params_out[j] = par[j];
-    return LSQR_OK;
+    out.n_params = out.ok ? np : 0;
+    return deliver_fit(out, params_out, info);
   }
   HIPCHK(c, hipMemcpyAsync(c->d_mom, block, sizeof(double) * nmom, hipMemcpyHostToDevice,
                            c->stream));
@@ -3581,17 +3655,14 @@ int lsqr_lm_step(lsqr_ctx *c, const double *block, double *x_trial_out, int *con
   fill_info(out, info);
   if (out.cont) {
     if (x_trial_out) {
-      HIPCHK(c, hipMemcpyAsync(c->h_pin, (const char *)c->d_lm + offsetof(LmState, xtrial),
+      HIPCHK(c, hipMemcpyAsync(c->h_pin->scratch, (const char *)c->d_lm + offsetof(LmState, xtrial),
                                sizeof(double) * LM_NMAX, hipMemcpyDeviceToHost, c->stream));
       HIPCHK(c, sync_stream(c));
-      memcpy(x_trial_out, c->h_pin, sizeof(double) * c->P);
+      memcpy(x_trial_out, c->h_pin->scratch, sizeof(double) * c->P);
     }
     return LSQR_OK;
   }
-  if (!out.ok) return LSQR_EMPTY;
-  if (params_out)
-    for (int j = 0; j < out.n_params; j++) params_out[j] = out.params[j];
-  return LSQR_OK;
+  return deliver_params(out, params_out);
 }
 
 int lsqr_stats(lsqr_ctx *c, const double *params, int use_mask, double out[4]) {
@@ -3663,6 +3734,67 @@ int lsqr_residuals(lsqr_ctx *c, const double *params, size_t begin, size_t end, 
   return LSQR_OK;
 }
 
+// ---- the finish of a winner ------------------------------------------------------------------------------------
+// first-max winner of the scanned batch -> d_counter[CNT_BEST], its scan row -> d_par
+static int enqueue_take_best(lsqr_ctx *c) {
+  hipLaunchKernelGGL(k_best, dim3(1), dim3(kBlock), 0, c->stream, c->d_votes, c->d_valid,
+                     (uint32_t)c->H, c->d_counter + CNT_BEST, 0u);
+  HIPCHK(c, hipGetLastError());
+  hipLaunchKernelGGL(k_take_best, dim3(1), dim3(64), 0, c->stream, c->d_counter + CNT_BEST, c->d_hparams,
+                     c->HS, c->d_par);
+  HIPCHK(c, hipGetLastError());
+  return LSQR_OK;
+}
+
+// The winner's scan row is in d_par: its fit origin -> d_vec, its consensus mask over all records with the fit's moment
+// block in the same pass where the model has one (*fused), the inlier count -> pin_head[0]; ORG_WINNER_DEV (the winner
+// is known on the device only): its packed value -> pin_head[1] as well.
+static int enqueue_winner_finish(lsqr_ctx *c, FitOrigin how, unsigned long long *pin_head, bool *fused) {
+  int st, nm = 0;
+  *fused = false;
+  if ((st = set_fit_origin(c, how)) != LSQR_OK) return st;
+  if ((st = launch_mask_moments(c, 0, c->n, &nm, fused)) != LSQR_OK) return st;
+  if (!*fused && (st = launch_mask(c, 0, c->n)) != LSQR_OK) return st;
+  static_assert(CNT_BEST == CNT_MASK + 1, "{inliers, packed winner} is one copy");
+  HIPCHK(c, hipMemcpyAsync(pin_head, c->d_counter + CNT_MASK, (how == ORG_WINNER_DEV ? 2 : 1) * sizeof(unsigned long long),
+                           hipMemcpyDeviceToHost, c->stream));
+  return LSQR_OK;
+}
+
+// the blocking finish: the head -> h_pin->mask_head, the consensus mask to the caller, the fit (which synchronises)
+static int run_winner_finish(lsqr_ctx *c, FitOrigin how, uint8_t *consensus_out, SolveOut *out) {
+  int st;
+  bool fused = false;
+  if ((st = enqueue_winner_finish(c, how, c->h_pin->mask_head, &fused)) != LSQR_OK) return st;
+  if (consensus_out)
+    HIPCHK(c, hipMemcpyAsync(consensus_out, c->d_mask, c->n, hipMemcpyDeviceToHost, c->stream));
+  memset(out, 0, sizeof *out);
+  return run_fit(c, 1, out, fused, true);
+}
+
+// The winner's scan row is in d_hparams[0]: its mask over the slice [begin, end) and the slice's phase-0 moment block
+// about the model's own point -> d_mask, d_counter[CNT_MASK], d_mom (*nmom doubles).
+static int enqueue_winner_slice(lsqr_ctx *c, size_t begin, size_t end, int *nmom) {
+  int st;
+  HIPCHK(c, hipMemsetAsync(c->d_par, 0, sizeof(double) * 128, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->d_par, c->d_hparams, sizeof(double) * c->HS, hipMemcpyDeviceToDevice,
+                           c->stream));
+  // the origin by this path's own rule, not set_fit_origin's: plane / line: a, sphere: c, zeros for every other model
+  HIPCHK(c, hipMemsetAsync(c->d_vec, 0, sizeof(double) * 32, c->stream));
+  const int m = c->cfg.model;
+  if (m == LSQR_MODEL_PLANE || m == LSQR_MODEL_LINE || m == LSQR_MODEL_SPHERE)
+    HIPCHK(c, hipMemcpyAsync(c->d_vec, c->d_par + (m == LSQR_MODEL_SPHERE ? 0 : c->ND),
+                             sizeof(double) * c->ND, hipMemcpyDeviceToDevice, c->stream));
+  bool fused = false;
+  if ((st = launch_mask_moments(c, begin, end, nmom, &fused)) != LSQR_OK) return st;
+  if (fused) return LSQR_OK;
+  if ((st = launch_mask(c, begin, end)) != LSQR_OK) return st;
+  return dispatch(c->cfg, [&](auto tag) -> int {
+    typedef typename decltype(tag)::type M;
+    return launch_moments<M>(c, 1, begin, end, 0, nmom);
+  });
+}
+
 // ---- RANSAC<T,S>::compute ------------------------------------------------------------------------------
 // RANSAC.hxx:129-139 for the winner stashed in d_best (its full scan-parameter row): consensus mask + the
 // moment block of its least squares fit in one pass, the fit, one host synchronisation (LM fits: one more per
@@ -3672,36 +3804,18 @@ static int finish_ransac(lsqr_ctx *c, bool has_best, uint32_t best_votes, double
   info->best_votes = best_votes;
   info->fraction = (double)best_votes / (double)c->n;
   info->n_params = 0;
-  if (!has_best || best_votes == 0) return LSQR_EMPTY;  // RANSAC.hxx:129: nothing written
+  if (!has_best || best_votes == 0) return LSQR_EMPTY;  // RANSAC.hxx:129: nothing written, nothing enqueued
   int st;
   HIPCHK(c, hipMemsetAsync(c->d_par, 0, sizeof(double) * 128, c->stream));
   HIPCHK(c, hipMemcpyAsync(c->d_par, c->d_best, sizeof(double) * c->HS, hipMemcpyDeviceToDevice, c->stream));
-  bool fused = false;
-  int nm = 0;
-  if ((st = set_fit_origin(c, ORG_WINNER)) != LSQR_OK) return st;
-  if ((st = launch_mask_moments(c, 0, c->n, &nm, &fused)) != LSQR_OK) return st;
-  if (!fused && (st = launch_mask(c, 0, c->n)) != LSQR_OK) return st;
-  unsigned long long *pin2 = (unsigned long long *)((char *)c->h_pin + 8192);
-  HIPCHK(c, hipMemcpyAsync(pin2, c->d_counter, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-  if (consensus_out)
-    HIPCHK(c, hipMemcpyAsync(consensus_out, c->d_mask, c->n, hipMemcpyDeviceToHost, c->stream));
   SolveOut out;
-  memset(&out, 0, sizeof out);
-  if ((st = run_fit(c, 1, &out, fused, true)) != LSQR_OK) return st;  // synchronises the stream
-  const unsigned long long cnt = pin2[0];
+  if ((st = run_winner_finish(c, ORG_WINNER, consensus_out, &out)) != LSQR_OK) return st;
+  const unsigned long long cnt = c->h_pin->mask_head[0];
   if (cnt != best_votes)
     return fail(c, LSQR_ERR_HIP, "consensus mask count %llu != scan votes %u", cnt, best_votes);
-  info->fit.n_params = out.ok ? out.n_params : 0;
-  info->fit.lm_info = out.lm_info;
-  info->fit.lm_nfev = out.lm_nfev;
-  info->fit.reserved = out.pad;
-  info->fit.cost = out.cost;
-  info->fit.n_used = cnt;
-  if (!out.ok) return LSQR_EMPTY;
-  info->n_params = out.n_params;
-  if (params_out)
-    for (int j = 0; j < out.n_params; j++) params_out[j] = out.params[j];
-  return LSQR_OK;
+  fill_ransac_fit(out, cnt, true, &info->fit);
+  info->n_params = info->fit.n_params;
+  return deliver_params(out, params_out);
 }
 
 int lsqr_ransac(lsqr_ctx *c, double p, uint64_t seed, const uint32_t *subsets, size_t n_subsets,
@@ -4024,45 +4138,12 @@ int lsqr_batch_fit(lsqr_ctx *c, uint64_t seed, uint64_t first, size_t H, double 
   if (st != LSQR_OK) return st;
   if ((st = run_scan_batch(c, 0)) != LSQR_OK) return st;
   c->scanned = true;
-  hipLaunchKernelGGL(k_best, dim3(1), dim3(kBlock), 0, c->stream, c->d_votes, c->d_valid,
-                     (uint32_t)c->H, c->d_counter + 1);
-  HIPCHK(c, hipGetLastError());
-  hipLaunchKernelGGL(k_take_best, dim3(1), dim3(64), 0, c->stream, c->d_counter + 1, c->d_hparams,
-                     c->HS, c->d_par);
-  HIPCHK(c, hipGetLastError());
-  bool fused = false;
-  int nm = 0;
-  if ((st = set_fit_origin(c, ORG_WINNER_DEV)) != LSQR_OK) return st;
-  if ((st = launch_mask_moments(c, 0, c->n, &nm, &fused)) != LSQR_OK) return st;
-  if (!fused && (st = launch_mask(c, 0, c->n)) != LSQR_OK) return st;
-  unsigned long long *pin2 = (unsigned long long *)((char *)c->h_pin + 8192);
-  HIPCHK(c, hipMemcpyAsync(pin2, c->d_counter, 2 * sizeof(unsigned long long),
-                           hipMemcpyDeviceToHost, c->stream));  // {inliers, packed winner}
-  if (consensus_out)
-    HIPCHK(c, hipMemcpyAsync(consensus_out, c->d_mask, c->n, hipMemcpyDeviceToHost, c->stream));
+  if ((st = enqueue_take_best(c)) != LSQR_OK) return st;
   SolveOut out;
-  memset(&out, 0, sizeof out);
-  if ((st = run_fit(c, 1, &out, fused, true)) != LSQR_OK) return st;  // synchronises the stream
-  const unsigned long long cnt = pin2[0], pk = pin2[1];
-  if (info) {
-    memset(info, 0, sizeof *info);
-    info->fraction = c->n ? (double)cnt / (double)c->n : 0.0;
-    info->iterations = H;
-    info->evaluated = H;
-    info->best_votes = (uint32_t)(pk >> 32);
-    info->best_index = pk ? first + (0xFFFFFFFFull - (pk & 0xFFFFFFFFull)) : 0;
-    info->n_params = out.ok ? out.n_params : 0;
-    info->fit.n_params = info->n_params;
-    info->fit.lm_info = out.lm_info;
-    info->fit.lm_nfev = out.lm_nfev;
-    info->fit.reserved = out.pad;
-    info->fit.n_used = cnt;
-    info->fit.cost = out.cost;
-  }
-  if (pk == 0 || !out.ok) return LSQR_EMPTY;
-  if (params_out)
-    for (int j = 0; j < out.n_params; j++) params_out[j] = out.params[j];
-  return LSQR_OK;
+  if ((st = run_winner_finish(c, ORG_WINNER_DEV, consensus_out, &out)) != LSQR_OK) return st;
+  const unsigned long long cnt = c->h_pin->mask_head[0], pk = c->h_pin->mask_head[1];
+  fill_ransac_info(info, pk, first, H, cnt, c->n, out);
+  return pk == 0 ? LSQR_EMPTY : deliver_params(out, params_out);
 }
 
 // Second half of a multi-GPU step on one rank, chained on the stream with one synchronisation: the
@@ -4075,46 +4156,27 @@ int lsqr_winner_moments(lsqr_ctx *c, uint64_t seed, uint64_t stream_index, size_
   int st = lsqr_hypotheses_sample(c, seed, stream_index, 1, nullptr);
   if (st != LSQR_OK) return st;
   if (begin > end || end > c->n || !block_out) return fail(c, LSQR_ERR_INVALID, "bad range");
-  HIPCHK(c, hipMemsetAsync(c->d_par, 0, sizeof(double) * 128, c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->d_par, c->d_hparams, sizeof(double) * c->HS, hipMemcpyDeviceToDevice,
-                           c->stream));
-  HIPCHK(c, hipMemsetAsync(c->d_vec, 0, sizeof(double) * 32, c->stream));
-  const int m = c->cfg.model;
-  if (m == LSQR_MODEL_PLANE || m == LSQR_MODEL_LINE || m == LSQR_MODEL_SPHERE)
-    HIPCHK(c, hipMemcpyAsync(c->d_vec, c->d_par + (m == LSQR_MODEL_SPHERE ? 0 : c->ND),
-                             sizeof(double) * c->ND, hipMemcpyDeviceToDevice, c->stream));
   int nmom = 0;
-  bool fused = false;
-  if ((st = launch_mask_moments(c, begin, end, &nmom, &fused)) != LSQR_OK) return st;
-  if (!fused) {
-    if ((st = launch_mask(c, begin, end)) != LSQR_OK) return st;
-    st = dispatch(c->cfg, [&](auto tag) -> int {
-      typedef typename decltype(tag)::type M;
-      return launch_moments<M>(c, 1, begin, end, 0, &nmom);
-    });
-    if (st != LSQR_OK) return st;
-  }
-  double *pin = (double *)((char *)c->h_pin + 16384);  // {valid, count, params[64], origin[32]}
-  HIPCHK(c, hipMemcpyAsync(pin, c->d_valid, 1, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(pin + 1, c->d_counter, sizeof(unsigned long long), hipMemcpyDeviceToHost,
+  if ((st = enqueue_winner_slice(c, begin, end, &nmom)) != LSQR_OK) return st;  // (its own origin rule)
+  WinnerPin *pin = &c->h_pin->winner;
+  HIPCHK(c, hipMemcpyAsync(&pin->valid, c->d_valid, 1, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(&pin->count, c->d_counter + CNT_MASK, sizeof(unsigned long long), hipMemcpyDeviceToHost,
                            c->stream));
-  HIPCHK(c, hipMemcpyAsync(pin + 2, c->d_hparams, sizeof(double) * c->P, hipMemcpyDeviceToHost,
+  HIPCHK(c, hipMemcpyAsync(pin->params, c->d_hparams, sizeof(double) * c->P, hipMemcpyDeviceToHost,
                            c->stream));
-  HIPCHK(c, hipMemcpyAsync(pin + 66, c->d_vec, sizeof(double) * 32, hipMemcpyDeviceToHost,
+  HIPCHK(c, hipMemcpyAsync(pin->origin, c->d_vec, sizeof(double) * 32, hipMemcpyDeviceToHost,
                            c->stream));
   HIPCHK(c, hipMemcpyAsync(block_out, c->d_mom, sizeof(double) * nmom, hipMemcpyDeviceToHost,
                            c->stream));
   HIPCHK(c, sync_stream(c));
-  if (*(const uint8_t *)pin == 0) return LSQR_EMPTY;  // degenerate subset: not a possible winner
-  if (count_out) memcpy(count_out, pin + 1, sizeof(uint64_t));
-  if (params_out) memcpy(params_out, pin + 2, sizeof(double) * c->P);
-  if (origin_out) memcpy(origin_out, pin + 66, sizeof(double) * 32);
+  if (pin->valid == 0) return LSQR_EMPTY;  // degenerate subset: not a possible winner
+  if (count_out) *count_out = pin->count;
+  if (params_out) memcpy(params_out, pin->params, sizeof(double) * c->P);
+  if (origin_out) memcpy(origin_out, pin->origin, sizeof(double) * 32);
   return LSQR_OK;
 }
 
 // ---- pipelined batches: enqueue now, read later ------------------------------------------------------------
-static char *slot_pin(lsqr_ctx *c, int slot) { return (char *)c->h_pin + 49152 + slot * 2048; }
-
 // slot s of a context with L lanes: lane s % L, that lane's own slot s / L (0 or 1)
 static int lane_count(const lsqr_ctx *c) {
   return c->is_lane ? 1 : std::max(1, std::min(c->opt_lanes, (int)lsqr_ctx::kMaxLanes));
@@ -4182,27 +4244,17 @@ int lsqr_batch_fit_enqueue(lsqr_ctx *c, uint64_t seed, uint64_t first, size_t H,
   c->slot_ovf_cap[slot] = c->ovf_cap;
   c->slot_seed[slot] = seed;
   if (c->ovf_cap)  // {fullest worklist segment of this batch's scan} beside the slot's results
-    HIPCHK(c, hipMemcpyAsync(slot_pin(c, slot) + 32, c->d_counter + 3, sizeof(unsigned long long), hipMemcpyDeviceToHost,
-                             c->stream));
+    HIPCHK(c, hipMemcpyAsync(&c->h_pin->batch[slot].ovf_fill, c->d_counter + CNT_OVF, sizeof(unsigned long long),
+                             hipMemcpyDeviceToHost, c->stream));
   c->slot_bsel_rec[slot] = c->bsel_seq != seq_before ? c->bsel_last_rec : -1;  // this batch's selection record
   c->slot_bsel_seq[slot] = c->bsel_seq;
   c->scanned = true;
-  hipLaunchKernelGGL(k_best, dim3(1), dim3(kBlock), 0, c->stream, c->d_votes, c->d_valid,
-                     (uint32_t)c->H, c->d_counter + 1, 0u);
-  HIPCHK(c, hipGetLastError());
-  hipLaunchKernelGGL(k_take_best, dim3(1), dim3(64), 0, c->stream, c->d_counter + 1, c->d_hparams,
-                     c->HS, c->d_par);
-  HIPCHK(c, hipGetLastError());
+  if ((st = enqueue_take_best(c)) != LSQR_OK) return st;
+  BatchSlot *pin = &c->h_pin->batch[slot];
   bool fused = false;
-  int nm = 0;
-  if ((st = set_fit_origin(c, ORG_WINNER_DEV)) != LSQR_OK) return st;
-  if ((st = launch_mask_moments(c, 0, c->n, &nm, &fused)) != LSQR_OK) return st;
-  if (!fused && (st = launch_mask(c, 0, c->n)) != LSQR_OK) return st;
-  char *pin = slot_pin(c, slot);
-  HIPCHK(c, hipMemcpyAsync(pin, c->d_counter, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost,
-                           c->stream));  // {inliers, packed winner}
+  if ((st = enqueue_winner_finish(c, ORG_WINNER_DEV, pin->head, &fused)) != LSQR_OK) return st;
   if ((st = enqueue_fit(c, 1, fused, true)) != LSQR_OK) return st;
-  HIPCHK(c, hipMemcpyAsync(pin + 64, c->d_out, sizeof(SolveOut), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(&pin->out, c->d_out, sizeof(SolveOut), hipMemcpyDeviceToHost, c->stream));
   if (!c->slot_ev[slot]) HIPCHK(c, hipEventCreateWithFlags(&c->slot_ev[slot], hipEventDisableTiming));
   HIPCHK(c, hipEventRecord(c->slot_ev[slot], c->stream));
   c->slot_first[slot] = first;
@@ -4233,10 +4285,10 @@ int lsqr_batch_fit_wait(lsqr_ctx *c, int slot, double *params_out, lsqr_ransac_i
   if (c->slot_bsel_rec[slot] >= 0 && c->bsel_seq_of[c->slot_bsel_rec[slot]] == c->slot_bsel_seq[slot])
     bsel_fold(c, c->slot_bsel_rec[slot]);  // the host has synchronised with this batch: its selection counts count
   c->slot_bsel_rec[slot] = -1;
-  const char *pin = slot_pin(c, slot);
+  const BatchSlot *pin = &c->h_pin->batch[slot];
   if (c->slot_ovf_cap[slot]) {
     unsigned int fill = 0;
-    memcpy(&fill, pin + 32, sizeof fill);
+    memcpy(&fill, &pin->ovf_fill, sizeof fill);
     if (fill > c->slot_ovf_cap[slot] || c->opt_test_overflow) {
       // a worklist segment of the matrix-core filter overflowed (never seen outside the tests): the batch again, blocking,
       // on the exact kernels
@@ -4251,27 +4303,11 @@ int lsqr_batch_fit_wait(lsqr_ctx *c, int slot, double *params_out, lsqr_ransac_i
       return st2;
     }
   }
-  unsigned long long head[2];
-  SolveOut out;
-  memcpy(head, pin, sizeof head);
-  memcpy(&out, pin + 64, sizeof out);
-  const unsigned long long cnt = head[0], pk = head[1];
-  if (info) {
-    memset(info, 0, sizeof *info);
-    info->fraction = c->n ? (double)cnt / (double)c->n : 0.0;
-    info->iterations = c->slot_H[slot];
-    info->evaluated = c->slot_H[slot];
-    info->best_votes = (uint32_t)(pk >> 32);
-    info->best_index = pk ? c->slot_first[slot] + (0xFFFFFFFFull - (pk & 0xFFFFFFFFull)) : 0;
-    info->n_params = out.ok ? out.n_params : 0;
-    info->fit.n_params = info->n_params;
-    info->fit.n_used = cnt;
-    info->fit.cost = out.cost;
-  }
-  if (pk == 0 || !out.ok) return LSQR_EMPTY;
-  if (params_out)
-    for (int j = 0; j < out.n_params; j++) params_out[j] = out.params[j];
-  return LSQR_OK;
+  const SolveOut out = pin->out;
+  const unsigned long long cnt = pin->head[0], pk = pin->head[1];
+  // unlike lsqr_batch_fit, fit.lm_info, lm_nfev and reserved stay 0 here (kept as it is: a behaviour change of its own)
+  fill_ransac_info(info, pk, c->slot_first[slot], c->slot_H[slot], cnt, c->n, out, false);
+  return pk == 0 ? LSQR_EMPTY : deliver_params(out, params_out);
 }
 
 // ---- multi-GPU step with device-resident exchange buffers (lsqr_hip.h) ----------------------------------
@@ -4315,33 +4351,13 @@ int lsqr_step_winner(lsqr_ctx *c, uint64_t seed, uint64_t batch_first, const uin
     HIPCHK(c, hipGetLastError());
   }
   if ((st = run_estimate(c)) != LSQR_OK) return st;
-  HIPCHK(c, hipMemsetAsync(c->d_par, 0, sizeof(double) * 128, c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->d_par, c->d_hparams, sizeof(double) * c->HS, hipMemcpyDeviceToDevice,
-                           c->stream));
-  HIPCHK(c, hipMemsetAsync(c->d_vec, 0, sizeof(double) * 32, c->stream));
-  const int m = c->cfg.model;
-  if (m == LSQR_MODEL_PLANE || m == LSQR_MODEL_LINE || m == LSQR_MODEL_SPHERE)
-    HIPCHK(c, hipMemcpyAsync(c->d_vec, c->d_par + (m == LSQR_MODEL_SPHERE ? 0 : c->ND),
-                             sizeof(double) * c->ND, hipMemcpyDeviceToDevice, c->stream));
   int nmom = 0;
-  bool fused = false;
-  if ((st = launch_mask_moments(c, begin, end, &nmom, &fused)) != LSQR_OK) return st;
-  if (!fused) {
-    if ((st = launch_mask(c, begin, end)) != LSQR_OK) return st;
-    st = dispatch(c->cfg, [&](auto tag) -> int {
-      typedef typename decltype(tag)::type M;
-      return launch_moments<M>(c, 1, begin, end, 0, &nmom);
-    });
-    if (st != LSQR_OK) return st;
-  }
-  hipLaunchKernelGGL(k_pack_block, dim3(1), dim3(256), 0, c->stream, c->d_mom, nmom, c->d_counter,
+  if ((st = enqueue_winner_slice(c, begin, end, &nmom)) != LSQR_OK) return st;  // (its own origin rule)
+  hipLaunchKernelGGL(k_pack_block, dim3(1), dim3(256), 0, c->stream, c->d_mom, nmom, c->d_counter + CNT_MASK,
                      block_dev);
   HIPCHK(c, hipGetLastError());
   return LSQR_OK;
 }
-
-// results of a step are staged per slot: {packed, count, valid, winner params[64], SolveOut, phantom block}
-static char *step_pin(lsqr_ctx *c, int slot) { return (char *)c->h_pin + 53248 + slot * 2048; }
 
 int lsqr_step_finish_enqueue(lsqr_ctx *c, const uint64_t *packed_dev, const double *block_dev, int slot) {
   int st = need_ready(c, true);
@@ -4349,31 +4365,23 @@ int lsqr_step_finish_enqueue(lsqr_ctx *c, const uint64_t *packed_dev, const doub
   if (!packed_dev || !block_dev || slot < 0 || slot > 1) return fail(c, LSQR_ERR_INVALID, "bad argument");
   if (c->step_busy[slot]) return fail(c, LSQR_ERR_STATE, "step slot %d holds an unread result", slot);
   const int nmom = lsqr_moments_len(&c->cfg, 0);
-  char *pin = step_pin(c, slot);
-  HIPCHK(c, hipMemcpyAsync(pin, packed_dev, 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(pin + 8, block_dev + nmom, 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(pin + 16, c->d_valid, 1, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(pin + 64, c->d_hparams, sizeof(double) * c->P, hipMemcpyDeviceToHost, c->stream));
+  StepSlot *pin = &c->h_pin->step[slot];  // (results of a step are staged per slot)
+  HIPCHK(c, hipMemcpyAsync(&pin->packed, packed_dev, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(&pin->count, block_dev + nmom, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(&pin->valid, c->d_valid, 1, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(pin->winner, c->d_hparams, sizeof(double) * c->P, hipMemcpyDeviceToHost, c->stream));
   if (c->cfg.model == LSQR_MODEL_PHANTOM) {  // solved on the host from the Gram block (in _wait)
-    double *blk = (double *)((char *)c->h_pin + 40960);  // one block area: phantom steps are not pipelined
-    HIPCHK(c, hipMemcpyAsync(blk, block_dev, sizeof(double) * nmom, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->h_pin->phantom_block, block_dev, sizeof(double) * nmom, hipMemcpyDeviceToHost,
+                             c->stream));
   } else {
     HIPCHK(c, hipMemcpyAsync(c->d_mom, block_dev, sizeof(double) * nmom, hipMemcpyDeviceToDevice,
                              c->stream));
     st = dispatch(c->cfg, [&](auto tag) -> int {
       typedef typename decltype(tag)::type M;
-      if constexpr (M::IS_DENSE) {
-        return launch_solve_dense(c);
-      } else {
-        ProfScope ps(c, KID_SOLVE);
-        hipLaunchKernelGGL((k_solve<M>), dim3(1), dim3(64), 0, c->stream, c->d_mom, c->d_vec, c->mc,
-                           c->d_out);
-        HIPCHK(c, hipGetLastError());
-        return LSQR_OK;
-      }
+      return launch_solve<M>(c);
     });
     if (st != LSQR_OK) return st;
-    HIPCHK(c, hipMemcpyAsync(pin + 1024, c->d_out, sizeof(SolveOut), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&pin->out, c->d_out, sizeof(SolveOut), hipMemcpyDeviceToHost, c->stream));
   }
   if (!c->step_ev[slot]) HIPCHK(c, hipEventCreateWithFlags(&c->step_ev[slot], hipEventDisableTiming));
   HIPCHK(c, hipEventRecord(c->step_ev[slot], c->stream));
@@ -4393,38 +4401,20 @@ int lsqr_step_finish_wait(lsqr_ctx *c, int slot, double *winner_out, double *par
   if (c->step_bsel_rec[slot] >= 0 && c->bsel_seq_of[c->step_bsel_rec[slot]] == c->step_bsel_seq[slot])
     bsel_fold(c, c->step_bsel_rec[slot]);
   c->step_bsel_rec[slot] = -1;
-  const char *pin = step_pin(c, slot);
-  unsigned long long pk;
-  double count;
-  memcpy(&pk, pin, 8);
-  memcpy(&count, pin + 8, 8);
-  const uint8_t valid = *(const uint8_t *)(pin + 16);
+  const StepSlot *pin = &c->h_pin->step[slot];
+  const unsigned long long pk = pin->packed;
   SolveOut out;
   memset(&out, 0, sizeof out);
   if (c->cfg.model == LSQR_MODEL_PHANTOM)
-    phantom_solve_block(c->cfg, (const double *)((const char *)c->h_pin + 40960), &out);
+    phantom_solve_block(c->cfg, c->h_pin->phantom_block, &out);
   else
-    memcpy(&out, pin + 1024, sizeof out);
-  if (info) {
-    memset(info, 0, sizeof *info);
-    info->evaluated = pk != 0;  // a winner exists
-    info->best_votes = (uint32_t)(pk >> 32);
-    info->best_index = pk ? 0xFFFFFFFFull - (pk & 0xFFFFFFFFull) : 0;
-    info->n_params = out.ok ? out.n_params : 0;
-    info->fit.n_params = info->n_params;
-    info->fit.lm_info = out.lm_info;
-    info->fit.lm_nfev = out.lm_nfev;
-    info->fit.reserved = out.pad;
-    info->fit.cost = out.cost;
-    info->fit.n_used = (uint64_t)(count + 0.5);
-    info->fraction = c->n ? count / (double)c->n : 0.0;
-  }
-  if (pk == 0 || !valid) return LSQR_EMPTY;
-  if (winner_out) memcpy(winner_out, pin + 64, sizeof(double) * c->P);
-  if (!out.ok) return LSQR_EMPTY;
-  if (params_out)
-    for (int j = 0; j < out.n_params; j++) params_out[j] = out.params[j];
-  return LSQR_OK;
+    out = pin->out;
+  // (the count travels as a double behind the summed block: a whole number; evaluated = a winner exists)
+  fill_ransac_info(info, pk, 0, pk != 0, (uint64_t)(pin->count + 0.5), c->n, out);
+  if (info) info->iterations = 0;
+  if (pk == 0 || !pin->valid) return LSQR_EMPTY;
+  if (winner_out) memcpy(winner_out, pin->winner, sizeof(double) * c->P);
+  return deliver_params(out, params_out);
 }
 
 int lsqr_step_finish(lsqr_ctx *c, const uint64_t *packed_dev, const double *block_dev,
@@ -4676,12 +4666,12 @@ int multi_finish(lsqr_multi *m, uint64_t seed, uint64_t batch_first, double *par
                          kMultiBlk, m->block[0]);
       MHIP(m, hipGetLastError());
       }
-      MHIP(m, hipMemcpyAsync(c0->h_pin, m->block[0], sizeof(double) * n1, hipMemcpyDeviceToHost, c0->stream));
+      MHIP(m, hipMemcpyAsync(c0->h_pin->scratch, m->block[0], sizeof(double) * n1, hipMemcpyDeviceToHost, c0->stream));
       for (int r = 0; r < n; r++) {  // every rank's x staging must be consumed before the next trial point
         MHIP(m, hipSetDevice(m->ctx[r]->device));
         MHIP(m, hipStreamSynchronize(m->ctx[r]->stream));
       }
-      memcpy(blk, c0->h_pin, sizeof(double) * n1);
+      memcpy(blk, c0->h_pin->scratch, sizeof(double) * n1);
       int cont = 0;
       lsqr_fit_info fi;
       st = lsqr_lm_step(c0, blk, xt, &cont, fit, &fi);
@@ -5210,9 +5200,9 @@ int lsqr_scan_workload(lsqr_ctx *c, uint32_t *bound_out, uint64_t out[8]) {
   const bool bounded = c->last_bound[0] != 0 && c->last_bound[3] == c->H;
   uint32_t h_sel[2] = {0, 0};
   if (bounded) {  // the selection of the bounded scan that just ran is still on the device
-    HIPCHK(c, hipMemcpyAsync(c->h_pin, c->d_bsel, sizeof(BoundSel), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->h_pin->scratch, c->d_bsel, sizeof(BoundSel), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, sync_stream(c));
-    memcpy(h_sel, c->h_pin, sizeof h_sel);
+    memcpy(h_sel, c->h_pin->scratch, sizeof h_sel);
   }
   st = dispatch(c->cfg, [&](auto tag) -> int {
     typedef typename decltype(tag)::type M;
@@ -5225,17 +5215,17 @@ int lsqr_scan_workload(lsqr_ctx *c, uint32_t *bound_out, uint64_t out[8]) {
     }
   });
   if (st != LSQR_OK) return st;
-  HIPCHK(c, hipMemsetAsync(c->d_counter + 2, 0, sizeof(unsigned long long), c->stream));
+  HIPCHK(c, hipMemsetAsync(c->d_counter + CNT_SUM, 0, sizeof(unsigned long long), c->stream));
   if (bounded) {
     hipLaunchKernelGGL(k_sum_selected, dim3(1), dim3(256), 0, c->stream, c->d_sel, &c->d_bsel->n_pilot, d_nc,
-                       c->d_counter + 2);
+                       c->d_counter + CNT_SUM);
     hipLaunchKernelGGL(k_sum_selected, dim3(8), dim3(256), 0, c->stream, c->d_sel + kPilots, &c->d_bsel->n_rest, d_nc,
-                       c->d_counter + 2);
+                       c->d_counter + CNT_SUM);
     HIPCHK(c, hipGetLastError());
   }
-  unsigned long long *pin = (unsigned long long *)c->h_pin;
-  HIPCHK(c, hipMemcpyAsync(pin, c->d_counter + 4, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(pin + 1, c->d_counter + 2, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+  unsigned long long *pin = c->h_pin->scratch_u64;
+  HIPCHK(c, hipMemcpyAsync(pin, c->d_counter + CNT_PAIRS, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(pin + 1, c->d_counter + CNT_SUM, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
   if (bound_out)
     HIPCHK(c, hipMemcpyAsync(bound_out, c->d_ub, c->H * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, sync_stream(c));
