@@ -339,6 +339,42 @@ LSQR_API int lsqr_ransac_many_dense(lsqr_ctx *ctx, const void *host_records, siz
 LSQR_API int lsqr_dense_fit_many(lsqr_ctx *ctx, const void *host_records, size_t stride_bytes,
                                  const uint64_t *offsets, size_t n_sets, const uint8_t *masks /* nullable */,
                                  double *params_out, lsqr_fit_info *fits, int32_t *status_out);
+/* Many independent RANSAC<T,S>::compute() problems of the EXHAUSTIVE overload (RANSAC.h:111-113, RANSAC.hxx:150-249:
+ * every k-subset in lexicographic order, the first maximum wins) in one call: no p, no seeds, deterministic.
+ * Arguments, record layout, argument errors (LSQR_ERR_INVALID, nothing written; n_problems == 0 is a no-op returning
+ * LSQR_OK) and the rule "the context's own upload, hypotheses and mask are not touched; the work runs on the context's
+ * stream" are lsqr_ransac_many's.
+ *   Models: every model lsqr_ransac_many accepts, and the geometric sphere (LSQR_LS_GEOMETRIC), whose winners get the
+ *     batched Levenberg-Marquardt stage of lsqr_ransac_many_lm after the algebraic finish.  LSQR_MODEL_DENSE,
+ *     LSQR_MODEL_US_SINGLE, LSQR_MODEL_US_POINTER and LSQR_MODEL_PHANTOM return LSQR_ERR_INVALID and write nothing.
+ *   Problem j is decided as lsqr_ransac_exhaustive decides it on a context holding its records alone:
+ *     N_j < k -> status_out[j] = LSQR_EMPTY, info zeroed, parameters untouched (RANSAC.hxx:165-169; NOT the
+ *       probabilistic overload's LSQR_ERR_INVALID);
+ *     C(N_j, k) not representable in 64 bits -> status_out[j] = LSQR_ERR_INVALID, info zeroed, parameters untouched,
+ *       the other problems unaffected;
+ *     no valid hypothesis with at least one vote, or a failed fit (the geometric sphere: fit.lm_info outside 1..4)
+ *       -> LSQR_EMPTY, parameters untouched; else LSQR_OK.
+ *   Bit-identical to that call: status, iterations (= evaluated = C(N_j, k)), best_index (the winner's lexicographic
+ *     rank: lsqr_comb_unrank turns it back into the subset), best_votes, fraction, n_params, fit.n_used and the
+ *     consensus bytes (0 for every record of a problem without a winner).  Closed-form parameters agree up to the order
+ *     of the fp64 sums of the final fit; the geometric sphere's parameters and fit.cost within the LM tolerances, as for
+ *     lsqr_ransac_many_lm.  The option max_iterations does not apply, as in lsqr_ransac_exhaustive.
+ *   Independence: problem j's results, parameters included, are bit-identical whichever other problems share the
+ *     call, in whatever order, however "many_round_hypotheses" cuts the rounds, and whichever device path runs: a
+ *     problem of at most 256 records and at most 65536 subsets is searched by one workgroup in one launch shared by
+ *     all such problems; every other problem in rounds of at most "many_round_hypotheses" hypotheses (0 = default
+ *     2^21, at most 2^30; a problem with more subsets spans several rounds).  Option "many_exhaustive_fused" 0 sends
+ *     every problem through the rounds (default 1). */
+LSQR_API int lsqr_ransac_many_exhaustive(lsqr_ctx *ctx, const void *host_records, size_t stride_bytes,
+                                         const uint64_t *offsets, size_t n_problems, double *params_out,
+                                         uint8_t *consensus_out /* nullable */, lsqr_ransac_info *infos,
+                                         int32_t *status_out);
+/* Host only (no context, no device).  lsqr_comb_count: C(n, k) exactly; LSQR_ERR_INVALID when k < 1, k > 64 or the
+ * value does not fit in 64 bits (k > n: 0).  lsqr_comb_unrank: the rank-th k-subset of {0..n-1} in the order of the
+ * exhaustive overload (computeAllChoices, RANSAC.hxx:197-213: lexicographic, increasing indices), k values in
+ * subset_out; LSQR_ERR_INVALID when k < 1, k > 64, n > 2^32, C(n, k) does not fit or rank >= C(n, k). */
+LSQR_API int lsqr_comb_count(uint64_t n, int k, uint64_t *count_out);
+LSQR_API int lsqr_comb_unrank(uint64_t n, int k, uint64_t rank, uint32_t *subset_out);
 /* One fixed-size batch of the same loop without the adaptive stopping rule: hypotheses
  * [first_index, first_index + H) of the sampler stream `seed` are solved and scanned, the first
  * hypothesis with the maximal vote count wins (the strict '>' of RANSAC.hxx:100), its consensus set

@@ -111,6 +111,10 @@ SIGNATURES = {
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lsqr_dense_fit_many": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p]),
+    "lsqr_ransac_many_exhaustive": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lsqr_comb_count": (C.c_int, [C.c_uint64, C.c_int, _u64p]),
+    "lsqr_comb_unrank": (C.c_int, [C.c_uint64, C.c_int, C.c_uint64, C.c_void_p]),
     "lsqr_batch_fit": (C.c_int, [_ctx, C.c_uint64, C.c_uint64, C.c_size_t, C.c_void_p, C.c_void_p,
                                  C.POINTER(RansacInfo)]),
     "lsqr_batch_fit_enqueue": (C.c_int, [_ctx, C.c_uint64, C.c_uint64, C.c_size_t, C.c_int]),

@@ -294,8 +294,10 @@ class Context:
         cons = np.zeros(max(total, 1), dtype=np.uint8) if want_consensus else None
         infos = (L.RansacInfo * max(n, 1))()
         status = np.zeros(max(n, 1), dtype=np.int32)
-        self._chk(fn(self._h, L.ptr(recs), self.ND * 8, L.ptr(offs), n, float(p), L.ptr(seeds), L.ptr(params),
-                     L.ptr(cons), infos, L.ptr(status)))
+        # (p is None: the exhaustive search, which takes neither p nor seeds)
+        draw = () if p is None else (float(p), L.ptr(seeds))
+        self._chk(fn(self._h, L.ptr(recs), self.ND * 8, L.ptr(offs), n, *draw, L.ptr(params), L.ptr(cons), infos,
+                     L.ptr(status)))
         status, params = status[:n], params[:n]
         params[status != L.OK] = 0.0
         inf = np.ctypeslib.as_array(infos)[:n]  # structured view of the lsqr_ransac_info array
@@ -339,6 +341,16 @@ class Context:
         cost of each problem's final fit."""
         return self._ransac_many(self._lib.lsqr_ransac_many_lm, problems, p, seeds, want_consensus,
                                  extra=("lm_info", "lm_nfev", "cost"))
+
+    def ransac_many_exhaustive(self, problems, want_consensus=True):
+        """Many independent problems of the exhaustive search (lsqr_ransac_many_exhaustive: every k-subset in
+        lexicographic order, the first maximum wins; no p, no seeds) with the context's model: every model ransac_many
+        takes, and the geometric sphere.  Problem j is decided as ransac_exhaustive() on its records alone; a problem
+        of fewer than k records has status EMPTY.  -> ransac_many's dict (best_index: the winner's rank, see
+        comb_unrank); with a geometric-sphere context also lm_info, lm_nfev and cost."""
+        lm = self.cfg is not None and self.cfg.model == L.SPHERE and self.cfg.ls_type == L.LS_GEOMETRIC
+        return self._ransac_many(self._lib.lsqr_ransac_many_exhaustive, problems, None, None, want_consensus,
+                                 extra=("lm_info", "lm_nfev", "cost") if lm else ())
 
     def lm_fit_many(self, problems, x0, masks=None):
         """The geometric sphere fit (SphereParametersEstimator::geometricLeastSquaresEstimate) of many record sets
@@ -544,3 +556,23 @@ def replay(n, k, p, subsets, valid, votes, dedup=True):
         lib.lsqr_dedup_destroy(d)
     return dict(used=used, i=st[0], num_tries=st[1], best_votes=st[2], best_index=st[3],
                 has_best=bool(st[4]), done=bool(st[5]))
+
+
+def comb_count(n, k):
+    """C(n, k) as the exhaustive search counts its hypotheses (lsqr_comb_count; host only); LsqrError(ERR_INVALID)
+    when k is outside 1..64 or the value does not fit in 64 bits."""
+    out = C.c_uint64(0)
+    st = L.load().lsqr_comb_count(int(n), int(k), C.byref(out))
+    if st != L.OK:
+        raise L.LsqrError(st, "C(%d, %d) is not representable" % (n, k))
+    return out.value
+
+
+def comb_unrank(n, k, rank):
+    """The rank-th k-subset of range(n) in the exhaustive search's order (lsqr_comb_unrank; host only): the subset
+    behind a best_index of ransac_exhaustive / ransac_many_exhaustive, as a uint32 array of increasing indices."""
+    out = np.zeros(max(int(k), 1), dtype=np.uint32)
+    st = L.load().lsqr_comb_unrank(int(n), int(k), int(rank), L.ptr(out))
+    if st != L.OK:
+        raise L.LsqrError(st, "no subset of rank %d among C(%d, %d)" % (rank, n, k))
+    return out

@@ -39,6 +39,7 @@
 #include "host_entry.h"
 #include "many.h"
 #include "many_dense.h"
+#include "many_exhaustive.h"
 
 #include <condition_variable>
 #include <mutex>
@@ -305,6 +306,7 @@ struct lsqr_ctx {
   int opt_mask_band = 0;  // tests: scale factor of the dense fused mask's band (forces its serial re-evaluation path)
   long long opt_max_iter = 0;  // 0 = the reference's bound (numTries <= C(N,k))
   long long opt_many_round = 0;  // lsqr_ransac_many: hypotheses per round (0 = kManyRoundDefault)
+  bool opt_many_ex_fused = true;  // lsqr_ransac_many_exhaustive: small problems take k_many_ex_small
   ManyBufs *many = nullptr;       // lsqr_ransac_many's buffers (its own: the context's upload is not touched)
   LmState h_lm;  // host copy of the LM state (opt_lm_host)
   double *d_lmrec = nullptr;  // consensus set copied tight and in order for the iterative fits (k_compact_*)
@@ -3896,8 +3898,8 @@ int lsqr_ransac(lsqr_ctx *c, double p, uint64_t seed, const uint32_t *subsets, s
                        consensus_out, info);
 }
 
-// ---- many independent problems in one call (many.h, many_lm.h, many_dense.h) ---------------------------------------
-// What the six batched entry points share.  The checks, in the contract's order: the context is ready; the entry
+// ---- many independent problems in one call (many.h, many_lm.h, many_dense.h, many_exhaustive.h) --------------------
+// What the seven batched entry points share.  The checks, in the contract's order: the context is ready; the entry
 // point's model gate (gate(): LSQR_OK, or its own fail()); n == 0 is LSQR_OK with every output untouched; null
 // arguments (args: the entry point's own pointers are all there); p, where given (the RANSAC kind); offsets; records;
 // stride.  Then the job from the context -- the caller has set what its kind alone has: p, the seeds and the outputs
@@ -3937,6 +3939,7 @@ static int many_call(lsqr_ctx *c, const char *fn, ManyJob &J, const void *host_r
   lm_settings(c->cfg, &J.lm_n, &J.lm_ftol, &J.lm_xtol, &J.lm_gtol, &J.lm_maxfev);
   J.dense_fast = c->opt_dense_fast ? 1 : 0;
   J.dense_dd = c->opt_dense_dd ? 1 : 0;
+  J.ex_fused = c->opt_many_ex_fused ? 1 : 0;
   J.buf = c->many;
   st = dispatch(c->cfg, [&](auto tag) -> int { return run(J, tag); });
   if (st != LSQR_OK) return fail(c, st, "%s: %s", fn, J.err[0] ? J.err : "model not in this build");
@@ -4069,6 +4072,49 @@ int lsqr_dense_fit_many(lsqr_ctx *c, const void *host_records, size_t stride_byt
         if constexpr (M::IS_DENSE) return many_dense_fit<M::NR>(J, masks, fits);
         else return LSQR_ERR_INVALID;
       });
+}
+
+// many independent problems of the exhaustive overload (many_exhaustive.h); the geometric sphere's winners get the
+// LM stage, as in lsqr_ransac_many_lm
+int lsqr_ransac_many_exhaustive(lsqr_ctx *c, const void *host_records, size_t stride_bytes, const uint64_t *offsets,
+                                size_t n_problems, double *params_out, uint8_t *consensus_out,
+                                lsqr_ransac_info *infos, int32_t *status_out) {
+  ManyJob J;
+  J.params_out = params_out;
+  J.consensus_out = consensus_out;
+  J.infos = infos;
+  J.status_out = status_out;
+  return many_call(
+      c, "lsqr_ransac_many_exhaustive", J, host_records, stride_bytes, offsets, n_problems,
+      params_out && infos && status_out, nullptr,
+      [&]() -> int {
+        const lsqr_model_cfg &cfg = c->cfg;
+        if (cfg.model == LSQR_MODEL_PLANE || cfg.model == LSQR_MODEL_LINE || cfg.model == LSQR_MODEL_SPHERE ||
+            cfg.model == LSQR_MODEL_ABSOR || cfg.model == LSQR_MODEL_PIVOT || cfg.model == LSQR_MODEL_RAY ||
+            cfg.model == LSQR_MODEL_LINE2D)
+          return LSQR_OK;
+        return fail(c, LSQR_ERR_INVALID,
+                    "lsqr_ransac_many_exhaustive: plane, line, sphere, absolute orientation, pivot, ray and 2-D line "
+                    "only (model %d)", cfg.model);
+      },
+      [](ManyJob &J, auto tag) -> int {
+        typedef typename decltype(tag)::type M;
+        if constexpr (ManyModel<M>::value) return many_ex_run<M>(J);
+        else return LSQR_ERR_INVALID;
+      });
+}
+
+// C(n,k) and the rank-th k-subset in the exhaustive overload's order (comb.h); host only
+int lsqr_comb_count(uint64_t n, int k, uint64_t *count_out) {
+  if (!count_out || k < 1 || k > 64) return LSQR_ERR_INVALID;
+  return comb_count(n, k, count_out) ? LSQR_OK : LSQR_ERR_INVALID;
+}
+int lsqr_comb_unrank(uint64_t n, int k, uint64_t rank, uint32_t *subset_out) {
+  uint64_t count = 0;
+  if (!subset_out || k < 1 || k > 64 || n > 0x100000000ull) return LSQR_ERR_INVALID;
+  if (!comb_count(n, k, &count) || rank >= count) return LSQR_ERR_INVALID;
+  comb_unrank(n, k, rank, subset_out);
+  return LSQR_OK;
 }
 
 int lsqr_ransac_exhaustive(lsqr_ctx *c, double *params_out, uint8_t *consensus_out,
@@ -5008,6 +5054,10 @@ static int set_option_one(lsqr_ctx *c, const char *name, int value) {
   if (!strcmp(name, "many_round_hypotheses")) {  // lsqr_ransac_many: hypotheses per round (0 = default)
     if (value < 0) return fail(c, LSQR_ERR_INVALID, "many_round_hypotheses must be >= 0");
     c->opt_many_round = value;
+    return LSQR_OK;
+  }
+  if (!strcmp(name, "many_exhaustive_fused")) {  // 1 (default): small problems in one fused launch; 0: rounds for all
+    c->opt_many_ex_fused = value != 0;
     return LSQR_OK;
   }
   if (!strcmp(name, "syrk_diag")) {  // 1: loads only, 2: MFMAs only (timing diagnostics, wrong sums)

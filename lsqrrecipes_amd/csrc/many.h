@@ -68,8 +68,8 @@ hipError_t many_grow(T **p, size_t *cap, size_t n) {
 #endif
 }  // namespace lsqr
 
-// a HIP call of the batched host code (many.h, many_lm.h, many_dense.h; undefined at the end of the last): J is the
-// job at hand, a ManyJob or the LM stage's ManyLmJob, whose err is the ManyJob's
+// a HIP call of the batched host code (many.h, many_lm.h, many_dense.h, many_exhaustive.h; undefined at the end of the
+// last): J is the job at hand, a ManyJob or the LM stage's ManyLmJob, whose err is the ManyJob's
 #define MANYCHK(call)                                                                                \
   do {                                                                                               \
     hipError_t e_ = (call);                                                                          \
@@ -309,6 +309,14 @@ struct ManyBufs {
   double *d_mom = nullptr, *d_ddpart = nullptr;
   int *d_flags = nullptr;
   size_t c_sub = 0, c_marked = 0, c_mom = 0, c_ddpart = 0, c_flags = 0;
+  // lsqr_ransac_many_exhaustive (many_exhaustive.h): the round's items, the fused path's problems, every problem's
+  // running {votes, rank}, and two pinned staging buffers with the events that guard their reuse
+  char *d_exitems = nullptr, *d_exsmall = nullptr;
+  unsigned long long *d_exbest = nullptr;
+  size_t c_exitems = 0, c_exsmall = 0, c_exbest = 0;
+  char *h_ex[2] = {nullptr, nullptr};
+  size_t c_hex[2] = {0, 0};
+  hipEvent_t ev_ex[2] = {nullptr, nullptr};
 };
 
 #if defined(__HIPCC__)
@@ -316,11 +324,15 @@ inline void many_free(ManyBufs *b) {
   if (!b) return;
   void *dev[] = {b->d_data, b->d_hparams, b->d_best, b->d_partials, b->d_items, b->d_tiles, b->d_parts, b->d_valid,
                  b->d_mask, b->d_votes, b->d_pairs, b->d_pbeg, b->d_fin, b->d_counts, b->d_out,
-                 b->d_sub, b->d_marked, b->d_mom, b->d_ddpart, b->d_flags};
+                 b->d_sub, b->d_marked, b->d_mom, b->d_ddpart, b->d_flags, b->d_exitems, b->d_exsmall, b->d_exbest};
   for (void *p : dev)
     if (p) (void)hipFree(p);
   if (b->h_stage) (void)hipHostFree(b->h_stage);
   if (b->h_pairs) (void)hipHostFree(b->h_pairs);
+  for (int s = 0; s < 2; s++) {
+    if (b->h_ex[s]) (void)hipHostFree(b->h_ex[s]);
+    if (b->ev_ex[s]) (void)hipEventDestroy(b->ev_ex[s]);
+  }
   many_lm_free(b->lm);
   delete b;
 }
@@ -362,6 +374,7 @@ struct ManyJob {
   int lm_n = 0, lm_maxfev = 0;  // lm_settings
   double lm_ftol = 0, lm_xtol = 0, lm_gtol = 0;
   int dense_fast = 1, dense_dd = 1;  // options dense_fast_solve / dense_dd (many_dense.h)
+  int ex_fused = 1;                  // option many_exhaustive_fused (many_exhaustive.h)
   ManyBufs *buf = nullptr;
   std::vector<double> packed;  // many_upload's staging copy of strided records
   char err[256] = "";
@@ -812,40 +825,20 @@ inline SolveOut many_lm_solve_out(const ManyLmOut &r) {
   return o;
 }
 
-template <class M>
-int many_run(ManyJob &J) {
-  constexpr int K = M::K, SP = M::SP, P = M::P;
+// The finish of a RANSAC job of the closed-form models, after the rounds have left every winner's scan row in
+// B.d_best and its votes and index in pr: finish_ransac for every problem with a winner (many_plan_finish .. many_end),
+// and the LM stage for the geometric sphere.  org(j, q): the record of problem j's fit origin (read where
+// fit_origin_offset is negative: the first record of the winning minimal subset).  Shared by many_run and the
+// exhaustive search (many_exhaustive.h).
+template <class M, class Org>
+int many_finish(ManyJob &J, const std::vector<ManyProb> &pr, Org &&org) {
+  constexpr int K = M::K, P = M::P;
   const int W = many_width<M>(J.W);
   ManyBufs &B = *J.buf;
   const int org_off = fit_origin_offset<M>(J.cfg);
   static_assert(M::NMOM <= 64, "one lane per moment in k_many_solve");
   int st0;
-  if (J.round_cap == 0) J.round_cap = kManyRoundDefault;
-  std::vector<ManyProb> pr;
-  if ((st0 = many_begin(J, W, K, SP, pr)) != LSQR_OK) return st0;
-
-  if ((st0 = many_rounds(J, pr, K, SP, kManySeg, [&](size_t n_items, uint64_t Ht, size_t n_tiles) -> int {
-         hipLaunchKernelGGL((k_many_sample_estimate<M>), dim3((unsigned)((Ht + kBlock - 1) / kBlock)), dim3(kBlock),
-                            0, J.stream, B.d_data, W, B.d_items, (int)n_items, (uint32_t)Ht, J.mc, B.d_hparams,
-                            B.d_valid);
-         MANYCHK(hipGetLastError());
-         hipLaunchKernelGGL((k_many_scan<M>), dim3((unsigned)n_tiles), dim3(kManyBlock), 0, J.stream, B.d_data, W,
-                            B.d_tiles, B.d_hparams, B.d_valid, J.mc, B.d_votes);
-         MANYCHK(hipGetLastError());
-         return LSQR_OK;
-       })) != LSQR_OK)
-    return st0;
-
-  // ---- finish: finish_ransac for every problem with a winner -----------------------------------------------------
-  ManyFinish F = many_plan_finish(J, pr, K, [&](size_t j, const ManyProb &q) {
-    uint64_t org = J.offsets[j];  // (unused with org_off >= 0)
-    if (org_off < 0) {  // the winner's first drawn record, as lsqr_ransac reads it from d_subsets
-      uint32_t idx[K], sorted[K];
-      ctr_subset(J.seeds[j], q.rs[RS_BEST_IDX], J.offsets[j + 1] - J.offsets[j], K, idx, sorted);
-      org += idx[0];
-    }
-    return org;
-  });
+  ManyFinish F = many_plan_finish(J, pr, K, org);
   const size_t NF = F.size();
   if (NF) {
     if ((st0 = many_stage_finish(J, F, true)) != LSQR_OK) return st0;
@@ -880,6 +873,40 @@ int many_run(ManyJob &J) {
   }
   many_end(J, F, P);
   return LSQR_OK;
+}
+
+template <class M>
+int many_run(ManyJob &J) {
+  constexpr int K = M::K, SP = M::SP;
+  const int W = many_width<M>(J.W);
+  ManyBufs &B = *J.buf;
+  const int org_off = fit_origin_offset<M>(J.cfg);
+  int st0;
+  if (J.round_cap == 0) J.round_cap = kManyRoundDefault;
+  std::vector<ManyProb> pr;
+  if ((st0 = many_begin(J, W, K, SP, pr)) != LSQR_OK) return st0;
+
+  if ((st0 = many_rounds(J, pr, K, SP, kManySeg, [&](size_t n_items, uint64_t Ht, size_t n_tiles) -> int {
+         hipLaunchKernelGGL((k_many_sample_estimate<M>), dim3((unsigned)((Ht + kBlock - 1) / kBlock)), dim3(kBlock),
+                            0, J.stream, B.d_data, W, B.d_items, (int)n_items, (uint32_t)Ht, J.mc, B.d_hparams,
+                            B.d_valid);
+         MANYCHK(hipGetLastError());
+         hipLaunchKernelGGL((k_many_scan<M>), dim3((unsigned)n_tiles), dim3(kManyBlock), 0, J.stream, B.d_data, W,
+                            B.d_tiles, B.d_hparams, B.d_valid, J.mc, B.d_votes);
+         MANYCHK(hipGetLastError());
+         return LSQR_OK;
+       })) != LSQR_OK)
+    return st0;
+
+  return many_finish<M>(J, pr, [&](size_t j, const ManyProb &q) {
+    uint64_t org = J.offsets[j];  // (unused with org_off >= 0)
+    if (org_off < 0) {  // the winner's first drawn record, as lsqr_ransac reads it from d_subsets
+      uint32_t idx[K], sorted[K];
+      ctr_subset(J.seeds[j], q.rs[RS_BEST_IDX], J.offsets[j + 1] - J.offsets[j], K, idx, sorted);
+      org += idx[0];
+    }
+    return org;
+  });
 }
 
 // lsqr_lm_fit_many: set j = records [offsets[j], offsets[j+1]) where masks (nullable: every record) is set, fitted

@@ -458,5 +458,3 @@ int many_dense_fit(ManyJob &J, const uint8_t *masks, lsqr_fit_info *fits) {
 #endif
 
 }  // namespace lsqr
-
-#undef MANYCHK

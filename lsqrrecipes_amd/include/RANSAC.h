@@ -184,6 +184,60 @@ class RANSAC {
     return fraction;
   }
 
+  // Many independent exhaustive searches (not in the reference): the overload next to the probabilistic computeMany,
+  // as the two compute() overloads stand side by side.  computeMany(...)[j] equals the exhaustive compute() on data[j]:
+  // parameters[j] is cleared first, a problem of fewer records than a minimal subset returns 0.  Plane, line, sphere
+  // (algebraic and geometric), absolute orientation, pivot calibration, ray intersection and the 2-D line run in ONE
+  // device call (lsqr_ransac_many_exhaustive); the dense linear system, the other device estimators, estimators
+  // without a device model and forceHostLoop() loop over compute().  lastInfo() is not updated by the batched call.
+  static std::vector<double> computeMany(std::vector<std::vector<S> > &parameters,
+                                         ParametersEstimator<T, S> *paramEstimator,
+                                         const std::vector<std::vector<T> > &data,
+                                         std::vector<std::vector<bool> > *consensusSets = NULL) {
+    if (!paramEstimator) throw std::invalid_argument("lsqrRecipes::RANSAC: null estimator");
+    const size_t n = data.size();
+    parameters.resize(n);
+    if (consensusSets) consensusSets->resize(n);
+    std::vector<double> fraction(n, 0.0);
+    if (n == 0) return fraction;
+    lsqr_model_cfg cfg;
+    const bool device = paramEstimator->deviceModel(cfg) && !forceHostLoop();
+    const bool batched = device && (cfg.model == LSQR_MODEL_PLANE || cfg.model == LSQR_MODEL_LINE ||
+                                    cfg.model == LSQR_MODEL_SPHERE || cfg.model == LSQR_MODEL_ABSOR ||
+                                    cfg.model == LSQR_MODEL_PIVOT || cfg.model == LSQR_MODEL_RAY ||
+                                    cfg.model == LSQR_MODEL_LINE2D);
+    if (!batched) {
+      for (size_t j = 0; j < n; j++)
+        fraction[j] = compute(parameters[j], paramEstimator, const_cast<std::vector<T> &>(data[j]),
+                              consensusSets ? &(*consensusSets)[j] : NULL);
+      return fraction;
+    }
+    std::vector<uint64_t> offsets(n + 1, 0);
+    for (size_t j = 0; j < n; j++) offsets[j + 1] = offsets[j] + data[j].size();
+    std::vector<T> records;
+    records.reserve((size_t)offsets[n]);
+    for (size_t j = 0; j < n; j++) records.insert(records.end(), data[j].begin(), data[j].end());
+    detail::Device &d = detail::Device::instance();
+    lsqr_ctx *ctx = d.ctx();
+    if (lsqr_multi *m = d.multi()) ctx = lsqr_multi_ctx(m, 0);
+    d.check(lsqr_set_model(ctx, &cfg));
+    const int P = lsqr_num_params(&cfg);
+    std::vector<double> par(n * (size_t)P);
+    std::vector<uint8_t> cons(consensusSets ? (size_t)offsets[n] : 0);
+    std::vector<lsqr_ransac_info> info(n);
+    std::vector<int32_t> status(n);
+    d.check(lsqr_ransac_many_exhaustive(ctx, records.empty() ? NULL : &records[0], sizeof(T), &offsets[0], n, &par[0],
+                                        cons.empty() ? NULL : &cons[0], &info[0], &status[0]));
+    for (size_t j = 0; j < n; j++) {
+      parameters[j].clear();  // RANSAC.hxx:165 clears before the size check
+      if (info[j].best_votes > 0 && consensusSets)
+        (*consensusSets)[j].assign(cons.begin() + (size_t)offsets[j], cons.begin() + (size_t)offsets[j + 1]);
+      if (status[j] == LSQR_OK) parameters[j].assign(&par[j * P], &par[j * P] + info[j].n_params);
+      fraction[j] = info[j].fraction;
+    }
+    return fraction;
+  }
+
   // sampler stream of the probabilistic overload (default 1); set it to vary the hypotheses
   static uint64_t &seed() {
     static thread_local uint64_t s = 1;

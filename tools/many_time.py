@@ -20,6 +20,13 @@ context (--shapes dense: all three; delta 0.1, 1e-3 relative noise on b, outlier
   dense6   n =  6  10 000 problems x    500 rows, 20 % outliers
   dense16  n = 16   1 000 problems x  5 000 rows, 10 % outliers
   dense64  n = 64     100 problems x 20 000 rows,  3 % outliers
+and the exhaustive search, Context.ransac_many_exhaustive against the Context.ransac_exhaustive loop, with the fused
+path on (many_ms, the default) and off (general_ms: every problem through the rounds):
+  python tools/many_time.py --shapes exhaustive
+  ex_rays     100 000 problems x  12 rays,        C(12,2) =     66 subsets each
+  ex_absor     10 000 problems x  20 point pairs, C(20,3) =  1 140
+  ex_plane     10 000 problems x  40 points,      C(40,3) =  9 880
+  ex_plane300     100 problems x 300 points,      C(300,3) = 4 455 100 (N > 256: the general path in both settings)
 Each row also gives the loop's time per problem (loop_ms_per_problem).  Every timed call
 ends in a device synchronisation (both entry points return host results); each shape is warmed first; the two
 paths alternate in one process.  --quick: one repetition, small loop (for a kernel-trace run under rocprofv3).
@@ -128,6 +135,11 @@ RIGID_SHAPES = {"rays": (L.RAY, 100_000, 12, 0.7, 1.0, np.pi / 180), "absor": (L
 GEOMETRIC_SHAPES = {"sphere_lm": (1_000, 10_000), "sphere_lm_small": (10_000, 300)}
 # name -> (n, problems, rows, inlier share)
 DENSE_SHAPES = {"dense6": (6, 10_000, 500, 0.8), "dense16": (16, 1_000, 5_000, 0.9), "dense64": (64, 100, 20_000, 0.97)}
+# name -> (generator's name, model, problems, records, inlier share, delta, aux)
+EXHAUSTIVE_SHAPES = {"ex_rays": ("rays", L.RAY, 100_000, 12, 0.7, 1.0, np.pi / 180),
+                     "ex_absor": ("absor", L.ABSOR, 10_000, 20, 0.7, 1.0, 0.0),
+                     "ex_plane": ("plane", L.PLANE, 10_000, 40, 0.5, 0.5, 0.0),
+                     "ex_plane300": ("plane", L.PLANE, 100, 300, 0.5, 0.5, 0.0)}
 
 
 def timed(f, reps):
@@ -140,6 +152,42 @@ def timed(f, reps):
     return float(np.median(t)), r
 
 
+def exhaustive(ctx, name, reps, loop_n):
+    """one exhaustive shape: the batched call with the fused path on and off against the ransac_exhaustive loop"""
+    kind, model, P, N, inl, delta, aux = EXHAUSTIVE_SHAPES[name]
+    recs, offs = gen(model, P, N, inl, seed=model + N) if kind == "plane" else gen_rigid(kind, P, N, inl, seed=model)
+    ctx.set_model(model, 3, delta, 0, aux=aux)
+    m = min(loop_n, P, max(3, 200_000 // N ** 2))   # (a 300-point problem is 4.5 M hypotheses on its own)
+
+    def many(fused):
+        ctx.set_option("many_exhaustive_fused", fused)
+        try:
+            return ctx.ransac_many_exhaustive((recs, offs))
+        finally:
+            ctx.set_option("many_exhaustive_fused", 1)
+
+    def loop():
+        it = 0
+        for j in range(m):
+            ctx.upload(recs[int(offs[j]):int(offs[j + 1])])
+            it += ctx.ransac_exhaustive()["info"].iterations
+        return it
+    res = many(1)   # warm
+    many(0)
+    loop()
+    t_fused, t_general, t_loop = [], [], []
+    for _ in range(reps):  # alternate the paths
+        t_fused.append(timed(lambda: many(1), 1)[0])
+        t_general.append(timed(lambda: many(0), 1)[0])
+        t_loop.append(timed(loop, 1)[0])
+    tm, tg, tl = float(np.median(t_fused)), float(np.median(t_general)), float(np.median(t_loop)) * P / m
+    ev = res["evaluated"].astype(np.float64)
+    return dict(shape=name, problems=P, records=N, many_ms=1e3 * tm, general_ms=1e3 * tg, loop_ms=1e3 * tl,
+                loop_ms_per_problem=1e3 * tl / P, loop_extrapolated_from=m if m < P else None, speedup=tl / tm,
+                speedup_general=tl / tg, fused_over_general=tg / tm, ok=int(np.sum(res["status"] == L.OK)),
+                hypotheses_scanned=float(ev.sum()), agree_evaluations=float((ev * N).sum()))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true")
@@ -147,15 +195,16 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--out", default=None, help="also write the results as one JSON file")
     ap.add_argument("--shapes", default="plane,sphere,line",
-                    help="comma-separated shapes (%s), or 'rigid' / 'geometric' / 'dense' for the closed-form "
-                         "estimators' / the LM sphere's / the dense system's"
-                         % ", ".join(list(POINT_SHAPES) + list(RIGID_SHAPES) + list(GEOMETRIC_SHAPES) + list(DENSE_SHAPES)))
+                    help="comma-separated shapes (%s), or 'rigid' / 'geometric' / 'dense' / 'exhaustive' for the "
+                         "closed-form estimators' / the LM sphere's / the dense system's / the exhaustive search's"
+                         % ", ".join(list(POINT_SHAPES) + list(RIGID_SHAPES) + list(GEOMETRIC_SHAPES) + list(DENSE_SHAPES)
+                                     + list(EXHAUSTIVE_SHAPES)))
     a = ap.parse_args()
     names = {"rigid": list(RIGID_SHAPES), "geometric": list(GEOMETRIC_SHAPES),
-             "dense": list(DENSE_SHAPES)}.get(a.shapes, a.shapes.split(","))
+             "dense": list(DENSE_SHAPES), "exhaustive": list(EXHAUSTIVE_SHAPES)}.get(a.shapes, a.shapes.split(","))
     for name in names:
         if (name not in POINT_SHAPES and name not in RIGID_SHAPES and name not in GEOMETRIC_SHAPES
-                and name not in DENSE_SHAPES):
+                and name not in DENSE_SHAPES and name not in EXHAUSTIVE_SHAPES):
             ap.error("unknown shape %r" % name)
     reps = 1 if a.quick else a.reps
     loop_n = 100 if a.quick else a.loop
@@ -163,6 +212,11 @@ def main():
     out = dict(shapes=[], latency=[])
     for name in names:
         batched = ctx.ransac_many
+        if name in EXHAUSTIVE_SHAPES:
+            row = exhaustive(ctx, name, reps, loop_n)
+            out["shapes"].append(row)
+            print(json.dumps(row), flush=True)
+            continue
         if name in POINT_SHAPES:
             model, P, N = POINT_SHAPES[name]
             recs, offs = gen(model, P, N, 0.5, seed=model)
