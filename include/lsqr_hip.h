@@ -247,6 +247,36 @@ LSQR_API int lsqr_residuals(lsqr_ctx *ctx, const double *params, size_t begin, s
 LSQR_API int lsqr_ransac(lsqr_ctx *ctx, double p, uint64_t seed, const uint32_t *subsets,
                          size_t n_subsets, double *params_out, uint8_t *consensus_out,
                          lsqr_ransac_info *info);
+/* Sequential RANSAC: up to max_models models from the context's current upload / attach of N records, the records
+ * staying on the device between the rounds.  Round r is decided exactly as lsqr_ransac(ctx2, p, seeds[r], NULL, 0, ...)
+ * would decide it on a fresh context ctx2 with the same model and options that holds only the records no earlier round
+ * claimed, in their original order, tightly packed: every model lsqr_ransac accepts (the Levenberg-Marquardt fits
+ * included), the option "max_iterations" and the 2^22 no-model stop apply per round.  There is no caller-supplied
+ * subset stream.
+ *   Accepting: round r is accepted when it returns LSQR_OK with best_votes >= max(min_votes, 1); it then claims its
+ *     consensus set.  The first round that is not accepted is the last one; it claims nothing and *n_models_out = r.
+ *     infos[r], status_out[r] and row r of params_out (lsqr_num_params doubles) are written as lsqr_ransac returns /
+ *     writes them for every round that ran, the rejected one included (the caller sees the rejected candidate).
+ *   Rounds that did not run: before the first round every status_out entry is set to LSQR_ERR_STATE ("round not run")
+ *     and every infos entry is zeroed.  A round does not run when r == max_models or when fewer than lsqr_min_subset
+ *     records remain.
+ *   labels_out (nullable, N entries in upload order): r where round r claimed the record, else -1; copied to the host
+ *     once, at the end.  infos[r].fraction is votes / records that remained in round r, as the fresh-context call
+ *     reports it; infos[r].best_index and the fit origin of the first-record models refer to the compacted records.
+ *   Argument errors (LSQR_ERR_INVALID, nothing written): p outside (0, 1); with max_models > 0 a null seeds,
+ *     params_out, infos, status_out or n_models_out.  max_models == 0 returns LSQR_OK and sets *n_models_out = 0.  No
+ *     model or no records: LSQR_ERR_STATE.  A round that fails outright (LSQR_ERR_HIP) ends the call with that status.
+ *   Afterwards the context holds the caller's original records again -- same pointer, count and stride, exactly as
+ *     after lsqr_upload / lsqr_attach: hypotheses and mask are void, the spatial index is dropped.  The caller's
+ *     records are only read: attached (caller-owned) device memory is never written; the survivors of a round are
+ *     compacted (stable, with their upload indices) into buffers the context owns (csrc/sequential.h), and the context
+ *     is re-pointed at them by the path lsqr_attach takes.  The work runs on the context's stream (lsqr_set_stream).
+ *   lsqr_multi handles have no sequential form: call it on one device's context. */
+LSQR_API int lsqr_ransac_sequential(lsqr_ctx *ctx, double p, const uint64_t *seeds /* max_models */, size_t max_models,
+                                    uint64_t min_votes, double *params_out /* max_models * lsqr_num_params */,
+                                    int32_t *labels_out /* nullable: N entries, upload order */,
+                                    lsqr_ransac_info *infos /* max_models */, int32_t *status_out /* max_models */,
+                                    size_t *n_models_out);
 /* Many independent RANSAC<T,S>::compute() problems (probabilistic overload, RANSAC.h:75-79) in one call.
  * Problem j is records [offsets[j], offsets[j+1]) of host_records (stride_bytes apart, laid out as for
  * lsqr_upload), walks sampler stream seeds[j] and is decided exactly as lsqr_ransac(ctx, p, seeds[j], NULL, 0, ...)

@@ -256,6 +256,40 @@ class Context:
                     consensus=cons[:self.n] if (cons is not None and info.best_votes > 0) else None,
                     info=info)
 
+    def ransac_sequential(self, p, max_models, seeds=None, min_votes=0, want_labels=True):
+        """Sequential RANSAC on the current upload / attach (lsqr_ransac_sequential): find a model, take its consensus
+        set out, search what is left, up to max_models times, the records staying on the device.  Round r is decided
+        as ransac(p, seed=seeds[r]) on a context holding only the records no earlier round claimed (default seeds
+        1 + r); a round is accepted when it is OK with best_votes >= max(min_votes, 1), the first one that is not
+        ends the call.  -> dict: n_models; params (max_models x P, zero rows where status is not OK); labels (one
+        int32 per record in upload order: the round that claimed it, else -1; None unless want_labels); status
+        (ERR_STATE for a round that did not run) and, per round, fraction, iterations, best_index, best_votes,
+        evaluated, n_params, n_used, lm_info, lm_nfev, cost -- the rejected round's included.  The context holds the
+        original records afterwards, as after upload / attach."""
+        m = int(max_models)
+        if m < 0:
+            raise ValueError("max_models must not be negative")
+        seeds = (1 + np.arange(m, dtype=np.uint64)) if seeds is None else np.ascontiguousarray(seeds, dtype=np.uint64)
+        if seeds.shape != (m,):
+            raise ValueError("one seed per model")
+        params = np.zeros((max(m, 1), self.P))
+        labels = np.full(max(self.n, 1), -1, dtype=np.int32) if want_labels else None
+        infos = (L.RansacInfo * max(m, 1))()
+        status = np.full(max(m, 1), L.ERR_STATE, dtype=np.int32)
+        n_models = C.c_size_t(0)
+        self._chk(self._lib.lsqr_ransac_sequential(self._h, float(p), L.ptr(seeds), m, int(min_votes), L.ptr(params),
+                                                   L.ptr(labels), infos, L.ptr(status), C.byref(n_models)))
+        status, params = status[:m], params[:m]
+        params[status != L.OK] = 0.0
+        inf = np.ctypeslib.as_array(infos)[:m]
+        f = lambda name: inf[name].copy()
+        fit = inf["fit"]
+        return dict(n_models=int(n_models.value), params=params, labels=labels[:self.n] if labels is not None else None,
+                    status=status, fraction=f("fraction"), iterations=f("iterations"), best_index=f("best_index"),
+                    best_votes=f("best_votes"), evaluated=f("evaluated"), n_params=f("n_params"),
+                    n_used=fit["n_used"].copy(), lm_info=fit["lm_info"].copy(), lm_nfev=fit["lm_nfev"].copy(),
+                    cost=fit["cost"].copy())
+
     def ransac_many(self, problems, p, seeds=None, want_consensus=True):
         """Many independent RANSAC problems in one call (lsqr_ransac_many) with the context's model: plane, line,
         algebraic sphere, absolute orientation (ls_type 0, or 2 with 7-double weighted records), pivot, ray and 2-D

@@ -40,6 +40,7 @@
 #include "many.h"
 #include "many_dense.h"
 #include "many_exhaustive.h"
+#include "sequential.h"
 
 #include <condition_variable>
 #include <mutex>
@@ -308,6 +309,14 @@ struct lsqr_ctx {
   long long opt_many_round = 0;  // lsqr_ransac_many: hypotheses per round (0 = kManyRoundDefault)
   bool opt_many_ex_fused = true;  // lsqr_ransac_many_exhaustive: small problems take k_many_ex_small
   ManyBufs *many = nullptr;       // lsqr_ransac_many's buffers (its own: the context's upload is not touched)
+  // lsqr_ransac_sequential (sequential.h): the survivors of a round go from the current buffer into the OTHER of two
+  // owned buffers (never into the caller's upload), their upload indices beside them; labels in upload order
+  double *d_seq_rec[2] = {nullptr, nullptr};
+  uint32_t *d_seq_orig[2] = {nullptr, nullptr};
+  size_t seq_rec_cap[2] = {0, 0}, seq_orig_cap[2] = {0, 0};
+  int32_t *d_seq_labels = nullptr;
+  uint32_t *d_seq_counts = nullptr;
+  size_t seq_labels_cap = 0, seq_counts_cap = 0;
   LmState h_lm;  // host copy of the LM state (opt_lm_host)
   double *d_lmrec = nullptr;  // consensus set copied tight and in order for the iterative fits (k_compact_*)
   size_t lmrec_cap = 0;
@@ -3057,7 +3066,8 @@ void lsqr_ctx_destroy(lsqr_ctx *c) {
   (void)hipStreamSynchronize(c->stream);
   free_index(c);
   many_free(c->many);
-  void *bufs[] = {c->d_refused, c->d_us16, c->d_us16_x, c->d_h16, c->d_h16_bs, c->d_h16_thr, c->d_ddpart, c->d_ub2, c->d_axis, c->d_cellT, c->d_vpart, c->d_paircnt, c->d_paircost, c->d_sel, c->d_bsel, c->d_hparams2, c->d_hparams2_f32, c->d_votes2, c->d_lmrec, c->d_idx_scratch, c->d_ub, c->d_queues, c->d_data_owned, c->d_subsets, c->d_hparams, c->d_hparams_f32, c->d_amb, c->d_valid, c->d_votes, c->d_mask, c->d_rows,
+  void *bufs[] = {c->d_seq_rec[0], c->d_seq_rec[1], c->d_seq_orig[0], c->d_seq_orig[1], c->d_seq_labels, c->d_seq_counts,
+                  c->d_refused, c->d_us16, c->d_us16_x, c->d_h16, c->d_h16_bs, c->d_h16_thr, c->d_ddpart, c->d_ub2, c->d_axis, c->d_cellT, c->d_vpart, c->d_paircnt, c->d_paircost, c->d_sel, c->d_bsel, c->d_hparams2, c->d_hparams2_f32, c->d_votes2, c->d_lmrec, c->d_idx_scratch, c->d_ub, c->d_queues, c->d_data_owned, c->d_subsets, c->d_hparams, c->d_hparams_f32, c->d_amb, c->d_valid, c->d_votes, c->d_mask, c->d_rows,
                   c->d_partials, c->d_mom, c->d_vec, c->d_par, c->d_best, c->d_lm, c->d_out, c->d_counter};
   for (void *b : bufs)
     if (b) (void)hipFree(b);
@@ -3896,6 +3906,97 @@ int lsqr_ransac(lsqr_ctx *c, double p, uint64_t seed, const uint32_t *subsets, s
   info->best_index = rs[RS_BEST_IDX];
   return finish_ransac(c, rs[RS_HAS] != 0, (uint32_t)rs[RS_BEST], params_out,
                        consensus_out, info);
+}
+
+// ---- sequential RANSAC: several models from one upload (sequential.h) ----------------------------------------------
+// Round r is lsqr_ransac itself on the records no earlier round claimed.  Between rounds the survivors are compacted on
+// the device and the context is re-pointed at them through set_data_common -- the path of lsqr_upload / lsqr_attach --
+// so that everything derived from the records (index, bounds, absmax, fp16 fragments, lanes, selection feedback, the
+// win / origin state) starts over as after a real upload.  The caller's records are only read; they are put back, the
+// same way, whatever the outcome.
+int lsqr_ransac_sequential(lsqr_ctx *c, double p, const uint64_t *seeds, size_t max_models, uint64_t min_votes,
+                           double *params_out, int32_t *labels_out, lsqr_ransac_info *infos, int32_t *status_out,
+                           size_t *n_models_out) {
+  int st = need_ready(c, false);
+  if (st != LSQR_OK) return st;
+  if (!(p > 0.0) || !(p < 1.0)) return fail(c, LSQR_ERR_INVALID, "lsqr_ransac_sequential: p must lie in (0, 1)");
+  if (max_models > 0 && (!seeds || !params_out || !infos || !status_out || !n_models_out))
+    return fail(c, LSQR_ERR_INVALID, "lsqr_ransac_sequential: null argument");
+  if (max_models == 0) {
+    if (n_models_out) *n_models_out = 0;
+    return LSQR_OK;
+  }
+  if (max_models > 0x7FFFFFFFull) return fail(c, LSQR_ERR_INVALID, "lsqr_ransac_sequential: too many models");
+  if ((st = need_ready(c, true)) != LSQR_OK) return st;
+  if (c->ND < 2 || c->ND > kSeqMaxD) return fail(c, LSQR_ERR_INVALID, "lsqr_ransac_sequential: records of %d doubles", c->ND);
+  for (size_t r = 0; r < max_models; r++) status_out[r] = LSQR_ERR_STATE;  // round not run
+  memset(infos, 0, sizeof(lsqr_ransac_info) * max_models);
+  *n_models_out = 0;
+
+  const double *const data0 = c->d_data;
+  const size_t n0 = c->n, stride0 = c->stride;
+  const int W = c->ND;
+  if (labels_out) {
+    if ((st = ensure(c, &c->d_seq_labels, &c->seq_labels_cap, n0)) != LSQR_OK) return st;
+    HIPCHK(c, hipMemsetAsync(c->d_seq_labels, 0xFF, sizeof(int32_t) * n0, c->stream));  // -1
+  }
+  int32_t *const d_labels = labels_out ? c->d_seq_labels : nullptr;
+  const uint32_t *orig = nullptr;  // upload indices of the current records (null: they are the upload)
+  int cur = -1;                    // the owned buffer the context reads (-1: the caller's records)
+  size_t r = 0;
+  int result = LSQR_OK;
+  while (r < max_models && c->n >= (size_t)c->K) {
+    st = lsqr_ransac(c, p, seeds[r], nullptr, 0, params_out + r * (size_t)c->P, nullptr, &infos[r]);
+    status_out[r] = st;
+    if (st != LSQR_OK && st != LSQR_EMPTY) {  // a failure, not an outcome: c->err is lsqr_ransac's
+      result = st;
+      break;
+    }
+    if (st != LSQR_OK || (uint64_t)infos[r].best_votes < std::max<uint64_t>(min_votes, 1)) break;  // rejected: claims nothing
+    const size_t n_cur = c->n, survivors = n_cur - infos[r].best_votes;
+    const int32_t round = (int32_t)r++;
+    hipError_t e = hipSuccess;
+    if (r == max_models || survivors < (size_t)c->K) {  // no round follows: the labels alone
+      if (d_labels) e = seq_label(c->stream, c->d_mask, (uint32_t)n_cur, orig, round, d_labels, (uint32_t)n0);
+      if (e != hipSuccess) result = fail(c, LSQR_ERR_HIP, "lsqr_ransac_sequential: %s", hipGetErrorString(e));
+      break;
+    }
+    const int dst = cur == 0 ? 1 : 0;
+    if ((st = ensure(c, &c->d_seq_rec[dst], &c->seq_rec_cap[dst], survivors * (size_t)W)) != LSQR_OK ||
+        (st = ensure(c, &c->d_seq_orig[dst], &c->seq_orig_cap[dst], survivors)) != LSQR_OK ||
+        (st = ensure(c, &c->d_seq_counts, &c->seq_counts_cap, (size_t)seq_chunks(n_cur))) != LSQR_OK) {
+      result = st;
+      break;
+    }
+    e = seq_partition(c->stream, c->d_data, c->stride, (uint32_t)n_cur, W, c->d_mask, orig, c->d_seq_counts,
+                      (uint32_t)survivors, round, c->d_seq_rec[dst], c->d_seq_orig[dst], d_labels, (uint32_t)n0);
+    if (e != hipSuccess) {
+      result = fail(c, LSQR_ERR_HIP, "lsqr_ransac_sequential: %s", hipGetErrorString(e));
+      break;
+    }
+    if ((st = set_data_common(c, survivors, sizeof(double) * (size_t)W)) != LSQR_OK) {
+      result = st;
+      break;
+    }
+    c->d_data = c->d_seq_rec[dst];
+    orig = c->d_seq_orig[dst];
+    cur = dst;
+  }
+  *n_models_out = r;
+  if (result == LSQR_OK && labels_out) {
+    hipError_t e = hipMemcpyAsync(labels_out, d_labels, sizeof(int32_t) * n0, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = sync_stream(c);
+    if (e != hipSuccess) result = fail(c, LSQR_ERR_HIP, "lsqr_ransac_sequential: %s", hipGetErrorString(e));
+  } else if (result != LSQR_OK) {
+    (void)sync_stream(c);  // nothing of this call is left in flight on the scratch buffers
+  }
+  // the caller's records again, as after lsqr_upload / lsqr_attach (hypotheses, mask and index are void)
+  char keep[sizeof c->err];
+  memcpy(keep, c->err, sizeof keep);
+  st = set_data_common(c, n0, sizeof(double) * stride0);
+  c->d_data = data0;
+  if (result != LSQR_OK) memcpy(c->err, keep, sizeof keep);
+  return result != LSQR_OK ? result : st;
 }
 
 // ---- many independent problems in one call (many.h, many_lm.h, many_dense.h, many_exhaustive.h) --------------------

@@ -238,6 +238,58 @@ class RANSAC {
     return fraction;
   }
 
+  // Sequential RANSAC (not in the reference): find the best model, take its consensus set out of the data, search
+  // what is left, up to maxModels times.  Round r walks sampler stream seed() + r and is decided as compute() would
+  // decide it on the records no earlier round claimed, in their original order; it is accepted when it yields
+  // parameters and its consensus set has at least max(minVotes, 1) records.  The first round that is not accepted is
+  // the last one and claims nothing; no round runs on fewer records than a minimal subset.
+  //   parameters: one vector per ACCEPTED round.  Return value: the fraction of every round that RAN, each relative to
+  //   the records that were left for it -- one entry more than `parameters` when the last round was rejected.
+  //   labels (optional): per record of `data` the round that claimed it, else -1.  lastInfo(): the last round that ran.
+  //   Invalid input (as compute(): too few records, p outside (0, 1)) or maxModels == 0: nothing runs, both are empty.
+  // Estimators with a device model run in ONE device call (lsqr_ransac_sequential: one upload, the survivors of every
+  // round compacted on the device); estimators without one, and forceHostLoop(), run the same loop on the host over
+  // the plugin path with the consensus set erased, on the same seeds.  Under LSQR_DEVICES the call runs on the first
+  // listed device's context.
+  static std::vector<double> computeSequential(std::vector<std::vector<S> > &parameters,
+                                               ParametersEstimator<T, S> *paramEstimator, std::vector<T> &data,
+                                               double desiredProbabilityForNoOutliers, size_t maxModels,
+                                               size_t minVotes, std::vector<int> *labels = NULL) {
+    lsqr_model_cfg cfg;
+    if (!paramEstimator) throw std::invalid_argument("lsqrRecipes::RANSAC: null estimator");
+    const double p = desiredProbabilityForNoOutliers;
+    parameters.clear();
+    if (labels) labels->assign(data.size(), -1);
+    if (maxModels == 0 || data.size() < paramEstimator->numForEstimate() || p >= 1.0 || p <= 0.0)
+      return std::vector<double>();
+    if (!paramEstimator->deviceModel(cfg) || forceHostLoop())
+      return pluginComputeSequential(parameters, paramEstimator, data, p, maxModels, minVotes, labels);
+    detail::Device &d = detail::Device::instance();
+    lsqr_ctx *ctx = d.ctx();
+    if (lsqr_multi *m = d.multi()) ctx = lsqr_multi_ctx(m, 0);
+    d.check(lsqr_set_model(ctx, &cfg));
+    d.check(lsqr_upload(ctx, &data[0], data.size(), sizeof(T)));
+    return sequentialOn(d, ctx, cfg, data.size(), parameters, p, maxModels, minVotes, labels);
+  }
+
+  // the same on resident records (lsqrRecipes::ResidentData): no upload; the records are only read
+  static std::vector<double> computeSequential(std::vector<std::vector<S> > &parameters,
+                                               ParametersEstimator<T, S> *paramEstimator, ResidentData<T> &data,
+                                               double desiredProbabilityForNoOutliers, size_t maxModels,
+                                               size_t minVotes, std::vector<int> *labels = NULL) {
+    lsqr_model_cfg cfg;
+    if (!paramEstimator) throw std::invalid_argument("lsqrRecipes::RANSAC: null estimator");
+    const double p = desiredProbabilityForNoOutliers;
+    parameters.clear();
+    if (labels) labels->assign(data.size(), -1);
+    if (maxModels == 0 || data.size() < paramEstimator->numForEstimate() || p >= 1.0 || p <= 0.0)
+      return std::vector<double>();
+    if (!paramEstimator->deviceModel(cfg))
+      throw std::invalid_argument("lsqrRecipes::RANSAC: ResidentData needs an estimator with a device model");
+    lsqr_ctx *ctx = data.attach(cfg);
+    return sequentialOn(data, ctx, cfg, data.size(), parameters, p, maxModels, minVotes, labels);
+  }
+
   // sampler stream of the probabilistic overload (default 1); set it to vary the hypotheses
   static uint64_t &seed() {
     static thread_local uint64_t s = 1;
@@ -362,6 +414,63 @@ class RANSAC {
       }
     }
     return pluginFinish(parameters, est, data, best, bestVotes, index, bestIndex, consensusSet);
+  }
+
+  // one lsqr_ransac_sequential call on a context that holds the records; `chk` turns a failure status into its throw
+  template <class Checker>
+  static std::vector<double> sequentialOn(Checker &chk, lsqr_ctx *ctx, const lsqr_model_cfg &cfg, size_t N,
+                                          std::vector<std::vector<S> > &parameters, double p, size_t maxModels,
+                                          size_t minVotes, std::vector<int> *labels) {
+    const int P = lsqr_num_params(&cfg);
+    std::vector<uint64_t> seeds(maxModels);
+    for (size_t r = 0; r < maxModels; r++) seeds[r] = seed() + r;
+    std::vector<double> par(maxModels * (size_t)P);
+    std::vector<int32_t> lab(labels ? N : 0), status(maxModels);
+    std::vector<lsqr_ransac_info> info(maxModels);
+    size_t nModels = 0;
+    chk.check(lsqr_ransac_sequential(ctx, p, &seeds[0], maxModels, minVotes, &par[0], labels ? &lab[0] : NULL,
+                                     &info[0], &status[0], &nModels));
+    std::vector<double> fraction;
+    for (size_t r = 0; r < maxModels && status[r] != LSQR_ERR_STATE; r++) {  // the rounds that ran
+      fraction.push_back(info[r].fraction);
+      lastInfo() = info[r];
+      if (r < nModels) parameters.push_back(std::vector<S>(&par[r * P], &par[r * P] + info[r].n_params));
+    }
+    if (labels) labels->assign(lab.begin(), lab.end());
+    return fraction;
+  }
+
+  // the host loop of computeSequential: pluginCompute on the records that are left, the consensus set erased
+  static std::vector<double> pluginComputeSequential(std::vector<std::vector<S> > &parameters,
+                                                     ParametersEstimator<T, S> *est, std::vector<T> &data, double p,
+                                                     size_t maxModels, size_t minVotes, std::vector<int> *labels) {
+    std::vector<T> cur(data);
+    std::vector<size_t> orig(data.size());
+    for (size_t i = 0; i < orig.size(); i++) orig[i] = i;
+    std::vector<double> fraction;
+    const uint64_t s0 = seed();
+    for (size_t r = 0; r < maxModels && cur.size() >= est->numForEstimate(); r++) {
+      std::vector<S> model;
+      std::vector<bool> cons;
+      seed() = s0 + r;
+      fraction.push_back(pluginCompute(model, est, cur, p, &cons));
+      seed() = s0;
+      const uint64_t votes = lastInfo().best_votes;
+      if (model.empty() || votes < std::max<uint64_t>(minVotes, 1)) break;  // rejected: claims nothing
+      parameters.push_back(model);
+      size_t w = 0;
+      for (size_t i = 0; i < cur.size(); i++) {
+        if (cons[i]) {
+          if (labels) (*labels)[orig[i]] = (int)r;
+        } else {
+          if (w != i) cur[w] = cur[i];  // (guarded: no self-assignment of a record)
+          orig[w++] = orig[i];
+        }
+      }
+      cur.erase(cur.begin() + (std::ptrdiff_t)w, cur.end());  // (T need not be default-constructible)
+      orig.resize(w);
+    }
+    return fraction;
   }
 
   static double finish(bool ok, const lsqr_ransac_info &info, const std::vector<double> &p,

@@ -1,0 +1,29 @@
+"""RANSAC<T,S>::computeSequential of the C++ drop-in: tests/cpp/computeSequentialTest.cxx compiles and links on the
+CPU (against lsqr_ransac_sequential of the C ABI); on the GPU it checks computeSequential against the loop of compute()
+on erased data for the plane, the default sphere, a user-defined plugin estimator and the ResidentData overload."""
+import os
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PROG = os.path.join(ROOT, "examples", "build", "computeSequentialTest")
+
+
+def _build():
+    subprocess.check_call(["make", "-C", os.path.join(ROOT, "examples"), "build/computeSequentialTest"],
+                          stdout=subprocess.DEVNULL)
+
+
+def test_compute_sequential_compiles_and_links():
+    _build()
+    assert os.access(PROG, os.X_OK)
+
+
+@pytest.mark.gpu
+def test_compute_sequential_matches_loop_on_gpu():
+    if not os.path.exists(PROG):
+        _build()
+    r = subprocess.run([PROG], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
+    assert "all checks passed" in r.stdout
