@@ -273,7 +273,7 @@ struct lsqr_ctx {
   uint32_t ovf_cap = 0;          // segment size the deferred check compares against (0: this scan has no worklist)
   uint32_t slot_ovf_cap[2] = {0, 0};
   uint64_t slot_seed[2] = {0, 0};
-  int opt_test_overflow = 0;     // tests: lsqr_batch_fit_wait treats the slot's worklist as overflowed
+  int opt_test_overflow = 0;     // tests: worklist_check and lsqr_batch_fit_wait treat the worklist as overflowed
   uint64_t ovf_reruns = 0;       // batches run again because a worklist segment overflowed (diagnostics)
   uint64_t slot_first[2] = {0, 0}, slot_H[2] = {0, 0};
   bool slot_busy[2] = {false, false};
@@ -426,6 +426,13 @@ struct ProfScope {
     c->ev_pending.push_back({id, pair});
   }
 };
+// no scopes of their own for the launches below one "whole" ProfScope (restored when the guard goes)
+struct ProfMute {
+  lsqr_ctx *c;
+  bool was;
+  explicit ProfMute(lsqr_ctx *c) : c(c), was(c->prof) { c->prof = false; }
+  ~ProfMute() { c->prof = was; }
+};
 
 size_t dense_lds_bytes(int n) { return sizeof(double) * ((size_t)2 * n * (n | 1) + 3 * n); }
 constexpr int dense_ne(int n) { return (n + 1) * (n + 2) / 2; }
@@ -433,6 +440,7 @@ constexpr int dense_ne(int n) { return (n + 1) * (n + 2) / 2; }
 static_assert(sizeof(double) * (dense_ne(30) + 1) <= sizeof(PinLayout::phantom_block) &&
               sizeof(double) * (dense_ne(30) + 1) <= sizeof(PinLayout::scratch));
 constexpr int kDenseBlocks = 256;
+constexpr size_t kPartialsBytes = sizeof(double) * 2 * kDenseBlocks * 2160;  // lsqr_ctx::d_partials
 int dense_pstride(int n) { return (dense_ne(n) + 1 + 7) & ~7; }
 
 template <class T>
@@ -1204,12 +1212,7 @@ int run_scan_bounded(lsqr_ctx *c) {
   typedef typename CM::M M;
   // profiling: ONE scope over the whole scan phase (bounds, selections, both counting launches)
   ProfScope whole(c, KID_SCAN);
-  struct Mute {
-    lsqr_ctx *c;
-    bool was;
-    ~Mute() { c->prof = was; }
-  } mute{c, c->prof};
-  c->prof = false;
+  ProfMute mute(c);
   // the record this scan will write: whatever it still holds (the scan two back) has to have landed before it is
   // reused, and is folded here at the latest
   if (!c->h_bsel) {
@@ -1341,6 +1344,54 @@ int run_early_exit(lsqr_ctx *c, size_t align, const EeBuf &b, Scan &&scan, Gathe
   return LSQR_OK;
 }
 
+// ---- scratch and worklist of the matrix-core filters ------------------------------------------------------
+// The fp16 / fp32 filters of the dense, US and phantom scans keep their per-batch operands and the fill of their
+// worklist segments in d_partials (the fits use it between scans); the fp64 dense filter keeps its thresholds there.
+constexpr size_t kFilterHypCap = 8192;         // hypotheses per batch of the fp16 / fp32 filters
+constexpr size_t kSegWords = 1024;             // segment counters (one per filter workgroup: <= 512 in use)
+constexpr uint32_t kSegCap = kAmbCap / 1024;   // worklist entries per segment
+struct FilterScratchLayout {
+  float thr32[2 * kFilterHypCap];   // 2 floats per hypothesis
+  float sp32[64 * kFilterHypCap];   // 64 floats per hypothesis (2 MB); the fp16 filter's rows live here too
+  unsigned int segcnt[kSegWords];
+};
+static_assert(offsetof(FilterScratchLayout, sp32) == sizeof(float) * 2 * 8192 &&
+              offsetof(FilterScratchLayout, segcnt) == sizeof(float) * (2 * 8192 + 64 * 8192), "areas stay where they were");
+static_assert(sizeof(FilterScratchLayout) <= kPartialsBytes && kSegWords * kSegCap <= kAmbCap, "d_partials / d_amb hold it");
+struct FilterScratch {
+  float *thr32, *sp32;
+  unsigned int *segcnt;
+  double *thr;  // the fp64 filter: 2 doubles per hypothesis (H checked by its caller)
+};
+FilterScratch filter_scratch(lsqr_ctx *c) {
+  FilterScratchLayout *l = (FilterScratchLayout *)c->d_partials;
+  return {l->thr32, l->sp32, l->segcnt, c->d_partials};
+}
+// before a filter's launches: no segment holds anything, no fill recorded (fs == null: the fp64 filter's one worklist)
+int worklist_reset(lsqr_ctx *c, const FilterScratch *fs) {
+  if (fs) HIPCHK(c, hipMemsetAsync(fs->segcnt, 0, kSegWords * sizeof(unsigned int), c->stream));
+  HIPCHK(c, hipMemsetAsync(c->d_counter + CNT_OVF, 0, sizeof(unsigned long long), c->stream));
+  return LSQR_OK;
+}
+// after them: did the fullest segment stay within seg_cap?  lsqr_batch_fit_enqueue (defer_ovf) must not wait: the scan only
+// notes seg_cap, lsqr_batch_fit_wait compares; everyone else synchronises here.  "scan_test_overflow": always OVERFLOWED.
+struct WorklistFill {
+  enum { DEFERRED, FITS, OVERFLOWED } state;
+  unsigned int fill;
+};
+int worklist_check(lsqr_ctx *c, uint32_t seg_cap, WorklistFill *w) {
+  *w = {WorklistFill::DEFERRED, 0};
+  if (c->defer_ovf) {
+    c->ovf_cap = seg_cap;
+    return LSQR_OK;
+  }
+  HIPCHK(c, hipMemcpyAsync(c->h_pin->scratch, c->d_counter + CNT_OVF, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, sync_stream(c));
+  w->fill = *(unsigned int *)c->h_pin->scratch;
+  w->state = w->fill > seg_cap || c->opt_test_overflow ? WorklistFill::OVERFLOWED : WorklistFill::FITS;
+  return LSQR_OK;
+}
+
 // once per context: does this device's matrix unit align the products of one instruction as the fp16 filters'
 // thresholds assume (dense_h16.h: k_dense_h16_probe)?  c->h16_unit = 1 / -1.
 int h16_probe_unit(lsqr_ctx *c) {
@@ -1418,10 +1469,11 @@ int ensure_us_h16(lsqr_ctx *c, bool *ok) {
 // frames [rb, re) against the H hypotheses whose scan parameters are `sp` (the batch or a compact selection): split of
 // the unknowns, the filter in launches of 1024 hypotheses, the exact decision of the band
 template <class M>
-int launch_us_h16(lsqr_ctx *c, size_t rb, size_t re, const double *sp, uint32_t H, unsigned int *d_segcnt, uint32_t seg_cap,
-                  const uint32_t *h_dev, const uint32_t *sel, const uint32_t *range_dev) {
+int launch_us_h16(lsqr_ctx *c, size_t rb, size_t re, const double *sp, uint32_t H, const uint32_t *h_dev,
+                  const uint32_t *sel, const uint32_t *range_dev) {
   constexpr bool PH = requires { M::IS_PHANTOM; };
   constexpr bool SINGLE = PH || M::K == 4;
+  unsigned int *d_segcnt = filter_scratch(c).segcnt;
   if constexpr (PH)
     hipLaunchKernelGGL(k_phantom_prep_h16, dim3((H + 31 + 255) / 256), dim3(256), 0, c->stream, sp, (int)M::SP, H,
                        sqrt(c->mc.delta_sq), c->mc.absmax, c->mc.absmax_rot, c->us16_sc, c->d_us16_x, c->d_h16_thr);
@@ -1435,18 +1487,18 @@ int launch_us_h16(lsqr_ctx *c, size_t rb, size_t re, const double *sp, uint32_t 
     const uint32_t hc = (uint32_t)std::min<size_t>(kUs16HypChunk, H - h0);
     if constexpr (PH)
       hipLaunchKernelGGL(k_scan_phantom_h16, dim3(nblk), dim3(kPh16Wg), phantom_h16_lds(hc), c->stream, c->d_us16, c->n, rb, re,
-                         c->d_us16_x + (h0 / 32) * 256, c->d_h16_thr + 4 * h0, hc, c->d_votes, c->d_amb, d_segcnt, seg_cap,
+                         c->d_us16_x + (h0 / 32) * 256, c->d_h16_thr + 4 * h0, hc, c->d_votes, c->d_amb, d_segcnt, kSegCap,
                          (uint32_t)h0, h_dev, sel, range_dev);
     else
       hipLaunchKernelGGL((k_scan_us_h16<SINGLE>), dim3(nblk), dim3(kUs16Wg), us_h16_lds(hc), c->stream, c->d_us16, c->n, rb,
-                         re, c->d_us16_x + (h0 / 32) * 128, c->d_h16_thr + 4 * h0, hc, c->d_votes, c->d_amb, d_segcnt, seg_cap,
+                         re, c->d_us16_x + (h0 / 32) * 128, c->d_h16_thr + 4 * h0, hc, c->d_votes, c->d_amb, d_segcnt, kSegCap,
                          (uint32_t)h0, h_dev, sel, range_dev);
     HIPCHK(c, hipGetLastError());
     // the exact decision of the band: the phantom after every launch (its 31-term sums leave ~3e-4 of the pairs there,
     // a workgroup's segment holds one launch's share, not four), the calibrations once
     if (PH || h0 + kUs16HypChunk >= H) {
       hipLaunchKernelGGL((k_us_recheck_seg<M>), dim3(256), dim3(1024), 0, c->stream, c->d_data, c->stride, c->d_hparams,
-                         (int)M::SP, c->mc, c->d_amb, d_segcnt, seg_cap, c->d_votes, (unsigned int *)(c->d_counter + CNT_OVF));
+                         (int)M::SP, c->mc, c->d_amb, d_segcnt, kSegCap, c->d_votes, (unsigned int *)(c->d_counter + CNT_OVF));
       HIPCHK(c, hipGetLastError());
     }
   }
@@ -1498,8 +1550,7 @@ int ensure_dense_h16(lsqr_ctx *c, bool *ok) {
 }
 // rows [rb, re) against hypotheses of `xh` / `thr4` (the batch itself or a compact selection), in launches of 1024
 int launch_dense_h16(lsqr_ctx *c, size_t rb, size_t re, const _Float16 *xh, const float *thr4, uint32_t H,
-                     unsigned int *d_segcnt, uint32_t seg_cap, const uint32_t *h_dev, const uint32_t *sel,
-                     const uint32_t *range_dev, size_t *nblk_out) {
+                     const uint32_t *h_dev, const uint32_t *sel, const uint32_t *range_dev, size_t *nblk_out) {
   const size_t passes = (re - rb + kH16RowsPerWg - 1) / kH16RowsPerWg;
   const size_t nb = std::min<size_t>(passes, 512);  // two workgroups per CU
   const size_t rpb = (passes + nb - 1) / nb * kH16RowsPerWg;
@@ -1508,20 +1559,76 @@ int launch_dense_h16(lsqr_ctx *c, size_t rb, size_t re, const _Float16 *xh, cons
   for (size_t h0 = 0; h0 < H; h0 += 1024) {
     const uint32_t hc = (uint32_t)std::min<size_t>(1024, H - h0);
     hipLaunchKernelGGL((k_scan_dense_h16<64>), dim3((unsigned)nblk), dim3(256), dense_h16_lds(hc), c->stream, c->d_h16,
-                       c->d_h16_bs, rb, re, rpb, xh + h0 * 128, thr4 + 4 * h0, hc, c->d_votes, c->d_amb, d_segcnt,
-                       seg_cap, (uint32_t)h0, h_dev, sel, range_dev);
+                       c->d_h16_bs, rb, re, rpb, xh + h0 * 128, thr4 + 4 * h0, hc, c->d_votes, c->d_amb,
+                       filter_scratch(c).segcnt, kSegCap, (uint32_t)h0, h_dev, sel, range_dev);
     HIPCHK(c, hipGetLastError());
   }
   return LSQR_OK;
 }
 
+// rows [rb, re) against hypotheses of `rows` / `thr` (the batch itself or a compact selection): the fp32 filter (dense.h:
+// k_scan_dense_mfma32r), hypothesis fragments prefetched through an LDS ring, in launches of 1024
+int launch_dense_f32(lsqr_ctx *c, size_t rb, size_t re, const float *rows, const float *thr, uint32_t H,
+                     const uint32_t *h_dev, const uint32_t *sel, const uint32_t *range_dev, size_t *nblk_out) {
+  // two waves per SIMD (the A fragments live in registers): exactly two workgroups per CU
+  const size_t tiles = (re - rb + 63) / 64;
+  const size_t nb2 = std::min<size_t>(tiles, 512);
+  const size_t rpb = (tiles + nb2 - 1) / nb2 * 64;
+  const size_t nblk = (re - rb + rpb - 1) / rpb;
+  if (nblk_out) *nblk_out = nblk;
+  constexpr size_t kRingChunk = 1024;  // 62.7 KiB of LDS per workgroup: two per CU
+  for (size_t h0 = 0; h0 < H; h0 += kRingChunk) {
+    const uint32_t hc = (uint32_t)std::min<size_t>(kRingChunk, H - h0);
+    const uint32_t nhb2 = (((hc + 63) / 64) + 1) & ~1u;
+    const size_t lds = sizeof(float) * (8192 + 64 * kDmPitch32 + 64 + 128 * nhb2) + sizeof(uint32_t) * (hc + 1);
+    hipLaunchKernelGGL((k_scan_dense_mfma32r<64>), dim3((unsigned)nblk), dim3(256), lds, c->stream, c->d_data,
+                       c->stride, rb, re, rpb, rows + h0 * 64, thr + 2 * h0, hc, (int)c->cfg.dim, c->d_votes,
+                       c->d_amb, filter_scratch(c).segcnt, kSegCap, (uint32_t)h0, h_dev, sel, range_dev);
+    HIPCHK(c, hipGetLastError());
+  }
+  return LSQR_OK;
+}
+// the exact decision of the band the fp16 / fp32 filter left in its segments
+int launch_dense_recheck_seg(lsqr_ctx *c, size_t nblk) {
+  hipLaunchKernelGGL((k_dense_recheck_seg<64>), dim3((unsigned)nblk), dim3(256), 0, c->stream, c->d_data, c->stride,
+                     c->d_hparams, c->mc, c->d_amb, filter_scratch(c).segcnt, kSegCap, c->d_votes,
+                     (unsigned int *)(c->d_counter + CNT_OVF));
+  HIPCHK(c, hipGetLastError());
+  return LSQR_OK;
+}
+// the batch's operands of the fp16 (dense_h16.h) or the fp32 filter
+int dense_filter_prep(lsqr_ctx *c, const FilterScratch &fs, bool h16) {
+  const uint32_t H = (uint32_t)c->H;
+  if (h16)  // the fp16 filter's rows live where the fp32 filter keeps its own (256 B per hypothesis either way)
+    hipLaunchKernelGGL(k_dense_prep_h16, dim3((H + 3) / 4), dim3(256), 0, c->stream, c->d_hparams, H, (int)c->cfg.dim,
+                       64, c->mc.delta, c->mc.absmax_rot, c->mc.absmax, c->h16_pa, (_Float16 *)fs.sp32, c->d_h16_thr);
+  else
+    hipLaunchKernelGGL(k_dense_thresholds32, dim3((H + 255) / 256), dim3(256), 0, c->stream, c->d_hparams, H,
+                       (int)c->cfg.dim, 64, c->mc.delta, c->mc.absmax_rot, c->mc.absmax, fs.thr32, fs.sp32);
+  HIPCHK(c, hipGetLastError());
+  return LSQR_OK;
+}
 // diagnostics (LSQR_DENSE_DEBUG): how full the dense scan's worklist got (the exact kernel has emptied the segments by
 // now: the fullest one is what it recorded; a launch's total is about that times the filter's workgroups)
-static void dense_worklist_debug(lsqr_ctx *c, const unsigned int *, uint32_t seg_cap) {
+static void dense_worklist_debug(lsqr_ctx *c) {
   static const bool dbg_on = getenv("LSQR_DENSE_DEBUG") != nullptr;
   if (dbg_on)
-    fprintf(stderr, "dense scan: fullest worklist segment %u of %u (%zu rows x %zu hypotheses)\n", c->dense_amb_max, seg_cap,
+    fprintf(stderr, "dense scan: fullest worklist segment %u of %u (%zu rows x %zu hypotheses)\n", c->dense_amb_max, kSegCap,
             (size_t)c->n, (size_t)c->H);
+}
+// the dense fp16 / fp32 filter's worklist check: *fits = false (and the note) when the fp64 filter has to count instead
+int dense_worklist_check(lsqr_ctx *c, bool *fits) {
+  WorklistFill w;
+  int st = worklist_check(c, kSegCap, &w);
+  if (st != LSQR_OK) return st;
+  *fits = w.state != WorklistFill::OVERFLOWED;
+  if (w.state == WorklistFill::DEFERRED) return LSQR_OK;
+  c->dense_amb_max = w.fill;
+  dense_worklist_debug(c);
+  if (!*fits)
+    (void)fail(c, LSQR_OK, "dense fp16 / fp32 filter: worklist segment overflow (fill %u > %u), fp64 filter used",
+               c->dense_amb_max, kSegCap);
+  return LSQR_OK;
 }
 
 // dense system, n > 32: the fp32 matrix-core filter (dense.h: k_scan_dense_mfma32r) over row chunks and compacted
@@ -1534,86 +1641,59 @@ int run_scan_dense_ee(lsqr_ctx *c, bool *done) {
   int st = ee_buffers(c, &b);
   if (st != LSQR_OK) return st;
   const uint32_t H = (uint32_t)c->H;
-  const uint32_t seg_cap = kAmbCap / 1024;
-  float *d_thr32 = (float *)c->d_partials;
-  float *d_sp32 = (float *)c->d_partials + 2 * 8192;
-  unsigned int *d_segcnt = (unsigned int *)((float *)c->d_partials + 2 * 8192 + 64 * 8192);
+  const FilterScratch fs = filter_scratch(c);
   ProfScope whole(c, KID_SCAN);
-  struct Mute {
-    lsqr_ctx *c;
-    bool was;
-    ~Mute() { c->prof = was; }
-  } mute{c, c->prof};
-  c->prof = false;
-  HIPCHK(c, hipMemsetAsync(d_segcnt, 0, 1024 * sizeof(unsigned int), c->stream));
-  HIPCHK(c, hipMemsetAsync(c->d_counter + CNT_OVF, 0, sizeof(unsigned long long), c->stream));
+  ProfMute mute(c);
+  if ((st = worklist_reset(c, &fs)) != LSQR_OK) return st;
   bool h16 = false;
   if (c->opt_dense_f32 == 2 && (st = ensure_dense_h16(c, &h16)) != LSQR_OK) return st;
-  if (h16)  // the fp16 filter's rows live where the fp32 filter keeps its own (256 B per hypothesis either way)
-    hipLaunchKernelGGL(k_dense_prep_h16, dim3((H + 3) / 4), dim3(256), 0, c->stream, c->d_hparams, H, (int)c->cfg.dim,
-                       64, c->mc.delta, c->mc.absmax_rot, c->mc.absmax, c->h16_pa, (_Float16 *)d_sp32, c->d_h16_thr);
-  else
-    hipLaunchKernelGGL(k_dense_thresholds32, dim3((H + 255) / 256), dim3(256), 0, c->stream, c->d_hparams, H,
-                       (int)c->cfg.dim, 64, c->mc.delta, c->mc.absmax_rot, c->mc.absmax, d_thr32, d_sp32);
-  HIPCHK(c, hipGetLastError());
+  if ((st = dense_filter_prep(c, fs, h16)) != LSQR_OK) return st;
   auto scan = [&](size_t rb, size_t re, const uint32_t *range_dev, const uint32_t *h_dev, const uint32_t *sel) -> int {
     if (rb >= re) return LSQR_OK;
-    if (h16) {
-      int s2 = launch_dense_h16(c, rb, re, (const _Float16 *)(sel ? b.rows_c : d_sp32), sel ? b.thr_c : c->d_h16_thr, H,
-                                d_segcnt, seg_cap, h_dev, sel, range_dev, nullptr);
-      if (s2 != LSQR_OK) return s2;
-      hipLaunchKernelGGL((k_dense_recheck_seg<64>), dim3(512), dim3(256), 0, c->stream, c->d_data, c->stride,
-                         c->d_hparams, c->mc, c->d_amb, d_segcnt, seg_cap, c->d_votes, (unsigned int *)(c->d_counter + CNT_OVF));
-      HIPCHK(c, hipGetLastError());
-      return LSQR_OK;
-    }
-    const size_t tiles = (re - rb + 63) / 64;
-    const size_t nb2 = std::min<size_t>(tiles, 512);  // two workgroups per CU
-    const size_t rpb = (tiles + nb2 - 1) / nb2 * 64;
-    const size_t nblk = (re - rb + rpb - 1) / rpb;
-    const float *rows = sel ? b.rows_c : d_sp32, *thr = sel ? b.thr_c : d_thr32;
-    constexpr size_t kRingChunk = 1024;  // 62.7 KiB of LDS per workgroup: two per CU
-    for (size_t h0 = 0; h0 < H; h0 += kRingChunk) {
-      const uint32_t hc = (uint32_t)std::min<size_t>(kRingChunk, H - h0);
-      const uint32_t nhb2 = (((hc + 63) / 64) + 1) & ~1u;
-      const size_t lds = sizeof(float) * (8192 + 64 * kDmPitch32 + 64 + 128 * nhb2) + sizeof(uint32_t) * (hc + 1);
-      hipLaunchKernelGGL((k_scan_dense_mfma32r<64>), dim3((unsigned)nblk), dim3(256), lds, c->stream, c->d_data,
-                         c->stride, rb, re, rpb, rows + h0 * 64, thr + 2 * h0, hc, (int)c->cfg.dim, c->d_votes,
-                         c->d_amb, d_segcnt, seg_cap, (uint32_t)h0, h_dev, sel, range_dev);
-      HIPCHK(c, hipGetLastError());
-    }
-    hipLaunchKernelGGL((k_dense_recheck_seg<64>), dim3(512), dim3(256), 0, c->stream, c->d_data, c->stride,
-                       c->d_hparams, c->mc, c->d_amb, d_segcnt, seg_cap, c->d_votes, (unsigned int *)(c->d_counter + CNT_OVF));
-    HIPCHK(c, hipGetLastError());
-    return LSQR_OK;
+    int s2 = h16 ? launch_dense_h16(c, rb, re, (const _Float16 *)(sel ? b.rows_c : fs.sp32), sel ? b.thr_c : c->d_h16_thr, H,
+                                    h_dev, sel, range_dev, nullptr)
+                 : launch_dense_f32(c, rb, re, sel ? b.rows_c : fs.sp32, sel ? b.thr_c : fs.thr32, H, h_dev, sel, range_dev,
+                                    nullptr);
+    return s2 != LSQR_OK ? s2 : launch_dense_recheck_seg(c, 512);
   };
   auto gather = [&](const uint32_t *sel, const uint32_t *n_dev) -> int {
-    if (h16)  // (positions past the selection are never read: the scan takes its size from *n_dev)
-      hipLaunchKernelGGL(k_ee_gather_f32, dim3((H + 3) / 4), dim3(256), 0, c->stream, sel, n_dev, H,
-                         (const float *)d_sp32, 64, b.rows_c, (const float *)c->d_h16_thr, 4, b.thr_c, 0.0f);
-    else
-    hipLaunchKernelGGL(k_ee_gather_f32, dim3((H + 3) / 4), dim3(256), 0, c->stream, sel, n_dev, H,
-                       (const float *)d_sp32, 64, b.rows_c, (const float *)d_thr32, 2, b.thr_c, -1.0f);
+    // (fp16: positions past the selection are never read, the scan takes its size from *n_dev)
+    hipLaunchKernelGGL(k_ee_gather_f32, dim3((H + 3) / 4), dim3(256), 0, c->stream, sel, n_dev, H, (const float *)fs.sp32, 64,
+                       b.rows_c, (const float *)(h16 ? c->d_h16_thr : fs.thr32), h16 ? 4 : 2, b.thr_c, h16 ? 0.0f : -1.0f);
     HIPCHK(c, hipGetLastError());
     return LSQR_OK;
   };
   if ((st = run_early_exit(c, 64, b, scan, gather)) != LSQR_OK) return st;
-  if (c->defer_ovf) {  // lsqr_batch_fit_enqueue: no host synchronisation here, lsqr_batch_fit_wait checks the fill
-    c->ovf_cap = seg_cap;
-    *done = true;
-    return LSQR_OK;
-  }
-  HIPCHK(c, hipMemcpyAsync(c->h_pin->scratch, c->d_counter + CNT_OVF, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, sync_stream(c));
-  c->dense_amb_max = *(unsigned int *)c->h_pin->scratch;
-  dense_worklist_debug(c, d_segcnt, seg_cap);
-  if (c->dense_amb_max <= seg_cap) {
-    *done = true;
-    return LSQR_OK;
-  }
-  c->ee_last = false;
-  (void)fail(c, LSQR_OK, "dense fp16 / fp32 filter: worklist segment overflow (fill %u > %u), fp64 filter used",
-             c->dense_amb_max, seg_cap);
+  if ((st = dense_worklist_check(c, done)) != LSQR_OK) return st;
+  if (!*done) c->ee_last = false;
+  return LSQR_OK;
+}
+
+// k_scan_us_f32 (the packed fp32 filter of the US calibrations / plane phantom): frames [rb, re) against the hc
+// hypotheses of sp / spf, votes to `votes`
+template <class M>
+int launch_us_f32(lsqr_ctx *c, size_t rb, size_t re, const double *sp, const float *spf, uint32_t hc, uint32_t *votes,
+                  const uint32_t *h_dev, const uint32_t *sel, const uint32_t *range_dev) {
+  const int np = c->opt_ppl == 2 ? 1 : 2;  // pairs of frames per lane (scan_ppl 2 / 4)
+  const size_t tile = (size_t)kBlock * 2 * np;
+  const size_t tiles = (re - rb + tile - 1) / tile;
+  const size_t lds = (size_t)hc * sizeof(uint32_t);
+  int per_cu = (int)std::min<size_t>(8, (160 * 1024) / std::max<size_t>(lds, 1));
+  if (per_cu < 1) per_cu = 1;
+  const size_t max_blocks = (size_t)256 * per_cu;
+  const size_t tpb = (tiles + max_blocks - 1) / max_blocks;
+  const int grid = (int)((tiles + tpb - 1) / tpb);
+  // few tiles (1 M frames = 977): split the hypothesis range over blockIdx.y to fill the chip
+  unsigned ysplit = (unsigned)std::min<size_t>(std::max<size_t>(1, (size_t)256 * 5 / (size_t)grid),
+                                               std::max<size_t>(1, hc / 256));
+  if (c->opt_hsplit > 0) ysplit = (unsigned)c->opt_hsplit;
+  if (np == 1)
+    hipLaunchKernelGGL((k_scan_us_f32<M, 1>), dim3(grid, ysplit), dim3(kBlock), lds, c->stream, c->d_data, c->stride,
+                       rb, re, sp, spf, hc, c->mc, votes, h_dev, sel, range_dev);
+  else
+    hipLaunchKernelGGL((k_scan_us_f32<M, 2>), dim3(grid, ysplit), dim3(kBlock), lds, c->stream, c->d_data, c->stride,
+                       rb, re, sp, spf, hc, c->mc, votes, h_dev, sel, range_dev);
+  HIPCHK(c, hipGetLastError());
   return LSQR_OK;
 }
 
@@ -1624,53 +1704,25 @@ int run_scan_us_ee(lsqr_ctx *c) {
   int st = ee_buffers(c, &b);
   if (st != LSQR_OK) return st;
   const uint32_t H = (uint32_t)c->H;
-  const int np = c->opt_ppl == 2 ? 1 : 2;
-  const size_t tile = (size_t)kBlock * 2 * np;
+  const size_t tile = (size_t)kBlock * 2 * (c->opt_ppl == 2 ? 1 : 2);
   ProfScope whole(c, KID_SCAN);
-  struct Mute {
-    lsqr_ctx *c;
-    bool was;
-    ~Mute() { c->prof = was; }
-  } mute{c, c->prof};
-  c->prof = false;
+  ProfMute mute(c);
   bool h16 = false;
-  unsigned int *d_segcnt = (unsigned int *)((float *)c->d_partials + 2 * 8192 + 64 * 8192);
-  const uint32_t seg_cap = kAmbCap / 1024;
   if constexpr (kHasUsH16<M>) {
-    if (c->opt_us_h16 && H <= 8192) {
+    if (c->opt_us_h16 && H <= kFilterHypCap) {
       if ((st = ensure_us_h16<M>(c, &h16)) != LSQR_OK) return st;
-      if (h16) {
-        HIPCHK(c, hipMemsetAsync(d_segcnt, 0, 1024 * sizeof(unsigned int), c->stream));
-        HIPCHK(c, hipMemsetAsync(c->d_counter + CNT_OVF, 0, sizeof(unsigned long long), c->stream));
-      }
+      const FilterScratch fs = filter_scratch(c);
+      if (h16 && (st = worklist_reset(c, &fs)) != LSQR_OK) return st;
     }
   }
   auto scan = [&](size_t rb, size_t re, const uint32_t *range_dev, const uint32_t *h_dev, const uint32_t *sel) -> int {
     if (rb >= re) return LSQR_OK;
     if constexpr (kHasUsH16<M>) {
       if (h16)  // fp16 matrix cores (us_h16.h); the band of every chunk is decided exactly before the next selection
-        return launch_us_h16<M>(c, rb, re, sel ? c->d_hparams2 : c->d_hparams, H, d_segcnt, seg_cap, h_dev, sel, range_dev);
+        return launch_us_h16<M>(c, rb, re, sel ? c->d_hparams2 : c->d_hparams, H, h_dev, sel, range_dev);
     }
-    const size_t tiles = (re - rb + tile - 1) / tile;
-    const size_t lds = (size_t)H * sizeof(uint32_t);
-    int per_cu = (int)std::min<size_t>(8, (160 * 1024) / std::max<size_t>(lds, 1));
-    if (per_cu < 1) per_cu = 1;
-    const size_t max_blocks = (size_t)256 * per_cu;
-    const size_t tpb = (tiles + max_blocks - 1) / max_blocks;
-    const int grid = (int)((tiles + tpb - 1) / tpb);
-    unsigned ysplit = (unsigned)std::min<size_t>(std::max<size_t>(1, (size_t)256 * 5 / (size_t)grid),
-                                                 std::max<size_t>(1, H / 256));
-    if (c->opt_hsplit > 0) ysplit = (unsigned)c->opt_hsplit;
-    const double *sp = sel ? c->d_hparams2 : c->d_hparams;
-    const float *spf = sel ? c->d_hparams2_f32 : c->d_hparams_f32;
-    if (np == 1)
-      hipLaunchKernelGGL((k_scan_us_f32<M, 1>), dim3(grid, ysplit), dim3(kBlock), lds, c->stream, c->d_data, c->stride,
-                         rb, re, sp, spf, H, c->mc, c->d_votes, h_dev, sel, range_dev);
-    else
-      hipLaunchKernelGGL((k_scan_us_f32<M, 2>), dim3(grid, ysplit), dim3(kBlock), lds, c->stream, c->d_data, c->stride,
-                         rb, re, sp, spf, H, c->mc, c->d_votes, h_dev, sel, range_dev);
-    HIPCHK(c, hipGetLastError());
-    return LSQR_OK;
+    return launch_us_f32<M>(c, rb, re, sel ? c->d_hparams2 : c->d_hparams, sel ? c->d_hparams2_f32 : c->d_hparams_f32, H,
+                            c->d_votes, h_dev, sel, range_dev);
   };
   auto gather = [&](const uint32_t *sel, const uint32_t *n_dev) -> int {
     hipLaunchKernelGGL(k_gather_rows, dim3((H + 3) / 4), dim3(256), 0, c->stream, sel, n_dev, H, c->d_hparams,
@@ -1679,350 +1731,297 @@ int run_scan_us_ee(lsqr_ctx *c) {
     return LSQR_OK;
   };
   if ((st = run_early_exit(c, tile, b, scan, gather)) != LSQR_OK) return st;
-  if (h16 && c->defer_ovf) {  // lsqr_batch_fit_enqueue: lsqr_batch_fit_wait checks the fill (no synchronisation here)
-    c->ovf_cap = seg_cap;
-    return LSQR_OK;
-  }
-  if (h16) {  // a worklist segment that overflowed (not seen): everything again with the packed fp32 filter
-    HIPCHK(c, hipMemcpyAsync(c->h_pin->scratch, c->d_counter + CNT_OVF, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, sync_stream(c));
-    if (*(unsigned int *)c->h_pin->scratch > seg_cap) {
-      (void)fail(c, LSQR_OK, "US fp16 filter: worklist segment overflow (fill %u > %u), fp32 filter used",
-                 *(unsigned int *)c->h_pin->scratch, seg_cap);
-      const int keep = c->opt_us_h16;
-      c->opt_us_h16 = 0;
-      c->prof = mute.was;
-      st = run_scan_us_ee<M>(c);
-      c->opt_us_h16 = keep;
-      return st;
+  if (!h16) return LSQR_OK;
+  WorklistFill w;
+  if ((st = worklist_check(c, kSegCap, &w)) != LSQR_OK) return st;
+  if (w.state != WorklistFill::OVERFLOWED) return LSQR_OK;
+  // a worklist segment that overflowed (not seen): everything again with the packed fp32 filter
+  (void)fail(c, LSQR_OK, "US fp16 filter: worklist segment overflow (fill %u > %u), fp32 filter used", w.fill, kSegCap);
+  const int keep = c->opt_us_h16;
+  c->opt_us_h16 = 0;
+  c->prof = mute.was;
+  st = run_scan_us_ee<M>(c);
+  c->opt_us_h16 = keep;
+  return st;
+}
+
+// ---- the scan families: each either counts the batch (*done = true) or leaves it to the next one (run_scan) --------
+// dense system, fp64 matrix-core filter + exact recheck of the ambiguous pairs; a worklist overflow leaves the batch
+// to the exact kernel
+template <class M>
+int scan_dense_f64(lsqr_ctx *c, bool *done) {
+  int st = worklist_reset(c, nullptr);
+  if (st != LSQR_OK) return st;
+  double *d_thr = filter_scratch(c).thr;  // scratch: 2 doubles per hypothesis (H <= 2^20 checked)
+  if (c->H * 2 > (size_t)kDenseBlocks * 2160) return fail(c, LSQR_ERR_INVALID, "batch too large");
+  size_t tiles = (c->n + 63) / 64;
+  size_t nblk = std::min<size_t>(tiles, 768);  // 3 workgroups per CU
+  size_t rpb = (tiles + nblk - 1) / nblk * 64;
+  nblk = (c->n + rpb - 1) / rpb;
+  {
+    ProfScope ps(c, KID_SCAN);
+    hipLaunchKernelGGL(k_dense_thresholds, dim3((unsigned)((c->H + 255) / 256)), dim3(256), 0, c->stream, c->d_hparams,
+                       (uint32_t)c->H, (int)c->cfg.dim, (int)M::NR, c->mc.delta, c->mc.absmax, d_thr);
+    HIPCHK(c, hipGetLastError());
+    for (size_t h0 = 0; h0 < c->H; h0 += kDmHypChunk) {
+      uint32_t hc = (uint32_t)std::min<size_t>(kDmHypChunk, c->H - h0);
+      if constexpr (M::NR == 64) {
+        {  // n = 64: B fragments in registers, no barriers per block
+          size_t lds2 = sizeof(double) * (64 * kDmPitch + 64) + sizeof(uint32_t) * hc;
+          hipLaunchKernelGGL((k_scan_dense_mfma2<64>), dim3((unsigned)nblk), dim3(256), lds2, c->stream, c->d_data,
+                             c->stride, c->n, rpb, c->d_hparams + h0 * M::NR, d_thr + 2 * h0, hc, (int)c->cfg.dim,
+                             c->d_votes + h0, c->d_amb, (unsigned int *)(c->d_counter + CNT_OVF), (uint32_t)h0);
+          HIPCHK(c, hipGetLastError());
+          continue;
+        }
+      }
+      size_t lds = sizeof(double) * (2 * 64 * kDmPitch + 3 * 64) + sizeof(uint32_t) * hc;
+      hipLaunchKernelGGL((k_scan_dense_mfma<M::NR>), dim3((unsigned)nblk), dim3(256), lds, c->stream, c->d_data,
+                         c->stride, c->n, rpb, c->d_hparams + h0 * M::NR, d_thr + 2 * h0, hc, (int)c->cfg.dim,
+                         c->d_votes + h0, c->d_amb, (unsigned int *)(c->d_counter + CNT_OVF), (uint32_t)h0);
+      HIPCHK(c, hipGetLastError());
     }
+    hipLaunchKernelGGL((k_dense_recheck<M::NR>), dim3(64), dim3(256), 0, c->stream, c->d_data, c->stride, c->d_hparams,
+                       c->mc, c->d_amb, (const unsigned int *)(c->d_counter + CNT_OVF), c->d_votes);
+    HIPCHK(c, hipGetLastError());
+  }
+  // worklist overflow (never seen: ~1e-13 of the pairs are ambiguous) -> exact kernel
+  WorklistFill w;
+  if ((st = worklist_check(c, kAmbCap, &w)) != LSQR_OK) return st;
+  *done = w.state != WorklistFill::OVERFLOWED;
+  if (!*done)
+    (void)fail(c, LSQR_OK, "dense fp64 filter: worklist overflow (fill %u > %u), exact kernel used", w.fill, kAmbCap);
+  return LSQR_OK;
+}
+// default at n > 32: the filter in fp32 on the matrix cores (twice the fp64 MFMA rate); its band holds
+// ~1e-4 of the pairs, decided exactly from a per-workgroup worklist.  A segment overflow (not seen)
+// leaves the batch to the fp64 filter.
+int scan_dense_f32(lsqr_ctx *c, bool *done) {
+  const FilterScratch fs = filter_scratch(c);
+  int st = worklist_reset(c, &fs);
+  if (st != LSQR_OK) return st;
+  bool h16 = false;  // fp16 matrix cores on two-way splits (dense_h16.h)
+  if (c->opt_dense_f32 == 2 && (st = ensure_dense_h16(c, &h16)) != LSQR_OK) return st;
+  {
+    ProfScope ps(c, KID_SCAN);
+    if ((st = dense_filter_prep(c, fs, h16)) != LSQR_OK) return st;
+    size_t nblk = 0;
+    st = h16 ? launch_dense_h16(c, 0, c->n, (const _Float16 *)fs.sp32, c->d_h16_thr, (uint32_t)c->H, nullptr, nullptr,
+                                nullptr, &nblk)
+             : launch_dense_f32(c, 0, c->n, fs.sp32, fs.thr32, (uint32_t)c->H, nullptr, nullptr, nullptr, &nblk);
+    if (st != LSQR_OK || (st = launch_dense_recheck_seg(c, nblk)) != LSQR_OK) return st;
+  }
+  return dense_worklist_check(c, done);
+}
+// dense system.  default: MFMA filter + exact recheck of ambiguous pairs
+template <class M>
+int scan_dense(lsqr_ctx *c, bool *done) {
+  if (!c->opt_filter) return LSQR_OK;
+  int st = ensure_absmax(c);
+  if (st != LSQR_OK) return st;
+  if (!c->d_amb) HIPCHK(c, hipMalloc((void **)&c->d_amb, sizeof(unsigned long long) * kAmbCap));
+  if (!(c->mc.absmax <= 1e100)) return LSQR_OK;  // finite, sane magnitudes: the filter's bound applies
+  if constexpr (M::NR == 64) {
+    // batch entry points: chunked early exit (earlyexit.h) -- hypotheses that can no longer become the running
+    // maximum stop being counted
+    if (c->allow_bound && c->opt_bound && c->opt_dense_f32 && c->H >= 128 &&
+        c->H <= kEeCap && c->n >= 65536 && c->mc.absmax < 1e15)
+      if ((st = run_scan_dense_ee(c, done)) != LSQR_OK || *done) return st;
+  }
+  HIPCHK(c, hipMemsetAsync(c->d_votes, 0, c->H * sizeof(uint32_t), c->stream));
+  if constexpr (M::NR == 64) {
+    if (c->opt_dense_f32 && c->H <= kFilterHypCap && c->mc.absmax < 1e15) {
+      if ((st = scan_dense_f32(c, done)) != LSQR_OK || *done) return st;
+      HIPCHK(c, hipMemsetAsync(c->d_votes, 0, c->H * sizeof(uint32_t), c->stream));   // overflow: fp64 filter
+    }
+  }
+  return scan_dense_f64<M>(c, done);
+}
+
+// US calibrations / plane phantom: packed fp32 pre-filter (scan_filter 1); US: 2 = the fused fp64 filter
+template <class M>
+int scan_us(lsqr_ctx *c, bool *done) {
+  if (!(c->opt_filter == 1 && c->absmax_valid && c->mc.absmax <= 1e15)) return LSQR_OK;
+  *done = true;
+  c->ee_last = false;
+  if (c->allow_bound && c->opt_bound && c->H >= 256 && c->H <= kEeCap && c->n >= 65536)
+    return run_scan_us_ee<M>(c);  // batch entry points: chunked early exit (earlyexit.h)
+  int st;
+  HIPCHK(c, hipMemsetAsync(c->d_votes, 0, c->H * sizeof(uint32_t), c->stream));
+  if constexpr (kHasUsH16<M>) {
+    if (c->opt_us_h16 && c->H >= 32 && c->H <= kFilterHypCap && c->n >= 4096) {  // fp16 matrix cores (us_h16.h)
+      bool h16 = false;
+      if ((st = ensure_us_h16<M>(c, &h16)) != LSQR_OK) return st;
+      if (h16) {
+        const FilterScratch fs = filter_scratch(c);
+        if ((st = worklist_reset(c, &fs)) != LSQR_OK) return st;
+        {
+          ProfScope ps(c, KID_SCAN);
+          if ((st = launch_us_h16<M>(c, 0, c->n, c->d_hparams, (uint32_t)c->H, nullptr, nullptr, nullptr)) != LSQR_OK) return st;
+        }
+        WorklistFill w;
+        if ((st = worklist_check(c, kSegCap, &w)) != LSQR_OK) return st;
+        if (w.state != WorklistFill::OVERFLOWED) return LSQR_OK;
+        (void)fail(c, LSQR_OK, "US fp16 filter: worklist segment overflow (fill %u > %u), fp32 filter used", w.fill, kSegCap);
+        HIPCHK(c, hipMemsetAsync(c->d_votes, 0, c->H * sizeof(uint32_t), c->stream));
+      }
+    }
+  }
+  for (size_t h0 = 0; h0 < c->H; h0 += kScanChunk) {
+    uint32_t hc = (uint32_t)std::min<size_t>(kScanChunk, c->H - h0);
+    ProfScope ps(c, KID_SCAN);
+    if ((st = launch_us_f32<M>(c, 0, c->n, c->d_hparams + h0 * M::SP, c->d_hparams_f32 + h0 * M::SPF, hc, c->d_votes + h0,
+                               nullptr, nullptr, nullptr)) != LSQR_OK)
+      return st;
   }
   return LSQR_OK;
 }
 
+// plane, sphere, line: magnitudes the fp32 copies cannot hold (or NaN) go to the plain fp64 kernel
+static bool f32_magnitudes_ok(const lsqr_ctx *c) { return c->absmax_valid && c->mc.absmax <= 1e15; }
+// two-level scan over the spatial index; auto: built once an upload has seen enough
+// hypotheses to pay for the build (a few HBM passes).  Returns whether this batch scans over the index (built here
+// if need be) and its cell size.
+template <class M>
+bool scan_index_ready(lsqr_ctx *c, uint32_t *cell_pts_out) {
+  typedef typename CellOf<M>::type CM;
+  const bool tuned_defaults = c->opt_filter == 1 && c->opt_ppl == 0;  // A/B knobs untouched
+  // Cost model of the build (auto mode).  Per (hypothesis, observation) the exhaustive filter kernel costs
+  // ~1.9e-13 s and the two-level scan ~0.2e-13 s (10 M points x 4096 hypotheses: 7.6 ms against 0.8 ms);
+  // the build costs ~1.2e-10 s per observation (radix sort + k-d refinement + gather; r03 without the
+  // refinement: 0.7e-10).  It pays for itself once
+  //   hypotheses still to come  >  1.2e-10 / 1.7e-13  ~  700,
+  // and "still to come" is estimated by the larger of what the caller announced (lsqr_ransac: the current
+  // numTries bound) and what this upload has been asked to scan so far, this batch included.
+  constexpr uint64_t kIndexPaysAfter = 768;
+  const uint64_t to_come = std::max<uint64_t>(c->hyp_expected, c->hyp_since_upload);
+  const bool want = c->opt_filter && f32_magnitudes_ok(c) && c->mc.absmax >= 1e-10 && !c->index_failed &&
+                    (c->opt_index == 2 ||
+                     (c->opt_index == 1 && tuned_defaults &&
+                      (c->index_valid || (c->n >= 65536 && to_come >= kIndexPaysAfter))));
+  if (!want) return false;
+  uint32_t cell_pts = c->opt_cell ? (uint32_t)c->opt_cell : (uint32_t)CM::DEFAULT_CELL;
+  if constexpr (!requires { CM::MAX_PP; }) cell_pts = cell_pts > 512 ? 512 : cell_pts;
+  *cell_pts_out = cell_pts;
+  // the k-d levels above the runs: 5 - 12 % fewer surviving pairs for 4.5 ms more per build (10 M records) -- worth
+  // it once an upload has been scanned by "scan_kd_after" hypotheses (what the caller announced does not count
+  // here: the adaptive bound of a RANSAC run starts in the millions and collapses within a few batches)
+  int kd_now = c->opt_refine && c->hyp_since_upload >= (uint64_t)c->opt_kd_after ? c->opt_kd_levels : 0;
+  if constexpr (std::is_same<CM, PlaneCell<3>>::value) {
+    // ... except for the plane's BOUNDED scan: its axis bound (axis.h: k_bound_axis) is tighter on the flat
+    // Morton runs than on the more cubical k-d regions (166 against 207 of 4096 hypotheses reach the exact
+    // count: 0.30 against 0.32 ms), while the full count gains 8 % from the levels.  So a bounded batch never
+    // asks for them (an index that has them keeps them: no rebuilding back and forth), a counting one does.
+    if (CM::USE_BOUND && c->allow_bound && c->opt_bound) kd_now = c->index_kd_levels;
+  }
+  if (!c->index_valid || c->cell_pts != cell_pts || kd_now > c->index_kd_levels) {
+    c->kd_build_levels = kd_now;
+    // the index is an accelerator: if it cannot be built (typically no memory for the sorted
+    // copy) this upload keeps the exhaustive kernels instead of failing the scan
+    if (build_index<M::ND>(c, cell_pts) != LSQR_OK) {
+      (void)hipGetLastError();
+      c->index_failed = true;
+      return false;
+    }
+  }
+  return true;
+}
+// the plane's full count with the batch in key order (cells.h: k_plane_order): similar planes share a 64-group
+template <class M>
+int scan_plane_key_order(lsqr_ctx *c, uint32_t cell_pts) {
+  typedef typename CellOf<M>::type CM;
+  const uint32_t H = (uint32_t)c->H;
+  uint32_t *perm = c->d_sel + kPilots, *cnt = (uint32_t *)(c->d_counter + CNT_FLAG);
+  double *sp_b = c->d_hparams2 + (size_t)kPilots * M::SP;
+  float *spf_b = c->d_hparams2_f32 + (size_t)kPilots * M::SPF;
+  uint32_t *votes_b = c->d_votes2 + kPilots;
+  hipLaunchKernelGGL((k_plane_order<M::SP>), dim3(1), dim3(1024), 0, c->stream, c->d_hparams, H, c->mc.absmax, perm, cnt);
+  hipLaunchKernelGGL(k_gather_rows, dim3((H + 3) / 4), dim3(256), 0, c->stream, perm, cnt, H, c->d_hparams, (int)M::SP,
+                     c->d_hparams_f32, (int)M::SPF, sp_b, spf_b);
+  HIPCHK(c, hipGetLastError());
+  const ScanBatch pb = {sp_b, spf_b, (size_t)H, votes_b, nullptr};
+  int st2 = with_pp<CM>(cell_pts, [&](auto pp) { return run_scan_pairs<CM, decltype(pp)::value>(c, pb); });
+  if (st2 != LSQR_OK) return st2;
+  hipLaunchKernelGGL(k_scatter_perm, dim3((H + 255) / 256), dim3(256), 0, c->stream, perm, H, votes_b, c->d_votes);
+  HIPCHK(c, hipGetLastError());
+  return LSQR_OK;
+}
+// plane, sphere, line over the index: bounded, statically balanced or dynamically tiled
+template <class M>
+int scan_indexed(lsqr_ctx *c, bool *done) {
+  typedef typename CellOf<M>::type CM;
+  uint32_t cell_pts = 0;
+  if (!scan_index_ready<M>(c, &cell_pts)) return LSQR_OK;
+  // one cell per wave tile; several cells per tile and 128-record cells were measured dead ends
+  //  and are no longer instantiated
+  *done = true;
+  c->last_bound[0] = 0;
+  // batch entry points: hypotheses that cannot become the running maximum are not counted (the extra
+  // launches only pay for batches of >= 1024; the selection kernels handle <= 8192)
+  if (CM::USE_BOUND && c->allow_bound && c->opt_bound && c->H >= 1024 && c->H <= kSelCap && c->n_cells > 0)
+    return with_pp<CM>(cell_pts, [&](auto pp) { return run_scan_bounded<CM, decltype(pp)::value>(c); });
+  // plain scans of a large batch: the statically balanced kernel where it measured faster (plane, 10 M x
+  // 4096: 1.13 against 1.24 ms; sphere and line are faster with tiles handed out dynamically);
+  // "scan_pairs" 1 / 2 force one or the other (A/B)
+  bool full_pairs = false;
+  if constexpr (requires { CM::FULL_COUNT_PAIRS; }) full_pairs = c->opt_pairs == 0 && c->H >= 1024;
+  if (c->opt_pairs == 1 || full_pairs) {
+    if constexpr (std::is_same<CM, PlaneCell<3>>::value) {
+      if (c->opt_hyp_order && c->H >= 1024 && c->H <= kOrderCap) return scan_plane_key_order<M>(c, cell_pts);
+    }
+    const ScanBatch b = {c->d_hparams, c->d_hparams_f32, c->H, c->d_votes, nullptr};
+    return with_pp<CM>(cell_pts, [&](auto pp) { return run_scan_pairs<CM, decltype(pp)::value>(c, b); });
+  }
+  return with_pp<CM>(cell_pts, [&](auto pp) { return run_scan_cells<CM, decltype(pp)::value, 1>(c); });
+}
+// plane, sphere, line: fp32 pre-filter + exact re-evaluation
+template <class M>
+int scan_f32(lsqr_ctx *c, bool *done) {
+  if (!(c->opt_filter && f32_magnitudes_ok(c))) return LSQR_OK;
+  *done = true;
+  int ppl = c->opt_ppl ? c->opt_ppl : 4;  // measured best (tools/ab_scan.py)
+  // re-check granularity: per packed pair (line: wide band, ambiguous tiles are common) or per
+  // tile; scan_filter 2 / 3 force one or the other for A/B runs
+  const bool pair = c->opt_filter == 2 || (c->opt_filter == 1 && M::FGRAN == 1);
+  if (pair) {
+    if (ppl == 8) return run_scan_f32<M, 8, 1>(c);
+    return run_scan_f32<M, 4, 1>(c);
+  }
+  if (ppl == 8) return run_scan_f32<M, 8>(c);
+  if (ppl == 16) return run_scan_f32<M, 16>(c);
+  return run_scan_f32<M, 4>(c);
+}
+// the exact kernels: every model, every magnitude
+template <class M>
+int scan_exact(lsqr_ctx *c) {
+  if constexpr (M::REC <= 3) {  // point models: PPL is tunable
+    int ppl = c->opt_ppl ? c->opt_ppl : 8;
+    if (ppl == 2) return run_scan_ppl<M, 2>(c);
+    if (ppl == 8) return run_scan_ppl<M, 8>(c);
+    return run_scan_ppl<M, 4>(c);
+  } else {
+    return run_scan_ppl<M, M::PPL>(c);
+  }
+}
+
+// the votes of the current batch: the first family that takes the batch (model, options, magnitudes) counts it
 int run_scan(lsqr_ctx *c) {
   c->hyp_since_upload += c->H;
   c->ee_last = false;
   return dispatch(c->cfg, [&](auto tag) -> int {
     typedef typename decltype(tag)::type M;
-    if constexpr (M::IS_DENSE) {  // default: MFMA filter + exact recheck of ambiguous pairs
-      if (c->opt_filter) {
-        int st = ensure_absmax(c);
-        if (st != LSQR_OK) return st;
-        if (!c->d_amb) HIPCHK(c, hipMalloc((void **)&c->d_amb, sizeof(unsigned long long) * kAmbCap));
-        if (c->mc.absmax <= 1e100) {  // finite, sane magnitudes: the filter's bound applies
-          if constexpr (M::NR == 64) {
-            // batch entry points: chunked early exit (earlyexit.h) -- hypotheses that can no longer become the running
-            // maximum stop being counted
-            if (c->allow_bound && c->opt_bound && c->opt_dense_f32 && c->H >= 128 &&
-                c->H <= kEeCap && c->n >= 65536 && c->mc.absmax < 1e15) {
-              bool done = false;
-              if ((st = run_scan_dense_ee(c, &done)) != LSQR_OK) return st;
-              if (done) return LSQR_OK;
-            }
-          }
-          HIPCHK(c, hipMemsetAsync(c->d_votes, 0, c->H * sizeof(uint32_t), c->stream));
-          HIPCHK(c, hipMemsetAsync(c->d_counter + CNT_OVF, 0, sizeof(unsigned long long), c->stream));
-          double *d_thr = c->d_partials;  // scratch: 2 doubles per hypothesis (H <= 2^20 checked)
-          if (c->H * 2 > (size_t)kDenseBlocks * 2160) return fail(c, LSQR_ERR_INVALID, "batch too large");
-          size_t tiles = (c->n + 63) / 64;
-          size_t nblk = std::min<size_t>(tiles, 768);  // 3 workgroups per CU
-          size_t rpb = (tiles + nblk - 1) / nblk * 64;
-          nblk = (c->n + rpb - 1) / rpb;
-          if constexpr (M::NR == 64) {
-            // default at n > 32: the filter in fp32 on the matrix cores (twice the fp64 MFMA rate); its band holds
-            // ~1e-4 of the pairs, decided exactly from a per-workgroup worklist.  A segment overflow (not seen)
-            // falls through to the fp64 filter below.
-            if (c->opt_dense_f32 && c->H <= 8192 && c->mc.absmax < 1e15) {
-              const uint32_t seg_cap = kAmbCap / 1024;  // <= 512 segments
-              {  // two waves per SIMD (the A fragments live in registers): exactly two workgroups per CU
-                size_t nb2 = std::min<size_t>(tiles, 512);
-                rpb = (tiles + nb2 - 1) / nb2 * 64;
-                nblk = (c->n + rpb - 1) / rpb;
-              }
-              float *d_thr32 = (float *)c->d_partials;                        // 2 floats per hypothesis
-              float *d_sp32 = (float *)c->d_partials + 2 * 8192;              // 64 floats per hypothesis (2 MB)
-              unsigned int *d_segcnt = (unsigned int *)((float *)c->d_partials + 2 * 8192 + 64 * 8192);  // 1024 words
-              HIPCHK(c, hipMemsetAsync(d_segcnt, 0, 1024 * sizeof(unsigned int), c->stream));
-              bool h16 = false;
-              if (c->opt_dense_f32 == 2 && (st = ensure_dense_h16(c, &h16)) != LSQR_OK) return st;
-              if (h16) {  // fp16 matrix cores on two-way splits (dense_h16.h)
-                ProfScope ps(c, KID_SCAN);
-                hipLaunchKernelGGL(k_dense_prep_h16, dim3((unsigned)((c->H + 3) / 4)), dim3(256), 0, c->stream,
-                                   c->d_hparams, (uint32_t)c->H, (int)c->cfg.dim, 64, c->mc.delta, c->mc.absmax_rot,
-                                   c->mc.absmax, c->h16_pa, (_Float16 *)d_sp32, c->d_h16_thr);
-                HIPCHK(c, hipGetLastError());
-                size_t nb16 = 0;
-                if ((st = launch_dense_h16(c, 0, c->n, (const _Float16 *)d_sp32, c->d_h16_thr, (uint32_t)c->H, d_segcnt,
-                                           seg_cap, nullptr, nullptr, nullptr, &nb16)) != LSQR_OK)
-                  return st;
-                hipLaunchKernelGGL((k_dense_recheck_seg<64>), dim3((unsigned)nb16), dim3(256), 0, c->stream, c->d_data,
-                                   c->stride, c->d_hparams, c->mc, c->d_amb, d_segcnt, seg_cap, c->d_votes,
-                                   (unsigned int *)(c->d_counter + CNT_OVF));
-                HIPCHK(c, hipGetLastError());
-              } else {
-                ProfScope ps(c, KID_SCAN);
-                hipLaunchKernelGGL(k_dense_thresholds32, dim3((unsigned)((c->H + 255) / 256)), dim3(256), 0, c->stream,
-                                   c->d_hparams, (uint32_t)c->H, (int)c->cfg.dim, 64, c->mc.delta, c->mc.absmax_rot,
-                                   c->mc.absmax, d_thr32, d_sp32);
-                HIPCHK(c, hipGetLastError());
-                {  // hypothesis fragments prefetched through an LDS ring (dense.h)
-                  constexpr size_t kRingChunk = 1024;  // 62.7 KiB of LDS per workgroup: two per CU
-                  for (size_t h0 = 0; h0 < c->H; h0 += kRingChunk) {
-                    uint32_t hc = (uint32_t)std::min<size_t>(kRingChunk, c->H - h0);
-                    const uint32_t nhb2 = (((hc + 63) / 64) + 1) & ~1u;
-                    size_t lds = sizeof(float) * (8192 + 64 * kDmPitch32 + 64 + 128 * nhb2) + sizeof(uint32_t) * (hc + 1);
-                    hipLaunchKernelGGL((k_scan_dense_mfma32r<64>), dim3((unsigned)nblk), dim3(256), lds, c->stream,
-                                       c->d_data, c->stride, (size_t)0, c->n, rpb, d_sp32 + h0 * 64, d_thr32 + 2 * h0, hc,
-                                       (int)c->cfg.dim, c->d_votes, c->d_amb, d_segcnt, seg_cap, (uint32_t)h0,
-                                       (const uint32_t *)nullptr, (const uint32_t *)nullptr, (const uint32_t *)nullptr);
-                    HIPCHK(c, hipGetLastError());
-                  }
-                }
-                hipLaunchKernelGGL((k_dense_recheck_seg<64>), dim3((unsigned)nblk), dim3(256), 0, c->stream, c->d_data,
-                                   c->stride, c->d_hparams, c->mc, c->d_amb, d_segcnt, seg_cap, c->d_votes,
-                                   (unsigned int *)(c->d_counter + CNT_OVF));
-                HIPCHK(c, hipGetLastError());
-              }
-              if (c->defer_ovf) {
-                c->ovf_cap = seg_cap;
-                return LSQR_OK;
-              }
-              HIPCHK(c, hipMemcpyAsync(c->h_pin->scratch, c->d_counter + CNT_OVF, sizeof(unsigned long long), hipMemcpyDeviceToHost,
-                                       c->stream));
-              HIPCHK(c, sync_stream(c));
-              c->dense_amb_max = *(unsigned int *)c->h_pin->scratch;
-              dense_worklist_debug(c, d_segcnt, seg_cap);
-              if (c->dense_amb_max <= seg_cap) return LSQR_OK;
-              (void)fail(c, LSQR_OK, "dense fp16 / fp32 filter: worklist segment overflow (fill %u > %u), fp64 filter used",
-                         c->dense_amb_max, seg_cap);
-              HIPCHK(c, hipMemsetAsync(c->d_votes, 0, c->H * sizeof(uint32_t), c->stream));   // overflow: fp64 filter
-              HIPCHK(c, hipMemsetAsync(c->d_counter + CNT_OVF, 0, sizeof(unsigned long long), c->stream));
-            }
-          }
-          {
-            ProfScope ps(c, KID_SCAN);
-            hipLaunchKernelGGL(k_dense_thresholds, dim3((unsigned)((c->H + 255) / 256)), dim3(256), 0,
-                               c->stream, c->d_hparams, (uint32_t)c->H, (int)c->cfg.dim, (int)M::NR,
-                               c->mc.delta, c->mc.absmax, d_thr);
-            HIPCHK(c, hipGetLastError());
-            for (size_t h0 = 0; h0 < c->H; h0 += kDmHypChunk) {
-              uint32_t hc = (uint32_t)std::min<size_t>(kDmHypChunk, c->H - h0);
-              if constexpr (M::NR == 64) {
-                {  // n = 64: B fragments in registers, no barriers per block
-                  size_t lds2 = sizeof(double) * (64 * kDmPitch + 64) + sizeof(uint32_t) * hc;
-                  hipLaunchKernelGGL((k_scan_dense_mfma2<64>), dim3((unsigned)nblk), dim3(256), lds2,
-                                     c->stream, c->d_data, c->stride, c->n, rpb,
-                                     c->d_hparams + h0 * M::NR, d_thr + 2 * h0, hc, (int)c->cfg.dim,
-                                     c->d_votes + h0, c->d_amb, (unsigned int *)(c->d_counter + CNT_OVF),
-                                     (uint32_t)h0);
-                  HIPCHK(c, hipGetLastError());
-                  continue;
-                }
-              }
-              size_t lds = sizeof(double) * (2 * 64 * kDmPitch + 3 * 64) + sizeof(uint32_t) * hc;
-              hipLaunchKernelGGL((k_scan_dense_mfma<M::NR>), dim3((unsigned)nblk), dim3(256), lds,
-                                 c->stream, c->d_data, c->stride, c->n, rpb,
-                                 c->d_hparams + h0 * M::NR, d_thr + 2 * h0, hc, (int)c->cfg.dim,
-                                 c->d_votes + h0, c->d_amb, (unsigned int *)(c->d_counter + CNT_OVF),
-                                 (uint32_t)h0);
-              HIPCHK(c, hipGetLastError());
-            }
-            hipLaunchKernelGGL((k_dense_recheck<M::NR>), dim3(64), dim3(256), 0, c->stream, c->d_data,
-                               c->stride, c->d_hparams, c->mc, c->d_amb,
-                               (const unsigned int *)(c->d_counter + CNT_OVF), c->d_votes);
-            HIPCHK(c, hipGetLastError());
-          }
-          // worklist overflow (never seen: ~1e-13 of the pairs are ambiguous) -> exact kernel
-          if (c->defer_ovf) {
-            c->ovf_cap = kAmbCap;
-            return LSQR_OK;
-          }
-          HIPCHK(c, hipMemcpyAsync(c->h_pin->scratch, c->d_counter + CNT_OVF, sizeof(unsigned long long),
-                                   hipMemcpyDeviceToHost, c->stream));
-          HIPCHK(c, sync_stream(c));
-          if (*(unsigned int *)c->h_pin->scratch <= kAmbCap) return LSQR_OK;
-        }
-      }
+    bool done = false;
+    int st = LSQR_OK;
+    if constexpr (M::IS_DENSE) st = scan_dense<M>(c, &done);
+    if (st != LSQR_OK || done) return st;
+    if constexpr (requires { M::NF32; }) {
+      st = scan_us<M>(c, &done);
+    } else if constexpr (requires { M::SPF; }) {
+      if constexpr (requires { typename CellOf<M>::type; }) st = scan_indexed<M>(c, &done);
+      if (st == LSQR_OK && !done) st = scan_f32<M>(c, &done);
     }
-    if constexpr (requires { M::NF32; }) {  // packed fp32 pre-filter (scan_filter 1); US: 2 = the fused fp64 filter
-      if (c->opt_filter == 1 && c->absmax_valid && c->mc.absmax <= 1e15) {
-        c->ee_last = false;
-        if (c->allow_bound && c->opt_bound && c->H >= 256 && c->H <= kEeCap && c->n >= 65536)
-          return run_scan_us_ee<M>(c);  // batch entry points: chunked early exit (earlyexit.h)
-        const int np = c->opt_ppl == 2 ? 1 : 2;  // pairs of frames per lane (scan_ppl 2 / 4)
-        HIPCHK(c, hipMemsetAsync(c->d_votes, 0, c->H * sizeof(uint32_t), c->stream));
-        if constexpr (kHasUsH16<M>) {
-          if (c->opt_us_h16 && c->H >= 32 && c->H <= 8192 && c->n >= 4096) {  // fp16 matrix cores (us_h16.h)
-            bool h16 = false;
-            int st = ensure_us_h16<M>(c, &h16);
-            if (st != LSQR_OK) return st;
-            if (h16) {
-              unsigned int *d_segcnt = (unsigned int *)((float *)c->d_partials + 2 * 8192 + 64 * 8192);
-              const uint32_t seg_cap = kAmbCap / 1024;
-              HIPCHK(c, hipMemsetAsync(d_segcnt, 0, 1024 * sizeof(unsigned int), c->stream));
-              HIPCHK(c, hipMemsetAsync(c->d_counter + CNT_OVF, 0, sizeof(unsigned long long), c->stream));
-              {
-                ProfScope ps(c, KID_SCAN);
-                if ((st = launch_us_h16<M>(c, 0, c->n, c->d_hparams, (uint32_t)c->H, d_segcnt, seg_cap, nullptr, nullptr,
-                                           nullptr)) != LSQR_OK)
-                  return st;
-              }
-              if (c->defer_ovf) {
-                c->ovf_cap = seg_cap;
-                return LSQR_OK;
-              }
-              HIPCHK(c, hipMemcpyAsync(c->h_pin->scratch, c->d_counter + CNT_OVF, sizeof(unsigned long long), hipMemcpyDeviceToHost,
-                                       c->stream));
-              HIPCHK(c, sync_stream(c));
-              if (*(unsigned int *)c->h_pin->scratch <= seg_cap) return LSQR_OK;
-              (void)fail(c, LSQR_OK, "US fp16 filter: worklist segment overflow (fill %u > %u), fp32 filter used",
-                         *(unsigned int *)c->h_pin->scratch, seg_cap);
-              HIPCHK(c, hipMemsetAsync(c->d_votes, 0, c->H * sizeof(uint32_t), c->stream));
-            }
-          }
-        }
-        size_t tiles = (c->n + (size_t)kBlock * 2 * np - 1) / ((size_t)kBlock * 2 * np);
-        for (size_t h0 = 0; h0 < c->H; h0 += kScanChunk) {
-          uint32_t hc = (uint32_t)std::min<size_t>(kScanChunk, c->H - h0);
-          size_t lds = (size_t)hc * sizeof(uint32_t);
-          int per_cu = (int)std::min<size_t>(8, (160 * 1024) / std::max<size_t>(lds, 1));
-          if (per_cu < 1) per_cu = 1;
-          size_t max_blocks = (size_t)256 * per_cu;
-          size_t tpb = (tiles + max_blocks - 1) / max_blocks;
-          int grid = (int)((tiles + tpb - 1) / tpb);
-          // few tiles (1 M frames = 977): split the hypothesis range over blockIdx.y to fill the chip
-          unsigned ysplit = (unsigned)std::min<size_t>(std::max<size_t>(1, (size_t)256 * 5 / (size_t)grid),
-                                                       std::max<size_t>(1, hc / 256));
-          if (c->opt_hsplit > 0) ysplit = (unsigned)c->opt_hsplit;
-          ProfScope ps(c, KID_SCAN);
-          if (np == 1)
-            hipLaunchKernelGGL((k_scan_us_f32<M, 1>), dim3(grid, ysplit), dim3(kBlock), lds, c->stream,
-                               c->d_data, c->stride, (size_t)0, c->n, c->d_hparams + h0 * M::SP,
-                               c->d_hparams_f32 + h0 * M::SPF, hc, c->mc, c->d_votes + h0, (const uint32_t *)nullptr,
-                               (const uint32_t *)nullptr, (const uint32_t *)nullptr);
-          else
-            hipLaunchKernelGGL((k_scan_us_f32<M, 2>), dim3(grid, ysplit), dim3(kBlock), lds, c->stream,
-                               c->d_data, c->stride, (size_t)0, c->n, c->d_hparams + h0 * M::SP,
-                               c->d_hparams_f32 + h0 * M::SPF, hc, c->mc, c->d_votes + h0, (const uint32_t *)nullptr,
-                               (const uint32_t *)nullptr, (const uint32_t *)nullptr);
-          HIPCHK(c, hipGetLastError());
-        }
-        return LSQR_OK;
-      }
-    } else if constexpr (requires { M::SPF; }) {  // plane, sphere, line: fp32 pre-filter + exact re-evaluation
-      // magnitudes the fp32 copies cannot hold (or NaN): the plain fp64 kernel below
-      const bool f32_ok = c->absmax_valid && c->mc.absmax <= 1e15;
-      if constexpr (requires { typename CellOf<M>::type; }) {
-        typedef typename CellOf<M>::type CM;
-        // two-level scan over the spatial index; auto: built once an upload has seen enough
-        // hypotheses to pay for the build (a few HBM passes)
-        const bool tuned_defaults = c->opt_filter == 1 && c->opt_ppl == 0;  // A/B knobs untouched
-        // Cost model of the build (auto mode).  Per (hypothesis, observation) the exhaustive filter kernel costs
-        // ~1.9e-13 s and the two-level scan ~0.2e-13 s (10 M points x 4096 hypotheses: 7.6 ms against 0.8 ms);
-        // the build costs ~1.2e-10 s per observation (radix sort + k-d refinement + gather; r03 without the
-        // refinement: 0.7e-10).  It pays for itself once
-        //   hypotheses still to come  >  1.2e-10 / 1.7e-13  ~  700,
-        // and "still to come" is estimated by the larger of what the caller announced (lsqr_ransac: the current
-        // numTries bound) and what this upload has been asked to scan so far, this batch included.
-        constexpr uint64_t kIndexPaysAfter = 768;
-        const uint64_t to_come = std::max<uint64_t>(c->hyp_expected, c->hyp_since_upload);
-        const bool want = c->opt_filter && f32_ok && c->mc.absmax >= 1e-10 && !c->index_failed &&
-                          (c->opt_index == 2 ||
-                           (c->opt_index == 1 && tuned_defaults &&
-                            (c->index_valid || (c->n >= 65536 && to_come >= kIndexPaysAfter))));
-        if (want) {
-          uint32_t cell_pts = c->opt_cell ? (uint32_t)c->opt_cell : (uint32_t)CM::DEFAULT_CELL;
-          if constexpr (!requires { CM::MAX_PP; }) cell_pts = cell_pts > 512 ? 512 : cell_pts;
-          bool usable = true;
-          // the k-d levels above the runs: 5 - 12 % fewer surviving pairs for 4.5 ms more per build (10 M records) -- worth
-          // it once an upload has been scanned by "scan_kd_after" hypotheses (what the caller announced does not count
-          // here: the adaptive bound of a RANSAC run starts in the millions and collapses within a few batches)
-          int kd_now = c->opt_refine && c->hyp_since_upload >= (uint64_t)c->opt_kd_after ? c->opt_kd_levels : 0;
-          if constexpr (std::is_same<CM, PlaneCell<3>>::value) {
-            // ... except for the plane's BOUNDED scan: its axis bound (axis.h: k_bound_axis) is tighter on the flat
-            // Morton runs than on the more cubical k-d regions (166 against 207 of 4096 hypotheses reach the exact
-            // count: 0.30 against 0.32 ms), while the full count gains 8 % from the levels.  So a bounded batch never
-            // asks for them (an index that has them keeps them: no rebuilding back and forth), a counting one does.
-            if (CM::USE_BOUND && c->allow_bound && c->opt_bound) kd_now = c->index_kd_levels;
-          }
-          if (!c->index_valid || c->cell_pts != cell_pts || kd_now > c->index_kd_levels) {
-            c->kd_build_levels = kd_now;
-            // the index is an accelerator: if it cannot be built (typically no memory for the sorted
-            // copy) this upload keeps the exhaustive kernels instead of failing the scan
-            if (build_index<M::ND>(c, cell_pts) != LSQR_OK) {
-              (void)hipGetLastError();
-              c->index_failed = true;
-              usable = false;
-            }
-          }
-          // one cell per wave tile; several cells per tile and 128-record cells were measured dead ends
-          //  and are no longer instantiated
-          if (usable) {
-            c->last_bound[0] = 0;
-            // batch entry points: hypotheses that cannot become the running maximum are not counted (the extra
-            // launches only pay for batches of >= 1024; the selection kernels handle <= 8192)
-            if (CM::USE_BOUND && c->allow_bound && c->opt_bound && c->H >= 1024 && c->H <= kSelCap && c->n_cells > 0) {
-              return with_pp<CM>(cell_pts, [&](auto pp) { return run_scan_bounded<CM, decltype(pp)::value>(c); });
-            }
-            // plain scans of a large batch: the statically balanced kernel where it measured faster (plane, 10 M x
-            // 4096: 1.13 against 1.24 ms; sphere and line are faster with tiles handed out dynamically);
-            // "scan_pairs" 1 / 2 force one or the other (A/B)
-            bool full_pairs = false;
-            if constexpr (requires { CM::FULL_COUNT_PAIRS; }) full_pairs = c->opt_pairs == 0 && c->H >= 1024;
-            if (c->opt_pairs == 1 || full_pairs) {
-              if constexpr (std::is_same<CM, PlaneCell<3>>::value) {
-                // the batch in key order (cells.h: k_plane_order): similar planes share a 64-group
-                if (c->opt_hyp_order && c->H >= 1024 && c->H <= kOrderCap) {
-                  const uint32_t H = (uint32_t)c->H;
-                  uint32_t *perm = c->d_sel + kPilots, *cnt = (uint32_t *)(c->d_counter + CNT_FLAG);
-                  double *sp_b = c->d_hparams2 + (size_t)kPilots * M::SP;
-                  float *spf_b = c->d_hparams2_f32 + (size_t)kPilots * M::SPF;
-                  uint32_t *votes_b = c->d_votes2 + kPilots;
-                  hipLaunchKernelGGL((k_plane_order<M::SP>), dim3(1), dim3(1024), 0, c->stream, c->d_hparams, H,
-                                     c->mc.absmax, perm, cnt);
-                  hipLaunchKernelGGL(k_gather_rows, dim3((H + 3) / 4), dim3(256), 0, c->stream, perm, cnt, H,
-                                     c->d_hparams, (int)M::SP, c->d_hparams_f32, (int)M::SPF, sp_b, spf_b);
-                  HIPCHK(c, hipGetLastError());
-                  const ScanBatch pb = {sp_b, spf_b, (size_t)H, votes_b, nullptr};
-                  int st2 = with_pp<CM>(cell_pts,
-                                        [&](auto pp) { return run_scan_pairs<CM, decltype(pp)::value>(c, pb); });
-                  if (st2 != LSQR_OK) return st2;
-                  hipLaunchKernelGGL(k_scatter_perm, dim3((H + 255) / 256), dim3(256), 0, c->stream, perm, H, votes_b,
-                                     c->d_votes);
-                  HIPCHK(c, hipGetLastError());
-                  return LSQR_OK;
-                }
-              }
-              const ScanBatch b = {c->d_hparams, c->d_hparams_f32, c->H, c->d_votes, nullptr};
-              return with_pp<CM>(cell_pts, [&](auto pp) { return run_scan_pairs<CM, decltype(pp)::value>(c, b); });
-            }
-            return with_pp<CM>(cell_pts, [&](auto pp) { return run_scan_cells<CM, decltype(pp)::value, 1>(c); });
-          }
-        }
-      }
-      if (c->opt_filter && f32_ok) {
-        int ppl = c->opt_ppl ? c->opt_ppl : 4;  // measured best (tools/ab_scan.py)
-        // re-check granularity: per packed pair (line: wide band, ambiguous tiles are common) or per
-        // tile; scan_filter 2 / 3 force one or the other for A/B runs
-        const bool pair = c->opt_filter == 2 || (c->opt_filter == 1 && M::FGRAN == 1);
-        if (pair) {
-          if (ppl == 8) return run_scan_f32<M, 8, 1>(c);
-          return run_scan_f32<M, 4, 1>(c);
-        }
-        if (ppl == 8) return run_scan_f32<M, 8>(c);
-        if (ppl == 16) return run_scan_f32<M, 16>(c);
-        return run_scan_f32<M, 4>(c);
-      }
-    }
-    if constexpr (M::REC <= 3) {  // point models: PPL is tunable
-      int ppl = c->opt_ppl ? c->opt_ppl : 8;
-      if (ppl == 2) return run_scan_ppl<M, 2>(c);
-      if (ppl == 8) return run_scan_ppl<M, 8>(c);
-      return run_scan_ppl<M, 4>(c);
-    } else {
-      return run_scan_ppl<M, M::PPL>(c);
-    }
+    if (st != LSQR_OK || done) return st;
+    return scan_exact<M>(c);
   });
 }
 
@@ -3029,7 +3028,7 @@ int lsqr_ctx_create(int device, lsqr_ctx **out) {
   c->device = device;
   bool ok = hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking) == hipSuccess &&
             hipEventCreate(&c->ev0) == hipSuccess && hipEventCreate(&c->ev1) == hipSuccess &&
-            hipMalloc((void **)&c->d_partials, sizeof(double) * 2 * kDenseBlocks * 2160) == hipSuccess &&
+            hipMalloc((void **)&c->d_partials, kPartialsBytes) == hipSuccess &&
             hipMalloc((void **)&c->d_mom, sizeof(double) * 4096) == hipSuccess &&
             hipMalloc((void **)&c->d_vec, sizeof(double) * 128) == hipSuccess &&
             hipMalloc((void **)&c->d_par, sizeof(double) * 128) == hipSuccess &&
@@ -5284,7 +5283,7 @@ static int set_option_one(lsqr_ctx *c, const char *name, int value) {
     c->opt_phantom_fast = (int)std::max<long long>(0, value);
     return LSQR_OK;
   }
-  if (!strcmp(name, "scan_test_overflow")) {  // tests: the deferred worklist check of lsqr_batch_fit_wait fires
+  if (!strcmp(name, "scan_test_overflow")) {  // tests: every worklist check answers "overflowed" (worklist_check, lsqr_batch_fit_wait)
     c->opt_test_overflow = value != 0;
     return LSQR_OK;
   }

@@ -1,7 +1,9 @@
 """lsqr_batch_fit_enqueue must return without waiting for the device (include/lsqr_hip.h): the matrix-core filters of
 the dense / US / plane-phantom scans note the size of their worklist segments instead of reading the fill back, the fill
 travels with the slot's record, and lsqr_batch_fit_wait runs the batch again on the exact kernels if a segment ever
-overflowed (the scan had become blocking).  `scan_test_overflow` makes the wait take that path."""
+overflowed (the scan had become blocking).  `scan_test_overflow` makes every worklist check answer
+"overflowed": here the wait takes that path (its blocking rerun runs without the filter and meets no check); the
+blocking scans' own fallbacks are in test_gpu_scan_fallbacks.py."""
 import time
 
 import numpy as np
