@@ -277,6 +277,51 @@ LSQR_API int lsqr_ransac_sequential(lsqr_ctx *ctx, double p, const uint64_t *see
                                     int32_t *labels_out /* nullable: N entries, upload order */,
                                     lsqr_ransac_info *infos /* max_models */, int32_t *status_out /* max_models */,
                                     size_t *n_models_out);
+/* Sequential RANSAC over many independent problems in one call: lsqr_ransac_sequential's loop for every record set of
+ * an lsqr_ransac_many upload.  Problem j is records [offsets[j], offsets[j+1]) of host_records (laid out as for
+ * lsqr_ransac_many) and is decided exactly as lsqr_ransac_sequential(ctx2, p, seeds + j * max_models, max_models,
+ * min_votes, ...) decides it on a fresh context ctx2, with the same model and options, that holds those records alone.
+ *   Rounds: round r of problem j is the lsqr_ransac decision with seed seeds[j * max_models + r] on the records of j no
+ *     earlier round claimed, in their original order.  It is accepted when it is LSQR_OK with best_votes >=
+ *     max(min_votes, 1) and then claims its consensus set.  The first round that is not accepted is the problem's last:
+ *     infos[j * max_models + r], status_out[j * max_models + r] and row j * max_models + r of params_out
+ *     (lsqr_num_params doubles; written where the status is LSQR_OK) are still written, and it claims nothing.
+ *     n_models_out[j]: the accepted rounds of problem j.
+ *   Rounds that did not run: before the first round every status_out entry is set to LSQR_ERR_STATE and every infos
+ *     entry is zeroed.  A round does not run when r == max_models or when fewer than lsqr_min_subset records of the
+ *     problem remain.  A problem that starts with fewer than lsqr_min_subset records, zero included, runs no round:
+ *     n_models_out[j] = 0, its labels are -1, and the other problems are unaffected.
+ *   labels_out (nullable, offsets[n_problems] entries in the caller's record order): the round that claimed the
+ *     record, else -1; copied to the host once, at the end.  infos[j][r].fraction is votes / the records of j that
+ *     remained in round r; best_index and the fit origin of the first-record models refer to problem j's compacted
+ *     records, as in lsqr_ransac_sequential.
+ *   Models, taken from the context's lsqr_set_model: every model lsqr_ransac_many, lsqr_ransac_many_lm (the geometric
+ *     sphere: every round ends in the batched Levenberg-Marquardt stage) or lsqr_ransac_many_dense accepts; a round is
+ *     one job of the run those entry points use, on the survivors.  LSQR_MODEL_US_SINGLE, LSQR_MODEL_US_POINTER and
+ *     LSQR_MODEL_PHANTOM return LSQR_ERR_INVALID and write nothing.  Records wider than 18 doubles (the dense system
+ *     with dim > 17) and more than 2^32 - 16 records in all are refused with LSQR_ERR_INVALID, nothing written, as
+ *     lsqr_ransac_sequential refuses them.
+ *   Argument errors (LSQR_ERR_INVALID, nothing written) and the n_problems == 0 no-op are lsqr_ransac_many's; in
+ *     addition, with max_models > 0, a null seeds, params_out, infos, status_out or n_models_out.  max_models == 0
+ *     returns LSQR_OK and zeroes n_models_out (where given).  A null context is refused before anything is touched.
+ *   Per round and problem, against that lsqr_ransac_sequential call: bit-identical n_models, status, iterations,
+ *     best_index, best_votes, fraction, n_params, fit.n_used and labels; parameters and fit.cost up to the fp64
+ *     summation order of the final fit; the LM fields as lsqr_ransac_many_lm states them.  The options
+ *     "max_iterations" and the 2^22 no-model stop apply per problem and per round.
+ *   Independence: problem j's results, parameters and labels included, are bit-identical whichever other problems
+ *     share the call, in whatever order, and however "many_round_hypotheses" cuts the rounds.
+ *   The records are uploaded once; between two rounds the unclaimed records of the problems that go on are compacted
+ *     on the device (csrc/many_sequential.h), and the consensus bytes never cross to the host.  The context's own
+ *     upload, hypotheses and mask are not touched; the work runs on the context's stream (lsqr_set_stream). */
+LSQR_API int lsqr_ransac_many_sequential(lsqr_ctx *ctx, const void *host_records, size_t stride_bytes,
+                                         const uint64_t *offsets /* n_problems + 1 */, size_t n_problems, double p,
+                                         const uint64_t *seeds /* n_problems * max_models, seeds[j * max_models + r] */,
+                                         size_t max_models, uint64_t min_votes,
+                                         double *params_out /* n_problems * max_models * lsqr_num_params */,
+                                         int32_t *labels_out /* nullable: offsets[n_problems] entries, record order */,
+                                         lsqr_ransac_info *infos /* n_problems * max_models */,
+                                         int32_t *status_out /* n_problems * max_models */,
+                                         size_t *n_models_out /* n_problems */);
 /* Many independent RANSAC<T,S>::compute() problems (probabilistic overload, RANSAC.h:75-79) in one call.
  * Problem j is records [offsets[j], offsets[j+1]) of host_records (stride_bytes apart, laid out as for
  * lsqr_upload), walks sampler stream seeds[j] and is decided exactly as lsqr_ransac(ctx, p, seeds[j], NULL, 0, ...)

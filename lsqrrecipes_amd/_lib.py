@@ -103,6 +103,9 @@ SIGNATURES = {
                               C.c_void_p, C.POINTER(RansacInfo)]),
     "lsqr_ransac_sequential": (C.c_int, [_ctx, C.c_double, C.c_void_p, C.c_size_t, C.c_uint64, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t)]),
+    "lsqr_ransac_many_sequential": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_double,
+                                              C.c_void_p, C.c_size_t, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p]),
     "lsqr_ransac_many": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_double, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lsqr_ransac_many_lm": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_double, C.c_void_p,

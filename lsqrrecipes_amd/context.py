@@ -301,6 +301,47 @@ class Context:
         consensus (flat, aligned with offsets; None unless want_consensus) and offsets."""
         return self._ransac_many(self._lib.lsqr_ransac_many, problems, p, seeds, want_consensus)
 
+    def ransac_many_sequential(self, problems, p, max_models, seeds=None, min_votes=0, want_labels=True):
+        """Sequential RANSAC over many independent problems in one call (lsqr_ransac_many_sequential): one upload,
+        every round one batched search over the problems still going, their unclaimed records compacted on the device
+        in between.  problems as for ransac_many; every model ransac_many, ransac_many_lm or ransac_many_dense takes.
+        seeds: (n, max_models), default 1 + j * max_models + r.  Problem j is decided as upload(problem j) +
+        ransac_sequential(p, max_models, seeds[j], min_votes).  -> dict: n_models (n,); status and the keys of
+        ransac_sequential per round, (n, max_models) (ERR_STATE / zeros for a round that did not run); params
+        (n, max_models, P), zero where status is not OK; labels (flat int32, aligned with offsets: the round that
+        claimed the record, else -1; None unless want_labels) and offsets."""
+        m = int(max_models)
+        if m < 0:
+            raise ValueError("max_models must not be negative")
+        recs, offs = self._many_records(problems)
+        n = len(offs) - 1
+        if seeds is None:
+            seeds = 1 + np.arange(n * m, dtype=np.uint64).reshape(n, m)
+        seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
+        if seeds.shape != (n, m):
+            raise ValueError("one seed per problem and model")
+        total = int(offs[-1]) if n else 0
+        params = np.zeros((max(n * m, 1), self.P))
+        labels = np.full(max(total, 1), -1, dtype=np.int32) if want_labels else None
+        infos = (L.RansacInfo * max(n * m, 1))()
+        status = np.full(max(n * m, 1), L.ERR_STATE, dtype=np.int32)
+        n_models = np.zeros(max(n, 1), dtype=np.uintp)
+        self._chk(self._lib.lsqr_ransac_many_sequential(self._h, L.ptr(recs), self.ND * 8, L.ptr(offs), n, float(p),
+                                                        L.ptr(seeds), m, int(min_votes), L.ptr(params), L.ptr(labels),
+                                                        infos, L.ptr(status), L.ptr(n_models)))
+        status = status[:n * m].reshape(n, m)
+        params = params[:n * m].reshape(n, m, self.P)
+        params[status != L.OK] = 0.0
+        inf = np.ctypeslib.as_array(infos)[:n * m]
+        f = lambda name: inf[name].reshape(n, m).copy()
+        fit = inf["fit"]
+        g = lambda name: fit[name].reshape(n, m).copy()
+        return dict(n_models=n_models[:n].astype(np.int64), params=params,
+                    labels=labels[:total] if labels is not None else None, status=status, fraction=f("fraction"),
+                    iterations=f("iterations"), best_index=f("best_index"), best_votes=f("best_votes"),
+                    evaluated=f("evaluated"), n_params=f("n_params"), n_used=g("n_used"), lm_info=g("lm_info"),
+                    lm_nfev=g("lm_nfev"), cost=g("cost"), offsets=offs)
+
     def _many_records(self, problems):
         if self.cfg is None:
             raise L.LsqrError(L.ERR_STATE, "set_model has not been called")

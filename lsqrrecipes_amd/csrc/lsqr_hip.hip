@@ -41,6 +41,7 @@
 #include "many_dense.h"
 #include "many_exhaustive.h"
 #include "sequential.h"
+#include "many_sequential.h"
 
 #include <condition_variable>
 #include <mutex>
@@ -4201,6 +4202,47 @@ int lsqr_ransac_many_exhaustive(lsqr_ctx *c, const void *host_records, size_t st
         typedef typename decltype(tag)::type M;
         if constexpr (ManyModel<M>::value) return many_ex_run<M>(J);
         else return LSQR_ERR_INVALID;
+      });
+}
+
+// sequential RANSAC over many problems (many_sequential.h): every round is one job of many_run / many_dense_run on the
+// survivors, which stay on the device
+int lsqr_ransac_many_sequential(lsqr_ctx *c, const void *host_records, size_t stride_bytes, const uint64_t *offsets,
+                                size_t n_problems, double p, const uint64_t *seeds, size_t max_models,
+                                uint64_t min_votes, double *params_out, int32_t *labels_out, lsqr_ransac_info *infos,
+                                int32_t *status_out, size_t *n_models_out) {
+  const char *fn = "lsqr_ransac_many_sequential";
+  ManyJob J;
+  J.p = p;
+  return many_call(
+      c, fn, J, host_records, stride_bytes, offsets, n_problems,
+      max_models == 0 || (seeds && params_out && infos && status_out && n_models_out), &p,
+      [&]() -> int {
+        const lsqr_model_cfg &cfg = c->cfg;
+        if (cfg.model == LSQR_MODEL_US_SINGLE || cfg.model == LSQR_MODEL_US_POINTER || cfg.model == LSQR_MODEL_PHANTOM)
+          return fail(c, LSQR_ERR_INVALID,
+                      "%s: the models of lsqr_ransac_many, lsqr_ransac_many_lm and lsqr_ransac_many_dense only "
+                      "(model %d)", fn, cfg.model);
+        if (max_models > 0x7FFFFFFFull) return fail(c, LSQR_ERR_INVALID, "%s: too many models", fn);
+        return LSQR_OK;
+      },
+      [&](ManyJob &J, auto tag) -> int {
+        typedef typename decltype(tag)::type M;
+        if (max_models == 0) {
+          if (n_models_out) memset(n_models_out, 0, sizeof(size_t) * n_problems);
+          return LSQR_OK;
+        }
+        if constexpr (M::IS_DENSE) {
+          const int n = (int)J.cfg.dim;
+          return many_seq_run(J, n, n, seeds, max_models, min_votes, params_out, labels_out, infos, status_out,
+                              n_models_out, [](ManyJob &S) -> int { return many_dense_run<M::NR>(S); });
+        } else if constexpr (ManyModel<M>::value) {
+          // (the sphere: J.lm says whether the rounds end in the LM stage, as lsqr_ransac_many_lm)
+          return many_seq_run(J, (int)M::K, (int)M::P, seeds, max_models, min_votes, params_out, labels_out, infos,
+                              status_out, n_models_out, [](ManyJob &S) -> int { return many_run<M>(S); });
+        } else {
+          return LSQR_ERR_INVALID;
+        }
       });
 }
 

@@ -68,8 +68,8 @@ hipError_t many_grow(T **p, size_t *cap, size_t n) {
 #endif
 }  // namespace lsqr
 
-// a HIP call of the batched host code (many.h, many_lm.h, many_dense.h, many_exhaustive.h; undefined at the end of the
-// last): J is the job at hand, a ManyJob or the LM stage's ManyLmJob, whose err is the ManyJob's
+// a HIP call of the batched host code (many.h, many_lm.h, many_dense.h, many_exhaustive.h, many_sequential.h; undefined
+// at the end of the last): J is the job at hand, a ManyJob or the LM stage's ManyLmJob, whose err is the ManyJob's
 #define MANYCHK(call)                                                                                \
   do {                                                                                               \
     hipError_t e_ = (call);                                                                          \
@@ -317,6 +317,14 @@ struct ManyBufs {
   char *h_ex[2] = {nullptr, nullptr};
   size_t c_hex[2] = {0, 0};
   hipEvent_t ev_ex[2] = {nullptr, nullptr};
+  // lsqr_ransac_many_sequential (many_sequential.h): the record buffer the survivors of a round are packed into (it
+  // and d_data change places after every partition), the survivors' upload indices (two, in turn), the labels, the
+  // partition's parts and their survivor counts, and the pinned staging of the parts
+  double *d_seq_rec = nullptr;
+  uint32_t *d_seq_orig[2] = {nullptr, nullptr}, *d_seq_counts = nullptr;
+  int32_t *d_seq_labels = nullptr;
+  char *d_seq_parts = nullptr, *h_seq = nullptr;
+  size_t c_seq_rec = 0, c_seq_orig[2] = {0, 0}, c_seq_counts = 0, c_seq_labels = 0, c_seq_parts = 0, c_hseq = 0;
 };
 
 #if defined(__HIPCC__)
@@ -324,11 +332,13 @@ inline void many_free(ManyBufs *b) {
   if (!b) return;
   void *dev[] = {b->d_data, b->d_hparams, b->d_best, b->d_partials, b->d_items, b->d_tiles, b->d_parts, b->d_valid,
                  b->d_mask, b->d_votes, b->d_pairs, b->d_pbeg, b->d_fin, b->d_counts, b->d_out,
-                 b->d_sub, b->d_marked, b->d_mom, b->d_ddpart, b->d_flags, b->d_exitems, b->d_exsmall, b->d_exbest};
+                 b->d_sub, b->d_marked, b->d_mom, b->d_ddpart, b->d_flags, b->d_exitems, b->d_exsmall, b->d_exbest,
+                 b->d_seq_rec, b->d_seq_orig[0], b->d_seq_orig[1], b->d_seq_counts, b->d_seq_labels, b->d_seq_parts};
   for (void *p : dev)
     if (p) (void)hipFree(p);
   if (b->h_stage) (void)hipHostFree(b->h_stage);
   if (b->h_pairs) (void)hipHostFree(b->h_pairs);
+  if (b->h_seq) (void)hipHostFree(b->h_seq);
   for (int s = 0; s < 2; s++) {
     if (b->h_ex[s]) (void)hipHostFree(b->h_ex[s]);
     if (b->ev_ex[s]) (void)hipEventDestroy(b->ev_ex[s]);
@@ -356,6 +366,9 @@ struct ManyJob {
   lsqr_model_cfg cfg = {};
   ModelConsts mc = {};
   const char *host = nullptr;  // records, stride bytes apart
+  // the records lie in buf->d_data already, packed (a round of many_sequential.h on the survivors of the last one):
+  // many_upload copies nothing and host stays unread
+  bool resident = false;
   size_t stride = 0;
   const uint64_t *offsets = nullptr;
   size_t n = 0;  // problems
@@ -395,7 +408,7 @@ inline int many_upload(ManyJob &J) {
   const uint64_t NT = J.offsets[J.n];
   const size_t W = J.W;
   const double *src = (const double *)J.host;
-  if (NT > 0) {
+  if (NT > 0 && !J.resident) {
     MANYCHK(many_grow(&B.d_data, &B.c_data, NT * W));
     if (J.stride != sizeof(double) * W) {
       J.packed.resize(NT * W);

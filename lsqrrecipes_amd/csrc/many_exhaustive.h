@@ -354,5 +354,3 @@ int many_ex_run(ManyJob &J) {
 #endif
 
 }  // namespace lsqr
-
-#undef MANYCHK

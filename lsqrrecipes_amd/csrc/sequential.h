@@ -15,6 +15,9 @@
 //                 record writes labels[its upload index] = round.
 //   k_seq_label   the last round, which nothing follows: the labels alone.
 //
+// The tile body of k_seq_write is seq_write_tile, shared with the segmented partition of lsqr_ransac_many_sequential
+// (many_sequential.h: k_mseq_write).
+//
 // No workgroup waits for another one: the order between the three steps is the stream's.  The host needs no count back:
 // the survivors are n - best_votes, and finish_ransac has checked best_votes against the mask.  k_seq_write clamps its
 // stores to that count all the same, so a mask that disagreed could not write past the destination.
@@ -75,6 +78,58 @@ __global__ __launch_bounds__(kBlock) void k_seq_scan(uint32_t *__restrict__ coun
   }
 }
 
+// LDS of one workgroup of the write kernels (k_seq_write here, k_mseq_write in many_sequential.h); buf: the dynamic
+// part, kBlock * D doubles
+struct SeqTileLds {
+  uint32_t slot[kBlock], orig[kBlock], w[kBlock / 64];
+};
+
+// One tile of the stable partition, by a whole workgroup of kBlock lanes: records [t0, min(t0 + kBlock, c1)) of `data`
+// (D doubles each, `stride` doubles apart; mask and orig_in -- nullable: identity -- indexed like the records).  The
+// survivors (mask byte 0) leave as one contiguous run at slot `base` of out / orig_out, clamped to slot `lim`; a
+// claimed record writes labels[its upload index] = round (labels nullable, n_labels entries).  magic: ceil(2^32 / D).
+// -> the tile's survivors.  Ends in a barrier: the LDS may be rewritten at once.
+__device__ __forceinline__ uint32_t seq_write_tile(const double *__restrict__ data, size_t stride, uint64_t t0,
+                                                   uint64_t c1, uint32_t uD, uint32_t magic,
+                                                   const uint8_t *__restrict__ mask,
+                                                   const uint32_t *__restrict__ orig_in, int32_t round,
+                                                   int32_t *__restrict__ labels, uint32_t n_labels, uint32_t base,
+                                                   uint32_t lim, double *__restrict__ out,
+                                                   uint32_t *__restrict__ orig_out, double *s_buf, SeqTileLds &s) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const uint64_t i = t0 + threadIdx.x;
+  const bool in_range = i < c1;
+  const bool keep = in_range && mask[i] == 0;
+  const uint32_t o = in_range ? (orig_in ? orig_in[i] : (uint32_t)i) : 0u;
+  if (in_range && !keep && labels && o < n_labels) labels[o] = round;
+  const uint64_t bal = __ballot(keep);
+  const uint32_t below = (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+  if (lane == 0) s.w[wave] = (uint32_t)__popcll(bal);
+  __syncthreads();
+  uint32_t off = 0, tot = 0;
+  for (int w = 0; w < kBlock / 64; w++) {
+    if (w < wave) off += s.w[w];
+    tot += s.w[w];
+  }
+  s.slot[threadIdx.x] = keep ? off + below : 0xFFFFFFFFu;
+  if (keep) s.orig[off + below] = o;
+  __syncthreads();
+  const uint32_t cnt = (uint32_t)(c1 - t0 < (uint64_t)kBlock ? c1 - t0 : (uint64_t)kBlock);
+  for (uint32_t e = threadIdx.x; e < cnt * uD; e += kBlock) {
+    const uint32_t rec = __umulhi(e, magic), k = e - rec * uD;
+    const uint32_t sl = s.slot[rec];
+    if (sl != 0xFFFFFFFFu) s_buf[sl * uD + k] = data[(t0 + rec) * stride + k];
+  }
+  __syncthreads();
+  const uint32_t room = base < lim ? lim - base : 0u;
+  const uint32_t run = tot < room ? tot : room;
+  double *dst = out + (uint64_t)base * uD;
+  for (uint32_t e = threadIdx.x; e < run * uD; e += kBlock) dst[e] = s_buf[e];
+  if (threadIdx.x < run) orig_out[base + threadIdx.x] = s.orig[threadIdx.x];
+  __syncthreads();  // slot, orig, w and s_buf are rewritten by the next tile
+  return tot;
+}
+
 // data: n records of D doubles, `stride` doubles apart; orig_in (nullable: identity): their indices in the caller's
 // upload; offsets: k_seq_scan's result; out / orig_out: room for n_out records; labels (nullable): n_labels entries.
 // Dynamic LDS: kBlock * D doubles.
@@ -86,46 +141,15 @@ __global__ __launch_bounds__(kBlock) void k_seq_write(const double *__restrict__
                                                       uint32_t *__restrict__ orig_out, int32_t *__restrict__ labels,
                                                       uint32_t n_labels) {
   extern __shared__ double s_buf[];
-  __shared__ uint32_t s_slot[kBlock], s_orig[kBlock], s_w[kBlock / 64];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  __shared__ SeqTileLds s;
   const uint64_t c0 = (uint64_t)blockIdx.x * kSeqChunk;
   const uint32_t c1 = (uint32_t)(c0 + kSeqChunk < n ? c0 + kSeqChunk : n);
   const uint32_t uD = (uint32_t)D;
   const uint32_t magic = 0xFFFFFFFFu / uD + 1u;  // ceil(2^32 / D): __umulhi(e, magic) == e / D for e < 2^32 / D
   uint32_t base = offsets[blockIdx.x];
-  for (uint64_t t0 = c0; t0 < c1; t0 += kBlock) {
-    const uint64_t i = t0 + threadIdx.x;
-    const bool in_range = i < c1;
-    const bool keep = in_range && mask[i] == 0;
-    const uint32_t o = in_range ? (orig_in ? orig_in[i] : (uint32_t)i) : 0u;
-    if (in_range && !keep && labels && o < n_labels) labels[o] = round;
-    const uint64_t bal = __ballot(keep);
-    const uint32_t below = (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
-    if (lane == 0) s_w[wave] = (uint32_t)__popcll(bal);
-    __syncthreads();
-    uint32_t off = 0, tot = 0;
-    for (int w = 0; w < kBlock / 64; w++) {
-      if (w < wave) off += s_w[w];
-      tot += s_w[w];
-    }
-    s_slot[threadIdx.x] = keep ? off + below : 0xFFFFFFFFu;
-    if (keep) s_orig[off + below] = o;
-    __syncthreads();
-    const uint32_t cnt = (uint32_t)(c1 - t0 < (uint64_t)kBlock ? c1 - t0 : (uint64_t)kBlock);
-    for (uint32_t e = threadIdx.x; e < cnt * uD; e += kBlock) {
-      const uint32_t rec = __umulhi(e, magic), k = e - rec * uD;
-      const uint32_t sl = s_slot[rec];
-      if (sl != 0xFFFFFFFFu) s_buf[sl * uD + k] = data[(t0 + rec) * stride + k];
-    }
-    __syncthreads();
-    const uint32_t room = base < n_out ? n_out - base : 0u;
-    const uint32_t run = tot < room ? tot : room;
-    double *dst = out + (uint64_t)base * uD;
-    for (uint32_t e = threadIdx.x; e < run * uD; e += kBlock) dst[e] = s_buf[e];
-    if (threadIdx.x < run) orig_out[base + threadIdx.x] = s_orig[threadIdx.x];
-    base += tot;
-    __syncthreads();  // s_slot, s_orig, s_w and s_buf are rewritten by the next tile
-  }
+  for (uint64_t t0 = c0; t0 < c1; t0 += kBlock)
+    base += seq_write_tile(data, stride, t0, c1, uD, magic, mask, orig_in, round, labels, n_labels, base, n_out, out,
+                           orig_out, s_buf, s);
 }
 
 __global__ __launch_bounds__(kBlock) void k_seq_label(const uint8_t *__restrict__ mask, uint32_t n,

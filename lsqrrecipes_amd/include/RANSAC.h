@@ -290,6 +290,80 @@ class RANSAC {
     return sequentialOn(data, ctx, cfg, data.size(), parameters, p, maxModels, minVotes, labels);
   }
 
+  // Sequential RANSAC over many independent problems (not in the reference): problem j is data[j], and
+  // computeManySequential(...)[j], parameters[j] and (*labels)[j] equal what computeSequential returns / leaves on
+  // data[j] after seed(seed() + j * maxModels) -- round r of problem j walks sampler stream seed() + j * maxModels + r.
+  // Per problem as computeSequential: invalid input (too few records, p outside (0, 1)) or maxModels == 0 runs
+  // nothing and leaves both empty, the labels -1.
+  // The models computeMany batches (plane, line, both sphere fits, the dense linear system up to 17 unknowns, absolute
+  // orientation, pivot calibration, ray intersection, 2-D line) run in ONE device call
+  // (lsqr_ransac_many_sequential: one upload, every round one batched search over the problems still going, the
+  // survivors compacted on the device); estimators without a device model, the other device estimators and
+  // forceHostLoop() loop over computeSequential with the same seeds.  Under LSQR_DEVICES the batched call runs on the
+  // first listed device's context.  lastInfo() is not updated by the batched call.
+  static std::vector<std::vector<double> > computeManySequential(
+      std::vector<std::vector<std::vector<S> > > &parameters, ParametersEstimator<T, S> *paramEstimator,
+      const std::vector<std::vector<T> > &data, double desiredProbabilityForNoOutliers, size_t maxModels,
+      size_t minVotes, std::vector<std::vector<int> > *labels = NULL) {
+    if (!paramEstimator) throw std::invalid_argument("lsqrRecipes::RANSAC: null estimator");
+    const size_t n = data.size();
+    const double p = desiredProbabilityForNoOutliers;
+    parameters.resize(n);
+    if (labels) labels->resize(n);
+    std::vector<std::vector<double> > fraction(n);
+    for (size_t j = 0; j < n; j++) {
+      parameters[j].clear();
+      if (labels) (*labels)[j].assign(data[j].size(), -1);
+    }
+    if (n == 0 || maxModels == 0 || p >= 1.0 || p <= 0.0) return fraction;
+    lsqr_model_cfg cfg;
+    const bool device = paramEstimator->deviceModel(cfg) && !forceHostLoop();
+    const bool batched =
+        device && lsqr_record_doubles(&cfg) <= 18 &&
+        (cfg.model == LSQR_MODEL_PLANE || cfg.model == LSQR_MODEL_LINE || cfg.model == LSQR_MODEL_SPHERE ||
+         cfg.model == LSQR_MODEL_DENSE || cfg.model == LSQR_MODEL_ABSOR || cfg.model == LSQR_MODEL_PIVOT ||
+         cfg.model == LSQR_MODEL_RAY || cfg.model == LSQR_MODEL_LINE2D);
+    if (!batched) {
+      const uint64_t s0 = seed();
+      for (size_t j = 0; j < n; j++) {
+        seed() = s0 + j * maxModels;
+        // (computeSequential reads the records only; it takes them by non-const reference as compute() does)
+        fraction[j] = computeSequential(parameters[j], paramEstimator, const_cast<std::vector<T> &>(data[j]), p,
+                                        maxModels, minVotes, labels ? &(*labels)[j] : NULL);
+      }
+      seed() = s0;
+      return fraction;
+    }
+    std::vector<uint64_t> offsets(n + 1, 0), seeds(n * maxModels);
+    for (size_t j = 0; j < n; j++) offsets[j + 1] = offsets[j] + data[j].size();
+    for (size_t e = 0; e < n * maxModels; e++) seeds[e] = seed() + e;
+    std::vector<T> records;
+    records.reserve((size_t)offsets[n]);
+    for (size_t j = 0; j < n; j++) records.insert(records.end(), data[j].begin(), data[j].end());
+    detail::Device &d = detail::Device::instance();
+    lsqr_ctx *ctx = d.ctx();
+    if (lsqr_multi *m = d.multi()) ctx = lsqr_multi_ctx(m, 0);
+    d.check(lsqr_set_model(ctx, &cfg));
+    const int P = lsqr_num_params(&cfg);
+    std::vector<double> par(n * maxModels * (size_t)P);
+    std::vector<int32_t> lab(labels ? (size_t)offsets[n] : 0), status(n * maxModels);
+    std::vector<lsqr_ransac_info> info(n * maxModels);
+    std::vector<size_t> nModels(n, 0);
+    d.check(lsqr_ransac_many_sequential(ctx, records.empty() ? NULL : &records[0], sizeof(T), &offsets[0], n, p,
+                                        &seeds[0], maxModels, minVotes, &par[0], lab.empty() ? NULL : &lab[0],
+                                        &info[0], &status[0], &nModels[0]));
+    for (size_t j = 0; j < n; j++) {
+      for (size_t r = 0; r < maxModels && status[j * maxModels + r] != LSQR_ERR_STATE; r++) {  // the rounds that ran
+        const size_t e = j * maxModels + r;
+        fraction[j].push_back(info[e].fraction);
+        if (r < nModels[j]) parameters[j].push_back(std::vector<S>(&par[e * P], &par[e * P] + info[e].n_params));
+      }
+      if (labels && !lab.empty())
+        (*labels)[j].assign(lab.begin() + (std::ptrdiff_t)offsets[j], lab.begin() + (std::ptrdiff_t)offsets[j + 1]);
+    }
+    return fraction;
+  }
+
   // sampler stream of the probabilistic overload (default 1); set it to vary the hypotheses
   static uint64_t &seed() {
     static thread_local uint64_t s = 1;
