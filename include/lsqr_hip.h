@@ -322,6 +322,47 @@ LSQR_API int lsqr_ransac_many_sequential(lsqr_ctx *ctx, const void *host_records
                                          lsqr_ransac_info *infos /* n_problems * max_models */,
                                          int32_t *status_out /* n_problems * max_models */,
                                          size_t *n_models_out /* n_problems */);
+/* Grouped RANSAC: one problem per label over the records the context already holds on the device.  It works on the
+ * context's current upload or attach (lsqr_upload / lsqr_attach), as lsqr_ransac_sequential does: the records are
+ * lsqr_count(ctx) records at the context's pointer and stride; they are only read, and attached (caller-owned) memory
+ * is never written.  groups[i] is the label of record i: problem g is the records with groups[i] == g, in upload
+ * order; a record whose label is negative or >= n_groups belongs to no problem.
+ *   on_device = 1: groups and consensus_out are device pointers (say, tensors beside the attached records); 0: host
+ *     pointers -- then the labels go up and the consensus comes down by one copy each.  seeds, params_out,
+ *     offsets_out, infos and status_out are host pointers in both forms.
+ *   Contract: problem g is decided exactly as the matching batched entry point decides problem g of a host call whose
+ *     records are the stable gather by label of the context's records, tightly packed, with offsets the prefix sums of
+ *     the group sizes and the same seeds: lsqr_ransac_many for the closed-form models, lsqr_ransac_many_lm for the
+ *     geometric sphere, lsqr_ransac_many_dense for LSQR_MODEL_DENSE.  The records are grouped on the device (keys, a
+ *     stable radix sort, a gather of lsqr_record_doubles 8-byte words per record copied as integers:
+ *     csrc/grouped.h), and the search is the same job -- the run those entry points use, unchanged -- on the same
+ *     packed bytes under the same offsets.  So everything those entry points write is bit-identical, parameters,
+ *     fit.cost and the LM fields included; only info.evaluated is exempt, as it is between two calls of theirs.
+ *   Outputs: status_out[g], infos[g] and row g of params_out follow those entry points' rules, N_g < k ->
+ *     LSQR_ERR_INVALID for that group included.  consensus_out (nullable, lsqr_count(ctx) bytes in upload order):
+ *     the consensus byte of record i in its problem, as those entry points report it; 0 for a record in no problem and
+ *     for every record of a problem without a winner; every byte is written.  offsets_out (nullable, host,
+ *     n_groups + 1): the prefix sums of the group sizes.
+ *   Models, taken from the context's lsqr_set_model: every model the three entry points accept; the dense system up
+ *     to dim 64.  LSQR_MODEL_US_SINGLE, LSQR_MODEL_US_POINTER and LSQR_MODEL_PHANTOM return LSQR_ERR_INVALID and write
+ *     nothing.
+ *   Argument errors (LSQR_ERR_INVALID, nothing written): p outside (0, 1); with n_groups > 0 a null groups, seeds,
+ *     params_out, infos or status_out; n_groups > 2^31 - 1; more than 2^32 - 16 records.  No model, or no records in
+ *     the context: LSQR_ERR_STATE.  n_groups == 0 is a no-op returning LSQR_OK.  A null context is refused before
+ *     anything is touched.
+ *   The context's upload, hypotheses, mask and spatial index are untouched; the work runs on the context's stream
+ *     (lsqr_set_stream), and the call returns after it has finished.  One synchronisation precedes the search: the
+ *     n_groups + 1 offsets cross to the host, where the batched job plans its rounds.  The options "max_iterations",
+ *     "many_round_hypotheses", "dense_fast_solve", "dense_dd" and the 2^22 no-model stop apply per problem as in the
+ *     batched entry points.  lsqr_multi handles have no grouped form. */
+LSQR_API int lsqr_ransac_grouped(lsqr_ctx *ctx, const int32_t *groups /* lsqr_count(ctx) entries, upload order */,
+                                 size_t n_groups, int on_device /* 1: groups, consensus_out on the device; 0: host */,
+                                 double p, const uint64_t *seeds /* host, n_groups */,
+                                 double *params_out      /* host, n_groups * lsqr_num_params */,
+                                 uint8_t *consensus_out  /* nullable: lsqr_count(ctx) bytes, upload order */,
+                                 uint64_t *offsets_out   /* nullable, host: n_groups + 1 */,
+                                 lsqr_ransac_info *infos /* host, n_groups */,
+                                 int32_t *status_out     /* host, n_groups */);
 /* Many independent RANSAC<T,S>::compute() problems (probabilistic overload, RANSAC.h:75-79) in one call.
  * Problem j is records [offsets[j], offsets[j+1]) of host_records (stride_bytes apart, laid out as for
  * lsqr_upload), walks sampler stream seeds[j] and is decided exactly as lsqr_ransac(ctx, p, seeds[j], NULL, 0, ...)

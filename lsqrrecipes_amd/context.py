@@ -52,6 +52,7 @@ class Context:
         a = a.reshape(-1, a.shape[-1]) if a.ndim > 1 else a.reshape(-1, self.ND)
         self._chk(self._lib.lsqr_upload(self._h, L.ptr(a), a.shape[0], a.shape[1] * 8))
         self.n = a.shape[0]
+        self._keep = None  # an upload replaces an attach: the attached memory is the caller's again
         return self
 
     def attach(self, device_ptr, count, stride_bytes, keepalive=None):
@@ -341,6 +342,76 @@ class Context:
                     iterations=f("iterations"), best_index=f("best_index"), best_votes=f("best_votes"),
                     evaluated=f("evaluated"), n_params=f("n_params"), n_used=g("n_used"), lm_info=g("lm_info"),
                     lm_nfev=g("lm_nfev"), cost=g("cost"), offsets=offs)
+
+    def ransac_grouped(self, groups, n_groups, p, seeds=None, want_consensus=True, consensus_out=None):
+        """One RANSAC problem per label over the records of the current upload / attach (lsqr_ransac_grouped): problem g
+        is the records i with groups[i] == g, in upload order; a label that is negative or >= n_groups puts the record
+        in no problem.  The records are grouped on the device and never cross to the host.  Every model ransac_many,
+        ransac_many_lm or ransac_many_dense takes; problem g is decided, bit for bit, as that call decides it on the
+        stable gather by label of the records with seeds[g] (default 1 + arange(n_groups)).
+        groups: a numpy integer array (host form), or a device tensor -- anything with data_ptr() and is_cuda, int32,
+        contiguous, one entry per record.  For the device form, consensus_out may be a uint8 device tensor of one byte
+        per record, which receives the consensus without a copy to the host.
+        -> ransac_many's dict plus lm_info, lm_nfev, cost and reserved; offsets: the prefix sums of the group sizes;
+        consensus: one byte per record in upload order, 0 for a record in no problem or in a problem without a winner
+        -- a numpy array for the host form, the caller's tensor for the device form (None unless want_consensus, or
+        where the device form got no consensus_out)."""
+        if self.cfg is None:
+            raise L.LsqrError(L.ERR_STATE, "set_model has not been called")
+        n = int(n_groups)
+        if n < 0:
+            raise ValueError("n_groups must not be negative")
+        total = int(self._lib.lsqr_count(self._h))
+        on_device = hasattr(groups, "data_ptr")
+        cons = None
+        if on_device:
+            if not groups.is_cuda or "int32" not in str(groups.dtype) or not groups.is_contiguous():
+                raise ValueError("device groups must be a contiguous int32 device tensor")
+            if groups.numel() != total:
+                raise ValueError("one label per record")
+            g_ptr = groups.data_ptr()
+            c_ptr = None
+            if consensus_out is not None and want_consensus:
+                c = consensus_out
+                if not (hasattr(c, "data_ptr") and c.is_cuda and "uint8" in str(c.dtype) and c.is_contiguous()
+                        and c.numel() == total):
+                    raise ValueError("consensus_out must be a contiguous uint8 device tensor of one byte per record")
+                cons, c_ptr = c, c.data_ptr()
+        else:
+            if consensus_out is not None:
+                raise ValueError("consensus_out goes with device groups")
+            g = np.asarray(groups)
+            if g.dtype.kind not in "iu":
+                raise ValueError("groups must be integers")
+            if g.shape != (total,):
+                raise ValueError("one label per record")
+            # (labels beyond int32 are in no problem, as -1 is)
+            g = np.ascontiguousarray(np.where((g >= 0) & (g <= 0x7FFFFFFF), g, -1) if g.dtype != np.int32 else g,
+                                     dtype=np.int32)
+            g_ptr = L.ptr(g)
+            cons = np.zeros(max(total, 1), dtype=np.uint8) if want_consensus else None
+            c_ptr = L.ptr(cons)
+        seeds = (1 + np.arange(n, dtype=np.uint64)) if seeds is None else np.ascontiguousarray(seeds, dtype=np.uint64)
+        if seeds.shape != (n,):
+            raise ValueError("one seed per group")
+        params = np.zeros((max(n, 1), self.P))
+        offs = np.zeros(n + 1, dtype=np.uint64)
+        infos = (L.RansacInfo * max(n, 1))()
+        status = np.zeros(max(n, 1), dtype=np.int32)
+        self._chk(self._lib.lsqr_ransac_grouped(self._h, g_ptr, n, 1 if on_device else 0, float(p), L.ptr(seeds),
+                                                L.ptr(params), c_ptr, L.ptr(offs), infos, L.ptr(status)))
+        status, params = status[:n], params[:n]
+        params[status != L.OK] = 0.0
+        inf = np.ctypeslib.as_array(infos)[:n]
+        f = lambda name: inf[name].copy()
+        fit = inf["fit"]
+        if cons is not None and not on_device:
+            cons = cons[:total]
+        return dict(status=status, fraction=f("fraction"), iterations=f("iterations"), best_index=f("best_index"),
+                    best_votes=f("best_votes"), evaluated=f("evaluated"), n_params=f("n_params"),
+                    n_used=fit["n_used"].copy(), lm_info=fit["lm_info"].copy(), lm_nfev=fit["lm_nfev"].copy(),
+                    cost=fit["cost"].copy(), reserved=fit["reserved"].copy(), params=params, consensus=cons,
+                    offsets=offs)
 
     def _many_records(self, problems):
         if self.cfg is None:

@@ -40,6 +40,7 @@
 #include "many.h"
 #include "many_dense.h"
 #include "many_exhaustive.h"
+#include "grouped.h"
 #include "sequential.h"
 #include "many_sequential.h"
 
@@ -4006,6 +4007,24 @@ int lsqr_ransac_sequential(lsqr_ctx *c, double p, const uint64_t *seeds, size_t 
 // stride.  Then the job from the context -- the caller has set what its kind alone has: p, the seeds and the outputs
 // -- and run(J, tag), dispatched on the model.  J.lm is the geometric sphere, which only the _lm gates let through.
 extern "C++" {
+// what every batched job takes from the context: the stream, the model, the options and the context's ManyBufs.  The
+// one place where an option reaches a job, for many_call's entry points and for lsqr_ransac_grouped alike.
+static void many_job_from_ctx(lsqr_ctx *c, ManyJob &J) {
+  if (!c->many) c->many = new ManyBufs();
+  J.stream = c->stream;
+  J.cfg = c->cfg;
+  J.mc = c->mc;
+  J.W = c->ND;  // lsqr_record_doubles(cfg)
+  J.max_iter = c->opt_max_iter;
+  J.round_cap = c->opt_many_round > 0 ? (size_t)c->opt_many_round : 0;
+  J.lm = c->cfg.model == LSQR_MODEL_SPHERE && c->cfg.ls_type == LSQR_LS_GEOMETRIC;
+  lm_settings(c->cfg, &J.lm_n, &J.lm_ftol, &J.lm_xtol, &J.lm_gtol, &J.lm_maxfev);
+  J.dense_fast = c->opt_dense_fast ? 1 : 0;
+  J.dense_dd = c->opt_dense_dd ? 1 : 0;
+  J.ex_fused = c->opt_many_ex_fused ? 1 : 0;
+  J.buf = c->many;
+}
+
 template <class Gate, class Run>
 static int many_call(lsqr_ctx *c, const char *fn, ManyJob &J, const void *host_records, size_t stride_bytes,
                      const uint64_t *offsets, size_t n, bool args, const double *p, Gate &&gate, Run &&run) {
@@ -4025,23 +4044,11 @@ static int many_call(lsqr_ctx *c, const char *fn, ManyJob &J, const void *host_r
   if (stride_bytes < sizeof(double) * (size_t)c->ND)
     return fail(c, LSQR_ERR_INVALID, "%s: stride %zu below the record's %zu bytes", fn, stride_bytes,
                 sizeof(double) * (size_t)c->ND);
-  if (!c->many) c->many = new ManyBufs();
-  J.stream = c->stream;
-  J.cfg = c->cfg;
-  J.mc = c->mc;
+  many_job_from_ctx(c, J);
   J.host = (const char *)host_records;
   J.stride = stride_bytes;
   J.offsets = offsets;
   J.n = n;
-  J.W = c->ND;  // lsqr_record_doubles(cfg)
-  J.max_iter = c->opt_max_iter;
-  J.round_cap = c->opt_many_round > 0 ? (size_t)c->opt_many_round : 0;
-  J.lm = c->cfg.model == LSQR_MODEL_SPHERE && c->cfg.ls_type == LSQR_LS_GEOMETRIC;
-  lm_settings(c->cfg, &J.lm_n, &J.lm_ftol, &J.lm_xtol, &J.lm_gtol, &J.lm_maxfev);
-  J.dense_fast = c->opt_dense_fast ? 1 : 0;
-  J.dense_dd = c->opt_dense_dd ? 1 : 0;
-  J.ex_fused = c->opt_many_ex_fused ? 1 : 0;
-  J.buf = c->many;
   st = dispatch(c->cfg, [&](auto tag) -> int { return run(J, tag); });
   if (st != LSQR_OK) return fail(c, st, "%s: %s", fn, J.err[0] ? J.err : "model not in this build");
   return LSQR_OK;
@@ -4244,6 +4251,52 @@ int lsqr_ransac_many_sequential(lsqr_ctx *c, const void *host_records, size_t st
           return LSQR_ERR_INVALID;
         }
       });
+}
+
+// one problem per label over the context's own records (grouped.h): grouped on the device into the batched calls'
+// packed buffer, one job of many_run / many_dense_run on that copy, the consensus back in upload order
+int lsqr_ransac_grouped(lsqr_ctx *c, const int32_t *groups, size_t n_groups, int on_device, double p,
+                        const uint64_t *seeds, double *params_out, uint8_t *consensus_out, uint64_t *offsets_out,
+                        lsqr_ransac_info *infos, int32_t *status_out) {
+  const char *fn = "lsqr_ransac_grouped";
+  int st = need_ready(c, false);
+  if (st != LSQR_OK) return st;
+  const lsqr_model_cfg &cfg = c->cfg;
+  if (cfg.model == LSQR_MODEL_US_SINGLE || cfg.model == LSQR_MODEL_US_POINTER || cfg.model == LSQR_MODEL_PHANTOM)
+    return fail(c, LSQR_ERR_INVALID,
+                "%s: the models of lsqr_ransac_many, lsqr_ransac_many_lm and lsqr_ransac_many_dense only (model %d)",
+                fn, cfg.model);
+  if (n_groups == 0) return LSQR_OK;  // (the order of many_call's checks)
+  if (!groups || !seeds || !params_out || !infos || !status_out)
+    return fail(c, LSQR_ERR_INVALID, "%s: null argument", fn);
+  if (!(p > 0.0) || !(p < 1.0)) return fail(c, LSQR_ERR_INVALID, "%s: p must lie in (0, 1)", fn);
+  if (n_groups > 0x7FFFFFFFull) return fail(c, LSQR_ERR_INVALID, "%s: more than 2^31 - 1 groups", fn);
+  if ((st = need_ready(c, true)) != LSQR_OK) return st;
+  if (c->n > 0xFFFFFFF0ull) return fail(c, LSQR_ERR_INVALID, "%s: more than 2^32 - 16 records", fn);
+  ManyJob J;
+  many_job_from_ctx(c, J);  // (the same fill as many_call's: the bit-identity rests on it)
+  J.resident = true;
+  J.n = n_groups;
+  J.p = p;
+  J.seeds = seeds;
+  J.params_out = params_out;
+  J.infos = infos;
+  J.status_out = status_out;
+  const double *data = c->d_data;
+  const size_t stride = c->stride, N = c->n;
+  st = dispatch(c->cfg, [&](auto tag) -> int {
+    typedef typename decltype(tag)::type M;
+    if constexpr (M::IS_DENSE)
+      return grouped_run(J, data, stride, N, groups, on_device, consensus_out, offsets_out,
+                         [](ManyJob &S) -> int { return many_dense_run<M::NR>(S); });
+    else if constexpr (ManyModel<M>::value)  // (the sphere: J.lm says whether the job ends in the LM stage)
+      return grouped_run(J, data, stride, N, groups, on_device, consensus_out, offsets_out,
+                         [](ManyJob &S) -> int { return many_run<M>(S); });
+    else
+      return LSQR_ERR_INVALID;
+  });
+  if (st != LSQR_OK) return fail(c, st, "%s: %s", fn, J.err[0] ? J.err : "model not in this build");
+  return LSQR_OK;
 }
 
 // C(n,k) and the rank-th k-subset in the exhaustive overload's order (comb.h); host only

@@ -68,8 +68,9 @@ hipError_t many_grow(T **p, size_t *cap, size_t n) {
 #endif
 }  // namespace lsqr
 
-// a HIP call of the batched host code (many.h, many_lm.h, many_dense.h, many_exhaustive.h, many_sequential.h; undefined
-// at the end of the last): J is the job at hand, a ManyJob or the LM stage's ManyLmJob, whose err is the ManyJob's
+// a HIP call of the batched host code (many.h, many_lm.h, many_dense.h, many_exhaustive.h, grouped.h,
+// many_sequential.h; undefined at the end of the last): J is the job at hand, a ManyJob or the LM stage's ManyLmJob,
+// whose err is the ManyJob's
 #define MANYCHK(call)                                                                                \
   do {                                                                                               \
     hipError_t e_ = (call);                                                                          \
@@ -325,6 +326,16 @@ struct ManyBufs {
   int32_t *d_seq_labels = nullptr;
   char *d_seq_parts = nullptr, *h_seq = nullptr;
   size_t c_seq_rec = 0, c_seq_orig[2] = {0, 0}, c_seq_counts = 0, c_seq_labels = 0, c_seq_parts = 0, c_hseq = 0;
+  // lsqr_ransac_grouped (grouped.h): the (label key, record index) pairs before and after the sort, the sort's
+  // temporaries, the group offsets, the winner flags, the labels and the consensus of the host form, and the pinned
+  // staging of the offsets and flags
+  uint32_t *d_grp_keys[2] = {nullptr, nullptr}, *d_grp_vals[2] = {nullptr, nullptr};
+  char *d_grp_tmp = nullptr, *h_grp = nullptr;
+  uint64_t *d_grp_off = nullptr;
+  uint8_t *d_grp_flag = nullptr, *d_grp_cons = nullptr;
+  int32_t *d_grp_labels = nullptr;
+  size_t c_grp_keys[2] = {0, 0}, c_grp_vals[2] = {0, 0}, c_grp_tmp = 0, c_hgrp = 0, c_grp_off = 0, c_grp_flag = 0,
+         c_grp_cons = 0, c_grp_labels = 0;
 };
 
 #if defined(__HIPCC__)
@@ -333,12 +344,15 @@ inline void many_free(ManyBufs *b) {
   void *dev[] = {b->d_data, b->d_hparams, b->d_best, b->d_partials, b->d_items, b->d_tiles, b->d_parts, b->d_valid,
                  b->d_mask, b->d_votes, b->d_pairs, b->d_pbeg, b->d_fin, b->d_counts, b->d_out,
                  b->d_sub, b->d_marked, b->d_mom, b->d_ddpart, b->d_flags, b->d_exitems, b->d_exsmall, b->d_exbest,
-                 b->d_seq_rec, b->d_seq_orig[0], b->d_seq_orig[1], b->d_seq_counts, b->d_seq_labels, b->d_seq_parts};
+                 b->d_seq_rec, b->d_seq_orig[0], b->d_seq_orig[1], b->d_seq_counts, b->d_seq_labels, b->d_seq_parts,
+                 b->d_grp_keys[0], b->d_grp_keys[1], b->d_grp_vals[0], b->d_grp_vals[1], b->d_grp_tmp, b->d_grp_off,
+                 b->d_grp_flag, b->d_grp_cons, b->d_grp_labels};
   for (void *p : dev)
     if (p) (void)hipFree(p);
   if (b->h_stage) (void)hipHostFree(b->h_stage);
   if (b->h_pairs) (void)hipHostFree(b->h_pairs);
   if (b->h_seq) (void)hipHostFree(b->h_seq);
+  if (b->h_grp) (void)hipHostFree(b->h_grp);
   for (int s = 0; s < 2; s++) {
     if (b->h_ex[s]) (void)hipHostFree(b->h_ex[s]);
     if (b->ev_ex[s]) (void)hipEventDestroy(b->ev_ex[s]);

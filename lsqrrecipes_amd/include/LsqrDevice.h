@@ -212,6 +212,8 @@ inline void lmFit(const lsqr_model_cfg &cfg, const T *recs, size_t count,
 // consensus) may be repeated with another threshold, probability, seed or least squares type -- or another estimator
 // of the same record type -- without the PCIe copy that dominates a cold call (4.3 of 5.3 ms at 10 M points).  What
 // was derived from the records alone (bounds, spatial index) is kept while the estimator type stays the same.
+// The vector must outlive the first compute(); it may go after that unless RANSAC<T,S>::computeGrouped is to run
+// through its host loop (see `host` below), which gathers from the vector itself.
 template <class T>
 class ResidentData {
  public:
@@ -232,6 +234,9 @@ class ResidentData {
     if (h) lsqr_ctx_destroy(h);
   }
   size_t size() const { return n; }
+  // the vector the records were taken from (RANSAC<T,S>::computeGrouped's host loop gathers from it); valid ONLY
+  // while the caller keeps that vector alive and unchanged: this class holds the pointer, not a copy
+  const T *hostRecords() const { return host; }
   // the context with `cfg` as its model and the records resident (uploaded on first use: the record layout check
   // of lsqr_upload needs a model)
   lsqr_ctx *attach(const lsqr_model_cfg &cfg) {
@@ -259,7 +264,10 @@ class ResidentData {
   }
   lsqr_ctx *h;
   size_t n;
-  const T *host;   // the caller's vector must outlive the first compute() (it is read once, then never again)
+  // The caller's vector.  compute() reads it once, for the upload on first use, and never again.  The one later
+  // reader is RANSAC<T,S>::computeGrouped's host loop (hostRecords()): a caller of computeGrouped with an estimator
+  // that is not batched on the device, or under forceHostLoop(), must keep the vector alive until that call returns.
+  const T *host;
   bool uploaded;
 };
 

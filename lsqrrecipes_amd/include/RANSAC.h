@@ -184,6 +184,73 @@ class RANSAC {
     return fraction;
   }
 
+  // Grouped RANSAC on resident records (not in the reference): problem g is the records i of `data` with
+  // groups[i] == g, in their order; a label that is negative or >= nGroups puts the record in no problem.  Problem g
+  // walks sampler stream seed() + g, so computeGrouped(...)[g] and parameters[g] equal what computeMany returns / leaves
+  // for the per-group vectors; consensus (optional, one entry per record of `data`) is set where the record is in its
+  // problem's consensus set.  The estimators computeMany batches run in ONE device call (lsqr_ransac_grouped: the
+  // records are grouped on the device, where they already are; only the labels go up and the consensus comes down).
+  // The estimators computeMany sends through its loop, and forceHostLoop(), go through computeMany itself on the
+  // per-group vectors, gathered from the vector `data` was made from.  THAT VECTOR MUST THEN STILL BE ALIVE AND
+  // UNCHANGED: ResidentData keeps a pointer to it, not a copy, and this is the one call that reads it after the
+  // upload (the batched path never does).
+  static std::vector<double> computeGrouped(std::vector<std::vector<S> > &parameters,
+                                            ParametersEstimator<T, S> *paramEstimator, ResidentData<T> &data,
+                                            const std::vector<int> &groups, size_t nGroups,
+                                            double desiredProbabilityForNoOutliers,
+                                            std::vector<bool> *consensus = NULL) {
+    if (!paramEstimator) throw std::invalid_argument("lsqrRecipes::RANSAC: null estimator");
+    if (groups.size() != data.size()) throw std::invalid_argument("lsqrRecipes::RANSAC: one group label per record");
+    const size_t n = nGroups, N = data.size();
+    const double p = desiredProbabilityForNoOutliers;
+    parameters.resize(n);
+    if (consensus) consensus->assign(N, false);
+    std::vector<double> fraction(n, 0.0);
+    if (n == 0 || N == 0 || p >= 1.0 || p <= 0.0) return fraction;  // RANSAC.hxx:16-19 for every problem
+    lsqr_model_cfg cfg;
+    const bool device = paramEstimator->deviceModel(cfg) && !forceHostLoop();
+    const bool batched = device && (cfg.model == LSQR_MODEL_PLANE || cfg.model == LSQR_MODEL_LINE ||
+                                    cfg.model == LSQR_MODEL_SPHERE || cfg.model == LSQR_MODEL_DENSE ||
+                                    cfg.model == LSQR_MODEL_ABSOR || cfg.model == LSQR_MODEL_PIVOT ||
+                                    cfg.model == LSQR_MODEL_RAY || cfg.model == LSQR_MODEL_LINE2D);
+    if (!batched) {
+      const T *host = data.hostRecords();
+      std::vector<std::vector<T> > sets(n);
+      std::vector<std::vector<size_t> > index(n);
+      for (size_t i = 0; i < N; i++)
+        if (groups[i] >= 0 && (size_t)groups[i] < n) {
+          sets[(size_t)groups[i]].push_back(host[i]);
+          index[(size_t)groups[i]].push_back(i);
+        }
+      std::vector<std::vector<bool> > cons;
+      fraction = computeMany(parameters, paramEstimator, sets, p, consensus ? &cons : NULL);
+      if (consensus)
+        for (size_t g = 0; g < n; g++)
+          for (size_t q = 0; q < cons[g].size(); q++) (*consensus)[index[g][q]] = cons[g][q];
+      return fraction;
+    }
+    std::vector<uint64_t> seeds(n);
+    for (size_t g = 0; g < n; g++) seeds[g] = seed() + g;
+    std::vector<int32_t> labels(groups.begin(), groups.end());
+    lsqr_ctx *ctx = data.attach(cfg);
+    const int P = lsqr_num_params(&cfg);
+    std::vector<double> par(n * (size_t)P);
+    std::vector<uint8_t> cons(consensus ? N : 0);
+    std::vector<lsqr_ransac_info> info(n);
+    std::vector<int32_t> status(n);
+    data.check(lsqr_ransac_grouped(ctx, &labels[0], n, 0, p, &seeds[0], &par[0], cons.empty() ? NULL : &cons[0], NULL,
+                                   &info[0], &status[0]));
+    for (size_t g = 0; g < n; g++) {
+      if (status[g] == LSQR_ERR_INVALID) continue;  // fewer records than a minimal subset: untouched, 0
+      parameters[g].clear();  // RANSAC.hxx:43
+      if (status[g] == LSQR_OK) parameters[g].assign(&par[g * P], &par[g * P] + info[g].n_params);
+      fraction[g] = info[g].fraction;
+    }
+    if (consensus)
+      for (size_t i = 0; i < N; i++) (*consensus)[i] = cons[i] != 0;
+    return fraction;
+  }
+
   // Many independent exhaustive searches (not in the reference): the overload next to the probabilistic computeMany,
   // as the two compute() overloads stand side by side.  computeMany(...)[j] equals the exhaustive compute() on data[j]:
   // parameters[j] is cleared first, a problem of fewer records than a minimal subset returns 0.  Plane, line, sphere

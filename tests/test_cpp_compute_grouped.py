@@ -1,0 +1,29 @@
+"""RANSAC<T,S>::computeGrouped of the C++ drop-in: tests/cpp/computeGroupedTest.cxx compiles and links on the CPU
+(against lsqr_ransac_grouped of the C ABI); on the GPU it checks computeGrouped on resident records against computeMany
+on the per-group vectors for the plane, the default sphere and a user-defined plugin estimator (the host loop)."""
+import os
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PROG = os.path.join(ROOT, "examples", "build", "computeGroupedTest")
+
+
+def _build():
+    subprocess.check_call(["make", "-C", os.path.join(ROOT, "examples"), "build/computeGroupedTest"],
+                          stdout=subprocess.DEVNULL)
+
+
+def test_compute_grouped_compiles_and_links():
+    _build()
+    assert os.access(PROG, os.X_OK)
+
+
+@pytest.mark.gpu
+def test_compute_grouped_matches_compute_many_on_gpu():
+    if not os.path.exists(PROG):
+        _build()
+    r = subprocess.run([PROG], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
+    assert "all checks passed" in r.stdout
