@@ -682,6 +682,9 @@ LSQR_API void lsqr_dedup_destroy(void *set);
  *                upload: 1 (default) = the batch is walked in the order of a Morton key of (normal direction, offset)
  *                so that the 64 hypotheses of a group miss the same cells (csrc/cells.h: k_plane_order); 0 = sampling
  *                order.  Votes are identical;
+ * "scan_prepared": cell models whose per-hypothesis state does not depend on the cell (plane): 1 (default) = it is
+ *                written once per batch (csrc/cells.h: k_prepare_hyps) and read back by the counted two-level scan; 0 = it
+ *                is rebuilt for every (cell, group of 64 hypotheses) (A/B knob).  Votes are identical;
  * "dense_mask_ring": LDS tile buffers per wave of the dense final fit's fused mask + normal-equations pass: 4 (default at
  *                n = 64) = one workgroup per CU with three tiles in flight, 2 = two workgroups per CU (A/B knob);
  * "mom_chunk":   records per workgroup of the mask / moment passes in units of 256 (0 = default: 4, wide US / phantom

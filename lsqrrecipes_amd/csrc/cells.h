@@ -712,9 +712,23 @@ __global__ __launch_bounds__(256) void k_super_boxes(const CellBox *__restrict__
 //   value(xs, fp)            packed fp32 filter measure v of two observations with the guarantee
 //                            |v| < tin => agrees,  |v| >= tout => does not agree   (exact fp64 predicate
 //                            decides in between)
+//   PREPARED = 1, prepare()  (optional) Hyp is plain data, a multiple of 16 bytes, and prepare() -- load()'s body --
+//                            may run once per batch (k_prepare_hyps) for the counted scan to read Hyp from memory
 // CellConsts are per-launch constants derived on the host (cell_consts<CM>()).
 struct CellConsts {
   float f[8];
+};
+template <class CM>
+constexpr bool cell_prepared() {
+  if constexpr (requires { CM::PREPARED; }) return CM::PREPARED != 0;
+  return false;
+}
+// a prepared Hyp as the 16-byte words it is stored in (lane = hypothesis: 16-byte loads / stores per lane)
+template <class CM>
+struct HypWords {
+  static_assert(sizeof(typename CM::Hyp) % 16 == 0, "a prepared Hyp is padded to a multiple of 16 bytes");
+  enum { N4 = sizeof(typename CM::Hyp) / 16 };
+  float w[4 * N4];
 };
 // an fp64 value fetched as two 32-bit words of a float row
 __device__ inline double f64_from(const float *w) {
@@ -757,8 +771,16 @@ struct PlaneCell {
     double n[3], c;
     float nf[3], e0;
   };
-  static __device__ inline void load(const float *row, const float *, bool valid,
+  // Hyp depends on the hypothesis alone and is as large as the row it is made from (48 bytes): the counted scan
+  // (k_cells_bounds(cnt) / k_scan_pairs) has it written once per batch by k_prepare_hyps and reads it back with three
+  // 16-byte loads instead of rebuilding it for every (cell, group) -- ~160 times per hypothesis in a full count
+  enum { PREPARED = 1 };
+  static __device__ inline void load(const float *row, const float *row2, bool valid,
                                      const CellConsts &cc, Hyp &h) {
+    prepare(row, row2, valid, cc, h);
+  }
+  static __device__ inline void prepare(const float *row, const float *, bool valid,
+                                        const CellConsts &cc, Hyp &h) {
     double r[2 * D];
 #pragma unroll
     for (int i = 0; i < 2 * D; i++) r[i] = f64_from(row + 2 * i);
@@ -1517,11 +1539,61 @@ __global__ __launch_bounds__(256) void k_scatter_votes(const uint32_t *__restric
   if (j < *n_b) votes[sel_b[j]] = v_b[j];
 }
 
+// Hyp of every hypothesis of a batch, once (cell models with PREPARED): out[h] for h in [0, H rounded up to whole
+// groups of 64) -- the scan reads whole groups -- with the lanes past the batch (or past the device-side count: h_dev,
+// h_off as in k_scan_pairs) prepared as load() has them, from row 0 and not valid.  Runs on the stream after the rows
+// are final and before the counting pass, so it sees every permutation and compaction the rows went through.
+template <class CM>
+__global__ __launch_bounds__(256) void k_prepare_hyps(const float *__restrict__ rows, const float *__restrict__ spf,
+                                                      uint32_t H, CellConsts cc, const uint32_t *__restrict__ h_dev,
+                                                      uint32_t h_off, float4 *__restrict__ out) {
+  typedef typename CM::M M;
+  constexpr int ROW = CM::ROW, NR4 = ROW / 4, NR2 = CM::ROW2 / 4, NH4 = HypWords<CM>::N4;
+  const uint32_t cap = (H + 63) & ~63u;
+  if (h_dev) {
+    const uint32_t hd = *h_dev > h_off ? *h_dev - h_off : 0u;  // hypotheses [h_off, h_off + H) of the selection
+    H = hd < H ? hd : H;
+  }
+  const uint32_t h = blockIdx.x * 256 + threadIdx.x;
+  if (h >= cap) return;
+  float row[ROW], row2[NR2 ? 4 * NR2 : 4];
+  const float4 *r4 = (const float4 *)(rows + (size_t)(h < H ? h : 0) * ROW);
+#pragma unroll
+  for (int k = 0; k < NR4; k++) {
+    const float4 v = r4[k];
+    row[4 * k] = v.x, row[4 * k + 1] = v.y, row[4 * k + 2] = v.z, row[4 * k + 3] = v.w;
+  }
+  if constexpr (NR2 > 0) {
+    const float4 *q4 = (const float4 *)(spf + (size_t)(h < H ? h : 0) * M::SPF + CM::ROW2_OFF);
+#pragma unroll
+    for (int k = 0; k < NR2; k++) {
+      const float4 v = q4[k];
+      row2[4 * k] = v.x, row2[4 * k + 1] = v.y, row2[4 * k + 2] = v.z, row2[4 * k + 3] = v.w;
+    }
+  }
+  typename CM::Hyp hy;
+  CM::prepare(row, row2, h < H, cc, hy);
+  const HypWords<CM> hw = __builtin_bit_cast(HypWords<CM>, hy);
+#pragma unroll
+  for (int k = 0; k < NH4; k++)
+    out[(size_t)h * NH4 + k] = make_float4(hw.w[4 * k], hw.w[4 * k + 1], hw.w[4 * k + 2], hw.w[4 * k + 3]);
+}
+// ... and read back: NH4 16-byte loads of the lane's hypothesis
+template <class CM>
+__device__ __forceinline__ typename CM::Hyp hyp_from(const float4 (&v)[HypWords<CM>::N4]) {
+  HypWords<CM> hw;
+#pragma unroll
+  for (int k = 0; k < HypWords<CM>::N4; k++)
+    hw.w[4 * k] = v[k].x, hw.w[4 * k + 1] = v[k].y, hw.w[4 * k + 2] = v[k].z, hw.w[4 * k + 3] = v[k].w;
+  return __builtin_bit_cast(typename CM::Hyp, hw);
+}
+
 // Level 1 alone (measurement, and the vote bound of the two-pass scan): per hypothesis the summed population
 // of its surviving cells -- an upper bound on its votes, every agreeing observation lies in a surviving cell --
 // and, per launch, the number of surviving (hypothesis, cell) pairs, i.e. what level 2 has to look at.
 // Lane = hypothesis; blockIdx.y * 4 + wave = group of 64 hypotheses; blockIdx.x = a run of cells.
-template <class CM, int PP>
+// PREP: Hyp comes from the batch's prepared block `hyps` (k_prepare_hyps) instead of load().
+template <class CM, int PP, bool PREP = false>
 __global__ __launch_bounds__(256) void k_cells_bounds(const CellBox *__restrict__ boxes, uint32_t ncells,
                                                       size_t ns, const float *__restrict__ rows,
                                                       const float *__restrict__ spf, uint32_t H,
@@ -1531,7 +1603,7 @@ __global__ __launch_bounds__(256) void k_cells_bounds(const CellBox *__restrict_
                                                       uint32_t *__restrict__ ncells_out,
                                                       uint8_t *__restrict__ cnt, uint32_t gstride,
                                                       const uint32_t *__restrict__ h_dev, uint32_t h_off,
-                                                      uint32_t box_pop) {
+                                                      uint32_t box_pop, const float4 *__restrict__ hyps) {
   typedef typename CM::M M;
   constexpr int ROW = CM::ROW, NR4 = ROW / 4, NR2 = CM::ROW2 / 4;
   const size_t CP = box_pop;  // observations per box: 128 * PP for the cells, a multiple for merged boxes
@@ -1544,25 +1616,33 @@ __global__ __launch_bounds__(256) void k_cells_bounds(const CellBox *__restrict_
   const uint32_t h = grp * 64 + lane;
   if (blockIdx.y * 256 >= H) return;   // workgroup-uniform: the barriers below are for whole workgroups
   const bool active = h - lane < H;    // wave-uniform
-  float row[ROW], row2[NR2 ? 4 * NR2 : 4];
-  {
-    const float4 *r4 = (const float4 *)(rows + (size_t)(h < H ? h : 0) * ROW);
+  typename CM::Hyp hy;
+  if constexpr (PREP) {  // (the block holds whole groups: every lane of an active wave has an entry)
+    constexpr int NH4 = HypWords<CM>::N4;
+    float4 v[NH4];
 #pragma unroll
-    for (int k = 0; k < NR4; k++) {
-      const float4 v = r4[k];
-      row[4 * k] = v.x, row[4 * k + 1] = v.y, row[4 * k + 2] = v.z, row[4 * k + 3] = v.w;
-    }
-    if constexpr (NR2 > 0) {
-      const float4 *q4 = (const float4 *)(spf + (size_t)(h < H ? h : 0) * M::SPF + CM::ROW2_OFF);
+    for (int k = 0; k < NH4; k++) v[k] = hyps[(size_t)(active ? h : 0) * NH4 + k];
+    hy = hyp_from<CM>(v);
+  } else {
+    float row[ROW], row2[NR2 ? 4 * NR2 : 4];
+    {
+      const float4 *r4 = (const float4 *)(rows + (size_t)(h < H ? h : 0) * ROW);
 #pragma unroll
-      for (int k = 0; k < NR2; k++) {
-        const float4 v = q4[k];
-        row2[4 * k] = v.x, row2[4 * k + 1] = v.y, row2[4 * k + 2] = v.z, row2[4 * k + 3] = v.w;
+      for (int k = 0; k < NR4; k++) {
+        const float4 v = r4[k];
+        row[4 * k] = v.x, row[4 * k + 1] = v.y, row[4 * k + 2] = v.z, row[4 * k + 3] = v.w;
+      }
+      if constexpr (NR2 > 0) {
+        const float4 *q4 = (const float4 *)(spf + (size_t)(h < H ? h : 0) * M::SPF + CM::ROW2_OFF);
+#pragma unroll
+        for (int k = 0; k < NR2; k++) {
+          const float4 v = q4[k];
+          row2[4 * k] = v.x, row2[4 * k + 1] = v.y, row2[4 * k + 2] = v.z, row2[4 * k + 3] = v.w;
+        }
       }
     }
+    CM::load(row, row2, h < H, cc, hy);
   }
-  typename CM::Hyp hy;
-  CM::load(row, row2, h < H, cc, hy);
   const uint32_t c0 = blockIdx.x * cells_per_block;
   const uint32_t c1 = c0 + cells_per_block < ncells ? c0 + cells_per_block : ncells;
   uint32_t u = 0, nc = 0;
@@ -1689,17 +1769,23 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v, int lane) {
   return v;
 }
 
-template <class CM, int PP, int BS, bool LDSB>
+template <class CM, int PP, int BS, bool LDSB, bool PREP = false>
 __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(PP >= 8 ? 4 : CM::MIN_WAVES, 8))) void k_scan_pairs(
     const double *__restrict__ sorted, size_t ns, const CellBox *__restrict__ boxes, uint32_t ncells,
     const double *__restrict__ sp, const float *__restrict__ rows, const float *__restrict__ spf, uint32_t H,
     ModelConsts mc, CellConsts cc, uint32_t *__restrict__ vpart, uint32_t vstride,
     const uint32_t *__restrict__ h_dev, const uint8_t *__restrict__ cnt, uint32_t gstride, const uint32_t *__restrict__ cost,
-    const uint32_t *__restrict__ csum, uint32_t nchunks, uint32_t h_off) {
+    const uint32_t *__restrict__ csum, uint32_t nchunks, uint32_t h_off, const float4 *__restrict__ hyps) {
   typedef typename CM::M M;
   constexpr int NB = CM::NB;
   constexpr int SPD = M::SP;
-  constexpr int ROW = CM::ROW, NR4 = ROW / 4, NR2 = CM::ROW2 / 4;
+  [[maybe_unused]] constexpr int ROW = CM::ROW;
+  constexpr int NR2 = CM::ROW2 / 4;
+  // what is fetched one group ahead: the row load() starts from, or (PREP) the prepared Hyp itself
+  constexpr int NR4 = [] {
+    if constexpr (PREP) return (int)HypWords<CM>::N4;
+    else return (int)CM::ROW / 4;
+  }();
   if (h_dev) {
     const uint32_t hd = *h_dev > h_off ? *h_dev - h_off : 0u;  // hypotheses [h_off, h_off + H) of the selection
     H = hd < H ? hd : H;
@@ -1767,13 +1853,18 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(PP >= 8 ? 4 
   };
   auto load_rows = [&](uint32_t g, float4(&r)[NR4], float4(&r2)[NR2 ? NR2 : 1]) {
     const uint32_t h = g * 64 + lane;
-    const float4 *r4 = (const float4 *)(rows + (size_t)(h < H ? h : 0) * ROW);
+    if constexpr (PREP) {  // (the block holds whole groups, the lanes past the batch as load() has them)
 #pragma unroll
-    for (int k = 0; k < NR4; k++) r[k] = r4[k];
-    if constexpr (NR2 > 0) {
-      const float4 *q4 = (const float4 *)(spf + (size_t)(h < H ? h : 0) * M::SPF + CM::ROW2_OFF);
+      for (int k = 0; k < NR4; k++) r[k] = hyps[(size_t)h * NR4 + k];
+    } else {
+      const float4 *r4 = (const float4 *)(rows + (size_t)(h < H ? h : 0) * ROW);
 #pragma unroll
-      for (int k = 0; k < NR2; k++) r2[k] = q4[k];
+      for (int k = 0; k < NR4; k++) r[k] = r4[k];
+      if constexpr (NR2 > 0) {
+        const float4 *q4 = (const float4 *)(spf + (size_t)(h < H ? h : 0) * M::SPF + CM::ROW2_OFF);
+#pragma unroll
+        for (int k = 0; k < NR2; k++) r2[k] = q4[k];
+      }
     }
   };
   while (budget && cell < ncells) {
@@ -1816,15 +1907,20 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(PP >= 8 ? 4 
       const int g = __builtin_ctzll(gm);
       gm &= gm - 1;
       const uint32_t cg = (uint32_t)__builtin_amdgcn_readlane((int)gc, g);
-      float row[ROW], row2[NR2 ? 4 * NR2 : 4];
+      [[maybe_unused]] float row[4 * NR4], row2[NR2 ? 4 * NR2 : 4];
+      typename CM::Hyp hy;
+      if constexpr (PREP) {
+        hy = hyp_from<CM>(nxt);
+      } else {
 #pragma unroll
-      for (int k = 0; k < NR4; k++)
-        row[4 * k] = nxt[k].x, row[4 * k + 1] = nxt[k].y, row[4 * k + 2] = nxt[k].z, row[4 * k + 3] = nxt[k].w;
-      if constexpr (NR2 > 0) {
+        for (int k = 0; k < NR4; k++)
+          row[4 * k] = nxt[k].x, row[4 * k + 1] = nxt[k].y, row[4 * k + 2] = nxt[k].z, row[4 * k + 3] = nxt[k].w;
+        if constexpr (NR2 > 0) {
 #pragma unroll
-        for (int k = 0; k < NR2; k++)
-          row2[4 * k] = nxt2[k].x, row2[4 * k + 1] = nxt2[k].y, row2[4 * k + 2] = nxt2[k].z,
-                   row2[4 * k + 3] = nxt2[k].w;
+          for (int k = 0; k < NR2; k++)
+            row2[4 * k] = nxt2[k].x, row2[4 * k + 1] = nxt2[k].y, row2[4 * k + 2] = nxt2[k].z,
+                     row2[4 * k + 3] = nxt2[k].w;
+        }
       }
       if (gm) load_rows((uint32_t)__builtin_ctzll(gm), nxt, nxt2);  // the next group's rows meanwhile
       // my part [lo, hi) of the group's cost units; pair j sits at unit kGroupPad + j
@@ -1835,8 +1931,7 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(PP >= 8 ? 4 
                      jhi = (hi > kGroupPad ? hi : kGroupPad) - kGroupPad;
       if (jhi <= jlo) continue;
       const uint32_t h0 = (uint32_t)g * 64, h = h0 + lane;
-      typename CM::Hyp hy;
-      CM::load(row, row2, h < H, cc, hy);
+      if constexpr (!PREP) CM::load(row, row2, h < H, cc, hy);
       float bc[NB];
       const bool l1 = CM::level1(hy, bx, ctr, cc, bc);
       unsigned long long surv = __ballot(l1);  // == the counting pass: cg - pad bits

@@ -236,6 +236,9 @@ struct lsqr_ctx {
   uint32_t *d_paircost = nullptr; // [n_cells cell costs | chunk sums]
   uint32_t *d_vpart = nullptr;    // per-workgroup partial votes of k_scan_pairs
   size_t paircnt_cap = 0, paircost_cap = 0, vpart_cap = 0;
+  float4 *d_hyps = nullptr;       // k_prepare_hyps: CM::Hyp of every hypothesis of the batch k_scan_pairs is counting
+  size_t hyps_cap = 0;
+  int opt_prepared = 1;           // 1: cell models with PREPARED read Hyp from d_hyps; 0: load() per (cell, group) (A/B)
   // bounded scan (cells.h: k_pick_*): the selected hypotheses as a compact batch
   uint32_t *d_sel = nullptr;        // [kPilots pilots | H_cap rest]
   BoundSel *d_bsel = nullptr;
@@ -1089,7 +1092,7 @@ int run_cells_bounds(lsqr_ctx *c, uint32_t *d_ub, uint32_t *d_nc = nullptr) {
                      CM::ROW_F32 ? c->d_hparams_f32 : (const float *)c->d_hparams, c->d_hparams_f32,
                      (uint32_t)c->H, cc, per, d_ub, d_nc ? c->d_counter + CNT_PAIRS : (unsigned long long *)nullptr, d_nc,
                      (uint8_t *)nullptr, 0u, (const uint32_t *)nullptr, 0u,  // (pair total: diagnostics only -- 8192
-                     (uint32_t)(128 * PP) * merge);                          // atomics on one address are ~100 us)
+                     (uint32_t)(128 * PP) * merge, (const float4 *)nullptr);  // atomics on one address are ~100 us)
   HIPCHK(c, hipGetLastError());
   return LSQR_OK;
 }
@@ -1126,13 +1129,32 @@ int run_scan_pairs(lsqr_ctx *c, const ScanBatch &b0) {
   if ((st = ensure(c, &c->d_paircost, &c->paircost_cap, (size_t)c->n_cells + nchunks)) != LSQR_OK) return st;
   uint32_t *d_cost = c->d_paircost, *d_csum = c->d_paircost + c->n_cells;
   const float *rows = CM::ROW_F32 ? b.spf : (const float *)b.sp;
+  // the hypothesis-only part of level 1 once per batch instead of once per (cell, group): both kernels below read it
+  constexpr bool kPrep = cell_prepared<CM>();
+  const bool prep = kPrep && c->opt_prepared;
+  if constexpr (kPrep) {
+    if (prep) {
+      const uint32_t slots = (Hc + 63) & ~63u;  // whole groups
+      if ((st = ensure(c, &c->d_hyps, &c->hyps_cap, (size_t)slots * HypWords<CM>::N4)) != LSQR_OK) return st;
+      hipLaunchKernelGGL((k_prepare_hyps<CM>), dim3((slots + 255) / 256), dim3(256), 0, c->stream, rows, b.spf, Hc, cc,
+                         b.h_dev, b.h_off, c->d_hyps);
+      HIPCHK(c, hipGetLastError());
+    }
+  }
+  const float4 *hyps = prep ? c->d_hyps : nullptr;
   {  // counting pass: waves past the device-side H leave at once, so the grid is cut finely in x
     const unsigned gy = (Hc + 255) / 256;
     const uint32_t per = std::max<uint32_t>(8, (c->n_cells + 1023) / 1024);
     const unsigned gx = (c->n_cells + per - 1) / per;
-    hipLaunchKernelGGL((k_cells_bounds<CM, PP>), dim3(gx, gy), dim3(256), 0, c->stream, c->d_boxes, c->n_cells,
-                       c->n_sorted, rows, b.spf, Hc, cc, per, (uint32_t *)nullptr, (unsigned long long *)nullptr,
-                       (uint32_t *)nullptr, c->d_paircnt, gstride, b.h_dev, b.h_off, (uint32_t)(128 * PP));
+    auto count = [&](auto kern) {
+      hipLaunchKernelGGL(kern, dim3(gx, gy), dim3(256), 0, c->stream, c->d_boxes, c->n_cells, c->n_sorted, rows, b.spf,
+                         Hc, cc, per, (uint32_t *)nullptr, (unsigned long long *)nullptr, (uint32_t *)nullptr,
+                         c->d_paircnt, gstride, b.h_dev, b.h_off, (uint32_t)(128 * PP), hyps);
+    };
+    if (prep)
+      count(k_cells_bounds<CM, PP, kPrep>);
+    else
+      count(k_cells_bounds<CM, PP>);
     HIPCHK(c, hipGetLastError());
   }
   hipLaunchKernelGGL(k_tile_costs, dim3(nchunks), dim3(kChunkCells), 0, c->stream, c->d_paircnt, gstride, Hc, b.h_dev,
@@ -1157,13 +1179,14 @@ int run_scan_pairs(lsqr_ctx *c, const ScanBatch &b0) {
     ProfScope ps(c, KID_SCAN);
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(BS), lds, c->stream, c->d_sorted, c->n_sorted, c->d_boxes, c->n_cells,
                        b.sp, rows, b.spf, Hc, c->mc, cc, c->d_vpart, Hc, b.h_dev, (const uint8_t *)c->d_paircnt, gstride,
-                       (const uint32_t *)d_cost, (const uint32_t *)d_csum, nchunks, b.h_off);
+                       (const uint32_t *)d_cost, (const uint32_t *)d_csum, nchunks, b.h_off, hyps);
     HIPCHK(c, hipGetLastError());
     hipLaunchKernelGGL(k_votes_reduce, dim3((Hc + 63) / 64, 48), dim3(256), 0, c->stream,
                        (const uint32_t *)c->d_vpart, Hc, (uint32_t)blocks, Hc, b.h_dev, b.votes, b.h_off);
     HIPCHK(c, hipGetLastError());
     return LSQR_OK;
   };
+  if (prep) return ldsb ? launch(k_scan_pairs<CM, PP, BS, true, kPrep>) : launch(k_scan_pairs<CM, PP, BS, false, kPrep>);
   return ldsb ? launch(k_scan_pairs<CM, PP, BS, true>) : launch(k_scan_pairs<CM, PP, BS, false>);
 }
 
@@ -3068,7 +3091,7 @@ void lsqr_ctx_destroy(lsqr_ctx *c) {
   free_index(c);
   many_free(c->many);
   void *bufs[] = {c->d_seq_rec[0], c->d_seq_rec[1], c->d_seq_orig[0], c->d_seq_orig[1], c->d_seq_labels, c->d_seq_counts,
-                  c->d_refused, c->d_us16, c->d_us16_x, c->d_h16, c->d_h16_bs, c->d_h16_thr, c->d_ddpart, c->d_ub2, c->d_axis, c->d_cellT, c->d_vpart, c->d_paircnt, c->d_paircost, c->d_sel, c->d_bsel, c->d_hparams2, c->d_hparams2_f32, c->d_votes2, c->d_lmrec, c->d_idx_scratch, c->d_ub, c->d_queues, c->d_data_owned, c->d_subsets, c->d_hparams, c->d_hparams_f32, c->d_amb, c->d_valid, c->d_votes, c->d_mask, c->d_rows,
+                  c->d_refused, c->d_us16, c->d_us16_x, c->d_h16, c->d_h16_bs, c->d_h16_thr, c->d_ddpart, c->d_ub2, c->d_axis, c->d_cellT, c->d_vpart, c->d_paircnt, c->d_paircost, c->d_hyps, c->d_sel, c->d_bsel, c->d_hparams2, c->d_hparams2_f32, c->d_votes2, c->d_lmrec, c->d_idx_scratch, c->d_ub, c->d_queues, c->d_data_owned, c->d_subsets, c->d_hparams, c->d_hparams_f32, c->d_amb, c->d_valid, c->d_votes, c->d_mask, c->d_rows,
                   c->d_partials, c->d_mom, c->d_vec, c->d_par, c->d_best, c->d_lm, c->d_out, c->d_counter};
   for (void *b : bufs)
     if (b) (void)hipFree(b);
@@ -5293,6 +5316,10 @@ static int set_option_one(lsqr_ctx *c, const char *name, int value) {
   }
   if (!strcmp(name, "scan_pairs")) {  // 0: default, 1: k_scan_pairs for plain scans too (A/B)
     c->opt_pairs = value;
+    return LSQR_OK;
+  }
+  if (!strcmp(name, "scan_prepared")) {  // 1 (default): the counted scan reads each hypothesis' prepared Hyp; 0: load() per (cell, group)
+    c->opt_prepared = value != 0;
     return LSQR_OK;
   }
   if (!strcmp(name, "scan_axis")) {  // 1 (default): axis-sorted cells + vote bounds by rank (plane, 3-D); 0: off

@@ -19,7 +19,8 @@ from bench import kernel_source_hash  # noqa: E402
 
 CSRC = os.path.join(ROOT, "lsqrrecipes_amd", "csrc")
 # (key, substrings the mangled name must contain)
-KERNELS = [("k_scan_pairs_plane", ["k_scan_pairs", "PlaneCell", "Li3E"]),
+KERNELS = [("k_scan_pairs_plane", ["k_scan_pairs", "PlaneCell", "Li3E", "Li4ELi256ELb1ELb1E"]),  # LDS broadcast, prepared Hyp: what runs
+           ("k_scan_pairs_plane_unprepared", ["k_scan_pairs", "PlaneCell", "Li3E", "Li4ELi256ELb1ELb0E"]),  # scan_prepared=0
            ("k_scan_pairs_sphere", ["k_scan_pairs", "SphereCell", "Li3E"]),
            ("k_scan_pairs_line", ["k_scan_pairs", "LineCell", "Li3E"]),
            ("k_scan_us_f32", ["k_scan_us_f32", "USModel", "Lb1E"]),

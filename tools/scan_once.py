@@ -1,5 +1,6 @@
 # one bench step (lsqr_batch_fit) of a BASELINE workload on the bench's shapes and seed (for rocprofv3 --pmc passes):
 #   python3 tools/scan_once.py plane|sphere|line|us|dense|phantom [launches] [scan_bound: 0 = full count, 1 = early exit]
+#                              [NAME=VALUE ...]   (further lsqr_set_option settings, A/B passes: scan_prepared=0)
 import sys
 sys.path.insert(0, '.')
 from lsqrrecipes_amd import _lib as L, synth
@@ -20,6 +21,8 @@ if wl in ('plane', 'sphere', 'line'):
     ctx.set_option('scan_index', 2)
     ctx.set_option('scan_kd_after', 0)   # the order the bench's timed steps run on (there: built with the fourth batch)
 ctx.set_option('scan_bound', bound)
+for kv in sys.argv[4:]:
+    ctx.set_option(kv.split('=')[0], int(kv.split('=')[1]))
 for _ in range(reps):
     # one bench step: sample, solve, scan, winner, mask, closed-form fit
     ctx.batch_fit(0xC0FFEE, 0, H)

@@ -1,14 +1,15 @@
 #!/usr/bin/env python3
 """SQ_INSTS_VALU / SQ_INSTS_SALU per kernel of ONE bench step (rocprofv3 --pmc, one pass):
-    python3 tools/valu_by_kernel.py plane [0|1]      (scan_bound)"""
+    python3 tools/valu_by_kernel.py plane [0|1] [NAME=VALUE ...]      (scan_bound; options for tools/scan_once.py)
+Counters only: no tracing in the same pass."""
 import collections, csv, glob, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 w = sys.argv[1]
 bound = sys.argv[2] if len(sys.argv) > 2 else "0"
 d = "/tmp/valu_by_kernel"
 subprocess.run(["rm", "-rf", d])
-cmd = ["rocprofv3", "--pmc", "SQ_INSTS_VALU", "SQ_INSTS_SALU", "SQ_WAVES", "--kernel-trace", "-d", d, "--output-format",
-       "csv", "--", "python3", "tools/scan_once.py", w, "3", bound]
+cmd = ["rocprofv3", "--pmc", "SQ_INSTS_VALU", "SQ_INSTS_SALU", "SQ_WAVES", "-d", d, "--output-format",
+       "csv", "--", "python3", "tools/scan_once.py", w, "3", bound] + sys.argv[3:]
 subprocess.run(cmd, cwd=ROOT, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=300)
 f = glob.glob(d + "/**/*counter_collection.csv", recursive=True)[0]
 acc = collections.defaultdict(lambda: collections.defaultdict(float))
