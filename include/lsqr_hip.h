@@ -363,6 +363,51 @@ LSQR_API int lsqr_ransac_grouped(lsqr_ctx *ctx, const int32_t *groups /* lsqr_co
                                  uint64_t *offsets_out   /* nullable, host: n_groups + 1 */,
                                  lsqr_ransac_info *infos /* host, n_groups */,
                                  int32_t *status_out     /* host, n_groups */);
+/* Grouped sequential RANSAC: several models per label over the records the context already holds on the device --
+ * lsqr_ransac_grouped's records and labels, lsqr_ransac_many_sequential's rounds.  It works on the context's current
+ * upload or attach: lsqr_count(ctx) records at the context's pointer and stride, which are only read; attached
+ * (caller-owned) memory is never written.  Labels as in lsqr_ransac_grouped: group g is the records with
+ * groups[i] == g, in upload order; a record whose label is negative or >= n_groups belongs to no group.
+ *   on_device = 1: groups and labels_out are device pointers, and nothing per-record crosses to the host; 0: host
+ *     pointers -- then the labels go up and the result comes down by one copy each.  seeds, params_out, offsets_out,
+ *     infos, status_out and n_models_out are host pointers in both forms.
+ *   Contract: group g is decided exactly as lsqr_ransac_many_sequential decides problem g of a host call whose records
+ *     are the stable gather by label of the context's records, tightly packed, with offsets the prefix sums of the
+ *     group sizes and the same seeds (seeds[g * max_models + r]), max_models, min_votes, p, model and options.  The
+ *     records are grouped on the device as in lsqr_ransac_grouped (integer copies); round 0 runs on the same packed
+ *     bytes under the same offsets through the same job, and every later round is that entry point's own code
+ *     (csrc/grouped.h, csrc/many_sequential.h).  So everything that call writes is bit-identical, parameters, fit.cost
+ *     and the LM fields included; only info.evaluated is exempt, as it is between two calls of the existing entry
+ *     points.
+ *   labels_out (nullable, lsqr_count(ctx) entries in upload order): the round that claimed record i inside its group;
+ *     -1 for an unclaimed record and for a record in no group.  Every entry is written exactly once (no fill of the
+ *     caller's buffer precedes it).  offsets_out (nullable, host, n_groups + 1): the prefix sums of the group sizes.
+ *   Outputs: infos[g * max_models + r], status_out[g * max_models + r], row g * max_models + r of params_out and
+ *     n_models_out[g] follow lsqr_ransac_many_sequential's rules: LSQR_ERR_STATE and a zeroed info for a round that did
+ *     not run; the rejected round's row is written; a group of fewer than lsqr_min_subset records runs no round.
+ *     best_index and the fit origin of the first-record models refer to the group's compacted records, as there.
+ *   Models, taken from the context's lsqr_set_model: those of lsqr_ransac_many_sequential.  LSQR_MODEL_US_SINGLE,
+ *     LSQR_MODEL_US_POINTER and LSQR_MODEL_PHANTOM return LSQR_ERR_INVALID; so do records outside 2 .. 18 doubles (the
+ *     dense system with dim > 17); nothing is written, as there.
+ *   Checks, in this order: a null context is refused before anything is touched; the model; n_groups == 0 is a no-op
+ *     returning LSQR_OK; with max_models > 0 a null groups, seeds, params_out, infos, status_out or n_models_out
+ *     (LSQR_ERR_INVALID); p outside (0, 1) (LSQR_ERR_INVALID); n_groups or max_models > 2^31 - 1 (LSQR_ERR_INVALID); no
+ *     model, or no records in the context (LSQR_ERR_STATE); more than 2^32 - 16 records (LSQR_ERR_INVALID);
+ *     max_models == 0 returns LSQR_OK, zeroes n_models_out where given and writes nothing else.  Every argument error
+ *     writes nothing.
+ *   The context's upload, hypotheses, mask and spatial index are untouched; the work runs on the context's stream
+ *     (lsqr_set_stream), and the call returns after it has finished.  One synchronisation precedes round 0 (the
+ *     n_groups + 1 offsets cross to the host); then come those of the rounds.  The options "max_iterations",
+ *     "many_round_hypotheses", "dense_fast_solve", "dense_dd" and the 2^22 no-model stop apply per group and round, as
+ *     in the entry points it is made of.  lsqr_multi handles have no such form. */
+LSQR_API int lsqr_ransac_grouped_sequential(
+    lsqr_ctx *ctx, const int32_t *groups /* lsqr_count(ctx) entries, upload order */, size_t n_groups,
+    int on_device /* 1: groups, labels_out on the device; 0: host */, double p,
+    const uint64_t *seeds /* host, n_groups * max_models, seeds[g * max_models + r] */, size_t max_models,
+    uint64_t min_votes, double *params_out /* host, n_groups * max_models * lsqr_num_params */,
+    int32_t *labels_out /* nullable: lsqr_count(ctx) entries, upload order */,
+    uint64_t *offsets_out /* nullable, host: n_groups + 1 */, lsqr_ransac_info *infos /* host, n_groups * max_models */,
+    int32_t *status_out /* host, n_groups * max_models */, size_t *n_models_out /* host, n_groups */);
 /* Many independent RANSAC<T,S>::compute() problems (probabilistic overload, RANSAC.h:75-79) in one call.
  * Problem j is records [offsets[j], offsets[j+1]) of host_records (stride_bytes apart, laid out as for
  * lsqr_upload), walks sampler stream seeds[j] and is decided exactly as lsqr_ransac(ctx, p, seeds[j], NULL, 0, ...)

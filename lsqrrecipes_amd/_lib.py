@@ -108,6 +108,9 @@ SIGNATURES = {
                                               C.c_void_p, C.c_void_p]),
     "lsqr_ransac_grouped": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_int, C.c_double, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lsqr_ransac_grouped_sequential": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_int, C.c_double, C.c_void_p,
+                                                 C.c_size_t, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p]),
     "lsqr_ransac_many": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_double, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lsqr_ransac_many_lm": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_double, C.c_void_p,

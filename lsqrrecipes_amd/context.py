@@ -413,6 +413,86 @@ class Context:
                     cost=fit["cost"].copy(), reserved=fit["reserved"].copy(), params=params, consensus=cons,
                     offsets=offs)
 
+    def ransac_grouped_sequential(self, groups, n_groups, p, max_models, seeds=None, min_votes=0, want_labels=True,
+                                  labels_out=None):
+        """Several models per label over the records of the current upload / attach (lsqr_ransac_grouped_sequential):
+        ransac_grouped's records and labels, ransac_many_sequential's rounds.  Group g is the records i with
+        groups[i] == g, in upload order; a label that is negative or >= n_groups puts the record in no group.  The
+        records are grouped on the device and never cross to the host.  Every model ransac_many_sequential takes; group
+        g is decided, bit for bit, as that call decides problem g of the stable gather by label of the records with
+        seeds[g] (seeds: (n_groups, max_models), default 1 + g * max_models + r) and the same max_models, min_votes, p.
+        groups: a numpy integer array (host form), or a device tensor -- anything with data_ptr() and is_cuda, int32,
+        contiguous, one entry per record.  For the device form, labels_out may be a contiguous int32 device tensor of
+        one entry per record, which receives the labels without a copy to the host; nothing is allocated on the device
+        here.
+        -> ransac_many_sequential's dict (status ERR_STATE / zeros for rounds not run, params zero where status is not
+        OK); offsets: the prefix sums of the group sizes; labels: per record in upload order the round that claimed it
+        inside its group, -1 for an unclaimed record or one in no group -- a numpy array for the host form, the
+        caller's tensor for the device form (None unless want_labels, or where the device form got no labels_out)."""
+        if self.cfg is None:
+            raise L.LsqrError(L.ERR_STATE, "set_model has not been called")
+        n, m = int(n_groups), int(max_models)
+        if n < 0:
+            raise ValueError("n_groups must not be negative")
+        if m < 0:
+            raise ValueError("max_models must not be negative")
+        total = int(self._lib.lsqr_count(self._h))
+        on_device = hasattr(groups, "data_ptr")
+        labels = None
+        if on_device:
+            if not groups.is_cuda or "int32" not in str(groups.dtype) or not groups.is_contiguous():
+                raise ValueError("device groups must be a contiguous int32 device tensor")
+            if groups.numel() != total:
+                raise ValueError("one label per record")
+            g_ptr = groups.data_ptr()
+            l_ptr = None
+            if labels_out is not None and want_labels:
+                t = labels_out
+                if not (hasattr(t, "data_ptr") and t.is_cuda and "int32" in str(t.dtype) and t.is_contiguous()
+                        and t.numel() == total):
+                    raise ValueError("labels_out must be a contiguous int32 device tensor of one entry per record")
+                labels, l_ptr = t, t.data_ptr()
+        else:
+            if labels_out is not None:
+                raise ValueError("labels_out goes with device groups")
+            g = np.asarray(groups)
+            if g.dtype.kind not in "iu":
+                raise ValueError("groups must be integers")
+            if g.shape != (total,):
+                raise ValueError("one label per record")
+            # (labels beyond int32 are in no group, as -1 is)
+            g = np.ascontiguousarray(np.where((g >= 0) & (g <= 0x7FFFFFFF), g, -1) if g.dtype != np.int32 else g,
+                                     dtype=np.int32)
+            g_ptr = L.ptr(g)
+            labels = np.full(max(total, 1), -1, dtype=np.int32) if want_labels else None
+            l_ptr = L.ptr(labels)
+        if seeds is None:
+            seeds = 1 + np.arange(n * m, dtype=np.uint64).reshape(n, m)
+        seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
+        if seeds.shape != (n, m):
+            raise ValueError("one seed per group and model")
+        params = np.zeros((max(n * m, 1), self.P))
+        offs = np.zeros(n + 1, dtype=np.uint64)
+        infos = (L.RansacInfo * max(n * m, 1))()
+        status = np.full(max(n * m, 1), L.ERR_STATE, dtype=np.int32)
+        n_models = np.zeros(max(n, 1), dtype=np.uintp)
+        self._chk(self._lib.lsqr_ransac_grouped_sequential(
+            self._h, g_ptr, n, 1 if on_device else 0, float(p), L.ptr(seeds), m, int(min_votes), L.ptr(params), l_ptr,
+            L.ptr(offs), infos, L.ptr(status), L.ptr(n_models)))
+        status = status[:n * m].reshape(n, m)
+        params = params[:n * m].reshape(n, m, self.P)
+        params[status != L.OK] = 0.0
+        inf = np.ctypeslib.as_array(infos)[:n * m]
+        f = lambda name: inf[name].reshape(n, m).copy()
+        fit = inf["fit"]
+        h = lambda name: fit[name].reshape(n, m).copy()
+        if labels is not None and not on_device:
+            labels = labels[:total]
+        return dict(n_models=n_models[:n].astype(np.int64), params=params, labels=labels, status=status,
+                    fraction=f("fraction"), iterations=f("iterations"), best_index=f("best_index"),
+                    best_votes=f("best_votes"), evaluated=f("evaluated"), n_params=f("n_params"), n_used=h("n_used"),
+                    lm_info=h("lm_info"), lm_nfev=h("lm_nfev"), cost=h("cost"), offsets=offs)
+
     def _many_records(self, problems):
         if self.cfg is None:
             raise L.LsqrError(L.ERR_STATE, "set_model has not been called")

@@ -14,6 +14,9 @@
 //   k_grp_scatter  one lane per sorted position r: consensus[perm[r]] = the job's mask byte of r where r's problem has
 //                  a winner, else 0 (also for the records in no problem); perm is a permutation, so every byte of the
 //                  consensus is written exactly once
+//   k_grp_scatter_labels  (lsqr_ransac_grouped_sequential) one lane per sorted position r: labels[perm[r]] = the round
+//                  label of packed position r, or -1 for the records in no problem (r >= the grouped total); written
+//                  exactly once, as the consensus is
 //
 // "A problem with a winner" is one whose search took a finishing slot (fit.n_used > 0), NOT "status LSQR_OK": a winner
 // whose final least-squares fit fails ends LSQR_EMPTY with its hypothesis' consensus in the mask, and lsqr_ransac_many
@@ -31,6 +34,13 @@
 // context's records, tightly packed, bit for bit (integer copies), under the prefix sums of the group sizes -- the
 // bytes a host that had gathered them would upload -- and its kernels and host replay are many_run's /
 // many_dense_run's.
+//
+// lsqr_ransac_grouped_sequential (grouped_seq_run) is the same front half -- grouped_pack: keys, sort, offsets, the one
+// synchronisation, the gather -- followed by many_seq_run (many_sequential.h) on the resident packed buffer instead of
+// one job: round 0 reads what the gather wrote, the later rounds are many_seq_run's own, and its round labels, which
+// it leaves on the device in packed order, go back to upload order through k_grp_scatter_labels.  It equals
+// lsqr_ransac_many_sequential on the gather for the reason above, applied to round 0; every later round is the same
+// code on the same bytes.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -41,6 +51,7 @@
 
 #include "many.h"
 #include "many_dense.h"
+#include "many_sequential.h"
 #include "sort.h"
 
 namespace lsqr {
@@ -99,22 +110,29 @@ __global__ __launch_bounds__(kBlock) void k_grp_scatter(const uint32_t *__restri
   }
 }
 
+// perm: the sorted record indices; packed: the round labels of the first total sorted positions (the grouped records,
+// in packed order; unread where total is 0); labels: n entries in upload order
+__global__ __launch_bounds__(kBlock) void k_grp_scatter_labels(const uint32_t *__restrict__ perm, uint32_t n,
+                                                               uint32_t total, const int32_t *__restrict__ packed,
+                                                               int32_t *__restrict__ labels) {
+  for (uint64_t r = (uint64_t)blockIdx.x * kBlock + threadIdx.x; r < n; r += (uint64_t)gridDim.x * kBlock)
+    labels[perm[r]] = r < total ? packed[r] : -1;
+}
+
 inline unsigned grp_grid(uint64_t lanes) {
   return (unsigned)std::min<uint64_t>(std::max<uint64_t>((lanes + kBlock - 1) / kBlock, 1), kGrpMaxGrid);
 }
 
-// The call.  J: the job of the batched search as lsqr_ransac_grouped has filled it from the context (stream, model,
-// options, seeds, the host outputs; resident, no consensus_out, n = n_groups); its offsets are set here.  data /
-// stride / N: the context's records (stride in doubles).  groups / consensus_out (nullable): device pointers with
-// on_device, else host.  offsets_out: nullable.  run(J): many_run<M> or many_dense_run<NR>.
-template <class Run>
-int grouped_run(ManyJob &J, const double *data, size_t stride, size_t N, const int32_t *groups, int on_device,
-                uint8_t *consensus_out, uint64_t *offsets_out, Run &&run) {
+// The front half of both calls: the records grouped by label into B.d_data.  J: the job as the entry point has filled
+// it from the context (stream, W, buf; n = n_groups).  data / stride / N: the context's records (stride in doubles).
+// groups: a device pointer with on_device, else host.  offsets: the n_groups + 1 prefix sums of the group sizes, on
+// the host after the call's one synchronisation.  The sorted pairs stay in B.d_grp_keys[1] / B.d_grp_vals[1].
+inline int grouped_pack(ManyJob &J, const double *data, size_t stride, size_t N, const int32_t *groups, int on_device,
+                        std::vector<uint64_t> &offsets) {
   ManyBufs &B = *J.buf;
   const size_t NG = J.n;
   const uint32_t n = (uint32_t)N, ng = (uint32_t)NG;
   const size_t W = (size_t)J.W;
-  int st;
   unsigned bits = 0;  // of the largest key, n_groups
   while (bits < 32 && (NG >> bits) != 0) bits++;
 
@@ -148,7 +166,7 @@ int grouped_run(ManyJob &J, const double *data, size_t stride, size_t N, const i
   uint64_t *h_off = (uint64_t *)B.h_grp;
   MANYCHK(hipMemcpyAsync(h_off, B.d_grp_off, sizeof(uint64_t) * (NG + 1), hipMemcpyDeviceToHost, J.stream));
   MANYCHK(hipStreamSynchronize(J.stream));  // the one wait before the search: its rounds are planned from host offsets
-  std::vector<uint64_t> offsets(h_off, h_off + NG + 1);
+  offsets.assign(h_off, h_off + NG + 1);
   if (offsets[0] != 0 || offsets[NG] > N) {
     snprintf(J.err, sizeof J.err, "group offsets out of range");
     return LSQR_ERR_HIP;
@@ -160,7 +178,7 @@ int grouped_run(ManyJob &J, const double *data, size_t stride, size_t N, const i
     }
   const uint64_t NT = offsets[NG];
 
-  // the packed copy, and the batched search on it
+  // the packed copy
   if (NT) {
     MANYCHK(many_grow(&B.d_data, &B.c_data, (size_t)NT * W));
     hipLaunchKernelGGL(k_grp_gather, dim3(grp_grid(NT * W)), dim3(kBlock), 0, J.stream,
@@ -168,6 +186,24 @@ int grouped_run(ManyJob &J, const double *data, size_t stride, size_t N, const i
                        (unsigned long long *)B.d_data);
     MANYCHK(hipGetLastError());
   }
+  return LSQR_OK;
+}
+
+// lsqr_ransac_grouped.  J: the job of the batched search as the entry point has filled it from the context (stream,
+// model, options, seeds, the host outputs; resident, no consensus_out, n = n_groups); its offsets are set here.
+// data / stride / N, groups: as grouped_pack.  consensus_out (nullable): a device pointer with on_device, else host.
+// offsets_out: nullable.  run(J): many_run<M> or many_dense_run<NR>.
+template <class Run>
+int grouped_run(ManyJob &J, const double *data, size_t stride, size_t N, const int32_t *groups, int on_device,
+                uint8_t *consensus_out, uint64_t *offsets_out, Run &&run) {
+  ManyBufs &B = *J.buf;
+  const size_t NG = J.n;
+  const uint32_t n = (uint32_t)N, ng = (uint32_t)NG;
+  int st;
+  std::vector<uint64_t> offsets;
+  if ((st = grouped_pack(J, data, stride, N, groups, on_device, offsets)) != LSQR_OK) return st;
+  const uint32_t *keys = B.d_grp_keys[1], *perm = B.d_grp_vals[1];
+  // the batched search on the packed copy
   J.offsets = offsets.data();
   if ((st = run(J)) != LSQR_OK) return st;
   // (the job ended in a synchronisation: B.d_mask holds every winner's consensus bytes in packed order)
@@ -177,7 +213,7 @@ int grouped_run(ManyJob &J, const double *data, size_t stride, size_t N, const i
   // a problem with a winner is one that took a finishing slot: many_end has set its fit's records in use, which
   // many_begin had zeroed for every problem.  (LSQR_OK, and the LSQR_EMPTY of a winner whose final fit failed: see
   // the head of this file.)
-  uint8_t *h_flag = (uint8_t *)B.h_grp + o_flag;
+  uint8_t *h_flag = (uint8_t *)B.h_grp + sizeof(uint64_t) * (NG + 1);
   for (size_t g = 0; g < NG; g++)
     h_flag[g] = J.infos[g].fit.n_used > 0 ? 1 : 0;
   MANYCHK(hipMemcpyAsync(B.d_grp_flag, h_flag, NG, hipMemcpyHostToDevice, J.stream));
@@ -193,6 +229,48 @@ int grouped_run(ManyJob &J, const double *data, size_t stride, size_t N, const i
   MANYCHK(hipStreamSynchronize(J.stream));  // the consensus is the caller's; h_grp is free again
   return LSQR_OK;
 }
+
+// lsqr_ransac_grouped_sequential.  J: filled from the context as for grouped_run (its seeds and outputs stay unset:
+// many_seq_run's rounds have their own).  K / P, seeds ... n_models_out, run(S): many_seq_run's.  labels_out
+// (nullable): N entries in upload order, a device pointer with on_device, else host.
+template <class Run>
+int grouped_seq_run(ManyJob &J, const double *data, size_t stride, size_t N, const int32_t *groups, int on_device,
+                    int K, int P, const uint64_t *seeds, size_t max_models, uint64_t min_votes, double *params_out,
+                    int32_t *labels_out, uint64_t *offsets_out, lsqr_ransac_info *infos, int32_t *status_out,
+                    size_t *n_models_out, Run &&run) {
+  ManyBufs &B = *J.buf;
+  const size_t NG = J.n;
+  int st;
+  if (J.W < 2 || J.W > kSeqMaxD) {  // (many_seq_run's check, before any work)
+    snprintf(J.err, sizeof J.err, "records of %d doubles (2 .. %d)", J.W, kSeqMaxD);
+    return LSQR_ERR_INVALID;
+  }
+  std::vector<uint64_t> offsets;
+  if ((st = grouped_pack(J, data, stride, N, groups, on_device, offsets)) != LSQR_OK) return st;
+  const uint32_t *perm = B.d_grp_vals[1];
+  const uint64_t NT = offsets[NG];
+  // the rounds on the packed copy; with labels wanted they stay in B.d_seq_labels, in packed order
+  J.offsets = offsets.data();
+  if ((st = many_seq_run(J, K, P, seeds, max_models, min_votes, params_out, nullptr, labels_out != nullptr, infos,
+                         status_out, n_models_out, run)) != LSQR_OK)
+    return st;
+  if (offsets_out) memcpy(offsets_out, offsets.data(), sizeof(uint64_t) * (NG + 1));
+  if (labels_out) {
+    int32_t *d_lab = labels_out;
+    if (!on_device) {
+      MANYCHK(many_grow(&B.d_grp_lab, &B.c_grp_lab, N));
+      d_lab = B.d_grp_lab;
+    }
+    hipLaunchKernelGGL(k_grp_scatter_labels, dim3(grp_grid(N)), dim3(kBlock), 0, J.stream, perm, (uint32_t)N,
+                       (uint32_t)NT, NT ? B.d_seq_labels : nullptr, d_lab);
+    MANYCHK(hipGetLastError());
+    if (!on_device) MANYCHK(hipMemcpyAsync(labels_out, d_lab, sizeof(int32_t) * N, hipMemcpyDeviceToHost, J.stream));
+  }
+  MANYCHK(hipStreamSynchronize(J.stream));  // the labels are the caller's; the last partition has read h_seq
+  return LSQR_OK;
+}
 #endif
 
 }  // namespace lsqr
+
+#undef MANYCHK

@@ -40,9 +40,9 @@
 #include "many.h"
 #include "many_dense.h"
 #include "many_exhaustive.h"
-#include "grouped.h"
 #include "sequential.h"
 #include "many_sequential.h"
+#include "grouped.h"
 
 #include <condition_variable>
 #include <mutex>
@@ -4264,12 +4264,12 @@ int lsqr_ransac_many_sequential(lsqr_ctx *c, const void *host_records, size_t st
         }
         if constexpr (M::IS_DENSE) {
           const int n = (int)J.cfg.dim;
-          return many_seq_run(J, n, n, seeds, max_models, min_votes, params_out, labels_out, infos, status_out,
+          return many_seq_run(J, n, n, seeds, max_models, min_votes, params_out, labels_out, false, infos, status_out,
                               n_models_out, [](ManyJob &S) -> int { return many_dense_run<M::NR>(S); });
         } else if constexpr (ManyModel<M>::value) {
           // (the sphere: J.lm says whether the rounds end in the LM stage, as lsqr_ransac_many_lm)
-          return many_seq_run(J, (int)M::K, (int)M::P, seeds, max_models, min_votes, params_out, labels_out, infos,
-                              status_out, n_models_out, [](ManyJob &S) -> int { return many_run<M>(S); });
+          return many_seq_run(J, (int)M::K, (int)M::P, seeds, max_models, min_votes, params_out, labels_out, false,
+                              infos, status_out, n_models_out, [](ManyJob &S) -> int { return many_run<M>(S); });
         } else {
           return LSQR_ERR_INVALID;
         }
@@ -4317,6 +4317,58 @@ int lsqr_ransac_grouped(lsqr_ctx *c, const int32_t *groups, size_t n_groups, int
                          [](ManyJob &S) -> int { return many_run<M>(S); });
     else
       return LSQR_ERR_INVALID;
+  });
+  if (st != LSQR_OK) return fail(c, st, "%s: %s", fn, J.err[0] ? J.err : "model not in this build");
+  return LSQR_OK;
+}
+
+// several models per label over the context's own records (grouped.h): the front half of lsqr_ransac_grouped, then
+// the rounds of lsqr_ransac_many_sequential on the resident packed copy, the round labels back in upload order
+int lsqr_ransac_grouped_sequential(lsqr_ctx *c, const int32_t *groups, size_t n_groups, int on_device, double p,
+                                   const uint64_t *seeds, size_t max_models, uint64_t min_votes, double *params_out,
+                                   int32_t *labels_out, uint64_t *offsets_out, lsqr_ransac_info *infos,
+                                   int32_t *status_out, size_t *n_models_out) {
+  const char *fn = "lsqr_ransac_grouped_sequential";
+  int st = need_ready(c, false);
+  if (st != LSQR_OK) return st;
+  const lsqr_model_cfg &cfg = c->cfg;
+  if (cfg.model == LSQR_MODEL_US_SINGLE || cfg.model == LSQR_MODEL_US_POINTER || cfg.model == LSQR_MODEL_PHANTOM)
+    return fail(c, LSQR_ERR_INVALID,
+                "%s: the models of lsqr_ransac_many, lsqr_ransac_many_lm and lsqr_ransac_many_dense only (model %d)",
+                fn, cfg.model);
+  if (n_groups == 0) return LSQR_OK;  // (the order of lsqr_ransac_grouped's checks, then lsqr_ransac_many_sequential's)
+  if (max_models > 0 && (!groups || !seeds || !params_out || !infos || !status_out || !n_models_out))
+    return fail(c, LSQR_ERR_INVALID, "%s: null argument", fn);
+  if (!(p > 0.0) || !(p < 1.0)) return fail(c, LSQR_ERR_INVALID, "%s: p must lie in (0, 1)", fn);
+  if (n_groups > 0x7FFFFFFFull) return fail(c, LSQR_ERR_INVALID, "%s: more than 2^31 - 1 groups", fn);
+  if (max_models > 0x7FFFFFFFull) return fail(c, LSQR_ERR_INVALID, "%s: too many models", fn);
+  if ((st = need_ready(c, true)) != LSQR_OK) return st;
+  if (c->n > 0xFFFFFFF0ull) return fail(c, LSQR_ERR_INVALID, "%s: more than 2^32 - 16 records", fn);
+  if (max_models == 0) {
+    if (n_models_out) memset(n_models_out, 0, sizeof(size_t) * n_groups);
+    return LSQR_OK;
+  }
+  ManyJob J;
+  many_job_from_ctx(c, J);  // (the same fill as many_call's: the bit-identity rests on it)
+  J.resident = true;
+  J.n = n_groups;
+  J.p = p;
+  const double *data = c->d_data;
+  const size_t stride = c->stride, N = c->n;
+  st = dispatch(c->cfg, [&](auto tag) -> int {
+    typedef typename decltype(tag)::type M;
+    if constexpr (M::IS_DENSE) {
+      const int n = (int)J.cfg.dim;
+      return grouped_seq_run(J, data, stride, N, groups, on_device, n, n, seeds, max_models, min_votes, params_out,
+                             labels_out, offsets_out, infos, status_out, n_models_out,
+                             [](ManyJob &S) -> int { return many_dense_run<M::NR>(S); });
+    } else if constexpr (ManyModel<M>::value) {  // (the sphere: J.lm says whether the rounds end in the LM stage)
+      return grouped_seq_run(J, data, stride, N, groups, on_device, (int)M::K, (int)M::P, seeds, max_models, min_votes,
+                             params_out, labels_out, offsets_out, infos, status_out, n_models_out,
+                             [](ManyJob &S) -> int { return many_run<M>(S); });
+    } else {
+      return LSQR_ERR_INVALID;
+    }
   });
   if (st != LSQR_OK) return fail(c, st, "%s: %s", fn, J.err[0] ? J.err : "model not in this build");
   return LSQR_OK;

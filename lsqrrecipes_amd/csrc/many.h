@@ -68,8 +68,8 @@ hipError_t many_grow(T **p, size_t *cap, size_t n) {
 #endif
 }  // namespace lsqr
 
-// a HIP call of the batched host code (many.h, many_lm.h, many_dense.h, many_exhaustive.h, grouped.h,
-// many_sequential.h; undefined at the end of the last): J is the job at hand, a ManyJob or the LM stage's ManyLmJob,
+// a HIP call of the batched host code (many.h, many_lm.h, many_dense.h, many_exhaustive.h, many_sequential.h,
+// grouped.h; undefined at the end of the last): J is the job at hand, a ManyJob or the LM stage's ManyLmJob,
 // whose err is the ManyJob's
 #define MANYCHK(call)                                                                                \
   do {                                                                                               \
@@ -334,8 +334,9 @@ struct ManyBufs {
   uint64_t *d_grp_off = nullptr;
   uint8_t *d_grp_flag = nullptr, *d_grp_cons = nullptr;
   int32_t *d_grp_labels = nullptr;
+  int32_t *d_grp_lab = nullptr;  // lsqr_ransac_grouped_sequential, host form: the round labels in upload order
   size_t c_grp_keys[2] = {0, 0}, c_grp_vals[2] = {0, 0}, c_grp_tmp = 0, c_hgrp = 0, c_grp_off = 0, c_grp_flag = 0,
-         c_grp_cons = 0, c_grp_labels = 0;
+         c_grp_cons = 0, c_grp_labels = 0, c_grp_lab = 0;
 };
 
 #if defined(__HIPCC__)
@@ -346,7 +347,7 @@ inline void many_free(ManyBufs *b) {
                  b->d_sub, b->d_marked, b->d_mom, b->d_ddpart, b->d_flags, b->d_exitems, b->d_exsmall, b->d_exbest,
                  b->d_seq_rec, b->d_seq_orig[0], b->d_seq_orig[1], b->d_seq_counts, b->d_seq_labels, b->d_seq_parts,
                  b->d_grp_keys[0], b->d_grp_keys[1], b->d_grp_vals[0], b->d_grp_vals[1], b->d_grp_tmp, b->d_grp_off,
-                 b->d_grp_flag, b->d_grp_cons, b->d_grp_labels};
+                 b->d_grp_flag, b->d_grp_cons, b->d_grp_labels, b->d_grp_lab};
   for (void *p : dev)
     if (p) (void)hipFree(p);
   if (b->h_stage) (void)hipHostFree(b->h_stage);

@@ -23,6 +23,10 @@
 // its problems, in their original order, tightly packed, with offsets of its own -- the input lsqr_ransac_many would
 // get from a host that had compacted them -- and its kernels and host replay are many_run's.  Independence is
 // lsqr_ransac_many's: which problems share a round's job does not enter any problem's result.
+//
+// "Upload indices" in this file are positions in the round-0 buffer: the caller's packed host records for
+// lsqr_ransac_many_sequential, the label-sorted packed copy for lsqr_ransac_grouped_sequential (grouped.h), which maps
+// the labels from there to its own record order.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -112,12 +116,16 @@ struct ManySeqProb {
 };
 
 // The call.  J: the job many_call has filled (host records, the caller's offsets; its seeds / outputs are unused: the
-// rounds' jobs have their own); K / P: the model's minimal subset and parameter count; seeds [j * max_models + r];
-// params_out, infos, status_out: rows [j][r]; labels_out nullable; run(sub): many_run<M> or many_dense_run<NR>.
+// rounds' jobs have their own), or grouped.h's with J.resident set: nothing is uploaded, and round 0 reads the packed
+// records that lie in B.d_data.  K / P: the model's minimal subset and parameter count; seeds [j * max_models + r];
+// params_out, infos, status_out: rows [j][r]; labels_out nullable, host; keep_labels: the labels are made and left
+// on the device -- B.d_seq_labels, offsets[n] entries in the order of the round-0 buffer, -1-filled (unmade where
+// offsets[n] is 0) -- and the call ends without a synchronisation: the caller's work follows on the stream, and the
+// caller waits.  run(sub): many_run<M> or many_dense_run<NR>.
 template <class Run>
 int many_seq_run(ManyJob &J, int K, int P, const uint64_t *seeds, size_t max_models, uint64_t min_votes,
-                 double *params_out, int32_t *labels_out, lsqr_ransac_info *infos, int32_t *status_out,
-                 size_t *n_models_out, Run &&run) {
+                 double *params_out, int32_t *labels_out, bool keep_labels, lsqr_ransac_info *infos,
+                 int32_t *status_out, size_t *n_models_out, Run &&run) {
   ManyBufs &B = *J.buf;
   const size_t N = J.n, MM = max_models;
   const uint64_t NT = J.offsets[N];
@@ -138,7 +146,7 @@ int many_seq_run(ManyJob &J, int K, int P, const uint64_t *seeds, size_t max_mod
 
   if ((st = many_upload(J)) != LSQR_OK) return st;
   int32_t *d_labels = nullptr;
-  if (labels_out && NT) {
+  if ((labels_out || keep_labels) && NT) {
     MANYCHK(many_grow(&B.d_seq_labels, &B.c_seq_labels, (size_t)NT));
     MANYCHK(hipMemsetAsync(B.d_seq_labels, 0xFF, sizeof(int32_t) * NT, J.stream));  // -1
     d_labels = B.d_seq_labels;
@@ -264,6 +272,7 @@ int many_seq_run(ManyJob &J, int K, int P, const uint64_t *seeds, size_t max_mod
     orig = B.d_seq_orig[dst];
     cur = dst;
   }
+  if (keep_labels) return LSQR_OK;
   if (d_labels) MANYCHK(hipMemcpyAsync(labels_out, d_labels, sizeof(int32_t) * NT, hipMemcpyDeviceToHost, J.stream));
   MANYCHK(hipStreamSynchronize(J.stream));  // the labels; the last partition has read h_seq
   return LSQR_OK;
@@ -272,4 +281,3 @@ int many_seq_run(ManyJob &J, int K, int P, const uint64_t *seeds, size_t max_mod
 
 }  // namespace lsqr
 
-#undef MANYCHK

@@ -431,6 +431,74 @@ class RANSAC {
     return fraction;
   }
 
+  // Grouped sequential RANSAC on resident records (not in the reference): several models per label.  Group g is the
+  // records i of `data` with groups[i] == g, in their order; a label that is negative or >= nGroups puts the record in
+  // no group.  Round r of group g walks sampler stream seed() + g * maxModels + r, so computeGroupedSequential(...)[g]
+  // and parameters[g] equal what computeManySequential returns / leaves for the per-group vectors, and labels
+  // (optional, one entry per record of `data`: the round that claimed the record inside its group, else -1) hold its
+  // per-group labels at the records' own places.  Invalid p or maxModels == 0 runs nothing, as there.
+  // The estimators computeManySequential batches run in ONE device call (lsqr_ransac_grouped_sequential: the records
+  // are grouped on the device, where they already are; only the group labels go up and the round labels come down).
+  // The others, and forceHostLoop(), go through computeManySequential itself on the per-group vectors, gathered from
+  // the vector `data` was made from.  THAT VECTOR MUST THEN STILL BE ALIVE AND UNCHANGED: ResidentData keeps a pointer
+  // to it, not a copy (see computeGrouped).
+  static std::vector<std::vector<double> > computeGroupedSequential(
+      std::vector<std::vector<std::vector<S> > > &parameters, ParametersEstimator<T, S> *paramEstimator,
+      ResidentData<T> &data, const std::vector<int> &groups, size_t nGroups, double desiredProbabilityForNoOutliers,
+      size_t maxModels, size_t minVotes, std::vector<int> *labels = NULL) {
+    if (!paramEstimator) throw std::invalid_argument("lsqrRecipes::RANSAC: null estimator");
+    if (groups.size() != data.size()) throw std::invalid_argument("lsqrRecipes::RANSAC: one group label per record");
+    const size_t n = nGroups, N = data.size();
+    const double p = desiredProbabilityForNoOutliers;
+    parameters.resize(n);
+    for (size_t g = 0; g < n; g++) parameters[g].clear();
+    if (labels) labels->assign(N, -1);
+    std::vector<std::vector<double> > fraction(n);
+    if (n == 0 || N == 0 || maxModels == 0 || p >= 1.0 || p <= 0.0) return fraction;
+    lsqr_model_cfg cfg;
+    const bool device = paramEstimator->deviceModel(cfg) && !forceHostLoop();
+    const bool batched =
+        device && lsqr_record_doubles(&cfg) <= 18 &&
+        (cfg.model == LSQR_MODEL_PLANE || cfg.model == LSQR_MODEL_LINE || cfg.model == LSQR_MODEL_SPHERE ||
+         cfg.model == LSQR_MODEL_DENSE || cfg.model == LSQR_MODEL_ABSOR || cfg.model == LSQR_MODEL_PIVOT ||
+         cfg.model == LSQR_MODEL_RAY || cfg.model == LSQR_MODEL_LINE2D);
+    if (!batched) {
+      const T *host = data.hostRecords();
+      std::vector<std::vector<T> > sets(n);
+      std::vector<std::vector<size_t> > index(n);
+      for (size_t i = 0; i < N; i++)
+        if (groups[i] >= 0 && (size_t)groups[i] < n) {
+          sets[(size_t)groups[i]].push_back(host[i]);
+          index[(size_t)groups[i]].push_back(i);
+        }
+      std::vector<std::vector<int> > lab;
+      fraction = computeManySequential(parameters, paramEstimator, sets, p, maxModels, minVotes, labels ? &lab : NULL);
+      if (labels)
+        for (size_t g = 0; g < n; g++)
+          for (size_t q = 0; q < lab[g].size(); q++) (*labels)[index[g][q]] = lab[g][q];
+      return fraction;
+    }
+    std::vector<uint64_t> seeds(n * maxModels);
+    for (size_t e = 0; e < n * maxModels; e++) seeds[e] = seed() + e;
+    std::vector<int32_t> glab(groups.begin(), groups.end());
+    lsqr_ctx *ctx = data.attach(cfg);
+    const int P = lsqr_num_params(&cfg);
+    std::vector<double> par(n * maxModels * (size_t)P);
+    std::vector<int32_t> lab(labels ? N : 0), status(n * maxModels);
+    std::vector<lsqr_ransac_info> info(n * maxModels);
+    std::vector<size_t> nModels(n, 0);
+    data.check(lsqr_ransac_grouped_sequential(ctx, &glab[0], n, 0, p, &seeds[0], maxModels, minVotes, &par[0],
+                                              lab.empty() ? NULL : &lab[0], NULL, &info[0], &status[0], &nModels[0]));
+    for (size_t g = 0; g < n; g++)
+      for (size_t r = 0; r < maxModels && status[g * maxModels + r] != LSQR_ERR_STATE; r++) {  // the rounds that ran
+        const size_t e = g * maxModels + r;
+        fraction[g].push_back(info[e].fraction);
+        if (r < nModels[g]) parameters[g].push_back(std::vector<S>(&par[e * P], &par[e * P] + info[e].n_params));
+      }
+    if (labels) labels->assign(lab.begin(), lab.end());
+    return fraction;
+  }
+
   // sampler stream of the probabilistic overload (default 1); set it to vary the hypotheses
   static uint64_t &seed() {
     static thread_local uint64_t s = 1;
