@@ -138,18 +138,18 @@ inline int grouped_pack(ManyJob &J, const double *data, size_t stride, size_t N,
 
   size_t tmp_bytes = 0;
   MANYCHK(sort_pairs_u32(nullptr, &tmp_bytes, nullptr, nullptr, nullptr, nullptr, N, bits, J.stream));
-  MANYCHK(many_grow(&B.d_grp_keys[0], &B.c_grp_keys[0], N));
-  MANYCHK(many_grow(&B.d_grp_keys[1], &B.c_grp_keys[1], N));
-  MANYCHK(many_grow(&B.d_grp_vals[0], &B.c_grp_vals[0], N));
-  MANYCHK(many_grow(&B.d_grp_vals[1], &B.c_grp_vals[1], N));
-  MANYCHK(many_grow(&B.d_grp_tmp, &B.c_grp_tmp, std::max<size_t>(tmp_bytes, 1)));
-  MANYCHK(many_grow(&B.d_grp_off, &B.c_grp_off, NG + 1));
-  MANYCHK(many_grow(&B.d_grp_flag, &B.c_grp_flag, NG));
+  MANYCHK(many_grow(B.d_grp_keys[0], N));
+  MANYCHK(many_grow(B.d_grp_keys[1], N));
+  MANYCHK(many_grow(B.d_grp_vals[0], N));
+  MANYCHK(many_grow(B.d_grp_vals[1], N));
+  MANYCHK(many_grow(B.d_grp_tmp, std::max<size_t>(tmp_bytes, 1)));
+  MANYCHK(many_grow(B.d_grp_off, NG + 1));
+  MANYCHK(many_grow(B.d_grp_flag, NG));
   const size_t o_flag = sizeof(uint64_t) * (NG + 1);
-  MANYCHK(many_grow_pinned(&B.h_grp, &B.c_hgrp, o_flag + NG));  // (every earlier call ended in a synchronisation)
+  MANYCHK(many_grow_pinned(B.h_grp, o_flag + NG));  // (every earlier call ended in a synchronisation)
   const int32_t *d_groups = groups;
   if (!on_device) {
-    MANYCHK(many_grow(&B.d_grp_labels, &B.c_grp_labels, N));
+    MANYCHK(many_grow(B.d_grp_labels, N));
     MANYCHK(hipMemcpyAsync(B.d_grp_labels, groups, sizeof(int32_t) * N, hipMemcpyHostToDevice, J.stream));
     d_groups = B.d_grp_labels;
   }
@@ -163,7 +163,7 @@ inline int grouped_pack(ManyJob &J, const double *data, size_t stride, size_t N,
   const uint32_t *keys = B.d_grp_keys[1], *perm = B.d_grp_vals[1];
   hipLaunchKernelGGL(k_grp_offsets, dim3(grp_grid(NG + 1)), dim3(kBlock), 0, J.stream, keys, n, ng, B.d_grp_off);
   MANYCHK(hipGetLastError());
-  uint64_t *h_off = (uint64_t *)B.h_grp;
+  uint64_t *h_off = (uint64_t *)B.h_grp.get();
   MANYCHK(hipMemcpyAsync(h_off, B.d_grp_off, sizeof(uint64_t) * (NG + 1), hipMemcpyDeviceToHost, J.stream));
   MANYCHK(hipStreamSynchronize(J.stream));  // the one wait before the search: its rounds are planned from host offsets
   offsets.assign(h_off, h_off + NG + 1);
@@ -180,10 +180,10 @@ inline int grouped_pack(ManyJob &J, const double *data, size_t stride, size_t N,
 
   // the packed copy
   if (NT) {
-    MANYCHK(many_grow(&B.d_data, &B.c_data, (size_t)NT * W));
+    MANYCHK(many_grow(B.d_data, (size_t)NT * W));
     hipLaunchKernelGGL(k_grp_gather, dim3(grp_grid(NT * W)), dim3(kBlock), 0, J.stream,
                        (const unsigned long long *)data, stride, perm, (uint32_t)W, NT,
-                       (unsigned long long *)B.d_data);
+                       (unsigned long long *)B.d_data.get());
     MANYCHK(hipGetLastError());
   }
   return LSQR_OK;
@@ -213,13 +213,13 @@ int grouped_run(ManyJob &J, const double *data, size_t stride, size_t N, const i
   // a problem with a winner is one that took a finishing slot: many_end has set its fit's records in use, which
   // many_begin had zeroed for every problem.  (LSQR_OK, and the LSQR_EMPTY of a winner whose final fit failed: see
   // the head of this file.)
-  uint8_t *h_flag = (uint8_t *)B.h_grp + sizeof(uint64_t) * (NG + 1);
+  uint8_t *h_flag = (uint8_t *)B.h_grp.get() + sizeof(uint64_t) * (NG + 1);
   for (size_t g = 0; g < NG; g++)
     h_flag[g] = J.infos[g].fit.n_used > 0 ? 1 : 0;
   MANYCHK(hipMemcpyAsync(B.d_grp_flag, h_flag, NG, hipMemcpyHostToDevice, J.stream));
   uint8_t *d_cons = consensus_out;
   if (!on_device) {
-    MANYCHK(many_grow(&B.d_grp_cons, &B.c_grp_cons, N));
+    MANYCHK(many_grow(B.d_grp_cons, N));
     d_cons = B.d_grp_cons;
   }
   hipLaunchKernelGGL(k_grp_scatter, dim3(grp_grid(N)), dim3(kBlock), 0, J.stream, keys, perm, n, ng, B.d_grp_flag,
@@ -258,7 +258,7 @@ int grouped_seq_run(ManyJob &J, const double *data, size_t stride, size_t N, con
   if (labels_out) {
     int32_t *d_lab = labels_out;
     if (!on_device) {
-      MANYCHK(many_grow(&B.d_grp_lab, &B.c_grp_lab, N));
+      MANYCHK(many_grow(B.d_grp_lab, N));
       d_lab = B.d_grp_lab;
     }
     hipLaunchKernelGGL(k_grp_scatter_labels, dim3(grp_grid(N)), dim3(kBlock), 0, J.stream, perm, (uint32_t)N,

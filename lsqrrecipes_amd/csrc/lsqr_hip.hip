@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../../include/lsqr_hip.h"
+#include "devbuf.h"
 #include "kernels.h"
 #include "models_nd.h"
 #include "dense.h"
@@ -89,8 +90,9 @@ struct PinLayout {
   BatchSlot batch[2];
   StepSlot step[2];
   double mdev_x[4][64];  // lsqr_moments_dev: staging slots of x
+  char pad3[(1 << 16) - 57344 - sizeof(double) * 4 * 64];
 };
-static_assert(sizeof(PinLayout) <= 1 << 16, "h_pin is 64 KiB");
+static_assert(sizeof(PinLayout) == 1 << 16, "h_pin is 64 KiB");
 static_assert(std::is_trivially_copyable_v<SolveOut> && std::is_trivially_copyable_v<LmpCtl> &&
               std::is_trivially_copyable_v<BoundsRow>, "staged with memcpy");
 static_assert(offsetof(PinLayout, mask_head) == 8192 && offsetof(PinLayout, winner) == 16384 &&
@@ -133,29 +135,27 @@ struct lsqr_ctx {
   int K = 0, P = 0, ND = 0, HS = 0;  // HS: row stride (doubles) of d_hparams
 
   const double *d_data = nullptr;  // observations (owned or attached)
-  double *d_data_owned = nullptr;
-  size_t data_cap = 0;  // doubles
+  DevBuf<double> d_data_owned;
   size_t n = 0, stride = 0;  // stride in doubles
 
   size_t H = 0, H_cap = 0;
-  uint32_t *d_subsets = nullptr;
-  double *d_hparams = nullptr;
-  float *d_hparams_f32 = nullptr;
-  unsigned long long *d_amb = nullptr;  // worklist of the dense MFMA filter
+  DevBuf<uint32_t> d_subsets;
+  DevBuf<double> d_hparams;
+  DevBuf<float> d_hparams_f32;
+  DevBuf<unsigned long long> d_amb;  // worklist of the dense MFMA filter
   bool absmax_valid = false;
   // spatial index of the point models (cells.h): Morton-sorted copy + one fp32 box per 128 records
-  double *d_sorted = nullptr;
-  uint32_t *d_queues = nullptr;  // work-queue counters of k_scan_cells
-  CellBox *d_boxes = nullptr;   // [n_cells cell boxes | merged boxes of the bounds pass (k_super_boxes)]
-  size_t sorted_cap = 0, boxes_cap = 0;  // doubles / boxes allocated
+  DevBuf<double> d_sorted;
+  DevBuf<uint32_t> d_queues;  // work-queue counters of k_scan_cells
+  DevBuf<CellBox> d_boxes;   // [n_cells cell boxes | merged boxes of the bounds pass (k_super_boxes)]
   uint32_t super_merge = 0;     // cells per merged box the second part currently holds (0: not built)
   // Selection counts of the bounded scans come back through pinned memory and steer the NEXT batches' launch sequence
   // (merged boxes or cells; pilot pass or not).  Two records, written alternately; a record is folded into
   // `bsel_known` only at a point where the host HAS synchronised with the batch that wrote it -- a ..._wait of its
   // slot, the end of a blocking entry point, or right before the record is reused (two bounded scans later) -- so the
   // launch sequence of a batch follows from the call sequence, never from host / device timing.
-  BoundSel *h_bsel = nullptr;   // pinned [2], 64 B apart
-  hipEvent_t bsel_ev[2] = {nullptr, nullptr};
+  PinBuf<BoundSel> h_bsel;   // pinned [2], 64 B apart
+  Event bsel_ev[2];
   bool bsel_pending[2] = {false, false};
   uint64_t bsel_seq_of[2] = {0, 0};
   uint32_t bsel_H_of[2] = {0, 0};
@@ -178,8 +178,7 @@ struct lsqr_ctx {
   // the fp32 filters' absmax and the Morton grid of the index
   BoundsRow h_bounds{};
   bool bounds_valid = false;
-  void *d_idx_scratch = nullptr;  // keys / permutation / radix-sort temporaries of the index build (kept)
-  size_t idx_scratch_cap = 0;
+  DevBuf<char> d_idx_scratch;  // keys / permutation / radix-sort temporaries of the index build (kept)
   uint64_t hyp_since_upload = 0;  // hypotheses scanned on this upload (index build heuristic)
   uint64_t hyp_expected = 0;      // hypotheses the caller still expects to scan on this upload (lsqr_ransac: numTries)
   unsigned dense_amb_max = 0;  // fullest worklist segment of the last fp32 dense scan (diagnostics)
@@ -188,24 +187,21 @@ struct lsqr_ctx {
                           // cores (hypothesis fragments through an LDS ring + next tile in registers), 0 = fp64 matrix
                           // cores; every filter sends its band to the exact fp64 re-check
   // dense_h16.h: the rows as fp16 fragment pairs (8 KiB per 32 rows) + the scaled right-hand sides, once per upload
-  uint4 *d_h16 = nullptr;
-  float *d_h16_bs = nullptr;
-  size_t h16_tiles_cap = 0;
+  DevBuf<uint4> d_h16;
+  DevBuf<float> d_h16_bs;
   bool h16_valid = false, h16_attr = false, h16_nomem = false;  // nomem: no room for the fragments on this upload
   int h16_unit = 0;       // 0: this device's matrix unit not probed yet, 1: keeps dense_h16.h's accumulation assumption, -1: not
   double h16_unit_dev = 0.0;  // the probe's worst deviation (u of the sum of magnitudes)
   double h16_pa = 1.0;
-  float *d_h16_thr = nullptr;  // (-a, band, -ph, 0) per hypothesis of the batch
+  DevBuf<float> d_h16_thr;  // (-a, band, -ph, 0) per hypothesis of the batch
   // us_h16.h: the frames as fp16 fragment pairs (6 KiB per 32 frames), once per upload; the batch's hypothesis fragments
-  uint4 *d_us16 = nullptr, *d_us16_x = nullptr;
-  size_t us16_tiles_cap = 0;
+  DevBuf<uint4> d_us16, d_us16_x;
   bool us16_valid = false, us16_attr = false, us16_nomem = false;
   Us16Scales us16_sc{};
   int opt_us_h16 = 1;  // US calibrations: 1 = agree() scan on the fp16 matrix cores (us_h16.h), 0 = packed fp32 filter
   int opt_dense_fast = 1;  // minimal solves: elimination first, SVD when near the rank decision
   int opt_us_fast = 1;     // US calibrations' minimal solves likewise (k_estimate_us)
-  uint8_t *d_refused = nullptr;  // k_estimate_phantom_lu: hypotheses left to the Jacobi kernel
-  size_t refused_cap = 0;
+  DevBuf<uint8_t> d_refused;  // k_estimate_phantom_lu: hypotheses left to the Jacobi kernel
   int opt_phantom_fast = 1;  // plane phantom's minimal solves: LU + inverse iteration first (> 1: its iteration limit), Jacobi SVD for what it refuses; 0: Jacobi only
   int opt_lm_tiles = 1;      // matrix-core LM pass: compacted consensus set in field-major tiles, next tile in flight
   int opt_us_mask_mfma = 1;  // US calibrations: mask + analytic moment block on the fp64 matrix cores (kernels.h)
@@ -218,40 +214,37 @@ struct lsqr_ctx {
   int opt_dense_wave = 3;  // dense minimal solves: 3 = elimination by one wave per system IN REGISTERS (n = 64; else as 1),
                            // 1 / 2 = in the wave's LDS area, four / two systems per workgroup, 0 = one workgroup per system
   int opt_dense_dd = 1;    // dense fit: systems the elimination refuses are solved again from the rows in double-double
-  double *d_ddpart = nullptr;  // partial double-double Gram blocks of k_gram_dd_dense (allocated on first use)
+  DevBuf<double> d_ddpart;  // partial double-double Gram blocks of k_gram_dd_dense (allocated on first use)
   int opt_index = 1, opt_cpt = 0, opt_cell = 0, opt_block = 0, opt_hsplit = 0, opt_pairs = 0, opt_pairs_waves = 0;  // 0 off, 1 auto, 2 always; cells per wave tile, cell size
-  uint8_t *d_valid = nullptr;
-  uint32_t *d_votes = nullptr;
-  uint32_t *d_ub = nullptr;  // per-hypothesis vote bound of the two-level scan's first level (k_cells_bounds)
+  DevBuf<uint8_t> d_valid;
+  DevBuf<uint32_t> d_votes;
+  DevBuf<uint32_t> d_ub;  // per-hypothesis vote bound of the two-level scan's first level (k_cells_bounds)
   // axis-sorted cells (axis.h; plane, 3-D): per-cell axis, the cells' sorted projections
-  CellAxis *d_axis = nullptr;
-  float *d_cellT = nullptr;
-  size_t axis_cap = 0, cellT_cap = 0;
+  DevBuf<CellAxis> d_axis;
+  DevBuf<float> d_cellT;
   bool axis_valid = false;
   int opt_mom_chunk = 0;          // chunk of the mask / moment passes in units of kBlock records (0 = default; A/B)
   int opt_hyp_order = 1;          // 1: a full count of the plane walks the batch in key order (k_plane_order)
   int opt_axis = 1;               // 1: the bounded scan of the plane takes its vote bounds by rank (k_bound_axis)
-  uint32_t *d_ub2 = nullptr;  // rank bounds: [upper | lower] of the candidates (compact order) | lower per hypothesis
-  uint8_t *d_paircnt = nullptr;   // k_scan_pairs: survivors per (cell, group of 64 hypotheses)
-  uint32_t *d_paircost = nullptr; // [n_cells cell costs | chunk sums]
-  uint32_t *d_vpart = nullptr;    // per-workgroup partial votes of k_scan_pairs
-  size_t paircnt_cap = 0, paircost_cap = 0, vpart_cap = 0;
-  float4 *d_hyps = nullptr;       // k_prepare_hyps: CM::Hyp of every hypothesis of the batch k_scan_pairs is counting
-  size_t hyps_cap = 0;
+  DevBuf<uint32_t> d_ub2;  // rank bounds: [upper | lower] of the candidates (compact order) | lower per hypothesis
+  DevBuf<uint8_t> d_paircnt;   // k_scan_pairs: survivors per (cell, group of 64 hypotheses)
+  DevBuf<uint32_t> d_paircost; // [n_cells cell costs | chunk sums]
+  DevBuf<uint32_t> d_vpart;    // per-workgroup partial votes of k_scan_pairs
+  DevBuf<float4> d_hyps;       // k_prepare_hyps: CM::Hyp of every hypothesis of the batch k_scan_pairs is counting
   int opt_prepared = 1;           // 1: cell models with PREPARED read Hyp from d_hyps; 0: load() per (cell, group) (A/B)
   // bounded scan (cells.h: k_pick_*): the selected hypotheses as a compact batch
-  uint32_t *d_sel = nullptr;        // [kPilots pilots | H_cap rest]
-  BoundSel *d_bsel = nullptr;
-  double *d_hparams2 = nullptr;
-  float *d_hparams2_f32 = nullptr;
-  uint32_t *d_votes2 = nullptr;     // [kPilots | H_cap]
+  DevBuf<uint32_t> d_sel;        // [kPilots pilots | H_cap rest]
+  DevBuf<BoundSel> d_bsel;
+  DevBuf<double> d_hparams2;
+  DevBuf<float> d_hparams2_f32;
+  DevBuf<uint32_t> d_votes2;     // [kPilots | H_cap]
   int opt_bound = 1;                // 1: batch entry points skip hypotheses that cannot win (exact winner), 0: count all
   uint32_t best_before = 0;         // exact votes of the best hypothesis of earlier batches (lsqr_ransac)
   bool allow_bound = false;         // set by the batch entry points around run_scan (lsqr_scan always counts all)
   uint64_t last_bound[4] = {0, 0, 0, 0};  // diagnostics of the last bounded scan: {used, pilots, rest, H}
   // chunked early exit of the dense / US scans (earlyexit.h)
-  void *d_ee = nullptr;             // [EeState | sel_c | sel_o x 2 | compact thresholds | compact fp32 rows]
-  EeState *h_ee = nullptr;          // pinned copy of the last early-exit scan's state (diagnostics: read after a synchronisation, lsqr_scan_work)
+  DevBuf<char> d_ee;             // [EeState | sel_c | sel_o x 2 | compact thresholds | compact fp32 rows]
+  PinBuf<EeState> h_ee;          // pinned copy of the last early-exit scan's state (diagnostics: read after a synchronisation, lsqr_scan_work)
   bool ee_last = false;             // the last scan of this context took the early-exit path
   uint64_t ee_H = 0, ee_n = 0;      // its batch size and observation count
   bool scanned = false;
@@ -268,7 +261,7 @@ struct lsqr_ctx {
   uint64_t data_epoch = 1;   // bumped whenever the records or the model change
   uint64_t lane_epoch = 0;   // (lanes) the epoch of the parent this lane is attached to
   std::vector<std::pair<std::string, int>> opt_log;  // options set on this context, replayed on new lanes
-  hipEvent_t slot_ev[2] = {nullptr, nullptr};  // lsqr_batch_fit_enqueue / _wait
+  Event slot_ev[2];  // lsqr_batch_fit_enqueue / _wait
   // The matrix-core filters of the dense / US / phantom scans decide their band from per-workgroup worklists; a segment
   // that overflowed (never seen) means "scan again without the filter".  The blocking entry points read the fill right
   // after the scan (one host synchronisation); lsqr_batch_fit_enqueue must not wait, so there the scan only notes the
@@ -282,27 +275,25 @@ struct lsqr_ctx {
   uint64_t ovf_reruns = 0;       // batches run again because a worklist segment overflowed (diagnostics)
   uint64_t slot_first[2] = {0, 0}, slot_H[2] = {0, 0};
   bool slot_busy[2] = {false, false};
-  hipEvent_t mdev_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // lsqr_moments_dev: staging slots of x
+  Event mdev_ev[4];  // lsqr_moments_dev: staging slots of x
   unsigned mdev_next = 0;
-  hipEvent_t step_ev[2] = {nullptr, nullptr};  // lsqr_step_finish_enqueue / _wait
+  Event step_ev[2];  // lsqr_step_finish_enqueue / _wait
   bool step_busy[2] = {false, false};
 
-  double *d_rows = nullptr;  // plane phantom: the data rows a_i as an n x 32 matrix (phantom.h)
-  size_t rows_cap = 0;
+  DevBuf<double> d_rows;  // plane phantom: the data rows a_i as an n x 32 matrix (phantom.h)
   bool rows_valid = false;
 
-  uint8_t *d_mask = nullptr;
-  size_t mask_cap = 0;
+  DevBuf<uint8_t> d_mask;
   bool mask_valid = false;
 
-  double *d_partials = nullptr;  // kMaxPartials * MOM_MAX
-  double *d_mom = nullptr;       // MOM_MAX
-  double *d_vec = nullptr;       // 32 doubles: origin / parameter vector handed to kernels
-  double *d_par = nullptr;       // 32 doubles: model parameters for mask/stats
-  double *d_best = nullptr;      // scan-parameter row of the best hypothesis so far (lsqr_ransac*)
-  LmState *d_lm = nullptr;
-  SolveOut *d_out = nullptr;
-  unsigned long long *d_counter = nullptr;
+  DevBuf<double> d_partials;  // kMaxPartials * MOM_MAX
+  DevBuf<double> d_mom;       // MOM_MAX
+  DevBuf<double> d_vec;       // 32 doubles: origin / parameter vector handed to kernels
+  DevBuf<double> d_par;       // 32 doubles: model parameters for mask/stats
+  DevBuf<double> d_best;      // scan-parameter row of the best hypothesis so far (lsqr_ransac*)
+  DevBuf<LmState> d_lm;
+  DevBuf<SolveOut> d_out;
+  DevBuf<unsigned long long> d_counter;
   bool origin_valid = false;  // d_par holds the parameters the device mask was made from (set_fit_origin)
   uint64_t win_rec = 0;       // first drawn record of the winning minimal subset (lsqr_ransac*, set_fit_origin)
   int opt_ppl = 0, opt_filter = 1, opt_lm_host = 1, opt_syrk_diag = 0;
@@ -313,19 +304,16 @@ struct lsqr_ctx {
   long long opt_max_iter = 0;  // 0 = the reference's bound (numTries <= C(N,k))
   long long opt_many_round = 0;  // lsqr_ransac_many: hypotheses per round (0 = kManyRoundDefault)
   bool opt_many_ex_fused = true;  // lsqr_ransac_many_exhaustive: small problems take k_many_ex_small
-  ManyBufs *many = nullptr;       // lsqr_ransac_many's buffers (its own: the context's upload is not touched)
+  std::unique_ptr<ManyBufs> many;  // lsqr_ransac_many's buffers (its own: the context's upload is not touched)
   // lsqr_ransac_sequential (sequential.h): the survivors of a round go from the current buffer into the OTHER of two
   // owned buffers (never into the caller's upload), their upload indices beside them; labels in upload order
-  double *d_seq_rec[2] = {nullptr, nullptr};
-  uint32_t *d_seq_orig[2] = {nullptr, nullptr};
-  size_t seq_rec_cap[2] = {0, 0}, seq_orig_cap[2] = {0, 0};
-  int32_t *d_seq_labels = nullptr;
-  uint32_t *d_seq_counts = nullptr;
-  size_t seq_labels_cap = 0, seq_counts_cap = 0;
+  DevBuf<double> d_seq_rec[2];
+  DevBuf<uint32_t> d_seq_orig[2];
+  DevBuf<int32_t> d_seq_labels;
+  DevBuf<uint32_t> d_seq_counts;
   LmState h_lm;  // host copy of the LM state (opt_lm_host)
-  double *d_lmrec = nullptr;  // consensus set copied tight and in order for the iterative fits (k_compact_*)
-  size_t lmrec_cap = 0;
-  unsigned long long *h_lmres = nullptr;  // pinned, device-visible: tagged granules written by k_lm_publish
+  DevBuf<double> d_lmrec;  // consensus set copied tight and in order for the iterative fits (k_compact_*)
+  PinBufCoherent<unsigned long long> h_lmres;  // pinned, device-visible: tagged granules written by k_lm_publish
   uint32_t lm_seq = 0;        // sequence number of the last evaluation (the tag the host polls for)
   int opt_lm_mfma = 1;        // 1: the LM pass accumulates (J | f)^T (J | f) on the matrix cores; 0: per-lane sums
   int opt_lm_fused = 1;       // 1: one launch per LM evaluation, result polled in pinned memory; 0: r01 path
@@ -340,8 +328,8 @@ struct lsqr_ctx {
                                          // bit-identical, measured no faster (r05: 12.4 us against 11.1 us per pass + broadcast at 245
                                          // workgroups -- with 1.9 waves per SIMD the pass is bound by its dependent chains, not by HBM)
   int opt_lm_persist_test_abort = 0;     // tests: workgroup 0 gives up at this evaluation (the fallback path)
-  LmpCtl *d_lmp = nullptr;
-  unsigned long long *h_lmcmd = nullptr;  // pinned, device-visible: the host's reply (coefficient granules + command)
+  DevBuf<LmpCtl> d_lmp;
+  PinBufCoherent<unsigned long long> h_lmcmd;  // pinned, device-visible: the host's reply (coefficient granules + command)
   bool counted = false;  // this context counts among the device's root contexts (lmp_pool: the share of a persistent fit)
   // diagnostics of the last persistent fit: {mode, G, evaluations, status, kernel us, fallbacks, host ns waiting, host ns stepping}
   uint64_t lmp_last[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -352,19 +340,18 @@ struct lsqr_ctx {
   // while earlier chunks are in flight to the device
   static constexpr int kUpSlots = 8;
   static constexpr size_t kUpChunk = (size_t)8 << 20;
-  void *h_up[kUpSlots] = {nullptr};
-  hipEvent_t up_ev[kUpSlots] = {nullptr};
+  PinBuf<char> h_up[kUpSlots];
+  Event up_ev[kUpSlots];
   int opt_upload_threads = -1;  // -1: LSQR_UPLOAD_THREADS or 4; 0: one plain hipMemcpy
   double last_upload_ms = 0.0;
-  PinLayout *h_pin = nullptr;  // pinned staging
-  void *h_batch = nullptr;  // pinned results of a lsqr_ransac batch (grown on demand)
-  size_t batch_pin_cap = 0;
+  PinBuf<PinLayout> h_pin;  // pinned staging
+  PinBuf<char> h_batch;  // pinned results of a lsqr_ransac batch (grown on demand)
 
   bool prof = false;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  Event ev0, ev1;
   // HIP-event pairs of profiled launches; resolved lazily (lsqr_profile_get) so that profiling
   // adds no host synchronisation between kernels
-  std::vector<hipEvent_t> ev_pool;
+  std::vector<Event> ev_pool;
   std::vector<std::pair<int, int>> ev_pending;  // (kernel id, pair index)
   int ev_next = 0;
   uint64_t launches[8] = {0};
@@ -417,10 +404,10 @@ struct ProfScope {
     constexpr int kPairs = 512;
     if (c->ev_next >= kPairs) prof_flush(c);
     if ((int)c->ev_pool.size() < 2 * (c->ev_next + 1)) {
-      hipEvent_t a = nullptr, b = nullptr;
-      if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) return;
-      c->ev_pool.push_back(a);
-      c->ev_pool.push_back(b);
+      Event a, b;
+      if (a.create() != hipSuccess || b.create() != hipSuccess) return;
+      c->ev_pool.push_back(std::move(a));
+      c->ev_pool.push_back(std::move(b));
     }
     pair = c->ev_next++;
     (void)hipEventRecord(c->ev_pool[2 * pair], c->stream);
@@ -449,45 +436,31 @@ constexpr size_t kPartialsBytes = sizeof(double) * 2 * kDenseBlocks * 2160;  // 
 int dense_pstride(int n) { return (dense_ne(n) + 1 + 7) & ~7; }
 
 template <class T>
-int ensure(lsqr_ctx *c, T **p, size_t *cap, size_t need) {
-  if (need <= *cap && *p) return LSQR_OK;
-  if (*p) HIPCHK(c, hipFree(*p));
-  *p = nullptr;
-  size_t ncap = std::max(need, *cap * 2);
-  HIPCHK(c, hipMalloc((void **)p, ncap * sizeof(T)));
-  *cap = ncap;
+int ensure(lsqr_ctx *c, DevBuf<T> &buf, size_t need) {
+  if (const size_t ncap = grow_double(buf, need)) HIPCHK(c, buf.alloc(ncap));
   return LSQR_OK;
 }
 
 int ensure_hyp(lsqr_ctx *c, size_t H) {
   if (H <= c->H_cap) return LSQR_OK;
   size_t cap = std::max<size_t>(H, 4096);
-  if (c->d_subsets) (void)hipFree(c->d_subsets);
-  if (c->d_hparams) (void)hipFree(c->d_hparams);
-  if (c->d_hparams_f32) (void)hipFree(c->d_hparams_f32);
-  c->d_hparams_f32 = nullptr;
-  if (c->d_valid) (void)hipFree(c->d_valid);
-  if (c->d_votes) (void)hipFree(c->d_votes);
-  if (c->d_ub) (void)hipFree(c->d_ub);
-  c->d_ub = nullptr;
-  if (c->d_ub2) (void)hipFree(c->d_ub2);
-  c->d_ub2 = nullptr;  // (allocated by the first bounded scan with rank bounds)
-  for (void *b : {(void *)c->d_sel, (void *)c->d_bsel, (void *)c->d_hparams2, (void *)c->d_hparams2_f32, (void *)c->d_votes2})
-    if (b) (void)hipFree(b);
-  c->d_sel = nullptr; c->d_bsel = nullptr; c->d_hparams2 = nullptr; c->d_hparams2_f32 = nullptr; c->d_votes2 = nullptr;
-  c->d_subsets = nullptr; c->d_hparams = nullptr; c->d_valid = nullptr; c->d_votes = nullptr;
   c->H_cap = 0;
-  HIPCHK(c, hipMalloc((void **)&c->d_subsets, cap * 64 * sizeof(uint32_t)));
-  HIPCHK(c, hipMalloc((void **)&c->d_hparams, cap * 64 * sizeof(double)));
-  HIPCHK(c, hipMalloc((void **)&c->d_hparams_f32, cap * 32 * sizeof(float)));  // M::SPF <= 32
-  HIPCHK(c, hipMalloc((void **)&c->d_valid, cap));
-  HIPCHK(c, hipMalloc((void **)&c->d_votes, cap * sizeof(uint32_t)));
-  HIPCHK(c, hipMalloc((void **)&c->d_ub, cap * sizeof(uint32_t)));
-  HIPCHK(c, hipMalloc((void **)&c->d_sel, (cap + kPilots) * sizeof(uint32_t)));
-  HIPCHK(c, hipMalloc((void **)&c->d_bsel, sizeof(BoundSel)));
-  HIPCHK(c, hipMalloc((void **)&c->d_hparams2, (cap + kPilots) * 64 * sizeof(double)));
-  HIPCHK(c, hipMalloc((void **)&c->d_hparams2_f32, (cap + kPilots) * 32 * sizeof(float)));
-  HIPCHK(c, hipMalloc((void **)&c->d_votes2, (cap + kPilots) * sizeof(uint32_t)));
+  // everything goes before anything comes back: the old and the new batch never have to fit side by side
+  c->d_subsets.reset(), c->d_hparams.reset(), c->d_hparams_f32.reset(), c->d_valid.reset(), c->d_votes.reset();
+  c->d_ub.reset(), c->d_sel.reset(), c->d_bsel.reset(), c->d_hparams2.reset(), c->d_hparams2_f32.reset();
+  c->d_votes2.reset();
+  c->d_ub2.reset();  // (allocated by the first bounded scan with rank bounds, sized from H_cap)
+  HIPCHK(c, c->d_subsets.alloc(cap * 64));
+  HIPCHK(c, c->d_hparams.alloc(cap * 64));
+  HIPCHK(c, c->d_hparams_f32.alloc(cap * 32));  // M::SPF <= 32
+  HIPCHK(c, c->d_valid.alloc(cap));
+  HIPCHK(c, c->d_votes.alloc(cap));
+  HIPCHK(c, c->d_ub.alloc(cap));
+  HIPCHK(c, c->d_sel.alloc(cap + kPilots));
+  HIPCHK(c, c->d_bsel.alloc(1));
+  HIPCHK(c, c->d_hparams2.alloc((cap + kPilots) * 64));
+  HIPCHK(c, c->d_hparams2_f32.alloc((cap + kPilots) * 32));
+  HIPCHK(c, c->d_votes2.alloc(cap + kPilots));
   c->H_cap = cap;
   return LSQR_OK;
 }
@@ -519,7 +492,7 @@ template <int D>
 int run_bounds(lsqr_ctx *c);
 
 // ---- selection feedback of the bounded scan (see lsqr_ctx::h_bsel) ----------------------------------------------
-static BoundSel *bsel_rec(lsqr_ctx *c, int r) { return (BoundSel *)((char *)c->h_bsel + 64 * r); }
+static BoundSel *bsel_rec(lsqr_ctx *c, int r) { return (BoundSel *)((char *)c->h_bsel.get() + 64 * r); }
 // the host has synchronised with the batch that wrote record r
 static void bsel_fold(lsqr_ctx *c, int r) {
   if (r < 0 || !c->h_bsel || !c->bsel_pending[r]) return;
@@ -608,12 +581,12 @@ int run_estimate(lsqr_ctx *c) {
       // the sweeps are bound by instruction issue, and a single-wave workgroup lands on any SIMD)
       if (c->opt_phantom_fast) {
         // r05: LU + inverse iteration (phantom.h: k_estimate_phantom_lu), the Jacobi SVD for what it refuses
-        int st = ensure(c, &c->d_refused, &c->refused_cap, std::max<size_t>(c->H, 1));
+        int st = ensure(c, c->d_refused, std::max<size_t>(c->H, 1));
         if (st != LSQR_OK) return st;
         uint8_t *d_ref = c->d_refused;
         static const bool dbg_on = getenv("LSQR_PHANTOM_DEBUG") != nullptr;
-        unsigned long long *d_dbg = nullptr;
-        if (dbg_on) (void)hipMalloc((void **)&d_dbg, sizeof(unsigned long long) * 4 * c->H);
+        DevBuf<unsigned long long> d_dbg;
+        if (dbg_on) (void)d_dbg.alloc(4 * c->H);
         hipLaunchKernelGGL(k_estimate_phantom_lu, dim3((unsigned)((c->H + 3) / 4)), dim3(256), 0, c->stream, c->d_data,
                            c->stride, c->n, c->d_subsets, (uint32_t)c->H, c->d_hparams, c->d_valid, d_ref,
                            c->opt_phantom_fast > 1 ? c->opt_phantom_fast : 96, d_dbg);
@@ -621,7 +594,6 @@ int run_estimate(lsqr_ctx *c) {
           std::vector<unsigned long long> hd(4 * c->H);
           (void)hipStreamSynchronize(c->stream);
           (void)hipMemcpy(hd.data(), d_dbg, hd.size() * 8, hipMemcpyDeviceToHost);
-          (void)hipFree(d_dbg);
           double sit = 0, slu = 0, sitr = 0, sfin = 0, mit = 0, mitr = 0, spcg = 0, mpcg = 0;
           size_t nref = 0, nconv = 0;
           for (size_t h = 0; h < c->H; h++) {
@@ -779,21 +751,13 @@ void drop_index(lsqr_ctx *c) {
   c->index_kd_levels = 0;
   c->axis_valid = false;
 }
-void free_index(lsqr_ctx *c) {
-  if (c->d_sorted) (void)hipFree(c->d_sorted);
-  if (c->d_boxes) (void)hipFree(c->d_boxes);
-  c->d_sorted = nullptr;
-  c->d_boxes = nullptr;
-  c->sorted_cap = c->boxes_cap = 0;
-  drop_index(c);
-}
 
 // k_bounds over the current upload (point models): min / max per dimension, max |coordinate|, non-finite count
 template <int D>
 int run_bounds(lsqr_ctx *c) {
   if (c->bounds_valid) return LSQR_OK;
   const int nb = grid_for(c->n, 256 * 16, 1024);
-  BoundsRow *rows = (BoundsRow *)c->d_partials;  // scratch: 1024 rows x 64 B (d_partials holds 4.4 MB)
+  BoundsRow *rows = (BoundsRow *)c->d_partials.get();  // scratch: 1024 rows x 64 B (d_partials holds 4.4 MB)
   static_assert(sizeof(BoundsRow) == 64, "BoundsRow is 8 words");
   {
     ProfScope ps(c, KID_ABSMAX);
@@ -863,22 +827,16 @@ int build_index(lsqr_ctx *c, uint32_t cell_pts) {
   constexpr size_t kSegExtBytes = 4096 * sizeof(SegExtent);
   // (+ one more index array and the compact fp32 copy of the coordinates for the k-d levels: 16 B per record)
   const size_t need = (5 + D) * words * sizeof(uint32_t) + tmp_bytes + 256 + kSegExtBytes;
-  if (need > c->idx_scratch_cap) {
-    if (c->d_idx_scratch) (void)hipFree(c->d_idx_scratch);
-    c->d_idx_scratch = nullptr;
-    c->idx_scratch_cap = 0;
-    IDXCHK(hipMalloc(&c->d_idx_scratch, need));
-    c->idx_scratch_cap = need;
-  }
-  if ((st = ensure(c, &c->d_sorted, &c->sorted_cap, std::max<size_t>(n, 1) * D)) != LSQR_OK) return st;
+  if (need > c->d_idx_scratch.cap()) IDXCHK(c->d_idx_scratch.alloc(need));
+  if ((st = ensure(c, c->d_sorted, std::max<size_t>(n, 1) * D)) != LSQR_OK) return st;
   const size_t n_sorted = n - (size_t)hb.nonfinite;  // the non-finite records carry the largest key: they sort to the tail
   const uint32_t n_cells = (uint32_t)((n_sorted + cell_pts - 1) / cell_pts);
-  if ((st = ensure(c, &c->d_boxes, &c->boxes_cap, std::max<size_t>((size_t)n_cells + n_cells / 2 + 2, 1))) != LSQR_OK)
+  if ((st = ensure(c, c->d_boxes, std::max<size_t>((size_t)n_cells + n_cells / 2 + 2, 1))) != LSQR_OK)
     return st;
   c->super_merge = 0;
   // every buffer is in place (kept across uploads): from here on the build is device work only
   ProfScope ps(c, KID_INDEX);
-  uint32_t *k_in = (uint32_t *)c->d_idx_scratch, *v_in = k_in + words, *k_out = v_in + words,
+  uint32_t *k_in = (uint32_t *)c->d_idx_scratch.get(), *v_in = k_in + words, *k_out = v_in + words,
            *v_out = k_out + words;
   uint32_t *q_b = v_out + words;
   float *xyz = (float *)(q_b + words);
@@ -939,10 +897,10 @@ int build_index(lsqr_ctx *c, uint32_t cell_pts) {
   // axis-sorted cells (axis.h): plane in 3-D, cells of 256 / 512 records
   c->axis_valid = false;
   if (D == 3 && c->opt_axis && c->cfg.model == LSQR_MODEL_PLANE && c->n_cells && (cell_pts == 512 || cell_pts == 256)) {
-    if ((st = ensure(c, &c->d_axis, &c->axis_cap, (size_t)c->n_cells)) != LSQR_OK) return st;
-    if ((st = ensure(c, &c->d_cellT, &c->cellT_cap, (size_t)c->n_cells * cell_pts)) != LSQR_OK) return st;
-    double *d_cmom = (double *)c->d_idx_scratch;  // 80 B per cell: the sort's scratch is free again (16 B per record)
-    if ((size_t)c->n_cells * 10 * sizeof(double) <= c->idx_scratch_cap) {
+    if ((st = ensure(c, c->d_axis, (size_t)c->n_cells)) != LSQR_OK) return st;
+    if ((st = ensure(c, c->d_cellT, (size_t)c->n_cells * cell_pts)) != LSQR_OK) return st;
+    double *d_cmom = (double *)c->d_idx_scratch.get();  // 80 B per cell: the sort's scratch is free again (16 B per record)
+    if ((size_t)c->n_cells * 10 * sizeof(double) <= c->d_idx_scratch.cap()) {
       const unsigned gc = (c->n_cells + 3) / 4;
       if (cell_pts == 512) {
         hipLaunchKernelGGL((k_cell_moments<8>), dim3(gc), dim3(256), 0, c->stream, c->d_sorted, c->n_sorted, c->n_cells,
@@ -988,7 +946,7 @@ int launch_scan_cells(lsqr_ctx *c, const ScanBatch &b) {
   if (c->n_cells == 0) return LSQR_OK;
   const size_t wtiles = ((size_t)c->n_cells + CPT - 1) / CPT;
   constexpr int wpb = BS / 64;  // waves per workgroup
-  if (!c->d_queues) HIPCHK(c, hipMalloc((void **)&c->d_queues, kQueues * kQueuePitch * sizeof(uint32_t)));
+  if (!c->d_queues) HIPCHK(c, c->d_queues.alloc(kQueues * kQueuePitch));
   uint32_t *d_next = c->d_queues;
   for (size_t h0 = 0; h0 < b.H; h0 += kScanChunk) {
     uint32_t hc = (uint32_t)std::min<size_t>(kScanChunk, b.H - h0);
@@ -1089,7 +1047,7 @@ int run_cells_bounds(lsqr_ctx *c, uint32_t *d_ub, uint32_t *d_nc = nullptr) {
   const uint32_t per = (nbox + gx - 1) / gx;
   gx = (nbox + per - 1) / per;
   hipLaunchKernelGGL((k_cells_bounds<CM, PP>), dim3(gx, gy), dim3(256), 0, c->stream, boxes, nbox, c->n_sorted,
-                     CM::ROW_F32 ? c->d_hparams_f32 : (const float *)c->d_hparams, c->d_hparams_f32,
+                     CM::ROW_F32 ? c->d_hparams_f32 : (const float *)c->d_hparams.get(), c->d_hparams_f32,
                      (uint32_t)c->H, cc, per, d_ub, d_nc ? c->d_counter + CNT_PAIRS : (unsigned long long *)nullptr, d_nc,
                      (uint8_t *)nullptr, 0u, (const uint32_t *)nullptr, 0u,  // (pair total: diagnostics only -- 8192
                      (uint32_t)(128 * PP) * merge, (const float4 *)nullptr);  // atomics on one address are ~100 us)
@@ -1125,8 +1083,8 @@ int run_scan_pairs(lsqr_ctx *c, const ScanBatch &b0) {
   const uint32_t gstride = groups <= 1 ? 1u : (groups + 15) / 16 * 16;  // 16-byte rows for k_tile_costs
   const uint32_t nchunks = (c->n_cells + kChunkCells - 1) / kChunkCells;
   int st;
-  if ((st = ensure(c, &c->d_paircnt, &c->paircnt_cap, (size_t)c->n_cells * gstride)) != LSQR_OK) return st;
-  if ((st = ensure(c, &c->d_paircost, &c->paircost_cap, (size_t)c->n_cells + nchunks)) != LSQR_OK) return st;
+  if ((st = ensure(c, c->d_paircnt, (size_t)c->n_cells * gstride)) != LSQR_OK) return st;
+  if ((st = ensure(c, c->d_paircost, (size_t)c->n_cells + nchunks)) != LSQR_OK) return st;
   uint32_t *d_cost = c->d_paircost, *d_csum = c->d_paircost + c->n_cells;
   const float *rows = CM::ROW_F32 ? b.spf : (const float *)b.sp;
   // the hypothesis-only part of level 1 once per batch instead of once per (cell, group): both kernels below read it
@@ -1135,7 +1093,7 @@ int run_scan_pairs(lsqr_ctx *c, const ScanBatch &b0) {
   if constexpr (kPrep) {
     if (prep) {
       const uint32_t slots = (Hc + 63) & ~63u;  // whole groups
-      if ((st = ensure(c, &c->d_hyps, &c->hyps_cap, (size_t)slots * HypWords<CM>::N4)) != LSQR_OK) return st;
+      if ((st = ensure(c, c->d_hyps, (size_t)slots * HypWords<CM>::N4)) != LSQR_OK) return st;
       hipLaunchKernelGGL((k_prepare_hyps<CM>), dim3((slots + 255) / 256), dim3(256), 0, c->stream, rows, b.spf, Hc, cc,
                          b.h_dev, b.h_off, c->d_hyps);
       HIPCHK(c, hipGetLastError());
@@ -1174,7 +1132,7 @@ int run_scan_pairs(lsqr_ctx *c, const ScanBatch &b0) {
     if (per_cu < 1) per_cu = 1;
     if (c->opt_pairs_waves > 0) per_cu = std::min(per_cu, c->opt_pairs_waves);
     const unsigned blocks = (unsigned)std::min<size_t>(((size_t)c->n_cells + wpb - 1) / wpb, (size_t)256 * per_cu);
-    int st2 = ensure(c, &c->d_vpart, &c->vpart_cap, (size_t)blocks * Hc);
+    int st2 = ensure(c, c->d_vpart, (size_t)blocks * Hc);
     if (st2 != LSQR_OK) return st2;
     ProfScope ps(c, KID_SCAN);
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(BS), lds, c->stream, c->d_sorted, c->n_sorted, c->d_boxes, c->n_cells,
@@ -1199,7 +1157,7 @@ int run_rank_bounds(lsqr_ctx *c, const uint32_t **lo_out) {
   typedef typename CM::M M;
   const uint32_t H = (uint32_t)c->H;
   int st;
-  if (!c->d_ub2) HIPCHK(c, hipMalloc((void **)&c->d_ub2, 3 * c->H_cap * sizeof(uint32_t)));  // [ub2 | lb2 | lo]
+  if (!c->d_ub2) HIPCHK(c, c->d_ub2.alloc(3 * c->H_cap));  // [ub2 | lb2 | lo]
   uint32_t *ub2 = c->d_ub2, *lb2 = c->d_ub2 + c->H_cap, *lo = c->d_ub2 + 2 * c->H_cap;
   const CellConsts cc = cell_consts((const CM *)nullptr, c->mc);
   // (the candidate list and their rows use the second pass's areas: free until the pilots have been counted)
@@ -1241,9 +1199,9 @@ int run_scan_bounded(lsqr_ctx *c) {
   // the record this scan will write: whatever it still holds (the scan two back) has to have landed before it is
   // reused, and is folded here at the latest
   if (!c->h_bsel) {
-    HIPCHK(c, hipHostMalloc((void **)&c->h_bsel, 128));
+    HIPCHK(c, c->h_bsel.alloc(128 / sizeof(BoundSel)));
     memset(c->h_bsel, 0, 128);
-    for (int r = 0; r < 2; r++) HIPCHK(c, hipEventCreateWithFlags(&c->bsel_ev[r], hipEventDisableTiming));
+    for (int r = 0; r < 2; r++) HIPCHK(c, c->bsel_ev[r].create(hipEventDisableTiming));
   }
   const int rec = (int)(c->bsel_seq & 1);
   if (c->bsel_pending[rec]) {
@@ -1311,12 +1269,12 @@ struct EeBuf {
 };
 int ee_buffers(lsqr_ctx *c, EeBuf *b) {
   const size_t bytes = 256 + 3 * kEeCap * sizeof(uint32_t) + (4 + 64) * (kEeCap + 64) * sizeof(float);
-  if (!c->d_ee) HIPCHK(c, hipMalloc(&c->d_ee, bytes));
+  if (!c->d_ee) HIPCHK(c, c->d_ee.alloc(bytes));
   if (!c->h_ee) {
-    HIPCHK(c, hipHostMalloc((void **)&c->h_ee, 64));
-    memset(c->h_ee, 0, 64);
+    HIPCHK(c, c->h_ee.alloc(1));
+    memset(c->h_ee, 0, sizeof(EeState));
   }
-  char *p = (char *)c->d_ee;
+  char *p = c->d_ee;
   b->st = (EeState *)p;
   b->sel_c = (uint32_t *)(p + 256);
   b->sel_o[0] = b->sel_c + kEeCap;
@@ -1389,7 +1347,7 @@ struct FilterScratch {
   double *thr;  // the fp64 filter: 2 doubles per hypothesis (H checked by its caller)
 };
 FilterScratch filter_scratch(lsqr_ctx *c) {
-  FilterScratchLayout *l = (FilterScratchLayout *)c->d_partials;
+  FilterScratchLayout *l = (FilterScratchLayout *)c->d_partials.get();
   return {l->thr32, l->sp32, l->segcnt, c->d_partials};
 }
 // before a filter's launches: no segment holds anything, no fill recorded (fs == null: the fp64 filter's one worklist)
@@ -1421,7 +1379,7 @@ int worklist_check(lsqr_ctx *c, uint32_t seg_cap, WorklistFill *w) {
 // thresholds assume (dense_h16.h: k_dense_h16_probe)?  c->h16_unit = 1 / -1.
 int h16_probe_unit(lsqr_ctx *c) {
   if (c->h16_unit != 0) return LSQR_OK;
-  if (!c->d_h16_thr) HIPCHK(c, hipMalloc((void **)&c->d_h16_thr, sizeof(float) * 4 * 8192));
+  if (!c->d_h16_thr) HIPCHK(c, c->d_h16_thr.alloc(4 * 8192));
   float *d_probe = c->d_h16_thr;  // (the batch's threshold block: not in use yet)
   hipLaunchKernelGGL(k_dense_h16_probe, dim3(1), dim3(64), 0, c->stream, d_probe);
   // ... and 64 instructions of random operands (65 536 sums of 16 products and an addend against fp64)
@@ -1458,16 +1416,11 @@ int ensure_us_h16(lsqr_ctx *c, bool *ok) {
   const Us16Scales sc = us16_scales<SINGLE>(X, Rm);
   if (!c->us16_valid || memcmp(&sc, &c->us16_sc, sizeof sc) != 0) {
     const size_t n_tiles = (c->n + 31) / 32 + 2;
-    if (n_tiles > c->us16_tiles_cap) {
-      if (c->d_us16) (void)hipFree(c->d_us16);
-      c->d_us16 = nullptr, c->us16_tiles_cap = 0;
-      if (hipMalloc((void **)&c->d_us16, n_tiles * (size_t)kUs16FrameTile) != hipSuccess) {
-        (void)hipGetLastError();  // (no room for the fragments: not an error -- the packed fp32 filter scans the records)
-        c->d_us16 = nullptr;
-        c->us16_nomem = true;
-        return LSQR_OK;
-      }
-      c->us16_tiles_cap = n_tiles;
+    constexpr size_t kTileElems = kUs16FrameTile / sizeof(uint4);
+    if (n_tiles * kTileElems > c->d_us16.cap() && c->d_us16.alloc(n_tiles * kTileElems) != hipSuccess) {
+      (void)hipGetLastError();  // (no room for the fragments: not an error -- the packed fp32 filter scans the records)
+      c->us16_nomem = true;
+      return LSQR_OK;
     }
     if constexpr (PH)  // (4 KiB per 32 frames of the 6 KiB the allocation holds)
       hipLaunchKernelGGL(k_phantom_rows_h16, dim3((unsigned)((n_tiles + 3) / 4)), dim3(256), 0, c->stream, c->d_data, c->stride,
@@ -1479,9 +1432,9 @@ int ensure_us_h16(lsqr_ctx *c, bool *ok) {
     c->us16_valid = true;
     c->us16_sc = sc;
   }
-  if (!c->d_us16_x) HIPCHK(c, hipMalloc((void **)&c->d_us16_x, (size_t)(8192 / 32) * 4096));
-  if (!c->d_h16_thr) HIPCHK(c, hipMalloc((void **)&c->d_h16_thr, sizeof(float) * 4 * 8192));
-  if (!c->d_amb) HIPCHK(c, hipMalloc((void **)&c->d_amb, sizeof(unsigned long long) * kAmbCap));
+  if (!c->d_us16_x) HIPCHK(c, c->d_us16_x.alloc((size_t)(8192 / 32) * 4096 / sizeof(uint4)));
+  if (!c->d_h16_thr) HIPCHK(c, c->d_h16_thr.alloc(4 * 8192));
+  if (!c->d_amb) HIPCHK(c, c->d_amb.alloc(kAmbCap));
   if constexpr (PH)  // (every time: one flag per context served two kernels and missed the second)
     (void)hipFuncSetAttribute((const void *)k_scan_phantom_h16, hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)phantom_h16_lds(kPh16HypChunk));
@@ -1543,20 +1496,16 @@ int ensure_dense_h16(lsqr_ctx *c, bool *ok) {
   if (c->h16_unit < 0) return LSQR_OK;
   if (!c->h16_valid || c->h16_pa != pa) {
     const size_t n_tiles = (c->n + 31) / 32 + 8;  // a workgroup pass reads up to 255 rows past its last one
-    if (n_tiles > c->h16_tiles_cap) {
-      if (c->d_h16) (void)hipFree(c->d_h16);
-      if (c->d_h16_bs) (void)hipFree(c->d_h16_bs);
-      c->d_h16 = nullptr, c->d_h16_bs = nullptr, c->h16_tiles_cap = 0;
+    if (n_tiles * 32 > c->d_h16_bs.cap()) {  // (the two grow together)
+      c->d_h16.reset(), c->d_h16_bs.reset();
       // (no room for the second copy of the rows: not an error -- the fp32 filter scans the fp64 rows)
-      if (hipMalloc((void **)&c->d_h16, n_tiles * (size_t)kH16TileBytes) != hipSuccess ||
-          hipMalloc((void **)&c->d_h16_bs, n_tiles * 32 * sizeof(float)) != hipSuccess) {
+      if (c->d_h16.alloc(n_tiles * (kH16TileBytes / sizeof(uint4))) != hipSuccess ||
+          c->d_h16_bs.alloc(n_tiles * 32) != hipSuccess) {
         (void)hipGetLastError();
-        if (c->d_h16) (void)hipFree(c->d_h16);
-        c->d_h16 = nullptr, c->d_h16_bs = nullptr;
+        c->d_h16.reset(), c->d_h16_bs.reset();
         c->h16_nomem = true;
         return LSQR_OK;
       }
-      c->h16_tiles_cap = n_tiles;
     }
     hipLaunchKernelGGL(k_dense_rows_h16, dim3((unsigned)((n_tiles + 3) / 4)), dim3(256), 0, c->stream, c->d_data,
                        c->stride, c->n, (int)c->cfg.dim, pa, c->d_h16, c->d_h16_bs, n_tiles);
@@ -1564,7 +1513,7 @@ int ensure_dense_h16(lsqr_ctx *c, bool *ok) {
     c->h16_valid = true;
     c->h16_pa = pa;
   }
-  if (!c->d_h16_thr) HIPCHK(c, hipMalloc((void **)&c->d_h16_thr, sizeof(float) * 4 * 8192));
+  if (!c->d_h16_thr) HIPCHK(c, c->d_h16_thr.alloc(4 * 8192));
   if (!c->h16_attr) {  // (per context: the attribute belongs to the device the context lives on)
     c->h16_attr = true;
     (void)hipFuncSetAttribute((const void *)k_scan_dense_h16<64>, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1844,7 +1793,7 @@ int scan_dense(lsqr_ctx *c, bool *done) {
   if (!c->opt_filter) return LSQR_OK;
   int st = ensure_absmax(c);
   if (st != LSQR_OK) return st;
-  if (!c->d_amb) HIPCHK(c, hipMalloc((void **)&c->d_amb, sizeof(unsigned long long) * kAmbCap));
+  if (!c->d_amb) HIPCHK(c, c->d_amb.alloc(kAmbCap));
   if (!(c->mc.absmax <= 1e100)) return LSQR_OK;  // finite, sane magnitudes: the filter's bound applies
   if constexpr (M::NR == 64) {
     // batch entry points: chunked early exit (earlyexit.h) -- hypotheses that can no longer become the running
@@ -2123,7 +2072,7 @@ void phantom_to_out(const PhantomFit &f, SolveOut *out) {
 // are materialised once per upload (256 B per frame) and summed on the matrix cores by the dense SYRK.
 int launch_moments_phantom(lsqr_ctx *c, int use_mask, size_t begin, size_t end, int *nmom) {
   if (!c->rows_valid) {
-    int st = ensure(c, &c->d_rows, &c->rows_cap, std::max<size_t>(c->n, 1) * 32);
+    int st = ensure(c, c->d_rows, std::max<size_t>(c->n, 1) * 32);
     if (st != LSQR_OK) return st;
     ProfScope ps(c, KID_MOMENTS);
     hipLaunchKernelGGL(k_phantom_rows, dim3((unsigned)((c->n * 8 + 255) / 256)), dim3(256), 0, c->stream,
@@ -2155,7 +2104,7 @@ int launch_solve_dense(lsqr_ctx *c, bool rows = false, int use_mask = 0, size_t 
                      c->opt_dense_fast, c->d_out, rows ? flag : (int *)nullptr);
   HIPCHK(c, hipGetLastError());
   if (!rows) return LSQR_OK;
-  if (!c->d_ddpart) HIPCHK(c, hipMalloc((void **)&c->d_ddpart, sizeof(double) * 2 * kDdNe * kDdBlocks));
+  if (!c->d_ddpart) HIPCHK(c, c->d_ddpart.alloc((size_t)2 * kDdNe * kDdBlocks));
   const int nb = (int)std::min<size_t>(kDdBlocks, (end - begin + 31) / 32);
   hipLaunchKernelGGL((k_gram_dd_dense<32>), dim3(nb), dim3(256), 0, c->stream, c->d_data, c->stride, begin, end, n,
                      use_mask ? c->d_mask : (const uint8_t *)nullptr, flag, c->d_ddpart);
@@ -2481,10 +2430,9 @@ int lm_persist_fit(lsqr_ctx *c, const double *tiles, size_t cnt, int nb, LmState
   typedef typename M::LmCoef Coef;
   constexpr int NCW = (int)(sizeof(Coef) / 8), NMOM = (int)M::NMOM_LM;
   if (!c->d_lmp) {
-    if (hipMalloc((void **)&c->d_lmp, sizeof(LmpCtl)) != hipSuccess) return LSQR_OK;
-    if (hipHostMalloc((void **)&c->h_lmcmd, sizeof(unsigned long long) * 256, hipHostMallocCoherent) != hipSuccess) {
-      (void)hipFree(c->d_lmp);
-      c->d_lmp = nullptr;
+    if (c->d_lmp.alloc(1) != hipSuccess) return LSQR_OK;
+    if (c->h_lmcmd.alloc(256) != hipSuccess) {
+      c->d_lmp.reset();
       return LSQR_OK;
     }
     memset(c->h_lmcmd, 0, sizeof(unsigned long long) * 256);
@@ -2666,14 +2614,14 @@ int run_fit(lsqr_ctx *c, int use_mask, SolveOut *out, bool have_moments = false,
             size_t cchunk = (c->n + cb - 1) / cb;
             cchunk = (cchunk + kBlock - 1) / kBlock * kBlock;
             cb = (int)((c->n + cchunk - 1) / cchunk);
-            uint32_t *d_cnt = (uint32_t *)c->d_partials, *d_off = d_cnt + 1024;  // scratch (4.4 MB buffer)
+            uint32_t *d_cnt = (uint32_t *)c->d_partials.get(), *d_off = d_cnt + 1024;  // scratch (4.4 MB buffer)
             hipLaunchKernelGGL(k_compact_count, dim3(cb), dim3(kBlock), 0, c->stream, c->d_mask, c->n, cchunk, d_cnt);
             hipLaunchKernelGGL(k_compact_scan, dim3(1), dim3(1024), 0, c->stream, d_cnt, cb, d_off);
             HIPCHK(c, hipGetLastError());
             HIPCHK(c, hipMemcpyAsync(pin + 200, d_off + cb, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, sync_stream(c));
             cnt = *(const uint32_t *)(pin + 200);
-            int st2 = ensure(c, &c->d_lmrec, &c->lmrec_cap, ((std::max<size_t>(cnt, 1) + 63) & ~(size_t)63) * M::ND);
+            int st2 = ensure(c, c->d_lmrec, ((std::max<size_t>(cnt, 1) + 63) & ~(size_t)63) * M::ND);
             if (st2 != LSQR_OK) return st2;
             if (tile_layout)  // the matrix-core pass reads tiles of 64 records stored field-major (kernels.h)
               hipLaunchKernelGGL((k_compact_write_tiles<M::ND>), dim3(cb), dim3(kBlock), 0, c->stream, c->d_data,
@@ -2819,7 +2767,7 @@ int run_fit(lsqr_ctx *c, int use_mask, SolveOut *out, bool have_moments = false,
                        xtol, gtol, maxfev, 100.0);
     HIPCHK(c, hipGetLastError());
     for (;;) {
-      HIPCHK(c, hipMemcpyAsync(c->d_vec, (const char *)c->d_lm + offsetof(LmState, xtrial),
+      HIPCHK(c, hipMemcpyAsync(c->d_vec, (const char *)c->d_lm.get() + offsetof(LmState, xtrial),
                                sizeof(double) * n, hipMemcpyDeviceToDevice, c->stream));
       if ((st = launch_moments<M>(c, use_mask, 0, c->n, 1, &nmom)) != LSQR_OK) return st;
       {
@@ -2838,7 +2786,7 @@ int run_fit(lsqr_ctx *c, int use_mask, SolveOut *out, bool have_moments = false,
 }
 
 int launch_mask(lsqr_ctx *c, size_t begin, size_t end) {
-  int st = ensure(c, &c->d_mask, &c->mask_cap, c->n);
+  int st = ensure(c, c->d_mask, c->n);
   if (st != LSQR_OK) return st;
   st = dispatch(c->cfg, [&](auto tag) -> int {
     typedef typename decltype(tag)::type M;
@@ -2892,7 +2840,7 @@ int run_mask(lsqr_ctx *c, size_t begin, size_t end, uint8_t *mask_out, uint64_t 
 int launch_mask_moments(lsqr_ctx *c, size_t begin, size_t end, int *nmom, bool *fused) {
   *fused = false;
   if (c->cfg.model == LSQR_MODEL_PHANTOM || !c->opt_fuse_mask) return LSQR_OK;
-  int st = ensure(c, &c->d_mask, &c->mask_cap, c->n);
+  int st = ensure(c, c->d_mask, c->n);
   if (st != LSQR_OK) return st;
   if (c->cfg.model == LSQR_MODEL_DENSE) {
     // dense system: mask + sum z z^T of the agreeing rows in one pass (dense.h: k_mask_syrk_dense); tight records
@@ -3052,17 +3000,13 @@ int lsqr_ctx_create(int device, lsqr_ctx **out) {
   lsqr_ctx *c = new lsqr_ctx();
   c->device = device;
   bool ok = hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking) == hipSuccess &&
-            hipEventCreate(&c->ev0) == hipSuccess && hipEventCreate(&c->ev1) == hipSuccess &&
-            hipMalloc((void **)&c->d_partials, kPartialsBytes) == hipSuccess &&
-            hipMalloc((void **)&c->d_mom, sizeof(double) * 4096) == hipSuccess &&
-            hipMalloc((void **)&c->d_vec, sizeof(double) * 128) == hipSuccess &&
-            hipMalloc((void **)&c->d_par, sizeof(double) * 128) == hipSuccess &&
-            hipMalloc((void **)&c->d_best, sizeof(double) * 128) == hipSuccess &&
-            hipMalloc((void **)&c->d_lm, sizeof(LmState)) == hipSuccess &&
-            hipMalloc((void **)&c->d_out, sizeof(SolveOut)) == hipSuccess &&
-            hipMalloc((void **)&c->d_counter, 64) == hipSuccess &&
-            hipHostMalloc(&c->h_pin, 1 << 16) == hipSuccess &&
-            hipHostMalloc((void **)&c->h_lmres, sizeof(unsigned long long) * 256, hipHostMallocCoherent) == hipSuccess;
+            c->ev0.create() == hipSuccess && c->ev1.create() == hipSuccess &&
+            c->d_partials.alloc(kPartialsBytes / sizeof(double)) == hipSuccess &&
+            c->d_mom.alloc(4096) == hipSuccess && c->d_vec.alloc(128) == hipSuccess &&
+            c->d_par.alloc(128) == hipSuccess && c->d_best.alloc(128) == hipSuccess &&
+            c->d_lm.alloc(1) == hipSuccess && c->d_out.alloc(1) == hipSuccess &&
+            c->d_counter.alloc(8) == hipSuccess &&  // CNT_* words
+            c->h_pin.alloc(1) == hipSuccess && c->h_lmres.alloc(256) == hipSuccess;
   if (ok) {
     memset(c->h_lmres, 0, sizeof(unsigned long long) * 256);
     ok = hipMemsetAsync(c->d_counter, 0, 64, c->own_stream) == hipSuccess;
@@ -3088,36 +3032,8 @@ void lsqr_ctx_destroy(lsqr_ctx *c) {
       c->lanes[i] = nullptr;
     }
   (void)hipStreamSynchronize(c->stream);
-  free_index(c);
-  many_free(c->many);
-  void *bufs[] = {c->d_seq_rec[0], c->d_seq_rec[1], c->d_seq_orig[0], c->d_seq_orig[1], c->d_seq_labels, c->d_seq_counts,
-                  c->d_refused, c->d_us16, c->d_us16_x, c->d_h16, c->d_h16_bs, c->d_h16_thr, c->d_ddpart, c->d_ub2, c->d_axis, c->d_cellT, c->d_vpart, c->d_paircnt, c->d_paircost, c->d_hyps, c->d_sel, c->d_bsel, c->d_hparams2, c->d_hparams2_f32, c->d_votes2, c->d_lmrec, c->d_idx_scratch, c->d_ub, c->d_queues, c->d_data_owned, c->d_subsets, c->d_hparams, c->d_hparams_f32, c->d_amb, c->d_valid, c->d_votes, c->d_mask, c->d_rows,
-                  c->d_partials, c->d_mom, c->d_vec, c->d_par, c->d_best, c->d_lm, c->d_out, c->d_counter};
-  for (void *b : bufs)
-    if (b) (void)hipFree(b);
-  if (c->h_bsel) (void)hipHostFree(c->h_bsel);
-  for (int r = 0; r < 2; r++)
-    if (c->bsel_ev[r]) (void)hipEventDestroy(c->bsel_ev[r]);
-  if (c->h_pin) (void)hipHostFree(c->h_pin);
-  if (c->h_lmres) (void)hipHostFree(c->h_lmres);
-  if (c->h_lmcmd) (void)hipHostFree(c->h_lmcmd);
-  if (c->d_lmp) (void)hipFree(c->d_lmp);
-  if (c->h_batch) (void)hipHostFree(c->h_batch);
-  for (int i = 0; i < lsqr_ctx::kUpSlots; i++) {
-    if (c->h_up[i]) (void)hipHostFree(c->h_up[i]);
-    if (c->up_ev[i]) (void)hipEventDestroy(c->up_ev[i]);
-  }
-  for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
-  if (c->ev0) (void)hipEventDestroy(c->ev0);
-  if (c->ev1) (void)hipEventDestroy(c->ev1);
-  for (hipEvent_t e : c->slot_ev)
-    if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : c->step_ev)
-    if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : c->mdev_ev)
-    if (e) (void)hipEventDestroy(e);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
-  delete c;
+  delete c;  // every buffer and event is a member: gone with the context
 }
 
 const char *lsqr_last_error(const lsqr_ctx *c) { return c ? c->err : "null context"; }
@@ -3225,8 +3141,8 @@ static int set_data_common(lsqr_ctx *c, size_t count, size_t stride_bytes) {
 // filled, so the host copies and the PCIe transfers overlap.
 static int staged_upload(lsqr_ctx *c, void *dst, const void *src, size_t bytes, int threads) {
   for (int i = 0; i < lsqr_ctx::kUpSlots; i++) {
-    if (!c->h_up[i]) HIPCHK(c, hipHostMalloc(&c->h_up[i], lsqr_ctx::kUpChunk));
-    if (!c->up_ev[i]) HIPCHK(c, hipEventCreateWithFlags(&c->up_ev[i], hipEventDisableTiming));
+    if (!c->h_up[i]) HIPCHK(c, c->h_up[i].alloc(lsqr_ctx::kUpChunk));
+    if (!c->up_ev[i]) HIPCHK(c, c->up_ev[i].create(hipEventDisableTiming));
   }
   const size_t chunk = lsqr_ctx::kUpChunk, nchunks = (bytes + chunk - 1) / chunk;
   std::atomic<size_t> next{0};
@@ -3254,7 +3170,7 @@ static int staged_upload(lsqr_ctx *c, void *dst, const void *src, size_t bytes, 
         }
       }
       const size_t off = i * chunk, len = std::min(chunk, bytes - off);
-      memcpy(c->h_up[slot], (const char *)src + off, len);
+      memcpy(c->h_up[slot].get(), (const char *)src + off, len);
       hipError_t e = hipMemcpyAsync((char *)dst + off, c->h_up[slot], len, hipMemcpyHostToDevice, c->stream);
       if (e == hipSuccess) e = hipEventRecord(c->up_ev[slot], c->stream);
       if (e != hipSuccess) err.store((int)e);
@@ -3277,7 +3193,7 @@ int lsqr_upload(lsqr_ctx *c, const void *host, size_t count, size_t stride_bytes
   if (!host && count) return fail(c, LSQR_ERR_INVALID, "null records");
   if ((st = set_data_common(c, count, stride_bytes)) != LSQR_OK) return st;
   size_t doubles = std::max<size_t>(count * c->stride, 1);
-  if ((st = ensure(c, &c->d_data_owned, &c->data_cap, doubles)) != LSQR_OK) return st;
+  if ((st = ensure(c, c->d_data_owned, doubles)) != LSQR_OK) return st;
   const size_t bytes = count * stride_bytes;
   // measured on the MI355X box (bench.py cold_call, 240 MB from a pageable numpy buffer): one plain
   // hipMemcpy 4.3 ms = 56 GB/s, the staged ring with 4 threads 5.1 ms -- so the plain copy is the default and
@@ -3438,7 +3354,7 @@ int lsqr_set_mask(lsqr_ctx *c, const uint8_t *mask) {
   int st = need_ready(c, true);
   if (st != LSQR_OK) return st;
   if (!mask) return fail(c, LSQR_ERR_INVALID, "null mask");
-  if ((st = ensure(c, &c->d_mask, &c->mask_cap, c->n)) != LSQR_OK) return st;
+  if ((st = ensure(c, c->d_mask, c->n)) != LSQR_OK) return st;
   HIPCHK(c, hipMemcpyAsync(c->d_mask, mask, c->n, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, sync_stream(c));
   c->mask_valid = true;
@@ -3542,7 +3458,7 @@ static int enqueue_moments(lsqr_ctx *c, int use_mask, size_t begin, size_t end, 
   if (!x) return fail(c, LSQR_ERR_INVALID, "moments need an origin / evaluation point");
   const int slot = staged ? c->mdev_next++ & 3 : 0;
   if (staged) {
-    if (!c->mdev_ev[slot]) HIPCHK(c, hipEventCreateWithFlags(&c->mdev_ev[slot], hipEventDisableTiming));
+    if (!c->mdev_ev[slot]) HIPCHK(c, c->mdev_ev[slot].create(hipEventDisableTiming));
     else HIPCHK(c, hipEventSynchronize(c->mdev_ev[slot]));
     memcpy(c->h_pin->mdev_x[slot], x, sizeof(double) * 32);
     x = c->h_pin->mdev_x[slot];
@@ -3691,7 +3607,7 @@ int lsqr_lm_step(lsqr_ctx *c, const double *block, double *x_trial_out, int *con
   fill_info(out, info);
   if (out.cont) {
     if (x_trial_out) {
-      HIPCHK(c, hipMemcpyAsync(c->h_pin->scratch, (const char *)c->d_lm + offsetof(LmState, xtrial),
+      HIPCHK(c, hipMemcpyAsync(c->h_pin->scratch, (const char *)c->d_lm.get() + offsetof(LmState, xtrial),
                                sizeof(double) * LM_NMAX, hipMemcpyDeviceToHost, c->stream));
       HIPCHK(c, sync_stream(c));
       memcpy(x_trial_out, c->h_pin->scratch, sizeof(double) * c->P);
@@ -3752,7 +3668,7 @@ int lsqr_residuals(lsqr_ctx *c, const double *params, size_t begin, size_t end, 
   if (begin == end) return LSQR_OK;
   // staged through d_rows (the phantom's row matrix is rebuilt on the next fit)
   c->rows_valid = false;
-  if ((st = ensure(c, &c->d_rows, &c->rows_cap, end - begin)) != LSQR_OK) return st;
+  if ((st = ensure(c, c->d_rows, end - begin)) != LSQR_OK) return st;
   HIPCHK(c, hipMemsetAsync(c->d_par, 0, sizeof(double) * 128, c->stream));
   HIPCHK(c, hipMemcpyAsync(c->d_par, params, sizeof(double) * c->P, hipMemcpyHostToDevice, c->stream));
   st = dispatch(c->cfg, [&](auto tag) -> int {
@@ -3881,14 +3797,8 @@ int lsqr_ransac(lsqr_ctx *c, double p, uint64_t seed, const uint32_t *subsets, s
     if (H == 0) break;
     // batch results land in pinned memory with one synchronisation: {votes[H], subsets[H*k], valid[H]}
     const size_t need = H * sizeof(uint32_t) * (1 + (size_t)k) + H;
-    if (need > c->batch_pin_cap) {
-      if (c->h_batch) (void)hipHostFree(c->h_batch);
-      c->h_batch = nullptr;
-      c->batch_pin_cap = 0;
-      HIPCHK(c, hipHostMalloc(&c->h_batch, std::max<size_t>(need, 1 << 16)));
-      c->batch_pin_cap = std::max<size_t>(need, 1 << 16);
-    }
-    uint32_t *p_votes = (uint32_t *)c->h_batch, *p_sub = p_votes + H;
+    if (need > c->h_batch.cap()) HIPCHK(c, c->h_batch.alloc(std::max<size_t>(need, 1 << 16)));
+    uint32_t *p_votes = (uint32_t *)c->h_batch.get(), *p_sub = p_votes + H;
     uint8_t *p_valid = (uint8_t *)(p_sub + H * k);
     if (subsets) {
       memcpy(p_sub, subsets + base * k, H * k * sizeof(uint32_t));
@@ -3961,7 +3871,7 @@ int lsqr_ransac_sequential(lsqr_ctx *c, double p, const uint64_t *seeds, size_t 
   const size_t n0 = c->n, stride0 = c->stride;
   const int W = c->ND;
   if (labels_out) {
-    if ((st = ensure(c, &c->d_seq_labels, &c->seq_labels_cap, n0)) != LSQR_OK) return st;
+    if ((st = ensure(c, c->d_seq_labels, n0)) != LSQR_OK) return st;
     HIPCHK(c, hipMemsetAsync(c->d_seq_labels, 0xFF, sizeof(int32_t) * n0, c->stream));  // -1
   }
   int32_t *const d_labels = labels_out ? c->d_seq_labels : nullptr;
@@ -3986,9 +3896,9 @@ int lsqr_ransac_sequential(lsqr_ctx *c, double p, const uint64_t *seeds, size_t 
       break;
     }
     const int dst = cur == 0 ? 1 : 0;
-    if ((st = ensure(c, &c->d_seq_rec[dst], &c->seq_rec_cap[dst], survivors * (size_t)W)) != LSQR_OK ||
-        (st = ensure(c, &c->d_seq_orig[dst], &c->seq_orig_cap[dst], survivors)) != LSQR_OK ||
-        (st = ensure(c, &c->d_seq_counts, &c->seq_counts_cap, (size_t)seq_chunks(n_cur))) != LSQR_OK) {
+    if ((st = ensure(c, c->d_seq_rec[dst], survivors * (size_t)W)) != LSQR_OK ||
+        (st = ensure(c, c->d_seq_orig[dst], survivors)) != LSQR_OK ||
+        (st = ensure(c, c->d_seq_counts, (size_t)seq_chunks(n_cur))) != LSQR_OK) {
       result = st;
       break;
     }
@@ -4033,7 +3943,7 @@ extern "C++" {
 // what every batched job takes from the context: the stream, the model, the options and the context's ManyBufs.  The
 // one place where an option reaches a job, for many_call's entry points and for lsqr_ransac_grouped alike.
 static void many_job_from_ctx(lsqr_ctx *c, ManyJob &J) {
-  if (!c->many) c->many = new ManyBufs();
+  if (!c->many) c->many.reset(new ManyBufs());
   J.stream = c->stream;
   J.cfg = c->cfg;
   J.mc = c->mc;
@@ -4045,7 +3955,7 @@ static void many_job_from_ctx(lsqr_ctx *c, ManyJob &J) {
   J.dense_fast = c->opt_dense_fast ? 1 : 0;
   J.dense_dd = c->opt_dense_dd ? 1 : 0;
   J.ex_fused = c->opt_many_ex_fused ? 1 : 0;
-  J.buf = c->many;
+  J.buf = c->many.get();
 }
 
 template <class Gate, class Run>
@@ -4571,7 +4481,7 @@ int lsqr_batch_fit_enqueue(lsqr_ctx *c, uint64_t seed, uint64_t first, size_t H,
   if ((st = enqueue_winner_finish(c, ORG_WINNER_DEV, pin->head, &fused)) != LSQR_OK) return st;
   if ((st = enqueue_fit(c, 1, fused, true)) != LSQR_OK) return st;
   HIPCHK(c, hipMemcpyAsync(&pin->out, c->d_out, sizeof(SolveOut), hipMemcpyDeviceToHost, c->stream));
-  if (!c->slot_ev[slot]) HIPCHK(c, hipEventCreateWithFlags(&c->slot_ev[slot], hipEventDisableTiming));
+  if (!c->slot_ev[slot]) HIPCHK(c, c->slot_ev[slot].create(hipEventDisableTiming));
   HIPCHK(c, hipEventRecord(c->slot_ev[slot], c->stream));
   c->slot_first[slot] = first;
   c->slot_H[slot] = H;
@@ -4699,7 +4609,7 @@ int lsqr_step_finish_enqueue(lsqr_ctx *c, const uint64_t *packed_dev, const doub
     if (st != LSQR_OK) return st;
     HIPCHK(c, hipMemcpyAsync(&pin->out, c->d_out, sizeof(SolveOut), hipMemcpyDeviceToHost, c->stream));
   }
-  if (!c->step_ev[slot]) HIPCHK(c, hipEventCreateWithFlags(&c->step_ev[slot], hipEventDisableTiming));
+  if (!c->step_ev[slot]) HIPCHK(c, c->step_ev[slot].create(hipEventDisableTiming));
   HIPCHK(c, hipEventRecord(c->step_ev[slot], c->stream));
   c->step_bsel_rec[slot] = c->bsel_last_rec;   // the step's scan (lsqr_step_scan) came before on this stream
   c->step_bsel_seq[slot] = c->bsel_last_rec >= 0 ? c->bsel_seq_of[c->bsel_last_rec] : 0;
@@ -5146,7 +5056,7 @@ int lsqr_multi_upload(lsqr_multi *m, const void *host, size_t count, size_t stri
     lsqr_ctx *c = m->ctx[r];
     if ((st = need_ready(c, false)) != LSQR_OK) return mfail(m, st, "context not ready", c);
     if ((st = set_data_common(c, count, stride_bytes)) != LSQR_OK) return mfail(m, st, "bad records", c);
-    if ((st = ensure(c, &c->d_data_owned, &c->data_cap, std::max<size_t>(count * c->stride, 1))) != LSQR_OK)
+    if ((st = ensure(c, c->d_data_owned, std::max<size_t>(count * c->stride, 1))) != LSQR_OK)
       return mfail(m, st, "replica allocation", c);
     if (count) MHIP(m, hipMemcpyPeerAsync(c->d_data_owned, c->device, c0->d_data, c0->device, count * stride_bytes,
                                            c->stream));

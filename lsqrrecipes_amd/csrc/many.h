@@ -41,6 +41,7 @@
 #include <thread>
 #include <vector>
 
+#include "devbuf.h"
 #include "host_entry.h"
 #include "kernels.h"
 
@@ -55,15 +56,14 @@ constexpr size_t kManyRoundDefault = 1u << 21;  // hypotheses per round (option 
 #if defined(__HIPCC__)
 // a device buffer of the batched calls, grown on demand
 template <class T>
-hipError_t many_grow(T **p, size_t *cap, size_t n) {
-  if (n <= *cap && *p) return hipSuccess;
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  const size_t want = std::max<size_t>(n + n / 4, 64);
-  hipError_t e = hipMalloc((void **)p, sizeof(T) * want);
-  if (e == hipSuccess) *cap = want;
-  return e;
+hipError_t many_grow(DevBuf<T> &b, size_t n) {
+  const size_t want = grow_quarter(b, n, 64);
+  return want ? b.alloc(want) : hipSuccess;
+}
+// pinned host memory; the caller has synchronised the stream if an old buffer may still be read by a copy
+inline hipError_t many_grow_pinned(PinBuf<char> &b, size_t bytes) {
+  const size_t want = grow_quarter(b, bytes, 1 << 16);
+  return want ? b.alloc(want) : hipSuccess;
 }
 #endif
 }  // namespace lsqr
@@ -289,90 +289,49 @@ __global__ __launch_bounds__(64) void k_many_solve(const double *__restrict__ da
 #endif
 
 // ---- host side -------------------------------------------------------------------------------------------------
-// device and pinned buffers of the call, owned by the context and grown on demand
+// device and pinned buffers of the call, owned by the context and grown on demand; deleting the set frees them all
+#if defined(__HIPCC__)
 struct ManyBufs {
-  double *d_data = nullptr, *d_hparams = nullptr, *d_best = nullptr, *d_partials = nullptr;
-  ManyItem *d_items = nullptr;
-  ManyTile *d_tiles = nullptr;
-  ManyPart *d_parts = nullptr;
-  uint8_t *d_valid = nullptr, *d_mask = nullptr;
-  uint32_t *d_votes = nullptr, *d_pairs = nullptr, *d_pbeg = nullptr, *d_fin = nullptr;
-  unsigned long long *d_counts = nullptr;
-  SolveOut *d_out = nullptr;
-  size_t c_data = 0, c_hparams = 0, c_best = 0, c_partials = 0, c_items = 0, c_tiles = 0, c_parts = 0, c_valid = 0,
-         c_mask = 0, c_votes = 0, c_pairs = 0, c_pbeg = 0, c_fin = 0, c_counts = 0, c_out = 0;
-  char *h_stage = nullptr, *h_pairs = nullptr;  // pinned: the round's tables and results / the winner pairs
-  size_t c_stage = 0, c_hpairs = 0;
+  DevBuf<double> d_data, d_hparams, d_best, d_partials;
+  DevBuf<ManyItem> d_items;
+  DevBuf<ManyTile> d_tiles;
+  DevBuf<ManyPart> d_parts;
+  DevBuf<uint8_t> d_valid, d_mask;
+  DevBuf<uint32_t> d_votes, d_pairs, d_pbeg, d_fin;
+  DevBuf<unsigned long long> d_counts;
+  DevBuf<SolveOut> d_out;
+  PinBuf<char> h_stage, h_pairs;  // pinned: the round's tables and results / the winner pairs
   ManyLmBufs lm;  // the LM stage of lsqr_ransac_many_lm / lsqr_lm_fit_many (many_lm.h)
   // lsqr_ransac_many_dense / lsqr_dense_fit_many (many_dense.h): the round's subsets, the minimal systems the
   // elimination refused, the problems' moment blocks, their double-double flags and the double-double Gram partials
-  uint32_t *d_sub = nullptr, *d_marked = nullptr;
-  double *d_mom = nullptr, *d_ddpart = nullptr;
-  int *d_flags = nullptr;
-  size_t c_sub = 0, c_marked = 0, c_mom = 0, c_ddpart = 0, c_flags = 0;
+  DevBuf<uint32_t> d_sub, d_marked;
+  DevBuf<double> d_mom, d_ddpart;
+  DevBuf<int> d_flags;
   // lsqr_ransac_many_exhaustive (many_exhaustive.h): the round's items, the fused path's problems, every problem's
   // running {votes, rank}, and two pinned staging buffers with the events that guard their reuse
-  char *d_exitems = nullptr, *d_exsmall = nullptr;
-  unsigned long long *d_exbest = nullptr;
-  size_t c_exitems = 0, c_exsmall = 0, c_exbest = 0;
-  char *h_ex[2] = {nullptr, nullptr};
-  size_t c_hex[2] = {0, 0};
-  hipEvent_t ev_ex[2] = {nullptr, nullptr};
+  DevBuf<char> d_exitems, d_exsmall;
+  DevBuf<unsigned long long> d_exbest;
+  PinBuf<char> h_ex[2];
+  Event ev_ex[2];
   // lsqr_ransac_many_sequential (many_sequential.h): the record buffer the survivors of a round are packed into (it
   // and d_data change places after every partition), the survivors' upload indices (two, in turn), the labels, the
   // partition's parts and their survivor counts, and the pinned staging of the parts
-  double *d_seq_rec = nullptr;
-  uint32_t *d_seq_orig[2] = {nullptr, nullptr}, *d_seq_counts = nullptr;
-  int32_t *d_seq_labels = nullptr;
-  char *d_seq_parts = nullptr, *h_seq = nullptr;
-  size_t c_seq_rec = 0, c_seq_orig[2] = {0, 0}, c_seq_counts = 0, c_seq_labels = 0, c_seq_parts = 0, c_hseq = 0;
+  DevBuf<double> d_seq_rec;
+  DevBuf<uint32_t> d_seq_orig[2], d_seq_counts;
+  DevBuf<int32_t> d_seq_labels;
+  DevBuf<char> d_seq_parts;
+  PinBuf<char> h_seq;
   // lsqr_ransac_grouped (grouped.h): the (label key, record index) pairs before and after the sort, the sort's
   // temporaries, the group offsets, the winner flags, the labels and the consensus of the host form, and the pinned
   // staging of the offsets and flags
-  uint32_t *d_grp_keys[2] = {nullptr, nullptr}, *d_grp_vals[2] = {nullptr, nullptr};
-  char *d_grp_tmp = nullptr, *h_grp = nullptr;
-  uint64_t *d_grp_off = nullptr;
-  uint8_t *d_grp_flag = nullptr, *d_grp_cons = nullptr;
-  int32_t *d_grp_labels = nullptr;
-  int32_t *d_grp_lab = nullptr;  // lsqr_ransac_grouped_sequential, host form: the round labels in upload order
-  size_t c_grp_keys[2] = {0, 0}, c_grp_vals[2] = {0, 0}, c_grp_tmp = 0, c_hgrp = 0, c_grp_off = 0, c_grp_flag = 0,
-         c_grp_cons = 0, c_grp_labels = 0, c_grp_lab = 0;
+  DevBuf<uint32_t> d_grp_keys[2], d_grp_vals[2];
+  DevBuf<char> d_grp_tmp;
+  PinBuf<char> h_grp;
+  DevBuf<uint64_t> d_grp_off;
+  DevBuf<uint8_t> d_grp_flag, d_grp_cons;
+  DevBuf<int32_t> d_grp_labels;
+  DevBuf<int32_t> d_grp_lab;  // lsqr_ransac_grouped_sequential, host form: the round labels in upload order
 };
-
-#if defined(__HIPCC__)
-inline void many_free(ManyBufs *b) {
-  if (!b) return;
-  void *dev[] = {b->d_data, b->d_hparams, b->d_best, b->d_partials, b->d_items, b->d_tiles, b->d_parts, b->d_valid,
-                 b->d_mask, b->d_votes, b->d_pairs, b->d_pbeg, b->d_fin, b->d_counts, b->d_out,
-                 b->d_sub, b->d_marked, b->d_mom, b->d_ddpart, b->d_flags, b->d_exitems, b->d_exsmall, b->d_exbest,
-                 b->d_seq_rec, b->d_seq_orig[0], b->d_seq_orig[1], b->d_seq_counts, b->d_seq_labels, b->d_seq_parts,
-                 b->d_grp_keys[0], b->d_grp_keys[1], b->d_grp_vals[0], b->d_grp_vals[1], b->d_grp_tmp, b->d_grp_off,
-                 b->d_grp_flag, b->d_grp_cons, b->d_grp_labels, b->d_grp_lab};
-  for (void *p : dev)
-    if (p) (void)hipFree(p);
-  if (b->h_stage) (void)hipHostFree(b->h_stage);
-  if (b->h_pairs) (void)hipHostFree(b->h_pairs);
-  if (b->h_seq) (void)hipHostFree(b->h_seq);
-  if (b->h_grp) (void)hipHostFree(b->h_grp);
-  for (int s = 0; s < 2; s++) {
-    if (b->h_ex[s]) (void)hipHostFree(b->h_ex[s]);
-    if (b->ev_ex[s]) (void)hipEventDestroy(b->ev_ex[s]);
-  }
-  many_lm_free(b->lm);
-  delete b;
-}
-
-// pinned host memory; the caller has synchronised the stream if an old buffer may still be read by a copy
-inline hipError_t many_grow_pinned(char **p, size_t *cap, size_t bytes) {
-  if (bytes <= *cap && *p) return hipSuccess;
-  if (*p) (void)hipHostFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  const size_t want = std::max<size_t>(bytes + bytes / 4, 1 << 16);
-  hipError_t e = hipHostMalloc((void **)p, want);
-  if (e == hipSuccess) *cap = want;
-  return e;
-}
 
 // One batched call.  The entry point fills it from the context (lsqr_hip.hip: many_call); p, seeds, consensus_out and
 // infos are a RANSAC call's and stay unset in a *_fit_many job, which reads none of them.
@@ -424,7 +383,7 @@ inline int many_upload(ManyJob &J) {
   const size_t W = J.W;
   const double *src = (const double *)J.host;
   if (NT > 0 && !J.resident) {
-    MANYCHK(many_grow(&B.d_data, &B.c_data, NT * W));
+    MANYCHK(many_grow(B.d_data, NT * W));
     if (J.stride != sizeof(double) * W) {
       J.packed.resize(NT * W);
       for (uint64_t i = 0; i < NT; i++) memcpy(&J.packed[i * W], J.host + i * J.stride, sizeof(double) * W);
@@ -559,14 +518,14 @@ int many_rounds(ManyJob &J, std::vector<ManyProb> &pr, int K, int SP, uint64_t s
     const size_t b_items = sizeof(ManyItem) * items.size(), b_tiles = sizeof(ManyTile) * tiles.size();
     const size_t o_tiles = (b_items + 15) & ~(size_t)15, o_votes = (o_tiles + b_tiles + 15) & ~(size_t)15;
     const size_t o_valid = o_votes + sizeof(uint32_t) * Ht;
-    MANYCHK(many_grow_pinned(&B.h_stage, &B.c_stage, o_valid + Ht));  // the previous round ended in a sync
+    MANYCHK(many_grow_pinned(B.h_stage, o_valid + Ht));  // the previous round ended in a sync
     memcpy(B.h_stage, items.data(), b_items);
     memcpy(B.h_stage + o_tiles, tiles.data(), b_tiles);
-    MANYCHK(many_grow(&B.d_items, &B.c_items, items.size()));
-    MANYCHK(many_grow(&B.d_tiles, &B.c_tiles, tiles.size()));
-    MANYCHK(many_grow(&B.d_hparams, &B.c_hparams, Ht * SP));
-    MANYCHK(many_grow(&B.d_valid, &B.c_valid, Ht));
-    MANYCHK(many_grow(&B.d_votes, &B.c_votes, Ht));
+    MANYCHK(many_grow(B.d_items, items.size()));
+    MANYCHK(many_grow(B.d_tiles, tiles.size()));
+    MANYCHK(many_grow(B.d_hparams, Ht * SP));
+    MANYCHK(many_grow(B.d_valid, Ht));
+    MANYCHK(many_grow(B.d_votes, Ht));
     MANYCHK(hipMemcpyAsync(B.d_items, B.h_stage, b_items, hipMemcpyHostToDevice, J.stream));
     MANYCHK(hipMemcpyAsync(B.d_tiles, B.h_stage + o_tiles, b_tiles, hipMemcpyHostToDevice, J.stream));
     MANYCHK(hipMemsetAsync(B.d_votes, 0, sizeof(uint32_t) * Ht, J.stream));
@@ -604,13 +563,13 @@ int many_rounds(ManyJob &J, std::vector<ManyProb> &pr, int K, int SP, uint64_t s
               std::chrono::duration<double, std::milli>(Clock::now() - t_replay).count());
     round++;
     if (np) {  // winner rows -> best[problem], on the device, before the next round overwrites the rows
-      MANYCHK(many_grow_pinned(&B.h_pairs, &B.c_hpairs, sizeof(uint32_t) * np));
+      MANYCHK(many_grow_pinned(B.h_pairs, sizeof(uint32_t) * np));
       size_t o = 0;
       for (auto &v : pairs) {
-        memcpy((uint32_t *)B.h_pairs + o, v.data(), sizeof(uint32_t) * v.size());
+        memcpy((uint32_t *)B.h_pairs.get() + o, v.data(), sizeof(uint32_t) * v.size());
         o += v.size();
       }
-      MANYCHK(many_grow(&B.d_pairs, &B.c_pairs, np));
+      MANYCHK(many_grow(B.d_pairs, np));
       MANYCHK(hipMemcpyAsync(B.d_pairs, B.h_pairs, sizeof(uint32_t) * np, hipMemcpyHostToDevice, J.stream));
       const uint32_t npairs = (uint32_t)(np / 2);
       hipLaunchKernelGGL(k_many_gather, dim3((unsigned)((npairs * SP + kBlock - 1) / kBlock)), dim3(kBlock), 0,
@@ -645,7 +604,7 @@ inline int many_begin(ManyJob &J, int W, int K, int SP, std::vector<ManyProb> &p
     pr[j].live = !pr[j].rs[RS_DONE];
   }
   if ((st = many_upload(J)) != LSQR_OK) return st;
-  MANYCHK(many_grow(&J.buf->d_best, &J.buf->c_best, std::max<size_t>(J.n, 1) * SP));
+  MANYCHK(many_grow(J.buf->d_best, std::max<size_t>(J.n, 1) * SP));
   return LSQR_OK;
 }
 
@@ -701,12 +660,12 @@ inline int many_stage_finish(ManyJob &J, const ManyFinish &F, bool with_fin) {
   const size_t NF = F.size();
   const size_t b_parts = sizeof(ManyPart) * F.parts.size(), b_pbeg = sizeof(uint32_t) * F.pbeg.size();
   const size_t o_pbeg = (b_parts + 15) & ~(size_t)15, o_fin = (o_pbeg + b_pbeg + 15) & ~(size_t)15;
-  MANYCHK(many_grow(&B.d_parts, &B.c_parts, F.parts.size()));
-  MANYCHK(many_grow(&B.d_pbeg, &B.c_pbeg, F.pbeg.size()));
-  if (with_fin) MANYCHK(many_grow(&B.d_fin, &B.c_fin, NF));
-  MANYCHK(many_grow(&B.d_counts, &B.c_counts, NF));
-  MANYCHK(many_grow(&B.d_out, &B.c_out, NF));
-  MANYCHK(many_grow_pinned(&B.h_stage, &B.c_stage, with_fin ? o_fin + sizeof(uint32_t) * NF : o_pbeg + b_pbeg));
+  MANYCHK(many_grow(B.d_parts, F.parts.size()));
+  MANYCHK(many_grow(B.d_pbeg, F.pbeg.size()));
+  if (with_fin) MANYCHK(many_grow(B.d_fin, NF));
+  MANYCHK(many_grow(B.d_counts, NF));
+  MANYCHK(many_grow(B.d_out, NF));
+  MANYCHK(many_grow_pinned(B.h_stage, with_fin ? o_fin + sizeof(uint32_t) * NF : o_pbeg + b_pbeg));
   memcpy(B.h_stage, F.parts.data(), b_parts);
   memcpy(B.h_stage + o_pbeg, F.pbeg.data(), b_pbeg);
   MANYCHK(hipMemcpyAsync(B.d_parts, B.h_stage, b_parts, hipMemcpyHostToDevice, J.stream));
@@ -804,7 +763,7 @@ inline int many_fit_begin(ManyJob &J, int W, const uint8_t *masks, std::vector<u
   if (sets.empty()) return LSQR_OK;
   if ((st = many_upload(J)) != LSQR_OK) return st;
   if (masks) {
-    MANYCHK(many_grow(&B.d_mask, &B.c_mask, NT));
+    MANYCHK(many_grow(B.d_mask, NT));
     MANYCHK(hipMemcpyAsync(B.d_mask, masks, NT, hipMemcpyHostToDevice, J.stream));
   }
   return LSQR_OK;
@@ -870,8 +829,8 @@ int many_finish(ManyJob &J, const std::vector<ManyProb> &pr, Org &&org) {
   const size_t NF = F.size();
   if (NF) {
     if ((st0 = many_stage_finish(J, F, true)) != LSQR_OK) return st0;
-    MANYCHK(many_grow(&B.d_partials, &B.c_partials, F.parts.size() * M::NMOM));
-    MANYCHK(many_grow(&B.d_mask, &B.c_mask, J.offsets[J.n]));
+    MANYCHK(many_grow(B.d_partials, F.parts.size() * M::NMOM));
+    MANYCHK(many_grow(B.d_mask, J.offsets[J.n]));
     hipLaunchKernelGGL((k_many_mask_moments<M>), dim3((unsigned)F.parts.size()), dim3(kBlock), 0, J.stream, B.d_data,
                        W, B.d_parts, B.d_best, org_off, J.mc, B.d_mask, B.d_counts, B.d_partials);
     MANYCHK(hipGetLastError());
@@ -892,7 +851,7 @@ int many_finish(ManyJob &J, const std::vector<ManyProb> &pr, Org &&org) {
         if (F.outs[f].ok)
           lp.push_back(ManyLmProb{J.offsets[j], J.offsets[j + 1] - J.offsets[j], 0, F.counts[f], (uint32_t)f, 0});
       }
-      ManyLmJob L = many_lm_job(J, B.d_mask, (const double *)((const char *)B.d_out + offsetof(SolveOut, params)),
+      ManyLmJob L = many_lm_job(J, B.d_mask, (const double *)((const char *)B.d_out.get() + offsetof(SolveOut, params)),
                                 sizeof(SolveOut) / sizeof(double));
       std::vector<ManyLmOut> res;
       if ((st0 = many_lm_run<M>(L, lp, res)) != LSQR_OK) return st0;
@@ -952,7 +911,7 @@ int many_lm_fit(ManyJob &J, const uint8_t *masks, const double *x0, lsqr_fit_inf
     const uint32_t j = sets[q];
     lp.push_back(ManyLmProb{J.offsets[j], J.offsets[j + 1] - J.offsets[j], 0, used[q], j, 0});
   }
-  MANYCHK(many_grow(&B.d_best, &B.c_best, J.n * P));  // the starts (no RANSAC rounds run here)
+  MANYCHK(many_grow(B.d_best, J.n * P));  // the starts (no RANSAC rounds run here)
   MANYCHK(hipMemcpyAsync(B.d_best, x0, sizeof(double) * J.n * P, hipMemcpyHostToDevice, J.stream));
   ManyLmJob L = many_lm_job(J, masks ? B.d_mask : nullptr, B.d_best, P);
   std::vector<ManyLmOut> res;

@@ -345,9 +345,9 @@ int many_dense_finish(ManyJob &J, const ManyFinish &F, const double *best, const
   int st;
   if (NF == 0) return LSQR_OK;
   if ((st = many_stage_finish(J, F, false)) != LSQR_OK) return st;  // (no kernel here reads fin)
-  MANYCHK(many_grow(&B.d_flags, &B.c_flags, NF));
-  MANYCHK(many_grow(&B.d_mom, &B.c_mom, NF * ps));
-  MANYCHK(many_grow(&B.d_partials, &B.c_partials, F.parts.size() * ps));
+  MANYCHK(many_grow(B.d_flags, NF));
+  MANYCHK(many_grow(B.d_mom, NF * ps));
+  MANYCHK(many_grow(B.d_partials, F.parts.size() * ps));
   MANYCHK(hipMemsetAsync(B.d_flags, 0, sizeof(int) * NF, J.stream));
   hipLaunchKernelGGL((k_many_dense_mask_moments<NR>), dim3((unsigned)F.parts.size()), dim3(256), 0, J.stream, B.d_data,
                      n, B.d_parts, best, J.mc.delta, mask_in, B.d_mask, B.d_counts, B.d_partials, ps);
@@ -369,7 +369,7 @@ int many_dense_finish(ManyJob &J, const ManyFinish &F, const double *best, const
     for (size_t f = 0; f < NF; f++) {
       if (!flags[f]) continue;
       if (!any) {
-        MANYCHK(many_grow(&B.d_ddpart, &B.c_ddpart, (size_t)2 * kDdNe * kDdBlocks));
+        MANYCHK(many_grow(B.d_ddpart, (size_t)2 * kDdNe * kDdBlocks));
         (void)hipFuncSetAttribute((const void *)k_dense_dd_solve, hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)dense_dd_lds(64));
         any = true;
@@ -402,8 +402,8 @@ int many_dense_run(ManyJob &J) {
   (void)hipFuncSetAttribute((const void *)k_many_dense_svd, hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)many_dense_lds(64));
   if ((st0 = many_rounds(J, pr, K, NR, many_dense_seg<NR>(), [&](size_t n_items, uint64_t Ht, size_t n_tiles) -> int {
-         MANYCHK(many_grow(&B.d_sub, &B.c_sub, Ht * n));
-         MANYCHK(many_grow(&B.d_marked, &B.c_marked, Ht + 1));
+         MANYCHK(many_grow(B.d_sub, Ht * n));
+         MANYCHK(many_grow(B.d_marked, Ht + 1));
          uint32_t *d_cnt = B.d_marked + Ht;  // the list's length, after the list
          MANYCHK(hipMemsetAsync(d_cnt, 0, sizeof(uint32_t), J.stream));
          if (n == 64 && J.dense_fast)
@@ -430,7 +430,7 @@ int many_dense_run(ManyJob &J) {
 
   // ---- finish: finish_ransac for every problem with a winner (the dense moments have no origin) -------------------
   ManyFinish F = many_plan_finish(J, pr, K, [](size_t, const ManyProb &) -> uint64_t { return 0; });
-  if (F.size()) MANYCHK(many_grow(&B.d_mask, &B.c_mask, J.offsets[J.n]));
+  if (F.size()) MANYCHK(many_grow(B.d_mask, J.offsets[J.n]));
   if ((st0 = many_dense_finish<NR>(J, F, B.d_best, nullptr)) != LSQR_OK) return st0;
   if ((st0 = many_fetch_finish(J, F, true)) != LSQR_OK) return st0;
   // fit.reserved = SolveOut::pad: 1: the double-double route (2: dense_dd 0 and a pivot below 1e-6, as lsqr_ransac);

@@ -189,9 +189,9 @@ __global__ __launch_bounds__(kManyBlock) void k_many_ex_small(const double *__re
 // pinned staging buffer `slot` of the call, at least `bytes` long, once the copies that last read it are done
 inline int many_ex_stage(ManyJob &J, int slot, size_t bytes, char **out) {
   ManyBufs &B = *J.buf;
-  if (!B.ev_ex[slot]) MANYCHK(hipEventCreateWithFlags(&B.ev_ex[slot], hipEventDisableTiming));
+  if (!B.ev_ex[slot]) MANYCHK(B.ev_ex[slot].create(hipEventDisableTiming));
   else MANYCHK(hipEventSynchronize(B.ev_ex[slot]));
-  MANYCHK(many_grow_pinned(&B.h_ex[slot], &B.c_hex[slot], bytes));
+  MANYCHK(many_grow_pinned(B.h_ex[slot], bytes));
   *out = B.h_ex[slot];
   return LSQR_OK;
 }
@@ -223,8 +223,8 @@ int many_ex_run(ManyJob &J) {
     else general.push_back((uint32_t)j);
   }
   if ((st = many_upload(J)) != LSQR_OK) return st;
-  MANYCHK(many_grow(&B.d_best, &B.c_best, NP * SP));
-  MANYCHK(many_grow(&B.d_exbest, &B.c_exbest, 2 * NP));
+  MANYCHK(many_grow(B.d_best, NP * SP));
+  MANYCHK(many_grow(B.d_exbest, 2 * NP));
   MANYCHK(hipMemsetAsync(B.d_exbest, 0, sizeof(unsigned long long) * 2 * NP, J.stream));
 
   int slot = 0;
@@ -233,12 +233,12 @@ int many_ex_run(ManyJob &J) {
     const size_t bytes = sizeof(ManyExSmall) * small.size();
     if ((st = many_ex_stage(J, slot, bytes, &h)) != LSQR_OK) return st;
     memcpy(h, small.data(), bytes);
-    MANYCHK(many_grow(&B.d_exsmall, &B.c_exsmall, bytes));
+    MANYCHK(many_grow(B.d_exsmall, bytes));
     MANYCHK(hipMemcpyAsync(B.d_exsmall, h, bytes, hipMemcpyHostToDevice, J.stream));
     MANYCHK(hipEventRecord(B.ev_ex[slot], J.stream));
     slot ^= 1;
     hipLaunchKernelGGL((k_many_ex_small<M>), dim3((unsigned)small.size()), dim3(kManyBlock), 0, J.stream, B.d_data, W,
-                       (const ManyExSmall *)B.d_exsmall, J.mc, B.d_best, B.d_exbest);
+                       (const ManyExSmall *)B.d_exsmall.get(), J.mc, B.d_best, B.d_exbest);
     MANYCHK(hipGetLastError());
   }
 
@@ -253,11 +253,11 @@ int many_ex_run(ManyJob &J) {
       seg_max = std::max(seg_max, segs);
       seg_sum += segs;
     }
-    MANYCHK(many_grow(&B.d_exitems, &B.c_exitems, sizeof(ManyExItem) * general.size()));
-    MANYCHK(many_grow(&B.d_tiles, &B.c_tiles, (size_t)((all / kManyBlock) * seg_max + seg_sum)));
-    MANYCHK(many_grow(&B.d_hparams, &B.c_hparams, (size_t)all * SP));
-    MANYCHK(many_grow(&B.d_valid, &B.c_valid, (size_t)all));
-    MANYCHK(many_grow(&B.d_votes, &B.c_votes, (size_t)all));
+    MANYCHK(many_grow(B.d_exitems, sizeof(ManyExItem) * general.size()));
+    MANYCHK(many_grow(B.d_tiles, (size_t)((all / kManyBlock) * seg_max + seg_sum)));
+    MANYCHK(many_grow(B.d_hparams, (size_t)all * SP));
+    MANYCHK(many_grow(B.d_valid, (size_t)all));
+    MANYCHK(many_grow(B.d_votes, (size_t)all));
   }
   std::vector<ManyExItem> items;
   std::vector<ManyTile> tiles;
@@ -295,7 +295,7 @@ int many_ex_run(ManyJob &J) {
     if ((st = many_ex_stage(J, slot, o_tiles + b_tiles, &h)) != LSQR_OK) return st;
     memcpy(h, items.data(), b_items);
     memcpy(h + o_tiles, tiles.data(), b_tiles);
-    if (b_items > B.c_exitems || tiles.size() > B.c_tiles || Ht > B.c_votes) {
+    if (b_items > B.d_exitems.cap() || tiles.size() > B.d_tiles.cap() || Ht > B.d_votes.cap()) {
       snprintf(J.err, sizeof J.err, "round %zu exceeds the buffers sized for it", rounds);
       return LSQR_ERR_HIP;
     }
@@ -304,7 +304,7 @@ int many_ex_run(ManyJob &J) {
     MANYCHK(hipEventRecord(B.ev_ex[slot], J.stream));
     slot ^= 1;
     MANYCHK(hipMemsetAsync(B.d_votes, 0, sizeof(uint32_t) * Ht, J.stream));
-    const ManyExItem *d_items = (const ManyExItem *)B.d_exitems;
+    const ManyExItem *d_items = (const ManyExItem *)B.d_exitems.get();
     hipLaunchKernelGGL((k_many_ex_estimate<M>), dim3((unsigned)((Ht + kBlock - 1) / kBlock)), dim3(kBlock), 0,
                        J.stream, B.d_data, W, d_items, (int)items.size(), (uint32_t)Ht, J.mc, B.d_hparams, B.d_valid);
     MANYCHK(hipGetLastError());

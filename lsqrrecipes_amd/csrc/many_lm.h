@@ -28,6 +28,7 @@
 #include <cstdlib>
 #include <vector>
 
+#include "devbuf.h"
 #include "kernels.h"
 #include "lm_core.h"
 
@@ -57,17 +58,15 @@ struct ManyLmOut {   // a finished problem (SolveOut's LM fields)
 
 // device and pinned buffers of the stage, owned by the context (ManyBufs) and grown on demand
 struct ManyLmBufs {
-  double *d_rec = nullptr, *d_partials = nullptr;
-  ManyLmProb *d_prob = nullptr;
-  ManyLmRaw *d_raw = nullptr;
-  ManyLmPart *d_parts = nullptr;
-  uint32_t *d_rcount = nullptr, *d_live = nullptr;
-  int *d_flag = nullptr;
-  LmState *d_state = nullptr;
-  ManyLmOut *d_out = nullptr;
-  size_t c_rec = 0, c_partials = 0, c_prob = 0, c_raw = 0, c_parts = 0, c_rcount = 0, c_live = 0, c_flag = 0,
-         c_state = 0, c_out = 0;
-  uint32_t *h_live = nullptr;  // pinned
+  DevBuf<double> d_rec, d_partials;
+  DevBuf<ManyLmProb> d_prob;
+  DevBuf<ManyLmRaw> d_raw;
+  DevBuf<ManyLmPart> d_parts;
+  DevBuf<uint32_t> d_rcount, d_live;
+  DevBuf<int> d_flag;
+  DevBuf<LmState> d_state;
+  DevBuf<ManyLmOut> d_out;
+  PinBuf<uint32_t> h_live;
 };
 
 #if defined(__HIPCC__)
@@ -232,15 +231,6 @@ __global__ __launch_bounds__(64 * kManyLmWaves) void k_many_lm_step(LmState *__r
   }
 }
 
-inline void many_lm_free(ManyLmBufs &b) {
-  void *dev[] = {b.d_rec, b.d_partials, b.d_prob, b.d_raw, b.d_parts, b.d_rcount, b.d_live, b.d_flag, b.d_state,
-                 b.d_out};
-  for (void *p : dev)
-    if (p) (void)hipFree(p);
-  if (b.h_live) (void)hipHostFree(b.h_live);
-  b = ManyLmBufs();
-}
-
 // One call of the stage (filled by many_lm_job, many.h).  The records (D doubles each, packed) and the mask (nullable:
 // every record) are on the device; problem q's start is row prob[q].xsrc of x0 (x0_stride doubles apart, on the
 // device).  The host fills rec, n, cnt (> 0: its masked records) and xsrc; the stage fills c0 and pbeg.
@@ -279,17 +269,17 @@ int many_lm_run(ManyLmJob &J, std::vector<ManyLmProb> &prob, std::vector<ManyLmO
       parts.push_back(ManyLmPart{P.c0 + r, P.c0 + std::min<uint64_t>(P.cnt, r + kManyPart), (uint32_t)q, 0});
   }
   const uint64_t C = c;
-  MANYCHK(many_grow(&B.d_rec, &B.c_rec, std::max<uint64_t>(C, 1) * D));
-  MANYCHK(many_grow(&B.d_prob, &B.c_prob, (size_t)Q));
-  MANYCHK(many_grow(&B.d_raw, &B.c_raw, raw.size()));
-  MANYCHK(many_grow(&B.d_rcount, &B.c_rcount, raw.size()));
-  MANYCHK(many_grow(&B.d_parts, &B.c_parts, parts.size()));
-  MANYCHK(many_grow(&B.d_partials, &B.c_partials, parts.size() * N));
-  MANYCHK(many_grow(&B.d_flag, &B.c_flag, (size_t)Q));
-  MANYCHK(many_grow(&B.d_state, &B.c_state, (size_t)Q));
-  MANYCHK(many_grow(&B.d_out, &B.c_out, (size_t)Q));
-  MANYCHK(many_grow(&B.d_live, &B.c_live, 1));
-  if (!B.h_live) MANYCHK(hipHostMalloc((void **)&B.h_live, 64));
+  MANYCHK(many_grow(B.d_rec, std::max<uint64_t>(C, 1) * D));
+  MANYCHK(many_grow(B.d_prob, (size_t)Q));
+  MANYCHK(many_grow(B.d_raw, raw.size()));
+  MANYCHK(many_grow(B.d_rcount, raw.size()));
+  MANYCHK(many_grow(B.d_parts, parts.size()));
+  MANYCHK(many_grow(B.d_partials, parts.size() * N));
+  MANYCHK(many_grow(B.d_flag, (size_t)Q));
+  MANYCHK(many_grow(B.d_state, (size_t)Q));
+  MANYCHK(many_grow(B.d_out, (size_t)Q));
+  MANYCHK(many_grow(B.d_live, 1));
+  if (!B.h_live) MANYCHK(B.h_live.alloc(16));
   // (the host vectors are pageable: these copies complete before the calls return)
   MANYCHK(hipMemcpyAsync(B.d_prob, prob.data(), sizeof(ManyLmProb) * Q, hipMemcpyHostToDevice, J.stream));
   MANYCHK(hipMemcpyAsync(B.d_raw, raw.data(), sizeof(ManyLmRaw) * raw.size(), hipMemcpyHostToDevice, J.stream));
@@ -311,16 +301,9 @@ int many_lm_run(ManyLmJob &J, std::vector<ManyLmProb> &prob, std::vector<ManyLmO
   // diagnostics (LSQR_MANY_TRACE): per round the live problems, the parts launched, pass / step time, device wait
   static const bool trace = getenv("LSQR_MANY_TRACE") != nullptr;
   typedef std::chrono::steady_clock Clock;
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+  Event ev[3];
   if (trace)
-    for (auto &e : ev) MANYCHK(hipEventCreate(&e));
-  struct EvGuard {
-    hipEvent_t *e;
-    ~EvGuard() {
-      for (int k = 0; k < 3; k++)
-        if (e[k]) (void)hipEventDestroy(e[k]);
-    }
-  } guard{ev};
+    for (auto &e : ev) MANYCHK(e.create());
   uint32_t live = (uint32_t)Q;
   const unsigned n_steps = (unsigned)((Q + kManyLmWaves - 1) / kManyLmWaves);
   // every lm_advance call consumes one evaluation and stops at maxfev: maxfev rounds finish every problem

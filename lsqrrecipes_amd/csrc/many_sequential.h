@@ -147,7 +147,7 @@ int many_seq_run(ManyJob &J, int K, int P, const uint64_t *seeds, size_t max_mod
   if ((st = many_upload(J)) != LSQR_OK) return st;
   int32_t *d_labels = nullptr;
   if ((labels_out || keep_labels) && NT) {
-    MANYCHK(many_grow(&B.d_seq_labels, &B.c_seq_labels, (size_t)NT));
+    MANYCHK(many_grow(B.d_seq_labels, (size_t)NT));
     MANYCHK(hipMemsetAsync(B.d_seq_labels, 0xFF, sizeof(int32_t) * NT, J.stream));  // -1
     d_labels = B.d_seq_labels;
   }
@@ -249,14 +249,14 @@ int many_seq_run(ManyJob &J, int K, int P, const uint64_t *seeds, size_t max_mod
     if (parts.empty()) break;
     const int dst = cur == 0 ? 1 : 0;
     const size_t b_parts = sizeof(ManySeqPart) * parts.size();
-    MANYCHK(many_grow_pinned(&B.h_seq, &B.c_hseq, b_parts));  // (the round's job ended in a synchronisation)
+    MANYCHK(many_grow_pinned(B.h_seq, b_parts));  // (the round's job ended in a synchronisation)
     memcpy(B.h_seq, parts.data(), b_parts);
-    MANYCHK(many_grow(&B.d_seq_parts, &B.c_seq_parts, b_parts));
-    MANYCHK(many_grow(&B.d_seq_counts, &B.c_seq_counts, parts.size()));
-    MANYCHK(many_grow(&B.d_seq_rec, &B.c_seq_rec, (size_t)std::max<uint64_t>(next_total, 1) * W));
-    MANYCHK(many_grow(&B.d_seq_orig[dst], &B.c_seq_orig[dst], (size_t)std::max<uint64_t>(next_total, 1)));
+    MANYCHK(many_grow(B.d_seq_parts, b_parts));
+    MANYCHK(many_grow(B.d_seq_counts, parts.size()));
+    MANYCHK(many_grow(B.d_seq_rec, (size_t)std::max<uint64_t>(next_total, 1) * W));
+    MANYCHK(many_grow(B.d_seq_orig[dst], (size_t)std::max<uint64_t>(next_total, 1)));
     MANYCHK(hipMemcpyAsync(B.d_seq_parts, B.h_seq, b_parts, hipMemcpyHostToDevice, J.stream));
-    const ManySeqPart *d_parts = (const ManySeqPart *)B.d_seq_parts;
+    const ManySeqPart *d_parts = (const ManySeqPart *)B.d_seq_parts.get();
     if (next_total) {
       hipLaunchKernelGGL(k_mseq_count, dim3((unsigned)parts.size()), dim3(kBlock), 0, J.stream, d_parts, B.d_mask,
                          B.d_seq_counts);
@@ -268,7 +268,6 @@ int many_seq_run(ManyJob &J, int K, int P, const uint64_t *seeds, size_t max_mod
     MANYCHK(hipGetLastError());
     if (next_total == 0) break;  // labels only: no round follows
     std::swap(B.d_data, B.d_seq_rec);  // the next round's job reads the survivors as its upload
-    std::swap(B.c_data, B.c_seq_rec);
     orig = B.d_seq_orig[dst];
     cur = dst;
   }
