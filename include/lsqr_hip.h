@@ -730,6 +730,12 @@ LSQR_API void lsqr_dedup_destroy(void *set);
  * "scan_prepared": cell models whose per-hypothesis state does not depend on the cell (plane): 1 (default) = it is
  *                written once per batch (csrc/cells.h: k_prepare_hyps) and read back by the counted two-level scan; 0 = it
  *                is rebuilt for every (cell, group of 64 hypotheses) (A/B knob).  Votes are identical;
+ * "scan_lean":   the counted two-level scan of the cell models (plane, sphere, line): 1 (default) = its counting pass
+ *                runs a count-only form (csrc/cells.h: k_cells_bounds<..., COUNT>: survivor counts and nothing else) and,
+ *                where the hypotheses are prepared (plane, "scan_prepared" 1), k_scan_pairs keeps its share arithmetic
+ *                on the scalar unit, refills its one prepared hypothesis for the next group as soon as level 1 has
+ *                read it and reads the pair loop's addends as stored; 0 = the general forms of both kernels (A/B knob).
+ *                Votes are identical;
  * "dense_mask_ring": LDS tile buffers per wave of the dense final fit's fused mask + normal-equations pass: 4 (default at
  *                n = 64) = one workgroup per CU with three tiles in flight, 2 = two workgroups per CU (A/B knob);
  * "mom_chunk":   records per workgroup of the mask / moment passes in units of 256 (0 = default: 4, wide US / phantom

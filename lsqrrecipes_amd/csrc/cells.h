@@ -1073,7 +1073,10 @@ __device__ __forceinline__ void cells_filter_squares(float (&bc)[NB]) {
   bc[NB - 1] = off ? __builtin_bit_cast(float, 0xFFFFFFFFu) : band;
 }
 
-template <class CM, int PP, bool LDSB>
+// DUP (LDSB, NB = 6, NV = 4: the plane's lean scan): the two ADDENDS of the pair loop -- fp[3] and the filter's a -- lie
+// twice in the broadcast area, in the two halves of an aligned pair, so that the packed FMAs take them as they are read
+// (the compiler selects one half of a pair for both lanes in src0 / src1, not the high half in src2: a v_mov_b32 a pair).
+template <class CM, int PP, bool LDSB, bool DUP = false>
 __device__ __forceinline__ void cells_survivors(const v2f (&xs)[PP][4], const float (&bc)[CM::NB], float *s_bc,
                                                 unsigned long long surv, const int lane,
                                                 const double *__restrict__ sorted, const size_t ns, const size_t cell,
@@ -1084,10 +1087,16 @@ __device__ __forceinline__ void cells_survivors(const v2f (&xs)[PP][4], const fl
   (void)D, (void)NV, (void)CP;
   if (LDSB && surv) {  // the lane's values -> LDS; survivors are fetched with uniform-address reads
     float4 w0, w1;
-    w0.x = bc[0], w0.y = NB > 1 ? bc[1 < NB ? 1 : 0] : 0.0f, w0.z = NB > 2 ? bc[2 < NB ? 2 : 0] : 0.0f,
-    w0.w = NB > 3 ? bc[3 < NB ? 3 : 0] : 0.0f;
-    w1.x = NB > 4 ? bc[4 < NB ? 4 : 0] : 0.0f, w1.y = NB > 5 ? bc[5 < NB ? 5 : 0] : 0.0f,
-    w1.z = NB > 6 ? bc[6 < NB ? 6 : 0] : 0.0f, w1.w = NB > 7 ? bc[7 < NB ? 7 : 0] : 0.0f;
+    if constexpr (DUP) {
+      static_assert(LDSB && NB == 6 && NV == 4, "slots: fp0 fp1 fp3 fp3 | a a fp2 band");
+      w0.x = bc[0], w0.y = bc[1], w0.z = bc[3], w0.w = bc[3];
+      w1.x = bc[4], w1.y = bc[4], w1.z = bc[2], w1.w = bc[5];
+    } else {
+      w0.x = bc[0], w0.y = NB > 1 ? bc[1 < NB ? 1 : 0] : 0.0f, w0.z = NB > 2 ? bc[2 < NB ? 2 : 0] : 0.0f,
+      w0.w = NB > 3 ? bc[3 < NB ? 3 : 0] : 0.0f;
+      w1.x = NB > 4 ? bc[4 < NB ? 4 : 0] : 0.0f, w1.y = NB > 5 ? bc[5 < NB ? 5 : 0] : 0.0f,
+      w1.z = NB > 6 ? bc[6 < NB ? 6 : 0] : 0.0f, w1.w = NB > 7 ? bc[7 < NB ? 7 : 0] : 0.0f;
+    }
     ((float4 *)s_bc)[2 * lane] = w0;
     ((float4 *)s_bc)[2 * lane + 1] = w1;
   }
@@ -1096,7 +1105,13 @@ __device__ __forceinline__ void cells_survivors(const v2f (&xs)[PP][4], const fl
     asm("s_bitset0_b64 %0, %1" : "+s"(surv) : "s"(b));  // surv &= ~(1 << b)
     v2f fp[NV], na;
     uint32_t band;
-    if (LDSB) {
+    if constexpr (DUP) {
+      const float4 r0 = ((const float4 *)s_bc)[2 * b], r1 = ((const float4 *)s_bc)[2 * b + 1];
+      fp[0].x = r0.x, fp[0].y = r0.x, fp[1].x = r0.y, fp[1].y = r0.y, fp[2].x = r1.z, fp[2].y = r1.z;
+      fp[3].x = r0.z, fp[3].y = r0.w;
+      na.x = -r1.x, na.y = -r1.y;
+      band = __builtin_bit_cast(uint32_t, r1.w);
+    } else if (LDSB) {
       static_assert(NB <= 8, "broadcast area holds 8 floats per lane");
       const float4 r0 = ((const float4 *)s_bc)[2 * b], r1 = ((const float4 *)s_bc)[2 * b + 1];
       const float rb[8] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w};
@@ -1593,7 +1608,12 @@ __device__ __forceinline__ typename CM::Hyp hyp_from(const float4 (&v)[HypWords<
 // and, per launch, the number of surviving (hypothesis, cell) pairs, i.e. what level 2 has to look at.
 // Lane = hypothesis; blockIdx.y * 4 + wave = group of 64 hypotheses; blockIdx.x = a run of cells.
 // PREP: Hyp comes from the batch's prepared block `hyps` (k_prepare_hyps) instead of load().
-template <class CM, int PP, bool PREP = false>
+// COUNT: the counting launch of the counted scan (option "scan_lean"): cnt is written and nothing else -- no
+// population, no surviving-cell count, ub / total / ncells_out are not looked at.  The survivor count is the population
+// count of level 1's own compare mask; a wave's bytes of a chunk of boxes sit at i * gstride from ONE scalar address,
+// and the four cells of an unrolled iteration are stored under one `lane == 0`.  cnt is byte for byte what the general
+// form writes.
+template <class CM, int PP, bool PREP = false, bool COUNT = false>
 __global__ __launch_bounds__(256) void k_cells_bounds(const CellBox *__restrict__ boxes, uint32_t ncells,
                                                       size_t ns, const float *__restrict__ rows,
                                                       const float *__restrict__ spf, uint32_t H,
@@ -1612,7 +1632,8 @@ __global__ __launch_bounds__(256) void k_cells_bounds(const CellBox *__restrict_
     const uint32_t hd = *h_dev > h_off ? *h_dev - h_off : 0u;  // hypotheses [h_off, h_off + H) of the selection
     H = hd < H ? hd : H;
   }
-  const uint32_t grp = blockIdx.y * 4 + (threadIdx.x >> 6);
+  const uint32_t grp = COUNT ? blockIdx.y * 4 + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6))
+                             : blockIdx.y * 4 + (threadIdx.x >> 6);
   const uint32_t h = grp * 64 + lane;
   if (blockIdx.y * 256 >= H) return;   // workgroup-uniform: the barriers below are for whole workgroups
   const bool active = h - lane < H;    // wave-uniform
@@ -1664,6 +1685,32 @@ __global__ __launch_bounds__(256) void k_cells_bounds(const CellBox *__restrict_
     }
     __syncthreads();
     if (!active) continue;
+    if constexpr (COUNT) {
+      // padded survivor count of the wave's group in one box: every lane of an active wave takes part in the compare
+      auto padded = [&](const CellBox &bx, const double (&ctr)[3]) {
+        float bc[CM::NB];
+        const uint32_t pc = (uint32_t)__builtin_popcountll(__ballot(CM::level1(hy, bx, ctr, cc, bc)));
+        return (uint8_t)(pc ? pc + kGroupPad : 0u);  // <= 64 + pad
+      };
+      uint8_t *p = cnt + ((size_t)cb * gstride + grp);  // wave-uniform; the chunk's rows are < BCH * gstride away
+      uint32_t i = 0;
+      for (; i + 4 <= n; i += 4, p += 4 * gstride) {  // four boxes in flight
+        const CellBox b0 = s_box[i], b1 = s_box[i + 1], b2 = s_box[i + 2], b3 = s_box[i + 3];
+        const double t0[3] = {s_ctr[i][0], s_ctr[i][1], s_ctr[i][2]};
+        const double t1[3] = {s_ctr[i + 1][0], s_ctr[i + 1][1], s_ctr[i + 1][2]};
+        const double t2[3] = {s_ctr[i + 2][0], s_ctr[i + 2][1], s_ctr[i + 2][2]};
+        const double t3[3] = {s_ctr[i + 3][0], s_ctr[i + 3][1], s_ctr[i + 3][2]};
+        const uint8_t p0 = padded(b0, t0), p1 = padded(b1, t1), p2 = padded(b2, t2), p3 = padded(b3, t3);
+        if (lane == 0) p[0] = p0, p[gstride] = p1, p[2 * gstride] = p2, p[3 * gstride] = p3;
+      }
+      for (; i < n; i++, p += gstride) {
+        const CellBox b0 = s_box[i];
+        const double t0[3] = {s_ctr[i][0], s_ctr[i][1], s_ctr[i][2]};
+        const uint8_t p0 = padded(b0, t0);
+        if (lane == 0) p[0] = p0;
+      }
+      continue;
+    }
     auto one = [&](const uint32_t i, const CellBox &bx, const double (&ctr)[3]) {
       const uint32_t c = cb + i;
       float bc[CM::NB];
@@ -1695,6 +1742,7 @@ __global__ __launch_bounds__(256) void k_cells_bounds(const CellBox *__restrict_
       one(i, b0, t0);
     }
   }
+  if constexpr (COUNT) return;
   if (ub && h < H && u) atomicAdd(&ub[h], u);
   if (ncells_out && h < H && nc) atomicAdd(&ncells_out[h], nc);  // surviving cells of the hypothesis (diagnostics)
   if (total) {
@@ -1769,7 +1817,15 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v, int lane) {
   return v;
 }
 
-template <class CM, int PP, int BS, bool LDSB, bool PREP = false>
+// LEAN (option "scan_lean"; prepared hypotheses only): the same enumeration with
+//   - the share arithmetic on the scalar unit: skip, budget and cell are wave-uniform and are made so for the compiler
+//     (readfirstlane), and a wave's part of a group is worked out in cost units (no saturating subtraction, which
+//     exists on the vector unit only), so lo / hi, their compares and the two bit-peeling loops are scalar code;
+//   - ONE Hyp, refilled for group k + 1 as soon as level 1 of group k has read it: the prefetched block is never
+//     copied (the general form moves it into level 1's registers and back, twelve 64-bit moves a group);
+//   - the pair loop's two addends twice in the broadcast area (cells_survivors<..., DUP>).
+// Which bits of a survivor mask a wave keeps, and with them every vote, are those of the general form.
+template <class CM, int PP, int BS, bool LDSB, bool PREP = false, bool LEAN = false>
 __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(PP >= 8 ? 4 : CM::MIN_WAVES, 8))) void k_scan_pairs(
     const double *__restrict__ sorted, size_t ns, const CellBox *__restrict__ boxes, uint32_t ncells,
     const double *__restrict__ sp, const float *__restrict__ rows, const float *__restrict__ spf, uint32_t H,
@@ -1839,6 +1895,11 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(PP >= 8 ? 4 
     skip = r - before - (second ? c0v : 0u);
   }
 
+  if constexpr (LEAN) {  // wave-uniform by construction (C, wid, W and the readlane'd prefix sums are)
+    budget = (uint32_t)__builtin_amdgcn_readfirstlane((int)budget);
+    cell = (uint32_t)__builtin_amdgcn_readfirstlane((int)cell);
+    skip = (uint32_t)__builtin_amdgcn_readfirstlane((int)skip);
+  }
   const uint32_t G = (H + 63) / 64;
   // cost units [skip, skip + budget) of the enumeration that starts at `cell`: a padded item of P units in front of
   // the position consumes what of it lies in my range
@@ -1899,8 +1960,75 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(PP >= 8 ? 4 
     double ctr[3];
 #pragma unroll
     for (int d = 0; d < 3; d++) ctr[d] = (double)bx.c[d];
+    if constexpr (LEAN && PP >= 4) {  // the centre is the same in every lane: in scalar registers it is an operand of
+                                      // level 1's fp64 FMAs all the same and gives back the six vector registers the
+                                      // 512-point cells are short of (smaller cells have room, and lose a wave to it)
+#pragma unroll
+      for (int d = 0; d < 3; d++) {
+        const unsigned long long u = __builtin_bit_cast(unsigned long long, ctr[d]);
+        // (the builtin is folded away again: the compiler knows the value to be uniform.  Its hazard recogniser does
+        // not look into inline assembly, and gfx950 wants one wait state between a vector write of a VGPR and a lane
+        // read of it, two between a vector write of an SGPR and a vector read of it: the s_nops stand for them.
+        // Below this point ctr may only ever be an operand of VECTOR ARITHMETIC -- cells_load's subtractions, level 1's
+        // FMAs --: a memory instruction that took these registers as an address or offset would want five wait states
+        // after the write, and nothing would flag their absence)
+        uint32_t l, m;
+        asm("s_nop 0\n\tv_readfirstlane_b32 %0, %1\n\ts_nop 1" : "=s"(l) : "v"((uint32_t)u));
+        asm("s_nop 0\n\tv_readfirstlane_b32 %0, %1\n\ts_nop 1" : "=s"(m) : "v"((uint32_t)(u >> 32)));
+        ctr[d] = __builtin_bit_cast(double, (unsigned long long)m << 32 | l);
+      }
+    }
     v2f xs[PP][4];
     cells_load<CM, PP>(sorted, ns, (size_t)cell, lane, ctr, xs);
+    if constexpr (LEAN) {
+      // level 1 is the only reader of a group's Hyp and comes first, so the next group's Hyp is fetched into the
+      // registers it has just read -- as far ahead of its use, but for level 1 itself, as a second buffer would have it
+      static_assert(PREP, "the lean group loop is built for prepared hypotheses");
+      typename CM::Hyp hy;
+      {
+        float4 r[NR4], r2[1];
+        load_rows((uint32_t)__builtin_ctzll(gm), r, r2);
+        hy = hyp_from<CM>(r);
+      }
+      while (gm && budget) {
+        const int g = __builtin_ctzll(gm);
+        gm &= gm - 1;
+        const uint32_t cg = (uint32_t)__builtin_amdgcn_readlane((int)gc, g);
+        // my part [lo, hi) of the group's cost units; pair j sits at unit kGroupPad + j, so the survivors number
+        // klo - pad ... hi - pad - 1 in lane order are mine (the general form's jlo, jhi), if there are any
+        const uint32_t lo = skip, hi = cg < skip + budget ? cg : skip + budget;  // skip < cg here
+        budget -= hi - lo;
+        skip = 0;
+        const uint32_t klo = lo > kGroupPad ? lo : kGroupPad;
+        const bool mine = hi > klo;
+        const uint32_t h0 = (uint32_t)g * 64, h = h0 + lane;
+        float bc[NB];
+        unsigned long long surv = 0;
+        if (mine) surv = __ballot(CM::level1(hy, bx, ctr, cc, bc));  // == the counting pass: cg - pad bits
+        if (gm) {  // the next group's rows meanwhile
+          float4 r[NR4], r2[1];
+          load_rows((uint32_t)__builtin_ctzll(gm), r, r2);
+          hy = hyp_from<CM>(r);
+        }
+        if (!mine) continue;
+        cells_filter_squares(bc);
+        for (uint32_t k = kGroupPad; k < lo; k++) surv &= surv - 1;  // the first klo - pad are not mine
+        if (hi < cg) {  // the tail belongs to the next wave: keep the lowest hi - klo bits
+          unsigned long long keep = 0, m = surv;
+          for (uint32_t k = klo; k < hi; k++) {
+            keep |= m & (0ull - m);
+            m &= m - 1;
+          }
+          surv = keep;
+        }
+        uint32_t accv = 0;
+        cells_survivors<CM, PP, LDSB, LDSB>(xs, bc, s_bc, surv, lane, sorted, ns, (size_t)cell, sp + (size_t)h0 * SPD,
+                                            mc, accv);
+        if (accv) atomicAdd(&s_cnt[h], accv);
+      }
+      cell++;
+      continue;
+    }
     float4 nxt[NR4], nxt2[NR2 ? NR2 : 1];
     load_rows((uint32_t)__builtin_ctzll(gm), nxt, nxt2);
     while (gm && budget) {

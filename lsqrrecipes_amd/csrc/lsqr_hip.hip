@@ -231,6 +231,7 @@ struct lsqr_ctx {
   DevBuf<uint32_t> d_paircost; // [n_cells cell costs | chunk sums]
   DevBuf<uint32_t> d_vpart;    // per-workgroup partial votes of k_scan_pairs
   DevBuf<float4> d_hyps;       // k_prepare_hyps: CM::Hyp of every hypothesis of the batch k_scan_pairs is counting
+  int opt_lean = 1;               // 1: count-only counting pass, k_scan_pairs<..., LEAN> for prepared models; 0: the general forms (A/B)
   int opt_prepared = 1;           // 1: cell models with PREPARED read Hyp from d_hyps; 0: load() per (cell, group) (A/B)
   // bounded scan (cells.h: k_pick_*): the selected hypotheses as a compact batch
   DevBuf<uint32_t> d_sel;        // [kPilots pilots | H_cap rest]
@@ -1109,7 +1110,12 @@ int run_scan_pairs(lsqr_ctx *c, const ScanBatch &b0) {
                          Hc, cc, per, (uint32_t *)nullptr, (unsigned long long *)nullptr, (uint32_t *)nullptr,
                          c->d_paircnt, gstride, b.h_dev, b.h_off, (uint32_t)(128 * PP), hyps);
     };
-    if (prep)
+    if (c->opt_lean) {  // cnt and nothing else
+      if (prep)
+        count(k_cells_bounds<CM, PP, kPrep, true>);
+      else
+        count(k_cells_bounds<CM, PP, false, true>);
+    } else if (prep)
       count(k_cells_bounds<CM, PP, kPrep>);
     else
       count(k_cells_bounds<CM, PP>);
@@ -1144,6 +1150,10 @@ int run_scan_pairs(lsqr_ctx *c, const ScanBatch &b0) {
     HIPCHK(c, hipGetLastError());
     return LSQR_OK;
   };
+  if constexpr (kPrep) {  // the lean group loop walks the prepared block
+    if (prep && c->opt_lean)
+      return ldsb ? launch(k_scan_pairs<CM, PP, BS, true, true, true>) : launch(k_scan_pairs<CM, PP, BS, false, true, true>);
+  }
   if (prep) return ldsb ? launch(k_scan_pairs<CM, PP, BS, true, kPrep>) : launch(k_scan_pairs<CM, PP, BS, false, kPrep>);
   return ldsb ? launch(k_scan_pairs<CM, PP, BS, true>) : launch(k_scan_pairs<CM, PP, BS, false>);
 }
@@ -5282,6 +5292,10 @@ static int set_option_one(lsqr_ctx *c, const char *name, int value) {
   }
   if (!strcmp(name, "scan_prepared")) {  // 1 (default): the counted scan reads each hypothesis' prepared Hyp; 0: load() per (cell, group)
     c->opt_prepared = value != 0;
+    return LSQR_OK;
+  }
+  if (!strcmp(name, "scan_lean")) {  // 1 (default): count-only counting pass, lean k_scan_pairs (prepared models); 0: the general forms
+    c->opt_lean = value != 0;
     return LSQR_OK;
   }
   if (!strcmp(name, "scan_axis")) {  // 1 (default): axis-sorted cells + vote bounds by rank (plane, 3-D); 0: off

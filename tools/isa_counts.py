@@ -19,8 +19,12 @@ from bench import kernel_source_hash  # noqa: E402
 
 CSRC = os.path.join(ROOT, "lsqrrecipes_amd", "csrc")
 # (key, substrings the mangled name must contain)
-KERNELS = [("k_scan_pairs_plane", ["k_scan_pairs", "PlaneCell", "Li3E", "Li4ELi256ELb1ELb1E"]),  # LDS broadcast, prepared Hyp: what runs
-           ("k_scan_pairs_plane_unprepared", ["k_scan_pairs", "PlaneCell", "Li3E", "Li4ELi256ELb1ELb0E"]),  # scan_prepared=0
+# (k_scan_pairs<CM, PP, BS, LDSB, PREP, LEAN>, k_cells_bounds<CM, PP, PREP, COUNT>: the bools are the trailing LbNE)
+KERNELS = [("k_scan_pairs_plane", ["k_scan_pairs", "PlaneCell", "Li3E", "Li4ELi256ELb1ELb1ELb1E"]),  # LDS broadcast, prepared Hyp, lean: what runs
+           ("k_scan_pairs_plane_general", ["k_scan_pairs", "PlaneCell", "Li3E", "Li4ELi256ELb1ELb1ELb0E"]),  # scan_lean=0
+           ("k_scan_pairs_plane_unprepared", ["k_scan_pairs", "PlaneCell", "Li3E", "Li4ELi256ELb1ELb0ELb0E"]),  # scan_prepared=0 scan_lean=0
+           ("k_cells_bounds_plane", ["k_cells_bounds", "PlaneCell", "Li3E", "Li4ELb1ELb1E"]),  # count-only counting pass: what runs
+           ("k_cells_bounds_plane_general", ["k_cells_bounds", "PlaneCell", "Li3E", "Li4ELb1ELb0E"]),  # scan_lean=0
            ("k_scan_pairs_sphere", ["k_scan_pairs", "SphereCell", "Li3E"]),
            ("k_scan_pairs_line", ["k_scan_pairs", "LineCell", "Li3E"]),
            ("k_scan_us_f32", ["k_scan_us_f32", "USModel", "Lb1E"]),
@@ -115,6 +119,11 @@ def main():
         # the loop with the most packed instructions = the packed fp32 filter's body (level 2 of the point models)
         l2 = max(rows, key=lambda r: r["valu_packed"]) if rows else None
         res[key] = {"function": best[1][:120], "loops": rows,
+                    # counting pass: the loop with the most vector instructions (its header block "LBBn_m" and the
+                    # blocks "BBn_m" inside it taken together) is the four-cells-at-a-time loop
+                    "valu_per_cell": max(sum(r["valu"] for r in rows if r["loop"].lstrip("L") == n)
+                                         for n in {r["loop"].lstrip("L") for r in rows}) / 4.0
+                    if key.startswith("k_cells_bounds") and rows else None,
                     "packed_body": {"loop": l2["loop"], "valu": l2["valu"], "valu_packed": l2["valu_packed"],
                                     "valu_cmp": l2["valu_cmp"], "salu": l2["salu"]} if l2 else None}
     out = {"what": "tools/isa_counts.py: instructions per loop of the scan kernels in this tree's ISA (one pass over a loop "
@@ -122,7 +131,7 @@ def main():
            "kernel_source_hash": kernel_source_hash(), "kernels": res}
     json.dump(out, open(out_path, "w"), indent=1)
     for k, v in res.items():
-        print(k, v["packed_body"])
+        print(k, v["packed_body"] if v["valu_per_cell"] is None else {"valu_per_cell": v["valu_per_cell"]})
 
 
 if __name__ == "__main__":
