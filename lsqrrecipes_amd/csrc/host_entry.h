@@ -1,10 +1,12 @@
 // host_entry.h -- everything of the C ABI that needs no device: the model dispatch, the description of a model
 // (minimal subset, parameters, record), the counter-based subset stream on the host (lsqr_sample_subsets), the replay of
 // RANSAC.hxx:49-117 over a batch (lsqr_replay*: duplicate set, strict '>' update, adaptive numTries with the reference's
-// saturating choose), and the single-datum host calls (lsqr_agree_host / lsqr_estimate_host: the kernels' own per-model
-// code compiled for the host).  Plain C++ -- no HIP runtime -- so that the SAME source is (a) compiled into
-// liblsqr_hip.so by hipcc (lsqr_hip.hip wraps every host_* function in its extern "C" entry point) and (b) compiled
-// alone by g++ -fsanitize=address,undefined in the CPU suite (tests/test_sanitizers.py, tests/sanitize/driver.cpp).
+// saturating choose), the single-datum host calls (lsqr_agree_host / lsqr_estimate_host: the kernels' own per-model
+// code compiled for the host), and the host's small decisions around a device pass (pass_shape: the cut into blocks;
+// wants_lm / lm_settings / lm_fill_result / lm_granule_decode: the iterative fits).  Plain C++ -- no HIP runtime -- so
+// that the SAME source is (a) compiled into liblsqr_hip.so by hipcc (lsqr_hip.hip wraps every host_* function in its
+// extern "C" entry point) and (b) compiled alone by g++ -fsanitize=address,undefined in the CPU suite
+// (tests/test_sanitizers.py, tests/sanitize/driver.cpp).
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -15,6 +17,7 @@
 
 #include "../../include/lsqr_hip.h"
 #include "dense_model.h"
+#include "lm_core.h"
 #include "models.h"
 #include "models_nd.h"
 #include "phantom.h"
@@ -380,5 +383,84 @@ inline int host_estimate_host(const lsqr_model_cfg *cfg, const void *records, si
   });
 }
 
+// ---- cutting a pass into blocks ------------------------------------------------------------------------------------
+inline int grid_for(size_t items, int per_block, int max_blocks) {
+  size_t b = (items + per_block - 1) / per_block;
+  if (b < 1) b = 1;
+  if (b > (size_t)max_blocks) b = max_blocks;
+  return (int)b;
+}
+
+// `cnt` records in nb blocks of `chunk` consecutive records each: about per_block records per block, at most
+// max_blocks blocks, chunk a multiple of round_to (the kernel's tile), and no block without a record --
+// (nb - 1) * chunk < cnt <= nb * chunk.  Nothing to cut (cnt == 0) is one block.
+struct PassShape {
+  int nb;
+  size_t chunk;
+};
+inline PassShape pass_shape(size_t cnt, int per_block, int max_blocks, int round_to) {
+  int nb = grid_for(cnt, per_block, max_blocks);
+  size_t chunk = (std::max<size_t>(cnt, 1) + nb - 1) / nb;
+  chunk = (chunk + round_to - 1) / round_to * round_to;
+  nb = (int)((cnt + chunk - 1) / chunk);
+  return {nb < 1 ? 1 : nb, chunk};
+}
+
+// ---- the iterative (Levenberg-Marquardt) fits: what the host decides ------------------------------------------------
+inline bool wants_lm(const lsqr_model_cfg &cfg) {
+  return (cfg.model == LSQR_MODEL_SPHERE && cfg.ls_type == LSQR_LS_GEOMETRIC) ||
+         ((cfg.model == LSQR_MODEL_US_SINGLE || cfg.model == LSQR_MODEL_US_POINTER) &&
+          cfg.ls_type == LSQR_LS_ITERATIVE) ||
+         (cfg.model == LSQR_MODEL_PHANTOM && cfg.ls_type == LSQR_LS_ITERATIVE);
+}
+
+inline void lm_settings(const lsqr_model_cfg &cfg, int *n, double *ftol, double *xtol, double *gtol, int *maxfev) {
+  // SphereParametersEstimator.hxx:323-329: x and g tolerances 10e-16, 500 evaluations; ftol is
+  // vnl_nonlinear_minimizer's default xtol*0.01 = 1e-10.
+  *n = cfg.dim + 1;
+  *ftol = 1e-10;
+  *xtol = 10e-16;
+  *gtol = 10e-16;
+  *maxfev = 500;
+  if (cfg.model == LSQR_MODEL_US_SINGLE) {  // SinglePointTarget...Estimator.cxx:287-295
+    *n = 11;
+    *ftol = *xtol = *gtol = 10e-16;
+    *maxfev = 5000;
+  } else if (cfg.model == LSQR_MODEL_PHANTOM) {  // PlanePhantom...Estimator.cxx:368-376
+    *n = 11;
+    *ftol = *xtol = *gtol = 10e-16;
+    *maxfev = 5000;
+  } else if (cfg.model == LSQR_MODEL_US_POINTER) {  // :931-939
+    *n = 8;
+    *ftol = *xtol = *gtol = 10e-8;
+    *maxfev = 5000;
+  }
+}
+
+// the record a host-stepped minimisation leaves when lm_advance has stopped; np: what M::lm_finalize returned (the
+// parameters are the caller's to write).  While the fit goes on (info 0) the record says "no result yet".
+inline void lm_fill_result(const LmState &s, int np, SolveOut *out) {
+  const bool ok = s.info >= 1 && s.info <= 4;  // vnl_levenberg_marquardt::minimize -> true
+  out->ok = ok ? 1 : 0;
+  out->n_params = ok ? np : 0;
+  out->lm_info = s.info;
+  out->lm_nfev = s.nfev;
+  out->cont = 0;
+  out->pad = s.stall;
+  out->cost = s.fnorm * s.fnorm;
+}
+
+// One double of an evaluation's moment block crosses from the device to pinned host memory as two 8-byte granules,
+// {high word | tag} and {low word | tag}: each is written whole, so it is valid the moment its tag is the
+// evaluation's -- no flag, no fence.  false: sum j of evaluation `tag` has not arrived (yet).
+inline bool lm_granule_decode(const volatile unsigned long long *res, int j, uint32_t tag, double *value) {
+  const unsigned long long g0 = res[2 * j];
+  if ((uint32_t)g0 != tag) return false;
+  const unsigned long long g1 = res[2 * j + 1];
+  if ((uint32_t)g1 != tag) return false;
+  const unsigned long long bits = (g0 & 0xFFFFFFFF00000000ULL) | (g1 >> 32);
+  memcpy(value, &bits, 8);
+  return true;
+}
 
 }  // namespace lsqr

@@ -990,14 +990,6 @@ __global__ __launch_bounds__(64) void k_reduce(const double *__restrict__ partia
   if (threadIdx.x == 0) mom[k] = t;
 }
 
-// result block written by the solve kernels: {status(1 ok / 0 empty), n_params, lm_info, lm_nfev,
-// continue flag}
-struct SolveOut {
-  int ok, n_params, lm_info, lm_nfev, cont, pad;
-  double cost;
-  double params[64];
-};
-
 // the small solve of one moment block on one lane: k_solve, and the batched solve of lsqr_ransac_many (many.h)
 template <class M>
 __device__ inline void solve_small(const double *m, const double *org, const ModelConsts &mc, double *ws,

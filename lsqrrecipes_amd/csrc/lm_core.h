@@ -30,6 +30,15 @@ struct LmState {
   double cstall;    // the cost at `stall`
 };
 
+// result block written by the solve kernels: {status(1 ok / 0 empty), n_params, lm_info, lm_nfev,
+// continue flag}.  It lives here, not with the kernels, because the host's record of a stopped minimisation
+// (host_entry.h: lm_fill_result) fills the same block and is compiled without the HIP runtime.
+struct SolveOut {
+  int ok, n_params, lm_info, lm_nfev, cont, pad;
+  double cost;
+  double params[64];
+};
+
 LSQR_HD int lm_mom_len(int n) { return 1 + n * (n + 1) / 2 + n; }
 
 LSQR_HD double lm_enorm(int n, const double *x) {

@@ -481,12 +481,6 @@ static inline int mom_chunk(const lsqr_ctx *c) {
   const int m = c->cfg.model;
   return (m == LSQR_MODEL_US_SINGLE || m == LSQR_MODEL_US_POINTER || m == LSQR_MODEL_PHANTOM) ? kMomChunkWide : kMomChunk;
 }
-int grid_for(size_t items, int per_block, int max_blocks) {
-  size_t b = (items + per_block - 1) / per_block;
-  if (b < 1) b = 1;
-  if (b > (size_t)max_blocks) b = max_blocks;
-  return (int)b;
-}
 
 // ---- hypotheses ---------------------------------------------------------------------------------
 template <int D>
@@ -2026,12 +2020,7 @@ int run_scan_batch(lsqr_ctx *c, uint32_t best_before) {
 int launch_syrk(lsqr_ctx *c, const double *data, size_t stride, int n, int use_mask, size_t begin,
                 size_t end, int *nmom) {
   const int ne = dense_ne(n), ps = dense_pstride(n);
-  size_t cnt = end - begin;
-  int nb = grid_for(cnt, kSyrkTile * 8, kDenseBlocks);
-  size_t chunk = (cnt + nb - 1) / nb;
-  chunk = (chunk + kSyrkTile - 1) / kSyrkTile * kSyrkTile;
-  nb = (int)((cnt + chunk - 1) / chunk);
-  if (nb < 1) nb = 1;
+  const auto [nb, chunk] = pass_shape(end - begin, kSyrkTile * 8, kDenseBlocks, kSyrkTile);
   *nmom = ne + 1;
   {
     ProfScope ps_(c, KID_MOMENTS);
@@ -2149,48 +2138,43 @@ int launch_moments(lsqr_ctx *c, int use_mask, size_t begin, size_t end, int phas
     if (phase != 0) return fail(c, LSQR_ERR_INVALID, "dense model has no iterative phase");
     return launch_moments_dense(c, use_mask, begin, end, nmom);
   } else {
-  size_t cnt = end - begin;
-  int nb = grid_for(cnt, mom_chunk(c), kMaxPartials);
-  size_t chunk = (cnt + nb - 1) / nb;
-  chunk = (chunk + kBlock - 1) / kBlock * kBlock;
-  nb = (int)((cnt + chunk - 1) / chunk);
-  if (nb < 1) nb = 1;
-  {
-    ProfScope ps(c, KID_MOMENTS);
-    if (phase == 0) {
-      *nmom = M::NMOM;
-      if (use_mask)
-        hipLaunchKernelGGL((k_moments<M, AccLs<M>, true>), dim3(nb), dim3(kBlock), 0, c->stream,
-                           c->d_data, c->stride, begin, end, chunk, c->d_mask, c->d_vec, c->mc,
-                           c->d_partials);
-      else
-        hipLaunchKernelGGL((k_moments<M, AccLs<M>, false>), dim3(nb), dim3(kBlock), 0, c->stream,
-                           c->d_data, c->stride, begin, end, chunk, c->d_mask, c->d_vec, c->mc,
-                           c->d_partials);
-    } else {
-      if constexpr (requires { M::NMOM_LM; }) {
-        *nmom = M::NMOM_LM;
+    const auto [nb, chunk] = pass_shape(end - begin, mom_chunk(c), kMaxPartials, kBlock);
+    {
+      ProfScope ps(c, KID_MOMENTS);
+      if (phase == 0) {
+        *nmom = M::NMOM;
         if (use_mask)
-          hipLaunchKernelGGL((k_moments<M, AccLm<M>, true>), dim3(nb), dim3(kBlock), 0, c->stream,
+          hipLaunchKernelGGL((k_moments<M, AccLs<M>, true>), dim3(nb), dim3(kBlock), 0, c->stream,
                              c->d_data, c->stride, begin, end, chunk, c->d_mask, c->d_vec, c->mc,
                              c->d_partials);
         else
-          hipLaunchKernelGGL((k_moments<M, AccLm<M>, false>), dim3(nb), dim3(kBlock), 0,
-                             c->stream, c->d_data, c->stride, begin, end, chunk, c->d_mask,
-                             c->d_vec, c->mc, c->d_partials);
+          hipLaunchKernelGGL((k_moments<M, AccLs<M>, false>), dim3(nb), dim3(kBlock), 0, c->stream,
+                             c->d_data, c->stride, begin, end, chunk, c->d_mask, c->d_vec, c->mc,
+                             c->d_partials);
       } else {
-        return fail(c, LSQR_ERR_INVALID, "model has no iterative phase");
+        if constexpr (requires { M::NMOM_LM; }) {
+          *nmom = M::NMOM_LM;
+          if (use_mask)
+            hipLaunchKernelGGL((k_moments<M, AccLm<M>, true>), dim3(nb), dim3(kBlock), 0, c->stream,
+                               c->d_data, c->stride, begin, end, chunk, c->d_mask, c->d_vec, c->mc,
+                               c->d_partials);
+          else
+            hipLaunchKernelGGL((k_moments<M, AccLm<M>, false>), dim3(nb), dim3(kBlock), 0,
+                               c->stream, c->d_data, c->stride, begin, end, chunk, c->d_mask,
+                               c->d_vec, c->mc, c->d_partials);
+        } else {
+          return fail(c, LSQR_ERR_INVALID, "model has no iterative phase");
+        }
       }
+      HIPCHK(c, hipGetLastError());
     }
-    HIPCHK(c, hipGetLastError());
-  }
-  {
-    ProfScope ps(c, KID_SOLVE);
-    hipLaunchKernelGGL(k_reduce, dim3(*nmom), dim3(64), 0, c->stream, c->d_partials, nb,
-                       (int)MOM_MAX, *nmom, c->d_mom);
-    HIPCHK(c, hipGetLastError());
-  }
-  return LSQR_OK;
+    {
+      ProfScope ps(c, KID_SOLVE);
+      hipLaunchKernelGGL(k_reduce, dim3(*nmom), dim3(64), 0, c->stream, c->d_partials, nb,
+                         (int)MOM_MAX, *nmom, c->d_mom);
+      HIPCHK(c, hipGetLastError());
+    }
+    return LSQR_OK;
   }
 }
 
@@ -2200,37 +2184,6 @@ int read_out(lsqr_ctx *c, SolveOut *o) {
   HIPCHK(c, sync_stream(c));
   memcpy(o, c->h_pin->scratch, sizeof(SolveOut));
   return LSQR_OK;
-}
-
-bool wants_lm(const lsqr_model_cfg &cfg) {
-  return (cfg.model == LSQR_MODEL_SPHERE && cfg.ls_type == LSQR_LS_GEOMETRIC) ||
-         ((cfg.model == LSQR_MODEL_US_SINGLE || cfg.model == LSQR_MODEL_US_POINTER) &&
-          cfg.ls_type == LSQR_LS_ITERATIVE) ||
-         (cfg.model == LSQR_MODEL_PHANTOM && cfg.ls_type == LSQR_LS_ITERATIVE);
-}
-
-void lm_settings(const lsqr_model_cfg &cfg, int *n, double *ftol, double *xtol, double *gtol,
-                 int *maxfev) {
-  // SphereParametersEstimator.hxx:323-329: x and g tolerances 10e-16, 500 evaluations; ftol is
-  // vnl_nonlinear_minimizer's default xtol*0.01 = 1e-10.
-  *n = cfg.dim + 1;
-  *ftol = 1e-10;
-  *xtol = 10e-16;
-  *gtol = 10e-16;
-  *maxfev = 500;
-  if (cfg.model == LSQR_MODEL_US_SINGLE) {  // SinglePointTarget...Estimator.cxx:287-295
-    *n = 11;
-    *ftol = *xtol = *gtol = 10e-16;
-    *maxfev = 5000;
-  } else if (cfg.model == LSQR_MODEL_PHANTOM) {  // PlanePhantom...Estimator.cxx:368-376
-    *n = 11;
-    *ftol = *xtol = *gtol = 10e-16;
-    *maxfev = 5000;
-  } else if (cfg.model == LSQR_MODEL_US_POINTER) {  // :931-939
-    *n = 8;
-    *ftol = *xtol = *gtol = 10e-8;
-    *maxfev = 5000;
-  }
 }
 
 // ---- the fit origin ------------------------------------------------------------------------------------------------
@@ -2430,10 +2383,35 @@ void lmp_release(int device, int G) {
   p.cv.notify_all();
 }
 
+// The moment block of evaluation `tag` out of the pinned granules `res` (host_entry.h: lm_granule_decode), polled in
+// order.  LM_LEFT: the stream has drained and the block is not there -- whatever was to publish it has ended without
+// doing so; LM_STREAM_ERROR: the stream reports *err.
+enum LmWait { LM_GOT, LM_LEFT, LM_STREAM_ERROR };
+LmWait lm_wait_block(lsqr_ctx *c, const volatile unsigned long long *res, uint32_t tag, int nmom, double *blk,
+                     hipError_t *err) {
+  unsigned long long spins = 0;
+  for (int j = 0; j < nmom; j++)
+    while (!lm_granule_decode(res, j, tag, &blk[j])) {
+      if ((++spins & 0xFFFF) != 0) continue;  // every 65 k polls: is the stream still alive?
+      const hipError_t q = hipStreamQuery(c->stream);
+      if (q != hipSuccess && q != hipErrorNotReady) {
+        *err = q;
+        return LM_STREAM_ERROR;
+      }
+      if (q == hipSuccess && !lm_granule_decode(res, j, tag, &blk[j])) return LM_LEFT;
+    }
+  return LM_GOT;
+}
+
+struct LmSet {  // lm_settings of the model
+  int n, maxfev;
+  double ftol, xtol, gtol;
+};
+
 // *done = true: finished, `s` holds the final state; false: not run or given up (the caller takes the launch path)
 template <class M>
-int lm_persist_fit(lsqr_ctx *c, const double *tiles, size_t cnt, int nb, LmState &s, const double *x0, int n,
-                   double ftol, double xtol, double gtol, int maxfev, bool *done) {
+int lm_persist_fit(lsqr_ctx *c, const double *tiles, size_t cnt, int nb, LmState &s, const double *x0, const LmSet &t,
+                   bool *done) {
   *done = false;
   static const bool shared_gpu = getenv("LSQR_SHARE_GPU") != nullptr;  // several processes on one device: no tokens across them
   if (!c->opt_lm_persist || shared_gpu || c->is_lane) return LSQR_OK;
@@ -2464,72 +2442,55 @@ int lm_persist_fit(lsqr_ctx *c, const double *tiles, size_t cnt, int nb, LmState
   const size_t lds = std::max<size_t>((size_t)(threads / 64) * 64 * 17 * sizeof(double), (size_t)96 << 10);
   // a fit that has the device to itself in one round keeps its tiles in registers (k_lm_persist<M, 4>: 512 threads)
   const bool resident = host_step && threads == 512 && (size_t)Gl * 2 >= (size_t)nb && c->opt_lm_persist_resident;
-  if (hipFuncSetAttribute((const void *)k_lm_persist<M, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 << 10) !=
-          hipSuccess ||
-      hipFuncSetAttribute((const void *)k_lm_persist<M, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 << 10) !=
-          hipSuccess) {
-    lmp_release(c->device, G);
-    return LSQR_OK;
-  }
-  LmpInit init{};
-  init.n = n;
-  init.maxfev = maxfev;
-  init.ftol = ftol;
-  init.xtol = xtol;
-  init.gtol = gtol;
-  init.factor = 100.0;
-  for (int j = 0; j < LM_NMAX; j++) init.x0[j] = j < n ? x0[j] : 0.0;
-  const uint32_t seq0 = c->lm_seq;
-  c->lm_seq += (uint32_t)maxfev + 8;
-  const unsigned long long timeout = (unsigned long long)std::max(1, c->opt_lm_persist_timeout_ms) * 100000ULL;  // 100 MHz
-  auto give_up = [&](int rc) {
+  auto give_up = [&](int rc) {  // every way out before the kernel has ended and the tokens have gone back
     lmp_release(c->device, G);
     return rc;
   };
+  if (hipFuncSetAttribute((const void *)k_lm_persist<M, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 << 10) !=
+          hipSuccess ||
+      hipFuncSetAttribute((const void *)k_lm_persist<M, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 << 10) !=
+          hipSuccess)
+    return give_up(LSQR_OK);
+  LmpInit init{};
+  init.n = t.n;
+  init.maxfev = t.maxfev;
+  init.ftol = t.ftol;
+  init.xtol = t.xtol;
+  init.gtol = t.gtol;
+  init.factor = 100.0;
+  for (int j = 0; j < LM_NMAX; j++) init.x0[j] = j < t.n ? x0[j] : 0.0;
+  const uint32_t seq0 = c->lm_seq;
+  c->lm_seq += (uint32_t)t.maxfev + 8;
+  const unsigned long long timeout = (unsigned long long)std::max(1, c->opt_lm_persist_timeout_ms) * 100000ULL;  // 100 MHz
   if (hipMemsetAsync(c->d_lmp, 0, sizeof(LmpCtl), c->stream) != hipSuccess) return give_up(LSQR_OK);
   {
     ProfScope ps(c, KID_MOMENTS);
-    if (resident)
-      hipLaunchKernelGGL((k_lm_persist<M, 4>), dim3(Gl), dim3(threads), lds, c->stream, tiles, cnt, nb, c->d_lmp,
-                         c->d_partials, c->h_lmres, c->h_lmcmd, c->d_lm, c->d_out, init, seq0, host_step, timeout,
+    auto launch = [&](auto kern) {
+      hipLaunchKernelGGL(kern, dim3(Gl), dim3(threads), lds, c->stream, tiles, cnt, nb, c->d_lmp, c->d_partials,
+                         c->h_lmres, c->h_lmcmd, c->d_lm, c->d_out, init, seq0, host_step, timeout,
                          (uint32_t)c->opt_lm_persist_test_abort);
-    else
-      hipLaunchKernelGGL((k_lm_persist<M, 0>), dim3(Gl), dim3(threads), lds, c->stream, tiles, cnt, nb, c->d_lmp,
-                         c->d_partials, c->h_lmres, c->h_lmcmd, c->d_lm, c->d_out, init, seq0, host_step, timeout,
-                         (uint32_t)c->opt_lm_persist_test_abort);
+    };
+    if (resident) launch(k_lm_persist<M, 4>);
+    else launch(k_lm_persist<M, 0>);
   }
   if (hipGetLastError() != hipSuccess) return give_up(LSQR_OK);
   bool gave_up = false;
   uint64_t host_wait_ns = 0, host_step_ns = 0;
   if (host_step) {
-    lm_init(s, n, x0, ftol, xtol, gtol, maxfev, 100.0);
-    volatile unsigned long long *res = c->h_lmres;
+    lm_init(s, t.n, x0, t.ftol, t.xtol, t.gtol, t.maxfev, 100.0);
     volatile unsigned long long *cmd = c->h_lmcmd;
-    for (uint32_t e = 1; !gave_up; e++) {
+    for (uint32_t e = 1;; e++) {
       const uint32_t tag = seq0 + e;
-      unsigned long long spins = 0;
       double blk[LM_MOM_MAX];
+      hipError_t q = hipSuccess;
       const auto tw0 = std::chrono::steady_clock::now();
-      for (int j = 0; j < NMOM && !gave_up; j++) {
-        unsigned long long g0, g1;
-        while ((uint32_t)(g0 = res[2 * j]) != tag || (uint32_t)(g1 = res[2 * j + 1]) != tag) {
-          if ((++spins & 0xFFFF) == 0) {  // every 65 k polls: is the kernel still there?
-            hipError_t q = hipStreamQuery(c->stream);
-            if (q != hipSuccess && q != hipErrorNotReady) {
-              lmp_release(c->device, G);
-              return fail(c, LSQR_ERR_HIP, "persistent LM kernel failed: %s", hipGetErrorString(q));
-            }
-            if (q == hipSuccess && ((uint32_t)res[2 * j] != tag || (uint32_t)res[2 * j + 1] != tag)) {
-              gave_up = true;  // the kernel left (a bounded wait expired) without this evaluation
-              break;
-            }
-          }
-        }
-        if (gave_up) break;
-        const unsigned long long bits = (g0 & 0xFFFFFFFF00000000ULL) | (g1 >> 32);
-        memcpy(&blk[j], &bits, 8);
+      const LmWait w = lm_wait_block(c, c->h_lmres, tag, NMOM, blk, &q);
+      if (w == LM_STREAM_ERROR)
+        return give_up(fail(c, LSQR_ERR_HIP, "persistent LM kernel failed: %s", hipGetErrorString(q)));
+      if (w == LM_LEFT) {  // the kernel left (a bounded wait expired) without this evaluation
+        gave_up = true;
+        break;
       }
-      if (gave_up) break;
       const auto tw1 = std::chrono::steady_clock::now();
       const bool cont = lm_advance(s, blk);
       uint32_t words[2 * LMP_MAXCOEF] = {0};
@@ -2569,228 +2530,238 @@ int lm_persist_fit(lsqr_ctx *c, const double *tiles, size_t cnt, int nb, LmState
   return LSQR_OK;
 }
 
+// ---- the iterative fit: three drivers of one minimisation (lm_core.h) -------------------------------------------------
+// the matrix-core pass pays when the (J | f) rows are wide (US: 12 / 9 columns, 78 / 45 sums); for the sphere's 5
+// columns the 16 x 16 tile is mostly padding and the instruction time alone (25 us at 3.8 M points) exceeds the
+// per-lane version's whole pass
+template <class M>
+bool lm_mfma_pass(const lsqr_ctx *c) {
+  return c->opt_lm_mfma && M::NLM >= 8;
+}
+
+// what an evaluation of the fused driver reads -- the upload, through the mask or not, or the compacted consensus
+// set -- and how the pass is cut into blocks
+struct LmPassSet {
+  const double *data;
+  size_t stride, cnt;
+  bool through_mask;
+  bool tiles;  // compacted in tiles of 64 records, field-major (kernels.h: k_compact_write_tiles)
+  int nb;
+  size_t chunk;
+};
+
+// the consensus set, tight and in order (every evaluation then streams n_in records, all lanes busy) -> d_lmrec
+template <class M>
+int lm_compact(lsqr_ctx *c, LmPassSet &w) {
+  const bool tile_layout = lm_mfma_pass<M>(c) && c->opt_lm_tiles;
+  double *pin = c->h_pin->scratch_f64;
+  const auto [cb, cchunk] = pass_shape(c->n, kBlock * 8, 1024, kBlock);  // (c->n > 0: need_ready(c, true))
+  uint32_t *d_cnt = (uint32_t *)c->d_partials.get(), *d_off = d_cnt + 1024;  // scratch (4.4 MB buffer)
+  hipLaunchKernelGGL(k_compact_count, dim3(cb), dim3(kBlock), 0, c->stream, c->d_mask, c->n, cchunk, d_cnt);
+  hipLaunchKernelGGL(k_compact_scan, dim3(1), dim3(1024), 0, c->stream, d_cnt, cb, d_off);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(pin + 200, d_off + cb, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, sync_stream(c));
+  w.cnt = *(const uint32_t *)(pin + 200);
+  int st = ensure(c, c->d_lmrec, ((std::max<size_t>(w.cnt, 1) + 63) & ~(size_t)63) * M::ND);
+  if (st != LSQR_OK) return st;
+  if (tile_layout)  // the matrix-core pass reads tiles of 64 records stored field-major (kernels.h)
+    hipLaunchKernelGGL((k_compact_write_tiles<M::ND>), dim3(cb), dim3(kBlock), 0, c->stream, c->d_data, c->stride,
+                       c->d_mask, c->n, cchunk, d_off, c->d_lmrec);
+  else
+    hipLaunchKernelGGL((k_compact_write<M::ND>), dim3(cb), dim3(kBlock), 0, c->stream, c->d_data, c->stride,
+                       c->d_mask, c->n, cchunk, d_off, c->d_lmrec);
+  HIPCHK(c, hipGetLastError());
+  w.data = c->d_lmrec;
+  w.stride = M::ND;
+  w.through_mask = false;
+  w.tiles = tile_layout;
+  return LSQR_OK;
+}
+
+void lm_shape(LmPassSet &w, bool mfma_pass) {
+  if (w.tiles) {  // four tiles per wave and more: one in flight behind the one being evaluated
+    w.nb = (int)std::min<size_t>(512, std::max<size_t>(1, (w.cnt + 1023) / 1024));
+    w.chunk = 0;
+    return;
+  }
+  const PassShape ps = pass_shape(w.cnt, kBlock * (mfma_pass ? 2 : 8), kMaxPartials, kBlock);
+  w.nb = ps.nb;
+  w.chunk = ps.chunk;
+}
+
+// the sums of one evaluation at xk -> d_partials (w.nb blocks)
+template <class M>
+int lm_launch_pass(lsqr_ctx *c, const LmPassSet &w, const LmX &xk) {
+  bool launched = false;
+  if constexpr (requires { typename M::LmCoef; }) {
+    if (lm_mfma_pass<M>(c)) {
+      typename M::LmCoef coef;
+      M::lm_coef(xk.x, coef);
+      if (w.tiles)
+        hipLaunchKernelGGL((k_lm_pass_mfma_t<M>), dim3(w.nb), dim3(kBlock), 0, c->stream, w.data, w.cnt, coef,
+                           c->d_partials);
+      else
+        hipLaunchKernelGGL((k_lm_pass_mfma<M>), dim3(w.nb), dim3(kBlock), 0, c->stream, w.data, w.stride, w.cnt, coef,
+                           c->mc, c->d_partials);
+      launched = true;
+    }
+  }
+  if (!launched) {
+    auto launch = [&](auto kern, const uint8_t *mask) {
+      hipLaunchKernelGGL(kern, dim3(w.nb), dim3(kBlock), 0, c->stream, w.data, w.stride, (size_t)0, w.cnt, w.chunk, mask,
+                         xk, c->mc, c->d_partials);
+    };
+    if (w.through_mask) launch(k_lm_pass<M, true>, (const uint8_t *)c->d_mask);
+    else launch(k_lm_pass<M, false>, (const uint8_t *)nullptr);
+  }
+  HIPCHK(c, hipGetLastError());
+  return LSQR_OK;
+}
+
+// The host's step and one launch per evaluation: trial point by value, block sums + final sum in the same kernel, the
+// result lands in pinned host memory and the host polls its sequence flag (no stream synchronisation, no staging
+// copies): per evaluation = the pass + one launch latency + a few hundred host flops.
+// Compacting the consensus set costs about as much as six evaluations through the mask save (10 M records, 38 %
+// inliers: count + scan + host read-back + write = 130 us; a pass over the compacted set is 23 us against 43 us), and
+// the sphere's geometric fit from the algebraic start typically needs three: the per-lane pass starts THROUGH THE MASK
+// and the set is compacted once `kCompactAfter` evaluations have been spent.  The matrix-core pass (US: thousands of
+// evaluations) reads compacted records only and compacts at once.
+template <class M>
+int lm_fit_fused(lsqr_ctx *c, int use_mask, const LmSet &t, const double *x0, LmState &s) {
+  constexpr int kCompactAfter = 8;
+  const bool mfma_pass = lm_mfma_pass<M>(c);
+  LmPassSet w{c->d_data, c->stride, c->n, use_mask != 0, false, 1, 0};
+  int st;
+  if (use_mask && mfma_pass && (st = lm_compact<M>(c, w)) != LSQR_OK) return st;
+  lm_shape(w, mfma_pass);
+  bool persist_done = false;
+  if constexpr (requires { typename M::LmCoef; }) {
+    if (mfma_pass && w.tiles) {  // the whole fit in one launch (lm_persist.h); falls through when it gives up
+      if ((st = lm_persist_fit<M>(c, w.data, w.cnt, w.nb, s, x0, t, &persist_done)) != LSQR_OK) return st;
+    }
+  }
+  if (!persist_done) lm_init(s, t.n, x0, t.ftol, t.xtol, t.gtol, t.maxfev, 100.0);
+  while (!persist_done) {
+    if (w.through_mask && s.nfev >= kCompactAfter) {
+      if ((st = lm_compact<M>(c, w)) != LSQR_OK) return st;
+      lm_shape(w, mfma_pass);
+    }
+    LmX xk;
+    for (int j = 0; j < LM_NMAX; j++) xk.x[j] = j < t.n ? s.xtrial[j] : 0.0;
+    uint32_t seq = ++c->lm_seq;
+    if (seq == 0) seq = c->lm_seq = 1;  // (the zero-initialised granules carry tag 0)
+    // profiling: every 16th evaluation carries event pairs (four event records per evaluation would cost
+    // more host time than the evaluation's own launches); lsqr_profile_get's averages are unaffected
+    const bool timed = c->prof && (s.nfev & 15) == 0;
+    const bool prof_saved = c->prof;
+    c->prof = timed;
+    {
+      ProfScope ps(c, KID_MOMENTS);
+      if ((st = lm_launch_pass<M>(c, w, xk)) != LSQR_OK) return st;
+    }
+    {
+      ProfScope ps(c, KID_SOLVE);
+      hipLaunchKernelGGL(k_lm_publish, dim3((unsigned)M::NMOM_LM), dim3(64), 0, c->stream, c->d_partials, w.nb,
+                         (int)M::NMOM_LM, c->h_lmres, seq);
+      HIPCHK(c, hipGetLastError());
+    }
+    c->prof = prof_saved;
+    double blk[LM_MOM_MAX];
+    hipError_t q = hipSuccess;
+    switch (lm_wait_block(c, c->h_lmres, seq, (int)M::NMOM_LM, blk, &q)) {
+      case LM_STREAM_ERROR: return fail(c, LSQR_ERR_HIP, "LM pass failed: %s", hipGetErrorString(q));
+      case LM_LEFT: return fail(c, LSQR_ERR_HIP, "LM pass finished without publishing its result");
+      case LM_GOT: break;
+    }
+    if (!lm_advance(s, blk)) break;
+  }
+  HIPCHK(c, sync_stream(c));
+  return LSQR_OK;
+}
+
+// the host's step through staged copies ("lm_fused" 0): trial point up, launch_moments, block down, per evaluation
+template <class M>
+int lm_fit_staged(lsqr_ctx *c, int use_mask, const LmSet &t, const double *x0, LmState &s) {
+  lm_init(s, t.n, x0, t.ftol, t.xtol, t.gtol, t.maxfev, 100.0);
+  double *pin = c->h_pin->scratch_f64;
+  for (;;) {
+    int nmom = 0, st;
+    for (int j = 0; j < t.n; j++) pin[j] = s.xtrial[j];
+    HIPCHK(c, hipMemcpyAsync(c->d_vec, pin, sizeof(double) * t.n, hipMemcpyHostToDevice, c->stream));
+    if ((st = launch_moments<M>(c, use_mask, 0, c->n, 1, &nmom)) != LSQR_OK) return st;
+    HIPCHK(c, hipMemcpyAsync(pin + 64, c->d_mom, sizeof(double) * nmom, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, sync_stream(c));
+    if (!lm_advance(s, pin + 64)) return LSQR_OK;
+  }
+}
+
+// the step in a device kernel ("lm_host" 0), from the algebraic result in d_out; every evaluation reads `out` back
+template <class M>
+int lm_fit_on_device(lsqr_ctx *c, int use_mask, const LmSet &t, SolveOut *out) {
+  hipLaunchKernelGGL(k_lm_init, dim3(1), dim3(64), 0, c->stream, c->d_lm, c->d_out, t.n, t.ftol, t.xtol, t.gtol,
+                     t.maxfev, 100.0);
+  HIPCHK(c, hipGetLastError());
+  for (;;) {
+    int nmom = 0, st;
+    HIPCHK(c, hipMemcpyAsync(c->d_vec, (const char *)c->d_lm.get() + offsetof(LmState, xtrial), sizeof(double) * t.n,
+                             hipMemcpyDeviceToDevice, c->stream));
+    if ((st = launch_moments<M>(c, use_mask, 0, c->n, 1, &nmom)) != LSQR_OK) return st;
+    {
+      ProfScope ps(c, KID_SOLVE);
+      hipLaunchKernelGGL((k_lm_advance<M>), dim3(1), dim3(64), 0, c->stream, c->d_lm, c->d_mom, c->d_out);
+      HIPCHK(c, hipGetLastError());
+    }
+    if ((st = read_out(c, out)) != LSQR_OK) return st;
+    if (!out->cont) return LSQR_OK;
+  }
+}
+
+// the plane phantom: both fits from the Gram block, on the host
+int fit_phantom(lsqr_ctx *c, int use_mask, SolveOut *out) {
+  int nmom = 0, st;
+  if ((st = launch_moments_phantom(c, use_mask, 0, c->n, &nmom)) != LSQR_OK) return st;
+  HIPCHK(c, hipMemcpyAsync(c->h_pin->scratch, c->d_mom, sizeof(double) * nmom, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, sync_stream(c));
+  phantom_solve_block(c->cfg, c->h_pin->scratch_f64, out);
+  return LSQR_OK;
+}
+
 // leastSquaresEstimate over [0,n) (single device).  Leaves the result in d_out.
 // have_moments: d_mom already holds the phase-0 block about d_vec (launch_mask_moments)
 // have_origin: the caller has put the fit origin into d_vec (set_fit_origin)
 int run_fit(lsqr_ctx *c, int use_mask, SolveOut *out, bool have_moments = false, bool have_origin = false) {
   return dispatch(c->cfg, [&](auto tag) -> int {
     typedef typename decltype(tag)::type M;
-    int nmom = 0, st;
     if constexpr (requires { M::IS_PHANTOM; }) {
-      if ((st = launch_moments_phantom(c, use_mask, 0, c->n, &nmom)) != LSQR_OK) return st;
-      HIPCHK(c, hipMemcpyAsync(c->h_pin->scratch, c->d_mom, sizeof(double) * nmom, hipMemcpyDeviceToHost,
-                               c->stream));
-      HIPCHK(c, sync_stream(c));
-      phantom_solve_block(c->cfg, c->h_pin->scratch_f64, out);
-      return LSQR_OK;
-    } else if constexpr (M::IS_DENSE) {
-      if ((st = enqueue_closed_fit<M>(c, use_mask, have_moments, have_origin)) != LSQR_OK) return st;
-      return read_out(c, out);
+      return fit_phantom(c, use_mask, out);
     } else {
-    if ((st = enqueue_closed_fit<M>(c, use_mask, have_moments, have_origin)) != LSQR_OK) return st;
-    if (!wants_lm(c->cfg)) return read_out(c, out);
-    if ((st = read_out(c, out)) != LSQR_OK) return st;
-    if (!out->ok) return LSQR_OK;  // algebraic initialiser failed -> empty (Sphere...hxx:231-232)
-    int n;
-    double ftol, xtol, gtol;
-    int maxfev;
-    lm_settings(c->cfg, &n, &ftol, &xtol, &gtol, &maxfev);
-    if constexpr (requires { M::NMOM_LM; }) {
-      if (c->opt_lm_host) {
-        // MINPACK's control flow between device passes runs on the host (like the RANSAC replay):
-        // a few hundred flops per evaluation; every N-scale operation stays a device pass.
-        LmState &s = c->h_lm;
-        lm_init(s, n, out->params, ftol, xtol, gtol, maxfev, 100.0);
-        double *pin = c->h_pin->scratch_f64;
-        if (c->opt_lm_fused) {
-          // one launch per evaluation: trial point by value, block sums + final sum in the same kernel, the
-          // result lands in pinned host memory and the host polls its sequence flag (no stream synchronisation,
-          // no staging copies): per evaluation = the pass + one launch latency + a few hundred host flops
-          // the consensus set, tight and in order (every evaluation then streams n_in records, all lanes busy)
-          // Compacting costs about as much as six evaluations through the mask save (10 M records, 38 % inliers:
-          // count + scan + host read-back + write = 130 us; a pass over the compacted set is 23 us against 43 us), and
-          // the sphere's geometric fit from the algebraic start typically needs three: the per-lane pass starts
-          // THROUGH THE MASK and the set is compacted once `kCompactAfter` evaluations have been spent.  The
-          // matrix-core pass (US: thousands of evaluations) reads compacted records only and compacts at once.
-          constexpr int kCompactAfter = 8;
-          const bool mfma_pass = c->opt_lm_mfma && M::NLM >= 8;
-          const bool tile_layout = mfma_pass && c->opt_lm_tiles;   // compacted set in tiles of 64 records, field-major
-          bool tiles = false;                                      // ... and it has been written that way
-          const double *lm_data = c->d_data;
-          size_t lm_stride = c->stride, cnt = c->n;
-          bool through_mask = use_mask;
-          auto compact = [&]() -> int {
-            int cb = grid_for(c->n, kBlock * 8, 1024);
-            size_t cchunk = (c->n + cb - 1) / cb;
-            cchunk = (cchunk + kBlock - 1) / kBlock * kBlock;
-            cb = (int)((c->n + cchunk - 1) / cchunk);
-            uint32_t *d_cnt = (uint32_t *)c->d_partials.get(), *d_off = d_cnt + 1024;  // scratch (4.4 MB buffer)
-            hipLaunchKernelGGL(k_compact_count, dim3(cb), dim3(kBlock), 0, c->stream, c->d_mask, c->n, cchunk, d_cnt);
-            hipLaunchKernelGGL(k_compact_scan, dim3(1), dim3(1024), 0, c->stream, d_cnt, cb, d_off);
-            HIPCHK(c, hipGetLastError());
-            HIPCHK(c, hipMemcpyAsync(pin + 200, d_off + cb, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, sync_stream(c));
-            cnt = *(const uint32_t *)(pin + 200);
-            int st2 = ensure(c, c->d_lmrec, ((std::max<size_t>(cnt, 1) + 63) & ~(size_t)63) * M::ND);
-            if (st2 != LSQR_OK) return st2;
-            if (tile_layout)  // the matrix-core pass reads tiles of 64 records stored field-major (kernels.h)
-              hipLaunchKernelGGL((k_compact_write_tiles<M::ND>), dim3(cb), dim3(kBlock), 0, c->stream, c->d_data,
-                                 c->stride, c->d_mask, c->n, cchunk, d_off, c->d_lmrec);
-            else
-              hipLaunchKernelGGL((k_compact_write<M::ND>), dim3(cb), dim3(kBlock), 0, c->stream, c->d_data, c->stride,
-                                 c->d_mask, c->n, cchunk, d_off, c->d_lmrec);
-            HIPCHK(c, hipGetLastError());
-            lm_data = c->d_lmrec;
-            lm_stride = M::ND;
-            through_mask = false;
-            tiles = tile_layout;
-            return LSQR_OK;
-          };
-          int nb = 1;
-          size_t chunk = 0;
-          auto shape = [&]() {
-            if (tiles) {   // four tiles per wave and more: one in flight behind the one being evaluated
-              nb = (int)std::min<size_t>(512, std::max<size_t>(1, (cnt + 1023) / 1024));
-              chunk = 0;
-              return;
-            }
-            nb = grid_for(cnt, kBlock * (mfma_pass ? 2 : 8), kMaxPartials);
-            chunk = (cnt + nb - 1) / nb;
-            chunk = (chunk + kBlock - 1) / kBlock * kBlock;
-            nb = (int)((cnt + chunk - 1) / chunk);
-            if (nb < 1) nb = 1;
-          };
-          if (use_mask && mfma_pass && (st = compact()) != LSQR_OK) return st;
-          shape();
-          bool persist_done = false;
-          if constexpr (requires { typename M::LmCoef; }) {
-            if (mfma_pass && tiles) {  // the whole fit in one launch (lm_persist.h); falls through when it gives up
-              if ((st = lm_persist_fit<M>(c, lm_data, cnt, nb, s, out->params, n, ftol, xtol, gtol, maxfev,
-                                          &persist_done)) != LSQR_OK)
-                return st;
-              if (!persist_done) lm_init(s, n, out->params, ftol, xtol, gtol, maxfev, 100.0);
-            }
-          }
-          volatile unsigned long long *res = c->h_lmres;
-          while (!persist_done) {
-            if (through_mask && s.nfev >= kCompactAfter) {
-              if ((st = compact()) != LSQR_OK) return st;
-              shape();
-            }
-            LmX xk;
-            for (int j = 0; j < LM_NMAX; j++) xk.x[j] = j < n ? s.xtrial[j] : 0.0;
-            uint32_t seq = ++c->lm_seq;
-            if (seq == 0) seq = c->lm_seq = 1;  // (the zero-initialised granules carry tag 0)
-            // profiling: every 16th evaluation carries event pairs (four event records per evaluation would cost
-            // more host time than the evaluation's own launches); lsqr_profile_get's averages are unaffected
-            const bool timed = c->prof && (s.nfev & 15) == 0;
-            const bool prof_saved = c->prof;
-            c->prof = timed;
-            {
-              ProfScope ps(c, KID_MOMENTS);
-              if constexpr (requires { typename M::LmCoef; }) {
-                // the matrix-core pass pays when the (J | f) rows are wide (US: 12 / 9 columns, 78 / 45 sums); for the
-                // sphere's 5 columns the 16 x 16 tile is mostly padding and the instruction time alone (25 us at 3.8 M
-                // points) exceeds the per-lane version's whole pass
-                if (mfma_pass && tiles) {
-                  typename M::LmCoef coef;
-                  M::lm_coef(xk.x, coef);
-                  hipLaunchKernelGGL((k_lm_pass_mfma_t<M>), dim3(nb), dim3(kBlock), 0, c->stream, lm_data, cnt, coef,
-                                     c->d_partials);
-                } else if (mfma_pass) {
-                  typename M::LmCoef coef;
-                  M::lm_coef(xk.x, coef);
-                  hipLaunchKernelGGL((k_lm_pass_mfma<M>), dim3(nb), dim3(kBlock), 0, c->stream, lm_data, lm_stride,
-                                     cnt, coef, c->mc, c->d_partials);
-                } else if (through_mask)
-                  hipLaunchKernelGGL((k_lm_pass<M, true>), dim3(nb), dim3(kBlock), 0, c->stream, lm_data, lm_stride,
-                                     (size_t)0, cnt, chunk, (const uint8_t *)c->d_mask, xk, c->mc, c->d_partials);
-                else
-                  hipLaunchKernelGGL((k_lm_pass<M, false>), dim3(nb), dim3(kBlock), 0, c->stream, lm_data, lm_stride,
-                                     (size_t)0, cnt, chunk, (const uint8_t *)nullptr, xk, c->mc, c->d_partials);
-              } else if (through_mask) {
-                hipLaunchKernelGGL((k_lm_pass<M, true>), dim3(nb), dim3(kBlock), 0, c->stream, lm_data, lm_stride,
-                                   (size_t)0, cnt, chunk, (const uint8_t *)c->d_mask, xk, c->mc, c->d_partials);
-              } else {
-                hipLaunchKernelGGL((k_lm_pass<M, false>), dim3(nb), dim3(kBlock), 0, c->stream, lm_data, lm_stride,
-                                   (size_t)0, cnt, chunk, (const uint8_t *)nullptr, xk, c->mc, c->d_partials);
-              }
-              HIPCHK(c, hipGetLastError());
-            }
-            {
-              ProfScope ps(c, KID_SOLVE);
-              hipLaunchKernelGGL(k_lm_publish, dim3((unsigned)M::NMOM_LM), dim3(64), 0, c->stream, c->d_partials, nb,
-                                 (int)M::NMOM_LM, c->h_lmres, seq);
-              HIPCHK(c, hipGetLastError());
-            }
-            c->prof = prof_saved;
-            // poll the granules in order: each one is valid as soon as its tag is this evaluation's
-            unsigned long long spins = 0;
-            double blk[LM_MOM_MAX];
-            for (int j = 0; j < (int)M::NMOM_LM; j++) {
-              unsigned long long g0, g1;
-              while ((uint32_t)(g0 = res[2 * j]) != seq || (uint32_t)(g1 = res[2 * j + 1]) != seq) {
-                if ((++spins & 0xFFFF) == 0) {  // every 65 k polls: is the stream still alive?
-                  hipError_t q = hipStreamQuery(c->stream);
-                  if (q != hipSuccess && q != hipErrorNotReady)
-                    return fail(c, LSQR_ERR_HIP, "LM pass failed: %s", hipGetErrorString(q));
-                  if (q == hipSuccess && ((uint32_t)res[2 * j] != seq || (uint32_t)res[2 * j + 1] != seq))
-                    return fail(c, LSQR_ERR_HIP, "LM pass finished without publishing its result");
-                }
-              }
-              const unsigned long long bits = (g0 & 0xFFFFFFFF00000000ULL) | (g1 >> 32);
-              memcpy(&blk[j], &bits, 8);
-            }
-            if (!lm_advance(s, blk)) break;
-          }
-          HIPCHK(c, sync_stream(c));
-        } else
-        for (;;) {
-          for (int j = 0; j < n; j++) pin[j] = s.xtrial[j];
-          HIPCHK(c, hipMemcpyAsync(c->d_vec, pin, sizeof(double) * n, hipMemcpyHostToDevice,
-                                   c->stream));
-          if ((st = launch_moments<M>(c, use_mask, 0, c->n, 1, &nmom)) != LSQR_OK) return st;
-          HIPCHK(c, hipMemcpyAsync(pin + 64, c->d_mom, sizeof(double) * nmom,
-                                   hipMemcpyDeviceToHost, c->stream));
-          HIPCHK(c, sync_stream(c));
-          if (!lm_advance(s, pin + 64)) break;
-        }
-        bool ok = s.info >= 1 && s.info <= 4;  // vnl_levenberg_marquardt::minimize -> true
-        {
+      int st;
+      if ((st = enqueue_closed_fit<M>(c, use_mask, have_moments, have_origin)) != LSQR_OK) return st;
+      if ((st = read_out(c, out)) != LSQR_OK) return st;
+      if constexpr (requires { M::NMOM_LM; }) {  // (every model wants_lm can name today has an LM block)
+        if (!wants_lm(c->cfg) || !out->ok) return LSQR_OK;  // algebraic initialiser failed -> empty (Sphere...hxx:231-232)
+        LmSet t;
+        lm_settings(c->cfg, &t.n, &t.ftol, &t.xtol, &t.gtol, &t.maxfev);
+        if (c->opt_lm_host) {
+          // MINPACK's control flow between device passes runs on the host (like the RANSAC replay):
+          // a few hundred flops per evaluation; every N-scale operation stays a device pass.
+          LmState &s = c->h_lm;
+          st = c->opt_lm_fused ? lm_fit_fused<M>(c, use_mask, t, out->params, s)
+                               : lm_fit_staged<M>(c, use_mask, t, out->params, s);
+          if (st != LSQR_OK) return st;
           static const bool dbg_on = getenv("LSQR_LM_DEBUG") != nullptr;
           if (dbg_on)
             fprintf(stderr, "lm: info %d nfev %d outer iterations %d (accepted steps %d) cost %.17g stall %d par %.3g delta %.3g\n",
                     s.info, s.nfev, s.iter, s.iter - 1, s.fnorm * s.fnorm, s.stall, s.par, s.delta);
+          lm_fill_result(s, M::lm_finalize(s.x, out->params), out);
+          return LSQR_OK;
         }
-        out->ok = ok ? 1 : 0;
-        out->cont = 0;
-        out->lm_info = s.info;
-        out->lm_nfev = s.nfev;
-        out->pad = s.stall;
-        out->cost = s.fnorm * s.fnorm;
-        int np = M::lm_finalize(s.x, out->params);
-        out->n_params = ok ? np : 0;
+        return lm_fit_on_device<M>(c, use_mask, t, out);
+      } else {
+        if (wants_lm(c->cfg) && out->ok) return fail(c, LSQR_ERR_INVALID, "model has no iterative phase");
         return LSQR_OK;
       }
-    }
-    hipLaunchKernelGGL(k_lm_init, dim3(1), dim3(64), 0, c->stream, c->d_lm, c->d_out, n, ftol,
-                       xtol, gtol, maxfev, 100.0);
-    HIPCHK(c, hipGetLastError());
-    for (;;) {
-      HIPCHK(c, hipMemcpyAsync(c->d_vec, (const char *)c->d_lm.get() + offsetof(LmState, xtrial),
-                               sizeof(double) * n, hipMemcpyDeviceToDevice, c->stream));
-      if ((st = launch_moments<M>(c, use_mask, 0, c->n, 1, &nmom)) != LSQR_OK) return st;
-      {
-        ProfScope ps(c, KID_SOLVE);
-        if constexpr (requires { M::NMOM_LM; })
-          hipLaunchKernelGGL((k_lm_advance<M>), dim3(1), dim3(64), 0, c->stream, c->d_lm, c->d_mom,
-                             c->d_out);
-        HIPCHK(c, hipGetLastError());
-      }
-      if ((st = read_out(c, out)) != LSQR_OK) return st;
-      if (!out->cont) break;
-    }
-    return LSQR_OK;
     }
   });
 }
@@ -2861,12 +2832,11 @@ int launch_mask_moments(lsqr_ctx *c, size_t begin, size_t end, int *nmom, bool *
       return LSQR_OK;
     if ((st = ensure_absmax(c)) != LSQR_OK) return st;  // magnitudes for the band of the four-chain evaluation
     HIPCHK(c, hipMemsetAsync(c->d_counter + CNT_MASK, 0, sizeof(unsigned long long), c->stream));
-    const size_t cnt = end - begin;
     const int nbuf = (c->opt_mask_ring == 4 && n == 64) ? 4 : 2;
-    int nb = grid_for(cnt, 64 * 4, nbuf == 2 ? 512 : 256);   // two workgroups per CU / one
-    size_t chunk = (cnt + nb - 1) / nb;
-    chunk = (chunk + 63) / 64 * 64;                 // whole rounds of the four waves' 16-row tiles
-    nb = (int)((cnt + chunk - 1) / chunk);
+    // two workgroups per CU / one; whole rounds of the four waves' 16-row tiles (end > begin: checked above)
+    const PassShape shape = pass_shape(end - begin, 64 * 4, nbuf == 2 ? 512 : 256, 64);
+    const int nb = shape.nb;
+    const size_t chunk = shape.chunk;
     const int ps = dense_pstride(n), na16 = (n + 15) / 16;
     // ring + model + waiting rows while streaming; the fold area afterwards
     const size_t lds = std::max<size_t>(sizeof(double) * (4 * nbuf * 16 * nz + 64 + 4 * 3 * nz),
@@ -2883,12 +2853,13 @@ int launch_mask_moments(lsqr_ctx *c, size_t begin, size_t end, int *nmom, bool *
       };
       if (nbuf == 4) {
         launch(k_mask_syrk_dense<4, 4>);   // n = 64: one workgroup per CU, three tiles in flight per wave
-      } else
-      switch (na16) {
-        case 1: launch(k_mask_syrk_dense<1, 2>); break;
-        case 2: launch(k_mask_syrk_dense<2, 2>); break;
-        case 3: launch(k_mask_syrk_dense<3, 2>); break;
-        default: launch(k_mask_syrk_dense<4, 2>); break;
+      } else {
+        switch (na16) {
+          case 1: launch(k_mask_syrk_dense<1, 2>); break;
+          case 2: launch(k_mask_syrk_dense<2, 2>); break;
+          case 3: launch(k_mask_syrk_dense<3, 2>); break;
+          default: launch(k_mask_syrk_dense<4, 2>); break;
+        }
       }
       HIPCHK(c, hipGetLastError());
     }
@@ -2912,12 +2883,10 @@ int launch_mask_moments(lsqr_ctx *c, size_t begin, size_t end, int *nmom, bool *
         hipLaunchKernelGGL((k_prepare<M>), dim3(1), dim3(64), 0, c->stream, c->d_par, c->mc);
         HIPCHK(c, hipGetLastError());
       }
-      size_t cnt = end - begin;
-      int nb = grid_for(cnt, mom_chunk(c), kMaxPartials);  // the chunking of launch_moments
-      size_t chunk = (cnt + nb - 1) / nb;
-      chunk = (chunk + kBlock - 1) / kBlock * kBlock;
-      nb = (int)((cnt + chunk - 1) / chunk);
-      if (nb < 1) nb = 1;
+      const size_t cnt = end - begin;
+      const PassShape shape = pass_shape(cnt, mom_chunk(c), kMaxPartials, kBlock);  // as launch_moments
+      int nb = shape.nb;
+      const size_t chunk = shape.chunk;
       *nmom = M::NMOM;
       bool done = false;
       if constexpr (M::IS_US) {
@@ -3575,25 +3544,21 @@ int lsqr_lm_step(lsqr_ctx *c, const double *block, double *x_trial_out, int *con
     LmState &s = c->h_lm;
     bool go = lm_advance(s, block);
     *cont = go ? 1 : 0;
-    SolveOut out;  // the record run_fit's host loop leaves
+    SolveOut out;  // the record run_fit's host-stepped drivers leave
     memset(&out, 0, sizeof out);
-    out.lm_info = s.info;
-    out.lm_nfev = s.nfev;
-    out.pad = s.stall;
-    out.cost = s.fnorm * s.fnorm;
     if (go) {
+      lm_fill_result(s, 0, &out);
       if (x_trial_out)
         for (int j = 0; j < s.n; j++) x_trial_out[j] = s.xtrial[j];
       fill_info(out, info);
       return LSQR_OK;
     }
-    out.ok = s.info >= 1 && s.info <= 4;
     const int np = dispatch(c->cfg, [&](auto tag) -> int {
       typedef typename decltype(tag)::type M;
       if constexpr (requires { M::NMOM_LM; }) return M::lm_finalize(s.x, out.params);
       else return 0;
     });
-    out.n_params = out.ok ? np : 0;
+    lm_fill_result(s, np, &out);
     return deliver_fit(out, params_out, info);
   }
   HIPCHK(c, hipMemcpyAsync(c->d_mom, block, sizeof(double) * nmom, hipMemcpyHostToDevice,
@@ -3635,10 +3600,9 @@ int lsqr_stats(lsqr_ctx *c, const double *params, int use_mask, double out[4]) {
   HIPCHK(c, hipMemsetAsync(c->d_par, 0, sizeof(double) * 128, c->stream));
   HIPCHK(c, hipMemcpyAsync(c->d_par, params, sizeof(double) * c->P, hipMemcpyHostToDevice,
                            c->stream));
-  int nb = grid_for(c->n, mom_chunk(c), kMaxPartials);
-  size_t chunk = (c->n + nb - 1) / nb;
-  chunk = (chunk + kBlock - 1) / kBlock * kBlock;
-  nb = (int)((c->n + chunk - 1) / chunk);
+  const PassShape shape = pass_shape(c->n, mom_chunk(c), kMaxPartials, kBlock);  // (c->n > 0: need_ready(c, true))
+  const int nb = shape.nb;
+  const size_t chunk = shape.chunk;
   st = dispatch(c->cfg, [&](auto tag) -> int {
     typedef typename decltype(tag)::type M;
     if (use_mask)

@@ -1,5 +1,6 @@
 // CPU sanitizer leg (tests/test_sanitizers.py): the product's host-side code -- csrc/host_entry.h (subset stream, replay of
-// RANSAC.hxx:49-117, duplicate set, single-datum agree / estimate for every model), csrc/lm_core.h + the per-model
+// RANSAC.hxx:49-117, duplicate set, single-datum agree / estimate for every model, the cut of a pass into blocks, the
+// tagged granules and the result record of the iterative fits), csrc/lm_core.h + the per-model
 // arithmetic of csrc/{models,models_nd,rigid,us,phantom,dense_model}.h, and the plugin loop of
 // lsqrrecipes_amd/include/RANSAC.h -- compiled by g++ with -fsanitize=address,undefined -fno-sanitize-recover and driven
 // with buffers of exactly the documented sizes (heap blocks: a read or write one element past them stops the run),
@@ -7,6 +8,7 @@
 // definitions below are the library's own wrappers (lsqr_hip.hip) over the same host_* functions; being defined in the
 // executable they take precedence over liblsqr_hip.so's, so RANSAC.h's plugin path runs on the sanitized copies.
 // The oracle's C sources are linked in (same flags) and used as the checker.  Test-only.
+#include <cfloat>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -348,11 +350,117 @@ static void pluginTest() {
   CHECK(fe > 0 && c2.size() == few.size());
 }
 
+// pass_shape against the seven-line idiom it replaced, for every (per_block, max_blocks, round_to) the library uses
+static void passShapeTest() {
+  const int kBlock = 256, kMaxPartials = 1024, kSyrkTile = 32, kDenseBlocks = 256;  // kernels.h, dense.h, lsqr_hip.hip
+  const int triples[][3] = {
+      {kSyrkTile * 8, kDenseBlocks, kSyrkTile},                                     // launch_syrk
+      {kBlock * 4, kMaxPartials, kBlock},  {kBlock * 16, kMaxPartials, kBlock},     // mom_chunk: kMomChunk, kMomChunkWide
+      {kBlock * 1, kMaxPartials, kBlock},                                           // ... and the option "mom_chunk" 1
+      {kBlock * 8, 1024, kBlock},                                                   // lm_compact
+      {kBlock * 2, kMaxPartials, kBlock},  {kBlock * 8, kMaxPartials, kBlock},      // lm_shape: matrix-core / per-lane pass
+      {256, 512, 64},                      {256, 256, 64},                          // launch_mask_moments, dense
+  };
+  for (const auto &t : triples) {
+    const int per_block = t[0], max_blocks = t[1], round_to = t[2];
+    std::vector<size_t> cnts;
+    for (size_t cnt = 0; cnt <= 5000; cnt++) cnts.push_back(cnt);
+    const size_t full = (size_t)per_block * (size_t)max_blocks;
+    for (size_t k = 1; k <= 40; k++)
+      for (size_t d = 0; d <= 4; d++) cnts.push_back(k * full + d - 2);
+    for (size_t d = 0; d <= 4; d++) cnts.push_back(((size_t)1 << 33) / full * full + d - 2);  // past 32 bits
+    for (size_t cnt : cnts) {
+      const PassShape got = pass_shape(cnt, per_block, max_blocks, round_to);
+      CHECK(got.nb >= 1 && got.nb <= max_blocks);
+      CHECK((size_t)got.nb * got.chunk >= cnt);
+      CHECK(got.chunk % (size_t)round_to == 0);
+      if (cnt == 0) continue;  // (the idiom divided by a chunk of zero there; no caller passed it an empty range)
+      CHECK((size_t)(got.nb - 1) * got.chunk < cnt);
+      int nb = grid_for(cnt, per_block, max_blocks);
+      size_t chunk = (cnt + nb - 1) / nb;
+      chunk = (chunk + round_to - 1) / round_to * round_to;
+      nb = (int)((cnt + chunk - 1) / chunk);
+      if (nb < 1) nb = 1;
+      CHECK(got.nb == nb && got.chunk == chunk);
+    }
+  }
+  CHECK(grid_for(0, 256, 8) == 1 && grid_for(257, 256, 8) == 2 && grid_for(1 << 20, 256, 8) == 8);
+}
+
+// the tagged granules a moment block crosses in: every bit pattern survives, a stale half is "not there yet"
+static void granuleTest() {
+  const uint64_t patterns[] = {0x0000000000000000ull, 0x8000000000000000ull,  // +0, -0
+                               0x7FF8000000000001ull, 0xFFF0DEADBEEF1234ull,  // NaN payloads, quiet and signalling
+                               0x7FF0000000000000ull, 0x0000000000000001ull,  // infinity, the smallest denormal
+                               0x000FFFFFFFFFFFFFull, 0x7FEFFFFFFFFFFFFFull,  // the largest denormal, DBL_MAX
+                               0x3FF0000000000000ull, 0xC08F400000000001ull};
+  const int n = (int)(sizeof patterns / sizeof patterns[0]);
+  for (uint32_t tag : {1u, 0x7FFFFFFFu, 0xF0000001u, 0xFFFFFFFFu}) {
+    auto res = block<unsigned long long>(2 * (size_t)n);
+    for (int j = 0; j < n; j++) {  // as k_lm_publish writes them: {high word | tag}, {low word | tag}
+      res[2 * j] = (patterns[j] & 0xFFFFFFFF00000000ull) | tag;
+      res[2 * j + 1] = (patterns[j] << 32) | tag;
+    }
+    for (int j = 0; j < n; j++) {
+      double v = 12345.0;
+      CHECK(lm_granule_decode(res.get(), j, tag, &v));
+      uint64_t bits;
+      memcpy(&bits, &v, 8);
+      CHECK(bits == patterns[j]);
+      CHECK(!lm_granule_decode(res.get(), j, tag + 1, &v));  // the next evaluation has not arrived
+      for (int half = 0; half < 2; half++) {                 // one half still carries the evaluation before
+        const unsigned long long keep = res[2 * j + half];
+        res[2 * j + half] = (keep & 0xFFFFFFFF00000000ull) | (uint32_t)(tag - 1);
+        double w = 777.0;
+        CHECK(!lm_granule_decode(res.get(), j, tag, &w) && w == 777.0);
+        res[2 * j + half] = keep;
+      }
+    }
+  }
+  const double big = DBL_MAX;
+  CHECK(memcmp(&big, &patterns[7], 8) == 0);
+}
+
+// the record a stopped host-stepped minimisation leaves: ok for MINPACK's info 1..4 only, parameters counted only then
+static void lmResultTest() {
+  for (int info = 0; info <= 8; info++) {
+    LmState s{};
+    s.info = info;
+    s.nfev = 17 + info;
+    s.stall = 5 + info;
+    s.fnorm = 1.5 + info;
+    SolveOut out;
+    memset(&out, 0xA5, sizeof out);
+    double before[64];
+    memcpy(before, out.params, sizeof before);
+    lm_fill_result(s, 4, &out);
+    const bool ok = info >= 1 && info <= 4;  // vnl_levenberg_marquardt::minimize -> true
+    CHECK(out.ok == (ok ? 1 : 0) && out.n_params == (ok ? 4 : 0));
+    CHECK(out.lm_info == info && out.lm_nfev == 17 + info && out.cont == 0 && out.pad == 5 + info);
+    CHECK(out.cost == (1.5 + info) * (1.5 + info));
+    CHECK(memcmp(before, out.params, sizeof before) == 0);  // the parameters are M::lm_finalize's, not this function's
+  }
+  lsqr_model_cfg cfg{};
+  cfg.model = LSQR_MODEL_SPHERE, cfg.dim = 3, cfg.ls_type = LSQR_LS_GEOMETRIC;
+  int n, maxfev;
+  double ftol, xtol, gtol;
+  lm_settings(cfg, &n, &ftol, &xtol, &gtol, &maxfev);
+  CHECK(wants_lm(cfg) && n == 4 && maxfev == 500 && ftol == 1e-10 && xtol == 10e-16 && gtol == 10e-16);
+  cfg.ls_type = LSQR_LS_ALGEBRAIC;
+  CHECK(!wants_lm(cfg));
+  cfg.model = LSQR_MODEL_US_POINTER, cfg.ls_type = LSQR_LS_ITERATIVE;
+  lm_settings(cfg, &n, &ftol, &xtol, &gtol, &maxfev);
+  CHECK(wants_lm(cfg) && n == 8 && maxfev == 5000 && ftol == 10e-8);
+}
+
 int main() {
   samplerTest();
   replayTest();
   hostCallsTest();
   lmTest();
+  passShapeTest();
+  granuleTest();
+  lmResultTest();
   pluginTest();
   if (failures) {
     printf("%d checks failed\n", failures);
