@@ -677,9 +677,11 @@ LSQR_API void lsqr_dedup_destroy(void *set);
  *                it or are still announced by the adaptive bound (the build costs about as much as 700 exhaustive
  *                hypothesis scans) --,
  *                0 = never, 2 = always.  Votes are
- *                bit-identical either way;  "scan_cell": observations per cell (128, 256 or 512; 0 = the
- *                model's default), "scan_cpt": cells per wave tile (1, 2 or 4; 0 = default), "scan_block":
- *                workgroup size (256 / 1024), "scan_hsplit": hypothesis segments per tile (A/B knobs);
+ *                bit-identical either way;  "scan_cell": observations per cell (256 or 512; 0 = the
+ *                model's default), "scan_cpt": cells per wave tile (1; 0 = default, also 1), "scan_block":
+ *                256 threads per workgroup either way -- 256 = hypotheses broadcast by v_readlane, 257 = through LDS
+ *                (0 = the model's choice), "scan_hsplit": hypothesis segments per tile (0..128; 0 = auto; A/B knobs).
+ *                Any other value of these is refused with LSQR_ERR_INVALID;
  * "scan_bound":  1 (default) = the batch entry points (lsqr_batch_fit*, lsqr_step_scan, lsqr_ransac) over an indexed
  *                upload count only hypotheses that can still become the running maximum (an upper bound on every
  *                hypothesis' votes from the cell boxes, a few early candidates counted first); the others
@@ -703,9 +705,9 @@ LSQR_API void lsqr_dedup_destroy(void *set);
  *                1 = always k_scan_pairs, 2 = always k_scan_cells (A/B knob); "scan_pairs_waves": workgroups
  *                per CU of that kernel (0 = what fits); "scan_bound_merge": cells per box of the vote bounds
  *                (0 = default: 4 while >= 4096 boxes remain, 1 = the cells themselves, 2 / 4 / 8);
- * "dense_f32":   dense scan filter at n > 32: 1 (default) = fp32 matrix cores, hypothesis fragments prefetched through
- *                an LDS ring (global_load_lds) and the next tile of rows in registers, 0 = fp64 matrix cores.  Votes are
- *                identical (the band is decided exactly);
+ * "dense_f32":   dense scan filter at n > 32: 2 (default) = fp16 matrix cores (two-way splits), 1 = fp32 matrix cores,
+ *                hypothesis fragments prefetched through an LDS ring (global_load_lds) and the next tile of rows in
+ *                registers, 0 = fp64 matrix cores.  Votes are identical (the band is decided exactly);
  * "dense_fast_solve": 1 (default) = the n x n minimal solves of the dense system use elimination with
  *                partial pivoting and only fall back to the SVD pseudo-inverse near the rank decision,
  *                0 = always the SVD pseudo-inverse (and, for the dense least-squares fit, always the double-double

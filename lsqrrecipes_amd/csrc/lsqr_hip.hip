@@ -343,7 +343,7 @@ struct lsqr_ctx {
   static constexpr size_t kUpChunk = (size_t)8 << 20;
   PinBuf<char> h_up[kUpSlots];
   Event up_ev[kUpSlots];
-  int opt_upload_threads = -1;  // -1: LSQR_UPLOAD_THREADS or 4; 0: one plain hipMemcpy
+  int opt_upload_threads = -1;  // -1: LSQR_UPLOAD_THREADS or 0; 0: one plain hipMemcpy
   double last_upload_ms = 0.0;
   PinBuf<PinLayout> h_pin;  // pinned staging
   PinBuf<char> h_batch;  // pinned results of a lsqr_ransac batch (grown on demand)

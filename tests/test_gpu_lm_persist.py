@@ -93,6 +93,25 @@ def test_a_wait_that_expires_falls_back_to_the_launch_path():
         assert _info(ctx)["status"] == 2 and np.array_equal(got[1], ref[1])
 
 
+def test_the_bound_of_the_waits_changes_nothing_while_no_wait_expires():
+    """lm_persist_timeout_ms (default 2000, 1..60000) only bounds the waits inside the persistent kernel: with a longer
+    bound the fit runs in the kernel (status 2, no fallback) through the same iterates; values outside the range are
+    refused and leave the bound as it was"""
+    data = synth.us_single_fast(3_001, 0.0, seed=43)[0]
+    with Context(0) as ctx:
+        ref = _fit(ctx, L.US_SINGLE, data, 0)
+        for ms in (5000, 2000):
+            got = _fit(ctx, L.US_SINGLE, data, 3, lm_persist_timeout_ms=ms)
+            inf = _info(ctx)
+            assert inf["status"] == 2 and inf["fallbacks"] == 0 and inf["evals"] == ref[3], (ms, inf)
+            assert got[2:4] == ref[2:4] and np.array_equal(got[1], ref[1]) and np.array_equal(got[0], ref[0]), ms
+        for ms in (0, 60001):
+            with pytest.raises(L.LsqrError):
+                ctx.set_option("lm_persist_timeout_ms", ms)
+        got = _fit(ctx, L.US_SINGLE, data, 3)
+        assert _info(ctx)["status"] == 2 and np.array_equal(got[1], ref[1])
+
+
 def test_four_contexts_fit_at_the_same_time():
     """four host threads with a context each (bench.py's C5 leg): the device's compute units are shared by tokens, every
     fit equals its own launch-path run"""

@@ -226,6 +226,39 @@ def test_error_conventions(ctx):
         ctx.set_model(L.SPHERE, 3, 0.5, ls_type=5)
 
 
+def test_set_option_refuses_values_the_code_does_not_take(ctx):
+    """lsqr_set_option: a value outside what include/lsqr_hip.h lists, a removed arrangement (scan_pairs_mfma) and an
+    unknown name are LSQR_ERR_INVALID; the option keeps its value, so the next scan counts as the one before"""
+    data = synth.plane(70_001, 0.5, seed=8)[0]
+    ctx.set_model(L.PLANE, 3, 0.5).upload(data)
+    subs = O.ctr_subsets(3, 0, 200, len(data), 3)
+
+    def votes():
+        ctx.hypotheses_from_subsets(subs)
+        ctx.scan()
+        _, valid, v = ctx.hypotheses(params=False)
+        return valid.copy(), v.copy()
+
+    ctx.set_option("scan_index", 2)
+    try:
+        valid, before = votes()
+        assert ctx.index_info()["built"] and before.max() > 0
+        want = O.scan_many(O.cfg(O.PLANE, 3, 0.5), ctx.hypotheses()[0][:8], valid[:8], data)
+        assert np.array_equal(np.where(valid[:8] > 0, before[:8], 0), want)
+        for name, value in (("scan_cell", 128), ("scan_cpt", 2), ("scan_block", 1024), ("scan_ppl", 3),
+                            ("scan_hsplit", 129), ("scan_kd_levels", 13), ("scan_bound_merge", 3), ("scan_index", 3),
+                            ("lm_persist", 4), ("scan_pairs_mfma", 1), ("no_such_option", 1)):
+            with pytest.raises(L.LsqrError) as e:
+                ctx.set_option(name, value)
+            assert e.value.status == L.ERR_INVALID, (name, e.value.args)
+            v2, after = votes()
+            assert ctx.index_info()["built"]              # "scan_index" still 2
+            assert np.array_equal(v2, valid) and np.array_equal(after, before), name
+        ctx.set_option("scan_pairs_mfma", 0)              # the value that is left is taken
+    finally:
+        ctx.set_option("scan_index", 1)
+
+
 def test_strided_records(ctx):
     """std::vector<T> with sizeof(T) larger than the payload (stride in bytes is honoured)."""
     data = synth.plane(3000, 0.3, seed=8)[0]
