@@ -738,6 +738,12 @@ LSQR_API void lsqr_dedup_destroy(void *set);
  *                on the scalar unit, refills its one prepared hypothesis for the next group as soon as level 1 has
  *                read it and reads the pair loop's addends as stored; 0 = the general forms of both kernels (A/B knob).
  *                Votes are identical;
+ * "scan_pack":   the lean counted scan of the prepared cell models (plane, 3-D and 2-D; "scan_prepared" 1 and
+ *                "scan_lean" 1): 1 (default) = the counting pass stores level 1's 64-bit survivor mask of every (cell, group of 64
+ *                hypotheses) instead of a count, and k_scan_pairs repeats level 1 on packed blocks of 64 consecutive
+ *                survivors of a cell, gathered through a per-wave id list in LDS (csrc/cells.h: k_scan_pairs<..., PACK>),
+ *                instead of on every group of 64 that holds a survivor; 0 = per group (A/B knob).  Accepted values 0 and 1;
+ *                without effect on other models and with either of the two other options 0.  Votes are identical;
  * "dense_mask_ring": LDS tile buffers per wave of the dense final fit's fused mask + normal-equations pass: 4 (default at
  *                n = 64) = one workgroup per CU with three tiles in flight, 2 = two workgroups per CU (A/B knob);
  * "mom_chunk":   records per workgroup of the mask / moment passes in units of 256 (0 = default: 4, wide US / phantom

@@ -42,6 +42,7 @@ namespace lsqr {
 
 constexpr int kCellPtsMin = 128;
 constexpr uint32_t kGroupPad = 4, kCellPad = 16;  // k_scan_pairs: cost padding per group / per cell, in pairs (see there)
+constexpr uint32_t kBlockPad = 6;  // k_scan_pairs<..., PACK>: cost padding per packed block of 64 survivors (see k_tile_costs)
 constexpr uint32_t kQueues = 32;   // work queues of k_scan_cells (one atomic counter each)
 constexpr uint32_t kQueuePitch = 1088;  // uint32 words between counters: separate cache lines / channels  // cell sizes are multiples of one packed fp32 pair per lane
 
@@ -1076,12 +1077,15 @@ __device__ __forceinline__ void cells_filter_squares(float (&bc)[NB]) {
 // DUP (LDSB, NB = 6, NV = 4: the plane's lean scan): the two ADDENDS of the pair loop -- fp[3] and the filter's a -- lie
 // twice in the broadcast area, in the two halves of an aligned pair, so that the packed FMAs take them as they are read
 // (the compiler selects one half of a pair for both lanes in src0 / src1, not the high half in src2: a v_mov_b32 a pair).
-template <class CM, int PP, bool LDSB, bool DUP = false>
+// PACKED (k_scan_pairs<..., PACK>): lane b holds survivor b of a packed block, hypothesis ids[b] of the batch and not
+// b of one group: spg is the batch's first row, and the exact path -- the only reader of the index -- takes it from
+// the block's id list in LDS.
+template <class CM, int PP, bool LDSB, bool DUP = false, bool PACKED = false>
 __device__ __forceinline__ void cells_survivors(const v2f (&xs)[PP][4], const float (&bc)[CM::NB], float *s_bc,
                                                 unsigned long long surv, const int lane,
                                                 const double *__restrict__ sorted, const size_t ns, const size_t cell,
                                                 const double *__restrict__ spg, const ModelConsts &mc,
-                                                uint32_t &accv) {
+                                                uint32_t &accv, const uint16_t *ids = nullptr) {
   typedef typename CM::M M;
   constexpr int D = M::ND, NB = CM::NB, NV = CM::NV, SPD = M::SP, CP = 128 * PP;
   (void)D, (void)NV, (void)CP;
@@ -1159,6 +1163,7 @@ __device__ __forceinline__ void cells_survivors(const v2f (&xs)[PP][4], const fl
     const unsigned long long amb = __ballot(dmin <= band);
     if (amb) {  // some observation sits in the band: exact fp64 predicate for the whole cell
       const double *hp = spg + (size_t)b * SPD;  // wave-uniform -> scalar loads
+      if constexpr (PACKED) hp = spg + (size_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)ids[b]) * SPD;
 #pragma unroll
       for (int p = 0; p < PP; p++) {
         const size_t i0 = cell * CP + p * 128 + lane, i1 = i0 + 64;
@@ -1613,7 +1618,11 @@ __device__ __forceinline__ typename CM::Hyp hyp_from(const float4 (&v)[HypWords<
 // count of level 1's own compare mask; a wave's bytes of a chunk of boxes sit at i * gstride from ONE scalar address,
 // and the four cells of an unrolled iteration are stored under one `lane == 0`.  cnt is byte for byte what the general
 // form writes.
-template <class CM, int PP, bool PREP = false, bool COUNT = false>
+// MASK (COUNT only; option "scan_pack"): instead of the cnt byte the launch stores level 1's 64-bit survivor ballot of
+// every (cell, group) -- `cnt` then points to n_cells x gstride 64-bit words, [cell][group], so that lane g of a wave
+// of k_scan_pairs<..., PACK> reads the 64 masks of a cell with one 8-byte load per lane; lanes past the batch never
+// survive (NaN), so their bits are 0.  Counts and costs are population counts of the masks (k_tile_costs<true>).
+template <class CM, int PP, bool PREP = false, bool COUNT = false, bool MASK = false>
 __global__ __launch_bounds__(256) void k_cells_bounds(const CellBox *__restrict__ boxes, uint32_t ncells,
                                                       size_t ns, const float *__restrict__ rows,
                                                       const float *__restrict__ spf, uint32_t H,
@@ -1685,6 +1694,31 @@ __global__ __launch_bounds__(256) void k_cells_bounds(const CellBox *__restrict_
     }
     __syncthreads();
     if (!active) continue;
+    if constexpr (MASK) {
+      static_assert(COUNT, "the masks are written by the count-only form");
+      auto mask = [&](const CellBox &bx, const double (&ctr)[3]) {
+        float bc[CM::NB];
+        return (unsigned long long)__ballot(CM::level1(hy, bx, ctr, cc, bc));
+      };
+      unsigned long long *p = (unsigned long long *)cnt + ((size_t)cb * gstride + grp);  // wave-uniform
+      uint32_t i = 0;
+      for (; i + 4 <= n; i += 4, p += 4 * gstride) {  // four boxes in flight
+        const CellBox b0 = s_box[i], b1 = s_box[i + 1], b2 = s_box[i + 2], b3 = s_box[i + 3];
+        const double t0[3] = {s_ctr[i][0], s_ctr[i][1], s_ctr[i][2]};
+        const double t1[3] = {s_ctr[i + 1][0], s_ctr[i + 1][1], s_ctr[i + 1][2]};
+        const double t2[3] = {s_ctr[i + 2][0], s_ctr[i + 2][1], s_ctr[i + 2][2]};
+        const double t3[3] = {s_ctr[i + 3][0], s_ctr[i + 3][1], s_ctr[i + 3][2]};
+        const unsigned long long m0 = mask(b0, t0), m1 = mask(b1, t1), m2 = mask(b2, t2), m3 = mask(b3, t3);
+        if (lane == 0) p[0] = m0, p[gstride] = m1, p[2 * gstride] = m2, p[3 * gstride] = m3;
+      }
+      for (; i < n; i++, p += gstride) {
+        const CellBox b0 = s_box[i];
+        const double t0[3] = {s_ctr[i][0], s_ctr[i][1], s_ctr[i][2]};
+        const unsigned long long m0 = mask(b0, t0);
+        if (lane == 0) p[0] = m0;
+      }
+      continue;
+    }
     if constexpr (COUNT) {
       // padded survivor count of the wave's group in one box: every lane of an active wave takes part in the compare
       auto padded = [&](const CellBox &bx, const double (&ctr)[3]) {
@@ -1773,7 +1807,36 @@ constexpr uint32_t kChunkCells = 128;
 // group's / cell's pairs, so that a stretch of far cells with one or two survivors per group is not handed to one
 // wave as if it were free (measured before the padding: one wave walking 574 groups for 662 pairs, 1.5 ms against a
 // mean of 0.44 ms).
+//
+// PACK (option "scan_pack"): `cnt` holds the survivor MASKS of the counting pass (k_cells_bounds<..., MASK>) and the
+// enumeration is cell-major, inside a cell the dense order of its S survivors (group-major, lane-minor).  A wave
+// evaluates level 1 once per packed block of 64 consecutive survivors, so the cell's units are
+//   kCellPad | kBlockPad, survivors 0..63 | kBlockPad, survivors 64..127 | ...       (pack_cell_cost, pack_first)
+// kBlockPad is derived like kGroupPad: a packed block pays level 1 with the filter's squares, the id read and the
+// gather's addresses (~43 vector instructions), the id scatter of the ~6 groups it overlaps (8 each) -- three pairs'
+// worth of instructions -- and TWO dependent loads (ids from LDS, then Hyp from L2) where a group pays one: 6.
+// A wave's blocks start at its own first survivor, so it may evaluate one block more than its share was charged.
+__host__ __device__ constexpr uint32_t pack_cell_cost(uint32_t S) {
+  return S ? kCellPad + (S + 63) / 64 * kBlockPad + S : 0u;
+}
+// the first survivor of a cell (dense order) whose cost unit is >= u; survivor j sits at unit
+// kCellPad + (j / 64 + 1) * kBlockPad + j
+__host__ __device__ constexpr uint32_t pack_first(uint32_t u) {
+  const uint32_t v = u > kCellPad ? u - kCellPad : 0u, B = 64 + kBlockPad, q = v / B, r = v - q * B;
+  return 64 * q + (r > kBlockPad ? r - kBlockPad : 0u);
+}
+// the survivors of a cell of cost c > 0: with nb blocks, c - kCellPad lies in (B (nb - 1), B nb], B = 64 + kBlockPad
+__host__ __device__ constexpr uint32_t pack_cell_survivors(uint32_t c) {
+  const uint32_t x = c - kCellPad, B = 64 + kBlockPad;
+  return x - (x + B - 1) / B * kBlockPad;
+}
+static_assert(pack_cell_survivors(pack_cell_cost(1)) == 1 && pack_cell_survivors(pack_cell_cost(64)) == 64 &&
+              pack_cell_survivors(pack_cell_cost(65)) == 65 && pack_cell_survivors(pack_cell_cost(4096)) == 4096);
+static_assert(pack_first(0) == 0 && pack_first(kCellPad + kBlockPad) == 0 && pack_first(kCellPad + kBlockPad + 1) == 1 &&
+              pack_first(kCellPad + kBlockPad + 64) == 64 && pack_first(kCellPad + 2 * kBlockPad + 64) == 64 &&
+              pack_first(kCellPad + 2 * kBlockPad + 65) == 65);
 
+template <bool PACK = false>
 __global__ __launch_bounds__(128) void k_tile_costs(const uint8_t *__restrict__ cnt, uint32_t gstride, uint32_t H,
                                                     const uint32_t *__restrict__ h_dev, uint32_t ncells,
                                                     uint32_t *__restrict__ cost, uint32_t *__restrict__ csum,
@@ -1786,7 +1849,19 @@ __global__ __launch_bounds__(128) void k_tile_costs(const uint8_t *__restrict__ 
   const uint32_t G = (H + 63) / 64;
   const uint32_t c = blockIdx.x * kChunkCells + threadIdx.x;
   uint32_t t = 0;
-  if (c < ncells) {
+  if (PACK && c < ncells) {  // survivors of the cell: population of its masks, 512 contiguous bytes at 64 groups
+    const unsigned long long *p = (const unsigned long long *)cnt + (size_t)c * gstride;
+    uint32_t g = 0;
+    if ((gstride & 1u) == 0)
+      for (; g + 2 <= G; g += 2) {
+        const uint4 v = *(const uint4 *)(p + g);
+        t += (uint32_t)(__builtin_popcount(v.x) + __builtin_popcount(v.y) + __builtin_popcount(v.z) +
+                        __builtin_popcount(v.w));
+      }
+    for (; g < G; g++) t += (uint32_t)__builtin_popcountll(p[g]);
+    t = pack_cell_cost(t);
+    cost[c] = t;
+  } else if (c < ncells) {
     const uint8_t *p = cnt + (size_t)c * gstride;
     // (only the groups below G have been written by the counting pass)
     uint32_t g = 0;
@@ -1817,6 +1892,19 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v, int lane) {
   return v;
 }
 
+// the same on the data-parallel path of the vector unit: four shifts inside the rows of 16 lanes, then lane 15 of
+// row 0 / 2 into row 1 / 3 and lane 31 into rows 2 and 3; lanes without a source add 0.  Needs neither the lane
+// index nor LDS (the per-cell prefix of k_scan_pairs<..., PACK>, whose loop has no registers to spare)
+__device__ __forceinline__ uint32_t wave_incl_scan_dpp(uint32_t v) {
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false);  // row_shr:1
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false);  // row_shr:2
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false);  // row_shr:4
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false);  // row_shr:8
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);  // row_bcast:15 -> rows 1, 3
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);  // row_bcast:31 -> rows 2, 3
+  return v;
+}
+
 // LEAN (option "scan_lean"; prepared hypotheses only): the same enumeration with
 //   - the share arithmetic on the scalar unit: skip, budget and cell are wave-uniform and are made so for the compiler
 //     (readfirstlane), and a wave's part of a group is worked out in cost units (no saturating subtraction, which
@@ -1825,7 +1913,20 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v, int lane) {
 //     copied (the general form moves it into level 1's registers and back, twelve 64-bit moves a group);
 //   - the pair loop's two addends twice in the broadcast area (cells_survivors<..., DUP>).
 // Which bits of a survivor mask a wave keeps, and with them every vote, are those of the general form.
-template <class CM, int PP, int BS, bool LDSB, bool PREP = false, bool LEAN = false>
+//
+// PACK (option "scan_pack"; on top of LEAN): level 1 with lane = hypothesis is run on PACKED blocks of 64 consecutive
+// survivors of the cell's dense order (group-major, lane-minor) instead of on every group of 64 with a survivor --
+// at 4096 hypotheses in key order a group holds 11 survivors on average, the other 53 lanes compute, load and store
+// for nothing.  `cnt` holds the counting pass' survivor masks ([cell][group], 64-bit).  Per cell opened: lane g loads
+// the mask of group g, its population count and the exclusive prefix over the lanes give every survivor its rank; the
+// wave's share [lo, hi) of the cell's cost units (pack_cell_cost) is the rank range [jlo, jhi) (pack_first).  Per
+// block [base, base + 64): the groups that overlap it are walked on the scalar unit, their set lanes whose rank
+// (prefix + mbcnt of the mask) falls inside write their hypothesis index into the wave's 64-slot id list in LDS;
+// lane i then reads slot i and gathers hyps[id].  Level 1, the filter's squares and cells_survivors run as in the
+// lean form with surv = the low `n` bits (level 1 repeats the counting pass bit for bit: every lane of the block
+// survives), votes go to s_cnt[id].  The next block's ids and Hyp are fetched as soon as level 1 has read this one's.
+// Which wave counts which pair differs from the group forms; votes are integer sums and do not.
+template <class CM, int PP, int BS, bool LDSB, bool PREP = false, bool LEAN = false, bool PACK = false>
 __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(PP >= 8 ? 4 : CM::MIN_WAVES, 8))) void k_scan_pairs(
     const double *__restrict__ sorted, size_t ns, const CellBox *__restrict__ boxes, uint32_t ncells,
     const double *__restrict__ sp, const float *__restrict__ rows, const float *__restrict__ spf, uint32_t H,
@@ -1853,6 +1954,16 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(PP >= 8 ? 4 
   float *s_bc = (float *)(s_cnt + ((H + 3) & ~3u)) + (size_t)(threadIdx.x >> 6) * 512;
   const uint32_t W = gridDim.x * (BS / 64);
   const uint32_t wid = blockIdx.x * (BS / 64) + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  // PACK: the wave's two id lists, 64 x u16 each, behind the broadcast areas (the next block's is filled while this
+  // block's is still read: votes, exact path); slots a block does not fill keep an earlier id (or 0): always an
+  // entry of the prepared block
+  [[maybe_unused]] uint16_t *s_id = nullptr;
+  if constexpr (PACK) {
+    static_assert(LEAN && PREP, "packed blocks gather prepared hypotheses and run the lean pair loop");
+    s_id = (uint16_t *)((float *)(s_cnt + ((H + 3) & ~3u)) + (LDSB ? (size_t)(BS / 64) * 512 : 0)) +
+           (size_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) * 128;
+    s_id[lane] = 0, s_id[64 + lane] = 0;
+  }
 
   // ---- my share of the pairs: [t0, t0 + budget) of C
   unsigned long long C = 0;
@@ -1929,6 +2040,7 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(PP >= 8 ? 4 
     }
   };
   while (budget && cell < ncells) {
+    [[maybe_unused]] uint32_t ccost = 0;  // PACK: the cell's cost
     // jump over cells nothing survives in
     {
       const uint32_t v = cell + lane < ncells ? cost[cell + lane] : 0u;
@@ -1938,23 +2050,48 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(PP >= 8 ? 4 
         continue;
       }
       cell += (uint32_t)__builtin_ctzll(nz);
+      if constexpr (PACK) ccost = (uint32_t)__builtin_amdgcn_readlane((int)v, __builtin_ctzll(nz));
     }
-    pad(kCellPad);
-    // padded survivor counts of the cell's groups: lane g <-> group g (the host cuts batches of more than 4096
-    // hypotheses into launches of 4096: a third loop level here costs the 4096 case 28 spilled registers)
-    const uint32_t gc = (uint32_t)lane < G ? (uint32_t)cnt[(size_t)cell * gstride + lane] : 0u;
-    unsigned long long gm = __ballot(gc != 0);
-    // groups that lie before my range altogether
-    while (gm && budget) {
-      const int g = __builtin_ctzll(gm);
-      const uint32_t cg = (uint32_t)__builtin_amdgcn_readlane((int)gc, g);
-      if (skip < cg) break;
-      skip -= cg;
-      gm &= gm - 1;
-    }
-    if (!gm || !budget) {
-      cell++;
-      continue;
+    // PACK: [jlo, jhi) is my part of the dense order of the cell's S survivors, from the cell's cost alone
+    [[maybe_unused]] uint32_t jlo = 0, jhi = 0;
+    uint32_t gc = 0;
+    unsigned long long gm = 0;
+    if constexpr (PACK) {
+      if (skip >= ccost) {  // (only if the share began past the table's end)
+        skip -= ccost;
+        cell++;
+        continue;
+      }
+      const uint32_t S = pack_cell_survivors(ccost);
+      const uint32_t lo = skip, hi = ccost < skip + budget ? ccost : skip + budget;
+      budget -= hi - lo;
+      skip = 0;
+      // (pack_first subtracts with saturation, which the vector unit alone has: back to scalar registers, once a cell)
+      jlo = (uint32_t)__builtin_amdgcn_readfirstlane((int)pack_first(lo));
+      jhi = (uint32_t)__builtin_amdgcn_readfirstlane((int)pack_first(hi));
+      jhi = jhi < S ? jhi : S;
+      if (jhi <= jlo) {  // my part is padding
+        cell++;
+        continue;
+      }
+    } else {
+      pad(kCellPad);
+      // padded survivor counts of the cell's groups: lane g <-> group g (the host cuts batches of more than 4096
+      // hypotheses into launches of 4096: a third loop level here costs the 4096 case 28 spilled registers)
+      gc = (uint32_t)lane < G ? (uint32_t)cnt[(size_t)cell * gstride + lane] : 0u;
+      gm = __ballot(gc != 0);
+      // groups that lie before my range altogether
+      while (gm && budget) {
+        const int g = __builtin_ctzll(gm);
+        const uint32_t cg = (uint32_t)__builtin_amdgcn_readlane((int)gc, g);
+        if (skip < cg) break;
+        skip -= cg;
+        gm &= gm - 1;
+      }
+      if (!gm || !budget) {
+        cell++;
+        continue;
+      }
     }
     const CellBox bx = boxes[cell];  // wave-uniform address -> scalar load
     double ctr[3];
@@ -1980,6 +2117,68 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(PP >= 8 ? 4 
     }
     v2f xs[PP][4];
     cells_load<CM, PP>(sorted, ns, (size_t)cell, lane, ctr, xs);
+    if constexpr (PACK) {
+      // survivor mask of group `lane` (fetched with the cell's observations in flight) and the exclusive prefix of the
+      // population counts = rank of the group's first survivor in the dense order (~0 for a group without
+      // survivors: it overlaps no block).  The cell's row of masks has a scalar base and a 32-bit lane offset
+      // (written plainly, cnt + 8 * lane is hoisted out of the cell loop as a 64-bit address per lane: two registers
+      // the loop does not have)
+      const unsigned long long ra = (unsigned long long)cnt + ((unsigned long long)cell * gstride << 3);
+      const unsigned long long *row = (const unsigned long long *)(
+          (unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(ra >> 32)) << 32 |
+          (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)ra));
+      const unsigned long long pm = (uint32_t)lane < G ? row[(uint32_t)lane] : 0ull;
+      const uint32_t pc = (uint32_t)__builtin_popcountll(pm);
+      const uint32_t incl = wave_incl_scan_dpp(pc);  // (every lane takes part)
+      const uint32_t excl = pc ? incl - pc : ~0u;
+      // ids of the block [base, base + 64) -> list, lane's own id back.  The groups that overlap it: from the one that
+      // holds rank `base` -- the last non-empty group that starts at or below it -- to the last that starts inside
+      auto block_ids = [&](const uint32_t base, uint16_t *list) {
+        const unsigned long long upto = __ballot(excl <= base);  // (never 0: base < S)
+        unsigned long long ov = __ballot(excl < base + 64) & (~0ull << (63 - __builtin_clzll(upto)));
+        while (ov) {
+          const int g = __builtin_ctzll(ov);
+          ov &= ov - 1;
+          const uint32_t mlo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)pm, g),
+                         mhi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(pm >> 32), g);
+          // rank - base of the group's set lanes (wraps below the block: not < 64)
+          const uint32_t r = (uint32_t)__builtin_amdgcn_readlane((int)excl, g) - base;
+          const uint32_t slot = __builtin_amdgcn_mbcnt_hi(mhi, __builtin_amdgcn_mbcnt_lo(mlo, r));
+          if (__builtin_amdgcn_inverse_ballot_w64((unsigned long long)mhi << 32 | mlo) && slot < 64)
+            list[slot] = (uint16_t)((uint32_t)g * 64 + (uint32_t)lane);
+        }
+        __builtin_amdgcn_wave_barrier();  // (one wave: LDS keeps its order, the compiler must too)
+        return (uint32_t)list[lane];
+      };
+      auto gather = [&](const uint32_t id) {
+        float4 r[NR4];
+#pragma unroll
+        for (int k = 0; k < NR4; k++) r[k] = hyps[(size_t)id * NR4 + k];
+        return hyp_from<CM>(r);
+      };
+      uint32_t base = jlo, par = 0;  // the block's list: s_id + par
+      typename CM::Hyp hy = gather(block_ids(base, s_id));
+      for (;;) {
+        // (64 - min(., 64) is a saturating subtraction, the vector unit's: the shift count back to a scalar register)
+        const uint32_t n = jhi - base < 64 ? jhi - base : 64;
+        const unsigned long long surv = ~0ull >> (uint32_t)__builtin_amdgcn_readfirstlane((int)(64 - n));
+        float bc[NB];
+        (void)CM::level1(hy, bx, ctr, cc, bc);  // true in the n lanes of the block: the counting pass said so
+        base += 64;
+        const bool more = base < jhi;
+        // the next block's ids and Hyp meanwhile (level 1 was the only reader of this one's)
+        if (more) hy = gather(block_ids(base, s_id + (par ^ 64)));
+        cells_filter_squares(bc);
+        uint32_t accv = 0;
+        cells_survivors<CM, PP, LDSB, LDSB, true>(xs, bc, s_bc, surv, lane, sorted, ns, (size_t)cell, sp, mc, accv,
+                                                  s_id + par);
+        if (accv) atomicAdd(&s_cnt[s_id[par + lane]], accv);
+        if (!more) break;
+        par ^= 64;
+      }
+      cell++;
+      continue;
+    }
     if constexpr (LEAN) {
       // level 1 is the only reader of a group's Hyp and comes first, so the next group's Hyp is fetched into the
       // registers it has just read -- as far ahead of its use, but for level 1 itself, as a second buffer would have it

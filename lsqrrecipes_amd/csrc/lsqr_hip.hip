@@ -232,6 +232,8 @@ struct lsqr_ctx {
   DevBuf<uint32_t> d_vpart;    // per-workgroup partial votes of k_scan_pairs
   DevBuf<float4> d_hyps;       // k_prepare_hyps: CM::Hyp of every hypothesis of the batch k_scan_pairs is counting
   int opt_lean = 1;               // 1: count-only counting pass, k_scan_pairs<..., LEAN> for prepared models; 0: the general forms (A/B)
+  DevBuf<unsigned long long> d_pairmask;  // k_scan_pairs<..., PACK>: level 1's survivor mask per (cell, group of 64 hypotheses)
+  int opt_pack = 1;               // 1: level 1 of the lean k_scan_pairs on packed blocks of 64 survivors; 0: per group (A/B)
   int opt_prepared = 1;           // 1: cell models with PREPARED read Hyp from d_hyps; 0: load() per (cell, group) (A/B)
   // bounded scan (cells.h: k_pick_*): the selected hypotheses as a compact batch
   DevBuf<uint32_t> d_sel;        // [kPilots pilots | H_cap rest]
@@ -1095,6 +1097,10 @@ int run_scan_pairs(lsqr_ctx *c, const ScanBatch &b0) {
     }
   }
   const float4 *hyps = prep ? c->d_hyps : nullptr;
+  // packed blocks (cells.h: k_scan_pairs<..., PACK>): the counting pass leaves survivor masks instead of counts
+  const bool pack = prep && c->opt_lean && c->opt_pack;
+  if (pack && (st = ensure(c, c->d_pairmask, (size_t)c->n_cells * gstride)) != LSQR_OK) return st;
+  uint8_t *d_cnt = pack ? (uint8_t *)c->d_pairmask.get() : c->d_paircnt.get();
   {  // counting pass: waves past the device-side H leave at once, so the grid is cut finely in x
     const unsigned gy = (Hc + 255) / 256;
     const uint32_t per = std::max<uint32_t>(8, (c->n_cells + 1023) / 1024);
@@ -1102,9 +1108,11 @@ int run_scan_pairs(lsqr_ctx *c, const ScanBatch &b0) {
     auto count = [&](auto kern) {
       hipLaunchKernelGGL(kern, dim3(gx, gy), dim3(256), 0, c->stream, c->d_boxes, c->n_cells, c->n_sorted, rows, b.spf,
                          Hc, cc, per, (uint32_t *)nullptr, (unsigned long long *)nullptr, (uint32_t *)nullptr,
-                         c->d_paircnt, gstride, b.h_dev, b.h_off, (uint32_t)(128 * PP), hyps);
+                         d_cnt, gstride, b.h_dev, b.h_off, (uint32_t)(128 * PP), hyps);
     };
-    if (c->opt_lean) {  // cnt and nothing else
+    if (pack) {  // masks and nothing else
+      if constexpr (kPrep) count(k_cells_bounds<CM, PP, true, true, true>);
+    } else if (c->opt_lean) {  // cnt and nothing else
       if (prep)
         count(k_cells_bounds<CM, PP, kPrep, true>);
       else
@@ -1115,14 +1123,21 @@ int run_scan_pairs(lsqr_ctx *c, const ScanBatch &b0) {
       count(k_cells_bounds<CM, PP>);
     HIPCHK(c, hipGetLastError());
   }
-  hipLaunchKernelGGL(k_tile_costs, dim3(nchunks), dim3(kChunkCells), 0, c->stream, c->d_paircnt, gstride, Hc, b.h_dev,
-                     c->n_cells, d_cost, d_csum, b.votes, b.h_off);  // (zeroes the batch's votes)
+  auto costs = [&](auto kern) {
+    hipLaunchKernelGGL(kern, dim3(nchunks), dim3(kChunkCells), 0, c->stream, (const uint8_t *)d_cnt, gstride, Hc,
+                       b.h_dev, c->n_cells, d_cost, d_csum, b.votes, b.h_off);  // (zeroes the batch's votes)
+  };
+  if (pack)
+    costs(k_tile_costs<true>);
+  else
+    costs(k_tile_costs<false>);
   HIPCHK(c, hipGetLastError());
   bool ldsb_default = CM::LDS_BROADCAST;
   if constexpr (requires { CM::LDS_BROADCAST_PAIRS; }) ldsb_default = CM::LDS_BROADCAST_PAIRS;
   const bool ldsb = c->opt_block == 257 || (c->opt_block == 0 && ldsb_default);
   constexpr int BS = 256, wpb = BS / 64;
-  const size_t lds = (size_t)((Hc + 3) & ~3u) * sizeof(uint32_t) + (ldsb ? (size_t)wpb * 2048 : 0);
+  const size_t lds = (size_t)((Hc + 3) & ~3u) * sizeof(uint32_t) + (ldsb ? (size_t)wpb * 2048 : 0) +
+                     (pack ? (size_t)wpb * 256 : 0);  // votes | broadcast areas | id lists of the packed blocks
   auto launch = [&](auto kern) -> int {
     int per_cu = (int)std::min<size_t>(32 / wpb, (160 * 1024) / std::max<size_t>(lds, 1)), occ = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, BS, lds) == hipSuccess && occ >= 1)
@@ -1136,7 +1151,7 @@ int run_scan_pairs(lsqr_ctx *c, const ScanBatch &b0) {
     if (st2 != LSQR_OK) return st2;
     ProfScope ps(c, KID_SCAN);
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(BS), lds, c->stream, c->d_sorted, c->n_sorted, c->d_boxes, c->n_cells,
-                       b.sp, rows, b.spf, Hc, c->mc, cc, c->d_vpart, Hc, b.h_dev, (const uint8_t *)c->d_paircnt, gstride,
+                       b.sp, rows, b.spf, Hc, c->mc, cc, c->d_vpart, Hc, b.h_dev, (const uint8_t *)d_cnt, gstride,
                        (const uint32_t *)d_cost, (const uint32_t *)d_csum, nchunks, b.h_off, hyps);
     HIPCHK(c, hipGetLastError());
     hipLaunchKernelGGL(k_votes_reduce, dim3((Hc + 63) / 64, 48), dim3(256), 0, c->stream,
@@ -1145,6 +1160,9 @@ int run_scan_pairs(lsqr_ctx *c, const ScanBatch &b0) {
     return LSQR_OK;
   };
   if constexpr (kPrep) {  // the lean group loop walks the prepared block
+    if (pack)
+      return ldsb ? launch(k_scan_pairs<CM, PP, BS, true, true, true, true>)
+                  : launch(k_scan_pairs<CM, PP, BS, false, true, true, true>);
     if (prep && c->opt_lean)
       return ldsb ? launch(k_scan_pairs<CM, PP, BS, true, true, true>) : launch(k_scan_pairs<CM, PP, BS, false, true, true>);
   }
@@ -5260,6 +5278,11 @@ static int set_option_one(lsqr_ctx *c, const char *name, int value) {
   }
   if (!strcmp(name, "scan_lean")) {  // 1 (default): count-only counting pass, lean k_scan_pairs (prepared models); 0: the general forms
     c->opt_lean = value != 0;
+    return LSQR_OK;
+  }
+  if (!strcmp(name, "scan_pack")) {  // 1 (default): the lean k_scan_pairs runs level 1 on packed blocks of 64 survivors; 0: per group
+    if (value != 0 && value != 1) return fail(c, LSQR_ERR_INVALID, "scan_pack must be 0 or 1");
+    c->opt_pack = value;
     return LSQR_OK;
   }
   if (!strcmp(name, "scan_axis")) {  // 1 (default): axis-sorted cells + vote bounds by rank (plane, 3-D); 0: off

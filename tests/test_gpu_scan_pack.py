@@ -1,0 +1,173 @@
+"""The packed form of the plane's lean counted scan (csrc/cells.h; option "scan_pack"): the counting pass stores level
+1's 64-bit survivor mask per (cell, group of 64 hypotheses) (k_cells_bounds<..., MASK>), the cost table is made of the
+masks' population counts (k_tile_costs<true>), and k_scan_pairs<..., PACK> repeats level 1 on packed blocks of 64
+consecutive survivors of a cell's dense order, gathered through a per-wave id list in LDS.  Which wave counts which
+pair changes; not a single vote may: with the option 1 and 0 the votes of every hypothesis are identical to each other
+and to the exhaustive fp64 kernel (scan_index 0), a 64-hypothesis sample equals the oracle's count, winner, fit and
+consensus set are equal, and the counted work (lsqr_scan_workload) does not depend on the option.
+
+Shapes are those of test_gpu_scan_lean: 200 k points plus eight far corner points = 391 cells = 3 x 128 + 7, delta 0.5,
+3-D and 2-D, H = 1024, 1100 (last group partial: lanes past H never enter a block) and 4200 (second launch; h_off > 0
+in the bounded selection), with the injected NaN / far / degenerate rows.  One batch holds a near-model hypothesis 94
+times -- a whole group and the first 30 rows of the next: in the inlier cells the first group's mask is all ones and
+the second group straddles two blocks.  Everything runs with scan_pairs_waves 1 as well, so that the waves' shares
+begin and end inside other blocks."""
+import numpy as np
+import pytest
+
+from lsqrrecipes_amd import _lib as L, synth
+from lsqrrecipes_amd.context import Context
+from oracle import pyoracle as O
+
+pytestmark = pytest.mark.gpu
+N = 200_000
+SEED = 0xBEEF
+DEFAULTS = {"scan_pack": 1, "scan_index": 1, "scan_pairs_waves": 0, "scan_hyp_order": 1, "scan_bound": 1}  # the library's
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    c = Context(0)
+    yield c
+    c.close()
+
+
+@pytest.fixture(autouse=True)
+def _restore(ctx):
+    yield
+    for name, value in DEFAULTS.items():
+        ctx.set_option(name, value)
+
+
+def _with_far(data, dim):
+    g = np.random.default_rng(dim)
+    far = np.where(g.random((8, dim)) < 0.5, -1.0, 1.0) * 4000.0 + g.normal(0, 0.3, (8, dim))
+    return np.ascontiguousarray(np.vstack([data, far]))
+
+
+@pytest.fixture(scope="module")
+def clouds():
+    """dim -> the points, with eight far corner points appended (they set absmax) for the injected rows"""
+    return {dim: _with_far(synth.plane(N, 0.5, dim=dim)[0], dim) for dim in (3, 2)}
+
+
+def _subsets(n, k, H):
+    """the sampler's subsets with the injected rows of test_gpu_scan_lean: degenerate subsets (NaN parameters, not
+    valid), subsets of the far corner points and mixed near / far subsets -- in the first, a middle and the last group"""
+    s = O.ctr_subsets(SEED, 0, H, n, k).astype(np.uint32)
+    far = np.arange(n - 8, n, dtype=np.uint32)
+    for base in (0, (H // 2) & ~63, H - 7):
+        s[base + 1] = s[base + 1][0]                  # one point, dim times
+        s[base + 2] = far[:k]
+        s[base + 3] = far[8 - k:]
+        s[base + 4, 0] = far[3]                       # one far point, the rest from the cloud
+        s[base + 5, :2] = s[base + 5, 0]              # two equal points
+    return s
+
+
+def _scan(ctx, subsets, index, pack, waves=0, order=1, workload=False):
+    ctx.set_option("scan_index", index)
+    ctx.set_option("scan_pack", pack)
+    ctx.set_option("scan_pairs_waves", waves)
+    ctx.set_option("scan_hyp_order", order)
+    ctx.hypotheses_from_subsets(subsets)
+    ctx.scan()
+    par, valid, votes = ctx.hypotheses()
+    valid, votes = valid.copy(), votes.copy()
+    built = ctx.index_info()["built"]
+    wl = ctx.scan_workload() if workload else None
+    return par, valid, votes, built, wl
+
+
+@pytest.mark.parametrize("H", [1024, 1100, 4200])
+@pytest.mark.parametrize("dim", [3, 2])
+def test_full_count_votes_do_not_depend_on_the_packed_form(ctx, clouds, dim, H):
+    data = clouds[dim]
+    ctx.set_model(L.PLANE, dim, 0.5).upload(data)
+    subsets = _subsets(len(data), ctx.K, H)
+    par, valid, exact, built, _ = _scan(ctx, subsets, 0, 1)
+    assert not built
+    _, v1, on, built, w1 = _scan(ctx, subsets, 2, 1, workload=True)
+    assert built
+    if dim == 3:
+        assert ctx.index_info()["cells"] == 391            # 3 x 128 + 7: both loops of the counting pass run
+    _, v0, off, built, w0 = _scan(ctx, subsets, 2, 0, workload=True)
+    assert built
+    assert np.array_equal(v1, valid) and np.array_equal(v0, valid)
+    assert not valid[1] and not valid[H - 6] and np.isnan(par[1]).all()       # the injected NaN rows are there
+    assert valid[2] and valid[H - 5] and np.abs(par[2][dim:]).max() > 3900.0  # ... and the far ones
+    assert np.array_equal(on, off), np.flatnonzero(on != off)[:8]
+    assert np.array_equal(on, exact), np.flatnonzero(on != exact)[:8]
+    assert exact.max() > 0.2 * N                           # near-model hypotheses: their cells take the exact path
+    assert w1["pairs_counted"] == w0["pairs_counted"] and w1["pairs"] == w0["pairs"] and w1["pairs"] > 0
+    # other splits: one workgroup per CU, and the sampling order of the hypotheses (masks of unrelated planes)
+    for waves, order in ((1, 1), (1, 0), (0, 0)):
+        for pack in (1, 0):
+            _, v, votes, built, _ = _scan(ctx, subsets, 2, pack, waves=waves, order=order)
+            assert built and np.array_equal(v, valid)
+            assert np.array_equal(votes, exact), (waves, order, pack, np.flatnonzero(votes != exact)[:8])
+    # the oracle on a sample: the injected rows of the first group, the winner, and every (H // 55)-th hypothesis
+    pick = np.unique(np.concatenate([np.arange(8), [int(np.argmax(exact))], np.arange(8, H, H // 55)]))[:64]
+    want = O.scan_many(O.cfg(O.PLANE, dim, 0.5), par[pick], valid[pick], data)
+    assert np.array_equal(np.where(valid[pick] > 0, on[pick], 0), want)
+
+
+@pytest.mark.parametrize("dim", [3, 2])
+def test_full_masks_a_whole_group_and_a_group_that_straddles_two_blocks(ctx, clouds, dim):
+    """a near-model hypothesis in all 64 rows of group 1 and in the first 30 rows of group 2: in every cell it
+    survives in, group 1's mask is all ones and group 2's survivors continue into the next block.  In sampling order
+    (scan_hyp_order 0) the copies sit in exactly these rows; in key order they are 94 consecutive rows elsewhere."""
+    H = 1100
+    data = clouds[dim]
+    ctx.set_model(L.PLANE, dim, 0.5).upload(data)
+    subsets = _subsets(len(data), ctx.K, H)
+    _, _, votes, _, _ = _scan(ctx, subsets, 0, 1)
+    w = int(np.argmax(votes))
+    subsets[64:158] = subsets[w]
+    _, valid, exact, built, _ = _scan(ctx, subsets, 0, 1)
+    assert not built
+    assert valid[64:158].all() and (exact[64:158] == exact[64]).all() and exact[64] == votes[w] > 0.2 * N
+    for waves in (0, 1):
+        for order in (0, 1):
+            for pack in (1, 0):
+                _, v, got, built, _ = _scan(ctx, subsets, 2, pack, waves=waves, order=order)
+                assert built and np.array_equal(v, valid)
+                assert np.array_equal(got, exact), (waves, order, pack, np.flatnonzero(got != exact)[:8])
+
+
+def _batches(ctx, H, bound, pack, firsts):
+    ctx.set_option("scan_bound", bound)
+    ctx.set_option("scan_pack", pack)
+    out = []
+    for first in firsts:
+        r = ctx.batch_fit(SEED, first, H, want_consensus=True)
+        _, valid, votes = ctx.hypotheses(params=False)
+        out.append((int(r["info"].best_index), int(r["info"].best_votes), r["params"].copy(), r["consensus"].copy(),
+                    valid.copy(), votes.copy()))
+    return out
+
+
+@pytest.mark.parametrize("H", [1024, 1100, 4200])
+@pytest.mark.parametrize("dim", [3, 2])
+def test_batches_counted_and_bounded_with_and_without_the_packed_form(ctx, clouds, dim, H):
+    """lsqr_batch_fit, two consecutive batches on one context, every hypothesis counted (scan_bound 0) and the bounded
+    scan (its compacted selection is counted through the same kernels, from h_off > 0 at H = 4200): winner, votes,
+    consensus set and fit do not depend on scan_pack; the counted votes equal the exhaustive kernel's"""
+    data = clouds[dim]
+    ctx.set_model(L.PLANE, dim, 0.5).upload(data)
+    firsts = (0, H)
+    ctx.set_option("scan_index", 0)
+    exact = _batches(ctx, H, 0, 1, firsts)
+    assert not ctx.index_info()["built"]
+    ctx.set_option("scan_index", 2)
+    res = {(b, p): _batches(ctx, H, b, p, firsts) for b in (0, 1) for p in (1, 0)}
+    assert ctx.index_info()["built"]
+    for k in range(len(firsts)):
+        for b in (0, 1):
+            on, off = res[(b, 1)][k], res[(b, 0)][k]
+            assert on[:2] == off[:2] and all(np.array_equal(x, y) for x, y in zip(on[2:], off[2:])), (b, k)
+            # winner, votes of the winner, fit and consensus set are the exhaustive kernel's
+            assert on[:2] == exact[k][:2] and np.array_equal(on[2], exact[k][2]) and np.array_equal(on[3], exact[k][3])
+        assert np.array_equal(res[(0, 1)][k][5], exact[k][5])       # every vote of the full count
+        bounded, full = res[(1, 1)][k][5], exact[k][5]              # bounded: exact or provably not the winner
+        assert np.all((bounded == full) | (bounded < full.max()))

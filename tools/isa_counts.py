@@ -19,12 +19,14 @@ from bench import kernel_source_hash  # noqa: E402
 
 CSRC = os.path.join(ROOT, "lsqrrecipes_amd", "csrc")
 # (key, substrings the mangled name must contain)
-# (k_scan_pairs<CM, PP, BS, LDSB, PREP, LEAN>, k_cells_bounds<CM, PP, PREP, COUNT>: the bools are the trailing LbNE)
-KERNELS = [("k_scan_pairs_plane", ["k_scan_pairs", "PlaneCell", "Li3E", "Li4ELi256ELb1ELb1ELb1E"]),  # LDS broadcast, prepared Hyp, lean: what runs
-           ("k_scan_pairs_plane_general", ["k_scan_pairs", "PlaneCell", "Li3E", "Li4ELi256ELb1ELb1ELb0E"]),  # scan_lean=0
-           ("k_scan_pairs_plane_unprepared", ["k_scan_pairs", "PlaneCell", "Li3E", "Li4ELi256ELb1ELb0ELb0E"]),  # scan_prepared=0 scan_lean=0
-           ("k_cells_bounds_plane", ["k_cells_bounds", "PlaneCell", "Li3E", "Li4ELb1ELb1E"]),  # count-only counting pass: what runs
-           ("k_cells_bounds_plane_general", ["k_cells_bounds", "PlaneCell", "Li3E", "Li4ELb1ELb0E"]),  # scan_lean=0
+# (k_scan_pairs<CM, PP, BS, LDSB, PREP, LEAN, PACK>, k_cells_bounds<CM, PP, PREP, COUNT, MASK>: the bools are the trailing LbNE)
+KERNELS = [("k_scan_pairs_plane", ["k_scan_pairs", "PlaneCell", "Li3E", "Li4ELi256ELb1ELb1ELb1ELb1EEE"]),  # LDS broadcast, prepared Hyp, lean, packed blocks: what runs
+           ("k_scan_pairs_plane_groups", ["k_scan_pairs", "PlaneCell", "Li3E", "Li4ELi256ELb1ELb1ELb1ELb0EEE"]),  # scan_pack=0
+           ("k_scan_pairs_plane_general", ["k_scan_pairs", "PlaneCell", "Li3E", "Li4ELi256ELb1ELb1ELb0ELb0EEE"]),  # scan_lean=0
+           ("k_scan_pairs_plane_unprepared", ["k_scan_pairs", "PlaneCell", "Li3E", "Li4ELi256ELb1ELb0ELb0ELb0EEE"]),  # scan_prepared=0 scan_lean=0
+           ("k_cells_bounds_plane", ["k_cells_bounds", "PlaneCell", "Li3E", "Li4ELb1ELb1ELb1EEE"]),  # mask-only counting pass: what runs
+           ("k_cells_bounds_plane_count", ["k_cells_bounds", "PlaneCell", "Li3E", "Li4ELb1ELb1ELb0EEE"]),  # scan_pack=0: count-only
+           ("k_cells_bounds_plane_general", ["k_cells_bounds", "PlaneCell", "Li3E", "Li4ELb1ELb0ELb0EEE"]),  # scan_lean=0
            ("k_scan_pairs_sphere", ["k_scan_pairs", "SphereCell", "Li3E"]),
            ("k_scan_pairs_line", ["k_scan_pairs", "LineCell", "Li3E"]),
            ("k_scan_us_f32", ["k_scan_us_f32", "USModel", "Lb1E"]),

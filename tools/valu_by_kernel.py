@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """SQ_INSTS_VALU / SQ_INSTS_SALU per kernel of ONE bench step (rocprofv3 --pmc, one pass):
     python3 tools/valu_by_kernel.py plane [0|1] [NAME=VALUE ...]      (scan_bound; options for tools/scan_once.py,
-                                                                       e.g. scan_prepared=0, scan_lean=0)
+                                                                       e.g. scan_prepared=0, scan_lean=0, scan_pack=0)
 Counters only: no tracing in the same pass."""
 import collections, csv, glob, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
