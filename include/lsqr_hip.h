@@ -166,6 +166,13 @@ LSQR_API int lsqr_sample_subsets(uint64_t seed, uint64_t first_index, size_t H, 
 LSQR_API int lsqr_agree_host(const lsqr_model_cfg *cfg, const double *params, const void *record, int *agree_out);
 LSQR_API int lsqr_estimate_host(const lsqr_model_cfg *cfg, const void *records, size_t count, size_t stride_bytes,
                                 double *params_out, int *n_params_out);
+/* The decision of lsqr_assign (below) for ONE record, on the host: params holds n_models rows of lsqr_num_params
+ * doubles; *label_out is the model the record goes to, or -1; *residual_out (nullable) its residual to that model,
+ * +infinity for -1.  The code the assignment kernel runs, compiled for the host: bit-identical labels and residuals.
+ * Models as for lsqr_assign; n_models == 0 returns LSQR_OK and writes nothing; n_models > 64 or a null cfg, params,
+ * record or label_out returns LSQR_ERR_INVALID. */
+LSQR_API int lsqr_assign_host(const lsqr_model_cfg *cfg, const double *params, size_t n_models, const void *record,
+                              int32_t *label_out, double *residual_out /* nullable */);
 
 /* ---- agree() scan over all observations (RANSAC.hxx:94-99, without the early exit) ---------- */
 LSQR_API int lsqr_scan(lsqr_ctx *ctx);
@@ -408,6 +415,55 @@ LSQR_API int lsqr_ransac_grouped_sequential(
     int32_t *labels_out /* nullable: lsqr_count(ctx) entries, upload order */,
     uint64_t *offsets_out /* nullable, host: n_groups + 1 */, lsqr_ransac_info *infos /* host, n_groups * max_models */,
     int32_t *status_out /* host, n_groups * max_models */, size_t *n_models_out /* host, n_groups */);
+/* ---- nearest-model assignment and refit on the device (csrc/assign.h) ---------------------------------------------
+ * The multi-model entry points above stop at greedy labels: round r claims every record that agrees with model r, and
+ * each model is fitted once, on what earlier rounds left.  These two finish the job on the records where they are.
+ * lsqr_assign: params holds n_models (<= 64) rows of lsqr_num_params doubles; each row becomes a scan row exactly as
+ *   lsqr_mask makes one.  For every record x of the context's upload / attach
+ *     label(x) = the smallest m in [0, n_models) that minimises residual(row_m, x) among the m with agree(row_m, x);
+ *                -1 when no m agrees
+ *   (ties go to the smaller m; a record with a non-finite coordinate agrees with nothing).  labels_out[i] is the
+ *   label of record i in upload order; residuals_out[i] (nullable) its residual to that model, +infinity for -1: the
+ *   values lsqr_mask and lsqr_residuals give for that row, bit for bit.  counts_out (nullable, host, n_models + 1):
+ *   the records per model, then the unassigned ones.  on_device = 1: labels_out and residuals_out are device
+ *   pointers; 0: host.
+ * lsqr_refine: assignment and least-squares refit in turn,
+ *     r = 0
+ *     loop: L_r = assign(params_r)
+ *           if r > 0 and L_r == L_{r-1}: converged, stop
+ *           if r == max_rounds: stop
+ *           params_{r+1} = refit(L_r);  r += 1
+ *   A round is ONE pass over the records (the pass that makes L_r also sums the moments of L_r, per model, about the
+ *   model's own point: the plane's and the line's point, the sphere's centre), one small solve launch and one 8-byte
+ *   read of the changed-counter.  On return *rounds_out = r, the refits done; params_inout = params_r; labels_out
+ *   (nullable) = L_r; counts_out (nullable) the counts of L_r; *converged_out says which stop it was.  So the
+ *   returned labels are always exactly lsqr_assign of the returned parameters, and max_rounds == 0 is lsqr_assign.
+ *   Refit of model m: with at least lsqr_min_subset records labelled m and a solve that gives a result the row is
+ *   replaced, otherwise it keeps its values for that round.  status_out[m]: LSQR_OK or LSQR_EMPTY for the last refit
+ *   round (LSQR_OK if no refit ran); fits[m].n_used: the records behind the last refit attempt; fits[m].n_params as
+ *   lsqr_ls_fit reports it (0 with LSQR_EMPTY, and where no refit ran).  No sum is a floating-point atomic: the same
+ *   call twice gives the same bits.
+ *   Models, taken from the context's lsqr_set_model: LSQR_MODEL_PLANE, LSQR_MODEL_LINE and LSQR_MODEL_SPHERE in every
+ *     dimension lsqr_set_model accepts for them, and LSQR_MODEL_LINE2D, whose parameters [n, a] carry a point: it is
+ *     accepted by both.  lsqr_assign takes the sphere with either ls_type; lsqr_refine refuses the geometric sphere
+ *     (its fit is Levenberg-Marquardt) with LSQR_ERR_INVALID.  Every other model returns LSQR_ERR_INVALID.
+ *   Checks, in this order: a null context is refused before anything is touched; the model (none set: LSQR_ERR_STATE);
+ *     n_models == 0 is a no-op returning LSQR_OK; n_models > 64, or a null params or labels_out (lsqr_assign), a null
+ *     params_inout, fits, status_out, rounds_out or converged_out (lsqr_refine) (LSQR_ERR_INVALID); no records in the
+ *     context (LSQR_ERR_STATE); more than 2^32 - 16 records (LSQR_ERR_INVALID).  Every argument error writes nothing.
+ *   The records are only read, at any stride; the context's hypotheses, mask, spatial index and the parameters of its
+ *     last mask are left as they were; the work runs on the context's stream (lsqr_set_stream), and the call returns
+ *     after it has finished.  lsqr_multi handles have no such form. */
+LSQR_API int lsqr_assign(lsqr_ctx *ctx, const double *params /* host, n_models * lsqr_num_params */, size_t n_models,
+                         int on_device /* 1: labels_out, residuals_out are device pointers */,
+                         int32_t *labels_out /* lsqr_count(ctx) entries, upload order */,
+                         double *residuals_out /* nullable */,
+                         uint64_t *counts_out /* nullable, host: n_models + 1, last = unassigned */);
+LSQR_API int lsqr_refine(lsqr_ctx *ctx, double *params_inout /* host, n_models * lsqr_num_params */, size_t n_models,
+                         size_t max_rounds, int on_device /* 1: labels_out is a device pointer */,
+                         int32_t *labels_out /* nullable */, uint64_t *counts_out /* nullable, host: n_models + 1 */,
+                         lsqr_fit_info *fits /* host, n_models */, int32_t *status_out /* host, n_models */,
+                         size_t *rounds_out, int *converged_out);
 /* Many independent RANSAC<T,S>::compute() problems (probabilistic overload, RANSAC.h:75-79) in one call.
  * Problem j is records [offsets[j], offsets[j+1]) of host_records (stride_bytes apart, laid out as for
  * lsqr_upload), walks sampler stream seeds[j] and is decided exactly as lsqr_ransac(ctx, p, seeds[j], NULL, 0, ...)

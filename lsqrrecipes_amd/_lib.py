@@ -68,6 +68,8 @@ SIGNATURES = {
     "lsqr_agree_host": (C.c_int, [C.POINTER(ModelCfg), C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
     "lsqr_estimate_host": (C.c_int, [C.POINTER(ModelCfg), C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p,
                                      C.POINTER(C.c_int)]),
+    "lsqr_assign_host": (C.c_int, [C.POINTER(ModelCfg), C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_int32),
+                                   _dp]),
     "lsqr_scan": (C.c_int, [_ctx]),
     "lsqr_get_hypotheses": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lsqr_num_hypotheses": (C.c_size_t, [_ctx]),
@@ -111,6 +113,9 @@ SIGNATURES = {
     "lsqr_ransac_grouped_sequential": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_int, C.c_double, C.c_void_p,
                                                  C.c_size_t, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
                                                  C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lsqr_assign": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lsqr_refine": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                              C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
     "lsqr_ransac_many": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_double, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lsqr_ransac_many_lm": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_double, C.c_void_p,

@@ -493,6 +493,74 @@ class Context:
                     best_votes=f("best_votes"), evaluated=f("evaluated"), n_params=f("n_params"), n_used=h("n_used"),
                     lm_info=h("lm_info"), lm_nfev=h("lm_nfev"), cost=h("cost"), offsets=offs)
 
+    def _assign_args(self, params, labels_out):
+        """the rows and the label buffer of assign / refine -> (params (M x P), M, total, on_device, labels, l_ptr)"""
+        if self.cfg is None:
+            raise L.LsqrError(L.ERR_STATE, "set_model has not been called")
+        par = np.array(params, dtype=np.float64, order="C")  # a copy: refine writes it
+        par = par.reshape(-1, self.P) if par.size else par.reshape(0, self.P)
+        total = int(self._lib.lsqr_count(self._h))
+        on_device = labels_out is not None
+        if on_device:
+            t = labels_out
+            if not (hasattr(t, "data_ptr") and t.is_cuda and "int32" in str(t.dtype) and t.is_contiguous()
+                    and t.numel() == total):
+                raise ValueError("labels_out must be a contiguous int32 device tensor of one entry per record")
+            labels, l_ptr = t, t.data_ptr()
+        else:
+            labels = np.full(max(total, 1), -1, dtype=np.int32)
+            l_ptr = L.ptr(labels)
+        return par, par.shape[0], total, on_device, labels, l_ptr
+
+    def assign(self, params, want_residuals=False, labels_out=None):
+        """Every record of the current upload / attach to the nearest of the models it agrees with (lsqr_assign).
+        params: M <= 64 rows of P parameters.  label = the smallest m that minimises residual(params[m], x) among the m
+        with agree(params[m], x), -1 when none agrees (and for a record with a non-finite coordinate).  Plane, line,
+        sphere (either ls_type) and 2-D line; any other model raises LsqrError(ERR_INVALID).
+        labels_out may be a contiguous int32 device tensor of one entry per record -- anything with data_ptr() and
+        is_cuda --, which receives the labels without a copy to the host; the residuals then stay on the host side out
+        of the call (want_residuals must be False).
+        -> dict: labels (int32 per record in upload order; a numpy array, or the caller's tensor), residuals (float64
+        per record: the residual to the assigned model, +inf for -1; None unless want_residuals) and counts (uint64,
+        M + 1: records per model, then the unassigned ones)."""
+        par, m, total, on_device, labels, l_ptr = self._assign_args(params, labels_out)
+        if on_device and want_residuals:
+            raise ValueError("want_residuals goes with host labels")
+        res = np.full(max(total, 1), np.inf) if want_residuals else None
+        counts = np.zeros(m + 1, dtype=np.uint64)
+        if m == 0:
+            counts[0] = total
+        self._chk(self._lib.lsqr_assign(self._h, L.ptr(par), m, 1 if on_device else 0, l_ptr, L.ptr(res),
+                                        L.ptr(counts)))
+        if not on_device:
+            labels = labels[:total]
+        return dict(labels=labels, residuals=res[:total] if res is not None else None, counts=counts)
+
+    def refine(self, params, max_rounds=8, labels_out=None):
+        """Assignment and least-squares refit in turn, on the device (lsqr_refine): L_r = assign(params_r); stop when
+        r > 0 and L_r == L_{r-1} (converged) or r == max_rounds; else params_{r+1} = the fit of every model on its own
+        records, r += 1.  A model with fewer than K records, or whose fit gives no result, keeps its row for that round.
+        The models of assign, except the geometric sphere (ERR_INVALID).  labels_out as for assign.
+        -> dict: params (M x P: params_r), labels (L_r: exactly assign(params)["labels"]), counts (M + 1, of L_r),
+        status (OK or EMPTY per model for the last refit round; OK when none ran), n_used (records behind the last
+        refit attempt), rounds (refits done) and converged."""
+        par, m, total, on_device, labels, l_ptr = self._assign_args(params, labels_out)
+        if int(max_rounds) < 0:
+            raise ValueError("max_rounds must not be negative")
+        counts = np.zeros(m + 1, dtype=np.uint64)
+        if m == 0:
+            counts[0] = total
+        fits = (L.FitInfo * max(m, 1))()
+        status = np.zeros(max(m, 1), dtype=np.int32)
+        rounds, conv = C.c_size_t(0), C.c_int(0)
+        self._chk(self._lib.lsqr_refine(self._h, L.ptr(par), m, int(max_rounds), 1 if on_device else 0, l_ptr,
+                                        L.ptr(counts), fits, L.ptr(status), C.byref(rounds), C.byref(conv)))
+        if not on_device:
+            labels = labels[:total]
+        return dict(params=par, labels=labels, counts=counts, status=status[:m],
+                    n_used=np.ctypeslib.as_array(fits)[:m]["n_used"].copy(), rounds=int(rounds.value),
+                    converged=bool(conv.value))
+
     def _many_records(self, problems):
         if self.cfg is None:
             raise L.LsqrError(L.ERR_STATE, "set_model has not been called")

@@ -1,0 +1,484 @@
+// assign.h -- lsqr_assign / lsqr_refine: every record of the context's upload goes to the NEAREST of up to 64 models it
+// agrees with, and (refine) every model is fitted again on its own records, round after round, on the device.
+//
+// The decision for one record (assign_one; the kernel and lsqr_assign_host run the same code):
+//   label(x) = the smallest m in [0, M) that minimises M::residual(row_m, x) among the m with M::agree(row_m, x);
+//              -1 when no m agrees, and for a record with a non-finite coordinate.  Strict '<' while m walks upwards.
+//   row_m is the scan row of the caller's parameters exactly as lsqr_mask makes one: zero-padded, then M::prepare.
+//
+//   k_assign_prepare  one lane per model: parameters -> scan rows
+//   k_assign_moments  ONE pass over the records.  A workgroup of kBlock lanes takes kAssignChunk consecutive records,
+//                     kAssignPerLane per lane, and keeps them in registers.  The M rows are read at wave-uniform
+//                     addresses (scalar loads, the scalar cache serves every wave of the chip), row by row, each row
+//                     against the lane's records.  The lane writes labels[i] (and residuals[i]); the workgroup counts
+//                     labels[i] != old[i] and the records per model (ballots, LDS integer adds, then one 64-bit integer
+//                     atomic per counter and workgroup).  WITH_MOMENTS: for every model m present in the chunk (one
+//                     64-bit presence mask per chunk) the phase-0 moment block of the records labelled m about model
+//                     m's own point (fit_origin_offset), by AccLs<M>::acc, reduced as k_many_mask_moments reduces:
+//                     the lane's records in index order, the __shfl_down tree, the four waves in index order;
+//                     -> partials[chunk][m][AccLs<M>::N].  A model absent from the chunk gets zeros.
+//   k_assign_solve    one workgroup per model: its partials summed in chunk order by one lane per moment (the four waves
+//                     stage them through LDS), then solve_small<M> about the model's own point (the body of
+//                     k_many_solve) -> SolveOut[m]; a model with at least lsqr_min_subset records and a solve that
+//                     succeeded gets its new scan row, any other keeps its row.
+//
+// Order of the sums: kAssignChunk fixes it, as kManyPart does for the batched finish.  Nothing is summed with a
+// floating-point atomic, so two runs of one call give the same bits.
+//
+// Budget (launch bounds kBlock = 4 waves): records 8 x REC doubles, labels 8, residuals 8 doubles, one moment block
+// (AccLs<M>::N <= 55 doubles) and its origin per lane -- the 3-D models take 92 .. 112 VGPRs (4 or 5 waves per SIMD), the
+// 8-D ones 256 and more (1 or 2 waves per SIMD); no kernel spills.  LDS of the pass: two buffers of 4 x N doubles for
+// the wave sums (3.4 KiB at N = 55), 64 counters, the four waves' presence masks -- under 4 KiB, no limit on occupancy.
+// The 64 x 45 doubles of an 8-D plane's accumulators never exist at once: one model's block at a time lives in
+// registers.  k_assign_solve: one tile of partials, 40 .. 60 KiB of LDS, one workgroup per model.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "devbuf.h"
+#include "host_entry.h"
+#include "kernels.h"
+#include "many.h"
+
+namespace lsqr {
+
+constexpr int kAssignMaxModels = 64;                        // one presence bit per model
+constexpr int kAssignPerLane = 8;                           // records a lane keeps in registers
+constexpr uint32_t kAssignChunk = kAssignPerLane * kBlock;  // records per workgroup (fixes the moment sums' order)
+
+inline uint32_t assign_chunks(uint64_t n) { return (uint32_t)((n + kAssignChunk - 1) / kAssignChunk); }
+
+// the models lsqr_assign takes: their parameters hold a point (fit_origin_offset >= 0)
+template <class M> struct AssignModel { static constexpr bool value = false; };
+template <int D> struct AssignModel<PlaneModel<D>> { static constexpr bool value = true; };
+template <int D> struct AssignModel<LineModel<D>> { static constexpr bool value = true; };
+template <int D> struct AssignModel<SphereModel<D>> { static constexpr bool value = true; };
+template <int D> struct AssignModel<PlaneModelN<D>> { static constexpr bool value = true; };
+template <int D> struct AssignModel<LineModelN<D>> { static constexpr bool value = true; };
+template <int D> struct AssignModel<SphereModelN<D>> { static constexpr bool value = true; };
+template <> struct AssignModel<Line2DModel> { static constexpr bool value = true; };  // [n, a]: a is its point
+
+inline bool assign_model_ok(const lsqr_model_cfg &cfg) {
+  return dispatch(cfg, [](auto tag) -> int {
+           return AssignModel<typename decltype(tag)::type>::value ? LSQR_OK : LSQR_ERR_INVALID;
+         }) == LSQR_OK;
+}
+
+// parameters -> scan row, as lsqr_mask makes one
+template <class M>
+LSQR_HD void assign_make_row(const double *params, const ModelConsts &mc, double *row) {
+  for (int j = 0; j < (int)M::SP; j++) row[j] = j < (int)M::P ? params[j] : 0.0;
+  M::prepare(row, mc);
+}
+
+template <class M>
+LSQR_HD bool assign_finite(const double *x) {
+  bool fin = true;
+  for (int d = 0; d < (int)M::REC; d++) fin = fin && (x[d] - x[d] == 0.0);  // false for NaN and +-Inf
+  return fin;
+}
+
+// model m against the record: the running (label, residual) of the walk m = 0, 1, ...
+template <class M>
+LSQR_HD void assign_step(const double *row, int32_t m, const double *x, const ModelConsts &mc, int32_t &label,
+                         double &res) {
+  if (M::agree(row, x, mc)) {
+    const double r = M::residual(row, x, mc);
+    if (r < res) {
+      res = r;
+      label = m;
+    }
+  }
+}
+
+// the decision for ONE record; rows: n_models scan rows of M::SP doubles.  -> label, *res_out (nullable) its residual
+template <class M>
+LSQR_HD int32_t assign_one(const double *rows, int n_models, const double *x, const ModelConsts &mc, double *res_out) {
+  int32_t label = -1;
+  double res = __builtin_inf();
+  if (assign_finite<M>(x))
+    for (int m = 0; m < n_models; m++) assign_step<M>(rows + (size_t)m * M::SP, m, x, mc, label, res);
+  if (res_out) *res_out = res;
+  return label;
+}
+
+// lsqr_assign_host: no context, no device
+inline int host_assign_host(const lsqr_model_cfg *cfg, const double *params, size_t n_models, const void *record,
+                            int32_t *label_out, double *residual_out) {
+  if (!cfg || !cfg_supported(*cfg) || !assign_model_ok(*cfg)) return LSQR_ERR_INVALID;
+  if (n_models == 0) return LSQR_OK;
+  if (n_models > (size_t)kAssignMaxModels || !params || !record || !label_out) return LSQR_ERR_INVALID;
+  ModelConsts mc;
+  model_consts(*cfg, &mc);
+  return dispatch(*cfg, [&](auto tag) -> int {
+    typedef typename decltype(tag)::type M;
+    if constexpr (AssignModel<M>::value) {
+      double rows[kAssignMaxModels * M::SP];
+      for (size_t m = 0; m < n_models; m++) assign_make_row<M>(params + m * M::P, mc, rows + m * M::SP);
+      double x[M::REC];
+      M::load((const double *)record, mc, x);
+      *label_out = assign_one<M>(rows, (int)n_models, x, mc, residual_out);
+      return LSQR_OK;
+    } else {
+      return LSQR_ERR_INVALID;
+    }
+  });
+}
+
+// the words of the call's device counters
+enum {
+  ASG_CHANGED = 0,                           // labels[i] != old[i]
+  ASG_COUNT = 1,                             // records per model of the last pass
+  ASG_USED = ASG_COUNT + kAssignMaxModels,   // records behind the last refit attempt
+  ASG_OK = ASG_USED + kAssignMaxModels,      // 1: that refit gave the model a new row
+  ASG_WORDS = ASG_OK + kAssignMaxModels
+};
+
+#if defined(__HIPCC__)
+template <class M>
+__global__ __launch_bounds__(64) void k_assign_prepare(const double *__restrict__ params, int n_models, ModelConsts mc,
+                                                       double *__restrict__ rows) {
+  const int m = threadIdx.x;
+  if (m >= n_models) return;
+  double p[M::P], row[M::SP];
+  for (int j = 0; j < (int)M::P; j++) p[j] = params[(size_t)m * M::P + j];
+  assign_make_row<M>(p, mc, row);
+  for (int j = 0; j < (int)M::SP; j++) rows[(size_t)m * M::SP + j] = row[j];
+}
+
+// data: n records, `stride` doubles apart; rows: n_models scan rows; labels: n entries; residuals, old: nullable;
+// counters: the ASG_ words, zeroed by the caller; partials (WITH_MOMENTS): [chunk][model][AccLs<M>::N]
+template <class M, bool WITH_MOMENTS>
+__global__ __launch_bounds__(kBlock) void k_assign_moments(const double *__restrict__ data, size_t stride, uint32_t n,
+                                                           const double *__restrict__ rows, int n_models, int org_off,
+                                                           ModelConsts mc, int32_t *__restrict__ labels,
+                                                           double *__restrict__ residuals,
+                                                           const int32_t *__restrict__ old,
+                                                           unsigned long long *__restrict__ counters,
+                                                           double *__restrict__ partials) {
+  typedef AccLs<M> A;
+  static_assert(A::N <= 64, "one lane per moment");
+  constexpr int R = kAssignPerLane, W = kBlock / 64;
+  __shared__ double s_m[2][W][WITH_MOMENTS ? (int)A::N : 1];
+  __shared__ unsigned long long s_p[W];
+  __shared__ uint32_t s_chg[W];
+  __shared__ uint32_t s_cnt[kAssignMaxModels];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const uint64_t c0 = (uint64_t)blockIdx.x * kAssignChunk;
+  const double qnan = __builtin_nan("");
+  if (threadIdx.x < kAssignMaxModels) s_cnt[threadIdx.x] = 0;
+
+  double x[R][M::REC], res[R];
+  int32_t lab[R];
+#pragma unroll
+  for (int j = 0; j < R; j++) {
+    const uint64_t i = c0 + (uint64_t)j * kBlock + threadIdx.x;
+    const bool in = i < n;
+    M::load(data + (in ? i : 0) * stride, mc, x[j]);
+    if (!in || !assign_finite<M>(x[j])) {
+#pragma unroll
+      for (int d = 0; d < (int)M::REC; d++) x[j][d] = qnan;  // NaN agrees with nothing
+    }
+    lab[j] = -1;
+    res[j] = __builtin_inf();
+  }
+  for (int m = 0; m < n_models; m++) {
+    const double *row = rows + (size_t)m * M::SP;  // wave-uniform: scalar loads
+#pragma unroll
+    for (int j = 0; j < R; j++) assign_step<M>(row, m, x[j], mc, lab[j], res[j]);
+  }
+
+  uint32_t chg = 0;
+  unsigned long long pres = 0;
+#pragma unroll
+  for (int j = 0; j < R; j++) {
+    const uint64_t i = c0 + (uint64_t)j * kBlock + threadIdx.x;
+    if (i >= n) continue;
+    labels[i] = lab[j];
+    if (residuals) residuals[i] = res[j];
+    if (old) chg += old[i] != lab[j] ? 1u : 0u;
+    if (lab[j] >= 0) pres |= 1ull << lab[j];
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    chg += __shfl_xor(chg, o);
+    pres |= __shfl_xor(pres, o);
+  }
+  if (lane == 0) {
+    s_p[wave] = pres;
+    s_chg[wave] = chg;
+  }
+  __syncthreads();
+  unsigned long long all = 0;
+  for (int w = 0; w < W; w++) all |= s_p[w];
+  // (uniform by construction; the scalar copies keep the model loop's control flow on the scalar unit)
+  const unsigned long long present = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(all >> 32)) << 32) |
+                                     __builtin_amdgcn_readfirstlane((uint32_t)all);
+  const unsigned long long mine = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(pres >> 32)) << 32) |
+                                  __builtin_amdgcn_readfirstlane((uint32_t)pres);
+
+  int it = 0;
+  for (unsigned long long rest = present; rest; rest &= rest - 1, it++) {
+    const int m = __builtin_ctzll(rest);
+    const bool here = (mine >> m) & 1ull;  // this wave holds records of model m
+    if (here) {
+      uint32_t cnt = 0;
+#pragma unroll
+      for (int j = 0; j < R; j++) cnt += (uint32_t)__popcll(__ballot(lab[j] == m));
+      if (lane == 0) atomicAdd(&s_cnt[m], cnt);
+    }
+    if constexpr (WITH_MOMENTS) {
+      double(*buf)[A::N] = s_m[it & 1];
+      if (here) {
+        constexpr int NC = M::P > M::REC ? M::P : M::REC;
+        double cv[NC], acc[A::N];
+        const double *org = rows + (size_t)m * M::SP + org_off;
+#pragma unroll
+        for (int k = 0; k < NC; k++) cv[k] = k < (int)M::ND ? org[k] : 0.0;
+#pragma unroll
+        for (int k = 0; k < (int)A::N; k++) acc[k] = 0.0;
+#pragma unroll
+        for (int j = 0; j < R; j++)
+          if (lab[j] == m) A::acc(x[j], cv, acc);
+#pragma unroll
+        for (int k = 0; k < (int)A::N; k++) {
+          double v = acc[k];
+          for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
+          if (lane == 0) buf[wave][k] = v;
+        }
+      } else if (lane < (int)A::N) {
+        buf[wave][lane] = 0.0;
+      }
+      // one barrier per model: the buffer written two models on is this one again, and no wave gets there before
+      // every wave has passed the barrier in between, that is, after this model's sums have been read
+      __syncthreads();
+      if (threadIdx.x < A::N) {
+        double t = 0.0;
+        for (int w = 0; w < W; w++) t += buf[w][threadIdx.x];
+        partials[((size_t)blockIdx.x * n_models + m) * A::N + threadIdx.x] = t;
+      }
+    }
+  }
+  if constexpr (WITH_MOMENTS) {
+    for (uint32_t e = threadIdx.x; e < (uint32_t)n_models * A::N; e += kBlock)
+      if (!((present >> (e / A::N)) & 1ull)) partials[(size_t)blockIdx.x * n_models * A::N + e] = 0.0;
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < n_models && s_cnt[threadIdx.x])
+    atomicAdd(&counters[ASG_COUNT + threadIdx.x], (unsigned long long)s_cnt[threadIdx.x]);
+  if (threadIdx.x == 0) {
+    unsigned long long t = 0;
+    for (int w = 0; w < W; w++) t += s_chg[w];
+    if (t) atomicAdd(&counters[ASG_CHANGED], t);
+  }
+}
+
+// one workgroup per model m: the partials of its `chunks` chunks summed in chunk order, then the solve of k_solve
+// about the model's own point.  A strictly serial sum of thousands of partials is bound by memory latency if one lane
+// loads what it adds, so the four waves stage tiles of kTile chunks through LDS -- every lane a few loads, all in
+// flight at once, the next tile's issued before this one is summed -- and lane k of wave 0 adds column k of the tile
+// in chunk order.  rows[m] becomes the new model's scan row when the model had at least M::K records and the solve gave
+// a result; counters[ASG_USED + m], counters[ASG_OK + m] and out[m] say what happened.
+template <class M>
+__global__ __launch_bounds__(kBlock) void k_assign_solve(const double *__restrict__ partials, uint32_t chunks,
+                                                         int n_models, int org_off, ModelConsts mc, double *rows,
+                                                         unsigned long long *counters, SolveOut *__restrict__ out) {
+  constexpr int N = M::NMOM;
+  constexpr int kTile = N <= 16 ? 512 : 128;            // chunks per tile: 40 KiB of LDS at N = 10, 55 KiB at N = 55
+  constexpr int E = (kTile * N + kBlock - 1) / kBlock;  // elements of a tile per lane
+  static_assert(N <= 64, "one lane per moment");
+  __shared__ double s_t[kTile * N];
+  __shared__ double mom[MOM_MAX];
+  __shared__ double ws[M::NMOM > 40 ? 512 : 8];
+  const int m = blockIdx.x, k = threadIdx.x;
+  const double *src = partials + (size_t)m * N;
+  const size_t qs = (size_t)n_models * N;  // from one chunk's block of model m to the next chunk's
+  double pre[E], t = 0.0;
+  auto fetch = [&](uint32_t q0) {  // tile [q0, q0 + kTile) -> registers
+    const uint32_t cnt = chunks - q0 < (uint32_t)kTile ? chunks - q0 : (uint32_t)kTile;
+#pragma unroll
+    for (int u = 0; u < E; u++) {
+      const uint32_t e = (uint32_t)u * kBlock + threadIdx.x, q = e / N;
+      pre[u] = q < cnt ? src[(size_t)(q0 + q) * qs + (e - q * N)] : 0.0;
+    }
+  };
+  if (chunks) fetch(0);
+  for (uint32_t q0 = 0; q0 < chunks; q0 += kTile) {
+    const uint32_t cnt = chunks - q0 < (uint32_t)kTile ? chunks - q0 : (uint32_t)kTile;
+    __syncthreads();  // the tile before has been summed
+#pragma unroll
+    for (int u = 0; u < E; u++) {
+      const uint32_t e = (uint32_t)u * kBlock + threadIdx.x;
+      if (e < (uint32_t)(kTile * N)) s_t[e] = pre[u];
+    }
+    __syncthreads();
+    if (q0 + kTile < chunks) fetch(q0 + kTile);
+    if (k < N)
+      for (uint32_t q = 0; q < cnt; q++) t += s_t[q * N + k];
+  }
+  if (k < N) mom[k] = t;
+  __syncthreads();
+  if (k != 0) return;
+  const unsigned long long cnt = counters[ASG_COUNT + m];
+  counters[ASG_USED + m] = cnt;
+  counters[ASG_OK + m] = 0;
+  SolveOut *o = out + m;
+  o->ok = o->n_params = o->lm_info = o->lm_nfev = o->cont = o->pad = 0;
+  o->cost = 0.0;
+  if (cnt < (unsigned long long)M::K) return;
+  constexpr int NC = M::P > M::REC ? M::P : M::REC;
+  double org[NC];
+  for (int j = 0; j < NC; j++) org[j] = j < (int)M::ND ? rows[(size_t)m * M::SP + org_off + j] : 0.0;
+  solve_small<M>(mom, org, mc, ws, o);
+  if (!o->ok) return;
+  double p[M::P], row[M::SP];
+  for (int j = 0; j < (int)M::P; j++) p[j] = o->params[j];
+  assign_make_row<M>(p, mc, row);
+  for (int j = 0; j < (int)M::SP; j++) rows[(size_t)m * M::SP + j] = row[j];
+  counters[ASG_OK + m] = 1;
+}
+
+// ---- host side -----------------------------------------------------------------------------------------------------
+struct AssignBufs {  // owned by the context, grown on demand
+  DevBuf<double> d_par, d_rows, d_partials, d_res;
+  DevBuf<int32_t> d_labels[2];
+  DevBuf<unsigned long long> d_cnt;
+  DevBuf<SolveOut> d_out;
+  PinBuf<char> h_pin;
+};
+
+struct AssignJob {
+  hipStream_t stream = nullptr;
+  lsqr_model_cfg cfg{};
+  ModelConsts mc{};
+  const double *data = nullptr;  // the context's records: n of them, `stride` doubles apart
+  size_t stride = 0;
+  uint32_t n = 0;
+  AssignBufs *B = nullptr;
+  // the call
+  double *params = nullptr;  // host, n_models rows of M::P: read, and written when a refit ran
+  size_t n_models = 0, max_rounds = 0;
+  int on_device = 0;
+  int32_t *labels_out = nullptr;
+  double *residuals_out = nullptr;
+  uint64_t *counts_out = nullptr;
+  lsqr_fit_info *fits = nullptr;
+  int32_t *status_out = nullptr;
+  size_t rounds = 0;
+  int converged = 0;
+  char err[256] = {0};
+};
+
+#define ASGCHK(call)                                                                                 \
+  do {                                                                                               \
+    hipError_t e_ = (call);                                                                          \
+    if (e_ != hipSuccess) {                                                                          \
+      snprintf(J.err, sizeof J.err, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, \
+               __LINE__);                                                                            \
+      return LSQR_ERR_HIP;                                                                           \
+    }                                                                                                \
+  } while (0)
+
+// lsqr_refine's loop (lsqr_assign: max_rounds == 0).  Round r: one pass -- labels L_r and, unless it is the last
+// round allowed, the moments of L_r --, the 8-byte changed-counter (with the counts: one copy) to the host, one solve
+// launch.  Returns after the stream has drained; the outputs are written only then.
+template <class M>
+int assign_run(AssignJob &J) {
+  AssignBufs &B = *J.B;
+  const int nm = (int)J.n_models, org_off = fit_origin_offset<M>(J.cfg);
+  const uint32_t n = J.n, chunks = assign_chunks(n);
+  const bool refine = J.max_rounds > 0;
+  // no refit and device pointers: the kernel writes the caller's buffers
+  const bool direct = !refine && J.on_device && J.labels_out;
+  const size_t pin_bytes = sizeof(double) * kAssignMaxModels * 16 + sizeof(unsigned long long) * ASG_WORDS;
+  static_assert(M::SP <= 16 && M::P <= 16, "pinned staging of the rows");
+  if (!B.h_pin.get()) ASGCHK(B.h_pin.alloc(pin_bytes));
+  ASGCHK(many_grow(B.d_par, (size_t)kAssignMaxModels * 16));
+  ASGCHK(many_grow(B.d_rows, (size_t)kAssignMaxModels * 16));
+  ASGCHK(many_grow(B.d_cnt, (size_t)ASG_WORDS));
+  if (!direct) ASGCHK(many_grow(B.d_labels[0], (size_t)n));
+  if (J.residuals_out && !J.on_device) ASGCHK(many_grow(B.d_res, (size_t)n));
+  if (refine) {
+    ASGCHK(many_grow(B.d_labels[1], (size_t)n));
+    ASGCHK(many_grow(B.d_partials, (size_t)chunks * nm * M::NMOM));
+    ASGCHK(many_grow(B.d_out, (size_t)kAssignMaxModels));
+  }
+  double *h_rows = (double *)B.h_pin.get();
+  unsigned long long *h_cnt = (unsigned long long *)(B.h_pin.get() + sizeof(double) * kAssignMaxModels * 16);
+
+  memcpy(h_rows, J.params, sizeof(double) * (size_t)nm * M::P);
+  ASGCHK(hipMemcpyAsync(B.d_par, h_rows, sizeof(double) * (size_t)nm * M::P, hipMemcpyHostToDevice, J.stream));
+  hipLaunchKernelGGL((k_assign_prepare<M>), dim3(1), dim3(64), 0, J.stream, B.d_par, nm, J.mc, B.d_rows);
+  ASGCHK(hipGetLastError());
+  ASGCHK(hipMemsetAsync(B.d_cnt, 0, sizeof(unsigned long long) * ASG_WORDS, J.stream));
+
+  int cur = 0;
+  size_t r = 0;
+  bool converged = false;
+  for (;;) {
+    const bool last = r == J.max_rounds;
+    int32_t *lab = direct ? J.labels_out : B.d_labels[cur].get();
+    double *res = !J.residuals_out ? nullptr : J.on_device ? J.residuals_out : B.d_res.get();
+    const int32_t *old = r > 0 ? B.d_labels[cur ^ 1].get() : nullptr;
+    if (r > 0)
+      ASGCHK(hipMemsetAsync(B.d_cnt, 0, sizeof(unsigned long long) * (ASG_COUNT + kAssignMaxModels), J.stream));
+    if (last)
+      hipLaunchKernelGGL((k_assign_moments<M, false>), dim3(chunks), dim3(kBlock), 0, J.stream, J.data, J.stride, n,
+                         B.d_rows, nm, org_off, J.mc, lab, res, old, B.d_cnt, nullptr);
+    else
+      hipLaunchKernelGGL((k_assign_moments<M, true>), dim3(chunks), dim3(kBlock), 0, J.stream, J.data, J.stride, n,
+                         B.d_rows, nm, org_off, J.mc, lab, res, old, B.d_cnt, B.d_partials);
+    ASGCHK(hipGetLastError());
+    ASGCHK(hipMemcpyAsync(h_cnt, B.d_cnt, sizeof(unsigned long long) * (ASG_COUNT + kAssignMaxModels),
+                          hipMemcpyDeviceToHost, J.stream));
+    ASGCHK(hipStreamSynchronize(J.stream));
+    if (r > 0 && h_cnt[ASG_CHANGED] == 0) {
+      converged = true;
+      break;
+    }
+    if (last) break;
+    hipLaunchKernelGGL((k_assign_solve<M>), dim3(nm), dim3(kBlock), 0, J.stream, B.d_partials, chunks, nm, org_off, J.mc,
+                       B.d_rows, B.d_cnt, B.d_out);
+    ASGCHK(hipGetLastError());
+    r++;
+    cur ^= 1;
+  }
+
+  // results: the rows and what the last refit did, then the labels of the last pass
+  if (r > 0) {
+    ASGCHK(hipMemcpyAsync(h_rows, B.d_rows, sizeof(double) * (size_t)nm * M::SP, hipMemcpyDeviceToHost, J.stream));
+    ASGCHK(hipMemcpyAsync(h_cnt + ASG_USED, B.d_cnt + ASG_USED, sizeof(unsigned long long) * 2 * kAssignMaxModels,
+                          hipMemcpyDeviceToHost, J.stream));
+  }
+  if (J.labels_out && !direct)
+    ASGCHK(hipMemcpyAsync(J.labels_out, B.d_labels[cur], sizeof(int32_t) * (size_t)n,
+                          J.on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, J.stream));
+  if (J.residuals_out && !J.on_device)
+    ASGCHK(hipMemcpyAsync(J.residuals_out, B.d_res, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, J.stream));
+  ASGCHK(hipStreamSynchronize(J.stream));
+  if (r > 0)
+    for (int m = 0; m < nm; m++)
+      for (int j = 0; j < (int)M::P; j++) J.params[(size_t)m * M::P + j] = h_rows[(size_t)m * M::SP + j];
+  if (J.counts_out) {
+    uint64_t sum = 0;
+    for (int m = 0; m < nm; m++) sum += (J.counts_out[m] = h_cnt[ASG_COUNT + m]);
+    J.counts_out[nm] = (uint64_t)n - sum;
+  }
+  if (J.fits) {  // lsqr_refine
+    for (int m = 0; m < nm; m++) {
+      const bool ok = r == 0 || h_cnt[ASG_OK + m] != 0;
+      J.status_out[m] = ok ? LSQR_OK : LSQR_EMPTY;
+      memset(&J.fits[m], 0, sizeof(lsqr_fit_info));
+      if (r > 0) {
+        J.fits[m].n_params = ok ? (int32_t)M::P : 0;
+        J.fits[m].n_used = h_cnt[ASG_USED + m];
+      }
+    }
+  }
+  J.rounds = r;
+  J.converged = converged ? 1 : 0;
+  return LSQR_OK;
+}
+#undef ASGCHK
+#endif  // __HIPCC__
+
+}  // namespace lsqr

@@ -44,6 +44,7 @@
 #include "sequential.h"
 #include "many_sequential.h"
 #include "grouped.h"
+#include "assign.h"
 
 #include <condition_variable>
 #include <mutex>
@@ -308,6 +309,7 @@ struct lsqr_ctx {
   long long opt_many_round = 0;  // lsqr_ransac_many: hypotheses per round (0 = kManyRoundDefault)
   bool opt_many_ex_fused = true;  // lsqr_ransac_many_exhaustive: small problems take k_many_ex_small
   std::unique_ptr<ManyBufs> many;  // lsqr_ransac_many's buffers (its own: the context's upload is not touched)
+  std::unique_ptr<AssignBufs> assign;  // lsqr_assign / lsqr_refine (assign.h): rows, labels, partials, counters
   // lsqr_ransac_sequential (sequential.h): the survivors of a round go from the current buffer into the OTHER of two
   // owned buffers (never into the caller's upload), their upload indices beside them; labels in upload order
   DevBuf<double> d_seq_rec[2];
@@ -3065,6 +3067,10 @@ int lsqr_estimate_host(const lsqr_model_cfg *cfg, const void *records, size_t co
                        double *params_out, int *n_params_out) {
   return host_estimate_host(cfg, records, count, stride_bytes, params_out, n_params_out);
 }
+int lsqr_assign_host(const lsqr_model_cfg *cfg, const double *params, size_t n_models, const void *record,
+                     int32_t *label_out, double *residual_out) {
+  return host_assign_host(cfg, params, n_models, record, label_out, residual_out);
+}
 
 int lsqr_set_model(lsqr_ctx *c, const lsqr_model_cfg *cfg) {
   if (!c || !cfg) return LSQR_ERR_INVALID;
@@ -4274,6 +4280,81 @@ int lsqr_ransac_grouped_sequential(lsqr_ctx *c, const int32_t *groups, size_t n_
   });
   if (st != LSQR_OK) return fail(c, st, "%s: %s", fn, J.err[0] ? J.err : "model not in this build");
   return LSQR_OK;
+}
+
+// ---- nearest-model assignment and refit (assign.h) -----------------------------------------------------------------
+// What lsqr_assign and lsqr_refine share.  The checks, in the contract's order: the context; the model gate; n_models
+// == 0 is LSQR_OK with every output untouched; n_models > 64 and the null arguments (args: the entry point's own
+// pointers are all there); the context holds a model and records; their count.  Then the job from the context and
+// assign_run, dispatched on the model.  The context's hypotheses, mask, index and d_par are not touched: the call has
+// buffers of its own (lsqr_ctx::assign).
+extern "C++" {
+static int assign_call(lsqr_ctx *c, const char *fn, bool refine, bool args, AssignJob &J) {
+  int st = need_ready(c, false);
+  if (st != LSQR_OK) return st;
+  if (!assign_model_ok(c->cfg))
+    return fail(c, LSQR_ERR_INVALID, "%s: plane, line, sphere and 2-D line only (model %d)", fn, c->cfg.model);
+  if (refine && wants_lm(c->cfg))
+    return fail(c, LSQR_ERR_INVALID, "%s: the geometric sphere's fit is iterative; lsqr_assign takes it", fn);
+  if (J.n_models == 0) return LSQR_OK;
+  if (J.n_models > (size_t)kAssignMaxModels) return fail(c, LSQR_ERR_INVALID, "%s: more than 64 models", fn);
+  if (!args) return fail(c, LSQR_ERR_INVALID, "%s: null argument", fn);
+  if ((st = need_ready(c, true)) != LSQR_OK) return st;
+  if (c->n > 0xFFFFFFF0ull) return fail(c, LSQR_ERR_INVALID, "%s: more than 2^32 - 16 records", fn);
+  if (!c->assign) c->assign.reset(new AssignBufs());
+  J.stream = c->stream;
+  J.cfg = c->cfg;
+  J.mc = c->mc;
+  J.data = c->d_data;
+  J.stride = c->stride;
+  J.n = (uint32_t)c->n;
+  J.B = c->assign.get();
+  st = dispatch(c->cfg, [&](auto tag) -> int {
+    typedef typename decltype(tag)::type M;
+    if constexpr (AssignModel<M>::value) return assign_run<M>(J);
+    else return LSQR_ERR_INVALID;
+  });
+  if (st != LSQR_OK) {
+    (void)sync_stream(c);  // nothing of this call is left in flight on its buffers
+    return fail(c, st, "%s: %s", fn, J.err[0] ? J.err : "model not in this build");
+  }
+  bsel_host_synced(c);  // (assign_run has waited for the stream)
+  return LSQR_OK;
+}
+}  // extern "C++"
+
+int lsqr_assign(lsqr_ctx *c, const double *params, size_t n_models, int on_device, int32_t *labels_out,
+                double *residuals_out, uint64_t *counts_out) {
+  AssignJob J;
+  J.params = const_cast<double *>(params);  // (read only: no refit runs)
+  J.n_models = n_models;
+  J.max_rounds = 0;
+  J.on_device = on_device ? 1 : 0;
+  J.labels_out = labels_out;
+  J.residuals_out = residuals_out;
+  J.counts_out = counts_out;
+  return assign_call(c, "lsqr_assign", false, params && labels_out, J);
+}
+
+int lsqr_refine(lsqr_ctx *c, double *params_inout, size_t n_models, size_t max_rounds, int on_device,
+                int32_t *labels_out, uint64_t *counts_out, lsqr_fit_info *fits, int32_t *status_out,
+                size_t *rounds_out, int *converged_out) {
+  AssignJob J;
+  J.params = params_inout;
+  J.n_models = n_models;
+  J.max_rounds = max_rounds;
+  J.on_device = on_device ? 1 : 0;
+  J.labels_out = labels_out;
+  J.counts_out = counts_out;
+  J.fits = fits;
+  J.status_out = status_out;
+  const bool args = params_inout && fits && status_out && rounds_out && converged_out;
+  const int st = assign_call(c, "lsqr_refine", true, args, J);
+  if (st == LSQR_OK && n_models > 0) {
+    *rounds_out = J.rounds;
+    *converged_out = J.converged;
+  }
+  return st;
 }
 
 // C(n,k) and the rank-th k-subset in the exhaustive overload's order (comb.h); host only

@@ -357,6 +357,70 @@ class RANSAC {
     return sequentialOn(data, ctx, cfg, data.size(), parameters, p, maxModels, minVotes, labels);
   }
 
+  // Nearest-model assignment (not in the reference), the follow-up of computeSequential: labels[i] is the model of
+  // `models` that record i goes to, else -1.  Estimators whose device model lsqr_assign takes (plane, line, sphere,
+  // 2-D line) run ONE device pass (lsqr_assign): the model with the smallest residual among those the record agrees
+  // with, ties to the smaller index.  Every other estimator -- a user-defined one without a device model, the device
+  // models lsqr_assign refuses, forceHostLoop() -- runs a plain host loop over the estimator's agree() virtual, the
+  // FIRST agreeing model winning: the interface has no residual to compare (this mirrors the plugin path of
+  // compute()).  No models, or no records: every label is -1.  More than 64 models on the device path, or a model
+  // vector of the wrong length, throw std::invalid_argument.
+  static void assignToModels(const std::vector<std::vector<S> > &models, ParametersEstimator<T, S> *paramEstimator,
+                             std::vector<T> &data, std::vector<int> &labels) {
+    lsqr_model_cfg cfg;
+    if (!paramEstimator) throw std::invalid_argument("lsqrRecipes::RANSAC: null estimator");
+    labels.assign(data.size(), -1);
+    if (models.empty() || data.empty()) return;
+    if (!paramEstimator->deviceModel(cfg) || forceHostLoop() || !assignOnDevice(cfg, false)) {
+      pluginAssign(models, paramEstimator, data, labels);
+      return;
+    }
+    detail::Device &d = detail::Device::instance();
+    lsqr_ctx *ctx = d.ctx();
+    if (lsqr_multi *m = d.multi()) ctx = lsqr_multi_ctx(m, 0);
+    d.check(lsqr_set_model(ctx, &cfg));
+    d.check(lsqr_upload(ctx, &data[0], data.size(), sizeof(T)));
+    std::vector<double> par = packModels(models, cfg);
+    std::vector<int32_t> lab(data.size());
+    d.check(lsqr_assign(ctx, &par[0], models.size(), 0, &lab[0], NULL, NULL));
+    labels.assign(lab.begin(), lab.end());
+  }
+
+  // Assignment and least-squares refit in turn: L_r = assignToModels(models_r); stop when r > 0 and L_r == L_{r-1}
+  // (*converged = true) or r == maxRounds; else every model is fitted again on its own records (leastSquaresEstimate;
+  // a model with fewer than numForEstimate() records, or whose fit comes back empty, keeps its parameters), r += 1.
+  // -> the refits done; `models` and `labels` are models_r and L_r, so the labels are always the assignment of the
+  // returned models.  The device path is ONE call (lsqr_refine: a round is one pass over the records on the device);
+  // the host loop, taken as in assignToModels and for the geometric sphere (its fit is iterative), assigns by the
+  // first agreeing model.
+  static size_t refineModels(std::vector<std::vector<S> > &models, ParametersEstimator<T, S> *paramEstimator,
+                             std::vector<T> &data, size_t maxRounds, std::vector<int> &labels,
+                             bool *converged = NULL) {
+    lsqr_model_cfg cfg;
+    if (!paramEstimator) throw std::invalid_argument("lsqrRecipes::RANSAC: null estimator");
+    labels.assign(data.size(), -1);
+    if (converged) *converged = false;
+    if (models.empty() || data.empty()) return 0;
+    if (!paramEstimator->deviceModel(cfg) || forceHostLoop() || !assignOnDevice(cfg, true))
+      return pluginRefine(models, paramEstimator, data, maxRounds, labels, converged);
+    detail::Device &d = detail::Device::instance();
+    lsqr_ctx *ctx = d.ctx();
+    if (lsqr_multi *m = d.multi()) ctx = lsqr_multi_ctx(m, 0);
+    d.check(lsqr_set_model(ctx, &cfg));
+    d.check(lsqr_upload(ctx, &data[0], data.size(), sizeof(T)));
+    const size_t M = models.size(), P = (size_t)lsqr_num_params(&cfg);
+    std::vector<double> par = packModels(models, cfg);
+    std::vector<int32_t> lab(data.size()), status(M);
+    std::vector<lsqr_fit_info> fits(M);
+    size_t rounds = 0;
+    int conv = 0;
+    d.check(lsqr_refine(ctx, &par[0], M, maxRounds, 0, &lab[0], NULL, &fits[0], &status[0], &rounds, &conv));
+    for (size_t m = 0; m < M; m++) models[m].assign(&par[m * P], &par[m * P] + P);
+    labels.assign(lab.begin(), lab.end());
+    if (converged) *converged = conv != 0;
+    return rounds;
+  }
+
   // Sequential RANSAC over many independent problems (not in the reference): problem j is data[j], and
   // computeManySequential(...)[j], parameters[j] and (*labels)[j] equal what computeSequential returns / leaves on
   // data[j] after seed(seed() + j * maxModels) -- round r of problem j walks sampler stream seed() + j * maxModels + r.
@@ -680,6 +744,63 @@ class RANSAC {
       orig.resize(w);
     }
     return fraction;
+  }
+
+  // ---- assignToModels / refineModels -------------------------------------------------------------------------
+  // the device models lsqr_assign (refit: lsqr_refine) takes
+  static bool assignOnDevice(const lsqr_model_cfg &cfg, bool refit) {
+    if (cfg.model == LSQR_MODEL_SPHERE) return !refit || cfg.ls_type == LSQR_LS_ALGEBRAIC;
+    return cfg.model == LSQR_MODEL_PLANE || cfg.model == LSQR_MODEL_LINE || cfg.model == LSQR_MODEL_LINE2D;
+  }
+
+  // the models as rows of lsqr_num_params doubles
+  static std::vector<double> packModels(const std::vector<std::vector<S> > &models, const lsqr_model_cfg &cfg) {
+    const size_t P = (size_t)lsqr_num_params(&cfg);
+    if (models.size() > 64) throw std::invalid_argument("lsqrRecipes::RANSAC: more than 64 models");
+    std::vector<double> par(models.size() * P);
+    for (size_t m = 0; m < models.size(); m++) {
+      if (models[m].size() != P) throw std::invalid_argument("lsqrRecipes::RANSAC: model vector of the wrong length");
+      for (size_t j = 0; j < P; j++) par[m * P + j] = (double)models[m][j];
+    }
+    return par;
+  }
+
+  // the host loop of assignToModels: the first model whose agree() holds
+  static void pluginAssign(const std::vector<std::vector<S> > &models, ParametersEstimator<T, S> *est,
+                           std::vector<T> &data, std::vector<int> &labels) {
+    std::vector<std::vector<S> > rows(models);  // (agree() takes its parameters by non-const reference)
+    for (size_t i = 0; i < data.size(); i++) {
+      labels[i] = -1;
+      for (size_t m = 0; m < rows.size() && labels[i] < 0; m++)
+        if (!rows[m].empty() && est->agree(rows[m], data[i])) labels[i] = (int)m;
+    }
+  }
+
+  // the host loop of refineModels
+  static size_t pluginRefine(std::vector<std::vector<S> > &models, ParametersEstimator<T, S> *est,
+                             std::vector<T> &data, size_t maxRounds, std::vector<int> &labels, bool *converged) {
+    std::vector<int> prev;
+    size_t r = 0;
+    for (;;) {
+      pluginAssign(models, est, data, labels);
+      if (r > 0 && labels == prev) {
+        if (converged) *converged = true;
+        break;
+      }
+      if (r == maxRounds) break;
+      for (size_t m = 0; m < models.size(); m++) {
+        std::vector<T *> own;
+        for (size_t i = 0; i < data.size(); i++)
+          if (labels[i] == (int)m) own.push_back(&data[i]);
+        if (own.size() < est->numForEstimate()) continue;
+        std::vector<S> fit;
+        est->leastSquaresEstimate(own, fit);
+        if (!fit.empty()) models[m] = fit;
+      }
+      prev = labels;
+      r++;
+    }
+    return r;
   }
 
   static double finish(bool ok, const lsqr_ransac_info &info, const std::vector<double> &p,
