@@ -464,6 +464,61 @@ LSQR_API int lsqr_refine(lsqr_ctx *ctx, double *params_inout /* host, n_models *
                          int32_t *labels_out /* nullable */, uint64_t *counts_out /* nullable, host: n_models + 1 */,
                          lsqr_fit_info *fits /* host, n_models */, int32_t *status_out /* host, n_models */,
                          size_t *rounds_out, int *converged_out);
+/* ---- the same with ONE MODEL SET PER LABEL (csrc/assign_grouped.h) -------------------------------------------------
+ * lsqr_assign_grouped / lsqr_refine_grouped take what lsqr_ransac_grouped_sequential leaves -- params_out and
+ * n_models_out, unchanged -- over the same groups array and the same resident records: row g * max_models + m of params
+ * is model m of group g; rows with m >= n_models[g] are never read and never written.  groups follows
+ * lsqr_ransac_grouped's rules: group g is the records with groups[i] == g, in upload order; a negative label or one
+ * >= n_groups puts the record in no group.  on_device = 1: groups, labels_out and residuals_out are device pointers;
+ * 0: host pointers, one copy up and one copy down.
+ *   Contract: group g is decided bit for bit as lsqr_assign / lsqr_refine decide it on a fresh context with the same
+ *     model and options that holds the stable gather of group g's records, tightly packed, and is given rows
+ *     g * max_models .. + n_models[g].  Bit-identical: labels_out[i] (the model index inside the record's group, or
+ *     -1), residuals_out[i], the counts; for lsqr_refine_grouped also the returned parameters, status_out,
+ *     fits[].n_used, fits[].n_params, rounds_out[g] and converged_out[g].  The sums keep lsqr_refine's order per
+ *     group (chunks of 2048 of the group's packed records), nothing is summed with a floating-point atomic, so a
+ *     group's results do not depend on the other groups of the call, on how the ids are numbered, or on the run.
+ *   Each group runs lsqr_refine's loop on its own: it stops when r > 0 and its labels did not change, or when
+ *     r == max_rounds; once stopped it is passed over, and its rows and labels stay as its last pass left them.  The
+ *     host reads one 8-byte word per round (the groups still going).  max_rounds == 0 is lsqr_assign_grouped, and the
+ *     returned labels are always exactly the grouped assignment of the returned parameters.
+ *   What does not run: a record in no group, and every record of a group with n_models[g] == 0, gets label -1 and
+ *     residual +infinity; every entry of labels_out / residuals_out is written exactly once (no fill of the caller's
+ *     buffer precedes it).  A group with no records or with n_models[g] == 0 has rounds_out[g] = 0,
+ *     converged_out[g] = 0, status_out LSQR_OK with zeroed fits for m < n_models[g], and untouched rows.  Entries
+ *     with m >= n_models[g]: status_out LSQR_ERR_STATE (model not there) and a zeroed fit.
+ *     counts_out[g * (max_models + 1) + m]: the records of group g labelled m (0 for m >= n_models[g]); slot
+ *     max_models: the group's unassigned records.  offsets_out: the prefix sums of the group sizes.
+ *   Models: those of lsqr_assign / lsqr_refine; lsqr_refine_grouped refuses the geometric sphere (LSQR_ERR_INVALID).
+ *   Checks, in this order: a null context is refused before anything is touched; the model (none set: LSQR_ERR_STATE;
+ *     one the call does not take: LSQR_ERR_INVALID); n_groups == 0 is a no-op returning LSQR_OK; max_models > 64,
+ *     n_groups > 2^31 - 1, a null groups, params, n_models or labels_out (assign), a null groups, params_inout,
+ *     n_models, fits, status_out, rounds_out or converged_out (refine), any n_models[g] > max_models
+ *     (LSQR_ERR_INVALID); no records in the context (LSQR_ERR_STATE); more than 2^32 - 16 records (LSQR_ERR_INVALID);
+ *     max_models == 0 returns LSQR_OK after writing the -1 / +infinity labels and the zero outputs above.  Every
+ *     argument error writes nothing.
+ *   The context's upload, hypotheses, mask, spatial index and the parameters of its last mask are left as they were;
+ *     the work runs on the context's stream, and the call returns after it has finished.  One synchronisation precedes
+ *     the first pass (the n_groups + 1 offsets cross to the host); then one per round.  lsqr_multi handles have no
+ *     such form. */
+LSQR_API int lsqr_assign_grouped(lsqr_ctx *ctx, const int32_t *groups /* lsqr_count(ctx), upload order */,
+                                 size_t n_groups, int on_device,
+                                 const double *params /* host, n_groups * max_models * lsqr_num_params */,
+                                 const size_t *n_models /* host, n_groups; each <= max_models */,
+                                 size_t max_models /* <= 64 */,
+                                 int32_t *labels_out /* lsqr_count(ctx) entries, upload order */,
+                                 double *residuals_out /* nullable */,
+                                 uint64_t *counts_out /* nullable, host: n_groups * (max_models + 1) */,
+                                 uint64_t *offsets_out /* nullable, host: n_groups + 1 */);
+LSQR_API int lsqr_refine_grouped(lsqr_ctx *ctx, const int32_t *groups, size_t n_groups, int on_device,
+                                 double *params_inout /* host, n_groups * max_models * lsqr_num_params */,
+                                 const size_t *n_models, size_t max_models, size_t max_rounds,
+                                 int32_t *labels_out /* nullable */, uint64_t *counts_out /* nullable */,
+                                 uint64_t *offsets_out /* nullable */,
+                                 lsqr_fit_info *fits /* host, n_groups * max_models */,
+                                 int32_t *status_out /* host, n_groups * max_models */,
+                                 size_t *rounds_out /* host, n_groups */,
+                                 int32_t *converged_out /* host, n_groups */);
 /* Many independent RANSAC<T,S>::compute() problems (probabilistic overload, RANSAC.h:75-79) in one call.
  * Problem j is records [offsets[j], offsets[j+1]) of host_records (stride_bytes apart, laid out as for
  * lsqr_upload), walks sampler stream seeds[j] and is decided exactly as lsqr_ransac(ctx, p, seeds[j], NULL, 0, ...)

@@ -561,6 +561,107 @@ class Context:
                     n_used=np.ctypeslib.as_array(fits)[:m]["n_used"].copy(), rounds=int(rounds.value),
                     converged=bool(conv.value))
 
+    def _assign_grouped_args(self, groups, n_groups, params, n_models, labels_out):
+        """the labels, rows and label buffer of assign_grouped / refine_grouped, groups and labels_out handled as in
+        ransac_grouped_sequential -> (n, m, total, on_device, g, g_ptr, par, nm, labels, l_ptr); g keeps the host
+        copy of the labels alive"""
+        if self.cfg is None:
+            raise L.LsqrError(L.ERR_STATE, "set_model has not been called")
+        n = int(n_groups)
+        if n < 0:
+            raise ValueError("n_groups must not be negative")
+        par = np.array(params, dtype=np.float64, order="C")  # a copy: refine_grouped writes it
+        if par.ndim != 3 or par.shape[0] != n or par.shape[2] != self.P:
+            raise ValueError("params must be shaped (n_groups, max_models, P)")
+        m = par.shape[1]
+        nm = np.full(n, m, dtype=np.uintp) if n_models is None else np.ascontiguousarray(n_models, dtype=np.uintp)
+        if nm.shape != (n,):
+            raise ValueError("one model count per group")
+        total = int(self._lib.lsqr_count(self._h))
+        on_device = hasattr(groups, "data_ptr")
+        labels, l_ptr = None, None
+        if on_device:
+            if not groups.is_cuda or "int32" not in str(groups.dtype) or not groups.is_contiguous():
+                raise ValueError("device groups must be a contiguous int32 device tensor")
+            if groups.numel() != total:
+                raise ValueError("one label per record")
+            g, g_ptr = groups, groups.data_ptr()
+            if labels_out is not None:
+                t = labels_out
+                if not (hasattr(t, "data_ptr") and t.is_cuda and "int32" in str(t.dtype) and t.is_contiguous()
+                        and t.numel() == total):
+                    raise ValueError("labels_out must be a contiguous int32 device tensor of one entry per record")
+                labels, l_ptr = t, t.data_ptr()
+        else:
+            if labels_out is not None:
+                raise ValueError("labels_out goes with device groups")
+            g = np.asarray(groups)
+            if g.dtype.kind not in "iu":
+                raise ValueError("groups must be integers")
+            if g.shape != (total,):
+                raise ValueError("one label per record")
+            # (labels beyond int32 are in no group, as -1 is)
+            g = np.ascontiguousarray(np.where((g >= 0) & (g <= 0x7FFFFFFF), g, -1) if g.dtype != np.int32 else g,
+                                     dtype=np.int32)
+            g_ptr = L.ptr(g)
+            labels = np.full(max(total, 1), -1, dtype=np.int32)
+            l_ptr = L.ptr(labels)
+        return n, m, total, on_device, g, g_ptr, par, nm, labels, l_ptr
+
+    def assign_grouped(self, groups, n_groups, params, n_models=None, want_residuals=False, labels_out=None):
+        """assign with one model set per label (lsqr_assign_grouped): group g is the records i with groups[i] == g, in
+        upload order, and goes to the nearest of params[g, :n_models[g]] as assign decides it on those records alone,
+        bit for bit.  params: (n_groups, max_models, P), max_models <= 64 -- what ransac_grouped_sequential returns as
+        params, with its n_models; n_models defaults to max_models for every group.  A record in no group (a label
+        that is negative or >= n_groups) or in a group without models gets -1 and +inf.
+        groups / labels_out: a numpy integer array (host form), or contiguous int32 device tensors of one entry per
+        record, as in ransac_grouped_sequential; the device form needs labels_out, allocates nothing on the device and
+        leaves the residuals out (want_residuals must be False).
+        -> dict: labels (the model index inside the record's group), residuals (None unless want_residuals), counts
+        (uint64, (n_groups, max_models + 1): records per model, then the group's unassigned ones) and offsets (the
+        prefix sums of the group sizes)."""
+        n, m, total, on_device, g, g_ptr, par, nm, labels, l_ptr = self._assign_grouped_args(
+            groups, n_groups, params, n_models, labels_out)
+        if on_device and want_residuals:
+            raise ValueError("want_residuals goes with host groups")
+        if on_device and labels is None:
+            raise ValueError("device groups need a device labels_out")
+        res = np.full(max(total, 1), np.inf) if want_residuals else None
+        counts = np.zeros((n, m + 1), dtype=np.uint64)
+        offs = np.zeros(n + 1, dtype=np.uint64)
+        self._chk(self._lib.lsqr_assign_grouped(self._h, g_ptr, n, 1 if on_device else 0, L.ptr(par), L.ptr(nm), m,
+                                                l_ptr, L.ptr(res), L.ptr(counts), L.ptr(offs)))
+        if not on_device:
+            labels = labels[:total]
+        return dict(labels=labels, residuals=res[:total] if res is not None else None, counts=counts, offsets=offs)
+
+    def refine_grouped(self, groups, n_groups, params, n_models=None, max_rounds=8, labels_out=None):
+        """refine with one model set per label (lsqr_refine_grouped): every group runs refine's loop on its own records
+        and rows, bit for bit as refine runs it on those records alone, and stops on its own (converged, or at
+        max_rounds); the records never leave the device.  Arguments as for assign_grouped; the device form may leave
+        labels_out out.  The models of refine.
+        -> dict: params ((n_groups, max_models, P); rows m >= n_models[g] as given), labels (None for the device form
+        without labels_out), counts ((n_groups, max_models + 1)), status and n_used ((n_groups, max_models); status
+        ERR_STATE where m >= n_models[g]), rounds (int64 per group), converged (bool per group) and offsets."""
+        n, m, total, on_device, g, g_ptr, par, nm, labels, l_ptr = self._assign_grouped_args(
+            groups, n_groups, params, n_models, labels_out)
+        if int(max_rounds) < 0:
+            raise ValueError("max_rounds must not be negative")
+        counts = np.zeros((n, m + 1), dtype=np.uint64)
+        offs = np.zeros(n + 1, dtype=np.uint64)
+        fits = (L.FitInfo * max(n * m, 1))()
+        status = np.full(max(n * m, 1), L.ERR_STATE, dtype=np.int32)
+        rounds = np.zeros(max(n, 1), dtype=np.uintp)
+        conv = np.zeros(max(n, 1), dtype=np.int32)
+        self._chk(self._lib.lsqr_refine_grouped(self._h, g_ptr, n, 1 if on_device else 0, L.ptr(par), L.ptr(nm), m,
+                                                int(max_rounds), l_ptr, L.ptr(counts), L.ptr(offs), fits,
+                                                L.ptr(status), L.ptr(rounds), L.ptr(conv)))
+        if labels is not None and not on_device:
+            labels = labels[:total]
+        n_used = np.ctypeslib.as_array(fits)[:n * m]["n_used"].reshape(n, m).copy()
+        return dict(params=par, labels=labels, counts=counts, status=status[:n * m].reshape(n, m), n_used=n_used,
+                    rounds=rounds[:n].astype(np.int64), converged=conv[:n].astype(bool), offsets=offs)
+
     def _many_records(self, problems):
         if self.cfg is None:
             raise L.LsqrError(L.ERR_STATE, "set_model has not been called")

@@ -17,6 +17,7 @@
 //   k_grp_scatter_labels  (lsqr_ransac_grouped_sequential) one lane per sorted position r: labels[perm[r]] = the round
 //                  label of packed position r, or -1 for the records in no problem (r >= the grouped total); written
 //                  exactly once, as the consensus is
+//   k_grp_scatter_f64     (lsqr_assign_grouped) the same for a packed array of doubles, with a fill value
 //
 // "A problem with a winner" is one whose search took a finishing slot (fit.n_used > 0), NOT "status LSQR_OK": a winner
 // whose final least-squares fit fails ends LSQR_EMPTY with its hypothesis' consensus in the mask, and lsqr_ransac_many
@@ -117,6 +118,14 @@ __global__ __launch_bounds__(kBlock) void k_grp_scatter_labels(const uint32_t *_
                                                                int32_t *__restrict__ labels) {
   for (uint64_t r = (uint64_t)blockIdx.x * kBlock + threadIdx.x; r < n; r += (uint64_t)gridDim.x * kBlock)
     labels[perm[r]] = r < total ? packed[r] : -1;
+}
+
+// its sibling for doubles (lsqr_assign_grouped's residuals): `fill` for the records in no problem
+__global__ __launch_bounds__(kBlock) void k_grp_scatter_f64(const uint32_t *__restrict__ perm, uint32_t n,
+                                                            uint32_t total, const double *__restrict__ packed,
+                                                            double fill, double *__restrict__ out) {
+  for (uint64_t r = (uint64_t)blockIdx.x * kBlock + threadIdx.x; r < n; r += (uint64_t)gridDim.x * kBlock)
+    out[perm[r]] = r < total ? packed[r] : fill;
 }
 
 inline unsigned grp_grid(uint64_t lanes) {

@@ -45,6 +45,7 @@
 #include "many_sequential.h"
 #include "grouped.h"
 #include "assign.h"
+#include "assign_grouped.h"
 
 #include <condition_variable>
 #include <mutex>
@@ -310,6 +311,7 @@ struct lsqr_ctx {
   bool opt_many_ex_fused = true;  // lsqr_ransac_many_exhaustive: small problems take k_many_ex_small
   std::unique_ptr<ManyBufs> many;  // lsqr_ransac_many's buffers (its own: the context's upload is not touched)
   std::unique_ptr<AssignBufs> assign;  // lsqr_assign / lsqr_refine (assign.h): rows, labels, partials, counters
+  std::unique_ptr<AssignGrpBufs> assign_grp;  // lsqr_assign_grouped / lsqr_refine_grouped (assign_grouped.h)
   // lsqr_ransac_sequential (sequential.h): the survivors of a round go from the current buffer into the OTHER of two
   // owned buffers (never into the caller's upload), their upload indices beside them; labels in upload order
   DevBuf<double> d_seq_rec[2];
@@ -4355,6 +4357,94 @@ int lsqr_refine(lsqr_ctx *c, double *params_inout, size_t n_models, size_t max_r
     *converged_out = J.converged;
   }
   return st;
+}
+
+// ---- the same with one model set per label (assign_grouped.h) ---------------------------------------------------------
+// What lsqr_assign_grouped and lsqr_refine_grouped share.  The checks, in the contract's order: the context; the model
+// gate; n_groups == 0 is LSQR_OK with every output untouched; max_models, n_groups, the null arguments (args: the
+// entry point's own pointers are all there) and every n_models[g]; the context holds records; their count.  The sort
+// and the packed copy live in the batched calls' buffers (lsqr_ctx::many), as lsqr_ransac_grouped's do; the rest in
+// lsqr_ctx::assign_grp.  The context's upload, hypotheses, mask, index and d_par are not touched.
+extern "C++" {
+static int assign_grouped_call(lsqr_ctx *c, const char *fn, bool args, AssignGrpJob &J) {
+  int st = need_ready(c, false);
+  if (st != LSQR_OK) return st;
+  if (!assign_model_ok(c->cfg))
+    return fail(c, LSQR_ERR_INVALID, "%s: plane, line, sphere and 2-D line only (model %d)", fn, c->cfg.model);
+  if (J.refine && wants_lm(c->cfg))
+    return fail(c, LSQR_ERR_INVALID, "%s: the geometric sphere's fit is iterative; lsqr_assign_grouped takes it", fn);
+  if (J.n_groups == 0) return LSQR_OK;
+  if (J.max_models > (size_t)kAssignMaxModels) return fail(c, LSQR_ERR_INVALID, "%s: more than 64 models", fn);
+  if (J.n_groups > 0x7FFFFFFFull) return fail(c, LSQR_ERR_INVALID, "%s: more than 2^31 - 1 groups", fn);
+  if (!args || !J.groups || !J.params || !J.n_models) return fail(c, LSQR_ERR_INVALID, "%s: null argument", fn);
+  for (size_t g = 0; g < J.n_groups; g++)
+    if (J.n_models[g] > J.max_models)
+      return fail(c, LSQR_ERR_INVALID, "%s: n_models[%zu] is above max_models", fn, g);
+  if ((st = need_ready(c, true)) != LSQR_OK) return st;
+  if (c->n > 0xFFFFFFF0ull) return fail(c, LSQR_ERR_INVALID, "%s: more than 2^32 - 16 records", fn);
+  if (!c->assign_grp) c->assign_grp.reset(new AssignGrpBufs());
+  many_job_from_ctx(c, J.pack);
+  J.pack.resident = true;
+  J.pack.n = J.n_groups;
+  J.cfg = c->cfg;
+  J.mc = c->mc;
+  J.data = c->d_data;
+  J.stride = c->stride;
+  J.n = c->n;
+  J.B = c->assign_grp.get();
+  st = dispatch(c->cfg, [&](auto tag) -> int {
+    typedef typename decltype(tag)::type M;
+    if constexpr (AssignModel<M>::value) return assign_grouped_run<M>(J);
+    else return LSQR_ERR_INVALID;
+  });
+  if (st != LSQR_OK) {
+    (void)sync_stream(c);  // nothing of this call is left in flight on its buffers
+    return fail(c, st, "%s: %s", fn, J.err[0] ? J.err : "model not in this build");
+  }
+  bsel_host_synced(c);  // (assign_grouped_run has waited for the stream)
+  return LSQR_OK;
+}
+}  // extern "C++"
+
+int lsqr_assign_grouped(lsqr_ctx *c, const int32_t *groups, size_t n_groups, int on_device, const double *params,
+                        const size_t *n_models, size_t max_models, int32_t *labels_out, double *residuals_out,
+                        uint64_t *counts_out, uint64_t *offsets_out) {
+  AssignGrpJob J;
+  J.groups = groups;
+  J.n_groups = n_groups;
+  J.on_device = on_device ? 1 : 0;
+  J.params = const_cast<double *>(params);  // (read only: no refit runs)
+  J.n_models = n_models;
+  J.max_models = max_models;
+  J.max_rounds = 0;
+  J.labels_out = labels_out;
+  J.residuals_out = residuals_out;
+  J.counts_out = counts_out;
+  J.offsets_out = offsets_out;
+  return assign_grouped_call(c, "lsqr_assign_grouped", labels_out != nullptr, J);
+}
+
+int lsqr_refine_grouped(lsqr_ctx *c, const int32_t *groups, size_t n_groups, int on_device, double *params_inout,
+                        const size_t *n_models, size_t max_models, size_t max_rounds, int32_t *labels_out,
+                        uint64_t *counts_out, uint64_t *offsets_out, lsqr_fit_info *fits, int32_t *status_out,
+                        size_t *rounds_out, int32_t *converged_out) {
+  AssignGrpJob J;
+  J.refine = true;
+  J.groups = groups;
+  J.n_groups = n_groups;
+  J.on_device = on_device ? 1 : 0;
+  J.params = params_inout;
+  J.n_models = n_models;
+  J.max_models = max_models;
+  J.max_rounds = max_rounds;
+  J.labels_out = labels_out;
+  J.counts_out = counts_out;
+  J.offsets_out = offsets_out;
+  J.fits = fits;
+  J.status_out = status_out;
+  J.rounds_out = rounds_out;
+  J.converged_out = converged_out;
+  return assign_grouped_call(c, "lsqr_refine_grouped", fits && status_out && rounds_out && converged_out, J);
 }
 
 // C(n,k) and the rank-th k-subset in the exhaustive overload's order (comb.h); host only

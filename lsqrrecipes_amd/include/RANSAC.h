@@ -421,6 +421,94 @@ class RANSAC {
     return rounds;
   }
 
+  // assignToModels with one model set per label on resident records (not in the reference), the follow-up of
+  // computeGroupedSequential: `models` is what that call leaves in `parameters` (models[g]: the models of group g;
+  // models.size() must be nGroups), `groups` and `data` are its own.  labels[i] is the model of models[groups[i]] that
+  // record i goes to, as assignToModels decides it on the records of the group alone; -1 when none agrees, for a
+  // record in no group (a negative label or one >= nGroups) and for a group without models.
+  // The estimators assignToModels sends to the device run ONE device call for all groups (lsqr_assign_grouped: the
+  // records are grouped on the device, where they already are; only the group labels go up and the labels come
+  // down).  The others, and forceHostLoop(), loop over assignToModels on the per-group vectors, gathered from the vector
+  // `data` was made from.  THAT VECTOR MUST THEN STILL BE ALIVE AND UNCHANGED (see computeGrouped).
+  static void assignToModelsGrouped(const std::vector<std::vector<std::vector<S> > > &models,
+                                    ParametersEstimator<T, S> *paramEstimator, ResidentData<T> &data,
+                                    const std::vector<int> &groups, size_t nGroups, std::vector<int> &labels) {
+    lsqr_model_cfg cfg;
+    groupedArgs(models.size(), paramEstimator, data, groups, nGroups);
+    const size_t n = nGroups, N = data.size();
+    labels.assign(N, -1);
+    if (n == 0 || N == 0) return;
+    if (!paramEstimator->deviceModel(cfg) || forceHostLoop() || !assignOnDevice(cfg, false)) {
+      std::vector<std::vector<T> > sets;
+      std::vector<std::vector<size_t> > index;
+      gatherGroups(data, groups, n, sets, index);
+      for (size_t g = 0; g < n; g++) {
+        std::vector<int> lab;
+        assignToModels(models[g], paramEstimator, sets[g], lab);
+        for (size_t q = 0; q < lab.size(); q++) labels[index[g][q]] = lab[q];
+      }
+      return;
+    }
+    size_t maxModels = 0;
+    std::vector<size_t> nModels;
+    std::vector<double> par = packGroupedModels(models, cfg, maxModels, nModels);
+    if (maxModels == 0) return;
+    std::vector<int32_t> glab(groups.begin(), groups.end()), lab(N);
+    lsqr_ctx *ctx = data.attach(cfg);
+    data.check(lsqr_assign_grouped(ctx, &glab[0], n, 0, &par[0], &nModels[0], maxModels, &lab[0], NULL, NULL, NULL));
+    labels.assign(lab.begin(), lab.end());
+  }
+
+  // refineModels with one model set per label on resident records: every group runs refineModels' loop on its own
+  // records and models and stops on its own.  -> the refits done per group; `models` and `labels` are every group's
+  // models_r and L_r; (*converged)[g] says which stop it was.  A group without records or without models runs
+  // nothing: 0 rounds, not converged.  Arguments and paths as for assignToModelsGrouped; the device path is ONE call
+  // (lsqr_refine_grouped), the host path loops over refineModels (also for the geometric sphere, as there).
+  static std::vector<size_t> refineModelsGrouped(std::vector<std::vector<std::vector<S> > > &models,
+                                                 ParametersEstimator<T, S> *paramEstimator, ResidentData<T> &data,
+                                                 const std::vector<int> &groups, size_t nGroups, size_t maxRounds,
+                                                 std::vector<int> &labels, std::vector<bool> *converged = NULL) {
+    lsqr_model_cfg cfg;
+    groupedArgs(models.size(), paramEstimator, data, groups, nGroups);
+    const size_t n = nGroups, N = data.size();
+    labels.assign(N, -1);
+    std::vector<size_t> rounds(n, 0);
+    if (converged) converged->assign(n, false);
+    if (n == 0 || N == 0) return rounds;
+    if (!paramEstimator->deviceModel(cfg) || forceHostLoop() || !assignOnDevice(cfg, true)) {
+      std::vector<std::vector<T> > sets;
+      std::vector<std::vector<size_t> > index;
+      gatherGroups(data, groups, n, sets, index);
+      for (size_t g = 0; g < n; g++) {
+        std::vector<int> lab;
+        bool conv = false;
+        rounds[g] = refineModels(models[g], paramEstimator, sets[g], maxRounds, lab, &conv);
+        if (converged) (*converged)[g] = conv;
+        for (size_t q = 0; q < lab.size(); q++) labels[index[g][q]] = lab[q];
+      }
+      return rounds;
+    }
+    size_t maxModels = 0;
+    std::vector<size_t> nModels;
+    std::vector<double> par = packGroupedModels(models, cfg, maxModels, nModels);
+    if (maxModels == 0) return rounds;
+    const size_t P = (size_t)lsqr_num_params(&cfg);
+    std::vector<int32_t> glab(groups.begin(), groups.end()), lab(N), status(n * maxModels), conv(n, 0);
+    std::vector<lsqr_fit_info> fits(n * maxModels);
+    lsqr_ctx *ctx = data.attach(cfg);
+    data.check(lsqr_refine_grouped(ctx, &glab[0], n, 0, &par[0], &nModels[0], maxModels, maxRounds, &lab[0], NULL, NULL,
+                                   &fits[0], &status[0], &rounds[0], &conv[0]));
+    for (size_t g = 0; g < n; g++) {
+      for (size_t m = 0; m < nModels[g]; m++) {
+        const double *row = &par[(g * maxModels + m) * P];
+        models[g][m].assign(row, row + P);
+      }
+      if (converged) (*converged)[g] = conv[g] != 0;
+    }
+    labels.assign(lab.begin(), lab.end());
+    return rounds;
+  }
+
   // Sequential RANSAC over many independent problems (not in the reference): problem j is data[j], and
   // computeManySequential(...)[j], parameters[j] and (*labels)[j] equal what computeSequential returns / leaves on
   // data[j] after seed(seed() + j * maxModels) -- round r of problem j walks sampler stream seed() + j * maxModels + r.
@@ -762,6 +850,48 @@ class RANSAC {
       if (models[m].size() != P) throw std::invalid_argument("lsqrRecipes::RANSAC: model vector of the wrong length");
       for (size_t j = 0; j < P; j++) par[m * P + j] = (double)models[m][j];
     }
+    return par;
+  }
+
+  // ---- assignToModelsGrouped / refineModelsGrouped ---------------------------------------------------------------
+  static void groupedArgs(size_t nSets, ParametersEstimator<T, S> *paramEstimator, ResidentData<T> &data,
+                          const std::vector<int> &groups, size_t nGroups) {
+    if (!paramEstimator) throw std::invalid_argument("lsqrRecipes::RANSAC: null estimator");
+    if (groups.size() != data.size()) throw std::invalid_argument("lsqrRecipes::RANSAC: one group label per record");
+    if (nSets != nGroups) throw std::invalid_argument("lsqrRecipes::RANSAC: one model set per group");
+  }
+
+  // the per-group vectors of the host loops (as computeGroupedSequential gathers them), and every record's own place
+  static void gatherGroups(ResidentData<T> &data, const std::vector<int> &groups, size_t n,
+                           std::vector<std::vector<T> > &sets, std::vector<std::vector<size_t> > &index) {
+    const T *host = data.hostRecords();
+    sets.assign(n, std::vector<T>());
+    index.assign(n, std::vector<size_t>());
+    for (size_t i = 0; i < data.size(); i++)
+      if (groups[i] >= 0 && (size_t)groups[i] < n) {
+        sets[(size_t)groups[i]].push_back(host[i]);
+        index[(size_t)groups[i]].push_back(i);
+      }
+  }
+
+  // the model sets as lsqr_assign_grouped's rows: row g * maxModels + m is models[g][m]; maxModels: the largest set
+  static std::vector<double> packGroupedModels(const std::vector<std::vector<std::vector<S> > > &models,
+                                               const lsqr_model_cfg &cfg, size_t &maxModels,
+                                               std::vector<size_t> &nModels) {
+    const size_t P = (size_t)lsqr_num_params(&cfg), n = models.size();
+    nModels.assign(n, 0);
+    maxModels = 0;
+    for (size_t g = 0; g < n; g++) {
+      nModels[g] = models[g].size();
+      if (nModels[g] > maxModels) maxModels = nModels[g];
+    }
+    if (maxModels > 64) throw std::invalid_argument("lsqrRecipes::RANSAC: more than 64 models");
+    std::vector<double> par(n * maxModels * P + 1, 0.0);  // (+ 1: never empty)
+    for (size_t g = 0; g < n; g++)
+      for (size_t m = 0; m < nModels[g]; m++) {
+        if (models[g][m].size() != P) throw std::invalid_argument("lsqrRecipes::RANSAC: model vector of the wrong length");
+        for (size_t j = 0; j < P; j++) par[(g * maxModels + m) * P + j] = (double)models[g][m][j];
+      }
     return par;
   }
 

@@ -14,7 +14,22 @@ parameter upload, the last assignment pass and the label copy are in both and ca
 host results (the stream has drained).  One warm call of each kind, then --reps repetitions, the three kinds
 alternating; median and min .. max are reported.  hbm_fraction = n x 24 B / round time / 8 TB/s (the records' bytes
 alone over the HBM3E peak: the label traffic, 8 B per record, is not counted).
-One JSON line per M on stdout; --out FILE also writes them to FILE."""
+One JSON line per M on stdout; --out FILE also writes them to FILE.
+
+--grouped: Context.refine_grouped (lsqr_refine_grouped: one model set per label) on the same --n plane records in three
+splits: (a) 1 group of 4 models, (b) 1 000 groups of n / 1 000 records with 4 models each, (c) 50 000 groups of
+n / 50 000 records with 3 models each.  Every group has its own planes (models / (models + 1) of its records, the rest clutter) and
+starts from the planted rows moved off by a different amount, so the groups stop at different rounds; the labels are
+shuffled over the upload.  The group labels live on the device and the timed calls ask for no labels: nothing per
+record crosses PCIe.
+ms per grouped round = (t(R2) - t(R1)) / (record-rounds done at R2 - at R1) x n, a record-round being one record of a
+group in one refit round of that group: the time of a round in which every group is still going.  The sort, the gather
+and the first pass are in both calls and cancel; grouped_call_ms is the whole call at R2 with them.
+The parent's only route, loop_call_ms: per group a host gather (from one stable sort of the labels, not timed), upload, Context.refine(max_rounds = R2) and the labels
+written back, timed on the first --loop-groups groups and scaled by n_groups / groups timed (the scaling is stated in
+the line).  For (a) refine_round_ms is Context.refine on the same records and rows: what the sort, the gather and
+the scatter cost is grouped_call_ms - refine_call_ms.  lane_share = records / (workgroups x 2048): the share of the
+pass's lanes that hold a record."""
 import argparse
 import json
 import os
@@ -85,6 +100,136 @@ def refine_rounds(ctx, rows, max_rounds):
     return int(rounds.value)
 
 
+class DeviceArray:
+    """a device allocation of the HIP runtime the library runs on, with the tensor attributes Context looks at"""
+
+    def __init__(self, host):
+        import ctypes as C
+        L.load()
+        path = [ln.split()[-1] for ln in open("/proc/self/maps") if "libamdhip64" in ln][0]
+        self._hip, self._C = C.CDLL(path), C
+        self.host = np.ascontiguousarray(host)
+        self.dtype, self.is_cuda = str(self.host.dtype), True
+        self.ptr = C.c_void_p()
+        assert self._hip.hipMalloc(C.byref(self.ptr), C.c_size_t(self.host.nbytes)) == 0
+        assert self._hip.hipMemcpy(self.ptr, C.c_void_p(self.host.ctypes.data), C.c_size_t(self.host.nbytes), 1) == 0
+
+    def free(self):
+        self._hip.hipFree(self.ptr)
+
+    def data_ptr(self):
+        return self.ptr.value
+
+    def is_contiguous(self):
+        return True
+
+    def numel(self):
+        return self.host.size
+
+
+def grouped_scene(n, n_groups, k, seed=20261020, box=1000.0, sigma=0.4):
+    """-> points (shuffled), labels, start rows (n_groups, k, 6): every group k planes of 1 / (k + 1) of its records each"""
+    g = np.random.default_rng(seed)
+    per = n // n_groups
+    nrm = g.normal(size=(n_groups, k, 3))
+    nrm /= np.linalg.norm(nrm, axis=2, keepdims=True)
+    u = np.cross(nrm, np.roll(nrm, 1, axis=2) + 0.5)
+    u /= np.linalg.norm(u, axis=2, keepdims=True)
+    v = np.cross(nrm, u)
+    a = g.uniform(-box / 2, box / 2, (n_groups, k, 3))
+    grp = np.repeat(np.arange(n_groups, dtype=np.int32), per)
+    j = np.tile(np.arange(per) % (k + 1), n_groups)  # model of the record; k: clutter
+    on = j < k
+    jj = np.minimum(j, k - 1)
+    st = g.uniform(-box, box, (grp.size, 2))
+    pts = (a[grp, jj] + st[:, :1] * u[grp, jj] + st[:, 1:] * v[grp, jj]
+           + g.normal(0.0, sigma, (grp.size, 1)) * nrm[grp, jj])
+    pts[~on] = g.uniform(-box, box, (int((~on).sum()), 3))
+    # the start: the normal turned by up to 3e-4, the point moved by up to 0.3 along the normal, per group its own size
+    size = g.uniform(0.2, 1.0, (n_groups, 1, 1))
+    n0 = nrm + 3e-4 * size * g.normal(size=nrm.shape)
+    n0 /= np.linalg.norm(n0, axis=2, keepdims=True)
+    rows = np.concatenate([n0, a + 0.3 * size * g.normal(size=(n_groups, k, 1)) * nrm], axis=2)
+    perm = g.permutation(grp.size)
+    return np.ascontiguousarray(pts[perm]), np.ascontiguousarray(grp[perm]), np.ascontiguousarray(rows)
+
+
+def grouped_main(a):
+    r1, r2 = a.rounds
+    ms = lambda v: [round(1e3 * float(f(v)), 4) for f in (np.median, np.min, np.max)]
+    lines = []
+    for name, n_groups, k in (("a", 1, 4), ("b", 1000, 4), ("c", 50000, 3)):
+        if name not in a.splits:
+            continue
+        data, grp, rows = grouped_scene(a.n, n_groups, k)
+        n = data.shape[0]
+        sizes = np.bincount(grp, minlength=n_groups)
+        order = np.argsort(grp, kind="stable")
+        first = np.concatenate([[0], np.cumsum(sizes)])
+        loop_groups = min(n_groups, a.loop_groups)
+        with Context(0) as ctx, Context(0) as one:
+            ctx.set_model(L.PLANE, 3, DELTA, L.LS_ALGEBRAIC).upload(data)
+            one.set_model(L.PLANE, 3, DELTA, L.LS_ALGEBRAIC)
+            dev = DeviceArray(grp)
+            t_lo, t_hi, t_loop, t_ref_lo, t_ref_hi, done, ref_done = [], [], [], [], [], None, None
+            for rep in range(-1, a.reps):  # rep -1 warms every kind
+                t0 = time.perf_counter()
+                lo = ctx.refine_grouped(dev, n_groups, rows, max_rounds=r1)
+                t1 = time.perf_counter()
+                hi = ctx.refine_grouped(dev, n_groups, rows, max_rounds=r2)
+                t2 = time.perf_counter()
+                if rep < a.baseline_reps:  # the parent's route on the first groups
+                    labels = np.full(n, -1, dtype=np.int32)
+                    for g in range(loop_groups):
+                        at = order[first[g]:first[g + 1]]
+                        one.upload(np.ascontiguousarray(data[at]))
+                        labels[at] = one.refine(rows[g], max_rounds=r2)["labels"]
+                t3 = time.perf_counter()
+                if n_groups == 1:
+                    ref = (refine_rounds(ctx, rows[0], r1), None)
+                    t4 = time.perf_counter()
+                    ref = (ref[0], refine_rounds(ctx, rows[0], r2))
+                    t5 = time.perf_counter()
+                    ref_done = ref
+                work = (int((sizes * lo["rounds"]).sum()), int((sizes * hi["rounds"]).sum()))
+                if work[1] <= work[0]:
+                    raise SystemExit("every group has stopped after %d rounds: nothing to time" % r1)
+                if done is not None and done != work:
+                    raise SystemExit("the rounds done differ between repetitions")
+                done = work
+                if rep >= 0:
+                    t_lo.append(t1 - t0)
+                    t_hi.append(t2 - t1)
+                    if rep < a.baseline_reps:
+                        t_loop.append((t3 - t2) * n_groups / loop_groups)
+                    if n_groups == 1:
+                        t_ref_lo.append(t4 - t3)
+                        t_ref_hi.append(t5 - t4)
+            dev.free()
+            per = [(h - l) / (done[1] - done[0]) * n for h, l in zip(t_hi, t_lo)]
+            rnd = float(np.median(per))
+            wgs = int(np.sum((sizes[sizes > 0] + 2047) // 2048))
+            row = dict(split=name, n=n, groups=n_groups, models=k, reps=a.reps, rounds=[r1, r2],
+                       record_rounds_done=list(done), rounds_hist=np.bincount(hi["rounds"]).tolist(),
+                       converged=int(hi["converged"].sum()), grouped_round_ms=ms(per), grouped_call_ms=ms(t_hi),
+                       workgroups=wgs, lane_share=round(n / (wgs * 2048.0), 4),
+                       hbm_fraction=round(n * 24 / rnd / HBM_PEAK, 4))
+            if t_loop:
+                row.update(loop_call_ms=ms(t_loop), loop_groups_timed=loop_groups,
+                           loop_scaled_by=n_groups / loop_groups, loop_reps=len(t_loop),
+                           ratio_call=round(float(np.median(t_loop) / np.median(t_hi)), 1))
+            if n_groups == 1:
+                row["refine_round_ms"] = ms([(h - l) / (ref_done[1] - ref_done[0]) for h, l in zip(t_ref_hi, t_ref_lo)])
+                row["refine_call_ms"] = ms(t_ref_hi)
+                row["refine_rounds_done"] = list(ref_done)
+            lines.append(json.dumps(row))
+            print(lines[-1], flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--n", type=int, default=10_000_000)
@@ -93,7 +238,12 @@ def main():
     ap.add_argument("--rounds", type=int, nargs=2, default=[1, 5], metavar=("R1", "R2"))
     ap.add_argument("--baseline-reps", type=int, default=3)
     ap.add_argument("--out")
+    ap.add_argument("--grouped", action="store_true", help="time Context.refine_grouped instead (see above)")
+    ap.add_argument("--splits", nargs="+", default=["a", "b", "c"], choices=["a", "b", "c"])
+    ap.add_argument("--loop-groups", type=int, default=200, help="--grouped: groups the per-group loop is timed on")
     a = ap.parse_args()
+    if a.grouped:
+        return grouped_main(a)
     data, planes = scene(a.n)
     r1, r2 = a.rounds
     lines = []
