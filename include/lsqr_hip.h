@@ -855,6 +855,11 @@ LSQR_API void lsqr_dedup_destroy(void *set);
  *                survivors of a cell, gathered through a per-wave id list in LDS (csrc/cells.h: k_scan_pairs<..., PACK>),
  *                instead of on every group of 64 that holds a survivor; 0 = per group (A/B knob).  Accepted values 0 and 1;
  *                without effect on other models and with either of the two other options 0.  Votes are identical;
+ * "scan_recheck": the exact path of the 3-D plane's packed counted scan ("scan_pack" 1 with the LDS broadcast area, the
+ *                default): a (hypothesis, cell) pair one of whose observations falls into the fp32 filter's band of
+ *                uncertainty re-evaluates the fp64 predicate 1 (default) = for the observations in the band alone, each
+ *                lane loading its own; 0 = for all observations of the cell (A/B knob).  Accepted values 0 and 1;
+ *                without effect on other kernels.  Votes are identical;
  * "dense_mask_ring": LDS tile buffers per wave of the dense final fit's fused mask + normal-equations pass: 4 (default at
  *                n = 64) = one workgroup per CU with three tiles in flight, 2 = two workgroups per CU (A/B knob);
  * "mom_chunk":   records per workgroup of the mask / moment passes in units of 256 (0 = default: 4, wide US / phantom
@@ -881,8 +886,11 @@ LSQR_API int lsqr_scan_workload(lsqr_ctx *ctx, uint32_t *bound_out, uint64_t out
  * winner, consensus set and iteration count are unchanged, an abandoned hypothesis reports its partial count.
  * out[0..5] = {1 if that path ran (0: every pair was evaluated), (observation, hypothesis) pairs handed to the scan
  * kernels, pairs of a full scan = H * N, candidates counted to the end first, hypotheses abandoned at the first
- * selection, hypotheses still alive after the last one}.  Used by bench.py to price the scan. */
-LSQR_API int lsqr_scan_work(lsqr_ctx *ctx, uint64_t out[6]);
+ * selection, hypotheses still alive after the last one}.  Used by bench.py to price the scan.
+ * out[6..7]: when the last scan went through the counted two-level scan of the 3-D plane (k_scan_pairs), the
+ * (hypothesis, cell) pairs that took the exact fp64 path because an observation fell into the fp32 filter's band, and
+ * the observations that were in the band (counted by the per-value re-check, "scan_recheck" 1, only); 0 otherwise. */
+LSQR_API int lsqr_scan_work(lsqr_ctx *ctx, uint64_t out[8]);
 
 /* The LAST persistent Levenberg-Marquardt fit of this context (option "lm_persist"; csrc/lm_persist.h):
  * out[0..7] = {mode (1 / 3: MINPACK's step on the host between granules in pinned memory, 2: on the device), resident

@@ -1080,12 +1080,31 @@ __device__ __forceinline__ void cells_filter_squares(float (&bc)[NB]) {
 // PACKED (k_scan_pairs<..., PACK>): lane b holds survivor b of a packed block, hypothesis ids[b] of the batch and not
 // b of one group: spg is the batch's first row, and the exact path -- the only reader of the index -- takes it from
 // the block's id list in LDS.
-template <class CM, int PP, bool LDSB, bool DUP = false, bool PACKED = false>
+// s_amb (k_scan_pairs; nullable): two counters of the workgroup in LDS, [0] += 1 per AMBIGUOUS pair -- a (hypothesis,
+// cell) pair with an observation in the band --, [1] += the observations the re-check found in the band (RECHECK only).
+// (LDS atomics, and one global atomic per workgroup at the kernel's end: the bench's step has ~50 000 ambiguous pairs,
+// and that many atomics on ONE global word serialise into 0.6 ms of L2 time -- measured: the step twice as long.
+// Words of the wave's own, read and written back without an atomic through a volatile pointer, were tried too: the
+// pointer stays generic, its two registers push the packed plane kernel into scratch.)
+// RECHECK (option "scan_recheck"; DUP only): an ambiguous pair re-evaluates the exact predicate for the observations IN
+// THE BAND and no others, instead of for the whole cell.  The eight d of a lane are not kept across the loop (the
+// registers are not there): the branch reads the pair's two slots again -- xs is live, slot b unchanged -- and repeats
+// the 16 packed FMAs, bit for bit.  inband = bits(d) <= band is the compare the minimum chain encodes (a negative d has
+// its sign bit set: never in the band).  Per value slot k: m = ballot(inband); m == 0 (wave-uniform) leaves in[k] alone;
+// otherwise the flagged lanes load their own observation (3 doubles, one round) and in[k] = (in[k] & ~m) | ballot(inband
+// && agree).  A value outside the band keeps the filter's decision d < 0, which is what the filter guarantees (|v32| <
+// t_in => agrees, |v32| >= t_out => does not; NaN rows: d < 0 false, agree false): every vote comes from the predicate
+// it came from before.  Filter off (band = 0xFFFFFFFF, a = 0): every d is non-negative or NaN, every bit pattern is
+// <= band, all 8 slots run for all lanes -- the whole-cell recount plus the recompute, slower than RECHECK = 0 by those
+// 16 FMAs a pair and nothing else.
+template <class CM, int PP, bool LDSB, bool DUP = false, bool PACKED = false, bool RECHECK = false>
 __device__ __forceinline__ void cells_survivors(const v2f (&xs)[PP][4], const float (&bc)[CM::NB], float *s_bc,
                                                 unsigned long long surv, const int lane,
                                                 const double *__restrict__ sorted, const size_t ns, const size_t cell,
                                                 const double *__restrict__ spg, const ModelConsts &mc,
-                                                uint32_t &accv, const uint16_t *ids = nullptr) {
+                                                uint32_t &accv, const uint16_t *ids = nullptr,
+                                                uint32_t *s_amb = nullptr) {
+  static_assert(!RECHECK || DUP, "the per-value re-check is built on the lean pair loop's slots");
   typedef typename CM::M M;
   constexpr int D = M::ND, NB = CM::NB, NV = CM::NV, SPD = M::SP, CP = 128 * PP;
   (void)D, (void)NV, (void)CP;
@@ -1164,17 +1183,51 @@ __device__ __forceinline__ void cells_survivors(const v2f (&xs)[PP][4], const fl
     if (amb) {  // some observation sits in the band: exact fp64 predicate for the whole cell
       const double *hp = spg + (size_t)b * SPD;  // wave-uniform -> scalar loads
       if constexpr (PACKED) hp = spg + (size_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)ids[b]) * SPD;
+      if (s_amb && lane == 0) atomicAdd(s_amb, 1u);
+      if constexpr (RECHECK) {
+        // the pair's slots and d again, as the loop above formed them
+        const float4 q0 = ((const float4 *)s_bc)[2 * b], q1 = ((const float4 *)s_bc)[2 * b + 1];
+        v2f fq[NV], nq;
+        fq[0].x = q0.x, fq[0].y = q0.x, fq[1].x = q0.y, fq[1].y = q0.y, fq[2].x = q1.z, fq[2].y = q1.z;
+        fq[3].x = q0.z, fq[3].y = q0.w;
+        nq.x = -q1.x, nq.y = -q1.y;
+        const uint32_t bandq = __builtin_bit_cast(uint32_t, q1.w);
+        uint32_t nrec = 0;
 #pragma unroll
-      for (int p = 0; p < PP; p++) {
-        const size_t i0 = cell * CP + p * 128 + lane, i1 = i0 + 64;
-        double r0[D], r1[D];
+        for (int p = 0; p < PP; p++) {
+          const v2f s = CM::value(xs[p], fq);
+          const v2f d = __builtin_elementwise_fma(s, s, nq);
 #pragma unroll
-        for (int d = 0; d < D; d++) {
-          r0[d] = i0 < ns ? sorted[i0 * D + d] : __builtin_nan("");
-          r1[d] = i1 < ns ? sorted[i1 * D + d] : __builtin_nan("");
+          for (int e = 0; e < 2; e++) {
+            const bool inband = __builtin_bit_cast(uint32_t, e ? d.y : d.x) <= bandq;
+            const unsigned long long m = __ballot(inband);
+            if (m == 0) continue;  // wave-uniform
+            nrec += (uint32_t)__builtin_popcountll(m);
+            bool ag = false;
+            if (inband) {
+              const size_t i = cell * CP + p * 128 + e * 64 + lane;
+              double r[D];
+#pragma unroll
+              for (int k = 0; k < D; k++) r[k] = i < ns ? sorted[i * D + k] : __builtin_nan("");
+              ag = M::agree(hp, r, mc);
+            }
+            in[2 * p + e] = (in[2 * p + e] & ~m) | __ballot(ag);
+          }
         }
-        in[2 * p] = __ballot(M::agree(hp, r0, mc));
-        in[2 * p + 1] = __ballot(M::agree(hp, r1, mc));
+        if (s_amb && lane == 0) atomicAdd(s_amb + 1, nrec);
+      } else {
+#pragma unroll
+        for (int p = 0; p < PP; p++) {
+          const size_t i0 = cell * CP + p * 128 + lane, i1 = i0 + 64;
+          double r0[D], r1[D];
+#pragma unroll
+          for (int d = 0; d < D; d++) {
+            r0[d] = i0 < ns ? sorted[i0 * D + d] : __builtin_nan("");
+            r1[d] = i1 < ns ? sorted[i1 * D + d] : __builtin_nan("");
+          }
+          in[2 * p] = __ballot(M::agree(hp, r0, mc));
+          in[2 * p + 1] = __ballot(M::agree(hp, r1, mc));
+        }
       }
     }
     uint32_t cnt = 0;
@@ -1836,12 +1889,17 @@ static_assert(pack_first(0) == 0 && pack_first(kCellPad + kBlockPad) == 0 && pac
               pack_first(kCellPad + kBlockPad + 64) == 64 && pack_first(kCellPad + 2 * kBlockPad + 64) == 64 &&
               pack_first(kCellPad + 2 * kBlockPad + 65) == 65);
 
+constexpr int kAmbSlots = 64;  // k_scan_pairs' counters of ambiguous pairs: pairs of words the workgroups spread over
 template <bool PACK = false>
 __global__ __launch_bounds__(128) void k_tile_costs(const uint8_t *__restrict__ cnt, uint32_t gstride, uint32_t H,
                                                     const uint32_t *__restrict__ h_dev, uint32_t ncells,
                                                     uint32_t *__restrict__ cost, uint32_t *__restrict__ csum,
-                                                    uint32_t *__restrict__ votes, uint32_t h_off) {
+                                                    uint32_t *__restrict__ votes, uint32_t h_off,
+                                                    unsigned long long *__restrict__ amb_zero) {
   for (uint32_t i = blockIdx.x * kChunkCells + threadIdx.x; i < H; i += gridDim.x * kChunkCells) votes[i] = 0;
+  // the first k_scan_pairs of a scan starts the scan's counters (k_scan_pairs: ambc) from zero
+  static_assert(2 * kAmbSlots == kChunkCells, "one thread per word");
+  if (amb_zero && blockIdx.x == 0) amb_zero[threadIdx.x] = 0;
   if (h_dev) {
     const uint32_t hd = *h_dev > h_off ? *h_dev - h_off : 0u;  // hypotheses [h_off, h_off + H) of the selection
     H = hd < H ? hd : H;
@@ -1926,13 +1984,20 @@ __device__ __forceinline__ uint32_t wave_incl_scan_dpp(uint32_t v) {
 // lean form with surv = the low `n` bits (level 1 repeats the counting pass bit for bit: every lane of the block
 // survives), votes go to s_cnt[id].  The next block's ids and Hyp are fetched as soon as level 1 has read this one's.
 // Which wave counts which pair differs from the group forms; votes are integer sums and do not.
-template <class CM, int PP, int BS, bool LDSB, bool PREP = false, bool LEAN = false, bool PACK = false>
+//
+// ambc: the context's counters of ambiguous pairs and band observations (cells_survivors: s_amb), kAmbSlots pairs of
+// words: a workgroup adds its two LDS counters to pair blockIdx.x % kAmbSlots when it ends.  RECHECK (option
+// "scan_recheck"; PACK with the broadcast area only): the exact path re-checks the observations in the band alone.
+template <class CM, int PP, int BS, bool LDSB, bool PREP = false, bool LEAN = false, bool PACK = false,
+          bool RECHECK = false>
 __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(PP >= 8 ? 4 : CM::MIN_WAVES, 8))) void k_scan_pairs(
     const double *__restrict__ sorted, size_t ns, const CellBox *__restrict__ boxes, uint32_t ncells,
     const double *__restrict__ sp, const float *__restrict__ rows, const float *__restrict__ spf, uint32_t H,
     ModelConsts mc, CellConsts cc, uint32_t *__restrict__ vpart, uint32_t vstride,
     const uint32_t *__restrict__ h_dev, const uint8_t *__restrict__ cnt, uint32_t gstride, const uint32_t *__restrict__ cost,
-    const uint32_t *__restrict__ csum, uint32_t nchunks, uint32_t h_off, const float4 *__restrict__ hyps) {
+    const uint32_t *__restrict__ csum, uint32_t nchunks, uint32_t h_off, const float4 *__restrict__ hyps,
+    unsigned long long *__restrict__ ambc) {
+  static_assert(!RECHECK || (PACK && LDSB), "the per-value re-check is built into the packed form");
   typedef typename CM::M M;
   constexpr int NB = CM::NB;
   constexpr int SPD = M::SP;
@@ -1948,7 +2013,14 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(PP >= 8 ? 4 
     H = hd < H ? hd : H;
   }
   extern __shared__ uint32_t s_cnt[];
+  // (the 3-D plane only: the 2-D plane's 512-record kernels sit at their 80 registers, the counter's few put them
+  // into scratch; sphere and line keep their instruction streams.  16 bytes: s_cnt and the areas behind it keep
+  // their alignment)
+  constexpr bool kCountAmb = cell_prepared<CM>() && M::ND == 3;
+  __shared__ __attribute__((aligned(16))) uint32_t s_amb_words[4];
+  uint32_t *const s_amb = kCountAmb ? s_amb_words : nullptr;
   for (uint32_t h = threadIdx.x; h < H; h += BS) s_cnt[h] = 0;
+  if (kCountAmb && threadIdx.x < 4) s_amb_words[threadIdx.x] = 0;
   __syncthreads();
   const int lane = threadIdx.x & 63;
   float *s_bc = (float *)(s_cnt + ((H + 3) & ~3u)) + (size_t)(threadIdx.x >> 6) * 512;
@@ -2170,8 +2242,8 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(PP >= 8 ? 4 
         if (more) hy = gather(block_ids(base, s_id + (par ^ 64)));
         cells_filter_squares(bc);
         uint32_t accv = 0;
-        cells_survivors<CM, PP, LDSB, LDSB, true>(xs, bc, s_bc, surv, lane, sorted, ns, (size_t)cell, sp, mc, accv,
-                                                  s_id + par);
+        cells_survivors<CM, PP, LDSB, LDSB, true, RECHECK>(xs, bc, s_bc, surv, lane, sorted, ns, (size_t)cell, sp, mc,
+                                                           accv, s_id + par, s_amb);
         if (accv) atomicAdd(&s_cnt[s_id[par + lane]], accv);
         if (!more) break;
         par ^= 64;
@@ -2222,7 +2294,7 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(PP >= 8 ? 4 
         }
         uint32_t accv = 0;
         cells_survivors<CM, PP, LDSB, LDSB>(xs, bc, s_bc, surv, lane, sorted, ns, (size_t)cell, sp + (size_t)h0 * SPD,
-                                            mc, accv);
+                                            mc, accv, nullptr, s_amb);
         if (accv) atomicAdd(&s_cnt[h], accv);
       }
       cell++;
@@ -2274,7 +2346,7 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(PP >= 8 ? 4 
       }
       uint32_t accv = 0;
       cells_survivors<CM, PP, LDSB>(xs, bc, s_bc, surv, lane, sorted, ns, (size_t)cell, sp + (size_t)h0 * SPD, mc,
-                                    accv);
+                                    accv, nullptr, s_amb);
       if (accv) atomicAdd(&s_cnt[h], accv);
     }
     cell++;
@@ -2285,6 +2357,8 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(PP >= 8 ? 4 
   // ~0.9 ms to drain, three times the counting itself).  The partial counts go out as plain coalesced stores and
   // k_votes_reduce adds them up.
   for (uint32_t i = threadIdx.x; i < H; i += BS) vpart[(size_t)blockIdx.x * vstride + i] = s_cnt[i];
+  if (kCountAmb && threadIdx.x < 2 && s_amb_words[threadIdx.x])
+    atomicAdd(&ambc[(blockIdx.x % kAmbSlots) * 2 + threadIdx.x], (unsigned long long)s_amb_words[threadIdx.x]);
 }
 
 // ---- hypothesis order of a full count (plane) -------------------------------------------------------------------

@@ -236,6 +236,10 @@ struct lsqr_ctx {
   int opt_lean = 1;               // 1: count-only counting pass, k_scan_pairs<..., LEAN> for prepared models; 0: the general forms (A/B)
   DevBuf<unsigned long long> d_pairmask;  // k_scan_pairs<..., PACK>: level 1's survivor mask per (cell, group of 64 hypotheses)
   int opt_pack = 1;               // 1: level 1 of the lean k_scan_pairs on packed blocks of 64 survivors; 0: per group (A/B)
+  int opt_recheck = 1;            // 1: the packed k_scan_pairs re-checks the band's observations alone; 0: the whole cell (A/B)
+  DevBuf<unsigned long long> d_ambcnt;  // k_scan_pairs: kAmbSlots x {ambiguous pairs, band observations} of the last scan
+  bool amb_reset = false;         // the next k_tile_costs zeroes d_ambcnt: the scan's first k_scan_pairs
+  bool amb_counted = false;       // the last scan went through k_scan_pairs: d_ambcnt holds its counts
   int opt_prepared = 1;           // 1: cell models with PREPARED read Hyp from d_hyps; 0: load() per (cell, group) (A/B)
   // bounded scan (cells.h: k_pick_*): the selected hypotheses as a compact batch
   DevBuf<uint32_t> d_sel;        // [kPilots pilots | H_cap rest]
@@ -1129,7 +1133,10 @@ int run_scan_pairs(lsqr_ctx *c, const ScanBatch &b0) {
   }
   auto costs = [&](auto kern) {
     hipLaunchKernelGGL(kern, dim3(nchunks), dim3(kChunkCells), 0, c->stream, (const uint8_t *)d_cnt, gstride, Hc,
-                       b.h_dev, c->n_cells, d_cost, d_csum, b.votes, b.h_off);  // (zeroes the batch's votes)
+                       b.h_dev, c->n_cells, d_cost, d_csum, b.votes, b.h_off,  // (zeroes the batch's votes)
+                       c->amb_reset ? c->d_ambcnt.get() : (unsigned long long *)nullptr);
+    c->amb_reset = false;
+    c->amb_counted = kPrep && M::ND == 3;  // (k_scan_pairs counts for the 3-D plane)
   };
   if (pack)
     costs(k_tile_costs<true>);
@@ -1156,7 +1163,8 @@ int run_scan_pairs(lsqr_ctx *c, const ScanBatch &b0) {
     ProfScope ps(c, KID_SCAN);
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(BS), lds, c->stream, c->d_sorted, c->n_sorted, c->d_boxes, c->n_cells,
                        b.sp, rows, b.spf, Hc, c->mc, cc, c->d_vpart, Hc, b.h_dev, (const uint8_t *)d_cnt, gstride,
-                       (const uint32_t *)d_cost, (const uint32_t *)d_csum, nchunks, b.h_off, hyps);
+                       (const uint32_t *)d_cost, (const uint32_t *)d_csum, nchunks, b.h_off, hyps,
+                       c->d_ambcnt.get());
     HIPCHK(c, hipGetLastError());
     hipLaunchKernelGGL(k_votes_reduce, dim3((Hc + 63) / 64, 48), dim3(256), 0, c->stream,
                        (const uint32_t *)c->d_vpart, Hc, (uint32_t)blocks, Hc, b.h_dev, b.votes, b.h_off);
@@ -1164,9 +1172,15 @@ int run_scan_pairs(lsqr_ctx *c, const ScanBatch &b0) {
     return LSQR_OK;
   };
   if constexpr (kPrep) {  // the lean group loop walks the prepared block
-    if (pack)
+    if (pack) {
+      // the per-value re-check reads the pair's slots of the broadcast area again; 3-D only: the 2-D plane's 512-record
+      // kernel has no register for it (12 bytes of scratch per lane with it, none without)
+      if constexpr (M::ND == 3) {
+        if (ldsb && c->opt_recheck) return launch(k_scan_pairs<CM, PP, BS, true, true, true, true, true>);
+      }
       return ldsb ? launch(k_scan_pairs<CM, PP, BS, true, true, true, true>)
                   : launch(k_scan_pairs<CM, PP, BS, false, true, true, true>);
+    }
     if (prep && c->opt_lean)
       return ldsb ? launch(k_scan_pairs<CM, PP, BS, true, true, true>) : launch(k_scan_pairs<CM, PP, BS, false, true, true>);
   }
@@ -2008,6 +2022,8 @@ int scan_exact(lsqr_ctx *c) {
 int run_scan(lsqr_ctx *c) {
   c->hyp_since_upload += c->H;
   c->ee_last = false;
+  c->amb_reset = true;
+  c->amb_counted = false;
   return dispatch(c->cfg, [&](auto tag) -> int {
     typedef typename decltype(tag)::type M;
     bool done = false;
@@ -3007,10 +3023,12 @@ int lsqr_ctx_create(int device, lsqr_ctx **out) {
             c->d_par.alloc(128) == hipSuccess && c->d_best.alloc(128) == hipSuccess &&
             c->d_lm.alloc(1) == hipSuccess && c->d_out.alloc(1) == hipSuccess &&
             c->d_counter.alloc(8) == hipSuccess &&  // CNT_* words
+            c->d_ambcnt.alloc(2 * kAmbSlots) == hipSuccess &&
             c->h_pin.alloc(1) == hipSuccess && c->h_lmres.alloc(256) == hipSuccess;
   if (ok) {
     memset(c->h_lmres, 0, sizeof(unsigned long long) * 256);
-    ok = hipMemsetAsync(c->d_counter, 0, 64, c->own_stream) == hipSuccess;
+    ok = hipMemsetAsync(c->d_counter, 0, 64, c->own_stream) == hipSuccess &&
+         hipMemsetAsync(c->d_ambcnt, 0, 2 * kAmbSlots * sizeof(unsigned long long), c->own_stream) == hipSuccess;
   }
   c->stream = c->own_stream;
   if (!ok) {
@@ -5456,6 +5474,11 @@ static int set_option_one(lsqr_ctx *c, const char *name, int value) {
     c->opt_pack = value;
     return LSQR_OK;
   }
+  if (!strcmp(name, "scan_recheck")) {  // 1 (default): an ambiguous pair of the packed k_scan_pairs re-checks the band's observations; 0: its whole cell
+    if (value != 0 && value != 1) return fail(c, LSQR_ERR_INVALID, "scan_recheck must be 0 or 1");
+    c->opt_recheck = value;
+    return LSQR_OK;
+  }
   if (!strcmp(name, "scan_axis")) {  // 1 (default): axis-sorted cells + vote bounds by rank (plane, 3-D); 0: off
     c->opt_axis = value != 0;
     return LSQR_OK;
@@ -5658,14 +5681,19 @@ int lsqr_lm_persist_info(const lsqr_ctx *c, uint64_t out[8], uint64_t *trace, ui
   return LSQR_OK;
 }
 
-int lsqr_scan_work(lsqr_ctx *c, uint64_t out[6]) {
+int lsqr_scan_work(lsqr_ctx *c, uint64_t out[8]) {
   int st = need_ready(c, true);
   if (st != LSQR_OK) return st;
   if (!out) return fail(c, LSQR_ERR_INVALID, "null argument");
   if (c->H == 0 || !c->scanned) return fail(c, LSQR_ERR_STATE, "no scanned batch");
+  unsigned long long *pin = c->h_pin->scratch_u64;
+  if (c->amb_counted)
+    HIPCHK(c, hipMemcpyAsync(pin, c->d_ambcnt, 2 * kAmbSlots * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, sync_stream(c));  // the state of the last early-exit scan has landed in h_ee
   const uint64_t all = (uint64_t)c->H * (uint64_t)c->n;
-  memset(out, 0, 6 * sizeof(uint64_t));
+  memset(out, 0, 8 * sizeof(uint64_t));
+  if (c->amb_counted)
+    for (int k = 0; k < kAmbSlots; k++) out[6] += pin[2 * k], out[7] += pin[2 * k + 1];
   out[2] = all;
   if (c->ee_last && c->h_ee && c->ee_H == c->H && c->ee_n == c->n) {
     out[0] = 1;
