@@ -6,31 +6,41 @@
 //              -1 when no m agrees, and for a record with a non-finite coordinate.  Strict '<' while m walks upwards.
 //   row_m is the scan row of the caller's parameters exactly as lsqr_mask makes one: zero-padded, then M::prepare.
 //
-//   k_assign_prepare  one lane per model: parameters -> scan rows
-//   k_assign_moments  ONE pass over the records.  A workgroup of kBlock lanes takes kAssignChunk consecutive records,
-//                     kAssignPerLane per lane, and keeps them in registers.  The M rows are read at wave-uniform
-//                     addresses (scalar loads, the scalar cache serves every wave of the chip), row by row, each row
-//                     against the lane's records.  The lane writes labels[i] (and residuals[i]); the workgroup counts
-//                     labels[i] != old[i] and the records per model (ballots, LDS integer adds, then one 64-bit integer
-//                     atomic per counter and workgroup).  WITH_MOMENTS: for every model m present in the chunk (one
-//                     64-bit presence mask per chunk) the phase-0 moment block of the records labelled m about model
-//                     m's own point (fit_origin_offset), by AccLs<M>::acc, reduced as k_many_mask_moments reduces:
-//                     the lane's records in index order, the __shfl_down tree, the four waves in index order;
-//                     -> partials[chunk][m][AccLs<M>::N].  A model absent from the chunk gets zeros.
-//   k_assign_solve    one workgroup per model: its partials summed in chunk order by one lane per moment (the four waves
-//                     stage them through LDS), then solve_small<M> about the model's own point (the body of
-//                     k_many_solve) -> SolveOut[m]; a model with at least lsqr_min_subset records and a solve that
-//                     succeeded gets its new scan row, any other keeps its row.
+// The grouped calls (assign_grouped.h: one model set per label) run the code of this file: assign_pass_chunk, the pass
+// over one chunk, is the body of k_assign_moments and of k_asg_grp_pass, which only locate their chunk; assign_refit is
+// what both solve kernels do with a model's summed moments; k_assign_prepare is launched by both drivers.
+//
+//   k_assign_prepare   one lane per row that is there: parameters -> scan rows
+//   assign_pass_chunk  ONE pass over a chunk.  A workgroup of kBlock lanes takes the chunk's (at most) kAssignChunk
+//                      consecutive records, kAssignPerLane per lane, and keeps them in registers.  The chunk's base is
+//                      folded into the (uniform) pointers, so the record indices are 32-bit and local to the chunk.
+//                      The M rows are read at wave-uniform addresses (scalar loads, the scalar cache serves every wave
+//                      of the chip), row by row, each row against the lane's records.  The lane writes labels[i] (and
+//                      residuals[i]); the workgroup counts labels[i] != old[i] and the records per model (ballots, LDS
+//                      integer adds, then one 64-bit integer atomic per counter and workgroup).  WITH_MOMENTS: for
+//                      every model m present in the chunk (one 64-bit presence mask per chunk) the phase-0 moment
+//                      block of the records labelled m about model m's own point (fit_origin_offset), by
+//                      AccLs<M>::acc, reduced as k_many_mask_moments reduces: the lane's records in index order, the
+//                      __shfl_down tree, the four waves in index order; one barrier per model, the wave sums in two
+//                      alternating LDS buffers; -> the chunk's partials [m][AccLs<M>::N].  A model absent from the
+//                      chunk gets zeros.  It must be inlined: as a called function it keeps its arrays in memory.
+//   k_assign_moments   chunk blockIdx.x of the upload: counters in the ASG_ words, partials[chunk][m][N]
+//   assign_refit       lane 0, after a solve kernel's sum: solve_small<M> about the model's own point (the body of
+//                      k_many_solve); a model with at least lsqr_min_subset records and a solve that succeeded gets
+//                      its new scan row, any other keeps its row
+//   k_assign_solve     one workgroup per model: its partials summed in chunk order by one lane per moment (the four
+//                      waves stage them through LDS), then assign_refit
 //
 // Order of the sums: kAssignChunk fixes it, as kManyPart does for the batched finish.  Nothing is summed with a
 // floating-point atomic, so two runs of one call give the same bits.
 //
 // Budget (launch bounds kBlock = 4 waves): records 8 x REC doubles, labels 8, residuals 8 doubles, one moment block
-// (AccLs<M>::N <= 55 doubles) and its origin per lane -- the 3-D models take 92 .. 112 VGPRs (4 or 5 waves per SIMD), the
-// 8-D ones 256 and more (1 or 2 waves per SIMD); no kernel spills.  LDS of the pass: two buffers of 4 x N doubles for
+// (AccLs<M>::N <= 55 doubles) and its origin per lane -- the 3-D models take 84 .. 110 VGPRs (4 or 5 waves per SIMD), the
+// 8-D ones 164 and more (1 to 3 waves per SIMD); no kernel spills.  LDS of the pass: two buffers of 4 x N doubles for
 // the wave sums (3.4 KiB at N = 55), 64 counters, the four waves' presence masks -- under 4 KiB, no limit on occupancy.
 // The 64 x 45 doubles of an 8-D plane's accumulators never exist at once: one model's block at a time lives in
-// registers.  k_assign_solve: one tile of partials, 40 .. 60 KiB of LDS, one workgroup per model.
+// registers.  k_assign_solve: one tile of partials and SolveOut, 22 .. 62 KiB of LDS, one workgroup per model
+// (DESIGN.md section 14).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -135,27 +145,35 @@ enum {
 };
 
 #if defined(__HIPCC__)
+// params: n_rows rows of M::P, row e of group e / max_models; nm (nullable: every row is there): the rows of each group
+// that are there.  A row that is not there is never read and never written.
 template <class M>
-__global__ __launch_bounds__(64) void k_assign_prepare(const double *__restrict__ params, int n_models, ModelConsts mc,
-                                                       double *__restrict__ rows) {
-  const int m = threadIdx.x;
-  if (m >= n_models) return;
-  double p[M::P], row[M::SP];
-  for (int j = 0; j < (int)M::P; j++) p[j] = params[(size_t)m * M::P + j];
-  assign_make_row<M>(p, mc, row);
-  for (int j = 0; j < (int)M::SP; j++) rows[(size_t)m * M::SP + j] = row[j];
+__global__ __launch_bounds__(kBlock) void k_assign_prepare(const double *__restrict__ params,
+                                                           const int32_t *__restrict__ nm, uint64_t n_rows,
+                                                           int max_models, ModelConsts mc, double *__restrict__ rows) {
+  for (uint64_t e = (uint64_t)blockIdx.x * kBlock + threadIdx.x; e < n_rows; e += (uint64_t)gridDim.x * kBlock) {
+    const uint64_t g = e / (uint32_t)max_models;
+    if (nm && (int)(e - g * (uint32_t)max_models) >= nm[g]) continue;
+    double p[M::P], row[M::SP];
+    for (int j = 0; j < (int)M::P; j++) p[j] = params[e * M::P + j];
+    assign_make_row<M>(p, mc, row);
+    for (int j = 0; j < (int)M::SP; j++) rows[e * M::SP + j] = row[j];
+  }
 }
 
-// data: n records, `stride` doubles apart; rows: n_models scan rows; labels: n entries; residuals, old: nullable;
-// counters: the ASG_ words, zeroed by the caller; partials (WITH_MOMENTS): [chunk][model][AccLs<M>::N]
+// The pass over ONE chunk, by one workgroup of kBlock lanes: the body of k_assign_moments and of k_asg_grp_pass.  The
+// chunk's base is in the pointers, so its records are [0, n), n <= kAssignChunk, and every index is 32-bit.
+// data: the chunk's records, `stride` doubles apart; rows: the n_models scan rows of the chunk's model set; labels /
+// residuals (nullable) / old (nullable): the chunk's n entries; changed: the word that counts labels[i] != old[i];
+// counts: one word per model; partials (WITH_MOMENTS): the chunk's [model][AccLs<M>::N]
 template <class M, bool WITH_MOMENTS>
-__global__ __launch_bounds__(kBlock) void k_assign_moments(const double *__restrict__ data, size_t stride, uint32_t n,
-                                                           const double *__restrict__ rows, int n_models, int org_off,
-                                                           ModelConsts mc, int32_t *__restrict__ labels,
-                                                           double *__restrict__ residuals,
-                                                           const int32_t *__restrict__ old,
-                                                           unsigned long long *__restrict__ counters,
-                                                           double *__restrict__ partials) {
+__device__ __forceinline__ void assign_pass_chunk(const double *__restrict__ data, size_t stride, uint32_t n,
+                                                  const double *__restrict__ rows, int n_models, int org_off,
+                                                  const ModelConsts &mc, int32_t *__restrict__ labels,
+                                                  double *__restrict__ residuals, const int32_t *__restrict__ old,
+                                                  unsigned long long *__restrict__ changed,
+                                                  unsigned long long *__restrict__ counts,
+                                                  double *__restrict__ partials) {
   typedef AccLs<M> A;
   static_assert(A::N <= 64, "one lane per moment");
   constexpr int R = kAssignPerLane, W = kBlock / 64;
@@ -164,7 +182,6 @@ __global__ __launch_bounds__(kBlock) void k_assign_moments(const double *__restr
   __shared__ uint32_t s_chg[W];
   __shared__ uint32_t s_cnt[kAssignMaxModels];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const uint64_t c0 = (uint64_t)blockIdx.x * kAssignChunk;
   const double qnan = __builtin_nan("");
   if (threadIdx.x < kAssignMaxModels) s_cnt[threadIdx.x] = 0;
 
@@ -172,9 +189,9 @@ __global__ __launch_bounds__(kBlock) void k_assign_moments(const double *__restr
   int32_t lab[R];
 #pragma unroll
   for (int j = 0; j < R; j++) {
-    const uint64_t i = c0 + (uint64_t)j * kBlock + threadIdx.x;
+    const uint32_t i = (uint32_t)j * kBlock + threadIdx.x;
     const bool in = i < n;
-    M::load(data + (in ? i : 0) * stride, mc, x[j]);
+    M::load(data + (size_t)(in ? i : 0) * stride, mc, x[j]);
     if (!in || !assign_finite<M>(x[j])) {
 #pragma unroll
       for (int d = 0; d < (int)M::REC; d++) x[j][d] = qnan;  // NaN agrees with nothing
@@ -192,7 +209,7 @@ __global__ __launch_bounds__(kBlock) void k_assign_moments(const double *__restr
   unsigned long long pres = 0;
 #pragma unroll
   for (int j = 0; j < R; j++) {
-    const uint64_t i = c0 + (uint64_t)j * kBlock + threadIdx.x;
+    const uint32_t i = (uint32_t)j * kBlock + threadIdx.x;
     if (i >= n) continue;
     labels[i] = lab[j];
     if (residuals) residuals[i] = res[j];
@@ -254,34 +271,71 @@ __global__ __launch_bounds__(kBlock) void k_assign_moments(const double *__restr
       if (threadIdx.x < A::N) {
         double t = 0.0;
         for (int w = 0; w < W; w++) t += buf[w][threadIdx.x];
-        partials[((size_t)blockIdx.x * n_models + m) * A::N + threadIdx.x] = t;
+        partials[(size_t)m * A::N + threadIdx.x] = t;
       }
     }
   }
   if constexpr (WITH_MOMENTS) {
     for (uint32_t e = threadIdx.x; e < (uint32_t)n_models * A::N; e += kBlock)
-      if (!((present >> (e / A::N)) & 1ull)) partials[(size_t)blockIdx.x * n_models * A::N + e] = 0.0;
+      if (!((present >> (e / A::N)) & 1ull)) partials[e] = 0.0;
   }
   __syncthreads();
   if ((int)threadIdx.x < n_models && s_cnt[threadIdx.x])
-    atomicAdd(&counters[ASG_COUNT + threadIdx.x], (unsigned long long)s_cnt[threadIdx.x]);
+    atomicAdd(&counts[threadIdx.x], (unsigned long long)s_cnt[threadIdx.x]);
   if (threadIdx.x == 0) {
     unsigned long long t = 0;
     for (int w = 0; w < W; w++) t += s_chg[w];
-    if (t) atomicAdd(&counters[ASG_CHANGED], t);
+    if (t) atomicAdd(changed, t);
   }
 }
 
-// one workgroup per model m: the partials of its `chunks` chunks summed in chunk order, then the solve of k_solve
-// about the model's own point.  A strictly serial sum of thousands of partials is bound by memory latency if one lane
-// loads what it adds, so the four waves stage tiles of kTile chunks through LDS -- every lane a few loads, all in
-// flight at once, the next tile's issued before this one is summed -- and lane k of wave 0 adds column k of the tile
-// in chunk order.  rows[m] becomes the new model's scan row when the model had at least M::K records and the solve gave
-// a result; counters[ASG_USED + m], counters[ASG_OK + m] and out[m] say what happened.
+// The least waves per SIMD a pass kernel is compiled for.  Left alone, the scheduler settles the 4-D plane's pass with
+// moments on 162 VGPRs (3 waves) where 126 do without scratch; no other instantiation is told anything
+template <class M, bool WITH_MOMENTS> constexpr int kAssignPassWaves = 1;
+template <> constexpr int kAssignPassWaves<PlaneModelN<4>, true> = 4;
+
+// chunk blockIdx.x of the context's n records.  data: `stride` doubles apart; labels: n entries; residuals, old:
+// nullable; counters: the ASG_ words, zeroed by the caller; partials (WITH_MOMENTS): [chunk][model][AccLs<M>::N]
+template <class M, bool WITH_MOMENTS>
+__global__ __launch_bounds__(kBlock, (kAssignPassWaves<M, WITH_MOMENTS>)) void k_assign_moments(
+    const double *__restrict__ data, size_t stride, uint32_t n, const double *__restrict__ rows, int n_models,
+    int org_off, ModelConsts mc, int32_t *__restrict__ labels, double *__restrict__ residuals,
+    const int32_t *__restrict__ old, unsigned long long *__restrict__ counters, double *__restrict__ partials) {
+  const uint32_t c0 = blockIdx.x * kAssignChunk, left = n - c0;  // (c0 < n: no wrap)
+  if constexpr (WITH_MOMENTS) partials += (size_t)blockIdx.x * n_models * AccLs<M>::N;
+  assign_pass_chunk<M, WITH_MOMENTS>(data + (size_t)c0 * stride, stride, left < kAssignChunk ? left : kAssignChunk, rows,
+                                     n_models, org_off, mc, labels + c0, residuals ? residuals + c0 : nullptr,
+                                     old ? old + c0 : nullptr, counters + ASG_CHANGED, counters + ASG_COUNT, partials);
+}
+
+// What lane 0 of a solve kernel does with a model's summed moments: the refit about the model's own point (the body of
+// k_many_solve), or nothing.  row_m becomes the new model's scan row, and the answer is true, when the model had at
+// least M::K records (cnt) and the solve gave a result; any other model keeps its row.
+template <class M>
+__device__ __forceinline__ bool assign_refit(const double *mom, double *row_m, unsigned long long cnt, int org_off,
+                                             const ModelConsts &mc, double *ws, SolveOut *so) {
+  if (cnt < (unsigned long long)M::K) return false;
+  constexpr int NC = M::P > M::REC ? M::P : M::REC;
+  double org[NC];
+  for (int j = 0; j < NC; j++) org[j] = j < (int)M::ND ? row_m[org_off + j] : 0.0;
+  solve_small<M>(mom, org, mc, ws, so);
+  if (!so->ok) return false;
+  double p[M::P], row[M::SP];
+  for (int j = 0; j < (int)M::P; j++) p[j] = so->params[j];
+  assign_make_row<M>(p, mc, row);
+  for (int j = 0; j < (int)M::SP; j++) row_m[j] = row[j];
+  return true;
+}
+
+// one workgroup per model m: the partials of its `chunks` chunks summed in chunk order, then assign_refit.  A strictly
+// serial sum of thousands of partials is bound by memory latency if one lane loads what it adds, so the four waves
+// stage tiles of kTile chunks through LDS -- every lane a few loads, all in flight at once, the next tile's issued
+// before this one is summed -- and lane k of wave 0 adds column k of the tile in chunk order.
+// counters[ASG_USED + m] and counters[ASG_OK + m] say what happened.
 template <class M>
 __global__ __launch_bounds__(kBlock) void k_assign_solve(const double *__restrict__ partials, uint32_t chunks,
                                                          int n_models, int org_off, ModelConsts mc, double *rows,
-                                                         unsigned long long *counters, SolveOut *__restrict__ out) {
+                                                         unsigned long long *counters) {
   constexpr int N = M::NMOM;
   constexpr int kTile = N <= 16 ? 512 : 128;            // chunks per tile: 40 KiB of LDS at N = 10, 55 KiB at N = 55
   constexpr int E = (kTile * N + kBlock - 1) / kBlock;  // elements of a tile per lane
@@ -289,6 +343,7 @@ __global__ __launch_bounds__(kBlock) void k_assign_solve(const double *__restric
   __shared__ double s_t[kTile * N];
   __shared__ double mom[MOM_MAX];
   __shared__ double ws[M::NMOM > 40 ? 512 : 8];
+  __shared__ SolveOut so;
   const int m = blockIdx.x, k = threadIdx.x;
   const double *src = partials + (size_t)m * N;
   const size_t qs = (size_t)n_models * N;  // from one chunk's block of model m to the next chunk's
@@ -320,21 +375,7 @@ __global__ __launch_bounds__(kBlock) void k_assign_solve(const double *__restric
   if (k != 0) return;
   const unsigned long long cnt = counters[ASG_COUNT + m];
   counters[ASG_USED + m] = cnt;
-  counters[ASG_OK + m] = 0;
-  SolveOut *o = out + m;
-  o->ok = o->n_params = o->lm_info = o->lm_nfev = o->cont = o->pad = 0;
-  o->cost = 0.0;
-  if (cnt < (unsigned long long)M::K) return;
-  constexpr int NC = M::P > M::REC ? M::P : M::REC;
-  double org[NC];
-  for (int j = 0; j < NC; j++) org[j] = j < (int)M::ND ? rows[(size_t)m * M::SP + org_off + j] : 0.0;
-  solve_small<M>(mom, org, mc, ws, o);
-  if (!o->ok) return;
-  double p[M::P], row[M::SP];
-  for (int j = 0; j < (int)M::P; j++) p[j] = o->params[j];
-  assign_make_row<M>(p, mc, row);
-  for (int j = 0; j < (int)M::SP; j++) rows[(size_t)m * M::SP + j] = row[j];
-  counters[ASG_OK + m] = 1;
+  counters[ASG_OK + m] = assign_refit<M>(mom, rows + (size_t)m * M::SP, cnt, org_off, mc, ws, &so) ? 1 : 0;
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------
@@ -342,7 +383,6 @@ struct AssignBufs {  // owned by the context, grown on demand
   DevBuf<double> d_par, d_rows, d_partials, d_res;
   DevBuf<int32_t> d_labels[2];
   DevBuf<unsigned long long> d_cnt;
-  DevBuf<SolveOut> d_out;
   PinBuf<char> h_pin;
 };
 
@@ -368,15 +408,19 @@ struct AssignJob {
   char err[256] = {0};
 };
 
-#define ASGCHK(call)                                                                                 \
-  do {                                                                                               \
-    hipError_t e_ = (call);                                                                          \
-    if (e_ != hipSuccess) {                                                                          \
-      snprintf(J.err, sizeof J.err, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, \
-               __LINE__);                                                                            \
-      return LSQR_ERR_HIP;                                                                           \
-    }                                                                                                \
-  } while (0)
+// lsqr_refine's and lsqr_refine_grouped's answer for one model of a set that ran `rounds` refit rounds; okf, used: the
+// ASG_OK and ASG_USED words of its last refit
+template <class M>
+void assign_fit_out(size_t rounds, unsigned long long okf, unsigned long long used, int32_t *status,
+                    lsqr_fit_info *fit) {
+  const bool ok = rounds == 0 || okf != 0;
+  *status = ok ? LSQR_OK : LSQR_EMPTY;
+  memset(fit, 0, sizeof *fit);
+  if (rounds > 0) {
+    fit->n_params = ok ? (int32_t)M::P : 0;
+    fit->n_used = used;
+  }
+}
 
 // lsqr_refine's loop (lsqr_assign: max_rounds == 0).  Round r: one pass -- labels L_r and, unless it is the last
 // round allowed, the moments of L_r --, the 8-byte changed-counter (with the counts: one copy) to the host, one solve
@@ -391,25 +435,25 @@ int assign_run(AssignJob &J) {
   const bool direct = !refine && J.on_device && J.labels_out;
   const size_t pin_bytes = sizeof(double) * kAssignMaxModels * 16 + sizeof(unsigned long long) * ASG_WORDS;
   static_assert(M::SP <= 16 && M::P <= 16, "pinned staging of the rows");
-  if (!B.h_pin.get()) ASGCHK(B.h_pin.alloc(pin_bytes));
-  ASGCHK(many_grow(B.d_par, (size_t)kAssignMaxModels * 16));
-  ASGCHK(many_grow(B.d_rows, (size_t)kAssignMaxModels * 16));
-  ASGCHK(many_grow(B.d_cnt, (size_t)ASG_WORDS));
-  if (!direct) ASGCHK(many_grow(B.d_labels[0], (size_t)n));
-  if (J.residuals_out && !J.on_device) ASGCHK(many_grow(B.d_res, (size_t)n));
+  if (!B.h_pin.get()) MANYCHK(B.h_pin.alloc(pin_bytes));
+  MANYCHK(many_grow(B.d_par, (size_t)kAssignMaxModels * 16));
+  MANYCHK(many_grow(B.d_rows, (size_t)kAssignMaxModels * 16));
+  MANYCHK(many_grow(B.d_cnt, (size_t)ASG_WORDS));
+  if (!direct) MANYCHK(many_grow(B.d_labels[0], (size_t)n));
+  if (J.residuals_out && !J.on_device) MANYCHK(many_grow(B.d_res, (size_t)n));
   if (refine) {
-    ASGCHK(many_grow(B.d_labels[1], (size_t)n));
-    ASGCHK(many_grow(B.d_partials, (size_t)chunks * nm * M::NMOM));
-    ASGCHK(many_grow(B.d_out, (size_t)kAssignMaxModels));
+    MANYCHK(many_grow(B.d_labels[1], (size_t)n));
+    MANYCHK(many_grow(B.d_partials, (size_t)chunks * nm * M::NMOM));
   }
   double *h_rows = (double *)B.h_pin.get();
   unsigned long long *h_cnt = (unsigned long long *)(B.h_pin.get() + sizeof(double) * kAssignMaxModels * 16);
 
   memcpy(h_rows, J.params, sizeof(double) * (size_t)nm * M::P);
-  ASGCHK(hipMemcpyAsync(B.d_par, h_rows, sizeof(double) * (size_t)nm * M::P, hipMemcpyHostToDevice, J.stream));
-  hipLaunchKernelGGL((k_assign_prepare<M>), dim3(1), dim3(64), 0, J.stream, B.d_par, nm, J.mc, B.d_rows);
-  ASGCHK(hipGetLastError());
-  ASGCHK(hipMemsetAsync(B.d_cnt, 0, sizeof(unsigned long long) * ASG_WORDS, J.stream));
+  MANYCHK(hipMemcpyAsync(B.d_par, h_rows, sizeof(double) * (size_t)nm * M::P, hipMemcpyHostToDevice, J.stream));
+  hipLaunchKernelGGL((k_assign_prepare<M>), dim3(1), dim3(kBlock), 0, J.stream, B.d_par, nullptr, (uint64_t)nm, nm, J.mc,
+                     B.d_rows);  // one group, every row there
+  MANYCHK(hipGetLastError());
+  MANYCHK(hipMemsetAsync(B.d_cnt, 0, sizeof(unsigned long long) * ASG_WORDS, J.stream));
 
   int cur = 0;
   size_t r = 0;
@@ -420,41 +464,41 @@ int assign_run(AssignJob &J) {
     double *res = !J.residuals_out ? nullptr : J.on_device ? J.residuals_out : B.d_res.get();
     const int32_t *old = r > 0 ? B.d_labels[cur ^ 1].get() : nullptr;
     if (r > 0)
-      ASGCHK(hipMemsetAsync(B.d_cnt, 0, sizeof(unsigned long long) * (ASG_COUNT + kAssignMaxModels), J.stream));
+      MANYCHK(hipMemsetAsync(B.d_cnt, 0, sizeof(unsigned long long) * (ASG_COUNT + kAssignMaxModels), J.stream));
     if (last)
       hipLaunchKernelGGL((k_assign_moments<M, false>), dim3(chunks), dim3(kBlock), 0, J.stream, J.data, J.stride, n,
                          B.d_rows, nm, org_off, J.mc, lab, res, old, B.d_cnt, nullptr);
     else
       hipLaunchKernelGGL((k_assign_moments<M, true>), dim3(chunks), dim3(kBlock), 0, J.stream, J.data, J.stride, n,
                          B.d_rows, nm, org_off, J.mc, lab, res, old, B.d_cnt, B.d_partials);
-    ASGCHK(hipGetLastError());
-    ASGCHK(hipMemcpyAsync(h_cnt, B.d_cnt, sizeof(unsigned long long) * (ASG_COUNT + kAssignMaxModels),
+    MANYCHK(hipGetLastError());
+    MANYCHK(hipMemcpyAsync(h_cnt, B.d_cnt, sizeof(unsigned long long) * (ASG_COUNT + kAssignMaxModels),
                           hipMemcpyDeviceToHost, J.stream));
-    ASGCHK(hipStreamSynchronize(J.stream));
+    MANYCHK(hipStreamSynchronize(J.stream));
     if (r > 0 && h_cnt[ASG_CHANGED] == 0) {
       converged = true;
       break;
     }
     if (last) break;
     hipLaunchKernelGGL((k_assign_solve<M>), dim3(nm), dim3(kBlock), 0, J.stream, B.d_partials, chunks, nm, org_off, J.mc,
-                       B.d_rows, B.d_cnt, B.d_out);
-    ASGCHK(hipGetLastError());
+                       B.d_rows, B.d_cnt);
+    MANYCHK(hipGetLastError());
     r++;
     cur ^= 1;
   }
 
   // results: the rows and what the last refit did, then the labels of the last pass
   if (r > 0) {
-    ASGCHK(hipMemcpyAsync(h_rows, B.d_rows, sizeof(double) * (size_t)nm * M::SP, hipMemcpyDeviceToHost, J.stream));
-    ASGCHK(hipMemcpyAsync(h_cnt + ASG_USED, B.d_cnt + ASG_USED, sizeof(unsigned long long) * 2 * kAssignMaxModels,
+    MANYCHK(hipMemcpyAsync(h_rows, B.d_rows, sizeof(double) * (size_t)nm * M::SP, hipMemcpyDeviceToHost, J.stream));
+    MANYCHK(hipMemcpyAsync(h_cnt + ASG_USED, B.d_cnt + ASG_USED, sizeof(unsigned long long) * 2 * kAssignMaxModels,
                           hipMemcpyDeviceToHost, J.stream));
   }
   if (J.labels_out && !direct)
-    ASGCHK(hipMemcpyAsync(J.labels_out, B.d_labels[cur], sizeof(int32_t) * (size_t)n,
+    MANYCHK(hipMemcpyAsync(J.labels_out, B.d_labels[cur], sizeof(int32_t) * (size_t)n,
                           J.on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, J.stream));
   if (J.residuals_out && !J.on_device)
-    ASGCHK(hipMemcpyAsync(J.residuals_out, B.d_res, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, J.stream));
-  ASGCHK(hipStreamSynchronize(J.stream));
+    MANYCHK(hipMemcpyAsync(J.residuals_out, B.d_res, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, J.stream));
+  MANYCHK(hipStreamSynchronize(J.stream));
   if (r > 0)
     for (int m = 0; m < nm; m++)
       for (int j = 0; j < (int)M::P; j++) J.params[(size_t)m * M::P + j] = h_rows[(size_t)m * M::SP + j];
@@ -463,22 +507,13 @@ int assign_run(AssignJob &J) {
     for (int m = 0; m < nm; m++) sum += (J.counts_out[m] = h_cnt[ASG_COUNT + m]);
     J.counts_out[nm] = (uint64_t)n - sum;
   }
-  if (J.fits) {  // lsqr_refine
-    for (int m = 0; m < nm; m++) {
-      const bool ok = r == 0 || h_cnt[ASG_OK + m] != 0;
-      J.status_out[m] = ok ? LSQR_OK : LSQR_EMPTY;
-      memset(&J.fits[m], 0, sizeof(lsqr_fit_info));
-      if (r > 0) {
-        J.fits[m].n_params = ok ? (int32_t)M::P : 0;
-        J.fits[m].n_used = h_cnt[ASG_USED + m];
-      }
-    }
-  }
+  if (J.fits)  // lsqr_refine
+    for (int m = 0; m < nm; m++)
+      assign_fit_out<M>(r, h_cnt[ASG_OK + m], h_cnt[ASG_USED + m], &J.status_out[m], &J.fits[m]);
   J.rounds = r;
   J.converged = converged ? 1 : 0;
   return LSQR_OK;
 }
-#undef ASGCHK
 #endif  // __HIPCC__
 
 }  // namespace lsqr

@@ -5,21 +5,20 @@
 //
 //   (grouped.h)           grouped_pack, once per call: keys, the stable radix sort, offsets, its one synchronisation, the
 //                         gather into the packed buffer.  Every round reads that copy (stride = the record's doubles).
-//   k_asg_grp_prepare     one lane per (group, model) row that is there: parameters -> scan row (k_assign_prepare's body)
+//   (assign.h)            k_assign_prepare with the groups' model counts: one lane per (group, model) row that is there
 //   k_asg_grp_pass        one workgroup per (group, chunk): chunk q of group g is the group's packed records
 //                         [q * kAssignChunk, (q + 1) * kAssignChunk).  The host lays the (group, chunk) list out from the
-//                         offsets.  Inside a workgroup the group is uniform, so the rows of the group are read at
-//                         wave-uniform addresses as k_assign_moments reads them; the lane's records in index order, the
-//                         presence mask, the per-model moment phase, the one-barrier double LDS buffer and the integer
-//                         atomics are k_assign_moments', with the changed-count and the counts per group and the
-//                         partials at gbase[g] + q * n_models[g].  A workgroup whose group has stopped exits at once.
+//                         offsets.  The kernel finds its chunk -- the group is uniform inside a workgroup, so the group's
+//                         rows are still read at wave-uniform addresses -- and runs assign_pass_chunk (assign.h) on it,
+//                         with the changed-count and the counts per group and the partials at gbase[g] + q *
+//                         n_models[g].  A workgroup whose group has stopped exits at once.
 //   k_asg_grp_decide      one lane per group after each pass: converged (r > 0 and nothing changed), stopped at
 //                         max_rounds, or going on; rounds[g]; the groups still going summed into the ONE word the host
 //                         reads per round.
 //   k_asg_grp_solve       one wave per (group, model) of a group still going: the partials of the group's chunks summed
 //                         in chunk order by one lane per moment (sixteen loads in flight, added in order), then
-//                         solve_small<M> about the model's own point and k_assign_solve's refit-or-keep decision.  No
-//                         tile staging: 1.3 KiB of LDS (the moment block, the small workspace, SolveOut).
+//                         assign_refit (assign.h), as k_assign_solve.  No tile staging: 1.3 KiB of LDS (the moment
+//                         block, the small workspace, SolveOut).
 //   (grouped.h)           k_grp_scatter_labels / k_grp_scatter_f64: packed order -> upload order, every entry once.
 //
 // Order of the sums, per group: the lane's records j * kBlock + tid in index order, the __shfl_down tree, the four
@@ -54,158 +53,25 @@ struct AsgGrpTab {  // the call's per-group tables, on the device
   uint32_t *state;          // 0: going; 1: stopped
 };
 
-template <class M>
-__global__ __launch_bounds__(kBlock) void k_asg_grp_prepare(const double *__restrict__ params,
-                                                            const int32_t *__restrict__ nm, uint64_t n_rows,
-                                                            int max_models, ModelConsts mc, double *__restrict__ rows) {
-  for (uint64_t e = (uint64_t)blockIdx.x * kBlock + threadIdx.x; e < n_rows; e += (uint64_t)gridDim.x * kBlock) {
-    const uint64_t g = e / (uint32_t)max_models;
-    if ((int)(e - g * (uint32_t)max_models) >= nm[g]) continue;  // a row that is not there: never read, never written
-    double p[M::P], row[M::SP];
-    for (int j = 0; j < (int)M::P; j++) p[j] = params[e * M::P + j];
-    assign_make_row<M>(p, mc, row);
-    for (int j = 0; j < (int)M::SP; j++) rows[e * M::SP + j] = row[j];
-  }
-}
-
 // data: the packed records, `stride` doubles apart; wgs: (group, chunk) per workgroup; rows: n_groups * max_models scan
 // rows; labels / residuals (nullable) / old (nullable): packed order; changed: one word per group; counts: max_models
 // words per group, zero for every group still going; partials (WITH_MOMENTS): [gbase[g] + q * nm[g] + m][AccLs<M>::N]
 template <class M, bool WITH_MOMENTS>
-__global__ __launch_bounds__(kBlock) void k_asg_grp_pass(const double *__restrict__ data, size_t stride,
-                                                         const uint2 *__restrict__ wgs, AsgGrpTab T,
-                                                         const double *__restrict__ rows, int max_models, int org_off,
-                                                         ModelConsts mc, int32_t *__restrict__ labels,
-                                                         double *__restrict__ residuals,
-                                                         const int32_t *__restrict__ old,
-                                                         unsigned long long *__restrict__ changed,
-                                                         unsigned long long *__restrict__ counts,
-                                                         double *__restrict__ partials) {
-  typedef AccLs<M> A;
-  static_assert(A::N <= 64, "one lane per moment");
-  constexpr int R = kAssignPerLane, W = kBlock / 64;
-  __shared__ double s_m[2][W][WITH_MOMENTS ? (int)A::N : 1];
-  __shared__ unsigned long long s_p[W];
-  __shared__ uint32_t s_chg[W];
-  __shared__ uint32_t s_cnt[kAssignMaxModels];
+__global__ __launch_bounds__(kBlock, (kAssignPassWaves<M, WITH_MOMENTS>)) void k_asg_grp_pass(
+    const double *__restrict__ data, size_t stride, const uint2 *__restrict__ wgs, AsgGrpTab T,
+    const double *__restrict__ rows, int max_models, int org_off, ModelConsts mc, int32_t *__restrict__ labels,
+    double *__restrict__ residuals, const int32_t *__restrict__ old, unsigned long long *__restrict__ changed,
+    unsigned long long *__restrict__ counts, double *__restrict__ partials) {
   const uint2 wg = wgs[blockIdx.x];  // workgroup-uniform: the group, its chunk
   const uint32_t g = wg.x;
   if (T.state[g]) return;
   const int n_models = T.nm[g];
-  // the chunk's records are [0, n) from here on: 32-bit indices, the chunk's base in the (uniform) pointers
   const uint64_t c0 = T.offsets[g] + (uint64_t)wg.y * kAssignChunk, left = T.offsets[g + 1] - c0;
-  const uint32_t n = left < kAssignChunk ? (uint32_t)left : kAssignChunk;
-  data += c0 * stride;
-  labels += c0;
-  if (residuals) residuals += c0;
-  if (old) old += c0;
-  rows += (size_t)g * max_models * M::SP;
-  if constexpr (WITH_MOMENTS) partials += (T.gbase[g] + (uint64_t)wg.y * n_models) * A::N;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const double qnan = __builtin_nan("");
-  if (threadIdx.x < kAssignMaxModels) s_cnt[threadIdx.x] = 0;
-
-  double x[R][M::REC], res[R];
-  int32_t lab[R];
-#pragma unroll
-  for (int j = 0; j < R; j++) {
-    const uint32_t i = (uint32_t)j * kBlock + threadIdx.x;
-    const bool in = i < n;
-    M::load(data + (size_t)(in ? i : 0) * stride, mc, x[j]);
-    if (!in || !assign_finite<M>(x[j])) {
-#pragma unroll
-      for (int d = 0; d < (int)M::REC; d++) x[j][d] = qnan;  // NaN agrees with nothing
-    }
-    lab[j] = -1;
-    res[j] = __builtin_inf();
-  }
-  for (int m = 0; m < n_models; m++) {
-    const double *row = rows + (size_t)m * M::SP;  // wave-uniform: scalar loads
-#pragma unroll
-    for (int j = 0; j < R; j++) assign_step<M>(row, m, x[j], mc, lab[j], res[j]);
-  }
-
-  uint32_t chg = 0;
-  unsigned long long pres = 0;
-#pragma unroll
-  for (int j = 0; j < R; j++) {
-    const uint32_t i = (uint32_t)j * kBlock + threadIdx.x;
-    if (i >= n) continue;
-    labels[i] = lab[j];
-    if (residuals) residuals[i] = res[j];
-    if (old) chg += old[i] != lab[j] ? 1u : 0u;
-    if (lab[j] >= 0) pres |= 1ull << lab[j];
-  }
-  for (int o = 32; o > 0; o >>= 1) {
-    chg += __shfl_xor(chg, o);
-    pres |= __shfl_xor(pres, o);
-  }
-  if (lane == 0) {
-    s_p[wave] = pres;
-    s_chg[wave] = chg;
-  }
-  __syncthreads();
-  unsigned long long all = 0;
-  for (int w = 0; w < W; w++) all |= s_p[w];
-  const unsigned long long present = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(all >> 32)) << 32) |
-                                     __builtin_amdgcn_readfirstlane((uint32_t)all);
-  const unsigned long long mine = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(pres >> 32)) << 32) |
-                                  __builtin_amdgcn_readfirstlane((uint32_t)pres);
-
-  int it = 0;
-  for (unsigned long long rest = present; rest; rest &= rest - 1, it++) {
-    const int m = __builtin_ctzll(rest);
-    const bool here = (mine >> m) & 1ull;  // this wave holds records of model m
-    if (here) {
-      uint32_t cnt = 0;
-#pragma unroll
-      for (int j = 0; j < R; j++) cnt += (uint32_t)__popcll(__ballot(lab[j] == m));
-      if (lane == 0) atomicAdd(&s_cnt[m], cnt);
-    }
-    if constexpr (WITH_MOMENTS) {
-      double(*buf)[A::N] = s_m[it & 1];
-      if (here) {
-        constexpr int NC = M::P > M::REC ? M::P : M::REC;
-        double cv[NC], acc[A::N];
-        const double *org = rows + (size_t)m * M::SP + org_off;
-#pragma unroll
-        for (int k = 0; k < NC; k++) cv[k] = k < (int)M::ND ? org[k] : 0.0;
-#pragma unroll
-        for (int k = 0; k < (int)A::N; k++) acc[k] = 0.0;
-#pragma unroll
-        for (int j = 0; j < R; j++)
-          if (lab[j] == m) A::acc(x[j], cv, acc);
-#pragma unroll
-        for (int k = 0; k < (int)A::N; k++) {
-          double v = acc[k];
-          for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-          if (lane == 0) buf[wave][k] = v;
-        }
-      } else if (lane < (int)A::N) {
-        buf[wave][lane] = 0.0;
-      }
-      // one barrier per model, as in k_assign_moments: the buffer written two models on is this one again, and no
-      // wave gets there before every wave has passed the barrier in between
-      __syncthreads();
-      if (threadIdx.x < A::N) {
-        double t = 0.0;
-        for (int w = 0; w < W; w++) t += buf[w][threadIdx.x];
-        partials[(size_t)m * A::N + threadIdx.x] = t;
-      }
-    }
-  }
-  if constexpr (WITH_MOMENTS) {
-    for (uint32_t e = threadIdx.x; e < (uint32_t)n_models * A::N; e += kBlock)
-      if (!((present >> (e / A::N)) & 1ull)) partials[e] = 0.0;
-  }
-  __syncthreads();
-  if ((int)threadIdx.x < n_models && s_cnt[threadIdx.x])
-    atomicAdd(&counts[(size_t)g * max_models + threadIdx.x], (unsigned long long)s_cnt[threadIdx.x]);
-  if (threadIdx.x == 0) {
-    unsigned long long t = 0;
-    for (int w = 0; w < W; w++) t += s_chg[w];
-    if (t) atomicAdd(&changed[g], t);
-  }
+  if constexpr (WITH_MOMENTS) partials += (T.gbase[g] + (uint64_t)wg.y * n_models) * AccLs<M>::N;
+  assign_pass_chunk<M, WITH_MOMENTS>(data + c0 * stride, stride, left < kAssignChunk ? (uint32_t)left : kAssignChunk,
+                                     rows + (size_t)g * max_models * M::SP, n_models, org_off, mc, labels + c0,
+                                     residuals ? residuals + c0 : nullptr, old ? old + c0 : nullptr, changed + g,
+                                     counts + (size_t)g * max_models, partials);
 }
 
 // after pass r (last: r == max_rounds): every group still going converges, stops, or goes on with a zeroed
@@ -274,19 +140,7 @@ __global__ __launch_bounds__(64) void k_asg_grp_solve(const uint2 *__restrict__ 
   const unsigned long long cnt = counts[e];
   counts[e] = 0;
   used[e] = cnt;
-  okf[e] = 0;
-  if (cnt < (unsigned long long)M::K) return;
-  constexpr int NC = M::P > M::REC ? M::P : M::REC;
-  double org[NC];
-  double *row_m = rows + e * M::SP;
-  for (int j = 0; j < NC; j++) org[j] = j < (int)M::ND ? row_m[org_off + j] : 0.0;
-  solve_small<M>(mom, org, mc, ws, &so);
-  if (!so.ok) return;
-  double p[M::P], row[M::SP];
-  for (int j = 0; j < (int)M::P; j++) p[j] = so.params[j];
-  assign_make_row<M>(p, mc, row);
-  for (int j = 0; j < (int)M::SP; j++) row_m[j] = row[j];
-  okf[e] = 1;
+  okf[e] = assign_refit<M>(mom, rows + e * M::SP, cnt, org_off, mc, ws, &so) ? 1 : 0;
 }
 
 __global__ __launch_bounds__(kBlock) void k_asg_grp_fill(double *__restrict__ p, uint64_t n, double v) {
@@ -327,16 +181,6 @@ struct AssignGrpJob {
   int32_t *converged_out = nullptr;
   char err[256] = {0};
 };
-
-#define AGCHK(call)                                                                                  \
-  do {                                                                                               \
-    hipError_t e_ = (call);                                                                          \
-    if (e_ != hipSuccess) {                                                                          \
-      snprintf(J.err, sizeof J.err, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, \
-               __LINE__);                                                                            \
-      return LSQR_ERR_HIP;                                                                           \
-    }                                                                                                \
-  } while (0)
 
 inline size_t asg_grp_up8(size_t b) { return (b + 7) & ~(size_t)7; }
 
@@ -388,7 +232,7 @@ int assign_grouped_run(AssignGrpJob &J) {
                u_state = u_nm + asg_grp_up8(sizeof(int32_t) * NG), v_going = u_state + asg_grp_up8(sizeof(uint32_t) * NG),
                v_rows = v_going + sizeof(ull), v_cnt = v_rows + sizeof(double) * NR * M::SP,
                v_conv = v_cnt + sizeof(ull) * c_words, pin_bytes = v_conv + asg_grp_up8(sizeof(uint32_t) * NG);
-  AGCHK(many_grow_pinned(B.h_pin, pin_bytes));  // (every earlier call ended in a synchronisation)
+  MANYCHK(many_grow_pinned(B.h_pin, pin_bytes));  // (every earlier call ended in a synchronisation)
   char *pin = B.h_pin.get();
   double *h_par = (double *)(pin + u_par);
   int32_t *h_nm = (int32_t *)(pin + u_nm);
@@ -407,44 +251,44 @@ int assign_grouped_run(AssignGrpJob &J) {
   if (NW) memcpy(pin + u_wgs, wgs.data(), sizeof(uint2) * NW);
   if (NP) memcpy(pin + u_pairs, pairs.data(), sizeof(uint2) * NP);
 
-  AGCHK(many_grow(B.d_nm, NG));
-  AGCHK(many_grow(B.d_gbase, NG));
-  AGCHK(many_grow(B.d_state, 2 * NG));  // state, converged
-  AGCHK(many_grow(B.d_cnt, c_words));
-  AGCHK(many_grow(B.d_par, std::max<size_t>(NR * M::P, 1)));
-  AGCHK(many_grow(B.d_rows, std::max<size_t>(NR * M::SP, 1)));
-  AGCHK(many_grow(B.d_wgs, std::max<size_t>(NW, 1)));
-  AGCHK(many_grow(B.d_pairs, std::max<size_t>(NP, 1)));
-  AGCHK(many_grow(B.d_labels[0], std::max<size_t>(NT, 1)));
-  if (J.refine) AGCHK(many_grow(B.d_labels[1], std::max<size_t>(NT, 1)));
-  if (J.residuals_out) AGCHK(many_grow(B.d_res, std::max<size_t>(NT, 1)));
-  if (moments) AGCHK(many_grow(B.d_partials, (size_t)pblocks * M::NMOM));
-  if (!J.on_device && J.labels_out) AGCHK(many_grow(B.d_lab_out, N));
-  if (!J.on_device && J.residuals_out) AGCHK(many_grow(B.d_res_out, N));
+  MANYCHK(many_grow(B.d_nm, NG));
+  MANYCHK(many_grow(B.d_gbase, NG));
+  MANYCHK(many_grow(B.d_state, 2 * NG));  // state, converged
+  MANYCHK(many_grow(B.d_cnt, c_words));
+  MANYCHK(many_grow(B.d_par, std::max<size_t>(NR * M::P, 1)));
+  MANYCHK(many_grow(B.d_rows, std::max<size_t>(NR * M::SP, 1)));
+  MANYCHK(many_grow(B.d_wgs, std::max<size_t>(NW, 1)));
+  MANYCHK(many_grow(B.d_pairs, std::max<size_t>(NP, 1)));
+  MANYCHK(many_grow(B.d_labels[0], std::max<size_t>(NT, 1)));
+  if (J.refine) MANYCHK(many_grow(B.d_labels[1], std::max<size_t>(NT, 1)));
+  if (J.residuals_out) MANYCHK(many_grow(B.d_res, std::max<size_t>(NT, 1)));
+  if (moments) MANYCHK(many_grow(B.d_partials, (size_t)pblocks * M::NMOM));
+  if (!J.on_device && J.labels_out) MANYCHK(many_grow(B.d_lab_out, N));
+  if (!J.on_device && J.residuals_out) MANYCHK(many_grow(B.d_res_out, N));
   ull *d_changed = B.d_cnt, *d_counts = B.d_cnt + c_counts, *d_used = B.d_cnt + c_used, *d_ok = B.d_cnt + c_ok,
       *d_rounds = B.d_cnt + c_rounds, *d_going = B.d_cnt + c_going;
   uint32_t *d_state = B.d_state, *d_conv = B.d_state + NG;
 
-  AGCHK(hipMemcpyAsync(B.d_nm, h_nm, sizeof(int32_t) * NG, hipMemcpyHostToDevice, stream));
-  AGCHK(hipMemcpyAsync(B.d_gbase, pin + u_gbase, sizeof(uint64_t) * NG, hipMemcpyHostToDevice, stream));
-  AGCHK(hipMemcpyAsync(d_state, h_state, sizeof(uint32_t) * NG, hipMemcpyHostToDevice, stream));
-  AGCHK(hipMemsetAsync(d_conv, 0, sizeof(uint32_t) * NG, stream));
-  AGCHK(hipMemsetAsync(B.d_cnt, 0, sizeof(ull) * c_words, stream));
+  MANYCHK(hipMemcpyAsync(B.d_nm, h_nm, sizeof(int32_t) * NG, hipMemcpyHostToDevice, stream));
+  MANYCHK(hipMemcpyAsync(B.d_gbase, pin + u_gbase, sizeof(uint64_t) * NG, hipMemcpyHostToDevice, stream));
+  MANYCHK(hipMemcpyAsync(d_state, h_state, sizeof(uint32_t) * NG, hipMemcpyHostToDevice, stream));
+  MANYCHK(hipMemsetAsync(d_conv, 0, sizeof(uint32_t) * NG, stream));
+  MANYCHK(hipMemsetAsync(B.d_cnt, 0, sizeof(ull) * c_words, stream));
   if (NW) {
-    AGCHK(hipMemcpyAsync(B.d_par, h_par, sizeof(double) * NR * M::P, hipMemcpyHostToDevice, stream));
-    AGCHK(hipMemcpyAsync(B.d_wgs, pin + u_wgs, sizeof(uint2) * NW, hipMemcpyHostToDevice, stream));
-    AGCHK(hipMemcpyAsync(B.d_pairs, pin + u_pairs, sizeof(uint2) * NP, hipMemcpyHostToDevice, stream));
-    hipLaunchKernelGGL((k_asg_grp_prepare<M>), dim3(grp_grid(NR)), dim3(kBlock), 0, stream, B.d_par, B.d_nm,
+    MANYCHK(hipMemcpyAsync(B.d_par, h_par, sizeof(double) * NR * M::P, hipMemcpyHostToDevice, stream));
+    MANYCHK(hipMemcpyAsync(B.d_wgs, pin + u_wgs, sizeof(uint2) * NW, hipMemcpyHostToDevice, stream));
+    MANYCHK(hipMemcpyAsync(B.d_pairs, pin + u_pairs, sizeof(uint2) * NP, hipMemcpyHostToDevice, stream));
+    hipLaunchKernelGGL((k_assign_prepare<M>), dim3(grp_grid(NR)), dim3(kBlock), 0, stream, B.d_par, B.d_nm.get(),
                        (uint64_t)NR, (int)MM, J.mc, B.d_rows);
-    AGCHK(hipGetLastError());
+    MANYCHK(hipGetLastError());
   }
   if (dead_records && NT) {  // no pass writes them
-    AGCHK(hipMemsetAsync(B.d_labels[0], 0xFF, sizeof(int32_t) * NT, stream));
-    if (J.refine) AGCHK(hipMemsetAsync(B.d_labels[1], 0xFF, sizeof(int32_t) * NT, stream));
+    MANYCHK(hipMemsetAsync(B.d_labels[0], 0xFF, sizeof(int32_t) * NT, stream));
+    if (J.refine) MANYCHK(hipMemsetAsync(B.d_labels[1], 0xFF, sizeof(int32_t) * NT, stream));
     if (J.residuals_out) {
       hipLaunchKernelGGL(k_asg_grp_fill, dim3(grp_grid(NT)), dim3(kBlock), 0, stream, B.d_res, (uint64_t)NT,
                          __builtin_inf());
-      AGCHK(hipGetLastError());
+      MANYCHK(hipGetLastError());
     }
   }
 
@@ -462,25 +306,25 @@ int assign_grouped_run(AssignGrpJob &J) {
     else
       hipLaunchKernelGGL((k_asg_grp_pass<M, true>), dim3((unsigned)NW), dim3(kBlock), 0, stream, P.d_data, W, B.d_wgs,
                          T, B.d_rows, (int)MM, org_off, J.mc, lab, res, old, d_changed, d_counts, B.d_partials);
-    AGCHK(hipGetLastError());
+    MANYCHK(hipGetLastError());
     if (last) break;  // every group still going stops here: nothing to read
-    AGCHK(hipMemsetAsync(d_going, 0, sizeof(ull), stream));
+    MANYCHK(hipMemsetAsync(d_going, 0, sizeof(ull), stream));
     hipLaunchKernelGGL(k_asg_grp_decide, dim3(grp_grid(NG)), dim3(kBlock), 0, stream, (uint32_t)NG, (ull)r, 0,
                        d_changed, d_state, d_rounds, d_conv, d_going);
-    AGCHK(hipGetLastError());
-    AGCHK(hipMemcpyAsync(pin + v_going, d_going, sizeof(ull), hipMemcpyDeviceToHost, stream));
-    AGCHK(hipStreamSynchronize(stream));  // the one word of the round
+    MANYCHK(hipGetLastError());
+    MANYCHK(hipMemcpyAsync(pin + v_going, d_going, sizeof(ull), hipMemcpyDeviceToHost, stream));
+    MANYCHK(hipStreamSynchronize(stream));  // the one word of the round
     if (*h_going == 0) break;
     hipLaunchKernelGGL((k_asg_grp_solve<M>), dim3((unsigned)NP), dim3(64), 0, stream, B.d_pairs, T, B.d_partials,
                        (int)MM, org_off, J.mc, B.d_rows, d_counts, d_used, d_ok);
-    AGCHK(hipGetLastError());
+    MANYCHK(hipGetLastError());
     r++;
     cur ^= 1;
   }
   if (NW && r == J.max_rounds) {  // the last pass allowed: its decision needs no answer
     hipLaunchKernelGGL(k_asg_grp_decide, dim3(grp_grid(NG)), dim3(kBlock), 0, stream, (uint32_t)NG, (ull)r, 1,
                        d_changed, d_state, d_rounds, d_conv, d_going);
-    AGCHK(hipGetLastError());
+    MANYCHK(hipGetLastError());
   }
 
   // results: the labels of the last pass in upload order, then the rows and the per-group words
@@ -488,22 +332,22 @@ int assign_grouped_run(AssignGrpJob &J) {
     int32_t *d_lab = J.on_device ? J.labels_out : B.d_lab_out.get();
     hipLaunchKernelGGL(k_grp_scatter_labels, dim3(grp_grid(N)), dim3(kBlock), 0, stream, perm, (uint32_t)N,
                        (uint32_t)NT, B.d_labels[cur].get(), d_lab);
-    AGCHK(hipGetLastError());
+    MANYCHK(hipGetLastError());
     if (!J.on_device)
-      AGCHK(hipMemcpyAsync(J.labels_out, d_lab, sizeof(int32_t) * N, hipMemcpyDeviceToHost, stream));
+      MANYCHK(hipMemcpyAsync(J.labels_out, d_lab, sizeof(int32_t) * N, hipMemcpyDeviceToHost, stream));
   }
   if (J.residuals_out) {
     double *d_r = J.on_device ? J.residuals_out : B.d_res_out.get();
     hipLaunchKernelGGL(k_grp_scatter_f64, dim3(grp_grid(N)), dim3(kBlock), 0, stream, perm, (uint32_t)N, (uint32_t)NT,
                        B.d_res.get(), __builtin_inf(), d_r);
-    AGCHK(hipGetLastError());
+    MANYCHK(hipGetLastError());
     if (!J.on_device)
-      AGCHK(hipMemcpyAsync(J.residuals_out, d_r, sizeof(double) * N, hipMemcpyDeviceToHost, stream));
+      MANYCHK(hipMemcpyAsync(J.residuals_out, d_r, sizeof(double) * N, hipMemcpyDeviceToHost, stream));
   }
-  if (r > 0) AGCHK(hipMemcpyAsync(pin + v_rows, B.d_rows, sizeof(double) * NR * M::SP, hipMemcpyDeviceToHost, stream));
-  AGCHK(hipMemcpyAsync(pin + v_cnt, B.d_cnt, sizeof(ull) * c_words, hipMemcpyDeviceToHost, stream));
-  AGCHK(hipMemcpyAsync(pin + v_conv, d_conv, sizeof(uint32_t) * NG, hipMemcpyDeviceToHost, stream));
-  AGCHK(hipStreamSynchronize(stream));
+  if (r > 0) MANYCHK(hipMemcpyAsync(pin + v_rows, B.d_rows, sizeof(double) * NR * M::SP, hipMemcpyDeviceToHost, stream));
+  MANYCHK(hipMemcpyAsync(pin + v_cnt, B.d_cnt, sizeof(ull) * c_words, hipMemcpyDeviceToHost, stream));
+  MANYCHK(hipMemcpyAsync(pin + v_conv, d_conv, sizeof(uint32_t) * NG, hipMemcpyDeviceToHost, stream));
+  MANYCHK(hipStreamSynchronize(stream));
 
   for (size_t g = 0; g < NG; g++) {
     const size_t nm = J.n_models[g];
@@ -523,23 +367,19 @@ int assign_grouped_run(AssignGrpJob &J) {
     J.converged_out[g] = (int32_t)h_conv[g];
     for (size_t m = 0; m < MM; m++) {
       const size_t e = g * MM + m;
-      memset(&J.fits[e], 0, sizeof(lsqr_fit_info));
-      if (m >= nm) {
+      if (m < nm) {
+        assign_fit_out<M>(rg, h_cnt[c_ok + e], h_cnt[c_used + e], &J.status_out[e], &J.fits[e]);
+      } else {
         J.status_out[e] = LSQR_ERR_STATE;  // model not there
-        continue;
-      }
-      const bool ok = rg == 0 || h_cnt[c_ok + e] != 0;
-      J.status_out[e] = ok ? LSQR_OK : LSQR_EMPTY;
-      if (rg > 0) {
-        J.fits[e].n_params = ok ? (int32_t)M::P : 0;
-        J.fits[e].n_used = h_cnt[c_used + e];
+        memset(&J.fits[e], 0, sizeof(lsqr_fit_info));
       }
     }
   }
   if (J.offsets_out) memcpy(J.offsets_out, off.data(), sizeof(uint64_t) * (NG + 1));
   return LSQR_OK;
 }
-#undef AGCHK
 #endif  // __HIPCC__
 
 }  // namespace lsqr
+
+#undef MANYCHK

@@ -281,5 +281,3 @@ int grouped_seq_run(ManyJob &J, const double *data, size_t stride, size_t N, con
 #endif
 
 }  // namespace lsqr
-
-#undef MANYCHK

@@ -4302,44 +4302,55 @@ int lsqr_ransac_grouped_sequential(lsqr_ctx *c, const int32_t *groups, size_t n_
   return LSQR_OK;
 }
 
-// ---- nearest-model assignment and refit (assign.h) -----------------------------------------------------------------
-// What lsqr_assign and lsqr_refine share.  The checks, in the contract's order: the context; the model gate; n_models
-// == 0 is LSQR_OK with every output untouched; n_models > 64 and the null arguments (args: the entry point's own
-// pointers are all there); the context holds a model and records; their count.  Then the job from the context and
-// assign_run, dispatched on the model.  The context's hypotheses, mask, index and d_par are not touched: the call has
-// buffers of its own (lsqr_ctx::assign).
+// ---- nearest-model assignment and refit (assign.h, assign_grouped.h) -------------------------------------------------
+// What the four entry points share.  The checks, in the contract's order: the context; the model gate; count == 0
+// (n_models, or n_groups of the grouped calls) is LSQR_OK with every output untouched; more than 64 models; own(), the
+// entry point's own arguments; the context holds a model and records; their count.  Then run(tag), the run function
+// on the model -- it has waited for the stream when it returns.  The context's upload, hypotheses, mask, index and
+// d_par are not touched: the calls have buffers of their own (lsqr_ctx::assign, lsqr_ctx::assign_grp).
 extern "C++" {
-static int assign_call(lsqr_ctx *c, const char *fn, bool refine, bool args, AssignJob &J) {
+template <class Own, class Run>
+static int assign_frame(lsqr_ctx *c, const char *fn, bool refine, const char *takes, size_t count, size_t max_models,
+                        const char *err, Own own, Run run) {
   int st = need_ready(c, false);
   if (st != LSQR_OK) return st;
   if (!assign_model_ok(c->cfg))
     return fail(c, LSQR_ERR_INVALID, "%s: plane, line, sphere and 2-D line only (model %d)", fn, c->cfg.model);
   if (refine && wants_lm(c->cfg))
-    return fail(c, LSQR_ERR_INVALID, "%s: the geometric sphere's fit is iterative; lsqr_assign takes it", fn);
-  if (J.n_models == 0) return LSQR_OK;
-  if (J.n_models > (size_t)kAssignMaxModels) return fail(c, LSQR_ERR_INVALID, "%s: more than 64 models", fn);
-  if (!args) return fail(c, LSQR_ERR_INVALID, "%s: null argument", fn);
+    return fail(c, LSQR_ERR_INVALID, "%s: the geometric sphere's fit is iterative; %s takes it", fn, takes);
+  if (count == 0) return LSQR_OK;
+  if (max_models > (size_t)kAssignMaxModels) return fail(c, LSQR_ERR_INVALID, "%s: more than 64 models", fn);
+  if ((st = own()) != LSQR_OK) return st;
   if ((st = need_ready(c, true)) != LSQR_OK) return st;
   if (c->n > 0xFFFFFFF0ull) return fail(c, LSQR_ERR_INVALID, "%s: more than 2^32 - 16 records", fn);
-  if (!c->assign) c->assign.reset(new AssignBufs());
-  J.stream = c->stream;
-  J.cfg = c->cfg;
-  J.mc = c->mc;
-  J.data = c->d_data;
-  J.stride = c->stride;
-  J.n = (uint32_t)c->n;
-  J.B = c->assign.get();
   st = dispatch(c->cfg, [&](auto tag) -> int {
-    typedef typename decltype(tag)::type M;
-    if constexpr (AssignModel<M>::value) return assign_run<M>(J);
+    if constexpr (AssignModel<typename decltype(tag)::type>::value) return run(tag);
     else return LSQR_ERR_INVALID;
   });
   if (st != LSQR_OK) {
     (void)sync_stream(c);  // nothing of this call is left in flight on its buffers
-    return fail(c, st, "%s: %s", fn, J.err[0] ? J.err : "model not in this build");
+    return fail(c, st, "%s: %s", fn, err[0] ? err : "model not in this build");
   }
-  bsel_host_synced(c);  // (assign_run has waited for the stream)
+  bsel_host_synced(c);
   return LSQR_OK;
+}
+
+// lsqr_assign and lsqr_refine; args: the entry point's own pointers are all there
+static int assign_call(lsqr_ctx *c, const char *fn, bool refine, bool args, AssignJob &J) {
+  return assign_frame(
+      c, fn, refine, "lsqr_assign", J.n_models, J.n_models, J.err,
+      [&]() -> int { return args ? LSQR_OK : fail(c, LSQR_ERR_INVALID, "%s: null argument", fn); },
+      [&](auto tag) -> int {
+        if (!c->assign) c->assign.reset(new AssignBufs());
+        J.stream = c->stream;
+        J.cfg = c->cfg;
+        J.mc = c->mc;
+        J.data = c->d_data;
+        J.stride = c->stride;
+        J.n = (uint32_t)c->n;
+        J.B = c->assign.get();
+        return assign_run<typename decltype(tag)::type>(J);
+      });
 }
 }  // extern "C++"
 
@@ -4377,50 +4388,33 @@ int lsqr_refine(lsqr_ctx *c, double *params_inout, size_t n_models, size_t max_r
   return st;
 }
 
-// ---- the same with one model set per label (assign_grouped.h) ---------------------------------------------------------
-// What lsqr_assign_grouped and lsqr_refine_grouped share.  The checks, in the contract's order: the context; the model
-// gate; n_groups == 0 is LSQR_OK with every output untouched; max_models, n_groups, the null arguments (args: the
-// entry point's own pointers are all there) and every n_models[g]; the context holds records; their count.  The sort
-// and the packed copy live in the batched calls' buffers (lsqr_ctx::many), as lsqr_ransac_grouped's do; the rest in
-// lsqr_ctx::assign_grp.  The context's upload, hypotheses, mask, index and d_par are not touched.
+// lsqr_assign_grouped and lsqr_refine_grouped.  The sort and the packed copy live in the batched calls' buffers
+// (lsqr_ctx::many), as lsqr_ransac_grouped's do.
 extern "C++" {
 static int assign_grouped_call(lsqr_ctx *c, const char *fn, bool args, AssignGrpJob &J) {
-  int st = need_ready(c, false);
-  if (st != LSQR_OK) return st;
-  if (!assign_model_ok(c->cfg))
-    return fail(c, LSQR_ERR_INVALID, "%s: plane, line, sphere and 2-D line only (model %d)", fn, c->cfg.model);
-  if (J.refine && wants_lm(c->cfg))
-    return fail(c, LSQR_ERR_INVALID, "%s: the geometric sphere's fit is iterative; lsqr_assign_grouped takes it", fn);
-  if (J.n_groups == 0) return LSQR_OK;
-  if (J.max_models > (size_t)kAssignMaxModels) return fail(c, LSQR_ERR_INVALID, "%s: more than 64 models", fn);
-  if (J.n_groups > 0x7FFFFFFFull) return fail(c, LSQR_ERR_INVALID, "%s: more than 2^31 - 1 groups", fn);
-  if (!args || !J.groups || !J.params || !J.n_models) return fail(c, LSQR_ERR_INVALID, "%s: null argument", fn);
-  for (size_t g = 0; g < J.n_groups; g++)
-    if (J.n_models[g] > J.max_models)
-      return fail(c, LSQR_ERR_INVALID, "%s: n_models[%zu] is above max_models", fn, g);
-  if ((st = need_ready(c, true)) != LSQR_OK) return st;
-  if (c->n > 0xFFFFFFF0ull) return fail(c, LSQR_ERR_INVALID, "%s: more than 2^32 - 16 records", fn);
-  if (!c->assign_grp) c->assign_grp.reset(new AssignGrpBufs());
-  many_job_from_ctx(c, J.pack);
-  J.pack.resident = true;
-  J.pack.n = J.n_groups;
-  J.cfg = c->cfg;
-  J.mc = c->mc;
-  J.data = c->d_data;
-  J.stride = c->stride;
-  J.n = c->n;
-  J.B = c->assign_grp.get();
-  st = dispatch(c->cfg, [&](auto tag) -> int {
-    typedef typename decltype(tag)::type M;
-    if constexpr (AssignModel<M>::value) return assign_grouped_run<M>(J);
-    else return LSQR_ERR_INVALID;
-  });
-  if (st != LSQR_OK) {
-    (void)sync_stream(c);  // nothing of this call is left in flight on its buffers
-    return fail(c, st, "%s: %s", fn, J.err[0] ? J.err : "model not in this build");
-  }
-  bsel_host_synced(c);  // (assign_grouped_run has waited for the stream)
-  return LSQR_OK;
+  return assign_frame(
+      c, fn, J.refine, "lsqr_assign_grouped", J.n_groups, J.max_models, J.err,
+      [&]() -> int {
+        if (J.n_groups > 0x7FFFFFFFull) return fail(c, LSQR_ERR_INVALID, "%s: more than 2^31 - 1 groups", fn);
+        if (!args || !J.groups || !J.params || !J.n_models) return fail(c, LSQR_ERR_INVALID, "%s: null argument", fn);
+        for (size_t g = 0; g < J.n_groups; g++)
+          if (J.n_models[g] > J.max_models)
+            return fail(c, LSQR_ERR_INVALID, "%s: n_models[%zu] is above max_models", fn, g);
+        return LSQR_OK;
+      },
+      [&](auto tag) -> int {
+        if (!c->assign_grp) c->assign_grp.reset(new AssignGrpBufs());
+        many_job_from_ctx(c, J.pack);
+        J.pack.resident = true;
+        J.pack.n = J.n_groups;
+        J.cfg = c->cfg;
+        J.mc = c->mc;
+        J.data = c->d_data;
+        J.stride = c->stride;
+        J.n = c->n;
+        J.B = c->assign_grp.get();
+        return assign_grouped_run<typename decltype(tag)::type>(J);
+      });
 }
 }  // extern "C++"
 

@@ -19,6 +19,7 @@ from oracle import pyoracle as O
 pytestmark = pytest.mark.gpu
 P = 0.999
 SMALL, LARGE = 300, 70_001  # below one chunk of the pass (2048 records) / several chunks, odd tail
+EDGES = (1, 2047, 2048, 2049, 4096, 4097)  # prefixes of the LARGE scene that end at, before and after a chunk's end
 MARGIN = 1e-6               # no record of a refine scene is this close to a decision
 REL = 1e-6                  # the README's fit tolerance
 
@@ -136,6 +137,28 @@ def test_assign_equals_the_host_call_record_by_record(ctx, name):
             masks = np.array([ctx.mask(r)[0] for r in rows])
             assert np.sum(masks.sum(axis=0) > 1) > SMALL // 10
             assert np.array_equal(got["labels"], host_assign(ctx, rows)[0])
+
+
+@pytest.mark.parametrize("n", EDGES)
+@pytest.mark.parametrize("name", ["plane", "plane5"])
+def test_assign_at_the_chunk_edges_equals_the_host_call(ctx, name, n):
+    """a last chunk of 1, 2047 and 2048 records, in one, two and three chunks: every record against lsqr_assign_host"""
+    rows = start(ctx, name, LARGE)[1]
+    data = scene(name, LARGE)[:n]
+    model, dim, delta, ls = MODELS[name][:4]
+    _setup(ctx, name).upload(data)
+    got = ctx.assign(rows, want_residuals=True)
+    cfg = L.ModelCfg(model, dim, delta, ls, 0, 0.0)
+    label, res = C.c_int32(0), C.c_double(0.0)
+    flat = np.ascontiguousarray(rows)
+    labels, residuals = np.empty(n, dtype=np.int32), np.empty(n)
+    for i, x in enumerate(data):
+        rec = np.ascontiguousarray(x)
+        assert L.load().lsqr_assign_host(C.byref(cfg), L.ptr(flat), 3, L.ptr(rec), C.byref(label), C.byref(res)) == L.OK
+        labels[i], residuals[i] = label.value, res.value
+    assert np.array_equal(got["labels"], labels)
+    assert np.array_equal(bits(got["residuals"]), bits(residuals))
+    assert np.array_equal(got["counts"], counts_of(labels, 3))
 
 
 class DeviceArray:
@@ -409,6 +432,31 @@ def test_refine_against_the_host_loop_round_by_round(ctx, name, n):
     assert np.array_equal(full["labels"], labels)
     assert_rows_close(name, full["params"], rows, "full")
     assert r >= 1 and np.all(full["status"] == L.OK)
+
+
+@pytest.mark.parametrize("n", [2049, 4096])
+def test_refine_at_the_chunk_edges_against_the_host_loop(ctx, n):
+    """a last chunk of one record and of 2048: the rounds of max_rounds = 2 against the host loop, as the test above
+    (both prefixes of the scene meet host_round's MARGIN condition, which it asserts)"""
+    rows0 = start(ctx, "plane", LARGE)[1]
+    _setup(ctx, "plane").upload(scene("plane", LARGE)[:n])
+    rows, prev = np.array(rows0), None
+    for r in range(3):  # (rows: params_r; left at the last round's when the loop ends)
+        labels, new, status, used = host_round(ctx, "plane", rows)
+        got = ctx.refine(rows0, max_rounds=r)
+        assert got["rounds"] == r and np.array_equal(got["labels"], labels), r
+        assert_rows_close("plane", got["params"], rows, "round %d" % r)
+        assert np.array_equal(got["counts"], counts_of(labels, 3))
+        if r > 0:
+            assert np.array_equal(got["status"], last_status) and np.array_equal(got["n_used"], last_used), r
+        assert got["converged"] == (r > 0 and np.array_equal(labels, prev))
+        if got["converged"] or r == 2:
+            break
+        rows, prev, last_status, last_used = new, labels, status, used
+    assert r >= 1
+    full = ctx.refine(rows0, max_rounds=2)
+    assert full["rounds"] == r and np.array_equal(full["labels"], labels)
+    assert_rows_close("plane", full["params"], rows, "full")
 
 
 @pytest.mark.parametrize("name,n", CASES)

@@ -16,6 +16,10 @@ alternating; median and min .. max are reported.  hbm_fraction = n x 24 B / roun
 alone over the HBM3E peak: the label traffic, 8 B per record, is not counted).
 One JSON line per M on stdout; --out FILE also writes them to FILE.
 
+--model {plane,line,sphere,line2d} / --dim D: another model's kernels on a scene of lsqrrecipes_amd.synth -- four planted
+models of 20 % each (sigma 0.4) and 20 % clutter, shuffled -- from the planted rows; M = 4 only.  With --grouped: split
+(a), one group, alone.
+
 --grouped: Context.refine_grouped (lsqr_refine_grouped: one model set per label) on the same --n plane records in three
 splits: (a) 1 group of 4 models, (b) 1 000 groups of n / 1 000 records with 4 models each, (c) 50 000 groups of
 n / 50 000 records with 3 models each.  Every group has its own planes (models / (models + 1) of its records, the rest clutter) and
@@ -40,6 +44,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from lsqrrecipes_amd import _lib as L  # noqa: E402
+from lsqrrecipes_amd import synth  # noqa: E402
 from lsqrrecipes_amd.context import Context  # noqa: E402
 
 DELTA = 0.5
@@ -60,6 +65,25 @@ def scene(n, seed=20261019, box=1000.0, sigma=0.4):
     parts.append(g.uniform(-box, box, (n - 4 * m, 3)))
     pts = np.concatenate(parts)
     return np.ascontiguousarray(pts[g.permutation(n)]), np.array(rows)
+
+
+# --model: (the library's model, the generator of lsqrrecipes_amd.synth whose params are that model's rows)
+SYNTH = {"plane": (L.PLANE, synth.plane), "line": (L.LINE, synth.line), "sphere": (L.SPHERE, synth.sphere),
+         "line2d": (L.LINE2D, synth.plane)}
+
+
+def synth_scene(n, model, dim, seed=20261021):
+    """-> points, the four planted models as rows"""
+    gen = SYNTH[model][1]
+    m = n // 5
+    parts, rows = [], []
+    for j in range(4):
+        pts, row, _ = gen(m, 0.0, seed=seed + 7 * j, dim=dim)
+        parts.append(pts)
+        rows.append(row)
+    parts.append(gen(n - 4 * m, 1.0, seed=seed + 999, dim=dim)[0])
+    pts = np.concatenate(parts)
+    return np.ascontiguousarray(pts[np.random.default_rng(seed).permutation(n)]), np.array(rows)
 
 
 def models(rows, m):
@@ -161,15 +185,19 @@ def grouped_main(a):
     for name, n_groups, k in (("a", 1, 4), ("b", 1000, 4), ("c", 50000, 3)):
         if name not in a.splits:
             continue
-        data, grp, rows = grouped_scene(a.n, n_groups, k)
+        if a.synth:  # one group: the ungrouped scene and rows
+            data, rows = synth_scene(a.n, a.model, a.dim)
+            grp, rows = np.zeros(a.n, dtype=np.int32), rows[None]
+        else:
+            data, grp, rows = grouped_scene(a.n, n_groups, k)
         n = data.shape[0]
         sizes = np.bincount(grp, minlength=n_groups)
         order = np.argsort(grp, kind="stable")
         first = np.concatenate([[0], np.cumsum(sizes)])
         loop_groups = min(n_groups, a.loop_groups)
         with Context(0) as ctx, Context(0) as one:
-            ctx.set_model(L.PLANE, 3, DELTA, L.LS_ALGEBRAIC).upload(data)
-            one.set_model(L.PLANE, 3, DELTA, L.LS_ALGEBRAIC)
+            ctx.set_model(a.model_id, a.dim, DELTA, L.LS_ALGEBRAIC).upload(data)
+            one.set_model(a.model_id, a.dim, DELTA, L.LS_ALGEBRAIC)
             dev = DeviceArray(grp)
             t_lo, t_hi, t_loop, t_ref_lo, t_ref_hi, done, ref_done = [], [], [], [], [], None, None
             for rep in range(-1, a.reps):  # rep -1 warms every kind
@@ -209,11 +237,11 @@ def grouped_main(a):
             per = [(h - l) / (done[1] - done[0]) * n for h, l in zip(t_hi, t_lo)]
             rnd = float(np.median(per))
             wgs = int(np.sum((sizes[sizes > 0] + 2047) // 2048))
-            row = dict(split=name, n=n, groups=n_groups, models=k, reps=a.reps, rounds=[r1, r2],
+            row = dict(split=name, model=a.model, dim=a.dim, n=n, groups=n_groups, models=k, reps=a.reps, rounds=[r1, r2],
                        record_rounds_done=list(done), rounds_hist=np.bincount(hi["rounds"]).tolist(),
                        converged=int(hi["converged"].sum()), grouped_round_ms=ms(per), grouped_call_ms=ms(t_hi),
                        workgroups=wgs, lane_share=round(n / (wgs * 2048.0), 4),
-                       hbm_fraction=round(n * 24 / rnd / HBM_PEAK, 4))
+                       hbm_fraction=round(n * 8 * a.dim / rnd / HBM_PEAK, 4))
             if t_loop:
                 row.update(loop_call_ms=ms(t_loop), loop_groups_timed=loop_groups,
                            loop_scaled_by=n_groups / loop_groups, loop_reps=len(t_loop),
@@ -241,16 +269,23 @@ def main():
     ap.add_argument("--grouped", action="store_true", help="time Context.refine_grouped instead (see above)")
     ap.add_argument("--splits", nargs="+", default=["a", "b", "c"], choices=["a", "b", "c"])
     ap.add_argument("--loop-groups", type=int, default=200, help="--grouped: groups the per-group loop is timed on")
+    ap.add_argument("--model", choices=sorted(SYNTH), default="plane")
+    ap.add_argument("--dim", type=int, default=3)
     a = ap.parse_args()
+    a.model_id = SYNTH[a.model][0]
+    a.synth = (a.model, a.dim) != ("plane", 3)  # the default scene is this tool's own
+    if a.synth:
+        a.dim = 2 if a.model == "line2d" else a.dim
+        a.models, a.splits = [4], ["a"]
     if a.grouped:
         return grouped_main(a)
-    data, planes = scene(a.n)
+    data, planes = synth_scene(a.n, a.model, a.dim) if a.synth else scene(a.n)
     r1, r2 = a.rounds
     lines = []
     with Context(0) as ctx:
-        ctx.set_model(L.PLANE, 3, DELTA, L.LS_ALGEBRAIC).upload(data)
+        ctx.set_model(a.model_id, a.dim, DELTA, L.LS_ALGEBRAIC).upload(data)
         for m in a.models:
-            rows = models(planes, m)
+            rows = planes if a.synth else models(planes, m)
             t_lo, t_hi, t_asg, t_base, done = [], [], [], [], None
             for rep in range(-1, a.reps):  # rep -1 warms every kind
                 t0 = time.perf_counter()
@@ -277,10 +312,11 @@ def main():
             per = [(h - l) / (done[1] - done[0]) for h, l in zip(t_hi, t_lo)]
             ms = lambda v: [round(1e3 * float(f(v)), 4) for f in (np.median, np.min, np.max)]
             rnd = float(np.median(per))
-            row = dict(n=a.n, models=m, reps=a.reps, rounds_done=list(done), counts_assigned=int(a.n - asg["counts"][-1]),
+            row = dict(model=a.model, dim=a.dim, n=a.n, models=m, reps=a.reps, rounds_done=list(done), counts_assigned=int(a.n - asg["counts"][-1]),
                        refine_round_ms=ms(per), assign_call_ms=ms(t_asg), baseline_round_ms=ms(t_base),
                        baseline_reps=len(t_base), ratio=round(float(np.median(t_base)) / rnd, 1),
-                       record_bytes_per_s=round(a.n * 24 / rnd, 0), hbm_fraction=round(a.n * 24 / rnd / HBM_PEAK, 4))
+                       record_bytes_per_s=round(a.n * 8 * a.dim / rnd, 0),
+                       hbm_fraction=round(a.n * 8 * a.dim / rnd / HBM_PEAK, 4))
             lines.append(json.dumps(row))
             print(lines[-1], flush=True)
     if a.out:
