@@ -844,7 +844,7 @@ LSQR_API void lsqr_dedup_destroy(void *set);
  *                written once per batch (csrc/cells.h: k_prepare_hyps) and read back by the counted two-level scan; 0 = it
  *                is rebuilt for every (cell, group of 64 hypotheses) (A/B knob).  Votes are identical;
  * "scan_lean":   the counted two-level scan of the cell models (plane, sphere, line): 1 (default) = its counting pass
- *                runs a count-only form (csrc/cells.h: k_cells_bounds<..., COUNT>: survivor counts and nothing else) and,
+ *                runs a count-only form (csrc/cells.h: k_cells_bounds, BoundsForm::Count: survivor counts and nothing else) and,
  *                where the hypotheses are prepared (plane, "scan_prepared" 1), k_scan_pairs keeps its share arithmetic
  *                on the scalar unit, refills its one prepared hypothesis for the next group as soon as level 1 has
  *                read it and reads the pair loop's addends as stored; 0 = the general forms of both kernels (A/B knob).
@@ -852,7 +852,7 @@ LSQR_API void lsqr_dedup_destroy(void *set);
  * "scan_pack":   the lean counted scan of the prepared cell models (plane, 3-D and 2-D; "scan_prepared" 1 and
  *                "scan_lean" 1): 1 (default) = the counting pass stores level 1's 64-bit survivor mask of every (cell, group of 64
  *                hypotheses) instead of a count, and k_scan_pairs repeats level 1 on packed blocks of 64 consecutive
- *                survivors of a cell, gathered through a per-wave id list in LDS (csrc/cells.h: k_scan_pairs<..., PACK>),
+ *                survivors of a cell, gathered through a per-wave id list in LDS (csrc/cells.h: k_scan_pairs, PairsForm::Packed),
  *                instead of on every group of 64 that holds a survivor; 0 = per group (A/B knob).  Accepted values 0 and 1;
  *                without effect on other models and with either of the two other options 0.  Votes are identical;
  * "scan_recheck": the exact path of the 3-D plane's packed counted scan ("scan_pack" 1 with the LDS broadcast area, the

@@ -42,7 +42,7 @@ namespace lsqr {
 
 constexpr int kCellPtsMin = 128;
 constexpr uint32_t kGroupPad = 4, kCellPad = 16;  // k_scan_pairs: cost padding per group / per cell, in pairs (see there)
-constexpr uint32_t kBlockPad = 6;  // k_scan_pairs<..., PACK>: cost padding per packed block of 64 survivors (see k_tile_costs)
+constexpr uint32_t kBlockPad = 6;  // packed k_scan_pairs: cost padding per packed block of 64 survivors (see k_tile_costs)
 constexpr uint32_t kQueues = 32;   // work queues of k_scan_cells (one atomic counter each)
 constexpr uint32_t kQueuePitch = 1088;  // uint32 words between counters: separate cache lines / channels  // cell sizes are multiples of one packed fp32 pair per lane
 
@@ -1047,6 +1047,55 @@ inline CellConsts cell_consts(const LineCell<D> *, const ModelConsts &mc) {
   return cc;
 }
 
+// ---- the forms of the counted scan ----------------------------------------------------------------------------
+// k_scan_pairs and its counting pass k_cells_bounds are each built in five forms; the options "scan_prepared",
+// "scan_lean", "scan_pack" and "scan_recheck" choose among them (the host decides once per launch: pairs_form() in
+// lsqr_hip.hip), and every form counts the same votes.
+//   General        load() per (cell, group); every cell model
+//   Prepared       Hyp read from the batch's prepared block (k_prepare_hyps)
+//   Lean           Prepared with the share arithmetic on the scalar unit and one Hyp in flight (k_scan_pairs: LEAN)
+//   Packed         Lean with level 1 on packed blocks of 64 survivors (pairs_cell_packed)
+//   PackedRecheck  Packed whose exact path re-checks the observations in the band alone (cells_survivors: Exact::Band)
+enum class PairsForm { General, Prepared, Lean, Packed, PackedRecheck };  // (each one builds on the one before it)
+constexpr bool prepared(PairsForm f) { return f >= PairsForm::Prepared; }
+constexpr bool lean(PairsForm f) { return f >= PairsForm::Lean; }
+constexpr bool packed(PairsForm f) { return f >= PairsForm::Packed; }
+constexpr bool recheck(PairsForm f) { return f == PairsForm::PackedRecheck; }
+//   General        vote bounds, surviving-cell counts and (cnt != nullptr) the padded survivor counts per (cell, group)
+//   Prepared       the same from prepared hypotheses
+//   Count          the padded survivor counts and nothing else, byte for byte what General writes
+//   PreparedCount  the same from prepared hypotheses
+//   PreparedMask   level 1's 64-bit survivor ballot of every (cell, group) instead of the count byte
+enum class BoundsForm { General, Prepared, Count, PreparedCount, PreparedMask };
+constexpr bool prepared(BoundsForm f) { return f != BoundsForm::General && f != BoundsForm::Count; }
+constexpr bool count(BoundsForm f) { return f >= BoundsForm::Count; }
+constexpr bool mask(BoundsForm f) { return f == BoundsForm::PreparedMask; }
+// The counting form whose table a form of k_scan_pairs reads (and k_tile_costs<packed(f)> sums).  The group forms read
+// count bytes and the packed forms read masks, each from hypotheses fetched the way the scan itself fetches them
+// (level 1 of the scan must repeat the counting pass bit for bit).  General reads the bytes of Count or, with
+// `count_only` = 0 (option "scan_lean" = 0), those of the General counting form: the same bytes.
+constexpr BoundsForm bounds_form(PairsForm f, bool count_only) {
+  switch (f) {
+    case PairsForm::General: return count_only ? BoundsForm::Count : BoundsForm::General;
+    case PairsForm::Prepared: return BoundsForm::Prepared;  // (chosen with "scan_lean" = 0 only)
+    case PairsForm::Lean: return BoundsForm::PreparedCount;
+    default: return BoundsForm::PreparedMask;
+  }
+}
+// Which (cell model, broadcast mode, form) exist.  A prepared form needs a cell model with PREPARED; the re-check reads
+// the pair's slots of the LDS broadcast area again, so it needs that area, and it is built in 3-D only: the 2-D plane's
+// 512-record kernel has no register for it (12 bytes of scratch per lane with it, none without).  (By the enum's
+// construction a form that rechecks is packed, a packed form is lean and a lean form is prepared; by bounds_form()
+// Packed reads PreparedMask's masks and Lean reads PreparedCount's bytes.)
+template <class CM, bool LDSB, PairsForm F>
+constexpr bool pairs_form_exists() {
+  return (!prepared(F) || cell_prepared<CM>()) && (!recheck(F) || (LDSB && CM::M::ND == 3));
+}
+template <class CM, BoundsForm F>
+constexpr bool bounds_form_exists() {
+  return !prepared(F) || cell_prepared<CM>();
+}
+
 // ---- level 2 of one (cell, group of 64 hypotheses): the surviving hypotheses of the group (bits of `surv`) against
 // the cell's observations held in registers.  bc[] are the lane's (= hypothesis') per-cell constants from level 1;
 // votes are added to lane b of accv for hypothesis b of the group.
@@ -1074,20 +1123,23 @@ __device__ __forceinline__ void cells_filter_squares(float (&bc)[NB]) {
   bc[NB - 1] = off ? __builtin_bit_cast(float, 0xFFFFFFFFu) : band;
 }
 
-// DUP (LDSB, NB = 6, NV = 4: the plane's lean scan): the two ADDENDS of the pair loop -- fp[3] and the filter's a -- lie
-// twice in the broadcast area, in the two halves of an aligned pair, so that the packed FMAs take them as they are read
-// (the compiler selects one half of a pair for both lanes in src0 / src1, not the high half in src2: a v_mov_b32 a pair).
-// PACKED (k_scan_pairs<..., PACK>): lane b holds survivor b of a packed block, hypothesis ids[b] of the batch and not
-// b of one group: spg is the batch's first row, and the exact path -- the only reader of the index -- takes it from
-// the block's id list in LDS.
+// Slots: how survivor b's values reach every lane.  Lanes: v_readlane from lane b's bc[].  Area: through the wave's LDS
+// broadcast area s_bc, 8 floats per lane.  AreaDup (NB = 6, NV = 4: the plane's lean scan): through the area with the
+// two ADDENDS of the pair loop -- fp[3] and the filter's a -- lying twice, in the two halves of an aligned pair, so that
+// the packed FMAs take them as they are read (the compiler selects one half of a pair for both lanes in src0 / src1, not
+// the high half in src2: a v_mov_b32 a pair).
+// Ids: which hypothesis lane b is.  Group: hypothesis b of the group whose first row is spg.  List (PairsForm::Packed):
+// survivor b of a packed block, hypothesis ids[b] of the batch: spg is the batch's first row, and the exact path -- the
+// only reader of the index -- takes it from the block's id list in LDS.
 // s_amb (k_scan_pairs; nullable): two counters of the workgroup in LDS, [0] += 1 per AMBIGUOUS pair -- a (hypothesis,
 // cell) pair with an observation in the band --, [1] += the observations the re-check found in the band (RECHECK only).
 // (LDS atomics, and one global atomic per workgroup at the kernel's end: the bench's step has ~50 000 ambiguous pairs,
 // and that many atomics on ONE global word serialise into 0.6 ms of L2 time -- measured: the step twice as long.
 // Words of the wave's own, read and written back without an atomic through a volatile pointer, were tried too: the
 // pointer stays generic, its two registers push the packed plane kernel into scratch.)
-// RECHECK (option "scan_recheck"; DUP only): an ambiguous pair re-evaluates the exact predicate for the observations IN
-// THE BAND and no others, instead of for the whole cell.  The eight d of a lane are not kept across the loop (the
+// Exact: what an ambiguous pair re-evaluates with the exact predicate.  Cell: the whole cell.  Band (option
+// "scan_recheck"; AreaDup only): the observations IN THE BAND and no others.
+// The eight d of a lane are not kept across the loop (the
 // registers are not there): the branch reads the pair's two slots again -- xs is live, slot b unchanged -- and repeats
 // the 16 packed FMAs, bit for bit.  inband = bits(d) <= band is the compare the minimum chain encodes (a negative d has
 // its sign bit set: never in the band).  Per value slot k: m = ballot(inband); m == 0 (wave-uniform) leaves in[k] alone;
@@ -1095,15 +1147,23 @@ __device__ __forceinline__ void cells_filter_squares(float (&bc)[NB]) {
 // && agree).  A value outside the band keeps the filter's decision d < 0, which is what the filter guarantees (|v32| <
 // t_in => agrees, |v32| >= t_out => does not; NaN rows: d < 0 false, agree false): every vote comes from the predicate
 // it came from before.  Filter off (band = 0xFFFFFFFF, a = 0): every d is non-negative or NaN, every bit pattern is
-// <= band, all 8 slots run for all lanes -- the whole-cell recount plus the recompute, slower than RECHECK = 0 by those
+// <= band, all 8 slots run for all lanes -- the whole-cell recount plus the recompute, slower than Exact::Cell by those
 // 16 FMAs a pair and nothing else.
-template <class CM, int PP, bool LDSB, bool DUP = false, bool PACKED = false, bool RECHECK = false>
+enum class Slots { Lanes, Area, AreaDup };
+enum class Ids { Group, List };
+enum class Exact { Cell, Band };
+// with the wave's broadcast area or without: the general forms' layout, and the lean and packed forms'
+constexpr Slots slots_plain(bool ldsb) { return ldsb ? Slots::Area : Slots::Lanes; }
+constexpr Slots slots_dup(bool ldsb) { return ldsb ? Slots::AreaDup : Slots::Lanes; }
+template <class CM, int PP, Slots SLOTS, Ids IDS = Ids::Group, Exact EXACT = Exact::Cell>
 __device__ __forceinline__ void cells_survivors(const v2f (&xs)[PP][4], const float (&bc)[CM::NB], float *s_bc,
                                                 unsigned long long surv, const int lane,
                                                 const double *__restrict__ sorted, const size_t ns, const size_t cell,
                                                 const double *__restrict__ spg, const ModelConsts &mc,
                                                 uint32_t &accv, const uint16_t *ids = nullptr,
                                                 uint32_t *s_amb = nullptr) {
+  constexpr bool LDSB = SLOTS != Slots::Lanes, DUP = SLOTS == Slots::AreaDup, PACKED = IDS == Ids::List,
+                 RECHECK = EXACT == Exact::Band;
   static_assert(!RECHECK || DUP, "the per-value re-check is built on the lean pair loop's slots");
   typedef typename CM::M M;
   constexpr int D = M::ND, NB = CM::NB, NV = CM::NV, SPD = M::SP, CP = 128 * PP;
@@ -1406,8 +1466,8 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(CPT == 1 ? (
         float bc[NB];
         unsigned long long surv = __ballot(CM::level1(hy, bx[q], ctr[q], cc, bc));
         cells_filter_squares(bc);
-        cells_survivors<CM, PP, LDSB>(xs[q], bc, s_bc, surv, lane, sorted, ns, (size_t)(wt * CPT + q),
-                                      sp + (size_t)h0 * SPD, mc, accv);
+        cells_survivors<CM, PP, slots_plain(LDSB)>(xs[q], bc, s_bc, surv, lane, sorted, ns, (size_t)(wt * CPT + q),
+                                             sp + (size_t)h0 * SPD, mc, accv);
       }
       if (accv) atomicAdd(&s_cnt[h], accv);  // h < H whenever accv != 0 (lanes past H never survive)
     }
@@ -1665,17 +1725,52 @@ __device__ __forceinline__ typename CM::Hyp hyp_from(const float4 (&v)[HypWords<
 // of its surviving cells -- an upper bound on its votes, every agreeing observation lies in a surviving cell --
 // and, per launch, the number of surviving (hypothesis, cell) pairs, i.e. what level 2 has to look at.
 // Lane = hypothesis; blockIdx.y * 4 + wave = group of 64 hypotheses; blockIdx.x = a run of cells.
-// PREP: Hyp comes from the batch's prepared block `hyps` (k_prepare_hyps) instead of load().
-// COUNT: the counting launch of the counted scan (option "scan_lean"): cnt is written and nothing else -- no
+// prepared(F): Hyp comes from the batch's prepared block `hyps` (k_prepare_hyps) instead of load().
+// count(F): the counting launch of the counted scan (option "scan_lean"): cnt is written and nothing else -- no
 // population, no surviving-cell count, ub / total / ncells_out are not looked at.  The survivor count is the population
 // count of level 1's own compare mask; a wave's bytes of a chunk of boxes sit at i * gstride from ONE scalar address,
 // and the four cells of an unrolled iteration are stored under one `lane == 0`.  cnt is byte for byte what the general
 // form writes.
-// MASK (COUNT only; option "scan_pack"): instead of the cnt byte the launch stores level 1's 64-bit survivor ballot of
+// mask(F) (option "scan_pack"): instead of the cnt byte the launch stores level 1's 64-bit survivor ballot of
 // every (cell, group) -- `cnt` then points to n_cells x gstride 64-bit words, [cell][group], so that lane g of a wave
-// of k_scan_pairs<..., PACK> reads the 64 masks of a cell with one 8-byte load per lane; lanes past the batch never
+// of the packed k_scan_pairs reads the 64 masks of a cell with one 8-byte load per lane; lanes past the batch never
 // survive (NaN), so their bits are 0.  Counts and costs are population counts of the masks (k_tile_costs<true>).
-template <class CM, int PP, bool PREP = false, bool COUNT = false, bool MASK = false>
+//
+// bounds_chunk: a wave's walk over the n boxes of a chunk in LDS for the forms that write a table and nothing else,
+// four boxes in flight and then the tail.  box(bx, ctr) is the form's value for one box; store(r...) takes the values of
+// the four boxes of an unrolled iteration, or of one box of the tail, in box order.  (The general form keeps the walk
+// written out: through bounds_chunk the sphere's kernels load eight bytes of the hypothesis' row twice.)
+template <class Box, class Store>
+__device__ __forceinline__ void bounds_chunk(const CellBox *s_box, const double (*s_ctr)[3], const uint32_t n, Box &&box,
+                                             Store &&store) {
+  uint32_t i = 0;
+  for (; i + 4 <= n; i += 4) {  // four boxes in flight
+    const CellBox b0 = s_box[i], b1 = s_box[i + 1], b2 = s_box[i + 2], b3 = s_box[i + 3];
+    const double t0[3] = {s_ctr[i][0], s_ctr[i][1], s_ctr[i][2]};
+    const double t1[3] = {s_ctr[i + 1][0], s_ctr[i + 1][1], s_ctr[i + 1][2]};
+    const double t2[3] = {s_ctr[i + 2][0], s_ctr[i + 2][1], s_ctr[i + 2][2]};
+    const double t3[3] = {s_ctr[i + 3][0], s_ctr[i + 3][1], s_ctr[i + 3][2]};
+    const auto r0 = box(b0, t0), r1 = box(b1, t1), r2 = box(b2, t2), r3 = box(b3, t3);
+    store(r0, r1, r2, r3);
+  }
+  for (; i < n; i++) {
+    const CellBox b0 = s_box[i];
+    const double t0[3] = {s_ctr[i][0], s_ctr[i][1], s_ctr[i][2]};
+    store(box(b0, t0));
+  }
+}
+// the results of consecutive boxes -> their rows of one column of the [box][group] table, under one `lane == 0`; returns
+// the column's next row
+template <class T, class... R>
+__device__ __forceinline__ T *bounds_put(T *p, const uint32_t gstride, const int lane, const R... r) {
+  const T v[] = {r...};
+  if (lane == 0) {
+#pragma unroll
+    for (uint32_t k = 0; k < (uint32_t)sizeof...(R); k++) p[k * gstride] = v[k];
+  }
+  return p + (uint32_t)sizeof...(R) * gstride;
+}
+template <class CM, int PP, BoundsForm F>
 __global__ __launch_bounds__(256) void k_cells_bounds(const CellBox *__restrict__ boxes, uint32_t ncells,
                                                       size_t ns, const float *__restrict__ rows,
                                                       const float *__restrict__ spf, uint32_t H,
@@ -1686,6 +1781,8 @@ __global__ __launch_bounds__(256) void k_cells_bounds(const CellBox *__restrict_
                                                       uint8_t *__restrict__ cnt, uint32_t gstride,
                                                       const uint32_t *__restrict__ h_dev, uint32_t h_off,
                                                       uint32_t box_pop, const float4 *__restrict__ hyps) {
+  static_assert(bounds_form_exists<CM, F>());
+  constexpr bool PREP = prepared(F), COUNT = count(F), MASK = mask(F);
   typedef typename CM::M M;
   constexpr int ROW = CM::ROW, NR4 = ROW / 4, NR2 = CM::ROW2 / 4;
   const size_t CP = box_pop;  // observations per box: 128 * PP for the cells, a multiple for merged boxes
@@ -1748,85 +1845,56 @@ __global__ __launch_bounds__(256) void k_cells_bounds(const CellBox *__restrict_
     __syncthreads();
     if (!active) continue;
     if constexpr (MASK) {
-      static_assert(COUNT, "the masks are written by the count-only form");
-      auto mask = [&](const CellBox &bx, const double (&ctr)[3]) {
-        float bc[CM::NB];
-        return (unsigned long long)__ballot(CM::level1(hy, bx, ctr, cc, bc));
-      };
       unsigned long long *p = (unsigned long long *)cnt + ((size_t)cb * gstride + grp);  // wave-uniform
-      uint32_t i = 0;
-      for (; i + 4 <= n; i += 4, p += 4 * gstride) {  // four boxes in flight
-        const CellBox b0 = s_box[i], b1 = s_box[i + 1], b2 = s_box[i + 2], b3 = s_box[i + 3];
-        const double t0[3] = {s_ctr[i][0], s_ctr[i][1], s_ctr[i][2]};
-        const double t1[3] = {s_ctr[i + 1][0], s_ctr[i + 1][1], s_ctr[i + 1][2]};
-        const double t2[3] = {s_ctr[i + 2][0], s_ctr[i + 2][1], s_ctr[i + 2][2]};
-        const double t3[3] = {s_ctr[i + 3][0], s_ctr[i + 3][1], s_ctr[i + 3][2]};
-        const unsigned long long m0 = mask(b0, t0), m1 = mask(b1, t1), m2 = mask(b2, t2), m3 = mask(b3, t3);
-        if (lane == 0) p[0] = m0, p[gstride] = m1, p[2 * gstride] = m2, p[3 * gstride] = m3;
-      }
-      for (; i < n; i++, p += gstride) {
-        const CellBox b0 = s_box[i];
-        const double t0[3] = {s_ctr[i][0], s_ctr[i][1], s_ctr[i][2]};
-        const unsigned long long m0 = mask(b0, t0);
-        if (lane == 0) p[0] = m0;
-      }
-      continue;
-    }
-    if constexpr (COUNT) {
-      // padded survivor count of the wave's group in one box: every lane of an active wave takes part in the compare
-      auto padded = [&](const CellBox &bx, const double (&ctr)[3]) {
-        float bc[CM::NB];
-        const uint32_t pc = (uint32_t)__builtin_popcountll(__ballot(CM::level1(hy, bx, ctr, cc, bc)));
-        return (uint8_t)(pc ? pc + kGroupPad : 0u);  // <= 64 + pad
-      };
+      bounds_chunk(
+          s_box, s_ctr, n,
+          [&](const CellBox &bx, const double(&ctr)[3]) {
+            float bc[CM::NB];
+            return (unsigned long long)__ballot(CM::level1(hy, bx, ctr, cc, bc));
+          },
+          [&](auto... m) { p = bounds_put(p, gstride, lane, m...); });
+    } else if constexpr (COUNT) {
       uint8_t *p = cnt + ((size_t)cb * gstride + grp);  // wave-uniform; the chunk's rows are < BCH * gstride away
+      bounds_chunk(
+          s_box, s_ctr, n,
+          // padded survivor count of the wave's group in one box: every lane of an active wave takes part in the compare
+          [&](const CellBox &bx, const double(&ctr)[3]) {
+            float bc[CM::NB];
+            const uint32_t pc = (uint32_t)__builtin_popcountll(__ballot(CM::level1(hy, bx, ctr, cc, bc)));
+            return (uint8_t)(pc ? pc + kGroupPad : 0u);  // <= 64 + pad
+          },
+          [&](auto... pc) { p = bounds_put(p, gstride, lane, pc...); });
+    } else {
+      auto one = [&](const uint32_t i, const CellBox &bx, const double (&ctr)[3]) {
+        const uint32_t c = cb + i;
+        float bc[CM::NB];
+        const bool s = CM::level1(hy, bx, ctr, cc, bc);
+        const size_t first = (size_t)c * CP;
+        const uint32_t pop = first + CP <= ns ? (uint32_t)CP : (uint32_t)(ns - first);
+        u += s ? pop : 0u;
+        nc += s ? 1u : 0u;
+        if (cnt) {  // survivors of this group in this cell: the cost table of k_scan_pairs
+          const uint32_t pc = (uint32_t)__builtin_popcountll(__ballot(s));
+          if (lane == 0) cnt[(size_t)c * gstride + grp] = (uint8_t)(pc ? pc + kGroupPad : 0u);  // <= 64 + pad
+        }
+      };
       uint32_t i = 0;
-      for (; i + 4 <= n; i += 4, p += 4 * gstride) {  // four boxes in flight
+      for (; i + 4 <= n; i += 4) {  // four boxes in flight
         const CellBox b0 = s_box[i], b1 = s_box[i + 1], b2 = s_box[i + 2], b3 = s_box[i + 3];
         const double t0[3] = {s_ctr[i][0], s_ctr[i][1], s_ctr[i][2]};
         const double t1[3] = {s_ctr[i + 1][0], s_ctr[i + 1][1], s_ctr[i + 1][2]};
         const double t2[3] = {s_ctr[i + 2][0], s_ctr[i + 2][1], s_ctr[i + 2][2]};
         const double t3[3] = {s_ctr[i + 3][0], s_ctr[i + 3][1], s_ctr[i + 3][2]};
-        const uint8_t p0 = padded(b0, t0), p1 = padded(b1, t1), p2 = padded(b2, t2), p3 = padded(b3, t3);
-        if (lane == 0) p[0] = p0, p[gstride] = p1, p[2 * gstride] = p2, p[3 * gstride] = p3;
+        one(i, b0, t0);
+        one(i + 1, b1, t1);
+        one(i + 2, b2, t2);
+        one(i + 3, b3, t3);
       }
-      for (; i < n; i++, p += gstride) {
+      for (; i < n; i++) {
         const CellBox b0 = s_box[i];
         const double t0[3] = {s_ctr[i][0], s_ctr[i][1], s_ctr[i][2]};
-        const uint8_t p0 = padded(b0, t0);
-        if (lane == 0) p[0] = p0;
+        one(i, b0, t0);
       }
-      continue;
-    }
-    auto one = [&](const uint32_t i, const CellBox &bx, const double (&ctr)[3]) {
-      const uint32_t c = cb + i;
-      float bc[CM::NB];
-      const bool s = CM::level1(hy, bx, ctr, cc, bc);
-      const size_t first = (size_t)c * CP;
-      const uint32_t pop = first + CP <= ns ? (uint32_t)CP : (uint32_t)(ns - first);
-      u += s ? pop : 0u;
-      nc += s ? 1u : 0u;
-      if (cnt) {  // survivors of this group in this cell: the cost table of k_scan_pairs
-        const uint32_t pc = (uint32_t)__builtin_popcountll(__ballot(s));
-        if (lane == 0) cnt[(size_t)c * gstride + grp] = (uint8_t)(pc ? pc + kGroupPad : 0u);  // <= 64 + pad
-      }
-    };
-    uint32_t i = 0;
-    for (; i + 4 <= n; i += 4) {  // four boxes in flight
-      const CellBox b0 = s_box[i], b1 = s_box[i + 1], b2 = s_box[i + 2], b3 = s_box[i + 3];
-      const double t0[3] = {s_ctr[i][0], s_ctr[i][1], s_ctr[i][2]};
-      const double t1[3] = {s_ctr[i + 1][0], s_ctr[i + 1][1], s_ctr[i + 1][2]};
-      const double t2[3] = {s_ctr[i + 2][0], s_ctr[i + 2][1], s_ctr[i + 2][2]};
-      const double t3[3] = {s_ctr[i + 3][0], s_ctr[i + 3][1], s_ctr[i + 3][2]};
-      one(i, b0, t0);
-      one(i + 1, b1, t1);
-      one(i + 2, b2, t2);
-      one(i + 3, b3, t3);
-    }
-    for (; i < n; i++) {
-      const CellBox b0 = s_box[i];
-      const double t0[3] = {s_ctr[i][0], s_ctr[i][1], s_ctr[i][2]};
-      one(i, b0, t0);
     }
   }
   if constexpr (COUNT) return;
@@ -1861,7 +1929,7 @@ constexpr uint32_t kChunkCells = 128;
 // wave as if it were free (measured before the padding: one wave walking 574 groups for 662 pairs, 1.5 ms against a
 // mean of 0.44 ms).
 //
-// PACK (option "scan_pack"): `cnt` holds the survivor MASKS of the counting pass (k_cells_bounds<..., MASK>) and the
+// PACK (option "scan_pack"): `cnt` holds the survivor MASKS of the counting pass (BoundsForm::PreparedMask) and the
 // enumeration is cell-major, inside a cell the dense order of its S survivors (group-major, lane-minor).  A wave
 // evaluates level 1 once per packed block of 64 consecutive survivors, so the cell's units are
 //   kCellPad | kBlockPad, survivors 0..63 | kBlockPad, survivors 64..127 | ...       (pack_cell_cost, pack_first)
@@ -1952,7 +2020,7 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v, int lane) {
 
 // the same on the data-parallel path of the vector unit: four shifts inside the rows of 16 lanes, then lane 15 of
 // row 0 / 2 into row 1 / 3 and lane 31 into rows 2 and 3; lanes without a source add 0.  Needs neither the lane
-// index nor LDS (the per-cell prefix of k_scan_pairs<..., PACK>, whose loop has no registers to spare)
+// index nor LDS (the per-cell prefix of pairs_cell_packed, whose loop has no registers to spare)
 __device__ __forceinline__ uint32_t wave_incl_scan_dpp(uint32_t v) {
   v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false);  // row_shr:1
   v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false);  // row_shr:2
@@ -1963,16 +2031,37 @@ __device__ __forceinline__ uint32_t wave_incl_scan_dpp(uint32_t v) {
   return v;
 }
 
-// LEAN (option "scan_lean"; prepared hypotheses only): the same enumeration with
-//   - the share arithmetic on the scalar unit: skip, budget and cell are wave-uniform and are made so for the compiler
-//     (readfirstlane), and a wave's part of a group is worked out in cost units (no saturating subtraction, which
-//     exists on the vector unit only), so lo / hi, their compares and the two bit-peeling loops are scalar code;
-//   - ONE Hyp, refilled for group k + 1 as soon as level 1 of group k has read it: the prefetched block is never
-//     copied (the general form moves it into level 1's registers and back, twelve 64-bit moves a group);
-//   - the pair loop's two addends twice in the broadcast area (cells_survivors<..., DUP>).
-// Which bits of a survivor mask a wave keeps, and with them every vote, are those of the general form.
-//
-// PACK (option "scan_pack"; on top of LEAN): level 1 with lane = hypothesis is run on PACKED blocks of 64 consecutive
+// ---- k_scan_pairs: the packed cell walker, the kernel -----------------------------------------------------------------
+// What a wave of k_scan_pairs knows for the whole launch and pairs_cell_packed reads: arguments of the kernel and the
+// wave's areas in LDS.
+struct PairsWave {
+  const double *sorted;
+  size_t ns;
+  const double *sp;
+  uint32_t G;  // the batch's groups of 64 hypotheses
+  const ModelConsts &mc;
+  const CellConsts &cc;
+  const uint8_t *cnt;  // the counting pass' masks
+  uint32_t gstride;
+  const float4 *hyps;
+  int lane;
+  uint32_t *s_cnt;  // votes of the workgroup
+  float *s_bc;      // the wave's broadcast area (LDSB)
+  uint32_t *s_amb;  // the workgroup's two counters of ambiguous pairs / band observations, or nullptr
+  uint16_t *s_id;   // the wave's two id lists
+};
+
+// the prepared Hyp of hypothesis `id` of the batch
+template <class CM>
+__device__ __forceinline__ typename CM::Hyp hyp_gather(const float4 *__restrict__ hyps, const uint32_t id) {
+  constexpr int NR4 = HypWords<CM>::N4;
+  float4 r[NR4];
+#pragma unroll
+  for (int k = 0; k < NR4; k++) r[k] = hyps[(size_t)id * NR4 + k];
+  return hyp_from<CM>(r);
+}
+
+// Packed (option "scan_pack"; on top of Lean): level 1 with lane = hypothesis is run on PACKED blocks of 64 consecutive
 // survivors of the cell's dense order (group-major, lane-minor) instead of on every group of 64 with a survivor --
 // at 4096 hypotheses in key order a group holds 11 survivors on average, the other 53 lanes compute, load and store
 // for nothing.  `cnt` holds the counting pass' survivor masks ([cell][group], 64-bit).  Per cell opened: lane g loads
@@ -1984,12 +2073,77 @@ __device__ __forceinline__ uint32_t wave_incl_scan_dpp(uint32_t v) {
 // lean form with surv = the low `n` bits (level 1 repeats the counting pass bit for bit: every lane of the block
 // survives), votes go to s_cnt[id].  The next block's ids and Hyp are fetched as soon as level 1 has read this one's.
 // Which wave counts which pair differs from the group forms; votes are integer sums and do not.
-//
+// EXACT: Exact::Band (PairsForm::PackedRecheck, option "scan_recheck") re-checks the observations in the band alone.
+// [jlo, jhi): the wave's part of the cell's dense order, not empty.
+template <class CM, int PP, bool LDSB, Exact EXACT>
+__device__ __forceinline__ void pairs_cell_packed(const PairsWave &w, const uint32_t cell, const CellBox &bx,
+                                                  const double (&ctr)[3], const v2f (&xs)[PP][4], const uint32_t jlo,
+                                                  const uint32_t jhi) {
+  constexpr int NB = CM::NB;
+  const uint32_t G = w.G;
+  const int lane = w.lane;
+  uint16_t *const s_id = w.s_id;
+  // survivor mask of group `lane` (fetched with the cell's observations in flight) and the exclusive prefix of the
+  // population counts = rank of the group's first survivor in the dense order (~0 for a group without
+  // survivors: it overlaps no block).  The cell's row of masks has a scalar base and a 32-bit lane offset
+  // (written plainly, cnt + 8 * lane is hoisted out of the cell loop as a 64-bit address per lane: two registers
+  // the loop does not have)
+  const unsigned long long ra = (unsigned long long)w.cnt + ((unsigned long long)cell * w.gstride << 3);
+  const unsigned long long *row = (const unsigned long long *)(
+      (unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(ra >> 32)) << 32 |
+      (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)ra));
+  const unsigned long long pm = (uint32_t)lane < G ? row[(uint32_t)lane] : 0ull;
+  const uint32_t pc = (uint32_t)__builtin_popcountll(pm);
+  const uint32_t incl = wave_incl_scan_dpp(pc);  // (every lane takes part)
+  const uint32_t excl = pc ? incl - pc : ~0u;
+  // ids of the block [base, base + 64) -> list, lane's own id back.  The groups that overlap it: from the one that
+  // holds rank `base` -- the last non-empty group that starts at or below it -- to the last that starts inside
+  auto block_ids = [&](const uint32_t base, uint16_t *list) {
+    const unsigned long long upto = __ballot(excl <= base);  // (never 0: base < S)
+    unsigned long long ov = __ballot(excl < base + 64) & (~0ull << (63 - __builtin_clzll(upto)));
+    while (ov) {
+      const int g = __builtin_ctzll(ov);
+      ov &= ov - 1;
+      const uint32_t mlo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)pm, g),
+                     mhi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(pm >> 32), g);
+      // rank - base of the group's set lanes (wraps below the block: not < 64)
+      const uint32_t r = (uint32_t)__builtin_amdgcn_readlane((int)excl, g) - base;
+      const uint32_t slot = __builtin_amdgcn_mbcnt_hi(mhi, __builtin_amdgcn_mbcnt_lo(mlo, r));
+      if (__builtin_amdgcn_inverse_ballot_w64((unsigned long long)mhi << 32 | mlo) && slot < 64)
+        list[slot] = (uint16_t)((uint32_t)g * 64 + (uint32_t)lane);
+    }
+    __builtin_amdgcn_wave_barrier();  // (one wave: LDS keeps its order, the compiler must too)
+    return (uint32_t)list[lane];
+  };
+  uint32_t base = jlo, par = 0;  // the block's list: s_id + par
+  typename CM::Hyp hy = hyp_gather<CM>(w.hyps, block_ids(base, s_id));
+  for (;;) {
+    // (64 - min(., 64) is a saturating subtraction, the vector unit's: the shift count back to a scalar register)
+    const uint32_t n = jhi - base < 64 ? jhi - base : 64;
+    const unsigned long long surv = ~0ull >> (uint32_t)__builtin_amdgcn_readfirstlane((int)(64 - n));
+    float bc[NB];
+    (void)CM::level1(hy, bx, ctr, w.cc, bc);  // true in the n lanes of the block: the counting pass said so
+    base += 64;
+    const bool more = base < jhi;
+    // the next block's ids and Hyp meanwhile (level 1 was the only reader of this one's)
+    if (more) hy = hyp_gather<CM>(w.hyps, block_ids(base, s_id + (par ^ 64)));
+    cells_filter_squares(bc);
+    uint32_t accv = 0;
+    cells_survivors<CM, PP, slots_dup(LDSB), Ids::List, EXACT>(
+        xs, bc, w.s_bc, surv, lane, w.sorted, w.ns, (size_t)cell, w.sp, w.mc, accv, s_id + par, w.s_amb);
+    if (accv) atomicAdd(&w.s_cnt[s_id[par + lane]], accv);
+    if (!more) break;
+    par ^= 64;
+  }
+}
+
+// The kernel: set-up, the search for the wave's share, the cell loop, the flush.  The cell loop finds what of a cell is
+// the wave's, opens the cell (box, centre, observations) and walks it: the packed forms in pairs_cell_packed, the lean
+// and the general group loops in place -- moved into functions of their own, they and the share search compile to other
+// instruction streams.
 // ambc: the context's counters of ambiguous pairs and band observations (cells_survivors: s_amb), kAmbSlots pairs of
-// words: a workgroup adds its two LDS counters to pair blockIdx.x % kAmbSlots when it ends.  RECHECK (option
-// "scan_recheck"; PACK with the broadcast area only): the exact path re-checks the observations in the band alone.
-template <class CM, int PP, int BS, bool LDSB, bool PREP = false, bool LEAN = false, bool PACK = false,
-          bool RECHECK = false>
+// words: a workgroup adds its two LDS counters to pair blockIdx.x % kAmbSlots when it ends.
+template <class CM, int PP, int BS, bool LDSB, PairsForm F>
 __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(PP >= 8 ? 4 : CM::MIN_WAVES, 8))) void k_scan_pairs(
     const double *__restrict__ sorted, size_t ns, const CellBox *__restrict__ boxes, uint32_t ncells,
     const double *__restrict__ sp, const float *__restrict__ rows, const float *__restrict__ spf, uint32_t H,
@@ -1997,7 +2151,8 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(PP >= 8 ? 4 
     const uint32_t *__restrict__ h_dev, const uint8_t *__restrict__ cnt, uint32_t gstride, const uint32_t *__restrict__ cost,
     const uint32_t *__restrict__ csum, uint32_t nchunks, uint32_t h_off, const float4 *__restrict__ hyps,
     unsigned long long *__restrict__ ambc) {
-  static_assert(!RECHECK || (PACK && LDSB), "the per-value re-check is built into the packed form");
+  static_assert(pairs_form_exists<CM, LDSB, F>());
+  constexpr bool PREP = prepared(F), LEAN = lean(F), PACK = packed(F);
   typedef typename CM::M M;
   constexpr int NB = CM::NB;
   constexpr int SPD = M::SP;
@@ -2031,7 +2186,6 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(PP >= 8 ? 4 
   // entry of the prepared block
   [[maybe_unused]] uint16_t *s_id = nullptr;
   if constexpr (PACK) {
-    static_assert(LEAN && PREP, "packed blocks gather prepared hypotheses and run the lean pair loop");
     s_id = (uint16_t *)((float *)(s_cnt + ((H + 3) & ~3u)) + (LDSB ? (size_t)(BS / 64) * 512 : 0)) +
            (size_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) * 128;
     s_id[lane] = 0, s_id[64 + lane] = 0;
@@ -2111,6 +2265,7 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(PP >= 8 ? 4 
       }
     }
   };
+  [[maybe_unused]] const PairsWave w = {sorted, ns, sp, G, mc, cc, cnt, gstride, hyps, lane, s_cnt, s_bc, s_amb, s_id};
   while (budget && cell < ncells) {
     [[maybe_unused]] uint32_t ccost = 0;  // PACK: the cell's cost
     // jump over cells nothing survives in
@@ -2190,71 +2345,22 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(PP >= 8 ? 4 
     v2f xs[PP][4];
     cells_load<CM, PP>(sorted, ns, (size_t)cell, lane, ctr, xs);
     if constexpr (PACK) {
-      // survivor mask of group `lane` (fetched with the cell's observations in flight) and the exclusive prefix of the
-      // population counts = rank of the group's first survivor in the dense order (~0 for a group without
-      // survivors: it overlaps no block).  The cell's row of masks has a scalar base and a 32-bit lane offset
-      // (written plainly, cnt + 8 * lane is hoisted out of the cell loop as a 64-bit address per lane: two registers
-      // the loop does not have)
-      const unsigned long long ra = (unsigned long long)cnt + ((unsigned long long)cell * gstride << 3);
-      const unsigned long long *row = (const unsigned long long *)(
-          (unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(ra >> 32)) << 32 |
-          (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)ra));
-      const unsigned long long pm = (uint32_t)lane < G ? row[(uint32_t)lane] : 0ull;
-      const uint32_t pc = (uint32_t)__builtin_popcountll(pm);
-      const uint32_t incl = wave_incl_scan_dpp(pc);  // (every lane takes part)
-      const uint32_t excl = pc ? incl - pc : ~0u;
-      // ids of the block [base, base + 64) -> list, lane's own id back.  The groups that overlap it: from the one that
-      // holds rank `base` -- the last non-empty group that starts at or below it -- to the last that starts inside
-      auto block_ids = [&](const uint32_t base, uint16_t *list) {
-        const unsigned long long upto = __ballot(excl <= base);  // (never 0: base < S)
-        unsigned long long ov = __ballot(excl < base + 64) & (~0ull << (63 - __builtin_clzll(upto)));
-        while (ov) {
-          const int g = __builtin_ctzll(ov);
-          ov &= ov - 1;
-          const uint32_t mlo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)pm, g),
-                         mhi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(pm >> 32), g);
-          // rank - base of the group's set lanes (wraps below the block: not < 64)
-          const uint32_t r = (uint32_t)__builtin_amdgcn_readlane((int)excl, g) - base;
-          const uint32_t slot = __builtin_amdgcn_mbcnt_hi(mhi, __builtin_amdgcn_mbcnt_lo(mlo, r));
-          if (__builtin_amdgcn_inverse_ballot_w64((unsigned long long)mhi << 32 | mlo) && slot < 64)
-            list[slot] = (uint16_t)((uint32_t)g * 64 + (uint32_t)lane);
-        }
-        __builtin_amdgcn_wave_barrier();  // (one wave: LDS keeps its order, the compiler must too)
-        return (uint32_t)list[lane];
-      };
-      auto gather = [&](const uint32_t id) {
-        float4 r[NR4];
-#pragma unroll
-        for (int k = 0; k < NR4; k++) r[k] = hyps[(size_t)id * NR4 + k];
-        return hyp_from<CM>(r);
-      };
-      uint32_t base = jlo, par = 0;  // the block's list: s_id + par
-      typename CM::Hyp hy = gather(block_ids(base, s_id));
-      for (;;) {
-        // (64 - min(., 64) is a saturating subtraction, the vector unit's: the shift count back to a scalar register)
-        const uint32_t n = jhi - base < 64 ? jhi - base : 64;
-        const unsigned long long surv = ~0ull >> (uint32_t)__builtin_amdgcn_readfirstlane((int)(64 - n));
-        float bc[NB];
-        (void)CM::level1(hy, bx, ctr, cc, bc);  // true in the n lanes of the block: the counting pass said so
-        base += 64;
-        const bool more = base < jhi;
-        // the next block's ids and Hyp meanwhile (level 1 was the only reader of this one's)
-        if (more) hy = gather(block_ids(base, s_id + (par ^ 64)));
-        cells_filter_squares(bc);
-        uint32_t accv = 0;
-        cells_survivors<CM, PP, LDSB, LDSB, true, RECHECK>(xs, bc, s_bc, surv, lane, sorted, ns, (size_t)cell, sp, mc,
-                                                           accv, s_id + par, s_amb);
-        if (accv) atomicAdd(&s_cnt[s_id[par + lane]], accv);
-        if (!more) break;
-        par ^= 64;
-      }
+      pairs_cell_packed<CM, PP, LDSB, recheck(F) ? Exact::Band : Exact::Cell>(w, cell, bx, ctr, xs, jlo, jhi);
       cell++;
       continue;
     }
     if constexpr (LEAN) {
+      // Lean (option "scan_lean"; prepared hypotheses only): the same enumeration with
+      //   - the share arithmetic on the scalar unit: skip, budget and cell are wave-uniform and are made so for the compiler
+      //     (readfirstlane), and a wave's part of a group is worked out in cost units (no saturating subtraction, which
+      //     exists on the vector unit only), so lo / hi, their compares and the two bit-peeling loops are scalar code;
+      //   - ONE Hyp, refilled for group k + 1 as soon as level 1 of group k has read it: the prefetched block is never
+      //     copied (the general form moves it into level 1's registers and back, twelve 64-bit moves a group);
+      //   - the pair loop's two addends twice in the broadcast area (cells_survivors: Slots::AreaDup).
+      // Which bits of a survivor mask a wave keeps, and with them every vote, are those of the general form.
+      //
       // level 1 is the only reader of a group's Hyp and comes first, so the next group's Hyp is fetched into the
       // registers it has just read -- as far ahead of its use, but for level 1 itself, as a second buffer would have it
-      static_assert(PREP, "the lean group loop is built for prepared hypotheses");
       typename CM::Hyp hy;
       {
         float4 r[NR4], r2[1];
@@ -2293,8 +2399,8 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(PP >= 8 ? 4 
           surv = keep;
         }
         uint32_t accv = 0;
-        cells_survivors<CM, PP, LDSB, LDSB>(xs, bc, s_bc, surv, lane, sorted, ns, (size_t)cell, sp + (size_t)h0 * SPD,
-                                            mc, accv, nullptr, s_amb);
+        cells_survivors<CM, PP, slots_dup(LDSB)>(xs, bc, s_bc, surv, lane, sorted, ns, (size_t)cell,
+                                                   sp + (size_t)h0 * SPD, mc, accv, nullptr, s_amb);
         if (accv) atomicAdd(&s_cnt[h], accv);
       }
       cell++;
@@ -2345,8 +2451,8 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(PP >= 8 ? 4 
         surv = keep;
       }
       uint32_t accv = 0;
-      cells_survivors<CM, PP, LDSB>(xs, bc, s_bc, surv, lane, sorted, ns, (size_t)cell, sp + (size_t)h0 * SPD, mc,
-                                    accv, nullptr, s_amb);
+      cells_survivors<CM, PP, slots_plain(LDSB)>(xs, bc, s_bc, surv, lane, sorted, ns, (size_t)cell, sp + (size_t)h0 * SPD,
+                                           mc, accv, nullptr, s_amb);
       if (accv) atomicAdd(&s_cnt[h], accv);
     }
     cell++;

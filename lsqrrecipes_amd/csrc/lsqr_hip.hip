@@ -233,8 +233,8 @@ struct lsqr_ctx {
   DevBuf<uint32_t> d_paircost; // [n_cells cell costs | chunk sums]
   DevBuf<uint32_t> d_vpart;    // per-workgroup partial votes of k_scan_pairs
   DevBuf<float4> d_hyps;       // k_prepare_hyps: CM::Hyp of every hypothesis of the batch k_scan_pairs is counting
-  int opt_lean = 1;               // 1: count-only counting pass, k_scan_pairs<..., LEAN> for prepared models; 0: the general forms (A/B)
-  DevBuf<unsigned long long> d_pairmask;  // k_scan_pairs<..., PACK>: level 1's survivor mask per (cell, group of 64 hypotheses)
+  int opt_lean = 1;               // 1: count-only counting pass, PairsForm::Lean for prepared models; 0: the general forms (A/B)
+  DevBuf<unsigned long long> d_pairmask;  // PairsForm::Packed: level 1's survivor mask per (cell, group of 64 hypotheses)
   int opt_pack = 1;               // 1: level 1 of the lean k_scan_pairs on packed blocks of 64 survivors; 0: per group (A/B)
   int opt_recheck = 1;            // 1: the packed k_scan_pairs re-checks the band's observations alone; 0: the whole cell (A/B)
   DevBuf<unsigned long long> d_ambcnt;  // k_scan_pairs: kAmbSlots x {ambiguous pairs, band observations} of the last scan
@@ -1051,13 +1051,43 @@ int run_cells_bounds(lsqr_ctx *c, uint32_t *d_ub, uint32_t *d_nc = nullptr) {
   unsigned gx = std::max(1u, std::min<unsigned>(nbox, 2048u / gy));
   const uint32_t per = (nbox + gx - 1) / gx;
   gx = (nbox + per - 1) / per;
-  hipLaunchKernelGGL((k_cells_bounds<CM, PP>), dim3(gx, gy), dim3(256), 0, c->stream, boxes, nbox, c->n_sorted,
+  hipLaunchKernelGGL((k_cells_bounds<CM, PP, BoundsForm::General>), dim3(gx, gy), dim3(256), 0, c->stream, boxes, nbox,
+                     c->n_sorted,
                      CM::ROW_F32 ? c->d_hparams_f32 : (const float *)c->d_hparams.get(), c->d_hparams_f32,
                      (uint32_t)c->H, cc, per, d_ub, d_nc ? c->d_counter + CNT_PAIRS : (unsigned long long *)nullptr, d_nc,
                      (uint8_t *)nullptr, 0u, (const uint32_t *)nullptr, 0u,  // (pair total: diagnostics only -- 8192
                      (uint32_t)(128 * PP) * merge, (const float4 *)nullptr);  // atomics on one address are ~100 us)
   HIPCHK(c, hipGetLastError());
   return LSQR_OK;
+}
+
+// The form of the counted scan (cells.h: PairsForm) a launch takes, from the cell model, the broadcast mode and the
+// options "scan_prepared", "scan_lean", "scan_pack", "scan_recheck"; which forms exist for a cell model and a broadcast
+// mode is cells.h' rule (pairs_form_exists).
+template <class CM>
+PairsForm pairs_form(bool ldsb, bool opt_prepared, bool opt_lean, bool opt_pack, bool opt_recheck) {
+  if (!cell_prepared<CM>() || !opt_prepared) return PairsForm::General;
+  if (!opt_lean) return PairsForm::Prepared;
+  if (!opt_pack) return PairsForm::Lean;
+  const bool can_recheck = ldsb && pairs_form_exists<CM, true, PairsForm::PackedRecheck>();
+  return can_recheck && opt_recheck ? PairsForm::PackedRecheck : PairsForm::Packed;
+}
+// f(form, ldsb) with both as compile-time constants, for the forms that exist (pairs_form_exists): PackedRecheck for the
+// 3-D plane with the broadcast area, the other prepared forms for the cell models with PREPARED, General for every one
+template <class CM, class F>
+int with_pairs_form(PairsForm form, bool ldsb, F &&f) {
+  auto go = [&](auto fc) { return ldsb ? f(fc, std::true_type{}) : f(fc, std::false_type{}); };
+  if constexpr (cell_prepared<CM>()) {
+    if constexpr (pairs_form_exists<CM, true, PairsForm::PackedRecheck>()) {
+      if (form == PairsForm::PackedRecheck && ldsb)
+        return f(std::integral_constant<PairsForm, PairsForm::PackedRecheck>{}, std::true_type{});
+    }
+    if (form == PairsForm::Packed) return go(std::integral_constant<PairsForm, PairsForm::Packed>{});
+    if (form == PairsForm::Lean) return go(std::integral_constant<PairsForm, PairsForm::Lean>{});
+    if (form == PairsForm::Prepared) return go(std::integral_constant<PairsForm, PairsForm::Prepared>{});
+  }
+  if (form == PairsForm::General) return go(std::integral_constant<PairsForm, PairsForm::General>{});
+  return LSQR_ERR_INVALID;  // (pairs_form() does not choose a form that is not built)
 }
 
 // Level 2 of a (compacted) batch in statically balanced pieces (cells.h, "statically balanced level 2"): count the
@@ -1092,11 +1122,14 @@ int run_scan_pairs(lsqr_ctx *c, const ScanBatch &b0) {
   if ((st = ensure(c, c->d_paircost, (size_t)c->n_cells + nchunks)) != LSQR_OK) return st;
   uint32_t *d_cost = c->d_paircost, *d_csum = c->d_paircost + c->n_cells;
   const float *rows = CM::ROW_F32 ? b.spf : (const float *)b.sp;
+  bool ldsb_default = CM::LDS_BROADCAST;
+  if constexpr (requires { CM::LDS_BROADCAST_PAIRS; }) ldsb_default = CM::LDS_BROADCAST_PAIRS;
+  const bool ldsb = c->opt_block == 257 || (c->opt_block == 0 && ldsb_default);
+  // the form, once: the counting pass, k_tile_costs, the LDS size and k_scan_pairs below all read it
+  const PairsForm form = pairs_form<CM>(ldsb, c->opt_prepared, c->opt_lean, c->opt_pack, c->opt_recheck);
   // the hypothesis-only part of level 1 once per batch instead of once per (cell, group): both kernels below read it
-  constexpr bool kPrep = cell_prepared<CM>();
-  const bool prep = kPrep && c->opt_prepared;
-  if constexpr (kPrep) {
-    if (prep) {
+  if constexpr (cell_prepared<CM>()) {
+    if (prepared(form)) {
       const uint32_t slots = (Hc + 63) & ~63u;  // whole groups
       if ((st = ensure(c, c->d_hyps, (size_t)slots * HypWords<CM>::N4)) != LSQR_OK) return st;
       hipLaunchKernelGGL((k_prepare_hyps<CM>), dim3((slots + 255) / 256), dim3(256), 0, c->stream, rows, b.spf, Hc, cc,
@@ -1104,52 +1137,40 @@ int run_scan_pairs(lsqr_ctx *c, const ScanBatch &b0) {
       HIPCHK(c, hipGetLastError());
     }
   }
-  const float4 *hyps = prep ? c->d_hyps : nullptr;
-  // packed blocks (cells.h: k_scan_pairs<..., PACK>): the counting pass leaves survivor masks instead of counts
-  const bool pack = prep && c->opt_lean && c->opt_pack;
-  if (pack && (st = ensure(c, c->d_pairmask, (size_t)c->n_cells * gstride)) != LSQR_OK) return st;
-  uint8_t *d_cnt = pack ? (uint8_t *)c->d_pairmask.get() : c->d_paircnt.get();
-  {  // counting pass: waves past the device-side H leave at once, so the grid is cut finely in x
-    const unsigned gy = (Hc + 255) / 256;
-    const uint32_t per = std::max<uint32_t>(8, (c->n_cells + 1023) / 1024);
-    const unsigned gx = (c->n_cells + per - 1) / per;
-    auto count = [&](auto kern) {
-      hipLaunchKernelGGL(kern, dim3(gx, gy), dim3(256), 0, c->stream, c->d_boxes, c->n_cells, c->n_sorted, rows, b.spf,
-                         Hc, cc, per, (uint32_t *)nullptr, (unsigned long long *)nullptr, (uint32_t *)nullptr,
-                         d_cnt, gstride, b.h_dev, b.h_off, (uint32_t)(128 * PP), hyps);
-    };
-    if (pack) {  // masks and nothing else
-      if constexpr (kPrep) count(k_cells_bounds<CM, PP, true, true, true>);
-    } else if (c->opt_lean) {  // cnt and nothing else
-      if (prep)
-        count(k_cells_bounds<CM, PP, kPrep, true>);
-      else
-        count(k_cells_bounds<CM, PP, false, true>);
-    } else if (prep)
-      count(k_cells_bounds<CM, PP, kPrep>);
-    else
-      count(k_cells_bounds<CM, PP>);
-    HIPCHK(c, hipGetLastError());
-  }
-  auto costs = [&](auto kern) {
-    hipLaunchKernelGGL(kern, dim3(nchunks), dim3(kChunkCells), 0, c->stream, (const uint8_t *)d_cnt, gstride, Hc,
-                       b.h_dev, c->n_cells, d_cost, d_csum, b.votes, b.h_off,  // (zeroes the batch's votes)
-                       c->amb_reset ? c->d_ambcnt.get() : (unsigned long long *)nullptr);
-    c->amb_reset = false;
-    c->amb_counted = kPrep && M::ND == 3;  // (k_scan_pairs counts for the 3-D plane)
-  };
-  if (pack)
-    costs(k_tile_costs<true>);
-  else
-    costs(k_tile_costs<false>);
-  HIPCHK(c, hipGetLastError());
-  bool ldsb_default = CM::LDS_BROADCAST;
-  if constexpr (requires { CM::LDS_BROADCAST_PAIRS; }) ldsb_default = CM::LDS_BROADCAST_PAIRS;
-  const bool ldsb = c->opt_block == 257 || (c->opt_block == 0 && ldsb_default);
+  const float4 *hyps = prepared(form) ? c->d_hyps : nullptr;
+  // packed blocks (cells.h: pairs_cell_packed): the counting pass leaves survivor masks instead of counts
+  if (packed(form) && (st = ensure(c, c->d_pairmask, (size_t)c->n_cells * gstride)) != LSQR_OK) return st;
+  uint8_t *d_cnt = packed(form) ? (uint8_t *)c->d_pairmask.get() : c->d_paircnt.get();
   constexpr int BS = 256, wpb = BS / 64;
   const size_t lds = (size_t)((Hc + 3) & ~3u) * sizeof(uint32_t) + (ldsb ? (size_t)wpb * 2048 : 0) +
-                     (pack ? (size_t)wpb * 256 : 0);  // votes | broadcast areas | id lists of the packed blocks
-  auto launch = [&](auto kern) -> int {
+                     (packed(form) ? (size_t)wpb * 256 : 0);  // votes | broadcast areas | id lists of the packed blocks
+  return with_pairs_form<CM>(form, ldsb, [&](auto form_c, auto ldsb_c) -> int {
+    constexpr PairsForm F = decltype(form_c)::value;
+    constexpr bool LDSB = decltype(ldsb_c)::value;
+    {  // counting pass: waves past the device-side H leave at once, so the grid is cut finely in x
+      const unsigned gy = (Hc + 255) / 256;
+      const uint32_t per = std::max<uint32_t>(8, (c->n_cells + 1023) / 1024);
+      const unsigned gx = (c->n_cells + per - 1) / per;
+      auto count = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3(gx, gy), dim3(256), 0, c->stream, c->d_boxes, c->n_cells, c->n_sorted, rows, b.spf,
+                           Hc, cc, per, (uint32_t *)nullptr, (unsigned long long *)nullptr, (uint32_t *)nullptr,
+                           d_cnt, gstride, b.h_dev, b.h_off, (uint32_t)(128 * PP), hyps);
+      };
+      // (General alone has two counting forms, and "scan_lean" says which: an option's value cannot be a template
+      // argument, so it is read once more here; for the other forms both branches name the same kernel)
+      if (c->opt_lean)  // masks, or cnt, and nothing else
+        count(k_cells_bounds<CM, PP, bounds_form(F, true)>);
+      else
+        count(k_cells_bounds<CM, PP, bounds_form(F, false)>);
+      HIPCHK(c, hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_tile_costs<packed(F)>, dim3(nchunks), dim3(kChunkCells), 0, c->stream, (const uint8_t *)d_cnt,
+                       gstride, Hc, b.h_dev, c->n_cells, d_cost, d_csum, b.votes, b.h_off,  // (zeroes the batch's votes)
+                       c->amb_reset ? c->d_ambcnt.get() : (unsigned long long *)nullptr);
+    c->amb_reset = false;
+    c->amb_counted = cell_prepared<CM>() && M::ND == 3;  // (k_scan_pairs counts for the 3-D plane)
+    HIPCHK(c, hipGetLastError());
+    const auto kern = k_scan_pairs<CM, PP, BS, LDSB, F>;
     int per_cu = (int)std::min<size_t>(32 / wpb, (160 * 1024) / std::max<size_t>(lds, 1)), occ = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, BS, lds) == hipSuccess && occ >= 1)
       per_cu = std::min(per_cu, occ);
@@ -1170,22 +1191,7 @@ int run_scan_pairs(lsqr_ctx *c, const ScanBatch &b0) {
                        (const uint32_t *)c->d_vpart, Hc, (uint32_t)blocks, Hc, b.h_dev, b.votes, b.h_off);
     HIPCHK(c, hipGetLastError());
     return LSQR_OK;
-  };
-  if constexpr (kPrep) {  // the lean group loop walks the prepared block
-    if (pack) {
-      // the per-value re-check reads the pair's slots of the broadcast area again; 3-D only: the 2-D plane's 512-record
-      // kernel has no register for it (12 bytes of scratch per lane with it, none without)
-      if constexpr (M::ND == 3) {
-        if (ldsb && c->opt_recheck) return launch(k_scan_pairs<CM, PP, BS, true, true, true, true, true>);
-      }
-      return ldsb ? launch(k_scan_pairs<CM, PP, BS, true, true, true, true>)
-                  : launch(k_scan_pairs<CM, PP, BS, false, true, true, true>);
-    }
-    if (prep && c->opt_lean)
-      return ldsb ? launch(k_scan_pairs<CM, PP, BS, true, true, true>) : launch(k_scan_pairs<CM, PP, BS, false, true, true>);
-  }
-  if (prep) return ldsb ? launch(k_scan_pairs<CM, PP, BS, true, kPrep>) : launch(k_scan_pairs<CM, PP, BS, false, kPrep>);
-  return ldsb ? launch(k_scan_pairs<CM, PP, BS, true>) : launch(k_scan_pairs<CM, PP, BS, false>);
+  });
 }
 
 // Vote bounds by rank (axis.h; plane in 3-D over axis-sorted cells) on top of the box-population bounds in d_ub:

@@ -1,6 +1,6 @@
 """The lean forms of the counted two-level scan (csrc/cells.h; option "scan_lean", default 1): the count-only counting
-pass (k_cells_bounds<..., COUNT>: survivor counts from level 1's own compare mask, nothing else computed or written)
-and, for the plane, k_scan_pairs<..., LEAN>: share arithmetic on the scalar unit, one Hyp that is refilled for the next
+pass (k_cells_bounds, BoundsForm::Count: survivor counts from level 1's own compare mask, nothing else computed or written)
+and, for the plane, k_scan_pairs, PairsForm::Lean: share arithmetic on the scalar unit, one Hyp that is refilled for the next
 group as soon as level 1 has read it, and the pair loop's two addends stored twice in the LDS broadcast area.  Not a
 single vote may change: with the option 1 and 0 the votes of every hypothesis are identical to each other and to the
 exhaustive fp64 kernel (scan_index 0), winner, fit and consensus set are equal, a 64-hypothesis sample equals the

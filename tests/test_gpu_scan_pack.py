@@ -1,6 +1,6 @@
 """The packed form of the plane's lean counted scan (csrc/cells.h; option "scan_pack"): the counting pass stores level
-1's 64-bit survivor mask per (cell, group of 64 hypotheses) (k_cells_bounds<..., MASK>), the cost table is made of the
-masks' population counts (k_tile_costs<true>), and k_scan_pairs<..., PACK> repeats level 1 on packed blocks of 64
+1's 64-bit survivor mask per (cell, group of 64 hypotheses) (k_cells_bounds, BoundsForm::PreparedMask), the cost table is made of the
+masks' population counts (k_tile_costs<true>), and k_scan_pairs, PairsForm::Packed, repeats level 1 on packed blocks of 64
 consecutive survivors of a cell's dense order, gathered through a per-wave id list in LDS.  Which wave counts which
 pair changes; not a single vote may: with the option 1 and 0 the votes of every hypothesis are identical to each other
 and to the exhaustive fp64 kernel (scan_index 0), a 64-hypothesis sample equals the oracle's count, winner, fit and

@@ -1,4 +1,4 @@
-"""The exact path of the plane's packed counted scan (csrc/cells.h: cells_survivors<..., RECHECK>; option
+"""The exact path of the plane's packed counted scan (csrc/cells.h: cells_survivors, Exact::Band; PairsForm::PackedRecheck; option
 "scan_recheck"): a (hypothesis, cell) pair one of whose observations falls into the fp32 filter's band re-evaluates the
 fp64 predicate for the observations in the band alone (1, the default) instead of for the whole cell (0).  The vote of
 every observation comes from the same predicate either way, so not a single vote may change: with the option 1 and 0

@@ -10,6 +10,7 @@ import collections
 import json
 import os
 import re
+import shutil
 import subprocess
 import sys
 
@@ -18,22 +19,57 @@ sys.path.insert(0, ROOT)
 from bench import kernel_source_hash  # noqa: E402
 
 CSRC = os.path.join(ROOT, "lsqrrecipes_amd", "csrc")
-# (key, substrings the mangled name must contain)
-# (k_scan_pairs<CM, PP, BS, LDSB, PREP, LEAN, PACK>, k_cells_bounds<CM, PP, PREP, COUNT, MASK>: the bools are the trailing LbNE)
-KERNELS = [("k_scan_pairs_plane", ["k_scan_pairs", "PlaneCell", "Li3E", "Li4ELi256ELb1ELb1ELb1ELb1EEE"]),  # LDS broadcast, prepared Hyp, lean, packed blocks: what runs
-           ("k_scan_pairs_plane_groups", ["k_scan_pairs", "PlaneCell", "Li3E", "Li4ELi256ELb1ELb1ELb1ELb0EEE"]),  # scan_pack=0
-           ("k_scan_pairs_plane_general", ["k_scan_pairs", "PlaneCell", "Li3E", "Li4ELi256ELb1ELb1ELb0ELb0EEE"]),  # scan_lean=0
-           ("k_scan_pairs_plane_unprepared", ["k_scan_pairs", "PlaneCell", "Li3E", "Li4ELi256ELb1ELb0ELb0ELb0EEE"]),  # scan_prepared=0 scan_lean=0
-           ("k_cells_bounds_plane", ["k_cells_bounds", "PlaneCell", "Li3E", "Li4ELb1ELb1ELb1EEE"]),  # mask-only counting pass: what runs
-           ("k_cells_bounds_plane_count", ["k_cells_bounds", "PlaneCell", "Li3E", "Li4ELb1ELb1ELb0EEE"]),  # scan_pack=0: count-only
-           ("k_cells_bounds_plane_general", ["k_cells_bounds", "PlaneCell", "Li3E", "Li4ELb1ELb0ELb0EEE"]),  # scan_lean=0
-           ("k_scan_pairs_sphere", ["k_scan_pairs", "SphereCell", "Li3E"]),
-           ("k_scan_pairs_line", ["k_scan_pairs", "LineCell", "Li3E"]),
-           ("k_scan_us_f32", ["k_scan_us_f32", "USModel", "Lb1E"]),
-           ("k_scan_dense_h16", ["k_scan_dense_h16"]),
-           ("k_scan_us_h16", ["k_scan_us_h16", "Lb1E"]),
-           ("k_scan_phantom_h16", ["k_scan_phantom_h16"]),
-           ("k_lm_persist_us", ["k_lm_persist", "USModel", "Lb1E", "Li0E"])]
+# (key, kernel, its template arguments as c++filt prints them): every key selects exactly one instantiation.  The forms
+# of the counted scan are written by name (cells.h: PairsForm, BoundsForm); PP = cell size / 128, then BS and LDSB.
+PLANE = "lsqr::PlaneCell<3>"
+KERNELS = [("k_scan_pairs_plane", "k_scan_pairs", [PLANE, "4", "256", "true", "PairsForm::PackedRecheck"]),  # what runs
+           ("k_scan_pairs_plane_whole_cell", "k_scan_pairs", [PLANE, "4", "256", "true", "PairsForm::Packed"]),  # scan_recheck=0
+           ("k_scan_pairs_plane_groups", "k_scan_pairs", [PLANE, "4", "256", "true", "PairsForm::Lean"]),  # scan_pack=0
+           ("k_scan_pairs_plane_general", "k_scan_pairs", [PLANE, "4", "256", "true", "PairsForm::Prepared"]),  # scan_lean=0
+           ("k_scan_pairs_plane_unprepared", "k_scan_pairs", [PLANE, "4", "256", "true", "PairsForm::General"]),  # scan_prepared=0 scan_lean=0
+           ("k_cells_bounds_plane", "k_cells_bounds", [PLANE, "4", "BoundsForm::PreparedMask"]),  # mask-only counting pass: what runs
+           ("k_cells_bounds_plane_count", "k_cells_bounds", [PLANE, "4", "BoundsForm::PreparedCount"]),  # scan_pack=0: count-only
+           ("k_cells_bounds_plane_general", "k_cells_bounds", [PLANE, "4", "BoundsForm::Prepared"]),  # scan_lean=0
+           ("k_scan_pairs_sphere", "k_scan_pairs", ["lsqr::SphereCell<3>", "4", "256", "true", "PairsForm::General"]),
+           ("k_scan_pairs_line", "k_scan_pairs", ["lsqr::LineCell<3>", "2", "256", "true", "PairsForm::General"]),
+           ("k_scan_us_f32", "k_scan_us_f32", ["lsqr::USModel<true>", "2"]),
+           ("k_scan_dense_h16", "k_scan_dense_h16", ["64", "false", "0"]),
+           ("k_scan_us_h16", "k_scan_us_h16", ["true"]),
+           ("k_scan_phantom_h16", "k_scan_phantom_h16", None),
+           ("k_lm_persist_us", "k_lm_persist", ["lsqr::USModel<true>", "0"])]
+
+
+def enum_values(name):
+    """enumerators of `enum class <name>` in cells.h, in order: c++filt prints a form as (lsqr::<name>)<index>"""
+    m = re.search(r"enum class %s \{([^}]*)\}" % name, open(os.path.join(CSRC, "cells.h")).read())
+    return [e.strip() for e in m.group(1).split(",")]
+
+
+def template_args(demangled):
+    """(kernel, [top-level template arguments]) of `[void ]lsqr::kernel[<args>](parameters)`, or None"""
+    m = re.match(r"(?:void )?lsqr::(\w+)", demangled)
+    if not m:
+        return None
+    rest = demangled[m.end():]
+    if not rest.startswith("<"):
+        return (m.group(1), None) if rest.startswith("(") else None
+    args, depth, cur = [], 0, ""
+    for ch in rest:
+        if ch in "<(":
+            depth += 1
+            if depth == 1:
+                continue
+        elif ch in ">)":
+            depth -= 1
+            if depth == 0:
+                args.append(cur.strip())
+                return m.group(1), args
+        if ch == "," and depth == 1:
+            args.append(cur.strip())
+            cur = ""
+        else:
+            cur += ch
+    return None
 
 
 def classify(op):
@@ -67,17 +103,25 @@ def main():
     text = open(asm).read()
     # function bodies: "<mangled>:" ... ".Lfunc_end"
     starts = [(m.start(), m.group(1)) for m in re.finditer(r"^(_Z[\w]+):\s*(?:;.*)?$", text, re.M)]
+    filt = shutil.which("c++filt") or shutil.which("llvm-cxxfilt")
+    if not filt:
+        sys.exit("neither c++filt nor llvm-cxxfilt on PATH: kernels are selected by their demangled names")
+    # (binutils' c++filt does not know _Float16, "DF16_": written as half, "Dh", neither of them a substitution candidate,
+    # the name demangles; only the parameter list reads differently)
+    names = subprocess.run([filt], input="\n".join(n.replace("DF16_", "Dh") for _, n in starts), capture_output=True,
+                           text=True, check=True).stdout.split("\n")
+    parsed = [(p, n, template_args(d)) for (p, n), d in zip(starts, names)]
+    forms = {"%s::%s" % (e, v): "(lsqr::%s)%d" % (e, i)
+             for e in ("PairsForm", "BoundsForm") for i, v in enumerate(enum_values(e))}
     res = {}
-    for key, subs in KERNELS:
-        cand = [(p, n) for p, n in starts if all(s_ in n for s_ in subs)]
-        if not cand:
+    bad = []
+    for key, kernel, args in KERNELS:
+        want = None if args is None else [forms.get(a, a) for a in args]
+        cand = [(p, n) for p, n, t in parsed if t == (kernel, want)]
+        if len(cand) != 1:
+            bad.append("%s: %d instantiations of %s<%s>" % (key, len(cand), kernel, ", ".join(args or [])))
             continue
-        # the largest instantiation (the default cell size / the production variant is the biggest body)
-        best = None
-        for p, n in cand:
-            e = text.index(".Lfunc_end", p)
-            if best is None or e - p > best[2] - best[0]:
-                best = (p, n, e)
+        best = (cand[0][0], cand[0][1], text.index(".Lfunc_end", cand[0][0]))
         body = text[best[0]:best[2]].split("\n")
         loops = collections.OrderedDict()
         cur = ("entry", 0)
@@ -128,6 +172,8 @@ def main():
                     if key.startswith("k_cells_bounds") and rows else None,
                     "packed_body": {"loop": l2["loop"], "valu": l2["valu"], "valu_packed": l2["valu_packed"],
                                     "valu_cmp": l2["valu_cmp"], "salu": l2["salu"]} if l2 else None}
+    if bad:  # (nothing is written: a profile with some of its keys would pass for a whole one)
+        sys.exit("no single kernel for\n  " + "\n  ".join(bad))
     out = {"what": "tools/isa_counts.py: instructions per loop of the scan kernels in this tree's ISA (one pass over a loop "
                    "body; a body the compiler unrolled covers several source iterations)",
            "kernel_source_hash": kernel_source_hash(), "kernels": res}
