@@ -860,6 +860,15 @@ LSQR_API void lsqr_dedup_destroy(void *set);
  *                uncertainty re-evaluates the fp64 predicate 1 (default) = for the observations in the band alone, each
  *                lane loading its own; 0 = for all observations of the cell (A/B knob).  Accepted values 0 and 1;
  *                without effect on other kernels.  Votes are identical;
+ * "scan_slab":   the counting pass of the 3-D plane's packed counted scan ("scan_pack" 1) over an axis-sorted index
+ *                ("scan_axis" 1, cells of 256 / 512): 1 (default) = a (hypothesis, cell) pair the box test keeps is
+ *                dropped again when the cell's oriented slab -- its axis of least spread and the interval of its
+ *                observations along it, built with the index (csrc/axis.h: k_cell_slabs) -- proves that no observation
+ *                of the cell can agree (csrc/cells.h: PlaneCell::slab); 0 = the plain box-test masks (A/B knob).
+ *                Accepted values 0 and 1; without effect on the 2-D plane, sphere, line, the non-packed forms and an
+ *                index without axes.  Votes are identical.  "scan_slab_gate": 1..8 (default 3), the slab of a cell is
+ *                tested only where its width is at most value / 4 of the box's extent along the axis (A/B knob; the
+ *                index is rebuilt);
  * "dense_mask_ring": LDS tile buffers per wave of the dense final fit's fused mask + normal-equations pass: 4 (default at
  *                n = 64) = one workgroup per CU with three tiles in flight, 2 = two workgroups per CU (A/B knob);
  * "mom_chunk":   records per workgroup of the mask / moment passes in units of 256 (0 = default: 4, wide US / phantom
@@ -891,6 +900,13 @@ LSQR_API int lsqr_scan_workload(lsqr_ctx *ctx, uint32_t *bound_out, uint64_t out
  * (hypothesis, cell) pairs that took the exact fp64 path because an observation fell into the fp32 filter's band, and
  * the observations that were in the band (counted by the per-value re-check, "scan_recheck" 1, only); 0 otherwise. */
 LSQR_API int lsqr_scan_work(lsqr_ctx *ctx, uint64_t out[8]);
+
+/* The table of the LAST counting launch of the counted two-level scan (k_scan_pairs' cost table; for the bounded scan
+ * that is its second pass): out[0..3] = {(hypothesis, cell) pairs in the table -- what level 2 was handed, after the
+ * slab test where it ran; lsqr_scan_workload keeps reporting the pairs of the box test alone --, 1 if the table holds
+ * survivor masks ("scan_pack"), 1 if the slab test ran ("scan_slab"), cells x hypotheses of the launch}.
+ * LSQR_ERR_STATE when the last scan did not go through that kernel. */
+LSQR_API int lsqr_scan_pairs_counted(lsqr_ctx *ctx, uint64_t out[4]);
 
 /* The LAST persistent Levenberg-Marquardt fit of this context (option "lm_persist"; csrc/lm_persist.h):
  * out[0..7] = {mode (1 / 3: MINPACK's step on the host between granules in pinned memory, 2: on the device), resident

@@ -851,6 +851,13 @@ class Context:
                 "candidates": int(out[3]), "dropped_first": int(out[4]), "alive_at_end": int(out[5]),
                 "ambiguous_pairs": int(out[6]), "band_records": int(out[7])}
 
+    def scan_pairs_counted(self):
+        """the (hypothesis, cell) pairs the last counted two-level scan handed to its second level
+        (lsqr_scan_pairs_counted) -> dict(pairs, masks, slab, table_entries)"""
+        out = (C.c_uint64 * 4)()
+        self._chk(self._lib.lsqr_scan_pairs_counted(self._h, out))
+        return {"pairs": int(out[0]), "masks": bool(out[1]), "slab": bool(out[2]), "table_entries": int(out[3])}
+
     def synchronize(self):
         self._chk(self._lib.lsqr_synchronize(self._h))
 

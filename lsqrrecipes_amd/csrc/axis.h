@@ -8,7 +8,9 @@
 //   * every cell gets an axis e -- the direction of least spread of its own observations, or of its group of eight
 //     consecutive cells when that serves the cell as well (more observations: a quieter estimate; k_cell_axes);
 //   * the observations of a cell are re-ordered by t = e . (x - ctr) (a bitonic sort inside the wave; the order inside
-//     a cell is irrelevant to every other kernel) and the sorted t are kept as fp32 T[] (k_cell_sort).
+//     a cell is irrelevant to every other kernel) and the sorted t are kept as fp32 T[] (k_cell_sort);
+//   * the ends of that T[] give the cell's oriented SLAB (k_cell_slabs): the counting pass of the full count drops the
+//     (hypothesis, cell) pairs whose plane passes the cell's box but not its slab (cells.h: PlaneCell::slab).
 // For a hypothesis (n, a) and a cell:  s(x) = n . (x - a) = alpha t + d0 + m . (x - ctr),  alpha = n.e / e.e,
 // m = n - alpha e,  d0 = n . (ctr - a)  -- an identity for ANY e.  When n is nearly parallel to e, |m . (x - ctr)| <=
 // rho = sum |m_i| h_i is small, and with E = rho + (rounding, below)
@@ -214,6 +216,47 @@ __global__ __launch_bounds__(256) void k_cell_sort(double *__restrict__ sorted, 
     if (ok[k] && i < ns) sorted[i * 3] = px[k], sorted[i * 3 + 1] = py[k], sorted[i * 3 + 2] = pz[k];
   }
   if (lane == 0) axis[cell].tmax = tmax;
+}
+
+// ---- build 4: one thread per cell: the cell's slab for the counting pass (cells.h: CellSlab, PlaneCell::slab) ---------
+// The interval of the cell's sorted T[] -- first and last valid entry -- moved outwards by T's own rounding (header,
+// "Rounding": |T - t| <= 2^-24 |t| + 1e-13 X; taken here as 6e-8 |T| + 2e-13 X, which is monotone in T, so the two ends
+// cover every observation between them), as a float centre and a half width rounded up.  tspan = +inf ("never
+// tested") where the slab cannot beat the box for the hypothesis it serves best, n parallel to e: there the slab's
+// term is tspan / |e| against the box's sum |e_i| h_i / |e|, and the gate is  tspan (e . e) > kappa sum |e_i| h_i
+// (kappa = gate4 / 4; DESIGN.md 3.1 has the measurement), and for an empty cell or values that are not finite.
+__global__ __launch_bounds__(256) void k_cell_slabs(const CellBox *__restrict__ boxes, const CellAxis *__restrict__ axis,
+                                                    const float *__restrict__ cellT, size_t ns, uint32_t ncells,
+                                                    uint32_t cell_pts, double xabs, uint32_t gate4,
+                                                    CellSlab *__restrict__ slabs) {
+  const uint32_t c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= ncells) return;
+  const CellBox bx = boxes[c];
+  const CellAxis ax = axis[c];
+  const size_t first = (size_t)c * cell_pts;
+  const uint32_t pop = first >= ns ? 0u : (first + cell_pts <= ns ? cell_pts : (uint32_t)(ns - first));
+  CellSlab s;
+  const double e0 = (double)ax.e[0], e1 = (double)ax.e[1], e2 = (double)ax.e[2], ee = e0 * e0 + e1 * e1 + e2 * e2;
+  const double r1 = (double)bx.h[0] + (double)bx.h[1] + (double)bx.h[2];
+  s.e[0] = ax.e[0], s.e[1] = ax.e[1], s.e[2] = ax.e[2];
+  s.iee = (float)(1.0 / ee);
+  s.tmid = 0.0f, s.tspan = __builtin_inff(), s.pad = 0.0f;
+  const double eabs = (1.3e-7 * r1 + 4e-12 * xabs) * (1.0 + 1e-6);
+  s.eabs = eabs <= 3.4e38 ? f32_up(eabs) : __builtin_inff();
+  if (pop) {
+    const double t0 = (double)cellT[first], t1 = (double)cellT[first + pop - 1];
+    const double lo = t0 - (6e-8 * fabs(t0) + 2e-13 * xabs), hi = t1 + (6e-8 * fabs(t1) + 2e-13 * xabs);
+    const float mid = (float)(0.5 * lo + 0.5 * hi);
+    const double span = fmax(hi - (double)mid, (double)mid - lo) * (1.0 + 1e-12);
+    const double box_e = fabs(e0) * (double)bx.h[0] + fabs(e1) * (double)bx.h[1] + fabs(e2) * (double)bx.h[2];
+    // (every compare false for NaN: the slab stays untested)
+    if (span >= 0.0 && span <= 1e30 && fabsf(mid) <= 1e30f && r1 <= 1e30 && ee > 0.25 && ee <= 4.0 &&
+        span * ee * 4.0 <= (double)gate4 * box_e) {
+      s.tmid = mid;
+      s.tspan = f32_up(span);
+    }
+  }
+  slabs[c] = s;
 }
 
 // ---- vote bounds by rank ------------------------------------------------------------------------------------------

@@ -51,6 +51,16 @@ struct CellBox {  // 32 B: one s_load_dwordx8
   float h[3];     // half extents, inflated: every point satisfies |x_i - c_i| * (1 + 2^-20) <= h_i
   float pad[2];   // pad[0]: bounding radius |h|, rounded up
 };
+// The oriented slab of a cell of the 3-D plane's axis-sorted index (axis.h: k_cell_slabs): with t = e . (x - c) in real
+// arithmetic, every observation x of the cell has |t - tmid| <= tspan.  tspan = +inf: the slab says nothing the box
+// does not (gated, empty cell, no axis) and is never tested.
+struct CellSlab {  // 32 B, staged like a CellBox
+  float e[3];      // the cell's axis (CellAxis::e)
+  float iee;       // ~ 1 / (e . e)  (any value serves: see PlaneCell::slab)
+  float tmid, tspan;
+  float eabs;      // the cell's share of slab()'s rounding, rounded up: 1.3e-7 (h_0 + h_1 + h_2) + 4e-12 X
+  float pad;
+};
 
 // ---- index build ---------------------------------------------------------------------------------
 __device__ inline unsigned long long ord_u64(double v) {  // monotone map double -> uint64
@@ -724,6 +734,11 @@ constexpr bool cell_prepared() {
   if constexpr (requires { CM::PREPARED; }) return CM::PREPARED != 0;
   return false;
 }
+template <class CM>
+constexpr bool cell_slab() {
+  if constexpr (requires { CM::SLAB; }) return CM::SLAB != 0;
+  return false;
+}
 // a prepared Hyp as the 16-byte words it is stored in (lane = hypothesis: 16-byte loads / stores per lane)
 template <class CM>
 struct HypWords {
@@ -776,6 +791,7 @@ struct PlaneCell {
   // (k_cells_bounds(cnt) / k_scan_pairs) has it written once per batch by k_prepare_hyps and reads it back with three
   // 16-byte loads instead of rebuilding it for every (cell, group) -- ~160 times per hypothesis in a full count
   enum { PREPARED = 1 };
+  enum { SLAB = D == 3 };  // the mask form of the counting pass may test the cell's slab as well (slab(), below)
   static __device__ inline void load(const float *row, const float *row2, bool valid,
                                      const CellConsts &cc, Hyp &h) {
     prepare(row, row2, valid, cc, h);
@@ -814,6 +830,37 @@ struct PlaneCell {
     const float tin = (cc.f[0] - E) * 0.9999997f;
     bc[0] = h.nf[0], bc[1] = h.nf[1], bc[2] = h.nf[2], bc[3] = d0, bc[4] = tin, bc[5] = tout;
     return __builtin_fabsf(d0) < (rr + tout) * 1.000004f;
+  }
+  // The second test of the counting pass (option "scan_slab"; 3-D, the mask form of k_cells_bounds alone): "may the
+  // cell's slab hold an agreeing observation?", for a pair level 1 kept, on level 1's own values bc[].  For ANY alpha,
+  // with m = n - alpha e formed from that same alpha, s* = d0* + alpha t + m . y where y = x - ctr, |y_i| <= h_i, and
+  // t = e . y lies in [tmid - tspan, tmid + tspan] (CellSlab), so
+  //   |s*| >= |d0* + alpha tmid| - |alpha| tspan - sum |m_i| h_i,
+  // and the pair is dropped when that lower bound is certainly >= tout >= T.  alpha is the fp32 value al below taken as
+  // a real (its own rounding, and that of iee, does not matter).  With u = 2^-24, R1 = h_0 + h_1 + h_2:
+  //   m32_i = fma(-al, e_i, n32_i), one rounding, |n_i - n32_i| <= 1.0000001 u:    |m_i| <= |m32_i| (1 + u) + 1.01 u
+  //   rho32 (three results) and W32 = fma(|al|, tspan, rho32), non-negative terms:
+  //                                     |al| tspan + sum |m_i| h_i <= W32 (1 + u)^5 + 1.01 u R1
+  //   c32 = fma(al, tmid, d0f), d0f = fl32(d), d level 1's fp64 value, |d - d0*| <= 1e-13 X:
+  //                                     |d0* + al tmid| >= |c32| (1 - u) - u (1 + 2u) |d0f| - 1e-13 X
+  //   a pair level 1 kept has |d0f| < (rr + tout) 1.000004, rr <= 1.0000003 R1:  u (1 + 2u) |d0f| <= 6.1e-8 (R1 + tout)
+  //   the reference decides on s_ref, |s_ref - s*| < 1e-13 X.
+  // So nothing in the cell agrees when  |c32| (1 - u) >= tout (1 + 6.1e-8) + 1.0000004 W32 + 1.22e-7 R1 + 3e-13 X;
+  // eabs >= 1.3e-7 R1 + 4e-12 X holds the last two terms, r = fl(fl(1.000001f W32 + tout) + eabs) is below the true sum
+  // by (1 + u)^2 at most, and the factor 1.000001f (= 1 + 9.5e-7) of the compare covers that, the (1 - u) and the
+  // 6.1e-8.  The compare is strict and false for NaN; an infinite right side (filter off: tout = inf) keeps the pair;
+  // |c32| = inf against a finite right side drops it rightly (the real value exceeds every float).
+  static __device__ inline bool slab(const Hyp &h, const float *bc, const CellBox &b, const CellSlab &s) {
+    static_assert(D == 3, "the axis-sorted index is built in 3-D");
+    const float al = __builtin_fmaf(h.nf[0], s.e[0], __builtin_fmaf(h.nf[1], s.e[1], h.nf[2] * s.e[2])) * s.iee;
+    const float m0 = __builtin_fmaf(-al, s.e[0], h.nf[0]), m1 = __builtin_fmaf(-al, s.e[1], h.nf[1]),
+                m2 = __builtin_fmaf(-al, s.e[2], h.nf[2]);
+    const float rho = __builtin_fmaf(__builtin_fabsf(m0), b.h[0],
+                                     __builtin_fmaf(__builtin_fabsf(m1), b.h[1], __builtin_fabsf(m2) * b.h[2]));
+    const float W = __builtin_fmaf(__builtin_fabsf(al), s.tspan, rho);
+    const float c = __builtin_fmaf(al, s.tmid, bc[3]);
+    const float r = __builtin_fmaf(1.000001f, W, bc[NB - 1]) + s.eabs;
+    return !(__builtin_fabsf(c) > r * 1.000001f);
   }
   static __device__ inline v2f value(const v2f *xs, const v2f *fp) {
     v2f s = fp[3];
@@ -1735,9 +1782,14 @@ __device__ __forceinline__ typename CM::Hyp hyp_from(const float4 (&v)[HypWords<
 // every (cell, group) -- `cnt` then points to n_cells x gstride 64-bit words, [cell][group], so that lane g of a wave
 // of the packed k_scan_pairs reads the 64 masks of a cell with one 8-byte load per lane; lanes past the batch never
 // survive (NaN), so their bits are 0.  Counts and costs are population counts of the masks (k_tile_costs<true>).
+// `slabs` (option "scan_slab"; the 3-D plane's mask form, else ignored): a bit level 1 set is cleared again when the
+// cell's oriented slab proves that no observation of the cell can agree (PlaneCell::slab) -- the axis-aligned box of a
+// thin oblique plate is many times thicker along the plate's normal than the plate.  The packed k_scan_pairs takes its
+// survivors from the stored masks and never asks level 1 for them, so a cleared bit removes the pair from the cost
+// table, from the static split and from level 2, and the kernel itself is the same code.
 //
 // bounds_chunk: a wave's walk over the n boxes of a chunk in LDS for the forms that write a table and nothing else,
-// four boxes in flight and then the tail.  box(bx, ctr) is the form's value for one box; store(r...) takes the values of
+// four boxes in flight and then the tail.  box(i, bx, ctr) is the form's value for box i; store(r...) takes the values of
 // the four boxes of an unrolled iteration, or of one box of the tail, in box order.  (The general form keeps the walk
 // written out: through bounds_chunk the sphere's kernels load eight bytes of the hypothesis' row twice.)
 template <class Box, class Store>
@@ -1750,13 +1802,13 @@ __device__ __forceinline__ void bounds_chunk(const CellBox *s_box, const double 
     const double t1[3] = {s_ctr[i + 1][0], s_ctr[i + 1][1], s_ctr[i + 1][2]};
     const double t2[3] = {s_ctr[i + 2][0], s_ctr[i + 2][1], s_ctr[i + 2][2]};
     const double t3[3] = {s_ctr[i + 3][0], s_ctr[i + 3][1], s_ctr[i + 3][2]};
-    const auto r0 = box(b0, t0), r1 = box(b1, t1), r2 = box(b2, t2), r3 = box(b3, t3);
+    const auto r0 = box(i, b0, t0), r1 = box(i + 1, b1, t1), r2 = box(i + 2, b2, t2), r3 = box(i + 3, b3, t3);
     store(r0, r1, r2, r3);
   }
   for (; i < n; i++) {
     const CellBox b0 = s_box[i];
     const double t0[3] = {s_ctr[i][0], s_ctr[i][1], s_ctr[i][2]};
-    store(box(b0, t0));
+    store(box(i, b0, t0));
   }
 }
 // the results of consecutive boxes -> their rows of one column of the [box][group] table, under one `lane == 0`; returns
@@ -1770,6 +1822,16 @@ __device__ __forceinline__ T *bounds_put(T *p, const uint32_t gstride, const int
   }
   return p + (uint32_t)sizeof...(R) * gstride;
 }
+// the slabs of a chunk of cells in LDS, in the instantiations that test them (k_cells_bounds: SLAB) and in no other
+template <bool ON>
+__device__ __forceinline__ CellSlab *slab_lds() {
+  if constexpr (ON) {
+    __shared__ CellSlab s_slab[128];
+    return s_slab;
+  } else {
+    return nullptr;
+  }
+}
 template <class CM, int PP, BoundsForm F>
 __global__ __launch_bounds__(256) void k_cells_bounds(const CellBox *__restrict__ boxes, uint32_t ncells,
                                                       size_t ns, const float *__restrict__ rows,
@@ -1780,9 +1842,11 @@ __global__ __launch_bounds__(256) void k_cells_bounds(const CellBox *__restrict_
                                                       uint32_t *__restrict__ ncells_out,
                                                       uint8_t *__restrict__ cnt, uint32_t gstride,
                                                       const uint32_t *__restrict__ h_dev, uint32_t h_off,
-                                                      uint32_t box_pop, const float4 *__restrict__ hyps) {
+                                                      uint32_t box_pop, const float4 *__restrict__ hyps,
+                                                      const CellSlab *__restrict__ slabs) {
   static_assert(bounds_form_exists<CM, F>());
   constexpr bool PREP = prepared(F), COUNT = count(F), MASK = mask(F);
+  constexpr bool SLAB = MASK && cell_slab<CM>();  // (every other form and cell model ignores `slabs`)
   typedef typename CM::M M;
   constexpr int ROW = CM::ROW, NR4 = ROW / 4, NR2 = CM::ROW2 / 4;
   const size_t CP = box_pop;  // observations per box: 128 * PP for the cells, a multiple for merged boxes
@@ -1831,12 +1895,16 @@ __global__ __launch_bounds__(256) void k_cells_bounds(const CellBox *__restrict_
   // measured 141 us for 1.25 M plane evaluations of ~20 instructions; LDS reads of one address are broadcasts that
   // return in order and pipeline across the unrolled loop.
   constexpr uint32_t BCH = 128;
+  static_assert(BCH == 128, "slab_lds() holds one chunk");
   __shared__ CellBox s_box[BCH];
   __shared__ double s_ctr[BCH][3];
   for (uint32_t cb = c0; cb < c1; cb += BCH) {
     const uint32_t n = c1 - cb < BCH ? c1 - cb : BCH;
     __syncthreads();  // the previous chunk has been consumed
     if (threadIdx.x < 2 * n) ((float4 *)s_box)[threadIdx.x] = ((const float4 *)(boxes + cb))[threadIdx.x];
+    if constexpr (SLAB) {  // the chunk's slabs with its boxes (workgroup-uniform: `slabs` is an argument)
+      if (slabs && threadIdx.x < 2 * n) ((float4 *)slab_lds<SLAB>())[threadIdx.x] = ((const float4 *)(slabs + cb))[threadIdx.x];
+    }
     __syncthreads();
     if (threadIdx.x < n) {
 #pragma unroll
@@ -1848,9 +1916,19 @@ __global__ __launch_bounds__(256) void k_cells_bounds(const CellBox *__restrict_
       unsigned long long *p = (unsigned long long *)cnt + ((size_t)cb * gstride + grp);  // wave-uniform
       bounds_chunk(
           s_box, s_ctr, n,
-          [&](const CellBox &bx, const double(&ctr)[3]) {
+          [&](const uint32_t i, const CellBox &bx, const double(&ctr)[3]) {
             float bc[CM::NB];
-            return (unsigned long long)__ballot(CM::level1(hy, bx, ctr, cc, bc));
+            unsigned long long m = __ballot(CM::level1(hy, bx, ctr, cc, bc));
+            if constexpr (SLAB) {
+              // the second test, where level 1 left a survivor and the cell's slab can beat its box: both wave-uniform
+              // (tspan is the same LDS word in every lane), so the whole wave takes the ~16 instructions or none
+              if (slabs && m) {
+                const CellSlab sl = slab_lds<SLAB>()[i];
+                if (__builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, sl.tspan)) < 0x7F800000)
+                  m &= __ballot(CM::slab(hy, bc, bx, sl));
+              }
+            }
+            return m;
           },
           [&](auto... m) { p = bounds_put(p, gstride, lane, m...); });
     } else if constexpr (COUNT) {
@@ -1858,7 +1936,7 @@ __global__ __launch_bounds__(256) void k_cells_bounds(const CellBox *__restrict_
       bounds_chunk(
           s_box, s_ctr, n,
           // padded survivor count of the wave's group in one box: every lane of an active wave takes part in the compare
-          [&](const CellBox &bx, const double(&ctr)[3]) {
+          [&](const uint32_t, const CellBox &bx, const double(&ctr)[3]) {
             float bc[CM::NB];
             const uint32_t pc = (uint32_t)__builtin_popcountll(__ballot(CM::level1(hy, bx, ctr, cc, bc)));
             return (uint8_t)(pc ? pc + kGroupPad : 0u);  // <= 64 + pad
@@ -2006,6 +2084,43 @@ __global__ __launch_bounds__(128) void k_tile_costs(const uint8_t *__restrict__ 
   if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = t;
   __syncthreads();
   if (threadIdx.x == 0) csum[blockIdx.x] = s_w[0] + s_w[1];
+}
+
+// Diagnostics (lsqr_scan_pairs_counted): the (hypothesis, cell) pairs in the table of the last counting launch, read
+// back from what k_tile_costs left -- PACK: the survivors behind every cell's cost; else the count bytes without their
+// padding.  One workgroup, no atomics; not on any scan's path.
+template <bool PACK>
+__global__ __launch_bounds__(1024) void k_pairs_in_table(const uint8_t *__restrict__ cnt, uint32_t gstride, uint32_t H,
+                                                         const uint32_t *__restrict__ h_dev, uint32_t h_off,
+                                                         uint32_t ncells, const uint32_t *__restrict__ cost,
+                                                         unsigned long long *__restrict__ out) {
+  unsigned long long t = 0;
+  if constexpr (PACK) {
+    for (uint32_t c = threadIdx.x; c < ncells; c += 1024) {
+      const uint32_t v = cost[c];
+      t += v ? pack_cell_survivors(v) : 0u;
+    }
+  } else {
+    if (h_dev) {
+      const uint32_t hd = *h_dev > h_off ? *h_dev - h_off : 0u;
+      H = hd < H ? hd : H;
+    }
+    const uint32_t G = (H + 63) / 64;
+    for (uint32_t c = threadIdx.x; c < ncells; c += 1024)
+      for (uint32_t g = 0; g < G; g++) {
+        const uint32_t b = cnt[(size_t)c * gstride + g];
+        t += b ? b - kGroupPad : 0u;
+      }
+  }
+  __shared__ unsigned long long s_t[16];
+  for (int o = 32; o > 0; o >>= 1) t += __shfl_down(t, o);
+  if ((threadIdx.x & 63) == 0) s_t[threadIdx.x >> 6] = t;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long a = 0;
+    for (int w = 0; w < 16; w++) a += s_t[w];
+    *out = a;
+  }
 }
 
 // inclusive prefix sum across the wave (lane i: sum of lanes 0..i)

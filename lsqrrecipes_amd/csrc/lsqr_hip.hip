@@ -225,6 +225,15 @@ struct lsqr_ctx {
   DevBuf<CellAxis> d_axis;
   DevBuf<float> d_cellT;
   bool axis_valid = false;
+  DevBuf<CellSlab> d_slab;        // per-cell oriented slab (axis.h: k_cell_slabs), built with d_axis
+  int opt_slab = 1;               // 1: the mask-storing counting pass of the 3-D plane tests the cell's slab too (PlaneCell::slab)
+  int opt_slab_gate = 3;          // kappa of k_cell_slabs' gate in quarters (A/B; drops the index)
+  // the table of the last counting launch of run_scan_pairs (lsqr_scan_pairs_counted)
+  struct {
+    bool valid = false, packed = false, slab = false;
+    uint32_t H = 0, h_off = 0, gstride = 0;
+    const uint32_t *h_dev = nullptr;
+  } last_count;
   int opt_mom_chunk = 0;          // chunk of the mask / moment passes in units of kBlock records (0 = default; A/B)
   int opt_hyp_order = 1;          // 1: a full count of the plane walks the batch in key order (k_plane_order)
   int opt_axis = 1;               // 1: the bounded scan of the plane takes its vote bounds by rank (k_bound_axis)
@@ -755,6 +764,7 @@ void drop_index(lsqr_ctx *c) {
   c->index_valid = false;
   c->index_kd_levels = 0;
   c->axis_valid = false;
+  c->last_count.valid = false;
 }
 
 // k_bounds over the current upload (point models): min / max per dimension, max |coordinate|, non-finite count
@@ -904,6 +914,7 @@ int build_index(lsqr_ctx *c, uint32_t cell_pts) {
   if (D == 3 && c->opt_axis && c->cfg.model == LSQR_MODEL_PLANE && c->n_cells && (cell_pts == 512 || cell_pts == 256)) {
     if ((st = ensure(c, c->d_axis, (size_t)c->n_cells)) != LSQR_OK) return st;
     if ((st = ensure(c, c->d_cellT, (size_t)c->n_cells * cell_pts)) != LSQR_OK) return st;
+    if ((st = ensure(c, c->d_slab, (size_t)c->n_cells)) != LSQR_OK) return st;
     double *d_cmom = (double *)c->d_idx_scratch.get();  // 80 B per cell: the sort's scratch is free again (16 B per record)
     if ((size_t)c->n_cells * 10 * sizeof(double) <= c->d_idx_scratch.cap()) {
       const unsigned gc = (c->n_cells + 3) / 4;
@@ -923,6 +934,12 @@ int build_index(lsqr_ctx *c, uint32_t cell_pts) {
       else
         hipLaunchKernelGGL((k_cell_sort<4>), dim3(gc), dim3(256), 0, c->stream, c->d_sorted, c->n_sorted, c->n_cells,
                            c->d_boxes, c->d_axis, c->d_cellT);
+      {  // the cells' slabs for the counting pass (option "scan_slab"), from the sorted T[]
+        double xabs;
+        memcpy(&xabs, &hb.amax, sizeof xabs);  // (k_bounds: the bit pattern of max |coordinate|)
+        hipLaunchKernelGGL(k_cell_slabs, dim3((c->n_cells + 255) / 256), dim3(256), 0, c->stream, c->d_boxes, c->d_axis,
+                           c->d_cellT, c->n_sorted, c->n_cells, cell_pts, xabs, (uint32_t)c->opt_slab_gate, c->d_slab);
+      }
       IDXCHK(hipGetLastError());
       c->axis_valid = true;
     }
@@ -1056,7 +1073,8 @@ int run_cells_bounds(lsqr_ctx *c, uint32_t *d_ub, uint32_t *d_nc = nullptr) {
                      CM::ROW_F32 ? c->d_hparams_f32 : (const float *)c->d_hparams.get(), c->d_hparams_f32,
                      (uint32_t)c->H, cc, per, d_ub, d_nc ? c->d_counter + CNT_PAIRS : (unsigned long long *)nullptr, d_nc,
                      (uint8_t *)nullptr, 0u, (const uint32_t *)nullptr, 0u,  // (pair total: diagnostics only -- 8192
-                     (uint32_t)(128 * PP) * merge, (const float4 *)nullptr);  // atomics on one address are ~100 us)
+                     (uint32_t)(128 * PP) * merge, (const float4 *)nullptr,   // atomics on one address are ~100 us)
+                     (const CellSlab *)nullptr);
   HIPCHK(c, hipGetLastError());
   return LSQR_OK;
 }
@@ -1151,10 +1169,17 @@ int run_scan_pairs(lsqr_ctx *c, const ScanBatch &b0) {
       const unsigned gy = (Hc + 255) / 256;
       const uint32_t per = std::max<uint32_t>(8, (c->n_cells + 1023) / 1024);
       const unsigned gx = (c->n_cells + per - 1) / per;
+      // the slab test (option "scan_slab"): the masks of the 3-D plane over an axis-sorted index of this cell size
+      const CellSlab *slabs = nullptr;
+      if constexpr (packed(F) && cell_slab<CM>()) {
+        if (c->opt_slab && c->axis_valid && c->cell_pts == (uint32_t)(128 * PP)) slabs = c->d_slab;
+      }
+      c->last_count.valid = true, c->last_count.packed = packed(F), c->last_count.slab = slabs != nullptr;
+      c->last_count.H = Hc, c->last_count.h_off = b.h_off, c->last_count.gstride = gstride, c->last_count.h_dev = b.h_dev;
       auto count = [&](auto kern) {
         hipLaunchKernelGGL(kern, dim3(gx, gy), dim3(256), 0, c->stream, c->d_boxes, c->n_cells, c->n_sorted, rows, b.spf,
                            Hc, cc, per, (uint32_t *)nullptr, (unsigned long long *)nullptr, (uint32_t *)nullptr,
-                           d_cnt, gstride, b.h_dev, b.h_off, (uint32_t)(128 * PP), hyps);
+                           d_cnt, gstride, b.h_dev, b.h_off, (uint32_t)(128 * PP), hyps, slabs);
       };
       // (General alone has two counting forms, and "scan_lean" says which: an option's value cannot be a template
       // argument, so it is read once more here; for the other forms both branches name the same kernel)
@@ -2030,6 +2055,7 @@ int run_scan(lsqr_ctx *c) {
   c->ee_last = false;
   c->amb_reset = true;
   c->amb_counted = false;
+  c->last_count.valid = false;
   return dispatch(c->cfg, [&](auto tag) -> int {
     typedef typename decltype(tag)::type M;
     bool done = false;
@@ -5479,6 +5505,17 @@ static int set_option_one(lsqr_ctx *c, const char *name, int value) {
     c->opt_recheck = value;
     return LSQR_OK;
   }
+  if (!strcmp(name, "scan_slab")) {  // 1 (default): the counting pass of the 3-D plane's packed scan drops the pairs the cell's slab proves empty; 0: plain level-1 masks
+    if (value != 0 && value != 1) return fail(c, LSQR_ERR_INVALID, "scan_slab must be 0 or 1");
+    c->opt_slab = value;
+    return LSQR_OK;
+  }
+  if (!strcmp(name, "scan_slab_gate")) {  // kappa of the slabs' gate in quarters (axis.h: k_cell_slabs; A/B knob)
+    if (value < 1 || value > 8) return fail(c, LSQR_ERR_INVALID, "scan_slab_gate must be 1..8 (quarters)");
+    c->opt_slab_gate = value;
+    drop_index(c);
+    return LSQR_OK;
+  }
   if (!strcmp(name, "scan_axis")) {  // 1 (default): axis-sorted cells + vote bounds by rank (plane, 3-D); 0: off
     c->opt_axis = value != 0;
     return LSQR_OK;
@@ -5707,6 +5744,31 @@ int lsqr_scan_work(lsqr_ctx *c, uint64_t out[8]) {
     if (c->last_bound[0] && c->last_bound[3] == c->H && c->bsel_known_H == c->H)
       out[3] = c->bsel_known.n_cand;  // bounded plane scan with rank bounds: the hypotheses whose bounds were refined
   }
+  return LSQR_OK;
+}
+
+int lsqr_scan_pairs_counted(lsqr_ctx *c, uint64_t out[4]) {
+  int st = need_ready(c, true);
+  if (st != LSQR_OK) return st;
+  if (!out) return fail(c, LSQR_ERR_INVALID, "null argument");
+  if (!c->scanned || !c->last_count.valid || !c->index_valid || c->n_cells == 0)
+    return fail(c, LSQR_ERR_STATE, "no counted scan over this index");
+  const auto &lc = c->last_count;
+  unsigned long long *d_sum = c->d_counter + CNT_SUM;
+  if (lc.packed)
+    hipLaunchKernelGGL(k_pairs_in_table<true>, dim3(1), dim3(1024), 0, c->stream, (const uint8_t *)nullptr, 0u, 0u,
+                       (const uint32_t *)nullptr, 0u, c->n_cells, (const uint32_t *)c->d_paircost.get(), d_sum);
+  else
+    hipLaunchKernelGGL(k_pairs_in_table<false>, dim3(1), dim3(1024), 0, c->stream, (const uint8_t *)c->d_paircnt.get(),
+                       lc.gstride, lc.H, lc.h_dev, lc.h_off, c->n_cells, (const uint32_t *)nullptr, d_sum);
+  HIPCHK(c, hipGetLastError());
+  unsigned long long *pin = c->h_pin->scratch_u64;
+  HIPCHK(c, hipMemcpyAsync(pin, d_sum, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, sync_stream(c));
+  out[0] = pin[0];
+  out[1] = lc.packed ? 1 : 0;
+  out[2] = lc.slab ? 1 : 0;
+  out[3] = (uint64_t)c->n_cells * lc.H;
   return LSQR_OK;
 }
 
