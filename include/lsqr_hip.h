@@ -446,7 +446,8 @@ LSQR_API int lsqr_ransac_grouped_sequential(
  *   Models, taken from the context's lsqr_set_model: LSQR_MODEL_PLANE, LSQR_MODEL_LINE and LSQR_MODEL_SPHERE in every
  *     dimension lsqr_set_model accepts for them, and LSQR_MODEL_LINE2D, whose parameters [n, a] carry a point: it is
  *     accepted by both.  lsqr_assign takes the sphere with either ls_type; lsqr_refine refuses the geometric sphere
- *     (its fit is Levenberg-Marquardt) with LSQR_ERR_INVALID.  Every other model returns LSQR_ERR_INVALID.
+ *     (its fit is Levenberg-Marquardt) with LSQR_ERR_INVALID: lsqr_refine_lm, below, takes it.  Every other model
+ *     returns LSQR_ERR_INVALID.
  *   Checks, in this order: a null context is refused before anything is touched; the model (none set: LSQR_ERR_STATE);
  *     n_models == 0 is a no-op returning LSQR_OK; n_models > 64, or a null params or labels_out (lsqr_assign), a null
  *     params_inout, fits, status_out, rounds_out or converged_out (lsqr_refine) (LSQR_ERR_INVALID); no records in the
@@ -464,6 +465,38 @@ LSQR_API int lsqr_refine(lsqr_ctx *ctx, double *params_inout /* host, n_models *
                          int32_t *labels_out /* nullable */, uint64_t *counts_out /* nullable, host: n_models + 1 */,
                          lsqr_fit_info *fits /* host, n_models */, int32_t *status_out /* host, n_models */,
                          size_t *rounds_out, int *converged_out);
+/* ---- lsqr_refine for the geometric sphere: a Levenberg-Marquardt run per model (csrc/assign_lm.h) ------------------
+ * lsqr_refine_lm is lsqr_refine -- its arguments, its loop, its stop rules, rounds_out / converged_out / counts_out /
+ * labels_out, the order of its checks, "every argument error writes nothing" -- for the one model lsqr_refine refuses.
+ * So here too the returned labels are always exactly lsqr_assign of the returned parameters, and max_rounds == 0 is
+ * lsqr_assign.
+ *   Models: LSQR_MODEL_SPHERE with LSQR_LS_GEOMETRIC (the default of lsqr_set_model's callers and of the reference) in
+ *     every dimension lsqr_set_model accepts (2..8).  Every other model, the algebraic sphere included, returns
+ *     LSQR_ERR_INVALID and writes nothing: lsqr_refine takes the fits in closed form.
+ *   Refit of model m in a round: with at least lsqr_min_subset records labelled m, the algebraic fit of those records
+ *     about the model's centre -- bit for bit the row lsqr_refine writes on an algebraic context -- is the START of a
+ *     Levenberg-Marquardt run over the same records, with the settings and the control flow of lsqr_ls_fit's geometric
+ *     sphere.  An evaluation is one pass over the records where they are, under the labels of the round, for all models
+ *     still running at once, one step launch and one 4-byte read.  The row is replaced only when the algebraic solve
+ *     gave a result AND the run ended with lm_info in 1..4; otherwise it keeps the values it had BEFORE the round (the
+ *     algebraic intermediate is never returned: the reference returns an empty vector and the caller keeps its model).
+ *   fits[m] and status_out[m] describe the last refit round: n_params (lsqr_num_params or 0), lm_info, lm_nfev,
+ *     reserved (the stall evaluation, as lsqr_ls_fit), cost, n_used; lm_info = 0 where no run started (too few records,
+ *     or no algebraic start).  status_out[m]: LSQR_OK or LSQR_EMPTY; LSQR_OK with a zeroed fit when no refit ran.
+ *   Round by round, model m's new row agrees within the LM tolerances with lsqr_set_mask(L_r == m) + lsqr_ls_fit(
+ *     use_mask = 1) on a geometric-sphere context over the same records: only the origin of the algebraic start and the
+ *     order of the fp64 sums differ.  No sum is a floating-point atomic: the same call twice gives the same bits.  Model
+ *     m's iterates are a function of its own records, their positions in the upload and its own trial points: the
+ *     other rows of the call, and where m sits among them, change nothing.
+ *   The context's hypotheses, mask, spatial index and the parameters of its last mask are left as they were; the work
+ *     runs on the context's stream.  The options lm_persist and lm_host do not apply (the step runs on the device, as
+ *     in lsqr_ransac_many_lm).  lsqr_multi handles and the grouped calls have no such form. */
+LSQR_API int lsqr_refine_lm(lsqr_ctx *ctx, double *params_inout /* host, n_models * lsqr_num_params */,
+                            size_t n_models, size_t max_rounds, int on_device /* 1: labels_out is a device pointer */,
+                            int32_t *labels_out /* nullable */,
+                            uint64_t *counts_out /* nullable, host: n_models + 1 */,
+                            lsqr_fit_info *fits /* host, n_models */, int32_t *status_out /* host, n_models */,
+                            size_t *rounds_out, int *converged_out);
 /* ---- the same with ONE MODEL SET PER LABEL (csrc/assign_grouped.h) -------------------------------------------------
  * lsqr_assign_grouped / lsqr_refine_grouped take what lsqr_ransac_grouped_sequential leaves -- params_out and
  * n_models_out, unchanged -- over the same groups array and the same resident records: row g * max_models + m of params

@@ -544,6 +544,10 @@ class Context:
         -> dict: params (M x P: params_r), labels (L_r: exactly assign(params)["labels"]), counts (M + 1, of L_r),
         status (OK or EMPTY per model for the last refit round; OK when none ran), n_used (records behind the last
         refit attempt), rounds (refits done) and converged."""
+        return self._refine(self._lib.lsqr_refine, params, max_rounds, labels_out)[0]
+
+    def _refine(self, call, params, max_rounds, labels_out):
+        """lsqr_refine or lsqr_refine_lm -> (refine's dict, the fits as a structured array)"""
         par, m, total, on_device, labels, l_ptr = self._assign_args(params, labels_out)
         if int(max_rounds) < 0:
             raise ValueError("max_rounds must not be negative")
@@ -553,13 +557,25 @@ class Context:
         fits = (L.FitInfo * max(m, 1))()
         status = np.zeros(max(m, 1), dtype=np.int32)
         rounds, conv = C.c_size_t(0), C.c_int(0)
-        self._chk(self._lib.lsqr_refine(self._h, L.ptr(par), m, int(max_rounds), 1 if on_device else 0, l_ptr,
-                                        L.ptr(counts), fits, L.ptr(status), C.byref(rounds), C.byref(conv)))
+        self._chk(call(self._h, L.ptr(par), m, int(max_rounds), 1 if on_device else 0, l_ptr, L.ptr(counts), fits,
+                       L.ptr(status), C.byref(rounds), C.byref(conv)))
         if not on_device:
             labels = labels[:total]
-        return dict(params=par, labels=labels, counts=counts, status=status[:m],
-                    n_used=np.ctypeslib.as_array(fits)[:m]["n_used"].copy(), rounds=int(rounds.value),
-                    converged=bool(conv.value))
+        f = np.ctypeslib.as_array(fits)[:m]
+        return dict(params=par, labels=labels, counts=counts, status=status[:m], n_used=f["n_used"].copy(),
+                    rounds=int(rounds.value), converged=bool(conv.value)), f
+
+    def refine_lm(self, params, max_rounds=8, labels_out=None):
+        """refine for the sphere with LS_GEOMETRIC, which refine refuses (lsqr_refine_lm): the same loop, and the refit
+        of a model is a Levenberg-Marquardt run over its own records from their algebraic fit, on the device, all
+        models at once.  A model whose run does not end with lm_info in 1..4 (or that has fewer than K records, or no
+        algebraic start) keeps the row it had before the round.  Any other model raises LsqrError(ERR_INVALID).
+        -> refine's dict, and per model for the last refit round lm_info, lm_nfev, cost and stall (the evaluation after
+        which the cost never again fell by more than 1e-7 relative); zeros where no run started."""
+        out, f = self._refine(self._lib.lsqr_refine_lm, params, max_rounds, labels_out)
+        out.update(lm_info=f["lm_info"].copy(), lm_nfev=f["lm_nfev"].copy(), cost=f["cost"].copy(),
+                   stall=f["reserved"].copy())
+        return out
 
     def _assign_grouped_args(self, groups, n_groups, params, n_models, labels_out):
         """the labels, rows and label buffer of assign_grouped / refine_grouped, groups and labels_out handled as in

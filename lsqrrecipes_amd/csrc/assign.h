@@ -28,8 +28,12 @@
 //   assign_refit       lane 0, after a solve kernel's sum: solve_small<M> about the model's own point (the body of
 //                      k_many_solve); a model with at least lsqr_min_subset records and a solve that succeeded gets
 //                      its new scan row, any other keeps its row
-//   k_assign_solve     one workgroup per model: its partials summed in chunk order by one lane per moment (the four
-//                      waves stage them through LDS), then assign_refit
+//   assign_sum_chunks  a model's blocks summed in chunk order by one lane per moment (the four waves stage them
+//                      through LDS): k_assign_solve's sum, and k_assign_lm_step's
+//   k_assign_solve     one workgroup per model: assign_sum_chunks, then assign_refit
+//
+// lsqr_refine_lm (assign_lm.h, the geometric sphere) runs this file's loop, assign_run<M, true>: the pass also stores
+// every chunk's presence word, the solve writes into a side array of start rows, and the refit is an LM stage.
 //
 // Order of the sums: kAssignChunk fixes it, as kManyPart does for the batched finish.  Nothing is summed with a
 // floating-point atomic, so two runs of one call give the same bits.
@@ -165,7 +169,8 @@ __global__ __launch_bounds__(kBlock) void k_assign_prepare(const double *__restr
 // chunk's base is in the pointers, so its records are [0, n), n <= kAssignChunk, and every index is 32-bit.
 // data: the chunk's records, `stride` doubles apart; rows: the n_models scan rows of the chunk's model set; labels /
 // residuals (nullable) / old (nullable): the chunk's n entries; changed: the word that counts labels[i] != old[i];
-// counts: one word per model; partials (WITH_MOMENTS): the chunk's [model][AccLs<M>::N]
+// counts: one word per model; partials (WITH_MOMENTS): the chunk's [model][AccLs<M>::N]; presence (WITH_MOMENTS,
+// nullable): the chunk's word for the mask of the models that own a record of the chunk
 template <class M, bool WITH_MOMENTS>
 __device__ __forceinline__ void assign_pass_chunk(const double *__restrict__ data, size_t stride, uint32_t n,
                                                   const double *__restrict__ rows, int n_models, int org_off,
@@ -173,7 +178,8 @@ __device__ __forceinline__ void assign_pass_chunk(const double *__restrict__ dat
                                                   double *__restrict__ residuals, const int32_t *__restrict__ old,
                                                   unsigned long long *__restrict__ changed,
                                                   unsigned long long *__restrict__ counts,
-                                                  double *__restrict__ partials) {
+                                                  double *__restrict__ partials,
+                                                  unsigned long long *__restrict__ presence) {
   typedef AccLs<M> A;
   static_assert(A::N <= 64, "one lane per moment");
   constexpr int R = kAssignPerLane, W = kBlock / 64;
@@ -278,6 +284,7 @@ __device__ __forceinline__ void assign_pass_chunk(const double *__restrict__ dat
   if constexpr (WITH_MOMENTS) {
     for (uint32_t e = threadIdx.x; e < (uint32_t)n_models * A::N; e += kBlock)
       if (!((present >> (e / A::N)) & 1ull)) partials[e] = 0.0;
+    if (presence && threadIdx.x == 0) *presence = present;
   }
   __syncthreads();
   if ((int)threadIdx.x < n_models && s_cnt[threadIdx.x])
@@ -295,17 +302,20 @@ template <class M, bool WITH_MOMENTS> constexpr int kAssignPassWaves = 1;
 template <> constexpr int kAssignPassWaves<PlaneModelN<4>, true> = 4;
 
 // chunk blockIdx.x of the context's n records.  data: `stride` doubles apart; labels: n entries; residuals, old:
-// nullable; counters: the ASG_ words, zeroed by the caller; partials (WITH_MOMENTS): [chunk][model][AccLs<M>::N]
+// nullable; counters: the ASG_ words, zeroed by the caller; partials (WITH_MOMENTS): [chunk][model][AccLs<M>::N];
+// presence (WITH_MOMENTS, nullable): one word per chunk (the LM stage of assign_lm.h reads it)
 template <class M, bool WITH_MOMENTS>
 __global__ __launch_bounds__(kBlock, (kAssignPassWaves<M, WITH_MOMENTS>)) void k_assign_moments(
     const double *__restrict__ data, size_t stride, uint32_t n, const double *__restrict__ rows, int n_models,
     int org_off, ModelConsts mc, int32_t *__restrict__ labels, double *__restrict__ residuals,
-    const int32_t *__restrict__ old, unsigned long long *__restrict__ counters, double *__restrict__ partials) {
+    const int32_t *__restrict__ old, unsigned long long *__restrict__ counters, double *__restrict__ partials,
+    unsigned long long *__restrict__ presence) {
   const uint32_t c0 = blockIdx.x * kAssignChunk, left = n - c0;  // (c0 < n: no wrap)
   if constexpr (WITH_MOMENTS) partials += (size_t)blockIdx.x * n_models * AccLs<M>::N;
   assign_pass_chunk<M, WITH_MOMENTS>(data + (size_t)c0 * stride, stride, left < kAssignChunk ? left : kAssignChunk, rows,
                                      n_models, org_off, mc, labels + c0, residuals ? residuals + c0 : nullptr,
-                                     old ? old + c0 : nullptr, counters + ASG_CHANGED, counters + ASG_COUNT, partials);
+                                     old ? old + c0 : nullptr, counters + ASG_CHANGED, counters + ASG_COUNT, partials,
+                                     presence ? presence + blockIdx.x : nullptr);
 }
 
 // What lane 0 of a solve kernel does with a model's summed moments: the refit about the model's own point (the body of
@@ -327,26 +337,17 @@ __device__ __forceinline__ bool assign_refit(const double *mom, double *row_m, u
   return true;
 }
 
-// one workgroup per model m: the partials of its `chunks` chunks summed in chunk order, then assign_refit.  A strictly
-// serial sum of thousands of partials is bound by memory latency if one lane loads what it adds, so the four waves
-// stage tiles of kTile chunks through LDS -- every lane a few loads, all in flight at once, the next tile's issued
-// before this one is summed -- and lane k of wave 0 adds column k of the tile in chunk order.
-// counters[ASG_USED + m] and counters[ASG_OK + m] say what happened.
-template <class M>
-__global__ __launch_bounds__(kBlock) void k_assign_solve(const double *__restrict__ partials, uint32_t chunks,
-                                                         int n_models, int org_off, ModelConsts mc, double *rows,
-                                                         unsigned long long *counters) {
-  constexpr int N = M::NMOM;
-  constexpr int kTile = N <= 16 ? 512 : 128;            // chunks per tile: 40 KiB of LDS at N = 10, 55 KiB at N = 55
+// One model's blocks of N sums, `qs` doubles apart from chunk to chunk, summed in chunk order by a workgroup of kBlock
+// lanes: mom[k] = sum over the chunks of src[chunk * qs + k], then a barrier.  A strictly serial sum of thousands of
+// partials is bound by memory latency if one lane loads what it adds, so the four waves stage tiles of kTile chunks
+// through LDS (s_t: kTile * N doubles) -- every lane a few loads, all in flight at once, the next tile's issued before
+// this one is summed -- and lane k of wave 0 adds column k of the tile in chunk order.
+template <int N, int kTile>
+__device__ __forceinline__ void assign_sum_chunks(const double *__restrict__ src, size_t qs, uint32_t chunks,
+                                                  double *s_t, double *mom) {
   constexpr int E = (kTile * N + kBlock - 1) / kBlock;  // elements of a tile per lane
   static_assert(N <= 64, "one lane per moment");
-  __shared__ double s_t[kTile * N];
-  __shared__ double mom[MOM_MAX];
-  __shared__ double ws[M::NMOM > 40 ? 512 : 8];
-  __shared__ SolveOut so;
-  const int m = blockIdx.x, k = threadIdx.x;
-  const double *src = partials + (size_t)m * N;
-  const size_t qs = (size_t)n_models * N;  // from one chunk's block of model m to the next chunk's
+  const int k = threadIdx.x;
   double pre[E], t = 0.0;
   auto fetch = [&](uint32_t q0) {  // tile [q0, q0 + kTile) -> registers
     const uint32_t cnt = chunks - q0 < (uint32_t)kTile ? chunks - q0 : (uint32_t)kTile;
@@ -372,19 +373,59 @@ __global__ __launch_bounds__(kBlock) void k_assign_solve(const double *__restric
   }
   if (k < N) mom[k] = t;
   __syncthreads();
-  if (k != 0) return;
+}
+
+// one workgroup per model m: the partials of its `chunks` chunks summed in chunk order (assign_sum_chunks), then
+// assign_refit.  counters[ASG_USED + m] and counters[ASG_OK + m] say what happened.  start (nullable): n_models rows
+// of M::SP; given, row m of `rows` is only read, and row m of `start` gets what `rows` would have got: the new scan
+// row where assign_refit says true, a copy of the old one where not (the LM stage of assign_lm.h starts from it)
+template <class M>
+__global__ __launch_bounds__(kBlock) void k_assign_solve(const double *__restrict__ partials, uint32_t chunks,
+                                                         int n_models, int org_off, ModelConsts mc, double *rows,
+                                                         unsigned long long *counters, double *start) {
+  constexpr int N = M::NMOM;
+  constexpr int kTile = N <= 16 ? 512 : 128;  // chunks per tile: 40 KiB of LDS at N = 10, 55 KiB at N = 55
+  __shared__ double s_t[kTile * N];
+  __shared__ double mom[MOM_MAX];
+  __shared__ double ws[M::NMOM > 40 ? 512 : 8];
+  __shared__ SolveOut so;
+  const int m = blockIdx.x;
+  assign_sum_chunks<N, kTile>(partials + (size_t)m * N, (size_t)n_models * N, chunks, s_t, mom);
+  if (threadIdx.x != 0) return;
   const unsigned long long cnt = counters[ASG_COUNT + m];
   counters[ASG_USED + m] = cnt;
-  counters[ASG_OK + m] = assign_refit<M>(mom, rows + (size_t)m * M::SP, cnt, org_off, mc, ws, &so) ? 1 : 0;
+  double *row_m = rows + (size_t)m * M::SP;
+  if (start) {
+    for (int j = 0; j < (int)M::SP; j++) start[(size_t)m * M::SP + j] = row_m[j];
+    row_m = start + (size_t)m * M::SP;
+  }
+  counters[ASG_OK + m] = assign_refit<M>(mom, row_m, cnt, org_off, mc, ws, &so) ? 1 : 0;
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------
+struct AssignLmOut {  // lsqr_refine_lm: what the LM run of one model's last refit left (zero where none ran)
+  int lm_info, lm_nfev, stall, pad;
+  double cost;
+};
+
 struct AssignBufs {  // owned by the context, grown on demand
   DevBuf<double> d_par, d_rows, d_partials, d_res;
   DevBuf<int32_t> d_labels[2];
   DevBuf<unsigned long long> d_cnt;
-  PinBuf<char> h_pin;
+  PinBuf<char> h_pin;  // kAssignPinBytes, laid out by the kAssignPin offsets
+  // the LM stage of lsqr_refine_lm (assign_lm.h)
+  DevBuf<double> d_start, d_lm_partials;
+  DevBuf<unsigned long long> d_presence, d_lm_mask;  // one word per chunk; the bits of the models whose LM goes on
+  DevBuf<uint32_t> d_lm_live;                         // their number
+  DevBuf<LmState> d_lm_state;
+  DevBuf<AssignLmOut> d_lm_out;
 };
+
+// h_pin: the rows, the ASG_ words, then lsqr_refine_lm's AssignLmOut per model and its live counter
+constexpr size_t kAssignPinCnt = sizeof(double) * kAssignMaxModels * 16;
+constexpr size_t kAssignPinLm = kAssignPinCnt + sizeof(unsigned long long) * ASG_WORDS;
+constexpr size_t kAssignPinLive = kAssignPinLm + sizeof(AssignLmOut) * kAssignMaxModels;
+constexpr size_t kAssignPinBytes = kAssignPinLive + sizeof(unsigned long long);
 
 struct AssignJob {
   hipStream_t stream = nullptr;
@@ -422,10 +463,18 @@ void assign_fit_out(size_t rounds, unsigned long long okf, unsigned long long us
   }
 }
 
+#if defined(__HIPCC__)
+// the LM stage of lsqr_refine_lm's round (assign_lm.h): its buffers, and the refit of every model from the moments
+// and the presence words the pass has just left, under the labels `lab`; it leaves the new rows in B.d_rows
+template <class M> int assign_lm_reserve(AssignJob &J, uint32_t chunks);
+template <class M> int assign_lm_run(AssignJob &J, const int32_t *lab, uint32_t chunks);
+#endif
+
 // lsqr_refine's loop (lsqr_assign: max_rounds == 0).  Round r: one pass -- labels L_r and, unless it is the last
 // round allowed, the moments of L_r --, the 8-byte changed-counter (with the counts: one copy) to the host, one solve
 // launch.  Returns after the stream has drained; the outputs are written only then.
-template <class M>
+// LM (lsqr_refine_lm, the geometric sphere): the same loop; the refit is assign_lm_run, and the fits carry its record.
+template <class M, bool LM = false>
 int assign_run(AssignJob &J) {
   AssignBufs &B = *J.B;
   const int nm = (int)J.n_models, org_off = fit_origin_offset<M>(J.cfg);
@@ -433,9 +482,8 @@ int assign_run(AssignJob &J) {
   const bool refine = J.max_rounds > 0;
   // no refit and device pointers: the kernel writes the caller's buffers
   const bool direct = !refine && J.on_device && J.labels_out;
-  const size_t pin_bytes = sizeof(double) * kAssignMaxModels * 16 + sizeof(unsigned long long) * ASG_WORDS;
   static_assert(M::SP <= 16 && M::P <= 16, "pinned staging of the rows");
-  if (!B.h_pin.get()) MANYCHK(B.h_pin.alloc(pin_bytes));
+  if (!B.h_pin.get()) MANYCHK(B.h_pin.alloc(kAssignPinBytes));
   MANYCHK(many_grow(B.d_par, (size_t)kAssignMaxModels * 16));
   MANYCHK(many_grow(B.d_rows, (size_t)kAssignMaxModels * 16));
   MANYCHK(many_grow(B.d_cnt, (size_t)ASG_WORDS));
@@ -444,9 +492,14 @@ int assign_run(AssignJob &J) {
   if (refine) {
     MANYCHK(many_grow(B.d_labels[1], (size_t)n));
     MANYCHK(many_grow(B.d_partials, (size_t)chunks * nm * M::NMOM));
+    if constexpr (LM) {
+      const int st = assign_lm_reserve<M>(J, chunks);
+      if (st != LSQR_OK) return st;
+    }
   }
   double *h_rows = (double *)B.h_pin.get();
-  unsigned long long *h_cnt = (unsigned long long *)(B.h_pin.get() + sizeof(double) * kAssignMaxModels * 16);
+  unsigned long long *h_cnt = (unsigned long long *)(B.h_pin.get() + kAssignPinCnt);
+  [[maybe_unused]] AssignLmOut *h_lm = (AssignLmOut *)(B.h_pin.get() + kAssignPinLm);
 
   memcpy(h_rows, J.params, sizeof(double) * (size_t)nm * M::P);
   MANYCHK(hipMemcpyAsync(B.d_par, h_rows, sizeof(double) * (size_t)nm * M::P, hipMemcpyHostToDevice, J.stream));
@@ -467,10 +520,11 @@ int assign_run(AssignJob &J) {
       MANYCHK(hipMemsetAsync(B.d_cnt, 0, sizeof(unsigned long long) * (ASG_COUNT + kAssignMaxModels), J.stream));
     if (last)
       hipLaunchKernelGGL((k_assign_moments<M, false>), dim3(chunks), dim3(kBlock), 0, J.stream, J.data, J.stride, n,
-                         B.d_rows, nm, org_off, J.mc, lab, res, old, B.d_cnt, nullptr);
+                         B.d_rows, nm, org_off, J.mc, lab, res, old, B.d_cnt, nullptr, nullptr);
     else
       hipLaunchKernelGGL((k_assign_moments<M, true>), dim3(chunks), dim3(kBlock), 0, J.stream, J.data, J.stride, n,
-                         B.d_rows, nm, org_off, J.mc, lab, res, old, B.d_cnt, B.d_partials);
+                         B.d_rows, nm, org_off, J.mc, lab, res, old, B.d_cnt, B.d_partials,
+                         LM ? B.d_presence.get() : nullptr);
     MANYCHK(hipGetLastError());
     MANYCHK(hipMemcpyAsync(h_cnt, B.d_cnt, sizeof(unsigned long long) * (ASG_COUNT + kAssignMaxModels),
                           hipMemcpyDeviceToHost, J.stream));
@@ -480,9 +534,14 @@ int assign_run(AssignJob &J) {
       break;
     }
     if (last) break;
-    hipLaunchKernelGGL((k_assign_solve<M>), dim3(nm), dim3(kBlock), 0, J.stream, B.d_partials, chunks, nm, org_off, J.mc,
-                       B.d_rows, B.d_cnt);
-    MANYCHK(hipGetLastError());
+    if constexpr (LM) {
+      const int st = assign_lm_run<M>(J, lab, chunks);
+      if (st != LSQR_OK) return st;
+    } else {
+      hipLaunchKernelGGL((k_assign_solve<M>), dim3(nm), dim3(kBlock), 0, J.stream, B.d_partials, chunks, nm, org_off,
+                         J.mc, B.d_rows, B.d_cnt, nullptr);
+      MANYCHK(hipGetLastError());
+    }
     r++;
     cur ^= 1;
   }
@@ -492,6 +551,8 @@ int assign_run(AssignJob &J) {
     MANYCHK(hipMemcpyAsync(h_rows, B.d_rows, sizeof(double) * (size_t)nm * M::SP, hipMemcpyDeviceToHost, J.stream));
     MANYCHK(hipMemcpyAsync(h_cnt + ASG_USED, B.d_cnt + ASG_USED, sizeof(unsigned long long) * 2 * kAssignMaxModels,
                           hipMemcpyDeviceToHost, J.stream));
+    if constexpr (LM)
+      MANYCHK(hipMemcpyAsync(h_lm, B.d_lm_out, sizeof(AssignLmOut) * (size_t)nm, hipMemcpyDeviceToHost, J.stream));
   }
   if (J.labels_out && !direct)
     MANYCHK(hipMemcpyAsync(J.labels_out, B.d_labels[cur], sizeof(int32_t) * (size_t)n,
@@ -507,9 +568,17 @@ int assign_run(AssignJob &J) {
     for (int m = 0; m < nm; m++) sum += (J.counts_out[m] = h_cnt[ASG_COUNT + m]);
     J.counts_out[nm] = (uint64_t)n - sum;
   }
-  if (J.fits)  // lsqr_refine
-    for (int m = 0; m < nm; m++)
+  if (J.fits)  // lsqr_refine, lsqr_refine_lm
+    for (int m = 0; m < nm; m++) {
       assign_fit_out<M>(r, h_cnt[ASG_OK + m], h_cnt[ASG_USED + m], &J.status_out[m], &J.fits[m]);
+      if constexpr (LM)
+        if (r > 0) {
+          J.fits[m].lm_info = h_lm[m].lm_info;
+          J.fits[m].lm_nfev = h_lm[m].lm_nfev;
+          J.fits[m].reserved = h_lm[m].stall;
+          J.fits[m].cost = h_lm[m].cost;
+        }
+    }
   J.rounds = r;
   J.converged = converged ? 1 : 0;
   return LSQR_OK;

@@ -71,7 +71,7 @@ __global__ __launch_bounds__(kBlock, (kAssignPassWaves<M, WITH_MOMENTS>)) void k
   assign_pass_chunk<M, WITH_MOMENTS>(data + c0 * stride, stride, left < kAssignChunk ? (uint32_t)left : kAssignChunk,
                                      rows + (size_t)g * max_models * M::SP, n_models, org_off, mc, labels + c0,
                                      residuals ? residuals + c0 : nullptr, old ? old + c0 : nullptr, changed + g,
-                                     counts + (size_t)g * max_models, partials);
+                                     counts + (size_t)g * max_models, partials, nullptr);
 }
 
 // after pass r (last: r == max_rounds): every group still going converges, stops, or goes on with a zeroed

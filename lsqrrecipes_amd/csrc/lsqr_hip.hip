@@ -45,6 +45,7 @@
 #include "many_sequential.h"
 #include "grouped.h"
 #include "assign.h"
+#include "assign_lm.h"
 #include "assign_grouped.h"
 
 #include <condition_variable>
@@ -323,7 +324,7 @@ struct lsqr_ctx {
   long long opt_many_round = 0;  // lsqr_ransac_many: hypotheses per round (0 = kManyRoundDefault)
   bool opt_many_ex_fused = true;  // lsqr_ransac_many_exhaustive: small problems take k_many_ex_small
   std::unique_ptr<ManyBufs> many;  // lsqr_ransac_many's buffers (its own: the context's upload is not touched)
-  std::unique_ptr<AssignBufs> assign;  // lsqr_assign / lsqr_refine (assign.h): rows, labels, partials, counters
+  std::unique_ptr<AssignBufs> assign;  // lsqr_assign / lsqr_refine / lsqr_refine_lm (assign.h, assign_lm.h)
   std::unique_ptr<AssignGrpBufs> assign_grp;  // lsqr_assign_grouped / lsqr_refine_grouped (assign_grouped.h)
   // lsqr_ransac_sequential (sequential.h): the survivors of a round go from the current buffer into the OTHER of two
   // owned buffers (never into the caller's upload), their upload indices beside them; labels in upload order
@@ -4335,21 +4336,33 @@ int lsqr_ransac_grouped_sequential(lsqr_ctx *c, const int32_t *groups, size_t n_
 }
 
 // ---- nearest-model assignment and refit (assign.h, assign_grouped.h) -------------------------------------------------
-// What the four entry points share.  The checks, in the contract's order: the context; the model gate; count == 0
+// What the five entry points share.  The checks, in the contract's order: the context; the model gate (AssignGate:
+// what the entry point does with the geometric sphere, whose fit is iterative); count == 0
 // (n_models, or n_groups of the grouped calls) is LSQR_OK with every output untouched; more than 64 models; own(), the
 // entry point's own arguments; the context holds a model and records; their count.  Then run(tag), the run function
 // on the model -- it has waited for the stream when it returns.  The context's upload, hypotheses, mask, index and
 // d_par are not touched: the calls have buffers of their own (lsqr_ctx::assign, lsqr_ctx::assign_grp).
 extern "C++" {
+enum AssignGate {
+  ASSIGN_GATE_ANY,     // the assignments: every model of assign_model_ok
+  ASSIGN_GATE_CLOSED,  // the refits in closed form: not the geometric sphere
+  ASSIGN_GATE_LM       // lsqr_refine_lm: the geometric sphere alone
+};
 template <class Own, class Run>
-static int assign_frame(lsqr_ctx *c, const char *fn, bool refine, const char *takes, size_t count, size_t max_models,
-                        const char *err, Own own, Run run) {
+static int assign_frame(lsqr_ctx *c, const char *fn, AssignGate gate, const char *takes, size_t count,
+                        size_t max_models, const char *err, Own own, Run run) {
   int st = need_ready(c, false);
   if (st != LSQR_OK) return st;
-  if (!assign_model_ok(c->cfg))
-    return fail(c, LSQR_ERR_INVALID, "%s: plane, line, sphere and 2-D line only (model %d)", fn, c->cfg.model);
-  if (refine && wants_lm(c->cfg))
-    return fail(c, LSQR_ERR_INVALID, "%s: the geometric sphere's fit is iterative; %s takes it", fn, takes);
+  if (gate == ASSIGN_GATE_LM) {
+    if (!(c->cfg.model == LSQR_MODEL_SPHERE && c->cfg.ls_type == LSQR_LS_GEOMETRIC))
+      return fail(c, LSQR_ERR_INVALID, "%s: the sphere with LSQR_LS_GEOMETRIC only (model %d); %s takes the fits in "
+                  "closed form", fn, c->cfg.model, takes);
+  } else {
+    if (!assign_model_ok(c->cfg))
+      return fail(c, LSQR_ERR_INVALID, "%s: plane, line, sphere and 2-D line only (model %d)", fn, c->cfg.model);
+    if (gate == ASSIGN_GATE_CLOSED && wants_lm(c->cfg))
+      return fail(c, LSQR_ERR_INVALID, "%s: the geometric sphere's fit is iterative; %s takes it", fn, takes);
+  }
   if (count == 0) return LSQR_OK;
   if (max_models > (size_t)kAssignMaxModels) return fail(c, LSQR_ERR_INVALID, "%s: more than 64 models", fn);
   if ((st = own()) != LSQR_OK) return st;
@@ -4367,10 +4380,10 @@ static int assign_frame(lsqr_ctx *c, const char *fn, bool refine, const char *ta
   return LSQR_OK;
 }
 
-// lsqr_assign and lsqr_refine; args: the entry point's own pointers are all there
-static int assign_call(lsqr_ctx *c, const char *fn, bool refine, bool args, AssignJob &J) {
+// lsqr_assign, lsqr_refine and lsqr_refine_lm; args: the entry point's own pointers are all there
+static int assign_call(lsqr_ctx *c, const char *fn, AssignGate gate, bool args, AssignJob &J) {
   return assign_frame(
-      c, fn, refine, "lsqr_assign", J.n_models, J.n_models, J.err,
+      c, fn, gate, gate == ASSIGN_GATE_LM ? "lsqr_refine" : "lsqr_assign", J.n_models, J.n_models, J.err,
       [&]() -> int { return args ? LSQR_OK : fail(c, LSQR_ERR_INVALID, "%s: null argument", fn); },
       [&](auto tag) -> int {
         if (!c->assign) c->assign.reset(new AssignBufs());
@@ -4381,7 +4394,11 @@ static int assign_call(lsqr_ctx *c, const char *fn, bool refine, bool args, Assi
         J.stride = c->stride;
         J.n = (uint32_t)c->n;
         J.B = c->assign.get();
-        return assign_run<typename decltype(tag)::type>(J);
+        typedef typename decltype(tag)::type M;
+        if constexpr (requires { M::NMOM_LM; }) {  // (the sphere)
+          if (gate == ASSIGN_GATE_LM) return assign_run<M, true>(J);
+        }
+        return assign_run<M>(J);
       });
 }
 }  // extern "C++"
@@ -4396,12 +4413,13 @@ int lsqr_assign(lsqr_ctx *c, const double *params, size_t n_models, int on_devic
   J.labels_out = labels_out;
   J.residuals_out = residuals_out;
   J.counts_out = counts_out;
-  return assign_call(c, "lsqr_assign", false, params && labels_out, J);
+  return assign_call(c, "lsqr_assign", ASSIGN_GATE_ANY, params && labels_out, J);
 }
 
-int lsqr_refine(lsqr_ctx *c, double *params_inout, size_t n_models, size_t max_rounds, int on_device,
-                int32_t *labels_out, uint64_t *counts_out, lsqr_fit_info *fits, int32_t *status_out,
-                size_t *rounds_out, int *converged_out) {
+extern "C++" {
+static int refine_call(lsqr_ctx *c, const char *fn, AssignGate gate, double *params_inout, size_t n_models,
+                       size_t max_rounds, int on_device, int32_t *labels_out, uint64_t *counts_out,
+                       lsqr_fit_info *fits, int32_t *status_out, size_t *rounds_out, int *converged_out) {
   AssignJob J;
   J.params = params_inout;
   J.n_models = n_models;
@@ -4412,12 +4430,27 @@ int lsqr_refine(lsqr_ctx *c, double *params_inout, size_t n_models, size_t max_r
   J.fits = fits;
   J.status_out = status_out;
   const bool args = params_inout && fits && status_out && rounds_out && converged_out;
-  const int st = assign_call(c, "lsqr_refine", true, args, J);
+  const int st = assign_call(c, fn, gate, args, J);
   if (st == LSQR_OK && n_models > 0) {
     *rounds_out = J.rounds;
     *converged_out = J.converged;
   }
   return st;
+}
+}  // extern "C++"
+
+int lsqr_refine(lsqr_ctx *c, double *params_inout, size_t n_models, size_t max_rounds, int on_device,
+                int32_t *labels_out, uint64_t *counts_out, lsqr_fit_info *fits, int32_t *status_out,
+                size_t *rounds_out, int *converged_out) {
+  return refine_call(c, "lsqr_refine", ASSIGN_GATE_CLOSED, params_inout, n_models, max_rounds, on_device, labels_out,
+                     counts_out, fits, status_out, rounds_out, converged_out);
+}
+
+int lsqr_refine_lm(lsqr_ctx *c, double *params_inout, size_t n_models, size_t max_rounds, int on_device,
+                   int32_t *labels_out, uint64_t *counts_out, lsqr_fit_info *fits, int32_t *status_out,
+                   size_t *rounds_out, int *converged_out) {
+  return refine_call(c, "lsqr_refine_lm", ASSIGN_GATE_LM, params_inout, n_models, max_rounds, on_device, labels_out,
+                     counts_out, fits, status_out, rounds_out, converged_out);
 }
 
 // lsqr_assign_grouped and lsqr_refine_grouped.  The sort and the packed copy live in the batched calls' buffers
@@ -4425,7 +4458,7 @@ int lsqr_refine(lsqr_ctx *c, double *params_inout, size_t n_models, size_t max_r
 extern "C++" {
 static int assign_grouped_call(lsqr_ctx *c, const char *fn, bool args, AssignGrpJob &J) {
   return assign_frame(
-      c, fn, J.refine, "lsqr_assign_grouped", J.n_groups, J.max_models, J.err,
+      c, fn, J.refine ? ASSIGN_GATE_CLOSED : ASSIGN_GATE_ANY, "lsqr_assign_grouped", J.n_groups, J.max_models, J.err,
       [&]() -> int {
         if (J.n_groups > 0x7FFFFFFFull) return fail(c, LSQR_ERR_INVALID, "%s: more than 2^31 - 1 groups", fn);
         if (!args || !J.groups || !J.params || !J.n_models) return fail(c, LSQR_ERR_INVALID, "%s: null argument", fn);

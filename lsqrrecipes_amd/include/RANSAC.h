@@ -392,7 +392,7 @@ class RANSAC {
   // -> the refits done; `models` and `labels` are models_r and L_r, so the labels are always the assignment of the
   // returned models.  The device path is ONE call (lsqr_refine: a round is one pass over the records on the device);
   // the host loop, taken as in assignToModels and for the geometric sphere (its fit is iterative), assigns by the
-  // first agreeing model.
+  // first agreeing model.  refineModelsLM (below) is the device path of the geometric sphere.
   static size_t refineModels(std::vector<std::vector<S> > &models, ParametersEstimator<T, S> *paramEstimator,
                              std::vector<T> &data, size_t maxRounds, std::vector<int> &labels,
                              bool *converged = NULL) {
@@ -403,22 +403,25 @@ class RANSAC {
     if (models.empty() || data.empty()) return 0;
     if (!paramEstimator->deviceModel(cfg) || forceHostLoop() || !assignOnDevice(cfg, true))
       return pluginRefine(models, paramEstimator, data, maxRounds, labels, converged);
-    detail::Device &d = detail::Device::instance();
-    lsqr_ctx *ctx = d.ctx();
-    if (lsqr_multi *m = d.multi()) ctx = lsqr_multi_ctx(m, 0);
-    d.check(lsqr_set_model(ctx, &cfg));
-    d.check(lsqr_upload(ctx, &data[0], data.size(), sizeof(T)));
-    const size_t M = models.size(), P = (size_t)lsqr_num_params(&cfg);
-    std::vector<double> par = packModels(models, cfg);
-    std::vector<int32_t> lab(data.size()), status(M);
-    std::vector<lsqr_fit_info> fits(M);
-    size_t rounds = 0;
-    int conv = 0;
-    d.check(lsqr_refine(ctx, &par[0], M, maxRounds, 0, &lab[0], NULL, &fits[0], &status[0], &rounds, &conv));
-    for (size_t m = 0; m < M; m++) models[m].assign(&par[m * P], &par[m * P] + P);
-    labels.assign(lab.begin(), lab.end());
-    if (converged) *converged = conv != 0;
-    return rounds;
+    return refineOnDevice(lsqr_refine, cfg, models, data, maxRounds, labels, converged);
+  }
+
+  // refineModels for the sphere estimator with the geometric least-squares fit (its default), on the device: ONE call
+  // (lsqr_refine_lm).  The loop, the stop rules and what comes back are refineModels'; the assignment is the device's
+  // (the NEAREST agreeing model, not the first), and the refit of a model is a Levenberg-Marquardt run over its own
+  // records from their algebraic fit, as SphereParametersEstimator::leastSquaresEstimate runs one; a model whose run
+  // gives no result keeps its parameters.  Any other estimator throws std::invalid_argument: refineModels takes it.
+  static size_t refineModelsLM(std::vector<std::vector<S> > &models, ParametersEstimator<T, S> *paramEstimator,
+                               std::vector<T> &data, size_t maxRounds, std::vector<int> &labels,
+                               bool *converged = NULL) {
+    lsqr_model_cfg cfg;
+    if (!paramEstimator) throw std::invalid_argument("lsqrRecipes::RANSAC: null estimator");
+    if (!paramEstimator->deviceModel(cfg) || cfg.model != LSQR_MODEL_SPHERE || cfg.ls_type != LSQR_LS_GEOMETRIC)
+      throw std::invalid_argument("lsqrRecipes::RANSAC: refineModelsLM takes the geometric sphere only");
+    labels.assign(data.size(), -1);
+    if (converged) *converged = false;
+    if (models.empty() || data.empty()) return 0;
+    return refineOnDevice(lsqr_refine_lm, cfg, models, data, maxRounds, labels, converged);
   }
 
   // assignToModels with one model set per label on resident records (not in the reference), the follow-up of
@@ -839,6 +842,29 @@ class RANSAC {
   static bool assignOnDevice(const lsqr_model_cfg &cfg, bool refit) {
     if (cfg.model == LSQR_MODEL_SPHERE) return !refit || cfg.ls_type == LSQR_LS_ALGEBRAIC;
     return cfg.model == LSQR_MODEL_PLANE || cfg.model == LSQR_MODEL_LINE || cfg.model == LSQR_MODEL_LINE2D;
+  }
+
+  // the device path of refineModels (lsqr_refine) and of refineModelsLM (lsqr_refine_lm)
+  typedef int (*RefineCall)(lsqr_ctx *, double *, size_t, size_t, int, int32_t *, uint64_t *, lsqr_fit_info *,
+                            int32_t *, size_t *, int *);
+  static size_t refineOnDevice(RefineCall call, lsqr_model_cfg &cfg, std::vector<std::vector<S> > &models,
+                               std::vector<T> &data, size_t maxRounds, std::vector<int> &labels, bool *converged) {
+    detail::Device &d = detail::Device::instance();
+    lsqr_ctx *ctx = d.ctx();
+    if (lsqr_multi *m = d.multi()) ctx = lsqr_multi_ctx(m, 0);
+    d.check(lsqr_set_model(ctx, &cfg));
+    d.check(lsqr_upload(ctx, &data[0], data.size(), sizeof(T)));
+    const size_t M = models.size(), P = (size_t)lsqr_num_params(&cfg);
+    std::vector<double> par = packModels(models, cfg);
+    std::vector<int32_t> lab(data.size()), status(M);
+    std::vector<lsqr_fit_info> fits(M);
+    size_t rounds = 0;
+    int conv = 0;
+    d.check(call(ctx, &par[0], M, maxRounds, 0, &lab[0], NULL, &fits[0], &status[0], &rounds, &conv));
+    for (size_t m = 0; m < M; m++) models[m].assign(&par[m * P], &par[m * P] + P);
+    labels.assign(lab.begin(), lab.end());
+    if (converged) *converged = conv != 0;
+    return rounds;
   }
 
   // the models as rows of lsqr_num_params doubles

@@ -33,7 +33,15 @@ The parent's only route, loop_call_ms: per group a host gather (from one stable 
 written back, timed on the first --loop-groups groups and scaled by n_groups / groups timed (the scaling is stated in
 the line).  For (a) refine_round_ms is Context.refine on the same records and rows: what the sort, the gather and
 the scatter cost is grouped_call_ms - refine_call_ms.  lane_share = records / (workgroups x 2048): the share of the
-pass's lanes that hold a record."""
+pass's lanes that hold a record.
+
+--lm: Context.refine_lm (lsqr_refine_lm: the geometric sphere, a Levenberg-Marquardt run per model on the device) on the
+--model sphere scene in 3-D: M = 4 and 64 rows, the four planted spheres moved off by 0.05 per centre coordinate, each
+M / 4 times with radii up to +-0.4 apart.  Three kinds alternate in one process: refine_lm_round_ms as refine_round_ms
+above; host_round_ms, the round the entry points allowed before -- Context.assign with its labels to the host, then per
+model set_mask(labels == m) + ls_fit(use_mask=True) on the same geometric context --; and alg_refine_round_ms,
+Context.refine on an algebraic context over the same records and rows, for scale.  lm_nfev: the evaluations per model
+in the last refit round of the R2 call (a round costs about 1 + max(lm_nfev) passes over the records)."""
 import argparse
 import json
 import os
@@ -111,17 +119,99 @@ def baseline_round(ctx, rows):
     return new
 
 
-def refine_rounds(ctx, rows, max_rounds):
-    """lsqr_refine without labels_out -> rounds done"""
+def refine_rounds(ctx, rows, max_rounds, lm=False, nfev=None):
+    """lsqr_refine (lm: lsqr_refine_lm) without labels_out -> rounds done; nfev (a list): gets the models' lm_nfev"""
     import ctypes as C
     par = np.array(rows, dtype=np.float64, order="C")
     m = par.shape[0]
     fits = (L.FitInfo * m)()
     status = np.zeros(m, dtype=np.int32)
     rounds, conv = C.c_size_t(0), C.c_int(0)
-    ctx._chk(ctx._lib.lsqr_refine(ctx._h, L.ptr(par), m, max_rounds, 0, None, None, fits, L.ptr(status),
-                                  C.byref(rounds), C.byref(conv)))
+    call = ctx._lib.lsqr_refine_lm if lm else ctx._lib.lsqr_refine
+    ctx._chk(call(ctx._h, L.ptr(par), m, max_rounds, 0, None, None, fits, L.ptr(status), C.byref(rounds),
+                  C.byref(conv)))
+    if nfev is not None:
+        nfev[:] = [int(f.lm_nfev) for f in fits]
     return int(rounds.value)
+
+
+def sphere_models(rows, m):
+    """m rows: every sphere m / 4 times, the radii up to +-0.4 apart (inside the noise band), the centres moved off"""
+    k = m // 4
+    out = []
+    for r in rows:
+        for j in range(k):
+            s = 0.0 if k == 1 else -0.4 + 0.8 * j / (k - 1)
+            out.append(np.concatenate([r[:3] + 0.05, [r[3] + s]]))
+    return np.array(out)
+
+
+def host_lm_round(ctx, rows):
+    """Context.assign, then per model set_mask(labels == m) + ls_fit(use_mask=True) -> the refitted rows"""
+    labels = ctx.assign(rows)["labels"]
+    new = rows.copy()
+    for m in range(len(rows)):
+        mask = (labels == m).astype(np.uint8)
+        if int(mask.sum()) < ctx.K:
+            continue
+        ctx.set_mask(mask)
+        fit, _ = ctx.ls_fit(use_mask=True)
+        if len(fit):
+            new[m] = fit
+    return new
+
+
+def lm_main(a):
+    r1, r2 = a.rounds
+    ms = lambda v: [round(1e3 * float(f(v)), 4) for f in (np.median, np.min, np.max)]
+    data, spheres = synth_scene(a.n, "sphere", 3)
+    lines = []
+    with Context(0) as ctx, Context(0) as alg:
+        ctx.set_model(L.SPHERE, 3, DELTA, L.LS_GEOMETRIC).upload(data)
+        alg.set_model(L.SPHERE, 3, DELTA, L.LS_ALGEBRAIC).upload(data)
+        for m in a.models:
+            rows = sphere_models(spheres, m)
+            t_lo, t_hi, t_alo, t_ahi, t_host, done, nfev = [], [], [], [], [], None, []
+            for rep in range(-1, a.reps):  # rep -1 warms every kind
+                t0 = time.perf_counter()
+                lo = refine_rounds(ctx, rows, r1, lm=True)
+                t1 = time.perf_counter()
+                hi = refine_rounds(ctx, rows, r2, lm=True, nfev=nfev)
+                t2 = time.perf_counter()
+                if rep < a.baseline_reps:
+                    host_lm_round(ctx, rows)
+                t3 = time.perf_counter()
+                alo = refine_rounds(alg, rows, r1)
+                t4 = time.perf_counter()
+                ahi = refine_rounds(alg, rows, r2)
+                t5 = time.perf_counter()
+                if hi <= lo or ahi <= alo:
+                    raise SystemExit("converged after %d / %d rounds: nothing to time" % (hi, ahi))
+                if done is not None and done != (lo, hi, alo, ahi):
+                    raise SystemExit("the rounds done differ between repetitions")
+                done = (lo, hi, alo, ahi)
+                if rep >= 0:
+                    t_lo.append(t1 - t0)
+                    t_hi.append(t2 - t1)
+                    if rep < a.baseline_reps:
+                        t_host.append(t3 - t2)
+                    t_alo.append(t4 - t3)
+                    t_ahi.append(t5 - t4)
+            per = [(h - l) / (done[1] - done[0]) for h, l in zip(t_hi, t_lo)]
+            aper = [(h - l) / (done[3] - done[2]) for h, l in zip(t_ahi, t_alo)]
+            rnd = float(np.median(per))
+            row = dict(model="sphere", ls="geometric", dim=3, n=a.n, models=m, reps=a.reps, rounds_done=list(done[:2]),
+                       alg_rounds_done=list(done[2:]), lm_nfev=[min(nfev), max(nfev)], refine_lm_round_ms=ms(per),
+                       refine_lm_call_ms=ms(t_hi), host_round_ms=ms(t_host), host_reps=len(t_host),
+                       alg_refine_round_ms=ms(aper), ratio_host=round(float(np.median(t_host)) / rnd, 1),
+                       ratio_alg=round(rnd / float(np.median(aper)), 2),
+                       passes_per_s=round((1 + max(nfev)) / rnd, 1))
+            lines.append(json.dumps(row))
+            print(lines[-1], flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
 
 
 class DeviceArray:
@@ -271,7 +361,11 @@ def main():
     ap.add_argument("--loop-groups", type=int, default=200, help="--grouped: groups the per-group loop is timed on")
     ap.add_argument("--model", choices=sorted(SYNTH), default="plane")
     ap.add_argument("--dim", type=int, default=3)
+    ap.add_argument("--lm", action="store_true", help="time Context.refine_lm on the sphere scene instead (see above)")
     a = ap.parse_args()
+    if a.lm:
+        a.models = [4, 64] if a.models == [4, 16, 64] else a.models
+        return lm_main(a)
     a.model_id = SYNTH[a.model][0]
     a.synth = (a.model, a.dim) != ("plane", 3)  # the default scene is this tool's own
     if a.synth:
