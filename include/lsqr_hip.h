@@ -790,7 +790,9 @@ LSQR_API void *lsqr_dedup_create(int k);
 LSQR_API void lsqr_dedup_destroy(void *set);
 
 /* ---- tuning knobs (A/B measurements inside one process; defaults are the tuned values) --------- */
-/* "scan_ppl": observations per lane in k_scan (2, 4 or 8; 0 = model default);
+/* The complete list -- every name with its default, the values it accepts and one line on what it does -- is the table
+ * in lsqrrecipes_amd/csrc/options.h; the options a caller is most likely to want are described at length here.
+ * "scan_ppl": observations per lane in k_scan (2, 4 or 8; 0 = model default);
  * "scan_filter": 1 = cheap pre-filter with a proven error band + exact fp64 re-evaluation of the
  *                ambiguous observations (bit-identical votes): packed fp32 for plane / sphere / line
  *                and the US estimators, fp64 MFMA for the dense system; 0 = plain fp64 scan; 2 / 3 =

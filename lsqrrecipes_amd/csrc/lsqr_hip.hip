@@ -23,6 +23,7 @@
 
 #include "../../include/lsqr_hip.h"
 #include "devbuf.h"
+#include "options.h"
 #include "kernels.h"
 #include "models_nd.h"
 #include "dense.h"
@@ -127,68 +128,134 @@ enum {
   CNT_FLAG = 7
 };
 
+// ---- host-side halves of the pinned slots and of the selection records ---------------------------------------------
+struct BatchSlotState {  // of PinLayout::batch[i]: lsqr_batch_fit_enqueue -> lsqr_batch_fit_wait
+  bool busy = false;
+  uint64_t first = 0, H = 0, seed = 0;  // the batch: for its info, and to run it again without the filter
+  uint32_t ovf_cap = 0;   // segment size the deferred worklist check compares BatchSlot::ovf_fill against (0: no worklist)
+  int bsel_rec = -1;      // the selection record of the slot's scan (-1: none) ...
+  uint64_t bsel_seq = 0;  // ... which is still that scan's while the record's sequence number is this one
+  Event ev;
+};
+struct StepSlotState {  // of PinLayout::step[i]: lsqr_step_finish_enqueue -> lsqr_step_finish_wait
+  bool busy = false;
+  int bsel_rec = -1;  // the record of the step's scan (lsqr_step_scan), as in BatchSlotState
+  uint64_t bsel_seq = 0;
+  Event ev;
+};
+struct BselRecord {  // of one of the two BoundSel of lsqr_ctx::h_bsel
+  Event ev;              // the copy into the record
+  bool pending = false;  // written by a scan the host has not folded yet
+  uint64_t seq = 0;      // that scan's sequence number (lsqr_ctx::bsel_seq) ...
+  uint32_t H = 0;        // ... and batch size
+};
+
 // ------------------------------------------------------------------------------------------------
 struct lsqr_ctx {
+  // ---- device, stream, options, model ----
   int device = 0;
   hipStream_t stream = nullptr;      // the stream all work is enqueued on
   hipStream_t own_stream = nullptr;  // created with the context (stream == own_stream unless lsqr_set_stream)
+  bool external_stream = false;
+  Options opt;  // lsqr_set_option (options.h: every knob, its default and its rule)
   lsqr_model_cfg cfg{};
   ModelConsts mc{};
   bool has_model = false;
   int K = 0, P = 0, ND = 0, HS = 0;  // HS: row stride (doubles) of d_hparams
 
+  // ---- records ----
   const double *d_data = nullptr;  // observations (owned or attached)
   DevBuf<double> d_data_owned;
   size_t n = 0, stride = 0;  // stride in doubles
+  uint64_t data_epoch = 1;   // bumped whenever the records or the model change
+  bool absmax_valid = false;
+  // k_bounds of the current upload (min / max per dimension, max |coordinate|, non-finite count): serves both
+  // the fp32 filters' absmax and the Morton grid of the index
+  BoundsRow h_bounds{};
+  bool bounds_valid = false;
+  uint64_t hyp_since_upload = 0;  // hypotheses scanned on this upload (index build heuristic)
+  uint64_t hyp_expected = 0;      // hypotheses the caller still expects to scan on this upload (lsqr_ransac: numTries)
+  DevBuf<double> d_rows;  // plane phantom: the data rows a_i as an n x 32 matrix (phantom.h)
+  bool rows_valid = false;
+  // staged upload (lsqr_upload of large pageable buffers): ring of pinned chunks filled by a few host threads
+  // while earlier chunks are in flight to the device
+  static constexpr int kUpSlots = 8;
+  static constexpr size_t kUpChunk = (size_t)8 << 20;
+  PinBuf<char> h_up[kUpSlots];
+  Event up_ev[kUpSlots];
+  double last_upload_ms = 0.0;
 
+  // ---- hypotheses ----
   size_t H = 0, H_cap = 0;
   DevBuf<uint32_t> d_subsets;
   DevBuf<double> d_hparams;
   DevBuf<float> d_hparams_f32;
-  DevBuf<unsigned long long> d_amb;  // worklist of the dense MFMA filter
-  bool absmax_valid = false;
-  // spatial index of the point models (cells.h): Morton-sorted copy + one fp32 box per 128 records
+  DevBuf<uint8_t> d_valid;
+  DevBuf<uint32_t> d_votes;
+  DevBuf<uint8_t> d_refused;  // k_estimate_phantom_lu: hypotheses left to the Jacobi kernel
+  bool scanned = false;
+
+  // ---- spatial index of the point models (cells.h): Morton-sorted copy + one fp32 box per 128 records ----
   DevBuf<double> d_sorted;
   DevBuf<uint32_t> d_queues;  // work-queue counters of k_scan_cells
   DevBuf<CellBox> d_boxes;   // [n_cells cell boxes | merged boxes of the bounds pass (k_super_boxes)]
   uint32_t super_merge = 0;     // cells per merged box the second part currently holds (0: not built)
+  size_t n_sorted = 0;      // finite records (non-finite ones never agree and are left out)
+  uint32_t n_cells = 0, cell_pts = 0;
+  bool index_valid = false;
+  bool index_failed = false;  // build failed on this upload: stay on the exhaustive kernels
+  DevBuf<char> d_idx_scratch;  // keys / permutation / radix-sort temporaries of the index build (kept)
+  int kd_build_levels = 0, index_kd_levels = 0;  // k-d levels of the build in progress / of the index in place
+  // axis-sorted cells (axis.h; plane, 3-D): per-cell axis, the cells' sorted projections
+  DevBuf<CellAxis> d_axis;
+  DevBuf<float> d_cellT;
+  bool axis_valid = false;
+  DevBuf<CellSlab> d_slab;        // per-cell oriented slab (axis.h: k_cell_slabs), built with d_axis
+
+  // ---- two-level scan and its counted forms ----
+  DevBuf<uint32_t> d_ub;  // per-hypothesis vote bound of the two-level scan's first level (k_cells_bounds)
+  // the table of the last counting launch of run_scan_pairs (lsqr_scan_pairs_counted)
+  struct {
+    bool valid = false, packed = false, slab = false;
+    uint32_t H = 0, h_off = 0, gstride = 0;
+    const uint32_t *h_dev = nullptr;
+  } last_count;
+  DevBuf<uint8_t> d_paircnt;   // k_scan_pairs: survivors per (cell, group of 64 hypotheses)
+  DevBuf<uint32_t> d_paircost; // [n_cells cell costs | chunk sums]
+  DevBuf<uint32_t> d_vpart;    // per-workgroup partial votes of k_scan_pairs
+  DevBuf<float4> d_hyps;       // k_prepare_hyps: CM::Hyp of every hypothesis of the batch k_scan_pairs is counting
+  DevBuf<unsigned long long> d_pairmask;  // PairsForm::Packed: level 1's survivor mask per (cell, group of 64 hypotheses)
+  DevBuf<unsigned long long> d_ambcnt;  // k_scan_pairs: kAmbSlots x {ambiguous pairs, band observations} of the last scan
+  bool amb_reset = false;         // the next k_tile_costs zeroes d_ambcnt: the scan's first k_scan_pairs
+  bool amb_counted = false;       // the last scan went through k_scan_pairs: d_ambcnt holds its counts
+
+  // ---- bounded scan (cells.h: k_pick_*): the selected hypotheses as a compact batch ----
+  DevBuf<uint32_t> d_sel;        // [kPilots pilots | H_cap rest]
+  DevBuf<BoundSel> d_bsel;
+  DevBuf<double> d_hparams2;
+  DevBuf<float> d_hparams2_f32;
+  DevBuf<uint32_t> d_votes2;     // [kPilots | H_cap]
+  DevBuf<uint32_t> d_ub2;  // rank bounds: [upper | lower] of the candidates (compact order) | lower per hypothesis
+  uint32_t best_before = 0;         // exact votes of the best hypothesis of earlier batches (lsqr_ransac)
+  bool allow_bound = false;         // set by the batch entry points around run_scan (lsqr_scan always counts all)
+  uint64_t last_bound[4] = {0, 0, 0, 0};  // diagnostics of the last bounded scan: {used, pilots, rest, H}
+  bool merge_off = false;       // this upload: merged boxes let too many hypotheses through, bounds stay on the cells
   // Selection counts of the bounded scans come back through pinned memory and steer the NEXT batches' launch sequence
   // (merged boxes or cells; pilot pass or not).  Two records, written alternately; a record is folded into
   // `bsel_known` only at a point where the host HAS synchronised with the batch that wrote it -- a ..._wait of its
   // slot, the end of a blocking entry point, or right before the record is reused (two bounded scans later) -- so the
   // launch sequence of a batch follows from the call sequence, never from host / device timing.
   PinBuf<BoundSel> h_bsel;   // pinned [2], 64 B apart
-  Event bsel_ev[2];
-  bool bsel_pending[2] = {false, false};
-  uint64_t bsel_seq_of[2] = {0, 0};
-  uint32_t bsel_H_of[2] = {0, 0};
+  BselRecord bsel[2];
   uint64_t bsel_seq = 0;        // bounded scans issued on this context
   int bsel_last_rec = -1;       // record the last bounded scan writes
   BoundSel bsel_known{};        // counts of the latest bounded scan the host has synchronised with ...
   uint32_t bsel_known_H = 0;    // ... its batch size (0: nothing known on this upload / model) ...
   uint64_t bsel_known_seq = 0;  // ... and its sequence number
-  int slot_bsel_rec[2] = {-1, -1};   // lsqr_batch_fit_enqueue: the record of the slot's scan
-  uint64_t slot_bsel_seq[2] = {0, 0};
-  int step_bsel_rec[2] = {-1, -1};   // lsqr_step_finish_enqueue: the record of the step's scan (lsqr_step_scan)
-  uint64_t step_bsel_seq[2] = {0, 0};
-  bool merge_off = false;       // this upload: merged boxes let too many hypotheses through, bounds stay on the cells
-  int opt_bound_merge = 0;      // 0: the cell model's default, 1: bounds on the cells themselves, 2 / 4 / 8
-  size_t n_sorted = 0;      // finite records (non-finite ones never agree and are left out)
-  uint32_t n_cells = 0, cell_pts = 0;
-  bool index_valid = false;
-  bool index_failed = false;  // build failed on this upload: stay on the exhaustive kernels
-  // k_bounds of the current upload (min / max per dimension, max |coordinate|, non-finite count): serves both
-  // the fp32 filters' absmax and the Morton grid of the index
-  BoundsRow h_bounds{};
-  bool bounds_valid = false;
-  DevBuf<char> d_idx_scratch;  // keys / permutation / radix-sort temporaries of the index build (kept)
-  uint64_t hyp_since_upload = 0;  // hypotheses scanned on this upload (index build heuristic)
-  uint64_t hyp_expected = 0;      // hypotheses the caller still expects to scan on this upload (lsqr_ransac: numTries)
+
+  // ---- matrix-core filters of the dense / US / phantom scans ----
+  DevBuf<unsigned long long> d_amb;  // worklist of the dense MFMA filter
   unsigned dense_amb_max = 0;  // fullest worklist segment of the last fp32 dense scan (diagnostics)
-  int opt_dense_f32 = 2;  // dense scan filter at n = 64: 2 = fp16 matrix cores on two-way splits of the rows and the
-                          // unknowns (dense_h16.h; the rows' fragments are built once per upload), 1 = fp32 matrix
-                          // cores (hypothesis fragments through an LDS ring + next tile in registers), 0 = fp64 matrix
-                          // cores; every filter sends its band to the exact fp64 re-check
   // dense_h16.h: the rows as fp16 fragment pairs (8 KiB per 32 rows) + the scaled right-hand sides, once per upload
   DevBuf<uint4> d_h16;
   DevBuf<float> d_h16_bs;
@@ -201,73 +268,21 @@ struct lsqr_ctx {
   DevBuf<uint4> d_us16, d_us16_x;
   bool us16_valid = false, us16_attr = false, us16_nomem = false;
   Us16Scales us16_sc{};
-  int opt_us_h16 = 1;  // US calibrations: 1 = agree() scan on the fp16 matrix cores (us_h16.h), 0 = packed fp32 filter
-  int opt_dense_fast = 1;  // minimal solves: elimination first, SVD when near the rank decision
-  int opt_us_fast = 1;     // US calibrations' minimal solves likewise (k_estimate_us)
-  DevBuf<uint8_t> d_refused;  // k_estimate_phantom_lu: hypotheses left to the Jacobi kernel
-  int opt_phantom_fast = 1;  // plane phantom's minimal solves: LU + inverse iteration first (> 1: its iteration limit), Jacobi SVD for what it refuses; 0: Jacobi only
-  int opt_lm_tiles = 1;      // matrix-core LM pass: compacted consensus set in field-major tiles, next tile in flight
-  int opt_us_mask_mfma = 1;  // US calibrations: mask + analytic moment block on the fp64 matrix cores (kernels.h)
-  int opt_refine = 1;      // index build: k-d refinement of the Morton order inside runs of 8192 records (cells.h)
-  int opt_kd_levels = 7;   // ... and this many k-d levels above the runs by segmented sorts (runs of 8192 << levels),
-  int opt_kd_after = 16384;  // built once the upload has been asked to scan this many hypotheses (the first index of an
-                             // upload keeps the Morton order above the runs: 1.3 instead of 5.8 ms per 10 M records)
-  int kd_build_levels = 0, index_kd_levels = 0;  // levels of the build in progress / of the index in place
-  int opt_presorted = 0;   // index build: cells = runs of the UPLOAD order (experiments with other spatial orders)
-  int opt_dense_wave = 3;  // dense minimal solves: 3 = elimination by one wave per system IN REGISTERS (n = 64; else as 1),
-                           // 1 / 2 = in the wave's LDS area, four / two systems per workgroup, 0 = one workgroup per system
-  int opt_dense_dd = 1;    // dense fit: systems the elimination refuses are solved again from the rows in double-double
-  DevBuf<double> d_ddpart;  // partial double-double Gram blocks of k_gram_dd_dense (allocated on first use)
-  int opt_index = 1, opt_cpt = 0, opt_cell = 0, opt_block = 0, opt_hsplit = 0, opt_pairs = 0, opt_pairs_waves = 0;  // 0 off, 1 auto, 2 always; cells per wave tile, cell size
-  DevBuf<uint8_t> d_valid;
-  DevBuf<uint32_t> d_votes;
-  DevBuf<uint32_t> d_ub;  // per-hypothesis vote bound of the two-level scan's first level (k_cells_bounds)
-  // axis-sorted cells (axis.h; plane, 3-D): per-cell axis, the cells' sorted projections
-  DevBuf<CellAxis> d_axis;
-  DevBuf<float> d_cellT;
-  bool axis_valid = false;
-  DevBuf<CellSlab> d_slab;        // per-cell oriented slab (axis.h: k_cell_slabs), built with d_axis
-  int opt_slab = 1;               // 1: the mask-storing counting pass of the 3-D plane tests the cell's slab too (PlaneCell::slab)
-  int opt_slab_gate = 3;          // kappa of k_cell_slabs' gate in quarters (A/B; drops the index)
-  // the table of the last counting launch of run_scan_pairs (lsqr_scan_pairs_counted)
-  struct {
-    bool valid = false, packed = false, slab = false;
-    uint32_t H = 0, h_off = 0, gstride = 0;
-    const uint32_t *h_dev = nullptr;
-  } last_count;
-  int opt_mom_chunk = 0;          // chunk of the mask / moment passes in units of kBlock records (0 = default; A/B)
-  int opt_hyp_order = 1;          // 1: a full count of the plane walks the batch in key order (k_plane_order)
-  int opt_axis = 1;               // 1: the bounded scan of the plane takes its vote bounds by rank (k_bound_axis)
-  DevBuf<uint32_t> d_ub2;  // rank bounds: [upper | lower] of the candidates (compact order) | lower per hypothesis
-  DevBuf<uint8_t> d_paircnt;   // k_scan_pairs: survivors per (cell, group of 64 hypotheses)
-  DevBuf<uint32_t> d_paircost; // [n_cells cell costs | chunk sums]
-  DevBuf<uint32_t> d_vpart;    // per-workgroup partial votes of k_scan_pairs
-  DevBuf<float4> d_hyps;       // k_prepare_hyps: CM::Hyp of every hypothesis of the batch k_scan_pairs is counting
-  int opt_lean = 1;               // 1: count-only counting pass, PairsForm::Lean for prepared models; 0: the general forms (A/B)
-  DevBuf<unsigned long long> d_pairmask;  // PairsForm::Packed: level 1's survivor mask per (cell, group of 64 hypotheses)
-  int opt_pack = 1;               // 1: level 1 of the lean k_scan_pairs on packed blocks of 64 survivors; 0: per group (A/B)
-  int opt_recheck = 1;            // 1: the packed k_scan_pairs re-checks the band's observations alone; 0: the whole cell (A/B)
-  DevBuf<unsigned long long> d_ambcnt;  // k_scan_pairs: kAmbSlots x {ambiguous pairs, band observations} of the last scan
-  bool amb_reset = false;         // the next k_tile_costs zeroes d_ambcnt: the scan's first k_scan_pairs
-  bool amb_counted = false;       // the last scan went through k_scan_pairs: d_ambcnt holds its counts
-  int opt_prepared = 1;           // 1: cell models with PREPARED read Hyp from d_hyps; 0: load() per (cell, group) (A/B)
-  // bounded scan (cells.h: k_pick_*): the selected hypotheses as a compact batch
-  DevBuf<uint32_t> d_sel;        // [kPilots pilots | H_cap rest]
-  DevBuf<BoundSel> d_bsel;
-  DevBuf<double> d_hparams2;
-  DevBuf<float> d_hparams2_f32;
-  DevBuf<uint32_t> d_votes2;     // [kPilots | H_cap]
-  int opt_bound = 1;                // 1: batch entry points skip hypotheses that cannot win (exact winner), 0: count all
-  uint32_t best_before = 0;         // exact votes of the best hypothesis of earlier batches (lsqr_ransac)
-  bool allow_bound = false;         // set by the batch entry points around run_scan (lsqr_scan always counts all)
-  uint64_t last_bound[4] = {0, 0, 0, 0};  // diagnostics of the last bounded scan: {used, pilots, rest, H}
   // chunked early exit of the dense / US scans (earlyexit.h)
   DevBuf<char> d_ee;             // [EeState | sel_c | sel_o x 2 | compact thresholds | compact fp32 rows]
   PinBuf<EeState> h_ee;          // pinned copy of the last early-exit scan's state (diagnostics: read after a synchronisation, lsqr_scan_work)
   bool ee_last = false;             // the last scan of this context took the early-exit path
   uint64_t ee_H = 0, ee_n = 0;      // its batch size and observation count
-  bool scanned = false;
-  bool external_stream = false;
+  // The filters decide their band from per-workgroup worklists; a segment that overflowed (never seen) means "scan
+  // again without the filter".  The blocking entry points read the fill right after the scan (one host
+  // synchronisation); lsqr_batch_fit_enqueue must not wait, so there the scan only notes the segment size (ovf_cap),
+  // the fill travels with the slot's pinned record and lsqr_batch_fit_wait runs the batch again without the filter if
+  // it ever exceeds it.
+  bool defer_ovf = false;        // set around run_scan_batch by lsqr_batch_fit_enqueue
+  uint32_t ovf_cap = 0;          // segment size the deferred check compares against (0: this scan has no worklist)
+  uint64_t ovf_reruns = 0;       // batches run again because a worklist segment overflowed (diagnostics)
+
+  // ---- lanes and slots ----
   // lsqr_batch_fit_enqueue / _wait run on LANES: independent contexts on the same device, each with its own stream
   // and buffers, attached to this context's records.  Batches of different lanes overlap on the device: the dozen
   // one-workgroup kernels of a batch (selection, winner, solve) and the tails of the big ones no longer leave the
@@ -275,54 +290,28 @@ struct lsqr_ctx {
   // Lane 0 is this context itself.
   static constexpr int kMaxLanes = 4;
   lsqr_ctx *lanes[kMaxLanes] = {nullptr, nullptr, nullptr, nullptr};
-  int opt_lanes = 4;
   bool is_lane = false;
-  uint64_t data_epoch = 1;   // bumped whenever the records or the model change
   uint64_t lane_epoch = 0;   // (lanes) the epoch of the parent this lane is attached to
-  std::vector<std::pair<std::string, int>> opt_log;  // options set on this context, replayed on new lanes
-  Event slot_ev[2];  // lsqr_batch_fit_enqueue / _wait
-  // The matrix-core filters of the dense / US / phantom scans decide their band from per-workgroup worklists; a segment
-  // that overflowed (never seen) means "scan again without the filter".  The blocking entry points read the fill right
-  // after the scan (one host synchronisation); lsqr_batch_fit_enqueue must not wait, so there the scan only notes the
-  // segment size (ovf_cap), the fill travels with the slot's pinned record and lsqr_batch_fit_wait runs the batch
-  // again without the filter if it ever exceeds it.
-  bool defer_ovf = false;        // set around run_scan_batch by lsqr_batch_fit_enqueue
-  uint32_t ovf_cap = 0;          // segment size the deferred check compares against (0: this scan has no worklist)
-  uint32_t slot_ovf_cap[2] = {0, 0};
-  uint64_t slot_seed[2] = {0, 0};
-  int opt_test_overflow = 0;     // tests: worklist_check and lsqr_batch_fit_wait treat the worklist as overflowed
-  uint64_t ovf_reruns = 0;       // batches run again because a worklist segment overflowed (diagnostics)
-  uint64_t slot_first[2] = {0, 0}, slot_H[2] = {0, 0};
-  bool slot_busy[2] = {false, false};
+  BatchSlotState slots[2];   // lsqr_batch_fit_enqueue / _wait
+  StepSlotState steps[2];    // lsqr_step_finish_enqueue / _wait
   Event mdev_ev[4];  // lsqr_moments_dev: staging slots of x
   unsigned mdev_next = 0;
-  Event step_ev[2];  // lsqr_step_finish_enqueue / _wait
-  bool step_busy[2] = {false, false};
 
-  DevBuf<double> d_rows;  // plane phantom: the data rows a_i as an n x 32 matrix (phantom.h)
-  bool rows_valid = false;
-
+  // ---- fit: mask, moments, solve ----
   DevBuf<uint8_t> d_mask;
   bool mask_valid = false;
-
   DevBuf<double> d_partials;  // kMaxPartials * MOM_MAX
   DevBuf<double> d_mom;       // MOM_MAX
   DevBuf<double> d_vec;       // 32 doubles: origin / parameter vector handed to kernels
   DevBuf<double> d_par;       // 32 doubles: model parameters for mask/stats
   DevBuf<double> d_best;      // scan-parameter row of the best hypothesis so far (lsqr_ransac*)
-  DevBuf<LmState> d_lm;
   DevBuf<SolveOut> d_out;
-  DevBuf<unsigned long long> d_counter;
+  DevBuf<unsigned long long> d_counter;  // CNT_* words
   bool origin_valid = false;  // d_par holds the parameters the device mask was made from (set_fit_origin)
   uint64_t win_rec = 0;       // first drawn record of the winning minimal subset (lsqr_ransac*, set_fit_origin)
-  int opt_ppl = 0, opt_filter = 1, opt_lm_host = 1, opt_syrk_diag = 0;
-  int opt_fuse_mask = 1;  // winner's mask + moment block in one pass (0: two kernels, for A/B runs)
-  int opt_mask_ring = 4;  // k_mask_syrk_dense: tile buffers per wave (2: two workgroups per CU; 4: one, three tiles in flight)
-  int opt_mask_diag = 0;  // timing diagnostics of k_mask_syrk_dense: 1 = no matrix instructions, 2 = no row evaluation
-  int opt_mask_band = 0;  // tests: scale factor of the dense fused mask's band (forces its serial re-evaluation path)
-  long long opt_max_iter = 0;  // 0 = the reference's bound (numTries <= C(N,k))
-  long long opt_many_round = 0;  // lsqr_ransac_many: hypotheses per round (0 = kManyRoundDefault)
-  bool opt_many_ex_fused = true;  // lsqr_ransac_many_exhaustive: small problems take k_many_ex_small
+  DevBuf<double> d_ddpart;  // partial double-double Gram blocks of k_gram_dd_dense (allocated on first use)
+  PinBuf<PinLayout> h_pin;  // pinned staging
+  PinBuf<char> h_batch;  // pinned results of a lsqr_ransac batch (grown on demand)
   std::unique_ptr<ManyBufs> many;  // lsqr_ransac_many's buffers (its own: the context's upload is not touched)
   std::unique_ptr<AssignBufs> assign;  // lsqr_assign / lsqr_refine / lsqr_refine_lm (assign.h, assign_lm.h)
   std::unique_ptr<AssignGrpBufs> assign_grp;  // lsqr_assign_grouped / lsqr_refine_grouped (assign_grouped.h)
@@ -332,23 +321,14 @@ struct lsqr_ctx {
   DevBuf<uint32_t> d_seq_orig[2];
   DevBuf<int32_t> d_seq_labels;
   DevBuf<uint32_t> d_seq_counts;
-  LmState h_lm;  // host copy of the LM state (opt_lm_host)
+
+  // ---- iterative (LM) fits ----
+  DevBuf<LmState> d_lm;
+  LmState h_lm;  // host copy of the LM state (opt.lm_host)
   DevBuf<double> d_lmrec;  // consensus set copied tight and in order for the iterative fits (k_compact_*)
   PinBufCoherent<unsigned long long> h_lmres;  // pinned, device-visible: tagged granules written by k_lm_publish
   uint32_t lm_seq = 0;        // sequence number of the last evaluation (the tag the host polls for)
-  int opt_lm_mfma = 1;        // 1: the LM pass accumulates (J | f)^T (J | f) on the matrix cores; 0: per-lane sums
-  int opt_lm_fused = 1;       // 1: one launch per LM evaluation, result polled in pinned memory; 0: r01 path
-  // lm_persist.h: a whole matrix-core LM fit in one launch.  0: the launch path (two launches per evaluation);
-  // 1: persistent kernel with MINPACK's step on the host between tagged granules in pinned memory WHEN this context is
-  // the only one of the process fitting on the device, the launch path otherwise; 3: the same kernel always; 2: persistent
-  // kernel with the step on the device (workgroup 0).  Same iterates every way.
-  int opt_lm_persist = 1;
-  int opt_lm_persist_wgs = 0;          // resident workgroups G (0: 256 / 128 / 64 by the number of contexts on the device)
-  int opt_lm_persist_timeout_ms = 2000;  // bound of every wait inside the kernel
-  int opt_lm_persist_resident = 0;       // 1: a fit alone on the device keeps its tiles in registers (k_lm_persist<M, 4>).  Built,
-                                         // bit-identical, measured no faster (r05: 12.4 us against 11.1 us per pass + broadcast at 245
-                                         // workgroups -- with 1.9 waves per SIMD the pass is bound by its dependent chains, not by HBM)
-  int opt_lm_persist_test_abort = 0;     // tests: workgroup 0 gives up at this evaluation (the fallback path)
+  // lm_persist.h: a whole matrix-core LM fit in one launch (opt.lm_persist)
   DevBuf<LmpCtl> d_lmp;
   PinBufCoherent<unsigned long long> h_lmcmd;  // pinned, device-visible: the host's reply (coefficient granules + command)
   bool counted = false;  // this context counts among the device's root contexts (lmp_pool: the share of a persistent fit)
@@ -357,17 +337,7 @@ struct lsqr_ctx {
   uint64_t lmp_trace[LMP_TRACE][4];
   uint32_t lmp_trace_n = 0;
 
-  // staged upload (lsqr_upload of large pageable buffers): ring of pinned chunks filled by a few host threads
-  // while earlier chunks are in flight to the device
-  static constexpr int kUpSlots = 8;
-  static constexpr size_t kUpChunk = (size_t)8 << 20;
-  PinBuf<char> h_up[kUpSlots];
-  Event up_ev[kUpSlots];
-  int opt_upload_threads = -1;  // -1: LSQR_UPLOAD_THREADS or 0; 0: one plain hipMemcpy
-  double last_upload_ms = 0.0;
-  PinBuf<PinLayout> h_pin;  // pinned staging
-  PinBuf<char> h_batch;  // pinned results of a lsqr_ransac batch (grown on demand)
-
+  // ---- profiling ----
   bool prof = false;
   Event ev0, ev1;
   // HIP-event pairs of profiled launches; resolved lazily (lsqr_profile_get) so that profiling
@@ -497,7 +467,7 @@ int need_ready(lsqr_ctx *c, bool need_data) {
 
 // smallest chunk per block of the mask / moment passes (kernels.h: kMomChunk)
 static inline int mom_chunk(const lsqr_ctx *c) {
-  if (c->opt_mom_chunk > 0) return c->opt_mom_chunk * kBlock;
+  if (c->opt.mom_chunk > 0) return c->opt.mom_chunk * kBlock;
   const int m = c->cfg.model;
   return (m == LSQR_MODEL_US_SINGLE || m == LSQR_MODEL_US_POINTER || m == LSQR_MODEL_PHANTOM) ? kMomChunkWide : kMomChunk;
 }
@@ -510,31 +480,31 @@ int run_bounds(lsqr_ctx *c);
 static BoundSel *bsel_rec(lsqr_ctx *c, int r) { return (BoundSel *)((char *)c->h_bsel.get() + 64 * r); }
 // the host has synchronised with the batch that wrote record r
 static void bsel_fold(lsqr_ctx *c, int r) {
-  if (r < 0 || !c->h_bsel || !c->bsel_pending[r]) return;
-  c->bsel_pending[r] = false;
-  if (c->bsel_known_H && c->bsel_seq_of[r] < c->bsel_known_seq) return;  // an older batch than the one known
+  if (r < 0 || !c->h_bsel || !c->bsel[r].pending) return;
+  BselRecord &b = c->bsel[r];
+  b.pending = false;
+  if (c->bsel_known_H && b.seq < c->bsel_known_seq) return;  // an older batch than the one known
   c->bsel_known = *bsel_rec(c, r);
-  c->bsel_known_H = c->bsel_H_of[r];
-  c->bsel_known_seq = c->bsel_seq_of[r];
+  c->bsel_known_H = b.H;
+  c->bsel_known_seq = b.seq;
 }
 // the host has synchronised with everything enqueued on the context's stream
 static void bsel_host_synced(lsqr_ctx *c) {
   if (!c->h_bsel) return;
-  const int first = c->bsel_seq_of[0] <= c->bsel_seq_of[1] ? 0 : 1;
+  const int first = c->bsel[0].seq <= c->bsel[1].seq ? 0 : 1;
   bsel_fold(c, first);
   bsel_fold(c, first ^ 1);
 }
 // new records / new model: nothing is known; copies still in flight are waited for, not abandoned
 static void bsel_reset(lsqr_ctx *c) {
-  for (int r = 0; r < 2; r++)
-    if (c->bsel_pending[r] && c->bsel_ev[r]) {
-      (void)hipEventSynchronize(c->bsel_ev[r]);
-      c->bsel_pending[r] = false;
+  for (BselRecord &b : c->bsel)
+    if (b.pending && b.ev) {
+      (void)hipEventSynchronize(b.ev);
+      b.pending = false;
     }
   c->bsel_known = BoundSel{};
   c->bsel_known_H = 0;
-  c->slot_bsel_rec[0] = c->slot_bsel_rec[1] = -1;
-  c->step_bsel_rec[0] = c->step_bsel_rec[1] = -1;
+  for (int s = 0; s < 2; s++) c->slots[s].bsel_rec = c->steps[s].bsel_rec = -1;
   c->bsel_last_rec = -1;
 }
 
@@ -594,7 +564,7 @@ int run_estimate(lsqr_ctx *c) {
     if constexpr (requires { M::IS_PHANTOM; }) {
       // one wave per hypothesis (measured 1.76 ms per 4096 against 1.96 / 2.53 ms with 128 / 256 threads:
       // the sweeps are bound by instruction issue, and a single-wave workgroup lands on any SIMD)
-      if (c->opt_phantom_fast) {
+      if (c->opt.phantom_fast) {
         // r05: LU + inverse iteration (phantom.h: k_estimate_phantom_lu), the Jacobi SVD for what it refuses
         int st = ensure(c, c->d_refused, std::max<size_t>(c->H, 1));
         if (st != LSQR_OK) return st;
@@ -604,7 +574,7 @@ int run_estimate(lsqr_ctx *c) {
         if (dbg_on) (void)d_dbg.alloc(4 * c->H);
         hipLaunchKernelGGL(k_estimate_phantom_lu, dim3((unsigned)((c->H + 3) / 4)), dim3(256), 0, c->stream, c->d_data,
                            c->stride, c->n, c->d_subsets, (uint32_t)c->H, c->d_hparams, c->d_valid, d_ref,
-                           c->opt_phantom_fast > 1 ? c->opt_phantom_fast : 96, d_dbg);
+                           c->opt.phantom_fast > 1 ? c->opt.phantom_fast : 96, d_dbg);
         if (d_dbg) {  // diagnostics (LSQR_PHANTOM_DEBUG): iterations and 10-ns ticks per phase and hypothesis
           std::vector<unsigned long long> hd(4 * c->H);
           (void)hipStreamSynchronize(c->stream);
@@ -624,7 +594,7 @@ int run_estimate(lsqr_ctx *c) {
         hipLaunchKernelGGL(k_estimate_phantom<64>, dim3((unsigned)std::min<size_t>(c->H, 512)), dim3(64), 0, c->stream,
                            c->d_data, c->stride, c->n, c->d_subsets, (uint32_t)c->H, c->d_hparams, c->d_valid,
                            (const uint8_t *)d_ref);
-      } else if (c->opt_block == 256)
+      } else if (c->opt.block == 256)
         hipLaunchKernelGGL(k_estimate_phantom<256>, dim3((unsigned)c->H), dim3(256), 0, c->stream, c->d_data,
                            c->stride, c->n, c->d_subsets, (uint32_t)c->H, c->d_hparams, c->d_valid, (const uint8_t *)nullptr);
       else
@@ -634,16 +604,16 @@ int run_estimate(lsqr_ctx *c) {
                          c->stream, c->d_hparams, (uint32_t)c->H, c->mc, c->d_hparams_f32);
     } else if constexpr (M::IS_DENSE) {
       const int n = (int)c->cfg.dim;
-      if (c->opt_dense_fast && c->opt_dense_wave) {
+      if (c->opt.dense_fast && c->opt.dense_wave) {
         // fast path: four hypotheses per workgroup, one wave each (dense.h: k_estimate_dense_w4); what its elimination
         // refuses is marked and taken through the SVD pseudo-inverse by the workgroup kernel behind it
-        const int wpb = c->opt_dense_wave == 2 ? 2 : 4;   // systems per workgroup (2: 68 KB of LDS at n = 64, A/B)
+        const int wpb = c->opt.dense_wave == 2 ? 2 : 4;   // systems per workgroup (2: 68 KB of LDS at n = 64, A/B)
         const size_t lds = sizeof(double) * wpb * ((size_t)n * (n | 1) + 2 * n);
         // (unconditionally: the attribute belongs to the (kernel, device) pair, and a flag per process or per context
         // misses the second device / the second kernel; the call is cheap)
         (void)hipFuncSetAttribute((const void *)k_estimate_dense_w4, hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)(sizeof(double) * 4 * (64 * 65 + 128)));
-        if (n == 64 && c->opt_dense_wave == 3)  // the system in registers, one wave per hypothesis (k_estimate_dense_r64)
+        if (n == 64 && c->opt.dense_wave == 3)  // the system in registers, one wave per hypothesis (k_estimate_dense_r64)
           hipLaunchKernelGGL(k_estimate_dense_r64, dim3((unsigned)c->H), dim3(64), 0, c->stream, c->d_data, c->stride, c->n,
                              c->d_subsets, (uint32_t)c->H, (int)M::SP, c->d_hparams, c->d_valid);
         else
@@ -653,13 +623,13 @@ int run_estimate(lsqr_ctx *c) {
                            c->stride, c->n, c->d_subsets, (uint32_t)c->H, n, (int)M::SP, 0, c->d_hparams, c->d_valid, 1);
       } else {
         hipLaunchKernelGGL(k_estimate_dense, dim3((unsigned)c->H), dim3(256), dense_lds_bytes(n), c->stream, c->d_data,
-                           c->stride, c->n, c->d_subsets, (uint32_t)c->H, n, (int)M::SP, c->opt_dense_fast,
+                           c->stride, c->n, c->d_subsets, (uint32_t)c->H, n, (int)M::SP, c->opt.dense_fast,
                            c->d_hparams, c->d_valid, 0);
       }
     } else if constexpr (M::IS_US) {
       hipLaunchKernelGGL((k_estimate_us<(M::K == 4)>), dim3((unsigned)c->H), dim3(64), 0,
                          c->stream, c->d_data, c->stride, c->n, c->d_subsets, (uint32_t)c->H,
-                         c->mc, c->d_hparams, c->d_valid, c->opt_us_fast);
+                         c->mc, c->d_hparams, c->d_valid, c->opt.us_fast);
       hipLaunchKernelGGL((k_prepare_f32_us<M>), dim3((unsigned)((c->H + 255) / 256)),
                          dim3(256), 0, c->stream, c->d_hparams, (uint32_t)c->H, c->mc,
                          c->d_hparams_f32);
@@ -689,7 +659,7 @@ int run_scan_ppl(lsqr_ctx *c) {
     size_t tpb = (tiles + max_blocks - 1) / max_blocks;
     int grid = (int)((tiles + tpb - 1) / tpb);
     ProfScope ps(c, KID_SCAN);
-    if (c->opt_filter)
+    if (c->opt.filter)
       hipLaunchKernelGGL((k_scan<M, PPL, true>), dim3(grid), dim3(kBlock), lds, c->stream, c->d_data,
                          c->stride, c->n, c->d_hparams + h0 * M::SP, hc, c->mc, c->d_votes + h0);
     else
@@ -752,7 +722,7 @@ void lanes_quiesce(lsqr_ctx *c) {
   for (int i = 1; i < lsqr_ctx::kMaxLanes; i++)
     if (c->lanes[i]) {
       (void)hipStreamSynchronize(c->lanes[i]->stream);
-      for (int s = 0; s < 2; s++) c->lanes[i]->slot_busy[s] = false;  // results of a replaced upload are void
+      for (BatchSlotState &s : c->lanes[i]->slots) s.busy = false;  // results of a replaced upload are void
     }
 }
 
@@ -860,14 +830,14 @@ int build_index(lsqr_ctx *c, uint32_t cell_pts) {
   uint32_t *perm = v_out;  // the order the cells are cut from
   const unsigned gn = (unsigned)((n + 255) / 256);
   hipLaunchKernelGGL((k_keys<D>), dim3(gn), dim3(256), 0, c->stream, c->d_data, c->stride, n, g, k_in, v_in,
-                     c->opt_presorted);
+                     c->opt.presorted);
   IDXCHK(hipGetLastError());
   IDXCHK(sort_pairs_u32(tmp, &tmp_bytes, k_in, k_out, v_in, v_out, n, (unsigned)(bits * D + 1), c->stream));
   c->n_sorted = n_sorted;
   c->n_cells = n_cells;
   // k-d levels above the runs (cells.h: k_seg_extent / k_seg_keys + one radix sort per level), then the local k-d
   // refinement of every run (k_refine_runs): compact cells, fewer surviving pairs
-  if (c->opt_refine && !c->opt_presorted && n_sorted > cell_pts && cell_pts >= 128 && cell_pts < kRunPts &&
+  if (c->opt.refine && !c->opt.presorted && n_sorted > cell_pts && cell_pts >= 128 && cell_pts < kRunPts &&
       (cell_pts & (cell_pts - 1)) == 0) {
     SegExtent *d_ext = (SegExtent *)((char *)tmp + ((tmp_bytes + 255) & ~(size_t)255));
     uint32_t *q_a = v_in;  // (k_in / v_in are free after the Morton sort) positions into the Morton-ordered copy
@@ -912,7 +882,7 @@ int build_index(lsqr_ctx *c, uint32_t cell_pts) {
   }
   // axis-sorted cells (axis.h): plane in 3-D, cells of 256 / 512 records
   c->axis_valid = false;
-  if (D == 3 && c->opt_axis && c->cfg.model == LSQR_MODEL_PLANE && c->n_cells && (cell_pts == 512 || cell_pts == 256)) {
+  if (D == 3 && c->opt.axis && c->cfg.model == LSQR_MODEL_PLANE && c->n_cells && (cell_pts == 512 || cell_pts == 256)) {
     if ((st = ensure(c, c->d_axis, (size_t)c->n_cells)) != LSQR_OK) return st;
     if ((st = ensure(c, c->d_cellT, (size_t)c->n_cells * cell_pts)) != LSQR_OK) return st;
     if ((st = ensure(c, c->d_slab, (size_t)c->n_cells)) != LSQR_OK) return st;
@@ -939,7 +909,7 @@ int build_index(lsqr_ctx *c, uint32_t cell_pts) {
         double xabs;
         memcpy(&xabs, &hb.amax, sizeof xabs);  // (k_bounds: the bit pattern of max |coordinate|)
         hipLaunchKernelGGL(k_cell_slabs, dim3((c->n_cells + 255) / 256), dim3(256), 0, c->stream, c->d_boxes, c->d_axis,
-                           c->d_cellT, c->n_sorted, c->n_cells, cell_pts, xabs, (uint32_t)c->opt_slab_gate, c->d_slab);
+                           c->d_cellT, c->n_sorted, c->n_cells, cell_pts, xabs, (uint32_t)c->opt.slab_gate, c->d_slab);
       }
       IDXCHK(hipGetLastError());
       c->axis_valid = true;
@@ -990,7 +960,7 @@ int launch_scan_cells(lsqr_ctx *c, const ScanBatch &b) {
     // waiting (2.4 ms instead of 1.6 ms at 4 segments)
     const size_t waves = blocks * wpb, groups = (hc + 63) / 64;
     uint32_t hsplit = 1;
-    if (c->opt_hsplit > 0) hsplit = (uint32_t)std::min<size_t>(groups, (size_t)c->opt_hsplit);
+    if (c->opt.hsplit > 0) hsplit = (uint32_t)std::min<size_t>(groups, (size_t)c->opt.hsplit);
     const size_t units = wtiles * hsplit;
     const uint32_t grab = (uint32_t)std::min<size_t>(8, std::max<size_t>(1, units / (32 * waves)));
     ProfScope ps(c, KID_SCAN);
@@ -1008,7 +978,7 @@ template <class CM, int PP, int CPT>
 int run_scan_cells(lsqr_ctx *c, const ScanBatch &b) {
   // hypothesis broadcast to the survivors: v_readlane, or (scan_block 257 / the model's choice)
   // uniform-address LDS reads.  (1024-thread workgroups measured 3-5 % slower and are no longer built.)
-  if (c->opt_block == 257 || (c->opt_block == 0 && CM::LDS_BROADCAST))
+  if (c->opt.block == 257 || (c->opt.block == 0 && CM::LDS_BROADCAST))
     return launch_scan_cells<CM, PP, CPT, 256, true>(c, b);
   return launch_scan_cells<CM, PP, CPT, 256>(c, b);
 }
@@ -1046,8 +1016,8 @@ int run_cells_bounds(lsqr_ctx *c, uint32_t *d_ub, uint32_t *d_nc = nullptr) {
   // hypothesis would be counted.  The selection counts of earlier batches come back through pinned memory
   // (bsel_known: the latest batch the host has synchronised with; an older value only delays the switch): once a
   // second pass held more than a third of its batch, the bounds of this upload stay on the cells.
-  uint32_t merge = c->opt_bound_merge ? (uint32_t)c->opt_bound_merge : (uint32_t)CM::BOUND_MERGE;
-  if (!c->opt_bound_merge) {
+  uint32_t merge = c->opt.bound_merge ? (uint32_t)c->opt.bound_merge : (uint32_t)CM::BOUND_MERGE;
+  if (!c->opt.bound_merge) {
     while (merge > 1 && c->n_cells / merge < 4096) merge /= 2;
     if (c->bsel_known_H && (uint64_t)c->bsel_known.n_rest * 3 > c->bsel_known_H) c->merge_off = true;
     if (c->merge_off) merge = 1;
@@ -1143,9 +1113,9 @@ int run_scan_pairs(lsqr_ctx *c, const ScanBatch &b0) {
   const float *rows = CM::ROW_F32 ? b.spf : (const float *)b.sp;
   bool ldsb_default = CM::LDS_BROADCAST;
   if constexpr (requires { CM::LDS_BROADCAST_PAIRS; }) ldsb_default = CM::LDS_BROADCAST_PAIRS;
-  const bool ldsb = c->opt_block == 257 || (c->opt_block == 0 && ldsb_default);
+  const bool ldsb = c->opt.block == 257 || (c->opt.block == 0 && ldsb_default);
   // the form, once: the counting pass, k_tile_costs, the LDS size and k_scan_pairs below all read it
-  const PairsForm form = pairs_form<CM>(ldsb, c->opt_prepared, c->opt_lean, c->opt_pack, c->opt_recheck);
+  const PairsForm form = pairs_form<CM>(ldsb, c->opt.prepared, c->opt.lean, c->opt.pack, c->opt.recheck);
   // the hypothesis-only part of level 1 once per batch instead of once per (cell, group): both kernels below read it
   if constexpr (cell_prepared<CM>()) {
     if (prepared(form)) {
@@ -1173,7 +1143,7 @@ int run_scan_pairs(lsqr_ctx *c, const ScanBatch &b0) {
       // the slab test (option "scan_slab"): the masks of the 3-D plane over an axis-sorted index of this cell size
       const CellSlab *slabs = nullptr;
       if constexpr (packed(F) && cell_slab<CM>()) {
-        if (c->opt_slab && c->axis_valid && c->cell_pts == (uint32_t)(128 * PP)) slabs = c->d_slab;
+        if (c->opt.slab && c->axis_valid && c->cell_pts == (uint32_t)(128 * PP)) slabs = c->d_slab;
       }
       c->last_count.valid = true, c->last_count.packed = packed(F), c->last_count.slab = slabs != nullptr;
       c->last_count.H = Hc, c->last_count.h_off = b.h_off, c->last_count.gstride = gstride, c->last_count.h_dev = b.h_dev;
@@ -1184,7 +1154,7 @@ int run_scan_pairs(lsqr_ctx *c, const ScanBatch &b0) {
       };
       // (General alone has two counting forms, and "scan_lean" says which: an option's value cannot be a template
       // argument, so it is read once more here; for the other forms both branches name the same kernel)
-      if (c->opt_lean)  // masks, or cnt, and nothing else
+      if (c->opt.lean)  // masks, or cnt, and nothing else
         count(k_cells_bounds<CM, PP, bounds_form(F, true)>);
       else
         count(k_cells_bounds<CM, PP, bounds_form(F, false)>);
@@ -1203,7 +1173,7 @@ int run_scan_pairs(lsqr_ctx *c, const ScanBatch &b0) {
     else
       (void)hipGetLastError();
     if (per_cu < 1) per_cu = 1;
-    if (c->opt_pairs_waves > 0) per_cu = std::min(per_cu, c->opt_pairs_waves);
+    if (c->opt.pairs_waves > 0) per_cu = std::min(per_cu, c->opt.pairs_waves);
     const unsigned blocks = (unsigned)std::min<size_t>(((size_t)c->n_cells + wpb - 1) / wpb, (size_t)256 * per_cu);
     int st2 = ensure(c, c->d_vpart, (size_t)blocks * Hc);
     if (st2 != LSQR_OK) return st2;
@@ -1273,11 +1243,12 @@ int run_scan_bounded(lsqr_ctx *c) {
   if (!c->h_bsel) {
     HIPCHK(c, c->h_bsel.alloc(128 / sizeof(BoundSel)));
     memset(c->h_bsel, 0, 128);
-    for (int r = 0; r < 2; r++) HIPCHK(c, c->bsel_ev[r].create(hipEventDisableTiming));
+    for (BselRecord &r : c->bsel) HIPCHK(c, r.ev.create(hipEventDisableTiming));
   }
   const int rec = (int)(c->bsel_seq & 1);
-  if (c->bsel_pending[rec]) {
-    HIPCHK(c, hipEventSynchronize(c->bsel_ev[rec]));
+  BselRecord &b = c->bsel[rec];
+  if (b.pending) {
+    HIPCHK(c, hipEventSynchronize(b.ev));
     bsel_fold(c, rec);
   }
   int st = run_cells_bounds<CM, PP>(c, c->d_ub);
@@ -1289,7 +1260,7 @@ int run_scan_bounded(lsqr_ctx *c) {
   float *spf_a = c->d_hparams2_f32, *spf_b = c->d_hparams2_f32 + (size_t)kPilots * M::SPF;
   const uint32_t *lo = nullptr;  // lower vote bounds (rank bounds of the plane), or none
   if constexpr (std::is_same<CM, PlaneCell<3>>::value && (PP == 4 || PP == 2)) {
-    if (c->axis_valid && c->opt_axis && c->cell_pts == (uint32_t)(128 * PP))
+    if (c->axis_valid && c->opt.axis && c->cell_pts == (uint32_t)(128 * PP))
       if ((st = run_rank_bounds<PP>(c, &lo)) != LSQR_OK) return st;
   }
   // The pilot pass is five launches that find nothing to do when a lower bound of the running maximum is known
@@ -1323,10 +1294,10 @@ int run_scan_bounded(lsqr_ctx *c) {
   c->last_bound[0] = 1;
   c->last_bound[3] = H;
   HIPCHK(c, hipMemcpyAsync(bsel_rec(c, rec), c->d_bsel, sizeof(BoundSel), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipEventRecord(c->bsel_ev[rec], c->stream));
-  c->bsel_pending[rec] = true;
-  c->bsel_seq_of[rec] = ++c->bsel_seq;
-  c->bsel_H_of[rec] = H;
+  HIPCHK(c, hipEventRecord(b.ev, c->stream));
+  b.pending = true;
+  b.seq = ++c->bsel_seq;
+  b.H = H;
   c->bsel_last_rec = rec;
   return LSQR_OK;
 }
@@ -1443,7 +1414,7 @@ int worklist_check(lsqr_ctx *c, uint32_t seg_cap, WorklistFill *w) {
   HIPCHK(c, hipMemcpyAsync(c->h_pin->scratch, c->d_counter + CNT_OVF, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, sync_stream(c));
   w->fill = *(unsigned int *)c->h_pin->scratch;
-  w->state = w->fill > seg_cap || c->opt_test_overflow ? WorklistFill::OVERFLOWED : WorklistFill::FITS;
+  w->state = w->fill > seg_cap || c->opt.test_overflow ? WorklistFill::OVERFLOWED : WorklistFill::FITS;
   return LSQR_OK;
 }
 
@@ -1692,7 +1663,7 @@ int run_scan_dense_ee(lsqr_ctx *c, bool *done) {
   ProfMute mute(c);
   if ((st = worklist_reset(c, &fs)) != LSQR_OK) return st;
   bool h16 = false;
-  if (c->opt_dense_f32 == 2 && (st = ensure_dense_h16(c, &h16)) != LSQR_OK) return st;
+  if (c->opt.dense_f32 == 2 && (st = ensure_dense_h16(c, &h16)) != LSQR_OK) return st;
   if ((st = dense_filter_prep(c, fs, h16)) != LSQR_OK) return st;
   auto scan = [&](size_t rb, size_t re, const uint32_t *range_dev, const uint32_t *h_dev, const uint32_t *sel) -> int {
     if (rb >= re) return LSQR_OK;
@@ -1720,7 +1691,7 @@ int run_scan_dense_ee(lsqr_ctx *c, bool *done) {
 template <class M>
 int launch_us_f32(lsqr_ctx *c, size_t rb, size_t re, const double *sp, const float *spf, uint32_t hc, uint32_t *votes,
                   const uint32_t *h_dev, const uint32_t *sel, const uint32_t *range_dev) {
-  const int np = c->opt_ppl == 2 ? 1 : 2;  // pairs of frames per lane (scan_ppl 2 / 4)
+  const int np = c->opt.ppl == 2 ? 1 : 2;  // pairs of frames per lane (scan_ppl 2 / 4)
   const size_t tile = (size_t)kBlock * 2 * np;
   const size_t tiles = (re - rb + tile - 1) / tile;
   const size_t lds = (size_t)hc * sizeof(uint32_t);
@@ -1732,7 +1703,7 @@ int launch_us_f32(lsqr_ctx *c, size_t rb, size_t re, const double *sp, const flo
   // few tiles (1 M frames = 977): split the hypothesis range over blockIdx.y to fill the chip
   unsigned ysplit = (unsigned)std::min<size_t>(std::max<size_t>(1, (size_t)256 * 5 / (size_t)grid),
                                                std::max<size_t>(1, hc / 256));
-  if (c->opt_hsplit > 0) ysplit = (unsigned)c->opt_hsplit;
+  if (c->opt.hsplit > 0) ysplit = (unsigned)c->opt.hsplit;
   if (np == 1)
     hipLaunchKernelGGL((k_scan_us_f32<M, 1>), dim3(grid, ysplit), dim3(kBlock), lds, c->stream, c->d_data, c->stride,
                        rb, re, sp, spf, hc, c->mc, votes, h_dev, sel, range_dev);
@@ -1750,12 +1721,12 @@ int run_scan_us_ee(lsqr_ctx *c) {
   int st = ee_buffers(c, &b);
   if (st != LSQR_OK) return st;
   const uint32_t H = (uint32_t)c->H;
-  const size_t tile = (size_t)kBlock * 2 * (c->opt_ppl == 2 ? 1 : 2);
+  const size_t tile = (size_t)kBlock * 2 * (c->opt.ppl == 2 ? 1 : 2);
   ProfScope whole(c, KID_SCAN);
   ProfMute mute(c);
   bool h16 = false;
   if constexpr (kHasUsH16<M>) {
-    if (c->opt_us_h16 && H <= kFilterHypCap) {
+    if (c->opt.us_h16 && H <= kFilterHypCap) {
       if ((st = ensure_us_h16<M>(c, &h16)) != LSQR_OK) return st;
       const FilterScratch fs = filter_scratch(c);
       if (h16 && (st = worklist_reset(c, &fs)) != LSQR_OK) return st;
@@ -1783,11 +1754,11 @@ int run_scan_us_ee(lsqr_ctx *c) {
   if (w.state != WorklistFill::OVERFLOWED) return LSQR_OK;
   // a worklist segment that overflowed (not seen): everything again with the packed fp32 filter
   (void)fail(c, LSQR_OK, "US fp16 filter: worklist segment overflow (fill %u > %u), fp32 filter used", w.fill, kSegCap);
-  const int keep = c->opt_us_h16;
-  c->opt_us_h16 = 0;
+  const int keep = c->opt.us_h16;
+  c->opt.us_h16 = 0;
   c->prof = mute.was;
   st = run_scan_us_ee<M>(c);
-  c->opt_us_h16 = keep;
+  c->opt.us_h16 = keep;
   return st;
 }
 
@@ -1847,7 +1818,7 @@ int scan_dense_f32(lsqr_ctx *c, bool *done) {
   int st = worklist_reset(c, &fs);
   if (st != LSQR_OK) return st;
   bool h16 = false;  // fp16 matrix cores on two-way splits (dense_h16.h)
-  if (c->opt_dense_f32 == 2 && (st = ensure_dense_h16(c, &h16)) != LSQR_OK) return st;
+  if (c->opt.dense_f32 == 2 && (st = ensure_dense_h16(c, &h16)) != LSQR_OK) return st;
   {
     ProfScope ps(c, KID_SCAN);
     if ((st = dense_filter_prep(c, fs, h16)) != LSQR_OK) return st;
@@ -1862,7 +1833,7 @@ int scan_dense_f32(lsqr_ctx *c, bool *done) {
 // dense system.  default: MFMA filter + exact recheck of ambiguous pairs
 template <class M>
 int scan_dense(lsqr_ctx *c, bool *done) {
-  if (!c->opt_filter) return LSQR_OK;
+  if (!c->opt.filter) return LSQR_OK;
   int st = ensure_absmax(c);
   if (st != LSQR_OK) return st;
   if (!c->d_amb) HIPCHK(c, c->d_amb.alloc(kAmbCap));
@@ -1870,13 +1841,13 @@ int scan_dense(lsqr_ctx *c, bool *done) {
   if constexpr (M::NR == 64) {
     // batch entry points: chunked early exit (earlyexit.h) -- hypotheses that can no longer become the running
     // maximum stop being counted
-    if (c->allow_bound && c->opt_bound && c->opt_dense_f32 && c->H >= 128 &&
+    if (c->allow_bound && c->opt.bound && c->opt.dense_f32 && c->H >= 128 &&
         c->H <= kEeCap && c->n >= 65536 && c->mc.absmax < 1e15)
       if ((st = run_scan_dense_ee(c, done)) != LSQR_OK || *done) return st;
   }
   HIPCHK(c, hipMemsetAsync(c->d_votes, 0, c->H * sizeof(uint32_t), c->stream));
   if constexpr (M::NR == 64) {
-    if (c->opt_dense_f32 && c->H <= kFilterHypCap && c->mc.absmax < 1e15) {
+    if (c->opt.dense_f32 && c->H <= kFilterHypCap && c->mc.absmax < 1e15) {
       if ((st = scan_dense_f32(c, done)) != LSQR_OK || *done) return st;
       HIPCHK(c, hipMemsetAsync(c->d_votes, 0, c->H * sizeof(uint32_t), c->stream));   // overflow: fp64 filter
     }
@@ -1887,15 +1858,15 @@ int scan_dense(lsqr_ctx *c, bool *done) {
 // US calibrations / plane phantom: packed fp32 pre-filter (scan_filter 1); US: 2 = the fused fp64 filter
 template <class M>
 int scan_us(lsqr_ctx *c, bool *done) {
-  if (!(c->opt_filter == 1 && c->absmax_valid && c->mc.absmax <= 1e15)) return LSQR_OK;
+  if (!(c->opt.filter == 1 && c->absmax_valid && c->mc.absmax <= 1e15)) return LSQR_OK;
   *done = true;
   c->ee_last = false;
-  if (c->allow_bound && c->opt_bound && c->H >= 256 && c->H <= kEeCap && c->n >= 65536)
+  if (c->allow_bound && c->opt.bound && c->H >= 256 && c->H <= kEeCap && c->n >= 65536)
     return run_scan_us_ee<M>(c);  // batch entry points: chunked early exit (earlyexit.h)
   int st;
   HIPCHK(c, hipMemsetAsync(c->d_votes, 0, c->H * sizeof(uint32_t), c->stream));
   if constexpr (kHasUsH16<M>) {
-    if (c->opt_us_h16 && c->H >= 32 && c->H <= kFilterHypCap && c->n >= 4096) {  // fp16 matrix cores (us_h16.h)
+    if (c->opt.us_h16 && c->H >= 32 && c->H <= kFilterHypCap && c->n >= 4096) {  // fp16 matrix cores (us_h16.h)
       bool h16 = false;
       if ((st = ensure_us_h16<M>(c, &h16)) != LSQR_OK) return st;
       if (h16) {
@@ -1931,7 +1902,7 @@ static bool f32_magnitudes_ok(const lsqr_ctx *c) { return c->absmax_valid && c->
 template <class M>
 bool scan_index_ready(lsqr_ctx *c, uint32_t *cell_pts_out) {
   typedef typename CellOf<M>::type CM;
-  const bool tuned_defaults = c->opt_filter == 1 && c->opt_ppl == 0;  // A/B knobs untouched
+  const bool tuned_defaults = c->opt.filter == 1 && c->opt.ppl == 0;  // A/B knobs untouched
   // Cost model of the build (auto mode).  Per (hypothesis, observation) the exhaustive filter kernel costs
   // ~1.9e-13 s and the two-level scan ~0.2e-13 s (10 M points x 4096 hypotheses: 7.6 ms against 0.8 ms);
   // the build costs ~1.2e-10 s per observation (radix sort + k-d refinement + gather; r03 without the
@@ -1941,24 +1912,24 @@ bool scan_index_ready(lsqr_ctx *c, uint32_t *cell_pts_out) {
   // numTries bound) and what this upload has been asked to scan so far, this batch included.
   constexpr uint64_t kIndexPaysAfter = 768;
   const uint64_t to_come = std::max<uint64_t>(c->hyp_expected, c->hyp_since_upload);
-  const bool want = c->opt_filter && f32_magnitudes_ok(c) && c->mc.absmax >= 1e-10 && !c->index_failed &&
-                    (c->opt_index == 2 ||
-                     (c->opt_index == 1 && tuned_defaults &&
+  const bool want = c->opt.filter && f32_magnitudes_ok(c) && c->mc.absmax >= 1e-10 && !c->index_failed &&
+                    (c->opt.index == 2 ||
+                     (c->opt.index == 1 && tuned_defaults &&
                       (c->index_valid || (c->n >= 65536 && to_come >= kIndexPaysAfter))));
   if (!want) return false;
-  uint32_t cell_pts = c->opt_cell ? (uint32_t)c->opt_cell : (uint32_t)CM::DEFAULT_CELL;
+  uint32_t cell_pts = c->opt.cell ? (uint32_t)c->opt.cell : (uint32_t)CM::DEFAULT_CELL;
   if constexpr (!requires { CM::MAX_PP; }) cell_pts = cell_pts > 512 ? 512 : cell_pts;
   *cell_pts_out = cell_pts;
   // the k-d levels above the runs: 5 - 12 % fewer surviving pairs for 4.5 ms more per build (10 M records) -- worth
   // it once an upload has been scanned by "scan_kd_after" hypotheses (what the caller announced does not count
   // here: the adaptive bound of a RANSAC run starts in the millions and collapses within a few batches)
-  int kd_now = c->opt_refine && c->hyp_since_upload >= (uint64_t)c->opt_kd_after ? c->opt_kd_levels : 0;
+  int kd_now = c->opt.refine && c->hyp_since_upload >= (uint64_t)c->opt.kd_after ? c->opt.kd_levels : 0;
   if constexpr (std::is_same<CM, PlaneCell<3>>::value) {
     // ... except for the plane's BOUNDED scan: its axis bound (axis.h: k_bound_axis) is tighter on the flat
     // Morton runs than on the more cubical k-d regions (166 against 207 of 4096 hypotheses reach the exact
     // count: 0.30 against 0.32 ms), while the full count gains 8 % from the levels.  So a bounded batch never
     // asks for them (an index that has them keeps them: no rebuilding back and forth), a counting one does.
-    if (CM::USE_BOUND && c->allow_bound && c->opt_bound) kd_now = c->index_kd_levels;
+    if (CM::USE_BOUND && c->allow_bound && c->opt.bound) kd_now = c->index_kd_levels;
   }
   if (!c->index_valid || c->cell_pts != cell_pts || kd_now > c->index_kd_levels) {
     c->kd_build_levels = kd_now;
@@ -2004,16 +1975,16 @@ int scan_indexed(lsqr_ctx *c, bool *done) {
   c->last_bound[0] = 0;
   // batch entry points: hypotheses that cannot become the running maximum are not counted (the extra
   // launches only pay for batches of >= 1024; the selection kernels handle <= 8192)
-  if (CM::USE_BOUND && c->allow_bound && c->opt_bound && c->H >= 1024 && c->H <= kSelCap && c->n_cells > 0)
+  if (CM::USE_BOUND && c->allow_bound && c->opt.bound && c->H >= 1024 && c->H <= kSelCap && c->n_cells > 0)
     return with_pp<CM>(cell_pts, [&](auto pp) { return run_scan_bounded<CM, decltype(pp)::value>(c); });
   // plain scans of a large batch: the statically balanced kernel where it measured faster (plane, 10 M x
   // 4096: 1.13 against 1.24 ms; sphere and line are faster with tiles handed out dynamically);
   // "scan_pairs" 1 / 2 force one or the other (A/B)
   bool full_pairs = false;
-  if constexpr (requires { CM::FULL_COUNT_PAIRS; }) full_pairs = c->opt_pairs == 0 && c->H >= 1024;
-  if (c->opt_pairs == 1 || full_pairs) {
+  if constexpr (requires { CM::FULL_COUNT_PAIRS; }) full_pairs = c->opt.pairs == 0 && c->H >= 1024;
+  if (c->opt.pairs == 1 || full_pairs) {
     if constexpr (std::is_same<CM, PlaneCell<3>>::value) {
-      if (c->opt_hyp_order && c->H >= 1024 && c->H <= kOrderCap) return scan_plane_key_order<M>(c, cell_pts);
+      if (c->opt.hyp_order && c->H >= 1024 && c->H <= kOrderCap) return scan_plane_key_order<M>(c, cell_pts);
     }
     const ScanBatch b = {c->d_hparams, c->d_hparams_f32, c->H, c->d_votes, nullptr};
     return with_pp<CM>(cell_pts, [&](auto pp) { return run_scan_pairs<CM, decltype(pp)::value>(c, b); });
@@ -2023,12 +1994,12 @@ int scan_indexed(lsqr_ctx *c, bool *done) {
 // plane, sphere, line: fp32 pre-filter + exact re-evaluation
 template <class M>
 int scan_f32(lsqr_ctx *c, bool *done) {
-  if (!(c->opt_filter && f32_magnitudes_ok(c))) return LSQR_OK;
+  if (!(c->opt.filter && f32_magnitudes_ok(c))) return LSQR_OK;
   *done = true;
-  int ppl = c->opt_ppl ? c->opt_ppl : 4;  // measured best (tools/ab_scan.py)
+  int ppl = c->opt.ppl ? c->opt.ppl : 4;  // measured best (tools/ab_scan.py)
   // re-check granularity: per packed pair (line: wide band, ambiguous tiles are common) or per
   // tile; scan_filter 2 / 3 force one or the other for A/B runs
-  const bool pair = c->opt_filter == 2 || (c->opt_filter == 1 && M::FGRAN == 1);
+  const bool pair = c->opt.filter == 2 || (c->opt.filter == 1 && M::FGRAN == 1);
   if (pair) {
     if (ppl == 8) return run_scan_f32<M, 8, 1>(c);
     return run_scan_f32<M, 4, 1>(c);
@@ -2041,7 +2012,7 @@ int scan_f32(lsqr_ctx *c, bool *done) {
 template <class M>
 int scan_exact(lsqr_ctx *c) {
   if constexpr (M::REC <= 3) {  // point models: PPL is tunable
-    int ppl = c->opt_ppl ? c->opt_ppl : 8;
+    int ppl = c->opt.ppl ? c->opt.ppl : 8;
     if (ppl == 2) return run_scan_ppl<M, 2>(c);
     if (ppl == 8) return run_scan_ppl<M, 8>(c);
     return run_scan_ppl<M, 4>(c);
@@ -2095,11 +2066,11 @@ int launch_syrk(lsqr_ctx *c, const double *data, size_t stride, int n, int use_m
   *nmom = ne + 1;
   {
     ProfScope ps_(c, KID_MOMENTS);
-    if (c->opt_filter) {  // default: matrix-core SYRK
-      if (c->opt_syrk_diag == 1)  // diagnostics (tools/syrk_ab.py): loads only / MFMAs only
+    if (c->opt.filter) {  // default: matrix-core SYRK
+      if (c->opt.syrk_diag == 1)  // diagnostics (tools/syrk_ab.py): loads only / MFMAs only
         hipLaunchKernelGGL(k_syrk_mfma<1>, dim3(nb), dim3(256), 0, c->stream, data, stride,
                            begin, end, chunk, n, c->d_mask, use_mask, ps, c->d_partials);
-      else if (c->opt_syrk_diag == 2)
+      else if (c->opt.syrk_diag == 2)
         hipLaunchKernelGGL(k_syrk_mfma<2>, dim3(nb), dim3(256), 0, c->stream, data, stride,
                            begin, end, chunk, n, c->d_mask, use_mask, ps, c->d_partials);
       else if (n + 1 <= 32)  // the plane phantom's 31 + 1 columns: two of the five column blocks
@@ -2168,10 +2139,10 @@ int launch_solve_dense(lsqr_ctx *c, bool rows = false, int use_mask = 0, size_t 
   ProfScope ps(c, KID_SOLVE);
   const int n = (int)c->cfg.dim;
   int *flag = (int *)(c->d_counter + CNT_FLAG) + 1;  // (the low word of the slot is k_plane_order's count: another model's)
-  rows = rows && c->opt_dense_dd && end > begin;
+  rows = rows && c->opt.dense_dd && end > begin;
   if (rows) HIPCHK(c, hipMemsetAsync(flag, 0, sizeof(int), c->stream));
   hipLaunchKernelGGL(k_solve_dense, dim3(1), dim3(256), dense_lds_bytes(n), c->stream, c->d_mom, n,
-                     c->opt_dense_fast, c->d_out, rows ? flag : (int *)nullptr);
+                     c->opt.dense_fast, c->d_out, rows ? flag : (int *)nullptr);
   HIPCHK(c, hipGetLastError());
   if (!rows) return LSQR_OK;
   if (!c->d_ddpart) HIPCHK(c, c->d_ddpart.alloc((size_t)2 * kDdNe * kDdBlocks));
@@ -2485,7 +2456,7 @@ int lm_persist_fit(lsqr_ctx *c, const double *tiles, size_t cnt, int nb, LmState
                    bool *done) {
   *done = false;
   static const bool shared_gpu = getenv("LSQR_SHARE_GPU") != nullptr;  // several processes on one device: no tokens across them
-  if (!c->opt_lm_persist || shared_gpu || c->is_lane) return LSQR_OK;
+  if (!c->opt.lm_persist || shared_gpu || c->is_lane) return LSQR_OK;
   typedef typename M::LmCoef Coef;
   constexpr int NCW = (int)(sizeof(Coef) / 8), NMOM = (int)M::NMOM_LM;
   if (!c->d_lmp) {
@@ -2502,9 +2473,9 @@ int lm_persist_fit(lsqr_ctx *c, const double *tiles, size_t cnt, int nb, LmState
     memset(c->h_lmres, 0, sizeof(unsigned long long) * 256);
     c->lm_seq = 0;
   }
-  const int host_step = c->opt_lm_persist != 2;
+  const int host_step = c->opt.lm_persist != 2;
   // one round of virtual blocks when the device is ours alone (512-thread workgroups: two blocks at a time each)
-  const int G = lmp_acquire(c->device, c, c->opt_lm_persist_wgs, (nb + 1) / 2, c->opt_lm_persist == 1);  // tokens held
+  const int G = lmp_acquire(c->device, c, c->opt.lm_persist_wgs, (nb + 1) / 2, c->opt.lm_persist == 1);  // tokens held
   if (G <= 0) return LSQR_OK;
   // workgroups of eight waves (two virtual blocks at a time) when the tokens cover all blocks in one round -- the pass
   // then spreads over twice the compute units --, else sixteen waves (four blocks at a time)
@@ -2512,7 +2483,7 @@ int lm_persist_fit(lsqr_ctx *c, const double *tiles, size_t cnt, int nb, LmState
   const int Gl = threads == 512 ? G : std::min(G, (nb + 3) / 4);  // workgroups launched
   const size_t lds = std::max<size_t>((size_t)(threads / 64) * 64 * 17 * sizeof(double), (size_t)96 << 10);
   // a fit that has the device to itself in one round keeps its tiles in registers (k_lm_persist<M, 4>: 512 threads)
-  const bool resident = host_step && threads == 512 && (size_t)Gl * 2 >= (size_t)nb && c->opt_lm_persist_resident;
+  const bool resident = host_step && threads == 512 && (size_t)Gl * 2 >= (size_t)nb && c->opt.lm_persist_resident;
   auto give_up = [&](int rc) {  // every way out before the kernel has ended and the tokens have gone back
     lmp_release(c->device, G);
     return rc;
@@ -2532,14 +2503,14 @@ int lm_persist_fit(lsqr_ctx *c, const double *tiles, size_t cnt, int nb, LmState
   for (int j = 0; j < LM_NMAX; j++) init.x0[j] = j < t.n ? x0[j] : 0.0;
   const uint32_t seq0 = c->lm_seq;
   c->lm_seq += (uint32_t)t.maxfev + 8;
-  const unsigned long long timeout = (unsigned long long)std::max(1, c->opt_lm_persist_timeout_ms) * 100000ULL;  // 100 MHz
+  const unsigned long long timeout = (unsigned long long)std::max(1, c->opt.lm_persist_timeout_ms) * 100000ULL;  // 100 MHz
   if (hipMemsetAsync(c->d_lmp, 0, sizeof(LmpCtl), c->stream) != hipSuccess) return give_up(LSQR_OK);
   {
     ProfScope ps(c, KID_MOMENTS);
     auto launch = [&](auto kern) {
       hipLaunchKernelGGL(kern, dim3(Gl), dim3(threads), lds, c->stream, tiles, cnt, nb, c->d_lmp, c->d_partials,
                          c->h_lmres, c->h_lmcmd, c->d_lm, c->d_out, init, seq0, host_step, timeout,
-                         (uint32_t)c->opt_lm_persist_test_abort);
+                         (uint32_t)c->opt.lm_persist_test_abort);
     };
     if (resident) launch(k_lm_persist<M, 4>);
     else launch(k_lm_persist<M, 0>);
@@ -2583,7 +2554,7 @@ int lm_persist_fit(lsqr_ctx *c, const double *tiles, size_t cnt, int nb, LmState
   if (se != hipSuccess) return fail(c, LSQR_ERR_HIP, "persistent LM kernel: %s", hipGetErrorString(se));
   LmpCtl *hc = &c->h_pin->lmp;  // (an area of its own, PinLayout: finish_ransac reads mask_head after the fit)
   HIPCHK(c, hipMemcpy(hc, c->d_lmp, sizeof(LmpCtl), hipMemcpyDeviceToHost));
-  c->lmp_last[0] = (uint64_t)c->opt_lm_persist;
+  c->lmp_last[0] = (uint64_t)c->opt.lm_persist;
   c->lmp_last[1] = (uint64_t)Gl;
   c->lmp_last[2] = hc->evals;
   c->lmp_last[3] = hc->status;
@@ -2607,7 +2578,7 @@ int lm_persist_fit(lsqr_ctx *c, const double *tiles, size_t cnt, int nb, LmState
 // per-lane version's whole pass
 template <class M>
 bool lm_mfma_pass(const lsqr_ctx *c) {
-  return c->opt_lm_mfma && M::NLM >= 8;
+  return c->opt.lm_mfma && M::NLM >= 8;
 }
 
 // what an evaluation of the fused driver reads -- the upload, through the mask or not, or the compacted consensus
@@ -2624,7 +2595,7 @@ struct LmPassSet {
 // the consensus set, tight and in order (every evaluation then streams n_in records, all lanes busy) -> d_lmrec
 template <class M>
 int lm_compact(lsqr_ctx *c, LmPassSet &w) {
-  const bool tile_layout = lm_mfma_pass<M>(c) && c->opt_lm_tiles;
+  const bool tile_layout = lm_mfma_pass<M>(c) && c->opt.lm_tiles;
   double *pin = c->h_pin->scratch_f64;
   const auto [cb, cchunk] = pass_shape(c->n, kBlock * 8, 1024, kBlock);  // (c->n > 0: need_ready(c, true))
   uint32_t *d_cnt = (uint32_t *)c->d_partials.get(), *d_off = d_cnt + 1024;  // scratch (4.4 MB buffer)
@@ -2814,11 +2785,11 @@ int run_fit(lsqr_ctx *c, int use_mask, SolveOut *out, bool have_moments = false,
         if (!wants_lm(c->cfg) || !out->ok) return LSQR_OK;  // algebraic initialiser failed -> empty (Sphere...hxx:231-232)
         LmSet t;
         lm_settings(c->cfg, &t.n, &t.ftol, &t.xtol, &t.gtol, &t.maxfev);
-        if (c->opt_lm_host) {
+        if (c->opt.lm_host) {
           // MINPACK's control flow between device passes runs on the host (like the RANSAC replay):
           // a few hundred flops per evaluation; every N-scale operation stays a device pass.
           LmState &s = c->h_lm;
-          st = c->opt_lm_fused ? lm_fit_fused<M>(c, use_mask, t, out->params, s)
+          st = c->opt.lm_fused ? lm_fit_fused<M>(c, use_mask, t, out->params, s)
                                : lm_fit_staged<M>(c, use_mask, t, out->params, s);
           if (st != LSQR_OK) return st;
           static const bool dbg_on = getenv("LSQR_LM_DEBUG") != nullptr;
@@ -2891,19 +2862,19 @@ int run_mask(lsqr_ctx *c, size_t begin, size_t end, uint8_t *mask_out, uint64_t 
 // whose moments are not a per-record accumulate (dense: SYRK on the matrix cores; phantom: Gram of the rows).
 int launch_mask_moments(lsqr_ctx *c, size_t begin, size_t end, int *nmom, bool *fused) {
   *fused = false;
-  if (c->cfg.model == LSQR_MODEL_PHANTOM || !c->opt_fuse_mask) return LSQR_OK;
+  if (c->cfg.model == LSQR_MODEL_PHANTOM || !c->opt.fuse_mask) return LSQR_OK;
   int st = ensure(c, c->d_mask, c->n);
   if (st != LSQR_OK) return st;
   if (c->cfg.model == LSQR_MODEL_DENSE) {
     // dense system: mask + sum z z^T of the agreeing rows in one pass (dense.h: k_mask_syrk_dense); tight records
     // and the matrix-core path only -- anything else keeps the two kernels
     const int n = c->cfg.dim, nz = n + 1;
-    if (c->stride != (size_t)nz || !c->opt_filter || c->opt_syrk_diag || end <= begin ||
+    if (c->stride != (size_t)nz || !c->opt.filter || c->opt.syrk_diag || end <= begin ||
         ((uintptr_t)c->d_data & 15) != 0 || ((begin * (size_t)nz) & 1) != 0)  // 16-byte pieces from the first row on
       return LSQR_OK;
     if ((st = ensure_absmax(c)) != LSQR_OK) return st;  // magnitudes for the band of the four-chain evaluation
     HIPCHK(c, hipMemsetAsync(c->d_counter + CNT_MASK, 0, sizeof(unsigned long long), c->stream));
-    const int nbuf = (c->opt_mask_ring == 4 && n == 64) ? 4 : 2;
+    const int nbuf = (c->opt.mask_ring == 4 && n == 64) ? 4 : 2;
     // two workgroups per CU / one; whole rounds of the four waves' 16-row tiles (end > begin: checked above)
     const PassShape shape = pass_shape(end - begin, 64 * 4, nbuf == 2 ? 512 : 256, 64);
     const int nb = shape.nb;
@@ -2920,7 +2891,7 @@ int launch_mask_moments(lsqr_ctx *c, size_t begin, size_t end, int *nmom, bool *
         (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         hipLaunchKernelGGL(kern, dim3(nb), dim3(256), lds, c->stream, c->d_data, begin, end, chunk, n, c->d_par,
                            c->mc.delta, c->d_mask, c->d_counter + CNT_MASK, ps, c->d_partials, c->mc.absmax_rot, c->mc.absmax,
-                           c->opt_mask_band > 0 ? (double)c->opt_mask_band : 1.0, c->opt_mask_diag);
+                           c->opt.mask_band > 0 ? (double)c->opt.mask_band : 1.0, c->opt.mask_diag);
       };
       if (nbuf == 4) {
         launch(k_mask_syrk_dense<4, 4>);   // n = 64: one workgroup per CU, three tiles in flight per wave
@@ -2962,7 +2933,7 @@ int launch_mask_moments(lsqr_ctx *c, size_t begin, size_t end, int *nmom, bool *
       bool done = false;
       if constexpr (M::IS_US) {
         // US calibrations with tight records: rows of the agreeing frames to the fp64 matrix cores (kernels.h)
-        if (c->opt_us_mask_mfma && c->stride == (size_t)M::REC && cnt > 0) {
+        if (c->opt.us_mask_mfma && c->stride == (size_t)M::REC && cnt > 0) {
           nb = (int)std::min<size_t>(1024, (cnt + 4 * 64 * 2 - 1) / (4 * 64 * 2));  // >= two tiles per wave: one in flight
           if (nb < 1) nb = 1;
           ProfScope ps(c, KID_MASK);
@@ -3254,7 +3225,7 @@ int lsqr_upload(lsqr_ctx *c, const void *host, size_t count, size_t stride_bytes
   // measured on the MI355X box (bench.py cold_call, 240 MB from a pageable numpy buffer): one plain
   // hipMemcpy 4.3 ms = 56 GB/s, the staged ring with 4 threads 5.1 ms -- so the plain copy is the default and
   // the staged path stays an option for hosts whose runtime stages pageable memory slowly
-  int threads = c->opt_upload_threads;
+  int threads = c->opt.upload_threads;
   if (threads < 0) {
     const char *e = getenv("LSQR_UPLOAD_THREADS");
     threads = e ? atoi(e) : 0;
@@ -3580,7 +3551,7 @@ int lsqr_lm_begin(lsqr_ctx *c, const double *x0, double *x_trial_out) {
   int n, maxfev;
   double ftol, xtol, gtol;
   lm_settings(c->cfg, &n, &ftol, &xtol, &gtol, &maxfev);
-  if (c->opt_lm_host || c->cfg.model == LSQR_MODEL_PHANTOM) {
+  if (c->opt.lm_host || c->cfg.model == LSQR_MODEL_PHANTOM) {
     lm_init(c->h_lm, n, x0, ftol, xtol, gtol, maxfev, 100.0);
     if (x_trial_out)
       for (int j = 0; j < n; j++) x_trial_out[j] = x0[j];
@@ -3617,7 +3588,7 @@ int lsqr_lm_step(lsqr_ctx *c, const double *block, double *x_trial_out, int *con
     *cont = 0;
     return deliver_fit(out, params_out, info);
   }
-  if (c->opt_lm_host) {
+  if (c->opt.lm_host) {
     LmState &s = c->h_lm;
     bool go = lm_advance(s, block);
     *cont = go ? 1 : 0;
@@ -3884,7 +3855,7 @@ int lsqr_ransac(lsqr_ctx *c, double p, uint64_t seed, const uint32_t *subsets, s
     // Safety stop (deviation from the reference, which would keep drawing up to C(N,k) subsets):
     // if 2^22 consecutive iterations produced no model at all the data are degenerate.
     if (!rs[RS_HAS] && base >= (1ull << 22)) break;
-    if (c->opt_max_iter > 0 && base >= (uint64_t)c->opt_max_iter) break;  // caller's budget
+    if (c->opt.max_iter > 0 && base >= (uint64_t)c->opt.max_iter) break;  // caller's budget
   }
   c->hyp_expected = 0;
   info->iterations = rs[RS_I];
@@ -3999,13 +3970,13 @@ static void many_job_from_ctx(lsqr_ctx *c, ManyJob &J) {
   J.cfg = c->cfg;
   J.mc = c->mc;
   J.W = c->ND;  // lsqr_record_doubles(cfg)
-  J.max_iter = c->opt_max_iter;
-  J.round_cap = c->opt_many_round > 0 ? (size_t)c->opt_many_round : 0;
+  J.max_iter = c->opt.max_iter;
+  J.round_cap = c->opt.many_round > 0 ? (size_t)c->opt.many_round : 0;
   J.lm = c->cfg.model == LSQR_MODEL_SPHERE && c->cfg.ls_type == LSQR_LS_GEOMETRIC;
   lm_settings(c->cfg, &J.lm_n, &J.lm_ftol, &J.lm_xtol, &J.lm_gtol, &J.lm_maxfev);
-  J.dense_fast = c->opt_dense_fast ? 1 : 0;
-  J.dense_dd = c->opt_dense_dd ? 1 : 0;
-  J.ex_fused = c->opt_many_ex_fused ? 1 : 0;
+  J.dense_fast = c->opt.dense_fast ? 1 : 0;
+  J.dense_dd = c->opt.dense_dd ? 1 : 0;
+  J.ex_fused = c->opt.many_ex_fused ? 1 : 0;
   J.buf = c->many.get();
 }
 
@@ -4645,7 +4616,7 @@ int lsqr_winner_moments(lsqr_ctx *c, uint64_t seed, uint64_t stream_index, size_
 // ---- pipelined batches: enqueue now, read later ------------------------------------------------------------
 // slot s of a context with L lanes: lane s % L, that lane's own slot s / L (0 or 1)
 static int lane_count(const lsqr_ctx *c) {
-  return c->is_lane ? 1 : std::max(1, std::min(c->opt_lanes, (int)lsqr_ctx::kMaxLanes));
+  return c->is_lane ? 1 : std::max(1, std::min(c->opt.lanes, (int)lsqr_ctx::kMaxLanes));
 }
 // the lane context, created on first use and (re-)attached to the parent's model, options and records
 static int lane_get(lsqr_ctx *c, int li, lsqr_ctx **out) {
@@ -4668,8 +4639,7 @@ static int lane_get(lsqr_ctx *c, int li, lsqr_ctx **out) {
     if (!c->has_model || !c->d_data) return fail(c, LSQR_ERR_STATE, "no model / records");
     HIPCHK(c, hipStreamSynchronize(l->stream));
     int st = lsqr_set_model(l, &c->cfg);
-    for (size_t k = 0; st == LSQR_OK && k < c->opt_log.size(); k++)
-      st = lsqr_set_option(l, c->opt_log[k].first.c_str(), c->opt_log[k].second);
+    l->opt = c->opt;  // (an option that drops the index needs no more here: lsqr_attach drops it)
     if (st == LSQR_OK) st = lsqr_attach(l, c->d_data, c->n, c->stride * sizeof(double));
     if (st != LSQR_OK) return fail(c, st, "lane %d: %s", li, lsqr_last_error(l));
     HIPCHK(c, sync_stream(c));  // an upload still in flight on the parent's stream
@@ -4696,7 +4666,8 @@ int lsqr_batch_fit_enqueue(lsqr_ctx *c, uint64_t seed, uint64_t first, size_t H,
     }
   }
   if (slot < 0 || slot > 1) return LSQR_ERR_INVALID;
-  if (c->slot_busy[slot]) return fail(c, LSQR_ERR_STATE, "slot %d holds an unread result", slot);
+  BatchSlotState &s = c->slots[slot];
+  if (s.busy) return fail(c, LSQR_ERR_STATE, "slot %d holds an unread result", slot);
   if (c->has_model && (wants_lm(c->cfg) || c->cfg.model == LSQR_MODEL_PHANTOM))
     return fail(c, LSQR_ERR_INVALID, "this model's fit needs the host between device passes");
   int st = lsqr_hypotheses_sample(c, seed, first, H, nullptr);
@@ -4707,13 +4678,13 @@ int lsqr_batch_fit_enqueue(lsqr_ctx *c, uint64_t seed, uint64_t first, size_t H,
   st = run_scan_batch(c, 0);
   c->defer_ovf = false;
   if (st != LSQR_OK) return st;
-  c->slot_ovf_cap[slot] = c->ovf_cap;
-  c->slot_seed[slot] = seed;
+  s.ovf_cap = c->ovf_cap;
+  s.seed = seed;
   if (c->ovf_cap)  // {fullest worklist segment of this batch's scan} beside the slot's results
     HIPCHK(c, hipMemcpyAsync(&c->h_pin->batch[slot].ovf_fill, c->d_counter + CNT_OVF, sizeof(unsigned long long),
                              hipMemcpyDeviceToHost, c->stream));
-  c->slot_bsel_rec[slot] = c->bsel_seq != seq_before ? c->bsel_last_rec : -1;  // this batch's selection record
-  c->slot_bsel_seq[slot] = c->bsel_seq;
+  s.bsel_rec = c->bsel_seq != seq_before ? c->bsel_last_rec : -1;  // this batch's selection record
+  s.bsel_seq = c->bsel_seq;
   c->scanned = true;
   if ((st = enqueue_take_best(c)) != LSQR_OK) return st;
   BatchSlot *pin = &c->h_pin->batch[slot];
@@ -4721,11 +4692,11 @@ int lsqr_batch_fit_enqueue(lsqr_ctx *c, uint64_t seed, uint64_t first, size_t H,
   if ((st = enqueue_winner_finish(c, ORG_WINNER_DEV, pin->head, &fused)) != LSQR_OK) return st;
   if ((st = enqueue_fit(c, 1, fused, true)) != LSQR_OK) return st;
   HIPCHK(c, hipMemcpyAsync(&pin->out, c->d_out, sizeof(SolveOut), hipMemcpyDeviceToHost, c->stream));
-  if (!c->slot_ev[slot]) HIPCHK(c, c->slot_ev[slot].create(hipEventDisableTiming));
-  HIPCHK(c, hipEventRecord(c->slot_ev[slot], c->stream));
-  c->slot_first[slot] = first;
-  c->slot_H[slot] = H;
-  c->slot_busy[slot] = true;
+  if (!s.ev) HIPCHK(c, s.ev.create(hipEventDisableTiming));
+  HIPCHK(c, hipEventRecord(s.ev, c->stream));
+  s.first = first;
+  s.H = H;
+  s.busy = true;
   return LSQR_OK;
 }
 
@@ -4744,35 +4715,35 @@ int lsqr_batch_fit_wait(lsqr_ctx *c, int slot, double *params_out, lsqr_ransac_i
     }
   }
   if (slot < 0 || slot > 1) return LSQR_ERR_INVALID;
-  if (!c->slot_busy[slot]) return fail(c, LSQR_ERR_STATE, "slot %d has nothing in flight", slot);
+  BatchSlotState &s = c->slots[slot];
+  if (!s.busy) return fail(c, LSQR_ERR_STATE, "slot %d has nothing in flight", slot);
   HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipEventSynchronize(c->slot_ev[slot]));
-  c->slot_busy[slot] = false;
-  if (c->slot_bsel_rec[slot] >= 0 && c->bsel_seq_of[c->slot_bsel_rec[slot]] == c->slot_bsel_seq[slot])
-    bsel_fold(c, c->slot_bsel_rec[slot]);  // the host has synchronised with this batch: its selection counts count
-  c->slot_bsel_rec[slot] = -1;
+  HIPCHK(c, hipEventSynchronize(s.ev));
+  s.busy = false;
+  if (s.bsel_rec >= 0 && c->bsel[s.bsel_rec].seq == s.bsel_seq)
+    bsel_fold(c, s.bsel_rec);  // the host has synchronised with this batch: its selection counts count
+  s.bsel_rec = -1;
   const BatchSlot *pin = &c->h_pin->batch[slot];
-  if (c->slot_ovf_cap[slot]) {
+  if (s.ovf_cap) {
     unsigned int fill = 0;
     memcpy(&fill, &pin->ovf_fill, sizeof fill);
-    if (fill > c->slot_ovf_cap[slot] || c->opt_test_overflow) {
+    if (fill > s.ovf_cap || c->opt.test_overflow) {
       // a worklist segment of the matrix-core filter overflowed (never seen outside the tests): the batch again, blocking,
       // on the exact kernels
       (void)fail(c, LSQR_OK, "worklist segment overflow in slot %d (fill %u > %u): batch run again without the filter",
-                 slot, fill, c->slot_ovf_cap[slot]);
+                 slot, fill, s.ovf_cap);
       c->ovf_reruns++;
-      const int keep = c->opt_filter;
-      c->opt_filter = 0;
-      const int st2 = lsqr_batch_fit(c, c->slot_seed[slot], c->slot_first[slot], (size_t)c->slot_H[slot], params_out,
-                                     nullptr, info);
-      c->opt_filter = keep;
+      const int keep = c->opt.filter;
+      c->opt.filter = 0;
+      const int st2 = lsqr_batch_fit(c, s.seed, s.first, (size_t)s.H, params_out, nullptr, info);
+      c->opt.filter = keep;
       return st2;
     }
   }
   const SolveOut out = pin->out;
   const unsigned long long cnt = pin->head[0], pk = pin->head[1];
   // unlike lsqr_batch_fit, fit.lm_info, lm_nfev and reserved stay 0 here (kept as it is: a behaviour change of its own)
-  fill_ransac_info(info, pk, c->slot_first[slot], c->slot_H[slot], cnt, c->n, out, false);
+  fill_ransac_info(info, pk, s.first, s.H, cnt, c->n, out, false);
   return pk == 0 ? LSQR_EMPTY : deliver_params(out, params_out);
 }
 
@@ -4829,7 +4800,8 @@ int lsqr_step_finish_enqueue(lsqr_ctx *c, const uint64_t *packed_dev, const doub
   int st = need_ready(c, true);
   if (st != LSQR_OK) return st;
   if (!packed_dev || !block_dev || slot < 0 || slot > 1) return fail(c, LSQR_ERR_INVALID, "bad argument");
-  if (c->step_busy[slot]) return fail(c, LSQR_ERR_STATE, "step slot %d holds an unread result", slot);
+  StepSlotState &s = c->steps[slot];
+  if (s.busy) return fail(c, LSQR_ERR_STATE, "step slot %d holds an unread result", slot);
   const int nmom = lsqr_moments_len(&c->cfg, 0);
   StepSlot *pin = &c->h_pin->step[slot];  // (results of a step are staged per slot)
   HIPCHK(c, hipMemcpyAsync(&pin->packed, packed_dev, 8, hipMemcpyDeviceToHost, c->stream));
@@ -4849,24 +4821,25 @@ int lsqr_step_finish_enqueue(lsqr_ctx *c, const uint64_t *packed_dev, const doub
     if (st != LSQR_OK) return st;
     HIPCHK(c, hipMemcpyAsync(&pin->out, c->d_out, sizeof(SolveOut), hipMemcpyDeviceToHost, c->stream));
   }
-  if (!c->step_ev[slot]) HIPCHK(c, c->step_ev[slot].create(hipEventDisableTiming));
-  HIPCHK(c, hipEventRecord(c->step_ev[slot], c->stream));
-  c->step_bsel_rec[slot] = c->bsel_last_rec;   // the step's scan (lsqr_step_scan) came before on this stream
-  c->step_bsel_seq[slot] = c->bsel_last_rec >= 0 ? c->bsel_seq_of[c->bsel_last_rec] : 0;
-  c->step_busy[slot] = true;
+  if (!s.ev) HIPCHK(c, s.ev.create(hipEventDisableTiming));
+  HIPCHK(c, hipEventRecord(s.ev, c->stream));
+  s.bsel_rec = c->bsel_last_rec;   // the step's scan (lsqr_step_scan) came before on this stream
+  s.bsel_seq = c->bsel_last_rec >= 0 ? c->bsel[c->bsel_last_rec].seq : 0;
+  s.busy = true;
   return LSQR_OK;
 }
 
 int lsqr_step_finish_wait(lsqr_ctx *c, int slot, double *winner_out, double *params_out,
                           lsqr_ransac_info *info) {
   if (!c || slot < 0 || slot > 1) return LSQR_ERR_INVALID;
-  if (!c->step_busy[slot]) return fail(c, LSQR_ERR_STATE, "step slot %d has nothing in flight", slot);
+  StepSlotState &s = c->steps[slot];
+  if (!s.busy) return fail(c, LSQR_ERR_STATE, "step slot %d has nothing in flight", slot);
   HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipEventSynchronize(c->step_ev[slot]));  // the one synchronisation of the step
-  c->step_busy[slot] = false;
-  if (c->step_bsel_rec[slot] >= 0 && c->bsel_seq_of[c->step_bsel_rec[slot]] == c->step_bsel_seq[slot])
-    bsel_fold(c, c->step_bsel_rec[slot]);
-  c->step_bsel_rec[slot] = -1;
+  HIPCHK(c, hipEventSynchronize(s.ev));  // the one synchronisation of the step
+  s.busy = false;
+  if (s.bsel_rec >= 0 && c->bsel[s.bsel_rec].seq == s.bsel_seq)
+    bsel_fold(c, s.bsel_rec);
+  s.bsel_rec = -1;
   const StepSlot *pin = &c->h_pin->step[slot];
   const unsigned long long pk = pin->packed;
   SolveOut out;
@@ -4885,7 +4858,7 @@ int lsqr_step_finish_wait(lsqr_ctx *c, int slot, double *winner_out, double *par
 
 int lsqr_step_finish(lsqr_ctx *c, const uint64_t *packed_dev, const double *block_dev,
                      double *winner_out, double *params_out, lsqr_ransac_info *info) {
-  if (c && c->step_busy[0]) return fail(c, LSQR_ERR_STATE, "step slot 0 holds an unread result");
+  if (c && c->steps[0].busy) return fail(c, LSQR_ERR_STATE, "step slot 0 holds an unread result");
   int st = lsqr_step_finish_enqueue(c, packed_dev, block_dev, 0);
   if (st != LSQR_OK) return st;
   return lsqr_step_finish_wait(c, 0, winner_out, params_out, info);
@@ -5092,7 +5065,7 @@ int multi_finish(lsqr_multi *m, uint64_t seed, uint64_t batch_first, double *par
         MHIP(m, hipMemcpyAsync(consensus_out + lo[r], c->d_mask + lo[r], hi[r] - lo[r], hipMemcpyDeviceToHost,
                                c->stream));
     }
-  if (c0->cfg.model == LSQR_MODEL_DENSE && info->fit.reserved == 2 && c0->opt_dense_dd) {
+  if (c0->cfg.model == LSQR_MODEL_DENSE && info->fit.reserved == 2 && c0->opt.dense_dd) {
     // the summed Gram block is ill-conditioned (a pivot below 1e-6 max|G|): its solution carries eps cond(A)^2, and a
     // one-device fit of the same rows would have taken the double-double route.  The records are replicated, so rank 0
     // masks the whole upload with the winner and fits from the rows -- the N-device fit IS the one-device fit then.
@@ -5398,7 +5371,7 @@ int lsqr_multi_ransac(lsqr_multi *m, double p, uint64_t seed, double *params_out
     if (used < total) break;
     per = std::min<size_t>(per * 4, 4096);
     if (!rs[RS_HAS] && base >= (1ull << 22)) break;
-    if (c0->opt_max_iter > 0 && base >= (uint64_t)c0->opt_max_iter) break;
+    if (c0->opt.max_iter > 0 && base >= (uint64_t)c0->opt.max_iter) break;
   }
   info->iterations = rs[RS_I];
   info->best_index = rs[RS_BEST_IDX];
@@ -5425,268 +5398,31 @@ int lsqr_multi_ransac(lsqr_multi *m, double p, uint64_t seed, double *params_out
   return st;
 }
 
-static int set_option_one(lsqr_ctx *c, const char *name, int value);
-int lsqr_set_option(lsqr_ctx *c, const char *name, int value) {
-  if (!c || !name) return LSQR_ERR_INVALID;
-  if (!strcmp(name, "batch_lanes")) {  // streams the pipelined batch entry points spread their slots over (1..4)
-    if (value < 1 || value > lsqr_ctx::kMaxLanes) return fail(c, LSQR_ERR_INVALID, "batch_lanes must be 1..4");
-    for (int s = 0; s < 2; s++)
-      if (c->slot_busy[s]) return fail(c, LSQR_ERR_STATE, "batches in flight");
-    for (int i = 1; i < lsqr_ctx::kMaxLanes; i++)
-      if (c->lanes[i])
-        for (int s = 0; s < 2; s++)
-          if (c->lanes[i]->slot_busy[s]) return fail(c, LSQR_ERR_STATE, "batches in flight");
-    c->opt_lanes = value;
-    return LSQR_OK;
-  }
-  int st = set_option_one(c, name, value);
-  if (st != LSQR_OK || c->is_lane) return st;
-  bool found = false;
-  for (auto &kv : c->opt_log)
-    if (kv.first == name) {
-      kv.second = value;
-      found = true;
-    }
-  if (!found) c->opt_log.emplace_back(name, value);
-  for (int i = 1; i < lsqr_ctx::kMaxLanes; i++)
-    if (c->lanes[i]) (void)set_option_one(c->lanes[i], name, value);
+// options.h holds the names, rules and defaults; what needs the context is here
+static int apply_option(lsqr_ctx *c, const char *name, int value) {
+  bool drops_index = false;
+  char why[256];
+  const int st = options_set(c->opt, name, value, &drops_index, why, sizeof why);
+  if (st == kOptUnknown) return fail(c, LSQR_ERR_INVALID, "unknown option %s", name);
+  if (st != LSQR_OK) return fail(c, st, "%s", why);
+  if (drops_index) drop_index(c);
   return LSQR_OK;
 }
-static int set_option_one(lsqr_ctx *c, const char *name, int value) {
-  if (!strcmp(name, "scan_ppl")) {
-    if (value != 0 && value != 2 && value != 4 && value != 8 && value != 16)
-      return fail(c, LSQR_ERR_INVALID, "scan_ppl must be 0, 2, 4, 8 or 16");
-    c->opt_ppl = value;
-    return LSQR_OK;
+int lsqr_set_option(lsqr_ctx *c, const char *name, int value) {
+  if (!c || !name) return LSQR_ERR_INVALID;
+  static_assert(lsqr_ctx::kMaxLanes == 4, "the range of batch_lanes' row");
+  const bool lanes = !strcmp(name, "batch_lanes");  // the one option that is the parent's alone
+  if (lanes && value >= 1 && value <= lsqr_ctx::kMaxLanes) {  // (a value out of range is the row's to refuse)
+    bool busy = c->slots[0].busy || c->slots[1].busy;
+    for (int i = 1; i < lsqr_ctx::kMaxLanes; i++)
+      if (c->lanes[i]) busy = busy || c->lanes[i]->slots[0].busy || c->lanes[i]->slots[1].busy;
+    if (busy) return fail(c, LSQR_ERR_STATE, "batches in flight");
   }
-  if (!strcmp(name, "scan_filter")) {
-    c->opt_filter = value < 0 ? 0 : (value > 3 ? 1 : value);  // 2 / 3: force pair / tile re-check
-    return LSQR_OK;
-  }
-  if (!strcmp(name, "upload_threads")) {  // host threads of the staged upload (0: one plain hipMemcpy, -1: default)
-    c->opt_upload_threads = value;
-    return LSQR_OK;
-  }
-  if (!strcmp(name, "max_iterations")) {  // budget for lsqr_ransac (0 = reference behaviour)
-    c->opt_max_iter = value;
-    return LSQR_OK;
-  }
-  if (!strcmp(name, "many_round_hypotheses")) {  // lsqr_ransac_many: hypotheses per round (0 = default)
-    if (value < 0) return fail(c, LSQR_ERR_INVALID, "many_round_hypotheses must be >= 0");
-    c->opt_many_round = value;
-    return LSQR_OK;
-  }
-  if (!strcmp(name, "many_exhaustive_fused")) {  // 1 (default): small problems in one fused launch; 0: rounds for all
-    c->opt_many_ex_fused = value != 0;
-    return LSQR_OK;
-  }
-  if (!strcmp(name, "syrk_diag")) {  // 1: loads only, 2: MFMAs only (timing diagnostics, wrong sums)
-    c->opt_syrk_diag = value;
-    return LSQR_OK;
-  }
-  if (!strcmp(name, "scan_bound")) {  // 1 (default): batch entry points skip hypotheses that cannot win; 0: count all
-    c->opt_bound = value != 0;
-    return LSQR_OK;
-  }
-  if (!strcmp(name, "lm_mfma")) {  // 1 (default): LM pass on the matrix cores; 0: per-lane accumulators + shuffle trees
-    c->opt_lm_mfma = value != 0;
-    return LSQR_OK;
-  }
-  if (!strcmp(name, "lm_fused")) {  // 1 (default): one launch per LM evaluation, result polled in pinned memory
-    c->opt_lm_fused = value != 0;
-    return LSQR_OK;
-  }
-  if (!strcmp(name, "lm_host")) {
-    c->opt_lm_host = value != 0;
-    return LSQR_OK;
-  }
-  if (!strcmp(name, "scan_index")) {  // 0 off, 1 auto, 2 always (point models)
-    if (value < 0 || value > 2) return fail(c, LSQR_ERR_INVALID, "scan_index must be 0, 1 or 2");
-    c->opt_index = value;
-    return LSQR_OK;
-  }
-  if (!strcmp(name, "scan_cpt")) {  // cells per wave tile of the two-level scan
-    if (value != 0 && value != 1) return fail(c, LSQR_ERR_INVALID, "scan_cpt must be 0 or 1");
-    c->opt_cpt = value;
-    return LSQR_OK;
-  }
-  if (!strcmp(name, "scan_bound_merge")) {  // cells per box of the bounds pass (0 = the cell model's default)
-    if (value != 0 && value != 1 && value != 2 && value != 4 && value != 8)
-      return fail(c, LSQR_ERR_INVALID, "scan_bound_merge must be 0, 1, 2, 4 or 8");
-    c->opt_bound_merge = value;
-    return LSQR_OK;
-  }
-  if (!strcmp(name, "scan_pairs")) {  // 0: default, 1: k_scan_pairs for plain scans too (A/B)
-    c->opt_pairs = value;
-    return LSQR_OK;
-  }
-  if (!strcmp(name, "scan_prepared")) {  // 1 (default): the counted scan reads each hypothesis' prepared Hyp; 0: load() per (cell, group)
-    c->opt_prepared = value != 0;
-    return LSQR_OK;
-  }
-  if (!strcmp(name, "scan_lean")) {  // 1 (default): count-only counting pass, lean k_scan_pairs (prepared models); 0: the general forms
-    c->opt_lean = value != 0;
-    return LSQR_OK;
-  }
-  if (!strcmp(name, "scan_pack")) {  // 1 (default): the lean k_scan_pairs runs level 1 on packed blocks of 64 survivors; 0: per group
-    if (value != 0 && value != 1) return fail(c, LSQR_ERR_INVALID, "scan_pack must be 0 or 1");
-    c->opt_pack = value;
-    return LSQR_OK;
-  }
-  if (!strcmp(name, "scan_recheck")) {  // 1 (default): an ambiguous pair of the packed k_scan_pairs re-checks the band's observations; 0: its whole cell
-    if (value != 0 && value != 1) return fail(c, LSQR_ERR_INVALID, "scan_recheck must be 0 or 1");
-    c->opt_recheck = value;
-    return LSQR_OK;
-  }
-  if (!strcmp(name, "scan_slab")) {  // 1 (default): the counting pass of the 3-D plane's packed scan drops the pairs the cell's slab proves empty; 0: plain level-1 masks
-    if (value != 0 && value != 1) return fail(c, LSQR_ERR_INVALID, "scan_slab must be 0 or 1");
-    c->opt_slab = value;
-    return LSQR_OK;
-  }
-  if (!strcmp(name, "scan_slab_gate")) {  // kappa of the slabs' gate in quarters (axis.h: k_cell_slabs; A/B knob)
-    if (value < 1 || value > 8) return fail(c, LSQR_ERR_INVALID, "scan_slab_gate must be 1..8 (quarters)");
-    c->opt_slab_gate = value;
-    drop_index(c);
-    return LSQR_OK;
-  }
-  if (!strcmp(name, "scan_axis")) {  // 1 (default): axis-sorted cells + vote bounds by rank (plane, 3-D); 0: off
-    c->opt_axis = value != 0;
-    return LSQR_OK;
-  }
-  if (!strcmp(name, "scan_hyp_order")) {  // 1 (default): full counts of the plane in key order (similar planes share a group)
-    c->opt_hyp_order = value != 0;
-    return LSQR_OK;
-  }
-  if (!strcmp(name, "mom_chunk")) {
-    c->opt_mom_chunk = value;
-    return LSQR_OK;
-  }
-  if (!strcmp(name, "us_mfma")) {  // 1 (default): US calibrations' scan on the fp16 matrix cores; 0: packed fp32 filter
-    c->opt_us_h16 = value != 0;
-    return LSQR_OK;
-  }
-  if (!strcmp(name, "scan_pairs_mfma")) {  // r04's level 2 of the plane on the fp16 matrix cores: exact, measured 25 % slower;
-    // out of the product since r05 (the kernel is kept under tools/attic/cells_h16.h)
-    return value == 0 ? LSQR_OK : fail(c, LSQR_ERR_INVALID, "scan_pairs_mfma: removed (measured slower; tools/attic/cells_h16.h)");
-  }
-  if (!strcmp(name, "scan_pairs_waves")) {  // workgroups per CU of k_scan_pairs (0 = what fits)
-    c->opt_pairs_waves = value;
-    return LSQR_OK;
-  }
-  if (!strcmp(name, "scan_hsplit")) {  // hypothesis segments per tile of the two-level scan (0 = auto)
-    if (value < 0 || value > 128) return fail(c, LSQR_ERR_INVALID, "scan_hsplit must be 0..128");
-    c->opt_hsplit = value;
-    return LSQR_OK;
-  }
-  if (!strcmp(name, "dense_mask_ring")) {  // A/B: 2 (default) or 4 tile buffers per wave
-    c->opt_mask_ring = value;
-    return LSQR_OK;
-  }
-  if (!strcmp(name, "dense_mask_diag")) {  // timing diagnostics (wrong results): 1 no MFMA, 2 no row evaluation
-    c->opt_mask_diag = value;
-    return LSQR_OK;
-  }
-  if (!strcmp(name, "dense_mask_band")) {  // tests: widen the band of k_mask_syrk_dense's four-chain evaluation
-    c->opt_mask_band = value;
-    return LSQR_OK;
-  }
-  if (!strcmp(name, "fuse_mask")) {  // winner's mask + moment block in one pass (default) or two kernels
-    c->opt_fuse_mask = value != 0;
-    return LSQR_OK;
-  }
-  if (!strcmp(name, "scan_block")) {  // workgroup size of the two-level scan
-    if (value != 0 && value != 256 && value != 257)
-      return fail(c, LSQR_ERR_INVALID, "scan_block must be 0, 256 or 257 (256 + LDS broadcast)");
-    c->opt_block = value;
-    return LSQR_OK;
-  }
-  if (!strcmp(name, "scan_cell")) {  // observations per cell of the spatial index
-    if (value != 0 && value != 256 && value != 512)
-      return fail(c, LSQR_ERR_INVALID, "scan_cell must be 0, 256 or 512");
-    c->opt_cell = value;
-    return LSQR_OK;
-  }
-  if (!strcmp(name, "dense_f32")) {  // 2 (default): dense scan filter on the fp16 matrix cores (two-way splits);
-    c->opt_dense_f32 = value < 0 ? 0 : value > 2 ? 2 : value;  // 1: fp32 matrix cores; 0: fp64 matrix cores
-    return LSQR_OK;
-  }
-  if (!strcmp(name, "us_fast_solve")) {  // 0: every minimal solve of the US calibrations through the SVD pseudo-inverse
-    c->opt_us_fast = value != 0;
-    return LSQR_OK;
-  }
-  if (!strcmp(name, "dense_fast_solve")) {  // 0: every minimal solve through the SVD pseudo-inverse
-    c->opt_dense_fast = value != 0;
-    return LSQR_OK;
-  }
-  if (!strcmp(name, "lm_persist")) {  // 0: two launches per LM evaluation; 1 (alone on the device) / 3 (always): one persistent launch per fit, step on the host; 2: step on the device
-    if (value < 0 || value > 3) return LSQR_ERR_INVALID;
-    c->opt_lm_persist = (int)value;
-    return LSQR_OK;
-  }
-  if (!strcmp(name, "lm_persist_wgs")) {  // resident workgroups of the persistent fit (0: by the contexts on the device)
-    if (value < 0 || value > 1024) return LSQR_ERR_INVALID;
-    c->opt_lm_persist_wgs = (int)value;
-    return LSQR_OK;
-  }
-  if (!strcmp(name, "phantom_fast_solve")) {  // 1 (default): null vectors by LU + inverse iteration, Jacobi SVD as the fallback; 0: Jacobi only; n > 1: iteration limit
-    c->opt_phantom_fast = (int)std::max<long long>(0, value);
-    return LSQR_OK;
-  }
-  if (!strcmp(name, "scan_test_overflow")) {  // tests: every worklist check answers "overflowed" (worklist_check, lsqr_batch_fit_wait)
-    c->opt_test_overflow = value != 0;
-    return LSQR_OK;
-  }
-  if (!strcmp(name, "lm_persist_resident")) {
-    c->opt_lm_persist_resident = value != 0;
-    return LSQR_OK;
-  }
-  if (!strcmp(name, "lm_persist_test_abort")) {
-    c->opt_lm_persist_test_abort = (int)std::max<long long>(0, value);
-    return LSQR_OK;
-  }
-  if (!strcmp(name, "lm_persist_timeout_ms")) {
-    if (value < 1 || value > 60000) return LSQR_ERR_INVALID;
-    c->opt_lm_persist_timeout_ms = (int)value;
-    return LSQR_OK;
-  }
-  if (!strcmp(name, "lm_tiles")) {  // 0: the r03 pass over the record-major compacted set (A/B knob)
-    c->opt_lm_tiles = value != 0;
-    return LSQR_OK;
-  }
-  if (!strcmp(name, "us_mask_mfma")) {  // 0: per-lane accumulators (k_mask_moments<US>; r03, A/B knob)
-    c->opt_us_mask_mfma = value != 0;
-    return LSQR_OK;
-  }
-  if (!strcmp(name, "scan_kd_after")) {  // hypotheses an upload is scanned by before the k-d levels above the runs are built
-    if (value < 0) return fail(c, LSQR_ERR_INVALID, "scan_kd_after: >= 0");
-    c->opt_kd_after = value;
-    return LSQR_OK;
-  }
-  if (!strcmp(name, "scan_kd_levels")) {  // k-d levels above the 8192-record runs (0: Morton order above them, as until r05)
-    if (value < 0 || value > 12) return fail(c, LSQR_ERR_INVALID, "scan_kd_levels: 0 .. 12");
-    c->opt_kd_levels = value;
-    drop_index(c);
-    return LSQR_OK;
-  }
-  if (!strcmp(name, "scan_refine")) {  // 0: cells are plain runs of the Morton order (r03; A/B knob)
-    c->opt_refine = value != 0;
-    drop_index(c);
-    return LSQR_OK;
-  }
-  if (!strcmp(name, "scan_presorted")) {  // cells are runs of the upload order (set before the index is built)
-    c->opt_presorted = value != 0;
-    drop_index(c);
-    return LSQR_OK;
-  }
-  if (!strcmp(name, "dense_wave_solve")) {  // 0: one workgroup per minimal solve (r03; bit-identical results, A/B)
-    c->opt_dense_wave = value;
-    return LSQR_OK;
-  }
-  if (!strcmp(name, "dense_dd")) {  // 0: an ill-conditioned dense fit stays on the Gram block (r03 behaviour; A/B)
-    c->opt_dense_dd = value != 0;
-    return LSQR_OK;
-  }
-  return fail(c, LSQR_ERR_INVALID, "unknown option %s", name);
+  const int st = apply_option(c, name, value);
+  if (st != LSQR_OK || c->is_lane || lanes) return st;
+  for (int i = 1; i < lsqr_ctx::kMaxLanes; i++)
+    if (c->lanes[i]) (void)apply_option(c->lanes[i], name, value);
+  return LSQR_OK;
 }
 
 int lsqr_scan_workload(lsqr_ctx *c, uint32_t *bound_out, uint64_t out[8]) {

@@ -1,4 +1,4 @@
-"""Every name lsqr_set_option compares (lsqrrecipes_amd/csrc/lsqr_hip.hip: lsqr_set_option / set_option_one) is passed
+"""Every name lsqr_set_option knows (the rows of kOptions in lsqrrecipes_amd/csrc/options.h) is passed
 to set_option by some test, or is listed in EXEMPT below with the reason why not.  Each knob selects another kernel
 instantiation, launch shape or host path, and the contract is that no answer depends on one (tests/
 test_gpu_option_matrix.py): a knob that arrives without a test fails here.  Runs without a GPU."""
@@ -7,7 +7,7 @@ import os
 import re
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SOURCE = os.path.join(ROOT, "lsqrrecipes_amd", "csrc", "lsqr_hip.hip")
+SOURCE = os.path.join(ROOT, "lsqrrecipes_amd", "csrc", "options.h")
 
 # option -> why no test sets it
 EXEMPT = {
@@ -21,11 +21,10 @@ EXEMPT = {
 def _option_names():
     with open(SOURCE) as f:
         text = f.read()
-    begin = text.index("int lsqr_set_option(lsqr_ctx *c, const char *name, int value) {")
-    end = text.index('"unknown option', begin)       # the last statement of set_option_one
-    body = text[begin:end]
-    assert "static int set_option_one(lsqr_ctx *c, const char *name, int value) {" in body
-    return re.findall(r'!strcmp\(name, "([A-Za-z0-9_]+)"\)', body)
+    begin = text.index("inline constexpr OptionRow kOptions[] = {")
+    end = text.index("\n};", begin)                   # the table's closing brace
+    # a row: {"name", &Options::member (nullptr for a removed option), rule, ...
+    return re.findall(r'^\s*\{"([A-Za-z0-9_]+)", (?:&Options::\w+|nullptr), OPT_[A-Z_]+,', text[begin:end], re.M)
 
 
 def _quoted_in_tests():
@@ -42,7 +41,7 @@ def _quoted_in_tests():
 def test_the_option_list_is_read_from_the_source():
     names = _option_names()
     assert len(names) == len(set(names)), sorted(n for n in names if names.count(n) > 1)
-    assert len(names) >= 49                           # (what the source held when this guard was written)
+    assert len(names) >= 53                           # (what the source held when this guard was written)
     for known in ("batch_lanes", "scan_ppl", "scan_hsplit", "upload_threads", "dense_dd"):  # first, last and between
         assert known in names
 
