@@ -21,8 +21,10 @@ namespace lsqr {
 // arguments -- enough to send two runs of an ill-conditioned minimisation down different iterates.  This is the
 // classical argument reduction by three-part pi/2 (Cody & Waite) and the minimax polynomials on [-pi/4, pi/4] (the
 // published fdlibm coefficients), written with plain IEEE multiplies, adds and rint only (the library is compiled
-// with -ffp-contract=off), so every operation rounds identically everywhere.  Error < 1 ulp for |x| < 2^19 pi/2;
-// beyond that (never an Euler angle of a minimisation) the platform's own functions answer.
+// with -ffp-contract=off), so every operation rounds identically everywhere.  Error < 2 ulp for |x| < 8.2e5 (just
+// under 2^19 pi/2; measured against 80-bit long double: at most 1.46 ulp, tests/test_small_linalg.py asserts the 2);
+// beyond that (never an Euler angle of a minimisation) the platform's own functions answer.  sin(-x) = -sin(x) and
+// cos(-x) = cos(x) bit for bit, and a zero keeps its sign: sin(-0.0) = -0.0.
 LSQR_HD double sc_kernel_sin(double x, double y, bool have_y) {
   const double S1 = -1.66666666666666324348e-01, S2 = 8.33333333332248946124e-03, S3 = -1.98412698298579493134e-04,
                S4 = 2.75573137070700676789e-06, S5 = -2.50507602534068634195e-08, S6 = 1.58969099521155010221e-10;
@@ -49,6 +51,11 @@ LSQR_HD void lsqr_sincos(double x, double *s, double *c) {
   if (!(ax < 8.2e5)) {  // huge, infinite or NaN: the platform's functions
     *s = sin(x);
     *c = cos(x);
+    return;
+  }
+  if (x == 0.0) {  // the polynomial would turn -0.0 into +0.0
+    *s = x;
+    *c = 1.0;
     return;
   }
   if (ax <= 0.78539816339744830962) {
@@ -83,11 +90,40 @@ LSQR_HD void lsqr_sincos(double x, double *s, double *c) {
   }
 }
 
+// The Jacobi routines below compare SQUARES and PRODUCTS of entries (off <= 1e-34 dg, |ga| <= 1e-16 sqrt(al be)), which
+// overflow or underflow long before the entries do and then end the iteration before its first rotation.  A matrix
+// whose largest |entry| is finite, non-zero and outside [2^-band, 2^band] is therefore multiplied by the power of two
+// that brings that entry into [1, 2) -- exact -- and the eigenvalues / singular values are scaled back; the vectors do
+// not depend on the scale.  Inside the band nothing is touched, so every in-range input keeps its bits.  Returns the
+// exponent e (the matrix was multiplied by 2^-e), 0 inside the band.
+LSQR_HD int jacobi_prescale(int rows, int cols, double *a, int lda, int band) {
+  double amax = 0.0;
+  for (int i = 0; i < rows; i++)
+    for (int j = 0; j < cols; j++) {
+      const double t = fabs(a[i * lda + j]);
+      amax = t > amax ? t : amax;
+    }
+  if (!(amax > 0.0) || !(amax < INFINITY)) return 0;  // zero, or not finite (a NaN entry never raises amax)
+  int e;
+  frexp(amax, &e);
+  e -= 1;  // amax = f 2^e, 1 <= f < 2
+  if (e >= -band && e <= band) return 0;
+  for (int i = 0; i < rows; i++)
+    for (int j = 0; j < cols; j++) a[i * lda + j] = ldexp(a[i * lda + j], -e);
+  return e;
+}
+
 // Symmetric eigen decomposition, N <= 64.  a: n*n row-major (destroyed), w ascending,
-// v: columns are unit eigenvectors.
+// v: columns are unit eigenvectors.  Cyclic Jacobi: V^T V = I, A V = V diag(w) and w to a few n eps max|A|
+// (tests/test_small_linalg.py asserts 8 n eps), for every finite A whatever its scale (jacobi_prescale, band 2^+-400);
+// a power-of-two multiple of A gives the same v bit for bit and w times that power.  On return the off-diagonal norm
+// is <= 1e-17 of the diagonal's, or, where a repeated eigenvalue stalls the iteration at the rounding floor, up to 1e-15
+// of it (the stall test below): a caller must not count on the 1e-17.
 LSQR_HD void sym_eig(int n, double *a, double *w, double *v) {
+  const int scale_exp = jacobi_prescale(n, n, a, n, 400);
   for (int i = 0; i < n; i++)
     for (int j = 0; j < n; j++) v[i * n + j] = (i == j) ? 1.0 : 0.0;
+  double off_prev = INFINITY;
   for (int sweep = 0; sweep < 64; sweep++) {
     double off = 0.0, dg = 0.0;
     for (int i = 0; i < n; i++) {
@@ -95,6 +131,13 @@ LSQR_HD void sym_eig(int n, double *a, double *w, double *v) {
       for (int j = i + 1; j < n; j++) off += a[i * n + j] * a[i * n + j];
     }
     if (off == 0.0 || off <= 1e-34 * dg) break;
+    // At the rounding floor: with a repeated eigenvalue (all-ones, a clustered spectrum; from n ~ 31 almost any matrix)
+    // off / dg settles at a few 1e-34 and never passes the test above; the sweeps then rotate noise inside the
+    // eigenspaces up to the limit -- 125 000 rotations at n = 64 -- and their rounding piles up in v (V^T V - I reached
+    // 10.7 n eps).  A converging iteration shrinks off by orders of magnitude per sweep down here (the convergence is
+    // quadratic), so a sweep that gained less than a factor 4 below 1e-30 dg has nothing left to gain.
+    if (off <= 1e-30 * dg && off >= 0.25 * off_prev) break;
+    off_prev = off;
     for (int p = 0; p < n - 1; p++)
       for (int q = p + 1; q < n; q++) {
         double apq = a[p * n + q];
@@ -119,7 +162,7 @@ LSQR_HD void sym_eig(int n, double *a, double *w, double *v) {
         }
       }
   }
-  for (int i = 0; i < n; i++) w[i] = a[i * n + i];
+  for (int i = 0; i < n; i++) w[i] = scale_exp ? ldexp(a[i * n + i], scale_exp) : a[i * n + i];
   for (int i = 0; i < n - 1; i++) {
     int m = i;
     for (int j = i + 1; j < n; j++)
@@ -138,8 +181,10 @@ LSQR_HD void sym_eig(int n, double *a, double *w, double *v) {
 }
 
 // Serial one-sided Jacobi SVD of an m*n matrix (m >= n, row-major with leading dimension lda,
-// overwritten by U*diag(s) then normalised to U); s unsorted; v n*n.
+// overwritten by U*diag(s) then normalised to U); s unsorted; v n*n.  A zero column gives s = 0 exactly and
+// keeps its zero column in U.  Scale-free like sym_eig (jacobi_prescale, band 2^+-200: al * be stays finite and normal).
 LSQR_HD void svd_jacobi(int m, int n, double *a, int lda, double *s, double *v) {
+  const int scale_exp = jacobi_prescale(m, n, a, lda, 200);
   for (int i = 0; i < n; i++)
     for (int j = 0; j < n; j++) v[i * n + j] = (i == j) ? 1.0 : 0.0;
   for (int sweep = 0; sweep < 60; sweep++) {
@@ -154,10 +199,12 @@ LSQR_HD void svd_jacobi(int m, int n, double *a, int lda, double *s, double *v) 
           ga += ui * uj;
         }
         if (ga == 0.0 || fabs(ga) <= 1e-16 * sqrt(al * be)) continue;
-        rotated = true;
         double zeta = (be - al) / (2.0 * ga);
         double t = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
         double c = 1.0 / sqrt(1.0 + t * t), sn = c * t;
+        // a column of rank deficiency shrinks until al underflows: zeta overflows and the rotation is the identity;
+        // counting it as one kept the sweeps going to their limit
+        if (sn != 0.0) rotated = true;
         for (int k = 0; k < m; k++) {
           double ui = a[k * lda + i], uj = a[k * lda + j];
           a[k * lda + i] = c * ui - sn * uj;
@@ -175,7 +222,7 @@ LSQR_HD void svd_jacobi(int m, int n, double *a, int lda, double *s, double *v) 
     double nrm = 0;
     for (int k = 0; k < m; k++) nrm += a[k * lda + j] * a[k * lda + j];
     nrm = sqrt(nrm);
-    s[j] = nrm;
+    s[j] = scale_exp ? ldexp(nrm, scale_exp) : nrm;
     if (nrm > 0)
       for (int k = 0; k < m; k++) a[k * lda + j] /= nrm;
   }

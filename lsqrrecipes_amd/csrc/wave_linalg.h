@@ -25,6 +25,42 @@ __device__ inline double wave_max(double v) {
   return v;
 }
 
+// The rotation tests below compare ga with sqrt(al * be) (or their squares), which overflow from column norms around
+// 2^255 and underflow as early the other way -- and then no column is ever rotated.  Like small_linalg.h's
+// jacobi_prescale: a matrix whose largest |entry| is finite, non-zero and outside [2^-200, 2^200] is multiplied by the
+// power of two that brings that entry into [1, 2); the callers scale singular values and solution back.  Inside the
+// band nothing is touched, so an in-range system keeps its bits.  All T threads call it; returns the exponent e (A was
+// multiplied by 2^-e), 0 inside the band.
+template <int T>
+__device__ inline int block_jacobi_prescale(int m, int n, double *A, int lda) {
+  __shared__ double s_pre[T / 64];
+  const int tid = threadIdx.x;
+  if constexpr (T > 64) __syncthreads();  // the staging of A by the other waves
+  double am = 0.0;
+  for (int idx = tid; idx < m * n; idx += T) {
+    const double v = fabs(A[(idx / m) * lda + idx % m]);
+    am = v > am ? v : am;
+  }
+  am = wave_max(am);
+  if constexpr (T > 64) {
+    if ((tid & 63) == 0) s_pre[tid >> 6] = am;
+    __syncthreads();
+    am = s_pre[0];
+    for (int w = 1; w < T / 64; w++) am = s_pre[w] > am ? s_pre[w] : am;
+  }
+  if (!(am > 0.0) || !(am < INFINITY)) return 0;  // zero, or not finite (a NaN entry never raises am)
+  int e;
+  frexp(am, &e);
+  e -= 1;  // am = f 2^e, 1 <= f < 2
+  if (e >= -200 && e <= 200) return 0;
+  for (int idx = tid; idx < m * n; idx += T) {
+    double *q = A + (idx / m) * lda + idx % m;
+    *q = ldexp(*q, -e);
+  }
+  __syncthreads();
+  return e;
+}
+
 // A: m x n (m >= n, n <= 64) column-major, leading dimension lda; destroyed (becomes U*S).
 // V: n x n column-major (ldv).  b: m.  x: n (output).  cwork: n scratch doubles.
 // Singular values <= max(tol_abs, tol_rel * sigma_max) are zeroed.  Returns the rank.
@@ -33,6 +69,14 @@ __device__ inline double wave_max(double v) {
 // with wave shuffles.
 // One-sided Jacobi sweeps (see block_pinv_solve): A (m x n, column-major) becomes U*S, V (n x n)
 // accumulates the rotations.
+// The cosine at which two columns count as orthogonal: the rounding floor of an m-term dot product, 2.5e-16 m (1.1 m
+// eps), capped at the 4e-15 that sixteen rows reach (longer columns: a tighter bound only re-rotates noise until the
+// sweep limit), and never under 1.6e-15 = 7 eps: a rotation itself leaves a few eps between the two columns it has
+// just rotated, however short they are (with 2.5e-16 m alone a 3 x 3 matrix of rank 2 ran to the limit of 60 sweeps).
+// What is left between the columns appears in x times cond2(A): with 4e-15 at every size, a 7 x 7 Hilbert system
+// (cond2 4.8e8) came back 1.6e-6 off where 10 eps cond2 allows 1.06e-6.
+__host__ __device__ constexpr double jacobi_cos_floor(int m) { return m >= 16 ? 4e-15 : m < 7 ? 1.6e-15 : 2.5e-16 * m; }
+
 template <int T>
 __device__ inline int block_jacobi_svd(int m, int n, double *A, int lda, double *V, int ldv) {
   constexpr int LPP = T / 32;  // lanes per pair
@@ -79,13 +123,15 @@ __device__ inline int block_jacobi_svd(int m, int n, double *A, int lda, double 
         be += __shfl_xor(be, o);
         ga += __shfl_xor(ga, o);
       }
-      // columns count as orthogonal once their cosine is at the rounding floor of an m-term dot
-      // product (a tighter bound only re-rotates noise until the sweep limit)
-      bool rot = active && ga != 0.0 && fabs(ga) > 4e-15 * sqrt(al * be);
+      // columns count as orthogonal once their cosine is at the rounding floor of an m-term dot product
+      bool rot = active && ga != 0.0 && fabs(ga) > jacobi_cos_floor(m) * sqrt(al * be);
       if (rot) {
         double zeta = (be - al) / (2.0 * ga);
         double t = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
         double c = 1.0 / sqrt(1.0 + t * t), sn = c * t;
+        // a column of rank deficiency shrinks until al underflows: zeta overflows, the rotation is the identity, and
+        // counting it as one kept the sweeps going to their limit (applying it leaves every bit as it is)
+        rot = sn != 0.0;
         for (int k = sub; k < m; k += LPP) {
           double ui = A[i * lda + k], uj = A[j * lda + k];
           A[i * lda + k] = c * ui - sn * uj;
@@ -177,13 +223,15 @@ __device__ inline int block_jacobi_svd_fixed(double *A, int lda, double *V, int 
         be += __shfl_xor(be, o);
         ga += __shfl_xor(ga, o);
       }
-      // |ga| > 4e-15 sqrt(al be), squared (no square root on the critical path; al be <= 1e300 for any
-      // system the callers accept)
-      const bool rot = active && ga != 0.0 && ga * ga > 1.6e-29 * (al * be);
+      // |ga| > jacobi_cos_floor(M) sqrt(al be), squared (no square root on the critical path; the callers'
+      // block_jacobi_prescale keeps the entries inside 2^+-200, so neither side overflows or underflows to zero)
+      constexpr double kFloorSq = jacobi_cos_floor(M) * jacobi_cos_floor(M);
+      bool rot = active && ga != 0.0 && ga * ga > kFloorSq * (al * be);
       if (rot) {
         double zeta = (be - al) / (2.0 * ga);
         double t = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
         double c = 1.0 / sqrt(1.0 + t * t), sn = c * t;
+        rot = sn != 0.0;  // (the identity is no rotation: see block_jacobi_svd)
         double *bi = A + i * lda, *bj = A + j * lda, *xi = V + i * ldv, *xj = V + j * ldv;
 #pragma unroll
         for (int q = 0; q < RA; q++) {
@@ -214,7 +262,11 @@ __device__ inline int block_jacobi_svd_fixed(double *A, int lda, double *V, int 
   return sweep;
 }
 
-// M, N > 0: compile-time sizes (m == M, n == N), register-batched rounds (block_jacobi_svd_fixed)
+// M, N > 0: compile-time sizes (m == M, n == N), register-batched rounds (block_jacobi_svd_fixed).
+// Scale-free: 2^k [A | b] gives the same x for every k that keeps the entries finite and normal, and tol_abs is
+// compared with the singular values of A as given (block_jacobi_prescale is undone on both).
+// Accuracy: the sweeps leave cosines up to jacobi_cos_floor(m) between columns, which x carries times cond2(A);
+// tests/test_gpu_small_linalg.py asks max(1e-8, 10 eps cond2) of the exact solution.
 template <int T, int M = 0, int N = 0>
 __device__ inline int block_pinv_solve(int m, int n, double *A, int lda, double *V, int ldv,
                                        const double *b, double tol_abs, double tol_rel, double *x,
@@ -222,6 +274,7 @@ __device__ inline int block_pinv_solve(int m, int n, double *A, int lda, double 
   __shared__ int s_rank;
   __shared__ double s_smax;
   const int tid = threadIdx.x;
+  const int scale_exp = block_jacobi_prescale<T>(m, n, A, lda);
   if constexpr (M > 0) block_jacobi_svd_fixed<T, M, N>(A, lda, V, ldv);
   else block_jacobi_svd<T>(m, n, A, lda, V, ldv);
   // singular values and projections of b
@@ -233,6 +286,7 @@ __device__ inline int block_pinv_solve(int m, int n, double *A, int lda, double 
       d = fma(a, b[k], d);
     }
   double sig = sqrt(s2);
+  if (scale_exp) sig = ldexp(sig, scale_exp);
   if (tid < 64) {  // n <= 64: the first wave holds every column
     double smax = wave_max(tid < n ? sig : 0.0);
     if (tid == 0) s_smax = smax;
@@ -245,7 +299,8 @@ __device__ inline int block_pinv_solve(int m, int n, double *A, int lda, double 
     int rank = __builtin_popcountll(__ballot(keep));
     if (tid == 0) s_rank = rank;
   }
-  if (tid < n) cwork[tid] = keep ? d / s2 : 0.0;  // (u.b)/sigma with u = a/sigma
+  // (u.b)/sigma with u = a/sigma; a carries 2^-scale_exp, so d / s2 carries 2^scale_exp
+  if (tid < n) cwork[tid] = keep ? (scale_exp ? ldexp(d / s2, -scale_exp) : d / s2) : 0.0;
   __syncthreads();
   if (tid < n) {
     double t = 0;
@@ -264,6 +319,7 @@ __device__ inline void block_null_vector(int m, int n, double *A, int lda, doubl
                                          double *x, int *n_positive) {
   __shared__ int s_jmin, s_npos;
   const int tid = threadIdx.x;
+  block_jacobi_prescale<T>(m, n, A, lda);  // (the vector does not depend on the scale)
   if constexpr (M > 0) block_jacobi_svd_fixed<T, M, N>(A, lda, V, ldv);
   else block_jacobi_svd<T>(m, n, A, lda, V, ldv);
   double s2 = 0;
@@ -298,7 +354,12 @@ __device__ inline void block_null_vector(int m, int n, double *A, int lda, doubl
 // is <= 2.2e-16 (DenseLinear...Estimator.hxx:38-45); for a well-conditioned system both give the
 // same solution to rounding (cond * eps).  The fast path only ACCEPTS when every pivot exceeds
 // 1e-8 * max(1, max|A|) -- far from the rank decision -- and reports false otherwise, in which case the
-// caller reloads the system and takes the SVD path, which makes the reference's rank decision.
+// caller reloads the system and takes the SVD path, which makes the reference's rank decision.  A system with
+// max|A| > 1e150 (or a NaN) is refused outright.
+// THE PIVOT RULE, shared by the three eliminations below: the entry of largest |a| in the column at or below the
+// diagonal, ties to the lower row index (reg64: the lower position).  With it the three are bit-identical in what they
+// accept and in x, also where every candidate ties (a +-1 matrix) and where every step swaps (a reversal permutation);
+// tests/test_gpu_small_linalg.py runs them on such systems.
 template <int T>
 __device__ inline bool block_gepp_solve(int n, double *A, int lda, double *b, double *x, double piv_rel = 1e-8) {
   __shared__ int s_p, s_fail;

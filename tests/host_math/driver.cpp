@@ -152,6 +152,25 @@ int hm_pinv_solve(int m, int n, double *a, const double *b, double tol, double *
   return pinv_solve(m, n, a, n, b, tol, x, s.data(), v.data());
 }
 
+// a (m*n row-major) -> U, s (n, unsorted), v (n*n row-major)
+void hm_svd_jacobi(int m, int n, double *a, double *s, double *v) { svd_jacobi(m, n, a, n, s, v); }
+
+// 1 and x written, or 0 and x untouched; g is not modified
+int hm_spd_solve_chol(int n, const double *g, const double *rhs, double *x) {
+  std::vector<double> work((size_t)n * n + n);
+  return spd_solve_chol(n, g, rhs, x, work.data()) ? 1 : 0;
+}
+
+// returns the rank; g is destroyed
+int hm_spd_solve_eig(int n, double *g, const double *rhs, double rtol, double *x) {
+  std::vector<double> work((size_t)2 * n * n + 3 * n);
+  return spd_solve_eig(n, g, rhs, rtol, x, work.data());
+}
+
+void hm_sincos(const double *x, size_t n, double *s, double *c) {
+  for (size_t i = 0; i < n; i++) lsqr_sincos(x[i], s + i, c + i);
+}
+
 
 // ---- plane phantom (phantom.h): rows, agree(), parameter extraction, both fits from the Gram matrix ----
 void hm_phantom_rows(const double *rec, size_t n, double *rows31) {
