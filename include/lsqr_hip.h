@@ -490,7 +490,8 @@ LSQR_API int lsqr_refine(lsqr_ctx *ctx, double *params_inout /* host, n_models *
  *     other rows of the call, and where m sits among them, change nothing.
  *   The context's hypotheses, mask, spatial index and the parameters of its last mask are left as they were; the work
  *     runs on the context's stream.  The options lm_persist and lm_host do not apply (the step runs on the device, as
- *     in lsqr_ransac_many_lm).  lsqr_multi handles and the grouped calls have no such form. */
+ *     in lsqr_ransac_many_lm).  lsqr_refine_lm_grouped, below, is the form with one model set per label; lsqr_multi
+ *     handles have no such form. */
 LSQR_API int lsqr_refine_lm(lsqr_ctx *ctx, double *params_inout /* host, n_models * lsqr_num_params */,
                             size_t n_models, size_t max_rounds, int on_device /* 1: labels_out is a device pointer */,
                             int32_t *labels_out /* nullable */,
@@ -522,7 +523,8 @@ LSQR_API int lsqr_refine_lm(lsqr_ctx *ctx, double *params_inout /* host, n_model
  *     with m >= n_models[g]: status_out LSQR_ERR_STATE (model not there) and a zeroed fit.
  *     counts_out[g * (max_models + 1) + m]: the records of group g labelled m (0 for m >= n_models[g]); slot
  *     max_models: the group's unassigned records.  offsets_out: the prefix sums of the group sizes.
- *   Models: those of lsqr_assign / lsqr_refine; lsqr_refine_grouped refuses the geometric sphere (LSQR_ERR_INVALID).
+ *   Models: those of lsqr_assign / lsqr_refine; lsqr_refine_grouped refuses the geometric sphere (LSQR_ERR_INVALID):
+ *     lsqr_refine_lm_grouped, below, takes it.
  *   Checks, in this order: a null context is refused before anything is touched; the model (none set: LSQR_ERR_STATE;
  *     one the call does not take: LSQR_ERR_INVALID); n_groups == 0 is a no-op returning LSQR_OK; max_models > 64,
  *     n_groups > 2^31 - 1, a null groups, params, n_models or labels_out (assign), a null groups, params_inout,
@@ -552,6 +554,39 @@ LSQR_API int lsqr_refine_grouped(lsqr_ctx *ctx, const int32_t *groups, size_t n_
                                  int32_t *status_out /* host, n_groups * max_models */,
                                  size_t *rounds_out /* host, n_groups */,
                                  int32_t *converged_out /* host, n_groups */);
+/* ---- lsqr_refine_grouped for the geometric sphere: LM fits per group on the device (csrc/assign_lm_grouped.h) ------
+ * lsqr_refine_lm_grouped is lsqr_refine_grouped -- its arguments and their shapes, on_device, the groups' rules, each
+ * group's own loop and stop, what does not run, counts_out / offsets_out, the order of its checks, "every argument error
+ * writes nothing" -- for the one model lsqr_refine_grouped refuses, with lsqr_refine_lm's refit.
+ *   Models: LSQR_MODEL_SPHERE with LSQR_LS_GEOMETRIC in every dimension lsqr_set_model accepts (2..8).  Every other
+ *     model, the algebraic sphere included, returns LSQR_ERR_INVALID and writes nothing: lsqr_refine_grouped takes the
+ *     fits in closed form.
+ *   Contract: group g -- the records with groups[i] == g, in upload order, with rows g * max_models .. + n_models[g] --
+ *     is decided bit for bit as lsqr_refine_lm decides it on a fresh context with the same model and options that
+ *     holds the stable gather of group g's records, tightly packed, with the same max_rounds.  Bit-identical per
+ *     group: labels_out (the model index inside the group, or -1) and the counts; the returned parameters and
+ *     status_out; every field of fits[] (n_params, lm_info, lm_nfev, reserved: the stall evaluation, n_used, cost);
+ *     rounds_out[g] and converged_out[g].  A model whose run gives no result (too few records, no algebraic start,
+ *     lm_info outside 1..4) keeps the row it had before the round; the algebraic intermediate never comes back.
+ *   Groups that run nothing, records in no group and rows m >= n_models[g] behave as lsqr_refine_grouped documents
+ *     them: -1 labels, LSQR_ERR_STATE with a zeroed fit, untouched rows.  max_rounds == 0 is lsqr_assign_grouped, and
+ *     the returned labels are always exactly the grouped assignment of the returned parameters.
+ *   An evaluation is one pass over the packed records of the groups still going, for all their live models at once,
+ *     one step launch and one 4-byte read for all groups together; a refit round lasts as many evaluations as its
+ *     slowest model needs.  Nothing is summed with a floating-point atomic: a group's results do not depend on the
+ *     other groups of the call, on how the ids are numbered, or on the run.
+ *   The context's upload, hypotheses, mask, spatial index and the parameters of its last mask are left as they were
+ *     (as lsqr_refine_grouped leaves them); the work runs on the context's stream, and the call returns after it has
+ *     finished.  The options lm_persist and lm_host do not apply.  lsqr_multi handles have no such form. */
+LSQR_API int lsqr_refine_lm_grouped(lsqr_ctx *ctx, const int32_t *groups, size_t n_groups, int on_device,
+                                    double *params_inout /* host, n_groups * max_models * lsqr_num_params */,
+                                    const size_t *n_models, size_t max_models, size_t max_rounds,
+                                    int32_t *labels_out /* nullable */, uint64_t *counts_out /* nullable */,
+                                    uint64_t *offsets_out /* nullable */,
+                                    lsqr_fit_info *fits /* host, n_groups * max_models */,
+                                    int32_t *status_out /* host, n_groups * max_models */,
+                                    size_t *rounds_out /* host, n_groups */,
+                                    int32_t *converged_out /* host, n_groups */);
 /* Many independent RANSAC<T,S>::compute() problems (probabilistic overload, RANSAC.h:75-79) in one call.
  * Problem j is records [offsets[j], offsets[j+1]) of host_records (stride_bytes apart, laid out as for
  * lsqr_upload), walks sampler stream seeds[j] and is decided exactly as lsqr_ransac(ctx, p, seeds[j], NULL, 0, ...)

@@ -659,6 +659,12 @@ class Context:
         -> dict: params ((n_groups, max_models, P); rows m >= n_models[g] as given), labels (None for the device form
         without labels_out), counts ((n_groups, max_models + 1)), status and n_used ((n_groups, max_models); status
         ERR_STATE where m >= n_models[g]), rounds (int64 per group), converged (bool per group) and offsets."""
+        return self._refine_grouped(self._lib.lsqr_refine_grouped, groups, n_groups, params, n_models, max_rounds,
+                                    labels_out)[0]
+
+    def _refine_grouped(self, call, groups, n_groups, params, n_models, max_rounds, labels_out):
+        """lsqr_refine_grouped or lsqr_refine_lm_grouped -> (refine_grouped's dict, the fits as a structured array
+        shaped (n_groups, max_models))"""
         n, m, total, on_device, g, g_ptr, par, nm, labels, l_ptr = self._assign_grouped_args(
             groups, n_groups, params, n_models, labels_out)
         if int(max_rounds) < 0:
@@ -669,14 +675,29 @@ class Context:
         status = np.full(max(n * m, 1), L.ERR_STATE, dtype=np.int32)
         rounds = np.zeros(max(n, 1), dtype=np.uintp)
         conv = np.zeros(max(n, 1), dtype=np.int32)
-        self._chk(self._lib.lsqr_refine_grouped(self._h, g_ptr, n, 1 if on_device else 0, L.ptr(par), L.ptr(nm), m,
-                                                int(max_rounds), l_ptr, L.ptr(counts), L.ptr(offs), fits,
-                                                L.ptr(status), L.ptr(rounds), L.ptr(conv)))
+        self._chk(call(self._h, g_ptr, n, 1 if on_device else 0, L.ptr(par), L.ptr(nm), m, int(max_rounds), l_ptr,
+                       L.ptr(counts), L.ptr(offs), fits, L.ptr(status), L.ptr(rounds), L.ptr(conv)))
         if labels is not None and not on_device:
             labels = labels[:total]
-        n_used = np.ctypeslib.as_array(fits)[:n * m]["n_used"].reshape(n, m).copy()
-        return dict(params=par, labels=labels, counts=counts, status=status[:n * m].reshape(n, m), n_used=n_used,
-                    rounds=rounds[:n].astype(np.int64), converged=conv[:n].astype(bool), offsets=offs)
+        f = np.ctypeslib.as_array(fits)[:n * m].reshape(n, m)
+        return dict(params=par, labels=labels, counts=counts, status=status[:n * m].reshape(n, m),
+                    n_used=f["n_used"].copy(), rounds=rounds[:n].astype(np.int64), converged=conv[:n].astype(bool),
+                    offsets=offs), f
+
+    def refine_lm_grouped(self, groups, n_groups, params, n_models=None, max_rounds=8, labels_out=None):
+        """refine_grouped for the sphere with LS_GEOMETRIC, which refine_grouped refuses (lsqr_refine_lm_grouped): every
+        group runs refine_lm's loop on its own records and rows, bit for bit as refine_lm runs it on those records
+        alone -- the refit of a model is a Levenberg-Marquardt run from the algebraic fit of its records, all models
+        of all groups still going evaluated together on the device.  A model whose run does not end with lm_info in
+        1..4 (or that has fewer than K records, or no algebraic start) keeps the row it had before the round.
+        Arguments as for refine_grouped.  Any other model raises LsqrError(ERR_INVALID).
+        -> refine_grouped's dict, and per (group, model) for the group's last refit round lm_info, lm_nfev, cost and
+        stall, each shaped (n_groups, max_models); zeros where no run started."""
+        out, f = self._refine_grouped(self._lib.lsqr_refine_lm_grouped, groups, n_groups, params, n_models, max_rounds,
+                                      labels_out)
+        out.update(lm_info=f["lm_info"].copy(), lm_nfev=f["lm_nfev"].copy(), cost=f["cost"].copy(),
+                   stall=f["reserved"].copy())
+        return out
 
     def _many_records(self, problems):
         if self.cfg is None:

@@ -33,6 +33,10 @@
 // Groups that run nothing (no records, or n_models[g] == 0) have no workgroups and start stopped.  Their records, and
 // the records in no group, get label -1 and residual +infinity: the packed buffers are filled with those first when such
 // a group has records, and the scatter writes them for the records past the grouped total.
+//
+// lsqr_refine_lm_grouped (assign_lm_grouped.h, the geometric sphere) runs this file's loop, assign_grouped_run<M, true>:
+// the pass also stores every workgroup's presence word, the solve writes into a side array of start rows, and the
+// refit is a grouped LM stage.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -55,13 +59,15 @@ struct AsgGrpTab {  // the call's per-group tables, on the device
 
 // data: the packed records, `stride` doubles apart; wgs: (group, chunk) per workgroup; rows: n_groups * max_models scan
 // rows; labels / residuals (nullable) / old (nullable): packed order; changed: one word per group; counts: max_models
-// words per group, zero for every group still going; partials (WITH_MOMENTS): [gbase[g] + q * nm[g] + m][AccLs<M>::N]
+// words per group, zero for every group still going; partials (WITH_MOMENTS): [gbase[g] + q * nm[g] + m][AccLs<M>::N];
+// presence (WITH_MOMENTS, nullable): one word per workgroup (the LM stage of assign_lm_grouped.h reads it)
 template <class M, bool WITH_MOMENTS>
 __global__ __launch_bounds__(kBlock, (kAssignPassWaves<M, WITH_MOMENTS>)) void k_asg_grp_pass(
     const double *__restrict__ data, size_t stride, const uint2 *__restrict__ wgs, AsgGrpTab T,
     const double *__restrict__ rows, int max_models, int org_off, ModelConsts mc, int32_t *__restrict__ labels,
     double *__restrict__ residuals, const int32_t *__restrict__ old, unsigned long long *__restrict__ changed,
-    unsigned long long *__restrict__ counts, double *__restrict__ partials) {
+    unsigned long long *__restrict__ counts, double *__restrict__ partials,
+    unsigned long long *__restrict__ presence) {
   const uint2 wg = wgs[blockIdx.x];  // workgroup-uniform: the group, its chunk
   const uint32_t g = wg.x;
   if (T.state[g]) return;
@@ -71,7 +77,8 @@ __global__ __launch_bounds__(kBlock, (kAssignPassWaves<M, WITH_MOMENTS>)) void k
   assign_pass_chunk<M, WITH_MOMENTS>(data + c0 * stride, stride, left < kAssignChunk ? (uint32_t)left : kAssignChunk,
                                      rows + (size_t)g * max_models * M::SP, n_models, org_off, mc, labels + c0,
                                      residuals ? residuals + c0 : nullptr, old ? old + c0 : nullptr, changed + g,
-                                     counts + (size_t)g * max_models, partials, nullptr);
+                                     counts + (size_t)g * max_models, partials,
+                                     presence ? presence + blockIdx.x : nullptr);
 }
 
 // after pass r (last: r == max_rounds): every group still going converges, stops, or goes on with a zeroed
@@ -102,13 +109,16 @@ __global__ __launch_bounds__(kBlock) void k_asg_grp_decide(uint32_t n_groups, un
 }
 
 // one wave per (group, model) pair of the groups that had work.  counts[g][m] is read as the records behind this
-// refit attempt and zeroed for the group's next pass; used / okf: what k_assign_solve leaves in ASG_USED / ASG_OK
-template <class M>
+// refit attempt and zeroed for the group's next pass; used / okf: what k_assign_solve leaves in ASG_USED / ASG_OK;
+// START (start: n_groups * max_models rows, else not read): as k_assign_solve's `start` -- `rows` is only read, and row
+// e of `start` gets what `rows` would have got.  A template flag and not a nullable pointer: the pointer test moved the
+// registers of 18 of the 22 instantiations, and the algebraic path keeps its code
+template <class M, bool START = false>
 __global__ __launch_bounds__(64) void k_asg_grp_solve(const uint2 *__restrict__ pairs, AsgGrpTab T,
                                                       const double *__restrict__ partials, int max_models, int org_off,
                                                       ModelConsts mc, double *rows, unsigned long long *counts,
                                                       unsigned long long *__restrict__ used,
-                                                      unsigned long long *__restrict__ okf) {
+                                                      unsigned long long *__restrict__ okf, double *start) {
   constexpr int N = M::NMOM, U = 16;
   static_assert(N <= 64, "one lane per moment");
   __shared__ double mom[MOM_MAX];
@@ -140,7 +150,12 @@ __global__ __launch_bounds__(64) void k_asg_grp_solve(const uint2 *__restrict__ 
   const unsigned long long cnt = counts[e];
   counts[e] = 0;
   used[e] = cnt;
-  okf[e] = assign_refit<M>(mom, rows + e * M::SP, cnt, org_off, mc, ws, &so) ? 1 : 0;
+  double *row_m = rows + e * M::SP;
+  if constexpr (START) {
+    for (int j = 0; j < (int)M::SP; j++) start[e * M::SP + j] = row_m[j];
+    row_m = start + e * M::SP;
+  }
+  okf[e] = assign_refit<M>(mom, row_m, cnt, org_off, mc, ws, &so) ? 1 : 0;
 }
 
 __global__ __launch_bounds__(kBlock) void k_asg_grp_fill(double *__restrict__ p, uint64_t n, double v) {
@@ -156,6 +171,12 @@ struct AssignGrpBufs {  // owned by the context, grown on demand (the sort and t
   DevBuf<uint32_t> d_state;
   DevBuf<uint2> d_wgs, d_pairs;
   PinBuf<char> h_pin;
+  // the LM stage of lsqr_refine_lm_grouped (assign_lm_grouped.h)
+  DevBuf<double> d_start, d_lm_partials;
+  DevBuf<unsigned long long> d_presence, d_lm_mask;  // one word per (group, chunk); per group, the models whose LM goes on
+  DevBuf<uint32_t> d_lm_live;                         // their number over all groups
+  DevBuf<LmState> d_lm_state;                         // per (group, model)
+  DevBuf<AssignLmOut> d_lm_out;
 };
 
 struct AssignGrpJob {
@@ -170,6 +191,7 @@ struct AssignGrpJob {
   size_t n_groups = 0, max_models = 0, max_rounds = 0;
   int on_device = 0;
   bool refine = false;
+  bool lm = false;  // lsqr_refine_lm_grouped
   double *params = nullptr;  // host, n_groups * max_models rows of M::P: read, and written where a refit ran
   const size_t *n_models = nullptr;
   int32_t *labels_out = nullptr;
@@ -184,8 +206,29 @@ struct AssignGrpJob {
 
 inline size_t asg_grp_up8(size_t b) { return (b + 7) & ~(size_t)7; }
 
-// Both calls.  Returns after the stream has drained; the outputs are written only then.
-template <class M>
+// what the LM stage of a round needs of the call's layout
+struct AsgGrpLmView {
+  AsgGrpTab T;
+  const uint2 *wgs, *pairs;
+  size_t n_wgs, n_pairs, n_groups, max_models;
+  uint64_t pblocks;    // (chunk, model) blocks of all groups
+  const double *data;  // the packed records
+  size_t stride;
+  double *rows;
+  unsigned long long *counts, *used, *ok;
+  uint32_t *h_live;  // pinned: the live counter's copy
+};
+
+// the LM stage of lsqr_refine_lm_grouped's round (assign_lm_grouped.h): its buffers, and the refit of every model of
+// every group still going from the moments and the presence words the pass has just left, under the packed labels
+// `lab`; it leaves the new rows in B.d_rows
+template <class M> int assign_lm_grp_reserve(AssignGrpJob &J, const AsgGrpLmView &V);
+template <class M> int assign_lm_grp_run(AssignGrpJob &J, const AsgGrpLmView &V, const int32_t *lab);
+
+// All three calls.  Returns after the stream has drained; the outputs are written only then.
+// LM (lsqr_refine_lm_grouped, the geometric sphere): the same loop; the refit is assign_lm_grp_run, and the fits carry
+// its record.
+template <class M, bool LM = false>
 int assign_grouped_run(AssignGrpJob &J) {
   typedef unsigned long long ull;
   AssignGrpBufs &B = *J.B;
@@ -231,7 +274,8 @@ int assign_grouped_run(AssignGrpJob &J) {
                u_pairs = u_wgs + sizeof(uint2) * NW, u_nm = u_pairs + sizeof(uint2) * NP,
                u_state = u_nm + asg_grp_up8(sizeof(int32_t) * NG), v_going = u_state + asg_grp_up8(sizeof(uint32_t) * NG),
                v_rows = v_going + sizeof(ull), v_cnt = v_rows + sizeof(double) * NR * M::SP,
-               v_conv = v_cnt + sizeof(ull) * c_words, pin_bytes = v_conv + asg_grp_up8(sizeof(uint32_t) * NG);
+               v_conv = v_cnt + sizeof(ull) * c_words, v_live = v_conv + asg_grp_up8(sizeof(uint32_t) * NG),
+               v_lm = v_live + (LM ? sizeof(ull) : 0), pin_bytes = v_lm + (LM ? sizeof(AssignLmOut) * NR : 0);
   MANYCHK(many_grow_pinned(B.h_pin, pin_bytes));  // (every earlier call ended in a synchronisation)
   char *pin = B.h_pin.get();
   double *h_par = (double *)(pin + u_par);
@@ -241,6 +285,7 @@ int assign_grouped_run(AssignGrpJob &J) {
   const double *h_rows = (const double *)(pin + v_rows);
   const ull *h_cnt = (const ull *)(pin + v_cnt);
   const uint32_t *h_conv = (const uint32_t *)(pin + v_conv);
+  [[maybe_unused]] const AssignLmOut *h_lm = (const AssignLmOut *)(pin + v_lm);
   for (size_t g = 0; g < NG; g++) {
     const size_t nm = J.n_models[g];
     h_nm[g] = (int32_t)nm;
@@ -293,6 +338,13 @@ int assign_grouped_run(AssignGrpJob &J) {
   }
 
   const AsgGrpTab T{P.d_grp_off, B.d_gbase, B.d_nm, d_state};
+  [[maybe_unused]] const AsgGrpLmView V{T,        B.d_wgs, B.d_pairs, NW,       NP,     NG,   MM, pblocks,
+                                        P.d_data, W,       B.d_rows,  d_counts, d_used, d_ok, (uint32_t *)(pin + v_live)};
+  if constexpr (LM)
+    if (moments) {
+      const int st = assign_lm_grp_reserve<M>(J, V);
+      if (st != LSQR_OK) return st;
+    }
   int cur = 0;
   size_t r = 0;
   while (NW) {
@@ -302,10 +354,12 @@ int assign_grouped_run(AssignGrpJob &J) {
     const int32_t *old = r > 0 ? B.d_labels[cur ^ 1].get() : nullptr;
     if (last)
       hipLaunchKernelGGL((k_asg_grp_pass<M, false>), dim3((unsigned)NW), dim3(kBlock), 0, stream, P.d_data, W,
-                         B.d_wgs, T, B.d_rows, (int)MM, org_off, J.mc, lab, res, old, d_changed, d_counts, nullptr);
+                         B.d_wgs, T, B.d_rows, (int)MM, org_off, J.mc, lab, res, old, d_changed, d_counts, nullptr,
+                         nullptr);
     else
       hipLaunchKernelGGL((k_asg_grp_pass<M, true>), dim3((unsigned)NW), dim3(kBlock), 0, stream, P.d_data, W, B.d_wgs,
-                         T, B.d_rows, (int)MM, org_off, J.mc, lab, res, old, d_changed, d_counts, B.d_partials);
+                         T, B.d_rows, (int)MM, org_off, J.mc, lab, res, old, d_changed, d_counts, B.d_partials,
+                         LM ? B.d_presence.get() : nullptr);
     MANYCHK(hipGetLastError());
     if (last) break;  // every group still going stops here: nothing to read
     MANYCHK(hipMemsetAsync(d_going, 0, sizeof(ull), stream));
@@ -315,9 +369,14 @@ int assign_grouped_run(AssignGrpJob &J) {
     MANYCHK(hipMemcpyAsync(pin + v_going, d_going, sizeof(ull), hipMemcpyDeviceToHost, stream));
     MANYCHK(hipStreamSynchronize(stream));  // the one word of the round
     if (*h_going == 0) break;
-    hipLaunchKernelGGL((k_asg_grp_solve<M>), dim3((unsigned)NP), dim3(64), 0, stream, B.d_pairs, T, B.d_partials,
-                       (int)MM, org_off, J.mc, B.d_rows, d_counts, d_used, d_ok);
-    MANYCHK(hipGetLastError());
+    if constexpr (LM) {
+      const int st = assign_lm_grp_run<M>(J, V, lab);
+      if (st != LSQR_OK) return st;
+    } else {
+      hipLaunchKernelGGL((k_asg_grp_solve<M>), dim3((unsigned)NP), dim3(64), 0, stream, B.d_pairs, T, B.d_partials,
+                         (int)MM, org_off, J.mc, B.d_rows, d_counts, d_used, d_ok, nullptr);
+      MANYCHK(hipGetLastError());
+    }
     r++;
     cur ^= 1;
   }
@@ -347,6 +406,9 @@ int assign_grouped_run(AssignGrpJob &J) {
   if (r > 0) MANYCHK(hipMemcpyAsync(pin + v_rows, B.d_rows, sizeof(double) * NR * M::SP, hipMemcpyDeviceToHost, stream));
   MANYCHK(hipMemcpyAsync(pin + v_cnt, B.d_cnt, sizeof(ull) * c_words, hipMemcpyDeviceToHost, stream));
   MANYCHK(hipMemcpyAsync(pin + v_conv, d_conv, sizeof(uint32_t) * NG, hipMemcpyDeviceToHost, stream));
+  if constexpr (LM)
+    if (r > 0)
+      MANYCHK(hipMemcpyAsync(pin + v_lm, B.d_lm_out, sizeof(AssignLmOut) * NR, hipMemcpyDeviceToHost, stream));
   MANYCHK(hipStreamSynchronize(stream));
 
   for (size_t g = 0; g < NG; g++) {
@@ -369,6 +431,13 @@ int assign_grouped_run(AssignGrpJob &J) {
       const size_t e = g * MM + m;
       if (m < nm) {
         assign_fit_out<M>(rg, h_cnt[c_ok + e], h_cnt[c_used + e], &J.status_out[e], &J.fits[e]);
+        if constexpr (LM)
+          if (rg > 0) {
+            J.fits[e].lm_info = h_lm[e].lm_info;
+            J.fits[e].lm_nfev = h_lm[e].lm_nfev;
+            J.fits[e].reserved = h_lm[e].stall;
+            J.fits[e].cost = h_lm[e].cost;
+          }
       } else {
         J.status_out[e] = LSQR_ERR_STATE;  // model not there
         memset(&J.fits[e], 0, sizeof(lsqr_fit_info));
@@ -381,5 +450,3 @@ int assign_grouped_run(AssignGrpJob &J) {
 #endif  // __HIPCC__
 
 }  // namespace lsqr
-
-#undef MANYCHK

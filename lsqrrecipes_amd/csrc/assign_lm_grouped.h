@@ -1,0 +1,219 @@
+// assign_lm_grouped.h -- lsqr_refine_lm_grouped: lsqr_refine_grouped's loop (assign_grouped.h: assign_grouped_run) for
+// the sphere with LSQR_LS_GEOMETRIC.  Group g is decided bit for bit as lsqr_refine_lm (assign_lm.h) decides it on a
+// fresh context that holds the group's records alone.  The refit of a round is the algebraic refit of every group still
+// going, kept aside as the START, and then one Levenberg-Marquardt run per (group, model), all of them in lock-step
+// evaluation rounds over the packed records.
+//
+//   k_asg_grp_pass<M, true>   as in lsqr_refine_grouped; it also stores the presence word of every (group, chunk)
+//   k_asg_grp_solve<M, true>  as in lsqr_refine_grouped, but into the start rows (its START flag): the rows stay
+//   k_asg_grp_lm_init         one wave per group still going, one lane per model: lm_init from its start row where the
+//                             algebraic refit gave one; the group's live mask; the live models of all groups added into
+//                             ONE counter; ok[g][m] cleared (the LM decides it)
+//   per evaluation:
+//   k_asg_grp_lm_pass         one workgroup per (group, chunk): todo = presence[wg] & mask[g]; a workgroup whose group
+//                             has stopped, or whose chunk holds no record of a live model, returns at once; any other
+//                             runs assign_lm_pass_chunk (assign_lm.h) on the group's packed chunk with the group's
+//                             LmState block -> partials [gbase[g] + q * nm[g] + m][M::NMOM_LM]
+//   k_asg_grp_lm_step         one wave per (group, model) whose bit is live: the blocks of the group's chunks summed in
+//                             chunk order by one lane per moment (sixteen loads in flight, added in order, as
+//                             k_asg_grp_solve), LmState staged in LDS, lane 0 runs lm_advance.  A model that finishes
+//                             writes its AssignLmOut and, with info in 1..4, its new scan row by assign_make_row and
+//                             ok[g][m]; then it leaves the group's mask and the live counter, which the host reads (4
+//                             bytes) after every evaluation, for all groups together.
+//
+// Why the bits are lsqr_refine_lm's.  The pass body is the same function on the same records at the same positions
+// inside their chunk (chunk q of the group is chunk q of the fresh context), with the same trial point.  The step's sum
+// starts from 0.0 and adds the chunks' blocks one by one in chunk order: that is the order of assign_sum_chunks, which
+// k_assign_lm_step uses -- tiles through LDS there, sixteen registers here, the additions the same.  lm_init, lm_advance,
+// M::lm_finalize and assign_make_row are the same code.  Nothing is summed with a floating-point atomic; the one
+// counter that all groups share is an integer.  So a group's results depend on its own records and rows alone.
+//
+// A model absent from a chunk has zeros there: the LM partials are cleared once per refit round (the labels, and so the
+// presence words, are fixed for the round), and the pass writes only the blocks of models that are present and live.
+// A stopped group keeps its rows, its ok / used words and its AssignLmOut as its last refit left them.
+//
+// Budget: LDS of the pass 2 x 4 x NMOM_LM doubles (3.4 KiB at D = 8); of the step the moment block and LmState (2.3
+// KiB).  Registers of the pass: assign_lm_pass_chunk's, plus the workgroup's table entries in
+// scalar registers.  See DESIGN.md section 14.3.
+//
+// Included after assign_lm.h and assign_grouped.h; assign_grouped_run<M, true> calls assign_lm_grp_reserve and
+// assign_lm_grp_run.
+#pragma once
+#include "assign_grouped.h"
+#include "assign_lm.h"
+
+namespace lsqr {
+
+#if defined(__HIPCC__)
+// group blockIdx.x.  start: the start rows k_asg_grp_solve left; okf[g][m]: its answer, cleared here; *live (zeroed by
+// the caller) += the models that start
+template <class M>
+__global__ __launch_bounds__(64) void k_asg_grp_lm_init(AsgGrpTab T, const double *__restrict__ start, int max_models,
+                                                        int n, double ftol, double xtol, double gtol, int maxfev,
+                                                        unsigned long long *__restrict__ okf,
+                                                        LmState *__restrict__ st, AssignLmOut *__restrict__ out,
+                                                        unsigned long long *__restrict__ mask,
+                                                        uint32_t *__restrict__ live) {
+  const uint32_t g = blockIdx.x;
+  if (T.state[g]) return;
+  const int m = threadIdx.x;
+  const bool there = m < T.nm[g];
+  const size_t e = (size_t)g * max_models + m;  // (read only where the row is there)
+  const bool go = there && okf[e] != 0;
+  if (there) {
+    okf[e] = 0;
+    out[e] = AssignLmOut{0, 0, 0, 0, 0.0};
+  }
+  if (go) lm_init(st[e], n, start + e * M::SP, ftol, xtol, gtol, maxfev, 100.0);
+  const unsigned long long all = __ballot(go);
+  if (m == 0) {
+    mask[g] = all;
+    if (all) atomicAdd(live, (uint32_t)__popcll(all));
+  }
+}
+
+// workgroup blockIdx.x = (group, chunk) wgs[blockIdx.x].  data, labels: packed order; presence: one word per
+// workgroup; mask: one word per group; st: [group][max_models]; partials: cleared at the start of the refit round
+template <class M>
+__global__ __launch_bounds__(kBlock) void k_asg_grp_lm_pass(const double *__restrict__ data, size_t stride,
+                                                            const uint2 *__restrict__ wgs, AsgGrpTab T,
+                                                            const int32_t *__restrict__ labels,
+                                                            const unsigned long long *__restrict__ presence,
+                                                            const unsigned long long *__restrict__ mask,
+                                                            const LmState *__restrict__ st, int max_models,
+                                                            ModelConsts mc, double *__restrict__ partials) {
+  const uint2 wg = wgs[blockIdx.x];  // workgroup-uniform: the group, its chunk
+  const uint32_t g = wg.x;
+  if (T.state[g]) return;
+  const unsigned long long t = presence[blockIdx.x] & mask[g];  // (uniform addresses)
+  const unsigned long long todo = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(t >> 32)) << 32) |
+                                  __builtin_amdgcn_readfirstlane((uint32_t)t);
+  if (!todo) return;
+  const int n_models = T.nm[g];
+  const uint64_t c0 = T.offsets[g] + (uint64_t)wg.y * kAssignChunk, left = T.offsets[g + 1] - c0;
+  assign_lm_pass_chunk<M>(data + c0 * stride, stride, left < kAssignChunk ? (uint32_t)left : kAssignChunk, labels + c0,
+                          todo, st + (size_t)g * max_models, mc,
+                          partials + (T.gbase[g] + (uint64_t)wg.y * n_models) * M::NMOM_LM);
+}
+
+// one wave per (group, model) pair: the evaluation's block of a model that is still live, then lm_advance
+template <class M>
+__global__ __launch_bounds__(64) void k_asg_grp_lm_step(const uint2 *__restrict__ pairs, AsgGrpTab T,
+                                                        const double *__restrict__ partials, int max_models,
+                                                        ModelConsts mc, LmState *__restrict__ st,
+                                                        double *__restrict__ rows, unsigned long long *__restrict__ okf,
+                                                        AssignLmOut *__restrict__ out, unsigned long long *mask,
+                                                        uint32_t *live) {
+  constexpr int N = M::NMOM_LM, U = 16;
+  constexpr int NW = (int)(sizeof(LmState) / sizeof(int));
+  static_assert(N <= 64, "one lane per moment");
+  __shared__ double mom[LM_MOM_MAX];
+  __shared__ LmState S;
+  const uint2 pr = pairs[blockIdx.x];
+  const uint32_t g = pr.x, m = pr.y;
+  if (T.state[g]) return;
+  if (!((mask[g] >> m) & 1ull)) return;  // finished, or never started (uniform over the wave)
+  const int k = threadIdx.x;
+  const size_t e = (size_t)g * max_models + m;
+  if (k < N) {
+    const uint32_t chunks = (uint32_t)((T.offsets[g + 1] - T.offsets[g] + kAssignChunk - 1) / kAssignChunk);
+    const size_t qs = (size_t)T.nm[g] * N;  // from one chunk's block of model m to the next chunk's
+    const double *src = partials + (T.gbase[g] + m) * N + k;
+    double t = 0.0;
+    uint32_t q = 0;
+    for (; q + U <= chunks; q += U) {  // U loads in flight, added in chunk order
+      double v[U];
+#pragma unroll
+      for (int u = 0; u < U; u++) v[u] = src[(size_t)(q + u) * qs];
+#pragma unroll
+      for (int u = 0; u < U; u++) t += v[u];
+    }
+    for (; q < chunks; q++) t += src[(size_t)q * qs];
+    mom[k] = t;
+  }
+  {
+    const int *src = (const int *)&st[e];
+    int *dst = (int *)&S;
+    for (int i = k; i < NW; i += 64) dst[i] = src[i];
+  }
+  __syncthreads();
+  if (k == 0 && !lm_advance(S, mom)) {
+    out[e] = AssignLmOut{S.info, S.nfev, S.stall, 0, S.fnorm * S.fnorm};
+    if (S.info >= 1 && S.info <= 4) {  // vnl_levenberg_marquardt::minimize -> true
+      double p[LM_NMAX], row[M::SP];
+      M::lm_finalize(S.x, p);
+      assign_make_row<M>(p, mc, row);
+      for (int j = 0; j < (int)M::SP; j++) rows[e * M::SP + j] = row[j];
+      okf[e] = 1;
+    }
+    atomicAnd(mask + g, ~(1ull << m));
+    atomicSub(live, 1u);
+  }
+  __syncthreads();
+  {
+    const int *src = (const int *)&S;
+    int *dst = (int *)&st[e];
+    for (int i = k; i < NW; i += 64) dst[i] = src[i];
+  }
+}
+
+// ---- host side -----------------------------------------------------------------------------------------------------
+template <class M>
+int assign_lm_grp_reserve(AssignGrpJob &J, const AsgGrpLmView &V) {
+  AssignGrpBufs &B = *J.B;
+  const size_t NR = V.n_groups * V.max_models;
+  MANYCHK(many_grow(B.d_start, NR * M::SP));
+  MANYCHK(many_grow(B.d_presence, V.n_wgs));
+  MANYCHK(many_grow(B.d_lm_partials, (size_t)V.pblocks * M::NMOM_LM));
+  MANYCHK(many_grow(B.d_lm_mask, V.n_groups));
+  MANYCHK(many_grow(B.d_lm_live, 1));
+  MANYCHK(many_grow(B.d_lm_state, NR));
+  MANYCHK(many_grow(B.d_lm_out, NR));
+  return LSQR_OK;
+}
+
+// The refit of one round, for every group still going.  The pass has left the moments of the labels `lab` in
+// B.d_partials and the presence words in B.d_presence.  Per evaluation: one pass, one step, one 4-byte read of the live
+// counter.  Every lm_advance call consumes one evaluation and stops at maxfev, so maxfev evaluations finish every model
+// (assign_lm_run's bound).
+template <class M>
+int assign_lm_grp_run(AssignGrpJob &J, const AsgGrpLmView &V, const int32_t *lab) {
+  AssignGrpBufs &B = *J.B;
+  hipStream_t stream = J.pack.stream;
+  const int MM = (int)V.max_models, org_off = fit_origin_offset<M>(J.cfg);
+  int n = 0, maxfev = 0;
+  double ftol = 0, xtol = 0, gtol = 0;
+  lm_settings(J.cfg, &n, &ftol, &xtol, &gtol, &maxfev);
+  hipLaunchKernelGGL((k_asg_grp_solve<M, true>), dim3((unsigned)V.n_pairs), dim3(64), 0, stream, V.pairs, V.T,
+                     B.d_partials.get(), MM, org_off, J.mc, V.rows, V.counts, V.used, V.ok, B.d_start.get());
+  MANYCHK(hipGetLastError());
+  MANYCHK(hipMemsetAsync(B.d_lm_live, 0, sizeof(uint32_t), stream));
+  hipLaunchKernelGGL((k_asg_grp_lm_init<M>), dim3((unsigned)V.n_groups), dim3(64), 0, stream, V.T, B.d_start.get(), MM,
+                     n, ftol, xtol, gtol, maxfev, V.ok, B.d_lm_state.get(), B.d_lm_out.get(), B.d_lm_mask.get(),
+                     B.d_lm_live.get());
+  MANYCHK(hipGetLastError());
+  MANYCHK(hipMemsetAsync(B.d_lm_partials, 0, sizeof(double) * (size_t)V.pblocks * M::NMOM_LM, stream));
+  for (int round = 0;; round++) {
+    if (round > maxfev) {
+      snprintf(J.err, sizeof J.err, "LM stage: %u models still live after %d evaluations", *V.h_live, round);
+      return LSQR_ERR_HIP;
+    }
+    hipLaunchKernelGGL((k_asg_grp_lm_pass<M>), dim3((unsigned)V.n_wgs), dim3(kBlock), 0, stream, V.data, V.stride,
+                       V.wgs, V.T, lab, B.d_presence.get(), B.d_lm_mask.get(), B.d_lm_state.get(), MM, J.mc,
+                       B.d_lm_partials.get());
+    MANYCHK(hipGetLastError());
+    hipLaunchKernelGGL((k_asg_grp_lm_step<M>), dim3((unsigned)V.n_pairs), dim3(64), 0, stream, V.pairs, V.T,
+                       B.d_lm_partials.get(), MM, J.mc, B.d_lm_state.get(), V.rows, V.ok, B.d_lm_out.get(),
+                       B.d_lm_mask.get(), B.d_lm_live.get());
+    MANYCHK(hipGetLastError());
+    MANYCHK(hipMemcpyAsync(V.h_live, B.d_lm_live, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    MANYCHK(hipStreamSynchronize(stream));
+    if (*V.h_live == 0) break;
+  }
+  return LSQR_OK;
+}
+#endif  // __HIPCC__
+
+}  // namespace lsqr
+
+#undef MANYCHK

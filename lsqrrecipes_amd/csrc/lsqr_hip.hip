@@ -48,6 +48,7 @@
 #include "assign.h"
 #include "assign_lm.h"
 #include "assign_grouped.h"
+#include "assign_lm_grouped.h"
 
 #include <condition_variable>
 #include <mutex>
@@ -314,7 +315,8 @@ struct lsqr_ctx {
   PinBuf<char> h_batch;  // pinned results of a lsqr_ransac batch (grown on demand)
   std::unique_ptr<ManyBufs> many;  // lsqr_ransac_many's buffers (its own: the context's upload is not touched)
   std::unique_ptr<AssignBufs> assign;  // lsqr_assign / lsqr_refine / lsqr_refine_lm (assign.h, assign_lm.h)
-  std::unique_ptr<AssignGrpBufs> assign_grp;  // lsqr_assign_grouped / lsqr_refine_grouped (assign_grouped.h)
+  // lsqr_assign_grouped / lsqr_refine_grouped / lsqr_refine_lm_grouped (assign_grouped.h, assign_lm_grouped.h)
+  std::unique_ptr<AssignGrpBufs> assign_grp;
   // lsqr_ransac_sequential (sequential.h): the survivors of a round go from the current buffer into the OTHER of two
   // owned buffers (never into the caller's upload), their upload indices beside them; labels in upload order
   DevBuf<double> d_seq_rec[2];
@@ -4307,7 +4309,7 @@ int lsqr_ransac_grouped_sequential(lsqr_ctx *c, const int32_t *groups, size_t n_
 }
 
 // ---- nearest-model assignment and refit (assign.h, assign_grouped.h) -------------------------------------------------
-// What the five entry points share.  The checks, in the contract's order: the context; the model gate (AssignGate:
+// What the six entry points share.  The checks, in the contract's order: the context; the model gate (AssignGate:
 // what the entry point does with the geometric sphere, whose fit is iterative); count == 0
 // (n_models, or n_groups of the grouped calls) is LSQR_OK with every output untouched; more than 64 models; own(), the
 // entry point's own arguments; the context holds a model and records; their count.  Then run(tag), the run function
@@ -4317,7 +4319,7 @@ extern "C++" {
 enum AssignGate {
   ASSIGN_GATE_ANY,     // the assignments: every model of assign_model_ok
   ASSIGN_GATE_CLOSED,  // the refits in closed form: not the geometric sphere
-  ASSIGN_GATE_LM       // lsqr_refine_lm: the geometric sphere alone
+  ASSIGN_GATE_LM       // lsqr_refine_lm, lsqr_refine_lm_grouped: the geometric sphere alone
 };
 template <class Own, class Run>
 static int assign_frame(lsqr_ctx *c, const char *fn, AssignGate gate, const char *takes, size_t count,
@@ -4424,12 +4426,14 @@ int lsqr_refine_lm(lsqr_ctx *c, double *params_inout, size_t n_models, size_t ma
                      counts_out, fits, status_out, rounds_out, converged_out);
 }
 
-// lsqr_assign_grouped and lsqr_refine_grouped.  The sort and the packed copy live in the batched calls' buffers
-// (lsqr_ctx::many), as lsqr_ransac_grouped's do.
+// lsqr_assign_grouped, lsqr_refine_grouped and lsqr_refine_lm_grouped.  The sort and the packed copy live in the batched
+// calls' buffers (lsqr_ctx::many), as lsqr_ransac_grouped's do.
 extern "C++" {
 static int assign_grouped_call(lsqr_ctx *c, const char *fn, bool args, AssignGrpJob &J) {
   return assign_frame(
-      c, fn, J.refine ? ASSIGN_GATE_CLOSED : ASSIGN_GATE_ANY, "lsqr_assign_grouped", J.n_groups, J.max_models, J.err,
+      c, fn, J.lm ? ASSIGN_GATE_LM : J.refine ? ASSIGN_GATE_CLOSED : ASSIGN_GATE_ANY,
+      J.lm ? "lsqr_refine_grouped" : J.refine ? "lsqr_refine_lm_grouped" : "lsqr_assign_grouped", J.n_groups,
+      J.max_models, J.err,
       [&]() -> int {
         if (J.n_groups > 0x7FFFFFFFull) return fail(c, LSQR_ERR_INVALID, "%s: more than 2^31 - 1 groups", fn);
         if (!args || !J.groups || !J.params || !J.n_models) return fail(c, LSQR_ERR_INVALID, "%s: null argument", fn);
@@ -4449,7 +4453,11 @@ static int assign_grouped_call(lsqr_ctx *c, const char *fn, bool args, AssignGrp
         J.stride = c->stride;
         J.n = c->n;
         J.B = c->assign_grp.get();
-        return assign_grouped_run<typename decltype(tag)::type>(J);
+        typedef typename decltype(tag)::type M;
+        if constexpr (requires { M::NMOM_LM; }) {  // (the sphere)
+          if (J.lm) return assign_grouped_run<M, true>(J);
+        }
+        return assign_grouped_run<M>(J);
       });
 }
 }  // extern "C++"
@@ -4493,6 +4501,30 @@ int lsqr_refine_grouped(lsqr_ctx *c, const int32_t *groups, size_t n_groups, int
   J.rounds_out = rounds_out;
   J.converged_out = converged_out;
   return assign_grouped_call(c, "lsqr_refine_grouped", fits && status_out && rounds_out && converged_out, J);
+}
+
+int lsqr_refine_lm_grouped(lsqr_ctx *c, const int32_t *groups, size_t n_groups, int on_device, double *params_inout,
+                           const size_t *n_models, size_t max_models, size_t max_rounds, int32_t *labels_out,
+                           uint64_t *counts_out, uint64_t *offsets_out, lsqr_fit_info *fits, int32_t *status_out,
+                           size_t *rounds_out, int32_t *converged_out) {
+  AssignGrpJob J;
+  J.refine = true;
+  J.lm = true;
+  J.groups = groups;
+  J.n_groups = n_groups;
+  J.on_device = on_device ? 1 : 0;
+  J.params = params_inout;
+  J.n_models = n_models;
+  J.max_models = max_models;
+  J.max_rounds = max_rounds;
+  J.labels_out = labels_out;
+  J.counts_out = counts_out;
+  J.offsets_out = offsets_out;
+  J.fits = fits;
+  J.status_out = status_out;
+  J.rounds_out = rounds_out;
+  J.converged_out = converged_out;
+  return assign_grouped_call(c, "lsqr_refine_lm_grouped", fits && status_out && rounds_out && converged_out, J);
 }
 
 // C(n,k) and the rank-th k-subset in the exhaustive overload's order (comb.h); host only

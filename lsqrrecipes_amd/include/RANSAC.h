@@ -512,6 +512,44 @@ class RANSAC {
     return rounds;
   }
 
+  // refineModelsGrouped for the sphere estimator with the geometric least-squares fit (its default), on the device: ONE
+  // call (lsqr_refine_lm_grouped).  Arguments and return value are refineModelsGrouped's; every group is decided as
+  // refineModelsLM decides it on the records of the group alone.  Any other estimator throws std::invalid_argument:
+  // refineModelsGrouped takes it.
+  static std::vector<size_t> refineModelsLMGrouped(std::vector<std::vector<std::vector<S> > > &models,
+                                                   ParametersEstimator<T, S> *paramEstimator, ResidentData<T> &data,
+                                                   const std::vector<int> &groups, size_t nGroups, size_t maxRounds,
+                                                   std::vector<int> &labels, std::vector<bool> *converged = NULL) {
+    lsqr_model_cfg cfg;
+    groupedArgs(models.size(), paramEstimator, data, groups, nGroups);
+    if (!paramEstimator->deviceModel(cfg) || cfg.model != LSQR_MODEL_SPHERE || cfg.ls_type != LSQR_LS_GEOMETRIC)
+      throw std::invalid_argument("lsqrRecipes::RANSAC: refineModelsLMGrouped takes the geometric sphere only");
+    const size_t n = nGroups, N = data.size();
+    labels.assign(N, -1);
+    std::vector<size_t> rounds(n, 0);
+    if (converged) converged->assign(n, false);
+    if (n == 0 || N == 0) return rounds;
+    size_t maxModels = 0;
+    std::vector<size_t> nModels;
+    std::vector<double> par = packGroupedModels(models, cfg, maxModels, nModels);
+    if (maxModels == 0) return rounds;
+    const size_t P = (size_t)lsqr_num_params(&cfg);
+    std::vector<int32_t> glab(groups.begin(), groups.end()), lab(N), status(n * maxModels), conv(n, 0);
+    std::vector<lsqr_fit_info> fits(n * maxModels);
+    lsqr_ctx *ctx = data.attach(cfg);
+    data.check(lsqr_refine_lm_grouped(ctx, &glab[0], n, 0, &par[0], &nModels[0], maxModels, maxRounds, &lab[0], NULL,
+                                      NULL, &fits[0], &status[0], &rounds[0], &conv[0]));
+    for (size_t g = 0; g < n; g++) {
+      for (size_t m = 0; m < nModels[g]; m++) {
+        const double *row = &par[(g * maxModels + m) * P];
+        models[g][m].assign(row, row + P);
+      }
+      if (converged) (*converged)[g] = conv[g] != 0;
+    }
+    labels.assign(lab.begin(), lab.end());
+    return rounds;
+  }
+
   // Sequential RANSAC over many independent problems (not in the reference): problem j is data[j], and
   // computeManySequential(...)[j], parameters[j] and (*labels)[j] equal what computeSequential returns / leaves on
   // data[j] after seed(seed() + j * maxModels) -- round r of problem j walks sampler stream seed() + j * maxModels + r.

@@ -41,7 +41,20 @@ M / 4 times with radii up to +-0.4 apart.  Three kinds alternate in one process:
 above; host_round_ms, the round the entry points allowed before -- Context.assign with its labels to the host, then per
 model set_mask(labels == m) + ls_fit(use_mask=True) on the same geometric context --; and alg_refine_round_ms,
 Context.refine on an algebraic context over the same records and rows, for scale.  lm_nfev: the evaluations per model
-in the last refit round of the R2 call (a round costs about 1 + max(lm_nfev) passes over the records)."""
+in the last refit round of the R2 call (a round costs about 1 + max(lm_nfev) passes over the records).
+
+--grouped --lm: Context.refine_lm_grouped (lsqr_refine_lm_grouped: the geometric sphere with one model set per label).
+Scene: --groups groups (default 3 000) of 300 .. 3 000 records each (--n is not used), every group three spheres of a
+quarter of its records each (sigma 0.1) and a quarter clutter, its start rows the planted ones moved off by up to 0.05
+per centre coordinate, per group its own size; the labels shuffled over the upload and resident on the device; the
+timed calls ask for no labels.  Three kinds alternate: the call at max_rounds 0 (the sort, the gather and one pass),
+at 1 (one refit round more) and at R2; then loop_call_ms, what a caller must do without the call: per group a host
+gather (from one stable sort of the labels, not timed), upload, Context.refine_lm(max_rounds = R2) and the labels
+written back, timed on the first --loop-groups groups and scaled by n_groups / groups timed.
+evaluations: the LM evaluations of refit round 1, max(lm_nfev) over all models of the max_rounds = 1 call;
+round1_ms = t(1) - t(0): that round, with its solve, its init and the assignment pass after it; eval_ms_upper =
+round1_ms / evaluations.  idle_share[j - 1]: the share of the (group, chunk) workgroups of evaluation j of round 1 that
+return at once -- no record of a model still live --, from the labels of the start rows and the models' lm_nfev."""
 import argparse
 import json
 import os
@@ -268,6 +281,99 @@ def grouped_scene(n, n_groups, k, seed=20261020, box=1000.0, sigma=0.4):
     return np.ascontiguousarray(pts[perm]), np.ascontiguousarray(grp[perm]), np.ascontiguousarray(rows)
 
 
+def grouped_sphere_scene(n_groups, k=3, seed=20261022, box=1000.0, sigma=0.1):
+    """-> points (shuffled), labels, start rows (n_groups, k, 4): group g has sizes[g] in 300 .. 3 000 records, k
+    spheres of 1 / (k + 1) of them each, the rest clutter"""
+    g = np.random.default_rng(seed)
+    sizes = g.integers(300, 3001, n_groups)
+    grp = np.repeat(np.arange(n_groups, dtype=np.int32), sizes)
+    first = np.concatenate([[0], np.cumsum(sizes)])[:-1]
+    j = (np.arange(grp.size) - first[grp]) % (k + 1)  # model of the record; k: clutter
+    on = j < k
+    jj = np.minimum(j, k - 1)
+    c = g.uniform(-box / 2, box / 2, (n_groups, k, 3))
+    r = g.uniform(50.0, 300.0, (n_groups, k))
+    u = g.normal(size=(grp.size, 3))
+    u /= np.linalg.norm(u, axis=1, keepdims=True)
+    pts = c[grp, jj] + r[grp, jj][:, None] * u + g.normal(0.0, sigma, (grp.size, 3))
+    pts[~on] = g.uniform(-box, box, (int((~on).sum()), 3))
+    size = g.uniform(0.2, 1.0, (n_groups, 1, 1))
+    rows = np.concatenate([c + 0.05 * size * g.choice([-1.0, 1.0], (n_groups, k, 3)), r[:, :, None] + 0.1 * size], axis=2)
+    perm = g.permutation(grp.size)
+    return np.ascontiguousarray(pts[perm]), np.ascontiguousarray(grp[perm]), np.ascontiguousarray(rows)
+
+
+def grouped_lm_main(a):
+    r2 = a.rounds[1]
+    ms = lambda v: [round(1e3 * float(f(v)), 4) for f in (np.median, np.min, np.max)]
+    n_groups, k = a.groups, 3
+    data, grp, rows = grouped_sphere_scene(n_groups, k)
+    n = data.shape[0]
+    sizes = np.bincount(grp, minlength=n_groups)
+    order = np.argsort(grp, kind="stable")
+    first = np.concatenate([[0], np.cumsum(sizes)])
+    loop_groups = min(n_groups, a.loop_groups)
+    with Context(0) as ctx, Context(0) as one:
+        ctx.set_model(L.SPHERE, 3, DELTA, L.LS_GEOMETRIC).upload(data)
+        one.set_model(L.SPHERE, 3, DELTA, L.LS_GEOMETRIC)
+        dev = DeviceArray(grp)
+        t_0, t_1, t_hi, t_loop, done = [], [], [], [], None
+        for rep in range(-1, a.reps):  # rep -1 warms every kind
+            t0 = time.perf_counter()
+            ctx.refine_lm_grouped(dev, n_groups, rows, max_rounds=0)
+            t1 = time.perf_counter()
+            lo = ctx.refine_lm_grouped(dev, n_groups, rows, max_rounds=1)
+            t2 = time.perf_counter()
+            hi = ctx.refine_lm_grouped(dev, n_groups, rows, max_rounds=r2)
+            t3 = time.perf_counter()
+            if rep < a.baseline_reps:  # what a caller must do without the call, on the first groups
+                labels = np.full(n, -1, dtype=np.int32)
+                for g in range(loop_groups):
+                    at = order[first[g]:first[g + 1]]
+                    one.upload(np.ascontiguousarray(data[at]))
+                    labels[at] = one.refine_lm(rows[g], max_rounds=r2)["labels"]
+            t4 = time.perf_counter()
+            work = (int(lo["rounds"].sum()), int(hi["rounds"].sum()))
+            if done is not None and done != work:
+                raise SystemExit("the rounds done differ between repetitions")
+            done = work
+            if rep >= 0:
+                t_0.append(t1 - t0)
+                t_1.append(t2 - t1)
+                t_hi.append(t3 - t2)
+                if rep < a.baseline_reps:
+                    t_loop.append((t4 - t3) * n_groups / loop_groups)
+        dev.free()
+        # round 1: its evaluations, and the workgroups that hold no record of a model still live
+        evals = int(lo["lm_nfev"].max())
+        lab0 = ctx.assign_grouped(grp, n_groups, rows)["labels"]
+        pos = np.empty(n, dtype=np.int64)
+        pos[order] = np.arange(n) - first[grp[order]]
+        chunk_first = np.concatenate([[0], np.cumsum((sizes + 2047) // 2048)])
+        wg = chunk_first[grp] + pos // 2048
+        wg_nfev = np.zeros(int(chunk_first[-1]), dtype=np.int64)
+        has = lab0 >= 0
+        np.maximum.at(wg_nfev, wg[has], lo["lm_nfev"][grp[has], lab0[has]])
+        idle = [round(float(np.mean(wg_nfev < j)), 4) for j in range(1, evals + 1)]
+    round1 = [b - c for b, c in zip(t_1, t_0)]
+    row = dict(model="sphere", ls="geometric", dim=3, n=n, groups=n_groups, models=k, reps=a.reps, rounds=[0, 1, r2],
+               rounds_hist=np.bincount(hi["rounds"]).tolist(), converged=int(hi["converged"].sum()),
+               lm_ok=int(((hi["lm_info"] >= 1) & (hi["lm_info"] <= 4)).sum()), call0_ms=ms(t_0), call1_ms=ms(t_1),
+               grouped_call_ms=ms(t_hi), round1_ms=ms(round1), evaluations=evals,
+               lm_nfev_hist=np.bincount(lo["lm_nfev"].ravel()).tolist(),
+               eval_ms_upper=round(1e3 * float(np.median(round1)) / max(evals, 1), 4),
+               workgroups=int(chunk_first[-1]), idle_share=idle)
+    if t_loop:
+        row.update(loop_call_ms=ms(t_loop), loop_groups_timed=loop_groups, loop_scaled_by=n_groups / loop_groups,
+                   loop_reps=len(t_loop), ratio_call=round(float(np.median(t_loop) / np.median(t_hi)), 1))
+    line = json.dumps(row)
+    print(line, flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
 def grouped_main(a):
     r1, r2 = a.rounds
     ms = lambda v: [round(1e3 * float(f(v)), 4) for f in (np.median, np.min, np.max)]
@@ -362,7 +468,10 @@ def main():
     ap.add_argument("--model", choices=sorted(SYNTH), default="plane")
     ap.add_argument("--dim", type=int, default=3)
     ap.add_argument("--lm", action="store_true", help="time Context.refine_lm on the sphere scene instead (see above)")
+    ap.add_argument("--groups", type=int, default=3000, help="--grouped --lm: the groups of the scene")
     a = ap.parse_args()
+    if a.lm and a.grouped:
+        return grouped_lm_main(a)
     if a.lm:
         a.models = [4, 64] if a.models == [4, 16, 64] else a.models
         return lm_main(a)
