@@ -173,6 +173,14 @@ LSQR_API int lsqr_estimate_host(const lsqr_model_cfg *cfg, const void *records, 
  * record or label_out returns LSQR_ERR_INVALID. */
 LSQR_API int lsqr_assign_host(const lsqr_model_cfg *cfg, const double *params, size_t n_models, const void *record,
                               int32_t *label_out, double *residual_out /* nullable */);
+/* The same for lsqr_assign_dense (below): cfg is LSQR_MODEL_DENSE with dim n = 1..64, params holds n_models rows of n
+ * doubles, record is one row (a[0..n), b) of n + 1 doubles.  The code the kernel of lsqr_assign_dense runs, compiled
+ * for the host: the residual is the running sum in slot order, sum += a[i] * x[i], then - b, bit for bit.  A record
+ * with a non-finite slot among its n + 1 gets -1 and +infinity.  n_models == 0 returns LSQR_OK and writes nothing;
+ * every other model, dim 0 or above 64, n_models > 64 or a null cfg, params, record or label_out returns
+ * LSQR_ERR_INVALID and writes nothing.  lsqr_assign_host keeps refusing LSQR_MODEL_DENSE. */
+LSQR_API int lsqr_assign_dense_host(const lsqr_model_cfg *cfg, const double *params, size_t n_models,
+                                    const void *record, int32_t *label_out, double *residual_out /* nullable */);
 
 /* ---- agree() scan over all observations (RANSAC.hxx:94-99, without the early exit) ---------- */
 LSQR_API int lsqr_scan(lsqr_ctx *ctx);
@@ -498,6 +506,59 @@ LSQR_API int lsqr_refine_lm(lsqr_ctx *ctx, double *params_inout /* host, n_model
                             uint64_t *counts_out /* nullable, host: n_models + 1 */,
                             lsqr_fit_info *fits /* host, n_models */, int32_t *status_out /* host, n_models */,
                             size_t *rounds_out, int *converged_out);
+/* ---- lsqr_assign / lsqr_refine for the dense linear system (csrc/assign_dense.h) -----------------------------------
+ * A mixture of linear regressions: every row (a | b) goes to the nearest of up to 64 regressions x_m it agrees with,
+ * and every regression is fitted again on its own rows.  lsqr_assign_dense / lsqr_refine_dense are lsqr_assign /
+ * lsqr_refine -- their arguments, their loop and its stop rules, rounds_out / converged_out / counts_out / labels_out,
+ * the order of their checks, "every argument error writes nothing" -- with the model changed; lsqr_assign and
+ * lsqr_refine keep refusing the dense model, as lsqr_ransac_many refuses it beside lsqr_ransac_many_dense.
+ *   Model: LSQR_MODEL_DENSE, dim n = 1..64, rows of n + 1 doubles (a[0..n), b) at any stride >= the record, from
+ *     lsqr_upload or lsqr_attach.  Every other model returns LSQR_ERR_INVALID and writes nothing.  n_models <= 64;
+ *     params holds n_models rows of n doubles.
+ *   Decision: label(x) = the smallest m that minimises |a . x_m - b| among the m with |a . x_m - b| < delta (strict
+ *     '<' while m walks upwards: ties go to the smaller m); -1 when none agrees, and for a row with a non-finite slot
+ *     among its n + 1.  The dot product is the reference's running sum in slot order, sum += a[i] * x[i], then - b, not
+ *     reassociated and not contracted, so labels_out[i] and residuals_out[i] (+infinity for -1) equal, bit for bit,
+ *     what lsqr_mask and lsqr_residuals give for that row of params on the same context, and what
+ *     lsqr_assign_dense_host gives.
+ *   Loop: lsqr_refine's.  max_rounds == 0 is lsqr_assign_dense, and the returned labels are always exactly
+ *     lsqr_assign_dense of the returned parameters.
+ *   Refit of model m in a round: with at least lsqr_min_subset (= n) rows labelled m, the least-squares solution over
+ *     those rows by lsqr_ls_fit's route: the packed block sum z z^T, z = (a | b); the elimination under the options
+ *     dense_fast_solve and dense_dd; where it meets a pivot below 1e-6 max|G| and dense_dd is on, the double-double
+ *     solve from the rows labelled m.  The row is replaced only when the solve gives a result, otherwise it keeps its
+ *     values.  status_out[m]: LSQR_OK or LSQR_EMPTY (LSQR_OK when no refit ran); fits[m] for the last refit round:
+ *     n_params (n or 0), n_used (the rows behind the attempt) and reserved, the route as lsqr_ls_fit reports it (0: the
+ *     elimination, 1: double-double from the rows, 2: dense_dd 0 and a pivot below 1e-6); zeroed where none ran.
+ *     Model m's new row agrees with lsqr_set_mask(L_r == m) + lsqr_ls_fit(use_mask = 1) on the same context up to the
+ *     order of the fp64 sums.
+ *   Sums: none is a floating-point atomic; the same call twice gives the same bits.  A model's block is a function of
+ *     its own rows, their positions in the upload and the fixed chunking (256 rows per chunk up to n = 32, 128 above;
+ *     within a chunk in row order, the chunks in order): not of the grid, of the other models of the call, or of where
+ *     m sits among them.
+ *   Per round the rows are read once (by the one pass that labels them and sums the blocks from the same on-chip
+ *     copy), and the host reads the changed-counter with the counts and, with dense_dd, the models' flags, in one copy.
+ *   Device scratch of a refine call: ceil(N / chunk) * n_models * ((n+1)(n+2)/2 + 1, rounded up to 8) doubles of
+ *     partial blocks, two label arrays, one word per chunk.  If it cannot be allocated the call returns LSQR_ERR_HIP
+ *     with the allocation in lsqr_last_error; there is no other path.
+ *   Checks, in this order: a null context; the model (none set: LSQR_ERR_STATE; not dense: LSQR_ERR_INVALID);
+ *     n_models == 0 is a no-op returning LSQR_OK; n_models > 64, or a null params or labels_out (lsqr_assign_dense), a
+ *     null params_inout, fits, status_out, rounds_out or converged_out (lsqr_refine_dense) (LSQR_ERR_INVALID); no
+ *     records in the context (LSQR_ERR_STATE); more than 2^32 - 16 records (LSQR_ERR_INVALID).
+ *   The context's hypotheses, mask, spatial index, fp16 fragment copies and the parameters of its last mask are left
+ *     as they were; the work runs on the context's stream, and the call returns after it has finished.  There is no
+ *     grouped form (one regression set per label) and lsqr_multi handles have no such form. */
+LSQR_API int lsqr_assign_dense(lsqr_ctx *ctx, const double *params /* host, n_models * n */, size_t n_models,
+                               int on_device /* 1: labels_out, residuals_out are device pointers */,
+                               int32_t *labels_out /* lsqr_count(ctx) entries, upload order */,
+                               double *residuals_out /* nullable */,
+                               uint64_t *counts_out /* nullable, host: n_models + 1, last = unassigned */);
+LSQR_API int lsqr_refine_dense(lsqr_ctx *ctx, double *params_inout /* host, n_models * n */, size_t n_models,
+                               size_t max_rounds, int on_device /* 1: labels_out is a device pointer */,
+                               int32_t *labels_out /* nullable */,
+                               uint64_t *counts_out /* nullable, host: n_models + 1 */,
+                               lsqr_fit_info *fits /* host, n_models */, int32_t *status_out /* host, n_models */,
+                               size_t *rounds_out, int *converged_out);
 /* ---- the same with ONE MODEL SET PER LABEL (csrc/assign_grouped.h) -------------------------------------------------
  * lsqr_assign_grouped / lsqr_refine_grouped take what lsqr_ransac_grouped_sequential leaves -- params_out and
  * n_models_out, unchanged -- over the same groups array and the same resident records: row g * max_models + m of params

@@ -18,6 +18,12 @@ KERNEL_IDS = {"sample": 0, "estimate": 1, "scan": 2, "mask": 3, "moments": 4, "s
               "index": 6, "absmax": 7}
 
 
+def assign_dense_chunk(n):
+    """rows per workgroup of the pass of lsqr_assign_dense / lsqr_refine_dense for dim n (kAssignDenseChunk of
+    csrc/assign_dense.h: it fixes the order of the refit's sums, and include/lsqr_hip.h states it)"""
+    return 256 if n <= 32 else 128
+
+
 class LsqrError(RuntimeError):
     def __init__(self, status, msg):
         RuntimeError.__init__(self, "lsqr_hip status %d: %s" % (status, msg))
@@ -70,6 +76,8 @@ SIGNATURES = {
                                      C.POINTER(C.c_int)]),
     "lsqr_assign_host": (C.c_int, [C.POINTER(ModelCfg), C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_int32),
                                    _dp]),
+    "lsqr_assign_dense_host": (C.c_int, [C.POINTER(ModelCfg), C.c_void_p, C.c_size_t, C.c_void_p,
+                                         C.POINTER(C.c_int32), _dp]),
     "lsqr_scan": (C.c_int, [_ctx]),
     "lsqr_get_hypotheses": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lsqr_num_hypotheses": (C.c_size_t, [_ctx]),
@@ -118,6 +126,9 @@ SIGNATURES = {
                               C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
     "lsqr_refine_lm": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
+    "lsqr_assign_dense": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lsqr_refine_dense": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
     "lsqr_assign_grouped": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lsqr_refine_grouped": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,

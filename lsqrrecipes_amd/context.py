@@ -577,6 +577,38 @@ class Context:
                    stall=f["reserved"].copy())
         return out
 
+    def assign_dense(self, params, want_residuals=False, labels_out=None):
+        """assign for the dense linear system, which assign refuses (lsqr_assign_dense): every row (a | b) of the
+        current upload / attach to the nearest of the regressions it agrees with.  params: M <= 64 rows of n
+        coefficients.  label = the smallest m that minimises |a . params[m] - b| among the m with
+        |a . params[m] - b| < delta, -1 when none agrees (and for a row with a non-finite slot among its n + 1).  The
+        dot product is the running sum in slot order, so labels and residuals equal mask() / residuals() of that row
+        bit for bit.  Any other model raises LsqrError(ERR_INVALID).  labels_out and the result as for assign."""
+        par, m, total, on_device, labels, l_ptr = self._assign_args(params, labels_out)
+        if on_device and want_residuals:
+            raise ValueError("want_residuals goes with host labels")
+        res = np.full(max(total, 1), np.inf) if want_residuals else None
+        counts = np.zeros(m + 1, dtype=np.uint64)
+        if m == 0:
+            counts[0] = total
+        self._chk(self._lib.lsqr_assign_dense(self._h, L.ptr(par), m, 1 if on_device else 0, l_ptr, L.ptr(res),
+                                              L.ptr(counts)))
+        if not on_device:
+            labels = labels[:total]
+        return dict(labels=labels, residuals=res[:total] if res is not None else None, counts=counts)
+
+    def refine_dense(self, params, max_rounds=8, labels_out=None):
+        """refine for the dense linear system (lsqr_refine_dense): the same loop, and the refit of a regression is the
+        least-squares solution over its own rows by ls_fit's route -- the elimination on the Gram block under the
+        options dense_fast_solve and dense_dd, the double-double solve from the rows where it meets a pivot below
+        1e-6 max|G|.  A regression with fewer than n rows, or whose solve gives no result, keeps its row for that
+        round.  Each round reads the rows once.  Any other model raises LsqrError(ERR_INVALID).
+        -> refine's dict, and route: per model the route of the last refit round as ls_fit reports it (0: the
+        elimination, 1: double-double, 2: dense_dd 0 and a pivot below 1e-6); zeros where none ran."""
+        out, f = self._refine(self._lib.lsqr_refine_dense, params, max_rounds, labels_out)
+        out.update(route=f["reserved"].copy())
+        return out
+
     def _assign_grouped_args(self, groups, n_groups, params, n_models, labels_out):
         """the labels, rows and label buffer of assign_grouped / refine_grouped, groups and labels_out handled as in
         ransac_grouped_sequential -> (n, m, total, on_device, g, g_ptr, par, nm, labels, l_ptr); g keeps the host

@@ -46,6 +46,7 @@
 #include "many_sequential.h"
 #include "grouped.h"
 #include "assign.h"
+#include "assign_dense.h"
 #include "assign_lm.h"
 #include "assign_grouped.h"
 #include "assign_lm_grouped.h"
@@ -315,6 +316,7 @@ struct lsqr_ctx {
   PinBuf<char> h_batch;  // pinned results of a lsqr_ransac batch (grown on demand)
   std::unique_ptr<ManyBufs> many;  // lsqr_ransac_many's buffers (its own: the context's upload is not touched)
   std::unique_ptr<AssignBufs> assign;  // lsqr_assign / lsqr_refine / lsqr_refine_lm (assign.h, assign_lm.h)
+  std::unique_ptr<AssignDenseBufs> assign_dense;  // lsqr_assign_dense / lsqr_refine_dense (assign_dense.h)
   // lsqr_assign_grouped / lsqr_refine_grouped / lsqr_refine_lm_grouped (assign_grouped.h, assign_lm_grouped.h)
   std::unique_ptr<AssignGrpBufs> assign_grp;
   // lsqr_ransac_sequential (sequential.h): the survivors of a round go from the current buffer into the OTHER of two
@@ -3097,6 +3099,10 @@ int lsqr_assign_host(const lsqr_model_cfg *cfg, const double *params, size_t n_m
                      int32_t *label_out, double *residual_out) {
   return host_assign_host(cfg, params, n_models, record, label_out, residual_out);
 }
+int lsqr_assign_dense_host(const lsqr_model_cfg *cfg, const double *params, size_t n_models, const void *record,
+                           int32_t *label_out, double *residual_out) {
+  return host_assign_dense_host(cfg, params, n_models, record, label_out, residual_out);
+}
 
 int lsqr_set_model(lsqr_ctx *c, const lsqr_model_cfg *cfg) {
   if (!c || !cfg) return LSQR_ERR_INVALID;
@@ -4424,6 +4430,77 @@ int lsqr_refine_lm(lsqr_ctx *c, double *params_inout, size_t n_models, size_t ma
                    size_t *rounds_out, int *converged_out) {
   return refine_call(c, "lsqr_refine_lm", ASSIGN_GATE_LM, params_inout, n_models, max_rounds, on_device, labels_out,
                      counts_out, fits, status_out, rounds_out, converged_out);
+}
+
+// ---- the same for the dense linear system (assign_dense.h) ----------------------------------------------------------
+// lsqr_assign_dense and lsqr_refine_dense: assign_frame's checks in assign_frame's order, with the model gate turned
+// round -- LSQR_MODEL_DENSE alone -- and assign_dense_run on the row class NR of the context's dim.
+extern "C++" {
+static int assign_dense_call(lsqr_ctx *c, const char *fn, bool args, AssignJob &J) {
+  int st = need_ready(c, false);
+  if (st != LSQR_OK) return st;
+  if (c->cfg.model != LSQR_MODEL_DENSE)
+    return fail(c, LSQR_ERR_INVALID, "%s: the dense linear system only (model %d); lsqr_assign / lsqr_refine take the "
+                "plane, line, sphere and 2-D line", fn, c->cfg.model);
+  if (J.n_models == 0) return LSQR_OK;
+  if (J.n_models > (size_t)kAssignMaxModels) return fail(c, LSQR_ERR_INVALID, "%s: more than 64 models", fn);
+  if (!args) return fail(c, LSQR_ERR_INVALID, "%s: null argument", fn);
+  if ((st = need_ready(c, true)) != LSQR_OK) return st;
+  if (c->n > 0xFFFFFFF0ull) return fail(c, LSQR_ERR_INVALID, "%s: more than 2^32 - 16 records", fn);
+  if (!c->assign_dense) c->assign_dense.reset(new AssignDenseBufs());
+  J.stream = c->stream;
+  J.cfg = c->cfg;
+  J.mc = c->mc;
+  J.data = c->d_data;
+  J.stride = c->stride;
+  J.n = (uint32_t)c->n;
+  const int fast = c->opt.dense_fast ? 1 : 0, dd = c->opt.dense_dd ? 1 : 0;
+  st = dispatch(c->cfg, [&](auto tag) -> int {
+    typedef typename decltype(tag)::type M;
+    if constexpr (M::IS_DENSE) return assign_dense_run<M::NR>(J, *c->assign_dense, fast, dd);
+    else return LSQR_ERR_INVALID;
+  });
+  if (st != LSQR_OK) {
+    (void)sync_stream(c);  // nothing of this call is left in flight on its buffers
+    return fail(c, st, "%s: %s", fn, J.err[0] ? J.err : "model not in this build");
+  }
+  bsel_host_synced(c);
+  return LSQR_OK;
+}
+}  // extern "C++"
+
+int lsqr_assign_dense(lsqr_ctx *c, const double *params, size_t n_models, int on_device, int32_t *labels_out,
+                      double *residuals_out, uint64_t *counts_out) {
+  AssignJob J;
+  J.params = const_cast<double *>(params);  // (read only: no refit runs)
+  J.n_models = n_models;
+  J.max_rounds = 0;
+  J.on_device = on_device ? 1 : 0;
+  J.labels_out = labels_out;
+  J.residuals_out = residuals_out;
+  J.counts_out = counts_out;
+  return assign_dense_call(c, "lsqr_assign_dense", params && labels_out, J);
+}
+
+int lsqr_refine_dense(lsqr_ctx *c, double *params_inout, size_t n_models, size_t max_rounds, int on_device,
+                      int32_t *labels_out, uint64_t *counts_out, lsqr_fit_info *fits, int32_t *status_out,
+                      size_t *rounds_out, int *converged_out) {
+  AssignJob J;
+  J.params = params_inout;
+  J.n_models = n_models;
+  J.max_rounds = max_rounds;
+  J.on_device = on_device ? 1 : 0;
+  J.labels_out = labels_out;
+  J.counts_out = counts_out;
+  J.fits = fits;
+  J.status_out = status_out;
+  const bool args = params_inout && fits && status_out && rounds_out && converged_out;
+  const int st = assign_dense_call(c, "lsqr_refine_dense", args, J);
+  if (st == LSQR_OK && n_models > 0) {
+    *rounds_out = J.rounds;
+    *converged_out = J.converged;
+  }
+  return st;
 }
 
 // lsqr_assign_grouped, lsqr_refine_grouped and lsqr_refine_lm_grouped.  The sort and the packed copy live in the batched

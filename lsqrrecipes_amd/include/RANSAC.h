@@ -424,6 +424,42 @@ class RANSAC {
     return refineOnDevice(lsqr_refine_lm, cfg, models, data, maxRounds, labels, converged);
   }
 
+  // assignToModels / refineModels for DenseLinearEquationSystemParametersEstimator<double,n> (a mixture of linear
+  // regressions), which those two send to the host loop: ONE device call each (lsqr_assign_dense / lsqr_refine_dense).
+  // The assignment is the device's -- the regression with the smallest |a . x - b| among those the row agrees with,
+  // ties to the smaller index --, the loop, the stop rules and what comes back are refineModels', and the refit of a
+  // regression is the least-squares solution over its own rows as leastSquaresEstimate computes it; a regression with
+  // fewer than n rows, or whose rows do not have full rank, keeps its parameters.  Any other estimator throws
+  // std::invalid_argument; more than 64 models, or a model vector of the wrong length, likewise.
+  static void assignToModelsDense(const std::vector<std::vector<S> > &models,
+                                  ParametersEstimator<T, S> *paramEstimator, std::vector<T> &data,
+                                  std::vector<int> &labels) {
+    lsqr_model_cfg cfg;
+    denseOnly(paramEstimator, cfg, "assignToModelsDense");
+    labels.assign(data.size(), -1);
+    if (models.empty() || data.empty()) return;
+    detail::Device &d = detail::Device::instance();
+    lsqr_ctx *ctx = d.ctx();
+    if (lsqr_multi *m = d.multi()) ctx = lsqr_multi_ctx(m, 0);
+    d.check(lsqr_set_model(ctx, &cfg));
+    d.check(lsqr_upload(ctx, &data[0], data.size(), sizeof(T)));
+    std::vector<double> par = packModels(models, cfg);
+    std::vector<int32_t> lab(data.size());
+    d.check(lsqr_assign_dense(ctx, &par[0], models.size(), 0, &lab[0], NULL, NULL));
+    labels.assign(lab.begin(), lab.end());
+  }
+
+  static size_t refineModelsDense(std::vector<std::vector<S> > &models, ParametersEstimator<T, S> *paramEstimator,
+                                  std::vector<T> &data, size_t maxRounds, std::vector<int> &labels,
+                                  bool *converged = NULL) {
+    lsqr_model_cfg cfg;
+    denseOnly(paramEstimator, cfg, "refineModelsDense");
+    labels.assign(data.size(), -1);
+    if (converged) *converged = false;
+    if (models.empty() || data.empty()) return 0;
+    return refineOnDevice(lsqr_refine_dense, cfg, models, data, maxRounds, labels, converged);
+  }
+
   // assignToModels with one model set per label on resident records (not in the reference), the follow-up of
   // computeGroupedSequential: `models` is what that call leaves in `parameters` (models[g]: the models of group g;
   // models.size() must be nGroups), `groups` and `data` are its own.  labels[i] is the model of models[groups[i]] that
@@ -882,7 +918,14 @@ class RANSAC {
     return cfg.model == LSQR_MODEL_PLANE || cfg.model == LSQR_MODEL_LINE || cfg.model == LSQR_MODEL_LINE2D;
   }
 
-  // the device path of refineModels (lsqr_refine) and of refineModelsLM (lsqr_refine_lm)
+  // assignToModelsDense / refineModelsDense: the estimator's device model must be the dense linear system
+  static void denseOnly(ParametersEstimator<T, S> *paramEstimator, lsqr_model_cfg &cfg, const char *fn) {
+    if (!paramEstimator) throw std::invalid_argument("lsqrRecipes::RANSAC: null estimator");
+    if (!paramEstimator->deviceModel(cfg) || cfg.model != LSQR_MODEL_DENSE)
+      throw std::invalid_argument(std::string("lsqrRecipes::RANSAC: ") + fn + " takes the dense linear system only");
+  }
+
+  // the device path of refineModels (lsqr_refine), refineModelsLM (lsqr_refine_lm) and refineModelsDense
   typedef int (*RefineCall)(lsqr_ctx *, double *, size_t, size_t, int, int32_t *, uint64_t *, lsqr_fit_info *,
                             int32_t *, size_t *, int *);
   static size_t refineOnDevice(RefineCall call, lsqr_model_cfg &cfg, std::vector<std::vector<S> > &models,

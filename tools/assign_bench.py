@@ -54,7 +54,15 @@ written back, timed on the first --loop-groups groups and scaled by n_groups / g
 evaluations: the LM evaluations of refit round 1, max(lm_nfev) over all models of the max_rounds = 1 call;
 round1_ms = t(1) - t(0): that round, with its solve, its init and the assignment pass after it; eval_ms_upper =
 round1_ms / evaluations.  idle_share[j - 1]: the share of the (group, chunk) workgroups of evaluation j of round 1 that
-return at once -- no record of a model still live --, from the labels of the start rows and the models' lm_nfev."""
+return at once -- no record of a model still live --, from the labels of the start rows and the models' lm_nfev.
+
+--model dense --dim n: Context.refine_dense (lsqr_refine_dense: a mixture of linear regressions) on --n rows (default
+1 M here) of n + 1 doubles: M planted regressions (--models, default 4 and 16) of 1 / (M + 1) of the rows each, Gaussian
+a, noise 0.01 on b, the rest clutter; delta 0.04; the start rows are the planted ones moved off inside the noise band.
+Two kinds alternate in one process: refine_round_ms as above, and baseline_round_ms, the round the entry points allowed
+before: M x (lsqr_mask + lsqr_set_mask + lsqr_ls_fit).  rows_read_per_round: how often a round reads each row -- once
+for the new call, 2 M times for the baseline (a mask pass and a Gram pass per model); partial_bytes: the call's device
+scratch for the chunk blocks, which a round writes once and reads once."""
 import argparse
 import json
 import os
@@ -132,15 +140,16 @@ def baseline_round(ctx, rows):
     return new
 
 
-def refine_rounds(ctx, rows, max_rounds, lm=False, nfev=None):
-    """lsqr_refine (lm: lsqr_refine_lm) without labels_out -> rounds done; nfev (a list): gets the models' lm_nfev"""
+def refine_rounds(ctx, rows, max_rounds, lm=False, nfev=None, dense=False):
+    """lsqr_refine (lm: lsqr_refine_lm, dense: lsqr_refine_dense) without labels_out -> rounds done; nfev (a list):
+    gets the models' lm_nfev"""
     import ctypes as C
     par = np.array(rows, dtype=np.float64, order="C")
     m = par.shape[0]
     fits = (L.FitInfo * m)()
     status = np.zeros(m, dtype=np.int32)
     rounds, conv = C.c_size_t(0), C.c_int(0)
-    call = ctx._lib.lsqr_refine_lm if lm else ctx._lib.lsqr_refine
+    call = ctx._lib.lsqr_refine_lm if lm else ctx._lib.lsqr_refine_dense if dense else ctx._lib.lsqr_refine
     ctx._chk(call(ctx._h, L.ptr(par), m, max_rounds, 0, None, None, fits, L.ptr(status), C.byref(rounds),
                   C.byref(conv)))
     if nfev is not None:
@@ -219,6 +228,74 @@ def lm_main(a):
                        alg_refine_round_ms=ms(aper), ratio_host=round(float(np.median(t_host)) / rnd, 1),
                        ratio_alg=round(rnd / float(np.median(aper)), 2),
                        passes_per_s=round((1 + max(nfev)) / rnd, 1))
+            lines.append(json.dumps(row))
+            print(lines[-1], flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+DENSE_SIGMA = 0.01
+
+
+def dense_scene(n, dim, m, seed=20261023):
+    """-> rows (a | b) shuffled, the start regressions: m planted ones of n / (m + 1) rows each, the rest clutter"""
+    g = np.random.default_rng([seed, dim, m])
+    x = g.normal(size=(m, dim))
+    rows = np.empty((n, dim + 1))
+    rows[:, :dim] = g.normal(size=(n, dim))
+    owner = np.arange(n) % (m + 1)  # m: clutter
+    on = owner < m
+    rows[:, dim] = np.einsum("ij,ij->i", rows[:, :dim], x[np.minimum(owner, m - 1)]) + DENSE_SIGMA * g.normal(size=n)
+    rows[~on, dim] = g.uniform(-10.0, 10.0, int((~on).sum()))
+    start = x + DENSE_SIGMA / np.sqrt(dim) * g.normal(size=x.shape)
+    return np.ascontiguousarray(rows[g.permutation(n)]), start
+
+
+def dense_main(a):
+    r1, r2 = a.rounds
+    ms = lambda v: [round(1e3 * float(f(v)), 4) for f in (np.median, np.min, np.max)]
+    lines = []
+    dim = a.dim
+    with Context(0) as ctx:
+        for m in a.models:
+            data, rows = dense_scene(a.n, dim, m)
+            ctx.set_model(L.DENSE, dim, 4 * DENSE_SIGMA).upload(data)
+            t_lo, t_hi, t_asg, t_base, done = [], [], [], [], None
+            for rep in range(-1, a.reps):  # rep -1 warms every kind
+                t0 = time.perf_counter()
+                asg = ctx.assign_dense(rows)
+                t1 = time.perf_counter()
+                lo = refine_rounds(ctx, rows, r1, dense=True)
+                t2 = time.perf_counter()
+                hi = refine_rounds(ctx, rows, r2, dense=True)
+                t3 = time.perf_counter()
+                if rep < a.baseline_reps:
+                    baseline_round(ctx, rows)
+                t4 = time.perf_counter()
+                if hi <= lo:
+                    raise SystemExit("converged after %d rounds: nothing to time" % hi)
+                if done is not None and done != (lo, hi):
+                    raise SystemExit("the rounds done differ between repetitions")
+                done = (lo, hi)
+                if rep >= 0:
+                    t_asg.append(t1 - t0)
+                    t_lo.append(t2 - t1)
+                    t_hi.append(t3 - t2)
+                    if rep < a.baseline_reps:
+                        t_base.append(t4 - t3)
+            per = [(h - l) / (done[1] - done[0]) for h, l in zip(t_hi, t_lo)]
+            rnd = float(np.median(per))
+            chunk = L.assign_dense_chunk(dim)
+            ps = ((dim + 1) * (dim + 2) // 2 + 1 + 7) & ~7
+            row = dict(model="dense", dim=dim, n=a.n, models=m, reps=a.reps, rounds_done=list(done),
+                       counts_assigned=int(a.n - asg["counts"][-1]), refine_round_ms=ms(per), assign_call_ms=ms(t_asg),
+                       baseline_round_ms=ms(t_base), baseline_reps=len(t_base),
+                       ratio=round(float(np.median(t_base)) / rnd, 2), rows_read_per_round=dict(refine=1, baseline=2 * m),
+                       chunk=chunk, partial_bytes=int((a.n + chunk - 1) // chunk * m * ps * 8),
+                       record_bytes_per_s=round(a.n * 8 * (dim + 1) / rnd, 0),
+                       hbm_fraction=round(a.n * 8 * (dim + 1) / rnd / HBM_PEAK, 4))
             lines.append(json.dumps(row))
             print(lines[-1], flush=True)
     if a.out:
@@ -465,7 +542,7 @@ def main():
     ap.add_argument("--grouped", action="store_true", help="time Context.refine_grouped instead (see above)")
     ap.add_argument("--splits", nargs="+", default=["a", "b", "c"], choices=["a", "b", "c"])
     ap.add_argument("--loop-groups", type=int, default=200, help="--grouped: groups the per-group loop is timed on")
-    ap.add_argument("--model", choices=sorted(SYNTH), default="plane")
+    ap.add_argument("--model", choices=sorted(SYNTH) + ["dense"], default="plane")
     ap.add_argument("--dim", type=int, default=3)
     ap.add_argument("--lm", action="store_true", help="time Context.refine_lm on the sphere scene instead (see above)")
     ap.add_argument("--groups", type=int, default=3000, help="--grouped --lm: the groups of the scene")
@@ -475,6 +552,12 @@ def main():
     if a.lm:
         a.models = [4, 64] if a.models == [4, 16, 64] else a.models
         return lm_main(a)
+    if a.model == "dense":
+        if a.grouped or a.lm:
+            raise SystemExit("--model dense goes with neither --grouped nor --lm")
+        a.n = 1_000_000 if a.n == 10_000_000 else a.n
+        a.models = [4, 16] if a.models == [4, 16, 64] else a.models
+        return dense_main(a)
     a.model_id = SYNTH[a.model][0]
     a.synth = (a.model, a.dim) != ("plane", 3)  # the default scene is this tool's own
     if a.synth:
