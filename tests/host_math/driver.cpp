@@ -1,5 +1,5 @@
 // Host-compiled unit-test driver for the PRODUCT's LSQR_HD math headers
-// (lsqrrecipes_amd/csrc/{models,lm_core,small_linalg,sampler,us,phantom}.h).  Built by tests/test_host_math.py
+// (lsqrrecipes_amd/csrc/{models,lm_core,small_linalg,sampler,us,phantom,rigid}.h).  Built by tests/test_host_math.py
 // with g++ -ffp-contract=off; lets the CPU suite check the product's per-model arithmetic, small
 // solvers and LM state machine against the oracle before anything runs on a GPU.  Test-only: the
 // product never executes this path.
@@ -9,6 +9,7 @@
 
 #include "models.h"
 #include "phantom.h"
+#include "rigid.h"
 #include "sampler.h"
 #include "us.h"
 
@@ -19,9 +20,14 @@ static int t_estimate(const double *recs, const ModelConsts &mc, double *par) {
   if constexpr (M::IS_US) {
     return -1;  // K1 of the US models is a wave kernel (device only)
   } else {
+  // through M::load, as the kernels read a record (the loaded record may be wider than the caller's: AbsOr's weight)
+  constexpr int W = M::ND > M::REC ? M::ND : M::REC;
   double r[M::K][M::ND];
-  for (int l = 0; l < M::K; l++)
-    for (int j = 0; j < M::ND; j++) r[l][j] = recs[l * M::ND + j];
+  for (int l = 0; l < M::K; l++) {
+    double x[W];
+    M::load(recs + l * M::ND, mc, x);
+    for (int j = 0; j < M::ND; j++) r[l][j] = j < M::REC ? x[j] : 0.0;
+  }
   return M::estimate(r, mc, par) ? M::P : 0;
   }
 }
@@ -29,9 +35,14 @@ static int t_estimate(const double *recs, const ModelConsts &mc, double *par) {
 template <class M>
 static int t_ls(const double *data, size_t n, const uint8_t *mask, const double *org,
                 const ModelConsts &mc, double *par, double *mom_out) {
+  constexpr int W = M::ND > M::REC ? M::ND : M::REC;
   double m[MOM_MAX] = {0};
   for (size_t i = 0; i < n; i++)
-    if (!mask || mask[i]) M::accumulate(data + i * M::ND, org, m);
+    if (!mask || mask[i]) {
+      double x[W];
+      M::load(data + i * M::ND, mc, x);
+      M::accumulate(x, org, m);
+    }
   if (mom_out) memcpy(mom_out, m, sizeof(double) * M::NMOM);
   return M::solve(m, org, mc, par) ? M::P : 0;
 }
@@ -62,8 +73,14 @@ static int t_lm(const double *data, size_t n, const double *x0, double ftol, dou
     case 32: { typedef LineModel<2> M; CALL; } break;                \
     case 50: { typedef USModel<true> M; CALL; } break;               \
     case 60: { typedef USModel<false> M; CALL; } break;              \
+    case 73: { typedef AbsOrModel M; CALL; } break;                  \
+    case 83: { typedef PivotModel M; CALL; } break;                  \
+    case 93: { typedef RayModel M; CALL; } break;                    \
+    case 102: { typedef Line2DModel M; CALL; } break;                \
     default: break;                                                  \
   }
+
+static double g_aux = 0.0;  // RAY: sin(minimal angle)^2, set by hm_set_aux
 
 static ModelConsts consts(int dim, double delta, int ls) {
   ModelConsts mc;
@@ -73,6 +90,8 @@ static ModelConsts consts(int dim, double delta, int ls) {
   mc.ls_type = ls;
   mc.thr = square_threshold(mc.delta_sq);
   mc.absmax = 0.0;
+  mc.absmax_rot = 0.0;
+  mc.aux = g_aux;
   return mc;
 }
 
@@ -94,7 +113,12 @@ int hm_agree(int model, int dim, double delta, const double *par, const double *
     double sp[M::SP];
     for (int j = 0; j < M::SP; j++) sp[j] = j < M::P ? par[j] : 0.0;
     M::prepare(sp, mc);
-    for (size_t i = 0; i < n; i++) mask[i] = M::agree(sp, data + i * M::ND, mc) ? 1 : 0;
+    constexpr int W = M::ND > M::REC ? M::ND : M::REC;
+    for (size_t i = 0; i < n; i++) {
+      double x[W];
+      M::load(data + i * M::ND, mc, x);
+      mask[i] = M::agree(sp, x, mc) ? 1 : 0;
+    }
   });
   return ok;
 }
@@ -105,6 +129,22 @@ int hm_ls(int model, int dim, double delta, const double *data, size_t n, const 
   int r = -1;
   DISPATCH(model, dim, r = t_ls<M>(data, n, mask, org, mc, par, mom_out));
   return r;
+}
+
+// the minimal angle between two rays (radians), as lsqr_model_cfg::aux
+void hm_set_aux(double aux) {
+  const double ce = sin(aux);
+  g_aux = ce * ce;
+}
+
+// USModel::finish: the solution of the analytic system x (12 single, 9 pointer) -> 20 (17) parameters
+int hm_us_finish(int single, const double *x12, double *par) {
+  if (single) {
+    USModel<true>::finish(x12, par);
+    return USModel<true>::P;
+  }
+  USModel<false>::finish(x12, par);
+  return USModel<false>::P;
 }
 
 int hm_us_lm(int single, const double *data, size_t n, const double *x0, double tol, int maxfev,
