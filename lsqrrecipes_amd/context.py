@@ -523,6 +523,10 @@ class Context:
         -> dict: labels (int32 per record in upload order; a numpy array, or the caller's tensor), residuals (float64
         per record: the residual to the assigned model, +inf for -1; None unless want_residuals) and counts (uint64,
         M + 1: records per model, then the unassigned ones)."""
+        return self._assign(self._lib.lsqr_assign, params, want_residuals, labels_out)
+
+    def _assign(self, call, params, want_residuals, labels_out):
+        """lsqr_assign or lsqr_assign_dense -> assign's dict"""
         par, m, total, on_device, labels, l_ptr = self._assign_args(params, labels_out)
         if on_device and want_residuals:
             raise ValueError("want_residuals goes with host labels")
@@ -530,8 +534,7 @@ class Context:
         counts = np.zeros(m + 1, dtype=np.uint64)
         if m == 0:
             counts[0] = total
-        self._chk(self._lib.lsqr_assign(self._h, L.ptr(par), m, 1 if on_device else 0, l_ptr, L.ptr(res),
-                                        L.ptr(counts)))
+        self._chk(call(self._h, L.ptr(par), m, 1 if on_device else 0, l_ptr, L.ptr(res), L.ptr(counts)))
         if not on_device:
             labels = labels[:total]
         return dict(labels=labels, residuals=res[:total] if res is not None else None, counts=counts)
@@ -547,7 +550,7 @@ class Context:
         return self._refine(self._lib.lsqr_refine, params, max_rounds, labels_out)[0]
 
     def _refine(self, call, params, max_rounds, labels_out):
-        """lsqr_refine or lsqr_refine_lm -> (refine's dict, the fits as a structured array)"""
+        """lsqr_refine, lsqr_refine_lm or lsqr_refine_dense -> (refine's dict, the fits as a structured array)"""
         par, m, total, on_device, labels, l_ptr = self._assign_args(params, labels_out)
         if int(max_rounds) < 0:
             raise ValueError("max_rounds must not be negative")
@@ -584,18 +587,7 @@ class Context:
         |a . params[m] - b| < delta, -1 when none agrees (and for a row with a non-finite slot among its n + 1).  The
         dot product is the running sum in slot order, so labels and residuals equal mask() / residuals() of that row
         bit for bit.  Any other model raises LsqrError(ERR_INVALID).  labels_out and the result as for assign."""
-        par, m, total, on_device, labels, l_ptr = self._assign_args(params, labels_out)
-        if on_device and want_residuals:
-            raise ValueError("want_residuals goes with host labels")
-        res = np.full(max(total, 1), np.inf) if want_residuals else None
-        counts = np.zeros(m + 1, dtype=np.uint64)
-        if m == 0:
-            counts[0] = total
-        self._chk(self._lib.lsqr_assign_dense(self._h, L.ptr(par), m, 1 if on_device else 0, l_ptr, L.ptr(res),
-                                              L.ptr(counts)))
-        if not on_device:
-            labels = labels[:total]
-        return dict(labels=labels, residuals=res[:total] if res is not None else None, counts=counts)
+        return self._assign(self._lib.lsqr_assign_dense, params, want_residuals, labels_out)
 
     def refine_dense(self, params, max_rounds=8, labels_out=None):
         """refine for the dense linear system (lsqr_refine_dense): the same loop, and the refit of a regression is the

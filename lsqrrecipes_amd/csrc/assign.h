@@ -32,8 +32,12 @@
 //                      through LDS): k_assign_solve's sum, and k_assign_lm_step's
 //   k_assign_solve     one workgroup per model: assign_sum_chunks, then assign_refit
 //
-// lsqr_refine_lm (assign_lm.h, the geometric sphere) runs this file's loop, assign_run<M, true>: the pass also stores
-// every chunk's presence word, the solve writes into a side array of start rows, and the refit is an LM stage.
+// assign_rounds<F> is the round loop of all six ungrouped calls, written once; a family F says what differs -- its
+// buffers, how parameters become scan rows and come back, which kernels make the pass, what the refit enqueues, its
+// counter words and what it adds to a fit record.  AssignClosed<M> (here) is lsqr_assign's and lsqr_refine's.
+// AssignLm<M> (assign_lm.h, the geometric sphere: lsqr_refine_lm) is AssignClosed<M> whose pass also stores every
+// chunk's presence word, whose solve writes into a side array of start rows and whose refit is an LM stage.
+// AssignDense<NR> (assign_dense.h) is the dense linear system's, with kernels of its own.
 //
 // Order of the sums: kAssignChunk fixes it, as kManyPart does for the batched finish.  Nothing is summed with a
 // floating-point atomic, so two runs of one call give the same bits.
@@ -48,6 +52,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <vector>
 
 #include "devbuf.h"
 #include "host_entry.h"
@@ -116,22 +122,29 @@ LSQR_HD int32_t assign_one(const double *rows, int n_models, const double *x, co
   return label;
 }
 
-// lsqr_assign_host: no context, no device
-inline int host_assign_host(const lsqr_model_cfg *cfg, const double *params, size_t n_models, const void *record,
-                            int32_t *label_out, double *residual_out) {
-  if (!cfg || !cfg_supported(*cfg) || !assign_model_ok(*cfg)) return LSQR_ERR_INVALID;
+// lsqr_assign_host, and (DENSE) lsqr_assign_dense_host: no context, no device.  DENSE takes the dense linear system
+// alone, whose parameters are cfg->dim coefficients; its scan rows (assign_dense.h) are zero beyond them
+template <bool DENSE>
+int host_assign_host(const lsqr_model_cfg *cfg, const double *params, size_t n_models, const void *record,
+                     int32_t *label_out, double *residual_out) {
+  if (!cfg || !cfg_supported(*cfg) || !(DENSE ? cfg->model == LSQR_MODEL_DENSE : assign_model_ok(*cfg)))
+    return LSQR_ERR_INVALID;
   if (n_models == 0) return LSQR_OK;
   if (n_models > (size_t)kAssignMaxModels || !params || !record || !label_out) return LSQR_ERR_INVALID;
   ModelConsts mc;
   model_consts(*cfg, &mc);
   return dispatch(*cfg, [&](auto tag) -> int {
     typedef typename decltype(tag)::type M;
-    if constexpr (AssignModel<M>::value) {
-      double rows[kAssignMaxModels * M::SP];
-      for (size_t m = 0; m < n_models; m++) assign_make_row<M>(params + m * M::P, mc, rows + m * M::SP);
+    if constexpr (DENSE ? (bool)M::IS_DENSE : AssignModel<M>::value) {
+      const size_t p = DENSE ? (size_t)cfg->dim : (size_t)M::P;
+      std::vector<double> rows(n_models * M::SP, 0.0);  // scan rows, as lsqr_mask makes one (assign_make_row)
+      for (size_t m = 0; m < n_models; m++) {
+        for (size_t j = 0; j < p; j++) rows[m * M::SP + j] = params[m * p + j];
+        M::prepare(&rows[m * M::SP], mc);
+      }
       double x[M::REC];
       M::load((const double *)record, mc, x);
-      *label_out = assign_one<M>(rows, (int)n_models, x, mc, residual_out);
+      *label_out = assign_one<M>(rows.data(), (int)n_models, x, mc, residual_out);
       return LSQR_OK;
     } else {
       return LSQR_ERR_INVALID;
@@ -408,11 +421,29 @@ struct AssignLmOut {  // lsqr_refine_lm: what the LM run of one model's last ref
   double cost;
 };
 
-struct AssignBufs {  // owned by the context, grown on demand
-  DevBuf<double> d_par, d_rows, d_partials, d_res;
+// what every family of the round loop holds: the scan rows, the chunk partials, the labels of this round and of the one
+// before, the residuals, the counter words, and their pinned staging
+struct AssignCore {
+  DevBuf<double> d_rows, d_partials, d_res;
   DevBuf<int32_t> d_labels[2];
   DevBuf<unsigned long long> d_cnt;
-  PinBuf<char> h_pin;  // kAssignPinBytes, laid out by the kAssignPin offsets
+  PinBuf<char> h_pin;  // the family's AssignPin
+};
+
+// h_pin: kAssignMaxModels rows of at most ROW_MAX doubles, the counter words -- ASG_CHANGED, then 1 + BLOCKS blocks of
+// kAssignMaxModels (ASG_COUNT, ASG_USED, ASG_OK, ...) --, then OWN bytes of the family's own
+template <int ROW_MAX, int BLOCKS, size_t OWN>
+struct AssignPin {
+  static constexpr int row_max = ROW_MAX;
+  static constexpr size_t words = ASG_USED + (size_t)BLOCKS * kAssignMaxModels;
+  static constexpr size_t cnt = sizeof(double) * kAssignMaxModels * ROW_MAX;
+  static constexpr size_t own = cnt + sizeof(unsigned long long) * words;
+  static constexpr size_t bytes = own + OWN;
+};
+
+struct AssignBufs {  // owned by the context (lsqr_ctx::assign), grown on demand
+  AssignCore core;
+  DevBuf<double> d_par;
   // the LM stage of lsqr_refine_lm (assign_lm.h)
   DevBuf<double> d_start, d_lm_partials;
   DevBuf<unsigned long long> d_presence, d_lm_mask;  // one word per chunk; the bits of the models whose LM goes on
@@ -421,12 +452,6 @@ struct AssignBufs {  // owned by the context, grown on demand
   DevBuf<AssignLmOut> d_lm_out;
 };
 
-// h_pin: the rows, the ASG_ words, then lsqr_refine_lm's AssignLmOut per model and its live counter
-constexpr size_t kAssignPinCnt = sizeof(double) * kAssignMaxModels * 16;
-constexpr size_t kAssignPinLm = kAssignPinCnt + sizeof(unsigned long long) * ASG_WORDS;
-constexpr size_t kAssignPinLive = kAssignPinLm + sizeof(AssignLmOut) * kAssignMaxModels;
-constexpr size_t kAssignPinBytes = kAssignPinLive + sizeof(unsigned long long);
-
 struct AssignJob {
   hipStream_t stream = nullptr;
   lsqr_model_cfg cfg{};
@@ -434,9 +459,8 @@ struct AssignJob {
   const double *data = nullptr;  // the context's records: n of them, `stride` doubles apart
   size_t stride = 0;
   uint32_t n = 0;
-  AssignBufs *B = nullptr;
   // the call
-  double *params = nullptr;  // host, n_models rows of M::P: read, and written when a refit ran
+  double *params = nullptr;  // host, n_models rows of the model's parameters: read, and written when a refit ran
   size_t n_models = 0, max_rounds = 0;
   int on_device = 0;
   int32_t *labels_out = nullptr;
@@ -449,84 +473,72 @@ struct AssignJob {
   char err[256] = {0};
 };
 
-// lsqr_refine's and lsqr_refine_grouped's answer for one model of a set that ran `rounds` refit rounds; okf, used: the
-// ASG_OK and ASG_USED words of its last refit
-template <class M>
-void assign_fit_out(size_t rounds, unsigned long long okf, unsigned long long used, int32_t *status,
-                    lsqr_fit_info *fit) {
+// a refine call's answer for one model of a set that ran `rounds` refit rounds; okf, used: the ASG_OK and ASG_USED
+// words of its last refit; n_params: what a model that was fitted reports
+inline void assign_fit_out(size_t rounds, unsigned long long okf, unsigned long long used, int32_t n_params,
+                           int32_t *status, lsqr_fit_info *fit) {
   const bool ok = rounds == 0 || okf != 0;
   *status = ok ? LSQR_OK : LSQR_EMPTY;
   memset(fit, 0, sizeof *fit);
   if (rounds > 0) {
-    fit->n_params = ok ? (int32_t)M::P : 0;
+    fit->n_params = ok ? n_params : 0;
     fit->n_used = used;
   }
 }
 
-#if defined(__HIPCC__)
-// the LM stage of lsqr_refine_lm's round (assign_lm.h): its buffers, and the refit of every model from the moments
-// and the presence words the pass has just left, under the labels `lab`; it leaves the new rows in B.d_rows
-template <class M> int assign_lm_reserve(AssignJob &J, uint32_t chunks);
-template <class M> int assign_lm_run(AssignJob &J, const int32_t *lab, uint32_t chunks);
-#endif
-
-// lsqr_refine's loop (lsqr_assign: max_rounds == 0).  Round r: one pass -- labels L_r and, unless it is the last
-// round allowed, the moments of L_r --, the 8-byte changed-counter (with the counts: one copy) to the host, one solve
-// launch.  Returns after the stream has drained; the outputs are written only then.
-// LM (lsqr_refine_lm, the geometric sphere): the same loop; the refit is assign_lm_run, and the fits carry its record.
-template <class M, bool LM = false>
-int assign_run(AssignJob &J) {
-  AssignBufs &B = *J.B;
-  const int nm = (int)J.n_models, org_off = fit_origin_offset<M>(J.cfg);
-  const uint32_t n = J.n, chunks = assign_chunks(n);
+// THE round loop of the six ungrouped calls (an assign call: max_rounds == 0).  Round r: the pass -- labels L_r and,
+// unless it is the last round allowed, whatever the refit needs of L_r --, the 8-byte changed-counter (with the counts:
+// one copy) to the host, one synchronisation, then the refit under L_r.  Returns after the stream has drained; the
+// outputs are written only then.  What differs from call to call is the family F (by value: a few references):
+//   F::Pin, F::SP        its AssignPin, and the doubles of one of its scan rows
+//   core()               the AssignCore among its buffers
+//   chunks_of(n)         its chunks of n records
+//   reserve(J, refine)   grows its own buffers (and d_partials, whose size is its own)
+//   rows_up(J, h_rows)   enqueues the caller's parameters -> d_rows, staged through h_rows
+//   pass(J, last, lab, res, old)   enqueues the pass of this round, with all that has to be under way before the sync
+//   refit(J, lab)        after the sync: enqueues the refit under the labels lab; it leaves the new rows in d_rows
+//   results(J)           enqueues its own result copies (the rows and the counter words are copied here)
+//   rows_down(J, h_rows) the rows that came back -> the caller's parameters
+//   n_params(J)          what a fitted model's record reports
+//   fit_more(J, m, h_cnt, fit)   what it adds to model m's record after a refit ran
+// AssignClosed<M> is lsqr_assign's and lsqr_refine's, AssignLm<M> (assign_lm.h) lsqr_refine_lm's, AssignDense<NR>
+// (assign_dense.h) the dense pair's.
+template <class F>
+int assign_rounds(AssignJob &J, F fam) {
+  typedef typename F::Pin Pin;
+  AssignCore &C = fam.core();
+  const int nm = (int)J.n_models;
+  const uint32_t n = J.n;
   const bool refine = J.max_rounds > 0;
   // no refit and device pointers: the kernel writes the caller's buffers
   const bool direct = !refine && J.on_device && J.labels_out;
-  static_assert(M::SP <= 16 && M::P <= 16, "pinned staging of the rows");
-  if (!B.h_pin.get()) MANYCHK(B.h_pin.alloc(kAssignPinBytes));
-  MANYCHK(many_grow(B.d_par, (size_t)kAssignMaxModels * 16));
-  MANYCHK(many_grow(B.d_rows, (size_t)kAssignMaxModels * 16));
-  MANYCHK(many_grow(B.d_cnt, (size_t)ASG_WORDS));
-  if (!direct) MANYCHK(many_grow(B.d_labels[0], (size_t)n));
-  if (J.residuals_out && !J.on_device) MANYCHK(many_grow(B.d_res, (size_t)n));
-  if (refine) {
-    MANYCHK(many_grow(B.d_labels[1], (size_t)n));
-    MANYCHK(many_grow(B.d_partials, (size_t)chunks * nm * M::NMOM));
-    if constexpr (LM) {
-      const int st = assign_lm_reserve<M>(J, chunks);
-      if (st != LSQR_OK) return st;
-    }
-  }
-  double *h_rows = (double *)B.h_pin.get();
-  unsigned long long *h_cnt = (unsigned long long *)(B.h_pin.get() + kAssignPinCnt);
-  [[maybe_unused]] AssignLmOut *h_lm = (AssignLmOut *)(B.h_pin.get() + kAssignPinLm);
+  static_assert(F::SP <= Pin::row_max, "pinned staging of the rows");
+  if (!C.h_pin.get()) MANYCHK(C.h_pin.alloc(Pin::bytes));
+  MANYCHK(many_grow(C.d_rows, (size_t)kAssignMaxModels * Pin::row_max));
+  MANYCHK(many_grow(C.d_cnt, Pin::words));
+  if (!direct) MANYCHK(many_grow(C.d_labels[0], (size_t)n));
+  if (J.residuals_out && !J.on_device) MANYCHK(many_grow(C.d_res, (size_t)n));
+  if (refine) MANYCHK(many_grow(C.d_labels[1], (size_t)n));
+  int st = fam.reserve(J, refine);
+  if (st != LSQR_OK) return st;
+  double *h_rows = (double *)C.h_pin.get();
+  unsigned long long *h_cnt = (unsigned long long *)(C.h_pin.get() + Pin::cnt);
 
-  memcpy(h_rows, J.params, sizeof(double) * (size_t)nm * M::P);
-  MANYCHK(hipMemcpyAsync(B.d_par, h_rows, sizeof(double) * (size_t)nm * M::P, hipMemcpyHostToDevice, J.stream));
-  hipLaunchKernelGGL((k_assign_prepare<M>), dim3(1), dim3(kBlock), 0, J.stream, B.d_par, nullptr, (uint64_t)nm, nm, J.mc,
-                     B.d_rows);  // one group, every row there
-  MANYCHK(hipGetLastError());
-  MANYCHK(hipMemsetAsync(B.d_cnt, 0, sizeof(unsigned long long) * ASG_WORDS, J.stream));
+  if ((st = fam.rows_up(J, h_rows)) != LSQR_OK) return st;
+  MANYCHK(hipMemsetAsync(C.d_cnt, 0, sizeof(unsigned long long) * Pin::words, J.stream));
 
   int cur = 0;
   size_t r = 0;
   bool converged = false;
   for (;;) {
     const bool last = r == J.max_rounds;
-    int32_t *lab = direct ? J.labels_out : B.d_labels[cur].get();
-    double *res = !J.residuals_out ? nullptr : J.on_device ? J.residuals_out : B.d_res.get();
-    const int32_t *old = r > 0 ? B.d_labels[cur ^ 1].get() : nullptr;
+    int32_t *lab = direct ? J.labels_out : C.d_labels[cur].get();
+    double *res = !J.residuals_out ? nullptr : J.on_device ? J.residuals_out : C.d_res.get();
+    const int32_t *old = r > 0 ? C.d_labels[cur ^ 1].get() : nullptr;
     if (r > 0)
-      MANYCHK(hipMemsetAsync(B.d_cnt, 0, sizeof(unsigned long long) * (ASG_COUNT + kAssignMaxModels), J.stream));
-    if (last)
-      hipLaunchKernelGGL((k_assign_moments<M, false>), dim3(chunks), dim3(kBlock), 0, J.stream, J.data, J.stride, n,
-                         B.d_rows, nm, org_off, J.mc, lab, res, old, B.d_cnt, nullptr, nullptr);
-    else
-      hipLaunchKernelGGL((k_assign_moments<M, true>), dim3(chunks), dim3(kBlock), 0, J.stream, J.data, J.stride, n,
-                         B.d_rows, nm, org_off, J.mc, lab, res, old, B.d_cnt, B.d_partials,
-                         LM ? B.d_presence.get() : nullptr);
-    MANYCHK(hipGetLastError());
-    MANYCHK(hipMemcpyAsync(h_cnt, B.d_cnt, sizeof(unsigned long long) * (ASG_COUNT + kAssignMaxModels),
+      MANYCHK(hipMemsetAsync(C.d_cnt, 0, sizeof(unsigned long long) * (ASG_COUNT + kAssignMaxModels), J.stream));
+    if ((st = fam.pass(J, last, lab, res, old)) != LSQR_OK) return st;
+    MANYCHK(hipMemcpyAsync(h_cnt, C.d_cnt, sizeof(unsigned long long) * (ASG_COUNT + kAssignMaxModels),
                           hipMemcpyDeviceToHost, J.stream));
     MANYCHK(hipStreamSynchronize(J.stream));
     if (r > 0 && h_cnt[ASG_CHANGED] == 0) {
@@ -534,55 +546,101 @@ int assign_run(AssignJob &J) {
       break;
     }
     if (last) break;
-    if constexpr (LM) {
-      const int st = assign_lm_run<M>(J, lab, chunks);
-      if (st != LSQR_OK) return st;
-    } else {
-      hipLaunchKernelGGL((k_assign_solve<M>), dim3(nm), dim3(kBlock), 0, J.stream, B.d_partials, chunks, nm, org_off,
-                         J.mc, B.d_rows, B.d_cnt, nullptr);
-      MANYCHK(hipGetLastError());
-    }
+    if ((st = fam.refit(J, lab)) != LSQR_OK) return st;
     r++;
     cur ^= 1;
   }
 
   // results: the rows and what the last refit did, then the labels of the last pass
   if (r > 0) {
-    MANYCHK(hipMemcpyAsync(h_rows, B.d_rows, sizeof(double) * (size_t)nm * M::SP, hipMemcpyDeviceToHost, J.stream));
-    MANYCHK(hipMemcpyAsync(h_cnt + ASG_USED, B.d_cnt + ASG_USED, sizeof(unsigned long long) * 2 * kAssignMaxModels,
+    MANYCHK(hipMemcpyAsync(h_rows, C.d_rows, sizeof(double) * (size_t)nm * F::SP, hipMemcpyDeviceToHost, J.stream));
+    MANYCHK(hipMemcpyAsync(h_cnt + ASG_USED, C.d_cnt + ASG_USED, sizeof(unsigned long long) * (Pin::words - ASG_USED),
                           hipMemcpyDeviceToHost, J.stream));
-    if constexpr (LM)
-      MANYCHK(hipMemcpyAsync(h_lm, B.d_lm_out, sizeof(AssignLmOut) * (size_t)nm, hipMemcpyDeviceToHost, J.stream));
+    if ((st = fam.results(J)) != LSQR_OK) return st;
   }
   if (J.labels_out && !direct)
-    MANYCHK(hipMemcpyAsync(J.labels_out, B.d_labels[cur], sizeof(int32_t) * (size_t)n,
+    MANYCHK(hipMemcpyAsync(J.labels_out, C.d_labels[cur], sizeof(int32_t) * (size_t)n,
                           J.on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, J.stream));
   if (J.residuals_out && !J.on_device)
-    MANYCHK(hipMemcpyAsync(J.residuals_out, B.d_res, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, J.stream));
+    MANYCHK(hipMemcpyAsync(J.residuals_out, C.d_res, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, J.stream));
   MANYCHK(hipStreamSynchronize(J.stream));
-  if (r > 0)
-    for (int m = 0; m < nm; m++)
-      for (int j = 0; j < (int)M::P; j++) J.params[(size_t)m * M::P + j] = h_rows[(size_t)m * M::SP + j];
+  if (r > 0) fam.rows_down(J, h_rows);
   if (J.counts_out) {
     uint64_t sum = 0;
     for (int m = 0; m < nm; m++) sum += (J.counts_out[m] = h_cnt[ASG_COUNT + m]);
     J.counts_out[nm] = (uint64_t)n - sum;
   }
-  if (J.fits)  // lsqr_refine, lsqr_refine_lm
+  if (J.fits)  // the refine calls
     for (int m = 0; m < nm; m++) {
-      assign_fit_out<M>(r, h_cnt[ASG_OK + m], h_cnt[ASG_USED + m], &J.status_out[m], &J.fits[m]);
-      if constexpr (LM)
-        if (r > 0) {
-          J.fits[m].lm_info = h_lm[m].lm_info;
-          J.fits[m].lm_nfev = h_lm[m].lm_nfev;
-          J.fits[m].reserved = h_lm[m].stall;
-          J.fits[m].cost = h_lm[m].cost;
-        }
+      assign_fit_out(r, h_cnt[ASG_OK + m], h_cnt[ASG_USED + m], fam.n_params(J), &J.status_out[m], &J.fits[m]);
+      if (r > 0) fam.fit_more(J, m, h_cnt, J.fits[m]);
     }
   J.rounds = r;
   J.converged = converged ? 1 : 0;
   return LSQR_OK;
 }
+
+// The closed form: lsqr_assign, and lsqr_refine, whose refit is one k_assign_solve launch.  Its h_pin has room for what
+// AssignLm<M> (assign_lm.h) reads back -- an AssignLmOut per model and the live counter --, since both run on
+// lsqr_ctx::assign and whichever comes first allocates it.
+template <class M>
+struct AssignClosed {
+  typedef AssignPin<16, 2, sizeof(AssignLmOut) * kAssignMaxModels + sizeof(unsigned long long)> Pin;
+  static constexpr int SP = M::SP;
+  static_assert(Pin::words == ASG_WORDS, "the counter words");
+  static_assert(M::P <= 16, "pinned staging of the parameters");
+  AssignBufs &B;
+
+  AssignCore &core() { return B.core; }
+  static uint32_t chunks_of(uint32_t n) { return assign_chunks(n); }
+  int reserve(AssignJob &J, bool refine) {
+    MANYCHK(many_grow(B.d_par, (size_t)kAssignMaxModels * 16));
+    if (refine) MANYCHK(many_grow(B.core.d_partials, (size_t)chunks_of(J.n) * J.n_models * M::NMOM));
+    return LSQR_OK;
+  }
+  int rows_up(AssignJob &J, double *h_rows) {  // upload, then k_assign_prepare
+    const int nm = (int)J.n_models;
+    memcpy(h_rows, J.params, sizeof(double) * (size_t)nm * M::P);
+    MANYCHK(hipMemcpyAsync(B.d_par, h_rows, sizeof(double) * (size_t)nm * M::P, hipMemcpyHostToDevice, J.stream));
+    hipLaunchKernelGGL((k_assign_prepare<M>), dim3(1), dim3(kBlock), 0, J.stream, B.d_par, nullptr, (uint64_t)nm, nm,
+                       J.mc, B.core.d_rows);  // one group, every row there
+    MANYCHK(hipGetLastError());
+    return LSQR_OK;
+  }
+  // presence: where a pass with moments leaves every chunk's word (nullable)
+  int pass_to(AssignJob &J, bool last, int32_t *lab, double *res, const int32_t *old, unsigned long long *presence) {
+    const int nm = (int)J.n_models, org_off = fit_origin_offset<M>(J.cfg);
+    const uint32_t chunks = chunks_of(J.n);
+    AssignCore &C = B.core;
+    if (last)
+      hipLaunchKernelGGL((k_assign_moments<M, false>), dim3(chunks), dim3(kBlock), 0, J.stream, J.data, J.stride, J.n,
+                         C.d_rows, nm, org_off, J.mc, lab, res, old, C.d_cnt, nullptr, nullptr);
+    else
+      hipLaunchKernelGGL((k_assign_moments<M, true>), dim3(chunks), dim3(kBlock), 0, J.stream, J.data, J.stride, J.n,
+                         C.d_rows, nm, org_off, J.mc, lab, res, old, C.d_cnt, C.d_partials, presence);
+    MANYCHK(hipGetLastError());
+    return LSQR_OK;
+  }
+  int pass(AssignJob &J, bool last, int32_t *lab, double *res, const int32_t *old) {
+    return pass_to(J, last, lab, res, old, nullptr);
+  }
+  // start (nullable): see k_assign_solve
+  int solve_to(AssignJob &J, double *start) {
+    const int nm = (int)J.n_models;
+    hipLaunchKernelGGL((k_assign_solve<M>), dim3(nm), dim3(kBlock), 0, J.stream, B.core.d_partials, chunks_of(J.n), nm,
+                       fit_origin_offset<M>(J.cfg), J.mc, B.core.d_rows, B.core.d_cnt, start);
+    MANYCHK(hipGetLastError());
+    return LSQR_OK;
+  }
+  int refit(AssignJob &J, const int32_t *) { return solve_to(J, nullptr); }
+  int results(AssignJob &) { return LSQR_OK; }
+  void rows_down(AssignJob &J, const double *h_rows) {
+    for (size_t m = 0; m < J.n_models; m++)
+      for (int j = 0; j < (int)M::P; j++) J.params[m * M::P + j] = h_rows[m * M::SP + j];
+  }
+  static int32_t n_params(const AssignJob &) { return (int32_t)M::P; }
+  void fit_more(AssignJob &, int, const unsigned long long *, lsqr_fit_info &) {}
+};
 #endif  // __HIPCC__
 
 }  // namespace lsqr

@@ -1,7 +1,8 @@
 // assign_dense.h -- lsqr_assign_dense / lsqr_refine_dense: lsqr_assign / lsqr_refine (assign.h) for the dense linear
 // system, DenseLinearEquationSystemParametersEstimator<double,n>, n = 1..64: every row (a | b) of the context's upload
 // goes to the NEAREST of up to 64 regressions it agrees with, and (refine) every regression is fitted again on its own
-// rows, round after round, on the device.
+// rows, round after round, on the device.  The rounds are assign.h's loop, assign_rounds, with the family
+// AssignDense<NR> of this file.
 //
 // The decision for one row is assign_one<DenseModel<NR>> (assign.h): the kernel and lsqr_assign_dense_host run that
 // code, so the residual is the reference's running sum in slot order, sum += x[i] * sp[i], then - b, and the label
@@ -55,7 +56,6 @@
 #include <stdint.h>
 
 #include <algorithm>
-#include <vector>
 
 #include "assign.h"
 #include "dense.h"
@@ -67,31 +67,6 @@ namespace lsqr {
 // 18, 34, 66 and 65 KiB -- so the wide classes still run two workgroups per CU beside it
 template <int NR> constexpr uint32_t kAssignDenseChunk = NR <= 32 ? 256u : 128u;
 constexpr int kAsdBlock = 256;
-
-// lsqr_assign_dense_host: no context, no device
-inline int host_assign_dense_host(const lsqr_model_cfg *cfg, const double *params, size_t n_models,
-                                  const void *record, int32_t *label_out, double *residual_out) {
-  if (!cfg || cfg->model != LSQR_MODEL_DENSE || !cfg_supported(*cfg)) return LSQR_ERR_INVALID;
-  if (n_models == 0) return LSQR_OK;
-  if (n_models > (size_t)kAssignMaxModels || !params || !record || !label_out) return LSQR_ERR_INVALID;
-  ModelConsts mc;
-  model_consts(*cfg, &mc);
-  const int n = (int)cfg->dim;
-  return dispatch(*cfg, [&](auto tag) -> int {
-    typedef typename decltype(tag)::type M;
-    if constexpr (M::IS_DENSE) {
-      std::vector<double> rows(n_models * M::SP, 0.0);  // scan rows: zero beyond n, as lsqr_mask makes one
-      for (size_t m = 0; m < n_models; m++)
-        for (int j = 0; j < n; j++) rows[m * M::SP + j] = params[m * n + j];
-      double x[M::REC];
-      M::load((const double *)record, mc, x);
-      *label_out = assign_one<M>(rows.data(), (int)n_models, x, mc, residual_out);
-      return LSQR_OK;
-    } else {
-      return LSQR_ERR_INVALID;
-    }
-  });
-}
 
 enum { ASD_ROUTE = ASG_WORDS, ASD_WORDS = ASD_ROUTE + kAssignMaxModels };  // SolveOut::pad of the last refit
 
@@ -296,99 +271,86 @@ __global__ __launch_bounds__(64) void k_asd_apply(const SolveOut *__restrict__ o
 
 // ---- host side -----------------------------------------------------------------------------------------------------
 struct AssignDenseBufs {  // owned by the context (lsqr_ctx::assign_dense), grown on demand
-  DevBuf<double> d_rows, d_partials, d_res, d_mom, d_ddpart;
-  DevBuf<int32_t> d_labels[2];
-  DevBuf<unsigned long long> d_cnt, d_presence;
+  AssignCore core;
+  DevBuf<double> d_mom, d_ddpart;
+  DevBuf<unsigned long long> d_presence;
   DevBuf<SolveOut> d_out;
   DevBuf<int> d_flags;
   DevBuf<uint8_t> d_mask;
-  PinBuf<char> h_pin;  // kAsdPinBytes: the rows, the ASG_ / ASD_ words, the flags
 };
-constexpr size_t kAsdPinCnt = sizeof(double) * kAssignMaxModels * 64;
-constexpr size_t kAsdPinFlags = kAsdPinCnt + sizeof(unsigned long long) * ASD_WORDS;
-constexpr size_t kAsdPinBytes = kAsdPinFlags + sizeof(int) * kAssignMaxModels;
 
-// lsqr_refine's loop (assign_run) for the dense system; J.B is not used, B holds the call's buffers.  Round r: one
-// pass -- labels L_r and, unless it is the last round allowed, the blocks of L_r --, the sum and the solve of every
-// model, then ONE copy to the host: the changed-counter with the counts and, with dense_dd, the flags.  Flagged models
-// are solved again from their rows in double-double; k_asd_apply makes the refit decision.  (The solve is enqueued
-// before the host knows whether L_r == L_{r-1}; on convergence its result is not applied.)
+// The dense system's family of the round loop (assign.h: assign_rounds).  Before the round's synchronisation its pass
+// enqueues, unless the round is the last one allowed, the sum and the solve of every model as well, and with dense_dd
+// the copy of the flags: ONE wait brings the changed-counter, the counts and the flags.  (So the solve is enqueued
+// before the host knows whether L_r == L_{r-1}; on convergence its result is not applied.)  The refit solves the
+// flagged models again from their rows in double-double; k_asd_apply makes the refit decision.
 template <int NR>
-int assign_dense_run(AssignJob &J, AssignDenseBufs &B, int dense_fast, int dense_dd) {
-  const int nm = (int)J.n_models, dim = (int)J.cfg.dim, ps = many_dense_ps(dim), ne = (dim + 1) * (dim + 2) / 2;
-  constexpr uint32_t CH = kAssignDenseChunk<NR>;
-  const uint32_t n = J.n, chunks = (uint32_t)(((uint64_t)n + CH - 1) / CH);
-  const bool refine = J.max_rounds > 0;
-  const bool direct = !refine && J.on_device && J.labels_out;  // the kernel writes the caller's buffers
-  const size_t lds_pass = sizeof(double) * CH * (NR + 1);
-  if (!B.h_pin.get()) MANYCHK(B.h_pin.alloc(kAsdPinBytes));
-  MANYCHK(many_grow(B.d_rows, (size_t)kAssignMaxModels * 64));
-  MANYCHK(many_grow(B.d_cnt, (size_t)ASD_WORDS));
-  if (!direct) MANYCHK(many_grow(B.d_labels[0], (size_t)n));
-  if (J.residuals_out && !J.on_device) MANYCHK(many_grow(B.d_res, (size_t)n));
-  if (refine) {
-    MANYCHK(many_grow(B.d_labels[1], (size_t)n));
-    MANYCHK(many_grow(B.d_partials, (size_t)chunks * nm * ps));
-    MANYCHK(many_grow(B.d_presence, (size_t)chunks));
-    MANYCHK(many_grow(B.d_mom, (size_t)nm * ps));
-    MANYCHK(many_grow(B.d_out, (size_t)kAssignMaxModels));
-    MANYCHK(many_grow(B.d_flags, (size_t)kAssignMaxModels));
-    (void)hipFuncSetAttribute((const void *)k_asd_solve, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)many_dense_lds(64));
-    (void)hipFuncSetAttribute((const void *)(k_asd_pass<NR, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+struct AssignDense {
+  typedef AssignPin<64, 3, sizeof(int) * kAssignMaxModels> Pin;  // the ASD_ROUTE block; its own: the flags
+  static_assert(Pin::words == ASD_WORDS, "the counter words");
+  static constexpr int SP = NR;
+  static constexpr uint32_t CH = kAssignDenseChunk<NR>;
+  static constexpr size_t lds_pass = sizeof(double) * CH * (NR + 1);
+  AssignDenseBufs &B;
+  int dense_fast, dense_dd;  // the context's options
+
+  AssignCore &core() { return B.core; }
+  static uint32_t chunks_of(uint32_t n) { return (uint32_t)(((uint64_t)n + CH - 1) / CH); }
+  int reserve(AssignJob &J, bool refine) {
+    if (refine) {
+      const size_t nm = J.n_models, ps = (size_t)many_dense_ps((int)J.cfg.dim), chunks = chunks_of(J.n);
+      MANYCHK(many_grow(B.core.d_partials, chunks * nm * ps));
+      MANYCHK(many_grow(B.d_presence, chunks));
+      MANYCHK(many_grow(B.d_mom, nm * ps));
+      MANYCHK(many_grow(B.d_out, (size_t)kAssignMaxModels));
+      MANYCHK(many_grow(B.d_flags, (size_t)kAssignMaxModels));
+      (void)hipFuncSetAttribute((const void *)k_asd_solve, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)many_dense_lds(64));
+      (void)hipFuncSetAttribute((const void *)(k_asd_pass<NR, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)lds_pass);
+    }
+    (void)hipFuncSetAttribute((const void *)(k_asd_pass<NR, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)lds_pass);
+    return LSQR_OK;
   }
-  (void)hipFuncSetAttribute((const void *)(k_asd_pass<NR, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lds_pass);
-  double *h_rows = (double *)B.h_pin.get();
-  unsigned long long *h_cnt = (unsigned long long *)(B.h_pin.get() + kAsdPinCnt);
-  int *h_flags = (int *)(B.h_pin.get() + kAsdPinFlags);
-
-  for (int m = 0; m < nm; m++)
-    for (int j = 0; j < NR; j++) h_rows[(size_t)m * NR + j] = j < dim ? J.params[(size_t)m * dim + j] : 0.0;
-  MANYCHK(hipMemcpyAsync(B.d_rows, h_rows, sizeof(double) * (size_t)nm * NR, hipMemcpyHostToDevice, J.stream));
-  MANYCHK(hipMemsetAsync(B.d_cnt, 0, sizeof(unsigned long long) * ASD_WORDS, J.stream));
-
-  int cur = 0;
-  size_t r = 0;
-  bool converged = false;
-  for (;;) {
-    const bool last = r == J.max_rounds;
-    int32_t *lab = direct ? J.labels_out : B.d_labels[cur].get();
-    double *res = !J.residuals_out ? nullptr : J.on_device ? J.residuals_out : B.d_res.get();
-    const int32_t *old = r > 0 ? B.d_labels[cur ^ 1].get() : nullptr;
-    if (r > 0)
-      MANYCHK(hipMemsetAsync(B.d_cnt, 0, sizeof(unsigned long long) * (ASG_COUNT + kAssignMaxModels), J.stream));
+  int rows_up(AssignJob &J, double *h_rows) {  // the zero-padded copy
+    const size_t nm = J.n_models, dim = J.cfg.dim;
+    for (size_t m = 0; m < nm; m++)
+      for (size_t j = 0; j < (size_t)NR; j++) h_rows[m * NR + j] = j < dim ? J.params[m * dim + j] : 0.0;
+    MANYCHK(hipMemcpyAsync(B.core.d_rows, h_rows, sizeof(double) * nm * NR, hipMemcpyHostToDevice, J.stream));
+    return LSQR_OK;
+  }
+  int pass(AssignJob &J, bool last, int32_t *lab, double *res, const int32_t *old) {
+    const int nm = (int)J.n_models, dim = (int)J.cfg.dim, ps = many_dense_ps(dim), ne = (dim + 1) * (dim + 2) / 2;
+    const uint32_t chunks = chunks_of(J.n);
+    AssignCore &C = B.core;
     if (last) {
       hipLaunchKernelGGL((k_asd_pass<NR, false>), dim3(chunks), dim3(kAsdBlock), lds_pass, J.stream, J.data, J.stride,
-                         n, dim, B.d_rows, nm, J.mc, lab, res, old, B.d_cnt, nullptr, ps, nullptr);
+                         J.n, dim, C.d_rows, nm, J.mc, lab, res, old, C.d_cnt, nullptr, ps, nullptr);
       MANYCHK(hipGetLastError());
-    } else {
-      hipLaunchKernelGGL((k_asd_pass<NR, true>), dim3(chunks), dim3(kAsdBlock), lds_pass, J.stream, J.data, J.stride,
-                         n, dim, B.d_rows, nm, J.mc, lab, res, old, B.d_cnt, B.d_partials, ps, B.d_presence);
-      MANYCHK(hipGetLastError());
-      hipLaunchKernelGGL(k_asd_sum, dim3(nm, (ne + 1 + kAsdBlock - 1) / kAsdBlock), dim3(kAsdBlock), 0, J.stream,
-                         B.d_partials, B.d_presence, chunks, nm, dim, ps, B.d_cnt, B.d_mom);
-      MANYCHK(hipGetLastError());
-      if (dense_dd) MANYCHK(hipMemsetAsync(B.d_flags, 0, sizeof(int) * kAssignMaxModels, J.stream));
-      hipLaunchKernelGGL(k_asd_solve, dim3(nm), dim3(256), many_dense_lds(dim), J.stream, B.d_mom, ps, dim, dense_fast,
-                         B.d_out, dense_dd ? B.d_flags.get() : (int *)nullptr);
-      MANYCHK(hipGetLastError());
-      if (dense_dd)
-        MANYCHK(hipMemcpyAsync(h_flags, B.d_flags, sizeof(int) * (size_t)nm, hipMemcpyDeviceToHost, J.stream));
+      return LSQR_OK;
     }
-    MANYCHK(hipMemcpyAsync(h_cnt, B.d_cnt, sizeof(unsigned long long) * (ASG_COUNT + kAssignMaxModels),
-                          hipMemcpyDeviceToHost, J.stream));
-    MANYCHK(hipStreamSynchronize(J.stream));
-    if (r > 0 && h_cnt[ASG_CHANGED] == 0) {
-      converged = true;
-      break;
-    }
-    if (last) break;
+    hipLaunchKernelGGL((k_asd_pass<NR, true>), dim3(chunks), dim3(kAsdBlock), lds_pass, J.stream, J.data, J.stride, J.n,
+                       dim, C.d_rows, nm, J.mc, lab, res, old, C.d_cnt, C.d_partials, ps, B.d_presence);
+    MANYCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_asd_sum, dim3(nm, (ne + 1 + kAsdBlock - 1) / kAsdBlock), dim3(kAsdBlock), 0, J.stream,
+                       C.d_partials, B.d_presence, chunks, nm, dim, ps, C.d_cnt, B.d_mom);
+    MANYCHK(hipGetLastError());
+    if (dense_dd) MANYCHK(hipMemsetAsync(B.d_flags, 0, sizeof(int) * kAssignMaxModels, J.stream));
+    hipLaunchKernelGGL(k_asd_solve, dim3(nm), dim3(256), many_dense_lds(dim), J.stream, B.d_mom, ps, dim, dense_fast,
+                       B.d_out, dense_dd ? B.d_flags.get() : (int *)nullptr);
+    MANYCHK(hipGetLastError());
+    if (dense_dd)
+      MANYCHK(hipMemcpyAsync(h_flags(), B.d_flags, sizeof(int) * (size_t)nm, hipMemcpyDeviceToHost, J.stream));
+    return LSQR_OK;
+  }
+  int refit(AssignJob &J, const int32_t *lab) {
+    const int nm = (int)J.n_models, dim = (int)J.cfg.dim, ps = many_dense_ps(dim);
+    const uint32_t n = J.n;
     if (dense_dd) {  // the ill-conditioned ones again from their rows, in double-double (launch_solve_dense's route)
       bool any = false;
       for (int m = 0; m < nm; m++) {
-        if (!h_flags[m]) continue;
+        if (!h_flags()[m]) continue;
         if (!any) {
           MANYCHK(many_grow(B.d_ddpart, (size_t)2 * kDdNe * kDdBlocks));
           MANYCHK(many_grow(B.d_mask, (size_t)n));
@@ -408,47 +370,22 @@ int assign_dense_run(AssignJob &J, AssignDenseBufs &B, int dense_fast, int dense
         MANYCHK(hipGetLastError());
       }
     }
-    hipLaunchKernelGGL(k_asd_apply, dim3(nm), dim3(64), 0, J.stream, B.d_out, dim, NR, B.d_rows, B.d_cnt);
+    hipLaunchKernelGGL(k_asd_apply, dim3(nm), dim3(64), 0, J.stream, B.d_out, dim, NR, B.core.d_rows, B.core.d_cnt);
     MANYCHK(hipGetLastError());
-    r++;
-    cur ^= 1;
+    return LSQR_OK;
   }
-
-  // results: the rows and what the last refit did, then the labels of the last pass
-  if (r > 0) {
-    MANYCHK(hipMemcpyAsync(h_rows, B.d_rows, sizeof(double) * (size_t)nm * NR, hipMemcpyDeviceToHost, J.stream));
-    MANYCHK(hipMemcpyAsync(h_cnt + ASG_USED, B.d_cnt + ASG_USED, sizeof(unsigned long long) * 3 * kAssignMaxModels,
-                          hipMemcpyDeviceToHost, J.stream));
+  int results(AssignJob &) { return LSQR_OK; }
+  void rows_down(AssignJob &J, const double *h_rows) {
+    const size_t dim = J.cfg.dim;
+    for (size_t m = 0; m < J.n_models; m++)
+      for (size_t j = 0; j < dim; j++) J.params[m * dim + j] = h_rows[m * NR + j];
   }
-  if (J.labels_out && !direct)
-    MANYCHK(hipMemcpyAsync(J.labels_out, B.d_labels[cur], sizeof(int32_t) * (size_t)n,
-                          J.on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, J.stream));
-  if (J.residuals_out && !J.on_device)
-    MANYCHK(hipMemcpyAsync(J.residuals_out, B.d_res, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, J.stream));
-  MANYCHK(hipStreamSynchronize(J.stream));
-  if (r > 0)
-    for (int m = 0; m < nm; m++)
-      for (int j = 0; j < dim; j++) J.params[(size_t)m * dim + j] = h_rows[(size_t)m * NR + j];
-  if (J.counts_out) {
-    uint64_t sum = 0;
-    for (int m = 0; m < nm; m++) sum += (J.counts_out[m] = h_cnt[ASG_COUNT + m]);
-    J.counts_out[nm] = (uint64_t)n - sum;
+  static int32_t n_params(const AssignJob &J) { return (int32_t)J.cfg.dim; }
+  void fit_more(AssignJob &, int m, const unsigned long long *h_cnt, lsqr_fit_info &fit) {
+    fit.reserved = (int32_t)h_cnt[ASD_ROUTE + m];
   }
-  if (J.fits)  // lsqr_refine_dense
-    for (int m = 0; m < nm; m++) {
-      const bool ok = r == 0 || h_cnt[ASG_OK + m] != 0;
-      J.status_out[m] = ok ? LSQR_OK : LSQR_EMPTY;
-      memset(&J.fits[m], 0, sizeof J.fits[m]);
-      if (r > 0) {
-        J.fits[m].n_params = ok ? dim : 0;
-        J.fits[m].n_used = h_cnt[ASG_USED + m];
-        J.fits[m].reserved = (int32_t)h_cnt[ASD_ROUTE + m];
-      }
-    }
-  J.rounds = r;
-  J.converged = converged ? 1 : 0;
-  return LSQR_OK;
-}
+  int *h_flags() { return (int *)(B.core.h_pin.get() + Pin::own); }
+};
 #endif  // __HIPCC__
 
 }  // namespace lsqr

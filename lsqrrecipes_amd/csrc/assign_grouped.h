@@ -191,7 +191,6 @@ struct AssignGrpJob {
   size_t n_groups = 0, max_models = 0, max_rounds = 0;
   int on_device = 0;
   bool refine = false;
-  bool lm = false;  // lsqr_refine_lm_grouped
   double *params = nullptr;  // host, n_groups * max_models rows of M::P: read, and written where a refit ran
   const size_t *n_models = nullptr;
   int32_t *labels_out = nullptr;
@@ -430,7 +429,7 @@ int assign_grouped_run(AssignGrpJob &J) {
     for (size_t m = 0; m < MM; m++) {
       const size_t e = g * MM + m;
       if (m < nm) {
-        assign_fit_out<M>(rg, h_cnt[c_ok + e], h_cnt[c_used + e], &J.status_out[e], &J.fits[e]);
+        assign_fit_out(rg, h_cnt[c_ok + e], h_cnt[c_used + e], (int32_t)M::P, &J.status_out[e], &J.fits[e]);
         if constexpr (LM)
           if (rg > 0) {
             J.fits[e].lm_info = h_lm[e].lm_info;

@@ -1,6 +1,7 @@
-// assign_lm.h -- lsqr_refine_lm: lsqr_refine's loop (assign.h: assign_run) for the sphere with LSQR_LS_GEOMETRIC.  The
-// refit of a round is the algebraic refit of assign.h, kept aside as the START, and then one Levenberg-Marquardt run per
-// model over the records labelled with it, all models in lock-step evaluation rounds, the records read where they are.
+// assign_lm.h -- lsqr_refine_lm: the round loop (assign.h: assign_rounds) for the sphere with LSQR_LS_GEOMETRIC, as the
+// family AssignLm<M>.  The refit of a round is the algebraic refit of assign.h, kept aside as the START, and then one
+// Levenberg-Marquardt run per model over the records labelled with it, all models in lock-step evaluation rounds, the
+// records read where they are.
 //
 //   k_assign_moments<M, true>   as in lsqr_refine; it also stores every chunk's presence word
 //   k_assign_solve              as in lsqr_refine, but into the start rows (its `start` argument): the round's rows stay
@@ -33,7 +34,8 @@
 // Budget: see DESIGN.md section 14.2.  LDS of the pass: two buffers of 4 x NMOM_LM doubles (3.4 KiB at D = 8); of the
 // step: one tile of partials (30 KiB at NMOM_LM <= 16, else up to 55 KiB), the moment block and LmState (1.7 KiB).
 //
-// Included by assign.h's users after it; assign_run<M, true> calls assign_lm_reserve and assign_lm_run.
+// assign_lm_start, assign_lm_stage and assign_lm_finish are the pieces of the init and step kernels that the grouped
+// call's kernels (assign_lm_grouped.h) run too, and assign_lm_evals is the evaluation loop of both drivers.
 #pragma once
 #include "assign.h"
 #include "lm_core.h"
@@ -41,6 +43,52 @@
 namespace lsqr {
 
 #if defined(__HIPCC__)
+// The pieces that k_assign_lm_init / k_assign_lm_step share with k_asg_grp_lm_init / k_asg_grp_lm_step
+// (assign_lm_grouped.h), so that a group's models start, advance and finish by the code of lsqr_refine_lm's.
+//
+// One lane per model of a set, the whole wave calling.  there: the lane has a model; okf, out, st, start (read and
+// written only where `there`): its answer from the algebraic refit (cleared: the LM decides it), its AssignLmOut, its
+// LmState and its start row.  -> the mask of the models whose LM run starts
+template <class M>
+__device__ __forceinline__ unsigned long long assign_lm_start(bool there, unsigned long long *okf, AssignLmOut *out,
+                                                              LmState *st, const double *start, int n, double ftol,
+                                                              double xtol, double gtol, int maxfev) {
+  const bool go = there && *okf != 0;
+  if (there) {
+    *okf = 0;
+    *out = AssignLmOut{0, 0, 0, 0, 0.0};
+  }
+  if (go) lm_init(*st, n, start, ftol, xtol, gtol, maxfev, 100.0);
+  return __ballot(go);
+}
+
+// an LmState between global memory and LDS, word by word, by a workgroup of WG lanes
+template <int WG>
+__device__ __forceinline__ void assign_lm_stage(const LmState *from, LmState *to) {
+  constexpr int NW = (int)(sizeof(LmState) / sizeof(int));
+  const int *src = (const int *)from;
+  int *dst = (int *)to;
+  for (int i = threadIdx.x; i < NW; i += WG) dst[i] = src[i];
+}
+
+// One lane, after lm_advance said that model m's run is over: its AssignLmOut and, with info in 1..4, its new scan row
+// by assign_make_row and its ok word; then it leaves its set's live mask and the live counter
+template <class M>
+__device__ __forceinline__ void assign_lm_finish(const LmState &S, const ModelConsts &mc, int m, double *row,
+                                                 unsigned long long *okf, AssignLmOut *out, unsigned long long *mask,
+                                                 uint32_t *live) {
+  *out = AssignLmOut{S.info, S.nfev, S.stall, 0, S.fnorm * S.fnorm};
+  if (S.info >= 1 && S.info <= 4) {  // vnl_levenberg_marquardt::minimize -> true
+    double p[LM_NMAX], r[M::SP];
+    M::lm_finalize(S.x, p);
+    assign_make_row<M>(p, mc, r);
+    for (int j = 0; j < (int)M::SP; j++) row[j] = r[j];
+    *okf = 1;
+  }
+  atomicAnd(mask, ~(1ull << m));
+  atomicSub(live, 1u);
+}
+
 // start: the n_models start rows k_assign_solve left; counters[ASG_OK + m]: its answer, cleared here
 template <class M>
 __global__ __launch_bounds__(64) void k_assign_lm_init(const double *__restrict__ start, int n_models, int n,
@@ -50,14 +98,8 @@ __global__ __launch_bounds__(64) void k_assign_lm_init(const double *__restrict_
                                                        unsigned long long *__restrict__ mask,
                                                        uint32_t *__restrict__ live) {
   const int m = threadIdx.x;
-  const bool there = m < n_models;
-  const bool go = there && counters[ASG_OK + m] != 0;
-  if (there) {
-    counters[ASG_OK + m] = 0;
-    out[m] = AssignLmOut{0, 0, 0, 0, 0.0};
-  }
-  if (go) lm_init(st[m], n, start + (size_t)m * M::SP, ftol, xtol, gtol, maxfev, 100.0);
-  const unsigned long long all = __ballot(go);
+  const unsigned long long all = assign_lm_start<M>(m < n_models, counters + ASG_OK + m, out + m, st + m,
+                                                    start + (size_t)m * M::SP, n, ftol, xtol, gtol, maxfev);
   if (m == 0) {
     *mask = all;
     *live = (uint32_t)__popcll(all);
@@ -153,88 +195,108 @@ __global__ __launch_bounds__(kBlock) void k_assign_lm_step(const double *__restr
                                                            uint32_t *live) {
   constexpr int N = M::NMOM_LM;
   constexpr int kTile = N <= 16 ? 256 : 128;  // chunks per tile: 30 KiB of LDS at N = 15, 55 KiB at N = 55
-  constexpr int NW = (int)(sizeof(LmState) / sizeof(int));
   __shared__ double s_t[kTile * N];
   __shared__ double mom[LM_MOM_MAX];
   __shared__ LmState S;
   const int m = blockIdx.x;
   if (!((*mask >> m) & 1ull)) return;  // finished, or never started (uniform over the workgroup)
   assign_sum_chunks<N, kTile>(partials + (size_t)m * N, (size_t)n_models * N, chunks, s_t, mom);
-  {
-    const int *src = (const int *)&st[m];
-    int *dst = (int *)&S;
-    for (int i = threadIdx.x; i < NW; i += kBlock) dst[i] = src[i];
-  }
+  assign_lm_stage<kBlock>(&st[m], &S);
   __syncthreads();
-  if (threadIdx.x == 0 && !lm_advance(S, mom)) {
-    out[m] = AssignLmOut{S.info, S.nfev, S.stall, 0, S.fnorm * S.fnorm};
-    if (S.info >= 1 && S.info <= 4) {  // vnl_levenberg_marquardt::minimize -> true
-      double p[LM_NMAX], row[M::SP];
-      M::lm_finalize(S.x, p);
-      assign_make_row<M>(p, mc, row);
-      for (int j = 0; j < (int)M::SP; j++) rows[(size_t)m * M::SP + j] = row[j];
-      counters[ASG_OK + m] = 1;
-    }
-    atomicAnd(mask, ~(1ull << m));
-    atomicSub(live, 1u);
-  }
+  if (threadIdx.x == 0 && !lm_advance(S, mom))
+    assign_lm_finish<M>(S, mc, m, rows + (size_t)m * M::SP, counters + ASG_OK + m, out + m, mask, live);
   __syncthreads();
-  {
-    const int *src = (const int *)&S;
-    int *dst = (int *)&st[m];
-    for (int i = threadIdx.x; i < NW; i += kBlock) dst[i] = src[i];
-  }
+  assign_lm_stage<kBlock>(&S, &st[m]);
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------
-template <class M>
-int assign_lm_reserve(AssignJob &J, uint32_t chunks) {
-  AssignBufs &B = *J.B;
-  MANYCHK(many_grow(B.d_start, (size_t)kAssignMaxModels * 16));
-  MANYCHK(many_grow(B.d_presence, (size_t)chunks));
-  MANYCHK(many_grow(B.d_lm_partials, (size_t)chunks * J.n_models * M::NMOM_LM));
-  MANYCHK(many_grow(B.d_lm_mask, 1));
-  MANYCHK(many_grow(B.d_lm_live, 1));
-  MANYCHK(many_grow(B.d_lm_state, (size_t)kAssignMaxModels));
-  MANYCHK(many_grow(B.d_lm_out, (size_t)kAssignMaxModels));
-  return LSQR_OK;
-}
-
-// The refit of one round.  The pass has left the moments of the labels `lab` in B.d_partials and the presence words in
-// B.d_presence.  Per evaluation: one pass, one step, one 4-byte read of the live counter.  Every lm_advance call
-// consumes one evaluation and stops at maxfev, so maxfev evaluations finish every model (many_lm_run's bound).
-template <class M>
-int assign_lm_run(AssignJob &J, const int32_t *lab, uint32_t chunks) {
-  AssignBufs &B = *J.B;
-  const int nm = (int)J.n_models, org_off = fit_origin_offset<M>(J.cfg);
-  int n = 0, maxfev = 0;
-  double ftol = 0, xtol = 0, gtol = 0;
-  lm_settings(J.cfg, &n, &ftol, &xtol, &gtol, &maxfev);
-  uint32_t *h_live = (uint32_t *)(B.h_pin.get() + kAssignPinLive);
-  hipLaunchKernelGGL((k_assign_solve<M>), dim3(nm), dim3(kBlock), 0, J.stream, B.d_partials, chunks, nm, org_off, J.mc,
-                     B.d_rows, B.d_cnt, B.d_start);
-  MANYCHK(hipGetLastError());
-  hipLaunchKernelGGL((k_assign_lm_init<M>), dim3(1), dim3(64), 0, J.stream, B.d_start, nm, n, ftol, xtol, gtol, maxfev,
-                     B.d_cnt, B.d_lm_state, B.d_lm_out, B.d_lm_mask, B.d_lm_live);
-  MANYCHK(hipGetLastError());
-  MANYCHK(hipMemsetAsync(B.d_lm_partials, 0, sizeof(double) * (size_t)chunks * nm * M::NMOM_LM, J.stream));
+// The evaluations of one refit round's LM stage, lsqr_refine_lm's and lsqr_refine_lm_grouped's: pass() and step() each
+// enqueue one launch; then one 4-byte read of the live counter and one synchronisation.  Every lm_advance call consumes
+// one evaluation and stops at maxfev, so maxfev evaluations finish every model (many_lm_run's bound).
+template <class Pass, class Step>
+int assign_lm_evals(hipStream_t stream, int maxfev, const uint32_t *d_live, uint32_t *h_live, char (&err)[256],
+                    Pass pass, Step step) {
+  struct {
+    char (&err)[256];
+  } J{err};  // (MANYCHK reports into J.err)
   for (int round = 0;; round++) {
     if (round > maxfev) {
-      snprintf(J.err, sizeof J.err, "LM stage: %u models still live after %d evaluations", *h_live, round);
+      snprintf(err, sizeof err, "LM stage: %u models still live after %d evaluations", *h_live, round);
       return LSQR_ERR_HIP;
     }
-    hipLaunchKernelGGL((k_assign_lm_pass<M>), dim3(chunks), dim3(kBlock), 0, J.stream, J.data, J.stride, J.n, lab,
-                       B.d_presence, B.d_lm_mask, B.d_lm_state, nm, J.mc, B.d_lm_partials);
+    pass();
     MANYCHK(hipGetLastError());
-    hipLaunchKernelGGL((k_assign_lm_step<M>), dim3(nm), dim3(kBlock), 0, J.stream, B.d_lm_partials, chunks, nm, J.mc,
-                       B.d_lm_state, B.d_rows, B.d_cnt, B.d_lm_out, B.d_lm_mask, B.d_lm_live);
+    step();
     MANYCHK(hipGetLastError());
-    MANYCHK(hipMemcpyAsync(h_live, B.d_lm_live, sizeof(uint32_t), hipMemcpyDeviceToHost, J.stream));
-    MANYCHK(hipStreamSynchronize(J.stream));
+    MANYCHK(hipMemcpyAsync(h_live, d_live, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    MANYCHK(hipStreamSynchronize(stream));
     if (*h_live == 0) break;
   }
   return LSQR_OK;
 }
+
+// lsqr_refine_lm's family: AssignClosed<M> whose pass also leaves the presence words and whose refit is the LM stage.
+// The pass has left the moments of the labels `lab` in d_partials and the presence words in d_presence; the refit is
+// the algebraic solve into the start rows, k_assign_lm_init, the partials cleared, then the evaluations.
+template <class M>
+struct AssignLm : AssignClosed<M> {
+  typedef AssignClosed<M> Base;
+  using Base::B;
+  using Base::chunks_of;
+
+  int reserve(AssignJob &J, bool refine) {
+    const int st = Base::reserve(J, refine);
+    if (st != LSQR_OK || !refine) return st;
+    const uint32_t chunks = chunks_of(J.n);
+    MANYCHK(many_grow(B.d_start, (size_t)kAssignMaxModels * 16));
+    MANYCHK(many_grow(B.d_presence, (size_t)chunks));
+    MANYCHK(many_grow(B.d_lm_partials, (size_t)chunks * J.n_models * M::NMOM_LM));
+    MANYCHK(many_grow(B.d_lm_mask, 1));
+    MANYCHK(many_grow(B.d_lm_live, 1));
+    MANYCHK(many_grow(B.d_lm_state, (size_t)kAssignMaxModels));
+    MANYCHK(many_grow(B.d_lm_out, (size_t)kAssignMaxModels));
+    return LSQR_OK;
+  }
+  int pass(AssignJob &J, bool last, int32_t *lab, double *res, const int32_t *old) {
+    return Base::pass_to(J, last, lab, res, old, B.d_presence.get());
+  }
+  int refit(AssignJob &J, const int32_t *lab) {
+    const int nm = (int)J.n_models;
+    const uint32_t chunks = chunks_of(J.n);
+    int n = 0, maxfev = 0;
+    double ftol = 0, xtol = 0, gtol = 0;
+    lm_settings(J.cfg, &n, &ftol, &xtol, &gtol, &maxfev);
+    const int st = Base::solve_to(J, B.d_start);
+    if (st != LSQR_OK) return st;
+    hipLaunchKernelGGL((k_assign_lm_init<M>), dim3(1), dim3(64), 0, J.stream, B.d_start, nm, n, ftol, xtol, gtol,
+                       maxfev, B.core.d_cnt, B.d_lm_state, B.d_lm_out, B.d_lm_mask, B.d_lm_live);
+    MANYCHK(hipGetLastError());
+    MANYCHK(hipMemsetAsync(B.d_lm_partials, 0, sizeof(double) * (size_t)chunks * nm * M::NMOM_LM, J.stream));
+    return assign_lm_evals(
+        J.stream, maxfev, B.d_lm_live, (uint32_t *)(h_lm() + kAssignMaxModels), J.err,
+        [&] {
+          hipLaunchKernelGGL((k_assign_lm_pass<M>), dim3(chunks), dim3(kBlock), 0, J.stream, J.data, J.stride, J.n, lab,
+                             B.d_presence, B.d_lm_mask, B.d_lm_state, nm, J.mc, B.d_lm_partials);
+        },
+        [&] {
+          hipLaunchKernelGGL((k_assign_lm_step<M>), dim3(nm), dim3(kBlock), 0, J.stream, B.d_lm_partials, chunks, nm,
+                             J.mc, B.d_lm_state, B.core.d_rows, B.core.d_cnt, B.d_lm_out, B.d_lm_mask, B.d_lm_live);
+        });
+  }
+  int results(AssignJob &J) {
+    MANYCHK(hipMemcpyAsync(h_lm(), B.d_lm_out, sizeof(AssignLmOut) * J.n_models, hipMemcpyDeviceToHost, J.stream));
+    return LSQR_OK;
+  }
+  void fit_more(AssignJob &, int m, const unsigned long long *, lsqr_fit_info &fit) {
+    const AssignLmOut &o = h_lm()[m];
+    fit.lm_info = o.lm_info;
+    fit.lm_nfev = o.lm_nfev;
+    fit.reserved = o.stall;
+    fit.cost = o.cost;
+  }
+  // the family's own of h_pin: an AssignLmOut per model, then the live counter's copy
+  AssignLmOut *h_lm() { return (AssignLmOut *)(B.core.h_pin.get() + Base::Pin::own); }
+};
 #endif  // __HIPCC__
 
 }  // namespace lsqr

@@ -21,12 +21,15 @@
 //                             ok[g][m]; then it leaves the group's mask and the live counter, which the host reads (4
 //                             bytes) after every evaluation, for all groups together.
 //
-// Why the bits are lsqr_refine_lm's.  The pass body is the same function on the same records at the same positions
-// inside their chunk (chunk q of the group is chunk q of the fresh context), with the same trial point.  The step's sum
-// starts from 0.0 and adds the chunks' blocks one by one in chunk order: that is the order of assign_sum_chunks, which
-// k_assign_lm_step uses -- tiles through LDS there, sixteen registers here, the additions the same.  lm_init, lm_advance,
-// M::lm_finalize and assign_make_row are the same code.  Nothing is summed with a floating-point atomic; the one
-// counter that all groups share is an integer.  So a group's results depend on its own records and rows alone.
+// Why the bits are lsqr_refine_lm's.  The pass body is the same function, assign_lm_pass_chunk, on the same records at
+// the same positions inside their chunk (chunk q of the group is chunk q of the fresh context), with the same trial
+// point.  The step's sum starts from 0.0 and adds the chunks' blocks one by one in chunk order: that is the order of
+// assign_sum_chunks, which k_assign_lm_step uses -- tiles through LDS there, sixteen registers here, the additions the
+// same; the two sums are the only code of the stage that exists twice.  A model starts in assign_lm_start, its LmState
+// travels by assign_lm_stage, and it finishes in assign_lm_finish (lm_finalize, assign_make_row, the ok word): both
+// pairs of kernels call these functions of assign_lm.h, and both drivers run assign_lm_evals.  Nothing is summed with a
+// floating-point atomic; the one counter that all groups share is an integer.  So a group's results depend on its own
+// records and rows alone.
 //
 // A model absent from a chunk has zeros there: the LM partials are cleared once per refit round (the labels, and so the
 // presence words, are fixed for the round), and the pass writes only the blocks of models that are present and live.
@@ -57,15 +60,9 @@ __global__ __launch_bounds__(64) void k_asg_grp_lm_init(AsgGrpTab T, const doubl
   const uint32_t g = blockIdx.x;
   if (T.state[g]) return;
   const int m = threadIdx.x;
-  const bool there = m < T.nm[g];
   const size_t e = (size_t)g * max_models + m;  // (read only where the row is there)
-  const bool go = there && okf[e] != 0;
-  if (there) {
-    okf[e] = 0;
-    out[e] = AssignLmOut{0, 0, 0, 0, 0.0};
-  }
-  if (go) lm_init(st[e], n, start + e * M::SP, ftol, xtol, gtol, maxfev, 100.0);
-  const unsigned long long all = __ballot(go);
+  const unsigned long long all =
+      assign_lm_start<M>(m < T.nm[g], okf + e, out + e, st + e, start + e * M::SP, n, ftol, xtol, gtol, maxfev);
   if (m == 0) {
     mask[g] = all;
     if (all) atomicAdd(live, (uint32_t)__popcll(all));
@@ -105,7 +102,6 @@ __global__ __launch_bounds__(64) void k_asg_grp_lm_step(const uint2 *__restrict_
                                                         AssignLmOut *__restrict__ out, unsigned long long *mask,
                                                         uint32_t *live) {
   constexpr int N = M::NMOM_LM, U = 16;
-  constexpr int NW = (int)(sizeof(LmState) / sizeof(int));
   static_assert(N <= 64, "one lane per moment");
   __shared__ double mom[LM_MOM_MAX];
   __shared__ LmState S;
@@ -131,30 +127,12 @@ __global__ __launch_bounds__(64) void k_asg_grp_lm_step(const uint2 *__restrict_
     for (; q < chunks; q++) t += src[(size_t)q * qs];
     mom[k] = t;
   }
-  {
-    const int *src = (const int *)&st[e];
-    int *dst = (int *)&S;
-    for (int i = k; i < NW; i += 64) dst[i] = src[i];
-  }
+  assign_lm_stage<64>(&st[e], &S);
   __syncthreads();
-  if (k == 0 && !lm_advance(S, mom)) {
-    out[e] = AssignLmOut{S.info, S.nfev, S.stall, 0, S.fnorm * S.fnorm};
-    if (S.info >= 1 && S.info <= 4) {  // vnl_levenberg_marquardt::minimize -> true
-      double p[LM_NMAX], row[M::SP];
-      M::lm_finalize(S.x, p);
-      assign_make_row<M>(p, mc, row);
-      for (int j = 0; j < (int)M::SP; j++) rows[e * M::SP + j] = row[j];
-      okf[e] = 1;
-    }
-    atomicAnd(mask + g, ~(1ull << m));
-    atomicSub(live, 1u);
-  }
+  if (k == 0 && !lm_advance(S, mom))
+    assign_lm_finish<M>(S, mc, (int)m, rows + e * M::SP, okf + e, out + e, mask + g, live);
   __syncthreads();
-  {
-    const int *src = (const int *)&S;
-    int *dst = (int *)&st[e];
-    for (int i = k; i < NW; i += 64) dst[i] = src[i];
-  }
+  assign_lm_stage<64>(&S, &st[e]);
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------
@@ -173,9 +151,7 @@ int assign_lm_grp_reserve(AssignGrpJob &J, const AsgGrpLmView &V) {
 }
 
 // The refit of one round, for every group still going.  The pass has left the moments of the labels `lab` in
-// B.d_partials and the presence words in B.d_presence.  Per evaluation: one pass, one step, one 4-byte read of the live
-// counter.  Every lm_advance call consumes one evaluation and stops at maxfev, so maxfev evaluations finish every model
-// (assign_lm_run's bound).
+// B.d_partials and the presence words in B.d_presence.  The evaluations are assign_lm_evals (assign_lm.h).
 template <class M>
 int assign_lm_grp_run(AssignGrpJob &J, const AsgGrpLmView &V, const int32_t *lab) {
   AssignGrpBufs &B = *J.B;
@@ -193,24 +169,18 @@ int assign_lm_grp_run(AssignGrpJob &J, const AsgGrpLmView &V, const int32_t *lab
                      B.d_lm_live.get());
   MANYCHK(hipGetLastError());
   MANYCHK(hipMemsetAsync(B.d_lm_partials, 0, sizeof(double) * (size_t)V.pblocks * M::NMOM_LM, stream));
-  for (int round = 0;; round++) {
-    if (round > maxfev) {
-      snprintf(J.err, sizeof J.err, "LM stage: %u models still live after %d evaluations", *V.h_live, round);
-      return LSQR_ERR_HIP;
-    }
-    hipLaunchKernelGGL((k_asg_grp_lm_pass<M>), dim3((unsigned)V.n_wgs), dim3(kBlock), 0, stream, V.data, V.stride,
-                       V.wgs, V.T, lab, B.d_presence.get(), B.d_lm_mask.get(), B.d_lm_state.get(), MM, J.mc,
-                       B.d_lm_partials.get());
-    MANYCHK(hipGetLastError());
-    hipLaunchKernelGGL((k_asg_grp_lm_step<M>), dim3((unsigned)V.n_pairs), dim3(64), 0, stream, V.pairs, V.T,
-                       B.d_lm_partials.get(), MM, J.mc, B.d_lm_state.get(), V.rows, V.ok, B.d_lm_out.get(),
-                       B.d_lm_mask.get(), B.d_lm_live.get());
-    MANYCHK(hipGetLastError());
-    MANYCHK(hipMemcpyAsync(V.h_live, B.d_lm_live, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    MANYCHK(hipStreamSynchronize(stream));
-    if (*V.h_live == 0) break;
-  }
-  return LSQR_OK;
+  return assign_lm_evals(
+      stream, maxfev, B.d_lm_live.get(), V.h_live, J.err,
+      [&] {
+        hipLaunchKernelGGL((k_asg_grp_lm_pass<M>), dim3((unsigned)V.n_wgs), dim3(kBlock), 0, stream, V.data, V.stride,
+                           V.wgs, V.T, lab, B.d_presence.get(), B.d_lm_mask.get(), B.d_lm_state.get(), MM, J.mc,
+                           B.d_lm_partials.get());
+      },
+      [&] {
+        hipLaunchKernelGGL((k_asg_grp_lm_step<M>), dim3((unsigned)V.n_pairs), dim3(64), 0, stream, V.pairs, V.T,
+                           B.d_lm_partials.get(), MM, J.mc, B.d_lm_state.get(), V.rows, V.ok, B.d_lm_out.get(),
+                           B.d_lm_mask.get(), B.d_lm_live.get());
+      });
 }
 #endif  // __HIPCC__
 

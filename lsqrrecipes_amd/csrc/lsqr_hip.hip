@@ -3097,11 +3097,11 @@ int lsqr_estimate_host(const lsqr_model_cfg *cfg, const void *records, size_t co
 }
 int lsqr_assign_host(const lsqr_model_cfg *cfg, const double *params, size_t n_models, const void *record,
                      int32_t *label_out, double *residual_out) {
-  return host_assign_host(cfg, params, n_models, record, label_out, residual_out);
+  return host_assign_host<false>(cfg, params, n_models, record, label_out, residual_out);
 }
 int lsqr_assign_dense_host(const lsqr_model_cfg *cfg, const double *params, size_t n_models, const void *record,
                            int32_t *label_out, double *residual_out) {
-  return host_assign_dense_host(cfg, params, n_models, record, label_out, residual_out);
+  return host_assign_host<true>(cfg, params, n_models, record, label_out, residual_out);
 }
 
 int lsqr_set_model(lsqr_ctx *c, const lsqr_model_cfg *cfg) {
@@ -4314,32 +4314,45 @@ int lsqr_ransac_grouped_sequential(lsqr_ctx *c, const int32_t *groups, size_t n_
   return LSQR_OK;
 }
 
-// ---- nearest-model assignment and refit (assign.h, assign_grouped.h) -------------------------------------------------
-// What the six entry points share.  The checks, in the contract's order: the context; the model gate (AssignGate:
-// what the entry point does with the geometric sphere, whose fit is iterative); count == 0
+// ---- nearest-model assignment and refit (assign.h, assign_dense.h, assign_grouped.h) ---------------------------------
+// What the ten entry points share.  The checks, in the contract's order: the context; the model gate (AssignGate:
+// which models the entry point takes, and what it does with the geometric sphere, whose fit is iterative); count == 0
 // (n_models, or n_groups of the grouped calls) is LSQR_OK with every output untouched; more than 64 models; own(), the
 // entry point's own arguments; the context holds a model and records; their count.  Then run(tag), the run function
 // on the model -- it has waited for the stream when it returns.  The context's upload, hypotheses, mask, index and
-// d_par are not touched: the calls have buffers of their own (lsqr_ctx::assign, lsqr_ctx::assign_grp).
+// d_par are not touched: the calls have buffers of their own (lsqr_ctx::assign, assign_dense, assign_grp).
 extern "C++" {
 enum AssignGate {
   ASSIGN_GATE_ANY,     // the assignments: every model of assign_model_ok
   ASSIGN_GATE_CLOSED,  // the refits in closed form: not the geometric sphere
-  ASSIGN_GATE_LM       // lsqr_refine_lm, lsqr_refine_lm_grouped: the geometric sphere alone
+  ASSIGN_GATE_LM,      // lsqr_refine_lm, lsqr_refine_lm_grouped: the geometric sphere alone
+  ASSIGN_GATE_DENSE    // lsqr_assign_dense, lsqr_refine_dense: the dense linear system alone
 };
-template <class Own, class Run>
-static int assign_frame(lsqr_ctx *c, const char *fn, AssignGate gate, const char *takes, size_t count,
-                        size_t max_models, const char *err, Own own, Run run) {
+// the entry point that takes what the gate refuses, [grouped][gate]
+static const char *const kAssignTakes[2][4] = {{"", "lsqr_refine_lm", "lsqr_refine", ""},
+                                               {"", "lsqr_refine_lm_grouped", "lsqr_refine_grouped", ""}};
+// the models run(tag) is compiled for
+template <AssignGate G, class M>
+constexpr bool kAssignTakesModel = G == ASSIGN_GATE_DENSE ? (bool)M::IS_DENSE : AssignModel<M>::value;
+
+template <AssignGate G, class Own, class Run>
+static int assign_frame(lsqr_ctx *c, const char *fn, bool grouped, size_t count, size_t max_models, const char *err,
+                        Own own, Run run) {
+  const char *takes = kAssignTakes[grouped][G];
   int st = need_ready(c, false);
   if (st != LSQR_OK) return st;
-  if (gate == ASSIGN_GATE_LM) {
+  if (G == ASSIGN_GATE_DENSE) {
+    if (c->cfg.model != LSQR_MODEL_DENSE)
+      return fail(c, LSQR_ERR_INVALID, "%s: the dense linear system only (model %d); lsqr_assign / lsqr_refine take "
+                  "the plane, line, sphere and 2-D line", fn, c->cfg.model);
+  } else if (G == ASSIGN_GATE_LM) {
     if (!(c->cfg.model == LSQR_MODEL_SPHERE && c->cfg.ls_type == LSQR_LS_GEOMETRIC))
       return fail(c, LSQR_ERR_INVALID, "%s: the sphere with LSQR_LS_GEOMETRIC only (model %d); %s takes the fits in "
                   "closed form", fn, c->cfg.model, takes);
   } else {
     if (!assign_model_ok(c->cfg))
       return fail(c, LSQR_ERR_INVALID, "%s: plane, line, sphere and 2-D line only (model %d)", fn, c->cfg.model);
-    if (gate == ASSIGN_GATE_CLOSED && wants_lm(c->cfg))
+    if (G == ASSIGN_GATE_CLOSED && wants_lm(c->cfg))
       return fail(c, LSQR_ERR_INVALID, "%s: the geometric sphere's fit is iterative; %s takes it", fn, takes);
   }
   if (count == 0) return LSQR_OK;
@@ -4348,7 +4361,7 @@ static int assign_frame(lsqr_ctx *c, const char *fn, AssignGate gate, const char
   if ((st = need_ready(c, true)) != LSQR_OK) return st;
   if (c->n > 0xFFFFFFF0ull) return fail(c, LSQR_ERR_INVALID, "%s: more than 2^32 - 16 records", fn);
   st = dispatch(c->cfg, [&](auto tag) -> int {
-    if constexpr (AssignModel<typename decltype(tag)::type>::value) return run(tag);
+    if constexpr (kAssignTakesModel<G, typename decltype(tag)::type>) return run(tag);
     else return LSQR_ERR_INVALID;
   });
   if (st != LSQR_OK) {
@@ -4359,158 +4372,114 @@ static int assign_frame(lsqr_ctx *c, const char *fn, AssignGate gate, const char
   return LSQR_OK;
 }
 
-// lsqr_assign, lsqr_refine and lsqr_refine_lm; args: the entry point's own pointers are all there
-static int assign_call(lsqr_ctx *c, const char *fn, AssignGate gate, bool args, AssignJob &J) {
-  return assign_frame(
-      c, fn, gate, gate == ASSIGN_GATE_LM ? "lsqr_refine" : "lsqr_assign", J.n_models, J.n_models, J.err,
+// the six ungrouped calls: the round loop (assign_rounds) with the gate's family; args: the entry point's own
+// pointers are all there
+template <AssignGate G>
+static int assign_call(lsqr_ctx *c, const char *fn, bool args, AssignJob &J) {
+  return assign_frame<G>(
+      c, fn, false, J.n_models, J.n_models, J.err,
       [&]() -> int { return args ? LSQR_OK : fail(c, LSQR_ERR_INVALID, "%s: null argument", fn); },
       [&](auto tag) -> int {
-        if (!c->assign) c->assign.reset(new AssignBufs());
         J.stream = c->stream;
         J.cfg = c->cfg;
         J.mc = c->mc;
         J.data = c->d_data;
         J.stride = c->stride;
         J.n = (uint32_t)c->n;
-        J.B = c->assign.get();
         typedef typename decltype(tag)::type M;
-        if constexpr (requires { M::NMOM_LM; }) {  // (the sphere)
-          if (gate == ASSIGN_GATE_LM) return assign_run<M, true>(J);
+        if constexpr (G == ASSIGN_GATE_DENSE) {
+          if (!c->assign_dense) c->assign_dense.reset(new AssignDenseBufs());
+          const int fast = c->opt.dense_fast ? 1 : 0, dd = c->opt.dense_dd ? 1 : 0;
+          return assign_rounds(J, AssignDense<M::NR>{*c->assign_dense, fast, dd});
+        } else {
+          if (!c->assign) c->assign.reset(new AssignBufs());
+          if constexpr (G != ASSIGN_GATE_LM) return assign_rounds(J, AssignClosed<M>{*c->assign});
+          else if constexpr (requires { M::NMOM_LM; }) return assign_rounds(J, AssignLm<M>{{*c->assign}});  // (the sphere)
+          else return LSQR_ERR_INVALID;
         }
-        return assign_run<M>(J);
       });
+}
+
+// lsqr_assign and lsqr_assign_dense
+template <AssignGate G>
+static int assign_only_call(lsqr_ctx *c, const char *fn, const double *params, size_t n_models, int on_device,
+                            int32_t *labels_out, double *residuals_out, uint64_t *counts_out) {
+  AssignJob J;
+  J.params = const_cast<double *>(params);  // (read only: no refit runs)
+  J.n_models = n_models;
+  J.max_rounds = 0;
+  J.on_device = on_device ? 1 : 0;
+  J.labels_out = labels_out;
+  J.residuals_out = residuals_out;
+  J.counts_out = counts_out;
+  return assign_call<G>(c, fn, params && labels_out, J);
+}
+
+// lsqr_refine, lsqr_refine_lm and lsqr_refine_dense
+template <AssignGate G>
+static int refine_call(lsqr_ctx *c, const char *fn, double *params_inout, size_t n_models, size_t max_rounds,
+                       int on_device, int32_t *labels_out, uint64_t *counts_out, lsqr_fit_info *fits,
+                       int32_t *status_out, size_t *rounds_out, int *converged_out) {
+  AssignJob J;
+  J.params = params_inout;
+  J.n_models = n_models;
+  J.max_rounds = max_rounds;
+  J.on_device = on_device ? 1 : 0;
+  J.labels_out = labels_out;
+  J.counts_out = counts_out;
+  J.fits = fits;
+  J.status_out = status_out;
+  const bool args = params_inout && fits && status_out && rounds_out && converged_out;
+  const int st = assign_call<G>(c, fn, args, J);
+  if (st == LSQR_OK && n_models > 0) {
+    *rounds_out = J.rounds;
+    *converged_out = J.converged;
+  }
+  return st;
 }
 }  // extern "C++"
 
 int lsqr_assign(lsqr_ctx *c, const double *params, size_t n_models, int on_device, int32_t *labels_out,
                 double *residuals_out, uint64_t *counts_out) {
-  AssignJob J;
-  J.params = const_cast<double *>(params);  // (read only: no refit runs)
-  J.n_models = n_models;
-  J.max_rounds = 0;
-  J.on_device = on_device ? 1 : 0;
-  J.labels_out = labels_out;
-  J.residuals_out = residuals_out;
-  J.counts_out = counts_out;
-  return assign_call(c, "lsqr_assign", ASSIGN_GATE_ANY, params && labels_out, J);
+  return assign_only_call<ASSIGN_GATE_ANY>(c, "lsqr_assign", params, n_models, on_device, labels_out, residuals_out,
+                                           counts_out);
 }
-
-extern "C++" {
-static int refine_call(lsqr_ctx *c, const char *fn, AssignGate gate, double *params_inout, size_t n_models,
-                       size_t max_rounds, int on_device, int32_t *labels_out, uint64_t *counts_out,
-                       lsqr_fit_info *fits, int32_t *status_out, size_t *rounds_out, int *converged_out) {
-  AssignJob J;
-  J.params = params_inout;
-  J.n_models = n_models;
-  J.max_rounds = max_rounds;
-  J.on_device = on_device ? 1 : 0;
-  J.labels_out = labels_out;
-  J.counts_out = counts_out;
-  J.fits = fits;
-  J.status_out = status_out;
-  const bool args = params_inout && fits && status_out && rounds_out && converged_out;
-  const int st = assign_call(c, fn, gate, args, J);
-  if (st == LSQR_OK && n_models > 0) {
-    *rounds_out = J.rounds;
-    *converged_out = J.converged;
-  }
-  return st;
-}
-}  // extern "C++"
 
 int lsqr_refine(lsqr_ctx *c, double *params_inout, size_t n_models, size_t max_rounds, int on_device,
                 int32_t *labels_out, uint64_t *counts_out, lsqr_fit_info *fits, int32_t *status_out,
                 size_t *rounds_out, int *converged_out) {
-  return refine_call(c, "lsqr_refine", ASSIGN_GATE_CLOSED, params_inout, n_models, max_rounds, on_device, labels_out,
-                     counts_out, fits, status_out, rounds_out, converged_out);
+  return refine_call<ASSIGN_GATE_CLOSED>(c, "lsqr_refine", params_inout, n_models, max_rounds, on_device, labels_out,
+                                         counts_out, fits, status_out, rounds_out, converged_out);
 }
 
 int lsqr_refine_lm(lsqr_ctx *c, double *params_inout, size_t n_models, size_t max_rounds, int on_device,
                    int32_t *labels_out, uint64_t *counts_out, lsqr_fit_info *fits, int32_t *status_out,
                    size_t *rounds_out, int *converged_out) {
-  return refine_call(c, "lsqr_refine_lm", ASSIGN_GATE_LM, params_inout, n_models, max_rounds, on_device, labels_out,
-                     counts_out, fits, status_out, rounds_out, converged_out);
+  return refine_call<ASSIGN_GATE_LM>(c, "lsqr_refine_lm", params_inout, n_models, max_rounds, on_device, labels_out,
+                                     counts_out, fits, status_out, rounds_out, converged_out);
 }
-
-// ---- the same for the dense linear system (assign_dense.h) ----------------------------------------------------------
-// lsqr_assign_dense and lsqr_refine_dense: assign_frame's checks in assign_frame's order, with the model gate turned
-// round -- LSQR_MODEL_DENSE alone -- and assign_dense_run on the row class NR of the context's dim.
-extern "C++" {
-static int assign_dense_call(lsqr_ctx *c, const char *fn, bool args, AssignJob &J) {
-  int st = need_ready(c, false);
-  if (st != LSQR_OK) return st;
-  if (c->cfg.model != LSQR_MODEL_DENSE)
-    return fail(c, LSQR_ERR_INVALID, "%s: the dense linear system only (model %d); lsqr_assign / lsqr_refine take the "
-                "plane, line, sphere and 2-D line", fn, c->cfg.model);
-  if (J.n_models == 0) return LSQR_OK;
-  if (J.n_models > (size_t)kAssignMaxModels) return fail(c, LSQR_ERR_INVALID, "%s: more than 64 models", fn);
-  if (!args) return fail(c, LSQR_ERR_INVALID, "%s: null argument", fn);
-  if ((st = need_ready(c, true)) != LSQR_OK) return st;
-  if (c->n > 0xFFFFFFF0ull) return fail(c, LSQR_ERR_INVALID, "%s: more than 2^32 - 16 records", fn);
-  if (!c->assign_dense) c->assign_dense.reset(new AssignDenseBufs());
-  J.stream = c->stream;
-  J.cfg = c->cfg;
-  J.mc = c->mc;
-  J.data = c->d_data;
-  J.stride = c->stride;
-  J.n = (uint32_t)c->n;
-  const int fast = c->opt.dense_fast ? 1 : 0, dd = c->opt.dense_dd ? 1 : 0;
-  st = dispatch(c->cfg, [&](auto tag) -> int {
-    typedef typename decltype(tag)::type M;
-    if constexpr (M::IS_DENSE) return assign_dense_run<M::NR>(J, *c->assign_dense, fast, dd);
-    else return LSQR_ERR_INVALID;
-  });
-  if (st != LSQR_OK) {
-    (void)sync_stream(c);  // nothing of this call is left in flight on its buffers
-    return fail(c, st, "%s: %s", fn, J.err[0] ? J.err : "model not in this build");
-  }
-  bsel_host_synced(c);
-  return LSQR_OK;
-}
-}  // extern "C++"
 
 int lsqr_assign_dense(lsqr_ctx *c, const double *params, size_t n_models, int on_device, int32_t *labels_out,
                       double *residuals_out, uint64_t *counts_out) {
-  AssignJob J;
-  J.params = const_cast<double *>(params);  // (read only: no refit runs)
-  J.n_models = n_models;
-  J.max_rounds = 0;
-  J.on_device = on_device ? 1 : 0;
-  J.labels_out = labels_out;
-  J.residuals_out = residuals_out;
-  J.counts_out = counts_out;
-  return assign_dense_call(c, "lsqr_assign_dense", params && labels_out, J);
+  return assign_only_call<ASSIGN_GATE_DENSE>(c, "lsqr_assign_dense", params, n_models, on_device, labels_out,
+                                             residuals_out, counts_out);
 }
 
 int lsqr_refine_dense(lsqr_ctx *c, double *params_inout, size_t n_models, size_t max_rounds, int on_device,
                       int32_t *labels_out, uint64_t *counts_out, lsqr_fit_info *fits, int32_t *status_out,
                       size_t *rounds_out, int *converged_out) {
-  AssignJob J;
-  J.params = params_inout;
-  J.n_models = n_models;
-  J.max_rounds = max_rounds;
-  J.on_device = on_device ? 1 : 0;
-  J.labels_out = labels_out;
-  J.counts_out = counts_out;
-  J.fits = fits;
-  J.status_out = status_out;
-  const bool args = params_inout && fits && status_out && rounds_out && converged_out;
-  const int st = assign_dense_call(c, "lsqr_refine_dense", args, J);
-  if (st == LSQR_OK && n_models > 0) {
-    *rounds_out = J.rounds;
-    *converged_out = J.converged;
-  }
-  return st;
+  return refine_call<ASSIGN_GATE_DENSE>(c, "lsqr_refine_dense", params_inout, n_models, max_rounds, on_device,
+                                        labels_out, counts_out, fits, status_out, rounds_out, converged_out);
 }
 
 // lsqr_assign_grouped, lsqr_refine_grouped and lsqr_refine_lm_grouped.  The sort and the packed copy live in the batched
 // calls' buffers (lsqr_ctx::many), as lsqr_ransac_grouped's do.
 extern "C++" {
+template <AssignGate G>
 static int assign_grouped_call(lsqr_ctx *c, const char *fn, bool args, AssignGrpJob &J) {
-  return assign_frame(
-      c, fn, J.lm ? ASSIGN_GATE_LM : J.refine ? ASSIGN_GATE_CLOSED : ASSIGN_GATE_ANY,
-      J.lm ? "lsqr_refine_grouped" : J.refine ? "lsqr_refine_lm_grouped" : "lsqr_assign_grouped", J.n_groups,
-      J.max_models, J.err,
+  J.refine = G != ASSIGN_GATE_ANY;
+  return assign_frame<G>(
+      c, fn, true, J.n_groups, J.max_models, J.err,
       [&]() -> int {
         if (J.n_groups > 0x7FFFFFFFull) return fail(c, LSQR_ERR_INVALID, "%s: more than 2^31 - 1 groups", fn);
         if (!args || !J.groups || !J.params || !J.n_models) return fail(c, LSQR_ERR_INVALID, "%s: null argument", fn);
@@ -4531,11 +4500,35 @@ static int assign_grouped_call(lsqr_ctx *c, const char *fn, bool args, AssignGrp
         J.n = c->n;
         J.B = c->assign_grp.get();
         typedef typename decltype(tag)::type M;
-        if constexpr (requires { M::NMOM_LM; }) {  // (the sphere)
-          if (J.lm) return assign_grouped_run<M, true>(J);
-        }
-        return assign_grouped_run<M>(J);
+        if constexpr (G != ASSIGN_GATE_LM) return assign_grouped_run<M>(J);
+        else if constexpr (requires { M::NMOM_LM; }) return assign_grouped_run<M, true>(J);  // (the sphere)
+        else return LSQR_ERR_INVALID;
       });
+}
+
+// lsqr_refine_grouped and, with lm, lsqr_refine_lm_grouped
+static int refine_grouped_call(lsqr_ctx *c, const char *fn, bool lm, const int32_t *groups, size_t n_groups,
+                               int on_device, double *params_inout, const size_t *n_models, size_t max_models,
+                               size_t max_rounds, int32_t *labels_out, uint64_t *counts_out, uint64_t *offsets_out,
+                               lsqr_fit_info *fits, int32_t *status_out, size_t *rounds_out, int32_t *converged_out) {
+  AssignGrpJob J;
+  J.groups = groups;
+  J.n_groups = n_groups;
+  J.on_device = on_device ? 1 : 0;
+  J.params = params_inout;
+  J.n_models = n_models;
+  J.max_models = max_models;
+  J.max_rounds = max_rounds;
+  J.labels_out = labels_out;
+  J.counts_out = counts_out;
+  J.offsets_out = offsets_out;
+  J.fits = fits;
+  J.status_out = status_out;
+  J.rounds_out = rounds_out;
+  J.converged_out = converged_out;
+  const bool args = fits && status_out && rounds_out && converged_out;
+  return lm ? assign_grouped_call<ASSIGN_GATE_LM>(c, fn, args, J)
+            : assign_grouped_call<ASSIGN_GATE_CLOSED>(c, fn, args, J);
 }
 }  // extern "C++"
 
@@ -4554,54 +4547,25 @@ int lsqr_assign_grouped(lsqr_ctx *c, const int32_t *groups, size_t n_groups, int
   J.residuals_out = residuals_out;
   J.counts_out = counts_out;
   J.offsets_out = offsets_out;
-  return assign_grouped_call(c, "lsqr_assign_grouped", labels_out != nullptr, J);
+  return assign_grouped_call<ASSIGN_GATE_ANY>(c, "lsqr_assign_grouped", labels_out != nullptr, J);
 }
 
 int lsqr_refine_grouped(lsqr_ctx *c, const int32_t *groups, size_t n_groups, int on_device, double *params_inout,
                         const size_t *n_models, size_t max_models, size_t max_rounds, int32_t *labels_out,
                         uint64_t *counts_out, uint64_t *offsets_out, lsqr_fit_info *fits, int32_t *status_out,
                         size_t *rounds_out, int32_t *converged_out) {
-  AssignGrpJob J;
-  J.refine = true;
-  J.groups = groups;
-  J.n_groups = n_groups;
-  J.on_device = on_device ? 1 : 0;
-  J.params = params_inout;
-  J.n_models = n_models;
-  J.max_models = max_models;
-  J.max_rounds = max_rounds;
-  J.labels_out = labels_out;
-  J.counts_out = counts_out;
-  J.offsets_out = offsets_out;
-  J.fits = fits;
-  J.status_out = status_out;
-  J.rounds_out = rounds_out;
-  J.converged_out = converged_out;
-  return assign_grouped_call(c, "lsqr_refine_grouped", fits && status_out && rounds_out && converged_out, J);
+  return refine_grouped_call(c, "lsqr_refine_grouped", false, groups, n_groups, on_device, params_inout, n_models,
+                             max_models, max_rounds, labels_out, counts_out, offsets_out, fits, status_out, rounds_out,
+                             converged_out);
 }
 
 int lsqr_refine_lm_grouped(lsqr_ctx *c, const int32_t *groups, size_t n_groups, int on_device, double *params_inout,
                            const size_t *n_models, size_t max_models, size_t max_rounds, int32_t *labels_out,
                            uint64_t *counts_out, uint64_t *offsets_out, lsqr_fit_info *fits, int32_t *status_out,
                            size_t *rounds_out, int32_t *converged_out) {
-  AssignGrpJob J;
-  J.refine = true;
-  J.lm = true;
-  J.groups = groups;
-  J.n_groups = n_groups;
-  J.on_device = on_device ? 1 : 0;
-  J.params = params_inout;
-  J.n_models = n_models;
-  J.max_models = max_models;
-  J.max_rounds = max_rounds;
-  J.labels_out = labels_out;
-  J.counts_out = counts_out;
-  J.offsets_out = offsets_out;
-  J.fits = fits;
-  J.status_out = status_out;
-  J.rounds_out = rounds_out;
-  J.converged_out = converged_out;
-  return assign_grouped_call(c, "lsqr_refine_lm_grouped", fits && status_out && rounds_out && converged_out, J);
+  return refine_grouped_call(c, "lsqr_refine_lm_grouped", true, groups, n_groups, on_device, params_inout, n_models,
+                             max_models, max_rounds, labels_out, counts_out, offsets_out, fits, status_out, rounds_out,
+                             converged_out);
 }
 
 // C(n,k) and the rank-th k-subset in the exhaustive overload's order (comb.h); host only

@@ -291,6 +291,7 @@ def test_geometric_sphere_assigns_but_does_not_refine(ctx):
     with pytest.raises(L.LsqrError) as e:
         ctx.refine(keep)
     assert e.value.status == L.ERR_INVALID
+    assert b"lsqr_refine_lm" in ctx._lib.lsqr_last_error(ctx._h)
     ctx.set_model(L.ABSOR, 3, 2.0, 0)
     with pytest.raises(L.LsqrError) as e:
         ctx.assign(np.zeros((1, 7)))
