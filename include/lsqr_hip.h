@@ -546,8 +546,9 @@ LSQR_API int lsqr_refine_lm(lsqr_ctx *ctx, double *params_inout /* host, n_model
  *     null params_inout, fits, status_out, rounds_out or converged_out (lsqr_refine_dense) (LSQR_ERR_INVALID); no
  *     records in the context (LSQR_ERR_STATE); more than 2^32 - 16 records (LSQR_ERR_INVALID).
  *   The context's hypotheses, mask, spatial index, fp16 fragment copies and the parameters of its last mask are left
- *     as they were; the work runs on the context's stream, and the call returns after it has finished.  There is no
- *     grouped form (one regression set per label) and lsqr_multi handles have no such form. */
+ *     as they were; the work runs on the context's stream, and the call returns after it has finished.
+ *     lsqr_assign_dense_grouped / lsqr_refine_dense_grouped, below, are the forms with one regression set per label;
+ *     lsqr_multi handles have no such form. */
 LSQR_API int lsqr_assign_dense(lsqr_ctx *ctx, const double *params /* host, n_models * n */, size_t n_models,
                                int on_device /* 1: labels_out, residuals_out are device pointers */,
                                int32_t *labels_out /* lsqr_count(ctx) entries, upload order */,
@@ -648,6 +649,51 @@ LSQR_API int lsqr_refine_lm_grouped(lsqr_ctx *ctx, const int32_t *groups, size_t
                                     int32_t *status_out /* host, n_groups * max_models */,
                                     size_t *rounds_out /* host, n_groups */,
                                     int32_t *converged_out /* host, n_groups */);
+/* ---- lsqr_assign_grouped / lsqr_refine_grouped for the dense linear system (csrc/assign_dense_grouped.h) ----------
+ * lsqr_assign_dense_grouped / lsqr_refine_dense_grouped are lsqr_assign_grouped / lsqr_refine_grouped -- their
+ * arguments and their shapes, on_device, the groups' rules, each group's own loop and stop, what does not run,
+ * counts_out / offsets_out, max_models == 0, "every entry of labels_out is written exactly once", the order of their
+ * checks, "every argument error writes nothing", what is left untouched on the context, the stream -- for the model
+ * they refuse, with lsqr_refine_dense's refit.  They finish lsqr_ransac_grouped_sequential on this model, and take
+ * n up to 64 whatever that call's record limit is.
+ *   Model: LSQR_MODEL_DENSE, dim n = 1..64, any stride, from lsqr_upload or lsqr_attach; a parameter row is n
+ *     doubles.  Every other model returns LSQR_ERR_INVALID and writes nothing: lsqr_assign_grouped /
+ *     lsqr_refine_grouped take the plane, line, sphere and 2-D line.
+ *   Contract: group g -- the rows with groups[i] == g, in upload order, with parameter rows g * max_models .. +
+ *     n_models[g] -- is decided bit for bit as lsqr_assign_dense / lsqr_refine_dense decide it on a fresh context with
+ *     the same model and options (dense_fast_solve, dense_dd) that holds the stable gather of group g's rows, tightly
+ *     packed, with the same max_rounds.  Bit-identical per group: labels_out (the model index inside the group, or
+ *     -1), residuals_out, the counts; the returned parameters, status_out, fits[].n_used, fits[].n_params and
+ *     fits[].reserved (the route 0 / 1 / 2), rounds_out[g] and converged_out[g].
+ *   Sums: lsqr_refine_dense's order with the chunks (256 rows up to n = 32, 128 above) counted inside the group's
+ *     packed rows; none is a floating-point atomic, so a group's results do not depend on the other groups of the
+ *     call, on how the ids are numbered, or on the run.  The double-double solve of a flagged (group, model) pair
+ *     runs over that group's packed rows alone, as the fresh context's does.
+ *   Per round the host waits once and reads two words: the groups still going and the flagged pairs; the list of
+ *     flagged pairs crosses only when there is one.
+ *   Device scratch of a refine call: sum over the groups of ceil(rows_g / chunk) * n_models[g] * ((n+1)(n+2)/2 + 1,
+ *     rounded up to 8) doubles of partial blocks; that many doubles once more and a 544-byte result block per (group,
+ *     model) pair; two packed label arrays; one word per (group, chunk); with dense_dd and a flagged pair one byte per
+ *     packed row and 9 MiB.  If it cannot be allocated the call returns LSQR_ERR_HIP with the allocation in
+ *     lsqr_last_error; there is no other path.  lsqr_multi handles have no such form. */
+LSQR_API int lsqr_assign_dense_grouped(lsqr_ctx *ctx, const int32_t *groups /* lsqr_count(ctx), upload order */,
+                                       size_t n_groups, int on_device,
+                                       const double *params /* host, n_groups * max_models * n */,
+                                       const size_t *n_models /* host, n_groups; each <= max_models */,
+                                       size_t max_models /* <= 64 */,
+                                       int32_t *labels_out /* lsqr_count(ctx) entries, upload order */,
+                                       double *residuals_out /* nullable */,
+                                       uint64_t *counts_out /* nullable, host: n_groups * (max_models + 1) */,
+                                       uint64_t *offsets_out /* nullable, host: n_groups + 1 */);
+LSQR_API int lsqr_refine_dense_grouped(lsqr_ctx *ctx, const int32_t *groups, size_t n_groups, int on_device,
+                                       double *params_inout /* host, n_groups * max_models * n */,
+                                       const size_t *n_models, size_t max_models, size_t max_rounds,
+                                       int32_t *labels_out /* nullable */, uint64_t *counts_out /* nullable */,
+                                       uint64_t *offsets_out /* nullable */,
+                                       lsqr_fit_info *fits /* host, n_groups * max_models */,
+                                       int32_t *status_out /* host, n_groups * max_models */,
+                                       size_t *rounds_out /* host, n_groups */,
+                                       int32_t *converged_out /* host, n_groups */);
 /* Many independent RANSAC<T,S>::compute() problems (probabilistic overload, RANSAC.h:75-79) in one call.
  * Problem j is records [offsets[j], offsets[j+1]) of host_records (stride_bytes apart, laid out as for
  * lsqr_upload), walks sampler stream seeds[j] and is decided exactly as lsqr_ransac(ctx, p, seeds[j], NULL, 0, ...)

@@ -137,6 +137,11 @@ SIGNATURES = {
     "lsqr_refine_lm_grouped": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
                                          C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p]),
+    "lsqr_assign_dense_grouped": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p,
+                                            C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lsqr_refine_dense_grouped": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p,
+                                            C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p]),
     "lsqr_ransac_many": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_double, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lsqr_ransac_many_lm": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_double, C.c_void_p,

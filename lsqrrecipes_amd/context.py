@@ -660,6 +660,11 @@ class Context:
         -> dict: labels (the model index inside the record's group), residuals (None unless want_residuals), counts
         (uint64, (n_groups, max_models + 1): records per model, then the group's unassigned ones) and offsets (the
         prefix sums of the group sizes)."""
+        return self._assign_grouped(self._lib.lsqr_assign_grouped, groups, n_groups, params, n_models, want_residuals,
+                                    labels_out)
+
+    def _assign_grouped(self, call, groups, n_groups, params, n_models, want_residuals, labels_out):
+        """lsqr_assign_grouped or lsqr_assign_dense_grouped -> assign_grouped's dict"""
         n, m, total, on_device, g, g_ptr, par, nm, labels, l_ptr = self._assign_grouped_args(
             groups, n_groups, params, n_models, labels_out)
         if on_device and want_residuals:
@@ -669,8 +674,8 @@ class Context:
         res = np.full(max(total, 1), np.inf) if want_residuals else None
         counts = np.zeros((n, m + 1), dtype=np.uint64)
         offs = np.zeros(n + 1, dtype=np.uint64)
-        self._chk(self._lib.lsqr_assign_grouped(self._h, g_ptr, n, 1 if on_device else 0, L.ptr(par), L.ptr(nm), m,
-                                                l_ptr, L.ptr(res), L.ptr(counts), L.ptr(offs)))
+        self._chk(call(self._h, g_ptr, n, 1 if on_device else 0, L.ptr(par), L.ptr(nm), m, l_ptr, L.ptr(res),
+                       L.ptr(counts), L.ptr(offs)))
         if not on_device:
             labels = labels[:total]
         return dict(labels=labels, residuals=res[:total] if res is not None else None, counts=counts, offsets=offs)
@@ -687,8 +692,8 @@ class Context:
                                     labels_out)[0]
 
     def _refine_grouped(self, call, groups, n_groups, params, n_models, max_rounds, labels_out):
-        """lsqr_refine_grouped or lsqr_refine_lm_grouped -> (refine_grouped's dict, the fits as a structured array
-        shaped (n_groups, max_models))"""
+        """lsqr_refine_grouped, lsqr_refine_lm_grouped or lsqr_refine_dense_grouped -> (refine_grouped's dict, the fits
+        as a structured array shaped (n_groups, max_models))"""
         n, m, total, on_device, g, g_ptr, par, nm, labels, l_ptr = self._assign_grouped_args(
             groups, n_groups, params, n_models, labels_out)
         if int(max_rounds) < 0:
@@ -721,6 +726,28 @@ class Context:
                                       labels_out)
         out.update(lm_info=f["lm_info"].copy(), lm_nfev=f["lm_nfev"].copy(), cost=f["cost"].copy(),
                    stall=f["reserved"].copy())
+        return out
+
+    def assign_dense_grouped(self, groups, n_groups, params, n_models=None, want_residuals=False, labels_out=None):
+        """assign_grouped for the dense linear system, which assign_grouped refuses (lsqr_assign_dense_grouped): group
+        g is the rows i with groups[i] == g, in upload order, and goes to the nearest of the regressions
+        params[g, :n_models[g]] as assign_dense decides it on those rows alone, bit for bit.  params: (n_groups,
+        max_models, n), max_models <= 64, n up to 64.  Arguments and result as for assign_grouped.  Any other model
+        raises LsqrError(ERR_INVALID)."""
+        return self._assign_grouped(self._lib.lsqr_assign_dense_grouped, groups, n_groups, params, n_models,
+                                    want_residuals, labels_out)
+
+    def refine_dense_grouped(self, groups, n_groups, params, n_models=None, max_rounds=8, labels_out=None):
+        """refine_grouped for the dense linear system (lsqr_refine_dense_grouped): every group runs refine_dense's
+        loop on its own rows and regressions, bit for bit as refine_dense runs it on those rows alone under the same
+        options (dense_fast_solve, dense_dd), and stops on its own; the rows never leave the device.  Arguments as for
+        refine_grouped.  Any other model raises LsqrError(ERR_INVALID).
+        -> refine_grouped's dict, and route: per (group, model) the route of the group's last refit round (0: the
+        elimination, 1: double-double from the group's rows, 2: dense_dd 0 and a pivot below 1e-6), shaped (n_groups,
+        max_models); zeros where none ran."""
+        out, f = self._refine_grouped(self._lib.lsqr_refine_dense_grouped, groups, n_groups, params, n_models,
+                                      max_rounds, labels_out)
+        out.update(route=f["reserved"].copy())
         return out
 
     def _many_records(self, problems):

@@ -162,6 +162,14 @@ enum {
 };
 
 #if defined(__HIPCC__)
+// v, the same in every lane of the wave, as a scalar: loops over its bits then stay on the scalar unit.  (The builtin
+// returns int: each half goes back through uint32_t, or a set bit 31 -- model 31 -- would smear over bits 32 .. 63.)
+__device__ __forceinline__ unsigned long long wave_uniform64(unsigned long long v) {
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));
+  return ((unsigned long long)hi << 32) | lo;
+}
+
 // params: n_rows rows of M::P, row e of group e / max_models; nm (nullable: every row is there): the rows of each group
 // that are there.  A row that is not there is never read and never written.
 template <class M>
@@ -247,10 +255,8 @@ __device__ __forceinline__ void assign_pass_chunk(const double *__restrict__ dat
   unsigned long long all = 0;
   for (int w = 0; w < W; w++) all |= s_p[w];
   // (uniform by construction; the scalar copies keep the model loop's control flow on the scalar unit)
-  const unsigned long long present = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(all >> 32)) << 32) |
-                                     __builtin_amdgcn_readfirstlane((uint32_t)all);
-  const unsigned long long mine = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(pres >> 32)) << 32) |
-                                  __builtin_amdgcn_readfirstlane((uint32_t)pres);
+  const unsigned long long present = wave_uniform64(all);
+  const unsigned long long mine = wave_uniform64(pres);
 
   int it = 0;
   for (unsigned long long rest = present; rest; rest &= rest - 1, it++) {

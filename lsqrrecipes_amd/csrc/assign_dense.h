@@ -27,6 +27,8 @@
 //                                    thread-per-entry form of k_many_dense_mask_moments) -> partials[chunk][m][ps].
 //                                    A model absent from the chunk costs nothing: its slot is not written and the
 //                                    chunk's presence word tells k_asd_sum to take 0.0 for it.
+//                       Its body is asd_pass_chunk, which k_asd_grp_pass (assign_dense_grouped.h: one regression set
+//                       per label) runs too; the kernels only locate their chunk.
 //   k_asd_sum           model m's blocks added in chunk order, one thread per entry; the count comes from the
 //                       integer counter -> mom[m][ps] (the block, then the count: solve_dense_wg's layout)
 //   k_asd_solve         one workgroup per model: solve_dense_wg (dense.h) where the model has at least n rows, with
@@ -71,19 +73,22 @@ constexpr int kAsdBlock = 256;
 enum { ASD_ROUTE = ASG_WORDS, ASD_WORDS = ASD_ROUTE + kAssignMaxModels };  // SolveOut::pad of the last refit
 
 #if defined(__HIPCC__)
-// chunk blockIdx.x of the context's n rows.  data: `stride` doubles apart, dim + 1 doubles each; rows: n_models scan
-// rows of NR doubles; labels: n entries; residuals, old: nullable; counters: the ASG_ words, zeroed by the caller;
-// partials (WITH_MOMENTS): [chunk][model][ps]; presence (WITH_MOMENTS): one word per chunk.
-// Dynamic LDS: kAssignDenseChunk<NR> * (NR + 1) doubles.
+// The pass over ONE chunk, by one workgroup of kAsdBlock lanes: the body of k_asd_pass and of k_asd_grp_pass
+// (assign_dense_grouped.h), which only locate their chunk.  The chunk's base is in the pointers, so its rows are
+// [0, cnt), cnt <= kAssignDenseChunk<NR>.  src: the chunk's rows, `stride` doubles apart, dim + 1 doubles each; rows:
+// the n_models scan rows of NR doubles of the chunk's model set; labels / residuals (nullable) / old (nullable): the
+// chunk's cnt entries; changed: the word that counts labels[i] != old[i]; counts: one word per model; partials
+// (WITH_MOMENTS): the chunk's [model][ps]; presence (WITH_MOMENTS): the chunk's word.
+// Dynamic LDS: kAssignDenseChunk<NR> * (NR + 1) doubles.  It must be inlined, as assign_pass_chunk (assign.h).
 template <int NR, bool WITH_MOMENTS>
-__global__ __launch_bounds__(kAsdBlock) void k_asd_pass(const double *__restrict__ data, size_t stride, uint32_t n,
-                                                        int dim, const double *__restrict__ rows, int n_models,
-                                                        ModelConsts mc, int32_t *__restrict__ labels,
-                                                        double *__restrict__ residuals,
-                                                        const int32_t *__restrict__ old,
-                                                        unsigned long long *__restrict__ counters,
-                                                        double *__restrict__ partials, int ps,
-                                                        unsigned long long *__restrict__ presence) {
+__device__ __forceinline__ void asd_pass_chunk(const double *__restrict__ src, size_t stride, uint32_t cnt, int dim,
+                                               const double *__restrict__ rows, int n_models, const ModelConsts &mc,
+                                               int32_t *__restrict__ labels, double *__restrict__ residuals,
+                                               const int32_t *__restrict__ old,
+                                               unsigned long long *__restrict__ changed,
+                                               unsigned long long *__restrict__ counts,
+                                               double *__restrict__ partials, int ps,
+                                               unsigned long long *__restrict__ presence) {
   typedef DenseModel<NR> M;
   constexpr uint32_t CH = kAssignDenseChunk<NR>;
   constexpr int PITCH = NR + 1, W = kAsdBlock / 64, U = ((NR + 1) * (NR + 2) / 2 + kAsdBlock - 1) / kAsdBlock;
@@ -95,14 +100,10 @@ __global__ __launch_bounds__(kAsdBlock) void k_asd_pass(const double *__restrict
   __shared__ unsigned long long s_p[W];
   __shared__ uint32_t s_chg[W];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const uint32_t c0 = blockIdx.x * CH, left = n - c0, cnt = left < CH ? left : CH;  // (c0 < n: no wrap)
 
-  {  // the chunk's rows -> LDS, zero-padded
-    const double *src = data + (size_t)c0 * stride;
-    for (uint32_t q = tid; q < cnt * PITCH; q += kAsdBlock) {
-      const uint32_t r = q / PITCH, k = q - r * PITCH;
-      s_rec[q] = (int)k < dim ? src[(size_t)r * stride + k] : (k == NR ? src[(size_t)r * stride + dim] : 0.0);
-    }
+  for (uint32_t q = tid; q < cnt * PITCH; q += kAsdBlock) {  // the chunk's rows -> LDS, zero-padded
+    const uint32_t r = q / PITCH, k = q - r * PITCH;
+    s_rec[q] = (int)k < dim ? src[(size_t)r * stride + k] : (k == NR ? src[(size_t)r * stride + dim] : 0.0);
   }
   s_wc[wave][lane] = 0;
   __syncthreads();
@@ -115,18 +116,17 @@ __global__ __launch_bounds__(kAsdBlock) void k_asd_pass(const double *__restrict
 #pragma unroll
     for (int k = 0; k < (int)M::REC; k++) x[k] = s_rec[tid * PITCH + k];
     lab = assign_one<M>(rows, n_models, x, mc, &res);
-    labels[c0 + tid] = lab;
-    if (residuals) residuals[c0 + tid] = res;
+    labels[tid] = lab;
+    if (residuals) residuals[tid] = res;
   }
-  uint32_t chg = in && old && old[c0 + tid] != lab ? 1u : 0u;
+  uint32_t chg = in && old && old[tid] != lab ? 1u : 0u;
   unsigned long long pres = lab >= 0 ? 1ull << lab : 0ull;
   for (int o = 32; o > 0; o >>= 1) {
     chg += __shfl_xor(chg, o);
     pres |= __shfl_xor(pres, o);
   }
   // (uniform by construction; the scalar copies keep the model loops' control flow on the scalar unit)
-  const unsigned long long mine = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(pres >> 32)) << 32) |
-                                  __builtin_amdgcn_readfirstlane((uint32_t)pres);
+  const unsigned long long mine = wave_uniform64(pres);
   uint32_t rank = 0;  // rows of the lane's model before it in its wave
   for (unsigned long long rest = mine; rest; rest &= rest - 1) {
     const int m = __builtin_ctzll(rest);
@@ -149,19 +149,17 @@ __global__ __launch_bounds__(kAsdBlock) void k_asd_pass(const double *__restrict
     }
     s_tot[tid] = t;
     s_base[tid] = incl - t;
-    if (tid < n_models && t) atomicAdd(&counters[ASG_COUNT + tid], (unsigned long long)t);
+    if (tid < n_models && t) atomicAdd(&counts[tid], (unsigned long long)t);
   }
   if (tid == 0) {
     unsigned long long t = 0;
     for (int w = 0; w < W; w++) t += s_chg[w];
-    if (t) atomicAdd(&counters[ASG_CHANGED], t);
+    if (t) atomicAdd(changed, t);
   }
   if constexpr (WITH_MOMENTS) {
     unsigned long long all = 0;
     for (int w = 0; w < W; w++) all |= s_p[w];
-    const unsigned long long present =
-        ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(all >> 32)) << 32) |
-        __builtin_amdgcn_readfirstlane((uint32_t)all);
+    const unsigned long long present = wave_uniform64(all);
     __syncthreads();
     if (lab >= 0) {
       uint32_t pos = s_base[lab] + rank;
@@ -195,58 +193,97 @@ __global__ __launch_bounds__(kAsdBlock) void k_asd_pass(const double *__restrict
 #pragma unroll
         for (int u = 0; u < U; u++) acc[u] += z[ea[u]] * z[eb[u]];
       }
-      double *out = partials + ((size_t)blockIdx.x * n_models + m) * ps;
+      double *out = partials + (size_t)m * ps;
 #pragma unroll
       for (int u = 0; u < U; u++)
         if (tid + kAsdBlock * u < ne) out[tid + kAsdBlock * u] = acc[u];
     }
-    if (tid == 0) presence[blockIdx.x] = present;
+    if (tid == 0) *presence = present;
   }
 }
 
-// model blockIdx.x, entries blockIdx.y * 256 + tid: its chunk blocks added in chunk order (0.0 where the chunk's
-// presence word says the model is not there), 32 loads in flight; entry ne is the count
-__global__ __launch_bounds__(kAsdBlock) void k_asd_sum(const double *__restrict__ partials,
-                                                       const unsigned long long *__restrict__ presence,
-                                                       uint32_t chunks, int n_models, int n, int ps,
-                                                       const unsigned long long *__restrict__ counters,
-                                                       double *__restrict__ mom) {
-  constexpr int PF = 32;
-  const int m = blockIdx.x, e = blockIdx.y * kAsdBlock + threadIdx.x, ne = (n + 1) * (n + 2) / 2;
-  if (e > ne) return;
-  if (e == ne) {
-    mom[(size_t)m * ps + ne] = (double)counters[ASG_COUNT + m];
-    return;
+// chunk blockIdx.x of the context's n rows.  data: `stride` doubles apart, dim + 1 doubles each; rows: n_models scan
+// rows of NR doubles; labels: n entries; residuals, old: nullable; counters: the ASG_ words, zeroed by the caller;
+// partials (WITH_MOMENTS): [chunk][model][ps]; presence (WITH_MOMENTS): one word per chunk.
+// Dynamic LDS: kAssignDenseChunk<NR> * (NR + 1) doubles.
+template <int NR, bool WITH_MOMENTS>
+__global__ __launch_bounds__(kAsdBlock) void k_asd_pass(const double *__restrict__ data, size_t stride, uint32_t n,
+                                                        int dim, const double *__restrict__ rows, int n_models,
+                                                        ModelConsts mc, int32_t *__restrict__ labels,
+                                                        double *__restrict__ residuals,
+                                                        const int32_t *__restrict__ old,
+                                                        unsigned long long *__restrict__ counters,
+                                                        double *__restrict__ partials, int ps,
+                                                        unsigned long long *__restrict__ presence) {
+  constexpr uint32_t CH = kAssignDenseChunk<NR>;
+  const uint32_t c0 = blockIdx.x * CH, left = n - c0;  // (c0 < n: no wrap)
+  if constexpr (WITH_MOMENTS) {
+    partials += (size_t)blockIdx.x * n_models * ps;
+    presence += blockIdx.x;
   }
+  asd_pass_chunk<NR, WITH_MOMENTS>(data + (size_t)c0 * stride, stride, left < CH ? left : CH, dim, rows, n_models, mc,
+                                   labels + c0, residuals ? residuals + c0 : nullptr, old ? old + c0 : nullptr,
+                                   counters + ASG_CHANGED, counters + ASG_COUNT, partials, ps, presence);
+}
+
+// One entry of one model's block: the chunk blocks added in chunk order, 32 loads in flight, 0.0 where the chunk's
+// presence word says the model is not there.  src: the entry in the model's block of chunk 0, `qs` doubles from chunk
+// to chunk; pw: the presence words of the `chunks` chunks.  The sum of k_asd_sum and of k_asd_grp_sum
+// (assign_dense_grouped.h): the bit-identity of the grouped calls rests on both running THIS loop.
+__device__ __forceinline__ double asd_sum_entry(const double *__restrict__ src, size_t qs,
+                                                const unsigned long long *__restrict__ pw, int m, uint32_t chunks) {
+  constexpr int PF = 32;
   double t = 0.0;
   for (uint32_t q0 = 0; q0 < chunks; q0 += PF) {
     double v[PF];
 #pragma unroll
     for (int u = 0; u < PF; u++) {
       const uint32_t q = q0 + u;
-      v[u] = q < chunks && ((presence[q] >> m) & 1ull) ? partials[((size_t)q * n_models + m) * ps + e] : 0.0;
+      v[u] = q < chunks && ((pw[q] >> m) & 1ull) ? src[(size_t)q * qs] : 0.0;
     }
 #pragma unroll
     for (int u = 0; u < PF; u++) t += v[u];
   }
-  mom[(size_t)m * ps + e] = t;
+  return t;
 }
 
-// flags (nullable: dense_dd 0, the block alone decides): one per model, zeroed by the caller.
-// Dynamic LDS: many_dense_lds(n).
-__global__ __launch_bounds__(256) void k_asd_solve(const double *__restrict__ mom, int ps, int n, int fast,
-                                                   SolveOut *__restrict__ out, int *__restrict__ flags) {
-  const uint32_t m = blockIdx.x;
-  const double *mm = mom + (size_t)m * ps;
+// model blockIdx.x, entries blockIdx.y * 256 + tid: its chunk blocks added in chunk order (asd_sum_entry); entry ne is
+// the count
+__global__ __launch_bounds__(kAsdBlock) void k_asd_sum(const double *__restrict__ partials,
+                                                       const unsigned long long *__restrict__ presence,
+                                                       uint32_t chunks, int n_models, int n, int ps,
+                                                       const unsigned long long *__restrict__ counters,
+                                                       double *__restrict__ mom) {
+  const int m = blockIdx.x, e = blockIdx.y * kAsdBlock + threadIdx.x, ne = (n + 1) * (n + 2) / 2;
+  if (e > ne) return;
+  if (e == ne) {
+    mom[(size_t)m * ps + ne] = (double)counters[ASG_COUNT + m];
+    return;
+  }
+  mom[(size_t)m * ps + e] = asd_sum_entry(partials + (size_t)m * ps + e, (size_t)n_models * ps, presence, m, chunks);
+}
+
+// One model's solve, by one workgroup of 256 lanes: solve_dense_wg on its block mm where it has at least n rows.  flag
+// (nullable: dense_dd 0, the block alone decides): the model's, zeroed by the caller.  The body of k_asd_solve and of
+// k_asd_grp_solve (assign_dense_grouped.h).  Dynamic LDS: many_dense_lds(n).
+__device__ __forceinline__ void asd_solve_one(const double *__restrict__ mm, int n, int fast,
+                                              SolveOut *__restrict__ out, int *__restrict__ flag) {
   if (mm[(n + 1) * (n + 2) / 2] < (double)n) {  // fewer than lsqr_min_subset rows: no refit (workgroup-uniform)
     if (threadIdx.x == 0) {
-      out[m].ok = 0;
-      out[m].n_params = 0;
-      out[m].pad = 0;
+      out->ok = 0;
+      out->n_params = 0;
+      out->pad = 0;
     }
     return;
   }
-  solve_dense_wg(mm, n, fast, out + m, flags ? flags + m : nullptr);
+  solve_dense_wg(mm, n, fast, out, flag);
+}
+
+// flags (nullable): one per model.  Dynamic LDS: many_dense_lds(n).
+__global__ __launch_bounds__(256) void k_asd_solve(const double *__restrict__ mom, int ps, int n, int fast,
+                                                   SolveOut *__restrict__ out, int *__restrict__ flags) {
+  const uint32_t m = blockIdx.x;
+  asd_solve_one(mom + (size_t)m * ps, n, fast, out + m, flags ? flags + m : nullptr);
 }
 
 __global__ __launch_bounds__(256) void k_asd_label_mask(const int32_t *__restrict__ labels, uint32_t n, int32_t m,
@@ -254,19 +291,30 @@ __global__ __launch_bounds__(256) void k_asd_label_mask(const int32_t *__restric
   for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) mask[i] = labels[i] == m ? 1 : 0;
 }
 
-// model blockIdx.x: what its refit gave -> its scan row (NR doubles, zero beyond n) and the ASG_ / ASD_ words
+// The refit decision for one model, by one wave (lane t): cnt rows were behind the attempt `out`; a model with at
+// least n rows and a solve that gave a result gets the new scan row (nr doubles, zero beyond n), any other keeps its
+// row; *used / *okf / *route say what happened.  The body of k_asd_apply and of k_asd_grp_apply
+// (assign_dense_grouped.h).
+__device__ __forceinline__ void asd_apply_one(const SolveOut *__restrict__ out, unsigned long long cnt, int n, int nr,
+                                              double *__restrict__ row, unsigned long long *used,
+                                              unsigned long long *okf, unsigned long long *route) {
+  const int t = threadIdx.x;
+  const bool ran = cnt >= (unsigned long long)n, ok = ran && out->ok != 0;
+  if (ok && t < nr) row[t] = t < n ? out->params[t] : 0.0;
+  if (t == 0) {
+    *used = cnt;
+    *okf = ok ? 1 : 0;
+    *route = ran ? (unsigned long long)out->pad : 0;
+  }
+}
+
+// model blockIdx.x: what its refit gave -> its scan row and the ASG_ / ASD_ words
 __global__ __launch_bounds__(64) void k_asd_apply(const SolveOut *__restrict__ out, int n, int nr,
                                                   double *__restrict__ rows,
                                                   unsigned long long *__restrict__ counters) {
-  const int m = blockIdx.x, t = threadIdx.x;
-  const unsigned long long cnt = counters[ASG_COUNT + m];
-  const bool ran = cnt >= (unsigned long long)n, ok = ran && out[m].ok != 0;
-  if (ok && t < nr) rows[(size_t)m * nr + t] = t < n ? out[m].params[t] : 0.0;
-  if (t == 0) {
-    counters[ASG_USED + m] = cnt;
-    counters[ASG_OK + m] = ok ? 1 : 0;
-    counters[ASD_ROUTE + m] = ran ? (unsigned long long)out[m].pad : 0;
-  }
+  const int m = blockIdx.x;
+  asd_apply_one(out + m, counters[ASG_COUNT + m], n, nr, rows + (size_t)m * nr, counters + ASG_USED + m,
+                counters + ASG_OK + m, counters + ASD_ROUTE + m);
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------

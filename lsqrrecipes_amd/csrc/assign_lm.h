@@ -131,8 +131,7 @@ __device__ __forceinline__ void assign_lm_pass_chunk(const double *__restrict__ 
     if (lab[j] >= 0) pres |= 1ull << lab[j];
   }
   for (int o = 32; o > 0; o >>= 1) pres |= __shfl_xor(pres, o);
-  const unsigned long long mine = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(pres >> 32)) << 32) |
-                                  __builtin_amdgcn_readfirstlane((uint32_t)pres);
+  const unsigned long long mine = wave_uniform64(pres);
 
   int it = 0;
   for (unsigned long long rest = todo; rest; rest &= rest - 1, it++) {
@@ -177,8 +176,7 @@ __global__ __launch_bounds__(kBlock) void k_assign_lm_pass(const double *__restr
                                                            const LmState *__restrict__ st, int n_models, ModelConsts mc,
                                                            double *__restrict__ partials) {
   const unsigned long long t = presence[blockIdx.x] & *mask;  // (uniform addresses)
-  const unsigned long long todo = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(t >> 32)) << 32) |
-                                  __builtin_amdgcn_readfirstlane((uint32_t)t);
+  const unsigned long long todo = wave_uniform64(t);
   if (!todo) return;
   const uint32_t c0 = blockIdx.x * kAssignChunk, left = n - c0;  // (c0 < n: no wrap)
   assign_lm_pass_chunk<M>(data + (size_t)c0 * stride, stride, left < kAssignChunk ? left : kAssignChunk, labels + c0,

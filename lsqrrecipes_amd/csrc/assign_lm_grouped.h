@@ -83,8 +83,7 @@ __global__ __launch_bounds__(kBlock) void k_asg_grp_lm_pass(const double *__rest
   const uint32_t g = wg.x;
   if (T.state[g]) return;
   const unsigned long long t = presence[blockIdx.x] & mask[g];  // (uniform addresses)
-  const unsigned long long todo = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(t >> 32)) << 32) |
-                                  __builtin_amdgcn_readfirstlane((uint32_t)t);
+  const unsigned long long todo = wave_uniform64(t);
   if (!todo) return;
   const int n_models = T.nm[g];
   const uint64_t c0 = T.offsets[g] + (uint64_t)wg.y * kAssignChunk, left = T.offsets[g + 1] - c0;
@@ -185,5 +184,3 @@ int assign_lm_grp_run(AssignGrpJob &J, const AsgGrpLmView &V, const int32_t *lab
 #endif  // __HIPCC__
 
 }  // namespace lsqr
-
-#undef MANYCHK

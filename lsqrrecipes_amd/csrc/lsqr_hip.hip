@@ -50,6 +50,7 @@
 #include "assign_lm.h"
 #include "assign_grouped.h"
 #include "assign_lm_grouped.h"
+#include "assign_dense_grouped.h"
 
 #include <condition_variable>
 #include <mutex>
@@ -319,6 +320,8 @@ struct lsqr_ctx {
   std::unique_ptr<AssignDenseBufs> assign_dense;  // lsqr_assign_dense / lsqr_refine_dense (assign_dense.h)
   // lsqr_assign_grouped / lsqr_refine_grouped / lsqr_refine_lm_grouped (assign_grouped.h, assign_lm_grouped.h)
   std::unique_ptr<AssignGrpBufs> assign_grp;
+  // what lsqr_assign_dense_grouped / lsqr_refine_dense_grouped hold beside it (assign_dense_grouped.h)
+  std::unique_ptr<AssignDenseGrpBufs> assign_dense_grp;
   // lsqr_ransac_sequential (sequential.h): the survivors of a round go from the current buffer into the OTHER of two
   // owned buffers (never into the caller's upload), their upload indices beside them; labels in upload order
   DevBuf<double> d_seq_rec[2];
@@ -4314,23 +4317,25 @@ int lsqr_ransac_grouped_sequential(lsqr_ctx *c, const int32_t *groups, size_t n_
   return LSQR_OK;
 }
 
-// ---- nearest-model assignment and refit (assign.h, assign_dense.h, assign_grouped.h) ---------------------------------
-// What the ten entry points share.  The checks, in the contract's order: the context; the model gate (AssignGate:
+// ---- nearest-model assignment and refit (assign.h, assign_dense.h, assign_grouped.h, assign_dense_grouped.h) ---------
+// What the twelve entry points share.  The checks, in the contract's order: the context; the model gate (AssignGate:
 // which models the entry point takes, and what it does with the geometric sphere, whose fit is iterative); count == 0
 // (n_models, or n_groups of the grouped calls) is LSQR_OK with every output untouched; more than 64 models; own(), the
 // entry point's own arguments; the context holds a model and records; their count.  Then run(tag), the run function
 // on the model -- it has waited for the stream when it returns.  The context's upload, hypotheses, mask, index and
-// d_par are not touched: the calls have buffers of their own (lsqr_ctx::assign, assign_dense, assign_grp).
+// d_par are not touched: the calls have buffers of their own (lsqr_ctx::assign, assign_dense, assign_grp,
+// assign_dense_grp).
 extern "C++" {
 enum AssignGate {
   ASSIGN_GATE_ANY,     // the assignments: every model of assign_model_ok
   ASSIGN_GATE_CLOSED,  // the refits in closed form: not the geometric sphere
   ASSIGN_GATE_LM,      // lsqr_refine_lm, lsqr_refine_lm_grouped: the geometric sphere alone
-  ASSIGN_GATE_DENSE    // lsqr_assign_dense, lsqr_refine_dense: the dense linear system alone
+  ASSIGN_GATE_DENSE    // lsqr_assign_dense, lsqr_refine_dense and their grouped forms: the dense linear system alone
 };
 // the entry point that takes what the gate refuses, [grouped][gate]
-static const char *const kAssignTakes[2][4] = {{"", "lsqr_refine_lm", "lsqr_refine", ""},
-                                               {"", "lsqr_refine_lm_grouped", "lsqr_refine_grouped", ""}};
+static const char *const kAssignTakes[2][4] = {
+    {"", "lsqr_refine_lm", "lsqr_refine", "lsqr_assign / lsqr_refine"},
+    {"", "lsqr_refine_lm_grouped", "lsqr_refine_grouped", "lsqr_assign_grouped / lsqr_refine_grouped"}};
 // the models run(tag) is compiled for
 template <AssignGate G, class M>
 constexpr bool kAssignTakesModel = G == ASSIGN_GATE_DENSE ? (bool)M::IS_DENSE : AssignModel<M>::value;
@@ -4343,8 +4348,8 @@ static int assign_frame(lsqr_ctx *c, const char *fn, bool grouped, size_t count,
   if (st != LSQR_OK) return st;
   if (G == ASSIGN_GATE_DENSE) {
     if (c->cfg.model != LSQR_MODEL_DENSE)
-      return fail(c, LSQR_ERR_INVALID, "%s: the dense linear system only (model %d); lsqr_assign / lsqr_refine take "
-                  "the plane, line, sphere and 2-D line", fn, c->cfg.model);
+      return fail(c, LSQR_ERR_INVALID, "%s: the dense linear system only (model %d); %s take "
+                  "the plane, line, sphere and 2-D line", fn, c->cfg.model, takes);
   } else if (G == ASSIGN_GATE_LM) {
     if (!(c->cfg.model == LSQR_MODEL_SPHERE && c->cfg.ls_type == LSQR_LS_GEOMETRIC))
       return fail(c, LSQR_ERR_INVALID, "%s: the sphere with LSQR_LS_GEOMETRIC only (model %d); %s takes the fits in "
@@ -4472,12 +4477,13 @@ int lsqr_refine_dense(lsqr_ctx *c, double *params_inout, size_t n_models, size_t
                                         labels_out, counts_out, fits, status_out, rounds_out, converged_out);
 }
 
-// lsqr_assign_grouped, lsqr_refine_grouped and lsqr_refine_lm_grouped.  The sort and the packed copy live in the batched
-// calls' buffers (lsqr_ctx::many), as lsqr_ransac_grouped's do.
+// lsqr_assign_grouped, lsqr_refine_grouped, lsqr_refine_lm_grouped and the dense pair.  The sort and the packed copy
+// live in the batched calls' buffers (lsqr_ctx::many), as lsqr_ransac_grouped's do.  (The dense gate serves an
+// assignment and a refit: J.refine is its caller's.)
 extern "C++" {
 template <AssignGate G>
 static int assign_grouped_call(lsqr_ctx *c, const char *fn, bool args, AssignGrpJob &J) {
-  J.refine = G != ASSIGN_GATE_ANY;
+  if (G != ASSIGN_GATE_DENSE) J.refine = G != ASSIGN_GATE_ANY;
   return assign_frame<G>(
       c, fn, true, J.n_groups, J.max_models, J.err,
       [&]() -> int {
@@ -4500,14 +4506,22 @@ static int assign_grouped_call(lsqr_ctx *c, const char *fn, bool args, AssignGrp
         J.n = c->n;
         J.B = c->assign_grp.get();
         typedef typename decltype(tag)::type M;
-        if constexpr (G != ASSIGN_GATE_LM) return assign_grouped_run<M>(J);
-        else if constexpr (requires { M::NMOM_LM; }) return assign_grouped_run<M, true>(J);  // (the sphere)
-        else return LSQR_ERR_INVALID;
+        if constexpr (G == ASSIGN_GATE_DENSE) {
+          if (!c->assign_dense_grp) c->assign_dense_grp.reset(new AssignDenseGrpBufs());
+          return assign_dense_grouped_run<M::NR>(J, *c->assign_dense_grp, J.pack.dense_fast, J.pack.dense_dd);
+        } else if constexpr (G != ASSIGN_GATE_LM) {
+          return assign_grouped_run<M>(J);
+        } else if constexpr (requires { M::NMOM_LM; }) {  // (the sphere)
+          return assign_grouped_run<M, true>(J);
+        } else {
+          return LSQR_ERR_INVALID;
+        }
       });
 }
 
-// lsqr_refine_grouped and, with lm, lsqr_refine_lm_grouped
-static int refine_grouped_call(lsqr_ctx *c, const char *fn, bool lm, const int32_t *groups, size_t n_groups,
+// lsqr_refine_grouped, lsqr_refine_lm_grouped and lsqr_refine_dense_grouped
+template <AssignGate G>
+static int refine_grouped_call(lsqr_ctx *c, const char *fn, const int32_t *groups, size_t n_groups,
                                int on_device, double *params_inout, const size_t *n_models, size_t max_models,
                                size_t max_rounds, int32_t *labels_out, uint64_t *counts_out, uint64_t *offsets_out,
                                lsqr_fit_info *fits, int32_t *status_out, size_t *rounds_out, int32_t *converged_out) {
@@ -4526,15 +4540,16 @@ static int refine_grouped_call(lsqr_ctx *c, const char *fn, bool lm, const int32
   J.status_out = status_out;
   J.rounds_out = rounds_out;
   J.converged_out = converged_out;
-  const bool args = fits && status_out && rounds_out && converged_out;
-  return lm ? assign_grouped_call<ASSIGN_GATE_LM>(c, fn, args, J)
-            : assign_grouped_call<ASSIGN_GATE_CLOSED>(c, fn, args, J);
+  J.refine = true;
+  return assign_grouped_call<G>(c, fn, fits && status_out && rounds_out && converged_out, J);
 }
-}  // extern "C++"
 
-int lsqr_assign_grouped(lsqr_ctx *c, const int32_t *groups, size_t n_groups, int on_device, const double *params,
-                        const size_t *n_models, size_t max_models, int32_t *labels_out, double *residuals_out,
-                        uint64_t *counts_out, uint64_t *offsets_out) {
+// lsqr_assign_grouped and lsqr_assign_dense_grouped
+template <AssignGate G>
+static int assign_only_grouped_call(lsqr_ctx *c, const char *fn, const int32_t *groups, size_t n_groups, int on_device,
+                                    const double *params, const size_t *n_models, size_t max_models,
+                                    int32_t *labels_out, double *residuals_out, uint64_t *counts_out,
+                                    uint64_t *offsets_out) {
   AssignGrpJob J;
   J.groups = groups;
   J.n_groups = n_groups;
@@ -4547,25 +4562,52 @@ int lsqr_assign_grouped(lsqr_ctx *c, const int32_t *groups, size_t n_groups, int
   J.residuals_out = residuals_out;
   J.counts_out = counts_out;
   J.offsets_out = offsets_out;
-  return assign_grouped_call<ASSIGN_GATE_ANY>(c, "lsqr_assign_grouped", labels_out != nullptr, J);
+  J.refine = false;
+  return assign_grouped_call<G>(c, fn, labels_out != nullptr, J);
+}
+}  // extern "C++"
+
+int lsqr_assign_grouped(lsqr_ctx *c, const int32_t *groups, size_t n_groups, int on_device, const double *params,
+                        const size_t *n_models, size_t max_models, int32_t *labels_out, double *residuals_out,
+                        uint64_t *counts_out, uint64_t *offsets_out) {
+  return assign_only_grouped_call<ASSIGN_GATE_ANY>(c, "lsqr_assign_grouped", groups, n_groups, on_device, params,
+                                                   n_models, max_models, labels_out, residuals_out, counts_out,
+                                                   offsets_out);
 }
 
 int lsqr_refine_grouped(lsqr_ctx *c, const int32_t *groups, size_t n_groups, int on_device, double *params_inout,
                         const size_t *n_models, size_t max_models, size_t max_rounds, int32_t *labels_out,
                         uint64_t *counts_out, uint64_t *offsets_out, lsqr_fit_info *fits, int32_t *status_out,
                         size_t *rounds_out, int32_t *converged_out) {
-  return refine_grouped_call(c, "lsqr_refine_grouped", false, groups, n_groups, on_device, params_inout, n_models,
-                             max_models, max_rounds, labels_out, counts_out, offsets_out, fits, status_out, rounds_out,
-                             converged_out);
+  return refine_grouped_call<ASSIGN_GATE_CLOSED>(c, "lsqr_refine_grouped", groups, n_groups, on_device, params_inout,
+                                             n_models, max_models, max_rounds, labels_out, counts_out, offsets_out,
+                                             fits, status_out, rounds_out, converged_out);
 }
 
 int lsqr_refine_lm_grouped(lsqr_ctx *c, const int32_t *groups, size_t n_groups, int on_device, double *params_inout,
                            const size_t *n_models, size_t max_models, size_t max_rounds, int32_t *labels_out,
                            uint64_t *counts_out, uint64_t *offsets_out, lsqr_fit_info *fits, int32_t *status_out,
                            size_t *rounds_out, int32_t *converged_out) {
-  return refine_grouped_call(c, "lsqr_refine_lm_grouped", true, groups, n_groups, on_device, params_inout, n_models,
-                             max_models, max_rounds, labels_out, counts_out, offsets_out, fits, status_out, rounds_out,
-                             converged_out);
+  return refine_grouped_call<ASSIGN_GATE_LM>(c, "lsqr_refine_lm_grouped", groups, n_groups, on_device, params_inout,
+                                             n_models, max_models, max_rounds, labels_out, counts_out, offsets_out,
+                                             fits, status_out, rounds_out, converged_out);
+}
+
+int lsqr_assign_dense_grouped(lsqr_ctx *c, const int32_t *groups, size_t n_groups, int on_device, const double *params,
+                              const size_t *n_models, size_t max_models, int32_t *labels_out, double *residuals_out,
+                              uint64_t *counts_out, uint64_t *offsets_out) {
+  return assign_only_grouped_call<ASSIGN_GATE_DENSE>(c, "lsqr_assign_dense_grouped", groups, n_groups, on_device,
+                                                     params, n_models, max_models, labels_out, residuals_out,
+                                                     counts_out, offsets_out);
+}
+
+int lsqr_refine_dense_grouped(lsqr_ctx *c, const int32_t *groups, size_t n_groups, int on_device, double *params_inout,
+                              const size_t *n_models, size_t max_models, size_t max_rounds, int32_t *labels_out,
+                              uint64_t *counts_out, uint64_t *offsets_out, lsqr_fit_info *fits, int32_t *status_out,
+                              size_t *rounds_out, int32_t *converged_out) {
+  return refine_grouped_call<ASSIGN_GATE_DENSE>(c, "lsqr_refine_dense_grouped", groups, n_groups, on_device,
+                                                params_inout, n_models, max_models, max_rounds, labels_out, counts_out,
+                                                offsets_out, fits, status_out, rounds_out, converged_out);
 }
 
 // C(n,k) and the rank-th k-subset in the exhaustive overload's order (comb.h); host only

@@ -69,9 +69,9 @@ inline hipError_t many_grow_pinned(PinBuf<char> &b, size_t bytes) {
 }  // namespace lsqr
 
 // a HIP call of the batched host code (many.h, many_lm.h, many_dense.h, many_exhaustive.h, many_sequential.h,
-// grouped.h, assign.h, assign_dense.h, assign_lm.h, assign_grouped.h, assign_lm_grouped.h; undefined at the end of the
-// last): J is the job at hand -- a ManyJob, the LM stage's ManyLmJob, whose err is the ManyJob's, an AssignJob or an
-// AssignGrpJob
+// grouped.h, assign.h, assign_dense.h, assign_lm.h, assign_grouped.h, assign_lm_grouped.h, assign_dense_grouped.h;
+// undefined at the end of the last): J is the job at hand -- a ManyJob, the LM stage's ManyLmJob, whose err is the
+// ManyJob's, an AssignJob or an AssignGrpJob
 #define MANYCHK(call)                                                                                \
   do {                                                                                               \
     hipError_t e_ = (call);                                                                          \

@@ -527,25 +527,8 @@ class RANSAC {
       }
       return rounds;
     }
-    size_t maxModels = 0;
-    std::vector<size_t> nModels;
-    std::vector<double> par = packGroupedModels(models, cfg, maxModels, nModels);
-    if (maxModels == 0) return rounds;
-    const size_t P = (size_t)lsqr_num_params(&cfg);
-    std::vector<int32_t> glab(groups.begin(), groups.end()), lab(N), status(n * maxModels), conv(n, 0);
-    std::vector<lsqr_fit_info> fits(n * maxModels);
-    lsqr_ctx *ctx = data.attach(cfg);
-    data.check(lsqr_refine_grouped(ctx, &glab[0], n, 0, &par[0], &nModels[0], maxModels, maxRounds, &lab[0], NULL, NULL,
-                                   &fits[0], &status[0], &rounds[0], &conv[0]));
-    for (size_t g = 0; g < n; g++) {
-      for (size_t m = 0; m < nModels[g]; m++) {
-        const double *row = &par[(g * maxModels + m) * P];
-        models[g][m].assign(row, row + P);
-      }
-      if (converged) (*converged)[g] = conv[g] != 0;
-    }
-    labels.assign(lab.begin(), lab.end());
-    return rounds;
+    return refineGroupedOnDevice(lsqr_refine_grouped, cfg, models, data, groups, n, maxRounds, labels, rounds,
+                                 converged);
   }
 
   // refineModelsGrouped for the sphere estimator with the geometric least-squares fit (its default), on the device: ONE
@@ -565,25 +548,50 @@ class RANSAC {
     std::vector<size_t> rounds(n, 0);
     if (converged) converged->assign(n, false);
     if (n == 0 || N == 0) return rounds;
+    return refineGroupedOnDevice(lsqr_refine_lm_grouped, cfg, models, data, groups, n, maxRounds, labels, rounds,
+                                 converged);
+  }
+
+  // assignToModelsGrouped / refineModelsGrouped for DenseLinearEquationSystemParametersEstimator<double,n>, which
+  // those two send to the host loop: ONE device call each for all groups (lsqr_assign_dense_grouped /
+  // lsqr_refine_dense_grouped), on the rows where they already are.  Arguments and what comes back are
+  // assignToModelsGrouped's / refineModelsGrouped's; every group is decided as assignToModelsDense / refineModelsDense
+  // decide it on the rows of the group alone.  Any other estimator throws std::invalid_argument.
+  static void assignToModelsDenseGrouped(const std::vector<std::vector<std::vector<S> > > &models,
+                                         ParametersEstimator<T, S> *paramEstimator, ResidentData<T> &data,
+                                         const std::vector<int> &groups, size_t nGroups, std::vector<int> &labels) {
+    lsqr_model_cfg cfg;
+    groupedArgs(models.size(), paramEstimator, data, groups, nGroups);
+    denseOnly(paramEstimator, cfg, "assignToModelsDenseGrouped");
+    const size_t n = nGroups, N = data.size();
+    labels.assign(N, -1);
+    if (n == 0 || N == 0) return;
     size_t maxModels = 0;
     std::vector<size_t> nModels;
     std::vector<double> par = packGroupedModels(models, cfg, maxModels, nModels);
-    if (maxModels == 0) return rounds;
-    const size_t P = (size_t)lsqr_num_params(&cfg);
-    std::vector<int32_t> glab(groups.begin(), groups.end()), lab(N), status(n * maxModels), conv(n, 0);
-    std::vector<lsqr_fit_info> fits(n * maxModels);
+    if (maxModels == 0) return;
+    std::vector<int32_t> glab(groups.begin(), groups.end()), lab(N);
     lsqr_ctx *ctx = data.attach(cfg);
-    data.check(lsqr_refine_lm_grouped(ctx, &glab[0], n, 0, &par[0], &nModels[0], maxModels, maxRounds, &lab[0], NULL,
-                                      NULL, &fits[0], &status[0], &rounds[0], &conv[0]));
-    for (size_t g = 0; g < n; g++) {
-      for (size_t m = 0; m < nModels[g]; m++) {
-        const double *row = &par[(g * maxModels + m) * P];
-        models[g][m].assign(row, row + P);
-      }
-      if (converged) (*converged)[g] = conv[g] != 0;
-    }
+    data.check(lsqr_assign_dense_grouped(ctx, &glab[0], n, 0, &par[0], &nModels[0], maxModels, &lab[0], NULL, NULL,
+                                         NULL));
     labels.assign(lab.begin(), lab.end());
-    return rounds;
+  }
+
+  static std::vector<size_t> refineModelsDenseGrouped(std::vector<std::vector<std::vector<S> > > &models,
+                                                      ParametersEstimator<T, S> *paramEstimator,
+                                                      ResidentData<T> &data, const std::vector<int> &groups,
+                                                      size_t nGroups, size_t maxRounds, std::vector<int> &labels,
+                                                      std::vector<bool> *converged = NULL) {
+    lsqr_model_cfg cfg;
+    groupedArgs(models.size(), paramEstimator, data, groups, nGroups);
+    denseOnly(paramEstimator, cfg, "refineModelsDenseGrouped");
+    const size_t n = nGroups, N = data.size();
+    labels.assign(N, -1);
+    std::vector<size_t> rounds(n, 0);
+    if (converged) converged->assign(n, false);
+    if (n == 0 || N == 0) return rounds;
+    return refineGroupedOnDevice(lsqr_refine_dense_grouped, cfg, models, data, groups, n, maxRounds, labels, rounds,
+                                 converged);
   }
 
   // Sequential RANSAC over many independent problems (not in the reference): problem j is data[j], and
@@ -918,7 +926,8 @@ class RANSAC {
     return cfg.model == LSQR_MODEL_PLANE || cfg.model == LSQR_MODEL_LINE || cfg.model == LSQR_MODEL_LINE2D;
   }
 
-  // assignToModelsDense / refineModelsDense: the estimator's device model must be the dense linear system
+  // assignToModelsDense / refineModelsDense and their grouped forms: the estimator's device model must be the dense
+  // linear system
   static void denseOnly(ParametersEstimator<T, S> *paramEstimator, lsqr_model_cfg &cfg, const char *fn) {
     if (!paramEstimator) throw std::invalid_argument("lsqrRecipes::RANSAC: null estimator");
     if (!paramEstimator->deviceModel(cfg) || cfg.model != LSQR_MODEL_DENSE)
@@ -966,6 +975,38 @@ class RANSAC {
     if (!paramEstimator) throw std::invalid_argument("lsqrRecipes::RANSAC: null estimator");
     if (groups.size() != data.size()) throw std::invalid_argument("lsqrRecipes::RANSAC: one group label per record");
     if (nSets != nGroups) throw std::invalid_argument("lsqrRecipes::RANSAC: one model set per group");
+  }
+
+  // the device path of refineModelsGrouped (lsqr_refine_grouped), refineModelsLMGrouped (lsqr_refine_lm_grouped) and
+  // refineModelsDenseGrouped (lsqr_refine_dense_grouped); labels, rounds and *converged hold the answer for "nothing
+  // ran"
+  typedef int (*RefineGroupedCall)(lsqr_ctx *, const int32_t *, size_t, int, double *, const size_t *, size_t, size_t,
+                                   int32_t *, uint64_t *, uint64_t *, lsqr_fit_info *, int32_t *, size_t *, int32_t *);
+  static std::vector<size_t> refineGroupedOnDevice(RefineGroupedCall call, lsqr_model_cfg &cfg,
+                                                   std::vector<std::vector<std::vector<S> > > &models,
+                                                   ResidentData<T> &data, const std::vector<int> &groups, size_t n,
+                                                   size_t maxRounds, std::vector<int> &labels,
+                                                   std::vector<size_t> &rounds, std::vector<bool> *converged) {
+    const size_t N = data.size();
+    size_t maxModels = 0;
+    std::vector<size_t> nModels;
+    std::vector<double> par = packGroupedModels(models, cfg, maxModels, nModels);
+    if (maxModels == 0) return rounds;
+    const size_t P = (size_t)lsqr_num_params(&cfg);
+    std::vector<int32_t> glab(groups.begin(), groups.end()), lab(N), status(n * maxModels), conv(n, 0);
+    std::vector<lsqr_fit_info> fits(n * maxModels);
+    lsqr_ctx *ctx = data.attach(cfg);
+    data.check(call(ctx, &glab[0], n, 0, &par[0], &nModels[0], maxModels, maxRounds, &lab[0], NULL, NULL, &fits[0],
+                    &status[0], &rounds[0], &conv[0]));
+    for (size_t g = 0; g < n; g++) {
+      for (size_t m = 0; m < nModels[g]; m++) {
+        const double *row = &par[(g * maxModels + m) * P];
+        models[g][m].assign(row, row + P);
+      }
+      if (converged) (*converged)[g] = conv[g] != 0;
+    }
+    labels.assign(lab.begin(), lab.end());
+    return rounds;
   }
 
   // the per-group vectors of the host loops (as computeGroupedSequential gathers them), and every record's own place

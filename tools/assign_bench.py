@@ -62,7 +62,17 @@ a, noise 0.01 on b, the rest clutter; delta 0.04; the start rows are the planted
 Two kinds alternate in one process: refine_round_ms as above, and baseline_round_ms, the round the entry points allowed
 before: M x (lsqr_mask + lsqr_set_mask + lsqr_ls_fit).  rows_read_per_round: how often a round reads each row -- once
 for the new call, 2 M times for the baseline (a mask pass and a Gram pass per model); partial_bytes: the call's device
-scratch for the chunk blocks, which a round writes once and reads once."""
+scratch for the chunk blocks, which a round writes once and reads once.
+
+--model dense --grouped: Context.refine_dense_grouped (lsqr_refine_dense_grouped: one regression set per label) on --n
+rows split into --groups groups of n / groups rows each, every group its own dense_scene: --models (the first value)
+planted regressions of 1 / (M + 1) of its rows each and clutter, the start rows moved off inside the noise band by a
+different amount per group, so the groups stop at different rounds; the labels are shuffled over the upload and live
+on the device, and the timed calls ask for no labels.  grouped_round_ms, grouped_call_ms and loop_call_ms (per group a
+host gather, upload, Context.refine_dense(max_rounds = R2) and the labels written back) as for --grouped above.  With
+--groups 1 also refine_round_ms / refine_call_ms, Context.refine_dense on the same rows: the per-round difference is
+the price of the (group, chunk) indirection, the whole-call difference the sort, the gather and the scatter.
+lane_share = rows / (workgroups x chunk)."""
 import argparse
 import json
 import os
@@ -302,6 +312,100 @@ def dense_main(a):
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
             f.write("\n".join(lines) + "\n")
+
+
+def dense_grouped_scene(n, n_groups, dim, m, seed=20261024):
+    """-> rows (a | b) shuffled, labels, start rows (n_groups, m, dim): every group a dense_scene of n / n_groups rows"""
+    g = np.random.default_rng([seed, dim, m, n_groups])
+    per = n // n_groups
+    x = g.normal(size=(n_groups, m, dim))
+    grp = np.repeat(np.arange(n_groups, dtype=np.int32), per)
+    owner = np.tile(np.arange(per) % (m + 1), n_groups)  # m: clutter
+    on = owner < m
+    rows = np.empty((grp.size, dim + 1))
+    rows[:, :dim] = g.normal(size=(grp.size, dim))
+    rows[:, dim] = (np.einsum("ij,ij->i", rows[:, :dim], x[grp, np.minimum(owner, m - 1)])
+                    + DENSE_SIGMA * g.normal(size=grp.size))
+    rows[~on, dim] = g.uniform(-10.0, 10.0, int((~on).sum()))
+    size = g.uniform(0.5, 2.0, (n_groups, 1, 1))  # per group its own distance from the planted rows
+    start = x + size * DENSE_SIGMA / np.sqrt(dim) * g.normal(size=x.shape)
+    perm = g.permutation(grp.size)
+    return np.ascontiguousarray(rows[perm]), np.ascontiguousarray(grp[perm]), np.ascontiguousarray(start)
+
+
+def dense_grouped_main(a):
+    r1, r2 = a.rounds
+    ms = lambda v: [round(1e3 * float(f(v)), 4) for f in (np.median, np.min, np.max)]
+    dim, n_groups, k = a.dim, a.groups, a.models[0]
+    data, grp, rows = dense_grouped_scene(a.n, n_groups, dim, k)
+    n = data.shape[0]
+    sizes = np.bincount(grp, minlength=n_groups)
+    order = np.argsort(grp, kind="stable")
+    first = np.concatenate([[0], np.cumsum(sizes)])
+    loop_groups = min(n_groups, a.loop_groups)
+    with Context(0) as ctx, Context(0) as one:
+        ctx.set_model(L.DENSE, dim, 4 * DENSE_SIGMA).upload(data)
+        one.set_model(L.DENSE, dim, 4 * DENSE_SIGMA)
+        dev = DeviceArray(grp)
+        t_lo, t_hi, t_loop, t_ref_lo, t_ref_hi, done, ref_done = [], [], [], [], [], None, None
+        for rep in range(-1, a.reps):  # rep -1 warms every kind
+            t0 = time.perf_counter()
+            lo = ctx.refine_dense_grouped(dev, n_groups, rows, max_rounds=r1)
+            t1 = time.perf_counter()
+            hi = ctx.refine_dense_grouped(dev, n_groups, rows, max_rounds=r2)
+            t2 = time.perf_counter()
+            if rep < a.baseline_reps:  # the only route without the call, on the first groups
+                labels = np.full(n, -1, dtype=np.int32)
+                for g in range(loop_groups):
+                    at = order[first[g]:first[g + 1]]
+                    one.upload(np.ascontiguousarray(data[at]))
+                    labels[at] = one.refine_dense(rows[g], max_rounds=r2)["labels"]
+            t3 = time.perf_counter()
+            if n_groups == 1:
+                ref = (refine_rounds(ctx, rows[0], r1, dense=True), None)
+                t4 = time.perf_counter()
+                ref = (ref[0], refine_rounds(ctx, rows[0], r2, dense=True))
+                t5 = time.perf_counter()
+                ref_done = ref
+            work = (int((sizes * lo["rounds"]).sum()), int((sizes * hi["rounds"]).sum()))
+            if work[1] <= work[0]:
+                raise SystemExit("every group has stopped after %d rounds: nothing to time" % r1)
+            if done is not None and done != work:
+                raise SystemExit("the rounds done differ between repetitions")
+            done = work
+            if rep >= 0:
+                t_lo.append(t1 - t0)
+                t_hi.append(t2 - t1)
+                if rep < a.baseline_reps:
+                    t_loop.append((t3 - t2) * n_groups / loop_groups)
+                if n_groups == 1:
+                    t_ref_lo.append(t4 - t3)
+                    t_ref_hi.append(t5 - t4)
+        dev.free()
+    per = [(h - l) / (done[1] - done[0]) * n for h, l in zip(t_hi, t_lo)]
+    rnd = float(np.median(per))
+    chunk = L.assign_dense_chunk(dim)
+    wgs = int(np.sum((sizes[sizes > 0] + chunk - 1) // chunk))
+    ps = ((dim + 1) * (dim + 2) // 2 + 1 + 7) & ~7
+    row = dict(model="dense", grouped=True, dim=dim, n=n, groups=n_groups, models=k, reps=a.reps, rounds=[r1, r2],
+               record_rounds_done=list(done), rounds_hist=np.bincount(hi["rounds"]).tolist(),
+               converged=int(hi["converged"].sum()), route_hist=np.bincount(hi["route"].ravel()).tolist(),
+               grouped_round_ms=ms(per), grouped_call_ms=ms(t_hi), chunk=chunk, workgroups=wgs,
+               lane_share=round(n / (wgs * float(chunk)), 4), partial_bytes=int(wgs * k * ps * 8),
+               hbm_fraction=round(n * 8 * (dim + 1) / rnd / HBM_PEAK, 4))
+    if t_loop:
+        row.update(loop_call_ms=ms(t_loop), loop_groups_timed=loop_groups, loop_scaled_by=n_groups / loop_groups,
+                   loop_reps=len(t_loop), ratio_call=round(float(np.median(t_loop) / np.median(t_hi)), 1))
+    if n_groups == 1:
+        row["refine_round_ms"] = ms([(h - l) / (ref_done[1] - ref_done[0]) for h, l in zip(t_ref_hi, t_ref_lo)])
+        row["refine_call_ms"] = ms(t_ref_hi)
+        row["refine_rounds_done"] = list(ref_done)
+    line = json.dumps(row)
+    print(line, flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
 
 
 class DeviceArray:
@@ -545,7 +649,7 @@ def main():
     ap.add_argument("--model", choices=sorted(SYNTH) + ["dense"], default="plane")
     ap.add_argument("--dim", type=int, default=3)
     ap.add_argument("--lm", action="store_true", help="time Context.refine_lm on the sphere scene instead (see above)")
-    ap.add_argument("--groups", type=int, default=3000, help="--grouped --lm: the groups of the scene")
+    ap.add_argument("--groups", type=int, default=3000, help="--grouped --lm, --model dense --grouped: the groups of the scene")
     a = ap.parse_args()
     if a.lm and a.grouped:
         return grouped_lm_main(a)
@@ -553,9 +657,12 @@ def main():
         a.models = [4, 64] if a.models == [4, 16, 64] else a.models
         return lm_main(a)
     if a.model == "dense":
-        if a.grouped or a.lm:
-            raise SystemExit("--model dense goes with neither --grouped nor --lm")
+        if a.lm:
+            raise SystemExit("--model dense does not go with --lm")
         a.n = 1_000_000 if a.n == 10_000_000 else a.n
+        if a.grouped:
+            a.models = [4] if a.models == [4, 16, 64] else a.models
+            return dense_grouped_main(a)
         a.models = [4, 16] if a.models == [4, 16, 64] else a.models
         return dense_main(a)
     a.model_id = SYNTH[a.model][0]
