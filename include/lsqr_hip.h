@@ -181,6 +181,15 @@ LSQR_API int lsqr_assign_host(const lsqr_model_cfg *cfg, const double *params, s
  * LSQR_ERR_INVALID and writes nothing.  lsqr_assign_host keeps refusing LSQR_MODEL_DENSE. */
 LSQR_API int lsqr_assign_dense_host(const lsqr_model_cfg *cfg, const double *params, size_t n_models,
                                     const void *record, int32_t *label_out, double *residual_out /* nullable */);
+/* The same for lsqr_assign_rigid (below): cfg is LSQR_MODEL_ABSOR (ls_type 0: record = a pair of 6 doubles; ls_type 2:
+ * 7 doubles, slot 6 the weight), LSQR_MODEL_PIVOT (a frame of 13 slots) or LSQR_MODEL_RAY (6 doubles); params holds
+ * n_models rows of lsqr_num_params doubles.  The code the kernel of lsqr_assign_rigid runs, compiled for the host:
+ * bit-identical labels and residuals.  A record with a non-finite slot among those the model loads -- the weight
+ * included with ls_type 2 -- gets -1 and +infinity.  n_models == 0 returns LSQR_OK and writes nothing; every other
+ * model, n_models > 64 or a null cfg, params, record or label_out returns LSQR_ERR_INVALID and writes nothing.
+ * lsqr_assign_host keeps refusing these three models. */
+LSQR_API int lsqr_assign_rigid_host(const lsqr_model_cfg *cfg, const double *params, size_t n_models,
+                                    const void *record, int32_t *label_out, double *residual_out /* nullable */);
 
 /* ---- agree() scan over all observations (RANSAC.hxx:94-99, without the early exit) ---------- */
 LSQR_API int lsqr_scan(lsqr_ctx *ctx);
@@ -556,6 +565,63 @@ LSQR_API int lsqr_assign_dense(lsqr_ctx *ctx, const double *params /* host, n_mo
                                uint64_t *counts_out /* nullable, host: n_models + 1, last = unassigned */);
 LSQR_API int lsqr_refine_dense(lsqr_ctx *ctx, double *params_inout /* host, n_models * n */, size_t n_models,
                                size_t max_rounds, int on_device /* 1: labels_out is a device pointer */,
+                               int32_t *labels_out /* nullable */,
+                               uint64_t *counts_out /* nullable, host: n_models + 1 */,
+                               lsqr_fit_info *fits /* host, n_models */, int32_t *status_out /* host, n_models */,
+                               size_t *rounds_out, int *converged_out);
+/* ---- lsqr_assign / lsqr_refine for absolute orientation, pivot and ray (csrc/assign_rigid.h) -------------------------
+ * Several rigid motions between two point sets, several tools pivoted in one recording, several targets triangulated
+ * from one bundle of rays: every record goes to the nearest of up to 64 models it agrees with, and every model is
+ * fitted again on its own records.  lsqr_assign_rigid / lsqr_refine_rigid are lsqr_assign / lsqr_refine -- their
+ * arguments, their loop and its stop rules, rounds_out / converged_out / counts_out / labels_out, the order of their
+ * checks, "every argument error writes nothing" -- with the model changed; lsqr_assign, lsqr_refine, lsqr_assign_host
+ * and every grouped form keep refusing these models.
+ *   Models: LSQR_MODEL_ABSOR with ls_type 0 (records of 6 doubles: first, second) or ls_type 2 (7 doubles, slot 6 the
+ *     weight: the weighted fit); LSQR_MODEL_PIVOT (frames of 13 slots); LSQR_MODEL_RAY (6 doubles: p, n; aux is not
+ *     used here).  Every other model returns LSQR_ERR_INVALID and writes nothing.  n_models <= 64; params holds
+ *     n_models rows of lsqr_num_params doubles (7 / 6 / 3).
+ *   Decision: label(x) = the smallest m that minimises residual(row_m, x) among the m with agree(row_m, x) (strict '<'
+ *     while m walks upwards: ties go to the smaller m); -1 when none agrees, and for a record with a non-finite slot
+ *     among those the model loads, the weight included with ls_type 2.  row_m is the scan row lsqr_mask makes of
+ *     params[m], so labels_out[i] and residuals_out[i] (+infinity for -1) equal, bit for bit, the first argmin over
+ *     lsqr_mask / lsqr_residuals of the same rows on the same context, and what lsqr_assign_rigid_host gives.  The
+ *     ray's agree() holds t >= 0 beside the distance; its residual is the distance to the ray's LINE.
+ *   Loop: lsqr_refine's.  max_rounds == 0 is lsqr_assign_rigid, and the returned labels are always exactly
+ *     lsqr_assign_rigid of the returned parameters.
+ *   Refit of model m in a round: with at least lsqr_min_subset (3 / 3 / 2) records labelled m, the moment block of
+ *     those records and the model's closed-form solve (Horn's quaternion, weighted with ls_type 2; the pivot's 6 x 6
+ *     normal equations; the rays' 3 x 3 system).  The row is replaced only when the solve gives a result -- rays that
+ *     are all parallel, or frames that are all the same, give none --, otherwise it keeps its values.  status_out[m],
+ *     fits[m].n_params and fits[m].n_used as lsqr_refine reports them.  Model m's new row agrees with
+ *     lsqr_set_mask(L_r == m) + lsqr_ls_fit(use_mask = 1) on the same context up to the origin and the order of the
+ *     fp64 sums (the quaternion up to its sign).
+ *   Origin of model m's moment block (these parameters hold no point, so it is part of the contract):
+ *     ray    the model's own point, params[m], as for the plane; it moves with the row from round to round;
+ *     pivot  none: the block is not shifted;
+ *     absolute orientation   the pair (first, second) of the lowest-index record that is finite and agrees with row m
+ *            AS PASSED IN, fixed for the whole call: lsqr_ls_fit's "first record whose mask bit is set" for the mask
+ *            of the entry row.  One pre-pass finds it, once per lsqr_refine_rigid call with max_rounds > 0 and never
+ *            for lsqr_assign_rigid, with integer minima only.  It lies among the model's data even when record 0 is an
+ *            outlier or not finite.  A model no record agrees with at entry can never receive one (rows change only by
+ *            a refit), so it has no origin and needs none.
+ *   Sums: none is a floating-point atomic; the same call twice gives the same bits.  A model's block is a function of
+ *     its own records, their positions in the upload, its own row and origin, and the fixed chunking (2048 records per
+ *     chunk for absolute orientation and the ray, 1024 for the pivot; within a chunk by lane and wave in a fixed tree,
+ *     the chunks in order): not of the grid, of the other rows of the call, or of where m sits among them.
+ *   Checks, in this order: a null context; the model (none set: LSQR_ERR_STATE; not one of the three:
+ *     LSQR_ERR_INVALID); n_models == 0 is a no-op returning LSQR_OK; n_models > 64, or a null params or labels_out
+ *     (lsqr_assign_rigid), a null params_inout, fits, status_out, rounds_out or converged_out (lsqr_refine_rigid)
+ *     (LSQR_ERR_INVALID); no records in the context (LSQR_ERR_STATE); more than 2^32 - 16 records (LSQR_ERR_INVALID).
+ *   The context's hypotheses, mask, spatial index and the parameters of its last mask are left as they were; the work
+ *     runs on the context's stream, and the call returns after it has finished.  There is no grouped form and no
+ *     lsqr_multi form; the US calibrations and the phantom are refused. */
+LSQR_API int lsqr_assign_rigid(lsqr_ctx *ctx, const double *params /* host, n_models * lsqr_num_params */,
+                               size_t n_models, int on_device /* 1: labels_out, residuals_out are device pointers */,
+                               int32_t *labels_out /* lsqr_count(ctx) entries, upload order */,
+                               double *residuals_out /* nullable */,
+                               uint64_t *counts_out /* nullable, host: n_models + 1, last = unassigned */);
+LSQR_API int lsqr_refine_rigid(lsqr_ctx *ctx, double *params_inout /* host, n_models * lsqr_num_params */,
+                               size_t n_models, size_t max_rounds, int on_device /* 1: labels_out is a device pointer */,
                                int32_t *labels_out /* nullable */,
                                uint64_t *counts_out /* nullable, host: n_models + 1 */,
                                lsqr_fit_info *fits /* host, n_models */, int32_t *status_out /* host, n_models */,

@@ -78,6 +78,8 @@ SIGNATURES = {
                                    _dp]),
     "lsqr_assign_dense_host": (C.c_int, [C.POINTER(ModelCfg), C.c_void_p, C.c_size_t, C.c_void_p,
                                          C.POINTER(C.c_int32), _dp]),
+    "lsqr_assign_rigid_host": (C.c_int, [C.POINTER(ModelCfg), C.c_void_p, C.c_size_t, C.c_void_p,
+                                         C.POINTER(C.c_int32), _dp]),
     "lsqr_scan": (C.c_int, [_ctx]),
     "lsqr_get_hypotheses": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lsqr_num_hypotheses": (C.c_size_t, [_ctx]),
@@ -128,6 +130,9 @@ SIGNATURES = {
                                  C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
     "lsqr_assign_dense": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lsqr_refine_dense": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
+    "lsqr_assign_rigid": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lsqr_refine_rigid": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
     "lsqr_assign_grouped": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -601,6 +601,26 @@ class Context:
         out.update(route=f["reserved"].copy())
         return out
 
+    def assign_rigid(self, params, want_residuals=False, labels_out=None):
+        """assign for absolute orientation (ls_type 0, or 2: weighted pairs), pivot calibration and ray intersection,
+        which assign refuses (lsqr_assign_rigid): every record of the current upload / attach to the nearest of the
+        models it agrees with.  params: M <= 64 rows of P parameters (7 / 6 / 3).  label = the smallest m that minimises
+        residual(params[m], x) among the m with agree(params[m], x), -1 when none agrees and for a record with a
+        non-finite slot (the weight included with ls_type 2); labels and residuals equal the first argmin over mask() /
+        residuals() of the same rows bit for bit.  Any other model raises LsqrError(ERR_INVALID).  labels_out and the
+        result as for assign."""
+        return self._assign(self._lib.lsqr_assign_rigid, params, want_residuals, labels_out)
+
+    def refine_rigid(self, params, max_rounds=8, labels_out=None):
+        """refine for the models of assign_rigid (lsqr_refine_rigid): the same loop, and the refit of a model is its
+        closed-form fit over its own records -- Horn's quaternion (weighted with ls_type 2), the pivot's normal
+        equations, the rays' 3 x 3 system.  A model with fewer than K records, or whose solve gives no result (rays all
+        parallel, frames all the same), keeps its row for that round.  The sums of a ray model are taken about the
+        model's own point; those of an absolute orientation about the lowest-index record that is finite and agrees
+        with the row as passed in, for the whole call.  Any other model raises LsqrError(ERR_INVALID).
+        -> refine's dict."""
+        return self._refine(self._lib.lsqr_refine_rigid, params, max_rounds, labels_out)[0]
+
     def _assign_grouped_args(self, groups, n_groups, params, n_models, labels_out):
         """the labels, rows and label buffer of assign_grouped / refine_grouped, groups and labels_out handled as in
         ransac_grouped_sequential -> (n, m, total, on_device, g, g_ptr, par, nm, labels, l_ptr); g keeps the host

@@ -32,12 +32,14 @@
 //                      through LDS): k_assign_solve's sum, and k_assign_lm_step's
 //   k_assign_solve     one workgroup per model: assign_sum_chunks, then assign_refit
 //
-// assign_rounds<F> is the round loop of all six ungrouped calls, written once; a family F says what differs -- its
+// assign_rounds<F> is the round loop of all eight ungrouped calls, written once; a family F says what differs -- its
 // buffers, how parameters become scan rows and come back, which kernels make the pass, what the refit enqueues, its
 // counter words and what it adds to a fit record.  AssignClosed<M> (here) is lsqr_assign's and lsqr_refine's.
 // AssignLm<M> (assign_lm.h, the geometric sphere: lsqr_refine_lm) is AssignClosed<M> whose pass also stores every
 // chunk's presence word, whose solve writes into a side array of start rows and whose refit is an LM stage.
-// AssignDense<NR> (assign_dense.h) is the dense linear system's, with kernels of its own.
+// AssignDense<NR> (assign_dense.h) is the dense linear system's, with kernels of its own.  AssignRigid<M>
+// (assign_rigid.h: absolute orientation, pivot, ray) is AssignClosed<M> with a chunk size of its own and, for the pass
+// body and assign_refit, an origin that need not be the model's own point.
 //
 // Order of the sums: kAssignChunk fixes it, as kManyPart does for the batched finish.  Nothing is summed with a
 // floating-point atomic, so two runs of one call give the same bits.
@@ -122,12 +124,38 @@ LSQR_HD int32_t assign_one(const double *rows, int n_models, const double *x, co
   return label;
 }
 
-// lsqr_assign_host, and (DENSE) lsqr_assign_dense_host: no context, no device.  DENSE takes the dense linear system
-// alone, whose parameters are cfg->dim coefficients; its scan rows (assign_dense.h) are zero beyond them
-template <bool DENSE>
+// The models lsqr_assign_rigid / lsqr_refine_rigid take (assign_rigid.h): closed-form fits whose parameters hold no
+// point to sum about.  A gate of its own: lsqr_assign, lsqr_refine and the grouped calls keep refusing them.
+template <class M> struct AssignRigidModel { static constexpr bool value = false; };
+template <> struct AssignRigidModel<AbsOrModel> { static constexpr bool value = true; };
+template <> struct AssignRigidModel<PivotModel> { static constexpr bool value = true; };
+template <> struct AssignRigidModel<RayModel> { static constexpr bool value = true; };
+
+inline bool assign_rigid_model_ok(const lsqr_model_cfg &cfg) {
+  // absolute orientation: records of 6 doubles (ls_type 0) or of 7 with a weight (ls_type 2), nothing else
+  if (cfg.model == LSQR_MODEL_ABSOR && cfg.ls_type != 0 && cfg.ls_type != 2) return false;
+  return dispatch(cfg, [](auto tag) -> int {
+           return AssignRigidModel<typename decltype(tag)::type>::value ? LSQR_OK : LSQR_ERR_INVALID;
+         }) == LSQR_OK;
+}
+
+// which models a single-record host call takes
+enum AssignHostKind { ASSIGN_HOST_POINT, ASSIGN_HOST_DENSE, ASSIGN_HOST_RIGID };
+template <AssignHostKind KIND, class M>
+constexpr bool kAssignHostTakes = KIND == ASSIGN_HOST_DENSE   ? (bool)M::IS_DENSE
+                                  : KIND == ASSIGN_HOST_RIGID ? AssignRigidModel<M>::value
+                                                              : AssignModel<M>::value;
+
+// lsqr_assign_host, (ASSIGN_HOST_DENSE) lsqr_assign_dense_host and (ASSIGN_HOST_RIGID) lsqr_assign_rigid_host: no
+// context, no device.  DENSE takes the dense linear system alone, whose parameters are cfg->dim coefficients; its scan
+// rows (assign_dense.h) are zero beyond them
+template <AssignHostKind KIND>
 int host_assign_host(const lsqr_model_cfg *cfg, const double *params, size_t n_models, const void *record,
                      int32_t *label_out, double *residual_out) {
-  if (!cfg || !cfg_supported(*cfg) || !(DENSE ? cfg->model == LSQR_MODEL_DENSE : assign_model_ok(*cfg)))
+  constexpr bool DENSE = KIND == ASSIGN_HOST_DENSE;
+  if (!cfg || !cfg_supported(*cfg) ||
+      !(DENSE ? cfg->model == LSQR_MODEL_DENSE
+              : KIND == ASSIGN_HOST_RIGID ? assign_rigid_model_ok(*cfg) : assign_model_ok(*cfg)))
     return LSQR_ERR_INVALID;
   if (n_models == 0) return LSQR_OK;
   if (n_models > (size_t)kAssignMaxModels || !params || !record || !label_out) return LSQR_ERR_INVALID;
@@ -135,7 +163,7 @@ int host_assign_host(const lsqr_model_cfg *cfg, const double *params, size_t n_m
   model_consts(*cfg, &mc);
   return dispatch(*cfg, [&](auto tag) -> int {
     typedef typename decltype(tag)::type M;
-    if constexpr (DENSE ? (bool)M::IS_DENSE : AssignModel<M>::value) {
+    if constexpr (kAssignHostTakes<KIND, M>) {
       const size_t p = DENSE ? (size_t)cfg->dim : (size_t)M::P;
       std::vector<double> rows(n_models * M::SP, 0.0);  // scan rows, as lsqr_mask makes one (assign_make_row)
       for (size_t m = 0; m < n_models; m++) {
@@ -191,8 +219,15 @@ __global__ __launch_bounds__(kBlock) void k_assign_prepare(const double *__restr
 // data: the chunk's records, `stride` doubles apart; rows: the n_models scan rows of the chunk's model set; labels /
 // residuals (nullable) / old (nullable): the chunk's n entries; changed: the word that counts labels[i] != old[i];
 // counts: one word per model; partials (WITH_MOMENTS): the chunk's [model][AccLs<M>::N]; presence (WITH_MOMENTS,
-// nullable): the chunk's word for the mask of the models that own a record of the chunk
-template <class M, bool WITH_MOMENTS>
+// nullable): the chunk's word for the mask of the models that own a record of the chunk.
+// R: the records a lane keeps, so n <= R * kBlock (assign_rigid.h takes fewer of the pivot's wide frames); org_tab
+// (nullable: null for every family but the rigid one): the origins [model][kAssignOrigin<M>] of the moment blocks,
+// taken instead of the model's own point at rows[m][org_off ..]
+template <class M> constexpr int kAssignOrigin = M::ND;  // the origin's doubles
+template <> constexpr int kAssignOrigin<RayModel> = 3;   // (a ray's record is [p, n]: its origin is a point)
+template <> constexpr int kAssignOrigin<PivotModel> = 0; // (PivotModel::accumulate reads none)
+
+template <class M, bool WITH_MOMENTS, int R = kAssignPerLane>
 __device__ __forceinline__ void assign_pass_chunk(const double *__restrict__ data, size_t stride, uint32_t n,
                                                   const double *__restrict__ rows, int n_models, int org_off,
                                                   const ModelConsts &mc, int32_t *__restrict__ labels,
@@ -200,10 +235,11 @@ __device__ __forceinline__ void assign_pass_chunk(const double *__restrict__ dat
                                                   unsigned long long *__restrict__ changed,
                                                   unsigned long long *__restrict__ counts,
                                                   double *__restrict__ partials,
-                                                  unsigned long long *__restrict__ presence) {
+                                                  unsigned long long *__restrict__ presence,
+                                                  const double *__restrict__ org_tab = nullptr) {
   typedef AccLs<M> A;
   static_assert(A::N <= 64, "one lane per moment");
-  constexpr int R = kAssignPerLane, W = kBlock / 64;
+  constexpr int W = kBlock / 64;
   __shared__ double s_m[2][W][WITH_MOMENTS ? (int)A::N : 1];
   __shared__ unsigned long long s_p[W];
   __shared__ uint32_t s_chg[W];
@@ -273,9 +309,9 @@ __device__ __forceinline__ void assign_pass_chunk(const double *__restrict__ dat
       if (here) {
         constexpr int NC = M::P > M::REC ? M::P : M::REC;
         double cv[NC], acc[A::N];
-        const double *org = rows + (size_t)m * M::SP + org_off;
+        const double *org = org_tab ? org_tab + (size_t)m * kAssignOrigin<M> : rows + (size_t)m * M::SP + org_off;
 #pragma unroll
-        for (int k = 0; k < NC; k++) cv[k] = k < (int)M::ND ? org[k] : 0.0;
+        for (int k = 0; k < NC; k++) cv[k] = k < kAssignOrigin<M> ? org[k] : 0.0;
 #pragma unroll
         for (int k = 0; k < (int)A::N; k++) acc[k] = 0.0;
 #pragma unroll
@@ -339,14 +375,17 @@ __global__ __launch_bounds__(kBlock, (kAssignPassWaves<M, WITH_MOMENTS>)) void k
 
 // What lane 0 of a solve kernel does with a model's summed moments: the refit about the model's own point (the body of
 // k_many_solve), or nothing.  row_m becomes the new model's scan row, and the answer is true, when the model had at
-// least M::K records (cnt) and the solve gave a result; any other model keeps its row.
+// least M::K records (cnt) and the solve gave a result; any other model keeps its row.  org_m (nullable: null for
+// every family but the rigid one): the model's origin of kAssignOrigin<M> doubles, taken instead of row_m[org_off ..]
 template <class M>
 __device__ __forceinline__ bool assign_refit(const double *mom, double *row_m, unsigned long long cnt, int org_off,
-                                             const ModelConsts &mc, double *ws, SolveOut *so) {
+                                             const ModelConsts &mc, double *ws, SolveOut *so,
+                                             const double *org_m = nullptr) {
   if (cnt < (unsigned long long)M::K) return false;
   constexpr int NC = M::P > M::REC ? M::P : M::REC;
   double org[NC];
-  for (int j = 0; j < NC; j++) org[j] = j < (int)M::ND ? row_m[org_off + j] : 0.0;
+  const double *o = org_m ? org_m : row_m + org_off;
+  for (int j = 0; j < NC; j++) org[j] = j < kAssignOrigin<M> ? o[j] : 0.0;
   solve_small<M>(mom, org, mc, ws, so);
   if (!so->ok) return false;
   double p[M::P], row[M::SP];
@@ -456,6 +495,9 @@ struct AssignBufs {  // owned by the context (lsqr_ctx::assign), grown on demand
   DevBuf<uint32_t> d_lm_live;                         // their number
   DevBuf<LmState> d_lm_state;
   DevBuf<AssignLmOut> d_lm_out;
+  // the origin pre-pass of lsqr_refine_rigid (assign_rigid.h): a record index and an origin per model
+  DevBuf<unsigned long long> d_first;
+  DevBuf<double> d_org;
 };
 
 struct AssignJob {
@@ -492,7 +534,7 @@ inline void assign_fit_out(size_t rounds, unsigned long long okf, unsigned long 
   }
 }
 
-// THE round loop of the six ungrouped calls (an assign call: max_rounds == 0).  Round r: the pass -- labels L_r and,
+// THE round loop of the eight ungrouped calls (an assign call: max_rounds == 0).  Round r: the pass -- labels L_r and,
 // unless it is the last round allowed, whatever the refit needs of L_r --, the 8-byte changed-counter (with the counts:
 // one copy) to the host, one synchronisation, then the refit under L_r.  Returns after the stream has drained; the
 // outputs are written only then.  What differs from call to call is the family F (by value: a few references):
@@ -508,7 +550,7 @@ inline void assign_fit_out(size_t rounds, unsigned long long okf, unsigned long 
 //   n_params(J)          what a fitted model's record reports
 //   fit_more(J, m, h_cnt, fit)   what it adds to model m's record after a refit ran
 // AssignClosed<M> is lsqr_assign's and lsqr_refine's, AssignLm<M> (assign_lm.h) lsqr_refine_lm's, AssignDense<NR>
-// (assign_dense.h) the dense pair's.
+// (assign_dense.h) the dense pair's, AssignRigid<M> (assign_rigid.h) the rigid pair's.
 template <class F>
 int assign_rounds(AssignJob &J, F fam) {
   typedef typename F::Pin Pin;

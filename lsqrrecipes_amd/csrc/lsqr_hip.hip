@@ -48,6 +48,7 @@
 #include "assign.h"
 #include "assign_dense.h"
 #include "assign_lm.h"
+#include "assign_rigid.h"
 #include "assign_grouped.h"
 #include "assign_lm_grouped.h"
 #include "assign_dense_grouped.h"
@@ -3100,11 +3101,15 @@ int lsqr_estimate_host(const lsqr_model_cfg *cfg, const void *records, size_t co
 }
 int lsqr_assign_host(const lsqr_model_cfg *cfg, const double *params, size_t n_models, const void *record,
                      int32_t *label_out, double *residual_out) {
-  return host_assign_host<false>(cfg, params, n_models, record, label_out, residual_out);
+  return host_assign_host<ASSIGN_HOST_POINT>(cfg, params, n_models, record, label_out, residual_out);
 }
 int lsqr_assign_dense_host(const lsqr_model_cfg *cfg, const double *params, size_t n_models, const void *record,
                            int32_t *label_out, double *residual_out) {
-  return host_assign_host<true>(cfg, params, n_models, record, label_out, residual_out);
+  return host_assign_host<ASSIGN_HOST_DENSE>(cfg, params, n_models, record, label_out, residual_out);
+}
+int lsqr_assign_rigid_host(const lsqr_model_cfg *cfg, const double *params, size_t n_models, const void *record,
+                           int32_t *label_out, double *residual_out) {
+  return host_assign_host<ASSIGN_HOST_RIGID>(cfg, params, n_models, record, label_out, residual_out);
 }
 
 int lsqr_set_model(lsqr_ctx *c, const lsqr_model_cfg *cfg) {
@@ -4317,8 +4322,8 @@ int lsqr_ransac_grouped_sequential(lsqr_ctx *c, const int32_t *groups, size_t n_
   return LSQR_OK;
 }
 
-// ---- nearest-model assignment and refit (assign.h, assign_dense.h, assign_grouped.h, assign_dense_grouped.h) ---------
-// What the twelve entry points share.  The checks, in the contract's order: the context; the model gate (AssignGate:
+// ---- nearest-model assignment and refit (assign.h, assign_dense.h, assign_rigid.h, assign_grouped.h, ...) -----------
+// What the fourteen entry points share.  The checks, in the contract's order: the context; the model gate (AssignGate:
 // which models the entry point takes, and what it does with the geometric sphere, whose fit is iterative); count == 0
 // (n_models, or n_groups of the grouped calls) is LSQR_OK with every output untouched; more than 64 models; own(), the
 // entry point's own arguments; the context holds a model and records; their count.  Then run(tag), the run function
@@ -4330,15 +4335,18 @@ enum AssignGate {
   ASSIGN_GATE_ANY,     // the assignments: every model of assign_model_ok
   ASSIGN_GATE_CLOSED,  // the refits in closed form: not the geometric sphere
   ASSIGN_GATE_LM,      // lsqr_refine_lm, lsqr_refine_lm_grouped: the geometric sphere alone
-  ASSIGN_GATE_DENSE    // lsqr_assign_dense, lsqr_refine_dense and their grouped forms: the dense linear system alone
+  ASSIGN_GATE_DENSE,   // lsqr_assign_dense, lsqr_refine_dense and their grouped forms: the dense linear system alone
+  ASSIGN_GATE_RIGID    // lsqr_assign_rigid, lsqr_refine_rigid: absolute orientation, pivot and ray (no grouped form)
 };
 // the entry point that takes what the gate refuses, [grouped][gate]
-static const char *const kAssignTakes[2][4] = {
-    {"", "lsqr_refine_lm", "lsqr_refine", "lsqr_assign / lsqr_refine"},
-    {"", "lsqr_refine_lm_grouped", "lsqr_refine_grouped", "lsqr_assign_grouped / lsqr_refine_grouped"}};
+static const char *const kAssignTakes[2][5] = {
+    {"", "lsqr_refine_lm", "lsqr_refine", "lsqr_assign / lsqr_refine", "lsqr_assign / lsqr_refine"},
+    {"", "lsqr_refine_lm_grouped", "lsqr_refine_grouped", "lsqr_assign_grouped / lsqr_refine_grouped", ""}};
 // the models run(tag) is compiled for
 template <AssignGate G, class M>
-constexpr bool kAssignTakesModel = G == ASSIGN_GATE_DENSE ? (bool)M::IS_DENSE : AssignModel<M>::value;
+constexpr bool kAssignTakesModel = G == ASSIGN_GATE_DENSE   ? (bool)M::IS_DENSE
+                                   : G == ASSIGN_GATE_RIGID ? AssignRigidModel<M>::value
+                                                            : AssignModel<M>::value;
 
 template <AssignGate G, class Own, class Run>
 static int assign_frame(lsqr_ctx *c, const char *fn, bool grouped, size_t count, size_t max_models, const char *err,
@@ -4350,6 +4358,10 @@ static int assign_frame(lsqr_ctx *c, const char *fn, bool grouped, size_t count,
     if (c->cfg.model != LSQR_MODEL_DENSE)
       return fail(c, LSQR_ERR_INVALID, "%s: the dense linear system only (model %d); %s take "
                   "the plane, line, sphere and 2-D line", fn, c->cfg.model, takes);
+  } else if (G == ASSIGN_GATE_RIGID) {
+    if (!assign_rigid_model_ok(c->cfg))
+      return fail(c, LSQR_ERR_INVALID, "%s: absolute orientation, pivot calibration and ray intersection only (model "
+                  "%d); %s take the plane, line, sphere and 2-D line", fn, c->cfg.model, takes);
   } else if (G == ASSIGN_GATE_LM) {
     if (!(c->cfg.model == LSQR_MODEL_SPHERE && c->cfg.ls_type == LSQR_LS_GEOMETRIC))
       return fail(c, LSQR_ERR_INVALID, "%s: the sphere with LSQR_LS_GEOMETRIC only (model %d); %s takes the fits in "
@@ -4377,7 +4389,7 @@ static int assign_frame(lsqr_ctx *c, const char *fn, bool grouped, size_t count,
   return LSQR_OK;
 }
 
-// the six ungrouped calls: the round loop (assign_rounds) with the gate's family; args: the entry point's own
+// the eight ungrouped calls: the round loop (assign_rounds) with the gate's family; args: the entry point's own
 // pointers are all there
 template <AssignGate G>
 static int assign_call(lsqr_ctx *c, const char *fn, bool args, AssignJob &J) {
@@ -4398,14 +4410,15 @@ static int assign_call(lsqr_ctx *c, const char *fn, bool args, AssignJob &J) {
           return assign_rounds(J, AssignDense<M::NR>{*c->assign_dense, fast, dd});
         } else {
           if (!c->assign) c->assign.reset(new AssignBufs());
-          if constexpr (G != ASSIGN_GATE_LM) return assign_rounds(J, AssignClosed<M>{*c->assign});
+          if constexpr (G == ASSIGN_GATE_RIGID) return assign_rounds(J, AssignRigid<M>{{*c->assign}});
+          else if constexpr (G != ASSIGN_GATE_LM) return assign_rounds(J, AssignClosed<M>{*c->assign});
           else if constexpr (requires { M::NMOM_LM; }) return assign_rounds(J, AssignLm<M>{{*c->assign}});  // (the sphere)
           else return LSQR_ERR_INVALID;
         }
       });
 }
 
-// lsqr_assign and lsqr_assign_dense
+// lsqr_assign, lsqr_assign_dense and lsqr_assign_rigid
 template <AssignGate G>
 static int assign_only_call(lsqr_ctx *c, const char *fn, const double *params, size_t n_models, int on_device,
                             int32_t *labels_out, double *residuals_out, uint64_t *counts_out) {
@@ -4420,7 +4433,7 @@ static int assign_only_call(lsqr_ctx *c, const char *fn, const double *params, s
   return assign_call<G>(c, fn, params && labels_out, J);
 }
 
-// lsqr_refine, lsqr_refine_lm and lsqr_refine_dense
+// lsqr_refine, lsqr_refine_lm, lsqr_refine_dense and lsqr_refine_rigid
 template <AssignGate G>
 static int refine_call(lsqr_ctx *c, const char *fn, double *params_inout, size_t n_models, size_t max_rounds,
                        int on_device, int32_t *labels_out, uint64_t *counts_out, lsqr_fit_info *fits,
@@ -4474,6 +4487,19 @@ int lsqr_refine_dense(lsqr_ctx *c, double *params_inout, size_t n_models, size_t
                       int32_t *labels_out, uint64_t *counts_out, lsqr_fit_info *fits, int32_t *status_out,
                       size_t *rounds_out, int *converged_out) {
   return refine_call<ASSIGN_GATE_DENSE>(c, "lsqr_refine_dense", params_inout, n_models, max_rounds, on_device,
+                                        labels_out, counts_out, fits, status_out, rounds_out, converged_out);
+}
+
+int lsqr_assign_rigid(lsqr_ctx *c, const double *params, size_t n_models, int on_device, int32_t *labels_out,
+                      double *residuals_out, uint64_t *counts_out) {
+  return assign_only_call<ASSIGN_GATE_RIGID>(c, "lsqr_assign_rigid", params, n_models, on_device, labels_out,
+                                             residuals_out, counts_out);
+}
+
+int lsqr_refine_rigid(lsqr_ctx *c, double *params_inout, size_t n_models, size_t max_rounds, int on_device,
+                      int32_t *labels_out, uint64_t *counts_out, lsqr_fit_info *fits, int32_t *status_out,
+                      size_t *rounds_out, int *converged_out) {
+  return refine_call<ASSIGN_GATE_RIGID>(c, "lsqr_refine_rigid", params_inout, n_models, max_rounds, on_device,
                                         labels_out, counts_out, fits, status_out, rounds_out, converged_out);
 }
 

@@ -460,6 +460,37 @@ class RANSAC {
     return refineOnDevice(lsqr_refine_dense, cfg, models, data, maxRounds, labels, converged);
   }
 
+  // assignToModels / refineModels for AbsoluteOrientationParametersEstimator (weighted or not),
+  // PivotCalibrationEstimator and RayIntersectionParametersEstimator, which those two send to the host loop: ONE device
+  // call each (lsqr_assign_rigid / lsqr_refine_rigid).  The assignment is the device's -- the NEAREST agreeing model,
+  // ties to the smaller index --, the loop, the stop rules and what comes back are refineModels', and the refit of a
+  // model is its closed-form fit over its own records as leastSquaresEstimate computes it; a model with fewer than
+  // numForEstimate() records, or whose fit comes back empty (rays all parallel, frames all the same), keeps its
+  // parameters.  Any other estimator throws std::invalid_argument; more than 64 models, or a model vector of the wrong
+  // length, likewise.
+  static void assignToModelsRigid(const std::vector<std::vector<S> > &models,
+                                  ParametersEstimator<T, S> *paramEstimator, std::vector<T> &data,
+                                  std::vector<int> &labels) {
+    lsqr_model_cfg cfg;
+    rigidOnly(paramEstimator, cfg, "assignToModelsRigid");
+    labels.assign(data.size(), -1);
+    if (models.empty() || data.empty()) return;
+    bool converged = false;
+    std::vector<std::vector<S> > same(models);  // (no refit runs: maxRounds = 0 is the assignment)
+    refineOnDevice(lsqr_refine_rigid, cfg, same, data, 0, labels, &converged);
+  }
+
+  static size_t refineModelsRigid(std::vector<std::vector<S> > &models, ParametersEstimator<T, S> *paramEstimator,
+                                  std::vector<T> &data, size_t maxRounds, std::vector<int> &labels,
+                                  bool *converged = NULL) {
+    lsqr_model_cfg cfg;
+    rigidOnly(paramEstimator, cfg, "refineModelsRigid");
+    labels.assign(data.size(), -1);
+    if (converged) *converged = false;
+    if (models.empty() || data.empty()) return 0;
+    return refineOnDevice(lsqr_refine_rigid, cfg, models, data, maxRounds, labels, converged);
+  }
+
   // assignToModels with one model set per label on resident records (not in the reference), the follow-up of
   // computeGroupedSequential: `models` is what that call leaves in `parameters` (models[g]: the models of group g;
   // models.size() must be nGroups), `groups` and `data` are its own.  labels[i] is the model of models[groups[i]] that
@@ -934,7 +965,18 @@ class RANSAC {
       throw std::invalid_argument(std::string("lsqrRecipes::RANSAC: ") + fn + " takes the dense linear system only");
   }
 
-  // the device path of refineModels (lsqr_refine), refineModelsLM (lsqr_refine_lm) and refineModelsDense
+  // assignToModelsRigid / refineModelsRigid: the estimator's device model must be absolute orientation, pivot
+  // calibration or ray intersection
+  static void rigidOnly(ParametersEstimator<T, S> *paramEstimator, lsqr_model_cfg &cfg, const char *fn) {
+    if (!paramEstimator) throw std::invalid_argument("lsqrRecipes::RANSAC: null estimator");
+    if (!paramEstimator->deviceModel(cfg) ||
+        !(cfg.model == LSQR_MODEL_ABSOR || cfg.model == LSQR_MODEL_PIVOT || cfg.model == LSQR_MODEL_RAY))
+      throw std::invalid_argument(std::string("lsqrRecipes::RANSAC: ") + fn +
+                                  " takes absolute orientation, pivot calibration and ray intersection only");
+  }
+
+  // the device path of refineModels (lsqr_refine), refineModelsLM (lsqr_refine_lm), refineModelsDense and the rigid
+  // pair (lsqr_refine_rigid)
   typedef int (*RefineCall)(lsqr_ctx *, double *, size_t, size_t, int, int32_t *, uint64_t *, lsqr_fit_info *,
                             int32_t *, size_t *, int *);
   static size_t refineOnDevice(RefineCall call, lsqr_model_cfg &cfg, std::vector<std::vector<S> > &models,

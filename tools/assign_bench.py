@@ -72,7 +72,16 @@ on the device, and the timed calls ask for no labels.  grouped_round_ms, grouped
 host gather, upload, Context.refine_dense(max_rounds = R2) and the labels written back) as for --grouped above.  With
 --groups 1 also refine_round_ms / refine_call_ms, Context.refine_dense on the same rows: the per-round difference is
 the price of the (group, chunk) indirection, the whole-call difference the sort, the gather and the scatter.
-lane_share = rows / (workgroups x chunk)."""
+lane_share = rows / (workgroups x chunk).
+
+--model {absor,absor_w,pivot,ray}: Context.refine_rigid (lsqr_refine_rigid: absolute orientation, plain or with weighted
+pairs, pivot calibration, ray intersection) on --n records (default 2 M here) of 6 / 7 / 13 / 6 doubles: four planted
+models of 20 % each and 20 % clutter, shuffled; M = --models rows (default 4 and 64), every planted model M / 4 times
+with its translation / pivot point / point moved by up to +-0.3, inside the noise band.  Two kinds alternate in one
+process: refine_round_ms as above, and baseline_round_ms, the round the entry points allowed before: M x (lsqr_mask +
+lsqr_set_mask + lsqr_ls_fit).  entry_ms = t(max_rounds = R1) - t(max_rounds = 0) - rounds done at R1 x refine_round_ms:
+what a refine call costs once beside its rounds -- for absolute orientation the origin pre-pass (one more read of the
+records); for the pivot and the ray, which have none, the same difference as a control."""
 import argparse
 import json
 import os
@@ -150,16 +159,17 @@ def baseline_round(ctx, rows):
     return new
 
 
-def refine_rounds(ctx, rows, max_rounds, lm=False, nfev=None, dense=False):
-    """lsqr_refine (lm: lsqr_refine_lm, dense: lsqr_refine_dense) without labels_out -> rounds done; nfev (a list):
-    gets the models' lm_nfev"""
+def refine_rounds(ctx, rows, max_rounds, lm=False, nfev=None, dense=False, rigid=False):
+    """lsqr_refine (lm: lsqr_refine_lm, dense: lsqr_refine_dense, rigid: lsqr_refine_rigid) without labels_out -> rounds
+    done; nfev (a list): gets the models' lm_nfev"""
     import ctypes as C
     par = np.array(rows, dtype=np.float64, order="C")
     m = par.shape[0]
     fits = (L.FitInfo * m)()
     status = np.zeros(m, dtype=np.int32)
     rounds, conv = C.c_size_t(0), C.c_int(0)
-    call = ctx._lib.lsqr_refine_lm if lm else ctx._lib.lsqr_refine_dense if dense else ctx._lib.lsqr_refine
+    call = (ctx._lib.lsqr_refine_lm if lm else ctx._lib.lsqr_refine_dense if dense
+            else ctx._lib.lsqr_refine_rigid if rigid else ctx._lib.lsqr_refine)
     ctx._chk(call(ctx._h, L.ptr(par), m, max_rounds, 0, None, None, fits, L.ptr(status), C.byref(rounds),
                   C.byref(conv)))
     if nfev is not None:
@@ -306,6 +316,120 @@ def dense_main(a):
                        chunk=chunk, partial_bytes=int((a.n + chunk - 1) // chunk * m * ps * 8),
                        record_bytes_per_s=round(a.n * 8 * (dim + 1) / rnd, 0),
                        hbm_fraction=round(a.n * 8 * (dim + 1) / rnd / HBM_PEAK, 4))
+            lines.append(json.dumps(row))
+            print(lines[-1], flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+# --model: (the library's model, ls_type, delta, doubles per record, the chunk of the pass)
+RIGID = {"absor": (L.ABSOR, 0, 2.0, 6, 2048), "absor_w": (L.ABSOR, 2, 2.0, 7, 2048), "pivot": (L.PIVOT, 0, 1.0, 13, 1024),
+         "ray": (L.RAY, 0, 2.0, 6, 2048)}
+
+
+def _rotations(g, n):
+    """n random rotation matrices (n, 3, 3) from unit quaternions"""
+    q = g.normal(size=(n, 4))
+    q /= np.linalg.norm(q, axis=1, keepdims=True)
+    s, x, y, z = q.T
+    R = np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - s * z), 2 * (x * z + s * y)],
+                  [2 * (x * y + s * z), 1 - 2 * (x * x + z * z), 2 * (y * z - s * x)],
+                  [2 * (x * z - s * y), 2 * (y * z + s * x), 1 - 2 * (x * x + y * y)]])
+    return np.moveaxis(R, 2, 0), q
+
+
+def rigid_scene(n, kind, seed=20261025):
+    """-> records (shuffled), the four planted models as rows: 20 % of the records each, the rest clutter"""
+    g = np.random.default_rng([seed, sorted(RIGID).index(kind)])
+    owner = np.arange(n) % 5  # 4: clutter
+    jj = np.minimum(owner, 3)
+    off = owner == 4
+    if kind in ("absor", "absor_w"):
+        R, q = _rotations(g, 4)
+        t = g.uniform(-1000.0, 1000.0, (4, 3))
+        first = g.uniform(-100.0, 100.0, (n, 3))
+        second = np.einsum("nij,nj->ni", R[jj], first) + t[jj] + g.normal(0.0, 0.5, (n, 3))
+        second[off] = g.uniform(-1500.0, 1500.0, (int(off.sum()), 3))
+        cols = [first, second] + ([g.uniform(0.25, 4.0, (n, 1))] if kind == "absor_w" else [])
+        rec, rows = np.hstack(cols), np.hstack([q, t])
+    elif kind == "ray":
+        target = g.uniform(-1000.0, 1000.0, (4, 3))
+        p = g.uniform(-1000.0, 1000.0, (n, 3))
+        aim = target[jj] + g.normal(0.0, 0.3, (n, 3))
+        aim[off] = g.uniform(-1000.0, 1000.0, (int(off.sum()), 3))
+        d = aim - p
+        d /= np.linalg.norm(d, axis=1, keepdims=True)
+        rec, rows = np.hstack([p, d]), target
+    else:
+        tip = np.array([-17.0, 1.0, -157.0])
+        piv = g.uniform(-1000.0, 1000.0, (4, 3))
+        R, _ = _rotations(g, n)
+        t = piv[jj] - R @ tip + g.normal(0.0, 0.15, (n, 3))
+        t[off] += g.uniform(-400.0, 400.0, (int(off.sum()), 3))
+        rec = np.zeros((n, 13))
+        rec[:, :9], rec[:, 9:12] = R.reshape(n, 9), t
+        rows = np.hstack([np.tile(tip, (4, 1)), piv])
+    return np.ascontiguousarray(rec[g.permutation(n)]), rows
+
+
+def rigid_models(rows, m):
+    """m rows: every planted model m / 4 times, its last three slots moved by up to +-0.3 (inside the noise band)"""
+    k = m // 4
+    out = []
+    for r in rows:
+        for j in range(k):
+            s = 0.05 if k == 1 else -0.3 + 0.6 * j / (k - 1)
+            out.append(np.concatenate([r[:-3], r[-3:] + s]))
+    return np.array(out)
+
+
+def rigid_main(a):
+    r1, r2 = a.rounds
+    ms = lambda v: [round(1e3 * float(f(v)), 4) for f in (np.median, np.min, np.max)]
+    model, ls, delta, width, chunk = RIGID[a.model]
+    data, planted = rigid_scene(a.n, a.model)
+    lines = []
+    with Context(0) as ctx:
+        ctx.set_model(model, 3, delta, ls, aux=0.017453292519943295 if a.model == "ray" else 0.0).upload(data)
+        for m in a.models:
+            rows = rigid_models(planted, m)
+            t_0, t_lo, t_hi, t_asg, t_base, done = [], [], [], [], [], None
+            for rep in range(-1, a.reps):  # rep -1 warms every kind
+                t0 = time.perf_counter()
+                asg = ctx.assign_rigid(rows)
+                t1 = time.perf_counter()
+                refine_rounds(ctx, rows, 0, rigid=True)
+                t2 = time.perf_counter()
+                lo = refine_rounds(ctx, rows, r1, rigid=True)
+                t3 = time.perf_counter()
+                hi = refine_rounds(ctx, rows, r2, rigid=True)
+                t4 = time.perf_counter()
+                if rep < a.baseline_reps:
+                    baseline_round(ctx, rows)
+                t5 = time.perf_counter()
+                if hi <= lo:
+                    raise SystemExit("converged after %d rounds: nothing to time" % hi)
+                if done is not None and done != (lo, hi):
+                    raise SystemExit("the rounds done differ between repetitions")
+                done = (lo, hi)
+                if rep >= 0:
+                    t_asg.append(t1 - t0)
+                    t_0.append(t2 - t1)
+                    t_lo.append(t3 - t2)
+                    t_hi.append(t4 - t3)
+                    if rep < a.baseline_reps:
+                        t_base.append(t5 - t4)
+            per = [(h - l) / (done[1] - done[0]) for h, l in zip(t_hi, t_lo)]
+            rnd = float(np.median(per))
+            entry = [l - z - done[0] * rnd for l, z in zip(t_lo, t_0)]
+            row = dict(model=a.model, n=a.n, models=m, reps=a.reps, rounds_done=list(done),
+                       counts_assigned=int(a.n - asg["counts"][-1]), refine_round_ms=ms(per), assign_call_ms=ms(t_asg),
+                       call0_ms=ms(t_0), entry_ms=ms(entry), baseline_round_ms=ms(t_base), baseline_reps=len(t_base),
+                       ratio=round(float(np.median(t_base)) / rnd, 1), record_bytes=8 * width, chunk=chunk,
+                       workgroups=(a.n + chunk - 1) // chunk, record_bytes_per_s=round(a.n * 8 * width / rnd, 0),
+                       hbm_fraction=round(a.n * 8 * width / rnd / HBM_PEAK, 4))
             lines.append(json.dumps(row))
             print(lines[-1], flush=True)
     if a.out:
@@ -646,11 +770,17 @@ def main():
     ap.add_argument("--grouped", action="store_true", help="time Context.refine_grouped instead (see above)")
     ap.add_argument("--splits", nargs="+", default=["a", "b", "c"], choices=["a", "b", "c"])
     ap.add_argument("--loop-groups", type=int, default=200, help="--grouped: groups the per-group loop is timed on")
-    ap.add_argument("--model", choices=sorted(SYNTH) + ["dense"], default="plane")
+    ap.add_argument("--model", choices=sorted(SYNTH) + ["dense"] + sorted(RIGID), default="plane")
     ap.add_argument("--dim", type=int, default=3)
     ap.add_argument("--lm", action="store_true", help="time Context.refine_lm on the sphere scene instead (see above)")
     ap.add_argument("--groups", type=int, default=3000, help="--grouped --lm, --model dense --grouped: the groups of the scene")
     a = ap.parse_args()
+    if a.model in RIGID:
+        if a.lm or a.grouped:
+            raise SystemExit("--model %s goes with neither --lm nor --grouped" % a.model)
+        a.n = 2_000_000 if a.n == 10_000_000 else a.n
+        a.models = [4, 64] if a.models == [4, 16, 64] else a.models
+        return rigid_main(a)
     if a.lm and a.grouped:
         return grouped_lm_main(a)
     if a.lm:
