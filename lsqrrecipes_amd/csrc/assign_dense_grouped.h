@@ -29,6 +29,8 @@
 // chunk order, of its chunk blocks, each the sum in row order of its own rows.  No floating-point atomic.  A group's
 // results depend on its own rows, parameter rows and n_models alone.
 //
+// The host side is AssignGrpDense<NR>, a family of assign_grouped.h's round loop (assign_grouped_rounds).
+//
 // Host traffic per round: one synchronisation and one read of two words -- the groups still going and the flagged
 // pairs.  The sum, the solve and the flag list are enqueued BEFORE that read; all of them pass over the groups the
 // decision has just stopped, so a converged group's solve never runs.  The list itself crosses only when it is not
@@ -143,281 +145,148 @@ __global__ __launch_bounds__(64) void k_asd_grp_apply(const uint2 *__restrict__ 
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------
-struct AssignDenseGrpBufs {  // owned by the context, beside AssignGrpBufs, grown on demand
+struct AssignDenseGrpBufs {  // owned by the context (lsqr_ctx::assign_dense_grp), beside AssignGrpBufs, grown on demand
   DevBuf<double> d_mom, d_ddpart;
   DevBuf<SolveOut> d_out;
   DevBuf<int> d_flags;
   DevBuf<uint32_t> d_list;
   DevBuf<uint8_t> d_mask;
-  DevBuf<uint64_t> d_wbase;
 };
 
-// Both calls (J.refine says which).  Returns after the stream has drained; the outputs are written only then.  J.B: the
-// grouped calls' buffers; D: this file's; dense_fast, dense_dd: the context's options.
+// The dense system's family of the grouped round loop (assign_grouped.h: assign_grouped_rounds), both calls.  Its own
+// counter block is route; its second going word counts the flagged pairs; of h_pin it keeps their list.  Before the
+// round's synchronisation it enqueues the sum, the solve and the flag list; the refit solves the flagged pairs again
+// from their group's rows in double-double, then k_asd_grp_apply makes the refit decision.
 template <int NR>
-int assign_dense_grouped_run(AssignGrpJob &J, AssignDenseGrpBufs &D, int dense_fast, int dense_dd) {
-  typedef unsigned long long ull;
-  constexpr uint32_t CH = kAssignDenseChunk<NR>;
-  constexpr size_t lds_pass = sizeof(double) * CH * (NR + 1);
-  AssignGrpBufs &B = *J.B;
-  ManyBufs &P = *J.pack.buf;
-  hipStream_t stream = J.pack.stream;
-  const size_t NG = J.n_groups, MM = J.max_models, N = J.n, NRW = NG * MM;
-  const size_t W = (size_t)J.pack.W;  // n + 1
-  const int dim = (int)J.cfg.dim, ps = many_dense_ps(dim), ne = (dim + 1) * (dim + 2) / 2;
+struct AssignGrpDense {
+  static constexpr int UP = NR, SP = NR, BLOCKS = 1, GOING = 2;
+  static constexpr bool WBASE = true;
+  static constexpr uint32_t CH = kAssignDenseChunk<NR>;
+  static constexpr size_t lds_pass = sizeof(double) * CH * (NR + 1);
+  AssignGrpCore &C;       // the grouped calls' (lsqr_ctx::assign_grp)
+  AssignDenseGrpBufs &D;  // this file's
+  int dense_fast, dense_dd;  // the context's options
+  int dim, ps;               // n, and many_dense_ps(n): the doubles of a moment block
+  bool dd_ready = false;     // the double-double detour's buffers are there
 
-  std::vector<uint64_t> off;
-  const int st = grouped_pack(J.pack, J.data, J.stride, N, J.groups, J.on_device, off);
-  if (st != LSQR_OK) {
-    memcpy(J.err, J.pack.err, sizeof J.err);
-    return st;
-  }
-  const uint64_t NT = off[NG];
-  const uint32_t *perm = P.d_grp_vals[1];
-
-  // the layout: the (group, chunk) workgroups, each group's place in the partials and among the workgroups, the
-  // (group, model) pairs
-  std::vector<uint2> wgs, pairs;
-  std::vector<uint64_t> gbase(NG, 0), wbase(NG, 0);
-  uint64_t pblocks = 0;
-  bool dead_records = false;  // rows of a group that runs nothing
-  for (size_t g = 0; g < NG; g++) {
-    const uint64_t ng = off[g + 1] - off[g];
-    const size_t nm = J.n_models[g];
-    if (ng && !nm) dead_records = true;
-    if (!ng || !nm) continue;
-    const uint32_t chunks = (uint32_t)((ng + CH - 1) / CH);
-    gbase[g] = pblocks;
-    wbase[g] = wgs.size();
-    pblocks += (uint64_t)chunks * nm;
-    for (uint32_t q = 0; q < chunks; q++) wgs.push_back(make_uint2((uint32_t)g, q));
-    for (size_t m = 0; m < nm; m++) pairs.push_back(make_uint2((uint32_t)g, (uint32_t)m));
-  }
-  const size_t NW = wgs.size(), NP = pairs.size();
-  const bool moments = J.refine && J.max_rounds > 0 && NW > 0;
-
-  // device words: changed[NG], counts / used / ok / route [NRW] each, rounds[NG], going, flagged
-  const size_t c_counts = NG, c_used = c_counts + NRW, c_ok = c_used + NRW, c_route = c_ok + NRW,
-               c_rounds = c_route + NRW, c_going = c_rounds + NG, c_words = c_going + 2;
-  // pinned: what goes up, then what comes down
-  const size_t u_rows = 0, u_gbase = u_rows + sizeof(double) * NRW * NR, u_wbase = u_gbase + sizeof(uint64_t) * NG,
-               u_wgs = u_wbase + sizeof(uint64_t) * NG, u_pairs = u_wgs + sizeof(uint2) * NW,
-               u_nm = u_pairs + sizeof(uint2) * NP, u_state = u_nm + asg_grp_up8(sizeof(int32_t) * NG),
-               v_going = u_state + asg_grp_up8(sizeof(uint32_t) * NG), v_rows = v_going + 2 * sizeof(ull),
-               v_cnt = v_rows + sizeof(double) * NRW * NR, v_conv = v_cnt + sizeof(ull) * c_words,
-               v_list = v_conv + asg_grp_up8(sizeof(uint32_t) * NG), pin_bytes = v_list + sizeof(uint32_t) * NP;
-  MANYCHK(many_grow_pinned(B.h_pin, pin_bytes));  // (every earlier call ended in a synchronisation)
-  char *pin = B.h_pin.get();
-  double *h_up = (double *)(pin + u_rows);
-  int32_t *h_nm = (int32_t *)(pin + u_nm);
-  uint32_t *h_state = (uint32_t *)(pin + u_state);
-  const ull *h_going = (const ull *)(pin + v_going);  // [0]: the groups still going; [1]: the flagged pairs
-  const double *h_rows = (const double *)(pin + v_rows);
-  const ull *h_cnt = (const ull *)(pin + v_cnt);
-  const uint32_t *h_conv = (const uint32_t *)(pin + v_conv);
-  const uint32_t *h_list = (const uint32_t *)(pin + v_list);
-  for (size_t g = 0; g < NG; g++) {
-    const size_t nm = J.n_models[g];
-    h_nm[g] = (int32_t)nm;
-    h_state[g] = (off[g + 1] > off[g] && nm) ? 0u : 1u;
-    for (size_t m = 0; m < MM; m++)  // the zero-padded scan rows (AssignDense::rows_up)
-      for (size_t j = 0; j < (size_t)NR; j++)
-        h_up[(g * MM + m) * NR + j] = m < nm && j < (size_t)dim ? J.params[(g * MM + m) * dim + j] : 0.0;
-  }
-  memcpy(pin + u_gbase, gbase.data(), sizeof(uint64_t) * NG);
-  memcpy(pin + u_wbase, wbase.data(), sizeof(uint64_t) * NG);
-  if (NW) memcpy(pin + u_wgs, wgs.data(), sizeof(uint2) * NW);
-  if (NP) memcpy(pin + u_pairs, pairs.data(), sizeof(uint2) * NP);
-
-  MANYCHK(many_grow(B.d_nm, NG));
-  MANYCHK(many_grow(B.d_gbase, NG));
-  MANYCHK(many_grow(D.d_wbase, NG));
-  MANYCHK(many_grow(B.d_state, 2 * NG));  // state, converged
-  MANYCHK(many_grow(B.d_cnt, c_words));
-  MANYCHK(many_grow(B.d_rows, std::max<size_t>(NRW * NR, 1)));
-  MANYCHK(many_grow(B.d_wgs, std::max<size_t>(NW, 1)));
-  MANYCHK(many_grow(B.d_pairs, std::max<size_t>(NP, 1)));
-  MANYCHK(many_grow(B.d_labels[0], std::max<size_t>(NT, 1)));
-  if (J.refine) MANYCHK(many_grow(B.d_labels[1], std::max<size_t>(NT, 1)));
-  if (J.residuals_out) MANYCHK(many_grow(B.d_res, std::max<size_t>(NT, 1)));
-  if (moments) {
-    MANYCHK(many_grow(B.d_partials, (size_t)pblocks * ps));
-    MANYCHK(many_grow(B.d_presence, NW));
-    MANYCHK(many_grow(D.d_mom, NP * (size_t)ps));
-    MANYCHK(many_grow(D.d_out, NP));
-    if (dense_dd) {
-      MANYCHK(many_grow(D.d_flags, NP));
-      MANYCHK(many_grow(D.d_list, NP));
+  AssignGrpCore &core() { return C; }
+  static uint32_t chunks_of(uint64_t n) { return (uint32_t)((n + CH - 1) / CH); }
+  static size_t pin_own(const AssignGrpLayout &L) { return sizeof(uint32_t) * L.NP; }
+  int reserve(AssignGrpJob &J, bool moments) {
+    if (moments) {
+      const size_t NP = J.L.NP;
+      MANYCHK(many_grow(C.d_partials, (size_t)J.L.pblocks * ps));
+      MANYCHK(many_grow(C.d_presence, J.L.NW));
+      MANYCHK(many_grow(D.d_mom, NP * (size_t)ps));
+      MANYCHK(many_grow(D.d_out, NP));
+      if (dense_dd) {
+        MANYCHK(many_grow(D.d_flags, NP));
+        MANYCHK(many_grow(D.d_list, NP));
+      }
+      (void)hipFuncSetAttribute((const void *)k_asd_grp_solve, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)many_dense_lds(64));
+      (void)hipFuncSetAttribute((const void *)(k_asd_grp_pass<NR, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)lds_pass);
     }
-    (void)hipFuncSetAttribute((const void *)k_asd_grp_solve, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)many_dense_lds(64));
-    (void)hipFuncSetAttribute((const void *)(k_asd_grp_pass<NR, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+    (void)hipFuncSetAttribute((const void *)(k_asd_grp_pass<NR, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)lds_pass);
+    return LSQR_OK;
   }
-  (void)hipFuncSetAttribute((const void *)(k_asd_grp_pass<NR, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lds_pass);
-  if (!J.on_device && J.labels_out) MANYCHK(many_grow(B.d_lab_out, N));
-  if (!J.on_device && J.residuals_out) MANYCHK(many_grow(B.d_res_out, N));
-  ull *d_changed = B.d_cnt, *d_counts = B.d_cnt + c_counts, *d_used = B.d_cnt + c_used, *d_ok = B.d_cnt + c_ok,
-      *d_route = B.d_cnt + c_route, *d_rounds = B.d_cnt + c_rounds, *d_going = B.d_cnt + c_going;
-  uint32_t *d_state = B.d_state, *d_conv = B.d_state + NG;
-
-  MANYCHK(hipMemcpyAsync(B.d_nm, h_nm, sizeof(int32_t) * NG, hipMemcpyHostToDevice, stream));
-  MANYCHK(hipMemcpyAsync(B.d_gbase, pin + u_gbase, sizeof(uint64_t) * NG, hipMemcpyHostToDevice, stream));
-  MANYCHK(hipMemcpyAsync(D.d_wbase, pin + u_wbase, sizeof(uint64_t) * NG, hipMemcpyHostToDevice, stream));
-  MANYCHK(hipMemcpyAsync(d_state, h_state, sizeof(uint32_t) * NG, hipMemcpyHostToDevice, stream));
-  MANYCHK(hipMemsetAsync(d_conv, 0, sizeof(uint32_t) * NG, stream));
-  MANYCHK(hipMemsetAsync(B.d_cnt, 0, sizeof(ull) * c_words, stream));
-  if (NW) {
-    MANYCHK(hipMemcpyAsync(B.d_rows, h_up, sizeof(double) * NRW * NR, hipMemcpyHostToDevice, stream));
-    MANYCHK(hipMemcpyAsync(B.d_wgs, pin + u_wgs, sizeof(uint2) * NW, hipMemcpyHostToDevice, stream));
-    MANYCHK(hipMemcpyAsync(B.d_pairs, pin + u_pairs, sizeof(uint2) * NP, hipMemcpyHostToDevice, stream));
+  int rows_up(AssignGrpJob &J, double *h_rows) {  // the zero-padded scan rows (AssignDense::rows_up)
+    const size_t MM = J.max_models, n = (size_t)dim;
+    for (size_t g = 0; g < J.n_groups; g++)
+      for (size_t m = 0; m < MM; m++)
+        for (size_t j = 0; j < (size_t)NR; j++)
+          h_rows[(g * MM + m) * NR + j] = m < J.n_models[g] && j < n ? J.params[(g * MM + m) * n + j] : 0.0;
+    MANYCHK(hipMemcpyAsync(C.d_rows, h_rows, sizeof(double) * J.L.NE * NR, hipMemcpyHostToDevice, J.pack.stream));
+    return LSQR_OK;
   }
-  if (dead_records && NT) {  // no pass writes them
-    MANYCHK(hipMemsetAsync(B.d_labels[0], 0xFF, sizeof(int32_t) * NT, stream));
-    if (J.refine) MANYCHK(hipMemsetAsync(B.d_labels[1], 0xFF, sizeof(int32_t) * NT, stream));
-    if (J.residuals_out) {
-      hipLaunchKernelGGL(k_asg_grp_fill, dim3(grp_grid(NT)), dim3(kBlock), 0, stream, B.d_res, (uint64_t)NT,
-                         __builtin_inf());
-      MANYCHK(hipGetLastError());
-    }
-  }
-
-  const AsgGrpTab T{P.d_grp_off, B.d_gbase, B.d_nm, d_state};
-  int cur = 0;
-  size_t r = 0;
-  bool dd_ready = false;
-  while (NW) {
-    const bool last = r == J.max_rounds;
-    int32_t *lab = B.d_labels[cur];
-    double *res = J.residuals_out ? B.d_res.get() : nullptr;
-    const int32_t *old = r > 0 ? B.d_labels[cur ^ 1].get() : nullptr;
+  int prepare(AssignGrpJob &) { return LSQR_OK; }
+  int pass(AssignGrpJob &J, bool last, int32_t *lab, double *res, const int32_t *old) {
+    const AssignGrpLayout &L = J.L;
+    const size_t W = (size_t)J.pack.W;  // n + 1
+    const int MM = (int)J.max_models;
     if (last)
-      hipLaunchKernelGGL((k_asd_grp_pass<NR, false>), dim3((unsigned)NW), dim3(kAsdBlock), lds_pass, stream, P.d_data, W,
-                         B.d_wgs, T, B.d_rows, (int)MM, dim, J.mc, lab, res, old, d_changed, d_counts, nullptr, ps,
-                         nullptr);
+      hipLaunchKernelGGL((k_asd_grp_pass<NR, false>), dim3((unsigned)L.NW), dim3(kAsdBlock), lds_pass, J.pack.stream,
+                         J.pack.buf->d_data, W, C.d_wgs, L.T, C.d_rows, MM, dim, J.mc, lab, res, old, L.d(0),
+                         L.d(L.c_counts), nullptr, ps, nullptr);
     else
-      hipLaunchKernelGGL((k_asd_grp_pass<NR, true>), dim3((unsigned)NW), dim3(kAsdBlock), lds_pass, stream, P.d_data, W,
-                         B.d_wgs, T, B.d_rows, (int)MM, dim, J.mc, lab, res, old, d_changed, d_counts, B.d_partials, ps,
-                         B.d_presence);
+      hipLaunchKernelGGL((k_asd_grp_pass<NR, true>), dim3((unsigned)L.NW), dim3(kAsdBlock), lds_pass, J.pack.stream,
+                         J.pack.buf->d_data, W, C.d_wgs, L.T, C.d_rows, MM, dim, J.mc, lab, res, old, L.d(0),
+                         L.d(L.c_counts), C.d_partials, ps, C.d_presence);
     MANYCHK(hipGetLastError());
-    if (last) break;  // every group still going stops here: nothing to read
-    MANYCHK(hipMemsetAsync(d_going, 0, 2 * sizeof(ull), stream));
-    hipLaunchKernelGGL(k_asg_grp_decide, dim3(grp_grid(NG)), dim3(kBlock), 0, stream, (uint32_t)NG, (ull)r, 0,
-                       d_changed, d_state, d_rounds, d_conv, d_going);
-    MANYCHK(hipGetLastError());
-    // the sum and the solve of the groups that go on, under way before the host knows which those are
+    return LSQR_OK;
+  }
+  // the sum and the solve of the groups that go on, under way before the host knows which those are
+  int before_sync(AssignGrpJob &J) {
+    const AssignGrpLayout &L = J.L;
+    hipStream_t stream = J.pack.stream;
+    const size_t NP = L.NP;
+    const int ne = (dim + 1) * (dim + 2) / 2;
     hipLaunchKernelGGL(k_asd_grp_sum, dim3((unsigned)NP, (ne + 1 + kAsdBlock - 1) / kAsdBlock), dim3(kAsdBlock), 0,
-                       stream, B.d_pairs, T, D.d_wbase, CH, B.d_partials, B.d_presence, (int)MM, dim, ps, d_counts,
-                       D.d_mom);
+                       stream, C.d_pairs, L.T, C.d_wbase, CH, C.d_partials, C.d_presence, (int)J.max_models, dim, ps,
+                       L.d(L.c_counts), D.d_mom);
     MANYCHK(hipGetLastError());
     if (dense_dd) MANYCHK(hipMemsetAsync(D.d_flags, 0, sizeof(int) * NP, stream));
-    hipLaunchKernelGGL(k_asd_grp_solve, dim3((unsigned)NP), dim3(256), many_dense_lds(dim), stream, B.d_pairs, d_state,
-                       D.d_mom, ps, dim, dense_fast, D.d_out, dense_dd ? D.d_flags.get() : (int *)nullptr);
+    hipLaunchKernelGGL(k_asd_grp_solve, dim3((unsigned)NP), dim3(256), many_dense_lds(dim), stream, C.d_pairs,
+                       L.T.state, D.d_mom, ps, dim, dense_fast, D.d_out, dense_dd ? D.d_flags.get() : (int *)nullptr);
     MANYCHK(hipGetLastError());
     if (dense_dd) {
       hipLaunchKernelGGL(k_asd_grp_flagged, dim3(grp_grid(NP)), dim3(kAsdBlock), 0, stream, D.d_flags, (uint32_t)NP,
-                         D.d_list, d_going + 1);
+                         D.d_list, L.d(L.c_going) + 1);
       MANYCHK(hipGetLastError());
     }
-    MANYCHK(hipMemcpyAsync(pin + v_going, d_going, 2 * sizeof(ull), hipMemcpyDeviceToHost, stream));
-    MANYCHK(hipStreamSynchronize(stream));  // the two words of the round
-    if (h_going[0] == 0) break;
-    if (h_going[1]) {  // the ill-conditioned pairs again from their group's rows, in double-double
-      const size_t nf = (size_t)h_going[1];
-      MANYCHK(hipMemcpyAsync(pin + v_list, D.d_list, sizeof(uint32_t) * nf, hipMemcpyDeviceToHost, stream));
+    return LSQR_OK;
+  }
+  int refit(AssignGrpJob &J, const int32_t *lab) {
+    const AssignGrpLayout &L = J.L;
+    hipStream_t stream = J.pack.stream;
+    const size_t W = (size_t)J.pack.W;
+    // the ill-conditioned pairs again from their group's rows, in double-double
+    if (const size_t nf = ((const unsigned long long *)L.h(L.v_going))[1]) {
+      const uint32_t *h_list = (const uint32_t *)L.h(L.v_own);
+      MANYCHK(hipMemcpyAsync(L.h(L.v_own), D.d_list, sizeof(uint32_t) * nf, hipMemcpyDeviceToHost, stream));
       MANYCHK(hipStreamSynchronize(stream));
       if (!dd_ready) {
         MANYCHK(many_grow(D.d_ddpart, (size_t)2 * kDdNe * kDdBlocks));
-        MANYCHK(many_grow(D.d_mask, (size_t)NT));
+        MANYCHK(many_grow(D.d_mask, (size_t)L.off[L.NG]));
         (void)hipFuncSetAttribute((const void *)k_dense_dd_solve, hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)dense_dd_lds(64));
         dd_ready = true;
       }
       for (size_t f = 0; f < nf; f++) {
         const uint32_t p = h_list[f];
-        if (p >= NP) {
+        if (p >= L.NP) {
           snprintf(J.err, sizeof J.err, "flagged pair out of range");
           return LSQR_ERR_HIP;
         }
-        const uint32_t g = pairs[p].x, m = pairs[p].y;
-        const uint32_t ng = (uint32_t)(off[g + 1] - off[g]);
+        const uint32_t g = L.pairs[p].x, m = L.pairs[p].y;
+        const uint32_t ng = (uint32_t)(L.off[g + 1] - L.off[g]);
         const int nb = (int)std::min<size_t>(kDdBlocks, ((size_t)ng + 31) / 32);
-        uint8_t *mask = D.d_mask.get() + off[g];
+        uint8_t *mask = D.d_mask.get() + L.off[g];
         hipLaunchKernelGGL(k_asd_label_mask, dim3(std::min<uint32_t>((ng + 255) / 256, 4096u)), dim3(256), 0, stream,
-                           lab + off[g], ng, (int32_t)m, mask);
+                           lab + L.off[g], ng, (int32_t)m, mask);
         MANYCHK(hipGetLastError());
-        hipLaunchKernelGGL((k_gram_dd_dense<32>), dim3(nb), dim3(256), 0, stream, P.d_data.get() + off[g] * W, W,
-                           (size_t)0, (size_t)ng, dim, mask, D.d_flags + p, D.d_ddpart);
+        hipLaunchKernelGGL((k_gram_dd_dense<32>), dim3(nb), dim3(256), 0, stream,
+                           J.pack.buf->d_data.get() + L.off[g] * W, W, (size_t)0, (size_t)ng, dim, mask, D.d_flags + p,
+                           D.d_ddpart);
         MANYCHK(hipGetLastError());
         hipLaunchKernelGGL(k_dense_dd_solve, dim3(1), dim3(256), dense_dd_lds(dim), stream, D.d_ddpart, nb, dim,
                            D.d_mom + (size_t)p * ps, D.d_flags + p, D.d_out + p);
         MANYCHK(hipGetLastError());
       }
     }
-    hipLaunchKernelGGL(k_asd_grp_apply, dim3((unsigned)NP), dim3(64), 0, stream, B.d_pairs, d_state, D.d_out, dim, NR,
-                       (int)MM, B.d_rows, d_counts, d_used, d_ok, d_route);
+    hipLaunchKernelGGL(k_asd_grp_apply, dim3((unsigned)L.NP), dim3(64), 0, stream, C.d_pairs, L.T.state, D.d_out, dim,
+                       NR, (int)J.max_models, C.d_rows, L.d(L.c_counts), L.d(L.c_used), L.d(L.c_ok), L.d(L.c_own));
     MANYCHK(hipGetLastError());
-    r++;
-    cur ^= 1;
+    return LSQR_OK;
   }
-  if (NW && r == J.max_rounds) {  // the last pass allowed: its decision needs no answer
-    hipLaunchKernelGGL(k_asg_grp_decide, dim3(grp_grid(NG)), dim3(kBlock), 0, stream, (uint32_t)NG, (ull)r, 1,
-                       d_changed, d_state, d_rounds, d_conv, d_going);
-    MANYCHK(hipGetLastError());
+  int results(AssignGrpJob &) { return LSQR_OK; }
+  int32_t n_params(const AssignGrpJob &) const { return dim; }
+  void fit_more(AssignGrpJob &J, size_t e, const unsigned long long *h_cnt, lsqr_fit_info &fit) {
+    fit.reserved = (int32_t)h_cnt[J.L.c_own + e];  // the route
   }
-
-  // results: the labels of the last pass in upload order, then the rows and the per-group words
-  if (J.labels_out) {
-    int32_t *d_lab = J.on_device ? J.labels_out : B.d_lab_out.get();
-    hipLaunchKernelGGL(k_grp_scatter_labels, dim3(grp_grid(N)), dim3(kBlock), 0, stream, perm, (uint32_t)N,
-                       (uint32_t)NT, B.d_labels[cur].get(), d_lab);
-    MANYCHK(hipGetLastError());
-    if (!J.on_device)
-      MANYCHK(hipMemcpyAsync(J.labels_out, d_lab, sizeof(int32_t) * N, hipMemcpyDeviceToHost, stream));
-  }
-  if (J.residuals_out) {
-    double *d_r = J.on_device ? J.residuals_out : B.d_res_out.get();
-    hipLaunchKernelGGL(k_grp_scatter_f64, dim3(grp_grid(N)), dim3(kBlock), 0, stream, perm, (uint32_t)N, (uint32_t)NT,
-                       B.d_res.get(), __builtin_inf(), d_r);
-    MANYCHK(hipGetLastError());
-    if (!J.on_device)
-      MANYCHK(hipMemcpyAsync(J.residuals_out, d_r, sizeof(double) * N, hipMemcpyDeviceToHost, stream));
-  }
-  if (r > 0) MANYCHK(hipMemcpyAsync(pin + v_rows, B.d_rows, sizeof(double) * NRW * NR, hipMemcpyDeviceToHost, stream));
-  MANYCHK(hipMemcpyAsync(pin + v_cnt, B.d_cnt, sizeof(ull) * c_words, hipMemcpyDeviceToHost, stream));
-  MANYCHK(hipMemcpyAsync(pin + v_conv, d_conv, sizeof(uint32_t) * NG, hipMemcpyDeviceToHost, stream));
-  MANYCHK(hipStreamSynchronize(stream));
-
-  for (size_t g = 0; g < NG; g++) {
-    const size_t nm = J.n_models[g];
-    const uint64_t ng = off[g + 1] - off[g];
-    const size_t rg = (size_t)h_cnt[c_rounds + g];
-    if (rg > 0)
-      for (size_t m = 0; m < nm; m++)
-        for (int j = 0; j < dim; j++) J.params[(g * MM + m) * dim + j] = h_rows[(g * MM + m) * NR + j];
-    if (J.counts_out) {
-      uint64_t sum = 0, *c = J.counts_out + g * (MM + 1);
-      for (size_t m = 0; m < MM; m++) sum += (c[m] = m < nm ? h_cnt[c_counts + g * MM + m] : 0);
-      c[MM] = ng - sum;
-    }
-    if (!J.refine) continue;
-    J.rounds_out[g] = rg;
-    J.converged_out[g] = (int32_t)h_conv[g];
-    for (size_t m = 0; m < MM; m++) {
-      const size_t e = g * MM + m;
-      if (m < nm) {
-        assign_fit_out(rg, h_cnt[c_ok + e], h_cnt[c_used + e], (int32_t)dim, &J.status_out[e], &J.fits[e]);
-        if (rg > 0) J.fits[e].reserved = (int32_t)h_cnt[c_route + e];
-      } else {
-        J.status_out[e] = LSQR_ERR_STATE;  // model not there
-        memset(&J.fits[e], 0, sizeof(lsqr_fit_info));
-      }
-    }
-  }
-  if (J.offsets_out) memcpy(J.offsets_out, off.data(), sizeof(uint64_t) * (NG + 1));
-  return LSQR_OK;
-}
+};
 #endif  // __HIPCC__
 
 #undef MANYCHK

@@ -34,9 +34,8 @@
 // the records in no group, get label -1 and residual +infinity: the packed buffers are filled with those first when such
 // a group has records, and the scatter writes them for the records past the grouped total.
 //
-// lsqr_refine_lm_grouped (assign_lm_grouped.h, the geometric sphere) runs this file's loop, assign_grouped_run<M, true>:
-// the pass also stores every workgroup's presence word, the solve writes into a side array of start rows, and the
-// refit is a grouped LM stage.
+// All five grouped calls run this file's round loop, assign_grouped_rounds<F> (below, with what a family F supplies), as
+// the ungrouped calls run assign_rounds (assign.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -163,20 +162,63 @@ __global__ __launch_bounds__(kBlock) void k_asg_grp_fill(double *__restrict__ p,
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------
-struct AssignGrpBufs {  // owned by the context, grown on demand (the sort and the packed copy are ManyBufs')
-  DevBuf<double> d_par, d_rows, d_partials, d_res, d_res_out;
+// what every family of the grouped round loop holds: the scan rows, the chunk partials and the presence word of every
+// (group, chunk), the packed labels of this round and of the one before, the residuals, the per-group tables, the
+// counter words, the outputs in upload order, and the pinned staging (the sort and the packed copy are ManyBufs')
+struct AssignGrpCore {
+  DevBuf<double> d_rows, d_partials, d_res, d_res_out;
   DevBuf<int32_t> d_labels[2], d_lab_out, d_nm;
-  DevBuf<unsigned long long> d_cnt;
-  DevBuf<uint64_t> d_gbase;
-  DevBuf<uint32_t> d_state;
+  DevBuf<unsigned long long> d_cnt, d_presence;
+  DevBuf<uint64_t> d_gbase, d_wbase;
+  DevBuf<uint32_t> d_state;  // state, converged
   DevBuf<uint2> d_wgs, d_pairs;
-  PinBuf<char> h_pin;
+  PinBuf<char> h_pin;  // AssignGrpLayout's u_ and v_ areas
+};
+
+struct AssignGrpBufs {  // owned by the context (lsqr_ctx::assign_grp), grown on demand
+  AssignGrpCore core;
+  DevBuf<double> d_par;
   // the LM stage of lsqr_refine_lm_grouped (assign_lm_grouped.h)
   DevBuf<double> d_start, d_lm_partials;
-  DevBuf<unsigned long long> d_presence, d_lm_mask;  // one word per (group, chunk); per group, the models whose LM goes on
-  DevBuf<uint32_t> d_lm_live;                         // their number over all groups
-  DevBuf<LmState> d_lm_state;                         // per (group, model)
+  DevBuf<unsigned long long> d_lm_mask;  // per group, the models whose LM goes on
+  DevBuf<uint32_t> d_lm_live;            // their number over all groups
+  DevBuf<LmState> d_lm_state;            // per (group, model)
   DevBuf<AssignLmOut> d_lm_out;
+};
+
+// One call's layout: its workgroups and pairs, the blocks of counter words in d_cnt and the areas of h_pin.
+// assign_grouped_rounds builds it before the first hook runs; the families read it.
+struct AssignGrpLayout {
+  typedef unsigned long long ull;
+  size_t NG = 0, NE = 0;               // groups, and groups * max_models: the (group, model) entries
+  std::vector<uint64_t> off;           // grouped_pack's offsets, NG + 1
+  std::vector<uint2> wgs, pairs;       // the (group, chunk) workgroups; the (group, model) pairs whose row is there
+  std::vector<uint64_t> gbase, wbase;  // per group: its first (chunk, model) block of the partials, its first workgroup
+  size_t NW = 0, NP = 0;               // workgroups, pairs
+  uint64_t pblocks = 0;                // (chunk, model) blocks of all groups
+  // words of d_cnt: changed[NG], counts / used / ok [NE] each, the family's blocks of NE, rounds[NG], the going words
+  size_t c_counts = 0, c_used = 0, c_ok = 0, c_own = 0, c_rounds = 0, c_going = 0, c_words = 0;
+  // bytes of h_pin: what goes up, then what comes down, then the family's own
+  size_t u_rows = 0, u_gbase = 0, u_wbase = 0, u_wgs = 0, u_pairs = 0, u_nm = 0, u_state = 0, v_going = 0, v_rows = 0,
+         v_cnt = 0, v_conv = 0, v_own = 0, bytes = 0;
+  AsgGrpTab T{};
+  ull *d_cnt = nullptr;  // d(c_counts): the counts on the device, and so on
+  char *pin = nullptr;   // h(v_going): the round's going words on the host; h(v_own): the family's own bytes
+  ull *d(size_t c) const { return d_cnt + c; }
+  char *h(size_t o) const { return pin + o; }
+
+  // up, sp: doubles of an uploaded row and of a scan row; blocks, going, own: the family's counter blocks, going words
+  // and pinned bytes
+  void place(size_t up, size_t sp, size_t blocks, size_t going, size_t own) {
+    const auto up8 = [](size_t b) { return (b + 7) & ~(size_t)7; };
+    c_counts = NG, c_used = c_counts + NE, c_ok = c_used + NE, c_own = c_ok + NE, c_rounds = c_own + blocks * NE,
+    c_going = c_rounds + NG, c_words = c_going + going;
+    u_rows = 0, u_gbase = u_rows + sizeof(double) * NE * up, u_wbase = u_gbase + sizeof(uint64_t) * NG,
+    u_wgs = u_wbase + sizeof(uint64_t) * NG, u_pairs = u_wgs + sizeof(uint2) * NW, u_nm = u_pairs + sizeof(uint2) * NP,
+    u_state = u_nm + up8(sizeof(int32_t) * NG), v_going = u_state + up8(sizeof(uint32_t) * NG),
+    v_rows = v_going + sizeof(ull) * going, v_cnt = v_rows + sizeof(double) * NE * sp,
+    v_conv = v_cnt + sizeof(ull) * c_words, v_own = v_conv + up8(sizeof(uint32_t) * NG), bytes = v_own + own;
+  }
 };
 
 struct AssignGrpJob {
@@ -185,13 +227,13 @@ struct AssignGrpJob {
   ModelConsts mc{};
   const double *data = nullptr;  // the context's records: n of them, `stride` doubles apart
   size_t stride = 0, n = 0;
-  AssignGrpBufs *B = nullptr;
+  AssignGrpLayout L;  // (assign_grouped_rounds fills it)
   // the call
   const int32_t *groups = nullptr;
   size_t n_groups = 0, max_models = 0, max_rounds = 0;
   int on_device = 0;
   bool refine = false;
-  double *params = nullptr;  // host, n_groups * max_models rows of M::P: read, and written where a refit ran
+  double *params = nullptr;  // host, n_groups * max_models rows of parameters: read, and written where a refit ran
   const size_t *n_models = nullptr;
   int32_t *labels_out = nullptr;
   double *residuals_out = nullptr;
@@ -203,42 +245,40 @@ struct AssignGrpJob {
   char err[256] = {0};
 };
 
-inline size_t asg_grp_up8(size_t b) { return (b + 7) & ~(size_t)7; }
-
-// what the LM stage of a round needs of the call's layout
-struct AsgGrpLmView {
-  AsgGrpTab T;
-  const uint2 *wgs, *pairs;
-  size_t n_wgs, n_pairs, n_groups, max_models;
-  uint64_t pblocks;    // (chunk, model) blocks of all groups
-  const double *data;  // the packed records
-  size_t stride;
-  double *rows;
-  unsigned long long *counts, *used, *ok;
-  uint32_t *h_live;  // pinned: the live counter's copy
-};
-
-// the LM stage of lsqr_refine_lm_grouped's round (assign_lm_grouped.h): its buffers, and the refit of every model of
-// every group still going from the moments and the presence words the pass has just left, under the packed labels
-// `lab`; it leaves the new rows in B.d_rows
-template <class M> int assign_lm_grp_reserve(AssignGrpJob &J, const AsgGrpLmView &V);
-template <class M> int assign_lm_grp_run(AssignGrpJob &J, const AsgGrpLmView &V, const int32_t *lab);
-
-// All three calls.  Returns after the stream has drained; the outputs are written only then.
-// LM (lsqr_refine_lm_grouped, the geometric sphere): the same loop; the refit is assign_lm_grp_run, and the fits carry
-// its record.
-template <class M, bool LM = false>
-int assign_grouped_run(AssignGrpJob &J) {
+// THE round loop of the five grouped calls (an assign call: max_rounds == 0).  Round r: the pass of every group still
+// going -- labels L_r and, unless it is the last round allowed, whatever the refit needs of L_r --, k_asg_grp_decide,
+// the going words to the host, one synchronisation, then the refit under L_r of the groups that go on.  The device
+// decides per group; the host only learns whether any group is left.  Returns after the stream has drained; the outputs
+// are written only then.  What differs from call to call is the family F (by value: a few references):
+//   F::UP, F::SP         the doubles of an uploaded row in h_pin, and of a scan row in d_rows
+//   F::BLOCKS, F::GOING  its own blocks of NE counter words after ok (L.c_own), and the words the host reads per round
+//   F::WBASE             it wants L.wbase on the device (d_wbase)
+//   core()               the AssignGrpCore among its buffers
+//   chunks_of(n)         its chunks of a group of n records
+//   pin_own(L)           the bytes of h_pin it keeps for itself (L.v_own)
+//   reserve(J, moments)  grows its own buffers (and d_partials and d_presence, whose use is its own)
+//   rows_up(J, h_rows)   enqueues the caller's parameters' way to the device, staged through h_rows
+//   prepare(J)           after the tables are up: enqueues what is left to make d_rows of the upload
+//   pass(J, last, lab, res, old)   enqueues the pass of this round
+//   before_sync(J)       enqueues what has to be under way before the round's synchronisation
+//   refit(J, lab)        after it: enqueues the refit under the packed labels lab; it leaves the new rows in d_rows
+//   results(J)           enqueues its own result copies (the rows, the counter words and converged are copied here)
+//   n_params(J)          what a fitted model's record reports: the leading doubles of a scan row are the parameters
+//   fit_more(J, e, h_cnt, fit)   what it adds to entry e's record after a refit ran
+// (rows_up and prepare are two hooks so that the copies of wgs and pairs stay between them, where they have always
+// been.)  AssignGrpClosed<M> is lsqr_assign_grouped's and lsqr_refine_grouped's, AssignGrpLm<M> (assign_lm_grouped.h)
+// lsqr_refine_lm_grouped's, AssignGrpDense<NR> (assign_dense_grouped.h) the dense pair's.
+template <class F>
+int assign_grouped_rounds(AssignGrpJob &J, F fam) {
   typedef unsigned long long ull;
-  AssignGrpBufs &B = *J.B;
+  AssignGrpCore &C = fam.core();
+  AssignGrpLayout &L = J.L;
   ManyBufs &P = *J.pack.buf;
   hipStream_t stream = J.pack.stream;
-  const size_t NG = J.n_groups, MM = J.max_models, N = J.n, NR = NG * MM;
-  const size_t W = (size_t)J.pack.W;
-  const int org_off = fit_origin_offset<M>(J.cfg);
+  const size_t NG = J.n_groups, MM = J.max_models, N = J.n, NE = NG * MM;
 
-  std::vector<uint64_t> off;
-  const int st = grouped_pack(J.pack, J.data, J.stride, N, J.groups, J.on_device, off);
+  std::vector<uint64_t> &off = L.off;
+  int st = grouped_pack(J.pack, J.data, J.stride, N, J.groups, J.on_device, off);
   if (st != LSQR_OK) {
     memcpy(J.err, J.pack.err, sizeof J.err);
     return st;
@@ -246,136 +286,105 @@ int assign_grouped_run(AssignGrpJob &J) {
   const uint64_t NT = off[NG];
   const uint32_t *perm = P.d_grp_vals[1];
 
-  // the layout: the (group, chunk) workgroups, each group's place in the partials, the (group, model) pairs
-  std::vector<uint2> wgs, pairs;
-  std::vector<uint64_t> gbase(NG, 0);
-  uint64_t pblocks = 0;
+  // the layout: the (group, chunk) workgroups, each group's place in the partials and among the workgroups, the
+  // (group, model) pairs
+  L.NG = NG, L.NE = NE, L.pblocks = 0;
+  L.wgs.clear(), L.pairs.clear();  // (a job used twice starts over)
+  L.gbase.assign(NG, 0), L.wbase.assign(NG, 0);
   bool dead_records = false;  // records of a group that runs nothing
   for (size_t g = 0; g < NG; g++) {
     const uint64_t ng = off[g + 1] - off[g];
     const size_t nm = J.n_models[g];
     if (ng && !nm) dead_records = true;
     if (!ng || !nm) continue;
-    const uint32_t chunks = assign_chunks(ng);
-    gbase[g] = pblocks;
-    pblocks += (uint64_t)chunks * nm;
-    for (uint32_t q = 0; q < chunks; q++) wgs.push_back(make_uint2((uint32_t)g, q));
-    for (size_t m = 0; m < nm; m++) pairs.push_back(make_uint2((uint32_t)g, (uint32_t)m));
+    const uint32_t chunks = fam.chunks_of(ng);
+    L.gbase[g] = L.pblocks;
+    L.wbase[g] = L.wgs.size();
+    L.pblocks += (uint64_t)chunks * nm;
+    for (uint32_t q = 0; q < chunks; q++) L.wgs.push_back(make_uint2((uint32_t)g, q));
+    for (size_t m = 0; m < nm; m++) L.pairs.push_back(make_uint2((uint32_t)g, (uint32_t)m));
   }
-  const size_t NW = wgs.size(), NP = pairs.size();
+  const size_t NW = L.NW = L.wgs.size(), NP = L.NP = L.pairs.size();
   const bool moments = J.refine && J.max_rounds > 0 && NW > 0;
+  L.place(F::UP, F::SP, F::BLOCKS, F::GOING, fam.pin_own(L));
 
-  // device words: changed[NG], counts / used / ok [NR] each, rounds[NG], going
-  const size_t c_counts = NG, c_used = c_counts + NR, c_ok = c_used + NR, c_rounds = c_ok + NR, c_going = c_rounds + NG,
-               c_words = c_going + 1;
-  // pinned: what goes up, then what comes down
-  const size_t u_par = 0, u_gbase = u_par + sizeof(double) * NR * M::P, u_wgs = u_gbase + sizeof(uint64_t) * NG,
-               u_pairs = u_wgs + sizeof(uint2) * NW, u_nm = u_pairs + sizeof(uint2) * NP,
-               u_state = u_nm + asg_grp_up8(sizeof(int32_t) * NG), v_going = u_state + asg_grp_up8(sizeof(uint32_t) * NG),
-               v_rows = v_going + sizeof(ull), v_cnt = v_rows + sizeof(double) * NR * M::SP,
-               v_conv = v_cnt + sizeof(ull) * c_words, v_live = v_conv + asg_grp_up8(sizeof(uint32_t) * NG),
-               v_lm = v_live + (LM ? sizeof(ull) : 0), pin_bytes = v_lm + (LM ? sizeof(AssignLmOut) * NR : 0);
-  MANYCHK(many_grow_pinned(B.h_pin, pin_bytes));  // (every earlier call ended in a synchronisation)
-  char *pin = B.h_pin.get();
-  double *h_par = (double *)(pin + u_par);
-  int32_t *h_nm = (int32_t *)(pin + u_nm);
-  uint32_t *h_state = (uint32_t *)(pin + u_state);
-  const ull *h_going = (const ull *)(pin + v_going);
-  const double *h_rows = (const double *)(pin + v_rows);
-  const ull *h_cnt = (const ull *)(pin + v_cnt);
-  const uint32_t *h_conv = (const uint32_t *)(pin + v_conv);
-  [[maybe_unused]] const AssignLmOut *h_lm = (const AssignLmOut *)(pin + v_lm);
+  MANYCHK(many_grow_pinned(C.h_pin, L.bytes));  // (every earlier call ended in a synchronisation)
+  char *pin = C.h_pin.get();
+  int32_t *h_nm = (int32_t *)(pin + L.u_nm);
+  uint32_t *h_state = (uint32_t *)(pin + L.u_state);
+  const double *h_rows = (const double *)(pin + L.v_rows);
+  const ull *h_cnt = (const ull *)(pin + L.v_cnt);
+  const uint32_t *h_conv = (const uint32_t *)(pin + L.v_conv);
   for (size_t g = 0; g < NG; g++) {
-    const size_t nm = J.n_models[g];
-    h_nm[g] = (int32_t)nm;
-    h_state[g] = (off[g + 1] > off[g] && nm) ? 0u : 1u;
-    if (nm) memcpy(h_par + g * MM * M::P, J.params + g * MM * M::P, sizeof(double) * nm * M::P);
+    h_nm[g] = (int32_t)J.n_models[g];
+    h_state[g] = (off[g + 1] > off[g] && J.n_models[g]) ? 0u : 1u;
   }
-  memcpy(pin + u_gbase, gbase.data(), sizeof(uint64_t) * NG);
-  if (NW) memcpy(pin + u_wgs, wgs.data(), sizeof(uint2) * NW);
-  if (NP) memcpy(pin + u_pairs, pairs.data(), sizeof(uint2) * NP);
+  memcpy(pin + L.u_gbase, L.gbase.data(), sizeof(uint64_t) * NG);
+  memcpy(pin + L.u_wbase, L.wbase.data(), sizeof(uint64_t) * NG);
+  if (NW) memcpy(pin + L.u_wgs, L.wgs.data(), sizeof(uint2) * NW);
+  if (NP) memcpy(pin + L.u_pairs, L.pairs.data(), sizeof(uint2) * NP);
 
-  MANYCHK(many_grow(B.d_nm, NG));
-  MANYCHK(many_grow(B.d_gbase, NG));
-  MANYCHK(many_grow(B.d_state, 2 * NG));  // state, converged
-  MANYCHK(many_grow(B.d_cnt, c_words));
-  MANYCHK(many_grow(B.d_par, std::max<size_t>(NR * M::P, 1)));
-  MANYCHK(many_grow(B.d_rows, std::max<size_t>(NR * M::SP, 1)));
-  MANYCHK(many_grow(B.d_wgs, std::max<size_t>(NW, 1)));
-  MANYCHK(many_grow(B.d_pairs, std::max<size_t>(NP, 1)));
-  MANYCHK(many_grow(B.d_labels[0], std::max<size_t>(NT, 1)));
-  if (J.refine) MANYCHK(many_grow(B.d_labels[1], std::max<size_t>(NT, 1)));
-  if (J.residuals_out) MANYCHK(many_grow(B.d_res, std::max<size_t>(NT, 1)));
-  if (moments) MANYCHK(many_grow(B.d_partials, (size_t)pblocks * M::NMOM));
-  if (!J.on_device && J.labels_out) MANYCHK(many_grow(B.d_lab_out, N));
-  if (!J.on_device && J.residuals_out) MANYCHK(many_grow(B.d_res_out, N));
-  ull *d_changed = B.d_cnt, *d_counts = B.d_cnt + c_counts, *d_used = B.d_cnt + c_used, *d_ok = B.d_cnt + c_ok,
-      *d_rounds = B.d_cnt + c_rounds, *d_going = B.d_cnt + c_going;
-  uint32_t *d_state = B.d_state, *d_conv = B.d_state + NG;
+  // (many_grow gives an empty buffer its least size even when asked for nothing)
+  MANYCHK(many_grow(C.d_nm, NG));
+  MANYCHK(many_grow(C.d_gbase, NG));
+  if (F::WBASE) MANYCHK(many_grow(C.d_wbase, NG));
+  MANYCHK(many_grow(C.d_state, 2 * NG));  // state, converged
+  MANYCHK(many_grow(C.d_cnt, L.c_words));
+  MANYCHK(many_grow(C.d_rows, NE * F::SP));
+  MANYCHK(many_grow(C.d_wgs, NW));
+  MANYCHK(many_grow(C.d_pairs, NP));
+  MANYCHK(many_grow(C.d_labels[0], (size_t)NT));
+  if (J.refine) MANYCHK(many_grow(C.d_labels[1], (size_t)NT));
+  if (J.residuals_out) MANYCHK(many_grow(C.d_res, (size_t)NT));
+  if (!J.on_device && J.labels_out) MANYCHK(many_grow(C.d_lab_out, N));
+  if (!J.on_device && J.residuals_out) MANYCHK(many_grow(C.d_res_out, N));
+  if ((st = fam.reserve(J, moments)) != LSQR_OK) return st;
+  uint32_t *d_state = C.d_state, *d_conv = C.d_state + NG;
+  L.d_cnt = C.d_cnt, L.pin = pin;
+  ull *d_changed = L.d(0), *d_rounds = L.d(L.c_rounds), *d_going = L.d(L.c_going);
+  L.T = AsgGrpTab{P.d_grp_off, C.d_gbase, C.d_nm, d_state};
 
-  MANYCHK(hipMemcpyAsync(B.d_nm, h_nm, sizeof(int32_t) * NG, hipMemcpyHostToDevice, stream));
-  MANYCHK(hipMemcpyAsync(B.d_gbase, pin + u_gbase, sizeof(uint64_t) * NG, hipMemcpyHostToDevice, stream));
+  MANYCHK(hipMemcpyAsync(C.d_nm, h_nm, sizeof(int32_t) * NG, hipMemcpyHostToDevice, stream));
+  MANYCHK(hipMemcpyAsync(C.d_gbase, pin + L.u_gbase, sizeof(uint64_t) * NG, hipMemcpyHostToDevice, stream));
+  if (F::WBASE)
+    MANYCHK(hipMemcpyAsync(C.d_wbase, pin + L.u_wbase, sizeof(uint64_t) * NG, hipMemcpyHostToDevice, stream));
   MANYCHK(hipMemcpyAsync(d_state, h_state, sizeof(uint32_t) * NG, hipMemcpyHostToDevice, stream));
   MANYCHK(hipMemsetAsync(d_conv, 0, sizeof(uint32_t) * NG, stream));
-  MANYCHK(hipMemsetAsync(B.d_cnt, 0, sizeof(ull) * c_words, stream));
+  MANYCHK(hipMemsetAsync(C.d_cnt, 0, sizeof(ull) * L.c_words, stream));
   if (NW) {
-    MANYCHK(hipMemcpyAsync(B.d_par, h_par, sizeof(double) * NR * M::P, hipMemcpyHostToDevice, stream));
-    MANYCHK(hipMemcpyAsync(B.d_wgs, pin + u_wgs, sizeof(uint2) * NW, hipMemcpyHostToDevice, stream));
-    MANYCHK(hipMemcpyAsync(B.d_pairs, pin + u_pairs, sizeof(uint2) * NP, hipMemcpyHostToDevice, stream));
-    hipLaunchKernelGGL((k_assign_prepare<M>), dim3(grp_grid(NR)), dim3(kBlock), 0, stream, B.d_par, B.d_nm.get(),
-                       (uint64_t)NR, (int)MM, J.mc, B.d_rows);
-    MANYCHK(hipGetLastError());
+    if ((st = fam.rows_up(J, (double *)(pin + L.u_rows))) != LSQR_OK) return st;
+    MANYCHK(hipMemcpyAsync(C.d_wgs, pin + L.u_wgs, sizeof(uint2) * NW, hipMemcpyHostToDevice, stream));
+    MANYCHK(hipMemcpyAsync(C.d_pairs, pin + L.u_pairs, sizeof(uint2) * NP, hipMemcpyHostToDevice, stream));
+    if ((st = fam.prepare(J)) != LSQR_OK) return st;
   }
   if (dead_records && NT) {  // no pass writes them
-    MANYCHK(hipMemsetAsync(B.d_labels[0], 0xFF, sizeof(int32_t) * NT, stream));
-    if (J.refine) MANYCHK(hipMemsetAsync(B.d_labels[1], 0xFF, sizeof(int32_t) * NT, stream));
+    MANYCHK(hipMemsetAsync(C.d_labels[0], 0xFF, sizeof(int32_t) * NT, stream));
+    if (J.refine) MANYCHK(hipMemsetAsync(C.d_labels[1], 0xFF, sizeof(int32_t) * NT, stream));
     if (J.residuals_out) {
-      hipLaunchKernelGGL(k_asg_grp_fill, dim3(grp_grid(NT)), dim3(kBlock), 0, stream, B.d_res, (uint64_t)NT,
+      hipLaunchKernelGGL(k_asg_grp_fill, dim3(grp_grid(NT)), dim3(kBlock), 0, stream, C.d_res, (uint64_t)NT,
                          __builtin_inf());
       MANYCHK(hipGetLastError());
     }
   }
 
-  const AsgGrpTab T{P.d_grp_off, B.d_gbase, B.d_nm, d_state};
-  [[maybe_unused]] const AsgGrpLmView V{T,        B.d_wgs, B.d_pairs, NW,       NP,     NG,   MM, pblocks,
-                                        P.d_data, W,       B.d_rows,  d_counts, d_used, d_ok, (uint32_t *)(pin + v_live)};
-  if constexpr (LM)
-    if (moments) {
-      const int st = assign_lm_grp_reserve<M>(J, V);
-      if (st != LSQR_OK) return st;
-    }
   int cur = 0;
   size_t r = 0;
   while (NW) {
     const bool last = r == J.max_rounds;
-    int32_t *lab = B.d_labels[cur];
-    double *res = J.residuals_out ? B.d_res.get() : nullptr;
-    const int32_t *old = r > 0 ? B.d_labels[cur ^ 1].get() : nullptr;
-    if (last)
-      hipLaunchKernelGGL((k_asg_grp_pass<M, false>), dim3((unsigned)NW), dim3(kBlock), 0, stream, P.d_data, W,
-                         B.d_wgs, T, B.d_rows, (int)MM, org_off, J.mc, lab, res, old, d_changed, d_counts, nullptr,
-                         nullptr);
-    else
-      hipLaunchKernelGGL((k_asg_grp_pass<M, true>), dim3((unsigned)NW), dim3(kBlock), 0, stream, P.d_data, W, B.d_wgs,
-                         T, B.d_rows, (int)MM, org_off, J.mc, lab, res, old, d_changed, d_counts, B.d_partials,
-                         LM ? B.d_presence.get() : nullptr);
-    MANYCHK(hipGetLastError());
+    int32_t *lab = C.d_labels[cur];
+    double *res = J.residuals_out ? C.d_res.get() : nullptr;
+    const int32_t *old = r > 0 ? C.d_labels[cur ^ 1].get() : nullptr;
+    if ((st = fam.pass(J, last, lab, res, old)) != LSQR_OK) return st;
     if (last) break;  // every group still going stops here: nothing to read
-    MANYCHK(hipMemsetAsync(d_going, 0, sizeof(ull), stream));
+    MANYCHK(hipMemsetAsync(d_going, 0, sizeof(ull) * F::GOING, stream));
     hipLaunchKernelGGL(k_asg_grp_decide, dim3(grp_grid(NG)), dim3(kBlock), 0, stream, (uint32_t)NG, (ull)r, 0,
                        d_changed, d_state, d_rounds, d_conv, d_going);
     MANYCHK(hipGetLastError());
-    MANYCHK(hipMemcpyAsync(pin + v_going, d_going, sizeof(ull), hipMemcpyDeviceToHost, stream));
-    MANYCHK(hipStreamSynchronize(stream));  // the one word of the round
-    if (*h_going == 0) break;
-    if constexpr (LM) {
-      const int st = assign_lm_grp_run<M>(J, V, lab);
-      if (st != LSQR_OK) return st;
-    } else {
-      hipLaunchKernelGGL((k_asg_grp_solve<M>), dim3((unsigned)NP), dim3(64), 0, stream, B.d_pairs, T, B.d_partials,
-                         (int)MM, org_off, J.mc, B.d_rows, d_counts, d_used, d_ok, nullptr);
-      MANYCHK(hipGetLastError());
-    }
+    if ((st = fam.before_sync(J)) != LSQR_OK) return st;
+    MANYCHK(hipMemcpyAsync(pin + L.v_going, d_going, sizeof(ull) * F::GOING, hipMemcpyDeviceToHost, stream));
+    MANYCHK(hipStreamSynchronize(stream));  // the going words of the round
+    if (*(const ull *)(pin + L.v_going) == 0) break;
+    if ((st = fam.refit(J, lab)) != LSQR_OK) return st;
     r++;
     cur ^= 1;
   }
@@ -387,40 +396,39 @@ int assign_grouped_run(AssignGrpJob &J) {
 
   // results: the labels of the last pass in upload order, then the rows and the per-group words
   if (J.labels_out) {
-    int32_t *d_lab = J.on_device ? J.labels_out : B.d_lab_out.get();
+    int32_t *d_lab = J.on_device ? J.labels_out : C.d_lab_out.get();
     hipLaunchKernelGGL(k_grp_scatter_labels, dim3(grp_grid(N)), dim3(kBlock), 0, stream, perm, (uint32_t)N,
-                       (uint32_t)NT, B.d_labels[cur].get(), d_lab);
+                       (uint32_t)NT, C.d_labels[cur].get(), d_lab);
     MANYCHK(hipGetLastError());
     if (!J.on_device)
       MANYCHK(hipMemcpyAsync(J.labels_out, d_lab, sizeof(int32_t) * N, hipMemcpyDeviceToHost, stream));
   }
   if (J.residuals_out) {
-    double *d_r = J.on_device ? J.residuals_out : B.d_res_out.get();
+    double *d_r = J.on_device ? J.residuals_out : C.d_res_out.get();
     hipLaunchKernelGGL(k_grp_scatter_f64, dim3(grp_grid(N)), dim3(kBlock), 0, stream, perm, (uint32_t)N, (uint32_t)NT,
-                       B.d_res.get(), __builtin_inf(), d_r);
+                       C.d_res.get(), __builtin_inf(), d_r);
     MANYCHK(hipGetLastError());
     if (!J.on_device)
       MANYCHK(hipMemcpyAsync(J.residuals_out, d_r, sizeof(double) * N, hipMemcpyDeviceToHost, stream));
   }
-  if (r > 0) MANYCHK(hipMemcpyAsync(pin + v_rows, B.d_rows, sizeof(double) * NR * M::SP, hipMemcpyDeviceToHost, stream));
-  MANYCHK(hipMemcpyAsync(pin + v_cnt, B.d_cnt, sizeof(ull) * c_words, hipMemcpyDeviceToHost, stream));
-  MANYCHK(hipMemcpyAsync(pin + v_conv, d_conv, sizeof(uint32_t) * NG, hipMemcpyDeviceToHost, stream));
-  if constexpr (LM)
-    if (r > 0)
-      MANYCHK(hipMemcpyAsync(pin + v_lm, B.d_lm_out, sizeof(AssignLmOut) * NR, hipMemcpyDeviceToHost, stream));
+  if (r > 0)
+    MANYCHK(hipMemcpyAsync(pin + L.v_rows, C.d_rows, sizeof(double) * NE * F::SP, hipMemcpyDeviceToHost, stream));
+  MANYCHK(hipMemcpyAsync(pin + L.v_cnt, C.d_cnt, sizeof(ull) * L.c_words, hipMemcpyDeviceToHost, stream));
+  MANYCHK(hipMemcpyAsync(pin + L.v_conv, d_conv, sizeof(uint32_t) * NG, hipMemcpyDeviceToHost, stream));
+  if (r > 0 && (st = fam.results(J)) != LSQR_OK) return st;
   MANYCHK(hipStreamSynchronize(stream));
 
+  const size_t np = (size_t)fam.n_params(J);
   for (size_t g = 0; g < NG; g++) {
     const size_t nm = J.n_models[g];
     const uint64_t ng = off[g + 1] - off[g];
-    const size_t rg = (size_t)h_cnt[c_rounds + g];
+    const size_t rg = (size_t)h_cnt[L.c_rounds + g];
     if (rg > 0)
       for (size_t m = 0; m < nm; m++)
-        for (int j = 0; j < (int)M::P; j++)
-          J.params[(g * MM + m) * M::P + j] = h_rows[(g * MM + m) * M::SP + j];
+        for (size_t j = 0; j < np; j++) J.params[(g * MM + m) * np + j] = h_rows[(g * MM + m) * F::SP + j];
     if (J.counts_out) {
       uint64_t sum = 0, *c = J.counts_out + g * (MM + 1);
-      for (size_t m = 0; m < MM; m++) sum += (c[m] = m < nm ? h_cnt[c_counts + g * MM + m] : 0);
+      for (size_t m = 0; m < MM; m++) sum += (c[m] = m < nm ? h_cnt[L.c_counts + g * MM + m] : 0);
       c[MM] = ng - sum;
     }
     if (!J.refine) continue;
@@ -429,14 +437,8 @@ int assign_grouped_run(AssignGrpJob &J) {
     for (size_t m = 0; m < MM; m++) {
       const size_t e = g * MM + m;
       if (m < nm) {
-        assign_fit_out(rg, h_cnt[c_ok + e], h_cnt[c_used + e], (int32_t)M::P, &J.status_out[e], &J.fits[e]);
-        if constexpr (LM)
-          if (rg > 0) {
-            J.fits[e].lm_info = h_lm[e].lm_info;
-            J.fits[e].lm_nfev = h_lm[e].lm_nfev;
-            J.fits[e].reserved = h_lm[e].stall;
-            J.fits[e].cost = h_lm[e].cost;
-          }
+        assign_fit_out(rg, h_cnt[L.c_ok + e], h_cnt[L.c_used + e], (int32_t)np, &J.status_out[e], &J.fits[e]);
+        if (rg > 0) fam.fit_more(J, e, h_cnt, J.fits[e]);
       } else {
         J.status_out[e] = LSQR_ERR_STATE;  // model not there
         memset(&J.fits[e], 0, sizeof(lsqr_fit_info));
@@ -446,6 +448,73 @@ int assign_grouped_run(AssignGrpJob &J) {
   if (J.offsets_out) memcpy(J.offsets_out, off.data(), sizeof(uint64_t) * (NG + 1));
   return LSQR_OK;
 }
+
+// The closed form: lsqr_assign_grouped, and lsqr_refine_grouped, whose refit is one k_asg_grp_solve launch.
+template <class M>
+struct AssignGrpClosed {
+  static constexpr int UP = M::P, SP = M::SP, BLOCKS = 0, GOING = 1;
+  static constexpr bool WBASE = false;
+  AssignGrpBufs &B;
+
+  AssignGrpCore &core() { return B.core; }
+  static uint32_t chunks_of(uint64_t n) { return assign_chunks(n); }
+  static size_t pin_own(const AssignGrpLayout &) { return 0; }
+  int reserve(AssignGrpJob &J, bool moments) {
+    MANYCHK(many_grow(B.d_par, J.L.NE * M::P));
+    if (moments) MANYCHK(many_grow(B.core.d_partials, (size_t)J.L.pblocks * M::NMOM));
+    return LSQR_OK;
+  }
+  int rows_up(AssignGrpJob &J, double *h_rows) {  // the rows that are there, as they are
+    const size_t MM = J.max_models;
+    for (size_t g = 0; g < J.n_groups; g++)
+      if (J.n_models[g])
+        memcpy(h_rows + g * MM * M::P, J.params + g * MM * M::P, sizeof(double) * J.n_models[g] * M::P);
+    MANYCHK(hipMemcpyAsync(B.d_par, h_rows, sizeof(double) * J.L.NE * M::P, hipMemcpyHostToDevice, J.pack.stream));
+    return LSQR_OK;
+  }
+  int prepare(AssignGrpJob &J) {  // k_assign_prepare with the groups' model counts
+    hipLaunchKernelGGL((k_assign_prepare<M>), dim3(grp_grid(J.L.NE)), dim3(kBlock), 0, J.pack.stream, B.d_par,
+                       B.core.d_nm.get(), (uint64_t)J.L.NE, (int)J.max_models, J.mc, B.core.d_rows);
+    MANYCHK(hipGetLastError());
+    return LSQR_OK;
+  }
+  // presence: where a pass with moments leaves every workgroup's word (nullable)
+  int pass_to(AssignGrpJob &J, bool last, int32_t *lab, double *res, const int32_t *old,
+              unsigned long long *presence) {
+    const AssignGrpLayout &L = J.L;
+    AssignGrpCore &C = B.core;
+    const size_t W = (size_t)J.pack.W;
+    const int MM = (int)J.max_models, org_off = fit_origin_offset<M>(J.cfg);
+    if (last)
+      hipLaunchKernelGGL((k_asg_grp_pass<M, false>), dim3((unsigned)L.NW), dim3(kBlock), 0, J.pack.stream,
+                         J.pack.buf->d_data, W, C.d_wgs, L.T, C.d_rows, MM, org_off, J.mc, lab, res, old, L.d(0),
+                         L.d(L.c_counts), nullptr, nullptr);
+    else
+      hipLaunchKernelGGL((k_asg_grp_pass<M, true>), dim3((unsigned)L.NW), dim3(kBlock), 0, J.pack.stream,
+                         J.pack.buf->d_data, W, C.d_wgs, L.T, C.d_rows, MM, org_off, J.mc, lab, res, old, L.d(0),
+                         L.d(L.c_counts), C.d_partials, presence);
+    MANYCHK(hipGetLastError());
+    return LSQR_OK;
+  }
+  int pass(AssignGrpJob &J, bool last, int32_t *lab, double *res, const int32_t *old) {
+    return pass_to(J, last, lab, res, old, nullptr);
+  }
+  int before_sync(AssignGrpJob &) { return LSQR_OK; }
+  // START, start: see k_asg_grp_solve
+  template <bool START>
+  int solve_to(AssignGrpJob &J, double *start) {
+    const AssignGrpLayout &L = J.L;
+    hipLaunchKernelGGL((k_asg_grp_solve<M, START>), dim3((unsigned)L.NP), dim3(64), 0, J.pack.stream, B.core.d_pairs,
+                       L.T, B.core.d_partials, (int)J.max_models, fit_origin_offset<M>(J.cfg), J.mc, B.core.d_rows,
+                       L.d(L.c_counts), L.d(L.c_used), L.d(L.c_ok), start);
+    MANYCHK(hipGetLastError());
+    return LSQR_OK;
+  }
+  int refit(AssignGrpJob &J, const int32_t *) { return solve_to<false>(J, nullptr); }
+  int results(AssignGrpJob &) { return LSQR_OK; }
+  static int32_t n_params(const AssignGrpJob &) { return (int32_t)M::P; }
+  void fit_more(AssignGrpJob &, size_t, const unsigned long long *, lsqr_fit_info &) {}
+};
 #endif  // __HIPCC__
 
 }  // namespace lsqr

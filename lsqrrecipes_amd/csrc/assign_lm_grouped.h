@@ -1,8 +1,8 @@
-// assign_lm_grouped.h -- lsqr_refine_lm_grouped: lsqr_refine_grouped's loop (assign_grouped.h: assign_grouped_run) for
-// the sphere with LSQR_LS_GEOMETRIC.  Group g is decided bit for bit as lsqr_refine_lm (assign_lm.h) decides it on a
-// fresh context that holds the group's records alone.  The refit of a round is the algebraic refit of every group still
-// going, kept aside as the START, and then one Levenberg-Marquardt run per (group, model), all of them in lock-step
-// evaluation rounds over the packed records.
+// assign_lm_grouped.h -- lsqr_refine_lm_grouped: the grouped round loop (assign_grouped.h: assign_grouped_rounds) for
+// the sphere with LSQR_LS_GEOMETRIC, as the family AssignGrpLm<M>.  Group g is decided bit for bit as lsqr_refine_lm
+// (assign_lm.h) decides it on a fresh context that holds the group's records alone.  The refit of a round is the
+// algebraic refit of every group still going, kept aside as the START, and then one Levenberg-Marquardt run per
+// (group, model), all of them in lock-step evaluation rounds over the packed records.
 //
 //   k_asg_grp_pass<M, true>   as in lsqr_refine_grouped; it also stores the presence word of every (group, chunk)
 //   k_asg_grp_solve<M, true>  as in lsqr_refine_grouped, but into the start rows (its START flag): the rows stay
@@ -39,8 +39,8 @@
 // KiB).  Registers of the pass: assign_lm_pass_chunk's, plus the workgroup's table entries in
 // scalar registers.  See DESIGN.md section 14.3.
 //
-// Included after assign_lm.h and assign_grouped.h; assign_grouped_run<M, true> calls assign_lm_grp_reserve and
-// assign_lm_grp_run.
+// AssignGrpLm<M> derives from AssignGrpClosed<M> as AssignLm<M> (assign_lm.h) does from AssignClosed<M>: its reserve
+// adds the stage's buffers, its pass hands over d_presence, and its refit is the stage.
 #pragma once
 #include "assign_grouped.h"
 #include "assign_lm.h"
@@ -135,52 +135,77 @@ __global__ __launch_bounds__(64) void k_asg_grp_lm_step(const uint2 *__restrict_
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------
+// lsqr_refine_lm_grouped's family: AssignGrpClosed<M> whose pass also leaves the presence words and whose refit is the
+// LM stage, for every group still going.  The pass has left the moments of the packed labels `lab` in d_partials and
+// the presence words in d_presence; the refit is the algebraic solve into the start rows, k_asg_grp_lm_init, the LM
+// partials cleared, then the evaluations (assign_lm_evals, assign_lm.h).
 template <class M>
-int assign_lm_grp_reserve(AssignGrpJob &J, const AsgGrpLmView &V) {
-  AssignGrpBufs &B = *J.B;
-  const size_t NR = V.n_groups * V.max_models;
-  MANYCHK(many_grow(B.d_start, NR * M::SP));
-  MANYCHK(many_grow(B.d_presence, V.n_wgs));
-  MANYCHK(many_grow(B.d_lm_partials, (size_t)V.pblocks * M::NMOM_LM));
-  MANYCHK(many_grow(B.d_lm_mask, V.n_groups));
-  MANYCHK(many_grow(B.d_lm_live, 1));
-  MANYCHK(many_grow(B.d_lm_state, NR));
-  MANYCHK(many_grow(B.d_lm_out, NR));
-  return LSQR_OK;
-}
+struct AssignGrpLm : AssignGrpClosed<M> {
+  typedef AssignGrpClosed<M> Base;
+  using Base::B;
 
-// The refit of one round, for every group still going.  The pass has left the moments of the labels `lab` in
-// B.d_partials and the presence words in B.d_presence.  The evaluations are assign_lm_evals (assign_lm.h).
-template <class M>
-int assign_lm_grp_run(AssignGrpJob &J, const AsgGrpLmView &V, const int32_t *lab) {
-  AssignGrpBufs &B = *J.B;
-  hipStream_t stream = J.pack.stream;
-  const int MM = (int)V.max_models, org_off = fit_origin_offset<M>(J.cfg);
-  int n = 0, maxfev = 0;
-  double ftol = 0, xtol = 0, gtol = 0;
-  lm_settings(J.cfg, &n, &ftol, &xtol, &gtol, &maxfev);
-  hipLaunchKernelGGL((k_asg_grp_solve<M, true>), dim3((unsigned)V.n_pairs), dim3(64), 0, stream, V.pairs, V.T,
-                     B.d_partials.get(), MM, org_off, J.mc, V.rows, V.counts, V.used, V.ok, B.d_start.get());
-  MANYCHK(hipGetLastError());
-  MANYCHK(hipMemsetAsync(B.d_lm_live, 0, sizeof(uint32_t), stream));
-  hipLaunchKernelGGL((k_asg_grp_lm_init<M>), dim3((unsigned)V.n_groups), dim3(64), 0, stream, V.T, B.d_start.get(), MM,
-                     n, ftol, xtol, gtol, maxfev, V.ok, B.d_lm_state.get(), B.d_lm_out.get(), B.d_lm_mask.get(),
-                     B.d_lm_live.get());
-  MANYCHK(hipGetLastError());
-  MANYCHK(hipMemsetAsync(B.d_lm_partials, 0, sizeof(double) * (size_t)V.pblocks * M::NMOM_LM, stream));
-  return assign_lm_evals(
-      stream, maxfev, B.d_lm_live.get(), V.h_live, J.err,
-      [&] {
-        hipLaunchKernelGGL((k_asg_grp_lm_pass<M>), dim3((unsigned)V.n_wgs), dim3(kBlock), 0, stream, V.data, V.stride,
-                           V.wgs, V.T, lab, B.d_presence.get(), B.d_lm_mask.get(), B.d_lm_state.get(), MM, J.mc,
-                           B.d_lm_partials.get());
-      },
-      [&] {
-        hipLaunchKernelGGL((k_asg_grp_lm_step<M>), dim3((unsigned)V.n_pairs), dim3(64), 0, stream, V.pairs, V.T,
-                           B.d_lm_partials.get(), MM, J.mc, B.d_lm_state.get(), V.rows, V.ok, B.d_lm_out.get(),
-                           B.d_lm_mask.get(), B.d_lm_live.get());
-      });
-}
+  // the family's own of h_pin: the live counter's copy, then an AssignLmOut per (group, model)
+  static size_t pin_own(const AssignGrpLayout &L) { return sizeof(unsigned long long) + sizeof(AssignLmOut) * L.NE; }
+  static AssignLmOut *h_lm(const AssignGrpLayout &L) { return (AssignLmOut *)(L.h(L.v_own) + 8); }
+
+  int reserve(AssignGrpJob &J, bool moments) {
+    const int st = Base::reserve(J, moments);
+    if (st != LSQR_OK || !moments) return st;
+    const AssignGrpLayout &L = J.L;
+    MANYCHK(many_grow(B.d_start, L.NE * M::SP));
+    MANYCHK(many_grow(B.core.d_presence, L.NW));
+    MANYCHK(many_grow(B.d_lm_partials, (size_t)L.pblocks * M::NMOM_LM));
+    MANYCHK(many_grow(B.d_lm_mask, L.NG));
+    MANYCHK(many_grow(B.d_lm_live, 1));
+    MANYCHK(many_grow(B.d_lm_state, L.NE));
+    MANYCHK(many_grow(B.d_lm_out, L.NE));
+    return LSQR_OK;
+  }
+  int pass(AssignGrpJob &J, bool last, int32_t *lab, double *res, const int32_t *old) {
+    return Base::pass_to(J, last, lab, res, old, B.core.d_presence.get());
+  }
+  int refit(AssignGrpJob &J, const int32_t *lab) {
+    const AssignGrpLayout &L = J.L;
+    AssignGrpCore &C = B.core;
+    hipStream_t stream = J.pack.stream;
+    unsigned long long *d_ok = L.d(L.c_ok);
+    const int MM = (int)J.max_models;
+    int n = 0, maxfev = 0;
+    double ftol = 0, xtol = 0, gtol = 0;
+    lm_settings(J.cfg, &n, &ftol, &xtol, &gtol, &maxfev);
+    const int st = Base::template solve_to<true>(J, B.d_start.get());
+    if (st != LSQR_OK) return st;
+    MANYCHK(hipMemsetAsync(B.d_lm_live, 0, sizeof(uint32_t), stream));
+    hipLaunchKernelGGL((k_asg_grp_lm_init<M>), dim3((unsigned)L.NG), dim3(64), 0, stream, L.T, B.d_start.get(), MM, n,
+                       ftol, xtol, gtol, maxfev, d_ok, B.d_lm_state.get(), B.d_lm_out.get(), B.d_lm_mask.get(),
+                       B.d_lm_live.get());
+    MANYCHK(hipGetLastError());
+    MANYCHK(hipMemsetAsync(B.d_lm_partials, 0, sizeof(double) * (size_t)L.pblocks * M::NMOM_LM, stream));
+    return assign_lm_evals(
+        stream, maxfev, B.d_lm_live.get(), (uint32_t *)L.h(L.v_own), J.err,
+        [&] {
+          hipLaunchKernelGGL((k_asg_grp_lm_pass<M>), dim3((unsigned)L.NW), dim3(kBlock), 0, stream,
+                             J.pack.buf->d_data.get(), (size_t)J.pack.W, C.d_wgs.get(), L.T, lab, C.d_presence.get(),
+                             B.d_lm_mask.get(), B.d_lm_state.get(), MM, J.mc, B.d_lm_partials.get());
+        },
+        [&] {
+          hipLaunchKernelGGL((k_asg_grp_lm_step<M>), dim3((unsigned)L.NP), dim3(64), 0, stream, C.d_pairs.get(), L.T,
+                             B.d_lm_partials.get(), MM, J.mc, B.d_lm_state.get(), C.d_rows.get(), d_ok,
+                             B.d_lm_out.get(), B.d_lm_mask.get(), B.d_lm_live.get());
+        });
+  }
+  int results(AssignGrpJob &J) {
+    MANYCHK(hipMemcpyAsync(h_lm(J.L), B.d_lm_out, sizeof(AssignLmOut) * J.L.NE, hipMemcpyDeviceToHost, J.pack.stream));
+    return LSQR_OK;
+  }
+  void fit_more(AssignGrpJob &J, size_t e, const unsigned long long *, lsqr_fit_info &fit) {
+    const AssignLmOut &o = h_lm(J.L)[e];
+    fit.lm_info = o.lm_info;
+    fit.lm_nfev = o.lm_nfev;
+    fit.reserved = o.stall;
+    fit.cost = o.cost;
+  }
+};
 #endif  // __HIPCC__
 
 }  // namespace lsqr

@@ -57,7 +57,8 @@ struct Buf {
 // already serves `need`.
 //   grow_double: the context's buffers (ensure): what is asked for, at least twice what is there
 //   grow_quarter: the batched calls' device buffers (many_grow): a quarter of head room, at least 64 elements;
-//                 their pinned buffers (many_grow_pinned) likewise in bytes, at least 64 KiB
+//                 their pinned buffers (many_grow_pinned) likewise in bytes, at least 64 KiB.  An EMPTY buffer gets
+//                 that least size even for need == 0: assign_grouped_rounds relies on it for its empty lists
 template <class B>
 size_t grow_double(const B &b, size_t need) {
   if (need <= b.cap() && b.get()) return 0;

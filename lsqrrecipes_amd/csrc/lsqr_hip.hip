@@ -4503,9 +4503,10 @@ int lsqr_refine_rigid(lsqr_ctx *c, double *params_inout, size_t n_models, size_t
                                         labels_out, counts_out, fits, status_out, rounds_out, converged_out);
 }
 
-// lsqr_assign_grouped, lsqr_refine_grouped, lsqr_refine_lm_grouped and the dense pair.  The sort and the packed copy
-// live in the batched calls' buffers (lsqr_ctx::many), as lsqr_ransac_grouped's do.  (The dense gate serves an
-// assignment and a refit: J.refine is its caller's.)
+// lsqr_assign_grouped, lsqr_refine_grouped, lsqr_refine_lm_grouped and the dense pair: the grouped round loop
+// (assign_grouped_rounds) with the gate's family.  The sort and the packed copy live in the batched calls' buffers
+// (lsqr_ctx::many), as lsqr_ransac_grouped's do.  (The dense gate serves an assignment and a refit: J.refine is its
+// caller's.)
 extern "C++" {
 template <AssignGate G>
 static int assign_grouped_call(lsqr_ctx *c, const char *fn, bool args, AssignGrpJob &J) {
@@ -4530,17 +4531,18 @@ static int assign_grouped_call(lsqr_ctx *c, const char *fn, bool args, AssignGrp
         J.data = c->d_data;
         J.stride = c->stride;
         J.n = c->n;
-        J.B = c->assign_grp.get();
         typedef typename decltype(tag)::type M;
         if constexpr (G == ASSIGN_GATE_DENSE) {
           if (!c->assign_dense_grp) c->assign_dense_grp.reset(new AssignDenseGrpBufs());
-          return assign_dense_grouped_run<M::NR>(J, *c->assign_dense_grp, J.pack.dense_fast, J.pack.dense_dd);
-        } else if constexpr (G != ASSIGN_GATE_LM) {
-          return assign_grouped_run<M>(J);
-        } else if constexpr (requires { M::NMOM_LM; }) {  // (the sphere)
-          return assign_grouped_run<M, true>(J);
+          const int dim = (int)c->cfg.dim;
+          return assign_grouped_rounds(J, AssignGrpDense<M::NR>{c->assign_grp->core, *c->assign_dense_grp,
+                                                                J.pack.dense_fast, J.pack.dense_dd, dim,
+                                                                many_dense_ps(dim)});
         } else {
-          return LSQR_ERR_INVALID;
+          AssignGrpBufs &B = *c->assign_grp;
+          if constexpr (G != ASSIGN_GATE_LM) return assign_grouped_rounds(J, AssignGrpClosed<M>{B});
+          else if constexpr (requires { M::NMOM_LM; }) return assign_grouped_rounds(J, AssignGrpLm<M>{{B}});  // (sphere)
+          else return LSQR_ERR_INVALID;
         }
       });
 }
