@@ -1112,6 +1112,16 @@ LSQR_API void lsqr_dedup_destroy(void *set);
  *                index without axes.  Votes are identical.  "scan_slab_gate": 1..8 (default 3), the slab of a cell is
  *                tested only where its width is at most value / 4 of the box's extent along the axis (A/B knob; the
  *                index is rebuilt);
+ * "scan_tiles":  the two-level scans (k_scan_pairs, k_scan_cells) open a cell 1 (default) = from fp32 tiles of the
+ *                index: the cell's observations relative to its centre as packed fp32 pairs (and the sphere's |x'|^2),
+ *                computed once behind the index build (csrc/cells.h: k_build_tiles; 12 bytes a record for plane and
+ *                line in 3-D, 16 for the sphere) and bit for bit what a wave would have computed; 0 = from the fp64
+ *                sorted copy, converted by every wave for every cell it opens.  Accepted values 0 and 1; keeps the
+ *                index, and with 0 set before the index is built no tiles are built.  Read by the forms a default
+ *                path reaches (plane: the packed counted forms, sphere and line: the general one, k_scan_cells; each
+ *                with the model's default "scan_block"; not by the 3-D plane's k_scan_cells and "scan_recheck" 0 form
+ *                over 512-record cells, which have no register for it); the exact fp64 paths keep reading the sorted
+ *                copy.  Votes are identical;
  * "dense_mask_ring": LDS tile buffers per wave of the dense final fit's fused mask + normal-equations pass: 4 (default at
  *                n = 64) = one workgroup per CU with three tiles in flight, 2 = two workgroups per CU (A/B knob);
  * "mom_chunk":   records per workgroup of the mask / moment passes in units of 256 (0 = default: 4, wide US / phantom
@@ -1121,6 +1131,12 @@ LSQR_API int lsqr_set_option(lsqr_ctx *ctx, const char *name, int value);
 /* State of the spatial index of the current upload ("scan_index"): out = {built (0/1), indexed
  * (finite) observations, cells, observations per cell}. */
 LSQR_API int lsqr_index_info(const lsqr_ctx *ctx, uint64_t out[4]);
+
+/* Debug: the fp32 tiles of the index ("scan_tiles") against the sorted copy.  Every cell is opened both ways on the
+ * device (csrc/cells.h: cells_load, cells_load_tile) and the results are compared as bit patterns:
+ * out = {observations per cell the tiles in place were built for (0: no tiles), cells, 32-bit words that differ,
+ * bytes the tiles occupy}. */
+LSQR_API int lsqr_scan_tiles_check(lsqr_ctx *ctx, uint64_t out[4]);
 
 /* Work of the two-level scan for the CURRENT batch of hypotheses over the indexed upload: runs level 1 (the
  * cell-box test) alone.  out[0..7] = {surviving (hypothesis, cell) pairs of ALL hypotheses, (64-hypothesis group,

@@ -185,6 +185,7 @@ SIGNATURES = {
     "lsqr_dedup_destroy": (None, [C.c_void_p]),
     "lsqr_set_option": (C.c_int, [_ctx, C.c_char_p, C.c_int]),
     "lsqr_index_info": (C.c_int, [_ctx, _u64p]),
+    "lsqr_scan_tiles_check": (C.c_int, [_ctx, _u64p]),
     "lsqr_scan_workload": (C.c_int, [_ctx, C.c_void_p, _u64p]),
     "lsqr_scan_work": (C.c_int, [_ctx, _u64p]),
     "lsqr_scan_pairs_counted": (C.c_int, [_ctx, _u64p]),

@@ -937,6 +937,13 @@ class Context:
         return {"built": bool(out[0]), "observations": int(out[1]), "cells": int(out[2]),
                 "cell_points": int(out[3])}
 
+    def scan_tiles_check(self):
+        """the index's fp32 tiles against the sorted copy, every cell opened both ways on the device
+        (lsqr_scan_tiles_check) -> dict(cell_points (0: no tiles), cells, words_differing, bytes)"""
+        out = (C.c_uint64 * 4)()
+        self._chk(self._lib.lsqr_scan_tiles_check(self._h, out))
+        return {"cell_points": int(out[0]), "cells": int(out[1]), "words_differing": int(out[2]), "bytes": int(out[3])}
+
     def scan_workload(self, want_bounds=False):
         """level 1 of the two-level scan alone over the current batch (lsqr_scan_workload) ->
         dict(pairs, level1_evaluations, cells, cell_points[, bounds])"""

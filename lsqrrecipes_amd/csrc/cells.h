@@ -1379,6 +1379,144 @@ __device__ __forceinline__ void cells_load(const double *__restrict__ sorted, co
   }
 }
 
+// ---- fp32 tiles of the index (option "scan_tiles") ------------------------------------------------------------
+// What cells_load leaves in xs depends on the index alone -- the records of the cell, their order, the cell's centre --
+// and not on the scan, so it is computed once per index (k_build_tiles, one wave per cell, cells_load itself: the tile
+// holds bit for bit what a wave of the scan would have computed, the NaN rows past the end included) and the scans
+// read it back with cells_load_tile: per lane PP to 3 PP loads of 16 or 8 bytes, one contiguous span per instruction,
+// against 2 D PP strided 8-byte loads, as many fp64 subtractions and conversions, and the guards.
+// Only the components the cell model uses are kept: its D coordinates, then q where it declares XQ.  Layout with NC
+// components, in units of 64 lanes x 8 bytes = 512 bytes (one v2f per lane: .x record p * 128 + lane of the cell, .y
+// record p * 128 + 64 + lane, as in xs): cell c starts at unit c PP NC, its packed pair p at p NC further on; there
+//   NC odd  (3-D plane and line, circle)  [component k][lane] {ck.x, ck.y}: an 8-byte load per component
+//   NC even (2-D, sphere)                 [k / 2][lane] {ck.x, ck.y, ck+1.x, ck+1.y}: a 16-byte load per two components
+// 12 bytes a record for the plane and the line in 3-D, 16 for the sphere, 8 in 2-D (12 for the circle).  (For NC = 3
+// the per-component form is the simplest and needs no register tuple wider than a packed pair: the 3-D plane's default
+// kernel stays at 80 registers, 6 waves and no scratch with it.  The mixed form -- 16 bytes for two components, 8 for
+// the third, 2 PP loads instead of 3 PP -- was built first and had that kernel in scratch; it was not built again
+// after the loads got their scalar base.)
+template <class CM>
+constexpr int tile_comps() {
+  if constexpr (requires { CM::XQ; }) return CM::M::ND + 1;
+  return CM::M::ND;
+}
+template <class CM>
+constexpr bool tile_paired() {
+  return tile_comps<CM>() % 2 == 0;
+}
+template <class CM>
+constexpr size_t tile_cell_floats(int pp) {
+  return (size_t)128 * pp * tile_comps<CM>();
+}
+// where component k of the tile sits in xs: the D coordinates in front, q (xs[.][3]) behind them
+template <class CM>
+constexpr int tile_slot(int k) {
+  return k < CM::M::ND ? k : 3;
+}
+typedef float v4f __attribute__((ext_vector_type(4)));
+
+// xs of cell `cell` -> its tile (k_build_tiles)
+template <class CM, int PP>
+__device__ __forceinline__ void cells_store_tile(float *__restrict__ tiles, const uint32_t cell, const int lane,
+                                                 const v2f (&xs)[PP][4]) {
+  constexpr int NC = tile_comps<CM>();
+  static_assert(NC >= 2 && NC <= 4);
+  float *const base = tiles + (size_t)cell * tile_cell_floats<CM>(PP);
+#pragma unroll
+  for (int p = 0; p < PP; p++) {
+#pragma unroll
+    for (int k = 0; k < NC; k += tile_paired<CM>() ? 2 : 1) {
+      float *const t = base + (p * NC + k) * 128;
+      const v2f a = xs[p][tile_slot<CM>(k)];
+      if constexpr (tile_paired<CM>()) {
+        const v2f b = xs[p][tile_slot<CM>(k + 1)];
+        *(v4f *)(t + 4 * lane) = v4f{a.x, a.y, b.x, b.y};
+      } else {
+        *(v2f *)(t + 2 * lane) = a;
+      }
+    }
+  }
+}
+
+// the tile of cell `cell` -> xs, as cells_load leaves it (the components the model does not use are 0 there too).
+// The cell's tile has a scalar base and the lane a 32-bit byte offset (as the mask row of pairs_cell_packed: written
+// plainly, a 64-bit address per lane is hoisted across the cell loop -- and spilled), and the loads are global ones by
+// their type: a pointer made from an integer is a flat one, which has no scalar base.
+template <class CM, int PP>
+__device__ __forceinline__ void cells_load_tile(const float *__restrict__ tiles, const uint32_t cell, const int lane,
+                                                v2f (&xs)[PP][4]) {
+  constexpr int NC = tile_comps<CM>();
+  static_assert(NC >= 2 && NC <= 4);
+  typedef const __attribute__((address_space(1))) char *gptr;
+  const unsigned long long ra = (unsigned long long)tiles + (unsigned long long)cell * (tile_cell_floats<CM>(PP) * 4);
+  const gptr base = (gptr)((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(ra >> 32)) << 32 |
+                           (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)ra));
+  // (the lane's offset is made here, once per cell opened, and out of the compiler's sight: written as lane * 8 it is
+  // merged with the 64-bit lane offsets the kernel already keeps, held across the cell loop and spilled, and the loads
+  // take a 64-bit address per lane instead of the scalar base)
+  uint32_t off;
+  asm volatile("v_lshlrev_b32 %0, %1, %2" : "=v"(off) : "n"(tile_paired<CM>() ? 4 : 3), "v"(lane));
+#pragma unroll
+  for (int p = 0; p < PP; p++) {
+#pragma unroll
+    for (int k = 0; k < 4; k++) xs[p][k] = v2f{0.0f, 0.0f};
+#pragma unroll
+    for (int k = 0; k < NC; k += tile_paired<CM>() ? 2 : 1) {
+      const gptr t = base + (p * NC + k) * 512 + off;
+      if constexpr (tile_paired<CM>()) {
+        const v4f a = *(const __attribute__((address_space(1))) v4f *)t;
+        xs[p][tile_slot<CM>(k)] = v2f{a.x, a.y};
+        xs[p][tile_slot<CM>(k + 1)] = v2f{a.z, a.w};
+      } else {
+        xs[p][tile_slot<CM>(k)] = *(const __attribute__((address_space(1))) v2f *)t;
+      }
+    }
+  }
+}
+
+// The builder: one wave per cell, after whatever fixed the final order of the sorted copy (k_gather_boxes, the
+// plane's k_cell_sort).  The centre is the scans': (double)box.c[d].
+template <class CM, int PP>
+__global__ __launch_bounds__(256) void k_build_tiles(const double *__restrict__ sorted, size_t ns,
+                                                     const CellBox *__restrict__ boxes, uint32_t ncells,
+                                                     float *__restrict__ tiles) {
+  const int lane = threadIdx.x & 63;
+  const uint32_t cell = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (cell >= ncells) return;
+  const CellBox bx = boxes[cell];
+  double ctr[3];
+#pragma unroll
+  for (int d = 0; d < 3; d++) ctr[d] = (double)bx.c[d];
+  v2f xs[PP][4];
+  cells_load<CM, PP>(sorted, ns, (size_t)cell, lane, ctr, xs);
+  cells_store_tile<CM, PP>(tiles, cell, lane, xs);
+}
+// Debug (lsqr_scan_tiles_check): *bad += the 32-bit words in which cells_load_tile and cells_load differ, all four
+// slots of xs compared as bit patterns
+template <class CM, int PP>
+__global__ __launch_bounds__(256) void k_check_tiles(const double *__restrict__ sorted, size_t ns,
+                                                     const CellBox *__restrict__ boxes, uint32_t ncells,
+                                                     const float *__restrict__ tiles, unsigned long long *bad) {
+  const int lane = threadIdx.x & 63;
+  const uint32_t cell = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (cell >= ncells) return;
+  const CellBox bx = boxes[cell];
+  double ctr[3];
+#pragma unroll
+  for (int d = 0; d < 3; d++) ctr[d] = (double)bx.c[d];
+  v2f xa[PP][4], xb[PP][4];
+  cells_load<CM, PP>(sorted, ns, (size_t)cell, lane, ctr, xa);
+  cells_load_tile<CM, PP>(tiles, cell, lane, xb);
+  uint32_t n = 0;
+#pragma unroll
+  for (int p = 0; p < PP; p++)
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+      n += (__builtin_bit_cast(uint32_t, xa[p][k].x) != __builtin_bit_cast(uint32_t, xb[p][k].x)) +
+           (__builtin_bit_cast(uint32_t, xa[p][k].y) != __builtin_bit_cast(uint32_t, xb[p][k].y));
+  if (n) atomicAdd(bad, (unsigned long long)n);
+}
+
 // ---- the scan ----------------------------------------------------------------------------------------
 // A cell is 128*PP consecutive records of the sorted copy (PP packed pairs per lane); a wave tile is
 // CPT cells whose observations stay in registers for the whole hypothesis loop.  Tiles are handed
@@ -1386,7 +1524,10 @@ __device__ __forceinline__ void cells_load(const double *__restrict__ sorted, co
 // assignment leaves a long tail); the next 64 hypotheses' parameters are prefetched while the
 // current 64 are processed.  Votes of the 64 hypotheses of a group are collected in one VGPR
 // (lane b = hypothesis h0 + b, v_readlane / v_writelane) and flushed with one LDS atomic per group.
-template <class CM, int PP, int CPT, int BS, bool LDSB = false>
+// TILES: empty, or `const float *`: the kernel then takes the index's fp32 tiles as its last argument and opens a cell
+// with cells_load_tile (option "scan_tiles").  With the empty pack the kernel is, argument for argument and instruction
+// for instruction, the one without tiles.
+template <class CM, int PP, int CPT, int BS, bool LDSB = false, class... TILES>
 // CM::MIN_WAVES (default tile shape only): the register budget that buys the occupancy measured best -- plane
 // 80 VGPRs = 6 waves per SIMD (98 VGPRs / 4 waves without the hint: 1.44 -> 1.31 ms; 7 waves spill: 1.40 ms)
 __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(CPT == 1 ? (PP >= 8 ? 4 : CM::MIN_WAVES) : 1, 8))) void k_scan_cells(const double *__restrict__ sorted, size_t ns,
@@ -1397,7 +1538,9 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(CPT == 1 ? (
                                                     ModelConsts mc, CellConsts cc,
                                                     uint32_t *__restrict__ votes,
                                                     uint32_t *__restrict__ next_tile, uint32_t grab,
-                                                    uint32_t hsplit, const uint32_t *__restrict__ h_dev) {
+                                                    uint32_t hsplit, const uint32_t *__restrict__ h_dev,
+                                                    TILES... tiles) {
+  static_assert(sizeof...(TILES) <= 1);
   typedef typename CM::M M;
   constexpr int NB = CM::NB;
   // the number of hypotheses may be decided on the device (bounded scan: the batch is a compacted selection);
@@ -1464,7 +1607,10 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(CPT == 1 ? (
       }
 #pragma unroll
       for (int d = 0; d < 3; d++) ctr[q][d] = (double)bx[q].c[d];
-      cells_load<CM, PP>(sorted, ns, (size_t)cell, lane, ctr[q], xs[q]);
+      if constexpr (sizeof...(TILES) != 0)  // (CPT == 1: cell < ncells)
+        cells_load_tile<CM, PP>(tiles..., cell, lane, xs[q]);
+      else
+        cells_load<CM, PP>(sorted, ns, (size_t)cell, lane, ctr[q], xs[q]);
     }
     float4 nxt[NR4];
     {
@@ -2258,15 +2404,17 @@ __device__ __forceinline__ void pairs_cell_packed(const PairsWave &w, const uint
 // instruction streams.
 // ambc: the context's counters of ambiguous pairs and band observations (cells_survivors: s_amb), kAmbSlots pairs of
 // words: a workgroup adds its two LDS counters to pair blockIdx.x % kAmbSlots when it ends.
-template <class CM, int PP, int BS, bool LDSB, PairsForm F>
+// TILES: as for k_scan_cells -- empty, or `const float *` for the index's fp32 tiles as the last argument.
+template <class CM, int PP, int BS, bool LDSB, PairsForm F, class... TILES>
 __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(PP >= 8 ? 4 : CM::MIN_WAVES, 8))) void k_scan_pairs(
     const double *__restrict__ sorted, size_t ns, const CellBox *__restrict__ boxes, uint32_t ncells,
     const double *__restrict__ sp, const float *__restrict__ rows, const float *__restrict__ spf, uint32_t H,
     ModelConsts mc, CellConsts cc, uint32_t *__restrict__ vpart, uint32_t vstride,
     const uint32_t *__restrict__ h_dev, const uint8_t *__restrict__ cnt, uint32_t gstride, const uint32_t *__restrict__ cost,
     const uint32_t *__restrict__ csum, uint32_t nchunks, uint32_t h_off, const float4 *__restrict__ hyps,
-    unsigned long long *__restrict__ ambc) {
+    unsigned long long *__restrict__ ambc, TILES... tiles) {
   static_assert(pairs_form_exists<CM, LDSB, F>());
+  static_assert(sizeof...(TILES) <= 1);
   constexpr bool PREP = prepared(F), LEAN = lean(F), PACK = packed(F);
   typedef typename CM::M M;
   constexpr int NB = CM::NB;
@@ -2458,7 +2606,10 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(PP >= 8 ? 4 
       }
     }
     v2f xs[PP][4];
-    cells_load<CM, PP>(sorted, ns, (size_t)cell, lane, ctr, xs);
+    if constexpr (sizeof...(TILES) != 0)
+      cells_load_tile<CM, PP>(tiles..., cell, lane, xs);
+    else
+      cells_load<CM, PP>(sorted, ns, (size_t)cell, lane, ctr, xs);
     if constexpr (PACK) {
       pairs_cell_packed<CM, PP, LDSB, recheck(F) ? Exact::Band : Exact::Cell>(w, cell, bx, ctr, xs, jlo, jhi);
       cell++;

@@ -215,6 +215,13 @@ struct lsqr_ctx {
   DevBuf<float> d_cellT;
   bool axis_valid = false;
   DevBuf<CellSlab> d_slab;        // per-cell oriented slab (axis.h: k_cell_slabs), built with d_axis
+  // fp32 tiles of the index (cells.h: k_build_tiles): what cells_load makes of every cell, built once behind the index
+  DevBuf<float> d_tiles;
+  uint32_t tiles_pts = 0;    // cell size the tiles in place were built for (0: none; dropped with the index)
+  bool tiles_nomem = false;  // no room for the tiles on this upload: the scans keep reading the sorted copy
+  // option "scan_tiles" (1: build and read the tiles).  Kept here and not in options.h: it keeps the index and is
+  // handed on to the lanes like a row of the table (apply_option)
+  bool use_tiles = true;
 
   // ---- two-level scan and its counted forms ----
   DevBuf<uint32_t> d_ub;  // per-hypothesis vote bound of the two-level scan's first level (k_cells_bounds)
@@ -743,6 +750,8 @@ void drop_index(lsqr_ctx *c) {
   c->index_valid = false;
   c->index_kd_levels = 0;
   c->axis_valid = false;
+  c->tiles_pts = 0;
+  c->tiles_nomem = false;
   c->last_count.valid = false;
 }
 
@@ -929,6 +938,27 @@ int build_index(lsqr_ctx *c, uint32_t cell_pts) {
   return LSQR_OK;
 }
 
+// ---- fp32 tiles of the index (cells.h: k_build_tiles; option "scan_tiles") ----
+// Built (build_tiles, below) on the stream right behind an index build (scan_index_ready), or in front of the first
+// scan that finds the option on and no tiles for the index in place; dropped with the index.  An accelerator like the index itself: without room for
+// them the scans keep opening their cells from the sorted copy.
+// the tiles a scan over cells of `cell_pts` records reads, or nullptr: it opens its cells with cells_load
+inline const float *scan_tiles(const lsqr_ctx *c, uint32_t cell_pts) {
+  return c->use_tiles && c->tiles_pts == cell_pts && c->cell_pts == cell_pts ? c->d_tiles.get() : nullptr;
+}
+// Which instantiations are built with the tile reader: the forms a default path reaches -- the packed forms of the
+// prepared models, General of the others, k_scan_cells, each with the model's default broadcast mode ("scan_block" 256 /
+// 257 and the forms behind "scan_pack", "scan_lean", "scan_prepared" 0 are A/B knobs) -- but for two kernels of the 3-D
+// plane over 512-record cells that sit at their 80 registers (6 waves) and go to scratch with it, 12 bytes a lane:
+// k_scan_cells and the packed form without the re-check ("scan_recheck" 0).  They keep cells_load.
+template <class CM, int PP>
+constexpr bool kTileSpills = std::is_same<CM, PlaneCell<3>>::value && PP == 4;
+template <class CM, int PP, int CPT, bool LDSB>
+constexpr bool kTileScanCells = CPT == 1 && LDSB == (CM::LDS_BROADCAST != 0) && !kTileSpills<CM, PP>;
+template <class CM, int PP, bool LDSB, bool LDSB_DEFAULT, PairsForm F>
+constexpr bool kTileScanPairs = (cell_prepared<CM>() ? packed(F) : F == PairsForm::General) && LDSB == LDSB_DEFAULT &&
+                                !(kTileSpills<CM, PP> && F == PairsForm::Packed);
+
 // a batch of hypotheses handed to the two-level scan: the context's current batch, or a compacted selection of it
 struct ScanBatch {
   const double *sp;       // fp64 scan parameters, M::SP per hypothesis
@@ -949,14 +979,14 @@ int launch_scan_cells(lsqr_ctx *c, const ScanBatch &b) {
   constexpr int wpb = BS / 64;  // waves per workgroup
   if (!c->d_queues) HIPCHK(c, c->d_queues.alloc(kQueues * kQueuePitch));
   uint32_t *d_next = c->d_queues;
-  for (size_t h0 = 0; h0 < b.H; h0 += kScanChunk) {
+  // kern: the kernel, `tiles`: nothing, or the index's tiles for the form that reads them
+  auto chunk = [&](auto kern, const size_t h0, auto... tiles) -> int {
     uint32_t hc = (uint32_t)std::min<size_t>(kScanChunk, b.H - h0);
     size_t lds = (size_t)((hc + 3) & ~3u) * sizeof(uint32_t) + (LDSB ? (size_t)wpb * 2048 : 0);
     int per_cu = (int)std::min<size_t>(32 / wpb, (160 * 1024) / std::max<size_t>(lds, 1));
     {  // persistent waves pulling tiles from the queues: launch exactly what is resident at once
       int occ = 0;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_scan_cells<CM, PP, CPT, BS, LDSB>, BS, lds) ==
-              hipSuccess && occ >= 1)
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, BS, lds) == hipSuccess && occ >= 1)
         per_cu = std::min(per_cu, occ);
       else
         (void)hipGetLastError();
@@ -973,12 +1003,24 @@ int launch_scan_cells(lsqr_ctx *c, const ScanBatch &b) {
     const uint32_t grab = (uint32_t)std::min<size_t>(8, std::max<size_t>(1, units / (32 * waves)));
     ProfScope ps(c, KID_SCAN);
     HIPCHK(c, hipMemsetAsync(d_next, 0, kQueues * kQueuePitch * sizeof(uint32_t), c->stream));
-    hipLaunchKernelGGL((k_scan_cells<CM, PP, CPT, BS, LDSB>), dim3((unsigned)blocks), dim3(BS), lds,
-                       c->stream, c->d_sorted, c->n_sorted, c->d_boxes, c->n_cells,
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(BS), lds,
+                       c->stream, c->d_sorted.get(), c->n_sorted, c->d_boxes.get(), c->n_cells,
                        b.sp + h0 * M::SP,
                        CM::ROW_F32 ? b.spf + h0 * M::SPF : (const float *)(b.sp + h0 * M::SP),
-                       b.spf + h0 * M::SPF, hc, c->mc, cc, b.votes + h0, d_next, grab, hsplit, b.h_dev);
+                       b.spf + h0 * M::SPF, hc, c->mc, cc, b.votes + h0, d_next, grab, hsplit, b.h_dev, tiles...);
     HIPCHK(c, hipGetLastError());
+    return LSQR_OK;
+  };
+  [[maybe_unused]] const float *tiles = scan_tiles(c, (uint32_t)(128 * PP));
+  for (size_t h0 = 0; h0 < b.H; h0 += kScanChunk) {
+    int st;
+    if constexpr (kTileScanCells<CM, PP, CPT, LDSB>) {
+      st = tiles ? chunk(k_scan_cells<CM, PP, CPT, BS, LDSB, const float *>, h0, tiles)
+                 : chunk(k_scan_cells<CM, PP, CPT, BS, LDSB>, h0);
+    } else {
+      st = chunk(k_scan_cells<CM, PP, CPT, BS, LDSB>, h0);
+    }
+    if (st != LSQR_OK) return st;
   }
   return LSQR_OK;
 }
@@ -1004,6 +1046,27 @@ int with_pp(uint32_t cell_pts, F &&f) {
   }
   if (cell_pts == 512) return f(std::integral_constant<int, 4>{});
   return f(std::integral_constant<int, 2>{});
+}
+
+// the index's fp32 tiles (see scan_tiles above)
+template <class CM>
+int build_tiles(lsqr_ctx *c) {
+  if (!c->use_tiles || !c->index_valid || c->n_cells == 0 || c->tiles_pts == c->cell_pts || c->tiles_nomem) return LSQR_OK;
+  const size_t need = (size_t)c->n_cells * tile_cell_floats<CM>((int)(c->cell_pts / 128));
+  if (need > c->d_tiles.cap() && c->d_tiles.alloc(need) != hipSuccess) {
+    (void)hipGetLastError();
+    c->tiles_nomem = true;
+    return LSQR_OK;
+  }
+  // (not timed under KID_INDEX: that id counts index builds, one launch scope each)
+  const int st = with_pp<CM>(c->cell_pts, [&](auto pp) -> int {
+    hipLaunchKernelGGL((k_build_tiles<CM, decltype(pp)::value>), dim3((c->n_cells + 3) / 4), dim3(256), 0, c->stream,
+                       c->d_sorted.get(), c->n_sorted, c->d_boxes.get(), c->n_cells, c->d_tiles.get());
+    HIPCHK(c, hipGetLastError());
+    return LSQR_OK;
+  });
+  if (st == LSQR_OK) c->tiles_pts = c->cell_pts;
+  return st;
 }
 
 // level 1 of the two-level scan alone over the current batch: d_ub[h] = vote bound, d_counter[CNT_PAIRS] = surviving pairs
@@ -1119,9 +1182,11 @@ int run_scan_pairs(lsqr_ctx *c, const ScanBatch &b0) {
   if ((st = ensure(c, c->d_paircost, (size_t)c->n_cells + nchunks)) != LSQR_OK) return st;
   uint32_t *d_cost = c->d_paircost, *d_csum = c->d_paircost + c->n_cells;
   const float *rows = CM::ROW_F32 ? b.spf : (const float *)b.sp;
-  bool ldsb_default = CM::LDS_BROADCAST;
-  if constexpr (requires { CM::LDS_BROADCAST_PAIRS; }) ldsb_default = CM::LDS_BROADCAST_PAIRS;
-  const bool ldsb = c->opt.block == 257 || (c->opt.block == 0 && ldsb_default);
+  constexpr bool kLdsbDefault = [] {
+    if constexpr (requires { CM::LDS_BROADCAST_PAIRS; }) return CM::LDS_BROADCAST_PAIRS != 0;
+    else return CM::LDS_BROADCAST != 0;
+  }();
+  const bool ldsb = c->opt.block == 257 || (c->opt.block == 0 && kLdsbDefault);
   // the form, once: the counting pass, k_tile_costs, the LDS size and k_scan_pairs below all read it
   const PairsForm form = pairs_form<CM>(ldsb, c->opt.prepared, c->opt.lean, c->opt.pack, c->opt.recheck);
   // the hypothesis-only part of level 1 once per batch instead of once per (cell, group): both kernels below read it
@@ -1174,27 +1239,34 @@ int run_scan_pairs(lsqr_ctx *c, const ScanBatch &b0) {
     c->amb_reset = false;
     c->amb_counted = cell_prepared<CM>() && M::ND == 3;  // (k_scan_pairs counts for the 3-D plane)
     HIPCHK(c, hipGetLastError());
-    const auto kern = k_scan_pairs<CM, PP, BS, LDSB, F>;
-    int per_cu = (int)std::min<size_t>(32 / wpb, (160 * 1024) / std::max<size_t>(lds, 1)), occ = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, BS, lds) == hipSuccess && occ >= 1)
-      per_cu = std::min(per_cu, occ);
-    else
-      (void)hipGetLastError();
-    if (per_cu < 1) per_cu = 1;
-    if (c->opt.pairs_waves > 0) per_cu = std::min(per_cu, c->opt.pairs_waves);
-    const unsigned blocks = (unsigned)std::min<size_t>(((size_t)c->n_cells + wpb - 1) / wpb, (size_t)256 * per_cu);
-    int st2 = ensure(c, c->d_vpart, (size_t)blocks * Hc);
-    if (st2 != LSQR_OK) return st2;
-    ProfScope ps(c, KID_SCAN);
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(BS), lds, c->stream, c->d_sorted, c->n_sorted, c->d_boxes, c->n_cells,
-                       b.sp, rows, b.spf, Hc, c->mc, cc, c->d_vpart, Hc, b.h_dev, (const uint8_t *)d_cnt, gstride,
-                       (const uint32_t *)d_cost, (const uint32_t *)d_csum, nchunks, b.h_off, hyps,
-                       c->d_ambcnt.get());
-    HIPCHK(c, hipGetLastError());
-    hipLaunchKernelGGL(k_votes_reduce, dim3((Hc + 63) / 64, 48), dim3(256), 0, c->stream,
-                       (const uint32_t *)c->d_vpart, Hc, (uint32_t)blocks, Hc, b.h_dev, b.votes, b.h_off);
-    HIPCHK(c, hipGetLastError());
-    return LSQR_OK;
+    // kern: the kernel, `tiles`: nothing, or the index's tiles for the form that reads them
+    auto scan = [&](auto kern, auto... tiles) -> int {
+      int per_cu = (int)std::min<size_t>(32 / wpb, (160 * 1024) / std::max<size_t>(lds, 1)), occ = 0;
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, BS, lds) == hipSuccess && occ >= 1)
+        per_cu = std::min(per_cu, occ);
+      else
+        (void)hipGetLastError();
+      if (per_cu < 1) per_cu = 1;
+      if (c->opt.pairs_waves > 0) per_cu = std::min(per_cu, c->opt.pairs_waves);
+      const unsigned blocks = (unsigned)std::min<size_t>(((size_t)c->n_cells + wpb - 1) / wpb, (size_t)256 * per_cu);
+      int st2 = ensure(c, c->d_vpart, (size_t)blocks * Hc);
+      if (st2 != LSQR_OK) return st2;
+      ProfScope ps(c, KID_SCAN);
+      hipLaunchKernelGGL(kern, dim3(blocks), dim3(BS), lds, c->stream, c->d_sorted.get(), c->n_sorted, c->d_boxes.get(),
+                         c->n_cells, b.sp, rows, b.spf, Hc, c->mc, cc, c->d_vpart.get(), Hc, b.h_dev, (const uint8_t *)d_cnt,
+                         gstride, (const uint32_t *)d_cost, (const uint32_t *)d_csum, nchunks, b.h_off, hyps,
+                         c->d_ambcnt.get(), tiles...);
+      HIPCHK(c, hipGetLastError());
+      hipLaunchKernelGGL(k_votes_reduce, dim3((Hc + 63) / 64, 48), dim3(256), 0, c->stream,
+                         (const uint32_t *)c->d_vpart, Hc, (uint32_t)blocks, Hc, b.h_dev, b.votes, b.h_off);
+      HIPCHK(c, hipGetLastError());
+      return LSQR_OK;
+    };
+    if constexpr (kTileScanPairs<CM, PP, LDSB, kLdsbDefault, F>) {
+      if (const float *tiles = scan_tiles(c, (uint32_t)(128 * PP)))
+        return scan(k_scan_pairs<CM, PP, BS, LDSB, F, const float *>, tiles);
+    }
+    return scan(k_scan_pairs<CM, PP, BS, LDSB, F>);
   });
 }
 
@@ -1949,6 +2021,9 @@ bool scan_index_ready(lsqr_ctx *c, uint32_t *cell_pts_out) {
       return false;
     }
   }
+  // the fp32 tiles of the index in place (nothing to do when they are there; a failed launch leaves the scans on
+  // the sorted copy)
+  if (build_tiles<CM>(c) != LSQR_OK) (void)hipGetLastError();
   return true;
 }
 // the plane's full count with the batch in key order (cells.h: k_plane_order): similar planes share a 64-group
@@ -4783,6 +4858,7 @@ static int lane_get(lsqr_ctx *c, int li, lsqr_ctx **out) {
     HIPCHK(c, hipStreamSynchronize(l->stream));
     int st = lsqr_set_model(l, &c->cfg);
     l->opt = c->opt;  // (an option that drops the index needs no more here: lsqr_attach drops it)
+    l->use_tiles = c->use_tiles;
     if (st == LSQR_OK) st = lsqr_attach(l, c->d_data, c->n, c->stride * sizeof(double));
     if (st != LSQR_OK) return fail(c, st, "lane %d: %s", li, lsqr_last_error(l));
     HIPCHK(c, sync_stream(c));  // an upload still in flight on the parent's stream
@@ -5543,6 +5619,14 @@ int lsqr_multi_ransac(lsqr_multi *m, double p, uint64_t seed, double *params_out
 
 // options.h holds the names, rules and defaults; what needs the context is here
 static int apply_option(lsqr_ctx *c, const char *name, int value) {
+  // "scan_tiles" is the context's own (lsqr_ctx::use_tiles): 0 or 1, keeps the index; tiles in place stay and are
+  // read again when the option comes back to 1
+  if (!strcmp(name, "scan_tiles")) {
+    if (value < 0 || value > 1)
+      return fail(c, LSQR_ERR_INVALID, "scan_tiles does not accept %d (0 or 1: the scans open a cell from the index's fp32 tiles)", value);
+    c->use_tiles = value != 0;
+    return LSQR_OK;
+  }
   bool drops_index = false;
   char why[256];
   const int st = options_set(c->opt, name, value, &drops_index, why, sizeof why);
@@ -5690,6 +5774,39 @@ int lsqr_index_info(const lsqr_ctx *c, uint64_t out[4]) {
   out[1] = c->n_sorted;
   out[2] = c->n_cells;
   out[3] = c->cell_pts;
+  return LSQR_OK;
+}
+
+int lsqr_scan_tiles_check(lsqr_ctx *c, uint64_t out[4]) {
+  int st = need_ready(c, true);
+  if (st != LSQR_OK) return st;
+  if (!out) return fail(c, LSQR_ERR_INVALID, "null argument");
+  out[0] = c->index_valid ? c->tiles_pts : 0;
+  out[1] = c->n_cells;
+  out[2] = out[3] = 0;
+  if (!out[0] || c->n_cells == 0) return LSQR_OK;
+  unsigned long long *d_bad = c->d_counter + CNT_SUM;
+  HIPCHK(c, hipMemsetAsync(d_bad, 0, sizeof(unsigned long long), c->stream));
+  st = dispatch(c->cfg, [&](auto tag) -> int {
+    typedef typename decltype(tag)::type M;
+    if constexpr (requires { typename CellOf<M>::type; }) {
+      typedef typename CellOf<M>::type CM;
+      out[3] = (uint64_t)c->n_cells * tile_cell_floats<CM>((int)(c->tiles_pts / 128)) * sizeof(float);
+      return with_pp<CM>(c->tiles_pts, [&](auto pp) -> int {
+        hipLaunchKernelGGL((k_check_tiles<CM, decltype(pp)::value>), dim3((c->n_cells + 3) / 4), dim3(256), 0, c->stream,
+                           c->d_sorted.get(), c->n_sorted, c->d_boxes.get(), c->n_cells, c->d_tiles.get(), d_bad);
+        HIPCHK(c, hipGetLastError());
+        return LSQR_OK;
+      });
+    } else {
+      return fail(c, LSQR_ERR_INVALID, "model has no two-level scan");
+    }
+  });
+  if (st != LSQR_OK) return st;
+  unsigned long long *pin = c->h_pin->scratch_u64;
+  HIPCHK(c, hipMemcpyAsync(pin, d_bad, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, sync_stream(c));
+  out[2] = pin[0];
   return LSQR_OK;
 }
 

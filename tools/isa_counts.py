@@ -22,7 +22,15 @@ CSRC = os.path.join(ROOT, "lsqrrecipes_amd", "csrc")
 # (key, kernel, its template arguments as c++filt prints them): every key selects exactly one instantiation.  The forms
 # of the counted scan are written by name (cells.h: PairsForm, BoundsForm); PP = cell size / 128, then BS and LDSB.
 PLANE = "lsqr::PlaneCell<3>"
-KERNELS = [("k_scan_pairs_plane", "k_scan_pairs", [PLANE, "4", "256", "true", "PairsForm::PackedRecheck"]),  # what runs
+# A trailing "float const*" selects the instantiation that opens a cell from the index's fp32 tiles (scan_tiles=1); the
+# key without it is the same form on cells_load (scan_tiles=0).  "cell_open" of a k_scan_pairs key counts the cell
+# loop's own instructions (share arithmetic + cell open, the loops inside it left out): the difference between a key
+# and its _tiles twin is what opening a cell from the sorted copy costs.
+TILES = "float const*"
+KERNELS = [("k_scan_pairs_plane", "k_scan_pairs", [PLANE, "4", "256", "true", "PairsForm::PackedRecheck"]),  # scan_tiles=0
+           ("k_scan_pairs_plane_tiles", "k_scan_pairs", [PLANE, "4", "256", "true", "PairsForm::PackedRecheck", TILES]),  # what runs
+           ("k_scan_pairs_sphere_tiles", "k_scan_pairs", ["lsqr::SphereCell<3>", "4", "256", "true", "PairsForm::General", TILES]),
+           ("k_scan_pairs_line_tiles", "k_scan_pairs", ["lsqr::LineCell<3>", "2", "256", "true", "PairsForm::General", TILES]),
            ("k_scan_pairs_plane_whole_cell", "k_scan_pairs", [PLANE, "4", "256", "true", "PairsForm::Packed"]),  # scan_recheck=0
            ("k_scan_pairs_plane_groups", "k_scan_pairs", [PLANE, "4", "256", "true", "PairsForm::Lean"]),  # scan_pack=0
            ("k_scan_pairs_plane_general", "k_scan_pairs", [PLANE, "4", "256", "true", "PairsForm::Prepared"]),  # scan_lean=0
@@ -161,10 +169,18 @@ def main():
                          "valu_cmp": cnt["valu_cmp"], "mfma": cnt["mfma"], "salu": cnt["salu"], "smem": cnt["smem"],
                          "lds": cnt["lds"], "vmem": cnt["vmem"], "control": cnt["control"],
                          "vector_ops": dict(sorted(top.items(), key=lambda kv: -kv[1])[:14])})
+        # the cell loop of k_scan_pairs: the outermost loop with the most instructions of its own
+        cell_open = None
+        if kernel == "k_scan_pairs":
+            (hdr, _), cnt = max(((k, c) for k, c in loops.items() if k[1] == 1),
+                                key=lambda kc: sum(v for o, v in kc[1].items() if o.startswith("op:")))
+            cell_open = {"loop": hdr, "valu": cnt["valu_packed"] + cnt["valu_cmp"] + cnt["valu_other"],
+                         "vmem": cnt["vmem"], "salu": cnt["salu"], "v_cvt_f32_f64": cnt["op:v_cvt_f32_f64_e32"],
+                         "v_add_f64": cnt["op:v_add_f64"]}
         rows.sort(key=lambda r: (-r["depth"], -r["valu"]))
         # the loop with the most packed instructions = the packed fp32 filter's body (level 2 of the point models)
         l2 = max(rows, key=lambda r: r["valu_packed"]) if rows else None
-        res[key] = {"function": best[1][:120], "loops": rows,
+        res[key] = {"function": best[1][:120], "loops": rows, "cell_open": cell_open,
                     # counting pass: the loop with the most vector instructions (its header block "LBBn_m" and the
                     # blocks "BBn_m" inside it taken together) is the four-cells-at-a-time loop
                     "valu_per_cell": max(sum(r["valu"] for r in rows if r["loop"].lstrip("L") == n)

@@ -1,6 +1,6 @@
 # one bench step (lsqr_batch_fit) of a BASELINE workload on the bench's shapes and seed (for rocprofv3 --pmc passes):
 #   python3 tools/scan_once.py plane|sphere|line|us|dense|phantom [launches] [scan_bound: 0 = full count, 1 = early exit]
-#                              [NAME=VALUE ...]   (further lsqr_set_option settings, A/B passes: scan_prepared=0, scan_lean=0, scan_pack=0, scan_recheck=0, scan_slab=0)
+#                              [NAME=VALUE ...]   (further lsqr_set_option settings, A/B passes: scan_prepared=0, scan_lean=0, scan_pack=0, scan_recheck=0, scan_slab=0, scan_tiles=0)
 import sys
 sys.path.insert(0, '.')
 from lsqrrecipes_amd import _lib as L, synth
